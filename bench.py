@@ -70,7 +70,12 @@ def parse_args(argv=None):
     ap.add_argument("--force-collective", action="store_true",
                     help="N=1 only: initialise the process group and send the tiles through the gather anyway (exercises the RCCL call on one GPU)")
     ap.add_argument("--dump-frame", default=None, help="rank 0 writes the assembled u8 frame (H*W,3) to this .npy")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -191,6 +196,8 @@ def main():
         assert frame.shape == (s["width"] * s["height"], 3)
         if args.dump_frame:
             np.save(args.dump_frame, frame)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame)
         ms_step = elapsed * 1e3 / args.steps
         headline = args.config == "C2_cornell_box" and not (args.width or args.height or args.spp)
         out = {
@@ -244,6 +251,25 @@ def main():
         if world > 1:
             dist.barrier()          # rank 0 finishes its extra (untimed) work before any rank tears the group down
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6     # every file --dump-outputs writes, .npy headers included
+
+
+def dump_outputs(out_dir, frame_u8):
+    """What a caller of the timed path receives from its last step: the assembled (H*W,3) u8 frame, as float32 in frame.npy.
+    A bigger frame than fits in DUMP_MAX_BYTES is cut to a fixed, seeded sample of pixels, whose ids go to
+    frame_pixel_ids.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = frame_u8.astype(np.float32)
+    budget = DUMP_MAX_BYTES - 2 * 4096          # (two .npy headers)
+    if frame.nbytes > budget:
+        n = budget // (frame.itemsize * frame.shape[1] + 8)
+        ids = np.sort(np.random.default_rng(0).choice(frame.shape[0], size=n, replace=False))
+        frame = frame[ids]
+        np.save(os.path.join(out_dir, "frame_pixel_ids.npy"), ids.astype(np.float64))
+    np.save(os.path.join(out_dir, "frame.npy"), frame)
 
 
 def exclusive_pass(tr, keys, frames):

@@ -17,9 +17,13 @@
   scenes/uvmap.png          <- /root/reference/uvmap.png           (ImageTexture of conics.rs / earth.rs)
   scenes/teapot_mesh.npz    <- /root/reference/scenes/teapot.yml   (4 TriangleMeshes with vertex normals = tobj 1.0's
                                output for teapot.obj; 6 320 triangles)
+  tests/golden/conics.yml, suzanne.yml.xz, teapot.yml.xz, teapot.obj.xz <- the reference's scene files and teapot.obj,
+                               byte for byte (xz-compressed where large): what tests/test_yaml_io.py and
+                               tests/test_obj_loader.py read
 
 Run in the build container only (/root/reference does not exist on the GPU box)."""
 import json
+import lzma
 import os
 import shutil
 import sys
@@ -137,6 +141,16 @@ def main():
     with open(f"{ROOT}/tests/golden/reference_yaml_pins.json", "w") as f:
         json.dump(pins, f, indent=1)
     print(len(pins), "rotor pins")
+    scene_files()
+
+
+def scene_files():
+    shutil.copyfile(f"{REF}/scenes/conics.yml", f"{ROOT}/tests/golden/conics.yml")
+    for src, dst in (("scenes/suzanne.yml", "suzanne.yml.xz"), ("scenes/teapot.yml", "teapot.yml.xz"), ("teapot.obj", "teapot.obj.xz")):
+        with open(f"{REF}/{src}", "rb") as f:
+            data = f.read()
+        with open(f"{ROOT}/tests/golden/{dst}", "wb") as f:
+            f.write(lzma.compress(data, preset=9 | lzma.PRESET_EXTREME))
 
 
 if __name__ == "__main__":

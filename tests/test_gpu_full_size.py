@@ -173,6 +173,18 @@ def test_bench_rccl_collective_runs_on_one_gpu(tmp_path):
     assert np.array_equal(np.load(f1), np.load(f2))
 
 
+def test_bench_dump_outputs_is_the_frame_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the frame the timed loop assembled in its last step, as float32 (DIR/frame.npy), holds the same
+    values as --dump-frame's u8 frame of the same run; --steps is the number of timed steps the line reports."""
+    f, out = str(tmp_path / "f.npy"), tmp_path / "out"
+    d = _bench(SMALL + ["--steps", "3", "--dump-frame", f, "--dump-outputs", str(out)])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == ["frame.npy"]
+    got = np.load(out / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (128 * 96, 3)
+    assert np.array_equal(got, np.load(f).astype(np.float32)) and got.max() > 0
+
+
 def test_bench_line_carries_roofline_parity_and_one_shot():
     d = _bench(["--width", "96", "--height", "96", "--spp", "32", "--steps", "2", "--warmup", "1", "--parity-seconds", "5"])
     assert d["unit"] == "Mrays/s" and d["scaling"] == "strong" and d["vs_baseline"] is None

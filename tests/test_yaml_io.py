@@ -1,6 +1,8 @@
 """The reference's YAML wire format (serde_yaml + typetag): round trips, and the reference's own scene files
-when /root/reference is present (build container only; skipped on the GPU box)."""
+(kept byte for byte under tests/golden/, xz-compressed where large: scripts/make_fixtures.py)."""
+import lzma
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -10,7 +12,22 @@ from firework_amd import scenes
 from firework_amd.api import Renderer
 from firework_amd.yaml_io import load_scene, save_scene, scene_to_dict
 
-REF = "/root/reference"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def reference_scene(tmp_path, name):
+    """The reference's scenes/<name>, written out as <tmp_path>/scenes/<name>: the reference's own layout, in which a
+    scene file names its images relative to the directory one level up."""
+    dst = tmp_path / "scenes" / name
+    dst.parent.mkdir(parents=True, exist_ok=True)
+    src = os.path.join(GOLDEN, name)
+    if os.path.exists(src):
+        shutil.copyfile(src, dst)
+    else:
+        with lzma.open(src + ".xz") as f:
+            dst.write_bytes(f.read())
+    return str(dst)
 
 
 def _same_render(oracle, a, b):
@@ -41,23 +58,22 @@ def test_schema_spelling():
     assert [list(f)[0] for f in box["faces"]] == ["XY", "XY", "XZ", "XZ", "YZ", "YZ"]      # rect3d.rs:19-77
 
 
-@pytest.mark.skipif(not os.path.exists(f"{REF}/scenes/suzanne.yml"), reason="reference tree not present")
-def test_reads_reference_suzanne_yml_and_matches_our_builder():
-    ref = load_scene(f"{REF}/scenes/suzanne.yml")
+def test_reads_reference_suzanne_yml_and_matches_our_builder(tmp_path):
+    path = reference_scene(tmp_path, "suzanne.yml")
+    ref = load_scene(path)
     ours, _ = scenes.suzanne()
     dr, do = scene_to_dict(ref), scene_to_dict(ours)
     assert dr["materials"] == do["materials"] and dr["environment"] == do["environment"]
     for a, b in zip(dr["render_objects"], do["render_objects"]):
         assert a == b
     # and our writer reproduces the reference file's data exactly
-    with open(f"{REF}/scenes/suzanne.yml") as f:
+    with open(path) as f:
         raw = yaml.load(f, Loader=getattr(yaml, "CSafeLoader", yaml.SafeLoader))
     assert raw == do
 
 
-@pytest.mark.skipif(not os.path.exists(f"{REF}/scenes/teapot.yml"), reason="reference tree not present")
-def test_reads_reference_teapot_yml_with_vertex_normals(oracle):
-    sc = load_scene(f"{REF}/scenes/teapot.yml")
+def test_reads_reference_teapot_yml_with_vertex_normals(oracle, tmp_path):
+    sc = load_scene(reference_scene(tmp_path, "teapot.yml"))
     meshes = [ro.obj for ro in sc.render_objects if type(ro.obj).__name__ == "TriangleMesh"]
     assert len(meshes) == 4 and sum(m.num_tris() for m in meshes) == 6320
     assert all(m.normals is not None for m in meshes)
@@ -68,13 +84,14 @@ def test_reads_reference_teapot_yml_with_vertex_normals(oracle):
     assert np.isfinite(img.linear).all() and img.linear.max() > 0
 
 
-@pytest.mark.skipif(not os.path.exists(f"{REF}/scenes/conics.yml"), reason="reference tree not present")
-def test_reads_reference_conics_yml(oracle):
+def test_reads_reference_conics_yml(oracle, tmp_path):
     """Cone / Cylinder / Disk + an ImageTexture named relative to the reference's working directory."""
-    sc = load_scene(f"{REF}/scenes/conics.yml")
+    path = reference_scene(tmp_path, "conics.yml")
+    shutil.copyfile(os.path.join(ROOT, "scenes", "uvmap.png"), tmp_path / "uvmap.png")     # the reference's uvmap.png
+    sc = load_scene(path)
     kinds = [type(ro.obj).__name__ for ro in sc.render_objects]
     assert kinds == ["Cylinder", "Disk", "Cone", "Cylinder", "Cylinder", "Disk", "XZRect", "YZRect"]
-    with open(f"{REF}/scenes/conics.yml") as f:
+    with open(path) as f:
         raw = yaml.load(f, Loader=getattr(yaml, "CSafeLoader", yaml.SafeLoader))
     assert scene_to_dict(sc) == raw                      # writer reproduces the reference file's data
     # constructors reproduce the serialised angles: Cylinder::partial(.., 300.) and Disk::new
