@@ -1,7 +1,7 @@
 """ctypes mirror of include/firework_hip.h (the C ABI).  Field order and types must match the header."""
 import ctypes as C
 
-FW_ABI_VERSION = 7
+FW_ABI_VERSION = 8
 FW_INIT_NO_ARENA = 0xFFFFFFFFFFFFFFFF   # fw_init: no path arena (the first render sizes its own)
 FW_MAX_SEGMENTS = 11
 
@@ -27,6 +27,7 @@ FW_ENV_COLOR, FW_ENV_SKY, FW_ENV_HDR = range(3)
 FW_RNG_CTR, FW_RNG_LCG = 0, 1
 FW_FLAG_TIME_KERNELS = 1
 FW_FLAG_COUNT_DEPOSITS = 2
+FW_NO_HIT = 0xFFFFFFFF   # fw_hit.object of a miss
 
 f32, i32, u32, u64 = C.c_float, C.c_int32, C.c_uint32, C.c_uint64
 
@@ -101,6 +102,16 @@ class fw_stats(C.Structure):
             v = getattr(self, name)
             d[name] = list(v) if hasattr(v, "__len__") else v
         return d
+
+
+class fw_hit(C.Structure):
+    _fields_ = [("t", f32), ("point", fw_vec3), ("normal", fw_vec3), ("u", f32), ("v", f32),
+                ("material", u32), ("object", u32), ("prim", u32)]
+
+
+class fw_trace_params(C.Structure):
+    _fields_ = [("use_bvh", i32), ("flags", u32), ("seed", u64), ("key_base", u32), ("rays_per_batch", u32),
+                ("on_device", i32), ("stream", C.c_void_p)]
 
 
 def vec3(v):

@@ -73,6 +73,10 @@ def load(preload=False, device=None):
     lib.fw_selftest_bvh_build.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     lib.fw_init.restype = C.c_int
     lib.fw_init.argtypes = [C.c_int, C.c_uint64]
+    lib.fw_trace_rays.restype = C.c_int
+    lib.fw_trace_rays.argtypes = [C.c_void_p, C.POINTER(A.fw_trace_params), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(A.fw_stats)]
+    lib.fw_camera_rays.restype = C.c_int
+    lib.fw_camera_rays.argtypes = [C.POINTER(A.fw_render_params), C.c_int, C.c_uint32, C.c_void_p]
     if lib.fw_abi_version() != A.FW_ABI_VERSION:
         raise FireworkError(A.FW_ERR_BAD_ARG, "ABI version mismatch between _abi.py and libfirework_hip.so")
     _lib = lib
@@ -181,6 +185,35 @@ def device_count():
     return load().fw_device_count()
 
 
+# numpy mirror of fw_hit (include/firework_hip.h): what DeviceScene.trace returns for host rays
+HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, (3,)), ("normal", np.float32, (3,)), ("u", np.float32),
+                      ("v", np.float32), ("material", np.uint32), ("object", np.uint32), ("prim", np.uint32)], align=True)
+# column of each field in the (n, 12) float32 records DeviceScene.trace returns for device tensors; material / object / prim are
+# integers: read them through an int32 view, hit_fields(records)
+HIT_COLUMNS = dict(t=0, point=slice(1, 4), normal=slice(4, 7), u=7, v=8, material=9, object=10, prim=11)
+
+
+def hit_fields(records):
+    """The fields of (n, 12) float32 trace records (a torch tensor) as views: t, point (n, 3), normal (n, 3), u, v float32; material,
+    object, prim int32 (object == -1, i.e. FW_NO_HIT, on a miss)."""
+    ints = records.view(dtype=__import__("torch").int32)
+    out = {k: records[:, c] for k, c in HIT_COLUMNS.items() if k not in ("material", "object", "prim")}
+    out.update(material=ints[:, 9], object=ints[:, 10], prim=ints[:, 11])
+    return out
+
+
+def camera_rays(renderer, sample=0, pixel_ids=None, device=0):
+    """fw_camera_rays: the segment-0 rays a render of `renderer` traces for `sample` of each pixel (pixel_ids, or every pixel in index
+    order), as an (n, 6) float32 array of origin and direction."""
+    lib = load()
+    ids = None if pixel_ids is None else np.ascontiguousarray(np.asarray(pixel_ids, dtype=np.uint32))
+    p = renderer.to_params(ids)
+    n = int(ids.shape[0]) if ids is not None else p.width * p.height
+    out = np.empty((n, 6), np.float32)
+    _check(lib, lib.fw_camera_rays(C.byref(p), int(device), int(sample), out.ctypes.data))
+    return out
+
+
 class DeviceScene:
     """An uploaded scene (`fw_scene*`): SoA scene arrays + TLAS/BLAS resident in HBM."""
 
@@ -229,6 +262,45 @@ class DeviceScene:
         _check(lib, lib.fw_render_progressive(self.handle, C.byref(p), int(first_sample), accum.ctypes.data, rgb8.ctypes.data,
                                               gam.ctypes.data, lin.ctypes.data, C.byref(st)))
         return RenderResult(rgb8, gam, lin, st.as_dict(), p.width, p.height)
+
+    def trace(self, rays, use_bvh, seed=0, key_base=0, rays_per_batch=0, time_kernels=False, stats=None):
+        """fw_trace_rays: one root.hit(ray, 0.001, 2e9) per ray.  rays: (n, 6) origin + direction.
+        - numpy (or anything array-like): returns a structured array of HIT_DTYPE (fw_hit's fields).
+        - a contiguous float32 torch tensor on this scene's device: traced in place on the current torch stream; returns an (n, 12)
+          float32 tensor on the device (columns: HIT_COLUMNS; hit_fields() gives the int32 views of material / object / prim).
+        A ray with a non-finite component or a zero direction comes back as a miss (object == FW_NO_HIT).  Ray i's medium draws are
+        keyed (seed, key_base + i).  stats: a dict to fill with fw_stats."""
+        lib = self._lib
+        p = A.fw_trace_params()
+        p.use_bvh = int(bool(use_bvh))
+        p.flags = A.FW_FLAG_TIME_KERNELS if time_kernels else 0
+        p.seed = int(seed)
+        p.key_base = int(key_base)
+        p.rays_per_batch = int(rays_per_batch)
+        st = A.fw_stats()
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 6:
+                raise ValueError("device rays must be a contiguous (n, 6) float32 tensor")
+            if rays.device.type != "cuda" or (rays.device.index or 0) != self.device:
+                raise ValueError(f"device rays must live on the scene's device (cuda:{self.device})")
+            n = int(rays.shape[0])
+            out = torch.empty((n, 12), dtype=torch.float32, device=rays.device)
+            p.on_device = 1
+            p.stream = C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream or None)
+            _check(lib, lib.fw_trace_rays(self.handle, C.byref(p), rays.data_ptr() if n else None, n, out.data_ptr() if n else None, C.byref(st)))
+        else:
+            r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32).reshape(-1, 6))
+            n = int(r.shape[0])
+            out = np.zeros(n, HIT_DTYPE)
+            _check(lib, lib.fw_trace_rays(self.handle, C.byref(p), r.ctypes.data, n, out.ctypes.data, C.byref(st)))
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out
+
+    def camera_rays(self, renderer, sample=0, pixel_ids=None):
+        """fw_camera_rays on this scene's device: see camera_rays()."""
+        return camera_rays(renderer, sample, pixel_ids, self.device)
 
     def close(self):
         if self.handle:

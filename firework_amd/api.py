@@ -915,6 +915,22 @@ class Renderer:
         """`pub fn render(&self, scene: Scene) -> Vec<Color>` (render.rs:109): (W*H, 3) uint8, row 0 = top."""
         return self.render_full(scene, None, device).rgb8
 
+    def gbuffer(self, scene, sample: int = 0, device: int = 0) -> dict:
+        """Depth / normal / ID buffers of the first hit of every pixel (not in the reference): the camera rays a render traces for
+        `sample` (fw_camera_rays), traced with this renderer's use_bvh and seed (fw_trace_rays).  Returns (H, W) arrays, row 0 =
+        image top: t, point (H, W, 3), normal (H, W, 3), u, v, material, object (FW_NO_HIT where the ray missed), prim.
+        `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        from . import _lib
+        s = self.settings
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            hits = ds.trace(ds.camera_rays(self, sample), s["use_bvh"], seed=s["seed"])
+        finally:
+            if ds is not scene:
+                ds.close()
+        h, w = int(s["height"]), int(s["width"])
+        return {name: hits[name].reshape((h, w) + hits.dtype[name].shape) for name in hits.dtype.names}
+
 
 def save_image(render: np.ndarray, path, width: int, height: int):
     """src/window.rs:59-66"""

@@ -138,6 +138,8 @@ struct DScene {
 //             numbers near 2*10^6 — noise — and the reference tests it whenever the ray passes the box of its DoubleLeaf node,
 //             a front-to-back walk when it passes the sphere's own box.  Flagged: origin farther than far_r from the cluster
 //             of the scene's small objects AND the ray passes that cluster's (inflated) box.
+constexpr uint32_t EX_TRACE_ZERO = 8u;   // DExact.mode bit of a trace under use_bvh only (k_trace_load; needs_exact ignores it): a caller ray whose
+                                         // direction has a zero component takes the exact walk (a ray inside a plane meets it at t = 0/0)
 struct DExact {
     uint32_t mode;
     uint32_t n_frames;            // distinct rotations of mesh objects (<= 4), rows of rotation_mat
@@ -249,6 +251,12 @@ void launch_shade(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, 
 void launch_bounce(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, float4 *sample_rad, int segment,
                    bool use_bvh);
 void launch_queue_totals(const LaunchCfg &, uint32_t *totals, const uint32_t *ptotal);
+// ray queries (fw_trace_rays / fw_camera_rays): caller rays (n x 6 floats) into the segment-0 queues, hit records out as fw_hit
+// (3 x float4 per ray), and the camera rays of a frame (n x 6 floats)
+void launch_trace_load(const LaunchCfg &, const DFrame &, const float *rays, DPaths out, uint32_t n, uint32_t key0, uint32_t *ids, uint32_t *slot_of);
+void launch_trace_store(const LaunchCfg &, const DScene &, const DFrame &, const DPaths &in, const float2 *hits, const uint32_t *slot_of, uint32_t n,
+                        float4 *out);
+void launch_camera_rays(hipStream_t stream, int n_cus, const DCamera &, const DFrame &, uint32_t n, float *out);
 void launch_scatter_tiles(hipStream_t stream, const uint32_t *ids, uint32_t n, const uint8_t *in8, const float *ing, const float *inl,
                           uint8_t *out8, float *outg, float *outl);
 void launch_tile_order(hipStream_t stream, uint32_t width, uint32_t height, uint32_t *ids);

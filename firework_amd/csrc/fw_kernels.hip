@@ -3691,9 +3691,128 @@ void launch_selftest_libm(hipStream_t stream, int fn, uint32_t n, const float *x
 }
 
 // ------------------------------------------------------------------------------------------------
+// Ray queries (fw_trace_rays, fw_camera_rays).  A trace is segment 0 of a render with the caller's rays in place of the camera's:
+// k_trace_load fills the segment-0 queues, the render's own launch_extend + launch_extend_exact trace them, k_trace_store turns
+// the hit records into fw_hit.  No walk of its own.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.40282347e+38f; }   // false for NaN and +-inf
+
+// The k_raygen of a trace.  Wave w takes the caller's rays (24-byte records) in the chunks k_raygen deals paths in, ray id =
+// chunk * n_waves * 64 + w * 64 + lane: a chunk's 1536 bytes are six dword loads per lane at consecutive addresses, transposed to
+// one ray per lane through LDS.  A ray with a non-finite component or an all-zero direction is not traced (slot_of = MISS); the
+// others are packed into the wave's queue in order and flagged for the exact walk as k_raygen flags camera rays.  The linear id of
+// the slot a ray lands in gets the ray's RNG pixel key in `ids` (= DFrame.pixel_ids, n_pixels = the batch, sample0 = 0), so the
+// draws of a ConstantMedium are keyed (key0 + ray id, sample 0, segment 0), as fw_trace_params.key_base promises.  The linear id of
+// position p of wave w, ((p >> 6) * n_waves + w) * 64 + (p & 63), never exceeds the ray id of the ray put there: ids has n entries.
+__global__ __launch_bounds__(WB) void k_trace_load(DFrame f, const float *__restrict__ rays, DPaths out, DQueue q, uint32_t n, uint32_t key0,
+                                                   uint32_t *__restrict__ ids, uint32_t *__restrict__ slot_of) {
+    __shared__ float tr[6 * 64];
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    if (w >= q.n_waves) return;
+    uint32_t produced = 0;
+    for (uint32_t chunk = 0;; chunk++) {
+        const uint32_t id0 = chunk * (q.n_waves * 64u) + w * 64u;
+        if (id0 >= n) break;
+        const uint32_t m = min(64u, n - id0);
+        const float *src = rays + (size_t)id0 * 6u;
+#pragma unroll
+        for (uint32_t k = 0; k < 6u; k++) { const uint32_t e = k * 64u + lane; if (e < 6u * m) tr[e] = src[e]; }
+        __syncthreads();                    // (one wave per workgroup: the barrier orders the LDS accesses only)
+        float v[6];
+#pragma unroll
+        for (uint32_t k = 0; k < 6u; k++) v[k] = tr[lane * 6u + k];
+        __syncthreads();
+        bool ok = lane < m;
+#pragma unroll
+        for (int k = 0; k < 6; k++) ok = ok && finite_f(v[k]);
+        ok = ok && !(v[3] == 0.f && v[4] == 0.f && v[5] == 0.f);
+        const unsigned long long bal = __ballot(ok);
+        const uint32_t pos = produced + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        const uint32_t slot = w * q.cap + pos, i = id0 + lane;
+        if (ok) {
+            qst(&out.ray_a[slot], make_float4(v[0], v[1], v[2], v[3]));
+            qst(&out.ray_b[slot], make_float2(v[4], v[5]));
+            ids[((pos >> 6) * q.n_waves + w) * 64u + (pos & 63u)] = key0 + i;
+        }
+        if (lane < m) slot_of[i] = ok ? slot : MISS;
+        // (EX_TRACE_ZERO, widened here and not in needs_exact, so renders keep their kernel mix: caller rays may run exactly inside a
+        // plane — t = 0/0 = NaN, a "hit" no comparison rejects, which the reference's tree walk lets a later hit replace or not by the
+        // order of its tests; camera and scattered rays practically never do)
+        const bool zero_dir = (f.ex.mode & EX_TRACE_ZERO) && (v[3] == 0.f || v[4] == 0.f || v[5] == 0.f);
+        const bool fl = ok && f.ex.mode && (zero_dir || needs_exact(f.ex, v[0], v[1], v[2], v[3], v[4], v[5]));
+        if (f.ex.mode) flag_exact(f.ex, fl, slot, 0);
+        produced += (uint32_t)__popcll(bal);
+    }
+    if (lane == 0) q.wcount[w] = produced;                                    // segment 0 queue length of this wave
+}
+
+// One fw_hit (48 bytes: t, point, normal, u | v, material, object, prim) per caller ray, in caller order, as three 16-byte stores.
+// The hit record is decoded as k_shade decodes it (4-byte records: t recomputed by recompute_t, as rebuild_hit does), the hit
+// rebuilt by rebuild_hit with uv.  The flattener keeps the order of fw_scene_desc.objects, so the device's object index is the
+// caller's.  A miss (or a ray k_trace_load left out): object = FW_NO_HIT, every other field 0.
+__global__ __launch_bounds__(BLOCK) void k_trace_store(DScene sc, DFrame f, DPaths in, const float2 *__restrict__ hits, const uint32_t *__restrict__ slot_of,
+                                                       uint32_t n, float4 *__restrict__ out) {
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const uint32_t slot = slot_of[i];
+        uint32_t code = MISS;
+        float t = 0.f;
+        if (slot != MISS) {
+            if (f.hit4) code = reinterpret_cast<const uint32_t *>(hits)[slot];
+            else { const float2 h = hits[slot]; t = h.x; code = __float_as_uint(h.y); }
+        }
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = make_float4(0.f, 0.f, __uint_as_float(MISS), 0.f);
+        if (code != MISS) {
+            const uint32_t obj = code >> sc.prim_bits, prim = code & ((1u << sc.prim_bits) - 1u);
+            const Obj o = load_obj(sc.obj, obj);
+            const float4 ra = in.ray_a[slot];
+            const float2 rb = in.ray_b[slot];
+            const Ray world{mk(ra.x, ra.y, ra.z), mk(ra.w, rb.x, rb.y)};
+            if (f.hit4) t = recompute_t(o, to_object_space(o, world), prim);
+            const HitInfo h = rebuild_hit(sc, o, world, t, prim, true);
+            r0 = make_float4(t, h.point.x, h.point.y, h.point.z);
+            r1 = make_float4(h.normal.x, h.normal.y, h.normal.z, h.u);
+            r2 = make_float4(h.v, __uint_as_float(h.material), __uint_as_float(obj), __uint_as_float(prim));
+        }
+        out[3 * (size_t)i] = r0; out[3 * (size_t)i + 1] = r1; out[3 * (size_t)i + 2] = r2;
+    }
+}
+
+// The segment-0 rays k_raygen makes for sample f.sample0 of pixel key_of_linear(f, i), i < n (DFrame as a render's with
+// spp_batch = 1): camera_ray itself, origin included — for a pinhole camera the position k_raygen's short rays stand for.
+// Written as 6 floats per ray, transposed through LDS into six coalesced dword stores per lane.
+__global__ __launch_bounds__(WB) void k_camera_rays(DCamera cam, DFrame f, uint32_t n, float *__restrict__ out) {
+    __shared__ float tr[6 * 64];
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t id0 = blockIdx.x * 64u; id0 < n; id0 += gridDim.x * 64u) {
+        const uint32_t m = min(64u, n - id0);
+        if (lane < m) {
+            const Ray r = camera_ray(cam, f, key_of_linear(f, id0 + lane));
+            float *d = tr + lane * 6u;
+            d[0] = r.o.x; d[1] = r.o.y; d[2] = r.o.z; d[3] = r.d.x; d[4] = r.d.y; d[5] = r.d.z;
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < 6u; k++) { const uint32_t e = k * 64u + lane; if (e < 6u * m) out[(size_t)id0 * 6u + e] = tr[e]; }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------------
 static dim3 wave_grid(const LaunchCfg &c) { return dim3((c.q.n_waves + WB / 64 - 1) / (WB / 64)); }
+void launch_trace_load(const LaunchCfg &c, const DFrame &f, const float *rays, DPaths out, uint32_t n, uint32_t key0, uint32_t *ids, uint32_t *slot_of) {
+    hipLaunchKernelGGL(k_trace_load, wave_grid(c), dim3(WB), 0, c.stream, f, rays, out, c.q, n, key0, ids, slot_of);
+}
+void launch_trace_store(const LaunchCfg &c, const DScene &sc, const DFrame &f, const DPaths &in, const float2 *hits, const uint32_t *slot_of, uint32_t n,
+                        float4 *out) {
+    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n + BLOCK - 1) / BLOCK, (uint64_t)c.n_cus * 32u));
+    hipLaunchKernelGGL(k_trace_store, dim3(blocks), dim3(BLOCK), 0, c.stream, sc, f, in, hits, slot_of, n, out);
+}
+void launch_camera_rays(hipStream_t stream, int n_cus, const DCamera &cam, const DFrame &f, uint32_t n, float *out) {
+    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n + 63u) / 64u, (uint64_t)n_cus * 64u));
+    hipLaunchKernelGGL(k_camera_rays, dim3(blocks), dim3(WB), 0, stream, cam, f, n, out);
+}
 
 void launch_raygen(const LaunchCfg &c, const DCamera &cam, const DFrame &f, DPaths out, float4 *sample_rad, uint32_t n_paths) {
     hipLaunchKernelGGL(k_raygen, wave_grid(c), dim3(WB), 0, c.stream, cam, f, out, sample_rad, c.q, n_paths);
@@ -3860,7 +3979,7 @@ void preload_kernels() {
     FW_TOUCH(k_extend_tlas); FW_TOUCH(k_extend_tlas_park); FW_TOUCH(k_blas); FW_TOUCH(k_blas_lds<true>); FW_TOUCH(k_blas_lds<false>); FW_TOUCH(k_extend_tlas_lds);
     FW_TOUCH((k_blas_wide<WIDE_F32, true>)); FW_TOUCH((k_blas_wide<WIDE_F32, false>)); FW_TOUCH((k_blas_wide<WIDE_Q8, true>)); FW_TOUCH((k_blas_wide<WIDE_Q8, false>));
     FW_TOUCH(k_extend_tlas_wide<true>); FW_TOUCH(k_extend_tlas_wide<false>); FW_TOUCH((k_extend_tlas_wide<true, true>)); FW_TOUCH((k_extend_tlas_wide<false, true>)); FW_TOUCH(k_extend_exact); FW_TOUCH(k_queue_totals); FW_TOUCH(k_count_deposits); FW_TOUCH(k_accumulate); FW_TOUCH(k_tile_order);
-    FW_TOUCH(k_resolve); FW_TOUCH(k_scatter_tiles);
+    FW_TOUCH(k_resolve); FW_TOUCH(k_scatter_tiles); FW_TOUCH(k_trace_load); FW_TOUCH(k_trace_store); FW_TOUCH(k_camera_rays);
     FW_TOUCH((k_shade<0, 0, false>)); FW_TOUCH((k_shade<0, 0, true>)); FW_TOUCH((k_shade<0, 1, false>)); FW_TOUCH((k_shade<0, 1, true>));
     FW_TOUCH((k_shade<1, 0, false>)); FW_TOUCH((k_shade<1, 0, true>)); FW_TOUCH((k_shade<1, 1, false>)); FW_TOUCH((k_shade<1, 1, true>));
     FW_TOUCH((k_shade<2, 0, false>)); FW_TOUCH((k_shade<2, 0, true>)); FW_TOUCH((k_shade<2, 1, false>)); FW_TOUCH((k_shade<2, 1, true>));

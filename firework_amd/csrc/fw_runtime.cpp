@@ -1551,6 +1551,35 @@ uint32_t default_paths_per_batch(const Options &O, size_t arena_bytes) {
     return (uint32_t)std::max<uint64_t>(budget, 1u << 16);
 }
 
+// The fields of the launch configuration that select and size the walks (launch_extend / launch_extend_exact): the scene's trees and
+// the options.  One function for render_impl and trace_impl, so that a trace runs the kernels a render of the scene runs.  Assigns
+// fields of a struct the caller has zeroed (the frame graph's key hashes its bytes, padding included).
+void set_walk_cfg(fw::LaunchCfg &cfg, const fw_scene *sc, const Options &O, const fw::DQueue &q, bool use_bvh, bool tlas_refill) {
+    cfg.q = q;
+    cfg.tlas_depth = (int)sc->tlas_depth; cfg.blas_depth = (int)sc->blas_depth;
+    cfg.n_mat = sc->n_mat; cfg.n_tex = sc->n_tex;
+    cfg.lds_tables = !O.no_lds_tables;
+    cfg.has_mesh = sc->d.has_mesh != 0;
+    cfg.simple_set = sc->simple_set; cfg.simple_but_meshes = sc->simple_but_meshes;
+#ifdef FW_NO_SIMPLE      // A/B build: the kernels of round 4 (every shape's code in every kernel that calls hit_object)
+    cfg.simple_set = cfg.simple_but_meshes = false;
+#endif
+    cfg.tlas_refill = tlas_refill;
+    cfg.n_cus = sc->n_cus;
+    cfg.blas_pair_nodes = sc->blas_pair_nodes; cfg.tlas_pair_nodes = sc->tlas_pair_nodes; cfg.max_tris = sc->max_tris; cfg.n_tris = sc->n_tris;
+    cfg.no_lds_tris = O.no_lds_tris;
+    cfg.n_defer = (!use_bvh && !O.no_defer) ? sc->n_defer : 0u;
+    cfg.lds_trees = !O.no_lds_trees;
+    cfg.wblas_fmt = sc->wblas_fmt; cfg.wtlas_fmt = sc->wtlas_fmt; cfg.wblas_nodes = sc->wblas_nodes; cfg.wtlas_nodes = sc->wtlas_nodes;
+    cfg.wblas_depth = sc->wblas_depth; cfg.wtlas_depth = sc->wtlas_depth;
+    cfg.exact_form = O.exact_form;
+    cfg.debug_wide_levels = 0;
+#if FW_AB
+    cfg.debug_wide_levels = (uint32_t)O.debug_wide_levels;
+#endif
+    cfg.ref_tlas_nodes = sc->tlas_nodes; cfg.ref_blas_nodes = sc->blas_nodes; cfg.ref_tlas_depth = sc->ref_tlas_depth; cfg.ref_blas_depth = sc->ref_blas_depth;
+}
+
 // first_sample / user_accum: fw_render_progressive (0 / nullptr for a plain render)
 int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb, fw_stats *stats,
                 uint32_t first_sample = 0, float *user_accum = nullptr) {
@@ -1708,31 +1737,9 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     HIPCHK(hipMemsetAsync(ws->totals.p, 0, (size_t)n_batches * fw::COUNT_STRIDE * 4, stream));
 
     fw::LaunchCfg cfg{};
-    cfg.q = q;
+    set_walk_cfg(cfg, sc, O, q, p->use_bvh != 0, tlas_refill);
     int max_blocks = sc->n_cus * 8;
     cfg.blocks_other = (int)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n_pix + fw::BLOCK - 1) / fw::BLOCK, (uint64_t)max_blocks));
-    cfg.tlas_depth = (int)sc->tlas_depth; cfg.blas_depth = (int)sc->blas_depth;
-    cfg.n_mat = sc->n_mat; cfg.n_tex = sc->n_tex;
-    cfg.lds_tables = !O.no_lds_tables;
-    cfg.has_mesh = sc->d.has_mesh != 0;
-    cfg.simple_set = sc->simple_set; cfg.simple_but_meshes = sc->simple_but_meshes;
-#ifdef FW_NO_SIMPLE      // A/B build: the kernels of round 4 (every shape's code in every kernel that calls hit_object)
-    cfg.simple_set = cfg.simple_but_meshes = false;
-#endif
-    cfg.tlas_refill = tlas_refill;
-    cfg.n_cus = sc->n_cus;
-    cfg.blas_pair_nodes = sc->blas_pair_nodes; cfg.tlas_pair_nodes = sc->tlas_pair_nodes; cfg.max_tris = sc->max_tris; cfg.n_tris = sc->n_tris;
-    cfg.no_lds_tris = O.no_lds_tris;
-    cfg.n_defer = (!p->use_bvh && !O.no_defer) ? sc->n_defer : 0u;
-    cfg.lds_trees = !O.no_lds_trees;
-    cfg.wblas_fmt = sc->wblas_fmt; cfg.wtlas_fmt = sc->wtlas_fmt; cfg.wblas_nodes = sc->wblas_nodes; cfg.wtlas_nodes = sc->wtlas_nodes;
-    cfg.wblas_depth = sc->wblas_depth; cfg.wtlas_depth = sc->wtlas_depth;
-    cfg.exact_form = O.exact_form;
-    cfg.debug_wide_levels = 0;
-#if FW_AB
-    cfg.debug_wide_levels = (uint32_t)O.debug_wide_levels;
-#endif
-    cfg.ref_tlas_nodes = sc->tlas_nodes; cfg.ref_blas_nodes = sc->blas_nodes; cfg.ref_tlas_depth = sc->ref_tlas_depth; cfg.ref_blas_depth = sc->ref_blas_depth;
     // k_shade's list entries are 16-bit queue positions: longer queues (cap > 65536: never with the default geometry) shade in line
     // Default: the cheap loop alone where the scene has nothing expensive (cornell k_shade -5 %), everything in line otherwise — the
     // list (mode 2) is slower wherever it was measured (gpurun_out/r03h: part2@16 11.7 -> 12.0 ms, hdri@64 5.5 -> 6.1, random_spheres
@@ -2078,6 +2085,217 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     return FW_OK;
 }
 
+// Device memory of a ray query (trace_impl, camera_rays_impl): the front of the path arena, grown like render_impl grows it.  A render
+// lays its own buffers out from the arena's start on every call, so nothing of a render outlives it there.  What a render does keep is
+// a frame graph (GRAPH) whose launches name arena addresses: its key hashes the arena's address and size, which a growth changes, and
+// the key is cleared here as well, so a graph recorded before a growth is never replayed.  Caller holds ws->mu.
+int query_arena_locked(Workspace *ws, int dev, size_t bytes, uint8_t *&base) {
+    size_t want = (bytes + ((size_t)1 << 30) - 1) & ~(((size_t)1 << 30) - 1);
+    if (want > ws->arena.bytes) {
+        if (ws->arena.bytes) want = std::max(want, (ws->arena.bytes + ws->arena.bytes / 4 + ((size_t)1 << 30) - 1) & ~(((size_t)1 << 30) - 1));
+        ws->fg.key = 0; ws->fg.seen = 0;
+        if (int rc = arena_reserve_locked(ws, dev, want)) return rc;
+    }
+    base = (uint8_t *)ws->arena.p;
+    return FW_OK;
+}
+// pinned host staging of a ray query's transfers (Workspace::host_out, which render_impl grows the same way)
+int query_host_locked(Workspace *ws, size_t bytes, uint8_t *&host) {
+    if (ws->host_out_bytes < bytes) {
+        if (ws->host_out) (void)hipHostFree(ws->host_out);
+        ws->host_out = nullptr; ws->host_out_bytes = 0;
+        if (hipHostMalloc(&ws->host_out, bytes + bytes / 4, hipHostMallocDefault) != hipSuccess) return fail(FW_ERR_OOM, "pinned staging allocation failed");
+        ws->host_out_bytes = bytes + bytes / 4;
+    }
+    host = (uint8_t *)ws->host_out;
+    return FW_OK;
+}
+
+static_assert(sizeof(fw_hit) == 48, "fw_hit is three 16-byte stores of k_trace_store");
+// fw_trace_rays: segment 0 of a render over the caller's rays.  Per batch, on the caller's stream: k_trace_load (the queues, the exact
+// walk's list) -> the render's launch_extend -> launch_extend_exact -> k_trace_store; with host memory the rays and hits pass through
+// pinned staging.  The queue geometry, the walk configuration and the hit-record form are chosen as render_impl chooses them for one
+// batch in flight, so every kernel-selecting option selects the same walks here.
+int trace_impl(fw_scene *sc, const fw_trace_params *p, const float *rays, uint32_t n, fw_hit *hits, fw_stats *stats) {
+    if (!sc || !p) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (n == 0) return FW_OK;
+    if (!rays || !hits) return fail(FW_ERR_BAD_ARG, "null rays or hits");
+    if (((uintptr_t)rays & 3u) || (p->on_device && ((uintptr_t)hits & 15u))) return fail(FW_ERR_BAD_ARG, "rays must be 4-byte aligned, device hits 16-byte aligned");
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(sc->device));
+    hipStream_t stream = (hipStream_t)p->stream;
+    Workspace *ws = workspace_for(sc->device);
+    if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
+    std::lock_guard<std::mutex> ws_guard(ws->mu);
+    { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }
+    const Options O = options();
+    const bool use_bvh = p->use_bvh != 0;
+    const uint32_t per = std::min(n, p->rays_per_batch ? p->rays_per_batch : default_paths_per_batch(O, ws->arena.bytes));
+    const uint32_t n_batches = (uint32_t)(((uint64_t)n + per - 1) / per);
+
+    // render_impl's queue geometry for a batch of `per` paths (one batch in flight)
+    fw::DQueue q{};
+    const uint32_t unit = (uint32_t)sc->n_cus * 4u * (use_bvh ? 20u : 28u);
+    const uint64_t chunks = ((uint64_t)per + 63u) / 64u;
+    uint32_t want_waves = unit * (uint32_t)std::min<uint64_t>(3u, std::max<uint64_t>(1u, chunks / ((uint64_t)unit * 16u)));
+    if (O.waves > 0) want_waves = (uint32_t)O.waves;
+    q.n_waves = std::max(4u, std::min(want_waves, (per + 511u) / 512u));
+    q.n_waves = (q.n_waves + 7u) & ~7u;
+    const uint32_t chunks_per_wave = (per + q.n_waves * 64u - 1) / (q.n_waves * 64u);
+    while ((1u << q.cpw_shift) < chunks_per_wave) q.cpw_shift++;
+    q.cap = 64u << q.cpw_shift;
+    const uint64_t cap64 = (uint64_t)q.cap * q.n_waves;
+    if (cap64 > 0x7fffffffull) return fail(FW_ERR_UNSUPPORTED, "too many rays per batch");
+    const size_t cap = (size_t)cap64;
+#if FW_AB
+    const bool tlas_refill = !O.tlas_refill_off;
+#else
+    const bool tlas_refill = true;
+#endif
+    // render_impl's exact walk, and under use_bvh the caller rays with a zero direction component as well (fw::EX_TRACE_ZERO)
+    const uint32_t exact_mode = (sc->ex.mode & 1u) | (use_bvh ? (sc->ex.mode & 6u) | fw::EX_TRACE_ZERO : ((sc->ex.mode & 4u) && sc->d.has_mesh ? 4u : 0u));
+    const bool park_meshes = use_bvh && sc->d.has_mesh != 0 && tlas_refill;
+
+    // device memory: the front of the arena
+    const size_t pcap = (size_t)(q.cap + 64u) * q.n_waves;
+    const size_t totals_bytes = (size_t)n_batches * fw::COUNT_STRIDE * 4;
+    size_t off = 0;
+    auto put = [&](size_t b) { const size_t at = off; off += (b + 255) & ~(size_t)255; return at; };
+    const size_t o_ra = put(cap * 16), o_rb = put(cap * 8), o_hits = put(cap * 8), o_wc = put((size_t)(fw::MAX_SEGMENTS + 1) * q.n_waves * 4);
+    const size_t o_ids = put((size_t)per * 4), o_slot = put((size_t)per * 4), o_tot = put(totals_bytes);
+    const size_t o_ex = exact_mode ? put(2 * (size_t)per * 4 + 64) : 0;
+    const size_t o_pa = park_meshes ? put(pcap * 16) : 0, o_pb = park_meshes ? put(pcap * 8) : 0, o_pm = park_meshes ? put(pcap * 16) : 0;
+    const size_t o_pc = park_meshes ? put((size_t)q.n_waves * 8) : 0;
+    const size_t o_in = p->on_device ? 0 : put((size_t)per * 24), o_out = p->on_device ? 0 : put((size_t)per * sizeof(fw_hit));
+    uint8_t *base = nullptr;
+    if (int rc = query_arena_locked(ws, sc->device, off, base)) return rc;
+    // pinned staging: the batches' queue counters, then (host memory) one batch of rays and one of hits
+    const size_t h_tot = 0, h_in = (totals_bytes + 255) & ~(size_t)255, h_out = h_in + (p->on_device ? 0 : ((size_t)per * 24 + 255) & ~(size_t)255);
+    uint8_t *host = nullptr;
+    if (int rc = query_host_locked(ws, h_out + (p->on_device ? 0 : (size_t)per * sizeof(fw_hit)), host)) return rc;
+    const bool timing = (p->flags & FW_FLAG_TIME_KERNELS) != 0;
+    while (ws->events.size() < 3) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, ws->events.size() < 2 ? hipEventDefault : hipEventDisableTiming)); ws->events.push_back(e); }
+    std::vector<hipEvent_t> &tev = ws->lanes[0].events;
+    while (timing && tev.size() < 2) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); tev.push_back(e); }
+
+    fw::LaunchCfg cfg{};
+    set_walk_cfg(cfg, sc, O, q, use_bvh, tlas_refill);
+    cfg.stream = stream;
+    cfg.q.wcount = (uint32_t *)(base + o_wc);
+    fw::DPaths paths{(float4 *)(base + o_ra), (float2 *)(base + o_rb), nullptr};     // segment 0 reads no path state
+    float2 *const hit_rec = (float2 *)(base + o_hits);
+    uint32_t *const ids = (uint32_t *)(base + o_ids), *const slot_of = (uint32_t *)(base + o_slot), *const totals = (uint32_t *)(base + o_tot);
+    const fw::DPark park{(float4 *)(base + o_pa), (float2 *)(base + o_pb), (float4 *)(base + o_pm), q.cap + 64u,
+                         park_meshes ? (uint32_t *)(base + o_pc) : nullptr, park_meshes ? (uint32_t *)(base + o_pc) + q.n_waves : nullptr};
+    fw::DFrame fr{};
+    fr.width = 1; fr.height = 1; fr.inv_width = 1.f;              // (camera fields: unused by a trace)
+    fr.pixel_ids = ids;
+    fr.seed32 = (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u);
+    fr.sample0 = 0; fr.spp_batch = 1;
+    fr.q_n_waves = q.n_waves; fr.q_shift = q.cpw_shift;
+    fr.pinhole0 = 0;                                             // caller rays are whole rays
+    fr.hit4 = (!use_bvh && sc->simple_shapes && !exact_mode && !O.no_hit4) ? 1u : 0u;
+    fr.ex = sc->ex; fr.ex.mode = exact_mode;
+    if (exact_mode) {
+        fr.ex.slots[0] = (uint32_t *)(base + o_ex); fr.ex.slots[1] = fr.ex.slots[0] + per;
+        fr.ex.count = fr.ex.slots[1] + per; fr.ex.cap = per;
+    }
+
+    if (ws->ev_upload) HIPCHK(hipStreamWaitEvent(stream, ws->ev_upload, 0));     // the scene's upload kernel
+    HIPCHK(hipEventRecord(ws->events[0], stream));
+    HIPCHK(hipMemsetAsync(totals, 0, totals_bytes, stream));
+    double ms_extend = 0.0;
+    for (uint32_t b = 0; b < n_batches; b++) {
+        const size_t first = (size_t)b * per;
+        const uint32_t nb = (uint32_t)std::min<size_t>(per, (size_t)n - first);
+        fr.n_pixels = nb; fr.inv_n_pixels = 1.0f / (float)nb;
+        HIPCHK(hipMemsetAsync(cfg.q.wcount, 0, (size_t)(fw::MAX_SEGMENTS + 1) * q.n_waves * 4, stream));
+        if (exact_mode) HIPCHK(hipMemsetAsync(fr.ex.count, 0, 64, stream));
+        if (park_meshes) HIPCHK(hipMemsetAsync(park.ptotal, 0, (size_t)q.n_waves * 4, stream));
+        const float *src = rays + first * 6;
+        if (!p->on_device) {
+            std::memcpy(host + h_in, src, (size_t)nb * 24);
+            HIPCHK(hipMemcpyAsync(base + o_in, host + h_in, (size_t)nb * 24, hipMemcpyHostToDevice, stream));
+            src = (const float *)(base + o_in);
+        }
+        fw::launch_trace_load(cfg, fr, src, paths, nb, p->key_base + (uint32_t)first, ids, slot_of);
+        if (timing) HIPCHK(hipEventRecord(tev[0], stream));
+        fw::launch_extend(cfg, sc->d, fr, paths, hit_rec, 0, use_bvh, park);
+        if (exact_mode) fw::launch_extend_exact(cfg, sc->d, fr, paths, hit_rec, 0, use_bvh);
+        if (timing) HIPCHK(hipEventRecord(tev[1], stream));
+        fw::launch_queue_totals(cfg, totals + (size_t)b * fw::COUNT_STRIDE, park.ptotal);
+        fw_hit *dst = p->on_device ? hits + first : (fw_hit *)(base + o_out);
+        fw::launch_trace_store(cfg, sc->d, fr, paths, hit_rec, slot_of, nb, (float4 *)dst);
+        if (!p->on_device) HIPCHK(hipMemcpyAsync(host + h_out, dst, (size_t)nb * sizeof(fw_hit), hipMemcpyDeviceToHost, stream));
+        if (timing || !p->on_device) HIPCHK(hipStreamSynchronize(stream));
+        if (timing) { float t = 0.f; HIPCHK(hipEventElapsedTime(&t, tev[0], tev[1])); ms_extend += t; }
+        if (!p->on_device) std::memcpy(hits + first, host + h_out, (size_t)nb * sizeof(fw_hit));
+    }
+    HIPCHK(hipEventRecord(ws->events[1], stream));
+    HIPCHK(hipMemcpyAsync(host + h_tot, totals, totals_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        const uint32_t *h_counts = (const uint32_t *)(host + h_tot);
+        for (uint32_t b = 0; b < n_batches; b++) {
+            stats->rays += h_counts[(size_t)b * fw::COUNT_STRIDE];
+            stats->parked_rays += h_counts[(size_t)b * fw::COUNT_STRIDE + fw::MAX_SEGMENTS];
+        }
+        stats->rays_per_depth[0] = stats->rays;
+        stats->n_batches = n_batches; stats->n_extend_launches = n_batches;
+        stats->tlas_nodes = sc->tlas_nodes; stats->blas_nodes = sc->blas_nodes;
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ws->events[0], ws->events[1]));
+        stats->ms_render = ms;
+        stats->ms_extend = ms_extend;
+        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FW_OK;
+}
+
+// fw_camera_rays: k_camera_rays over render_impl's camera and keys for one sample of the pixels
+int camera_rays_impl(const fw_render_params *p, int device, uint32_t sample, float *rays) {
+    if (!p || !rays) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
+    const uint64_t full = (uint64_t)p->width * p->height;
+    if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
+    const uint32_t n_pix = p->pixel_ids ? p->n_pixels : (uint32_t)full;
+    if (n_pix == 0) return fail(FW_ERR_BAD_ARG, "no pixels");
+    if (p->pixel_ids) for (uint32_t i = 0; i < n_pix; i++) if (p->pixel_ids[i] >= full) return fail(FW_ERR_BAD_ARG, "pixel id out of range");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    if (p->outputs_on_device && ((uintptr_t)rays & 3u)) return fail(FW_ERR_BAD_ARG, "rays must be 4-byte aligned");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)p->stream;
+    Workspace *ws = workspace_for(device);
+    if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
+    std::lock_guard<std::mutex> ws_guard(ws->mu);
+    { const int irc = init_device_locked(ws, device); if (irc) return irc; }
+    const size_t o_ids = 0, o_out = p->pixel_ids ? ((size_t)n_pix * 4 + 255) & ~(size_t)255 : 0;
+    uint8_t *base = nullptr;
+    if (int rc = query_arena_locked(ws, device, o_out + (p->outputs_on_device ? 0 : (size_t)n_pix * 24), base)) return rc;
+    const fw::DCamera cam = make_camera(p->camera, p->width, p->height);
+    fw::DFrame fr{};      // render_impl's frame fields that camera_ray / key_of_linear read, for a batch of one sample
+    fr.width = p->width; fr.height = p->height; fr.n_pixels = n_pix; fr.inv_n_pixels = 1.0f / (float)n_pix; fr.inv_width = 1.0f / (float)p->width;
+    fr.pixel_ids = p->pixel_ids ? (const uint32_t *)(base + o_ids) : nullptr;
+    fr.seed32 = (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u);
+    fr.sample0 = sample; fr.spp_batch = 1;
+    if (p->pixel_ids) HIPCHK(hipMemcpyAsync(base + o_ids, p->pixel_ids, (size_t)n_pix * 4, hipMemcpyHostToDevice, stream));
+    float *dst = p->outputs_on_device ? rays : (float *)(base + o_out);
+    fw::launch_camera_rays(stream, device_cus(device), cam, fr, n_pix, dst);
+    if (!p->outputs_on_device) {
+        uint8_t *host = nullptr;
+        if (int rc = query_host_locked(ws, (size_t)n_pix * 24, host)) return rc;
+        HIPCHK(hipMemcpyAsync(host, dst, (size_t)n_pix * 24, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        std::memcpy(rays, host, (size_t)n_pix * 24);
+    } else HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
 } // namespace
 
 // =========================================================================================================
@@ -2254,6 +2472,19 @@ int fw_render(fw_scene *scene, const fw_render_params *params, uint8_t *rgb8, fl
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_render"); }
 }
+
+int fw_trace_rays(fw_scene *scene, const fw_trace_params *params, const float *rays, uint32_t n_rays, fw_hit *hits, fw_stats *stats) {
+    try { return trace_impl(scene, params, rays, n_rays, hits, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_trace_rays"); }
+}
+
+int fw_camera_rays(const fw_render_params *params, int device, uint32_t sample, float *rays) {
+    try { return camera_rays_impl(params, device, sample, rays); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_camera_rays"); }
+}
+
 
 // ---- single-process multi-GPU: one host thread per device, 16x16 tiles dealt diagonally (the scheme of firework_amd/tiles.py),
 // each device renders its pixels with the keys one GPU would use, results are scattered into the caller's buffers.

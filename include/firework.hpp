@@ -236,6 +236,14 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
         p.camera = fw_camera_settings{lower(camera_.cam_pos_), lower(camera_.look_at_), camera_.vfov, camera_.aperture_, camera_.focus_dist_};
         return p; }
 
+    // The segment-0 rays a render traces for `sample` of every pixel, index order (fw_camera_rays, ABI v8): width*height x 6 floats
+    std::vector<float> camera_rays(uint32_t sample = 0) const {
+        fw_render_params p = params();
+        std::vector<float> rays(width_ * height_ * 6);
+        const int rc = fw_camera_rays(&p, device_, sample, rays.data());
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        return rays; }
+
     // several GPUs from this one process (fw_render_scene_tiled): the image does not depend on the list
     Renderer devices(std::vector<int> d) && { devices_ = std::move(d); return std::move(*this); }
     std::vector<int> devices_;
@@ -273,6 +281,29 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
         }
         fw_scene_destroy(sc);
         return buffer; }
+};
+
+// Ray queries (ABI v8, not in the reference): a scene uploaded once, and `Hitable::hit(ray, 0.001, 2e9)` (render.rs:19,44-57) for the
+// caller's rays — picking, depth / normal / ID buffers, visibility.  See fw_trace_rays for the contract.
+class DeviceScene {
+  public:
+    explicit DeviceScene(const Scene &scene, int device = 0) {
+        Lowered low(scene);                      // fw_scene_create copies what it needs
+        const int rc = fw_scene_create(&low.desc, device, &sc_);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+    }
+    ~DeviceScene() { if (sc_) fw_scene_destroy(sc_); }
+    DeviceScene(const DeviceScene &) = delete;
+    DeviceScene &operator=(const DeviceScene &) = delete;
+    // rays: n x 6 floats (origin, direction) -> one fw_hit per ray (object == FW_NO_HIT: a miss)
+    std::vector<fw_hit> trace(const std::vector<float> &rays, bool use_bvh, uint64_t seed = 0, uint32_t key_base = 0, fw_stats *stats = nullptr) const {
+        fw_trace_params p{}; p.use_bvh = use_bvh ? 1 : 0; p.seed = seed; p.key_base = key_base;
+        std::vector<fw_hit> hits(rays.size() / 6);
+        const int rc = fw_trace_rays(sc_, &p, rays.data(), (uint32_t)hits.size(), hits.data(), stats);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        return hits; }
+  private:
+    fw_scene *sc_ = nullptr;
 };
 
 // window.rs:59-66 `save_image` (binary PPM: no PNG encoder is linked into this header)

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define FW_ABI_VERSION 7   /* 7: + fw_init (loading the library no longer touches the GPU); options EXACT_PRODUCT, PHASE_LOCK, GRAPH; 6: + fw_set_option (the runtime switches leave the environment: read once at load), fw_selftest_wide_bvh; 3: + fw_render_progressive; 4: fw_stats carries this layout's own HBM bytes per kernel class and the one-shot timings;
+#define FW_ABI_VERSION 8   /* 8: + fw_trace_rays, fw_camera_rays (ray queries; fw_hit, fw_trace_params); 7: + fw_init (loading the library no longer touches the GPU); options EXACT_PRODUCT, PHASE_LOCK, GRAPH; 6: + fw_set_option (the runtime switches leave the environment: read once at load), fw_selftest_wide_bvh; 3: + fw_render_progressive; 4: fw_stats carries this layout's own HBM bytes per kernel class and the one-shot timings;
                               5: + fw_selftest_libm; the 4th float of an accumulation record counts the path segments of the samples that deposited */
 
 /* ---- status codes ------------------------------------------------------ */
@@ -295,6 +295,54 @@ int fw_render_scene(const fw_scene_desc *desc, const fw_render_params *params, i
 /* The wavefront workspace (path pools, tens of GB for big frames) is cached per device between calls — the library's
    only global state.  This frees it (e.g. before handing the GPU to another library). */
 void fw_release_workspace(int device);
+
+/* ---- ray queries (ABI v8) ------------------------------------------------
+   The operation the renderer is built on, `Hitable::hit(ray, t_min, t_max, rng) -> Option<RaycastHit>` (render.rs:44-57), for the
+   caller's own rays on an uploaded scene: picking, depth / normal / material / object-ID buffers, visibility, integrators of one's
+   own.  A trace runs the launches of a render's first segment — the same walks, the same exact-walk flagging, the same options
+   (BVH, WIDE, EXACT_ALL, EXACT_FORM, NO_DEFER, NO_HIT4, NO_LDS_TREES, NO_LDS_TRIS, WAVES, PATHS_PER_BATCH) — over the caller's rays.
+     - t range: the renderer's fixed (0.001, 2e9) (render.rs:19).  There is no per-ray range.
+     - A ray with a non-finite component or an all-zero direction is reported as a miss and never traced.
+     - n_rays == 0 returns FW_OK and writes nothing.  A NULL scene or params, and NULL rays / hits with n_rays > 0, return
+       FW_ERR_BAD_ARG; with on_device, hits must be 16-byte aligned.  Without a visible GPU the call returns FW_ERR_NO_DEVICE:
+       there is no CPU fallback.
+     - stats (may be NULL): rays = rays traced (= rays_per_depth[0]), parked_rays, n_batches, ms_render (first launch to last), and
+       ms_extend (the walks alone) under FW_FLAG_TIME_KERNELS; every other field 0.
+     - Synchronisation is fw_render's with outputs_on_device: the launches go to `stream` (after the scene's upload, which the stream
+       waits for), and the call returns after that stream has drained — with on_device the hits are complete on return, and the
+       caller's earlier work on `stream` is ordered before the trace reads the rays.
+     - A trace leaves renders as they were: it may grow the device's path workspace, which changes the key of a frame graph cached
+       by option GRAPH, so a render after it never replays launches recorded against memory the trace moved. */
+#define FW_NO_HIT UINT32_MAX
+
+typedef struct fw_hit {          /* RaycastHit (render.rs:35-41) of one ray; 48 bytes */
+    float t;                     /* in units of |direction|: directions are never normalised (ray.rs) */
+    fw_vec3 point, normal;       /* world space, as RenderObjectInternal::hit returns them (scene.rs:235-266) */
+    float u, v;
+    uint32_t material;           /* MaterialIdx */
+    uint32_t object;             /* index into fw_scene_desc.objects; FW_NO_HIT on a miss, every other field 0 */
+    uint32_t prim;               /* triangle of a TriangleMesh, face of a Rect3d, else 0 */
+} fw_hit;
+
+typedef struct fw_trace_params {
+    int32_t use_bvh;             /* TLAS walk or the linear list (scene.rs:137-175), as in fw_render_params */
+    uint32_t flags;              /* FW_FLAG_TIME_KERNELS */
+    uint64_t seed;               /* CTR key of ConstantMedium's draws */
+    uint32_t key_base;           /* ray i draws as (seed, pixel = key_base + i, sample 0, segment 0): fwo_trace's key at key_base 0 */
+    uint32_t rays_per_batch;     /* 0 = library default (a render's pool size) */
+    int32_t on_device;           /* rays and hits are device pointers on the scene's device */
+    void *stream;                /* hipStream_t, NULL = default */
+} fw_trace_params;
+
+/* One root.hit(ray, 0.001, 2e9) (render.rs:19) per ray, on an uploaded scene.  rays: n_rays x 6 floats (origin, direction);
+   hits: n_rays records in ray order. */
+int fw_trace_rays(fw_scene *scene, const fw_trace_params *params, const float *rays, uint32_t n_rays, fw_hit *hits, fw_stats *stats);
+
+/* The segment-0 rays k_raygen traces for `sample` of every pixel in params->pixel_ids (or all width*height pixels): n x 6 floats
+   in pixel_ids order.  Camera::ray (camera.rs:109-116) with the renderer's own keys (params->seed), bit for bit the rays a render
+   traces, origin included.  `rays` is host memory, or device memory on `device` when params->outputs_on_device (then on
+   params->stream, complete on return). */
+int fw_camera_rays(const fw_render_params *params, int device, uint32_t sample, float *rays);
 
 /* Diagnostic: the kernels' division / square-root helpers against the compiler's IEEE expansion, bit for bit,
    on n hashed operand pairs.  mode 0 = magnitudes 2^-40..2^40 (must be 0 mismatches), mode 1 = all bit patterns. */
