@@ -71,6 +71,8 @@ def load(preload=False, device=None):
     lib.fw_selftest_wide_bvh.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.fw_selftest_bvh_build.restype = C.c_int
     lib.fw_selftest_bvh_build.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    lib.fw_selftest_bvh_trees.restype = C.c_int
+    lib.fw_selftest_bvh_trees.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     lib.fw_init.restype = C.c_int
     lib.fw_init.argtypes = [C.c_int, C.c_uint64]
     lib.fw_trace_rays.restype = C.c_int
@@ -148,6 +150,21 @@ def selftest_bvh_build(boxes, threads):
     st = (C.c_uint32 * 4)()
     _check(lib, lib.fw_selftest_bvh_build(b.ctypes.data, b.shape[0], int(threads), h, st))
     return int(h[0]), int(h[1]), dict(median_nodes=int(st[0]), median_depth=int(st[1]), sah_nodes=int(st[2]), sah_depth=int(st[3]))
+
+
+def selftest_bvh_trees(boxes, device):
+    """fw_selftest_bvh_trees: both trees over n boxes (n x 6 float32), built on GPU `device` or, for device = -1, by the host builders.
+    -> (median-split nodes, SAH nodes, stats): node arrays of shape (nodes, 8) float32, stats = [median nodes, depth, SAH nodes, depth]"""
+    lib = load()
+    b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+    n = b.shape[0]
+    cap = max(1, 2 * n - 1) * 8
+    ref = np.zeros(cap, np.float32)
+    sah = np.zeros(cap, np.float32)
+    st = (C.c_uint32 * 4)()
+    _check(lib, lib.fw_selftest_bvh_trees(int(device), b.ctypes.data, n, ref.ctypes.data, sah.ctypes.data, st))
+    stats = np.array(list(st), np.uint32)
+    return ref[: int(stats[0]) * 8].reshape(-1, 8), sah[: int(stats[2]) * 8].reshape(-1, 8), stats
 
 
 def selftest_arith(n, seed=1, mode=0, device=0):

@@ -9,6 +9,7 @@
 // No CPU rendering path exists here: without a HIP device every entry point fails with FW_ERR_NO_DEVICE.
 #include "../../include/firework_hip.h"
 #include "fw_device.h"
+#include "fw_build.h"
 
 #include <algorithm>
 #include <atomic>
@@ -47,6 +48,7 @@ struct Options {
     int soft_shear_log2 = 5, exact_shear_log2 = 10; double exact_far_x = 256.0;   // SOFT_SHEAR_LOG2 (0: off), EXACT_SHEAR_LOG2, EXACT_FAR_X: the flag rules' thresholds (tools/flag_margin.py)
     double wide_node_cost = 0.0005;   // WIDE_NODE_COST: the constant a wide node costs in the collapse, in root areas (wide_convert)
     int wide = -1;                // WIDE=0|f32|q8: no wide nodes / force an encoding (-1: by size)
+    int build = -1;               // BUILD=host|device: where a scene's trees are built (-1: by size, BUILD_MIN)
     long waves = 0;               // WAVES=n wave queues (0: the library's choice)
     long long paths_per_batch = 0;
     std::string dump_path;        // DUMP_PATH=file (tools/diverge.py)
@@ -56,7 +58,7 @@ struct Options {
 #endif
 };
 const char *const OPTION_NAMES[] = {"BVH", "NO_EXACT", "EXACT_ALL", "EXACT_FORM", "NO_DEFER", "NO_HIT4", "NO_HOIST", "NO_LDS_TABLES", "NO_LDS_TREES", "NO_LDS_TRIS",
-                                    "NO_SHORT_RAYS", "NO_TILE_ORDER", "NO_ZERO_SKIP", "DEP_PIXEL_MAJOR", "DEP_SLOT_MAJOR", "NO_CHAIN", "EXACT_PRODUCT", "PHASE_LOCK", "GRAPH", "SOFT_SHEAR_LOG2", "EXACT_SHEAR_LOG2", "EXACT_FAR_X", "WIDE_NODE_COST", "TRACE", "STREAMS", "WIDE", "WAVES",
+                                    "NO_SHORT_RAYS", "NO_TILE_ORDER", "NO_ZERO_SKIP", "DEP_PIXEL_MAJOR", "DEP_SLOT_MAJOR", "NO_CHAIN", "EXACT_PRODUCT", "PHASE_LOCK", "GRAPH", "SOFT_SHEAR_LOG2", "EXACT_SHEAR_LOG2", "EXACT_FAR_X", "WIDE_NODE_COST", "TRACE", "STREAMS", "WIDE", "BUILD", "WAVES",
                                     "PATHS_PER_BATCH", "DUMP_PATH",
 #if FW_AB
                                     "FUSED", "TLAS_REFILL", "SHADE_LIST", "NO_SHADE_DEFER", "STAGGER", "DEBUG_WIDE_LEVELS",
@@ -92,6 +94,10 @@ bool option_apply(Options &o, const char *name, const char *v) {      // v == nu
     else if (n == "TRACE") o.trace = on();
     else if (n == "STREAMS") o.streams = (int)std::max<long long>(0, num());
     else if (n == "WIDE") o.wide = !v ? -1 : (std::strcmp(v, "0") == 0 ? 0 : (std::strcmp(v, "f32") == 0 ? 1 : (std::strcmp(v, "q8") == 0 ? 2 : -1)));
+    else if (n == "BUILD") {
+        if (v && std::strcmp(v, "host") != 0 && std::strcmp(v, "device") != 0) return false;
+        o.build = !v ? -1 : (std::strcmp(v, "device") == 0 ? 1 : 0);
+    }
     else if (n == "WAVES") o.waves = (long)std::max<long long>(0, num());
     else if (n == "PATHS_PER_BATCH") o.paths_per_batch = std::max<long long>(0, num());
     else if (n == "DUMP_PATH") o.dump_path = v ? v : "";
@@ -439,6 +445,25 @@ void sah_build(FlatBvh &out, const std::vector<Box> &boxes, BuildPool *shared = 
     const Centers ce = centers_of(boxes, pool);
     Box root;
     sah_build_rec(out, boxes, ce, idx.data(), idx.size(), 0, root, pool);
+}
+
+// ---- where a tree is built.  fw_build.hip restates both builders on the device, level by level, with the same nodes as the result
+// (tests/test_gpu_device_build.py); BUILD=host|device picks one, the default takes the device from BUILD_MIN items on: measured against 64
+// host threads, the device loses at 20 k triangles (14 against 10 ms of scene creation) and wins from 200 k (50 against 80 ms; DESIGN.md §9.4,
+// profiles/device_build.txt).  Every tree of a scene is built through build_tree.  device < 0: the host.  Errors come back as status codes.
+constexpr size_t BUILD_MIN = 100000;
+static_assert(sizeof(Box) == 24, "Box = 6 floats: fw::device_build_tree reads an array of them");
+int build_tree(int device, fw::BuildTree kind, const std::vector<Box> &boxes, FlatBvh &out, BuildPool *pool, fw::DeviceBuildTimes *times) {
+    const int where = options().build;
+    if (device >= 0 && !boxes.empty() && (where == 1 || (where == -1 && boxes.size() >= BUILD_MIN))) {
+        std::string msg;
+        const int rc = fw::device_build_tree(device, kind, reinterpret_cast<const float *>(boxes.data()), (uint32_t)boxes.size(), out.nodes, out.depth, times, msg);
+        return rc ? fail(rc, msg) : FW_OK;
+    }
+    if (kind == fw::BUILD_MEDIAN) {
+        try { (void)bvh_build(out, boxes, pool); } catch (NanError &) { return fail(FW_ERR_NAN_BBOX, "Float comparison failed in BVH constructor"); }
+    } else sah_build(out, boxes, pool);
+    return FW_OK;
 }
 
 // ---- the tree as walked on the device: pair nodes (fw_device.h), converted from a FlatBvh.  A DoubleLeaf becomes a
@@ -898,6 +923,8 @@ struct Flattener {
     bool wide_ok[2] = {true, true};
     std::vector<ShapeParams> mesh_cache;  // per shape index: a TriangleMesh shape referenced by several objects (or by a medium
     std::vector<uint8_t> mesh_cached;     // and an object) is flattened and built once, every user shares its triangles and BLAS
+    int device = -1;                      // where build_tree may build the meshes' trees
+    fw::DeviceBuildTimes dev_times;       // the device builds' upload / kernel / copy-back times (FIREWORK_TRACE)
     double ms_gather = 0, ms_ref = 0, ms_gate = 0, ms_sah = 0, ms_pair = 0, ms_wide = 0;   // where mesh_params spends its time (FIREWORK_TRACE=1, tools/big_mesh.py)
 
     int check_material(int32_t m) const { return (m < 0 || (uint32_t)m >= d->n_materials) ? FW_ERR_BAD_ARG : FW_OK; }
@@ -1013,10 +1040,13 @@ struct Flattener {
         // Round 5: the reference tree and the walked tree are built at the same time, each in parallel below its big nodes (BuildPool: one budget
         // of host threads for both), and the three forms of the walked tree — pair nodes, wide f32, wide q8 — are converted side by side.
         FlatBvh local, walked;
-        bool nan_error = false;
+        int ref_rc = FW_OK;
+        std::string ref_msg;
         std::exception_ptr ref_error;
         const bool two = n_tris >= PAR_SUBTREE_MIN && pool.take(1) == 1;
-        auto build_reference = [&] { try { (void)bvh_build(local, boxes, &pool); } catch (NanError &) { nan_error = true; } catch (...) { ref_error = std::current_exception(); } };
+        auto build_reference = [&] {
+            try { if ((ref_rc = build_tree(device, fw::BUILD_MEDIAN, boxes, local, &pool, &dev_times)) != FW_OK) ref_msg = g_last_error; }
+            catch (...) { ref_error = std::current_exception(); } };
         std::thread ref_thread;
         if (two) ref_thread = std::thread(build_reference); else build_reference();
         // the mesh's own box = the reference root's: the union of every triangle's box (fmin / fmax: the same in any order)
@@ -1031,12 +1061,15 @@ struct Flattener {
         }
         const bool sah = use_sah();
         std::exception_ptr sah_error;
-        if (sah) { try { sah_build(walked, wboxes, &pool); } catch (...) { sah_error = std::current_exception(); } }
+        int sah_rc = FW_OK;
+        std::string sah_msg;
+        if (sah) { try { if ((sah_rc = build_tree(device, fw::BUILD_SAH, wboxes, walked, &pool, &dev_times)) != FW_OK) sah_msg = g_last_error; } catch (...) { sah_error = std::current_exception(); } }
         lap(ms_sah);
         if (two) { ref_thread.join(); pool.give(1); }
-        if (nan_error) return fail(FW_ERR_NAN_BBOX, "Float comparison failed in BVH constructor");
+        if (ref_rc) return fail(ref_rc, ref_msg);
         if (ref_error) std::rethrow_exception(ref_error);
         if (sah_error) std::rethrow_exception(sah_error);
+        if (sah_rc) return fail(sah_rc, sah_msg);
         {   // ties are resolved by the reference tree's in-order rank, whatever tree is traversed
             std::vector<uint32_t> rk = reference_ranks(local, n_tris);
             tri_rank.insert(tri_rank.end(), rk.begin(), rk.end());
@@ -1117,6 +1150,8 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
     const auto tr0 = now();
 
     Flattener fl{desc};
+    fl.device = device;
+    fw::DeviceBuildTimes dev_times;           // the TLAS builds (the meshes' trees: fl.dev_times)
     std::vector<float> objs((size_t)desc->n_objects * fw::OBJ_Q * 4, 0.f);
     std::vector<Box> world(desc->n_objects), true_world(desc->n_objects);
     std::vector<uint32_t> obj_ref_blas(desc->n_objects, 0xffffffffu);
@@ -1186,7 +1221,7 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
         if (obj_bits + prim_bits > 32) return fail(FW_ERR_UNSUPPORTED, "objects x triangles-per-mesh exceed the 32-bit hit code");
     }
     FlatBvh tlas;
-    try { bvh_build(tlas, world); } catch (NanError &) { return fail(FW_ERR_NAN_BBOX, "Float comparison failed in BVH constructor"); }
+    if (int brc = build_tree(device, fw::BUILD_MEDIAN, world, tlas, nullptr, &dev_times)) return brc;
     std::vector<uint32_t> obj_rank = reference_ranks(tlas, desc->n_objects);
     uint32_t ref_tlas_nodes = tlas.count();
     const std::vector<float> ref_tlas = tlas.nodes;          // the reference's own tree: what k_extend_exact walks
@@ -1274,12 +1309,12 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
     }
     if (use_sah()) {
         FlatBvh sah;
-        if (hoisted.empty()) sah_build(sah, build_boxes);
+        if (hoisted.empty()) { if (int brc = build_tree(device, fw::BUILD_SAH, build_boxes, sah, nullptr, &dev_times)) return brc; }
         else {
             std::vector<Box> sub; std::vector<uint32_t> ids;
             for (uint32_t i = 0; i < desc->n_objects; i++)
                 if (std::find(hoisted.begin(), hoisted.end(), i) == hoisted.end()) { sub.push_back(build_boxes[i]); ids.push_back(i); }
-            sah_build(sah, sub);
+            if (int brc = build_tree(device, fw::BUILD_SAH, sub, sah, nullptr, &dev_times)) return brc;
             for (uint32_t i = 0; i < sah.count(); i++) {      // leaf items: positions in `sub` -> object ids
                 float *nd = &sah.nodes[(size_t)i * 8];
                 uint32_t A, B; std::memcpy(&A, nd + 3, 4); std::memcpy(&B, nd + 7, 4);
@@ -1443,8 +1478,12 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
     }
     if (trace) fprintf(stderr, "[firework] scene_create: build %.2f ms, blob %.2f ms (%zu B), alloc %.2f ms (%s), upload launch %.2f ms\n",
                        tr_build, tr_blob, total, tr_alloc, reused ? "cached" : "hipMalloc", ms_since(tr3));
-    if (trace && !fl.tri.empty()) fprintf(stderr, "[firework] scene_create: meshes (%zu triangles, %d host threads): gather %.2f ms | SAH tree, the reference tree beside it %.2f | wait for the reference tree + ranks %.2f | gate boxes %.2f | pair + wide f32 + wide q8 side by side %.2f\n",
+    if (trace && !fl.tri.empty() && fl.dev_times.kernel_ms == 0) fprintf(stderr, "[firework] scene_create: meshes (%zu triangles, %d host threads): gather %.2f ms | SAH tree, the reference tree beside it %.2f | wait for the reference tree + ranks %.2f | gate boxes %.2f | pair + wide f32 + wide q8 side by side %.2f\n",
                                           fl.tri.size() / 12, host_build_threads(), fl.ms_gather, fl.ms_sah, fl.ms_ref, fl.ms_gate, fl.ms_pair + fl.ms_wide);
+    if (trace && !fl.tri.empty() && fl.dev_times.kernel_ms > 0) fprintf(stderr, "[firework] scene_create: meshes (%zu triangles, trees on the device): gather %.2f ms | both trees %.2f (upload %.2f | kernels %.2f | copy back %.2f) | wait + ranks %.2f | gate boxes %.2f | pair + wide f32 + wide q8 side by side %.2f\n",
+                                          fl.tri.size() / 12, fl.ms_gather, fl.ms_sah, fl.dev_times.upload_ms, fl.dev_times.kernel_ms, fl.dev_times.copy_ms, fl.ms_ref, fl.ms_gate, fl.ms_pair + fl.ms_wide);
+    if (trace && dev_times.kernel_ms > 0) fprintf(stderr, "[firework] scene_create: TLAS trees on the device (%u objects): upload %.2f ms | kernels %.2f | copy back %.2f\n",
+                                                  desc->n_objects, dev_times.upload_ms, dev_times.kernel_ms, dev_times.copy_ms);
     if (rc) { delete sc; return rc; }
     const uint8_t *base = (const uint8_t *)sc->data.p;
     fw::DScene &d = sc->d;
@@ -2372,7 +2411,11 @@ int fw_set_option(const char *name, const char *value) {
     std::lock_guard<std::mutex> g(g_opt_mu);
     if (!name) { g_opt = options_from_env(); return FW_OK; }          // back to what the environment said
     const char *n = std::strncmp(name, "FIREWORK_", 9) == 0 ? name + 9 : name;
-    if (!option_apply(g_opt, n, value)) return fail(FW_ERR_BAD_ARG, std::string("unknown option ") + name);
+    if (!option_apply(g_opt, n, value)) {
+        bool known = false;
+        for (int k = 0; OPTION_NAMES[k] && !known; k++) known = std::strcmp(OPTION_NAMES[k], n) == 0;
+        return fail(FW_ERR_BAD_ARG, std::string(known ? "bad value for option " : "unknown option ") + name);
+    }
     return FW_OK;
 }
 
@@ -2415,6 +2458,38 @@ int fw_selftest_bvh_build(const float *boxes, uint32_t n, int threads, uint64_t 
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_selftest_bvh_build"); }
 }
 
+// Diagnostic: both trees over n item boxes, built on GPU `device` (fw_build.hip) or, for device = -1, by the host builders; the node arrays
+// (8 floats per node, up to 2n - 1 nodes each) are written to ref_nodes / sah_nodes, stats = nodes and depth of each.  The device build
+// must equal the host's bit for bit (tests/test_gpu_device_build.py).
+int fw_selftest_bvh_trees(int device, const float *boxes, uint32_t n, float *ref_nodes, float *sah_nodes, uint32_t stats[4]) {
+    if (!boxes || n == 0 || !ref_nodes || !sah_nodes || !stats || device < -1 || n > fw::NODE_MASK) return fail(FW_ERR_BAD_ARG, "bad argument");
+    try {
+        FlatBvh ref, sah;
+        if (device >= 0) {
+            int ndev = 0;
+            if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible"); }
+            if (device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+            HIPCHK(hipSetDevice(device));
+            std::string msg;
+            int rc = fw::device_build_tree(device, fw::BUILD_MEDIAN, boxes, n, ref.nodes, ref.depth, nullptr, msg);
+            if (!rc) rc = fw::device_build_tree(device, fw::BUILD_SAH, boxes, n, sah.nodes, sah.depth, nullptr, msg);
+            if (rc) return fail(rc, msg);
+        } else {
+            std::vector<Box> b(n);
+            for (uint32_t i = 0; i < n; i++) b[i] = Box{{boxes[6 * i], boxes[6 * i + 1], boxes[6 * i + 2]}, {boxes[6 * i + 3], boxes[6 * i + 4], boxes[6 * i + 5]}};
+            if (int rc = build_tree(-1, fw::BUILD_MEDIAN, b, ref, nullptr, nullptr)) return rc;
+            if (int rc = build_tree(-1, fw::BUILD_SAH, b, sah, nullptr, nullptr)) return rc;
+        }
+        if (ref.count() > 2 * (size_t)n - 1 || sah.count() > 2 * (size_t)n - 1) return fail(FW_ERR_HIP, "tree larger than 2n - 1 nodes");
+        std::memcpy(ref_nodes, ref.nodes.data(), ref.nodes.size() * 4);
+        std::memcpy(sah_nodes, sah.nodes.data(), sah.nodes.size() * 4);
+        stats[0] = ref.count(); stats[1] = ref.depth; stats[2] = sah.count(); stats[3] = sah.depth;
+        return FW_OK;
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_selftest_bvh_trees"); }
+}
+
 #if FW_AB
 int fw_debug_ab(void) { return 1; }      // present only in the A/B build: tests of the alternative kernels look for it
 #endif
@@ -2454,7 +2529,7 @@ void fw_release_workspace(int device) {
     Workspace *ws = workspace_for(device);
     if (!ws) return;
     std::lock_guard<std::mutex> g(ws->mu);
-    if (hipSetDevice(device) == hipSuccess) ws->release();
+    if (hipSetDevice(device) == hipSuccess) { ws->release(); fw::device_build_release(device); }
 }
 
 void fw_scene_destroy(fw_scene *scene) {

@@ -361,6 +361,8 @@ int fw_selftest_libm(int device, int fn, uint32_t n, const float *x, const float
    compared bit for bit in tests/) — except the diagnostics NO_EXACT / EXACT_ALL.  Names:
      BVH=median            walk the reference's own median-split topology instead of the SAH tree (parity / A-B mode)
      WIDE=0|f32|q8         no wide nodes (the pair-node kernels) / force an encoding of the wide nodes
+     BUILD=host|device     where a scene's trees are built: the host builders, or their restatement on the device (the same nodes bit for
+                           bit); default: the device for a tree of 100 000 items or more.  Other values: FW_ERR_BAD_ARG
      EXACT_ALL=1, NO_EXACT, EXACT_FORM=lane|wave      every ray / no ray through the literal reference walk; its form
      STREAMS=n, WAVES=n, PATHS_PER_BATCH=n            batches in flight, wave queues, pool size
      NO_DEFER NO_HIT4 NO_HOIST NO_LDS_TABLES NO_LDS_TREES NO_LDS_TRIS NO_SHORT_RAYS NO_TILE_ORDER NO_ZERO_SKIP
@@ -387,6 +389,13 @@ int fw_selftest_wide_bvh(const float *boxes, uint32_t n, int format, uint32_t *v
    two node arrays, stats = nodes and depth of the median tree, nodes and depth of the SAH tree.  Scene creation builds a mesh's trees in
    parallel (the reference builds inside its timed region, main.rs:40-44, on one thread); any thread count must give the one-thread trees. */
 int fw_selftest_bvh_build(const float *boxes, uint32_t n, int threads, uint64_t hashes[2], uint32_t stats[4]);
+
+/* Diagnostic: the same two trees over n item boxes (n x 6 floats), built on GPU `device` by the device builders, or by the host builders
+   for device = -1.  ref_nodes / sah_nodes receive the node arrays of the median-split and the SAH tree (8 floats per node: min.xyz, A,
+   max.xyz, B; depth-first order; at most (2n - 1) x 8 floats each); stats = nodes and depth of each, as fw_selftest_bvh_build gives them.
+   The device's trees equal the host's bit for bit.  Errors: FW_ERR_BAD_ARG (n = 0, a null pointer, device < -1 or out of range),
+   FW_ERR_NO_DEVICE (device >= 0 without a GPU), FW_ERR_NAN_BBOX (a centre the median tree compares is NaN), FW_ERR_OOM, FW_ERR_HIP. */
+int fw_selftest_bvh_trees(int device, const float *boxes, uint32_t n, float *ref_nodes, float *sah_nodes, uint32_t stats[4]);
 
 #ifdef __cplusplus
 }
