@@ -6,7 +6,8 @@ Same fixed view as main.rs: camera (0,30,50) -> (0,0,0), fov 40, 960x540, use_bv
 `Finished Rendering in {} s`.  Without `-o` the reference opens a minifb window; a GPU node has no display,
 so `-o` is required here.  Extra flags (not in the reference): --width/--height/--seed/--device, and
 --progressive N (write the image after each of N passes) / --checkpoint FILE (save the accumulation buffer after every
-pass and resume from it: the finished image is bit-identical to an uninterrupted render)."""
+pass and resume from it: the finished image is bit-identical to an uninterrupted render), --adaptive TOL [--min-samples M]
+(adaptive sampling up to -s samples per pixel; not with --progressive / --checkpoint)."""
 import argparse
 import sys
 import time
@@ -24,7 +25,12 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--progressive", type=int, default=0, metavar="N", help="render in N passes, saving the image after each")
     ap.add_argument("--checkpoint", default=None, metavar="FILE", help=".npz accumulation checkpoint: written after every pass, resumed from if present")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="TOL",
+                    help="adaptive sampling: render each pixel until its standard error is at most TOL x its brightness (-s is the cap)")
+    ap.add_argument("--min-samples", type=int, default=16, metavar="M", help="with --adaptive: the samples every pixel gets first")
     opt = ap.parse_args(argv)
+    if opt.adaptive is not None and (opt.progressive > 0 or opt.checkpoint):
+        ap.error("--adaptive cannot be combined with --progressive or --checkpoint")
 
     from . import _lib
     from .api import CameraSettings, Renderer, save_image
@@ -37,7 +43,11 @@ def main(argv=None):
     renderer = (Renderer.default().width(opt.width).height(opt.height).samples(opt.samples).use_bvh(True)
                 .camera(camera).seed(opt.seed))
     start = time.time()
-    if opt.progressive > 0 or opt.checkpoint:
+    if opt.adaptive is not None:
+        res = renderer.render_adaptive(scene, opt.adaptive, opt.min_samples, device=opt.device)
+        render = res.rgb8
+        print(f"adaptive: {len(res.rounds)} rounds, active pixels {res.rounds}, mean {float(res.counts.mean()):.1f} spp (cap {opt.samples})")
+    elif opt.progressive > 0 or opt.checkpoint:
         render = None
         for k, res in enumerate(renderer.render_progressive(scene, max(1, opt.progressive), device=opt.device, checkpoint=opt.checkpoint)):
             render = res.rgb8

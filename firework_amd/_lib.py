@@ -79,6 +79,9 @@ def load(preload=False, device=None):
     lib.fw_trace_rays.argtypes = [C.c_void_p, C.POINTER(A.fw_trace_params), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(A.fw_stats)]
     lib.fw_camera_rays.restype = C.c_int
     lib.fw_camera_rays.argtypes = [C.POINTER(A.fw_render_params), C.c_int, C.c_uint32, C.c_void_p]
+    lib.fw_render_adaptive.restype = C.c_int
+    lib.fw_render_adaptive.argtypes = [C.c_void_p, C.POINTER(A.fw_render_params), C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(A.fw_stats)]
     if lib.fw_abi_version() != A.FW_ABI_VERSION:
         raise FireworkError(A.FW_ERR_BAD_ARG, "ABI version mismatch between _abi.py and libfirework_hip.so")
     _lib = lib
@@ -279,6 +282,44 @@ class DeviceScene:
         _check(lib, lib.fw_render_progressive(self.handle, C.byref(p), int(first_sample), accum.ctypes.data, rgb8.ctypes.data,
                                               gam.ctypes.data, lin.ctypes.data, C.byref(st)))
         return RenderResult(rgb8, gam, lin, st.as_dict(), p.width, p.height)
+
+    def render_adaptive(self, renderer, tolerance, min_samples=16, out=None, stream=None):
+        """fw_render_adaptive: the whole frame, each pixel rendered until its noise estimate meets `tolerance` or its count reaches the
+        renderer's samples (the cap).  Returns an AdaptiveResult (host numpy arrays).  out: a dict of contiguous device tensors on this
+        scene's device to fill instead (keys rgb8 (n, 3) uint8, gamma, linear (n, 3) float32, accum, moments (n, 4) float32,
+        round_pixels (32,) int32; any may be missing), launched on `stream` (default: the current torch stream); returns the
+        AdaptiveResult with those tensors in place of arrays."""
+        from .api import AdaptiveResult
+        lib = self._lib
+        p = renderer.to_params(None)
+        n = p.width * p.height
+        st = A.fw_stats()
+        if out is not None:
+            import torch
+            want = dict(rgb8=((n, 3), torch.uint8), gamma=((n, 3), torch.float32), linear=((n, 3), torch.float32),
+                        accum=((n, 4), torch.float32), moments=((n, 4), torch.float32), round_pixels=((32,), torch.int32))
+            for k, t in out.items():
+                shape, dt = want[k]
+                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device.type != "cuda" or (t.device.index or 0) != self.device:
+                    raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor of shape {shape} on cuda:{self.device}")
+            p.outputs_on_device = 1
+            if stream is None:
+                stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+            p.stream = C.c_void_p(stream) if stream else None
+            ptr = {k: (out[k].data_ptr() if k in out else None) for k in want}
+            _check(lib, lib.fw_render_adaptive(self.handle, C.byref(p), float(tolerance), int(min_samples), ptr["accum"], ptr["moments"],
+                                               ptr["rgb8"], ptr["gamma"], ptr["linear"], ptr["round_pixels"], C.byref(st)))
+            return AdaptiveResult(out.get("rgb8"), out.get("gamma"), out.get("linear"), out.get("accum"), out.get("moments"),
+                                  out.get("round_pixels"), st.as_dict(), p.width, p.height)
+        rgb8 = np.empty((n, 3), np.uint8)
+        gam = np.empty((n, 3), np.float32)
+        lin = np.empty((n, 3), np.float32)
+        acc = np.empty((n, 4), np.float32)
+        mom = np.empty((n, 4), np.float32)
+        rounds = np.zeros(32, np.uint32)
+        _check(lib, lib.fw_render_adaptive(self.handle, C.byref(p), float(tolerance), int(min_samples), acc.ctypes.data, mom.ctypes.data,
+                                           rgb8.ctypes.data, gam.ctypes.data, lin.ctypes.data, rounds.ctypes.data, C.byref(st)))
+        return AdaptiveResult(rgb8, gam, lin, acc, mom, rounds, st.as_dict(), p.width, p.height)
 
     def trace(self, rays, use_bvh, seed=0, key_base=0, rays_per_batch=0, time_kernels=False, stats=None):
         """fw_trace_rays: one root.hit(ray, 0.001, 2e9) per ray.  rays: (n, 6) origin + direction.

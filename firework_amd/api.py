@@ -772,6 +772,40 @@ class RenderResult:
         return self.rgb8.reshape(self.height, self.width, 3)
 
 
+@dataclass
+class AdaptiveResult:
+    """fw_render_adaptive's outputs (numpy arrays, or the caller's device tensors): rgb8 / gamma / linear (N, 3) as RenderResult, each
+    pixel resolved with its own sample count; accum (N, 4) sums as fw_render_progressive keeps them; moments (N, 4) sums of squares and
+    .w = the pixel's sample count; round_pixels (32,) the active pixels of each round, then zeros."""
+    rgb8: object
+    gamma: object
+    linear: object
+    accum: object
+    moments: object
+    round_pixels: object
+    stats: dict
+    width: int
+    height: int
+
+    @property
+    def counts(self):
+        """(H, W) uint32: every pixel's final sample count"""
+        m = self.moments
+        if type(m).__module__.startswith("torch"):
+            import torch
+            return m[:, 3].to(torch.int64).reshape(self.height, self.width)
+        return m[:, 3].astype(np.uint32).reshape(self.height, self.width)
+
+    @property
+    def rounds(self):
+        """the active pixels of each round that ran"""
+        r = [int(x) for x in (self.round_pixels.tolist() if self.round_pixels is not None else [])]
+        return [x for x in r if x > 0]
+
+    def image(self) -> np.ndarray:
+        return self.rgb8.reshape(self.height, self.width, 3)
+
+
 class Renderer:
     """src/render.rs:59-218.  Builder methods carry the reference's names; read the current
     values from `.settings`."""
@@ -910,6 +944,19 @@ class Renderer:
                 yield res
         finally:
             ds.close()
+
+    def render_adaptive(self, scene, tolerance: float, min_samples: int = 16, device: int = 0, out: Optional[dict] = None) -> "AdaptiveResult":
+        """Adaptive sampling (not in the reference; fw_render_adaptive): every pixel gets `min_samples` samples, then the pixels whose
+        noise estimate does not yet meet `tolerance` go on in rounds that double their count, up to settings["samples"].  Each pixel's
+        outputs equal bit for bit a fixed-count render at its final count (AdaptiveResult.counts).  `scene`: a Scene, a SceneDesc or an
+        uploaded _lib.DeviceScene; out: device tensors to fill (see _lib.DeviceScene.render_adaptive)."""
+        from . import _lib
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            return ds.render_adaptive(self, tolerance, min_samples, out=out)
+        finally:
+            if ds is not scene:
+                ds.close()
 
     def render(self, scene, device: int = 0) -> np.ndarray:
         """`pub fn render(&self, scene: Scene) -> Vec<Color>` (render.rs:109): (W*H, 3) uint8, row 0 = top."""

@@ -271,6 +271,16 @@ void launch_selftest_libm(hipStream_t stream, int fn, uint32_t n, const float *x
 void launch_accumulate(const LaunchCfg &, const DFrame &, const float4 *sample_rad, float4 *accum);
 void launch_resolve(const LaunchCfg &, const DFrame &, const float4 *accum, uint32_t total_spp, float gamma,
                     uint8_t *rgb8, float *gamma_rgb, float *linear_rgb);
+// fw_render_adaptive (fw_kernels.hip, "fw_render_adaptive's decision and compaction"): a round's accumulation into whole-frame sums and
+// squares, the convergence rule + stable compaction of the survivors into out_ids (their number into *count), and the final resolve with
+// each pixel's own sample count.  mask: (n + 63) / 64 words; block_counts: adaptive_select_blocks(n) words.
+constexpr uint32_t ADAPTIVE_MAX_BLOCKS = 1024;
+void launch_accumulate_adaptive(const LaunchCfg &, const DFrame &, const float4 *sample_rad, float4 *accum, float4 *moments);
+uint32_t adaptive_select_blocks(uint32_t n);
+void launch_adaptive_select(hipStream_t stream, const uint32_t *ids, uint32_t n, const float4 *accum, float4 *moments, uint32_t n_samples, bool may_continue,
+                            float tol, unsigned long long *mask, uint32_t *block_counts, uint32_t *out_ids, uint32_t *count);
+void launch_resolve_adaptive(hipStream_t stream, int n_cus, uint32_t n, const float4 *accum, const float4 *moments, float gamma,
+                             uint8_t *rgb8, float *gamma_rgb, float *linear_rgb);
 
 constexpr int BLOCK = 256;
 

@@ -12,6 +12,9 @@
 //   k_accumulate  `total_color += color(..)` in sample order      render.rs:181
 //   k_resolve     /spp, powf(1/gamma), clamp, Color::from          render.rs:184-190, util.rs:14-23
 //   k_bounce      k_extend + k_shade of one segment in one launch (FIREWORK_FUSED=1; measured slower, kept for A/B)
+//   k_accumulate_adaptive, k_adaptive_select / k_adaptive_compact, k_resolve_adaptive
+//                 fw_render_adaptive (no counterpart in the reference): k_accumulate's walk plus the squares, the
+//                 convergence rule and the stable compaction of the surviving pixels, the per-pixel-count resolve
 //
 // One lane = one path.  Path state lives in HBM as SoA arrays.  The path pool is split into WAVE-PRIVATE
 // queues: wavefront w owns slots [w*cap, (w+1)*cap) of every array and compacts its
@@ -3497,79 +3500,17 @@ __global__ __launch_bounds__(BLOCK) void k_count_deposits(const uint32_t *__rest
 // One thread per pixel sums its samples in sample order (the reference's order; float addition does not reassociate).
 // Single-wave workgroups and 16 loads in flight per thread keep a 1/8-frame tile share (32 Ki pixels = 512 waves for
 // 1024 SIMDs) near the HBM rate: 0.49 -> see DESIGN §7.
+// k_accumulate_adaptive (fw_render_adaptive's rounds) walks the same records in the same order (fw_accumulate_walk.inc) and also sums
+// their squares; its accum and moments are whole frames indexed by pixel id (f.pixel_ids = the round's active pixels, or none: row order).
 __global__ __launch_bounds__(WB) void k_accumulate(DFrame f, const float4 *__restrict__ sample_rad, float4 *__restrict__ accum) {
-    // linear id of (sample s, pixel p) = s * n_pixels + p = (c * n_waves + w) * 64 + lane -> home = w * cap + c * 64 + lane;
-    // one sample further adds n_pixels = 64 * A + B to the linear id: (w, c, lane) are advanced without divisions
-    const uint32_t A = f.n_pixels >> 6, B = f.n_pixels & 63u, A_div = A / f.q_n_waves, A_mod = A % f.q_n_waves;
-    for (uint32_t p = blockIdx.x * WB + threadIdx.x; p < f.n_pixels; p += gridDim.x * WB) {
-        float4 a = accum[p];
-        uint32_t lane = p & 63u, c = (p >> 6) / f.q_n_waves, w = (p >> 6) % f.q_n_waves;
-        auto home_then_advance = [&]() {
-            const uint32_t home = (w << (f.q_shift + 6u)) | (c << 6) | lane;
-            lane += B;
-            const uint32_t carry = lane >> 6; lane &= 63u;
-            w += A_mod + carry; c += A_div;
-            if (w >= f.q_n_waves) { w -= f.q_n_waves; c++; }
-            return home;
-        };
-        uint32_t s = 0;
-        if (f.skip_zero_deposits) {
-            // black environment: only the slots whose bit is set hold a record (k_shade), all others contribute an exact +0:
-            // 1 bit instead of 16 bytes per sample is read, and nobody had to write the zeros
-            if (!f.dep_pixel_major) {     // slot-major bits (whole frames): the word of sample s is that of its home slot
-                for (; s + 16u <= f.spp_batch; s += 16u) {
-                    uint32_t h[16], bw[16];
-#pragma unroll
-                    for (int k = 0; k < 16; k++) { h[k] = home_then_advance(); bw[k] = f.dep_bits[h[k] >> 5]; }
-#pragma unroll
-                    for (int k = 0; k < 16; k++) if ((bw[k] >> (h[k] & 31u)) & 1u) { const float4 v = sample_rad[h[k]]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-                }
-                for (; s < f.spp_batch; s++) {
-                    const uint32_t h = home_then_advance();
-                    if ((f.dep_bits[h >> 5] >> (h & 31u)) & 1u) { const float4 v = sample_rad[h]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-                }
-                accum[p] = a;
-                continue;
-            }
-            // pixel-major bits (dep_bit_of): the pixel's bits are [p * spp, (p + 1) * spp) — eight words per round trip, then
-            // one record per set bit, in sample order
-            const uint32_t b0 = p * f.spp_batch, b1 = b0 + f.spp_batch, j_last = (b1 - 1u) >> 5;
-            for (uint32_t j0 = b0 >> 5; j0 <= j_last; j0 += 8u) {
-                uint32_t wd[8];
-#pragma unroll
-                for (uint32_t k = 0; k < 8u; k++) wd[k] = (j0 + k <= j_last) ? f.dep_bits[j0 + k] : 0u;
-#pragma unroll
-                for (uint32_t k = 0; k < 8u; k++) {
-                    const uint32_t j = j0 + k;
-                    uint32_t word = wd[k];
-                    if (j == (b0 >> 5)) word &= ~0u << (b0 & 31u);
-                    if (j == (b1 >> 5)) word &= (1u << (b1 & 31u)) - 1u;
-                    while (word) {
-                        const uint32_t bit = (uint32_t)__ffs((int)word) - 1u;
-                        word &= word - 1u;
-                        const uint32_t lin = (j * 32u + bit - b0) * f.n_pixels + p;       // s_local * n_pixels + p
-                        const uint32_t g = lin >> 6, cc = g / f.q_n_waves, ww = g - cc * f.q_n_waves;
-                        const float4 v = sample_rad[(ww << (f.q_shift + 6u)) | (cc << 6) | (lin & 63u)];
-                        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-                    }
-                }
-            }
-            accum[p] = a;
-            continue;
-        }
-        for (; s + 16u <= f.spp_batch; s += 16u) {
-            float4 v[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) v[k] = sample_rad[home_then_advance()];
-#pragma unroll
-            for (int k = 0; k < 16; k++) { a.x += v[k].x; a.y += v[k].y; a.z += v[k].z; a.w += v[k].w; }   // render.rs:181: total_color += color(...)
-        }
-        for (; s < f.spp_batch; s++) {
-            float4 v = sample_rad[home_then_advance()];
-            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-        }
-        accum[p] = a;
-    }
+    constexpr bool MOMENTS = false;
+    float4 *const moments = nullptr;
+#include "fw_accumulate_walk.inc"
+}
+__global__ __launch_bounds__(WB) void k_accumulate_adaptive(DFrame f, const float4 *__restrict__ sample_rad, float4 *__restrict__ accum,
+                                                            float4 *__restrict__ moments) {
+    constexpr bool MOMENTS = true;
+#include "fw_accumulate_walk.inc"
 }
 
 // A whole frame is traced in 16x16-tile order, not row order: the 64 paths of a chunk are then a 16x4 block of pixels whose
@@ -3622,19 +3563,106 @@ void launch_scatter_tiles(hipStream_t stream, const uint32_t *ids, uint32_t n, c
 
 __device__ __forceinline__ uint8_t sat_u8(float f) { if (!(f > 0.f)) return 0; if (f >= 255.f) return 255; return (uint8_t)f; }
 
+// One pixel's sums -> its three outputs at index p: k_resolve (one sample count for every pixel) and k_resolve_adaptive (its own each)
+__device__ __forceinline__ void resolve_pixel(float4 a, float spp, float gamma, uint32_t p, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
+    V3 total = mk(a.x, a.y, a.z) / spp;                                           // render.rs:184
+    float ig = fdiv(1.f, gamma);
+    V3 g = mk(fwlm::powf_glibc(total.x, ig), fwlm::powf_glibc(total.y, ig), fwlm::powf_glibc(total.z, ig));           // render.rs:186
+    auto clamp01 = [](float x) { return (x != x) ? x : (x < 0.f ? 0.f : (x > 1.f ? 1.f : x)); };
+    g = mk(clamp01(g.x), clamp01(g.y), clamp01(g.z));                             // render.rs:187
+    if (linear_rgb) { linear_rgb[3 * (size_t)p] = total.x; linear_rgb[3 * (size_t)p + 1] = total.y; linear_rgb[3 * (size_t)p + 2] = total.z; }
+    if (gamma_rgb) { gamma_rgb[3 * (size_t)p] = g.x; gamma_rgb[3 * (size_t)p + 1] = g.y; gamma_rgb[3 * (size_t)p + 2] = g.z; }
+    if (rgb8) { rgb8[3 * (size_t)p] = sat_u8(g.x * 255.99f); rgb8[3 * (size_t)p + 1] = sat_u8(g.y * 255.99f); rgb8[3 * (size_t)p + 2] = sat_u8(g.z * 255.99f); }   // util.rs:14-23
+}
 __global__ __launch_bounds__(BLOCK) void k_resolve(DFrame f, const float4 *__restrict__ accum, uint32_t total_spp, float gamma,
                                                    uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
     for (uint32_t q = blockIdx.x * BLOCK + threadIdx.x; q < f.n_pixels; q += gridDim.x * BLOCK) {
         float4 a = accum[q];
         const uint32_t p = f.scatter_out ? f.pixel_ids[q] : q;                       // output index (the library's tile order is undone here)
-        V3 total = mk(a.x, a.y, a.z) / (float)total_spp;                             // render.rs:184
-        float ig = fdiv(1.f, gamma);
-        V3 g = mk(fwlm::powf_glibc(total.x, ig), fwlm::powf_glibc(total.y, ig), fwlm::powf_glibc(total.z, ig));           // render.rs:186
-        auto clamp01 = [](float x) { return (x != x) ? x : (x < 0.f ? 0.f : (x > 1.f ? 1.f : x)); };
-        g = mk(clamp01(g.x), clamp01(g.y), clamp01(g.z));                             // render.rs:187
-        if (linear_rgb) { linear_rgb[3 * (size_t)p] = total.x; linear_rgb[3 * (size_t)p + 1] = total.y; linear_rgb[3 * (size_t)p + 2] = total.z; }
-        if (gamma_rgb) { gamma_rgb[3 * (size_t)p] = g.x; gamma_rgb[3 * (size_t)p + 1] = g.y; gamma_rgb[3 * (size_t)p + 2] = g.z; }
-        if (rgb8) { rgb8[3 * (size_t)p] = sat_u8(g.x * 255.99f); rgb8[3 * (size_t)p + 1] = sat_u8(g.y * 255.99f); rgb8[3 * (size_t)p + 2] = sat_u8(g.z * 255.99f); }   // util.rs:14-23
+        resolve_pixel(a, (float)total_spp, gamma, p, rgb8, gamma_rgb, linear_rgb);
+    }
+}
+// fw_render_adaptive: a whole frame in pixel order, each pixel divided by its own sample count (moments[p].w = (float)n_p)
+__global__ __launch_bounds__(BLOCK) void k_resolve_adaptive(uint32_t n, const float4 *__restrict__ accum, const float4 *__restrict__ moments, float gamma,
+                                                            uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
+    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < n; p += gridDim.x * BLOCK)
+        resolve_pixel(accum[p], moments[p].w, gamma, p, rgb8, gamma_rgb, linear_rgb);
+}
+
+// ------------------------------------------------------------------------------------------------
+// fw_render_adaptive's decision and compaction.  The active pixels of a round are ids[0, n) (ids == nullptr: pixel i is entry i);
+// block b of the grid owns entries [b * per, (b + 1) * per), per a multiple of BLOCK.
+//   k_adaptive_select : the convergence rule (include/firework_hip.h) for every entry, moments.w = n_samples; one 64-bit ballot of
+//                       the survivors per wave and step into mask[entry / 64], the block's survivor count into block_counts[b]
+//   k_adaptive_compact: each block's offset = the sum of the counts before it, then the survivors' ids in entry order (a stable
+//                       compaction: the list stays a subsequence of round 0's order); the last block writes the total to *count
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool adaptive_converged(float4 S, float4 Q, float nf, float tol) {
+    // IEEE division (the compiler's expansion, not fdiv: sums and squares may lie outside fdiv's exact range), no contraction
+    if (!(isfinite(S.x) && isfinite(S.y) && isfinite(S.z) && isfinite(Q.x) && isfinite(Q.y) && isfinite(Q.z))) return false;
+    const float m_r = S.x / nf, m_g = S.y / nf, m_b = S.z / nf, d = nf - 1.f;
+    const float v_r = (Q.x - S.x * m_r) / d, v_g = (Q.y - S.y * m_g) / d, v_b = (Q.z - S.z * m_b) / d;
+    const float L = ((m_r + m_g) + m_b) / 3.f;
+    const float t = tol * (L > (1.f / 256.f) ? L : (1.f / 256.f));
+    const float lim = (t * t) * nf;
+    return v_r <= lim && v_g <= lim && v_b <= lim;
+}
+__global__ __launch_bounds__(BLOCK) void k_adaptive_select(const uint32_t *__restrict__ ids, uint32_t n, uint32_t per, const float4 *__restrict__ accum,
+                                                           float4 *__restrict__ moments, uint32_t n_samples, uint32_t may_continue, float tol,
+                                                           unsigned long long *__restrict__ mask, uint32_t *__restrict__ block_counts) {
+    __shared__ uint32_t wave_total[BLOCK / 64];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t b0 = blockIdx.x * per, b1 = min(n, b0 + per);
+    const float nf = (float)n_samples;
+    uint32_t count = 0;
+    for (uint32_t base = b0; base < b1; base += BLOCK) {
+        const uint32_t i = base + threadIdx.x;
+        bool keep = false;
+        if (i < b1) {
+            const uint32_t id = ids ? ids[i] : i;
+            float4 m = moments[id];
+            keep = may_continue && !adaptive_converged(accum[id], m, nf, tol);
+            m.w = nf;
+            moments[id] = m;
+        }
+        const unsigned long long word = __ballot(keep);
+        if (lane == 0 && base + wv * 64u < b1) mask[(base + wv * 64u) >> 6] = word;
+        count += (uint32_t)__popcll(word);
+    }
+    if (lane == 0) wave_total[wv] = count;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (uint32_t k = 0; k < BLOCK / 64; k++) t += wave_total[k];
+        block_counts[blockIdx.x] = t;
+    }
+}
+__global__ __launch_bounds__(BLOCK) void k_adaptive_compact(const uint32_t *__restrict__ ids, uint32_t n, uint32_t per, const unsigned long long *__restrict__ mask,
+                                                            const uint32_t *__restrict__ block_counts, uint32_t *__restrict__ out_ids, uint32_t *__restrict__ count) {
+    __shared__ uint32_t part[BLOCK];
+    __shared__ uint32_t wave_total[BLOCK / 64];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    uint32_t before = 0;                                          // the scan: survivors of the blocks before this one
+    for (uint32_t k = threadIdx.x; k < blockIdx.x; k += BLOCK) before += block_counts[k];
+    part[threadIdx.x] = before;
+    __syncthreads();
+    for (uint32_t s2 = BLOCK / 2; s2 > 0; s2 >>= 1) { if (threadIdx.x < s2) part[threadIdx.x] += part[threadIdx.x + s2]; __syncthreads(); }
+    uint32_t off = part[0];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *count = off + block_counts[blockIdx.x];
+    const uint32_t b0 = blockIdx.x * per, b1 = min(n, b0 + per);
+    for (uint32_t base = b0; base < b1; base += BLOCK) {
+        const uint32_t w0 = base + wv * 64u;
+        const unsigned long long word = w0 < b1 ? mask[w0 >> 6] : 0ull;
+        __syncthreads();                                          // (the previous step's reads of wave_total are done)
+        if (lane == 0) wave_total[wv] = (uint32_t)__popcll(word);
+        __syncthreads();
+        uint32_t wave_off = off, step = 0;
+        for (uint32_t k = 0; k < BLOCK / 64; k++) { if (k < wv) wave_off += wave_total[k]; step += wave_total[k]; }
+        if ((word >> lane) & 1ull) {
+            const uint32_t i = w0 + lane;
+            out_ids[wave_off + (uint32_t)__popcll(word & ((1ull << lane) - 1ull))] = ids ? ids[i] : i;
+        }
+        off += step;
     }
 }
 
@@ -3979,7 +4007,7 @@ void preload_kernels() {
     FW_TOUCH(k_extend_tlas); FW_TOUCH(k_extend_tlas_park); FW_TOUCH(k_blas); FW_TOUCH(k_blas_lds<true>); FW_TOUCH(k_blas_lds<false>); FW_TOUCH(k_extend_tlas_lds);
     FW_TOUCH((k_blas_wide<WIDE_F32, true>)); FW_TOUCH((k_blas_wide<WIDE_F32, false>)); FW_TOUCH((k_blas_wide<WIDE_Q8, true>)); FW_TOUCH((k_blas_wide<WIDE_Q8, false>));
     FW_TOUCH(k_extend_tlas_wide<true>); FW_TOUCH(k_extend_tlas_wide<false>); FW_TOUCH((k_extend_tlas_wide<true, true>)); FW_TOUCH((k_extend_tlas_wide<false, true>)); FW_TOUCH(k_extend_exact); FW_TOUCH(k_queue_totals); FW_TOUCH(k_count_deposits); FW_TOUCH(k_accumulate); FW_TOUCH(k_tile_order);
-    FW_TOUCH(k_resolve); FW_TOUCH(k_scatter_tiles); FW_TOUCH(k_trace_load); FW_TOUCH(k_trace_store); FW_TOUCH(k_camera_rays);
+    FW_TOUCH(k_resolve); FW_TOUCH(k_accumulate_adaptive); FW_TOUCH(k_adaptive_select); FW_TOUCH(k_adaptive_compact); FW_TOUCH(k_resolve_adaptive); FW_TOUCH(k_scatter_tiles); FW_TOUCH(k_trace_load); FW_TOUCH(k_trace_store); FW_TOUCH(k_camera_rays);
     FW_TOUCH((k_shade<0, 0, false>)); FW_TOUCH((k_shade<0, 0, true>)); FW_TOUCH((k_shade<0, 1, false>)); FW_TOUCH((k_shade<0, 1, true>));
     FW_TOUCH((k_shade<1, 0, false>)); FW_TOUCH((k_shade<1, 0, true>)); FW_TOUCH((k_shade<1, 1, false>)); FW_TOUCH((k_shade<1, 1, true>));
     FW_TOUCH((k_shade<2, 0, false>)); FW_TOUCH((k_shade<2, 0, true>)); FW_TOUCH((k_shade<2, 1, false>)); FW_TOUCH((k_shade<2, 1, true>));
@@ -4022,6 +4050,22 @@ void launch_accumulate(const LaunchCfg &c, const DFrame &f, const float4 *sample
 void launch_resolve(const LaunchCfg &c, const DFrame &f, const float4 *accum, uint32_t total_spp, float gamma,
                     uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
     hipLaunchKernelGGL(k_resolve, dim3(c.blocks_other), dim3(BLOCK), 0, c.stream, f, accum, total_spp, gamma, rgb8, gamma_rgb, linear_rgb);
+}
+void launch_accumulate_adaptive(const LaunchCfg &c, const DFrame &f, const float4 *sample_rad, float4 *accum, float4 *moments) {
+    uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)f.n_pixels + WB - 1) / WB, 65536));
+    hipLaunchKernelGGL(k_accumulate_adaptive, dim3(blocks), dim3(WB), 0, c.stream, f, sample_rad, accum, moments);
+}
+void launch_resolve_adaptive(hipStream_t stream, int n_cus, uint32_t n, const float4 *accum, const float4 *moments, float gamma,
+                             uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
+    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n + BLOCK - 1) / BLOCK, (uint64_t)n_cus * 8));
+    hipLaunchKernelGGL(k_resolve_adaptive, dim3(blocks), dim3(BLOCK), 0, stream, n, accum, moments, gamma, rgb8, gamma_rgb, linear_rgb);
+}
+uint32_t adaptive_select_blocks(uint32_t n) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n + BLOCK - 1) / BLOCK, ADAPTIVE_MAX_BLOCKS)); }
+void launch_adaptive_select(hipStream_t stream, const uint32_t *ids, uint32_t n, const float4 *accum, float4 *moments, uint32_t n_samples, bool may_continue,
+                            float tol, unsigned long long *mask, uint32_t *block_counts, uint32_t *out_ids, uint32_t *count) {
+    const uint32_t blocks = adaptive_select_blocks(n), per_block = (n + blocks - 1) / blocks, per = (per_block + BLOCK - 1) / BLOCK * BLOCK;
+    hipLaunchKernelGGL(k_adaptive_select, dim3(blocks), dim3(BLOCK), 0, stream, ids, n, per, accum, moments, n_samples, may_continue ? 1u : 0u, tol, mask, block_counts);
+    hipLaunchKernelGGL(k_adaptive_compact, dim3(blocks), dim3(BLOCK), 0, stream, ids, n, per, (const unsigned long long *)mask, (const uint32_t *)block_counts, out_ids, count);
 }
 
 } // namespace fw

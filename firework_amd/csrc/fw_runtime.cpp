@@ -772,6 +772,11 @@ struct Workspace {
     struct FrameGraph { uint64_t key = 0, seen = 0; hipGraphExec_t exec = nullptr; hipStream_t origin = nullptr; bool broken = false; fw::DFrame fr_after{}; } fg;
     std::vector<hipEvent_t> phase_events; // PHASE_LOCK: [lane-in-group][segment] "this batch's extend of the segment has finished"
     DevBuf tile_ids; uint32_t tile_w = 0, tile_h = 0;   // the library's own 16x16-tile pixel order of a (tile_w x tile_h) frame
+    // fw_render_adaptive: whole-frame sums and squares, the two id lists the rounds alternate between, the survivor mask, per-block
+    // counts (+ the survivor count behind them), its own start / stop events and a pinned word for the survivor count
+    DevBuf ad_accum, ad_moments, ad_ids[2], ad_mask, ad_counts;
+    hipEvent_t ad_ev[2] = {nullptr, nullptr};
+    uint32_t *ad_count_host = nullptr;
     void *staging = nullptr; size_t staging_bytes = 0;  // pinned host memory the scene blob is assembled in (k_upload reads it)
     void *host_out = nullptr; size_t host_out_bytes = 0; // pinned host memory the counters and output frames are copied into
     hipEvent_t ev_upload = nullptr;       // after the latest scene upload on this device: renders wait for it in stream order
@@ -787,6 +792,9 @@ struct Workspace {
         if (staging) { (void)hipHostFree(staging); staging = nullptr; staging_bytes = 0; }
         if (host_out) { (void)hipHostFree(host_out); host_out = nullptr; host_out_bytes = 0; }
         tile_ids.release(); tile_w = tile_h = 0;
+        for (DevBuf *b : {&ad_accum, &ad_moments, &ad_ids[0], &ad_ids[1], &ad_mask, &ad_counts}) b->release();
+        for (hipEvent_t &e : ad_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        if (ad_count_host) { (void)hipHostFree(ad_count_host); ad_count_host = nullptr; }
         for (DevBuf *b : {&accum, &totals, &pixel_ids, &out_rgb8, &out_gamma, &out_linear, &scene_cache, &arena}) b->release();
         for (Lane &l : lanes) {
             for (hipEvent_t e : l.events) (void)hipEventDestroy(e);
@@ -1619,16 +1627,22 @@ void set_walk_cfg(fw::LaunchCfg &cfg, const fw_scene *sc, const Options &O, cons
     cfg.ref_tlas_nodes = sc->tlas_nodes; cfg.ref_blas_nodes = sc->blas_nodes; cfg.ref_tlas_depth = sc->ref_tlas_depth; cfg.ref_blas_depth = sc->ref_blas_depth;
 }
 
-// first_sample / user_accum: fw_render_progressive (0 / nullptr for a plain render)
+// One round of fw_render_adaptive (adaptive_impl), rendered by render_impl: the samples [first_sample, first_sample + samples) of the
+// n pixels of a device-resident id list (nullptr: pixels 0..n-1), added to whole-frame sums and squares (k_accumulate_adaptive).  The
+// caller holds the workspace's lock.  A round does no id validation, no copy of the list, no resolve, never runs as a frame graph, and
+// clears the cached frame-graph key if it grows the path arena.
+struct AdaptiveRound { const uint32_t *ids; uint32_t n; float4 *accum, *moments; };
+
+// first_sample / user_accum: fw_render_progressive (0 / nullptr for a plain render); rd: a round of fw_render_adaptive
 int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb, fw_stats *stats,
-                uint32_t first_sample = 0, float *user_accum = nullptr) {
+                uint32_t first_sample = 0, float *user_accum = nullptr, const AdaptiveRound *rd = nullptr) {
     if (!sc || !p) return fail(FW_ERR_BAD_ARG, "null argument");
     if (p->width == 0 || p->height == 0 || p->samples == 0) return fail(FW_ERR_BAD_ARG, "width, height and samples must be > 0");
     if (!(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be > 0");
     if (p->rng_mode != FW_RNG_CTR) return fail(FW_ERR_UNSUPPORTED, "the HIP path implements FW_RNG_CTR only (FW_RNG_LCG is a sequential stream)");
     uint64_t full = (uint64_t)p->width * p->height;
     if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
-    uint32_t n_pix = p->pixel_ids ? p->n_pixels : (uint32_t)full;
+    uint32_t n_pix = rd ? rd->n : (p->pixel_ids ? p->n_pixels : (uint32_t)full);
     if (n_pix == 0) return fail(FW_ERR_BAD_ARG, "no pixels to render");
     if ((uint64_t)first_sample + p->samples > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_sample + samples overflows");
     if (p->pixel_ids) for (uint32_t i = 0; i < n_pix; i++) if (p->pixel_ids[i] >= full) return fail(FW_ERR_BAD_ARG, "pixel id out of range");
@@ -1637,7 +1651,8 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     hipStream_t stream = (hipStream_t)p->stream;
     Workspace *ws = workspace_for(sc->device);
     if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
-    std::lock_guard<std::mutex> ws_guard(ws->mu);
+    std::unique_lock<std::mutex> ws_guard(ws->mu, std::defer_lock);
+    if (!rd) ws_guard.lock();                                                        // (an adaptive round's caller holds it)
     { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }     // after fw_release_workspace, or a scene made before it
     const Options O = options();
 
@@ -1740,18 +1755,19 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         const auto ta = std::chrono::steady_clock::now();
         const bool grow = want > ws->arena.bytes;
         if (!rc && grow) rc = arena_reserve_locked(ws, sc->device, want);
+        if (rd && grow) { ws->fg.key = 0; ws->fg.seen = 0; }     // a later plain render never replays launches against the moved arena
         if (O.trace && grow) fprintf(stderr, "[firework] render: path arena grown to %.1f GiB in %.2f ms\n", (double)want / (double)(1 << 30),
                                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count());
         if (!rc) layout((uint8_t *)ws->arena.p);
     }
     for (int l = 0; l < n_lanes && !rc; l++)
         if (!ws->lanes[l].stream && n_lanes > 1) HIPCHK(hipStreamCreateWithFlags(&ws->lanes[l].stream, hipStreamNonBlocking));
-    need(ws->accum, (size_t)n_pix * 16);
+    if (!rd) need(ws->accum, (size_t)n_pix * 16);
     need(ws->totals, (size_t)n_batches * fw::COUNT_STRIDE * 4);
     if (p->pixel_ids) need(ws->pixel_ids, (size_t)n_pix * 4);
     // a whole frame is traced in the library's own 16x16-tile order (k_tile_order); k_resolve undoes it.  Not for progressive
     // renders: their accumulation buffer belongs to the caller and stays in pixel order.
-    const bool own_order = !p->pixel_ids && !user_accum && n_pix >= 1024 && !O.no_tile_order;
+    const bool own_order = !p->pixel_ids && !user_accum && !rd && n_pix >= 1024 && !O.no_tile_order;
     if (own_order) { const void *before = ws->tile_ids.p; need(ws->tile_ids, (size_t)n_pix * 4); if (ws->tile_ids.p != before) ws->tile_w = ws->tile_h = 0; }
     uint8_t *d_rgb8 = rgb8; float *d_gamma = gamma_rgb, *d_linear = linear_rgb;
     if (!p->outputs_on_device) {
@@ -1772,7 +1788,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     }
     if (user_accum)     // resume: the sums of the samples rendered so far (host or device memory, like the outputs)
         HIPCHK(hipMemcpyAsync(ws->accum.p, user_accum, (size_t)n_pix * 16, p->outputs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-    else HIPCHK(hipMemsetAsync(ws->accum.p, 0, (size_t)n_pix * 16, stream));
+    else if (!rd) HIPCHK(hipMemsetAsync(ws->accum.p, 0, (size_t)n_pix * 16, stream));
     HIPCHK(hipMemsetAsync(ws->totals.p, 0, (size_t)n_batches * fw::COUNT_STRIDE * 4, stream));
 
     fw::LaunchCfg cfg{};
@@ -1791,7 +1807,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     fw::DCamera cam = make_camera(p->camera, p->width, p->height);
     fw::DFrame fr{};         // (zeroed: the frame graph's key hashes these structs, padding and not-yet-set per-batch fields included)
     fr.width = p->width; fr.height = p->height; fr.n_pixels = n_pix; fr.inv_n_pixels = 1.0f / (float)n_pix; fr.inv_width = 1.0f / (float)p->width;
-    fr.pixel_ids = p->pixel_ids ? (const uint32_t *)ws->pixel_ids.p : (own_order ? (const uint32_t *)ws->tile_ids.p : nullptr);
+    fr.pixel_ids = rd ? rd->ids : (p->pixel_ids ? (const uint32_t *)ws->pixel_ids.p : (own_order ? (const uint32_t *)ws->tile_ids.p : nullptr));
     fr.scatter_out = own_order ? 1u : 0u;
     fr.seed32 = (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u);
     fr.q_n_waves = q.n_waves; fr.q_shift = q.cpw_shift;
@@ -1868,7 +1884,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     const bool phase_lock = n_lanes == 2 && !fused && (O.phase_lock == 1 || (O.phase_lock < 0 && !p->use_bvh && cfg.n_defer > 0 && chunks >= PHASE_LOCK_MIN_CHUNKS));
     std::vector<hipEvent_t> &pe = ws->phase_events;
     while (phase_lock && pe.size() < 2 * (size_t)fw::MAX_SEGMENTS) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); pe.push_back(e); }
-    float4 *const accum = (float4 *)ws->accum.p;
+    float4 *const accum = rd ? rd->accum : (float4 *)ws->accum.p;
     auto begin_batch = [&](uint32_t b, BatchCtx &c) -> int {
         const int l = (int)(b % (uint32_t)n_lanes);
         Workspace::Lane &L = ws->lanes[l];
@@ -1937,7 +1953,8 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         // `total_color += color(..)` in sample order (render.rs:181): batch b is accumulated after batch b-1, whichever
         // lanes they ran on, so the image does not depend on the number of lanes or batches
         if (n_lanes > 1 && b > 0) HIPCHK(hipStreamWaitEvent(c.ls, ws->events[3 + b - 1], 0));
-        timed(c, 3, [&] { fw::launch_accumulate(c.cfg, c.fr, c.srad, accum); });
+        if (rd) timed(c, 3, [&] { fw::launch_accumulate_adaptive(c.cfg, c.fr, c.srad, accum, rd->moments); });
+        else timed(c, 3, [&] { fw::launch_accumulate(c.cfg, c.fr, c.srad, accum); });
         if (n_lanes > 1) HIPCHK(hipEventRecord(ws->events[3 + b], c.ls));
         return FW_OK;
     };
@@ -1967,7 +1984,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     {
         Workspace::FrameGraph &fg = ws->fg;
         constexpr uint64_t GRAPH_MAX_CHUNKS = 1u << 19;      // batches below 33 M paths
-        const bool graph_ok = O.graph != 0 && !fg.broken && !timing && !dump_one && !phase_lock && !stagger && (O.graph == 1 || chunks < GRAPH_MAX_CHUNKS);   // (a capture with PHASE_LOCK's events crashed inside the runtime: the two never meet by default — the lock wants batches of 100 M paths)
+        const bool graph_ok = O.graph != 0 && !rd && !fg.broken && !timing && !dump_one && !phase_lock && !stagger && (O.graph == 1 || chunks < GRAPH_MAX_CHUNKS);   // (a capture with PHASE_LOCK's events crashed inside the runtime: the two never meet by default — the lock wants batches of 100 M paths)
         uint64_t key = 0;
         if (graph_ok) {
             uint64_t h = 1469598103934665603ull;
@@ -2015,7 +2032,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         if (!done) { if (int frc = enqueue_frame()) return frc; }
     }
     cfg.stream = stream;
-    fw::launch_resolve(cfg, fr, (const float4 *)ws->accum.p, first_sample + p->samples, p->gamma, d_rgb8, d_gamma, d_linear);
+    if (!rd) fw::launch_resolve(cfg, fr, (const float4 *)ws->accum.p, first_sample + p->samples, p->gamma, d_rgb8, d_gamma, d_linear);
     if (user_accum) HIPCHK(hipMemcpyAsync(user_accum, ws->accum.p, (size_t)n_pix * 16, p->outputs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
     HIPCHK(hipEventRecord(ws->events[1], stream));
     HIPCHK(hipGetLastError());
@@ -2097,7 +2114,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
                 stats->bytes_extend = rd_ray + medium + stats->rays * b_hit + stats->parked_rays * 2 * fw::B_PARK;
                 stats->bytes_shade = shade_in + stats->rays * b_hit + shade_out;
             }
-            stats->bytes_accumulate = (fr.skip_zero_deposits ? stats->deposits * fw::B_DEPOSIT + S / 8 : S * fw::B_DEPOSIT) + (uint64_t)n_batches * n_pix * 2 * fw::B_ACCUM;
+            stats->bytes_accumulate = (fr.skip_zero_deposits ? stats->deposits * fw::B_DEPOSIT + S / 8 : S * fw::B_DEPOSIT) + (uint64_t)n_batches * n_pix * 2 * fw::B_ACCUM * (rd ? 2u : 1u);   // (a round reads and writes the squares too)
         }
         stats->ms_wall = std::chrono::duration<double, std::milli>(wall1 - wall0).count();
         float ms_copy = 0.f;
@@ -2120,6 +2137,118 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         stats->n_extend_launches = fused ? 0 : n_batches * fw::MAX_SEGMENTS; stats->n_shade_launches = n_batches * fw::MAX_SEGMENTS;
         stats->n_batches = n_batches; stats->tlas_nodes = sc->tlas_nodes; stats->blas_nodes = sc->blas_nodes;
         stats->reserved = ((sc->tlas_depth & 0x7fffu) << 16) | (sc->blas_depth & 0xffffu) | (graph_replayed ? 0x80000000u : 0u);   // depths of the trees actually walked; bit 31: the frame ran as a hipGraph (GRAPH)
+    }
+    return FW_OK;
+}
+
+// fw_render_adaptive: rounds of render_impl over the still-active pixels of a whole frame (include/firework_hip.h has the contract).
+// Round 0 renders every pixel (in the tile order render_impl would use) to min_samples; after each round k_adaptive_select applies the
+// convergence rule on the device and compacts the survivors into the other id list, whose length comes back in one 4-byte copy; the
+// next round takes them from n to min(2n, max) samples.  Every pixel's sums are those of fw_render at its final count, bit for bit.
+constexpr uint32_t ADAPTIVE_MAX_ROUNDS = 32;
+int adaptive_impl(fw_scene *sc, const fw_render_params *p, float tol, uint32_t min_samples, float *accum, float *moments, uint8_t *rgb8,
+                  float *gamma_rgb, float *linear_rgb, uint32_t *round_pixels, fw_stats *stats) {
+    // (arguments first: nothing below dereferences the scene before they are all valid)
+    if (!sc || !p) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (p->pixel_ids) return fail(FW_ERR_BAD_ARG, "fw_render_adaptive renders whole frames: pixel_ids must be NULL");
+    if (min_samples < 2) return fail(FW_ERR_BAD_ARG, "min_samples must be >= 2 (the rule needs a variance)");
+    if (p->samples < min_samples) return fail(FW_ERR_BAD_ARG, "samples (the cap) must be >= min_samples");
+    if (p->samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be <= 2^24 (the count is exact as a float)");
+    if (!std::isfinite(tol) || !(tol > 0.f)) return fail(FW_ERR_BAD_ARG, "tolerance must be finite and > 0");
+    if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
+    if (!(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be > 0");
+    if (p->rng_mode != FW_RNG_CTR) return fail(FW_ERR_UNSUPPORTED, "the HIP path implements FW_RNG_CTR only (FW_RNG_LCG is a sequential stream)");
+    const uint64_t full = (uint64_t)p->width * p->height;
+    if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
+    const uint32_t n = (uint32_t)full;
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(sc->device));
+    hipStream_t stream = (hipStream_t)p->stream;
+    Workspace *ws = workspace_for(sc->device);
+    if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
+    std::lock_guard<std::mutex> ws_guard(ws->mu);
+    { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }
+    const Options O = options();
+    int rc = FW_OK;
+    auto need = [&](DevBuf &b, size_t bytes) { if (!rc) rc = b.alloc(bytes); };
+    need(ws->ad_accum, (size_t)n * 16); need(ws->ad_moments, (size_t)n * 16);
+    need(ws->ad_ids[0], (size_t)n * 4); need(ws->ad_ids[1], (size_t)n * 4);
+    need(ws->ad_mask, ((size_t)n + 63) / 64 * 8); need(ws->ad_counts, ((size_t)fw::ADAPTIVE_MAX_BLOCKS + 1) * 4);
+    uint8_t *d_rgb8 = rgb8; float *d_gamma = gamma_rgb, *d_linear = linear_rgb;
+    if (!p->outputs_on_device) {
+        if (rgb8) { need(ws->out_rgb8, (size_t)n * 3); d_rgb8 = (uint8_t *)ws->out_rgb8.p; }
+        if (gamma_rgb) { need(ws->out_gamma, (size_t)n * 12); d_gamma = (float *)ws->out_gamma.p; }
+        if (linear_rgb) { need(ws->out_linear, (size_t)n * 12); d_linear = (float *)ws->out_linear.p; }
+    }
+    if (rc) return rc;
+    if (!ws->ad_count_host) HIPCHK(hipHostMalloc((void **)&ws->ad_count_host, 4, hipHostMallocDefault));
+    for (hipEvent_t &e : ws->ad_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    float4 *d_accum = (float4 *)ws->ad_accum.p, *d_moments = (float4 *)ws->ad_moments.p;
+    uint32_t *d_count = (uint32_t *)ws->ad_counts.p + fw::ADAPTIVE_MAX_BLOCKS;
+
+    if (ws->ev_upload) HIPCHK(hipStreamWaitEvent(stream, ws->ev_upload, 0));
+    HIPCHK(hipEventRecord(ws->ad_ev[0], stream));
+    HIPCHK(hipMemsetAsync(d_accum, 0, (size_t)n * 16, stream));
+    HIPCHK(hipMemsetAsync(d_moments, 0, (size_t)n * 16, stream));
+    // round 0's list: render_impl's choice for a whole frame (16x16 tiles from 1024 pixels on, unless NO_TILE_ORDER), row order = no list
+    const uint32_t *cur = nullptr;
+    if (n >= 1024 && !O.no_tile_order) { fw::launch_tile_order(stream, p->width, p->height, (uint32_t *)ws->ad_ids[0].p); cur = (const uint32_t *)ws->ad_ids[0].p; }
+
+    fw_stats total{};
+    uint32_t rounds[ADAPTIVE_MAX_ROUNDS] = {};
+    uint32_t n_rounds = 0, active = n, done = 0;
+    double ms_classes[4] = {0, 0, 0, 0};
+    while (active > 0) {
+        if (n_rounds >= ADAPTIVE_MAX_ROUNDS) return fail(FW_ERR_HIP, "adaptive render: more rounds than the schedule allows");
+        const uint32_t target = n_rounds == 0 ? min_samples : std::min<uint32_t>(2u * done, p->samples);
+        fw_render_params rp = *p;
+        rp.samples = target - done; rp.pixel_ids = nullptr; rp.n_pixels = 0;
+        const AdaptiveRound rd{cur, active, d_accum, d_moments};
+        fw_stats rs{};
+        if (int rrc = render_impl(sc, &rp, nullptr, nullptr, nullptr, &rs, done, nullptr, &rd)) return rrc;
+        rounds[n_rounds++] = active;
+        total.samples += rs.samples; total.rays += rs.rays; total.deposits += rs.deposits; total.parked_rays += rs.parked_rays;
+        for (int d = 0; d < FW_MAX_SEGMENTS; d++) total.rays_per_depth[d] += rs.rays_per_depth[d];
+        total.algorithmic_bytes += rs.algorithmic_bytes;
+        total.bytes_raygen += rs.bytes_raygen; total.bytes_extend += rs.bytes_extend; total.bytes_shade += rs.bytes_shade; total.bytes_accumulate += rs.bytes_accumulate;
+        total.n_batches += rs.n_batches; total.n_extend_launches += rs.n_extend_launches; total.n_shade_launches += rs.n_shade_launches;
+        total.tlas_nodes = rs.tlas_nodes; total.blas_nodes = rs.blas_nodes; total.reserved = rs.reserved;
+        ms_classes[0] += rs.ms_raygen; ms_classes[1] += rs.ms_extend; ms_classes[2] += rs.ms_shade; ms_classes[3] += rs.ms_accumulate;
+        done = target;
+        uint32_t *next = (uint32_t *)ws->ad_ids[cur == (const uint32_t *)ws->ad_ids[0].p ? 1 : 0].p;
+        fw::launch_adaptive_select(stream, cur, active, d_accum, d_moments, done, done < p->samples, tol, (unsigned long long *)ws->ad_mask.p,
+                                   (uint32_t *)ws->ad_counts.p, next, d_count);
+        HIPCHK(hipMemcpyAsync(ws->ad_count_host, d_count, 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (*ws->ad_count_host > active) return fail(FW_ERR_HIP, "adaptive render: survivor count out of range");
+        active = *ws->ad_count_host;
+        cur = next;
+    }
+    fw::launch_resolve_adaptive(stream, sc->n_cus, n, d_accum, d_moments, p->gamma, d_rgb8, d_gamma, d_linear);
+    HIPCHK(hipEventRecord(ws->ad_ev[1], stream));
+    const hipMemcpyKind kind = p->outputs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (accum) HIPCHK(hipMemcpyAsync(accum, d_accum, (size_t)n * 16, kind, stream));
+    if (moments) HIPCHK(hipMemcpyAsync(moments, d_moments, (size_t)n * 16, kind, stream));
+    if (!p->outputs_on_device) {
+        if (rgb8) HIPCHK(hipMemcpyAsync(rgb8, d_rgb8, (size_t)n * 3, kind, stream));
+        if (gamma_rgb) HIPCHK(hipMemcpyAsync(gamma_rgb, d_gamma, (size_t)n * 12, kind, stream));
+        if (linear_rgb) HIPCHK(hipMemcpyAsync(linear_rgb, d_linear, (size_t)n * 12, kind, stream));
+    }
+    if (round_pixels && p->outputs_on_device) HIPCHK(hipMemcpyAsync(round_pixels, rounds, sizeof rounds, hipMemcpyHostToDevice, stream));
+    if (!ws->ev_d2h) HIPCHK(hipEventCreate(&ws->ev_d2h));
+    HIPCHK(hipEventRecord(ws->ev_d2h, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    if (round_pixels && !p->outputs_on_device) std::memcpy(round_pixels, rounds, sizeof rounds);
+    if (stats) {
+        *stats = total;
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ws->ad_ev[0], ws->ad_ev[1]));
+        stats->ms_render = ms;
+        HIPCHK(hipEventElapsedTime(&ms, ws->ad_ev[1], ws->ev_d2h));
+        stats->ms_d2h = p->outputs_on_device ? 0.0 : ms;
+        if (p->flags & FW_FLAG_TIME_KERNELS) { stats->ms_raygen = ms_classes[0]; stats->ms_extend = ms_classes[1]; stats->ms_shade = ms_classes[2]; stats->ms_accumulate = ms_classes[3]; }
+        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     }
     return FW_OK;
 }
@@ -2703,6 +2832,13 @@ int fw_render_progressive(fw_scene *scene, const fw_render_params *params, uint3
     try { return render_impl(scene, params, rgb8, gamma_rgb, linear_rgb, stats, first_sample, accum); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_render_progressive"); }
+}
+
+int fw_render_adaptive(fw_scene *scene, const fw_render_params *params, float tolerance, uint32_t min_samples, float *accum, float *moments,
+                       uint8_t *rgb8, float *gamma_rgb, float *linear_rgb, uint32_t *round_pixels, fw_stats *stats) {
+    try { return adaptive_impl(scene, params, tolerance, min_samples, accum, moments, rgb8, gamma_rgb, linear_rgb, round_pixels, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_render_adaptive"); }
 }
 
 int fw_render_scene(const fw_scene_desc *desc, const fw_render_params *params, int device, uint8_t *rgb8, float *gamma_rgb,

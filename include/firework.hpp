@@ -281,6 +281,25 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
         }
         fw_scene_destroy(sc);
         return buffer; }
+
+    // Adaptive sampling (not in the reference; fw_render_adaptive): every pixel gets min_samples samples, then the pixels whose standard
+    // error is above tolerance x their brightness go on in rounds that double their count, up to samples().  Each pixel equals render() at
+    // its final count bit for bit; `counts` (if given) receives those counts, width*height in index order.
+    std::vector<Color> render_adaptive(const Scene &scene, float tolerance, uint32_t min_samples, std::vector<uint32_t> *counts = nullptr,
+                                       fw_stats *stats = nullptr) const {
+        Lowered low(scene);
+        fw_scene *sc = nullptr;
+        int rc = fw_scene_create(&low.desc, device_, &sc);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        fw_render_params p = params();
+        std::vector<Color> buffer(width_ * height_, Color{0, 0, 0});
+        std::vector<float> moments(counts ? width_ * height_ * 4 : 0);
+        rc = fw_render_adaptive(sc, &p, tolerance, min_samples, nullptr, counts ? moments.data() : nullptr, reinterpret_cast<uint8_t *>(buffer.data()),
+                                nullptr, nullptr, nullptr, stats);
+        fw_scene_destroy(sc);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        if (counts) { counts->resize(width_ * height_); for (size_t i = 0; i < counts->size(); i++) (*counts)[i] = (uint32_t)moments[4 * i + 3]; }
+        return buffer; }
 };
 
 // Ray queries (ABI v8, not in the reference): a scene uploaded once, and `Hitable::hit(ray, 0.001, 2e9)` (render.rs:19,44-57) for the

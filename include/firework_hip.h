@@ -287,6 +287,33 @@ int fw_render_scene_tiled(const fw_scene_desc *desc, const fw_render_params *par
 int fw_render_progressive(fw_scene *scene, const fw_render_params *params, uint32_t first_sample, float *accum,
                           uint8_t *rgb8, float *gamma_rgb, float *linear_rgb, fw_stats *stats);
 
+/* Adaptive sampling: renders a whole frame until every pixel's noise estimate meets `tolerance`, or its sample count reaches the cap
+   params->samples.  Every pixel first gets `min_samples` samples.  After a round in which the active pixels reached n samples, a pixel
+   stays active if it has not converged and n < cap, and the next round renders the samples [n, min(2n, cap)) of the active pixels only;
+   final counts therefore lie in {min, 2 min, 4 min, ..., cap}.  The rule, evaluated on the device in float32 (IEEE, no contraction):
+       nf = (float)n;  S_c, Q_c = the pixel's sum and sum of squares of channel c (r, g, b), in sample order
+       m_c = S_c / nf;  v_c = (Q_c - S_c * m_c) / (nf - 1);  L = ((m_r + m_g) + m_b) / 3;  t = tol * (L > 1/256 ? L : 1/256)
+       converged <=> all six of S_c, Q_c finite AND v_c <= (t * t) * nf for every c
+   (the standard error of every channel's mean is at most tol x the mean brightness; a pixel with a non-finite sum runs to the cap).
+   Every draw is keyed by (pixel, absolute sample) and sums are taken in sample order, so for every pixel p with final count n_p, accum[p],
+   rgb8, gamma_rgb and linear_rgb equal bit for bit what fw_render (or fw_render_progressive) at n_p samples gives that pixel, under every
+   kernel-selecting option.  Outputs (any may be NULL), W*H entries each in row-major pixel order:
+     accum        : n x 4 floats, fw_render_progressive's layout (r, g, b sums, then path segments)
+     moments      : n x 4 floats, r, g, b sums of squares, and .w = the pixel's final sample count as a float
+     rgb8 / gamma_rgb / linear_rgb : as fw_render, each pixel resolved with its own count
+     round_pixels : 32 entries, the active pixels of each round followed by zeros (at most 1 + ceil(log2(cap / min)) rounds)
+   With params->outputs_on_device every output is a device pointer, as in fw_render.  Errors: FW_ERR_BAD_ARG for a NULL scene or params,
+   params->pixel_ids != NULL (whole frames only), min_samples < 2, samples < min_samples, samples > 2^24, a tolerance that is not finite
+   or <= 0 — all checked before the scene is looked at; FW_ERR_UNSUPPORTED for FW_RNG_LCG; FW_ERR_NO_DEVICE without a GPU.
+   stats: samples = the sum of the final counts; rays, rays_per_depth, n_batches and the byte counts summed over the rounds; ms_render =
+   first launch to last; the per-class times under FW_FLAG_TIME_KERNELS (the accumulation with squares counted in ms_accumulate).
+   Synchronisation is fw_render's: the launches go to params->stream after the scene's upload, and the call returns after that stream has
+   drained (it also waits for one 4-byte survivor count per round).  A round never runs as a frame graph (option GRAPH); if it grows the
+   path workspace, the cached frame graph's key is cleared, as fw_trace_rays does. */
+int fw_render_adaptive(fw_scene *scene, const fw_render_params *params, float tolerance, uint32_t min_samples,
+                       float *accum, float *moments, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb,
+                       uint32_t *round_pixels, fw_stats *stats);
+
 /* One-shot form with the reference's exact shape: `Renderer::render(&self, scene: Scene)`
    (render.rs:109): scene conversion + BVH build + render inside one call. */
 int fw_render_scene(const fw_scene_desc *desc, const fw_render_params *params, int device,
