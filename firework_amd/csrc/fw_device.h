@@ -138,8 +138,8 @@ struct DScene {
 //             numbers near 2*10^6 — noise — and the reference tests it whenever the ray passes the box of its DoubleLeaf node,
 //             a front-to-back walk when it passes the sphere's own box.  Flagged: origin farther than far_r from the cluster
 //             of the scene's small objects AND the ray passes that cluster's (inflated) box.
-constexpr uint32_t EX_TRACE_ZERO = 8u;   // DExact.mode bit of a trace under use_bvh only (k_trace_load; needs_exact ignores it): a caller ray whose
-                                         // direction has a zero component takes the exact walk (a ray inside a plane meets it at t = 0/0)
+constexpr uint32_t EX_TRACE_ZERO = 8u;   // DExact.mode bit of a trace under use_bvh only (needs_exact ignores it): keeps the flag rule on, so that
+                                         // a caller ray whose direction has a zero component takes the exact walk (a ray inside a plane meets it at t = 0/0)
 struct DExact {
     uint32_t mode;
     uint32_t n_frames;            // distinct rotations of mesh objects (<= 4), rows of rotation_mat

@@ -336,9 +336,14 @@ __device__ __forceinline__ bool nan_ray(float ox, float oy, float oz, float dx, 
     const float s = ((ox + oy) + oz) + ((dx + dy) + dz);
     return s != s;
 }
+// A direction with a zero component may run exactly inside an axis-aligned plane it starts on (a rect, a box face): t = 0/0 = NaN, a
+// "hit" no comparison rejects, which the reference's tree walk lets a later hit replace or not by the order of its tests.  At unit
+// scale scattered rays practically never have one; far from the origin they do — a scattered direction is (target - point) with both
+// near 2e6, quantised to 0.25 (the Cornell box x 2^12: tests/test_gpu_coordinates.py) — so such rays take the exact walk.
 __device__ __forceinline__ bool needs_exact(const DExact &ex, float ox, float oy, float oz, float dx, float dy, float dz) {
     if (ex.mode & 4u) return true;
     if (nan_ray(ox, oy, oz, dx, dy, dz)) return true;
+    if (dx == 0.f || dy == 0.f || dz == 0.f) return true;
     if (ex.mode & 1u) {
         if (ill_direction(dx, dy, dz, ex.shear)) return true;
         for (uint32_t k = 0; k < ex.n_frames; k++) {            // inv_rotation_mat * d = rows of rotation_mat as columns (rot_inv)
@@ -2302,9 +2307,11 @@ template <int FMT> __device__ __forceinline__ WideSel wide_sel(V3 inv) {
 // FW_WIDE_FMA (round 5): a plane's distance as ONE fma — fma(plane, 1/d, -o/d) instead of (plane - o) * (1/d), and for quantised nodes
 // fma(q, 2^e/d, (origin - o)/d) instead of decoding the plane first: 33 instead of 51 vector instructions for the four boxes of an f32
 // step, 66 instead of 99 for a quantised one, in kernels that issue vector instructions 0.9 of the time.  The distances differ from the
-// subtract-first form by ~2^-24 |o/d| (absolute) — the ulp of the origin's coordinate, orders of magnitude below what the walked boxes are
-// relaxed by (hit_aabb_entry: exit planes x (1 + 2^-12), boxes grown by >= 2^-14 of their extent on the host) — and the walked boxes decide
-// nothing: which item wins is decided by the exact item tests, the reference-rank rule and the reference's own box test on its leaf node's
+// subtract-first form by up to 2^-24 |o/d| (absolute; a quantised node: 2^-23 (|node origin| + |o|) / |d|) — a plane moved by the ulp of
+// the origin's COORDINATE, which the size-relative growth of the walked boxes does not bound: a triangle of 0.03 at x = 1e4 is already
+// past it (tests/test_gpu_coordinates.py).  The host therefore grows each frame's walked boxes by 2^-21 of its largest coordinate as well
+// (fw_runtime.cpp: coord_max), which covers every ray whose origin lies within the scene's coordinates in that frame.  The walked
+// boxes decide nothing: which item wins is decided by the exact item tests, the reference-rank rule and the reference's own box test on its leaf node's
 // box (tri_gate_ok / obj_gate_ok).  Where a direction component is 0 the fma form meets inf - inf = NaN, which fmaxf / fminf drop: that axis
 // then constrains nothing (conservative: a few more visits for axis-parallel rays).
 template <int FMT>
@@ -3763,11 +3770,8 @@ __global__ __launch_bounds__(WB) void k_trace_load(DFrame f, const float *__rest
             ids[((pos >> 6) * q.n_waves + w) * 64u + (pos & 63u)] = key0 + i;
         }
         if (lane < m) slot_of[i] = ok ? slot : MISS;
-        // (EX_TRACE_ZERO, widened here and not in needs_exact, so renders keep their kernel mix: caller rays may run exactly inside a
-        // plane — t = 0/0 = NaN, a "hit" no comparison rejects, which the reference's tree walk lets a later hit replace or not by the
-        // order of its tests; camera and scattered rays practically never do)
-        const bool zero_dir = (f.ex.mode & EX_TRACE_ZERO) && (v[3] == 0.f || v[4] == 0.f || v[5] == 0.f);
-        const bool fl = ok && f.ex.mode && (zero_dir || needs_exact(f.ex, v[0], v[1], v[2], v[3], v[4], v[5]));
+        // (EX_TRACE_ZERO keeps the flag rule on under use_bvh, where needs_exact sends the rays with a zero direction component to the exact walk)
+        const bool fl = ok && f.ex.mode && needs_exact(f.ex, v[0], v[1], v[2], v[3], v[4], v[5]);
         if (f.ex.mode) flag_exact(f.ex, fl, slot, 0);
         produced += (uint32_t)__popcll(bal);
     }

@@ -330,6 +330,22 @@ inline Box grown_by(const Box &b, float g) {
     return Box{{b.mn.x - g, b.mn.y - g, b.mn.z - g}, {b.mx.x + g, b.mx.y + g, b.mx.z + g}};
 }
 inline Box grown(const Box &b) { return grown_by(b, std::ldexp(box_extent(b), -14)); }
+// The walks' plane distances carry a rounding that scales with the COORDINATES, not with the box: fw_kernels.hip's wide_step computes
+// fma(plane, 1/d, -o/d), and the rounding of -o/d moves the plane by up to 2^-24 |o|; a quantised node's (node origin - o) / d moves it
+// by up to 2^-23 (|node origin| + |o|).  For small items far from the origin that passes the growth above (a triangle of 0.03 at
+// x = 3e4: 2^-24 |o| = 1.8e-3, growth 2^-6 x 0.03 = 4.7e-4; tests/test_gpu_coordinates.py).  So a frame's walked boxes grow by at least
+// 2^-21 M as well, M a bound on the coordinates, in that frame, of every point of the scene: for a ray whose origin lies within M
+// (every ray that starts on the scene's geometry, and a camera inside the scene's range) that is 8x the fma form's rounding and 2x the
+// quantised form's.  A camera farther out than the scene's own coordinates is not covered.  The world frame's M is the largest finite
+// coordinate of the objects' boxes (for an object inside the far rule's cluster box: at most |far_c| + far_r, which bounds the origin of
+// every unflagged ray that reaches it); a mesh's frame's M is reach_in_frames' bound (the scene mapped into it), at least its own box's.
+inline float coord_max(const std::vector<Box> &bs) {
+    float m = 0.f;
+    for (const Box &b : bs)
+        for (float c : {b.mn.x, b.mn.y, b.mn.z, b.mx.x, b.mx.y, b.mx.z})
+            if (std::isfinite(c)) m = std::fmax(m, std::fabs(c));
+    return m;
+}
 
 // item boxes := the box of the reference leaf node that holds the item (its own box for a Leaf, the union for a DoubleLeaf)
 void leaf_node_boxes(const FlatBvh &ref, std::vector<Box> &boxes) {
@@ -910,6 +926,43 @@ struct fw_scene {
     }
 };
 
+// A bound on the coordinates of every point of the scene in the frame of each shape's objects (coord_max), from the description alone —
+// the meshes' walked trees are built before the objects' world boxes exist.  A shape's points lie within E of its frame's origin, E its
+// largest finite coordinate (a medium: its boundary's); an object's within |position| + E x (rotated: sqrt 3) in the world; a world point
+// x within (|x| + |position|) x (rotated: sqrt 3) in an object's frame.  max-norms throughout.
+static std::vector<float> reach_in_frames(const fw_scene_desc *d) {
+    auto fin = [](float v) { return std::isfinite(v) ? std::fabs(v) : 0.f; };
+    std::vector<float> ext(d->n_shapes, 0.f), reach(d->n_shapes, 0.f);
+    for (uint32_t i = 0; i < d->n_shapes; i++) {
+        const fw_shape &h = d->shapes[i];
+        float m = 0.f;
+        for (float v : {h.radius, h.height, h.inner_radius, h.a_min, h.a_max, h.b_min, h.b_max, h.k}) m = std::fmax(m, fin(v));
+        for (float v : {h.pos.x + h.size.x, h.pos.y + h.size.y, h.pos.z + h.size.z, h.pos.x, h.pos.y, h.pos.z}) m = std::fmax(m, fin(v));
+        if (h.kind == FW_SHAPE_TRIANGLE_MESH && h.verts)
+            for (size_t k = 0; k < (size_t)h.n_verts * 3; k++) m = std::fmax(m, fin(h.verts[k]));
+        ext[i] = m;
+    }
+    auto inner = [&](int32_t si) {
+        const fw_shape &h = d->shapes[si];
+        return (h.kind == FW_SHAPE_CONSTANT_MEDIUM && h.inner >= 0 && (uint32_t)h.inner < d->n_shapes) ? h.inner : si;
+    };
+    auto rotated = [](const fw_object &o) { return !(o.rotation.s == 1.f && o.rotation.xy == 0.f && o.rotation.xz == 0.f && o.rotation.yz == 0.f); };
+    auto pos_max = [&](const fw_object &o) { return std::fmax(fin(o.position.x), std::fmax(fin(o.position.y), fin(o.position.z))); };
+    float world = 0.f;
+    for (uint32_t i = 0; i < d->n_objects; i++) {
+        const fw_object &o = d->objects[i];
+        if (o.shape < 0 || (uint32_t)o.shape >= d->n_shapes) continue;
+        world = std::fmax(world, pos_max(o) + (rotated(o) ? 1.7321f : 1.f) * ext[inner(o.shape)]);
+    }
+    for (uint32_t i = 0; i < d->n_objects; i++) {
+        const fw_object &o = d->objects[i];
+        if (o.shape < 0 || (uint32_t)o.shape >= d->n_shapes) continue;
+        const int32_t si = inner(o.shape);
+        reach[si] = std::fmax(reach[si], (rotated(o) ? 1.7321f : 1.f) * (world + pos_max(o)));
+    }
+    return reach;
+}
+
 namespace {
 
 struct ShapeParams { float q3[4] = {0, 0, 0, 0}, q4[4] = {0, 0, 0, 0}; uint32_t kind = 0, flags = 0, aux0 = 0, aux1 = 0; Box box{};
@@ -932,6 +985,9 @@ struct Flattener {
     std::vector<ShapeParams> mesh_cache;  // per shape index: a TriangleMesh shape referenced by several objects (or by a medium
     std::vector<uint8_t> mesh_cached;     // and an object) is flattened and built once, every user shares its triangles and BLAS
     int device = -1;                      // where build_tree may build the meshes' trees
+    std::vector<float> frame_reach;       // per shape: a bound on the coordinates of every point of the scene in the frame of its objects
+                                          // (reach_in_frames; a mesh's walked boxes grow by 2^-21 of it, coord_max)
+    float reach = 0.f;                    // frame_reach of the mesh being built
     fw::DeviceBuildTimes dev_times;       // the device builds' upload / kernel / copy-back times (FIREWORK_TRACE)
     double ms_gather = 0, ms_ref = 0, ms_gate = 0, ms_sah = 0, ms_pair = 0, ms_wide = 0;   // where mesh_params spends its time (FIREWORK_TRACE=1, tools/big_mesh.py)
 
@@ -983,6 +1039,7 @@ struct Flattener {
         case FW_SHAPE_TRIANGLE_MESH: {
             if (mesh_cached.empty()) { mesh_cached.assign(d->n_shapes, 0); mesh_cache.resize(d->n_shapes); }
             if (mesh_cached[si]) { sp = mesh_cache[si]; return FW_OK; }
+            reach = (size_t)si < frame_reach.size() ? frame_reach[si] : 0.f;
             int rc = mesh_params(s, sp);
             if (rc == FW_OK) { mesh_cache[si] = sp; mesh_cached[si] = 1; }
             return rc; }
@@ -1064,8 +1121,8 @@ struct Flattener {
         // the boxes of the walked trees (grown_by: 2^-6 of a typical triangle, at least 2^-14 of the triangle's own extent)
         std::vector<Box> wboxes = boxes;
         {
-            const float typ = box_extent(sp.box) / std::sqrt((float)std::max(1u, n_tris));
-            for (Box &b : wboxes) b = grown_by(b, std::fmax(std::ldexp(typ, -6), std::ldexp(box_extent(b), -14)));
+            const float typ = box_extent(sp.box) / std::sqrt((float)std::max(1u, n_tris)), gc = std::ldexp(std::fmax(coord_max({sp.box}), reach), -21);
+            for (Box &b : wboxes) b = grown_by(b, std::fmax(std::fmax(std::ldexp(typ, -6), std::ldexp(box_extent(b), -14)), gc));
         }
         const bool sah = use_sah();
         std::exception_ptr sah_error;
@@ -1159,6 +1216,7 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
 
     Flattener fl{desc};
     fl.device = device;
+    fl.frame_reach = reach_in_frames(desc);
     fw::DeviceBuildTimes dev_times;           // the TLAS builds (the meshes' trees: fl.dev_times)
     std::vector<float> objs((size_t)desc->n_objects * fw::OBJ_Q * 4, 0.f);
     std::vector<Box> world(desc->n_objects), true_world(desc->n_objects);
@@ -1281,6 +1339,13 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
             if ((kf >> 8) & fw::OF_GATE) build_boxes[items[q]] = own_boxes[items[q]] = box_union(node_box, true_world[items[q]]);
         }
     }
+    // the world frame's coordinates (coord_max): M over all the objects' boxes; an object inside the far rule's cluster box is reached
+    // unflagged only by rays that start within far_r of far_c, so min(M, |far_c| + far_r) bounds their origins (a giant fog sphere's M
+    // then grows only the objects outside the cluster)
+    const float m_all = coord_max(build_boxes);
+    float m_near = m_all;
+    if (ex.mode & 2u)
+        m_near = std::fmin(m_all, std::fmax(std::fabs(ex.far_c[0]), std::fmax(std::fabs(ex.far_c[1]), std::fabs(ex.far_c[2]))) + ex.far_r);
     for (uint32_t i = 0; i < desc->n_objects; i++) {             // the walked trees' boxes (grown_by: what a walk must still reach)
         uint32_t kf; std::memcpy(&kf, &objs[(size_t)i * fw::OBJ_Q * 4 + 3], 4);
         const uint32_t kind = kf & 0xffu, inner = kf >> 24, shape = kind == FW_SHAPE_CONSTANT_MEDIUM ? inner : kind;
@@ -1289,7 +1354,11 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
         if (shape == FW_SHAPE_TRIANGLE_MESH) g = std::fmax(g, std::ldexp(obj_size[i], -5));                        // its triangles' boxes grew by 2^-6 of this, in the mesh's frame
         else if ((shape == FW_SHAPE_SPHERE || shape == FW_SHAPE_CONE || shape == FW_SHAPE_CYLINDER) && (ex.mode & 2u) && ext > 0.f)
             g = std::fmax(g, std::fmin(ext, std::ldexp(ex.far_r * ex.far_r / ext, -22)));
-        build_boxes[i] = grown_by(build_boxes[i], g);
+        const Box &b = build_boxes[i];
+        const bool near = (ex.mode & 2u) && std::fmin(b.mn.x, b.mx.x) >= ex.box_lo[0] && std::fmin(b.mn.y, b.mx.y) >= ex.box_lo[1] && std::fmin(b.mn.z, b.mx.z) >= ex.box_lo[2]
+                          && std::fmax(b.mn.x, b.mx.x) <= ex.box_hi[0] && std::fmax(b.mn.y, b.mx.y) <= ex.box_hi[1] && std::fmax(b.mn.z, b.mx.z) <= ex.box_hi[2];
+        const float gc = std::ldexp(near ? std::fmax(m_near, coord_max({b})) : m_all, -21);
+        build_boxes[i] = grown_by(build_boxes[i], std::fmax(g, gc));
     }
     auto pack_boxes = [&](const std::vector<Box> &bs) {
         std::vector<float> out((size_t)desc->n_objects * 8, 0.f);
@@ -2320,7 +2389,7 @@ int trace_impl(fw_scene *sc, const fw_trace_params *p, const float *rays, uint32
 #else
     const bool tlas_refill = true;
 #endif
-    // render_impl's exact walk, and under use_bvh the caller rays with a zero direction component as well (fw::EX_TRACE_ZERO)
+    // render_impl's exact walk; under use_bvh always on (fw::EX_TRACE_ZERO), for the caller rays with a zero direction component
     const uint32_t exact_mode = (sc->ex.mode & 1u) | (use_bvh ? (sc->ex.mode & 6u) | fw::EX_TRACE_ZERO : ((sc->ex.mode & 4u) && sc->d.has_mesh ? 4u : 0u));
     const bool park_meshes = use_bvh && sc->d.has_mesh != 0 && tlas_refill;
 
