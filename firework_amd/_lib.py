@@ -45,6 +45,8 @@ def load(preload=False, device=None):
     lib.fw_device_count.restype = C.c_int
     lib.fw_scene_create.restype = C.c_int
     lib.fw_scene_create.argtypes = [C.POINTER(A.fw_scene_desc), C.c_int, C.POINTER(C.c_void_p)]
+    lib.fw_scene_update.restype = C.c_int
+    lib.fw_scene_update.argtypes = [C.c_void_p, C.POINTER(A.fw_scene_desc)]
     lib.fw_scene_destroy.restype = None
     lib.fw_scene_destroy.argtypes = [C.c_void_p]
     lib.fw_render.restype = C.c_int
@@ -248,6 +250,18 @@ class DeviceScene:
         _check(lib, lib.fw_scene_create(scene_desc.ptr(), device, C.byref(h)))
         self.handle = h
         self.device = device
+
+    def update(self, scene):
+        """fw_scene_update: moves the objects of this resident scene.  `scene` is a SceneDesc of the scene this one was created from with
+        other object placements (position, rotation, flip_normals), or that Scene itself after its RenderObjects were moved: then only a
+        new fw_object array is built and the kept description's shape, material, texture and environment arrays are reused (no mesh,
+        image or HDR array is converted again).  Every later call equals the same call on DeviceScene(the moved scene) bit for bit.
+        ValueError if the Scene's objects no longer map to the same shapes; FireworkError for what the library rejects (the scene is
+        then as it was)."""
+        from .api import Scene
+        desc = self._desc.placements(scene) if isinstance(scene, Scene) else scene
+        _check(self._lib, self._lib.fw_scene_update(self.handle, desc.ptr()))
+        self._desc = desc
 
     def render(self, renderer, pixel_ids=None, out_device_ptrs=None, stream=None):
         """fw_render.  out_device_ptrs = (rgb8, gamma, linear) raw device pointers (ints or None) to

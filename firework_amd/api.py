@@ -538,6 +538,15 @@ class Scene:
         return SceneDesc(self)
 
 
+def _object_record(fo, ro: RenderObject, shape: int):
+    """Fills the fw_object `fo` with RenderObject `ro`'s placement and shape index `shape`; returns it."""
+    fo.shape = shape
+    fo.position = A.vec3(ro._position)
+    fo.rotation = ro.rotation.to_abi()
+    fo.flip_normals = int(ro._flip_normals)
+    return fo
+
+
 class SceneDesc:
     """Owns the ctypes arrays (and the numpy buffers they point into) of one fw_scene_desc."""
 
@@ -601,6 +610,7 @@ class SceneDesc:
             mats.append(fm)
 
         shapes: List[A.fw_shape] = []
+        self._shape_objs = []  # the Python shape object of each fw_shape (kept: placements() maps objects to shapes by identity)
 
         shape_index = {}      # one fw_shape per Python shape object: objects that share a TriangleMesh share its BLAS
 
@@ -643,17 +653,11 @@ class SceneDesc:
             else:
                 raise TypeError(f"unknown shape {type(s).__name__}")
             shapes.append(fs)
+            self._shape_objs.append(s)
             shape_index[id(s)] = len(shapes) - 1
             return len(shapes) - 1
 
-        objs = []
-        for ro in scene.render_objects:
-            fo = A.fw_object()
-            fo.shape = add_shape(ro.obj)
-            fo.position = A.vec3(ro._position)
-            fo.rotation = ro.rotation.to_abi()
-            fo.flip_normals = int(ro._flip_normals)
-            objs.append(fo)
+        objs = [_object_record(A.fw_object(), ro, add_shape(ro.obj)) for ro in scene.render_objects]
 
         env = A.fw_environment()
         e = scene.environment
@@ -686,6 +690,38 @@ class SceneDesc:
 
     def ptr(self):
         return C.byref(self.desc)
+
+    def placements(self, scene: Scene) -> "SceneDesc":
+        """The description of `scene`, the Scene this one was made from, after its RenderObjects were moved (position, rotation,
+        flip_normals): a new fw_object array, and this description's shape, material and texture arrays and environment as they are
+        (what DeviceScene.update passes to fw_scene_update).  ValueError if the scene's objects no longer map to the same shapes, by
+        identity as SceneDesc maps them."""
+        ros = scene.render_objects
+        if len(ros) != self.desc.n_objects:
+            raise ValueError(f"the scene has {len(ros)} objects, its description {self.desc.n_objects}")
+        index = {id(s): i for i, s in enumerate(self._shape_objs)}
+        objs = (A.fw_object * max(1, len(ros)))()
+        for i, ro in enumerate(ros):
+            si = index.get(id(ro.obj))
+            if si is None or si != self.objects[i].shape:
+                raise ValueError(f"object {i} no longer uses the shape it was created with (only placements may change)")
+            _object_record(objs[i], ro, si)
+        # the buffers of the description the chain started from, and this object array: a placements() of a placements() holds the
+        # same number of buffers, however long the chain (DeviceScene.update keeps the latest description)
+        base_keep = getattr(self, "_base_keep", self._keep)
+        out = SceneDesc.__new__(SceneDesc)
+        out._base_keep = base_keep
+        out._keep = base_keep + [objs]
+        out._shape_objs = self._shape_objs
+        out.objects, out.shapes, out.materials, out.textures = objs, self.shapes, self.materials, self.textures
+        d = A.fw_scene_desc()
+        d.objects, d.n_objects = objs, len(ros)
+        d.shapes, d.n_shapes = self.shapes, self.desc.n_shapes
+        d.materials, d.n_materials = self.materials, self.desc.n_materials
+        d.textures, d.n_textures = self.textures, self.desc.n_textures
+        d.environment = self.desc.environment
+        out.desc = d
+        return out
 
     def content_hash(self) -> str:
         """sha256 over everything a render depends on: every struct field that is not a pointer, and the arrays the

@@ -901,6 +901,36 @@ size_t default_arena_bytes(const Workspace *ws) {      // what fw_init(device, 0
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return std::min<size_t>((size_t)64 << 30, (free_b + ws->arena.bytes) / 3) & ~(((size_t)1 << 30) - 1);
 }
+// the pinned staging buffer holds at least `total` bytes and no upload still reads it.  Caller holds ws->mu.
+int staging_reserve_locked(Workspace *ws, size_t total) {
+    (void)hipEventSynchronize(ws->ev_upload);          // the previous upload has read the staging buffer (long done)
+    if (ws->staging_bytes >= total) return FW_OK;
+    if (ws->staging) (void)hipHostFree(ws->staging);
+    ws->staging = nullptr; ws->staging_bytes = 0;
+    const size_t want = std::max<size_t>(total + total / 4, 1 << 20);
+    if (hipHostMalloc(&ws->staging, want, hipHostMallocDefault) != hipSuccess) return fail(FW_ERR_OOM, "pinned staging allocation failed");
+    ws->staging_bytes = want;
+    return FW_OK;
+}
+
+struct ShapeParams { float q3[4] = {0, 0, 0, 0}, q4[4] = {0, 0, 0, 0}; uint32_t kind = 0, flags = 0, aux0 = 0, aux1 = 0; Box box{};
+                     uint32_t wroot_f32 = 0xffffffffu, wroot_q8 = 0xffffffffu;   // meshes: root reference of the wide tree in either encoding
+                     uint32_t ref_root = 0xffffffffu, n_tris = 0;   // meshes: first node of the reference tree in Flattener::ref_blas
+                     Box true_box{}; };   // OF_GATE shapes: a box that really encloses the geometry (object space)
+
+// What fw_scene_create keeps on the host for fw_scene_update: the small fields of the description it was made from
+// (to check a new one against: objects' shapes, the shapes, materials, textures and environment without the arrays they point to),
+// the parameters of every shape an object uses (a mesh's: roots, triangle count, boxes — so that an update never flattens it again),
+// each shape's largest coordinate (reach_in_frames) and the reach each mesh's walked trees were built with.
+struct SceneKeep {
+    std::vector<int32_t> obj_shape;
+    std::vector<fw_shape> shapes;
+    std::vector<fw_material> materials;
+    std::vector<fw_texture> textures;
+    fw_environment env{};
+    std::vector<ShapeParams> sp;         // per shape index (those the objects use, media with their inner shape's)
+    std::vector<float> ext, reach;       // per shape index
+};
 
 } // namespace
 
@@ -922,8 +952,13 @@ struct fw_scene {
     bool hdr_env = false;
     fw::DExact ex{};              // flag rule of the exact walk (bits pointer is per render)
     uint32_t ref_tlas_depth = 0, ref_blas_depth = 0;
+    SceneKeep keep;               // fw_scene_update's host copy of the description and the per-shape parameters
+    DevBuf obj_data;              // the object-level sections once an update has written them (data's own copies are then unused)
+    size_t blob_bytes = 0;        // bytes of the creation's upload
+    double ms_objects = 0, ms_objects_dev = 0;   // the last object-level build: host wall time, device tree builds (FIREWORK_TRACE)
     ~fw_scene() {
         data.release();
+        obj_data.release();
     }
 };
 
@@ -931,9 +966,10 @@ struct fw_scene {
 // the meshes' walked trees are built before the objects' world boxes exist.  A shape's points lie within E of its frame's origin, E its
 // largest finite coordinate (a medium: its boundary's); an object's within |position| + E x (rotated: sqrt 3) in the world; a world point
 // x within (|x| + |position|) x (rotated: sqrt 3) in an object's frame.  max-norms throughout.
-static std::vector<float> reach_in_frames(const fw_scene_desc *d) {
-    auto fin = [](float v) { return std::isfinite(v) ? std::fabs(v) : 0.f; };
-    std::vector<float> ext(d->n_shapes, 0.f), reach(d->n_shapes, 0.f);
+static inline float finite_abs(float v) { return std::isfinite(v) ? std::fabs(v) : 0.f; }
+static std::vector<float> shape_extents(const fw_scene_desc *d) {      // E per shape (the part of reach_in_frames that reads the vertices)
+    auto fin = finite_abs;
+    std::vector<float> ext(d->n_shapes, 0.f);
     for (uint32_t i = 0; i < d->n_shapes; i++) {
         const fw_shape &h = d->shapes[i];
         float m = 0.f;
@@ -943,6 +979,11 @@ static std::vector<float> reach_in_frames(const fw_scene_desc *d) {
             for (size_t k = 0; k < (size_t)h.n_verts * 3; k++) m = std::fmax(m, fin(h.verts[k]));
         ext[i] = m;
     }
+    return ext;
+}
+static std::vector<float> reach_in_frames(const fw_scene_desc *d, const std::vector<float> &ext) {
+    auto fin = finite_abs;
+    std::vector<float> reach(d->n_shapes, 0.f);
     auto inner = [&](int32_t si) {
         const fw_shape &h = d->shapes[si];
         return (h.kind == FW_SHAPE_CONSTANT_MEDIUM && h.inner >= 0 && (uint32_t)h.inner < d->n_shapes) ? h.inner : si;
@@ -965,11 +1006,6 @@ static std::vector<float> reach_in_frames(const fw_scene_desc *d) {
 }
 
 namespace {
-
-struct ShapeParams { float q3[4] = {0, 0, 0, 0}, q4[4] = {0, 0, 0, 0}; uint32_t kind = 0, flags = 0, aux0 = 0, aux1 = 0; Box box{};
-                     uint32_t wroot_f32 = 0xffffffffu, wroot_q8 = 0xffffffffu;   // meshes: root reference of the wide tree in either encoding
-                     uint32_t ref_root = 0xffffffffu, n_tris = 0;   // meshes: first node of the reference tree in Flattener::ref_blas
-                     Box true_box{}; };   // OF_GATE shapes: a box that really encloses the geometry (object space)
 
 struct Flattener {
     const fw_scene_desc *d;
@@ -1197,40 +1233,34 @@ struct Flattener {
     }
 };
 
-int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
-    if (!desc || !out) return fail(FW_ERR_BAD_ARG, "null argument");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
-    if (desc->n_objects == 0 || !desc->objects) return fail(FW_ERR_EMPTY_SCENE, "No render objects added to scene!");
-    if (desc->n_objects > fw::NODE_MASK) return fail(FW_ERR_UNSUPPORTED, "too many objects");
-    HIPCHK(hipSetDevice(device));
-    const int n_cus_dev = device_cus(device);
-    if (n_cus_dev <= 0) return fail(FW_ERR_HIP, "hipGetDeviceProperties failed");
-    // FIREWORK_TRACE=1: where a scene creation spends its time (host flatten + BVH builds | staging blob | alloc | copy)
-    const Options O = options();
-    const bool trace = O.trace;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(now() - t).count(); };
-    const auto tr0 = now();
-
-    Flattener fl{desc};
-    fl.device = device;
-    fl.frame_reach = reach_in_frames(desc);
-    fw::DeviceBuildTimes dev_times;           // the TLAS builds (the meshes' trees: fl.dev_times)
-    std::vector<float> objs((size_t)desc->n_objects * fw::OBJ_Q * 4, 0.f);
-    std::vector<Box> world(desc->n_objects), true_world(desc->n_objects);
-    std::vector<uint32_t> obj_ref_blas(desc->n_objects, 0xffffffffu);
-    std::vector<uint32_t> obj_wroot_f32(desc->n_objects, 0xffffffffu), obj_wroot_q8(desc->n_objects, 0xffffffffu);
-    std::vector<float> obj_size(desc->n_objects, 0.f);       // the exact walk's far rule: extent of an object (a mesh: of a typical triangle)
+// ---- the object level: everything of a scene that depends on where its objects are — the object records (rotation rows,
+// OF_ROTATED, OF_FLIP), the world / true / grown boxes, the reference's median TLAS with its ranks and gate boxes, the exact walk's rule
+// (far rule, cluster box, rotated mesh frames), hoisting, and the walked TLAS in pair and wide form.  fw_scene_create and fw_scene_update
+// both build it here from the per-shape parameters that creation computes once, so an update equals a creation by construction.
+struct ObjectLevel {
+    std::vector<float> objs, gate, cull, leafb, ref_tlas;
+    std::vector<uint32_t> obj_rank, hoisted;
+    PairBvh tlas_p;
+    uint32_t tlas_root = 0, ref_tlas_nodes = 0, ref_tlas_depth = 0;
+    WideBvh wtlas;
+    uint32_t wtlas_root = 0xffffffffu;
     fw::DExact ex{};
-    bool has_medium = false, has_perlin = false;
-    for (uint32_t i = 0; i < desc->n_objects; i++) {
+    fw::DeviceBuildTimes dev_times;       // the TLAS builds on the device (from BUILD_MIN objects on)
+};
+inline size_t wide_lds_bytes(const WideBvh &t, uint32_t waves) { return (size_t)t.words.size() * 4 + (size_t)waves * (3 * t.depth + 2) * 128 + 4096; }
+
+// sps: per shape index, the parameters of every shape an object uses.  has_mesh: the scene has triangles.  Errors: the median build's
+// (FW_ERR_NAN_BBOX for a non-finite box).
+int object_level(const fw_scene_desc *desc, int device, const Options &O, const std::vector<ShapeParams> &sps, bool has_mesh, ObjectLevel &L) {
+    const uint32_t n_obj = desc->n_objects;
+    std::vector<float> &objs = L.objs;
+    objs.assign((size_t)n_obj * fw::OBJ_Q * 4, 0.f);
+    std::vector<Box> world(n_obj), true_world(n_obj);
+    std::vector<float> obj_size(n_obj, 0.f);       // the exact walk's far rule: extent of an object (a mesh: of a typical triangle)
+    fw::DExact &ex = L.ex;
+    for (uint32_t i = 0; i < n_obj; i++) {
         const fw_object &o = desc->objects[i];
-        ShapeParams sp;
-        int rc = fl.shape_params(o.shape, sp, 0);
-        if (rc) return rc;
+        const ShapeParams &sp = sps[o.shape];
         float rows[3][3];
         rotor_rows(o.rotation, rows);
         uint32_t flags = sp.flags;
@@ -1252,8 +1282,6 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
         };
         world[i] = to_world(sp.box);
         if (flags & fw::OF_GATE) true_world[i] = to_world(sp.true_box);
-        obj_ref_blas[i] = sp.ref_root;
-        if ((sp.kind & 0xffu) == FW_SHAPE_TRIANGLE_MESH) { obj_wroot_f32[i] = sp.wroot_f32; obj_wroot_q8[i] = sp.wroot_q8; }
         {
             const Box &tb = (flags & fw::OF_GATE) ? sp.true_box : sp.box;
             const V3 e = tb.mx - tb.mn;
@@ -1269,7 +1297,6 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
         }
         if (o.flip_normals) flags |= fw::OF_FLIP;
         uint32_t kind = sp.kind & 0xffu, inner = (sp.kind >> 16) & 0xffu;
-        if (kind == FW_SHAPE_CONSTANT_MEDIUM) has_medium = true;
         int32_t material = desc->shapes[o.shape].material;
         float *q = &objs[(size_t)i * fw::OBJ_Q * 4];
         const float pos[3] = {o.position.x, o.position.y, o.position.z};
@@ -1280,26 +1307,19 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
         const uint32_t tail[3] = {(uint32_t)material, sp.aux0, sp.aux1};
         for (int r = 0; r < 3; r++) { q[12 + 4 * r] = rows[r][0]; q[13 + 4 * r] = rows[r][1]; q[14 + 4 * r] = rows[r][2]; q[15 + 4 * r] = bits_f(tail[r]); }
     }
-    // packed hit records: object << prim_bits | primitive must fit 32 bits with all-ones left for MISS
-    uint32_t prim_bits = 3;                                   // rect3d faces 0..5
-    while (prim_bits < 31 && (1ull << prim_bits) < (uint64_t)fl.max_tris) prim_bits++;
-    {
-        uint32_t obj_bits = 1; while (obj_bits < 32 && (1ull << obj_bits) < (uint64_t)desc->n_objects + 1) obj_bits++;
-        if (obj_bits + prim_bits > 32) return fail(FW_ERR_UNSUPPORTED, "objects x triangles-per-mesh exceed the 32-bit hit code");
-    }
     FlatBvh tlas;
-    if (int brc = build_tree(device, fw::BUILD_MEDIAN, world, tlas, nullptr, &dev_times)) return brc;
-    std::vector<uint32_t> obj_rank = reference_ranks(tlas, desc->n_objects);
-    uint32_t ref_tlas_nodes = tlas.count();
-    const std::vector<float> ref_tlas = tlas.nodes;          // the reference's own tree: what k_extend_exact walks
-    const uint32_t ref_tlas_depth = tlas.depth;
+    if (int brc = build_tree(device, fw::BUILD_MEDIAN, world, tlas, nullptr, &L.dev_times)) return brc;
+    L.obj_rank = reference_ranks(tlas, n_obj);
+    L.ref_tlas_nodes = tlas.count();
+    L.ref_tlas = tlas.nodes;          // the reference's own tree: what k_extend_exact walks
+    L.ref_tlas_depth = tlas.depth;
     {   // the exact walk's flag rule (fw_device.h DExact)
-        if (!fl.tri.empty()) ex.mode |= 1u;
+        if (has_mesh) ex.mode |= 1u;
         float min_size = 3.0e38f;
-        for (uint32_t i = 0; i < desc->n_objects; i++) if (obj_size[i] > 0.f) min_size = std::fmin(min_size, obj_size[i]);
+        for (uint32_t i = 0; i < n_obj; i++) if (obj_size[i] > 0.f) min_size = std::fmin(min_size, obj_size[i]);
         if (min_size < 3.0e38f) {
             Box cl{{3e38f, 3e38f, 3e38f}, {-3e38f, -3e38f, -3e38f}};
-            for (uint32_t i = 0; i < desc->n_objects; i++)
+            for (uint32_t i = 0; i < n_obj; i++)
                 if (obj_size[i] > 0.f && obj_size[i] <= 16.f * min_size) cl = box_union(cl, world[i].mn.x <= world[i].mx.x ? world[i] : Box{vmin(world[i].mn, world[i].mx), vmax(world[i].mn, world[i].mx)});
             const V3 c = box_center(cl), h = cl.mx - c;
             const float radius = std::fmax(h.x, std::fmax(h.y, h.z));
@@ -1322,7 +1342,8 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
     // DoubleLeaf: bvh.rs:44-52; the ancestors' boxes are supersets).  The walked trees keep the objects' own boxes (the unions cost
     // part2 26 %: gpurun_out/r04d); every object hit is checked against its reference leaf-node box (obj_gate) before it counts, and
     // a mesh before its rays are parked (fw_kernels.hip: obj_gate_ok).
-    std::vector<float> gate((size_t)desc->n_objects * 8, 0.f);
+    std::vector<float> &gate = L.gate;
+    gate.assign((size_t)n_obj * 8, 0.f);
     std::vector<Box> build_boxes = world, own_boxes = world;
     for (uint32_t i = 0; i < tlas.count(); i++) {
         const float *nd = &tlas.nodes[(size_t)i * 8];
@@ -1347,7 +1368,7 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
     float m_near = m_all;
     if (ex.mode & 2u)
         m_near = std::fmin(m_all, std::fmax(std::fabs(ex.far_c[0]), std::fmax(std::fabs(ex.far_c[1]), std::fabs(ex.far_c[2]))) + ex.far_r);
-    for (uint32_t i = 0; i < desc->n_objects; i++) {             // the walked trees' boxes (grown_by: what a walk must still reach)
+    for (uint32_t i = 0; i < n_obj; i++) {             // the walked trees' boxes (grown_by: what a walk must still reach)
         uint32_t kf; std::memcpy(&kf, &objs[(size_t)i * fw::OBJ_Q * 4 + 3], 4);
         const uint32_t kind = kf & 0xffu, inner = kf >> 24, shape = kind == FW_SHAPE_CONSTANT_MEDIUM ? inner : kind;
         const float ext = box_extent(build_boxes[i]);
@@ -1362,37 +1383,37 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
         build_boxes[i] = grown_by(build_boxes[i], std::fmax(g, gc));
     }
     auto pack_boxes = [&](const std::vector<Box> &bs) {
-        std::vector<float> out((size_t)desc->n_objects * 8, 0.f);
-        for (uint32_t i = 0; i < desc->n_objects; i++) {
+        std::vector<float> out((size_t)n_obj * 8, 0.f);
+        for (uint32_t i = 0; i < n_obj; i++) {
             const Box &b = bs[i];
             float *c = &out[(size_t)i * 8];
             c[0] = b.mn.x; c[1] = b.mn.y; c[2] = b.mn.z; c[4] = b.mx.x; c[5] = b.mx.y; c[6] = b.mx.z;
         }
         return out;
     };
-    const std::vector<float> cull = pack_boxes(own_boxes);       // enclosing world boxes of the objects themselves: the pre-tests of the linear scan (k_extend_linear*)
-    const std::vector<float> leafb = pack_boxes(build_boxes);    // the objects' boxes in the walked trees (k_extend_scan, hoisted_hits)
+    L.cull = pack_boxes(own_boxes);       // enclosing world boxes of the objects themselves: the pre-tests of the linear scan (k_extend_linear*)
+    L.leafb = pack_boxes(build_boxes);    // the objects' boxes in the walked trees (k_extend_scan, hoisted_hits)
     // Hoisting: an object whose box covers most of the scene (part2's r = 5000 fog medium) is met by nearly every ray, so in
     // the tree its leaf is one more divergent leaf test per ray.  Scenes without meshes and too many objects for the scan keep
     // such objects out of the WALKED tree; the kernels test them for every ray before the walk, with a wave-uniform index
     // (hoisted_hits in fw_kernels.hip: same own-box test, same tie rule, so the same result as the leaf would give).
-    std::vector<uint32_t> hoisted;
-    if (use_sah() && desc->n_objects > 8 && fl.tri.empty() && !O.no_hoist) {
+    std::vector<uint32_t> &hoisted = L.hoisted;
+    if (use_sah() && n_obj > 8 && !has_mesh && !O.no_hoist) {
         Box root = build_boxes[0];
         for (const Box &b : build_boxes) root = box_union(root, b);
         const float ra = box_area(root);
-        for (uint32_t i = 0; i < desc->n_objects && hoisted.size() < 4; i++)
+        for (uint32_t i = 0; i < n_obj && hoisted.size() < 4; i++)
             if (box_area(build_boxes[i]) >= 0.5f * ra) hoisted.push_back(i);
-        if (desc->n_objects - hoisted.size() < 2) hoisted.clear();
+        if (n_obj - hoisted.size() < 2) hoisted.clear();
     }
     if (use_sah()) {
         FlatBvh sah;
-        if (hoisted.empty()) { if (int brc = build_tree(device, fw::BUILD_SAH, build_boxes, sah, nullptr, &dev_times)) return brc; }
+        if (hoisted.empty()) { if (int brc = build_tree(device, fw::BUILD_SAH, build_boxes, sah, nullptr, &L.dev_times)) return brc; }
         else {
             std::vector<Box> sub; std::vector<uint32_t> ids;
-            for (uint32_t i = 0; i < desc->n_objects; i++)
+            for (uint32_t i = 0; i < n_obj; i++)
                 if (std::find(hoisted.begin(), hoisted.end(), i) == hoisted.end()) { sub.push_back(build_boxes[i]); ids.push_back(i); }
-            if (int brc = build_tree(device, fw::BUILD_SAH, sub, sah, nullptr, &dev_times)) return brc;
+            if (int brc = build_tree(device, fw::BUILD_SAH, sub, sah, nullptr, &L.dev_times)) return brc;
             for (uint32_t i = 0; i < sah.count(); i++) {      // leaf items: positions in `sub` -> object ids
                 float *nd = &sah.nodes[(size_t)i * 8];
                 uint32_t A, B; std::memcpy(&A, nd + 3, 4); std::memcpy(&B, nd + 7, 4);
@@ -1403,18 +1424,92 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
         }
         tlas = std::move(sah);
     }
-    PairBvh tlas_p;
-    const uint32_t tlas_root = pair_convert(tlas, build_boxes, tlas_p);
+    L.tlas_root = pair_convert(tlas, build_boxes, L.tlas_p);
     // WIDE nodes (fw_device.h) for the LDS-resident walks, where they fit a CU's LDS next to the walks' stacks: f32 nodes first,
     // quantised ones for a BLAS too big for those.  Option WIDE=0: none (the pair-node kernels, A/B); =f32 / =q8 force an encoding.
     const bool wide_on = use_sah() && O.wide != 0;
-    WideBvh wtlas; wtlas.fmt = fw::WIDE_F32;
-    uint32_t wtlas_root = 0xffffffffu;
-    auto wide_lds_bytes = [&](const WideBvh &t, uint32_t waves) { return (size_t)t.words.size() * 4 + (size_t)waves * (3 * t.depth + 2) * 128 + 4096; };
-    if (wide_on && fl.tri.empty() && desc->n_objects > 8) {
+    WideBvh &wtlas = L.wtlas; wtlas.fmt = fw::WIDE_F32;
+    uint32_t &wtlas_root = L.wtlas_root;
+    if (wide_on && !has_mesh && n_obj > 8) {
         wtlas_root = wide_convert(tlas, build_boxes, wtlas);     // (hoisted objects are not in `tlas`; its leaves hold object ids)
         if (wtlas_root == 0xffffffffu || wide_lds_bytes(wtlas, 8) > fw::LDS_TREE_LIMIT) { wtlas.words.clear(); wtlas_root = 0xffffffffu; }
     }
+    return FW_OK;
+}
+
+// every scene field the object level sets.  dev: where its sections live on the device, in this order: objs, tlas_p, obj_rank, gate, cull,
+// ref_tlas, leafb, wtlas (creation: in the scene's blob; an update: in sc->obj_data)
+void apply_object_level(fw_scene *sc, const ObjectLevel &L, const uint8_t *const dev[8]) {
+    fw::DScene &d = sc->d;
+    d.obj = (const float4 *)dev[0]; d.tlas = (const float4 *)dev[1]; d.obj_rank = (const uint32_t *)dev[2]; d.obj_gate = (const float4 *)dev[3];
+    d.obj_cull = (const float4 *)dev[4]; d.ref_tlas = (const float4 *)dev[5]; d.obj_leaf = (const float4 *)dev[6];
+    d.wtlas = L.wtlas.words.empty() ? nullptr : (const uint32_t *)dev[7];
+    d.wtlas_root = L.wtlas_root; d.tlas_root = L.tlas_root;
+    d.n_hoisted = (uint32_t)L.hoisted.size();
+    for (size_t i = 0; i < 4; i++) d.hoisted[i] = i < L.hoisted.size() ? L.hoisted[i] : 0u;
+    sc->wtlas_fmt = L.wtlas.words.empty() ? fw::WIDE_NONE : fw::WIDE_F32;
+    sc->wtlas_nodes = L.wtlas.count(); sc->wtlas_depth = L.wtlas.depth;
+    sc->ex = L.ex; sc->ref_tlas_depth = L.ref_tlas_depth;
+    sc->tlas_nodes = L.ref_tlas_nodes;    // reported: the reference topology (bvh.rs)
+    sc->tlas_depth = L.tlas_p.depth; sc->tlas_pair_nodes = L.tlas_p.count();
+}
+
+// reach: the frame_reach to build the meshes' walked trees with (nullptr: reach_in_frames of desc; fw_scene_update passes what a rebuild needs)
+int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out, const std::vector<float> *reach = nullptr) {
+    if (!desc || !out) return fail(FW_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    if (desc->n_objects == 0 || !desc->objects) return fail(FW_ERR_EMPTY_SCENE, "No render objects added to scene!");
+    if (desc->n_objects > fw::NODE_MASK) return fail(FW_ERR_UNSUPPORTED, "too many objects");
+    HIPCHK(hipSetDevice(device));
+    const int n_cus_dev = device_cus(device);
+    if (n_cus_dev <= 0) return fail(FW_ERR_HIP, "hipGetDeviceProperties failed");
+    // FIREWORK_TRACE=1: where a scene creation spends its time (host flatten + BVH builds | staging blob | alloc | copy)
+    const Options O = options();
+    const bool trace = O.trace;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(now() - t).count(); };
+    const auto tr0 = now();
+
+    Flattener fl{desc};
+    fl.device = device;
+    std::vector<float> ext = shape_extents(desc);
+    fl.frame_reach = reach ? *reach : reach_in_frames(desc, ext);
+    // every shape an object uses, in the objects' order (a mesh is flattened and its trees built where its first user is met)
+    std::vector<ShapeParams> sps(desc->n_shapes);
+    {
+        std::vector<uint8_t> known(desc->n_shapes, 0);
+        for (uint32_t i = 0; i < desc->n_objects; i++) {
+            const int32_t si = desc->objects[i].shape;
+            if (si >= 0 && (uint32_t)si < desc->n_shapes && known[si]) continue;
+            ShapeParams sp;
+            if (int rc = fl.shape_params(si, sp, 0)) return rc;
+            sps[si] = sp; known[si] = 1;
+        }
+    }
+    std::vector<uint32_t> obj_ref_blas(desc->n_objects, 0xffffffffu);
+    std::vector<uint32_t> obj_wroot_f32(desc->n_objects, 0xffffffffu), obj_wroot_q8(desc->n_objects, 0xffffffffu);
+    bool has_medium = false, has_perlin = false;
+    for (uint32_t i = 0; i < desc->n_objects; i++) {
+        const ShapeParams &sp = sps[desc->objects[i].shape];
+        obj_ref_blas[i] = sp.ref_root;
+        if ((sp.kind & 0xffu) == FW_SHAPE_TRIANGLE_MESH) { obj_wroot_f32[i] = sp.wroot_f32; obj_wroot_q8[i] = sp.wroot_q8; }
+        if ((sp.kind & 0xffu) == FW_SHAPE_CONSTANT_MEDIUM) has_medium = true;
+    }
+    // packed hit records: object << prim_bits | primitive must fit 32 bits with all-ones left for MISS
+    uint32_t prim_bits = 3;                                   // rect3d faces 0..5
+    while (prim_bits < 31 && (1ull << prim_bits) < (uint64_t)fl.max_tris) prim_bits++;
+    {
+        uint32_t obj_bits = 1; while (obj_bits < 32 && (1ull << obj_bits) < (uint64_t)desc->n_objects + 1) obj_bits++;
+        if (obj_bits + prim_bits > 32) return fail(FW_ERR_UNSUPPORTED, "objects x triangles-per-mesh exceed the 32-bit hit code");
+    }
+    const auto tl0 = now();
+    ObjectLevel L;
+    if (int rc = object_level(desc, device, O, sps, !fl.tri.empty(), L)) return rc;
+    const double ms_objects = ms_since(tl0);
+    const bool wide_on = use_sah() && O.wide != 0;
     int wblas_fmt = fw::WIDE_NONE;
     if (wide_on && !fl.tri.empty()) {
         const bool force_q8 = O.wide == 2, force_f32 = O.wide == 1;
@@ -1487,7 +1582,7 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
     if (e.kind == FW_ENV_HDR && (!e.hdr_rgb || !e.hdr_w || !e.hdr_h)) return fail(FW_ERR_BAD_ARG, "HdrEnv without pixels");
 
     // stack depth the kernels will be given
-    if (tlas_p.depth + 1 + fl.blas_depth + 1 > 120) return fail(FW_ERR_BVH_DEPTH, "BVH deeper than the LDS traversal stack (120 levels)");
+    if (L.tlas_p.depth + 1 + fl.blas_depth + 1 > 120) return fail(FW_ERR_BVH_DEPTH, "BVH deeper than the LDS traversal stack (120 levels)");
 
     fw_scene *sc = new (std::nothrow) fw_scene();
     if (!sc) return fail(FW_ERR_OOM, "host allocation failed");
@@ -1498,17 +1593,17 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
     // one-shot render): sections are 256-byte aligned inside a host staging blob
     struct Sec { const void *src; size_t bytes, off; };
     Sec secs[21] = {
-        {objs.data(), objs.size() * 4, 0}, {tlas_p.nodes.data(), tlas_p.nodes.size() * 4, 0}, {fl.blas.nodes.data(), fl.blas.nodes.size() * 4, 0},
+        {L.objs.data(), L.objs.size() * 4, 0}, {L.tlas_p.nodes.data(), L.tlas_p.nodes.size() * 4, 0}, {fl.blas.nodes.data(), fl.blas.nodes.size() * 4, 0},
         {fl.tri.data(), fl.tri.size() * 4, 0}, {fl.any_attr ? fl.tri_attr.data() : nullptr, fl.any_attr ? fl.tri_attr.size() * 4 : 0, 0},
-        {fl.tri_rank.data(), fl.tri_rank.size() * 4, 0}, {obj_rank.data(), obj_rank.size() * 4, 0}, {gate.data(), gate.size() * 4, 0},
+        {fl.tri_rank.data(), fl.tri_rank.size() * 4, 0}, {L.obj_rank.data(), L.obj_rank.size() * 4, 0}, {L.gate.data(), L.gate.size() * 4, 0},
         {mats.data(), mats.size() * 4, 0}, {texs.data(), texs.size() * 4, 0}, {images.data(), images.size(), 0},
         // the HDR map as 16-byte texels (rgb + pad), written straight into the blob below: a 12-byte texel straddles a 32-byte
         // sector in two offsets of eight, and a miss's lookup is one gather per path out of 100 MB
         {nullptr, e.kind == FW_ENV_HDR ? (size_t)e.hdr_w * e.hdr_h * 4 * 4 : 0, 0},
-        {cull.data(), cull.size() * 4, 0},
-        {ref_tlas.data(), ref_tlas.size() * 4, 0}, {fl.ref_blas.data(), fl.ref_blas.size() * 4, 0}, {obj_ref_blas.data(), obj_ref_blas.size() * 4, 0},
-        {leafb.data(), leafb.size() * 4, 0},
-        {wblas_fmt ? wblas.words.data() : nullptr, wblas_fmt ? wblas.words.size() * 4 : 0, 0}, {wtlas.words.data(), wtlas.words.size() * 4, 0},
+        {L.cull.data(), L.cull.size() * 4, 0},
+        {L.ref_tlas.data(), L.ref_tlas.size() * 4, 0}, {fl.ref_blas.data(), fl.ref_blas.size() * 4, 0}, {obj_ref_blas.data(), obj_ref_blas.size() * 4, 0},
+        {L.leafb.data(), L.leafb.size() * 4, 0},
+        {wblas_fmt ? wblas.words.data() : nullptr, wblas_fmt ? wblas.words.size() * 4 : 0, 0}, {L.wtlas.words.data(), L.wtlas.words.size() * 4, 0},
         {obj_wroot.data(), obj_wroot.size() * 4, 0}, {fl.tri_gate.data(), fl.tri_gate.size() * 4, 0}};
     size_t total = 0;
     for (Sec &x : secs) { x.off = total; total += (x.bytes + 255) & ~(size_t)255; }
@@ -1521,14 +1616,7 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
     if ((rc = init_device_locked(ws, device)) != FW_OK) { delete sc; return rc; }      // a host that never called fw_init pays for the device here, once
     // the blob is assembled in pinned host memory (grown on demand, kept per device) and copied by a kernel on the null
     // stream; renders of this scene wait for ws->ev_upload in stream order, the host never blocks here
-    (void)hipEventSynchronize(ws->ev_upload);          // the previous upload has read the staging buffer (long done)
-    if (ws->staging_bytes < total) {
-        if (ws->staging) (void)hipHostFree(ws->staging);
-        ws->staging = nullptr; ws->staging_bytes = 0;
-        const size_t want = std::max<size_t>(total + total / 4, 1 << 20);
-        if (hipHostMalloc(&ws->staging, want, hipHostMallocDefault) != hipSuccess) { delete sc; return fail(FW_ERR_OOM, "pinned staging allocation failed"); }
-        ws->staging_bytes = want;
-    }
+    if ((rc = staging_reserve_locked(ws, total)) != FW_OK) { delete sc; return rc; }
     uint8_t *blob = (uint8_t *)ws->staging;
     size_t prev_end = 0;
     for (const Sec &x : secs) {       // sections + zeroed padding between them
@@ -1560,34 +1648,32 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
                                           fl.tri.size() / 12, host_build_threads(), fl.ms_gather, fl.ms_sah, fl.ms_ref, fl.ms_gate, fl.ms_pair + fl.ms_wide);
     if (trace && !fl.tri.empty() && fl.dev_times.kernel_ms > 0) fprintf(stderr, "[firework] scene_create: meshes (%zu triangles, trees on the device): gather %.2f ms | both trees %.2f (upload %.2f | kernels %.2f | copy back %.2f) | wait + ranks %.2f | gate boxes %.2f | pair + wide f32 + wide q8 side by side %.2f\n",
                                           fl.tri.size() / 12, fl.ms_gather, fl.ms_sah, fl.dev_times.upload_ms, fl.dev_times.kernel_ms, fl.dev_times.copy_ms, fl.ms_ref, fl.ms_gate, fl.ms_pair + fl.ms_wide);
-    if (trace && dev_times.kernel_ms > 0) fprintf(stderr, "[firework] scene_create: TLAS trees on the device (%u objects): upload %.2f ms | kernels %.2f | copy back %.2f\n",
-                                                  desc->n_objects, dev_times.upload_ms, dev_times.kernel_ms, dev_times.copy_ms);
+    if (trace && L.dev_times.kernel_ms > 0) fprintf(stderr, "[firework] scene_create: TLAS trees on the device (%u objects): upload %.2f ms | kernels %.2f | copy back %.2f\n",
+                                                    desc->n_objects, L.dev_times.upload_ms, L.dev_times.kernel_ms, L.dev_times.copy_ms);
     if (rc) { delete sc; return rc; }
     const uint8_t *base = (const uint8_t *)sc->data.p;
     fw::DScene &d = sc->d;
-    d.obj = (const float4 *)(base + secs[0].off); d.tlas = (const float4 *)(base + secs[1].off); d.blas = (const float4 *)(base + secs[2].off);
+    d.blas = (const float4 *)(base + secs[2].off);
     d.tri = (const float4 *)(base + secs[3].off); d.tri_nrm = (const float4 *)(base + secs[4].off);
-    d.tri_rank = (const uint32_t *)(base + secs[5].off); d.obj_rank = (const uint32_t *)(base + secs[6].off); d.obj_gate = (const float4 *)(base + secs[7].off);
+    d.tri_rank = (const uint32_t *)(base + secs[5].off);
     d.mat = (const float4 *)(base + secs[8].off); d.tex = (const float4 *)(base + secs[9].off); d.images = base + secs[10].off;
     const float *hdr_dev = (const float *)(base + secs[11].off);
-    d.obj_cull = (const float4 *)(base + secs[12].off);
-    d.ref_tlas = (const float4 *)(base + secs[13].off); d.ref_blas = (const float4 *)(base + secs[14].off);
+    d.ref_blas = (const float4 *)(base + secs[14].off);
     d.obj_ref_blas = (const uint32_t *)(base + secs[15].off);
-    d.obj_leaf = (const float4 *)(base + secs[16].off);
     d.wblas = wblas_fmt ? (const uint32_t *)(base + secs[17].off) : nullptr;
-    d.wtlas = wtlas.words.empty() ? nullptr : (const uint32_t *)(base + secs[18].off);
     d.obj_wroot = (const uint32_t *)(base + secs[19].off);
     d.tri_gate = (const float4 *)(base + secs[20].off);
-    d.wtlas_root = wtlas_root;
-    sc->wblas_fmt = wblas_fmt; sc->wtlas_fmt = wtlas.words.empty() ? fw::WIDE_NONE : fw::WIDE_F32;
-    sc->wblas_nodes = wblas_fmt ? wblas.count() : 0; sc->wtlas_nodes = wtlas.count();
-    sc->wblas_depth = wblas_fmt ? wblas.depth : 0; sc->wtlas_depth = wtlas.depth;
-    sc->ex = ex; sc->ref_tlas_depth = ref_tlas_depth; sc->ref_blas_depth = fl.ref_blas_depth;
+    {
+        const uint8_t *obj_dev[8] = {base + secs[0].off, base + secs[1].off, base + secs[6].off, base + secs[7].off, base + secs[12].off, base + secs[13].off, base + secs[16].off, base + secs[18].off};
+        apply_object_level(sc, L, obj_dev);
+    }
+    sc->wblas_fmt = wblas_fmt;
+    sc->wblas_nodes = wblas_fmt ? wblas.count() : 0;
+    sc->wblas_depth = wblas_fmt ? wblas.depth : 0;
+    sc->ref_blas_depth = fl.ref_blas_depth;
     d.n_objects = desc->n_objects; d.has_medium = has_medium ? 1u : 0u; d.has_perlin = has_perlin ? 1u : 0u; d.has_mesh = fl.tri.empty() ? 0u : 1u;
-    d.prim_bits = prim_bits; d.tlas_root = tlas_root;
+    d.prim_bits = prim_bits;
     d.soft_shear = O.soft_shear_log2 > 0 ? std::ldexp(1.f, -O.soft_shear_log2) : 0.f;
-    d.n_hoisted = (uint32_t)hoisted.size();
-    for (size_t i = 0; i < 4; i++) d.hoisted[i] = i < hoisted.size() ? hoisted[i] : 0u;
     d.env.kind = e.kind;
     d.env.color[0] = e.color.x; d.env.color[1] = e.color.y; d.env.color[2] = e.color.z;
     d.env.zenith[0] = e.zenith.x; d.env.zenith[1] = e.zenith.y; d.env.zenith[2] = e.zenith.z;
@@ -1615,7 +1701,7 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
     sc->simple_shapes = true;
     sc->simple_set = true; sc->simple_but_meshes = true;
     for (uint32_t i = 0; i < desc->n_objects; i++) {
-        uint32_t kf; std::memcpy(&kf, &objs[(size_t)i * fw::OBJ_Q * 4 + 3], 4);
+        uint32_t kf; std::memcpy(&kf, &L.objs[(size_t)i * fw::OBJ_Q * 4 + 3], 4);
         if ((kf & 0xffu) > 4u) sc->simple_shapes = false;
         if ((kf & 0xffu) > 5u) sc->simple_but_meshes = false;
         if ((kf & 0xffu) > 4u && !((kf & 0xffu) == FW_SHAPE_CONSTANT_MEDIUM && (kf >> 24) == FW_SHAPE_SPHERE)) sc->simple_set = false;
@@ -1624,14 +1710,140 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out) {
     sc->n_defer = 0;
     if (!has_medium && fl.tri.empty())
         for (uint32_t i = desc->n_objects; i-- > 0 && sc->n_defer < 2u;) {
-            uint32_t kf; std::memcpy(&kf, &objs[(size_t)i * fw::OBJ_Q * 4 + 3], 4);
+            uint32_t kf; std::memcpy(&kf, &L.objs[(size_t)i * fw::OBJ_Q * 4 + 3], 4);
             if ((kf & 0xffu) == (uint32_t)FW_SHAPE_RECT3D && (((kf >> 8) & 0xffffu) & fw::OF_CULL0) && !(((kf >> 8) & 0xffffu) & fw::OF_GATE)) sc->n_defer++; else break;
         }
-    sc->tlas_nodes = ref_tlas_nodes; sc->blas_nodes = fl.ref_blas_nodes;   // reported: the reference topology (bvh.rs)
-    sc->tlas_depth = tlas_p.depth; sc->blas_depth = fl.blas_depth;
-    sc->blas_pair_nodes = fl.blas.count(); sc->tlas_pair_nodes = tlas_p.count(); sc->max_tris = fl.max_tris; sc->n_tris = (uint32_t)(fl.tri.size() / 12);
+    sc->blas_nodes = fl.ref_blas_nodes;   // reported: the reference topology (bvh.rs); the TLAS's: apply_object_level
+    sc->blas_depth = fl.blas_depth;
+    sc->blas_pair_nodes = fl.blas.count(); sc->max_tris = fl.max_tris; sc->n_tris = (uint32_t)(fl.tri.size() / 12);
     sc->n_mat = desc->n_materials; sc->n_tex = desc->n_textures;
+    {   // what fw_scene_update needs
+        SceneKeep &k = sc->keep;
+        k.obj_shape.resize(desc->n_objects);
+        for (uint32_t i = 0; i < desc->n_objects; i++) k.obj_shape[i] = desc->objects[i].shape;
+        k.shapes.assign(desc->shapes, desc->shapes + desc->n_shapes);
+        if (desc->n_materials) k.materials.assign(desc->materials, desc->materials + desc->n_materials);
+        if (desc->n_textures) k.textures.assign(desc->textures, desc->textures + desc->n_textures);
+        k.env = desc->environment;
+        k.sp = std::move(sps); k.ext = std::move(ext); k.reach = fl.frame_reach;
+    }
+    sc->blob_bytes = total; sc->ms_objects = ms_objects; sc->ms_objects_dev = L.dev_times.upload_ms + L.dev_times.kernel_ms + L.dev_times.copy_ms;
     *out = sc;
+    return FW_OK;
+}
+
+// ---- fw_scene_update ----------------------------------------------------------------------------------------------
+// FW_OK iff `d` differs from the description the scene was made from in its objects' placements alone: every field that is not a pointer
+// compared bit for bit, of the pointers only whether they are null (the arrays' contents are the caller's promise)
+int check_same_scene(const SceneKeep &k, const fw_scene_desc *d) {
+    auto differs = [](const char *what) { return fail(FW_ERR_BAD_ARG, std::string("fw_scene_update: ") + what + " differs from the scene's"); };
+    if (d->n_objects != k.obj_shape.size() || d->n_shapes != k.shapes.size() || d->n_materials != k.materials.size() || d->n_textures != k.textures.size())
+        return differs("the number of objects, shapes, materials or textures");
+    if (!d->objects || (d->n_shapes && !d->shapes) || (d->n_materials && !d->materials) || (d->n_textures && !d->textures)) return fail(FW_ERR_BAD_ARG, "null argument");
+    auto same = [](const auto &x, const auto &y) { return std::memcmp(&x, &y, sizeof x) == 0; };
+    auto same_null = [](const void *x, const void *y) { return (x == nullptr) == (y == nullptr); };
+    for (uint32_t i = 0; i < d->n_objects; i++) if (d->objects[i].shape != k.obj_shape[i]) return differs("an object's shape index");
+    for (uint32_t i = 0; i < d->n_shapes; i++) {
+        const fw_shape &a = d->shapes[i], &b = k.shapes[i];
+        if (!(same(a.kind, b.kind) && same(a.material, b.material) && same(a.radius, b.radius) && same(a.height, b.height) && same(a.phi_max, b.phi_max)
+              && same(a.inner_radius, b.inner_radius) && same(a.a_min, b.a_min) && same(a.a_max, b.a_max) && same(a.b_min, b.b_min) && same(a.b_max, b.b_max)
+              && same(a.k, b.k) && same(a.flip_normal, b.flip_normal) && same(a.pos, b.pos) && same(a.size, b.size) && same(a.n_verts, b.n_verts)
+              && same(a.n_indices, b.n_indices) && same(a.inner, b.inner) && same(a.density, b.density) && same_null(a.verts, b.verts)
+              && same_null(a.indices, b.indices) && same_null(a.normals, b.normals) && same_null(a.uvs, b.uvs))) return differs("a shape");
+    }
+    for (uint32_t i = 0; i < d->n_materials; i++) {
+        const fw_material &a = d->materials[i], &b = k.materials[i];
+        if (!(same(a.kind, b.kind) && same(a.texture, b.texture) && same(a.albedo, b.albedo) && same(a.roughness, b.roughness) && same(a.ref_idx, b.ref_idx)))
+            return differs("a material");
+    }
+    for (uint32_t i = 0; i < d->n_textures; i++) {
+        const fw_texture &a = d->textures[i], &b = k.textures[i];
+        if (!(same(a.kind, b.kind) && same(a.color, b.color) && same(a.scale, b.scale) && same(a.depth, b.depth) && same(a.odd, b.odd) && same(a.even, b.even)
+              && same(a.img_w, b.img_w) && same(a.img_h, b.img_h) && same_null(a.img_rgb8, b.img_rgb8))) return differs("a texture");
+    }
+    const fw_environment &a = d->environment, &b = k.env;
+    if (!(same(a.kind, b.kind) && same(a.color, b.color) && same(a.zenith, b.zenith) && same(a.horizon, b.horizon) && same(a.hdr_w, b.hdr_w) && same(a.hdr_h, b.hdr_h)
+          && same_null(a.hdr_rgb, b.hdr_rgb))) return differs("the environment");
+    return FW_OK;
+}
+
+int update_scene_impl(fw_scene *sc, const fw_scene_desc *desc) {
+    if (!sc || !desc) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = check_same_scene(sc->keep, desc)) return rc;
+    HIPCHK(hipSetDevice(sc->device));
+    const Options O = options();
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(now() - t).count(); };
+    const SceneKeep &k = sc->keep;
+    // A mesh's walked boxes grew by 2^-21 of its reach (reach_in_frames), which every object's position enters.  Where the new placements
+    // raise it above what the mesh's trees were built with, the scene is re-created (below); a lower reach keeps the trees (boxes grown by
+    // more than needed cull nothing a walk must reach).
+    std::vector<float> reach = k.reach;
+    uint32_t raised = 0, n_meshes = 0;
+    {
+        const std::vector<float> want = reach_in_frames(desc, k.ext);
+        std::vector<uint8_t> is_mesh(desc->n_shapes, 0);     // the meshes creation flattened: an object's shape, or a medium's inner one
+        for (int32_t si : k.obj_shape) {
+            const fw_shape &s = desc->shapes[si];
+            if (s.kind == FW_SHAPE_TRIANGLE_MESH) is_mesh[si] = 1;
+            else if (s.kind == FW_SHAPE_CONSTANT_MEDIUM && s.inner >= 0 && (uint32_t)s.inner < desc->n_shapes && desc->shapes[s.inner].kind == FW_SHAPE_TRIANGLE_MESH) is_mesh[s.inner] = 1;
+        }
+        for (uint32_t si = 0; si < desc->n_shapes; si++) {
+            n_meshes += is_mesh[si];
+            if (is_mesh[si] && want[si] > reach[si]) { reach[si] = want[si]; raised++; }
+        }
+    }
+    if (raised) {
+        // the meshes' trees share one array per form (pair, wide f32, wide q8) and their sizes change: the whole scene is re-created — every
+        // mesh flattened and its trees built again, the textures and environment uploaded again — with the raised reach (the other meshes
+        // at their kept reach, so their trees come out as they were), and the new scene takes the old one's place behind this handle
+        const auto t0 = now();
+        fw_scene *ns = nullptr;
+        if (int rc = create_scene_impl(desc, sc->device, &ns, &reach)) return rc;
+        DevBuf old_data = sc->data, old_obj = sc->obj_data;
+        *sc = *ns;                                     // (the handle stays the caller's; its DevBufs now name the new allocations)
+        ns->data = old_data; ns->obj_data = old_obj;   // ... and the old ones go with `ns`
+        fw_scene_destroy(ns);
+        if (O.trace) fprintf(stderr, "[firework] scene_update: %u objects, TLAS build %.2f ms host, %.2f ms device, %u meshes rebuilt, %zu B uploaded, %u hoisted (scene re-created: the reach of %u meshes rose; %.2f ms)\n",
+                             desc->n_objects, sc->ms_objects, sc->ms_objects_dev, n_meshes, sc->blob_bytes, sc->d.n_hoisted, raised, ms_since(t0));
+        return FW_OK;
+    }
+    const auto t0 = now();
+    ObjectLevel L;
+    if (int rc = object_level(desc, sc->device, O, k.sp, sc->d.has_mesh != 0, L)) return rc;
+    if (L.tlas_p.depth + 1 + sc->blas_depth + 1 > 120) return fail(FW_ERR_BVH_DEPTH, "BVH deeper than the LDS traversal stack (120 levels)");
+    const double ms_objects = ms_since(t0);
+    // the object-level sections, 256-byte aligned, in one allocation of the scene's own (grown on demand, reused by later updates)
+    struct Sec { const void *src; size_t bytes, off; };
+    Sec secs[8] = {{L.objs.data(), L.objs.size() * 4, 0}, {L.tlas_p.nodes.data(), L.tlas_p.nodes.size() * 4, 0}, {L.obj_rank.data(), L.obj_rank.size() * 4, 0},
+                   {L.gate.data(), L.gate.size() * 4, 0}, {L.cull.data(), L.cull.size() * 4, 0}, {L.ref_tlas.data(), L.ref_tlas.size() * 4, 0},
+                   {L.leafb.data(), L.leafb.size() * 4, 0}, {L.wtlas.words.data(), L.wtlas.words.size() * 4, 0}};
+    size_t total = 0;
+    for (Sec &x : secs) { x.off = total; total += (x.bytes + 255) & ~(size_t)255; }
+    total = std::max<size_t>(total, 256);
+    Workspace *ws = workspace_for(sc->device);
+    if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
+    std::lock_guard<std::mutex> ws_guard(ws->mu);
+    if (int rc = init_device_locked(ws, sc->device)) return rc;
+    if (int rc = staging_reserve_locked(ws, total)) return rc;
+    if (sc->obj_data.bytes < total || !sc->obj_data.p) {
+        DevBuf nb;
+        if (int rc = nb.alloc(total)) return rc;
+        sc->obj_data.release();                      // (no render of this scene is in flight: every call drains its stream before it returns)
+        sc->obj_data = nb;
+    }
+    uint8_t *blob = (uint8_t *)ws->staging;
+    std::memset(blob, 0, total);
+    for (const Sec &x : secs) if (x.bytes) std::memcpy(blob + x.off, x.src, x.bytes);
+    fw::launch_upload(ws->upload_stream, blob, sc->obj_data.p, total);
+    if (hipEventRecord(ws->ev_upload, ws->upload_stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail(FW_ERR_HIP, "scene upload failed");
+    const uint8_t *base = (const uint8_t *)sc->obj_data.p;
+    const uint8_t *dev[8];
+    for (int s = 0; s < 8; s++) dev[s] = base + secs[s].off;
+    apply_object_level(sc, L, dev);
+    sc->ms_objects = ms_objects; sc->ms_objects_dev = L.dev_times.upload_ms + L.dev_times.kernel_ms + L.dev_times.copy_ms;
+    if (O.trace) fprintf(stderr, "[firework] scene_update: %u objects, TLAS build %.2f ms host, %.2f ms device, %u meshes rebuilt, %zu B uploaded, %u hoisted\n",
+                         desc->n_objects, sc->ms_objects, sc->ms_objects_dev, 0u, total, sc->d.n_hoisted);
     return FW_OK;
 }
 
@@ -2824,6 +3036,12 @@ int fw_scene_create(const fw_scene_desc *desc, int device, fw_scene **out) {
     try { return create_scene_impl(desc, device, out); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_scene_create"); }
+}
+
+int fw_scene_update(fw_scene *scene, const fw_scene_desc *desc) {
+    try { return update_scene_impl(scene, desc); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_scene_update"); }
 }
 
 void fw_release_workspace(int device) {

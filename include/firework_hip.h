@@ -255,6 +255,24 @@ int fw_init(int device, uint64_t arena_bytes);
 int fw_scene_create(const fw_scene_desc *desc, int device, fw_scene **out);
 void fw_scene_destroy(fw_scene *scene);
 
+/* Moves the objects of a resident scene (additive at ABI 8): `desc` describes the scene `scene` was created from, and only the
+   `position`, `rotation` and `flip_normals` of its objects may differ.  After FW_OK every later call on `scene` gives bit for bit
+   what the same call gives on the scene fw_scene_create(desc) makes, with the same options in force at creation, update and call.
+   The object level alone is redone — object records, world boxes, the top-level trees — and only its sections are uploaded; the
+   meshes are not flattened again, and textures and environment maps are not uploaded again.  Exception: where the new placements
+   reach coordinates larger than a mesh's trees were built for, the whole scene is re-created from desc behind the same handle (every
+   mesh flattened again, everything uploaded again).  Memory: the first update moves the object-level sections into an
+   allocation of the scene's own; their first copies stay, unread, in the scene's creation allocation until the scene is destroyed
+   (about 300 bytes per object: records, boxes, ranks and both top-level trees).
+   The caller promises that the arrays desc points to (vertices, indices, normals, uvs, image and HDR pixels) hold what they held at
+   creation: they are not compared.  Errors, before any device state is touched (a failed update leaves the scene as it was):
+   FW_ERR_BAD_ARG for a NULL argument, another object, shape, material or texture count, another objects[i].shape, any other
+   difference in a field of a shape, material, texture or the environment that is not a pointer, or in whether a pointer is NULL;
+   a placement fw_scene_create rejects gets the status create returns for desc (a NaN position: FW_ERR_NAN_BBOX).
+   Synchronisation is fw_scene_create's: the upload is queued on the library's upload stream and every later call on the device waits
+   for it in stream order.  An update must not run at the same time as another call on the same scene. */
+int fw_scene_update(fw_scene *scene, const fw_scene_desc *desc);
+
 /* The hot path: render.rs:123-161 on an uploaded scene.
    Any output pointer may be NULL.  Sizes are N*3 with N = n_pixels (or width*height),
    index order = pixel_ids order, row 0 = image top (util.rs:31-33):
