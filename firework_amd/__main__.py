@@ -9,7 +9,9 @@ so `-o` is required here.  Extra flags (not in the reference): --width/--height/
 pass and resume from it: the finished image is bit-identical to an uninterrupted render), --adaptive TOL [--min-samples M]
 (adaptive sampling up to -s samples per pixel; not with --progressive / --checkpoint), --orbit N (a turntable: N views evenly spaced
 in azimuth around the fixed camera's look-at point, rendered in one call; -o must hold a format field, e.g. 'frame_{:03d}.png', which
-receives the view number; not with --progressive / --checkpoint / --adaptive)."""
+receives the view number; not with --progressive / --checkpoint / --adaptive), --denoise [L] (filter the frame with L a-trous
+iterations, default 5, guided by first-hit albedo / normal / position buffers; with a plain render or --adaptive, whose moments and
+per-pixel counts it uses; not with --progressive / --checkpoint / --orbit)."""
 import argparse
 import sys
 import time
@@ -32,9 +34,19 @@ def main(argv=None):
     ap.add_argument("--min-samples", type=int, default=16, metavar="M", help="with --adaptive: the samples every pixel gets first")
     ap.add_argument("--orbit", type=int, default=0, metavar="N",
                     help="render N views around the look-at point in one call; -o must hold a {} field for the view number")
+    ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="L",
+                    help="denoise the frame with L a-trous iterations (default 5) guided by first-hit albedo / normal / position buffers")
+    ap.add_argument("--aov-samples", type=int, default=8, metavar="S", help="with --denoise: samples per pixel of the guide buffers")
     opt = ap.parse_args(argv)
     if opt.adaptive is not None and (opt.progressive > 0 or opt.checkpoint):
         ap.error("--adaptive cannot be combined with --progressive or --checkpoint")
+    if opt.denoise is not None:
+        if opt.progressive > 0 or opt.checkpoint or opt.orbit:
+            ap.error("--denoise cannot be combined with --progressive, --checkpoint or --orbit")
+        if not 0 <= opt.denoise <= 10:
+            ap.error("--denoise L needs 0 <= L <= 10")
+        if opt.aov_samples < 1:
+            ap.error("--aov-samples needs S >= 1")
     if opt.orbit < 0:
         ap.error("--orbit N needs N >= 1")
     if opt.orbit > 0:
@@ -66,7 +78,9 @@ def main(argv=None):
             save_image(img, name, opt.width, opt.height)
         print(f'Saved {opt.orbit} views to "{names[0]}" .. "{names[-1]}"')
         return 0
-    if opt.adaptive is not None:
+    if opt.denoise is not None:
+        render = denoised(renderer, scene, opt)
+    elif opt.adaptive is not None:
         res = renderer.render_adaptive(scene, opt.adaptive, opt.min_samples, device=opt.device)
         render = res.rgb8
         print(f"adaptive: {len(res.rounds)} rounds, active pixels {res.rounds}, mean {float(res.counts.mean()):.1f} spp (cap {opt.samples})")
@@ -90,6 +104,21 @@ def main(argv=None):
         print(f"{name}: no display on this node; pass -o/--output to save the image", file=sys.stderr)
         return 2
     return 0
+
+
+def denoised(renderer, scene, opt):
+    """--denoise: the frame (a plain render, or --adaptive's with its moments and per-pixel counts) filtered by fw_denoise; returns rgb8."""
+    from . import _lib
+    if opt.adaptive is None:
+        return renderer.render_denoised(scene, opt.denoise, opt.aov_samples, device=opt.device).rgb8
+    ds = _lib.DeviceScene(scene.to_desc(), opt.device)
+    try:
+        res = ds.render_adaptive(renderer, opt.adaptive, opt.min_samples)
+        print(f"adaptive: {len(res.rounds)} rounds, active pixels {res.rounds}, mean {float(res.counts.mean()):.1f} spp (cap {opt.samples})")
+        aov = ds.aovs(renderer, opt.aov_samples)
+    finally:
+        ds.close()
+    return _lib.denoise(res.linear, aov, res.moments, opt.width, opt.height, opt.denoise, renderer.settings["gamma"], opt.device)[0]
 
 
 def view_paths(pattern, n):

@@ -114,5 +114,19 @@ class fw_trace_params(C.Structure):
                 ("on_device", i32), ("stream", C.c_void_p)]
 
 
+# fw_denoise (include/firework_hip.h): the filter's constants and its parameters
+FW_DENOISE_EPS = 0.01
+FW_DENOISE_NORMAL_POW = 128
+FW_DENOISE_PLANE = 0.01
+FW_DENOISE_LUM = 128.0
+FW_DENOISE_ITERATIONS = 5
+FW_DENOISE_MAX_ITERATIONS = 10
+
+
+class fw_denoise_params(C.Structure):
+    _fields_ = [("width", u32), ("height", u32), ("iterations", u32), ("gamma", f32), ("device", i32), ("on_device", i32),
+                ("stream", C.c_void_p)]
+
+
 def vec3(v):
     return fw_vec3(float(v[0]), float(v[1]), float(v[2]))

@@ -87,6 +87,10 @@ def load(preload=False, device=None):
     lib.fw_render_views.restype = C.c_int
     lib.fw_render_views.argtypes = [C.c_void_p, C.POINTER(A.fw_render_params), C.POINTER(A.fw_camera_settings), C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.POINTER(A.fw_stats)]
+    lib.fw_render_aovs.restype = C.c_int
+    lib.fw_render_aovs.argtypes = [C.c_void_p, C.POINTER(A.fw_render_params), C.c_void_p, C.POINTER(A.fw_stats)]
+    lib.fw_denoise.restype = C.c_int
+    lib.fw_denoise.argtypes = [C.POINTER(A.fw_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if lib.fw_abi_version() != A.FW_ABI_VERSION:
         raise FireworkError(A.FW_ERR_BAD_ARG, "ABI version mismatch between _abi.py and libfirework_hip.so")
     _lib = lib
@@ -397,6 +401,32 @@ class DeviceScene:
             stats.update(st.as_dict())
         return out
 
+    def aovs(self, renderer, samples, out=None, stream=None):
+        """fw_render_aovs: first-hit guide buffers of the whole frame averaged over `samples` samples (the renderer's own sample count is
+        not used), as an (N, 12) float32 array: albedo, coverage, normal, distance, position, 0 (AOV_COLUMNS).  out: a contiguous (N, 12)
+        float32 device tensor on this scene's device to fill instead, launched on `stream` (default: the current torch stream); returned.
+        stats: see aovs_stats after the call."""
+        import copy
+        lib = self._lib
+        r = copy.copy(renderer); r.settings = dict(renderer.settings); r.settings["samples"] = int(samples)
+        p = r.to_params(None)
+        n = p.width * p.height
+        st = A.fw_stats()
+        if out is not None:
+            import torch
+            _check_device_tensor(out, (n, 12), torch.float32, self.device, "out")
+            p.outputs_on_device = 1
+            if stream is None:
+                stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+            p.stream = C.c_void_p(stream) if stream else None
+            _check(lib, lib.fw_render_aovs(self.handle, C.byref(p), out.data_ptr(), C.byref(st)))
+            self.aovs_stats = st.as_dict()
+            return out
+        aov = np.empty((n, 12), np.float32)
+        _check(lib, lib.fw_render_aovs(self.handle, C.byref(p), aov.ctypes.data, C.byref(st)))
+        self.aovs_stats = st.as_dict()
+        return aov
+
     def camera_rays(self, renderer, sample=0, pixel_ids=None):
         """fw_camera_rays on this scene's device: see camera_rays()."""
         return camera_rays(renderer, sample, pixel_ids, self.device)
@@ -442,3 +472,52 @@ def render_scene_tiled(scene_desc, renderer, devices):
     _check(lib, lib.fw_render_scene_tiled(scene_desc.ptr(), C.byref(p), devs, len(devices), rgb8.ctypes.data, gam.ctypes.data,
                                           lin.ctypes.data, C.byref(st)))
     return RenderResult(rgb8, gam, lin, st.as_dict(), p.width, p.height)
+
+
+# columns of fw_render_aovs' (N, 12) records
+AOV_COLUMNS = dict(albedo=slice(0, 3), coverage=3, normal=slice(4, 7), distance=7, position=slice(8, 11))
+
+
+def _check_device_tensor(t, shape, dtype, device, name):
+    if (tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device.type != "cuda"
+            or (t.device.index or 0) != device):
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on cuda:{device}")
+
+
+def denoise(color, aov, moments=None, width=None, height=None, iterations=A.FW_DENOISE_ITERATIONS, gamma=2.2, device=0, stream=None):
+    """fw_denoise: the edge-avoiding a-trous filter (include/firework_hip.h) of a linear frame `color` (N, 3) guided by fw_render_aovs'
+    records `aov` (N, 12), with fw_render_adaptive's `moments` (N, 4) for the luminance term, or None.  All host arrays (numpy): returns
+    (rgb8, gamma, linear) host arrays of shape (N, 3).  All contiguous float32 torch tensors on cuda:`device`: filtered on `stream`
+    (default: the current torch stream), returns device tensors.  width * height must be N."""
+    lib = load()
+    if width is None or height is None:
+        raise ValueError("denoise needs width and height")
+    n = int(width) * int(height)
+    p = A.fw_denoise_params()
+    p.width, p.height, p.iterations, p.gamma, p.device = int(width), int(height), int(iterations), float(gamma), int(device)
+    if type(color).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(color, (n, 3), torch.float32, device, "color")
+        _check_device_tensor(aov, (n, 12), torch.float32, device, "aov")
+        if moments is not None:
+            _check_device_tensor(moments, (n, 4), torch.float32, device, "moments")
+        dev = color.device
+        rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+        gam = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        lin = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        p.on_device = 1
+        p.stream = C.c_void_p(stream) if stream else None
+        _check(lib, lib.fw_denoise(C.byref(p), color.data_ptr(), aov.data_ptr(), None if moments is None else moments.data_ptr(),
+                                   lin.data_ptr(), gam.data_ptr(), rgb8.data_ptr()))
+        return rgb8, gam, lin
+    c = np.ascontiguousarray(np.asarray(color, np.float32).reshape(n, 3))
+    a = np.ascontiguousarray(np.asarray(aov, np.float32).reshape(n, 12))
+    m = None if moments is None else np.ascontiguousarray(np.asarray(moments, np.float32).reshape(n, 4))
+    rgb8 = np.empty((n, 3), np.uint8)
+    gam = np.empty((n, 3), np.float32)
+    lin = np.empty((n, 3), np.float32)
+    _check(lib, lib.fw_denoise(C.byref(p), c.ctypes.data, a.ctypes.data, None if m is None else m.ctypes.data, lin.ctypes.data,
+                               gam.ctypes.data, rgb8.ctypes.data))
+    return rgb8, gam, lin

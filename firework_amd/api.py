@@ -803,6 +803,7 @@ class RenderResult:
     stats: dict
     width: int
     height: int
+    raw: Optional["RenderResult"] = None   # render_denoised: the frame before filtering
 
     def image(self) -> np.ndarray:
         return self.rgb8.reshape(self.height, self.width, 3)
@@ -1048,6 +1049,45 @@ class Renderer:
         finally:
             if ds is not scene:
                 ds.close()
+
+    def aovs(self, scene, samples: int = 8, device: int = 0) -> dict:
+        """First-hit guide buffers (not in the reference; fw_render_aovs): for `samples` samples of every pixel the camera ray a render
+        traces at segment 0, averaged.  Returns (H, W, .) float32 arrays, row 0 = image top: albedo (H, W, 3), coverage (H, W) = the
+        share of samples that hit something, normal (H, W, 3), distance (H, W), position (H, W, 3).  `scene`: a Scene, a SceneDesc or an
+        uploaded _lib.DeviceScene."""
+        from . import _lib
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            rec = ds.aovs(self, samples)
+        finally:
+            if ds is not scene:
+                ds.close()
+        h, w = int(self.settings["height"]), int(self.settings["width"])
+        return {k: rec[:, c].reshape((h, w, 3) if isinstance(c, slice) else (h, w)) for k, c in _lib.AOV_COLUMNS.items()}
+
+    def render_denoised(self, scene, iterations: int = 5, aov_samples: int = 8, device: int = 0) -> RenderResult:
+        """A render of settings["samples"] samples filtered by fw_denoise (not in the reference).  The frame comes from
+        fw_render_adaptive with min_samples = samples (one round at the fixed count: bit for bit fw_render's frame, with its moments for
+        the filter's luminance term), or from fw_render without moments for fewer than 2 samples; the guides from fw_render_aovs at
+        `aov_samples` samples.  All three calls share one uploaded scene.  Returns the filtered frame as a RenderResult whose .raw is
+        the frame before filtering."""
+        from . import _lib
+        s = self.settings
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            if int(s["samples"]) >= 2:
+                res = ds.render_adaptive(self, 1.0, int(s["samples"]))
+                raw = RenderResult(res.rgb8, res.gamma, res.linear, res.stats, res.width, res.height)
+                moments = res.moments
+            else:
+                raw, moments = ds.render(self), None
+            aov = ds.aovs(self, aov_samples)
+            dev = ds.device
+        finally:
+            if ds is not scene:
+                ds.close()
+        rgb8, gam, lin = _lib.denoise(raw.linear, aov, moments, raw.width, raw.height, iterations, s["gamma"], dev)
+        return RenderResult(rgb8, gam, lin, dict(raw.stats), raw.width, raw.height, raw=raw)
 
     def render(self, scene, device: int = 0) -> np.ndarray:
         """`pub fn render(&self, scene: Scene) -> Vec<Color>` (render.rs:109): (W*H, 3) uint8, row 0 = top."""

@@ -264,6 +264,15 @@ void launch_trace_load(const LaunchCfg &, const DFrame &, const float *rays, DPa
 void launch_trace_store(const LaunchCfg &, const DScene &, const DFrame &, const DPaths &in, const float2 *hits, const uint32_t *slot_of, uint32_t n,
                         float4 *out);
 void launch_camera_rays(hipStream_t stream, int n_cus, const DCamera &, const DFrame &, uint32_t n, float *out);
+// fw_render_aovs: one sample's first-hit values of a batch's pixels [first, first + n) added to their three float4 sums (the batch traced
+// by launch_trace_load + the walks), and the final division of the sums into fw_render_aovs' records (in place)
+void launch_aov_accumulate(hipStream_t stream, int n_cus, const DScene &, const DFrame &, const DPaths &in, const float2 *hits, const uint32_t *slot_of,
+                           uint32_t n, uint32_t first, float4 *sum);
+void launch_aov_finish(hipStream_t stream, int n_cus, uint32_t n, uint32_t spp, float4 *aov);
+// fw_denoise on device arrays: the prep pass, L a-trous iterations ping-ponging between ev0 and ev1 (guide: 2 x float4 per pixel, ev0 / ev1:
+// one float4 per pixel; all unused at L = 0), the final remodulation and resolve
+void launch_denoise(hipStream_t stream, int n_cus, uint32_t W, uint32_t H, uint32_t L, const float *color, const float4 *aov, const float4 *moments,
+                    float4 *guide, float4 *ev0, float4 *ev1, float gamma, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb);
 void launch_scatter_tiles(hipStream_t stream, const uint32_t *ids, uint32_t n, const uint8_t *in8, const float *ing, const float *inl,
                           uint8_t *out8, float *outg, float *outl);
 void launch_tile_order(hipStream_t stream, uint32_t width, uint32_t height, uint32_t *ids);

@@ -26,6 +26,7 @@
 // Numerics: compiled with -ffp-contract=off; +,-,*,/ and sqrt are IEEE-exact and written in the same
 // association as the reference's expressions, so hit/miss decisions follow the CPU oracle bit for
 // bit; libm-class functions (sin, atan2, asin, acos, log10, pow) are glibc's algorithms restated (fw_libm.h): the same bits.
+#include "../../include/firework_hip.h"     // FW_DENOISE_* (the filter's constants)
 #include "fw_device.h"
 #include "fw_libm.h"
 #include <atomic>
@@ -4132,6 +4133,239 @@ void launch_adaptive_select(hipStream_t stream, const uint32_t *ids, uint32_t n,
     const uint32_t blocks = adaptive_select_blocks(n), per_block = (n + blocks - 1) / blocks, per = (per_block + BLOCK - 1) / BLOCK * BLOCK;
     hipLaunchKernelGGL(k_adaptive_select, dim3(blocks), dim3(BLOCK), 0, stream, ids, n, per, accum, moments, n_samples, may_continue ? 1u : 0u, tol, mask, block_counts);
     hipLaunchKernelGGL(k_adaptive_compact, dim3(blocks), dim3(BLOCK), 0, stream, ids, n, per, (const unsigned long long *)mask, (const uint32_t *)block_counts, out_ids, count);
+}
+
+// ------------------------------------------------------------------------------------------------
+// fw_render_aovs: first-hit guide buffers.  A sample of the frame is one trace of its camera rays (k_trace_load with the real pixel
+// keys and sample0 = the sample, the render's segment-0 walks); k_aov_accumulate adds each pixel's values to its three float4 sums
+// (one thread per pixel per sample, the samples in order on one stream: the sums are taken in sample order), k_aov_finish divides.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float clamp01_keep_nan(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
+__device__ __forceinline__ float len_plain(float x, float y, float z) { return fsqrt((x * x + y * y) + z * z); }    // (no contraction: -ffp-contract=off)
+
+__global__ __launch_bounds__(BLOCK) void k_aov_accumulate(DScene sc, DFrame f, DPaths in, const float2 *__restrict__ hits, const uint32_t *__restrict__ slot_of,
+                                                          uint32_t n, uint32_t first, float4 *__restrict__ sum) {
+    if (sc.has_perlin) stage_perm();       // (a scene-wide, block-uniform condition)
+    __syncthreads();
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const uint32_t slot = slot_of[i];
+        uint32_t code = MISS;
+        float t = 0.f;
+        if (slot != MISS) {
+            if (f.hit4) code = reinterpret_cast<const uint32_t *>(hits)[slot];
+            else { const float2 h = hits[slot]; t = h.x; code = __float_as_uint(h.y); }
+        }
+        float4 *s = sum + 3 * (size_t)(first + i);
+        if (code == MISS) {
+            // the ray of a miss: its direction from the queue, or (not traced: a non-finite ray) nothing to sample
+            V3 c = mk(0.f, 0.f, 0.f);
+            if (slot != MISS) {
+                const float4 ra = in.ray_a[slot];
+                const float2 rb = in.ray_b[slot];
+                const float l = len_plain(ra.w, rb.x, rb.y);
+                c = env_sample(sc.env, mk(fdiv(ra.w, l), fdiv(rb.x, l), fdiv(rb.y, l)));
+            }
+            float4 a = s[0];
+            a.x += clamp01_keep_nan(c.x); a.y += clamp01_keep_nan(c.y); a.z += clamp01_keep_nan(c.z);
+            s[0] = a;
+            continue;
+        }
+        const uint32_t obj = code >> sc.prim_bits, prim = code & ((1u << sc.prim_bits) - 1u);
+        const Obj o = load_obj(sc.obj, obj);
+        const float4 ra = in.ray_a[slot];
+        const float2 rb = in.ray_b[slot];
+        const Ray world{mk(ra.x, ra.y, ra.z), mk(ra.w, rb.x, rb.y)};
+        if (f.hit4) t = recompute_t(o, to_object_space(o, world), prim);
+        const HitInfo h = rebuild_hit(sc, o, world, t, prim, true);
+        const float4 m0 = sc.mat[2 * h.material], m1 = sc.mat[2 * h.material + 1];
+        const uint32_t mkind = __float_as_uint(m0.x) & 0xffu, mtex = __float_as_uint(m0.y);
+        V3 alb;
+        if (mkind == 1u) alb = mk(m1.x, m1.y, m1.z);                                     // Metal: its albedo
+        else if (mkind == 2u) alb = mk(1.f, 1.f, 1.f);                                   // Dielectric
+        else {
+            alb = texture_sample(sc.tex, sc.images, mtex, h.u, h.v, h.point);          // Lambertian, Isotropic, Emissive
+            if (mkind == 3u) alb = mk(clamp01_keep_nan(alb.x), clamp01_keep_nan(alb.y), clamp01_keep_nan(alb.z));
+        }
+        const float nl = len_plain(h.normal.x, h.normal.y, h.normal.z);
+        const V3 nrm = nl == 0.f ? mk(0.f, 0.f, 0.f) : mk(fdiv(h.normal.x, nl), fdiv(h.normal.y, nl), fdiv(h.normal.z, nl));
+        const float dist = t * len_plain(world.d.x, world.d.y, world.d.z);
+        float4 a = s[0], b = s[1], c = s[2];
+        a.x += alb.x; a.y += alb.y; a.z += alb.z; a.w += 1.f;
+        b.x += nrm.x; b.y += nrm.y; b.z += nrm.z; b.w += dist;
+        c.x += h.point.x; c.y += h.point.y; c.z += h.point.z;
+        s[0] = a; s[1] = b; s[2] = c;
+    }
+}
+// sums -> the records: albedo and normal / S, distance and position / hits (0 without hits), coverage = hits / S
+__global__ __launch_bounds__(BLOCK) void k_aov_finish(uint32_t n, float spp, float4 *__restrict__ aov) {
+    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < n; p += gridDim.x * BLOCK) {
+        float4 *r = aov + 3 * (size_t)p;
+        const float4 a = r[0], b = r[1], c = r[2];
+        const float hits = a.w;
+        r[0] = make_float4(fdiv(a.x, spp), fdiv(a.y, spp), fdiv(a.z, spp), fdiv(hits, spp));
+        r[1] = make_float4(fdiv(b.x, spp), fdiv(b.y, spp), fdiv(b.z, spp), hits > 0.f ? fdiv(b.w, hits) : 0.f);
+        r[2] = hits > 0.f ? make_float4(fdiv(c.x, hits), fdiv(c.y, hits), fdiv(c.z, hits), 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// fw_denoise (include/firework_hip.h has the filter).  k_dn_prep demodulates and packs the per-tap guide data once per call: guide[2p]
+// = (normal, distance), guide[2p + 1] = (position, 0); ev[p] = (e, v).  k_dn_atrous runs one iteration over 16 x 16 tiles: for steps
+// h <= 4 the tile's taps (the tile grown by 2h on every side, at most 32 x 32 pixels = 48 KB) are staged in LDS first, wider steps
+// gather from L2.  k_dn_final remodulates and resolves.  No atomics: every output is one thread's.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t DN_TILE = 16;
+constexpr uint32_t DN_STAGE_MAX_STEP = 4;
+__device__ __forceinline__ bool finite4(float4 v) { return finite_f(v.x) && finite_f(v.y) && finite_f(v.z) && finite_f(v.w); }
+
+__global__ __launch_bounds__(BLOCK) void k_dn_prep(uint32_t n, const float *__restrict__ color, const float4 *__restrict__ aov,
+                                                   const float4 *__restrict__ moments, float4 *__restrict__ guide, float4 *__restrict__ ev) {
+    const float eps = FW_DENOISE_EPS;
+    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < n; p += gridDim.x * BLOCK) {
+        const float cr = color[3 * (size_t)p], cg = color[3 * (size_t)p + 1], cb = color[3 * (size_t)p + 2];
+        const float4 a = aov[3 * (size_t)p], nd = aov[3 * (size_t)p + 1], x = aov[3 * (size_t)p + 2];
+        const float ar = a.x + eps, ag = a.y + eps, ab = a.z + eps;
+        float v = 0.f;
+        if (moments) {
+            const float4 m = moments[p];
+            const float nf = m.w;
+            float vr = 0.f, vg = 0.f, vb = 0.f;
+            if (nf >= 2.f) {
+                vr = (m.x - nf * cr * cr) / (nf - 1.f); vg = (m.y - nf * cg * cg) / (nf - 1.f); vb = (m.z - nf * cb * cb) / (nf - 1.f);
+                vr = vr > 0.f ? vr : 0.f; vg = vg > 0.f ? vg : 0.f; vb = vb > 0.f ? vb : 0.f;
+            }
+            v = ((vr / (ar * ar) + vg / (ag * ag)) + vb / (ab * ab)) / 3.f / nf;
+        }
+        guide[2 * (size_t)p] = nd;
+        guide[2 * (size_t)p + 1] = make_float4(x.x, x.y, x.z, 0.f);
+        ev[p] = make_float4(cr / ar, cg / ag, cb / ab, v);
+    }
+}
+
+extern __shared__ float4 lds_dn[];
+// One iteration.  Tile b = blockIdx.x covers pixels (tx0 + 0..15, ty0 + 0..15); thread t takes pixel (t & 15, t >> 4) of it.
+template <bool STAGE>
+__global__ __launch_bounds__(BLOCK) void k_dn_atrous(uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t h, uint32_t lum, const float4 *__restrict__ guide,
+                                                     const float4 *__restrict__ ev_in, float4 *__restrict__ ev_out) {
+    const long long tx0 = (long long)(blockIdx.x % tiles_x) * DN_TILE, ty0 = (long long)(blockIdx.x / tiles_x) * DN_TILE;
+    const long long R = 2 * (long long)h, S = DN_TILE + 2 * R;            // staged square: the tile grown by 2h on every side
+    float4 *const sg0 = lds_dn, *const sg1 = lds_dn + S * S, *const sev = lds_dn + 2 * S * S;
+    if (STAGE) {
+        for (long long k = threadIdx.x; k < S * S; k += BLOCK) {
+            const long long gx = tx0 - R + k % S, gy = ty0 - R + k / S;
+            if (gx >= 0 && gy >= 0 && gx < (long long)W && gy < (long long)H) {
+                const size_t q = (size_t)gy * W + (size_t)gx;
+                sg0[k] = guide[2 * q]; sg1[k] = guide[2 * q + 1]; sev[k] = ev_in[q];
+            }
+        }
+        __syncthreads();
+    }
+    const long long px = tx0 + (threadIdx.x & 15u), py = ty0 + (threadIdx.x >> 4);
+    if (px >= (long long)W || py >= (long long)H) return;
+    // tap (qx, qy), known to be inside the image: its LDS entry, or its global index
+    auto idx = [&](long long qx, long long qy) -> size_t { return STAGE ? (size_t)((qy - ty0 + R) * S + (qx - tx0 + R)) : (size_t)qy * W + (size_t)qx; };
+    auto G0 = [&](size_t i) { return STAGE ? sg0[i] : guide[2 * i]; };
+    auto G1 = [&](size_t i) { return STAGE ? sg1[i] : guide[2 * i + 1]; };
+    auto EV = [&](size_t i) { return STAGE ? sev[i] : ev_in[i]; };
+    const size_t ip = idx(px, py);
+    const float4 np = G0(ip), xp = G1(ip), ep = EV(ip);
+    const float lp = ((ep.x + ep.y) + ep.z) / 3.f;
+    float lum_den = 1.f;
+    if (lum) {                                   // g_p: the 3x3 blur of v, in-image taps with a finite v, renormalised
+        const float k3[3] = {0.25f, 0.5f, 0.25f};
+        float gs = 0.f, gw = 0.f;
+        for (int dy = -1; dy <= 1; dy++)
+            for (int dx = -1; dx <= 1; dx++) {
+                const long long qx = px + dx, qy = py + dy;
+                if (qx < 0 || qy < 0 || qx >= (long long)W || qy >= (long long)H) continue;
+                const float vq = EV(idx(qx, qy)).w;
+                if (!finite_f(vq)) continue;
+                const float w = k3[dx + 1] * k3[dy + 1];
+                gs += w * vq; gw += w;
+            }
+        const float g = gw > 0.f ? gs / gw : 0.f;
+        lum_den = FW_DENOISE_LUM * sqrtf(g) + 1e-6f;
+    }
+    const float plane_den = FW_DENOISE_PLANE * np.w + 1e-6f;
+    const float kap[5] = {1.f / 16.f, 1.f / 4.f, 3.f / 8.f, 1.f / 4.f, 1.f / 16.f};
+    float sw = kap[2] * kap[2];
+    float se_r = sw * ep.x, se_g = sw * ep.y, se_b = sw * ep.z, sv = (sw * sw) * ep.w;
+    for (int dy = -2; dy <= 2; dy++) {
+        const long long qy = py + (long long)h * dy;
+        if (qy < 0 || qy >= (long long)H) continue;
+        for (int dx = -2; dx <= 2; dx++) {
+            if (dx == 0 && dy == 0) continue;
+            const long long qx = px + (long long)h * dx;
+            if (qx < 0 || qx >= (long long)W) continue;
+            const size_t iq = idx(qx, qy);
+            const float4 eq = EV(iq);
+            if (!finite4(eq)) continue;
+            const float4 nq = G0(iq), xq = G1(iq);
+            float wn = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+            wn = wn > 0.f ? wn : 0.f;
+#pragma unroll
+            for (int k = 0; k < 7; k++) wn = wn * wn;                          // ^128
+            const float pd = fabsf((np.x * (xq.x - xp.x) + np.y * (xq.y - xp.y)) + np.z * (xq.z - xp.z));
+            // (the hardware exponential, __expf: the filter's weights are held to a relative tolerance, not to glibc's bits)
+            float w = (kap[dx + 2] * kap[dy + 2]) * wn * __expf(-(pd / plane_den));
+            if (lum) {
+                const float lq = ((eq.x + eq.y) + eq.z) / 3.f;
+                w = w * __expf(-(fabsf(lp - lq) / lum_den));
+            }
+            se_r += w * eq.x; se_g += w * eq.y; se_b += w * eq.z; sv += (w * w) * eq.w; sw += w;
+        }
+    }
+    ev_out[(size_t)py * W + (size_t)px] = make_float4(se_r / sw, se_g / sw, se_b / sw, sv / (sw * sw));
+}
+
+// out = e^(L) (a + eps), or the input colour (L = 0, coverage 0, a non-finite input), resolved as a 1-sample pixel
+__global__ __launch_bounds__(BLOCK) void k_dn_final(uint32_t n, uint32_t L, const float *__restrict__ color, const float4 *__restrict__ aov,
+                                                    const float4 *__restrict__ ev, float gamma, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
+    const float eps = FW_DENOISE_EPS;
+    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < n; p += gridDim.x * BLOCK) {
+        float4 c = make_float4(color[3 * (size_t)p], color[3 * (size_t)p + 1], color[3 * (size_t)p + 2], 0.f);
+        const float4 a = aov[3 * (size_t)p];
+        if (L > 0u && a.w != 0.f && finite_f(c.x) && finite_f(c.y) && finite_f(c.z)) {
+            const float4 e = ev[p];
+            c = make_float4(e.x * (a.x + eps), e.y * (a.y + eps), e.z * (a.z + eps), 0.f);
+        }
+        resolve_pixel(c, 1.0f, gamma, p, rgb8, gamma_rgb, linear_rgb);
+    }
+}
+
+static uint32_t flat_blocks(uint64_t n, int n_cus, uint32_t per_cu) {
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + BLOCK - 1) / BLOCK, (uint64_t)std::max(1, n_cus) * per_cu));
+}
+void launch_aov_accumulate(hipStream_t stream, int n_cus, const DScene &sc, const DFrame &f, const DPaths &in, const float2 *hits, const uint32_t *slot_of,
+                           uint32_t n, uint32_t first, float4 *sum) {
+    hipLaunchKernelGGL(k_aov_accumulate, dim3(flat_blocks(n, n_cus, 32)), dim3(BLOCK), 0, stream, sc, f, in, hits, slot_of, n, first, sum);
+}
+void launch_aov_finish(hipStream_t stream, int n_cus, uint32_t n, uint32_t spp, float4 *aov) {
+    hipLaunchKernelGGL(k_aov_finish, dim3(flat_blocks(n, n_cus, 8)), dim3(BLOCK), 0, stream, n, (float)spp, aov);
+}
+void launch_denoise(hipStream_t stream, int n_cus, uint32_t W, uint32_t H, uint32_t L, const float *color, const float4 *aov, const float4 *moments,
+                    float4 *guide, float4 *ev0, float4 *ev1, float gamma, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
+    const uint32_t n = W * H;
+    const float4 *ev = ev0;
+    if (L > 0) {
+        hipLaunchKernelGGL(k_dn_prep, dim3(flat_blocks(n, n_cus, 8)), dim3(BLOCK), 0, stream, n, color, aov, moments, guide, ev0);
+        const uint32_t tiles_x = (W + DN_TILE - 1) / DN_TILE, tiles = tiles_x * ((H + DN_TILE - 1) / DN_TILE);
+        float4 *src = ev0, *dst = ev1;
+        for (uint32_t i = 0; i < L; i++) {
+            const uint32_t h = 1u << i;
+            if (h <= DN_STAGE_MAX_STEP) {
+                const size_t side = DN_TILE + 4 * h, lds = side * side * 3 * sizeof(float4);
+                hipLaunchKernelGGL(k_dn_atrous<true>, dim3(tiles), dim3(BLOCK), lds, stream, W, H, tiles_x, h, moments ? 1u : 0u, (const float4 *)guide,
+                                   (const float4 *)src, dst);
+            } else {
+                hipLaunchKernelGGL(k_dn_atrous<false>, dim3(tiles), dim3(BLOCK), 0, stream, W, H, tiles_x, h, moments ? 1u : 0u, (const float4 *)guide,
+                                   (const float4 *)src, dst);
+            }
+            std::swap(src, dst);
+        }
+        ev = src;
+    }
+    hipLaunchKernelGGL(k_dn_final, dim3(flat_blocks(n, n_cus, 8)), dim3(BLOCK), 0, stream, n, L, color, aov, ev, gamma, rgb8, gamma_rgb, linear_rgb);
 }
 
 } // namespace fw

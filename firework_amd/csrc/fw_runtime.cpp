@@ -2848,6 +2848,199 @@ int camera_rays_impl(const fw_render_params *p, int device, uint32_t sample, flo
     return FW_OK;
 }
 
+// fw_render_aovs: for every sample s, the frame's camera rays (k_camera_rays, the render's keys) are traced in batches as fw_trace_rays
+// traces the caller's rays — k_trace_load with the real pixel keys (key0 = the batch's first pixel, DFrame.sample0 = s), the render's
+// launch_extend + launch_extend_exact — and k_aov_accumulate adds the batch's values to its pixels' sums; k_aov_finish divides.  The
+// queue geometry, walk configuration and hit-record form are trace_impl's, so every kernel-selecting option selects the same walks.
+int aovs_impl(fw_scene *sc, const fw_render_params *p, float *aov, fw_stats *stats) {
+    // (arguments first: nothing below dereferences the scene before they are all valid)
+    if (!sc || !p || !aov) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (p->pixel_ids) return fail(FW_ERR_BAD_ARG, "fw_render_aovs renders whole frames: pixel_ids must be NULL");
+    if (p->samples == 0 || p->samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^24");
+    if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
+    if (p->outputs_on_device && ((uintptr_t)aov & 15u)) return fail(FW_ERR_BAD_ARG, "a device aov must be 16-byte aligned");
+    if (p->rng_mode != FW_RNG_CTR) return fail(FW_ERR_UNSUPPORTED, "the HIP path implements FW_RNG_CTR only (FW_RNG_LCG is a sequential stream)");
+    const uint64_t full = (uint64_t)p->width * p->height;
+    if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    const uint32_t n = (uint32_t)full;
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(sc->device));
+    hipStream_t stream = (hipStream_t)p->stream;
+    Workspace *ws = workspace_for(sc->device);
+    if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
+    std::lock_guard<std::mutex> ws_guard(ws->mu);
+    { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }
+    const Options O = options();
+    const bool use_bvh = p->use_bvh != 0;
+    const uint32_t per = std::min(n, default_paths_per_batch(O, ws->arena.bytes));
+    const uint32_t n_batches = (uint32_t)(((uint64_t)n + per - 1) / per), S = p->samples;
+
+    // trace_impl's queue geometry, exact walk and parking for a batch of `per` rays
+    fw::DQueue q{};
+    const uint32_t unit = (uint32_t)sc->n_cus * 4u * (use_bvh ? 20u : 28u);
+    const uint64_t chunks = ((uint64_t)per + 63u) / 64u;
+    uint32_t want_waves = unit * (uint32_t)std::min<uint64_t>(3u, std::max<uint64_t>(1u, chunks / ((uint64_t)unit * 16u)));
+    if (O.waves > 0) want_waves = (uint32_t)O.waves;
+    q.n_waves = std::max(4u, std::min(want_waves, (per + 511u) / 512u));
+    q.n_waves = (q.n_waves + 7u) & ~7u;
+    const uint32_t chunks_per_wave = (per + q.n_waves * 64u - 1) / (q.n_waves * 64u);
+    while ((1u << q.cpw_shift) < chunks_per_wave) q.cpw_shift++;
+    q.cap = 64u << q.cpw_shift;
+    const uint64_t cap64 = (uint64_t)q.cap * q.n_waves;
+    if (cap64 > 0x7fffffffull) return fail(FW_ERR_UNSUPPORTED, "too many rays per batch");
+    const size_t cap = (size_t)cap64;
+#if FW_AB
+    const bool tlas_refill = !O.tlas_refill_off;
+#else
+    const bool tlas_refill = true;
+#endif
+    const uint32_t exact_mode = (sc->ex.mode & 1u) | (use_bvh ? (sc->ex.mode & 6u) | fw::EX_TRACE_ZERO : ((sc->ex.mode & 4u) && sc->d.has_mesh ? 4u : 0u));
+    const bool park_meshes = use_bvh && sc->d.has_mesh != 0 && tlas_refill;
+
+    // device memory: the front of the arena — trace_impl's buffers, one sample's camera rays, and (host output) the sums
+    const size_t pcap = (size_t)(q.cap + 64u) * q.n_waves;
+    const size_t totals_bytes = (size_t)S * n_batches * fw::COUNT_STRIDE * 4;
+    size_t off = 0;
+    auto put = [&](size_t b) { const size_t at = off; off += (b + 255) & ~(size_t)255; return at; };
+    const size_t o_ra = put(cap * 16), o_rb = put(cap * 8), o_hits = put(cap * 8), o_wc = put((size_t)(fw::MAX_SEGMENTS + 1) * q.n_waves * 4);
+    const size_t o_ids = put((size_t)per * 4), o_slot = put((size_t)per * 4), o_tot = put(totals_bytes);
+    const size_t o_ex = exact_mode ? put(2 * (size_t)per * 4 + 64) : 0;
+    const size_t o_pa = park_meshes ? put(pcap * 16) : 0, o_pb = park_meshes ? put(pcap * 8) : 0, o_pm = park_meshes ? put(pcap * 16) : 0;
+    const size_t o_pc = park_meshes ? put((size_t)q.n_waves * 8) : 0;
+    const size_t o_rays = put((size_t)n * 24), o_sum = p->outputs_on_device ? 0 : put((size_t)n * 48);
+    uint8_t *base = nullptr;
+    if (int rc = query_arena_locked(ws, sc->device, off, base)) return rc;
+    const size_t h_out = (totals_bytes + 255) & ~(size_t)255;
+    uint8_t *host = nullptr;
+    if (int rc = query_host_locked(ws, h_out + (p->outputs_on_device ? 0 : (size_t)n * 48), host)) return rc;
+    while (ws->events.size() < 3) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, ws->events.size() < 2 ? hipEventDefault : hipEventDisableTiming)); ws->events.push_back(e); }
+
+    fw::LaunchCfg cfg{};
+    set_walk_cfg(cfg, sc, O, q, use_bvh, tlas_refill);
+    cfg.stream = stream;
+    cfg.q.wcount = (uint32_t *)(base + o_wc);
+    fw::DPaths paths{(float4 *)(base + o_ra), (float2 *)(base + o_rb), nullptr};
+    float2 *const hit_rec = (float2 *)(base + o_hits);
+    uint32_t *const ids = (uint32_t *)(base + o_ids), *const slot_of = (uint32_t *)(base + o_slot), *const totals = (uint32_t *)(base + o_tot);
+    const fw::DPark park{(float4 *)(base + o_pa), (float2 *)(base + o_pb), (float4 *)(base + o_pm), q.cap + 64u,
+                         park_meshes ? (uint32_t *)(base + o_pc) : nullptr, park_meshes ? (uint32_t *)(base + o_pc) + q.n_waves : nullptr};
+    const uint32_t seed32 = (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u);
+    fw::DFrame fr{};
+    fr.width = 1; fr.height = 1; fr.inv_width = 1.f;
+    fr.pixel_ids = ids;
+    fr.seed32 = seed32;
+    fr.spp_batch = 1;
+    fr.q_n_waves = q.n_waves; fr.q_shift = q.cpw_shift;
+    fr.pinhole0 = 0;
+    fr.hit4 = (!use_bvh && sc->simple_shapes && !exact_mode && !O.no_hit4) ? 1u : 0u;
+    fr.ex = sc->ex; fr.ex.mode = exact_mode;
+    if (exact_mode) {
+        fr.ex.slots[0] = (uint32_t *)(base + o_ex); fr.ex.slots[1] = fr.ex.slots[0] + per;
+        fr.ex.count = fr.ex.slots[1] + per; fr.ex.cap = per;
+    }
+    // camera_rays_impl's frame for one sample of the whole frame
+    const fw::DCamera cam = make_camera(p->camera, p->width, p->height);
+    fw::DFrame cf{};
+    cf.width = p->width; cf.height = p->height; cf.n_pixels = n; cf.inv_n_pixels = 1.0f / (float)n; cf.inv_width = 1.0f / (float)p->width;
+    cf.pixel_ids = nullptr; cf.seed32 = seed32; cf.spp_batch = 1;
+    float *const rays = (float *)(base + o_rays);
+    float4 *const sum = p->outputs_on_device ? (float4 *)aov : (float4 *)(base + o_sum);
+
+    if (ws->ev_upload) HIPCHK(hipStreamWaitEvent(stream, ws->ev_upload, 0));
+    HIPCHK(hipEventRecord(ws->events[0], stream));
+    HIPCHK(hipMemsetAsync(totals, 0, totals_bytes, stream));
+    HIPCHK(hipMemsetAsync(sum, 0, (size_t)n * 48, stream));
+    for (uint32_t s = 0; s < S; s++) {
+        cf.sample0 = s;
+        fw::launch_camera_rays(stream, sc->n_cus, cam, cf, n, rays);
+        fr.sample0 = s;
+        for (uint32_t b = 0; b < n_batches; b++) {
+            const uint32_t first = b * per, nb = std::min(per, n - first);
+            fr.n_pixels = nb; fr.inv_n_pixels = 1.0f / (float)nb;
+            HIPCHK(hipMemsetAsync(cfg.q.wcount, 0, (size_t)(fw::MAX_SEGMENTS + 1) * q.n_waves * 4, stream));
+            if (exact_mode) HIPCHK(hipMemsetAsync(fr.ex.count, 0, 64, stream));
+            if (park_meshes) HIPCHK(hipMemsetAsync(park.ptotal, 0, (size_t)q.n_waves * 4, stream));
+            fw::launch_trace_load(cfg, fr, rays + (size_t)first * 6, paths, nb, first, ids, slot_of);
+            fw::launch_extend(cfg, sc->d, fr, paths, hit_rec, 0, use_bvh, park);
+            if (exact_mode) fw::launch_extend_exact(cfg, sc->d, fr, paths, hit_rec, 0, use_bvh);
+            fw::launch_queue_totals(cfg, totals + ((size_t)s * n_batches + b) * fw::COUNT_STRIDE, park.ptotal);
+            fw::launch_aov_accumulate(stream, sc->n_cus, sc->d, fr, paths, hit_rec, slot_of, nb, first, sum);
+        }
+    }
+    fw::launch_aov_finish(stream, sc->n_cus, n, S, sum);
+    HIPCHK(hipEventRecord(ws->events[1], stream));
+    HIPCHK(hipMemcpyAsync(host, totals, totals_bytes, hipMemcpyDeviceToHost, stream));
+    if (!p->outputs_on_device) HIPCHK(hipMemcpyAsync(host + h_out, sum, (size_t)n * 48, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    if (!p->outputs_on_device) std::memcpy(aov, host + h_out, (size_t)n * 48);
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        const uint32_t *h_counts = (const uint32_t *)host;
+        for (size_t b = 0; b < (size_t)S * n_batches; b++) stats->rays += h_counts[b * fw::COUNT_STRIDE];
+        stats->rays_per_depth[0] = stats->rays;
+        stats->n_batches = S * n_batches;
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ws->events[0], ws->events[1]));
+        stats->ms_render = ms;
+        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FW_OK;
+}
+
+// fw_denoise: one device allocation per call — the packed guide (32 B per pixel) and the ping-pong e / v buffers (2 x 16 B per pixel), and
+// with host arrays the inputs and outputs staged behind them — released on every way out of this function.
+int denoise_impl(const fw_denoise_params *p, const float *color, const float *aov, const float *moments, float *linear_rgb, float *gamma_rgb,
+                 uint8_t *rgb8) {
+    if (!p || !color || !aov) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
+    if (p->iterations > FW_DENOISE_MAX_ITERATIONS) return fail(FW_ERR_BAD_ARG, "iterations must be in 0..10");
+    if (!std::isfinite(p->gamma) || !(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
+    if (p->device < 0 || p->device >= MAX_DEVICES) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    if (p->on_device && (((uintptr_t)aov & 15u) || ((uintptr_t)moments & 15u))) return fail(FW_ERR_BAD_ARG, "device aov and moments must be 16-byte aligned");
+    const uint64_t full = (uint64_t)p->width * p->height;
+    if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (p->device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    const uint32_t n = (uint32_t)full, L = p->iterations;
+    const int dev = p->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)p->stream;
+    const bool host_io = !p->on_device;
+    size_t off = 0;
+    auto put = [&](size_t b) { const size_t at = off; off += (b + 255) & ~(size_t)255; return at; };
+    const size_t o_guide = L ? put((size_t)n * 32) : 0, o_ev0 = L ? put((size_t)n * 16) : 0, o_ev1 = L ? put((size_t)n * 16) : 0;
+    const size_t o_col = host_io ? put((size_t)n * 12) : 0, o_aov = host_io ? put((size_t)n * 48) : 0;
+    const size_t o_mom = host_io && moments ? put((size_t)n * 16) : 0;
+    const size_t o_lin = host_io && linear_rgb ? put((size_t)n * 12) : 0, o_gam = host_io && gamma_rgb ? put((size_t)n * 12) : 0;
+    const size_t o_8 = host_io && rgb8 ? put((size_t)n * 3) : 0;
+    struct Scratch : DevBuf { int dev; explicit Scratch(int d) : dev(d) {} ~Scratch() { if (p) { (void)hipSetDevice(dev); release(); } } };
+    Scratch scratch(dev);
+    if (int rc = scratch.alloc(std::max<size_t>(off, 256))) return rc;
+    uint8_t *base = (uint8_t *)scratch.p;
+    const float *d_col = color; const float4 *d_aov = (const float4 *)aov, *d_mom = (const float4 *)moments;
+    float *d_lin = linear_rgb, *d_gam = gamma_rgb; uint8_t *d_8 = rgb8;
+    if (host_io) {
+        HIPCHK(hipMemcpyAsync(base + o_col, color, (size_t)n * 12, hipMemcpyHostToDevice, stream)); d_col = (const float *)(base + o_col);
+        HIPCHK(hipMemcpyAsync(base + o_aov, aov, (size_t)n * 48, hipMemcpyHostToDevice, stream)); d_aov = (const float4 *)(base + o_aov);
+        if (moments) { HIPCHK(hipMemcpyAsync(base + o_mom, moments, (size_t)n * 16, hipMemcpyHostToDevice, stream)); d_mom = (const float4 *)(base + o_mom); }
+        d_lin = linear_rgb ? (float *)(base + o_lin) : nullptr; d_gam = gamma_rgb ? (float *)(base + o_gam) : nullptr; d_8 = rgb8 ? base + o_8 : nullptr;
+    }
+    fw::launch_denoise(stream, device_cus(dev), p->width, p->height, L, d_col, d_aov, d_mom, (float4 *)(base + o_guide), (float4 *)(base + o_ev0),
+                       (float4 *)(base + o_ev1), p->gamma, d_8, d_gam, d_lin);
+    if (host_io) {
+        if (linear_rgb) HIPCHK(hipMemcpyAsync(linear_rgb, d_lin, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
+        if (gamma_rgb) HIPCHK(hipMemcpyAsync(gamma_rgb, d_gam, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
+        if (rgb8) HIPCHK(hipMemcpyAsync(rgb8, d_8, (size_t)n * 3, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
 } // namespace
 
 // =========================================================================================================
@@ -3077,6 +3270,19 @@ int fw_camera_rays(const fw_render_params *params, int device, uint32_t sample, 
     try { return camera_rays_impl(params, device, sample, rays); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_camera_rays"); }
+}
+
+int fw_render_aovs(fw_scene *scene, const fw_render_params *params, float *aov, fw_stats *stats) {
+    try { return aovs_impl(scene, params, aov, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_render_aovs"); }
+}
+
+int fw_denoise(const fw_denoise_params *p, const float *color, const float *aov, const float *moments, float *linear_rgb, float *gamma_rgb,
+               uint8_t *rgb8) {
+    try { return denoise_impl(p, color, aov, moments, linear_rgb, gamma_rgb, rgb8); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_denoise"); }
 }
 
 

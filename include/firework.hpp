@@ -319,6 +319,34 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
         std::vector<std::vector<Color>> views;
         for (size_t v = 0; v < cams.size(); v++) views.emplace_back(all.begin() + v * n, all.begin() + (v + 1) * n);
         return views; }
+
+    // A denoised frame (not in the reference): samples() samples per pixel filtered by fw_denoise with `iterations` a-trous steps, guided by
+    // fw_render_aovs at aov_samples samples.  The frame comes from fw_render_adaptive with min_samples = samples() (one round at the fixed
+    // count: fw_render's frame bit for bit, and its moments drive the filter's luminance term), or from fw_render below 2 samples.
+    std::vector<Color> render_denoised(const Scene &scene, uint32_t iterations = FW_DENOISE_ITERATIONS, uint32_t aov_samples = 8,
+                                       fw_stats *stats = nullptr) const {
+        Lowered low(scene);
+        fw_scene *sc = nullptr;
+        int rc = fw_scene_create(&low.desc, device_, &sc);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        fw_render_params p = params();
+        const size_t n = width_ * height_;
+        std::vector<float> linear(n * 3), moments(n * 4), aov(n * 12);
+        rc = p.samples >= 2 ? fw_render_adaptive(sc, &p, 1.0f, p.samples, nullptr, moments.data(), nullptr, nullptr, linear.data(), nullptr, stats)
+                            : fw_render(sc, &p, nullptr, nullptr, linear.data(), stats);
+        if (rc == FW_OK) {
+            fw_render_params pa = p;
+            pa.samples = aov_samples;
+            rc = fw_render_aovs(sc, &pa, aov.data(), nullptr);
+        }
+        fw_scene_destroy(sc);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        fw_denoise_params dp{(uint32_t)width_, (uint32_t)height_, iterations, p.gamma, device_, 0, nullptr};
+        std::vector<Color> buffer(n, Color{0, 0, 0});
+        rc = fw_denoise(&dp, linear.data(), aov.data(), p.samples >= 2 ? moments.data() : nullptr, nullptr, nullptr,
+                        reinterpret_cast<uint8_t *>(buffer.data()));
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        return buffer; }
 };
 
 // Ray queries (ABI v8, not in the reference): a scene uploaded once, and `Hitable::hit(ray, 0.001, 2e9)` (render.rs:19,44-57) for the

@@ -408,6 +408,66 @@ int fw_trace_rays(fw_scene *scene, const fw_trace_params *params, const float *r
    params->stream, complete on return). */
 int fw_camera_rays(const fw_render_params *params, int device, uint32_t sample, float *rays);
 
+/* ---- guide buffers and denoising (additive at ABI 8) -----------------------------------------------------------------------
+   fw_render_aovs: per-pixel guide buffers ("AOVs") of the first hit, averaged over params->samples samples.  Sample s of pixel p is the
+   segment-0 ray a render traces for it (fw_camera_rays(params, device, s)), traced by the render's segment-0 walks with the render's keys
+   (seed, p, s, segment 0): a ConstantMedium draws what the render draws.  One 48-byte record per pixel, W x H x 12 floats in row-major
+   pixel order (row 0 = top), three float4s:
+       [0] albedo.xyz, coverage = hits / S        [1] normal.xyz, distance        [2] position.xyz, 0
+   Per sample, in IEEE float32 without contraction (the kernels' division / square-root helpers, fw_selftest_arith):
+     hit  : albedo = texture_sample(texture, u, v, point) for Lambertian and Isotropic, the albedo of a Metal, (1, 1, 1) for a Dielectric,
+            texture_sample clamped to [0, 1] for an Emissive; normal = hit normal / sqrtf((nx*nx + ny*ny) + nz*nz) (0 if that is 0);
+            distance = t * sqrtf((dx*dx + dy*dy) + dz*dz); position = the hit point
+     miss : albedo = env_sample(d / sqrtf((dx*dx + dy*dy) + dz*dz)) clamped to [0, 1]; normal 0; no distance or position
+   Sums in sample order in float32; albedo and normal are divided by S, distance and position by the pixel's hits (0 without hits).
+   Errors, in this order: FW_ERR_BAD_ARG for a NULL scene, params or aov, params->pixel_ids != NULL (whole frames only), samples outside
+   1..2^24, width or height 0, with outputs_on_device an aov not 16-byte aligned — all before the scene is looked at; FW_ERR_UNSUPPORTED
+   for FW_RNG_LCG or W x H >= 2^32; FW_ERR_NO_DEVICE without a GPU.  stats (may be NULL): rays, n_batches, ms_render, ms_wall.
+   Synchronisation is fw_render's (params->stream, complete on return).  The call never runs as a frame graph; if it grows the path
+   workspace, the cached frame graph's key is cleared, as fw_trace_rays does.  Renders are left as they were. */
+int fw_render_aovs(fw_scene *scene, const fw_render_params *params, float *aov, fw_stats *stats);
+
+/* fw_denoise: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with SVGF's variance-guided luminance term, on the device in
+   float32.  color = a linear_rgb as fw_render writes it (N x 3), aov = fw_render_aovs' records (N x 12), moments = fw_render_adaptive's
+   (N x 4: sums of squares of r, g, b and .w = the pixel's count n) or NULL.  With eps = FW_DENOISE_EPS, per pixel p:
+     demodulate : e_p = c_p / (a_p + eps) per channel
+     variance   : var_c = max(0, (Q_c - n*c_c*c_c) / (n - 1)) (0 for n < 2);
+                  v_p = ((var_r/(a_r+eps)^2 + var_g/(a_g+eps)^2) + var_b/(a_b+eps)^2) / 3 / n; without moments no luminance term
+     iteration i = 0..L-1, step h = 2^i: taps q = p + h*(dx, dy), dx, dy in -2..2, inside the image; kappa = (1/16, 1/4, 3/8, 1/4, 1/16);
+                  the centre's weight is kappa(0)^2, every other tap's
+                    w = kappa(dx) kappa(dy) * max(0, n_p.n_q)^FW_DENOISE_NORMAL_POW
+                        * exp(-|n_p.(x_q - x_p)| / (FW_DENOISE_PLANE * d_p + 1e-6))
+                        * exp(-|l_p - l_q| / (FW_DENOISE_LUM * sqrt(g_p) + 1e-6))       (with moments only)
+                  l = (e_r + e_g + e_b) / 3; g_p = the 3x3 blur of v around p, weights (1/4, 1/2, 1/4) x (1/4, 1/2, 1/4), in-image taps
+                  with a finite v, renormalised; a tap whose e or v is not finite has weight 0.
+                  e'_p = sum w e_q / sum w;  v'_p = sum w^2 v_q / (sum w)^2
+     output     : out_p = e_p^(L) * (a_p + eps), then resolve_pixel(out_p, 1, gamma) into linear_rgb / gamma_rgb / rgb8 (any may be NULL).
+                  A pixel with coverage 0 or a non-finite input colour, and every pixel at L = 0, passes its input colour through: at L = 0
+                  the three outputs equal fw_render's bit for bit.
+   One launch per iteration (ping-pong buffers of e and v), no atomics: two calls give the same bits.  Device scratch is allocated per
+   call and freed on every path.  With on_device every array is a device pointer on `device` and the launches go to `stream` (complete on
+   return); otherwise host arrays.  Errors, all before HIP is called: FW_ERR_BAD_ARG for a NULL p, color or aov, width or height 0,
+   iterations > 10, gamma not finite or <= 0, device < 0, with on_device an aov or moments not 16-byte aligned; FW_ERR_UNSUPPORTED for
+   W x H >= 2^32; then FW_ERR_NO_DEVICE without a GPU, and FW_ERR_BAD_ARG for a device index past the last one. */
+#define FW_DENOISE_EPS 0.01f
+#define FW_DENOISE_NORMAL_POW 128       /* 7 squarings */
+#define FW_DENOISE_PLANE 0.01f
+#define FW_DENOISE_LUM 128.0f
+#define FW_DENOISE_ITERATIONS 5         /* the library's default L */
+#define FW_DENOISE_MAX_ITERATIONS 10
+
+typedef struct fw_denoise_params {
+    uint32_t width, height;
+    uint32_t iterations;    /* 0..10; 0 = no filtering; the library's default is FW_DENOISE_ITERATIONS */
+    float gamma;            /* for gamma_rgb / rgb8, as fw_render_params.gamma */
+    int32_t device;
+    int32_t on_device;      /* every array is a device pointer on `device` */
+    void *stream;           /* hipStream_t, NULL = default */
+} fw_denoise_params;
+
+int fw_denoise(const fw_denoise_params *p, const float *color, const float *aov, const float *moments,
+               float *linear_rgb, float *gamma_rgb, uint8_t *rgb8);
+
 /* Diagnostic: the kernels' division / square-root helpers against the compiler's IEEE expansion, bit for bit,
    on n hashed operand pairs.  mode 0 = magnitudes 2^-40..2^40 (must be 0 mismatches), mode 1 = all bit patterns. */
 int fw_selftest_arith(int device, uint32_t n, uint32_t seed, int mode, uint64_t *div_mismatches, uint64_t *sqrt_mismatches);
