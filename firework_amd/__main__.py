@@ -11,7 +11,11 @@ pass and resume from it: the finished image is bit-identical to an uninterrupted
 in azimuth around the fixed camera's look-at point, rendered in one call; -o must hold a format field, e.g. 'frame_{:03d}.png', which
 receives the view number; not with --progressive / --checkpoint / --adaptive), --denoise [L] (filter the frame with L a-trous
 iterations, default 5, guided by first-hit albedo / normal / position buffers; with a plain render or --adaptive, whose moments and
-per-pixel counts it uses; not with --progressive / --checkpoint / --orbit)."""
+per-pixel counts it uses; not with --progressive / --checkpoint / --orbit), --camera {pinhole,panorama,orthographic} (default pinhole:
+the fixed view above; panorama: an equirectangular 360-degree image from the fixed camera's position, --width x --height, which loads
+back as an HDR environment with the same orientation; orthographic: the fixed view's direction with parallel rays over a view plane
+--ortho-height H high, by default the height the fixed view sees at its look-at point; both rendered through caller-supplied rays, not
+with --orbit / --adaptive / --denoise / --progressive / --checkpoint)."""
 import argparse
 import sys
 import time
@@ -37,6 +41,10 @@ def main(argv=None):
     ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="L",
                     help="denoise the frame with L a-trous iterations (default 5) guided by first-hit albedo / normal / position buffers")
     ap.add_argument("--aov-samples", type=int, default=8, metavar="S", help="with --denoise: samples per pixel of the guide buffers")
+    ap.add_argument("--camera", choices=("pinhole", "panorama", "orthographic"), default="pinhole",
+                    help="camera model: the fixed pinhole view (default), an equirectangular panorama from its position, or an orthographic view")
+    ap.add_argument("--ortho-height", type=float, default=None, metavar="H",
+                    help="with --camera orthographic: the height of the view plane (default: what the pinhole view sees at its look-at point)")
     opt = ap.parse_args(argv)
     if opt.adaptive is not None and (opt.progressive > 0 or opt.checkpoint):
         ap.error("--adaptive cannot be combined with --progressive or --checkpoint")
@@ -49,6 +57,13 @@ def main(argv=None):
             ap.error("--aov-samples needs S >= 1")
     if opt.orbit < 0:
         ap.error("--orbit N needs N >= 1")
+    if opt.camera != "pinhole":
+        if opt.orbit or opt.adaptive is not None or opt.denoise is not None or opt.progressive > 0 or opt.checkpoint:
+            ap.error(f"--camera {opt.camera} cannot be combined with --orbit, --adaptive, --denoise, --progressive or --checkpoint")
+        if opt.ortho_height is not None and not opt.ortho_height > 0:
+            ap.error("--ortho-height H needs H > 0")
+    elif opt.ortho_height is not None:
+        ap.error("--ortho-height needs --camera orthographic")
     if opt.orbit > 0:
         if opt.progressive > 0 or opt.checkpoint or opt.adaptive is not None:
             ap.error("--orbit cannot be combined with --progressive, --checkpoint or --adaptive")
@@ -70,7 +85,9 @@ def main(argv=None):
     renderer = (Renderer.default().width(opt.width).height(opt.height).samples(opt.samples).use_bvh(True)
                 .camera(camera).seed(opt.seed))
     start = time.time()
-    if opt.orbit > 0:
+    if opt.camera != "pinhole":
+        render = camera_model_render(renderer, camera, scene, opt)
+    elif opt.orbit > 0:
         from .api import orbit_cameras
         res = renderer.render_views(scene, orbit_cameras(camera, opt.orbit), device=opt.device)
         print(f"Finished Rendering in {int(time.time() - start)} s")
@@ -78,7 +95,9 @@ def main(argv=None):
             save_image(img, name, opt.width, opt.height)
         print(f'Saved {opt.orbit} views to "{names[0]}" .. "{names[-1]}"')
         return 0
-    if opt.denoise is not None:
+    if opt.camera != "pinhole":
+        pass
+    elif opt.denoise is not None:
         render = denoised(renderer, scene, opt)
     elif opt.adaptive is not None:
         res = renderer.render_adaptive(scene, opt.adaptive, opt.min_samples, device=opt.device)
@@ -119,6 +138,24 @@ def denoised(renderer, scene, opt):
     finally:
         ds.close()
     return _lib.denoise(res.linear, aov, res.moments, opt.width, opt.height, opt.denoise, renderer.settings["gamma"], opt.device)[0]
+
+
+def camera_model_render(renderer, camera, scene, opt):
+    """--camera panorama / orthographic: the model's rays, made on the device sample by sample, rendered through fw_render_rays in
+    chunks of samples whose rays stay below 1 GiB; returns rgb8."""
+    import functools
+    import math
+    from .api import orthographic_rays, panorama_rays
+    if opt.camera == "panorama":
+        model = functools.partial(panorama_rays, camera._cam_pos, opt.width, opt.height, seed=opt.seed, device=opt.device)
+    else:
+        h = opt.ortho_height
+        if h is None:       # the height the pinhole view sees at its look-at point
+            dist = float(math.dist(camera._cam_pos.tolist(), camera._look_at.tolist()))
+            h = 2.0 * math.tan(math.radians(camera._vfov) / 2.0) * dist
+        model = functools.partial(orthographic_rays, camera, h, opt.width, opt.height, seed=opt.seed, device=opt.device)
+    chunk = max(1, min(64, (1 << 30) // (opt.width * opt.height * 24)))
+    return renderer.render_camera_model(scene, model, opt.samples, chunk=chunk, device=opt.device).image(opt.width, opt.height)
 
 
 def view_paths(pattern, n):

@@ -114,6 +114,12 @@ class fw_trace_params(C.Structure):
                 ("on_device", i32), ("stream", C.c_void_p)]
 
 
+class fw_render_rays_params(C.Structure):
+    _fields_ = [("n_rays", u32), ("first_sample", u32), ("samples", u32), ("per_sample_rays", i32), ("keys", C.POINTER(u32)),
+                ("key_base", u32), ("seed", u64), ("use_bvh", i32), ("gamma", f32), ("paths_per_batch", u32), ("flags", u32),
+                ("on_device", i32), ("stream", C.c_void_p)]
+
+
 # fw_denoise (include/firework_hip.h): the filter's constants and its parameters
 FW_DENOISE_EPS = 0.01
 FW_DENOISE_NORMAL_POW = 128

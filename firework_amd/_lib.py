@@ -87,6 +87,9 @@ def load(preload=False, device=None):
     lib.fw_render_views.restype = C.c_int
     lib.fw_render_views.argtypes = [C.c_void_p, C.POINTER(A.fw_render_params), C.POINTER(A.fw_camera_settings), C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.POINTER(A.fw_stats)]
+    lib.fw_render_rays.restype = C.c_int
+    lib.fw_render_rays.argtypes = [C.c_void_p, C.POINTER(A.fw_render_rays_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.POINTER(A.fw_stats)]
     lib.fw_render_aovs.restype = C.c_int
     lib.fw_render_aovs.argtypes = [C.c_void_p, C.POINTER(A.fw_render_params), C.c_void_p, C.POINTER(A.fw_stats)]
     lib.fw_denoise.restype = C.c_int
@@ -365,6 +368,69 @@ class DeviceScene:
         lin = np.empty((v, n, 3), np.float32)
         _check(lib, lib.fw_render_views(self.handle, C.byref(p), cams, v, rgb8.ctypes.data, gam.ctypes.data, lin.ctypes.data, C.byref(st)))
         return ViewsResult(rgb8, gam, lin, st.as_dict(), p.width, p.height, pixel_ids is not None)
+
+    def render_rays(self, rays, samples, first_sample=0, accum=None, keys=None, key_base=0, seed=0, use_bvh=True, gamma=2.2, stream=None,
+                    paths_per_batch=0, flags=0):
+        """fw_render_rays: radiance along the caller's rays, samples [first_sample, first_sample + samples) of N entries.  rays: (S, N, 6)
+        float32 origin + direction per sample (S = samples; rays[s] is absolute sample first_sample + s), or (N, 6) for the same rays in
+        every sample.  Draws of entry i are keyed by keys[i] (N uint32) or key_base + i.  accum: (N, 4) float32 sums of the samples
+        before first_sample (updated in place; None: zeros, only with first_sample 0).
+        - numpy arrays: returns a RaysResult of host arrays (rgb8 (N, 3) uint8, gamma / linear (N, 3) float32, accum (N, 4)).
+        - contiguous torch tensors on this scene's device (rays, and keys / accum when given): rendered on `stream` (default: the current
+          torch stream) into new device tensors; returns a RaysResult of tensors.  Device rays are the fast path: host rays pass
+          through pinned staging batch by batch."""
+        from .api import RaysResult
+        lib = self._lib
+        on_device = type(rays).__module__.startswith("torch")
+        shape = tuple(rays.shape)
+        if len(shape) == 3 and shape[2] == 6 and shape[0] == int(samples):
+            per_sample, n = 1, int(shape[1])
+        elif len(shape) == 2 and shape[1] == 6:
+            per_sample, n = 0, int(shape[0])
+        else:
+            raise ValueError(f"rays must have shape (samples={int(samples)}, N, 6) or (N, 6), not {shape}")
+        p = A.fw_render_rays_params()
+        p.n_rays, p.first_sample, p.samples, p.per_sample_rays = n, int(first_sample), int(samples), per_sample
+        p.key_base, p.seed, p.use_bvh, p.gamma = int(key_base), int(seed), int(bool(use_bvh)), float(gamma)
+        p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
+        st = A.fw_stats()
+        if on_device:
+            import torch
+            _check_device_tensor(rays, shape, torch.float32, self.device, "rays")
+            if keys is not None:
+                _check_device_tensor(keys, (n,), torch.int32, self.device, "keys")      # (the bits of uint32 keys)
+            if accum is None:
+                accum = torch.zeros((n, 4), dtype=torch.float32, device=rays.device)
+            _check_device_tensor(accum, (n, 4), torch.float32, self.device, "accum")
+            rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=rays.device)
+            gam = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+            lin = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(rays.device).cuda_stream
+            p.on_device = 1
+            p.stream = C.c_void_p(stream) if stream else None
+            if keys is not None:
+                p.keys = C.cast(C.c_void_p(keys.data_ptr()), C.POINTER(C.c_uint32))
+            _check(lib, lib.fw_render_rays(self.handle, C.byref(p), rays.data_ptr(), accum.data_ptr(), rgb8.data_ptr(), gam.data_ptr(),
+                                           lin.data_ptr(), C.byref(st)))
+            return RaysResult(rgb8, gam, lin, accum, st.as_dict())
+        r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
+        k = None
+        if keys is not None:
+            k = np.ascontiguousarray(np.asarray(keys, dtype=np.uint32))
+            if k.shape != (n,):
+                raise ValueError(f"keys must have shape ({n},)")
+            p.keys = k.ctypes.data_as(C.POINTER(C.c_uint32))
+        if accum is None:
+            accum = np.zeros((n, 4), np.float32)
+        if not (isinstance(accum, np.ndarray) and accum.dtype == np.float32 and accum.shape == (n, 4) and accum.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"accum must be a contiguous float32 array of shape ({n}, 4)")
+        rgb8 = np.empty((n, 3), np.uint8)
+        gam = np.empty((n, 3), np.float32)
+        lin = np.empty((n, 3), np.float32)
+        _check(lib, lib.fw_render_rays(self.handle, C.byref(p), r.ctypes.data, accum.ctypes.data, rgb8.ctypes.data, gam.ctypes.data,
+                                       lin.ctypes.data, C.byref(st)))
+        return RaysResult(rgb8, gam, lin, accum, st.as_dict())
 
     def trace(self, rays, use_bvh, seed=0, key_base=0, rays_per_batch=0, time_kernels=False, stats=None):
         """fw_trace_rays: one root.hit(ray, 0.001, 2e9) per ray.  rays: (n, 6) origin + direction.

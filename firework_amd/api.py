@@ -863,6 +863,102 @@ class ViewsResult:
             self.linear_rgb = self.linear_rgb.reshape(v, self.height, self.width, 3)
 
 
+@dataclass
+class RaysResult:
+    """fw_render_rays' outputs, in ray order (numpy arrays, or device tensors for device rays): rgb8 (N, 3) uint8, gamma / linear (N, 3)
+    float32 as RenderResult, accum (N, 4) float32 sums as fw_render_progressive keeps them."""
+    rgb8: object
+    gamma: object
+    linear: object
+    accum: object
+    stats: dict
+
+    def image(self, width: int, height: int) -> np.ndarray:
+        rgb8 = self.rgb8.cpu().numpy() if type(self.rgb8).__module__.startswith("torch") else self.rgb8
+        return np.asarray(rgb8).reshape(height, width, 3)
+
+
+# --------------------------------------------------------------------------- camera models over fw_render_rays
+def _hash32(x: np.ndarray) -> np.ndarray:
+    """a 32-bit integer mix (uint32 arrays, wrapping arithmetic)"""
+    x = x.astype(np.uint32, copy=True)
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7FEB352D)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846CA68B)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def pixel_jitter(seed: int, sample: int, n: int) -> np.ndarray:
+    """(n, 2) float64 in [0, 1): the sub-pixel offsets (x, y) of pixels 0..n-1 for one absolute sample, from a counter-based generator
+    keyed by (seed, sample, pixel, axis): sample s's offsets do not depend on which other samples are made with them."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    s32 = ((seed & 0xFFFFFFFF) ^ (((seed >> 32) * 0x9E3779B9) & 0xFFFFFFFF)) & 0xFFFFFFFF
+    key = _hash32(np.array([s32 ^ int(_hash32(np.array([(int(sample) + 0x9E3779B9) & 0xFFFFFFFF]))[0])], np.uint32))[0]
+    ctr = np.arange(2 * n, dtype=np.uint64).astype(np.uint32)
+    bits = _hash32(_hash32(ctr) ^ key) >> np.uint32(8)
+    return (bits.astype(np.float64) * 2.0 ** -24).reshape(n, 2)
+
+
+def _pixel_grid(width: int, height: int, sample: int, seed: int, jitter: bool):
+    """x + xi_x and j + xi_y of every pixel, row-major with row 0 = image top, float64"""
+    w, h = int(width), int(height)
+    if w < 1 or h < 1:
+        raise ValueError("width and height must be >= 1")
+    j, x = np.divmod(np.arange(w * h, dtype=np.int64), w)
+    xi = pixel_jitter(seed, sample, w * h) if jitter else np.full((w * h, 2), 0.5)
+    return x + xi[:, 0], j + xi[:, 1]
+
+
+def _rays_out(o: np.ndarray, d: np.ndarray, device):
+    rays = np.ascontiguousarray(np.concatenate([o, d], axis=1).astype(np.float32))
+    if device is None:
+        return rays
+    import torch
+    return torch.from_numpy(rays).to(torch.device("cuda", device) if isinstance(device, int) else device)
+
+
+def panorama_rays(position, width: int, height: int, sample: int, seed: int = 0, jitter: bool = True, device=None):
+    """Equirectangular panorama rays from `position`: (W*H, 6) float32 origin + direction, row-major, row 0 = image top, for absolute
+    sample `sample` (jitter from pixel_jitter(seed, sample); jitter=False: pixel centres).  The exact inverse of the HDR environment
+    lookup (sphere_uv, env_sample): for pixel (x, row j), u = (x + xi_x) / W, v = 1 - (j + xi_y) / H, phi = pi - 2 pi u,
+    theta = pi v - pi / 2, d = (cos theta cos phi, sin theta, cos theta sin phi) — so a panorama rendered this way loads as an
+    HdrEnvironment with the same orientation.  Computed in float64, rounded to float32.  device: a torch device (or index) to return a
+    tensor on instead of a numpy array."""
+    w, h = int(width), int(height)
+    px, py = _pixel_grid(w, h, sample, seed, jitter)
+    u, v = px / w, 1.0 - py / h
+    phi, theta = np.pi - 2.0 * np.pi * u, np.pi * v - np.pi / 2.0
+    d = np.stack([np.cos(theta) * np.cos(phi), np.sin(theta), np.cos(theta) * np.sin(phi)], axis=1)
+    o = np.broadcast_to(np.asarray(position, np.float64).reshape(1, 3), d.shape)
+    return _rays_out(o, d, device)
+
+
+def orthographic_rays(camera: CameraSettings, view_height: float, width: int, height: int, sample: int, seed: int = 0, jitter: bool = True,
+                      device=None):
+    """Orthographic rays: (W*H, 6) float32, row-major, row 0 = image top, for absolute sample `sample` (jitter as panorama_rays).  The
+    basis is camera.rs's: w = unit(cam_pos - look_at), u = unit(Y x w), v = w x u.  The view plane is view_height high and
+    view_height * W / H wide, centred on cam_pos; pixel (x, row j) starts at cam_pos + (s - 1/2) view_width u + (t - 1/2) view_height v
+    with s = (x + xi_x) / W, t = 1 - (j + xi_y) / H, and every ray's direction is look_at - cam_pos.  Computed in float64, rounded to
+    float32.  The camera's field of view, aperture and focus distance are not used."""
+    w_px, h_px = int(width), int(height)
+    pos = np.asarray(camera._cam_pos, np.float64)
+    at = np.asarray(camera._look_at, np.float64)
+    w = pos - at
+    w = w / np.linalg.norm(w)
+    u = np.cross(np.array([0.0, 1.0, 0.0]), w)
+    u = u / np.linalg.norm(u)
+    v = np.cross(w, u)
+    vh = float(view_height)
+    vw = vh * w_px / h_px
+    px, py = _pixel_grid(w_px, h_px, sample, seed, jitter)
+    s, t = px / w_px, 1.0 - py / h_px
+    o = pos + ((s - 0.5) * vw)[:, None] * u + ((t - 0.5) * vh)[:, None] * v
+    d = np.broadcast_to((at - pos).reshape(1, 3), o.shape)
+    return _rays_out(o, d, device)
+
+
 def orbit_cameras(camera: CameraSettings, n: int) -> list:
     """n cameras evenly spaced in azimuth around `camera`'s look_at: view k rotates cam_pos - look_at about +Y by 2 pi k / n (computed
     in float64, rounded to float32); look_at, field of view, aperture and focus distance stay.  View 0 is `camera` itself, unchanged."""
@@ -1046,6 +1142,51 @@ class Renderer:
         ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
         try:
             return ds.render_views(self, list(cameras), ids)
+        finally:
+            if ds is not scene:
+                ds.close()
+
+    def render_rays(self, scene, rays, samples: Optional[int] = None, first_sample: int = 0, accum=None, keys=None, key_base: int = 0,
+                    device: int = 0, stream=None) -> RaysResult:
+        """Radiance along caller-supplied rays (not in the reference; fw_render_rays) with this renderer's seed, use_bvh, gamma, batch
+        size and flags; its camera, size and sample count are not used.  rays: (S, N, 6) per sample (S = samples, default S) or (N, 6)
+        for the same rays in every sample (samples then defaults to settings["samples"]); numpy arrays or device tensors.  See
+        _lib.DeviceScene.render_rays.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        from . import _lib
+        s = self.settings
+        if samples is None:
+            samples = int(rays.shape[0]) if len(rays.shape) == 3 else int(s["samples"])
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            return ds.render_rays(rays, samples, first_sample, accum, keys, key_base, seed=s["seed"], use_bvh=s["use_bvh"], gamma=s["gamma"],
+                                  stream=stream, paths_per_batch=s["paths_per_batch"], flags=s["flags"])
+        finally:
+            if ds is not scene:
+                ds.close()
+
+    def render_camera_model(self, scene, model, samples: int, chunk: int = 64, device: int = 0) -> RaysResult:
+        """A camera model of the caller's rendered through fw_render_rays: model(sample) returns the (N, 6) rays of one absolute sample
+        (numpy, or device tensors), e.g. functools.partial(panorama_rays, position, W, H) with seed=... bound.  The samples
+        [0, samples) are rendered in chunks of `chunk`, accumulated in one (N, 4) buffer; any chunk size gives the same bits.  Returns
+        the last chunk's RaysResult (the whole image)."""
+        from . import _lib
+        samples, chunk = int(samples), max(1, int(chunk))
+        if samples < 1:
+            raise ValueError("samples must be >= 1")
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            accum, res = None, None
+            for lo in range(0, samples, chunk):
+                hi = min(samples, lo + chunk)
+                batch = [model(k) for k in range(lo, hi)]
+                if type(batch[0]).__module__.startswith("torch"):
+                    import torch
+                    rays = torch.stack(batch).contiguous()
+                else:
+                    rays = np.ascontiguousarray(np.stack([np.asarray(b, np.float32) for b in batch]))
+                res = self.render_rays(ds, rays, hi - lo, lo, accum)
+                accum = res.accum
+            return res
         finally:
             if ds is not scene:
                 ds.close()

@@ -251,6 +251,10 @@ void launch_raygen_views(const LaunchCfg &, const DCamera *cams, uint32_t n_view
 void launch_resolve_views(const LaunchCfg &, const DFrame &, uint32_t n_view, const float4 *accum, uint32_t total_spp, float gamma,
                           uint8_t *rgb8, float *gamma_rgb, float *linear_rgb);
 void launch_view_ids(hipStream_t stream, const uint32_t *src, uint32_t n_view, uint32_t n, uint32_t *out);
+// fw_render_rays: k_raygen_rays starts every path from the caller's ray (per_sample: `rays` is the batch's sample-major slab, else one ray
+// per entry) and sets *err for a ray with a non-finite component or an all-zero direction; k_ray_keys fills the key table base + i
+void launch_raygen_rays(const LaunchCfg &, const float *rays, bool per_sample, uint32_t *err, const DFrame &, DPaths out, uint32_t n_paths);
+void launch_ray_keys(hipStream_t stream, uint32_t base, uint32_t n, uint32_t *out);
 void launch_extend(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, float2 *hits, int segment, bool use_bvh, DPark park);
 void launch_extend_exact(const LaunchCfg &, const DScene &, const DFrame &, const DPaths &in, float2 *hits, int segment, bool use_bvh);
 void launch_shade(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,

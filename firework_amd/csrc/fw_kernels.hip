@@ -3882,6 +3882,63 @@ __global__ __launch_bounds__(WB) void k_camera_rays(DCamera cam, DFrame f, uint3
     }
 }
 
+// fw_render_rays: the k_raygen of a render over the caller's rays.  Path i is entry p_local of sample s_local (key_of_linear's float
+// quotient and fix-up) and starts from ray r = i of the batch's slab `rays` (per_sample: sample-major, spp_batch x n_pixels rays) or
+// r = p_local (fixed rays: one per entry); its draws are key_of_linear's (DFrame.pixel_ids: the call's key table).  A chunk's 64 rays
+// are contiguous per sample, and with fixed rays unless the chunk wraps round the entries: then six coalesced dword loads per lane,
+// transposed to one ray per lane through LDS as in k_trace_load; otherwise every lane loads its own ray.  A ray with a non-finite
+// component or an all-zero direction is replaced by a finite one and sets *err (the call then returns FW_ERR_BAD_ARG).  The rays are
+// stored in the 24-byte form (DFrame.pinhole0 = 0) and flagged for the exact walk as k_trace_load flags them.  A separate kernel, so
+// that k_raygen keeps its code.
+__global__ __launch_bounds__(WB) void k_raygen_rays(const float *__restrict__ rays, uint32_t per_sample, uint32_t *__restrict__ err, DFrame f,
+                                                    DPaths out, DQueue q, uint32_t n_paths) {
+    __shared__ float tr[6 * 64];
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    if (w >= q.n_waves) return;
+    uint32_t produced = 0;
+    for (uint32_t chunk = 0;; chunk++) {
+        const uint32_t id0 = chunk * (q.n_waves * 64u) + w * 64u;
+        if (id0 >= n_paths) break;
+        const uint32_t m = min(64u, n_paths - id0), i = id0 + lane;
+        const uint32_t slot = w * q.cap + chunk * 64u + lane;
+        const uint32_t s_local = (uint32_t)((float)i * f.inv_n_pixels);
+        int32_t p_local = (int32_t)(i - s_local * f.n_pixels);
+        if (p_local < 0) p_local += (int32_t)f.n_pixels; else if ((uint32_t)p_local >= f.n_pixels) p_local -= (int32_t)f.n_pixels;
+        const uint32_t r = per_sample ? i : (uint32_t)p_local;
+        const uint32_t r0 = (uint32_t)__shfl((int)r, 0);                          // lane 0's ray (m >= 1: lane 0 is a path)
+        float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (per_sample || r0 + m <= f.n_pixels) {                                 // wave-uniform: rays r0 .. r0 + m - 1
+            const float *src = rays + (size_t)r0 * 6u;
+#pragma unroll
+            for (uint32_t k = 0; k < 6u; k++) { const uint32_t e = k * 64u + lane; if (e < 6u * m) tr[e] = src[e]; }
+            __syncthreads();                // (one wave per workgroup: the barrier orders the LDS accesses only)
+#pragma unroll
+            for (uint32_t k = 0; k < 6u; k++) v[k] = tr[lane * 6u + k];
+            __syncthreads();
+        } else if (lane < m) {
+#pragma unroll
+            for (uint32_t k = 0; k < 6u; k++) v[k] = rays[(size_t)r * 6u + k];
+        }
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < 6; k++) ok = ok && finite_f(v[k]);
+        ok = ok && !(v[3] == 0.f && v[4] == 0.f && v[5] == 0.f);
+        if (lane < m) {
+            if (!ok) { *err = 1u; v[0] = v[1] = v[2] = 0.f; v[3] = v[4] = v[5] = 1.f; }
+            qst(&out.ray_a[slot], make_float4(v[0], v[1], v[2], v[3]));
+            qst(&out.ray_b[slot], make_float2(v[4], v[5]));
+        }
+        const bool fl = lane < m && f.ex.mode && needs_exact(f.ex, v[0], v[1], v[2], v[3], v[4], v[5]);
+        if (f.ex.mode) flag_exact(f.ex, fl, slot, 0);
+        produced += m;
+    }
+    if (lane == 0) q.wcount[w] = produced;                                    // segment 0 queue length of this wave
+}
+// fw_render_rays' key table when the caller gives none: out[i] = base + i, i < n
+__global__ __launch_bounds__(BLOCK) void k_ray_keys(uint32_t base, uint32_t n, uint32_t *__restrict__ out) {
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) out[i] = base + i;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------------
@@ -3904,6 +3961,12 @@ void launch_raygen(const LaunchCfg &c, const DCamera &cam, const DFrame &f, DPat
 }
 void launch_raygen_views(const LaunchCfg &c, const DCamera *cams, uint32_t n_view, const DFrame &f, DPaths out, float4 *sample_rad, uint32_t n_paths) {
     hipLaunchKernelGGL(k_raygen_views, wave_grid(c), dim3(WB), 0, c.stream, cams, n_view, f, out, sample_rad, c.q, n_paths);
+}
+void launch_raygen_rays(const LaunchCfg &c, const float *rays, bool per_sample, uint32_t *err, const DFrame &f, DPaths out, uint32_t n_paths) {
+    hipLaunchKernelGGL(k_raygen_rays, wave_grid(c), dim3(WB), 0, c.stream, rays, per_sample ? 1u : 0u, err, f, out, c.q, n_paths);
+}
+void launch_ray_keys(hipStream_t stream, uint32_t base, uint32_t n, uint32_t *out) {
+    hipLaunchKernelGGL(k_ray_keys, dim3(std::min<uint32_t>((n + BLOCK - 1) / BLOCK, 4096u)), dim3(BLOCK), 0, stream, base, n, out);
 }
 void launch_resolve_views(const LaunchCfg &c, const DFrame &f, uint32_t n_view, const float4 *accum, uint32_t total_spp, float gamma,
                           uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
@@ -4074,7 +4137,7 @@ void preload_kernels() {
     FW_TOUCH(k_extend_tlas); FW_TOUCH(k_extend_tlas_park); FW_TOUCH(k_blas); FW_TOUCH(k_blas_lds<true>); FW_TOUCH(k_blas_lds<false>); FW_TOUCH(k_extend_tlas_lds);
     FW_TOUCH((k_blas_wide<WIDE_F32, true>)); FW_TOUCH((k_blas_wide<WIDE_F32, false>)); FW_TOUCH((k_blas_wide<WIDE_Q8, true>)); FW_TOUCH((k_blas_wide<WIDE_Q8, false>));
     FW_TOUCH(k_extend_tlas_wide<true>); FW_TOUCH(k_extend_tlas_wide<false>); FW_TOUCH((k_extend_tlas_wide<true, true>)); FW_TOUCH((k_extend_tlas_wide<false, true>)); FW_TOUCH(k_extend_exact); FW_TOUCH(k_queue_totals); FW_TOUCH(k_count_deposits); FW_TOUCH(k_accumulate); FW_TOUCH(k_tile_order);
-    FW_TOUCH(k_resolve); FW_TOUCH(k_raygen_views); FW_TOUCH(k_resolve_views); FW_TOUCH(k_view_ids); FW_TOUCH(k_accumulate_adaptive); FW_TOUCH(k_adaptive_select); FW_TOUCH(k_adaptive_compact); FW_TOUCH(k_resolve_adaptive); FW_TOUCH(k_scatter_tiles); FW_TOUCH(k_trace_load); FW_TOUCH(k_trace_store); FW_TOUCH(k_camera_rays);
+    FW_TOUCH(k_resolve); FW_TOUCH(k_raygen_views); FW_TOUCH(k_resolve_views); FW_TOUCH(k_view_ids); FW_TOUCH(k_raygen_rays); FW_TOUCH(k_ray_keys); FW_TOUCH(k_accumulate_adaptive); FW_TOUCH(k_adaptive_select); FW_TOUCH(k_adaptive_compact); FW_TOUCH(k_resolve_adaptive); FW_TOUCH(k_scatter_tiles); FW_TOUCH(k_trace_load); FW_TOUCH(k_trace_store); FW_TOUCH(k_camera_rays);
     FW_TOUCH((k_shade<0, 0, false>)); FW_TOUCH((k_shade<0, 0, true>)); FW_TOUCH((k_shade<0, 1, false>)); FW_TOUCH((k_shade<0, 1, true>));
     FW_TOUCH((k_shade<1, 0, false>)); FW_TOUCH((k_shade<1, 0, true>)); FW_TOUCH((k_shade<1, 1, false>)); FW_TOUCH((k_shade<1, 1, true>));
     FW_TOUCH((k_shade<2, 0, false>)); FW_TOUCH((k_shade<2, 0, true>)); FW_TOUCH((k_shade<2, 1, false>)); FW_TOUCH((k_shade<2, 1, true>));

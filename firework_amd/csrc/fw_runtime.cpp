@@ -772,7 +772,8 @@ struct Workspace {
     // and allocated two dozen multi-GB buffers, 2 s in the caller's timed region (profiles/r03z_oneshot_trace.txt: the first
     // volume frame after suzanne).  The arena only grows, in steps of 1 GiB.
     struct Lane { void *ray_a[2] = {nullptr, nullptr}, *ray_b[2] = {nullptr, nullptr}, *state[2] = {nullptr, nullptr}, *hits = nullptr, *sample_rad = nullptr,
-                       *wcount = nullptr, *park_a = nullptr, *park_b = nullptr, *park_m = nullptr, *pcount = nullptr, *dep_bits = nullptr, *exact_slots = nullptr, *atten = nullptr;
+                       *wcount = nullptr, *park_a = nullptr, *park_b = nullptr, *park_m = nullptr, *pcount = nullptr, *dep_bits = nullptr, *exact_slots = nullptr, *atten = nullptr,
+                       *rays = nullptr;   // fw_render_rays with host rays: the batch's rays, copied in through ray_host
                   hipStream_t stream = nullptr;
                   std::vector<hipEvent_t> events; };
     DevBuf arena;
@@ -793,6 +794,10 @@ struct Workspace {
     DevBuf ad_accum, ad_moments, ad_ids[2], ad_mask, ad_counts;
     hipEvent_t ad_ev[2] = {nullptr, nullptr};
     DevBuf view_ids, view_cams;           // fw_render_views: a view group's repeated pixel table and its cameras (rewritten by every call)
+    // fw_render_rays: the key table, the error word of the invalid-ray check, the fixed rays of a host caller, and the pinned staging
+    // host rays pass through (one slab per lane)
+    DevBuf ray_keys, ray_err, ray_fixed;
+    void *ray_host = nullptr; size_t ray_host_bytes = 0;
     uint32_t *ad_count_host = nullptr;
     void *staging = nullptr; size_t staging_bytes = 0;  // pinned host memory the scene blob is assembled in (k_upload reads it)
     void *host_out = nullptr; size_t host_out_bytes = 0; // pinned host memory the counters and output frames are copied into
@@ -809,7 +814,8 @@ struct Workspace {
         if (staging) { (void)hipHostFree(staging); staging = nullptr; staging_bytes = 0; }
         if (host_out) { (void)hipHostFree(host_out); host_out = nullptr; host_out_bytes = 0; }
         tile_ids.release(); tile_w = tile_h = 0;
-        for (DevBuf *b : {&ad_accum, &ad_moments, &ad_ids[0], &ad_ids[1], &ad_mask, &ad_counts, &view_ids, &view_cams}) b->release();
+        for (DevBuf *b : {&ad_accum, &ad_moments, &ad_ids[0], &ad_ids[1], &ad_mask, &ad_counts, &view_ids, &view_cams, &ray_keys, &ray_err, &ray_fixed}) b->release();
+        if (ray_host) { (void)hipHostFree(ray_host); ray_host = nullptr; ray_host_bytes = 0; }
         for (hipEvent_t &e : ad_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ad_count_host) { (void)hipHostFree(ad_count_host); ad_count_host = nullptr; }
         for (DevBuf *b : {&accum, &totals, &pixel_ids, &out_rgb8, &out_gamma, &out_linear, &scene_cache, &arena}) b->release();
@@ -1932,17 +1938,25 @@ struct AdaptiveRound { const uint32_t *ids; uint32_t n; float4 *accum, *moments;
 // that of its real pixel, so each view is the fw_render of its camera.  The outputs are the group's n x N x 3 values.
 struct ViewGroup { const fw::DCamera *cams; uint32_t n; };
 
+// The caller's rays of fw_render_rays (rays_impl), rendered by render_impl: a frame of n entries (p: width n, height 1, no camera, no
+// pixel ids) whose paths start from `rays` (per_sample: sample-major, rays[s] of the call's sample first_sample + s; otherwise one ray
+// per entry) instead of the camera's, keyed by keys[i] or key_base + i.  on_device: rays and keys are device pointers (p's outputs and
+// accum follow p->outputs_on_device).  Entries stay in ray order (no tile order), the rays take the exact walk by fw_trace_rays' rule,
+// and the frame never runs as a frame graph; the cached graph's key is cleared if the call grows the path arena.
+struct RayInput { const float *rays; uint32_t n; bool per_sample; const uint32_t *keys; uint32_t key_base; bool on_device; };
+
 // first_sample / user_accum: fw_render_progressive (0 / nullptr for a plain render); rd: a round of fw_render_adaptive; vg: a view group of
-// fw_render_views
+// fw_render_views; ri: the rays of fw_render_rays
 int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb, fw_stats *stats,
-                uint32_t first_sample = 0, float *user_accum = nullptr, const AdaptiveRound *rd = nullptr, const ViewGroup *vg = nullptr) {
+                uint32_t first_sample = 0, float *user_accum = nullptr, const AdaptiveRound *rd = nullptr, const ViewGroup *vg = nullptr,
+                const RayInput *ri = nullptr) {
     if (!sc || !p) return fail(FW_ERR_BAD_ARG, "null argument");
     if (p->width == 0 || p->height == 0 || p->samples == 0) return fail(FW_ERR_BAD_ARG, "width, height and samples must be > 0");
     if (!(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be > 0");
     if (p->rng_mode != FW_RNG_CTR) return fail(FW_ERR_UNSUPPORTED, "the HIP path implements FW_RNG_CTR only (FW_RNG_LCG is a sequential stream)");
     uint64_t full = (uint64_t)p->width * p->height;
     if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
-    const uint32_t n_view = rd ? rd->n : (p->pixel_ids ? p->n_pixels : (uint32_t)full);     // the pixels of one view
+    const uint32_t n_view = rd ? rd->n : ri ? ri->n : (p->pixel_ids ? p->n_pixels : (uint32_t)full);     // the pixels of one view
     if (n_view == 0) return fail(FW_ERR_BAD_ARG, "no pixels to render");
     if ((uint64_t)first_sample + p->samples > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_sample + samples overflows");
     if (p->pixel_ids) for (uint32_t i = 0; i < n_view; i++) if (p->pixel_ids[i] >= full) return fail(FW_ERR_BAD_ARG, "pixel id out of range");
@@ -1980,6 +1994,9 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     const uint32_t budget = bb.budget;
     uint32_t spp_b = std::max<uint32_t>(1u, budget / n_pix);
     spp_b = std::min(spp_b, (p->samples + (uint32_t)n_lanes - 1) / (uint32_t)n_lanes);     // at least one batch per lane
+    // (caller rays: k_raygen_rays finds a fixed ray's entry from the sample quotient, exact only while spp_batch < 2^21 — key_of_linear's
+    //  bound.  Batching changes no result: the sums are taken in sample order whatever the batches)
+    if (ri) spp_b = std::min(spp_b, (1u << 21) - 1u);
     uint64_t paths64 = (uint64_t)n_pix * spp_b;
     if (paths64 > 0x7fffffffull) return fail(FW_ERR_UNSUPPORTED, "too many paths per batch");
     uint32_t max_paths = (uint32_t)paths64;
@@ -2025,8 +2042,12 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
 #else
     const bool fused_req = false, tlas_refill = true;
 #endif
-    const uint32_t exact_mode = fused_req ? 0u : ((sc->ex.mode & 1u) | (p->use_bvh ? (sc->ex.mode & 6u) : ((sc->ex.mode & 4u) && sc->d.has_mesh ? 4u : 0u)));
+    // (caller rays: fw_trace_rays' rule — under use_bvh the flag rule stays on (EX_TRACE_ZERO) for rays with a zero direction component,
+    //  which caller rays along an axis have and camera rays practically never)
+    const uint32_t exact_mode = fused_req ? 0u : ((sc->ex.mode & 1u) | (p->use_bvh ? (sc->ex.mode & 6u) | (ri ? fw::EX_TRACE_ZERO : 0u)
+                                                                                   : ((sc->ex.mode & 4u) && sc->d.has_mesh ? 4u : 0u)));
     const bool park_meshes = p->use_bvh && sc->d.has_mesh != 0 && tlas_refill;
+    const bool stage_rays = ri && ri->per_sample && !ri->on_device;      // host rays of every sample: one batch's slab per lane
     int rc = FW_OK;
     auto need = [&](DevBuf &b, size_t n) { if (!rc) rc = b.alloc(n); };
     // the lanes' buffers: slices of the workspace's arena (Workspace::Lane), laid out twice — sizes first, then pointers
@@ -2042,6 +2063,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
             if (exact_product && !fused_req) put(L.atten, (size_t)cap * (fw::MAX_SEGMENTS - 1) * fw::B_ATTEN); else L.atten = nullptr;
             if (exact_mode) put(L.exact_slots, 2 * (size_t)max_paths * 4 + 64);   // two lists of at most every ray of a segment, + the counters
             put(L.wcount, (size_t)(fw::MAX_SEGMENTS + 1) * q.n_waves * 4);
+            if (stage_rays) put(L.rays, (size_t)max_paths * 24); else L.rays = nullptr;
             if (park_meshes) {     // rays handed from k_extend_scan / k_extend_tlas_park to k_blas*: 40 B per slot
                 const size_t pcap = (size_t)(q.cap + 64u) * q.n_waves;     // park regions: q.cap + 64 entries per queue (DPark.stride)
                 put(L.park_a, pcap * 16); put(L.park_b, pcap * 8); put(L.park_m, pcap * 16); put(L.pcount, (size_t)q.n_waves * 8);   // pcount[n_waves] + ptotal[n_waves]
@@ -2058,7 +2080,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         const auto ta = std::chrono::steady_clock::now();
         const bool grow = want > ws->arena.bytes;
         if (!rc && grow) rc = arena_reserve_locked(ws, sc->device, want);
-        if (rd && grow) { ws->fg.key = 0; ws->fg.seen = 0; }     // a later plain render never replays launches against the moved arena
+        if ((rd || ri) && grow) { ws->fg.key = 0; ws->fg.seen = 0; }     // a later plain render never replays launches against the moved arena
         if (O.trace && grow) fprintf(stderr, "[firework] render: path arena grown to %.1f GiB in %.2f ms\n", (double)want / (double)(1 << 30),
                                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count());
         if (!rc) layout((uint8_t *)ws->arena.p);
@@ -2070,9 +2092,22 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     if (p->pixel_ids) need(ws->pixel_ids, (size_t)n_view * 4);
     // a whole frame is traced in the library's own 16x16-tile order (k_tile_order); k_resolve undoes it.  Not for progressive
     // renders: their accumulation buffer belongs to the caller and stays in pixel order.
-    const bool own_order = !p->pixel_ids && !user_accum && !rd && n_view >= 1024 && !O.no_tile_order;
+    const bool own_order = !p->pixel_ids && !user_accum && !rd && !ri && n_view >= 1024 && !O.no_tile_order;
     if (own_order) { const void *before = ws->tile_ids.p; need(ws->tile_ids, (size_t)n_view * 4); if (ws->tile_ids.p != before) ws->tile_w = ws->tile_h = 0; }
     if (vg) { need(ws->view_ids, (size_t)n_pix * 4); need(ws->view_cams, (size_t)vg->n * sizeof(fw::DCamera)); }
+    const bool ray_table = ri && (ri->keys || ri->key_base != 0);       // (keys 0..n-1 need no table: key_of_linear's p_local)
+    if (ri) {
+        need(ws->ray_err, 256);
+        if (ray_table) need(ws->ray_keys, (size_t)n_pix * 4);
+        if (!ri->per_sample && !ri->on_device) need(ws->ray_fixed, (size_t)n_pix * 24);
+        const size_t host_bytes = ri->on_device ? 0 : ri->per_sample ? (size_t)n_lanes * max_paths * 24 : (size_t)n_pix * 24;
+        if (!rc && ws->ray_host_bytes < host_bytes) {
+            if (ws->ray_host) (void)hipHostFree(ws->ray_host);
+            ws->ray_host = nullptr; ws->ray_host_bytes = 0;
+            if (hipHostMalloc(&ws->ray_host, host_bytes, hipHostMallocDefault) != hipSuccess) return fail(FW_ERR_OOM, "pinned ray staging allocation failed");
+            ws->ray_host_bytes = host_bytes;
+        }
+    }
     uint8_t *d_rgb8 = rgb8; float *d_gamma = gamma_rgb, *d_linear = linear_rgb;
     if (!p->outputs_on_device) {
         if (rgb8) { need(ws->out_rgb8, (size_t)n_pix * 3); d_rgb8 = (uint8_t *)ws->out_rgb8.p; }
@@ -2097,6 +2132,16 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
                             (uint32_t *)ws->view_ids.p);
         HIPCHK(hipMemcpyAsync(ws->view_cams.p, vg->cams, (size_t)vg->n * sizeof(fw::DCamera), hipMemcpyHostToDevice, stream));
     }
+    // caller rays: the error word, the key table (the caller's keys, or key_base + i) and fixed host rays, in stream order before the frame
+    if (ri) {
+        HIPCHK(hipMemsetAsync(ws->ray_err.p, 0, 4, stream));
+        if (ri->keys) HIPCHK(hipMemcpyAsync(ws->ray_keys.p, ri->keys, (size_t)n_pix * 4, ri->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+        else if (ray_table) fw::launch_ray_keys(stream, ri->key_base, n_pix, (uint32_t *)ws->ray_keys.p);
+        if (!ri->per_sample && !ri->on_device) {
+            std::memcpy(ws->ray_host, ri->rays, (size_t)n_pix * 24);
+            HIPCHK(hipMemcpyAsync(ws->ray_fixed.p, ws->ray_host, (size_t)n_pix * 24, hipMemcpyHostToDevice, stream));
+        }
+    }
     if (user_accum)     // resume: the sums of the samples rendered so far (host or device memory, like the outputs)
         HIPCHK(hipMemcpyAsync(ws->accum.p, user_accum, (size_t)n_pix * 16, p->outputs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
     else if (!rd) HIPCHK(hipMemsetAsync(ws->accum.p, 0, (size_t)n_pix * 16, stream));
@@ -2115,10 +2160,11 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     if (O.no_shade_defer) cfg.shade_mode = 0; else if (sc->has_expensive && O.shade_list && q.cap <= 65536u) cfg.shade_mode = 2;
 #endif
 
-    fw::DCamera cam = vg ? vg->cams[0] : make_camera(p->camera, p->width, p->height);
+    fw::DCamera cam = vg ? vg->cams[0] : ri ? fw::DCamera{} : make_camera(p->camera, p->width, p->height);
     fw::DFrame fr{};         // (zeroed: the frame graph's key hashes these structs, padding and not-yet-set per-batch fields included)
     fr.width = p->width; fr.height = p->height; fr.n_pixels = n_pix; fr.inv_n_pixels = 1.0f / (float)n_pix; fr.inv_width = 1.0f / (float)p->width;
-    fr.pixel_ids = rd ? rd->ids : vg ? (const uint32_t *)ws->view_ids.p : (p->pixel_ids ? (const uint32_t *)ws->pixel_ids.p : (own_order ? (const uint32_t *)ws->tile_ids.p : nullptr));
+    fr.pixel_ids = rd ? rd->ids : vg ? (const uint32_t *)ws->view_ids.p : ri ? (ray_table ? (const uint32_t *)ws->ray_keys.p : nullptr)
+                 : (p->pixel_ids ? (const uint32_t *)ws->pixel_ids.p : (own_order ? (const uint32_t *)ws->tile_ids.p : nullptr));
     fr.scatter_out = own_order ? 1u : 0u;
     fr.seed32 = (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u);
     fr.q_n_waves = q.n_waves; fr.q_shift = q.cpw_shift;
@@ -2130,7 +2176,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     //  24-byte form, which gives the same bits)
     bool one_position = true;
     if (vg) for (uint32_t v = 1; v < vg->n; v++) one_position = one_position && vg->cams[v].lens_radius == 0.f && std::memcmp(vg->cams[v].position, cam.position, sizeof cam.position) == 0;
-    fr.pinhole0 = (one_position && cam.lens_radius == 0.f && not_negative_zero(cam.position[0]) && not_negative_zero(cam.position[1]) && not_negative_zero(cam.position[2]) &&
+    fr.pinhole0 = (!ri && one_position && cam.lens_radius == 0.f && not_negative_zero(cam.position[0]) && not_negative_zero(cam.position[1]) && not_negative_zero(cam.position[2]) &&
                    !O.no_short_rays) ? 1u : 0u;
     // 4-byte hit records where k_shade can recompute t cheaply and exactly: the linear scan over spheres, rects and Rect3d
     fr.hit4 = (!p->use_bvh && sc->simple_shapes && !exact_mode && !O.no_hit4 && !fused_req) ? 1u : 0u;
@@ -2273,6 +2319,19 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         if (n_lanes > 1) HIPCHK(hipEventRecord(ws->events[3 + b], c.ls));
         return FW_OK;
     };
+    // caller rays: where batch b's rays lie.  Host rays of every sample are copied into the lane's slab through the lane's pinned
+    // slab, after the lane's previous batch has finished with both (a wait on the lane's stream: correct, not fast)
+    auto batch_rays = [&](uint32_t b, const BatchCtx &c, const float *&src) -> int {
+        if (!ri->per_sample) { src = ri->on_device ? ri->rays : (const float *)ws->ray_fixed.p; return FW_OK; }
+        const size_t first = (size_t)b * spp_b * n_pix * 6, bytes = (size_t)c.n_paths * 24;
+        if (ri->on_device) { src = ri->rays + first; return FW_OK; }
+        HIPCHK(hipStreamSynchronize(c.ls));
+        uint8_t *slab = (uint8_t *)ws->ray_host + (size_t)c.lane * max_paths * 24;
+        std::memcpy(slab, ri->rays + first, bytes);
+        HIPCHK(hipMemcpyAsync(ws->lanes[c.lane].rays, slab, bytes, hipMemcpyHostToDevice, c.ls));
+        src = (const float *)ws->lanes[c.lane].rays;
+        return FW_OK;
+    };
     auto enqueue_frame = [&]() -> int {
     if (int frc = fork_lanes()) return frc;
     for (uint32_t b0 = 0; b0 < n_batches; b0 += (uint32_t)n_lanes) {
@@ -2280,7 +2339,12 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         BatchCtx ctx[Workspace::MAX_LANES];
         for (int g = 0; g < group; g++) {
             if (int brc = begin_batch(b0 + (uint32_t)g, ctx[g])) return brc;
-            if (vg) timed(ctx[g], 0, [&] { fw::launch_raygen_views(ctx[g].cfg, (const fw::DCamera *)ws->view_cams.p, n_view, ctx[g].fr, ctx[g].buf[0], ctx[g].srad, ctx[g].n_paths); });
+            if (ri) {
+                const float *src = nullptr;
+                if (int src_rc = batch_rays(b0 + (uint32_t)g, ctx[g], src)) return src_rc;
+                timed(ctx[g], 0, [&] { fw::launch_raygen_rays(ctx[g].cfg, src, ri->per_sample, (uint32_t *)ws->ray_err.p, ctx[g].fr, ctx[g].buf[0], ctx[g].n_paths); });
+            }
+            else if (vg) timed(ctx[g], 0, [&] { fw::launch_raygen_views(ctx[g].cfg, (const fw::DCamera *)ws->view_cams.p, n_view, ctx[g].fr, ctx[g].buf[0], ctx[g].srad, ctx[g].n_paths); });
             else timed(ctx[g], 0, [&] { fw::launch_raygen(ctx[g].cfg, cam, ctx[g].fr, ctx[g].buf[0], ctx[g].srad, ctx[g].n_paths); });
         }
         for (int seg = 0; seg < fw::MAX_SEGMENTS; seg++)
@@ -2302,7 +2366,8 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         constexpr uint64_t GRAPH_MAX_CHUNKS = 1u << 19;      // batches below 33 M paths
         // (a view group of fw_render_views never runs as a frame graph: one call already spreads a frame's launches over all its views,
         //  and the groups of one call share a key, so a capture would be replayed inside the same call.  A group leaves the cached graph as it is)
-        const bool graph_ok = O.graph != 0 && !rd && !vg && !fg.broken && !timing && !dump_one && !phase_lock && !stagger && (O.graph == 1 || chunks < GRAPH_MAX_CHUNKS);   // (a capture with PHASE_LOCK's events crashed inside the runtime: the two never meet by default — the lock wants batches of 100 M paths)
+        // (nor do the caller rays of fw_render_rays: their launches read the caller's memory, which a replay would not see change)
+        const bool graph_ok = O.graph != 0 && !rd && !vg && !ri && !fg.broken && !timing && !dump_one && !phase_lock && !stagger && (O.graph == 1 || chunks < GRAPH_MAX_CHUNKS);   // (a capture with PHASE_LOCK's events crashed inside the runtime: the two never meet by default — the lock wants batches of 100 M paths)
         uint64_t key = 0;
         if (graph_ok) {
             uint64_t h = 1469598103934665603ull;
@@ -2374,7 +2439,8 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     const size_t off_c = 0, off_8 = (n_counts * 4 + 255) & ~(size_t)255;
     const size_t off_g = off_8 + ((!p->outputs_on_device && rgb8 ? (size_t)n_pix * 3 : 0) + 255 & ~(size_t)255);
     const size_t off_l = off_g + ((!p->outputs_on_device && gamma_rgb ? (size_t)n_pix * 12 : 0) + 255 & ~(size_t)255);
-    const size_t host_need = off_l + (!p->outputs_on_device && linear_rgb ? (size_t)n_pix * 12 : 0) + 256;
+    const size_t off_e = off_l + ((!p->outputs_on_device && linear_rgb ? (size_t)n_pix * 12 : 0) + 255 & ~(size_t)255);   // fw_render_rays' error word
+    const size_t host_need = off_e + 256;
     if (ws->host_out_bytes < host_need) {
         if (ws->host_out) (void)hipHostFree(ws->host_out);
         ws->host_out = nullptr; ws->host_out_bytes = 0;
@@ -2390,6 +2456,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         if (gamma_rgb) HIPCHK(hipMemcpyAsync(ho + off_g, d_gamma, (size_t)n_pix * 12, hipMemcpyDeviceToHost, stream));
         if (linear_rgb) HIPCHK(hipMemcpyAsync(ho + off_l, d_linear, (size_t)n_pix * 12, hipMemcpyDeviceToHost, stream));
     }
+    if (ri) HIPCHK(hipMemcpyAsync(ho + off_e, ws->ray_err.p, 4, hipMemcpyDeviceToHost, stream));
     const double t_outs = since(tq0);
     if (!ws->ev_d2h) HIPCHK(hipEventCreate(&ws->ev_d2h));
     HIPCHK(hipEventRecord(ws->ev_d2h, stream));
@@ -2404,6 +2471,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         return fail(FW_ERR_HIP, std::string("device error word: ") + ((ew & 1u) ? "LDS traversal stack overflow (a push beyond the levels the launch reserved) " : "") +
                                     ((ew & 2u) ? "a walk kernel's wave made no progress for 2^24 rounds (left its loop) " : ""));
 #endif
+    if (ri && *(const uint32_t *)(ho + off_e)) return fail(FW_ERR_BAD_ARG, "a ray has a non-finite component or an all-zero direction");
     if (trace) fprintf(stderr, "[firework] render: enqueue %.2f ms | counters copy queued +%.2f | output copies queued +%.2f | sync + host memcpy returned +%.2f\n",
                        std::chrono::duration<double, std::milli>(tq0 - wall0).count(), t_counts, t_outs, since(tq0));
     const auto wall1 = std::chrono::steady_clock::now();
@@ -2423,7 +2491,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
             const uint64_t S = stats->samples, ray0 = fr.pinhole0 ? fw::B_RAY_PINHOLE0 : fw::B_RAY, b_hit = fr.hit4 ? fw::B_HIT4 : fw::B_HIT;
             uint64_t rd_ray = R[0] * ray0, later = 0, survivors = 0;
             for (int s = 1; s < fw::MAX_SEGMENTS; s++) { rd_ray += R[s] * fw::B_RAY; later += R[s]; survivors += R[s]; }
-            stats->bytes_raygen = S * ray0 + (fr.pixel_ids ? S * 4 : 0);
+            stats->bytes_raygen = S * ray0 + (fr.pixel_ids ? S * 4 : 0) + (ri ? S * 24 : 0);     // (caller rays: read, then written)
             const uint64_t medium = sc->d.has_medium ? later * 4 : 0;       // the path's home slot (RNG key of the medium's draw)
             const uint64_t b_state = fr.chain_bits ? fw::B_STATE_CHAIN : fw::B_STATE;
             // (EXACT_PRODUCT: one attenuation record written per survivor; a depositing path reads back its own — at most its length: not counted)
@@ -2635,6 +2703,28 @@ int views_impl(fw_scene *sc, const fw_render_params *p, const fw_camera_settings
         stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     }
     return FW_OK;
+}
+
+// fw_render_rays: render_impl over a frame of n_rays entries whose paths start from the caller's rays (RayInput; include/firework_hip.h has
+// the contract).  The frame is n_rays x 1 pixels without a camera; batches, lanes, queues, walks, k_shade, the accumulation in sample
+// order and the resolve are the render's own.
+int rays_impl(fw_scene *sc, const fw_render_rays_params *rp, const float *rays, float *accum, uint8_t *rgb8, float *gamma_rgb,
+              float *linear_rgb, fw_stats *stats) {
+    // (arguments first, in a fixed order: nothing below dereferences the scene or calls HIP before they are all valid)
+    if (!sc || !rp || !rays) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (rp->n_rays == 0) return fail(FW_ERR_BAD_ARG, "n_rays must be > 0");
+    if (rp->samples == 0 || rp->samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^24");
+    if ((uint64_t)rp->first_sample + rp->samples > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_sample + samples overflows");
+    if (!std::isfinite(rp->gamma) || !(rp->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
+    if (!accum && rp->first_sample > 0) return fail(FW_ERR_BAD_ARG, "first_sample > 0 needs the accumulation buffer of the samples before it");
+    if (rp->on_device && (((uintptr_t)accum & 15u) || ((uintptr_t)rays & 3u))) return fail(FW_ERR_BAD_ARG, "device accum must be 16-byte aligned, device rays 4-byte aligned");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    fw_render_params P{};
+    P.width = rp->n_rays; P.height = 1; P.samples = rp->samples; P.gamma = rp->gamma; P.use_bvh = rp->use_bvh; P.seed = rp->seed;
+    P.rng_mode = FW_RNG_CTR; P.paths_per_batch = rp->paths_per_batch; P.flags = rp->flags; P.outputs_on_device = rp->on_device; P.stream = rp->stream;
+    const RayInput ri{rays, rp->n_rays, rp->per_sample_rays != 0, rp->keys, rp->key_base, rp->on_device != 0};
+    return render_impl(sc, &P, rgb8, gamma_rgb, linear_rgb, stats, rp->first_sample, accum, nullptr, nullptr, &ri);
 }
 
 // Device memory of a ray query (trace_impl, camera_rays_impl): the front of the path arena, grown like render_impl grows it.  A render
@@ -3442,6 +3532,13 @@ int fw_render_views(fw_scene *scene, const fw_render_params *params, const fw_ca
     try { return views_impl(scene, params, cameras, n_views, rgb8, gamma_rgb, linear_rgb, stats); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_render_views"); }
+}
+
+int fw_render_rays(fw_scene *scene, const fw_render_rays_params *p, const float *rays, float *accum,
+                   uint8_t *rgb8, float *gamma_rgb, float *linear_rgb, fw_stats *stats) {
+    try { return rays_impl(scene, p, rays, accum, rgb8, gamma_rgb, linear_rgb, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_render_rays"); }
 }
 
 int fw_render_scene(const fw_scene_desc *desc, const fw_render_params *params, int device, uint8_t *rgb8, float *gamma_rgb,

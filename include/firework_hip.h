@@ -351,6 +351,53 @@ int fw_render_adaptive(fw_scene *scene, const fw_render_params *params, float to
 int fw_render_views(fw_scene *scene, const fw_render_params *params, const fw_camera_settings *cameras, uint32_t n_views,
                     uint8_t *rgb8, float *gamma_rgb, float *linear_rgb, fw_stats *stats);
 
+/* Radiance along caller-supplied rays (additive at ABI 8): panoramas and light probes, orthographic or fisheye views, irradiance probes,
+   a sensor model of the caller's own.  Entry i (one output pixel) of absolute sample s runs render.rs:10-33 `color(ray, ...)` from its
+   ray, with every draw keyed (seed, keys[i] or key_base + i, s, segment) exactly as a render keys pixel keys[i]; duplicate keys are
+   allowed and give correlated draws, nothing else.  The call renders the absolute samples [first_sample, first_sample + samples).
+     per_sample_rays = 1: rays holds samples x n_rays x 6 floats (origin, direction), sample-major: rays[s] is absolute sample
+                          first_sample + s;  0: rays holds n_rays x 6 floats, the same ray for every sample (probes).
+     accum : n_rays x 4 floats, fw_render_progressive's layout (r, g, b sums, then path segments), the sums of the samples
+             [0, first_sample) — all zeros when first_sample is 0 — to which this call's samples are added in sample order; NULL
+             only when first_sample == 0 (the sums then start from zero and are not returned).  k calls of n samples leave accum and
+             the outputs of one call of k*n samples, bit for bit.
+     outputs: accum / (first_sample + samples) resolved as fw_render resolves a pixel, in ray order, n_rays x 3 each; any may be NULL.
+   With on_device, rays, keys, accum and the outputs are device pointers on the scene's device (the fast path: the rays are read by the
+   ray-generation kernel where they lie); otherwise host memory, and the rays of each batch pass through pinned staging.
+   The identity (the contract): for any fw_render_params P (any camera, aperture included, any seed, a pixel subset or the whole frame),
+   with rays[s] = fw_camera_rays(P, device, first_sample + s), keys = P.pixel_ids (or NULL with key_base = 0 for a whole frame) and P's
+   seed, use_bvh and gamma, accum, rgb8, gamma_rgb and linear_rgb equal fw_render_progressive(P, first_sample, accum)'s bit for bit,
+   and for first_sample = 0 fw_render(P)'s (whole frames in row-major order); stats.rays and rays_per_depth equal theirs.  This holds
+   under every kernel-selecting option.
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, params or rays,
+   n_rays == 0, samples outside 1..2^24, first_sample + samples >= 2^32, a gamma that is not finite or <= 0, a NULL accum with
+   first_sample > 0, with on_device an accum that is not 16-byte aligned; then FW_ERR_NO_DEVICE without a GPU.  A ray with a non-finite
+   component or an all-zero direction makes the call return FW_ERR_BAD_ARG after it has run: accum and the outputs are then unspecified,
+   nothing faults and later calls are unaffected.
+   stats as fw_render's for n_rays pixels (bytes_raygen counts the 24 bytes per sample read from rays).  The call never runs as a frame
+   graph (option GRAPH; reserved bit 31 stays clear); if it grows the path workspace, the cached graph's key is cleared, as fw_trace_rays
+   does, and fw_render's cached graph is otherwise left as it is.  Synchronisation is fw_render's with outputs_on_device: the launches go
+   to `stream` after the scene's upload, and the call returns after that stream has drained. */
+typedef struct fw_render_rays_params {
+    uint32_t n_rays;            /* entries (output pixels) */
+    uint32_t first_sample;      /* this call renders absolute samples [first_sample, first_sample + samples) */
+    uint32_t samples;           /* 1 .. 2^24 */
+    int32_t  per_sample_rays;   /* 1: rays = samples x n_rays x 6 floats, sample-major (rays[s] is absolute sample first_sample + s)
+                                   0: rays = n_rays x 6 floats, the same ray for every sample (probes) */
+    const uint32_t *keys;       /* n_rays RNG pixel keys (the `pixel` word of every draw), or NULL: key_base + i */
+    uint32_t key_base;
+    uint64_t seed;
+    int32_t  use_bvh;
+    float    gamma;
+    uint32_t paths_per_batch;   /* 0 = library default */
+    uint32_t flags;             /* FW_FLAG_TIME_KERNELS, FW_FLAG_COUNT_DEPOSITS */
+    int32_t  on_device;         /* rays, keys, accum and the outputs are device pointers on the scene's device */
+    void    *stream;
+} fw_render_rays_params;
+
+int fw_render_rays(fw_scene *scene, const fw_render_rays_params *p, const float *rays, float *accum,
+                   uint8_t *rgb8, float *gamma_rgb, float *linear_rgb, fw_stats *stats);
+
 /* One-shot form with the reference's exact shape: `Renderer::render(&self, scene: Scene)`
    (render.rs:109): scene conversion + BVH build + render inside one call. */
 int fw_render_scene(const fw_scene_desc *desc, const fw_render_params *params, int device,
