@@ -70,6 +70,8 @@ def load(preload=False, device=None):
     lib.fw_set_option.restype = C.c_int
     lib.fw_set_option.argtypes = [C.c_char_p, C.c_char_p]
     lib.fw_selftest_wide_bvh.restype = C.c_int
+    lib.fw_selftest_lights.restype = C.c_int
+    lib.fw_selftest_lights.argtypes = [C.POINTER(A.fw_scene_desc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.fw_selftest_wide_bvh.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.fw_selftest_bvh_build.restype = C.c_int
     lib.fw_selftest_bvh_build.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
@@ -155,6 +157,25 @@ def selftest_wide_bvh(boxes, fmt):
     stats = (C.c_uint32 * 4)()
     _check(lib, lib.fw_selftest_wide_bvh(b.ctypes.data, b.shape[0], int(fmt), C.byref(bad), stats))
     return int(bad.value), dict(nodes=int(stats[0]), leaves=int(stats[1]), free_slots=int(stats[2]), depth=int(stats[3]))
+
+
+def selftest_lights(scene_desc):
+    """fw_selftest_lights (CPU only): the sampled lights of a SceneDesc as FW_FLAG_LIGHT_SAMPLING sees them.  -> list of dicts
+    with obj, kind, corners ((4, 3) world corners of a rectangle) or centre + radius (a sphere), area, p_pick"""
+    lib = load()
+    n = C.c_uint32()
+    _check(lib, lib.fw_selftest_lights(scene_desc.ptr(), None, 0, C.byref(n)))
+    out = np.zeros((max(1, n.value), A.FW_LIGHT_RECORD_FLOATS), np.float32)
+    _check(lib, lib.fw_selftest_lights(scene_desc.ptr(), out.ctypes.data, n.value, C.byref(n)))
+    lights = []
+    for r in out[:n.value]:
+        d = dict(obj=int(r[0]), kind=int(r[1]), area=float(r[14]), p_pick=float(r[15]))
+        if d["kind"] == A.FW_SHAPE_SPHERE:
+            d["centre"], d["radius"] = r[2:5].astype(np.float64), float(r[5])
+        else:
+            d["corners"] = r[2:14].reshape(4, 3).astype(np.float64)
+        lights.append(d)
+    return lights
 
 
 def selftest_bvh_build(boxes, threads):

@@ -1037,6 +1037,14 @@ class Renderer:
             self.settings["flags"] & ~A.FW_FLAG_TIME_KERNELS)
         return self
 
+    def light_sampling(self, on=True):
+        """FW_FLAG_LIGHT_SAMPLING: next-event estimation with MIS at Lambertian and Isotropic vertices — the same image in
+        expectation with less noise per sample.  A scene without a sampled light (an EmissiveMat sphere or axis-aligned rectangle) renders
+        the default frame; fw_render_aovs ignores the flag."""
+        self.settings["flags"] = (self.settings["flags"] | A.FW_FLAG_LIGHT_SAMPLING) if on else (
+            self.settings["flags"] & ~A.FW_FLAG_LIGHT_SAMPLING)
+        return self
+
     def count_deposits(self, on=True):
         """FW_FLAG_COUNT_DEPOSITS: fw_stats.deposits / bytes_shade become exact where zero deposits are elided (one extra pass)."""
         self.settings["flags"] = (self.settings["flags"] | A.FW_FLAG_COUNT_DEPOSITS) if on else (

@@ -216,6 +216,30 @@ constexpr uint32_t MISS = 0xffffffffu;
 constexpr int MAX_SEGMENTS = 11;
 constexpr int COUNT_STRIDE = 16;  // u32 counters per batch: [0..10] queue sizes, [11] parked rays, [12] deposits written (FW_FLAG_COUNT_DEPOSITS)
 
+// ---- light sampling (FW_FLAG_LIGHT_SAMPLING) ----------------------------------------------------------------
+// The scene's sampled lights: objects whose material is EmissiveMat and whose shape is a sphere or an axis-aligned rectangle,
+// SoA (one array: the object index; every other property is read from the object record), picked uniformly (p_pick = 1/n).
+struct DLights {
+    const uint32_t *obj;
+    uint32_t n;
+    float p_pick;
+};
+// One batch's light-sampling buffers.  k_shade_ls appends one shadow ray per light-sampling vertex to the shadow queue (the path
+// queue's geometry: wave w owns [w*cap, (w+1)*cap)), the ordinary walks trace it, k_shadow_resolve adds the pending radiance of
+// the visible ones to nee[home].  pb: the BSDF's solid-angle density of each queued ray (0: the ray left no light-sampling
+// vertex), in the path queue's slots, in = this segment's queue, out = the next one's.
+struct DShadow {
+    DLights lt;
+    float4 *ray_a; float2 *ray_b;
+    float4 *state;        // (pending rgb, bits home slot): the walks read .w for a medium's key
+    uint32_t *obj;        // the sampled light's object
+    uint32_t *wcount;     // shadow rays of wave w made at segment s: wcount[(s + 1) * n_waves + w]
+    const float *pb_in;
+    float *pb_out;
+    float4 *nee;          // per home slot: the visible light-sampling contributions so far (zeroed per batch)
+};
+constexpr uint32_t SHADOW_SEED = 0x6e1a7c35u;   // the shadow walks' DFrame.seed32 = seed32 ^ SHADOW_SEED: their ConstantMedium draws (§9g)
+
 // launch wrappers (fw_kernels.hip)
 struct LaunchCfg {
     hipStream_t stream;
@@ -259,6 +283,11 @@ void launch_extend(const LaunchCfg &, const DScene &, const DFrame &, DPaths in,
 void launch_extend_exact(const LaunchCfg &, const DScene &, const DFrame &, const DPaths &in, float2 *hits, int segment, bool use_bvh);
 void launch_shade(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
                   float4 *sample_rad, int segment);
+// light sampling: k_shade's light-sampling instantiation (k_shade_ls; the frame has no chain state, no hit4, no EXACT_PRODUCT and
+// deposits every path) and the resolve of one segment's shadow rays after their walk
+void launch_shade_ls(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
+                     float4 *sample_rad, int segment, const DShadow &);
+void launch_shadow_resolve(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment);
 void launch_bounce(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, float4 *sample_rad, int segment,
                    bool use_bvh);
 void launch_queue_totals(const LaunchCfg &, uint32_t *totals, const uint32_t *ptotal);

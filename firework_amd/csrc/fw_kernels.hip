@@ -154,7 +154,7 @@ struct Phase {
 // ------------------------------------------------------------------------------------------------
 // counter RNG: pcg4d(pixel, sample, dimension, seed32) -> 4 x u32; float = (u >> 8) * 2^-24
 // ------------------------------------------------------------------------------------------------
-enum : uint32_t { P_JITTER = 0, P_LENS = 1, P_SCATTER = 2, P_FRESNEL = 3, P_VOLUME = 4 };
+enum : uint32_t { P_JITTER = 0, P_LENS = 1, P_SCATTER = 2, P_FRESNEL = 3, P_VOLUME = 4, P_LIGHT = 5 };   // 5: light sampling
 
 struct RngKey { uint32_t pixel, sample, seed32; };
 
@@ -3079,6 +3079,94 @@ __device__ __forceinline__ HitInfo rebuild_hit(const DScene &sc, const Obj &o, c
 }
 
 // ------------------------------------------------------------------------------------------------
+// Light sampling (FW_FLAG_LIGHT_SAMPLING): next-event estimation at Lambertian and Isotropic vertices, combined with the
+// BSDF's own sampling by the power heuristic.  A sampled light is a sphere or an axis-aligned rectangle with an EmissiveMat; it is
+// sampled in the frame the walks intersect it in (rotated only under OF_ROTATED), and its emission is evaluated as a hit there would be.
+// ------------------------------------------------------------------------------------------------
+// Solid-angle density of the direction of n + u, u uniform in the unit ball (material.rs:66 with n the reported normal, material.rs:201
+// with n = 0).  The direction w (unit) meets the ball around n along t w for t in [t-, t+], t+- = c +- sqrt(c^2 - |n|^2 + 1), c = n.w;
+// the density is the ball's volume along that cone, (t+^3 - max(t-, 0)^3) / 3 over 4 pi / 3: 2 cos^3 / pi for |n| = 1, 1 / 4 pi for n = 0.
+__device__ __forceinline__ float scatter_pdf(V3 n, V3 w) {
+    const float c = dot(n, w), disc = c * c - dot(n, n) + 1.f;
+    if (!(disc >= 0.f)) return 0.f;
+    const float s = fsqrt(disc), tp = c + s, tm = fmaxf(c - s, 0.f);
+    if (!(tp > 0.f)) return 0.f;
+    return (tp * tp * tp - tm * tm * tm) * (1.f / (4.f * PI_F));
+}
+__device__ __forceinline__ V3 obj_pos(const Obj &o) { return mk(o.q0.w, o.q1.w, o.q2.w); }
+__device__ __forceinline__ V3 rect_axis(uint32_t kind) { return mk(kind == 3u ? 1.f : 0.f, kind == 2u ? 1.f : 0.f, kind == 1u ? 1.f : 0.f); }   // plane normal of XY / XZ / YZ
+__device__ __forceinline__ float rect_area(const Obj &o) { return fabsf((o.q3.y - o.q3.x) * (o.q3.w - o.q3.z)); }
+// 1 - cos(theta_max) of the cone a sphere subtends from x, or 0 where x lies inside or on it
+__device__ __forceinline__ float sphere_cone(const Obj &o, V3 x, V3 &v, float &d2) {
+    v = obj_pos(o) - x; d2 = dot(v, v);
+    const float r2 = o.q3.x * o.q3.x;
+    if (!(d2 > r2)) return 0.f;
+    const float s2 = fdiv(r2, d2), cmax = fsqrt(1.f - s2);
+    return fdiv(s2, 1.f + cmax);
+}
+// p_omega of a light for a ray from org along d that meets it at t (the BSDF side of the weight)
+__device__ __forceinline__ float light_pdf_hit(const Obj &o, V3 org, V3 d, float t) {
+    const uint32_t kind = obj_kind(o);
+    if (kind == 0u) {
+        V3 v; float d2;
+        const float omc = sphere_cone(o, org, v, d2);
+        return omc > 0.f ? fdiv(1.f, 2.f * PI_F * omc) : 0.f;
+    }
+    V3 n = rect_axis(kind);
+    if (obj_flags(o) & OF_ROTATED) n = rot_fwd(o, n);
+    const float dn = fabsf(dot(n, d)), dl = mag(d);
+    if (!(dn > 0.f)) return 0.f;
+    return fdiv(t * t * dl * dl * dl, dn * rect_area(o));
+}
+// A point of light o seen from x (u1, u2 uniform): the shadow ray's direction (its end: t = 1), p_omega and the object-space point
+// (for the emission).  p_omega = 0: nothing to sample (x inside the sphere, or in the rectangle's plane).
+__device__ __forceinline__ float light_sample(const Obj &o, V3 x, float u1, float u2, V3 &d, V3 &p_obj) {
+    const uint32_t kind = obj_kind(o);
+    const bool rotated = (obj_flags(o) & OF_ROTATED) != 0u;
+    if (kind == 0u) {                                   // uniform in the cone the sphere subtends, the near intersection
+        V3 v; float d2;
+        const float omc = sphere_cone(o, x, v, d2);
+        if (!(omc > 0.f)) return 0.f;
+        const float dist = fsqrt(d2);
+        const V3 w = v / dist;
+        const float om = u1 * omc, cos_t = 1.f - om, sin_t = fsqrt(fmaxf(om * (2.f - om), 0.f));
+        float sp, cp; sincosf(2.f * PI_F * u2, &sp, &cp);
+        const float sg = w.z >= 0.f ? 1.f : -1.f, a = fdiv(-1.f, sg + w.z), b = w.x * w.y * a;      // orthonormal basis around w
+        const V3 e1 = mk(1.f + sg * w.x * w.x * a, sg * b, -sg * w.x), e2 = mk(b, sg + w.y * w.y * a, -w.y);
+        const V3 dir = (sin_t * cp) * e1 + (sin_t * sp) * e2 + cos_t * w;
+        const float bb = dot(dir, v), disc = bb * bb - (d2 - o.q3.x * o.q3.x);
+        const float t = bb - fsqrt(fmaxf(disc, 0.f));
+        d = t * dir;
+        const V3 rel = x + d - obj_pos(o);
+        p_obj = rotated ? rot_inv(o, rel) : rel;
+        return fdiv(1.f, 2.f * PI_F * omc);
+    }
+    const float a = o.q3.x + u1 * (o.q3.y - o.q3.x), b = o.q3.z + u2 * (o.q3.w - o.q3.z), k = o.q4.x;
+    p_obj = kind == 1u ? mk(a, b, k) : (kind == 2u ? mk(a, k, b) : mk(k, a, b));        // rect.rs: XY (x, y) at z, XZ (x, z) at y, YZ (y, z) at x
+    const V3 n = rotated ? rot_fwd(o, rect_axis(kind)) : rect_axis(kind);
+    d = (rotated ? rot_fwd(o, p_obj) : p_obj) + obj_pos(o) - x;
+    const float dn = fabsf(dot(n, d)), dl2 = dot(d, d);
+    if (!(dn > 0.f)) return 0.f;
+    return fdiv(dl2 * fsqrt(dl2), dn * rect_area(o));
+}
+// What a hit at p_obj of light o would emit (rebuild_hit's uv and point, then the EmissiveMat's texture)
+template <bool CHEAP_ONLY>
+__device__ __forceinline__ V3 light_emit(const DScene &sc, const float4 *matp, const float4 *texp, const Obj &o, V3 p_obj) {
+    const float4 m0 = matp[2 * o.material], m1 = matp[2 * o.material + 1];
+    const uint32_t mbits = __float_as_uint(m0.x);
+    if (CHEAP_ONLY || (mbits & MF_TEX_CONST)) return mk(m1.x, m1.y, m1.z);
+    const uint32_t kind = obj_kind(o);
+    float u = 0.f, v = 0.f;
+    if (mbits & MF_NEEDS_UV) {
+        if (kind == 0u) sphere_uv(p_obj / o.q3.x, u, v);
+        else { V3 n; rect_hitinfo(kind, o.q3.x, o.q3.y, o.q3.z, o.q3.w, false, p_obj, n, u, v, true); }
+    }
+    return texture_sample(texp, sc.images, __float_as_uint(m0.y), u, v, rot_fwd(o, p_obj) + obj_pos(o));
+}
+// k_shade_ls's per-path exchange with shade_path: the p_b of the ray being shaded (in) and of the ray it scatters (out), the shadow ray
+struct LsIO { float pb_in, pb_out; bool shadow; Ray sray; uint32_t sobj; V3 pending; };
+
+// ------------------------------------------------------------------------------------------------
 // K5 + K7  shade + stream compaction
 //
 // k_shade is latency-bound (rocprofv3: 79 % of wave cycles in s_waitcnt in the first version): the chain
@@ -3100,11 +3188,14 @@ __device__ __forceinline__ bool expensive_shading(const DScene &sc, const float4
 }
 // CHEAP_ONLY: the caller has sent the expensive cases elsewhere (expensive_shading), their code is compiled out.
 // CHAIN: the path's state is its chain of material ids (load_state_chain), `chain` in and `nchain` out; beta / nbeta are unused.
-template <bool CHEAP_ONLY = false, bool CHAIN = false>
+// LS: k_shade_ls: the MIS weight of emission reached from a light-sampling vertex, the light sample of a Lambertian or
+// Isotropic vertex (*ls: the shadow ray, left to k_shadow_resolve), and the path's visible light samples (sh->nee) in its deposit.
+template <bool CHEAP_ONLY = false, bool CHAIN = false, bool LS = false>
 __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, const float4 *objp, const float4 *matp,
                                            const float4 *texp, const Ray &r, V3 beta, uint32_t chain, uint32_t path_id, float t_hit,
                                            uint32_t hit_code, int segment, float4 *__restrict__ sample_rad, Ray &nr, V3 &nbeta, uint32_t &nchain PH_ARG,
-                                           const RngKey *pre_key = nullptr) {      // pre_key: the path's RNG key, when the caller has fetched it already (k_shade, FW_SHADE_PIPE)
+                                           const RngKey *pre_key = nullptr,       // pre_key: the path's RNG key, when the caller has fetched it already (k_shade, FW_SHADE_PIPE)
+                                           const DShadow *sh = nullptr, LsIO *ls = nullptr) {
     bool alive = false;
     const uint32_t obj_index = hit_code == MISS ? MISS : (hit_code >> sc.prim_bits);
     V3 rad = mk(0.f, 0.f, 0.f);
@@ -3154,6 +3245,10 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
         if (!CHEAP_ONLY && !CHAIN && !tex_const && (mkind == 0 || mkind == 3 || mkind == 4)) { PH_T0; texc = texture_sample(texp, sc.images, mtex, h.u, h.v, h.point); PH_ADD(3); }
         if (mkind == 3) {                                                      // EmissiveMat: emit, never scatters
             PH_T0;
+            if (LS && ls->pb_in > 0.f && obj_kind(o) <= 3u) {                  // a sampled light, reached from a light-sampling vertex: p_b^2 / (p_b^2 + p_l^2)
+                const float s_ = fdiv(sh->lt.p_pick * light_pdf_hit(o, r.o, r.d, t_hit), ls->pb_in);
+                texc = fdiv(1.f, 1.f + s_ * s_) * texc;
+            }
             rad = carried(texc);
             PH_ADD(4);
         } else if (segment < 10) {                                             // render.rs:21
@@ -3190,6 +3285,22 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
                 alive = true; break; }
             default: break;
             }
+            if (LS && (mkind == 0 || mkind == 4)) {                            // next-event estimation
+                const V3 n_b = mkind == 0 ? h.normal : mk(0.f, 0.f, 0.f);      // (Isotropic: n + u with n = 0)
+                ls->pb_out = scatter_pdf(n_b, normalized(nr.d));
+                const uint4 lu = draw(key, P_LIGHT, segment, 0);
+                const uint32_t li = min((uint32_t)(u2f(lu.x) * (float)sh->lt.n), sh->lt.n - 1u);
+                const uint32_t lobj = sh->lt.obj[li];
+                const Obj lo = load_obj(objp, lobj);
+                V3 d, p_obj;
+                const float pl = sh->lt.p_pick * light_sample(lo, h.point, u2f(lu.y), u2f(lu.z), d, p_obj);
+                const float pb = pl > 0.f ? scatter_pdf(n_b, normalized(d)) : 0.f;
+                if (pb > 0.f) {
+                    const float r_ = fdiv(pb, pl);                             // f cos / p_l * p_l^2 / (p_l^2 + p_b^2) = albedo * r / (1 + r^2)
+                    const V3 c = (beta * atten) * light_emit<CHEAP_ONLY>(sc, matp, texp, lo, p_obj) * fdiv(r_, 1.f + r_ * r_);
+                    if (c.x > 0.f || c.y > 0.f || c.z > 0.f) { ls->shadow = true; ls->sray = Ray{h.point, d}; ls->sobj = lobj; ls->pending = c; }
+                }
+            }
             if (CHAIN) nchain = chain | (o.material << (f.chain_bits * (uint32_t)segment));   // atten IS the material's constant (host: chain_bits)
             else {
                 nbeta = beta * atten;
@@ -3210,6 +3321,7 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
         // whenever every path deposits (any non-black environment, or FIREWORK_NO_ZERO_SKIP=1) — what tools/diverge.py
         // compares with the oracle's per-pixel counts to find a diverging path
         const float len = (float)(segment + 1);
+        if (LS) { const float4 e = sh->nee[path_id]; rad = rad + mk(e.x, e.y, e.z); }
         if (FW_NT_RAD) st_nt(&sample_rad[path_id], make_float4(rad.x, rad.y, rad.z, len));
         else sample_rad[path_id] = make_float4(rad.x, rad.y, rad.z, len);
         if (f.skip_zero_deposits) {                                  // "this path wrote a record" (3.6 % of cornell's paths)
@@ -3402,6 +3514,93 @@ __global__ __launch_bounds__(WB) void k_shade(DScene sc, DFrame f, DPaths in, DP
     if (MODE == 2) while (list_n) run_list(min(list_n, 64u));
     if (lane == 0) q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n;
     PH_FLUSH(1);
+}
+// Light sampling: k_shade with the light sample of every Lambertian / Isotropic vertex appended to the shadow queue, the
+// BSDF's p_b carried with each ray (sh.pb_in / pb_out) and the MIS weight on the emission it reaches.  k_shade's table modes and its
+// modes 0 and 1 (in line; MODE 1: nothing expensive in the scene), without the chain state: a light-sampling frame carries the running
+// product.  A kernel of its own, so that k_shade's instantiations stay as they are.
+template <int LDS_TAB, int MODE>
+__attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
+__global__ __launch_bounds__(WB) void k_shade_ls(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
+                                                    float4 *__restrict__ sample_rad, DQueue q, int segment,
+                                                    uint32_t n_mat, uint32_t n_tex, DShadow sh) {
+    static_assert(MODE == 0 || MODE == 1, "in line only");
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    const float4 *objp = sc.obj, *matp = sc.mat, *texp = sc.tex;
+    if (sc.has_perlin && MODE != 1) { stage_perm(); if (!LDS_TAB) __syncthreads(); }
+    if (LDS_TAB) {
+        const uint32_t no = LDS_TAB == 1 ? sc.n_objects * OBJ_Q : 0u, nm = 2 * n_mat, nt = 2 * n_tex;
+        if (LDS_TAB == 1) for (uint32_t k = threadIdx.x; k < no; k += WB) lds_tables[k] = sc.obj[k];
+        for (uint32_t k = threadIdx.x; k < nm; k += WB) lds_tables[no + k] = sc.mat[k];
+        for (uint32_t k = threadIdx.x; k < nt; k += WB) lds_tables[no + nm + k] = sc.tex[k];
+        __syncthreads();
+        if (LDS_TAB == 1) objp = lds_tables;
+        matp = lds_tables + no; texp = lds_tables + no + nm;
+    }
+    if (w >= q.n_waves) return;
+    const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
+    const uint32_t base = w * q.cap;
+    uint32_t out_n = 0, sh_n = 0;                                        // survivors / shadow rays written so far (wave-uniform)
+    PH_DECL;
+    float4 ra_n = make_float4(0, 0, 0, 0), st_n = ra_n; float2 rb_n = make_float2(0, 0), hr_n = rb_n; float pb_n = 0.f;
+    auto fetch = [&](uint32_t i) {
+        ra_n = qld(&in.ray_a[i]); rb_n = load_ray_b(in, i, f, segment); st_n = load_state(in, i, segment); hr_n = qld(&hits[i]);
+        pb_n = segment > 0 ? sh.pb_in[i] : 0.f;
+    };
+    if (lane < n) fetch(base + lane);
+    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
+        const uint32_t j = c0 + lane, i = base + j;
+        float4 ra = ra_n, st = st_n; float2 rb = rb_n, hr = hr_n;
+        LsIO ls{pb_n, 0.f, false, Ray{mk(0, 0, 0), mk(0, 0, 0)}, 0u, mk(0, 0, 0)};
+        if (j + 64u < n) fetch(i + 64u);
+        bool alive = false;
+        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
+        if (j < n) {
+            path_id = __float_as_uint(st.w);
+            alive = shade_path<MODE != 0, false, true>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id, hr.x,
+                                                       __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS, nullptr, &sh, &ls);
+        }
+        // k_shade's compaction, with p_b next to the state
+        const unsigned long long mask = __ballot(alive);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (alive) {
+            const uint32_t dst = base + out_n + rank;
+            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
+            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
+            qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
+            sh.pb_out[dst] = ls.pb_out;
+        }
+        if (f.ex.mode) flag_exact(f.ex, alive && needs_exact(f.ex, nr.o.x, nr.o.y, nr.o.z, nr.d.x, nr.d.y, nr.d.z), base + out_n + rank, segment + 1);
+        out_n += (uint32_t)__popcll(mask);
+        // the shadow rays: the same compaction, into the wave's region of the shadow queue
+        const unsigned long long sm = __ballot(ls.shadow);
+        if (sm) {
+            const uint32_t sr = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+            if (ls.shadow) {
+                const uint32_t d = base + sh_n + sr;
+                sh.ray_a[d] = make_float4(ls.sray.o.x, ls.sray.o.y, ls.sray.o.z, ls.sray.d.x);
+                sh.ray_b[d] = make_float2(ls.sray.d.y, ls.sray.d.z);
+                sh.state[d] = make_float4(ls.pending.x, ls.pending.y, ls.pending.z, __uint_as_float(path_id));
+                sh.obj[d] = ls.sobj;
+            }
+            sh_n += (uint32_t)__popcll(sm);
+        }
+    }
+    if (lane == 0) { q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n; sh.wcount[(size_t)(segment + 1) * q.n_waves + w] = sh_n; }
+}
+// One segment's shadow rays after their walk: a ray whose closest hit is the light it sampled adds its pending radiance to the path's
+// nee record.  One shadow ray per path and segment, segments in stream order: no atomics.
+__global__ __launch_bounds__(WB) void k_shadow_resolve(DShadow sh, const float2 *__restrict__ hits, DQueue q, int segment, uint32_t prim_bits) {
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    if (w >= q.n_waves) return;
+    const uint32_t n = sh.wcount[(size_t)(segment + 1) * q.n_waves + w], base = w * q.cap;
+    for (uint32_t j = lane; j < n; j += 64u) {
+        const uint32_t i = base + j, code = __float_as_uint(hits[i].y);
+        if (code == MISS || (code >> prim_bits) != sh.obj[i]) continue;
+        const float4 p = sh.state[i];
+        float4 &e = sh.nee[__float_as_uint(p.w)];
+        e = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, 0.f);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4112,6 +4311,22 @@ void launch_shade(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths 
 #undef FW_SHADE_L
 #undef FW_SHADE_C
 #undef FW_SHADE
+}
+void launch_shade_ls(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
+                     float4 *sample_rad, int segment, const DShadow &sh) {
+    // (launch_shade's table modes; the shading mode is 0 or 1: a light-sampling frame never takes the list)
+    const size_t tab = ((size_t)sc.n_objects * OBJ_Q + 2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
+    const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
+    const int lt = (c.lds_tables && tab <= LDS_TABLE_LIMIT) ? 1 : ((c.lds_tables && tab_mt <= LDS_TABLE_LIMIT) ? 2 : 0);
+    const size_t lds = lt == 1 ? tab : (lt == 2 ? tab_mt : 0);
+#define FW_SHADE_LS(L, M) hipLaunchKernelGGL((k_shade_ls<L, M>), wave_grid(c), dim3(WB), lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, sh)
+#define FW_SHADE_LS_M(L) do { if (c.shade_mode == 1) FW_SHADE_LS(L, 1); else FW_SHADE_LS(L, 0); } while (0)
+    if (lt == 1) FW_SHADE_LS_M(1); else if (lt == 2) FW_SHADE_LS_M(2); else FW_SHADE_LS_M(0);
+#undef FW_SHADE_LS_M
+#undef FW_SHADE_LS
+}
+void launch_shadow_resolve(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment) {
+    hipLaunchKernelGGL(k_shadow_resolve, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
 }
 #if FW_AB
 void launch_bounce(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, float4 *sample_rad,

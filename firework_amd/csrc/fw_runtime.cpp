@@ -773,7 +773,9 @@ struct Workspace {
     // volume frame after suzanne).  The arena only grows, in steps of 1 GiB.
     struct Lane { void *ray_a[2] = {nullptr, nullptr}, *ray_b[2] = {nullptr, nullptr}, *state[2] = {nullptr, nullptr}, *hits = nullptr, *sample_rad = nullptr,
                        *wcount = nullptr, *park_a = nullptr, *park_b = nullptr, *park_m = nullptr, *pcount = nullptr, *dep_bits = nullptr, *exact_slots = nullptr, *atten = nullptr,
-                       *rays = nullptr;   // fw_render_rays with host rays: the batch's rays, copied in through ray_host
+                       *rays = nullptr,   // fw_render_rays with host rays: the batch's rays, copied in through ray_host
+                       // light sampling (fw::DShadow): the shadow queue (ray, pending + home, light object, hit record, counts), p_b of the two path queues, nee
+                       *s_ray_a = nullptr, *s_ray_b = nullptr, *s_state = nullptr, *s_obj = nullptr, *s_hits = nullptr, *s_wcount = nullptr, *pb[2] = {nullptr, nullptr}, *nee = nullptr;
                   hipStream_t stream = nullptr;
                   std::vector<hipEvent_t> events; };
     DevBuf arena;
@@ -962,9 +964,13 @@ struct fw_scene {
     DevBuf obj_data;              // the object-level sections once an update has written them (data's own copies are then unused)
     size_t blob_bytes = 0;        // bytes of the creation's upload
     double ms_objects = 0, ms_objects_dev = 0;   // the last object-level build: host wall time, device tree builds (FIREWORK_TRACE)
+    DevBuf lights;                // the sampled lights' object indices (fw::DLights.obj; FW_FLAG_LIGHT_SAMPLING)
+    uint32_t n_lights = 0;
+    bool ls_vertices = false;     // some material is Lambertian or Isotropic: a vertex that samples lights can occur
     ~fw_scene() {
         data.release();
         obj_data.release();
+        lights.release();
     }
 };
 
@@ -1461,6 +1467,54 @@ void apply_object_level(fw_scene *sc, const ObjectLevel &L, const uint8_t *const
 }
 
 // reach: the frame_reach to build the meshes' walked trees with (nullptr: reach_in_frames of desc; fw_scene_update passes what a rebuild needs)
+// ---- light sampling -------------------------------------------------------------------------------------------------
+// The sampled lights of a description: every object whose material is EmissiveMat and whose shape is a sphere or an axis-aligned
+// rectangle, in object order, picked uniformly.  A record gives the geometry the walks intersect: a rectangle's four corners in the world,
+// rotated only where the object's rotation is not near the identity (cos_trace < 0.999, scene.rs:242-253: the reference intersects it
+// unrotated otherwise); a sphere's centre and radius.  fw_selftest_lights returns these records; the device keeps the object indices.
+struct LightRec { uint32_t obj, kind; float pts[12]; float area, p_pick; };
+static std::vector<LightRec> scene_lights(const fw_scene_desc *d) {
+    std::vector<LightRec> out;
+    for (uint32_t i = 0; i < d->n_objects; i++) {
+        const fw_object &o = d->objects[i];
+        if (o.shape < 0 || (uint32_t)o.shape >= d->n_shapes) continue;
+        const fw_shape &s = d->shapes[o.shape];
+        if (s.kind < FW_SHAPE_SPHERE || s.kind > FW_SHAPE_YZRECT) continue;
+        if (s.material < 0 || (uint32_t)s.material >= d->n_materials || d->materials[s.material].kind != FW_MAT_EMISSIVE) continue;
+        LightRec r{}; r.obj = i; r.kind = (uint32_t)s.kind;
+        const V3 pos = tov(o.position);
+        if (s.kind == FW_SHAPE_SPHERE) {
+            r.pts[0] = pos.x; r.pts[1] = pos.y; r.pts[2] = pos.z; r.pts[3] = s.radius;
+            r.area = 4.f * 3.14159265358979323846f * s.radius * s.radius;
+        } else {
+            float rows[3][3];
+            rotor_rows(o.rotation, rows);
+            const bool rotated = 0.5f * ((rows[0][0] + rows[1][1] + rows[2][2]) - 1.f) < 0.999f;     // fw::OF_ROTATED
+            const float a[4] = {s.a_min, s.a_max, s.a_max, s.a_min}, b[4] = {s.b_min, s.b_min, s.b_max, s.b_max};
+            for (int c = 0; c < 4; c++) {
+                const V3 p = s.kind == FW_SHAPE_XYRECT ? V3{a[c], b[c], s.k} : (s.kind == FW_SHAPE_XZRECT ? V3{a[c], s.k, b[c]} : V3{s.k, a[c], b[c]});
+                const V3 w = (rotated ? mat_mul(rows, p) : p) + pos;
+                r.pts[3 * c] = w.x; r.pts[3 * c + 1] = w.y; r.pts[3 * c + 2] = w.z;
+            }
+            r.area = std::fabs((s.a_max - s.a_min) * (s.b_max - s.b_min));
+        }
+        out.push_back(r);
+    }
+    for (LightRec &r : out) r.p_pick = 1.f / (float)out.size();
+    return out;
+}
+// the device's copy (object indices) and the scene's light-sampling facts; at creation and after every fw_scene_update
+static int upload_lights(fw_scene *sc, const fw_scene_desc *d) {
+    const std::vector<LightRec> L = scene_lights(d);
+    std::vector<uint32_t> objs(L.size());
+    for (size_t i = 0; i < L.size(); i++) objs[i] = L[i].obj;
+    if (int rc = sc->lights.upload(objs.data(), objs.size() * 4)) return rc;
+    sc->n_lights = (uint32_t)L.size();
+    sc->ls_vertices = false;
+    for (uint32_t m = 0; m < d->n_materials; m++) sc->ls_vertices = sc->ls_vertices || d->materials[m].kind == FW_MAT_LAMBERTIAN || d->materials[m].kind == FW_MAT_ISOTROPIC;
+    return FW_OK;
+}
+
 int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out, const std::vector<float> *reach = nullptr) {
     if (!desc || !out) return fail(FW_ERR_BAD_ARG, "null argument");
     *out = nullptr;
@@ -1734,6 +1788,7 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out, con
         k.sp = std::move(sps); k.ext = std::move(ext); k.reach = fl.frame_reach;
     }
     sc->blob_bytes = total; sc->ms_objects = ms_objects; sc->ms_objects_dev = L.dev_times.upload_ms + L.dev_times.kernel_ms + L.dev_times.copy_ms;
+    if (int rc = upload_lights(sc, desc)) { fw_scene_destroy(sc); return rc; }
     *out = sc;
     return FW_OK;
 }
@@ -1806,9 +1861,9 @@ int update_scene_impl(fw_scene *sc, const fw_scene_desc *desc) {
         const auto t0 = now();
         fw_scene *ns = nullptr;
         if (int rc = create_scene_impl(desc, sc->device, &ns, &reach)) return rc;
-        DevBuf old_data = sc->data, old_obj = sc->obj_data;
+        DevBuf old_data = sc->data, old_obj = sc->obj_data, old_lights = sc->lights;
         *sc = *ns;                                     // (the handle stays the caller's; its DevBufs now name the new allocations)
-        ns->data = old_data; ns->obj_data = old_obj;   // ... and the old ones go with `ns`
+        ns->data = old_data; ns->obj_data = old_obj; ns->lights = old_lights;   // ... and the old ones go with `ns`
         fw_scene_destroy(ns);
         if (O.trace) fprintf(stderr, "[firework] scene_update: %u objects, TLAS build %.2f ms host, %.2f ms device, %u meshes rebuilt, %zu B uploaded, %u hoisted (scene re-created: the reach of %u meshes rose; %.2f ms)\n",
                              desc->n_objects, sc->ms_objects, sc->ms_objects_dev, n_meshes, sc->blob_bytes, sc->d.n_hoisted, raised, ms_since(t0));
@@ -1847,6 +1902,7 @@ int update_scene_impl(fw_scene *sc, const fw_scene_desc *desc) {
     const uint8_t *dev[8];
     for (int s = 0; s < 8; s++) dev[s] = base + secs[s].off;
     apply_object_level(sc, L, dev);
+    if (int rc = upload_lights(sc, desc)) return rc;
     sc->ms_objects = ms_objects; sc->ms_objects_dev = L.dev_times.upload_ms + L.dev_times.kernel_ms + L.dev_times.copy_ms;
     if (O.trace) fprintf(stderr, "[firework] scene_update: %u objects, TLAS build %.2f ms host, %.2f ms device, %u meshes rebuilt, %zu B uploaded, %u hoisted\n",
                          desc->n_objects, sc->ms_objects, sc->ms_objects_dev, 0u, total, sc->d.n_hoisted);
@@ -1915,6 +1971,11 @@ void set_walk_cfg(fw::LaunchCfg &cfg, const fw_scene *sc, const Options &O, cons
     cfg.ref_tlas_nodes = sc->tlas_nodes; cfg.ref_blas_nodes = sc->blas_nodes; cfg.ref_tlas_depth = sc->ref_tlas_depth; cfg.ref_blas_depth = sc->ref_blas_depth;
 }
 
+// FW_FLAG_LIGHT_SAMPLING takes effect where the scene has a sampled light and a material whose vertices sample them;
+// otherwise the frame is the default frame
+static bool light_sampling(const fw_scene *sc, const fw_render_params *p) {
+    return (p->flags & FW_FLAG_LIGHT_SAMPLING) != 0 && sc->n_lights > 0 && sc->ls_vertices;
+}
 // render_impl's lanes (batches in flight) and paths per batch and lane for `p` (fw_render_views sizes its view groups by the same budget)
 struct BatchBudget { int n_lanes; bool exact_product; uint32_t budget; };
 BatchBudget batch_budget(const fw_scene *sc, const fw_render_params *p, const Options &O, size_t arena_bytes) {
@@ -1923,7 +1984,9 @@ BatchBudget batch_budget(const fw_scene *sc, const fw_render_params *p, const Op
     n_lanes = (int)std::min<uint32_t>((uint32_t)n_lanes, p->samples);
     // EXACT_PRODUCT: 160 more bytes per slot (ten attenuation records) where the scene has no chain state: half the default batch
     const bool exact_product = O.exact_product && (sc->chain_bits == 0 || O.no_chain);
-    const uint32_t budget = p->paths_per_batch ? p->paths_per_batch : default_paths_per_batch(O, arena_bytes) / (uint32_t)n_lanes / (exact_product ? 2u : 1u);
+    // light sampling: 92 more bytes per slot (fw::DShadow) — half the default batch as well
+    const bool ls = light_sampling(sc, p);
+    const uint32_t budget = p->paths_per_batch ? p->paths_per_batch : default_paths_per_batch(O, arena_bytes) / (uint32_t)n_lanes / (exact_product || ls ? 2u : 1u);
     return BatchBudget{n_lanes, exact_product, budget};
 }
 
@@ -1990,7 +2053,10 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // row on a box whose processes alternate between two k_shade modes: profiles/r05k_lanes2.txt).
     const BatchBudget bb = batch_budget(sc, p, O, ws->arena.bytes);
     int n_lanes = bb.n_lanes;
-    const bool exact_product = bb.exact_product;
+    // light sampling: a path deposits its visible light samples with its own end, so the frame keeps the running product (no
+    // chain state, no EXACT_PRODUCT records), deposits every path (no elided zeros) and keeps t in its hit records (no hit4)
+    const bool ls = light_sampling(sc, p);
+    const bool exact_product = bb.exact_product && !ls;
     const uint32_t budget = bb.budget;
     uint32_t spp_b = std::max<uint32_t>(1u, budget / n_pix);
     spp_b = std::min(spp_b, (p->samples + (uint32_t)n_lanes - 1) / (uint32_t)n_lanes);     // at least one batch per lane
@@ -2037,7 +2103,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // (the linear scan tests every object anyway: only a mesh's BLAS is walked there)
     // (FIREWORK_FUSED=1, the one-launch-per-segment A/B kernel, has no second pass: it runs without the exact walk)
 #if FW_AB
-    const bool fused_req = O.fused && !(p->use_bvh && sc->d.has_mesh);
+    const bool fused_req = O.fused && !ls && !(p->use_bvh && sc->d.has_mesh);
     const bool tlas_refill = !O.tlas_refill_off;
 #else
     const bool fused_req = false, tlas_refill = true;
@@ -2064,6 +2130,11 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
             if (exact_mode) put(L.exact_slots, 2 * (size_t)max_paths * 4 + 64);   // two lists of at most every ray of a segment, + the counters
             put(L.wcount, (size_t)(fw::MAX_SEGMENTS + 1) * q.n_waves * 4);
             if (stage_rays) put(L.rays, (size_t)max_paths * 24); else L.rays = nullptr;
+            if (ls) {
+                put(L.s_ray_a, (size_t)cap * 16); put(L.s_ray_b, (size_t)cap * 8); put(L.s_state, (size_t)cap * 16); put(L.s_obj, (size_t)cap * 4);
+                put(L.s_hits, (size_t)cap * 8); put(L.s_wcount, (size_t)(fw::MAX_SEGMENTS + 1) * q.n_waves * 4);
+                put(L.pb[0], (size_t)cap * 4); put(L.pb[1], (size_t)cap * 4); put(L.nee, (size_t)cap * 16);
+            }
             if (park_meshes) {     // rays handed from k_extend_scan / k_extend_tlas_park to k_blas*: 40 B per slot
                 const size_t pcap = (size_t)(q.cap + 64u) * q.n_waves;     // park regions: q.cap + 64 entries per queue (DPark.stride)
                 put(L.park_a, pcap * 16); put(L.park_b, pcap * 8); put(L.park_m, pcap * 16); put(L.pcount, (size_t)q.n_waves * 8);   // pcount[n_waves] + ptotal[n_waves]
@@ -2179,19 +2250,19 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     fr.pinhole0 = (!ri && one_position && cam.lens_radius == 0.f && not_negative_zero(cam.position[0]) && not_negative_zero(cam.position[1]) && not_negative_zero(cam.position[2]) &&
                    !O.no_short_rays) ? 1u : 0u;
     // 4-byte hit records where k_shade can recompute t cheaply and exactly: the linear scan over spheres, rects and Rect3d
-    fr.hit4 = (!p->use_bvh && sc->simple_shapes && !exact_mode && !O.no_hit4 && !fused_req) ? 1u : 0u;
+    fr.hit4 = (!p->use_bvh && sc->simple_shapes && !exact_mode && !O.no_hit4 && !fused_req && !ls) ? 1u : 0u;
     const fw::DEnv &env = sc->d.env;
     // (pixel-major bits need the sample index of a path from a float quotient that is exact only while spp_batch < 2^21: dep_bit_of)
     fr.dep_pixel_major = (((n_pix <= 65536u && !O.dep_slot_major) || O.dep_pixel_major) && spp_b < (1u << 21)) ? 1u : 0u;
     fr.ex = sc->ex; fr.ex.mode = exact_mode;
-    fr.chain_bits = (O.no_chain || fused_req || cfg.shade_mode == 2) ? 0u : sc->chain_bits;      // k_bounce and k_shade's list mode (A/B build) carry the running product
-    fr.skip_zero_deposits = (env.kind == 0 && env.color[0] == 0.f && env.color[1] == 0.f && env.color[2] == 0.f && !O.no_zero_skip) ? 1u : 0u;
+    fr.chain_bits = (O.no_chain || fused_req || cfg.shade_mode == 2 || ls) ? 0u : sc->chain_bits;      // k_bounce and k_shade's list mode (A/B build) carry the running product
+    fr.skip_zero_deposits = (env.kind == 0 && env.color[0] == 0.f && env.color[1] == 0.f && env.color[2] == 0.f && !O.no_zero_skip && !ls) ? 1u : 0u;
 
     // per-launch timing (FW_FLAG_TIME_KERNELS): one event after every launch on the launch's own stream; the end of
     // launch k is the start of launch k+1 of that lane.  With several lanes the intervals overlap in wall time.
     const bool timing = (p->flags & FW_FLAG_TIME_KERNELS) != 0;
     const bool count_deposits = (p->flags & FW_FLAG_COUNT_DEPOSITS) != 0 && fr.skip_zero_deposits != 0;   // otherwise every terminated path writes one
-    const size_t per_batch_launches = 1 + 3 * fw::MAX_SEGMENTS + 2;     // raygen, 11 x (extend, exact extend, shade), queue totals, accumulate
+    const size_t per_batch_launches = 1 + 3 * fw::MAX_SEGMENTS + 2 + (ls ? 2 * (fw::MAX_SEGMENTS - 1) : 0);     // raygen, 11 x (extend, exact extend, shade), queue totals, accumulate; light sampling: 10 x (shadow walk, resolve)
     std::vector<std::vector<int>> ev_class(n_lanes);   // per lane: class of the launch that ENDS at events[1 + k]
     std::vector<size_t> ev_next(n_lanes, 0);
     if (timing) for (int l = 0; l < n_lanes; l++) {
@@ -2232,7 +2303,8 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // PHASE_LOCK tie them: B's extend of a segment waits for A's extend of that segment, A's next extend for B's — so that an issue-bound
     // extend always runs beside the other batch's memory-bound shade (left alone, the two lanes drift INTO phase within three segments:
     // profiles/r05a_share_trace.txt).
-    struct BatchCtx { fw::DFrame fr; fw::LaunchCfg cfg; fw::DPaths buf[2]; float2 *hits; float4 *srad; fw::DPark park; uint32_t *totals; uint32_t n_paths; int cur; int lane; hipStream_t ls; };
+    struct BatchCtx { fw::DFrame fr; fw::LaunchCfg cfg; fw::DPaths buf[2]; float2 *hits; float4 *srad; fw::DPark park; uint32_t *totals; uint32_t n_paths; int cur; int lane; hipStream_t ls;
+                      fw::DShadow sh; };
     // Measured (profiles/r05j_phase_lock.txt, three interleaved pairs): cornell 33.4-33.8 -> 32.2-32.4 ms — the lock holds the frame in the faster
     // of the two phases it otherwise lands in by chance (profiles/r05h_layout_pad.txt) —, where extend and shade last about as long as each
     // other.  Under use_bvh an extend lasts three shades and waiting for the other batch's costs: suzanne 62.7 -> 67.7, part2 @256 119.6 ->
@@ -2271,6 +2343,13 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         c.park = fw::DPark{(float4 *)L.park_a, (float2 *)L.park_b, (float4 *)L.park_m, q.cap + 64u, (uint32_t *)L.pcount,
                            park_meshes ? (uint32_t *)L.pcount + q.n_waves : nullptr};
         if (park_meshes) HIPCHK(hipMemsetAsync(c.park.ptotal, 0, (size_t)q.n_waves * 4, c.ls));
+        c.sh = fw::DShadow{};
+        if (ls) {
+            c.sh.lt = fw::DLights{(const uint32_t *)sc->lights.p, sc->n_lights, 1.f / (float)sc->n_lights};
+            c.sh.ray_a = (float4 *)L.s_ray_a; c.sh.ray_b = (float2 *)L.s_ray_b; c.sh.state = (float4 *)L.s_state; c.sh.obj = (uint32_t *)L.s_obj;
+            c.sh.wcount = (uint32_t *)L.s_wcount; c.sh.nee = (float4 *)L.nee;
+            HIPCHK(hipMemsetAsync(c.sh.nee, 0, (size_t)cap * 16, c.ls));
+        }
         c.cur = 0;
         return FW_OK;
     };
@@ -2304,6 +2383,18 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
             HIPCHK(hipStreamSynchronize(c.ls));
             r[12] = (float)alive;
         }
+        if (ls) {
+            Workspace::Lane &L = ws->lanes[c.lane];
+            c.sh.pb_in = (const float *)L.pb[c.cur]; c.sh.pb_out = (float *)L.pb[c.cur ^ 1];
+            timed(c, 2, [&] { fw::launch_shade_ls(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh); });
+            if (seg < fw::MAX_SEGMENTS - 1) {     // segments 0-9 scatter (render.rs:21): their shadow rays through the ordinary walks, then the resolve
+                fw::LaunchCfg scfg = c.cfg; scfg.q.wcount = c.sh.wcount;
+                fw::DFrame sfr = c.fr; sfr.seed32 ^= fw::SHADOW_SEED; sfr.ex.mode = 0;
+                const fw::DPaths sp{c.sh.ray_a, c.sh.ray_b, c.sh.state};
+                timed(c, 1, [&] { fw::launch_extend(scfg, sc->d, sfr, sp, (float2 *)L.s_hits, seg + 1, use_bvh, c.park); });
+                timed(c, 2, [&] { fw::launch_shadow_resolve(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
+            }
+        } else
         timed(c, 2, [&] { fw::launch_shade(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg); });
         c.cur ^= 1;
         return FW_OK;
@@ -2367,7 +2458,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         // (a view group of fw_render_views never runs as a frame graph: one call already spreads a frame's launches over all its views,
         //  and the groups of one call share a key, so a capture would be replayed inside the same call.  A group leaves the cached graph as it is)
         // (nor do the caller rays of fw_render_rays: their launches read the caller's memory, which a replay would not see change)
-        const bool graph_ok = O.graph != 0 && !rd && !vg && !ri && !fg.broken && !timing && !dump_one && !phase_lock && !stagger && (O.graph == 1 || chunks < GRAPH_MAX_CHUNKS);   // (a capture with PHASE_LOCK's events crashed inside the runtime: the two never meet by default — the lock wants batches of 100 M paths)
+        const bool graph_ok = O.graph != 0 && !rd && !vg && !ri && !ls && !fg.broken && !timing && !dump_one && !phase_lock && !stagger && (O.graph == 1 || chunks < GRAPH_MAX_CHUNKS);   // (a capture with PHASE_LOCK's events crashed inside the runtime: the two never meet by default — the lock wants batches of 100 M paths)
         uint64_t key = 0;
         if (graph_ok) {
             uint64_t h = 1469598103934665603ull;
@@ -3237,6 +3328,23 @@ int fw_selftest_wide_bvh(const float *boxes, uint32_t n, int format, uint32_t *v
 // CPU-only diagnostic (ABI v7): the host builders — the reference's median-split tree (bvh.rs:21-71) and the binned-SAH tree that is walked —
 // over n item boxes with `threads` host threads (1 = the sequential recursion); hashes[0..1] = FNV-1a of the two node arrays, stats = nodes and
 // depth of each.  The parallel builds must reproduce the sequential ones bit for bit (tests/test_host_build_cpu.py).
+int fw_selftest_lights(const fw_scene_desc *desc, float *out, uint32_t cap, uint32_t *n) {
+    if (!desc || !n || (!out && cap > 0) || (desc->n_objects && !desc->objects) || (desc->n_shapes && !desc->shapes) || (desc->n_materials && !desc->materials))
+        return fail(FW_ERR_BAD_ARG, "bad argument");
+    try {
+        const std::vector<LightRec> L = scene_lights(desc);
+        *n = (uint32_t)L.size();
+        for (uint32_t i = 0; i < cap && i < *n; i++) {
+            float *r = out + (size_t)i * FW_LIGHT_RECORD_FLOATS;
+            r[0] = (float)L[i].obj; r[1] = (float)L[i].kind;
+            std::memcpy(r + 2, L[i].pts, sizeof L[i].pts);
+            r[14] = L[i].area; r[15] = L[i].p_pick;
+        }
+        return FW_OK;
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+}
+
 int fw_selftest_bvh_build(const float *boxes, uint32_t n, int threads, uint64_t hashes[2], uint32_t stats[4]) {
     if (!boxes || n == 0 || threads < 1 || !hashes || !stats) return fail(FW_ERR_BAD_ARG, "bad argument");
     try {

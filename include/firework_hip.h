@@ -206,6 +206,16 @@ typedef struct fw_render_params {
 #define FW_FLAG_COUNT_DEPOSITS 2u /* count the radiance records k_shade really wrote (one extra pass over the sample buffer per
                                      batch, outside the kernel classes' times): makes fw_stats.bytes_shade exact when zero
                                      deposits are elided over a black environment; without it they are counted as written */
+#define FW_FLAG_LIGHT_SAMPLING 4u /* next-event estimation with MIS: every Lambertian and Isotropic vertex of segments 0-9
+                                     samples one of the scene's sampled lights (EmissiveMat spheres and axis-aligned rectangles, picked
+                                     uniformly) through a shadow ray, weighted against the BSDF's own sampling by the power heuristic.  The
+                                     same pixels in expectation, with less noise; the paths themselves (fw_stats.rays, rays_per_depth) are
+                                     the default frame's, shadow rays are not counted there (their walks count in ms_extend, their resolve in
+                                     ms_shade; parked_rays includes their parks).  A scene without a sampled light or without a Lambertian
+                                     or Isotropic material renders the default frame.  Honoured by fw_render, fw_render_progressive,
+                                     fw_render_scene, fw_render_scene_tiled, fw_render_rays, fw_render_views and fw_render_adaptive (their
+                                     frames go through the same path); ignored by fw_render_aovs (first-hit values carry no lighting).
+                                     A build without it ignores the bit and renders the default frame. */
 
 #define FW_MAX_SEGMENTS 11  /* depths 0..10: render.rs:21 */
 
@@ -567,6 +577,14 @@ int fw_selftest_bvh_build(const float *boxes, uint32_t n, int threads, uint64_t 
    The device's trees equal the host's bit for bit.  Errors: FW_ERR_BAD_ARG (n = 0, a null pointer, device < -1 or out of range),
    FW_ERR_NO_DEVICE (device >= 0 without a GPU), FW_ERR_NAN_BBOX (a centre the median tree compares is NaN), FW_ERR_OOM, FW_ERR_HIP. */
 int fw_selftest_bvh_trees(int device, const float *boxes, uint32_t n, float *ref_nodes, float *sah_nodes, uint32_t stats[4]);
+
+/* Diagnostic, CPU only: the sampled lights of a description as FW_FLAG_LIGHT_SAMPLING sees them, in object order, FW_LIGHT_RECORD_FLOATS
+   floats each: object index, shape kind (FW_SHAPE_SPHERE / _XYRECT / _XZRECT / _YZRECT), then a rectangle's four world corners (12 floats;
+   rotated only where the reference intersects the object rotated, cos_trace < 0.999) or a sphere's centre and radius (4 floats, 8 zeros),
+   the area and p_pick (1 / number of lights).  *n = the number of lights; at most cap records are written.  Errors: FW_ERR_BAD_ARG (null
+   desc or n, out = NULL with cap > 0). */
+#define FW_LIGHT_RECORD_FLOATS 16
+int fw_selftest_lights(const fw_scene_desc *desc, float *out, uint32_t cap, uint32_t *n);
 
 #ifdef __cplusplus
 }
