@@ -9,7 +9,9 @@ step   : one full frame through the HIP wavefront path, tiles sharded over the r
 N>1    : one rank per GPU over RCCL (backend "nccl").  `python bench.py --gpus N` starts its own N ranks (children of a
          parent that never touches the GPU); under torch.distributed.run (WORLD_SIZE set) it is a rank itself.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps, writes
+--dump-outputs / --dump-frame and prints the line: the headline figure and what the timed loop itself counted, nothing else.
+`--full` adds the figures that take runs of their own, as these extra objects:
   schedule       — the timed loop runs the library's own schedule (two batches in flight where that is faster); per-kernel times come
                    from a labelled exclusive pass (one batch in flight) run right after it
   roofline       — k_shade (the kernel that moves most HBM bytes): THIS layout's algorithmic bytes (fw_stats.bytes_shade,
@@ -58,11 +60,15 @@ def parse_args(argv=None):
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--paths-per-batch", type=int, default=0)
-    ap.add_argument("--no-kernel-timing", action="store_true", help="skip per-launch HIP events (no roofline object)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what takes runs of its own: the exclusive pass (schedule, "
+                         "roofline, roofline_frame, kernel_ms_per_step), device, one_shot, one_shot_cold, cpu_baseline and parity; "
+                         "the --no-* options below leave parts of it out")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip per-launch HIP events (no roofline object)")
     ap.add_argument("--cpu-spp", type=int, default=0, help="spp of the bounded CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (cpu_baseline and parity)")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-one-shot", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs (cpu_baseline and parity)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity leg")
+    ap.add_argument("--no-one-shot", action="store_true", help="with --full: skip one_shot and one_shot_cold")
     ap.add_argument("--parity-seconds", type=float, default=45.0, help="CPU budget of the parity leg (pixel lattice chosen to fit)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (=RCCL over xGMI) for real multi-GPU runs; gloo stages the gather through host memory and "
@@ -216,34 +222,35 @@ def main():
                        "collective": (f"one gather of u8 tiles to rank 0 ({args.backend}, world_size {dist.get_world_size()})" if use_dist else "none"),
                        "rng": "counter (pcg4d) keyed by (seed,pixel,sample,dimension)", "seed": s["seed"]},
             "timed_region": "device-resident steady state: scene already in HBM, frame assembled in HBM on rank 0 "
-                            "(the reference's own region, main.rs:40-44, is `one_shot`)",
+                            "(the reference's own region, main.rs:40-44, is `one_shot` of a --full run)",
             "msamples_per_s": total_samples / elapsed / 1e6,
             "frame_time_ms": ms_step,
             "rays_per_sample": total_rays / max(1.0, total_samples),
             "ms_gather_per_step": ms_gather / args.steps,
         }
-        if not args.no_kernel_timing:
-            # The timed loop runs the library's own schedule (two batches in flight where that is faster: their kernels overlap, so
-            # their HIP-event times do too).  The roofline divides by a kernel's OWN time: a labelled exclusive pass, one batch in flight.
-            ex_acc, ex_ms = exclusive_pass(tr, keys, frames=max(2, min(5, args.steps)))
-            # the library keeps two batches in flight whenever a frame has two (fw_runtime.cpp: n_lanes) unless STREAMS says otherwise
-            overlapped = int(tr.last_stats.get("n_batches", 1)) >= 2 and os.environ.get("FIREWORK_STREAMS", "") != "1"
-            out["schedule"] = {"timed_loop": "two batches in flight on two streams (kernel times overlap)" if overlapped else "one batch in flight",
-                               "timed_loop_ms_per_step": ms_step, "exclusive_pass_ms_per_step": ex_ms,
-                               "exclusive_pass": f"FIREWORK_STREAMS=1, {ex_acc['frames']} frames after the timed loop: every kernel's HIP-event time is its own; "
-                                                 "roofline, roofline_frame and kernel_ms_per_step are taken from it"}
-            out.update(roofline_objects(ex_acc, args, tr, renderer, steps=ex_acc["frames"]))
-        out["device"] = device_info(device_index)
         if world > 1:
             out["ranks"] = rank_spread
-        if world == 1 and not args.no_one_shot:
-            out["one_shot"] = one_shot(scene, renderer, device_index)
-            out["one_shot_cold"] = one_shot_cold(args)
-        if world == 1 and not args.no_cpu_baseline:
-            cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-            out["cpu_baseline"] = cpu_baseline(args, s, cores)
-            if not args.no_parity:
-                out["parity"] = parity(args, tr, renderer, scene, frame, out["cpu_baseline"], cores)
+        if args.full:       # what takes runs of its own: after the timed loop and the dumps, never in a plain run
+            if not args.no_kernel_timing:
+                # The timed loop runs the library's own schedule (two batches in flight where that is faster: their kernels overlap, so
+                # their HIP-event times do too).  The roofline divides by a kernel's OWN time: a labelled exclusive pass, one batch in flight.
+                ex_acc, ex_ms = exclusive_pass(tr, keys, frames=max(2, min(5, args.steps)))
+                # the library keeps two batches in flight whenever a frame has two (fw_runtime.cpp: n_lanes) unless STREAMS says otherwise
+                overlapped = int(tr.last_stats.get("n_batches", 1)) >= 2 and os.environ.get("FIREWORK_STREAMS", "") != "1"
+                out["schedule"] = {"timed_loop": "two batches in flight on two streams (kernel times overlap)" if overlapped else "one batch in flight",
+                                   "timed_loop_ms_per_step": ms_step, "exclusive_pass_ms_per_step": ex_ms,
+                                   "exclusive_pass": f"FIREWORK_STREAMS=1, {ex_acc['frames']} frames after the timed loop: every kernel's HIP-event time is its own; "
+                                                     "roofline, roofline_frame and kernel_ms_per_step are taken from it"}
+                out.update(roofline_objects(ex_acc, args, tr, renderer, steps=ex_acc["frames"]))
+            out["device"] = device_info(device_index)
+            if world == 1 and not args.no_one_shot:
+                out["one_shot"] = one_shot(scene, renderer, device_index)
+                out["one_shot_cold"] = one_shot_cold(args)
+            if world == 1 and not args.no_cpu_baseline:
+                cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+                out["cpu_baseline"] = cpu_baseline(args, s, cores)
+                if not args.no_parity:
+                    out["parity"] = parity(args, tr, renderer, scene, frame, out["cpu_baseline"], cores)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     tr.close()

@@ -76,7 +76,7 @@ def main():
     ks = newest(f"{src}/trace/**/*_kernel_stats.csv")
     if ks:
         shutil.copyfile(ks[0], f"{ROOT}/profiles/{tag}_kernel_stats.csv")
-    pmc = {"command": "rocprofv3 --pmc <C> --kernel-trace --output-format csv -- python3 bench.py [--config ..] --steps 1 --warmup 0 --no-cpu-baseline --no-one-shot",
+    pmc = {"command": "rocprofv3 --pmc <C> --kernel-trace --output-format csv -- python3 bench.py [--config ..] --steps 1 --warmup 0 --full --no-cpu-baseline --no-one-shot",
            "note": "bytes = Counter_Value * 1024; read side doubled (gfx950 FETCH_SIZE = 1/2 of wide coalesced reads)",
            "source_sha": sha, "workload": workload, "kernels": {}}
     durs = {}

@@ -1,4 +1,4 @@
-"""bench.py's host side, no GPU: `--steps` and what `--dump-outputs` writes (float32, under its size cap, the same sample every run)."""
+"""bench.py's host side, no GPU: `--steps`, `--full` and what `--dump-outputs` writes (float32, under its size cap, the same sample every run)."""
 import os
 
 import numpy as np
@@ -11,6 +11,11 @@ def test_steps_sets_the_timed_steps_and_must_be_positive():
     assert bench.parse_args(["--steps", "7", "--warmup", "2"]).steps == 7
     with pytest.raises(SystemExit):
         bench.parse_args(["--steps", "0"])
+
+
+def test_full_is_off_by_default():
+    assert bench.parse_args(["--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse_args(["--steps", "3", "--warmup", "1", "--full"]).full is True
 
 
 def test_dump_outputs_writes_the_whole_frame_as_float32(tmp_path):

@@ -62,7 +62,7 @@ def test_formerly_diverging_paths_follow_the_oracle(oracle, monkeypatch, name, w
 
 
 def test_ray_counts_per_depth_equal_the_oracles_on_the_frames_they_came_from(oracle):
-    """the whole frames of the hunt (C3 at 16 spp, C5 at 4 spp; C2's 1024-spp frame is bench.py's own parity leg)"""
+    """the whole frames of the hunt (C3 at 16 spp, C5 at 4 spp; C2's 1024-spp frame is the parity leg of bench.py --full)"""
     for name, spp in (("C3_suzanne", 16), ("C5_part2_all", 4)):
         scene, renderer = scenes.config(name, samples=spp)
         gpu, cpu = renderer.render_full(scene), oracle.render(scene, renderer)

@@ -185,8 +185,22 @@ def test_bench_dump_outputs_is_the_frame_of_the_last_timed_step(tmp_path):
     assert np.array_equal(got, np.load(f).astype(np.float32)) and got.max() > 0
 
 
+FULL_ONLY = ("schedule", "roofline", "roofline_frame", "kernel_ms_per_step", "device", "one_shot", "one_shot_cold", "cpu_baseline", "parity")
+
+
+def test_plain_bench_line_carries_the_headline_and_nothing_that_takes_runs_of_its_own():
+    """A plain run times its steps and prints the line; the exclusive pass, device probe, one-shot calls, CPU baseline and
+    parity leg are --full's alone."""
+    d = _bench(["--width", "96", "--height", "96", "--spp", "32", "--steps", "2", "--warmup", "1"])
+    assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["frame_time_ms"] == d["ms_per_step"] and d["msamples_per_s"] > 0 and d["rays_per_sample"] >= 1
+    assert not [k for k in FULL_ONLY if k in d], [k for k in FULL_ONLY if k in d]
+
+
 def test_bench_line_carries_roofline_parity_and_one_shot():
-    d = _bench(["--width", "96", "--height", "96", "--spp", "32", "--steps", "2", "--warmup", "1", "--parity-seconds", "5"])
+    d = _bench(["--full", "--width", "96", "--height", "96", "--spp", "32", "--steps", "2", "--warmup", "1", "--parity-seconds", "5"])
+    assert all(k in d for k in FULL_ONLY), [k for k in FULL_ONLY if k not in d]
     assert d["unit"] == "Mrays/s" and d["scaling"] == "strong" and d["vs_baseline"] is None
     r = d["roofline"]
     # `roofline` names the kernel class with the larger exclusive time; the other class rides along, and no bound is ever null

@@ -2,7 +2,7 @@
 # time of the library's own schedule, the per-kernel times of the exclusive pass and the roofline objects (profiles/*_configs_full.jsonl).
 R=$PWD
 run() {
-  timeout -k 10 900 python3 $R/bench.py --config $1 --steps $2 --warmup $3 --no-cpu-baseline --no-one-shot 2>/dev/null | tail -1 | python3 -c "
+  timeout -k 10 900 python3 $R/bench.py --full --config $1 --steps $2 --warmup $3 --no-cpu-baseline --no-one-shot 2>/dev/null | tail -1 | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d.get('kernel_ms_per_step',{}); r=d.get('roofline',{}); o=r.get('other_kernel',{})
 print(json.dumps({'config': d['config']['workload'], 'Mrays/s': round(d['value']), 'Msamples/s': round(d['msamples_per_s']), 'ms_per_frame': round(d['ms_per_step'],2),

@@ -4,7 +4,7 @@
 # then:   python3 scripts/summarize_prof.py gpurun_out/<dir tag> <profiles tag> "<workload>"
 TAG=$1; shift
 export TMPDIR=/tmp; R=$PWD; O=$R/gpurun_out/$TAG; rm -rf $O; mkdir -p $O && cd /tmp
-B="--no-cpu-baseline --no-one-shot"
+B="--full --no-cpu-baseline --no-one-shot"
 # one batch in flight in every frame of these passes (round 3: the library's own schedule overlaps two batches, whose launches
 # carry half a frame each): per-launch averages then mean the same thing as bench.py's exclusive pass, which the roofline quotes
 export FIREWORK_STREAMS=1

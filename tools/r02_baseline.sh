@@ -7,7 +7,7 @@ timeout -k 10 300 bash tools/configs.sh > $O/configs_full.jsonl 2>$O/configs.err
 cd /tmp
 pmc() {  # cfg spp name counters...
   local cfg=$1 spp=$2 name=$3; shift 3
-  timeout -k 10 200 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/pmc_$cfg/$name -- python3 $R/bench.py --config $cfg --spp $spp --steps 1 --warmup 0 --no-cpu-baseline > $O/pmc_${cfg}_$name.log 2>&1
+  timeout -k 10 200 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/pmc_$cfg/$name -- python3 $R/bench.py --full --config $cfg --spp $spp --steps 1 --warmup 0 --no-cpu-baseline > $O/pmc_${cfg}_$name.log 2>&1
   echo "pmc $cfg $name rc=$?" | tee -a $O/summary.txt
 }
 for c in "C3_suzanne 64" "C5_part2_all 16"; do set -- $c

@@ -17,6 +17,6 @@ for v in 0 1; do
   for cfg in "C3_suzanne 2 1" "C5_part2_all 1 0" "C1_random_spheres 3 1"; do
     set -- $cfg
     if [ $v = 1 ]; then export FIREWORK_NO_EXACT=1; else unset FIREWORK_NO_EXACT; fi
-    timeout -k 10 300 python3 bench.py --config $1 --steps $2 --warmup $3 --no-cpu-baseline --no-one-shot 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d.get('kernel_ms_per_step',{}); print(json.dumps({'config': d['config']['workload'], 'ms_per_frame': round(d['ms_per_step'],2), 'ms_extend': round(k.get('ms_extend',0),2), 'ms_shade': round(k.get('ms_shade',0),2)}))"
+    timeout -k 10 300 python3 bench.py --full --config $1 --steps $2 --warmup $3 --no-cpu-baseline --no-one-shot 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d.get('kernel_ms_per_step',{}); print(json.dumps({'config': d['config']['workload'], 'ms_per_frame': round(d['ms_per_step'],2), 'ms_extend': round(k.get('ms_extend',0),2), 'ms_shade': round(k.get('ms_shade',0),2)}))"
   done
 done 2>&1 | tee $OUT/timing.txt

@@ -9,4 +9,4 @@ for c in "$@"; do
   timeout -k 10 500 python tools/diverge.py $NAME $W $H $SPP --max-pixels 6 --tol 1e-4 --out $OUT/diverge_$NAME.json > $OUT/diverge_$NAME.log 2>&1; echo "$NAME rc=$?"
   tail -n 1 $OUT/diverge_$NAME.log | cut -c1-600
 done
-timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-900 $OUT/bench.json
+timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-900 $OUT/bench.json

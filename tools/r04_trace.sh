@@ -7,7 +7,7 @@ export FIREWORK_STREAMS=1
 for cs in "$@"; do
   c=${cs%%:*}; spp=${cs##*:}
   rm -rf /tmp/tr_$c
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr_$c -- python3 $R/bench.py --config $c --spp $spp --steps 3 --warmup 1 --no-cpu-baseline --no-one-shot > $O/trace_$c.log 2>&1 || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr_$c -- python3 $R/bench.py --full --config $c --spp $spp --steps 3 --warmup 1 --no-cpu-baseline --no-one-shot > $O/trace_$c.log 2>&1 || exit 1
   f=$(find /tmp/tr_$c -name "*kernel_stats.csv" | head -1)
   echo "== $c @ $spp" | tee -a $O/kernel_split.txt
   python3 - "$f" <<'PY' | tee -a $O/kernel_split.txt

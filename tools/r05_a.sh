@@ -29,4 +29,4 @@ for W in (1, 4):
     for k, v in sorted(by.items(), key=lambda kv: -sum(kv[1])): print("   %-60s n=%5d sum %9.2f ms  mean %8.1f us  max %8.1f us" % (k, len(v), sum(v) / 1e3, sum(v) / len(v), max(v)))
 PY
 echo "== bench"
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"; cut -c1-400 $OUT/bench.json
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"; cut -c1-400 $OUT/bench.json

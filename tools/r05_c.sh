@@ -6,7 +6,7 @@ OUT=$PWD/gpurun_out/$1; mkdir -p $OUT; R=$PWD
 bash tools/r05_ab.sh $1 "base xcd nodep nopix" "-" 2 -- "" "--config C4a_hdri_test"
 echo "== per-segment trace (exclusive)"
 export TMPDIR=/tmp; cd /tmp
-FIREWORK_STREAMS=1 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/seg -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-one-shot > $OUT/seg_bench.json 2> $OUT/seg_bench.err; echo "rc=$?"
+FIREWORK_STREAMS=1 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/seg -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-one-shot > $OUT/seg_bench.json 2> $OUT/seg_bench.err; echo "rc=$?"
 cd $R
 python3 - <<PY
 import csv, glob, json
@@ -34,5 +34,5 @@ echo "== error word (A/B build)"
 FIREWORK_LIB=$R/firework_amd/lib/variants/lib_ab.so timeout -k 10 300 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "error_word or wide_node or chain_state" 2>&1 | tail -4
 echo "== EXACT_PRODUCT cost"
 for cfg in "--config C5_part2_all --spp 256" "--config C1_random_spheres" "--config earth"; do for i in 1 2; do
-  for e in 0 1; do FIREWORK_EXACT_PRODUCT=$e timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-one-shot $cfg 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d.get('kernel_ms_per_step',{}); print('EXACT_PRODUCT=$e %-34s' % '$cfg', 'ms', round(d['ms_per_step'],2), 'ext', round(k.get('ms_extend',0),2), 'shd', round(k.get('ms_shade',0),2))"; done
+  for e in 0 1; do FIREWORK_EXACT_PRODUCT=$e timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-one-shot $cfg 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d.get('kernel_ms_per_step',{}); print('EXACT_PRODUCT=$e %-34s' % '$cfg', 'ms', round(d['ms_per_step'],2), 'ext', round(k.get('ms_extend',0),2), 'shd', round(k.get('ms_shade',0),2))"; done
 done; done 2>&1 | tee $OUT/exact_product.txt

@@ -13,7 +13,7 @@ for v in xcd4k base; do L=$V/lib_$v.so; [ $v = base ] && L=$R/firework_amd/lib/l
 echo "== FW_WIDE_FMA"
 bash tools/r05_ab.sh $1 "nofma base" "base" 2 -- "--config C3_suzanne" "--config teapot --spp 128" "--config C5_part2_all --spp 256" "--config C1_random_spheres" "--config C3_suzanne --spp 64"
 echo "== C5 @4096 parity"
-( timeout -k 10 1000 python3 bench.py --config C5_part2_all --steps 2 --warmup 1 --no-one-shot --parity-seconds 150 > $OUT/c5_4096.json 2> $OUT/c5_4096.err; echo "rc=$?" > $OUT/c5_rc.txt ) &
+( timeout -k 10 1000 python3 bench.py --full --config C5_part2_all --steps 2 --warmup 1 --no-one-shot --parity-seconds 150 > $OUT/c5_4096.json 2> $OUT/c5_4096.err; echo "rc=$?" > $OUT/c5_rc.txt ) &
 PID=$!
 while kill -0 $PID 2>/dev/null; do sleep 45; echo "heartbeat $(date +%s)"; done
 cat $OUT/c5_rc.txt; python3 -c "
