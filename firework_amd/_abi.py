@@ -29,6 +29,8 @@ FW_FLAG_TIME_KERNELS = 1
 FW_FLAG_COUNT_DEPOSITS = 2
 FW_FLAG_LIGHT_SAMPLING = 4   # next-event estimation with MIS
 FW_LIGHT_RECORD_FLOATS = 16  # fw_selftest_lights
+FW_FLAG_ENV_SAMPLING = 8     # importance sampling of an HDR environment map
+FW_ENV_SAMPLE_FLOATS = 6     # fw_selftest_env_sample
 FW_NO_HIT = 0xFFFFFFFF   # fw_hit.object of a miss
 
 f32, i32, u32, u64 = C.c_float, C.c_int32, C.c_uint32, C.c_uint64

@@ -73,6 +73,10 @@ def load(preload=False, device=None):
     lib.fw_selftest_lights.restype = C.c_int
     lib.fw_selftest_lights.argtypes = [C.POINTER(A.fw_scene_desc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.fw_selftest_wide_bvh.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.fw_selftest_env_dist.restype = C.c_int
+    lib.fw_selftest_env_dist.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_double)]
+    lib.fw_selftest_env_sample.restype = C.c_int
+    lib.fw_selftest_env_sample.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.fw_selftest_bvh_build.restype = C.c_int
     lib.fw_selftest_bvh_build.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     lib.fw_selftest_bvh_trees.restype = C.c_int
@@ -176,6 +180,29 @@ def selftest_lights(scene_desc):
             d["corners"] = r[2:14].reshape(4, 3).astype(np.float64)
         lights.append(d)
     return lights
+
+
+def selftest_env_dist(rgb, device=0):
+    """fw_selftest_env_dist: the FW_FLAG_ENV_SAMPLING table of an (h, w, 3) float map as the device builds it.
+    -> ((h, w) float32 per-texel probabilities, total weight)"""
+    lib = load()
+    m = np.ascontiguousarray(rgb, np.float32)
+    h, w = m.shape[:2]
+    p = np.zeros((h, w), np.float32)
+    total = C.c_double()
+    _check(lib, lib.fw_selftest_env_dist(int(device), m.ctypes.data, w, h, p.ctypes.data, C.byref(total)))
+    return p, float(total.value)
+
+
+def selftest_env_sample(rgb, n, seed=1, device=0):
+    """fw_selftest_env_sample: n directions drawn from the table of an (h, w, 3) float map as k_shade_env draws them.  -> (dirs (n, 3),
+    reported pdf (n,), drawn texel (n,), looked-up texel (n,))"""
+    lib = load()
+    m = np.ascontiguousarray(rgb, np.float32)
+    h, w = m.shape[:2]
+    out = np.zeros((int(n), A.FW_ENV_SAMPLE_FLOATS), np.float32)
+    _check(lib, lib.fw_selftest_env_sample(int(device), m.ctypes.data, w, h, int(n), int(seed) & 0xFFFFFFFF, out.ctypes.data))
+    return out[:, 0:3].copy(), out[:, 3].copy(), out[:, 4].astype(np.int64), out[:, 5].astype(np.int64)
 
 
 def selftest_bvh_build(boxes, threads):

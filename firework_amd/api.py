@@ -1045,6 +1045,14 @@ class Renderer:
             self.settings["flags"] & ~A.FW_FLAG_LIGHT_SAMPLING)
         return self
 
+    def env_sampling(self, on=True):
+        """FW_FLAG_ENV_SAMPLING: importance sampling of an HDR environment map at Lambertian and Isotropic vertices, alone or
+        beside light_sampling's emitters — the same image in expectation with less noise under a bright sun.  Without an HDR map of positive
+        weight (or without a Lambertian or Isotropic material) the frame is the one without the flag; fw_render_aovs ignores it."""
+        self.settings["flags"] = (self.settings["flags"] | A.FW_FLAG_ENV_SAMPLING) if on else (
+            self.settings["flags"] & ~A.FW_FLAG_ENV_SAMPLING)
+        return self
+
     def count_deposits(self, on=True):
         """FW_FLAG_COUNT_DEPOSITS: fw_stats.deposits / bytes_shade become exact where zero deposits are elided (one extra pass)."""
         self.settings["flags"] = (self.settings["flags"] | A.FW_FLAG_COUNT_DEPOSITS) if on else (

@@ -240,6 +240,17 @@ struct DShadow {
 };
 constexpr uint32_t SHADOW_SEED = 0x6e1a7c35u;   // the shadow walks' DFrame.seed32 = seed32 ^ SHADOW_SEED: their ConstantMedium draws (§9g)
 
+// ---- environment sampling (FW_FLAG_ENV_SAMPLING) --------------------------------------------------------------
+// The HDR map's piecewise-constant distribution over env_sample's lookup index (w x h texels): cdf_m[y] the marginal over rows, cdf_c[y * w + x]
+// the conditional within row y (both inclusive, the last positive entry 1), dens[i] = p[i] / Omega_row(i) the solid-angle density of texel i.
+// p_env: the probability of picking the environment among the sampled lights (1, or 1/2 beside the emitters of DLights).  A kernel argument
+// of its own, beside DShadow: DShadow's size is part of k_shade_ls's and k_shadow_resolve's kernel arguments, which stay as they are.
+struct DEnvDist {
+    const float *cdf_m, *cdf_c, *dens;
+    float p_env;
+    uint32_t w, h;
+};
+
 // launch wrappers (fw_kernels.hip)
 struct LaunchCfg {
     hipStream_t stream;
@@ -288,6 +299,16 @@ void launch_shade(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, 
 void launch_shade_ls(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
                      float4 *sample_rad, int segment, const DShadow &);
 void launch_shadow_resolve(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment);
+// environment sampling: k_shade_ls with the environment among the sampled lights (k_shade_env; shading mode 0 only: an HDR map
+// is an expensive case), the resolve that also takes environment shadow rays (visible iff they miss), and the table build
+void launch_shade_env(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
+                      float4 *sample_rad, int segment, const DShadow &, const DEnvDist &);
+void launch_shadow_resolve_env(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment);
+// the table of env (w x h): scratch = 2 h + 1 doubles (row totals, the total); p_out (optional): the per-texel probabilities; *total = the total weight
+// (host memory, after a synchronisation of `stream`)
+int build_env_dist(hipStream_t stream, const DEnv &env, float *cdf_m, float *cdf_c, float *dens, float *p_out, double *scratch, double *total);
+// n samples of the table (fw_selftest_env_sample): per sample (dir xyz, reported pdf, drawn index, looked-up index)
+void launch_env_sample_test(hipStream_t stream, const DEnv &env, const DEnvDist &ed, uint32_t n, uint32_t seed32, float *out);
 void launch_bounce(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, float4 *sample_rad, int segment,
                    bool use_bvh);
 void launch_queue_totals(const LaunchCfg &, uint32_t *totals, const uint32_t *ptotal);

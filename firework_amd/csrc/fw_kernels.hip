@@ -2931,12 +2931,9 @@ __device__ __forceinline__ void sphere_uv(V3 p, float &u, float &v) {   // objec
     v = fdiv(theta + PI_F / 2.f, PI_F);
 }
 
-__device__ V3 env_sample(const DEnv &e, V3 dir) {     // environment.rs:21-26,60-67; examples/hdri_test.rs:70-82
-    if (e.kind == 0) return mk(e.color[0], e.color[1], e.color[2]);
-    if (e.kind == 1) {
-        float t = 0.5f * (dir.y + 1.0f);
-        return (1.f - t) * mk(e.horizon[0], e.horizon[1], e.horizon[2]) + t * mk(e.zenith[0], e.zenith[1], e.zenith[2]);
-    }
+// The HDR map's texel that a (unit) direction looks up: the reference's sphere_uv, its `(y as f32 * width) as usize + x` and the clamp at
+// the poles.  Shared by env_sample, the environment's sampling density and the MIS weight of a miss, so that all three agree.
+__device__ __forceinline__ unsigned long long env_texel(const DEnv &e, V3 dir) {
     float u, v; sphere_uv(dir, u, v);
     float width = (float)e.hdr_w, height = (float)e.hdr_h;
     auto sat64 = [](float f) -> unsigned long long { if (!(f > 0.f)) return 0ull; if (f >= 18446744073709551616.f) return ~0ull; return (unsigned long long)f; };
@@ -2944,7 +2941,15 @@ __device__ V3 env_sample(const DEnv &e, V3 dir) {     // environment.rs:21-26,60
     unsigned long long idx = sat64((float)y * width) + x;
     unsigned long long n = (unsigned long long)e.hdr_w * e.hdr_h;
     if (idx >= n) idx = n - 1;     // the reference indexes out of bounds at the poles; clamp
-    const float4 c = reinterpret_cast<const float4 *>(e.hdr)[idx];     // 16-byte texels (the host pads: fw_runtime.cpp)
+    return idx;
+}
+__device__ V3 env_sample(const DEnv &e, V3 dir) {     // environment.rs:21-26,60-67; examples/hdri_test.rs:70-82
+    if (e.kind == 0) return mk(e.color[0], e.color[1], e.color[2]);
+    if (e.kind == 1) {
+        float t = 0.5f * (dir.y + 1.0f);
+        return (1.f - t) * mk(e.horizon[0], e.horizon[1], e.horizon[2]) + t * mk(e.zenith[0], e.zenith[1], e.zenith[2]);
+    }
+    const float4 c = reinterpret_cast<const float4 *>(e.hdr)[env_texel(e, dir)];     // 16-byte texels (the host pads: fw_runtime.cpp)
     return mk(c.x, c.y, c.z);
 }
 
@@ -3167,6 +3172,30 @@ __device__ __forceinline__ V3 light_emit(const DScene &sc, const float4 *matp, c
 struct LsIO { float pb_in, pb_out; bool shadow; Ray sray; uint32_t sobj; V3 pending; };
 
 // ------------------------------------------------------------------------------------------------
+// Environment sampling (FW_FLAG_ENV_SAMPLING): the HDR map as a sampled light, p proportional to max(r, g, b) x the texel's solid
+// angle.  Texel (x, y) is what env_texel returns for u in [x/w, (x+1)/w), 1 - v in [y/h, (y+1)/h): phi = atan2(z, x) = pi (1 - 2u) and
+// sin(theta) = dir.y in [cos((y+1) pi/h), cos(y pi/h)], so Omega_row(y) = (2 pi / w) (cos(y pi/h) - cos((y+1) pi/h)) and a point uniform
+// in (phi, sin theta) inside the texel is uniform in solid angle there.
+// ------------------------------------------------------------------------------------------------
+// the first i with cdf[i] > xi: cdf is non-decreasing with cdf[n-1] = 1 > xi, so cdf[i-1] <= xi < cdf[i] and entry i has positive weight
+__device__ __forceinline__ uint32_t cdf_find(const float *__restrict__ cdf, uint32_t n, double xi) {
+    uint32_t lo = 0, hi = n - 1u;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((double)cdf[mid] > xi) hi = mid; else lo = mid + 1u; }
+    return lo;
+}
+// A direction drawn from the table (u = draw(key, P_LIGHT, segment, 1)): the row by u.x and the column by u.y as full 32-bit words, the point
+// inside the texel by u.z (phi) and u.w (sin theta).  t: the texel drawn (y w + x).
+__device__ __forceinline__ V3 env_dist_sample(const DEnvDist &ed, uint4 u, uint32_t &t) {
+    const uint32_t y = cdf_find(ed.cdf_m, ed.h, (double)u.x * 0x1p-32);
+    const uint32_t x = cdf_find(ed.cdf_c + (size_t)y * ed.w, ed.w, (double)u.y * 0x1p-32);
+    t = y * ed.w + x;
+    const double s_hi = cospi((double)y / (double)ed.h), s_lo = cospi((double)(y + 1u) / (double)ed.h);
+    const double s = s_lo + (double)u2f(u.w) * (s_hi - s_lo), c = sqrt(fmax((1.0 - s) * (1.0 + s), 0.0));
+    double sp, cp; sincospi(1.0 - 2.0 * ((double)x + (double)u2f(u.z)) / (double)ed.w, &sp, &cp);
+    return mk((float)(c * cp), (float)s, (float)(c * sp));
+}
+
+// ------------------------------------------------------------------------------------------------
 // K5 + K7  shade + stream compaction
 //
 // k_shade is latency-bound (rocprofv3: 79 % of wave cycles in s_waitcnt in the first version): the chain
@@ -3190,12 +3219,13 @@ __device__ __forceinline__ bool expensive_shading(const DScene &sc, const float4
 // CHAIN: the path's state is its chain of material ids (load_state_chain), `chain` in and `nchain` out; beta / nbeta are unused.
 // LS: k_shade_ls: the MIS weight of emission reached from a light-sampling vertex, the light sample of a Lambertian or
 // Isotropic vertex (*ls: the shadow ray, left to k_shadow_resolve), and the path's visible light samples (sh->nee) in its deposit.
-template <bool CHEAP_ONLY = false, bool CHAIN = false, bool LS = false>
+// ENV (with LS): k_shade_env: the HDR map is a sampled light as well (*ed), picked with probability ed->p_env.
+template <bool CHEAP_ONLY = false, bool CHAIN = false, bool LS = false, bool ENV = false>
 __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, const float4 *objp, const float4 *matp,
                                            const float4 *texp, const Ray &r, V3 beta, uint32_t chain, uint32_t path_id, float t_hit,
                                            uint32_t hit_code, int segment, float4 *__restrict__ sample_rad, Ray &nr, V3 &nbeta, uint32_t &nchain PH_ARG,
                                            const RngKey *pre_key = nullptr,       // pre_key: the path's RNG key, when the caller has fetched it already (k_shade, FW_SHADE_PIPE)
-                                           const DShadow *sh = nullptr, LsIO *ls = nullptr) {
+                                           const DShadow *sh = nullptr, LsIO *ls = nullptr, const DEnvDist *ed = nullptr) {
     bool alive = false;
     const uint32_t obj_index = hit_code == MISS ? MISS : (hit_code >> sc.prim_bits);
     V3 rad = mk(0.f, 0.f, 0.f);
@@ -3230,6 +3260,11 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
                 rad = carried((1.f - t) * mk(sc.env.horizon[0], sc.env.horizon[1], sc.env.horizon[2]) + t * mk(sc.env.zenith[0], sc.env.zenith[1], sc.env.zenith[2]));
             } else if (!f.skip_zero_deposits) rad = carried(mk(sc.env.color[0], sc.env.color[1], sc.env.color[2]));
             // else: a black ColorEnv (the host checked): the path carries nothing, whatever it scattered on, and writes no record (below)
+        } else if (ENV && ls->pb_in > 0.f) {   // the map, reached from a light-sampling vertex: p_b^2 / (p_b^2 + p_l^2)
+            const unsigned long long ti = env_texel(sc.env, dir);
+            const float4 c = reinterpret_cast<const float4 *>(sc.env.hdr)[ti];
+            const float s_ = fdiv(ed->p_env * ed->dens[ti], ls->pb_in);
+            rad = carried(fdiv(1.f, 1.f + s_ * s_) * mk(c.x, c.y, c.z));
         } else rad = carried(env_sample(sc.env, dir));
         PH_ADD(1);
     } else {
@@ -3289,16 +3324,32 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
                 const V3 n_b = mkind == 0 ? h.normal : mk(0.f, 0.f, 0.f);      // (Isotropic: n + u with n = 0)
                 ls->pb_out = scatter_pdf(n_b, normalized(nr.d));
                 const uint4 lu = draw(key, P_LIGHT, segment, 0);
-                const uint32_t li = min((uint32_t)(u2f(lu.x) * (float)sh->lt.n), sh->lt.n - 1u);
-                const uint32_t lobj = sh->lt.obj[li];
-                const Obj lo = load_obj(objp, lobj);
-                V3 d, p_obj;
-                const float pl = sh->lt.p_pick * light_sample(lo, h.point, u2f(lu.y), u2f(lu.z), d, p_obj);
-                const float pb = pl > 0.f ? scatter_pdf(n_b, normalized(d)) : 0.f;
-                if (pb > 0.f) {
-                    const float r_ = fdiv(pb, pl);                             // f cos / p_l * p_l^2 / (p_l^2 + p_b^2) = albedo * r / (1 + r^2)
-                    const V3 c = (beta * atten) * light_emit<CHEAP_ONLY>(sc, matp, texp, lo, p_obj) * fdiv(r_, 1.f + r_ * r_);
-                    if (c.x > 0.f || c.y > 0.f || c.z > 0.f) { ls->shadow = true; ls->sray = Ray{h.point, d}; ls->sobj = lobj; ls->pending = c; }
+                if (ENV && u2f(lu.x) < ed->p_env) {                            // the environment: visible iff the shadow ray misses
+                    uint32_t t_drawn;
+                    const V3 d = env_dist_sample(*ed, draw(key, P_LIGHT, segment, 1), t_drawn);
+                    const unsigned long long ti = env_texel(sc.env, d);
+                    const float pl = ed->p_env * ed->dens[ti];
+                    const float pb = pl > 0.f ? scatter_pdf(n_b, d) : 0.f;
+                    if (pb > 0.f) {
+                        const float r_ = fdiv(pb, pl);
+                        const float4 e = reinterpret_cast<const float4 *>(sc.env.hdr)[ti];
+                        const V3 c = (beta * atten) * mk(e.x, e.y, e.z) * fdiv(r_, 1.f + r_ * r_);
+                        if (c.x > 0.f || c.y > 0.f || c.z > 0.f) { ls->shadow = true; ls->sray = Ray{h.point, d}; ls->sobj = MISS; ls->pending = c; }
+                    }
+                } else {
+                    // (with the environment in the set the emitters share the rest of [0, 1): (xi - p_env) / (1 - p_env) picks among them)
+                    const float xi = ENV ? fdiv(u2f(lu.x) - ed->p_env, 1.f - ed->p_env) : u2f(lu.x);
+                    const uint32_t li = min((uint32_t)(xi * (float)sh->lt.n), sh->lt.n - 1u);
+                    const uint32_t lobj = sh->lt.obj[li];
+                    const Obj lo = load_obj(objp, lobj);
+                    V3 d, p_obj;
+                    const float pl = sh->lt.p_pick * light_sample(lo, h.point, u2f(lu.y), u2f(lu.z), d, p_obj);
+                    const float pb = pl > 0.f ? scatter_pdf(n_b, normalized(d)) : 0.f;
+                    if (pb > 0.f) {
+                        const float r_ = fdiv(pb, pl);                             // f cos / p_l * p_l^2 / (p_l^2 + p_b^2) = albedo * r / (1 + r^2)
+                        const V3 c = (beta * atten) * light_emit<CHEAP_ONLY>(sc, matp, texp, lo, p_obj) * fdiv(r_, 1.f + r_ * r_);
+                        if (c.x > 0.f || c.y > 0.f || c.z > 0.f) { ls->shadow = true; ls->sray = Ray{h.point, d}; ls->sobj = lobj; ls->pending = c; }
+                    }
                 }
             }
             if (CHAIN) nchain = chain | (o.material << (f.chain_bits * (uint32_t)segment));   // atten IS the material's constant (host: chain_bits)
@@ -3588,6 +3639,77 @@ __global__ __launch_bounds__(WB) void k_shade_ls(DScene sc, DFrame f, DPaths in,
     }
     if (lane == 0) { q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n; sh.wcount[(size_t)(segment + 1) * q.n_waves + w] = sh_n; }
 }
+// Environment sampling: k_shade_ls with the environment among the sampled lights (*ed), in shading mode 0 only (an HDR map is an
+// expensive case: the scene never takes mode 1).  A copy of k_shade_ls's body rather than a template parameter of it: with a shared body
+// k_shade_ls's instruction stream and SGPR spills changed, and §9g's kernels stay as they are.
+template <int LDS_TAB>
+__attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
+__global__ __launch_bounds__(WB) void k_shade_env(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
+                                                     float4 *__restrict__ sample_rad, DQueue q, int segment,
+                                                     uint32_t n_mat, uint32_t n_tex, DShadow sh, DEnvDist ed) {
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    const float4 *objp = sc.obj, *matp = sc.mat, *texp = sc.tex;
+    if (sc.has_perlin) { stage_perm(); if (!LDS_TAB) __syncthreads(); }
+    if (LDS_TAB) {
+        const uint32_t no = LDS_TAB == 1 ? sc.n_objects * OBJ_Q : 0u, nm = 2 * n_mat, nt = 2 * n_tex;
+        if (LDS_TAB == 1) for (uint32_t k = threadIdx.x; k < no; k += WB) lds_tables[k] = sc.obj[k];
+        for (uint32_t k = threadIdx.x; k < nm; k += WB) lds_tables[no + k] = sc.mat[k];
+        for (uint32_t k = threadIdx.x; k < nt; k += WB) lds_tables[no + nm + k] = sc.tex[k];
+        __syncthreads();
+        if (LDS_TAB == 1) objp = lds_tables;
+        matp = lds_tables + no; texp = lds_tables + no + nm;
+    }
+    if (w >= q.n_waves) return;
+    const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
+    const uint32_t base = w * q.cap;
+    uint32_t out_n = 0, sh_n = 0;                                        // survivors / shadow rays written so far (wave-uniform)
+    PH_DECL;
+    float4 ra_n = make_float4(0, 0, 0, 0), st_n = ra_n; float2 rb_n = make_float2(0, 0), hr_n = rb_n; float pb_n = 0.f;
+    auto fetch = [&](uint32_t i) {
+        ra_n = qld(&in.ray_a[i]); rb_n = load_ray_b(in, i, f, segment); st_n = load_state(in, i, segment); hr_n = qld(&hits[i]);
+        pb_n = segment > 0 ? sh.pb_in[i] : 0.f;
+    };
+    if (lane < n) fetch(base + lane);
+    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
+        const uint32_t j = c0 + lane, i = base + j;
+        float4 ra = ra_n, st = st_n; float2 rb = rb_n, hr = hr_n;
+        LsIO ls{pb_n, 0.f, false, Ray{mk(0, 0, 0), mk(0, 0, 0)}, 0u, mk(0, 0, 0)};
+        if (j + 64u < n) fetch(i + 64u);
+        bool alive = false;
+        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
+        if (j < n) {
+            path_id = __float_as_uint(st.w);
+            alive = shade_path<false, false, true, true>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id, hr.x,
+                                                            __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS, nullptr, &sh, &ls, &ed);
+        }
+        // k_shade's compaction, with p_b next to the state
+        const unsigned long long mask = __ballot(alive);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (alive) {
+            const uint32_t dst = base + out_n + rank;
+            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
+            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
+            qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
+            sh.pb_out[dst] = ls.pb_out;
+        }
+        if (f.ex.mode) flag_exact(f.ex, alive && needs_exact(f.ex, nr.o.x, nr.o.y, nr.o.z, nr.d.x, nr.d.y, nr.d.z), base + out_n + rank, segment + 1);
+        out_n += (uint32_t)__popcll(mask);
+        // the shadow rays: the same compaction, into the wave's region of the shadow queue
+        const unsigned long long sm = __ballot(ls.shadow);
+        if (sm) {
+            const uint32_t sr = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+            if (ls.shadow) {
+                const uint32_t d = base + sh_n + sr;
+                sh.ray_a[d] = make_float4(ls.sray.o.x, ls.sray.o.y, ls.sray.o.z, ls.sray.d.x);
+                sh.ray_b[d] = make_float2(ls.sray.d.y, ls.sray.d.z);
+                sh.state[d] = make_float4(ls.pending.x, ls.pending.y, ls.pending.z, __uint_as_float(path_id));
+                sh.obj[d] = ls.sobj;
+            }
+            sh_n += (uint32_t)__popcll(sm);
+        }
+    }
+    if (lane == 0) { q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n; sh.wcount[(size_t)(segment + 1) * q.n_waves + w] = sh_n; }
+}
 // One segment's shadow rays after their walk: a ray whose closest hit is the light it sampled adds its pending radiance to the path's
 // nee record.  One shadow ray per path and segment, segments in stream order: no atomics.
 __global__ __launch_bounds__(WB) void k_shadow_resolve(DShadow sh, const float2 *__restrict__ hits, DQueue q, int segment, uint32_t prim_bits) {
@@ -3601,6 +3723,99 @@ __global__ __launch_bounds__(WB) void k_shadow_resolve(DShadow sh, const float2 
         float4 &e = sh.nee[__float_as_uint(p.w)];
         e = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, 0.f);
     }
+}
+// The same with environment shadow rays in the queue (k_shade_env): their sh.obj is MISS, and they are visible iff they miss.
+__global__ __launch_bounds__(WB) void k_shadow_resolve_env(DShadow sh, const float2 *__restrict__ hits, DQueue q, int segment, uint32_t prim_bits) {
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    if (w >= q.n_waves) return;
+    const uint32_t n = sh.wcount[(size_t)(segment + 1) * q.n_waves + w], base = w * q.cap;
+    for (uint32_t j = lane; j < n; j += 64u) {
+        const uint32_t i = base + j, code = __float_as_uint(hits[i].y);
+        if ((code == MISS ? MISS : code >> prim_bits) != sh.obj[i]) continue;
+        const float4 p = sh.state[i];
+        float4 &e = sh.nee[__float_as_uint(p.w)];
+        e = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, 0.f);
+    }
+}
+
+// The environment's table, built once per scene: k_env_rows (one block per row: the texels' weights, the row's scan in double,
+// its conditional CDF), k_env_marg (one block: the scan of the row totals, the marginal CDF, the total), k_env_dens (per texel: p and p / Omega).
+// Every sum is taken in a fixed order (sequential runs per thread, wave scans, waves in order) and no atomics: two builds are equal bit for bit.
+constexpr uint32_t ENV_BUILD_THREADS = 256;
+// max(r, g, b) of texel i, with negative and non-finite channels counted as 0
+__device__ __forceinline__ double env_lum(const DEnv &e, size_t i) {
+    const float4 c = reinterpret_cast<const float4 *>(e.hdr)[i];
+    auto ok = [](float v) { return (v > 0.f && v <= 3.402823466e38f) ? v : 0.f; };
+    return (double)fmaxf(fmaxf(ok(c.x), ok(c.y)), ok(c.z));
+}
+// exclusive prefix of v over the block (ENV_BUILD_THREADS threads, waves in order), sums in double
+__device__ __forceinline__ double block_excl_scan(double v, double *wsum) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    double s = v;
+    for (uint32_t o = 1; o < 64u; o <<= 1) { const double t = __shfl_up(s, o, 64); if (lane >= o) s = s + t; }
+    double ex = __shfl_up(s, 1u, 64);
+    if (lane == 0) ex = 0.0;
+    if (lane == 63u) wsum[wv] = s;
+    __syncthreads();
+    double off = 0.0;
+    for (uint32_t k = 0; k < wv; k++) off = off + wsum[k];
+    return off + ex;
+}
+// One row's weights (p_row = sum of max(rgb) Omega_row) and conditional CDF; the thread that owns the row's last texel writes the total, so that
+// the last entry is total / total = 1 exactly.  scratch: row totals [0, h), the total [h], Omega_row [h + 1, 2h + 1).
+__global__ __launch_bounds__(ENV_BUILD_THREADS) void k_env_rows(DEnv e, float *__restrict__ cdf_c, double *__restrict__ scratch) {
+    __shared__ double wsum[ENV_BUILD_THREADS / 64];
+    __shared__ double row_total;
+    const uint32_t y = blockIdx.x, w = e.hdr_w, h = e.hdr_h, per = (w + ENV_BUILD_THREADS - 1) / ENV_BUILD_THREADS;
+    const uint32_t x0 = min(threadIdx.x * per, w), x1 = min(x0 + per, w);
+    const double omega = (2.0 * M_PI / (double)w) * (cospi((double)y / (double)h) - cospi((double)(y + 1u) / (double)h));
+    const size_t row = (size_t)y * w;
+    double run = 0.0;
+    for (uint32_t x = x0; x < x1; x++) run = run + env_lum(e, row + x) * omega;
+    const double base = block_excl_scan(run, wsum);
+    if (x0 < x1 && x1 == w) { row_total = base + run; scratch[y] = base + run; scratch[h + 1u + y] = omega; }
+    __syncthreads();
+    const double tot = row_total;
+    double pre = base;
+    for (uint32_t x = x0; x < x1; x++) {
+        pre = pre + env_lum(e, row + x) * omega;
+        cdf_c[row + x] = tot > 0.0 ? (float)(pre / tot) : 0.f;
+    }
+}
+__global__ __launch_bounds__(ENV_BUILD_THREADS) void k_env_marg(uint32_t h, float *__restrict__ cdf_m, double *__restrict__ scratch) {
+    __shared__ double wsum[ENV_BUILD_THREADS / 64];
+    __shared__ double all;
+    const uint32_t per = (h + ENV_BUILD_THREADS - 1) / ENV_BUILD_THREADS, y0 = min(threadIdx.x * per, h), y1 = min(y0 + per, h);
+    double run = 0.0;
+    for (uint32_t y = y0; y < y1; y++) run = run + scratch[y];
+    const double base = block_excl_scan(run, wsum);
+    if (y0 < y1 && y1 == h) { all = base + run; scratch[h] = base + run; }
+    __syncthreads();
+    const double tot = all;
+    double pre = base;
+    for (uint32_t y = y0; y < y1; y++) {
+        pre = pre + scratch[y];
+        cdf_m[y] = tot > 0.0 ? (float)(pre / tot) : 0.f;
+    }
+}
+__global__ __launch_bounds__(ENV_BUILD_THREADS) void k_env_dens(DEnv e, float *__restrict__ dens, float *__restrict__ p_out, const double *__restrict__ scratch) {
+    const size_t n = (size_t)e.hdr_w * e.hdr_h, i = (size_t)blockIdx.x * ENV_BUILD_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t y = (uint32_t)(i / e.hdr_w);
+    const double tot = scratch[e.hdr_h], omega = scratch[e.hdr_h + 1u + y];
+    const double p = tot > 0.0 ? env_lum(e, i) * omega / tot : 0.0;
+    dens[i] = (float)(p / omega);
+    if (p_out) p_out[i] = (float)p;
+}
+// fw_selftest_env_sample: sample i takes draw({i, 0, seed32}, P_LIGHT, 0, 1), as a vertex of segment 0 of pixel i would
+__global__ __launch_bounds__(WB) void k_env_sample_test(DEnv e, DEnvDist ed, uint32_t n, uint32_t seed32, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * WB + threadIdx.x;
+    if (i >= n) return;
+    uint32_t t;
+    const V3 d = env_dist_sample(ed, draw(RngKey{i, 0u, seed32}, P_LIGHT, 0, 1), t);
+    const unsigned long long ti = env_texel(e, d);
+    float *o = out + (size_t)i * FW_ENV_SAMPLE_FLOATS;
+    o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = ed.dens[ti]; o[4] = (float)t; o[5] = (float)ti;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4327,6 +4542,34 @@ void launch_shade_ls(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPat
 }
 void launch_shadow_resolve(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment) {
     hipLaunchKernelGGL(k_shadow_resolve, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
+}
+void launch_shade_env(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
+                      float4 *sample_rad, int segment, const DShadow &sh, const DEnvDist &ed) {
+    // (launch_shade_ls's table modes)
+    const size_t tab = ((size_t)sc.n_objects * OBJ_Q + 2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
+    const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
+    const int lt = (c.lds_tables && tab <= LDS_TABLE_LIMIT) ? 1 : ((c.lds_tables && tab_mt <= LDS_TABLE_LIMIT) ? 2 : 0);
+    const size_t lds = lt == 1 ? tab : (lt == 2 ? tab_mt : 0);
+#define FW_SHADE_ENV(L) hipLaunchKernelGGL((k_shade_env<L>), wave_grid(c), dim3(WB), lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, sh, ed)
+    if (lt == 1) FW_SHADE_ENV(1); else if (lt == 2) FW_SHADE_ENV(2); else FW_SHADE_ENV(0);
+#undef FW_SHADE_ENV
+}
+void launch_shadow_resolve_env(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment) {
+    hipLaunchKernelGGL(k_shadow_resolve_env, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
+}
+int build_env_dist(hipStream_t stream, const DEnv &env, float *cdf_m, float *cdf_c, float *dens, float *p_out, double *scratch, double *total) {
+    const size_t n = (size_t)env.hdr_w * env.hdr_h;
+    hipLaunchKernelGGL(k_env_rows, dim3(env.hdr_h), dim3(ENV_BUILD_THREADS), 0, stream, env, cdf_c, scratch);
+    hipLaunchKernelGGL(k_env_marg, dim3(1), dim3(ENV_BUILD_THREADS), 0, stream, env.hdr_h, cdf_m, scratch);
+    hipLaunchKernelGGL(k_env_dens, dim3((unsigned)((n + ENV_BUILD_THREADS - 1) / ENV_BUILD_THREADS)), dim3(ENV_BUILD_THREADS), 0, stream, env, dens, p_out,
+                       (const double *)scratch);
+    if (hipGetLastError() != hipSuccess) return FW_ERR_HIP;
+    if (hipMemcpyAsync(total, scratch + env.hdr_h, sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess) return FW_ERR_HIP;
+    if (hipStreamSynchronize(stream) != hipSuccess) return FW_ERR_HIP;
+    return FW_OK;
+}
+void launch_env_sample_test(hipStream_t stream, const DEnv &env, const DEnvDist &ed, uint32_t n, uint32_t seed32, float *out) {
+    hipLaunchKernelGGL(k_env_sample_test, dim3((n + WB - 1) / WB), dim3(WB), 0, stream, env, ed, n, seed32, out);
 }
 #if FW_AB
 void launch_bounce(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, float4 *sample_rad,

@@ -967,10 +967,16 @@ struct fw_scene {
     DevBuf lights;                // the sampled lights' object indices (fw::DLights.obj; FW_FLAG_LIGHT_SAMPLING)
     uint32_t n_lights = 0;
     bool ls_vertices = false;     // some material is Lambertian or Isotropic: a vertex that samples lights can occur
+    // the HDR map's sampling table (fw::DEnvDist: cdf_m, cdf_c, dens; FW_FLAG_ENV_SAMPLING), built on the device by the first
+    // render that needs it and kept for the scene's life (fw_scene_update never changes the environment)
+    DevBuf env_dist;
+    int env_state = 0;            // 0: not built; 1: built, positive total weight (the map is a sampled light); 2: built, nothing to sample
+    double env_build_ms = 0;
     ~fw_scene() {
         data.release();
         obj_data.release();
         lights.release();
+        env_dist.release();
     }
 };
 
@@ -1861,9 +1867,12 @@ int update_scene_impl(fw_scene *sc, const fw_scene_desc *desc) {
         const auto t0 = now();
         fw_scene *ns = nullptr;
         if (int rc = create_scene_impl(desc, sc->device, &ns, &reach)) return rc;
-        DevBuf old_data = sc->data, old_obj = sc->obj_data, old_lights = sc->lights;
+        DevBuf old_data = sc->data, old_obj = sc->obj_data, old_lights = sc->lights, kept_env = sc->env_dist;
+        const int kept_env_state = sc->env_state; const double kept_env_ms = sc->env_build_ms;
         *sc = *ns;                                     // (the handle stays the caller's; its DevBufs now name the new allocations)
         ns->data = old_data; ns->obj_data = old_obj; ns->lights = old_lights;   // ... and the old ones go with `ns`
+        // (the environment's table stays: the map is the same)
+        ns->env_dist = sc->env_dist; sc->env_dist = kept_env; sc->env_state = kept_env_state; sc->env_build_ms = kept_env_ms;
         fw_scene_destroy(ns);
         if (O.trace) fprintf(stderr, "[firework] scene_update: %u objects, TLAS build %.2f ms host, %.2f ms device, %u meshes rebuilt, %zu B uploaded, %u hoisted (scene re-created: the reach of %u meshes rose; %.2f ms)\n",
                              desc->n_objects, sc->ms_objects, sc->ms_objects_dev, n_meshes, sc->blob_bytes, sc->d.n_hoisted, raised, ms_since(t0));
@@ -1976,6 +1985,44 @@ void set_walk_cfg(fw::LaunchCfg &cfg, const fw_scene *sc, const Options &O, cons
 static bool light_sampling(const fw_scene *sc, const fw_render_params *p) {
     return (p->flags & FW_FLAG_LIGHT_SAMPLING) != 0 && sc->n_lights > 0 && sc->ls_vertices;
 }
+// ---- environment sampling -------------------------------------------------------------------------------------------
+// The table of an HDR map on the current device: buf = cdf_m (h floats), cdf_c (w h), dens (w h); p_out (optional, device): the per-texel
+// probabilities; total = the map's total weight.
+static int build_env_table(const fw::DEnv &env, DevBuf &buf, float *p_out, double &total, hipEvent_t after = nullptr) {
+    const size_t n = (size_t)env.hdr_w * env.hdr_h;
+    if (int rc = buf.alloc((env.hdr_h + 2 * n) * 4)) return rc;
+    DevBuf scratch;
+    if (int rc = scratch.alloc((2 * (size_t)env.hdr_h + 1) * 8)) return rc;
+    float *base = (float *)buf.p;
+    if (after && hipStreamWaitEvent(nullptr, after, 0) != hipSuccess) { scratch.release(); return fail(FW_ERR_HIP, "hipStreamWaitEvent failed"); }
+    const int rc = fw::build_env_dist(nullptr, env, base, base + env.hdr_h, base + env.hdr_h + n, p_out, (double *)scratch.p, &total);
+    scratch.release();
+    return rc ? fail(rc, "environment table build failed") : FW_OK;
+}
+static fw::DEnvDist env_dist_of(const DevBuf &buf, const fw::DEnv &env, float p_env) {
+    const float *base = (const float *)buf.p;
+    const size_t n = (size_t)env.hdr_w * env.hdr_h;
+    return fw::DEnvDist{base, base + env.hdr_h, base + env.hdr_h + n, p_env, env.hdr_w, env.hdr_h};
+}
+// The table, at the first render whose flags ask for it (the caller has set the scene's device and holds the workspace's lock).  The build
+// waits for the scene's upload (ws->ev_upload: the map is copied to the device on the upload stream).  A map of 2^32 texels or more (the
+// sampler's texel index is 32-bit) is not sampled.
+static int ensure_env_dist(fw_scene *sc, const fw_render_params *p, const Workspace *ws) {
+    if (!(p->flags & FW_FLAG_ENV_SAMPLING) || sc->d.env.kind != FW_ENV_HDR || !sc->ls_vertices || sc->env_state != 0) return FW_OK;
+    if ((uint64_t)sc->d.env.hdr_w * sc->d.env.hdr_h > 0xffffffffull) { sc->env_state = 2; return FW_OK; }
+    const auto t0 = std::chrono::steady_clock::now();
+    double total = 0;
+    if (int rc = build_env_table(sc->d.env, sc->env_dist, nullptr, total, ws->ev_upload)) return rc;
+    sc->env_state = total > 0 ? 1 : 2;
+    sc->env_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (options().trace) fprintf(stderr, "[firework] environment table: %u x %u texels, total weight %.6g, %.2f ms\n", sc->d.env.hdr_w, sc->d.env.hdr_h, total, sc->env_build_ms);
+    return FW_OK;
+}
+// FW_FLAG_ENV_SAMPLING takes effect where the environment is an HDR map of positive total weight and a material's vertices
+// sample lights; otherwise the frame is the frame without the flag (ensure_env_dist has run)
+static bool env_sampling(const fw_scene *sc, const fw_render_params *p) {
+    return (p->flags & FW_FLAG_ENV_SAMPLING) != 0 && sc->env_state == 1 && sc->ls_vertices;
+}
 // render_impl's lanes (batches in flight) and paths per batch and lane for `p` (fw_render_views sizes its view groups by the same budget)
 struct BatchBudget { int n_lanes; bool exact_product; uint32_t budget; };
 BatchBudget batch_budget(const fw_scene *sc, const fw_render_params *p, const Options &O, size_t arena_bytes) {
@@ -1984,8 +2031,8 @@ BatchBudget batch_budget(const fw_scene *sc, const fw_render_params *p, const Op
     n_lanes = (int)std::min<uint32_t>((uint32_t)n_lanes, p->samples);
     // EXACT_PRODUCT: 160 more bytes per slot (ten attenuation records) where the scene has no chain state: half the default batch
     const bool exact_product = O.exact_product && (sc->chain_bits == 0 || O.no_chain);
-    // light sampling: 92 more bytes per slot (fw::DShadow) — half the default batch as well
-    const bool ls = light_sampling(sc, p);
+    // light sampling: 92 more bytes per slot (fw::DShadow) — half the default batch as well (and so with environment sampling)
+    const bool ls = light_sampling(sc, p) || env_sampling(sc, p);
     const uint32_t budget = p->paths_per_batch ? p->paths_per_batch : default_paths_per_batch(O, arena_bytes) / (uint32_t)n_lanes / (exact_product || ls ? 2u : 1u);
     return BatchBudget{n_lanes, exact_product, budget};
 }
@@ -2035,6 +2082,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     std::unique_lock<std::mutex> ws_guard(ws->mu, std::defer_lock);
     if (!rd) ws_guard.lock();                                                        // (an adaptive round's caller holds it)
     { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }     // after fw_release_workspace, or a scene made before it
+    if (int erc = ensure_env_dist(sc, p, ws)) return erc;
     const Options O = options();
 
     // ---- batches and lanes -----------------------------------------------------------------------------------
@@ -2054,8 +2102,10 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     const BatchBudget bb = batch_budget(sc, p, O, ws->arena.bytes);
     int n_lanes = bb.n_lanes;
     // light sampling: a path deposits its visible light samples with its own end, so the frame keeps the running product (no
-    // chain state, no EXACT_PRODUCT records), deposits every path (no elided zeros) and keeps t in its hit records (no hit4)
-    const bool ls = light_sampling(sc, p);
+    // chain state, no EXACT_PRODUCT records), deposits every path (no elided zeros) and keeps t in its hit records (no hit4).  Environment
+    // sampling (§9h) takes the same frame: ls = either; es = the environment is among the sampled lights (k_shade_env)
+    const bool ls_lights = light_sampling(sc, p), es = env_sampling(sc, p);
+    const bool ls = ls_lights || es;
     const bool exact_product = bb.exact_product && !ls;
     const uint32_t budget = bb.budget;
     uint32_t spp_b = std::max<uint32_t>(1u, budget / n_pix);
@@ -2304,7 +2354,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // extend always runs beside the other batch's memory-bound shade (left alone, the two lanes drift INTO phase within three segments:
     // profiles/r05a_share_trace.txt).
     struct BatchCtx { fw::DFrame fr; fw::LaunchCfg cfg; fw::DPaths buf[2]; float2 *hits; float4 *srad; fw::DPark park; uint32_t *totals; uint32_t n_paths; int cur; int lane; hipStream_t ls;
-                      fw::DShadow sh; };
+                      fw::DShadow sh; fw::DEnvDist ed; };
     // Measured (profiles/r05j_phase_lock.txt, three interleaved pairs): cornell 33.4-33.8 -> 32.2-32.4 ms — the lock holds the frame in the faster
     // of the two phases it otherwise lands in by chance (profiles/r05h_layout_pad.txt) —, where extend and shade last about as long as each
     // other.  Under use_bvh an extend lasts three shades and waiting for the other batch's costs: suzanne 62.7 -> 67.7, part2 @256 119.6 ->
@@ -2343,9 +2393,13 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         c.park = fw::DPark{(float4 *)L.park_a, (float2 *)L.park_b, (float4 *)L.park_m, q.cap + 64u, (uint32_t *)L.pcount,
                            park_meshes ? (uint32_t *)L.pcount + q.n_waves : nullptr};
         if (park_meshes) HIPCHK(hipMemsetAsync(c.park.ptotal, 0, (size_t)q.n_waves * 4, c.ls));
-        c.sh = fw::DShadow{};
+        c.sh = fw::DShadow{}; c.ed = fw::DEnvDist{};
         if (ls) {
-            c.sh.lt = fw::DLights{(const uint32_t *)sc->lights.p, sc->n_lights, 1.f / (float)sc->n_lights};
+            // picking a light: the environment with p_env (1 alone, 1/2 beside emitters), each emitter with (1 - p_env) / n
+            const float p_env = es ? (ls_lights ? 0.5f : 1.f) : 0.f;
+            c.sh.lt = ls_lights ? fw::DLights{(const uint32_t *)sc->lights.p, sc->n_lights, es ? (1.f - p_env) / (float)sc->n_lights : 1.f / (float)sc->n_lights}
+                                : fw::DLights{(const uint32_t *)sc->lights.p, 0u, 0.f};
+            if (es) c.ed = env_dist_of(sc->env_dist, sc->d.env, p_env);
             c.sh.ray_a = (float4 *)L.s_ray_a; c.sh.ray_b = (float2 *)L.s_ray_b; c.sh.state = (float4 *)L.s_state; c.sh.obj = (uint32_t *)L.s_obj;
             c.sh.wcount = (uint32_t *)L.s_wcount; c.sh.nee = (float4 *)L.nee;
             HIPCHK(hipMemsetAsync(c.sh.nee, 0, (size_t)cap * 16, c.ls));
@@ -2386,13 +2440,15 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         if (ls) {
             Workspace::Lane &L = ws->lanes[c.lane];
             c.sh.pb_in = (const float *)L.pb[c.cur]; c.sh.pb_out = (float *)L.pb[c.cur ^ 1];
-            timed(c, 2, [&] { fw::launch_shade_ls(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh); });
+            if (es) timed(c, 2, [&] { fw::launch_shade_env(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, c.ed); });
+            else timed(c, 2, [&] { fw::launch_shade_ls(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh); });
             if (seg < fw::MAX_SEGMENTS - 1) {     // segments 0-9 scatter (render.rs:21): their shadow rays through the ordinary walks, then the resolve
                 fw::LaunchCfg scfg = c.cfg; scfg.q.wcount = c.sh.wcount;
                 fw::DFrame sfr = c.fr; sfr.seed32 ^= fw::SHADOW_SEED; sfr.ex.mode = 0;
                 const fw::DPaths sp{c.sh.ray_a, c.sh.ray_b, c.sh.state};
                 timed(c, 1, [&] { fw::launch_extend(scfg, sc->d, sfr, sp, (float2 *)L.s_hits, seg + 1, use_bvh, c.park); });
-                timed(c, 2, [&] { fw::launch_shadow_resolve(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
+                if (es) timed(c, 2, [&] { fw::launch_shadow_resolve_env(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
+                else timed(c, 2, [&] { fw::launch_shadow_resolve(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
             }
         } else
         timed(c, 2, [&] { fw::launch_shade(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg); });
@@ -2764,6 +2820,7 @@ int views_impl(fw_scene *sc, const fw_render_params *p, const fw_camera_settings
     {
         std::lock_guard<std::mutex> ws_guard(ws->mu);
         { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }
+        if (int erc = ensure_env_dist(sc, p, ws)) return erc;
         budget = batch_budget(sc, p, options(), ws->arena.bytes).budget;
     }
     const uint32_t per_group = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)n_views, budget / N, VIEW_GROUP_MAX_PIXELS / N}));
@@ -3341,6 +3398,57 @@ int fw_selftest_lights(const fw_scene_desc *desc, float *out, uint32_t cap, uint
             r[14] = L[i].area; r[15] = L[i].p_pick;
         }
         return FW_OK;
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+}
+
+// Diagnostics: the environment table of a caller's w x h RGB map built on GPU `device` as a render builds it, and n samples of it
+// as k_shade_env draws them.  EnvTest holds the map (16-byte texels, as a scene uploads it) and the table.
+struct EnvTest {
+    DevBuf map, dist, p;          // p: the per-texel probabilities (with_p)
+    fw::DEnv env{}; double total = 0;
+    int make(int device, const float *rgb, uint32_t w, uint32_t h, bool with_p) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible"); }
+        if (device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+        HIPCHK(hipSetDevice(device));
+        const size_t n = (size_t)w * h;
+        std::vector<float> px(n * 4, 0.f);
+        for (size_t k = 0; k < n; k++) { px[4 * k] = rgb[3 * k]; px[4 * k + 1] = rgb[3 * k + 1]; px[4 * k + 2] = rgb[3 * k + 2]; }
+        if (int rc = map.upload(px.data(), px.size() * 4)) return rc;
+        if (with_p) if (int rc = p.alloc(n * 4)) return rc;
+        env.kind = FW_ENV_HDR; env.hdr = (const float *)map.p; env.hdr_w = w; env.hdr_h = h;
+        return build_env_table(env, dist, with_p ? (float *)p.p : nullptr, total);
+    }
+    ~EnvTest() { map.release(); dist.release(); p.release(); }
+};
+static bool env_test_args(int device, const float *rgb, uint32_t w, uint32_t h) {
+    return device >= 0 && rgb && w > 0 && h > 0 && (uint64_t)w * h <= (1ull << 24);
+}
+int fw_selftest_env_dist(int device, const float *rgb, uint32_t w, uint32_t h, float *p, double *total) {
+    if (!env_test_args(device, rgb, w, h) || !p || !total) return fail(FW_ERR_BAD_ARG, "bad argument");
+    try {
+        EnvTest t;
+        if (int rc = t.make(device, rgb, w, h, true)) return rc;
+        if (hipMemcpy(p, t.p.p, (size_t)w * h * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(FW_ERR_HIP, "copy failed");
+        *total = t.total;
+        return FW_OK;
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+}
+int fw_selftest_env_sample(int device, const float *rgb, uint32_t w, uint32_t h, uint32_t n, uint32_t seed, float *out) {
+    if (!env_test_args(device, rgb, w, h) || n == 0 || n > (1u << 26) || !out) return fail(FW_ERR_BAD_ARG, "bad argument");
+    try {
+        EnvTest t;
+        if (int rc = t.make(device, rgb, w, h, false)) return rc;
+        if (!(t.total > 0)) return fail(FW_ERR_BAD_ARG, "the map has no positive weight");
+        DevBuf o;
+        if (int rc = o.alloc((size_t)n * FW_ENV_SAMPLE_FLOATS * 4)) return rc;
+        fw::launch_env_sample_test(nullptr, t.env, env_dist_of(t.dist, t.env, 1.f), n, seed, (float *)o.p);
+        int rc = FW_OK;
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, o.p, (size_t)n * FW_ENV_SAMPLE_FLOATS * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(FW_ERR_HIP, "sampling failed");
+        o.release();
+        return rc;
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
 }

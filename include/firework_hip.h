@@ -216,6 +216,14 @@ typedef struct fw_render_params {
                                      fw_render_scene, fw_render_scene_tiled, fw_render_rays, fw_render_views and fw_render_adaptive (their
                                      frames go through the same path); ignored by fw_render_aovs (first-hit values carry no lighting).
                                      A build without it ignores the bit and renders the default frame. */
+#define FW_FLAG_ENV_SAMPLING 8u   /* importance sampling of an HDR environment map: the map joins the sampled lights of
+                                     FW_FLAG_LIGHT_SAMPLING (p_env = 1 alone, 1/2 beside the emitters, each emitter (1 - p_env) / n),
+                                     sampled in proportion to max(r, g, b) x the solid angle of the texel env lookup returns, through a
+                                     shadow ray that counts where it misses, with the same MIS weights.  The same pixels in expectation, with
+                                     less noise under a bright sun; paths and shadow-ray accounting as FW_FLAG_LIGHT_SAMPLING.  The table is
+                                     built on the device at the first render that asks for it and kept with the scene.  Nothing to sample (a
+                                     ColorEnv or SkyEnv, a map of zero total weight, no Lambertian or Isotropic material): the frame without
+                                     the bit, bit for bit.  Honoured and ignored by the same entry points as FW_FLAG_LIGHT_SAMPLING. */
 
 #define FW_MAX_SEGMENTS 11  /* depths 0..10: render.rs:21 */
 
@@ -585,6 +593,16 @@ int fw_selftest_bvh_trees(int device, const float *boxes, uint32_t n, float *ref
    desc or n, out = NULL with cap > 0). */
 #define FW_LIGHT_RECORD_FLOATS 16
 int fw_selftest_lights(const fw_scene_desc *desc, float *out, uint32_t cap, uint32_t *n);
+
+/* Diagnostics (GPU): the FW_FLAG_ENV_SAMPLING table of a caller's w x h map (rgb: w h x 3 floats, row-major from the top row, as
+   fw_environment.hdr_rgb), built on `device` as a render builds it.  fw_selftest_env_dist: p = the w h per-texel probabilities (float32 of
+   the float64 table), *total = the total weight sum(max(r, g, b) x Omega_row).  fw_selftest_env_sample: n samples drawn as a segment-0
+   vertex of pixel i with seed32 = seed would draw them, FW_ENV_SAMPLE_FLOATS floats each: the direction (xyz), the reported density (per
+   steradian, of the texel the direction looks up), the drawn texel's index and the looked-up texel's index.  Errors: FW_ERR_BAD_ARG (null
+   pointers, w h = 0 or above 2^24, n = 0 or above 2^26, for sampling a map of zero total weight), FW_ERR_NO_DEVICE, FW_ERR_HIP. */
+#define FW_ENV_SAMPLE_FLOATS 6
+int fw_selftest_env_dist(int device, const float *rgb, uint32_t w, uint32_t h, float *p, double *total);
+int fw_selftest_env_sample(int device, const float *rgb, uint32_t w, uint32_t h, uint32_t n, uint32_t seed, float *out);
 
 #ifdef __cplusplus
 }
