@@ -17,7 +17,8 @@ back as an HDR environment with the same orientation; orthographic: the fixed vi
 --ortho-height H high, by default the height the fixed view sees at its look-at point; both rendered through caller-supplied rays, not
 with --orbit / --adaptive / --denoise / --progressive / --checkpoint), --light-sampling (sample the lights directly at diffuse vertices:
 next-event estimation with MIS; combines with every other flag), --env-sampling (sample an HDR environment map by its
-radiance at diffuse vertices; alone or with --light-sampling, and with every other flag)."""
+radiance at diffuse vertices; alone or with --light-sampling, and with every other flag), --all-emitters (light sampling
+over every emitting primitive, meshes, disks and boxes included, picked by power; implies --light-sampling)."""
 import argparse
 import sys
 import time
@@ -47,6 +48,8 @@ def main(argv=None):
                     help="sample the scene's lights directly at diffuse vertices (next-event estimation with MIS): less noise per sample")
     ap.add_argument("--env-sampling", action="store_true",
                     help="importance-sample an HDR environment map at diffuse vertices (with --light-sampling: beside the lights)")
+    ap.add_argument("--all-emitters", action="store_true",
+                    help="light sampling over every emitting primitive (meshes, disks, boxes too), picked by power; implies --light-sampling")
     ap.add_argument("--camera", choices=("pinhole", "panorama", "orthographic"), default="pinhole",
                     help="camera model: the fixed pinhole view (default), an equirectangular panorama from its position, or an orthographic view")
     ap.add_argument("--ortho-height", type=float, default=None, metavar="H",
@@ -90,6 +93,8 @@ def main(argv=None):
     camera = CameraSettings.default().cam_pos((0.0, 30.0, 50.0)).look_at((0.0, 0.0, 0.0)).field_of_view(40.0)
     renderer = (Renderer.default().width(opt.width).height(opt.height).samples(opt.samples).use_bvh(True)
                 .camera(camera).seed(opt.seed).light_sampling(opt.light_sampling).env_sampling(opt.env_sampling))
+    if opt.all_emitters:       # bits 4 and 16: light sampling over every emitting primitive
+        renderer.light_sampling().all_emitters()
     start = time.time()
     if opt.camera != "pinhole":
         render = camera_model_render(renderer, camera, scene, opt)

@@ -31,6 +31,9 @@ FW_FLAG_LIGHT_SAMPLING = 4   # next-event estimation with MIS
 FW_LIGHT_RECORD_FLOATS = 16  # fw_selftest_lights
 FW_FLAG_ENV_SAMPLING = 8     # importance sampling of an HDR environment map
 FW_ENV_SAMPLE_FLOATS = 6     # fw_selftest_env_sample
+FW_FLAG_ALL_EMITTERS = 16    # with FW_FLAG_LIGHT_SAMPLING: every emitting primitive, picked by power
+FW_EMITTER_RECORD_FLOATS = 5  # fw_selftest_emitters
+FW_EMITTER_SAMPLE_FLOATS = 9  # fw_selftest_emitter_sample
 FW_NO_HIT = 0xFFFFFFFF   # fw_hit.object of a miss
 
 f32, i32, u32, u64 = C.c_float, C.c_int32, C.c_uint32, C.c_uint64

@@ -77,6 +77,10 @@ def load(preload=False, device=None):
     lib.fw_selftest_env_dist.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_double)]
     lib.fw_selftest_env_sample.restype = C.c_int
     lib.fw_selftest_env_sample.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.fw_selftest_emitters.restype = C.c_int
+    lib.fw_selftest_emitters.argtypes = [C.POINTER(A.fw_scene_desc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.fw_selftest_emitter_sample.restype = C.c_int
+    lib.fw_selftest_emitter_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.fw_selftest_bvh_build.restype = C.c_int
     lib.fw_selftest_bvh_build.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     lib.fw_selftest_bvh_trees.restype = C.c_int
@@ -180,6 +184,30 @@ def selftest_lights(scene_desc):
             d["corners"] = r[2:14].reshape(4, 3).astype(np.float64)
         lights.append(d)
     return lights
+
+
+def selftest_emitters(scene_desc):
+    """fw_selftest_emitters (CPU only): the entries of a SceneDesc as FW_FLAG_ALL_EMITTERS sees them.  -> dict of arrays
+    obj, prim, kind (int64) and area, weight (float64 of the float32 records), one element per entry"""
+    lib = load()
+    n = C.c_uint32()
+    _check(lib, lib.fw_selftest_emitters(scene_desc.ptr(), None, 0, C.byref(n)))
+    out = np.zeros((max(1, n.value), A.FW_EMITTER_RECORD_FLOATS), np.float32)
+    _check(lib, lib.fw_selftest_emitters(scene_desc.ptr(), out.ctypes.data, n.value, C.byref(n)))
+    r = out[:n.value]
+    return dict(obj=r[:, 0].astype(np.int64), prim=r[:, 1].astype(np.int64), kind=r[:, 2].astype(np.int64),
+                area=r[:, 3].astype(np.float64), weight=r[:, 4].astype(np.float64))
+
+
+def selftest_emitter_sample(device_scene, x, n, seed=1):
+    """fw_selftest_emitter_sample: n picks of a DeviceScene's FW_FLAG_ALL_EMITTERS table from world point x, as k_shade_pl draws them.
+    -> dict: entry (int64), p_pick (the stored table's), p_omega, world (n, 3) and obj_point (n, 3) (the point in the object's frame)"""
+    lib = load()
+    xv = np.ascontiguousarray(x, np.float32)
+    out = np.zeros((int(n), A.FW_EMITTER_SAMPLE_FLOATS), np.float32)
+    _check(lib, lib.fw_selftest_emitter_sample(device_scene.handle, xv.ctypes.data, int(n), int(seed) & 0xFFFFFFFF, out.ctypes.data))
+    return dict(entry=out[:, 0].copy().view(np.uint32).astype(np.int64), p_pick=out[:, 1].astype(np.float64),
+                p_omega=out[:, 2].astype(np.float64), world=out[:, 3:6].astype(np.float64), obj_point=out[:, 6:9].astype(np.float64))
 
 
 def selftest_env_dist(rgb, device=0):

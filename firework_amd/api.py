@@ -1053,6 +1053,14 @@ class Renderer:
             self.settings["flags"] & ~A.FW_FLAG_ENV_SAMPLING)
         return self
 
+    def all_emitters(self, on=True):
+        """FW_FLAG_ALL_EMITTERS: with light_sampling, every emitting primitive is a sampled light — EmissiveMat spheres, rectangles, Rect3d
+        faces, disks and mesh triangles — picked in proportion to area x power (DESIGN.md §9i).  Without light_sampling it does nothing;
+        fw_render_aovs ignores it."""
+        self.settings["flags"] = (self.settings["flags"] | A.FW_FLAG_ALL_EMITTERS) if on else (
+            self.settings["flags"] & ~A.FW_FLAG_ALL_EMITTERS)
+        return self
+
     def count_deposits(self, on=True):
         """FW_FLAG_COUNT_DEPOSITS: fw_stats.deposits / bytes_shade become exact where zero deposits are elided (one extra pass)."""
         self.settings["flags"] = (self.settings["flags"] | A.FW_FLAG_COUNT_DEPOSITS) if on else (

@@ -251,6 +251,21 @@ struct DEnvDist {
     uint32_t w, h;
 };
 
+// ---- every emitter (FW_FLAG_ALL_EMITTERS with FW_FLAG_LIGHT_SAMPLING) ---------------------------------------------------
+// The entries: one per emitting primitive of an EmissiveMat object (sphere, rectangle, Rect3d face, disk, mesh triangle), weighted by area x
+// power and picked through an alias table over the entries of positive weight.  tab[c] = (threshold lo, threshold hi, entry, alias): column
+// c = the high 64 bits of a 64-bit uniform times n_cols, then the entry if a second 64-bit uniform is below the threshold, else the alias.
+// ent[e] = (object, primitive, bits of p_pick, kind): p_pick is the probability of the table as stored.  first[object] = the object's first
+// entry (MISS: not an emitter).  p_scale: 1 - p_env (the environment's share, §9h).  A kernel argument of its own, beside DShadow.
+struct DEmitters {
+    const uint4 *tab;
+    const uint4 *ent;
+    const uint32_t *first;
+    uint32_t n_cols;
+    float p_scale;
+};
+constexpr uint32_t EMITTER_MAX_ENTRIES = 1u << 26;
+
 // launch wrappers (fw_kernels.hip)
 struct LaunchCfg {
     hipStream_t stream;
@@ -309,6 +324,17 @@ void launch_shadow_resolve_env(const LaunchCfg &, const DScene &, const DShadow 
 int build_env_dist(hipStream_t stream, const DEnv &env, float *cdf_m, float *cdf_c, float *dens, float *p_out, double *scratch, double *total);
 // n samples of the table (fw_selftest_env_sample): per sample (dir xyz, reported pdf, drawn index, looked-up index)
 void launch_env_sample_test(hipStream_t stream, const DEnv &env, const DEnvDist &ed, uint32_t n, uint32_t seed32, float *out);
+// every emitter: k_shade_ls / k_shade_env with the entries of *em as the emitters (k_shade_pl, k_shade_pl_env), the resolve that
+// compares the full hit code (visible iff the closest hit is the sampled primitive, or a miss for an environment ray), and the weight pass
+void launch_shade_pl(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
+                     float4 *sample_rad, int segment, const DShadow &, const DEmitters &);
+void launch_shade_pl_env(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
+                         float4 *sample_rad, int segment, const DShadow &, const DEnvDist &, const DEmitters &);
+void launch_shadow_resolve_pl(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment);
+// w[e] of n entries: ent[e].z holds the entry's weight, or for a triangle the object's power (its area is taken from sc.tri here)
+void launch_emitter_weights(hipStream_t stream, const DScene &sc, const uint4 *ent, uint32_t n, float *w);
+// n picks from the point x (fw_selftest_emitter_sample): per pick FW_EMITTER_SAMPLE_FLOATS floats
+void launch_emitter_sample_test(hipStream_t stream, const DScene &sc, const DEmitters &em, float x, float y, float z, uint32_t n, uint32_t seed32, float *out);
 void launch_bounce(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, float4 *sample_rad, int segment,
                    bool use_bvh);
 void launch_queue_totals(const LaunchCfg &, uint32_t *totals, const uint32_t *ptotal);

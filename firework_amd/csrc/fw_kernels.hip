@@ -3196,6 +3196,122 @@ __device__ __forceinline__ V3 env_dist_sample(const DEnvDist &ed, uint4 u, uint3
 }
 
 // ------------------------------------------------------------------------------------------------
+// Every emitter (FW_FLAG_ALL_EMITTERS): the entries of DEmitters (spheres, rectangles, Rect3d faces, disks, mesh triangles of
+// EmissiveMat objects), picked by area x power through an alias table.  A sphere keeps light_sample's cone; every flat entry is sampled
+// uniformly in area, p_omega = d^2 / (|cos_l| A) with the geometric normal, two-sided.  Each in the frame the walks intersect its object in.
+// ------------------------------------------------------------------------------------------------
+// the entry a pick lands on, u = draw(key, P_LIGHT, segment, 2): the column from u.x:u.y (64 bits: a 32-bit word times n_cols would favour
+// some columns by up to n_cols / 2^32), the column's entry or its alias by u.z:u.w against the 64-bit threshold.  One dependent load.
+__device__ __forceinline__ uint32_t emitter_pick(const DEmitters &em, uint4 u) {
+    const unsigned long long a = ((unsigned long long)u.x << 32) | u.y, b = ((unsigned long long)u.z << 32) | u.w;
+    const uint4 t = em.tab[(uint32_t)__umul64hi(a, (unsigned long long)em.n_cols)];
+    return b < (((unsigned long long)t.y << 32) | t.x) ? t.z : t.w;
+}
+// face `prim` of a Rect3d (rebuild_hit's faces: 0, 1 -> XY at z = pz + sz, pz; 2, 3 -> XZ at y; 4, 5 -> YZ at x): its rect kind and bounds
+__device__ __forceinline__ uint32_t box_face(const Obj &o, uint32_t prim, float &a0, float &a1, float &b0, float &b1, float &k) {
+    const float px = o.q3.x, py = o.q3.y, pz = o.q3.z, sx = o.q3.w, sy = o.q4.x, sz = o.q4.y;
+    const uint32_t ax = prim >> 1;
+    const bool lo = (prim & 1u) != 0u;
+    if (ax == 0u) { a0 = px; a1 = px + sx; b0 = py; b1 = py + sy; k = lo ? pz : pz + sz; }
+    else if (ax == 1u) { a0 = px; a1 = px + sx; b0 = pz; b1 = pz + sz; k = lo ? py : py + sy; }
+    else { a0 = py; a1 = py + sy; b0 = pz; b1 = pz + sz; k = lo ? px : px + sx; }
+    return 1u + ax;
+}
+// a flat entry's geometric normal (object space, any length) and area; tv: a triangle's vertices (kind 5)
+__device__ __forceinline__ void flat_geom(const DScene &sc, const Obj &o, uint32_t prim, V3 &n, float &area, float4 tv[3]) {
+    const uint32_t kind = obj_kind(o);
+    if (kind == 5u) {
+        const float4 *tp = sc.tri + 3 * (size_t)(o.aux1 + prim);
+        tv[0] = tp[0]; tv[1] = tp[1]; tv[2] = tp[2];
+        n = cross(mk(tv[1].x - tv[0].x, tv[1].y - tv[0].y, tv[1].z - tv[0].z), mk(tv[2].x - tv[0].x, tv[2].y - tv[0].y, tv[2].z - tv[0].z));
+        area = 0.5f * mag(n);
+    } else if (kind == 9u) {                                                         // disk.rs: the y = 0 plane, normal +Y
+        n = mk(0.f, 1.f, 0.f);
+        area = 0.5f * o.q3.z * (o.q3.x * o.q3.x - o.q3.w * o.q3.w);
+    } else if (kind == 4u) {
+        float a0, a1, b0, b1, k;
+        const uint32_t fk = box_face(o, prim, a0, a1, b0, b1, k);
+        n = rect_axis(fk);
+        area = fabsf((a1 - a0) * (b1 - b0));
+    } else { n = rect_axis(kind); area = rect_area(o); }
+}
+// A point of entry (o, prim) seen from x (u1, u2 uniform): the shadow ray's direction (its end: t = 1), p_omega, the object-space point and
+// (a triangle) its barycentrics (1 - sqrt u1, sqrt u1 (1 - u2), sqrt u1 u2).  p_omega = 0: nothing to sample.
+__device__ __forceinline__ float entry_sample(const DScene &sc, const Obj &o, uint32_t prim, V3 x, float u1, float u2, V3 &d, V3 &p_obj, V3 &bary) {
+    const uint32_t kind = obj_kind(o);
+    if (kind <= 3u) return light_sample(o, x, u1, u2, d, p_obj);
+    V3 n; float area; float4 tv[3];
+    flat_geom(sc, o, prim, n, area, tv);
+    if (kind == 5u) {
+        const float s = fsqrt(u1);
+        bary = mk(1.f - s, s * (1.f - u2), s * u2);
+        p_obj = bary.x * mk(tv[0].x, tv[0].y, tv[0].z) + bary.y * mk(tv[1].x, tv[1].y, tv[1].z) + bary.z * mk(tv[2].x, tv[2].y, tv[2].z);
+    } else if (kind == 9u) {
+        const float r2 = o.q3.x * o.q3.x, i2 = o.q3.w * o.q3.w, rr = fsqrt(i2 + u1 * (r2 - i2));
+        float sp, cp; sincosf(u2 * o.q3.z, &sp, &cp);
+        p_obj = mk(rr * cp, 0.f, rr * sp);
+    } else {
+        float a0, a1, b0, b1, k;
+        const uint32_t fk = box_face(o, prim, a0, a1, b0, b1, k);
+        const float a = a0 + u1 * (a1 - a0), b = b0 + u2 * (b1 - b0);
+        p_obj = fk == 1u ? mk(a, b, k) : (fk == 2u ? mk(a, k, b) : mk(k, a, b));
+    }
+    const bool rotated = (obj_flags(o) & OF_ROTATED) != 0u;
+    const V3 nw = rotated ? rot_fwd(o, n) : n;
+    d = (rotated ? rot_fwd(o, p_obj) : p_obj) + obj_pos(o) - x;
+    const float dn = fabsf(dot(nw, d)), dl2 = dot(d, d);
+    if (!(dn > 0.f) || !(area > 0.f)) return 0.f;
+    return fdiv(dl2 * fsqrt(dl2) * mag(nw), dn * area);
+}
+// p_omega of entry (o, prim) for a ray from org along d that meets it at t (the BSDF side of the weight).  A hit without a point — t not a
+// positive number — has p_omega 0 (weight 1): the reference's triangle test (mesh.rs:147-162) shears by the SIGNED largest direction component,
+// so a direction like (0, -0.46, -0.39) divides by its zero x and "hits" with t = NaN; the walks reproduce that hit, and the light sampler can
+// never draw it.  (Without this its weight was NaN: NaN pixels in a 4096-spp frame of a mesh-lit cornell.)
+__device__ __forceinline__ float entry_pdf_hit(const DScene &sc, const Obj &o, uint32_t prim, V3 org, V3 d, float t) {
+    if (obj_kind(o) == 0u) return light_pdf_hit(o, org, d, t);
+    if (!(t > 0.f)) return 0.f;
+    V3 n; float area; float4 tv[3];
+    flat_geom(sc, o, prim, n, area, tv);
+    if (obj_flags(o) & OF_ROTATED) n = rot_fwd(o, n);
+    const float dn = fabsf(dot(n, d)), dl = mag(d);
+    if (!(dn > 0.f) || !(area > 0.f)) return 0.f;
+    return fdiv(t * t * dl * dl * dl * mag(n), dn * area);
+}
+// What a hit at p_obj of entry (o, prim) would emit: rebuild_hit's uv (a triangle's from bary) and world point, then the EmissiveMat's texture
+template <bool CHEAP_ONLY>
+__device__ __forceinline__ V3 entry_emit(const DScene &sc, const float4 *matp, const float4 *texp, const Obj &o, uint32_t prim, V3 p_obj, V3 bary) {
+    const float4 m0 = matp[2 * o.material], m1 = matp[2 * o.material + 1];
+    const uint32_t mbits = __float_as_uint(m0.x);
+    if (CHEAP_ONLY || (mbits & MF_TEX_CONST)) return mk(m1.x, m1.y, m1.z);
+    const uint32_t kind = obj_kind(o);
+    float u = 0.f, v = 0.f;
+    if (mbits & MF_NEEDS_UV) {
+        V3 n;
+        if (kind == 0u) sphere_uv(p_obj / o.q3.x, u, v);
+        else if (kind <= 3u) rect_hitinfo(kind, o.q3.x, o.q3.y, o.q3.z, o.q3.w, false, p_obj, n, u, v, true);
+        else if (kind == 4u) {
+            float a0, a1, b0, b1, k;
+            const uint32_t fk = box_face(o, prim, a0, a1, b0, b1, k);
+            rect_hitinfo(fk, a0, a1, b0, b1, false, p_obj, n, u, v, true);
+        } else if (kind == 5u) {                                                     // rebuild_hit case 5
+            const float4 *tp = sc.tri + 3 * (size_t)(o.aux1 + prim);
+            u = bary.x * tp[0].w + bary.y * tp[1].w + bary.z * tp[2].w;
+            if (obj_flags(o) & OF_MESH_ATTR) {
+                const float4 *np_ = sc.tri_nrm + 3 * (size_t)(o.aux1 + prim);
+                v = bary.x * np_[0].w + bary.y * np_[1].w + bary.z * np_[2].w;
+            } else v = bary.z;
+        } else {                                                                     // rebuild_hit case 9
+            float phi = fwlm::atan2f_glibc(p_obj.z, p_obj.x);
+            if (phi < 0.f) phi = phi + 2.f * PI_F;
+            u = fdiv(phi, o.q3.z);
+            const float dist = fsqrt(p_obj.x * p_obj.x + p_obj.z * p_obj.z);
+            v = 1.f - fdiv(dist - o.q3.w, o.q3.x - o.q3.w);
+        }
+    }
+    return texture_sample(texp, sc.images, __float_as_uint(m0.y), u, v, rot_fwd(o, p_obj) + obj_pos(o));
+}
+
+// ------------------------------------------------------------------------------------------------
 // K5 + K7  shade + stream compaction
 //
 // k_shade is latency-bound (rocprofv3: 79 % of wave cycles in s_waitcnt in the first version): the chain
@@ -3220,12 +3336,13 @@ __device__ __forceinline__ bool expensive_shading(const DScene &sc, const float4
 // LS: k_shade_ls: the MIS weight of emission reached from a light-sampling vertex, the light sample of a Lambertian or
 // Isotropic vertex (*ls: the shadow ray, left to k_shadow_resolve), and the path's visible light samples (sh->nee) in its deposit.
 // ENV (with LS): k_shade_env: the HDR map is a sampled light as well (*ed), picked with probability ed->p_env.
-template <bool CHEAP_ONLY = false, bool CHAIN = false, bool LS = false, bool ENV = false>
+// PL (with LS): k_shade_pl / k_shade_pl_env: the emitters are the entries of *em (every emitting primitive, picked by power).
+template <bool CHEAP_ONLY = false, bool CHAIN = false, bool LS = false, bool ENV = false, bool PL = false>
 __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, const float4 *objp, const float4 *matp,
                                            const float4 *texp, const Ray &r, V3 beta, uint32_t chain, uint32_t path_id, float t_hit,
                                            uint32_t hit_code, int segment, float4 *__restrict__ sample_rad, Ray &nr, V3 &nbeta, uint32_t &nchain PH_ARG,
                                            const RngKey *pre_key = nullptr,       // pre_key: the path's RNG key, when the caller has fetched it already (k_shade, FW_SHADE_PIPE)
-                                           const DShadow *sh = nullptr, LsIO *ls = nullptr, const DEnvDist *ed = nullptr) {
+                                           const DShadow *sh = nullptr, LsIO *ls = nullptr, const DEnvDist *ed = nullptr, const DEmitters *em = nullptr) {
     bool alive = false;
     const uint32_t obj_index = hit_code == MISS ? MISS : (hit_code >> sc.prim_bits);
     V3 rad = mk(0.f, 0.f, 0.f);
@@ -3280,7 +3397,15 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
         if (!CHEAP_ONLY && !CHAIN && !tex_const && (mkind == 0 || mkind == 3 || mkind == 4)) { PH_T0; texc = texture_sample(texp, sc.images, mtex, h.u, h.v, h.point); PH_ADD(3); }
         if (mkind == 3) {                                                      // EmissiveMat: emit, never scatters
             PH_T0;
-            if (LS && ls->pb_in > 0.f && obj_kind(o) <= 3u) {                  // a sampled light, reached from a light-sampling vertex: p_b^2 / (p_b^2 + p_l^2)
+            if (PL) {                                                          // an entry, reached from a light-sampling vertex
+                const uint32_t e0 = ls->pb_in > 0.f ? em->first[obj_index] : MISS;
+                if (e0 != MISS) {
+                    const uint32_t prim = hit_code & ((1u << sc.prim_bits) - 1u);
+                    const float pk = em->p_scale * __uint_as_float(em->ent[e0 + prim].z);
+                    const float s_ = fdiv(pk * entry_pdf_hit(sc, o, prim, r.o, r.d, t_hit), ls->pb_in);
+                    texc = fdiv(1.f, 1.f + s_ * s_) * texc;
+                }
+            } else if (LS && ls->pb_in > 0.f && obj_kind(o) <= 3u) {           // a sampled light, reached from a light-sampling vertex: p_b^2 / (p_b^2 + p_l^2)
                 const float s_ = fdiv(sh->lt.p_pick * light_pdf_hit(o, r.o, r.d, t_hit), ls->pb_in);
                 texc = fdiv(1.f, 1.f + s_ * s_) * texc;
             }
@@ -3335,6 +3460,18 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
                         const float4 e = reinterpret_cast<const float4 *>(sc.env.hdr)[ti];
                         const V3 c = (beta * atten) * mk(e.x, e.y, e.z) * fdiv(r_, 1.f + r_ * r_);
                         if (c.x > 0.f || c.y > 0.f || c.z > 0.f) { ls->shadow = true; ls->sray = Ray{h.point, d}; ls->sobj = MISS; ls->pending = c; }
+                    }
+                } else if (PL) {                                               // an entry: picked by draw index 2, its point by lu.y, lu.z
+                    const uint4 en = em->ent[emitter_pick(*em, draw(key, P_LIGHT, segment, 2))];
+                    const Obj lo = load_obj(objp, en.x);
+                    V3 d, p_obj, bary = mk(0.f, 0.f, 0.f);
+                    const float pl = em->p_scale * __uint_as_float(en.z) * entry_sample(sc, lo, en.y, h.point, u2f(lu.y), u2f(lu.z), d, p_obj, bary);
+                    const float pb = pl > 0.f ? scatter_pdf(n_b, normalized(d)) : 0.f;
+                    if (pb > 0.f) {
+                        const float r_ = fdiv(pb, pl);
+                        const V3 c = (beta * atten) * entry_emit<CHEAP_ONLY>(sc, matp, texp, lo, en.y, p_obj, bary) * fdiv(r_, 1.f + r_ * r_);
+                        // (the full hit code: visible iff the closest hit is this very primitive)
+                        if (c.x > 0.f || c.y > 0.f || c.z > 0.f) { ls->shadow = true; ls->sray = Ray{h.point, d}; ls->sobj = (en.x << sc.prim_bits) | en.y; ls->pending = c; }
                     }
                 } else {
                     // (with the environment in the set the emitters share the rest of [0, 1): (xi - p_env) / (1 - p_env) picks among them)
@@ -3736,6 +3873,193 @@ __global__ __launch_bounds__(WB) void k_shadow_resolve_env(DShadow sh, const flo
         float4 &e = sh.nee[__float_as_uint(p.w)];
         e = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, 0.f);
     }
+}
+// Every emitter: k_shade_ls and k_shade_env with the entries of `em` as the emitters (shade_path's PL).  Copies of their bodies,
+// as k_shade_env is of k_shade_ls's, so that §9g's and §9h's kernels stay as they are.
+template <int LDS_TAB, int MODE>
+__attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
+__global__ __launch_bounds__(WB) void k_shade_pl(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
+                                                    float4 *__restrict__ sample_rad, DQueue q, int segment,
+                                                    uint32_t n_mat, uint32_t n_tex, DShadow sh, DEmitters em) {
+    static_assert(MODE == 0 || MODE == 1, "in line only");
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    const float4 *objp = sc.obj, *matp = sc.mat, *texp = sc.tex;
+    if (sc.has_perlin && MODE != 1) { stage_perm(); if (!LDS_TAB) __syncthreads(); }
+    if (LDS_TAB) {
+        const uint32_t no = LDS_TAB == 1 ? sc.n_objects * OBJ_Q : 0u, nm = 2 * n_mat, nt = 2 * n_tex;
+        if (LDS_TAB == 1) for (uint32_t k = threadIdx.x; k < no; k += WB) lds_tables[k] = sc.obj[k];
+        for (uint32_t k = threadIdx.x; k < nm; k += WB) lds_tables[no + k] = sc.mat[k];
+        for (uint32_t k = threadIdx.x; k < nt; k += WB) lds_tables[no + nm + k] = sc.tex[k];
+        __syncthreads();
+        if (LDS_TAB == 1) objp = lds_tables;
+        matp = lds_tables + no; texp = lds_tables + no + nm;
+    }
+    if (w >= q.n_waves) return;
+    const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
+    const uint32_t base = w * q.cap;
+    uint32_t out_n = 0, sh_n = 0;                                        // survivors / shadow rays written so far (wave-uniform)
+    PH_DECL;
+    float4 ra_n = make_float4(0, 0, 0, 0), st_n = ra_n; float2 rb_n = make_float2(0, 0), hr_n = rb_n; float pb_n = 0.f;
+    auto fetch = [&](uint32_t i) {
+        ra_n = qld(&in.ray_a[i]); rb_n = load_ray_b(in, i, f, segment); st_n = load_state(in, i, segment); hr_n = qld(&hits[i]);
+        pb_n = segment > 0 ? sh.pb_in[i] : 0.f;
+    };
+    if (lane < n) fetch(base + lane);
+    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
+        const uint32_t j = c0 + lane, i = base + j;
+        float4 ra = ra_n, st = st_n; float2 rb = rb_n, hr = hr_n;
+        LsIO ls{pb_n, 0.f, false, Ray{mk(0, 0, 0), mk(0, 0, 0)}, 0u, mk(0, 0, 0)};
+        if (j + 64u < n) fetch(i + 64u);
+        bool alive = false;
+        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
+        if (j < n) {
+            path_id = __float_as_uint(st.w);
+            alive = shade_path<MODE != 0, false, true, false, true>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id,
+                                                                     hr.x, __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS, nullptr, &sh, &ls,
+                                                                     nullptr, &em);
+        }
+        // k_shade's compaction, with p_b next to the state
+        const unsigned long long mask = __ballot(alive);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (alive) {
+            const uint32_t dst = base + out_n + rank;
+            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
+            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
+            qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
+            sh.pb_out[dst] = ls.pb_out;
+        }
+        if (f.ex.mode) flag_exact(f.ex, alive && needs_exact(f.ex, nr.o.x, nr.o.y, nr.o.z, nr.d.x, nr.d.y, nr.d.z), base + out_n + rank, segment + 1);
+        out_n += (uint32_t)__popcll(mask);
+        // the shadow rays: the same compaction, into the wave's region of the shadow queue
+        const unsigned long long sm = __ballot(ls.shadow);
+        if (sm) {
+            const uint32_t sr = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+            if (ls.shadow) {
+                const uint32_t d = base + sh_n + sr;
+                sh.ray_a[d] = make_float4(ls.sray.o.x, ls.sray.o.y, ls.sray.o.z, ls.sray.d.x);
+                sh.ray_b[d] = make_float2(ls.sray.d.y, ls.sray.d.z);
+                sh.state[d] = make_float4(ls.pending.x, ls.pending.y, ls.pending.z, __uint_as_float(path_id));
+                sh.obj[d] = ls.sobj;
+            }
+            sh_n += (uint32_t)__popcll(sm);
+        }
+    }
+    if (lane == 0) { q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n; sh.wcount[(size_t)(segment + 1) * q.n_waves + w] = sh_n; }
+}
+template <int LDS_TAB>
+__attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
+__global__ __launch_bounds__(WB) void k_shade_pl_env(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
+                                                     float4 *__restrict__ sample_rad, DQueue q, int segment,
+                                                     uint32_t n_mat, uint32_t n_tex, DShadow sh, DEnvDist ed, DEmitters em) {
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    const float4 *objp = sc.obj, *matp = sc.mat, *texp = sc.tex;
+    if (sc.has_perlin) { stage_perm(); if (!LDS_TAB) __syncthreads(); }
+    if (LDS_TAB) {
+        const uint32_t no = LDS_TAB == 1 ? sc.n_objects * OBJ_Q : 0u, nm = 2 * n_mat, nt = 2 * n_tex;
+        if (LDS_TAB == 1) for (uint32_t k = threadIdx.x; k < no; k += WB) lds_tables[k] = sc.obj[k];
+        for (uint32_t k = threadIdx.x; k < nm; k += WB) lds_tables[no + k] = sc.mat[k];
+        for (uint32_t k = threadIdx.x; k < nt; k += WB) lds_tables[no + nm + k] = sc.tex[k];
+        __syncthreads();
+        if (LDS_TAB == 1) objp = lds_tables;
+        matp = lds_tables + no; texp = lds_tables + no + nm;
+    }
+    if (w >= q.n_waves) return;
+    const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
+    const uint32_t base = w * q.cap;
+    uint32_t out_n = 0, sh_n = 0;                                        // survivors / shadow rays written so far (wave-uniform)
+    PH_DECL;
+    float4 ra_n = make_float4(0, 0, 0, 0), st_n = ra_n; float2 rb_n = make_float2(0, 0), hr_n = rb_n; float pb_n = 0.f;
+    auto fetch = [&](uint32_t i) {
+        ra_n = qld(&in.ray_a[i]); rb_n = load_ray_b(in, i, f, segment); st_n = load_state(in, i, segment); hr_n = qld(&hits[i]);
+        pb_n = segment > 0 ? sh.pb_in[i] : 0.f;
+    };
+    if (lane < n) fetch(base + lane);
+    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
+        const uint32_t j = c0 + lane, i = base + j;
+        float4 ra = ra_n, st = st_n; float2 rb = rb_n, hr = hr_n;
+        LsIO ls{pb_n, 0.f, false, Ray{mk(0, 0, 0), mk(0, 0, 0)}, 0u, mk(0, 0, 0)};
+        if (j + 64u < n) fetch(i + 64u);
+        bool alive = false;
+        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
+        if (j < n) {
+            path_id = __float_as_uint(st.w);
+            alive = shade_path<false, false, true, true, true>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id,
+                                                                  hr.x, __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS, nullptr, &sh, &ls,
+                                                                  &ed, &em);
+        }
+        // k_shade's compaction, with p_b next to the state
+        const unsigned long long mask = __ballot(alive);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (alive) {
+            const uint32_t dst = base + out_n + rank;
+            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
+            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
+            qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
+            sh.pb_out[dst] = ls.pb_out;
+        }
+        if (f.ex.mode) flag_exact(f.ex, alive && needs_exact(f.ex, nr.o.x, nr.o.y, nr.o.z, nr.d.x, nr.d.y, nr.d.z), base + out_n + rank, segment + 1);
+        out_n += (uint32_t)__popcll(mask);
+        // the shadow rays: the same compaction, into the wave's region of the shadow queue
+        const unsigned long long sm = __ballot(ls.shadow);
+        if (sm) {
+            const uint32_t sr = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+            if (ls.shadow) {
+                const uint32_t d = base + sh_n + sr;
+                sh.ray_a[d] = make_float4(ls.sray.o.x, ls.sray.o.y, ls.sray.o.z, ls.sray.d.x);
+                sh.ray_b[d] = make_float2(ls.sray.d.y, ls.sray.d.z);
+                sh.state[d] = make_float4(ls.pending.x, ls.pending.y, ls.pending.z, __uint_as_float(path_id));
+                sh.obj[d] = ls.sobj;
+            }
+            sh_n += (uint32_t)__popcll(sm);
+        }
+    }
+    if (lane == 0) { q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n; sh.wcount[(size_t)(segment + 1) * q.n_waves + w] = sh_n; }
+}
+// The resolve of k_shade_pl / k_shade_pl_env: sh.obj holds the sampled primitive's full hit code (object << prim_bits | prim; MISS for an
+// environment ray), and a shadow ray counts iff its closest hit code equals it: a mesh can hide its own triangles, a box its back faces.
+__global__ __launch_bounds__(WB) void k_shadow_resolve_pl(DShadow sh, const float2 *__restrict__ hits, DQueue q, int segment) {
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    if (w >= q.n_waves) return;
+    const uint32_t n = sh.wcount[(size_t)(segment + 1) * q.n_waves + w], base = w * q.cap;
+    for (uint32_t j = lane; j < n; j += 64u) {
+        const uint32_t i = base + j;
+        if (__float_as_uint(hits[i].y) != sh.obj[i]) continue;
+        const float4 p = sh.state[i];
+        float4 &e = sh.nee[__float_as_uint(p.w)];
+        e = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, 0.f);
+    }
+}
+// The entries' weights, once per scene: ent[i].z holds the weight the host computed, or for a triangle (ent[i].w = 5) the
+// object's power, multiplied here by the triangle's object-space area |(p1 - p0) x (p2 - p0)| / 2 from the resident sc.tri.
+__global__ __launch_bounds__(WB) void k_emitter_weights(DScene sc, const uint4 *__restrict__ ent, uint32_t n, float *__restrict__ w) {
+    const uint32_t i = blockIdx.x * WB + threadIdx.x;
+    if (i >= n) return;
+    const uint4 e = ent[i];
+    float wi = __uint_as_float(e.z);
+    if (e.w == 5u) {             // (flat_geom's triangle, spelled out: with load_obj and flat_geom here six k_extend instantiations compiled differently)
+        const float4 *tp = sc.tri + 3 * (size_t)(__float_as_uint(sc.obj[(size_t)e.x * OBJ_Q + 5].w) + e.y);
+        const float4 a = tp[0], b = tp[1], c = tp[2];
+        wi = wi * (0.5f * mag(cross(mk(b.x - a.x, b.y - a.y, b.z - a.z), mk(c.x - a.x, c.y - a.y, c.z - a.z))));
+    }
+    w[i] = wi;
+}
+// fw_selftest_emitter_sample: pick i takes draw({i, 0, seed32}, P_LIGHT, 0, 0 and 2), as a vertex of segment 0 of pixel i would
+__global__ __launch_bounds__(WB) void k_emitter_sample_test(DScene sc, DEmitters em, float x, float y, float z, uint32_t n, uint32_t seed32,
+                                                              float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * WB + threadIdx.x;
+    if (i >= n) return;
+    const RngKey key{i, 0u, seed32};
+    const uint4 lu = draw(key, P_LIGHT, 0, 0);
+    const uint32_t e = emitter_pick(em, draw(key, P_LIGHT, 0, 2));
+    const uint4 en = em.ent[e];
+    const Obj o = load_obj(sc.obj, en.x);
+    const V3 xv = mk(x, y, z);
+    V3 d = mk(0.f, 0.f, 0.f), p_obj = d, bary = d;
+    const float pw = entry_sample(sc, o, en.y, xv, u2f(lu.y), u2f(lu.z), d, p_obj, bary);
+    const V3 pw_pt = xv + d;
+    float *op = out + (size_t)i * FW_EMITTER_SAMPLE_FLOATS;
+    op[0] = __uint_as_float(e); op[1] = __uint_as_float(en.z); op[2] = pw;
+    op[3] = pw_pt.x; op[4] = pw_pt.y; op[5] = pw_pt.z; op[6] = p_obj.x; op[7] = p_obj.y; op[8] = p_obj.z;
 }
 
 // The environment's table, built once per scene: k_env_rows (one block per row: the texels' weights, the row's scan in double,
@@ -4556,6 +4880,38 @@ void launch_shade_env(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPa
 }
 void launch_shadow_resolve_env(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment) {
     hipLaunchKernelGGL(k_shadow_resolve_env, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
+}
+void launch_shade_pl(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
+                     float4 *sample_rad, int segment, const DShadow &sh, const DEmitters &em) {
+    // (launch_shade_ls's table and shading modes)
+    const size_t tab = ((size_t)sc.n_objects * OBJ_Q + 2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
+    const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
+    const int lt = (c.lds_tables && tab <= LDS_TABLE_LIMIT) ? 1 : ((c.lds_tables && tab_mt <= LDS_TABLE_LIMIT) ? 2 : 0);
+    const size_t lds = lt == 1 ? tab : (lt == 2 ? tab_mt : 0);
+#define FW_SHADE_PL(L, M) hipLaunchKernelGGL((k_shade_pl<L, M>), wave_grid(c), dim3(WB), lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, sh, em)
+#define FW_SHADE_PL_M(L) do { if (c.shade_mode == 1) FW_SHADE_PL(L, 1); else FW_SHADE_PL(L, 0); } while (0)
+    if (lt == 1) FW_SHADE_PL_M(1); else if (lt == 2) FW_SHADE_PL_M(2); else FW_SHADE_PL_M(0);
+#undef FW_SHADE_PL_M
+#undef FW_SHADE_PL
+}
+void launch_shade_pl_env(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
+                         float4 *sample_rad, int segment, const DShadow &sh, const DEnvDist &ed, const DEmitters &em) {
+    const size_t tab = ((size_t)sc.n_objects * OBJ_Q + 2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
+    const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
+    const int lt = (c.lds_tables && tab <= LDS_TABLE_LIMIT) ? 1 : ((c.lds_tables && tab_mt <= LDS_TABLE_LIMIT) ? 2 : 0);
+    const size_t lds = lt == 1 ? tab : (lt == 2 ? tab_mt : 0);
+#define FW_SHADE_PL_ENV(L) hipLaunchKernelGGL((k_shade_pl_env<L>), wave_grid(c), dim3(WB), lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, sh, ed, em)
+    if (lt == 1) FW_SHADE_PL_ENV(1); else if (lt == 2) FW_SHADE_PL_ENV(2); else FW_SHADE_PL_ENV(0);
+#undef FW_SHADE_PL_ENV
+}
+void launch_shadow_resolve_pl(const LaunchCfg &c, const DScene &, const DShadow &sh, const float2 *hits, int segment) {
+    hipLaunchKernelGGL(k_shadow_resolve_pl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment);
+}
+void launch_emitter_weights(hipStream_t stream, const DScene &sc, const uint4 *ent, uint32_t n, float *w) {
+    hipLaunchKernelGGL(k_emitter_weights, dim3((n + WB - 1) / WB), dim3(WB), 0, stream, sc, ent, n, w);
+}
+void launch_emitter_sample_test(hipStream_t stream, const DScene &sc, const DEmitters &em, float x, float y, float z, uint32_t n, uint32_t seed32, float *out) {
+    hipLaunchKernelGGL(k_emitter_sample_test, dim3((n + WB - 1) / WB), dim3(WB), 0, stream, sc, em, x, y, z, n, seed32, out);
 }
 int build_env_dist(hipStream_t stream, const DEnv &env, float *cdf_m, float *cdf_c, float *dens, float *p_out, double *scratch, double *total) {
     const size_t n = (size_t)env.hdr_w * env.hdr_h;

@@ -942,6 +942,11 @@ struct SceneKeep {
 
 } // namespace
 
+// ---- every emitter (FW_FLAG_ALL_EMITTERS): the entries of a description, object by object (scene_emitters) ----------------
+// obj, shape kind, its entries [first, first + count); pre[k]: entry k's weight (area x power) — for a mesh the object's power, the areas of
+// its triangles come from the device's copy of them (fw::launch_emitter_weights)
+struct EmitterObj { uint32_t obj, kind, count; uint64_t first; float pre[6]; };
+
 struct fw_scene {
     int device = 0;
     int n_cus = 256;
@@ -972,11 +977,21 @@ struct fw_scene {
     DevBuf env_dist;
     int env_state = 0;            // 0: not built; 1: built, positive total weight (the map is a sampled light); 2: built, nothing to sample
     double env_build_ms = 0;
+    // every emitter (FW_FLAG_ALL_EMITTERS): the entry list from the description; the table (fw::DEmitters: tab, ent, first)
+    // built by the first render that needs it and kept for the scene's life (fw_scene_update moves objects, which changes no entry's weight)
+    std::vector<EmitterObj> emit_objs;
+    uint64_t n_entries = 0;
+    DevBuf emitters;
+    int emit_state = 0;           // 0: not built; 1: built, some entry of positive weight; 2: built, nothing to sample
+    uint32_t emit_cols = 0;       // the table's columns (entries of positive weight)
+    size_t emit_ent_off = 0, emit_first_off = 0;
+    double emit_build_ms = 0;
     ~fw_scene() {
         data.release();
         obj_data.release();
         lights.release();
         env_dist.release();
+        emitters.release();
     }
 };
 
@@ -1509,8 +1524,57 @@ static std::vector<LightRec> scene_lights(const fw_scene_desc *d) {
     for (LightRec &r : out) r.p_pick = 1.f / (float)out.size();
     return out;
 }
+// FW_FLAG_ALL_EMITTERS: an EmissiveMat's power, max(r, g, b) of a ConstantTexture with a negative or non-finite channel
+// counted as 0, and 1 for any other texture
+static double emitter_power(const fw_scene_desc *d, const fw_material &m) {
+    if (m.texture < 0 || (uint32_t)m.texture >= d->n_textures || d->textures[m.texture].kind != FW_TEX_CONSTANT) return 1.0;
+    const fw_vec3 c = d->textures[m.texture].color;
+    auto ok = [](float v) { return (std::isfinite(v) && v > 0.f) ? (double)v : 0.0; };
+    return std::max(ok(c.x), std::max(ok(c.y), ok(c.z)));
+}
+// the object-space areas of a shape's entries (not a mesh's): a sphere 4 pi r^2, a rectangle |da db|, a Rect3d's faces (+z -z +y -y +x -x),
+// a disk phi_max (r^2 - r_in^2) / 2
+static uint32_t emitter_areas(const fw_shape &s, double area[6]) {
+    switch (s.kind) {
+    case FW_SHAPE_SPHERE: area[0] = 4.0 * M_PI * (double)s.radius * s.radius; return 1;
+    case FW_SHAPE_XYRECT: case FW_SHAPE_XZRECT: case FW_SHAPE_YZRECT: area[0] = std::fabs(((double)s.a_max - s.a_min) * ((double)s.b_max - s.b_min)); return 1;
+    case FW_SHAPE_RECT3D: {
+        const double xy = std::fabs((double)s.size.x * s.size.y), xz = std::fabs((double)s.size.x * s.size.z), yz = std::fabs((double)s.size.y * s.size.z);
+        area[0] = area[1] = xy; area[2] = area[3] = xz; area[4] = area[5] = yz;
+        return 6; }
+    case FW_SHAPE_DISK: area[0] = 0.5 * (double)s.phi_max * ((double)s.radius * s.radius - (double)s.inner_radius * s.inner_radius); return 1;
+    default: return 0;
+    }
+}
+// a weight as the table takes it: negative and non-finite weights count as 0 (never picked)
+static inline double emitter_weight(double w) { return (std::isfinite(w) && w > 0.0) ? w : 0.0; }
+static std::vector<EmitterObj> scene_emitters(const fw_scene_desc *d, uint64_t &n_entries) {
+    std::vector<EmitterObj> out;
+    n_entries = 0;
+    for (uint32_t i = 0; i < d->n_objects; i++) {
+        const fw_object &o = d->objects[i];
+        if (o.shape < 0 || (uint32_t)o.shape >= d->n_shapes) continue;
+        const fw_shape &s = d->shapes[o.shape];
+        if (s.material < 0 || (uint32_t)s.material >= d->n_materials || d->materials[s.material].kind != FW_MAT_EMISSIVE) continue;
+        const double power = emitter_power(d, d->materials[s.material]);
+        if (!(power > 0.0)) continue;        // a black emitter: no entries (it emits nothing, so nothing is lost)
+        EmitterObj e{}; e.obj = i; e.kind = (uint32_t)s.kind; e.first = n_entries;
+        if (s.kind == FW_SHAPE_TRIANGLE_MESH) { e.count = (s.verts && s.indices) ? s.n_indices / 3 : 0u; e.pre[0] = (float)power; }
+        else {
+            double area[6];
+            e.count = emitter_areas(s, area);
+            for (uint32_t k = 0; k < e.count; k++) e.pre[k] = (float)emitter_weight(area[k] * power);
+        }
+        if (e.count == 0) continue;
+        n_entries += e.count;
+        out.push_back(e);
+    }
+    return out;
+}
+
 // the device's copy (object indices) and the scene's light-sampling facts; at creation and after every fw_scene_update
 static int upload_lights(fw_scene *sc, const fw_scene_desc *d) {
+    sc->emit_objs = scene_emitters(d, sc->n_entries);
     const std::vector<LightRec> L = scene_lights(d);
     std::vector<uint32_t> objs(L.size());
     for (size_t i = 0; i < L.size(); i++) objs[i] = L[i].obj;
@@ -1867,10 +1931,12 @@ int update_scene_impl(fw_scene *sc, const fw_scene_desc *desc) {
         const auto t0 = now();
         fw_scene *ns = nullptr;
         if (int rc = create_scene_impl(desc, sc->device, &ns, &reach)) return rc;
-        DevBuf old_data = sc->data, old_obj = sc->obj_data, old_lights = sc->lights, kept_env = sc->env_dist;
+        DevBuf old_data = sc->data, old_obj = sc->obj_data, old_lights = sc->lights, kept_env = sc->env_dist, old_emitters = sc->emitters;
         const int kept_env_state = sc->env_state; const double kept_env_ms = sc->env_build_ms;
         *sc = *ns;                                     // (the handle stays the caller's; its DevBufs now name the new allocations)
         ns->data = old_data; ns->obj_data = old_obj; ns->lights = old_lights;   // ... and the old ones go with `ns`
+        // (the emitters' table is built again for the new scene, whose triangles are new allocations: the old one goes with `ns`)
+        ns->emitters = old_emitters;
         // (the environment's table stays: the map is the same)
         ns->env_dist = sc->env_dist; sc->env_dist = kept_env; sc->env_state = kept_env_state; sc->env_build_ms = kept_env_ms;
         fw_scene_destroy(ns);
@@ -2023,6 +2089,109 @@ static int ensure_env_dist(fw_scene *sc, const fw_render_params *p, const Worksp
 static bool env_sampling(const fw_scene *sc, const fw_render_params *p) {
     return (p->flags & FW_FLAG_ENV_SAMPLING) != 0 && sc->env_state == 1 && sc->ls_vertices;
 }
+// ---- every emitter ----------------------------------------------------------------------------------------------------
+// The table of the scene's entries on the current device: the weights (the triangles' areas on the device, 4 bytes per entry read back),
+// Vose's alias table over the entries of positive weight in double on the host, and the probability each entry has under the table as
+// stored — its columns' 64-bit thresholds — which is what every estimate uses.  One allocation: tab (16 B per column), ent (16 B per
+// entry), first (4 B per object).  `after`: the scene's upload, which the weight pass reads.
+static int build_emitter_table(fw_scene *sc, hipEvent_t after) {
+    const uint64_t N = sc->n_entries;
+    const uint32_t n_obj = sc->d.n_objects;
+    std::vector<uint32_t> ent((size_t)N * 4), first(n_obj, fw::MISS);
+    for (const EmitterObj &e : sc->emit_objs) {
+        first[e.obj] = (uint32_t)e.first;
+        for (uint32_t k = 0; k < e.count; k++) {
+            uint32_t *r = &ent[(size_t)(e.first + k) * 4];
+            float pre = e.kind == FW_SHAPE_TRIANGLE_MESH ? e.pre[0] : e.pre[k];
+            r[0] = e.obj; r[1] = k; std::memcpy(&r[2], &pre, 4); r[3] = e.kind;
+        }
+    }
+    // the weights
+    std::vector<float> w((size_t)N);
+    {
+        DevBuf dent, dw;
+        if (int rc = dent.upload(ent.data(), ent.size() * 4)) return rc;
+        if (int rc = dw.alloc((size_t)N * 4)) { dent.release(); return rc; }
+        int rc = FW_OK;
+        if (after && hipStreamWaitEvent(nullptr, after, 0) != hipSuccess) rc = fail(FW_ERR_HIP, "hipStreamWaitEvent failed");
+        if (!rc) {
+            fw::launch_emitter_weights(nullptr, sc->d, (const uint4 *)dent.p, (uint32_t)N, (float *)dw.p);
+            if (hipGetLastError() != hipSuccess || hipMemcpy(w.data(), dw.p, (size_t)N * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(FW_ERR_HIP, "emitter weights failed");
+        }
+        dent.release(); dw.release();
+        if (rc) return rc;
+    }
+    // Vose's alias table over the entries of positive weight (in entry order), in double
+    std::vector<uint32_t> pos;
+    double total = 0;
+    for (uint64_t i = 0; i < N; i++) { const double wi = emitter_weight((double)w[i]); if (wi > 0.0) { pos.push_back((uint32_t)i); total += wi; } }
+    const uint32_t K = (uint32_t)pos.size();
+    sc->emit_cols = K;
+    if (K == 0 || !(total > 0.0) || !std::isfinite(total)) { sc->emit_state = 2; return FW_OK; }
+    std::vector<double> q(K);
+    std::vector<uint32_t> alias(K), small, large;
+    for (uint32_t c = 0; c < K; c++) { q[c] = (double)w[pos[c]] / total * (double)K; (q[c] < 1.0 ? small : large).push_back(c); }
+    while (!small.empty() && !large.empty()) {
+        const uint32_t s_ = small.back(), l = large.back();
+        small.pop_back(); large.pop_back();
+        alias[s_] = l;
+        q[l] = (q[l] + q[s_]) - 1.0;
+        (q[l] < 1.0 ? small : large).push_back(l);
+    }
+    for (uint32_t c : large) { q[c] = 1.0; alias[c] = c; }
+    for (uint32_t c : small) { q[c] = 1.0; alias[c] = c; }     // (rounding leftovers)
+    // the stored table: threshold = q 2^64 (an entry that keeps its whole column aliases itself), and the probability it gives each entry
+    std::vector<uint32_t> tab((size_t)K * 4);
+    std::vector<long double> prob((size_t)N, 0.0L);
+    const long double two64 = 18446744073709551616.0L;
+    for (uint32_t c = 0; c < K; c++) {
+        uint64_t thr;
+        if (alias[c] == c || q[c] >= 1.0) { thr = ~0ull; alias[c] = c; }
+        else if (!(q[c] > 0.0)) thr = 0;
+        else { const long double t = std::floor((long double)q[c] * two64 + 0.5L); thr = t >= two64 ? ~0ull : (uint64_t)t; }
+        const long double keep = alias[c] == c ? 1.0L : (long double)thr / two64;
+        prob[pos[c]] += keep / K;
+        prob[pos[alias[c]]] += (1.0L - keep) / K;
+        uint32_t *r = &tab[(size_t)c * 4];
+        r[0] = (uint32_t)thr; r[1] = (uint32_t)(thr >> 32); r[2] = pos[c]; r[3] = pos[alias[c]];
+    }
+    for (uint64_t i = 0; i < N; i++) { const float pk = (float)prob[i]; std::memcpy(&ent[(size_t)i * 4 + 2], &pk, 4); }
+    const size_t tab_b = ((size_t)K * 16 + 255) & ~(size_t)255, ent_b = ((size_t)N * 16 + 255) & ~(size_t)255;
+    std::vector<uint8_t> blob(tab_b + ent_b + (size_t)n_obj * 4, 0);
+    std::memcpy(blob.data(), tab.data(), (size_t)K * 16);
+    std::memcpy(blob.data() + tab_b, ent.data(), (size_t)N * 16);
+    std::memcpy(blob.data() + tab_b + ent_b, first.data(), (size_t)n_obj * 4);
+    if (int rc = sc->emitters.upload(blob.data(), blob.size())) return rc;
+    sc->emit_ent_off = tab_b; sc->emit_first_off = tab_b + ent_b;
+    sc->emit_state = 1;
+    return FW_OK;
+}
+static fw::DEmitters emitters_of(const fw_scene *sc, float p_env) {
+    const uint8_t *b = (const uint8_t *)sc->emitters.p;
+    return fw::DEmitters{(const uint4 *)b, (const uint4 *)(b + sc->emit_ent_off), (const uint32_t *)(b + sc->emit_first_off), sc->emit_cols, 1.f - p_env};
+}
+static bool all_emitters_asked(const fw_render_params *p) {
+    return (p->flags & FW_FLAG_LIGHT_SAMPLING) != 0 && (p->flags & FW_FLAG_ALL_EMITTERS) != 0;
+}
+// The table, at the first render whose flags ask for it (the caller has set the scene's device and holds the workspace's lock); more than
+// 2^26 entries: FW_ERR_UNSUPPORTED, before any launch
+static int ensure_emitters(fw_scene *sc, const fw_render_params *p, const Workspace *ws) {
+    if (!all_emitters_asked(p)) return FW_OK;
+    if (sc->n_entries > fw::EMITTER_MAX_ENTRIES) return fail(FW_ERR_UNSUPPORTED, "FW_FLAG_ALL_EMITTERS: more than 2^26 emitter entries");
+    if (!sc->ls_vertices || sc->emit_state != 0) return FW_OK;
+    if (sc->n_entries == 0) { sc->emit_state = 2; return FW_OK; }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = build_emitter_table(sc, ws->ev_upload)) return rc;
+    sc->emit_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (options().trace) fprintf(stderr, "[firework] emitter table: %llu entries, %u of positive weight, %.2f ms\n", (unsigned long long)sc->n_entries, sc->emit_cols, sc->emit_build_ms);
+    return FW_OK;
+}
+// FW_FLAG_ALL_EMITTERS takes effect with FW_FLAG_LIGHT_SAMPLING where some entry has positive weight and a material's vertices
+// sample lights; otherwise the frame is the frame without the bit (ensure_emitters has run)
+static bool all_emitters(const fw_scene *sc, const fw_render_params *p) {
+    return all_emitters_asked(p) && sc->emit_state == 1 && sc->ls_vertices;
+}
+
 // render_impl's lanes (batches in flight) and paths per batch and lane for `p` (fw_render_views sizes its view groups by the same budget)
 struct BatchBudget { int n_lanes; bool exact_product; uint32_t budget; };
 BatchBudget batch_budget(const fw_scene *sc, const fw_render_params *p, const Options &O, size_t arena_bytes) {
@@ -2032,7 +2201,7 @@ BatchBudget batch_budget(const fw_scene *sc, const fw_render_params *p, const Op
     // EXACT_PRODUCT: 160 more bytes per slot (ten attenuation records) where the scene has no chain state: half the default batch
     const bool exact_product = O.exact_product && (sc->chain_bits == 0 || O.no_chain);
     // light sampling: 92 more bytes per slot (fw::DShadow) — half the default batch as well (and so with environment sampling)
-    const bool ls = light_sampling(sc, p) || env_sampling(sc, p);
+    const bool ls = light_sampling(sc, p) || env_sampling(sc, p) || all_emitters(sc, p);
     const uint32_t budget = p->paths_per_batch ? p->paths_per_batch : default_paths_per_batch(O, arena_bytes) / (uint32_t)n_lanes / (exact_product || ls ? 2u : 1u);
     return BatchBudget{n_lanes, exact_product, budget};
 }
@@ -2082,6 +2251,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     std::unique_lock<std::mutex> ws_guard(ws->mu, std::defer_lock);
     if (!rd) ws_guard.lock();                                                        // (an adaptive round's caller holds it)
     { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }     // after fw_release_workspace, or a scene made before it
+    if (int erc = ensure_emitters(sc, p, ws)) return erc;     // (first: its FW_ERR_UNSUPPORTED comes before any launch)
     if (int erc = ensure_env_dist(sc, p, ws)) return erc;
     const Options O = options();
 
@@ -2103,9 +2273,11 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     int n_lanes = bb.n_lanes;
     // light sampling: a path deposits its visible light samples with its own end, so the frame keeps the running product (no
     // chain state, no EXACT_PRODUCT records), deposits every path (no elided zeros) and keeps t in its hit records (no hit4).  Environment
-    // sampling (§9h) takes the same frame: ls = either; es = the environment is among the sampled lights (k_shade_env)
-    const bool ls_lights = light_sampling(sc, p), es = env_sampling(sc, p);
-    const bool ls = ls_lights || es;
+    // sampling (§9h) takes the same frame: ls = either; es = the environment is among the sampled lights (k_shade_env).  Every emitter (§9i):
+    // pl = the entries replace §9g's lights (k_shade_pl, k_shade_pl_env)
+    const bool pl = all_emitters(sc, p);
+    const bool ls_lights = !pl && light_sampling(sc, p), es = env_sampling(sc, p);
+    const bool ls = ls_lights || es || pl;
     const bool exact_product = bb.exact_product && !ls;
     const uint32_t budget = bb.budget;
     uint32_t spp_b = std::max<uint32_t>(1u, budget / n_pix);
@@ -2354,7 +2526,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // extend always runs beside the other batch's memory-bound shade (left alone, the two lanes drift INTO phase within three segments:
     // profiles/r05a_share_trace.txt).
     struct BatchCtx { fw::DFrame fr; fw::LaunchCfg cfg; fw::DPaths buf[2]; float2 *hits; float4 *srad; fw::DPark park; uint32_t *totals; uint32_t n_paths; int cur; int lane; hipStream_t ls;
-                      fw::DShadow sh; fw::DEnvDist ed; };
+                      fw::DShadow sh; fw::DEnvDist ed; fw::DEmitters em; };
     // Measured (profiles/r05j_phase_lock.txt, three interleaved pairs): cornell 33.4-33.8 -> 32.2-32.4 ms — the lock holds the frame in the faster
     // of the two phases it otherwise lands in by chance (profiles/r05h_layout_pad.txt) —, where extend and shade last about as long as each
     // other.  Under use_bvh an extend lasts three shades and waiting for the other batch's costs: suzanne 62.7 -> 67.7, part2 @256 119.6 ->
@@ -2393,10 +2565,12 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         c.park = fw::DPark{(float4 *)L.park_a, (float2 *)L.park_b, (float4 *)L.park_m, q.cap + 64u, (uint32_t *)L.pcount,
                            park_meshes ? (uint32_t *)L.pcount + q.n_waves : nullptr};
         if (park_meshes) HIPCHK(hipMemsetAsync(c.park.ptotal, 0, (size_t)q.n_waves * 4, c.ls));
-        c.sh = fw::DShadow{}; c.ed = fw::DEnvDist{};
+        c.sh = fw::DShadow{}; c.ed = fw::DEnvDist{}; c.em = fw::DEmitters{};
         if (ls) {
-            // picking a light: the environment with p_env (1 alone, 1/2 beside emitters), each emitter with (1 - p_env) / n
-            const float p_env = es ? (ls_lights ? 0.5f : 1.f) : 0.f;
+            // picking a light: the environment with p_env (1 alone, 1/2 beside emitters), each emitter with (1 - p_env) / n, each entry (§9i)
+            // with (1 - p_env) p_i
+            const float p_env = es ? ((ls_lights || pl) ? 0.5f : 1.f) : 0.f;
+            if (pl) c.em = emitters_of(sc, p_env);
             c.sh.lt = ls_lights ? fw::DLights{(const uint32_t *)sc->lights.p, sc->n_lights, es ? (1.f - p_env) / (float)sc->n_lights : 1.f / (float)sc->n_lights}
                                 : fw::DLights{(const uint32_t *)sc->lights.p, 0u, 0.f};
             if (es) c.ed = env_dist_of(sc->env_dist, sc->d.env, p_env);
@@ -2440,14 +2614,17 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         if (ls) {
             Workspace::Lane &L = ws->lanes[c.lane];
             c.sh.pb_in = (const float *)L.pb[c.cur]; c.sh.pb_out = (float *)L.pb[c.cur ^ 1];
-            if (es) timed(c, 2, [&] { fw::launch_shade_env(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, c.ed); });
+            if (pl && es) timed(c, 2, [&] { fw::launch_shade_pl_env(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, c.ed, c.em); });
+            else if (pl) timed(c, 2, [&] { fw::launch_shade_pl(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, c.em); });
+            else if (es) timed(c, 2, [&] { fw::launch_shade_env(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, c.ed); });
             else timed(c, 2, [&] { fw::launch_shade_ls(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh); });
             if (seg < fw::MAX_SEGMENTS - 1) {     // segments 0-9 scatter (render.rs:21): their shadow rays through the ordinary walks, then the resolve
                 fw::LaunchCfg scfg = c.cfg; scfg.q.wcount = c.sh.wcount;
                 fw::DFrame sfr = c.fr; sfr.seed32 ^= fw::SHADOW_SEED; sfr.ex.mode = 0;
                 const fw::DPaths sp{c.sh.ray_a, c.sh.ray_b, c.sh.state};
                 timed(c, 1, [&] { fw::launch_extend(scfg, sc->d, sfr, sp, (float2 *)L.s_hits, seg + 1, use_bvh, c.park); });
-                if (es) timed(c, 2, [&] { fw::launch_shadow_resolve_env(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
+                if (pl) timed(c, 2, [&] { fw::launch_shadow_resolve_pl(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
+                else if (es) timed(c, 2, [&] { fw::launch_shadow_resolve_env(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
                 else timed(c, 2, [&] { fw::launch_shadow_resolve(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
             }
         } else
@@ -2820,6 +2997,7 @@ int views_impl(fw_scene *sc, const fw_render_params *p, const fw_camera_settings
     {
         std::lock_guard<std::mutex> ws_guard(ws->mu);
         { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }
+        if (int erc = ensure_emitters(sc, p, ws)) return erc;
         if (int erc = ensure_env_dist(sc, p, ws)) return erc;
         budget = batch_budget(sc, p, options(), ws->arena.bytes).budget;
     }
@@ -3447,6 +3625,61 @@ int fw_selftest_env_sample(int device, const float *rgb, uint32_t w, uint32_t h,
         fw::launch_env_sample_test(nullptr, t.env, env_dist_of(t.dist, t.env, 1.f), n, seed, (float *)o.p);
         int rc = FW_OK;
         if (hipGetLastError() != hipSuccess || hipMemcpy(out, o.p, (size_t)n * FW_ENV_SAMPLE_FLOATS * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(FW_ERR_HIP, "sampling failed");
+        o.release();
+        return rc;
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+}
+
+// Diagnostic: the entries of a description, their areas in float64 (a mesh's triangles from its vertices) and weights
+int fw_selftest_emitters(const fw_scene_desc *desc, float *out, uint32_t cap, uint32_t *n) {
+    if (!desc || !n || (!out && cap > 0)) return fail(FW_ERR_BAD_ARG, "bad argument");
+    try {
+        uint64_t total = 0;
+        const std::vector<EmitterObj> E = scene_emitters(desc, total);
+        *n = (uint32_t)std::min<uint64_t>(total, 0xffffffffull);
+        uint64_t i = 0;
+        for (const EmitterObj &e : E) {
+            const fw_shape &s = desc->shapes[desc->objects[e.obj].shape];
+            const double power = emitter_power(desc, desc->materials[s.material]);
+            double area[6] = {0, 0, 0, 0, 0, 0};
+            if (e.kind != FW_SHAPE_TRIANGLE_MESH) emitter_areas(s, area);
+            for (uint32_t k = 0; k < e.count && i < cap; k++, i++) {
+                double a = area[e.kind == FW_SHAPE_TRIANGLE_MESH ? 0 : k];
+                if (e.kind == FW_SHAPE_TRIANGLE_MESH) {
+                    double v[3][3];
+                    for (int c = 0; c < 3; c++) { const uint32_t vi = s.indices[3 * k + c]; for (int j = 0; j < 3; j++) v[c][j] = vi < s.n_verts ? (double)s.verts[3 * vi + j] : 0.0; }
+                    const double e1[3] = {v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2]}, e2[3] = {v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2]};
+                    const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+                    a = 0.5 * std::sqrt(cx * cx + cy * cy + cz * cz);
+                }
+                float *r = out + (size_t)i * FW_EMITTER_RECORD_FLOATS;
+                r[0] = (float)e.obj; r[1] = (float)k; r[2] = (float)e.kind; r[3] = (float)a; r[4] = (float)emitter_weight(a * power);
+            }
+        }
+        return FW_OK;
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+}
+int fw_selftest_emitter_sample(fw_scene *sc, const float *x, uint32_t n, uint32_t seed, float *out) {
+    if (!sc || !x || n == 0 || n > (1u << 26) || !out) return fail(FW_ERR_BAD_ARG, "bad argument");
+    try {
+        HIPCHK(hipSetDevice(sc->device));
+        Workspace *ws = workspace_for(sc->device);
+        if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
+        std::lock_guard<std::mutex> ws_guard(ws->mu);
+        if (int rc = init_device_locked(ws, sc->device)) return rc;
+        if (sc->n_entries > fw::EMITTER_MAX_ENTRIES) return fail(FW_ERR_UNSUPPORTED, "more than 2^26 emitter entries");
+        if (sc->emit_state == 0) {
+            if (sc->n_entries == 0) sc->emit_state = 2;
+            else if (int rc = build_emitter_table(sc, ws->ev_upload)) return rc;
+        }
+        if (sc->emit_state != 1) return fail(FW_ERR_UNSUPPORTED, "no emitter entry of positive weight");
+        DevBuf o;
+        if (int rc = o.alloc((size_t)n * FW_EMITTER_SAMPLE_FLOATS * 4)) return rc;
+        fw::launch_emitter_sample_test(nullptr, sc->d, emitters_of(sc, 0.f), x[0], x[1], x[2], n, seed, (float *)o.p);
+        int rc = FW_OK;
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, o.p, (size_t)n * FW_EMITTER_SAMPLE_FLOATS * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(FW_ERR_HIP, "sampling failed");
         o.release();
         return rc;
     }

@@ -218,7 +218,7 @@ inline void init(int device = 0, uint64_t arena_bytes = 0) {
 
 struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithreaded, no BVH, gamma 2.2
     size_t width_ = 1920, height_ = 1080, samples_ = 128; bool multithreaded_ = true, use_bvh_ = false; float gamma_ = 2.2f;
-    CameraSettings camera_; uint64_t seed_ = 0; int device_ = 0; bool light_sampling_ = false, env_sampling_ = false;
+    CameraSettings camera_; uint64_t seed_ = 0; int device_ = 0; bool light_sampling_ = false, env_sampling_ = false, all_emitters_ = false;
     static Renderer default_() { return {}; }
     Renderer width(size_t w) && { width_ = w; return std::move(*this); }
     Renderer height(size_t h) && { height_ = h; return std::move(*this); }
@@ -233,11 +233,14 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
     Renderer light_sampling(bool on = true) && { light_sampling_ = on; return std::move(*this); }
     // importance sampling of an HDR environment map at diffuse vertices (FW_FLAG_ENV_SAMPLING)
     Renderer env_sampling(bool on = true) && { env_sampling_ = on; return std::move(*this); }
+    // with light_sampling: every emitting primitive (meshes, disks, boxes too) a sampled light, picked by power (FW_FLAG_ALL_EMITTERS, §9i)
+    Renderer all_emitters(bool on = true) && { all_emitters_ = on; return std::move(*this); }
 
     fw_render_params params() const {
         fw_render_params p{}; p.width = (uint32_t)width_; p.height = (uint32_t)height_; p.samples = (uint32_t)samples_; p.gamma = gamma_;
         p.use_bvh = use_bvh_; p.multithreaded = multithreaded_; p.seed = seed_; p.rng_mode = FW_RNG_CTR;
-        p.flags = (light_sampling_ ? FW_FLAG_LIGHT_SAMPLING : 0u) | (env_sampling_ ? FW_FLAG_ENV_SAMPLING : 0u);
+        p.flags = (light_sampling_ ? FW_FLAG_LIGHT_SAMPLING : 0u) | (env_sampling_ ? FW_FLAG_ENV_SAMPLING : 0u) |
+                  (all_emitters_ ? FW_FLAG_ALL_EMITTERS : 0u);
         p.camera = fw_camera_settings{lower(camera_.cam_pos_), lower(camera_.look_at_), camera_.vfov, camera_.aperture_, camera_.focus_dist_};
         return p; }
 

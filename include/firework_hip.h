@@ -224,6 +224,21 @@ typedef struct fw_render_params {
                                      built on the device at the first render that asks for it and kept with the scene.  Nothing to sample (a
                                      ColorEnv or SkyEnv, a map of zero total weight, no Lambertian or Isotropic material): the frame without
                                      the bit, bit for bit.  Honoured and ignored by the same entry points as FW_FLAG_LIGHT_SAMPLING. */
+#define FW_FLAG_ALL_EMITTERS 16u  /* with FW_FLAG_LIGHT_SAMPLING: the sampled emitters are every emitting primitive of an
+                                     EmissiveMat object — a sphere, an axis-aligned rectangle, each face of a Rect3d, a Disk (full or an
+                                     annular sector), each triangle of a TriangleMesh (objects that share a mesh each have their own) — and
+                                     one is picked in proportion to area x power (power: max(r, g, b) of a ConstantTexture, negative or
+                                     non-finite channels counted as 0; any other texture 1), through an alias table whose stored
+                                     probabilities every estimate uses.  Flat primitives are sampled uniformly in area, spheres in their
+                                     cone; a shadow ray counts only where its closest hit is the sampled primitive itself.  With
+                                     FW_FLAG_ENV_SAMPLING the environment keeps p_env = 1/2 and each entry gets (1 - p_env) p_i.  Cones,
+                                     cylinders and media are never sampled (their light keeps MIS weight 1).  The table is built at the
+                                     first render that asks for it (the triangles' areas on the device, the alias table on the host) and
+                                     kept with the scene; fw_scene_update keeps it.  Paths and shadow-ray accounting as
+                                     FW_FLAG_LIGHT_SAMPLING.  Without FW_FLAG_LIGHT_SAMPLING the bit does nothing; a scene with no entry of
+                                     positive weight (or no Lambertian or Isotropic material) renders the frame without the bit.  More than
+                                     2^26 entries: FW_ERR_UNSUPPORTED before any launch.  Honoured and ignored by the same entry points as
+                                     FW_FLAG_LIGHT_SAMPLING. */
 
 #define FW_MAX_SEGMENTS 11  /* depths 0..10: render.rs:21 */
 
@@ -603,6 +618,21 @@ int fw_selftest_lights(const fw_scene_desc *desc, float *out, uint32_t cap, uint
 #define FW_ENV_SAMPLE_FLOATS 6
 int fw_selftest_env_dist(int device, const float *rgb, uint32_t w, uint32_t h, float *p, double *total);
 int fw_selftest_env_sample(int device, const float *rgb, uint32_t w, uint32_t h, uint32_t n, uint32_t seed, float *out);
+
+/* Diagnostic, CPU only: the entries of a description as FW_FLAG_ALL_EMITTERS sees them, in object order and within an object
+   in primitive order, FW_EMITTER_RECORD_FLOATS floats each: object index, primitive (a Rect3d's face 0-5, a mesh's triangle), shape kind,
+   area (object space) and weight (area x power), computed in float64 and rounded to float32.  An object of power 0 (a black emitter) has
+   no entries; a primitive of area 0 is listed with weight 0 and never picked.  *n = the number of entries (it may exceed 2^26, which a render refuses); at most cap records are written.  Errors:
+   FW_ERR_BAD_ARG (null desc or n, out = NULL with cap > 0). */
+#define FW_EMITTER_RECORD_FLOATS 5
+int fw_selftest_emitters(const fw_scene_desc *desc, float *out, uint32_t cap, uint32_t *n);
+/* Diagnostic (GPU): n picks of the scene's FW_FLAG_ALL_EMITTERS table (built here if no render has built it yet) from the world point x
+   (3 floats), pick i drawn as a segment-0 vertex of pixel i with seed32 = seed would draw it, FW_EMITTER_SAMPLE_FLOATS floats each: the
+   entry index (the float's bits are the uint32), the entry's pick probability as the table stores it, the sampled point's p_omega from x,
+   the sampled world point (xyz) and the point in the object's frame (xyz).  Errors: FW_ERR_BAD_ARG (null pointers, n = 0 or above 2^26),
+   FW_ERR_UNSUPPORTED (no entry of positive weight, or more than 2^26 entries), FW_ERR_HIP. */
+#define FW_EMITTER_SAMPLE_FLOATS 9
+int fw_selftest_emitter_sample(fw_scene *scene, const float *x, uint32_t n, uint32_t seed, float *out);
 
 #ifdef __cplusplus
 }
