@@ -18,10 +18,17 @@ back as an HDR environment with the same orientation; orthographic: the fixed vi
 with --orbit / --adaptive / --denoise / --progressive / --checkpoint), --light-sampling (sample the lights directly at diffuse vertices:
 next-event estimation with MIS; combines with every other flag), --env-sampling (sample an HDR environment map by its
 radiance at diffuse vertices; alone or with --light-sampling, and with every other flag), --all-emitters (light sampling
-over every emitting primitive, meshes, disks and boxes included, picked by power; implies --light-sampling)."""
+over every emitting primitive, meshes, disks and boxes included, picked by power; implies --light-sampling),
+--temporal [MAX_HISTORY] (only with --orbit: the views are rendered one after another as a sequence, each merged with the reprojected
+history of the view before it — a pixel carries over at most MAX_HISTORY samples, default 64 — and then denoised, DESIGN.md §9j;
+--denoise L and --aov-samples keep their meaning; view k renders with seed + k; not with --progressive / --checkpoint / --adaptive /
+--camera)."""
 import argparse
 import sys
 import time
+
+
+TEMPORAL_DEFAULT = 64.0    # api.DEFAULT_MAX_HISTORY (not imported here: the parser runs before the library is loaded)
 
 
 def main(argv=None):
@@ -44,6 +51,9 @@ def main(argv=None):
     ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="L",
                     help="denoise the frame with L a-trous iterations (default 5) guided by first-hit albedo / normal / position buffers")
     ap.add_argument("--aov-samples", type=int, default=8, metavar="S", help="with --denoise: samples per pixel of the guide buffers")
+    ap.add_argument("--temporal", type=float, nargs="?", const=TEMPORAL_DEFAULT, default=None, metavar="MAX_HISTORY",
+                    help="with --orbit: merge each view with the reprojected history of the view before it (at most MAX_HISTORY samples "
+                         "carried over per pixel, default 64), then denoise it")
     ap.add_argument("--light-sampling", action="store_true",
                     help="sample the scene's lights directly at diffuse vertices (next-event estimation with MIS): less noise per sample")
     ap.add_argument("--env-sampling", action="store_true",
@@ -57,8 +67,15 @@ def main(argv=None):
     opt = ap.parse_args(argv)
     if opt.adaptive is not None and (opt.progressive > 0 or opt.checkpoint):
         ap.error("--adaptive cannot be combined with --progressive or --checkpoint")
+    if opt.temporal is not None:
+        if opt.progressive > 0 or opt.checkpoint or opt.adaptive is not None or opt.camera != "pinhole":
+            ap.error("--temporal cannot be combined with --progressive, --checkpoint, --adaptive or --camera")
+        if opt.orbit <= 0:
+            ap.error("--temporal needs --orbit N: it merges each view with the one before it")
+        if not opt.temporal > 0:
+            ap.error("--temporal MAX_HISTORY needs MAX_HISTORY > 0")
     if opt.denoise is not None:
-        if opt.progressive > 0 or opt.checkpoint or opt.orbit:
+        if opt.progressive > 0 or opt.checkpoint or (opt.orbit and opt.temporal is None):
             ap.error("--denoise cannot be combined with --progressive, --checkpoint or --orbit")
         if not 0 <= opt.denoise <= 10:
             ap.error("--denoise L needs 0 <= L <= 10")
@@ -98,6 +115,15 @@ def main(argv=None):
     start = time.time()
     if opt.camera != "pinhole":
         render = camera_model_render(renderer, camera, scene, opt)
+    elif opt.orbit > 0 and opt.temporal is not None:
+        from .api import orbit_cameras
+        frames = renderer.render_sequence(scene, orbit_cameras(camera, opt.orbit), device=opt.device, max_history=opt.temporal,
+                                          iterations=5 if opt.denoise is None else opt.denoise, aov_samples=opt.aov_samples)
+        for name, res in zip(names, frames):
+            save_image(res.rgb8, name, opt.width, opt.height)
+        print(f"Finished Rendering in {int(time.time() - start)} s")
+        print(f'Saved {opt.orbit} views to "{names[0]}" .. "{names[-1]}"')
+        return 0
     elif opt.orbit > 0:
         from .api import orbit_cameras
         res = renderer.render_views(scene, orbit_cameras(camera, opt.orbit), device=opt.device)

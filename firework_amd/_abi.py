@@ -141,5 +141,16 @@ class fw_denoise_params(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+# fw_temporal (include/firework_hip.h): the reprojection's constants and its parameters
+FW_TEMPORAL_NORMAL_COS = 0.9
+FW_TEMPORAL_PLANE = 0.02
+FW_TEMPORAL_MIN_TAP = 1e-3
+
+
+class fw_temporal_params(C.Structure):
+    _fields_ = [("width", u32), ("height", u32), ("camera", fw_camera_settings), ("prev_camera", fw_camera_settings), ("samples", u32),
+                ("max_history", f32), ("device", i32), ("on_device", i32), ("stream", C.c_void_p)]
+
+
 def vec3(v):
     return fw_vec3(float(v[0]), float(v[1]), float(v[2]))

@@ -104,6 +104,8 @@ def load(preload=False, device=None):
     lib.fw_render_aovs.argtypes = [C.c_void_p, C.POINTER(A.fw_render_params), C.c_void_p, C.POINTER(A.fw_stats)]
     lib.fw_denoise.restype = C.c_int
     lib.fw_denoise.argtypes = [C.POINTER(A.fw_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fw_temporal.restype = C.c_int
+    lib.fw_temporal.argtypes = [C.POINTER(A.fw_temporal_params)] + [C.c_void_p] * 10
     if lib.fw_abi_version() != A.FW_ABI_VERSION:
         raise FireworkError(A.FW_ERR_BAD_ARG, "ABI version mismatch between _abi.py and libfirework_hip.so")
     _lib = lib
@@ -663,3 +665,52 @@ def denoise(color, aov, moments=None, width=None, height=None, iterations=A.FW_D
     _check(lib, lib.fw_denoise(C.byref(p), c.ctypes.data, a.ctypes.data, None if m is None else m.ctypes.data, lin.ctypes.data,
                                gam.ctypes.data, rgb8.ctypes.data))
     return rgb8, gam, lin
+
+
+def temporal(color, aov, moments=None, history=None, prev_position=None, width=None, height=None, camera=None, prev_camera=None, samples=0,
+             max_history=float("inf"), device=0, stream=None):
+    """fw_temporal: merges the linear frame `color` (N, 3) — with fw_render_adaptive's `moments` (N, 4), or None and the frame's `samples`
+    — with the previous frame's `history` = (hist_color (N, 3), hist_moments (N, 4), hist_aov (N, 12)): the previous call's first two
+    results and the previous frame's guides, reprojected with `prev_camera` through this frame's guides `aov` (N, 12) and tested
+    geometrically (include/firework_hip.h).  history None = a first frame.  prev_position (N, 3): where each pixel's surface point was
+    in the previous frame; None = a static scene.  camera / prev_camera: CameraSettings or fw_camera_settings (prev_camera defaults to
+    camera).  Returns (out_color (N, 3), out_moments (N, 4), out_history (N,)): host arrays for host arrays; for contiguous float32
+    torch tensors on cuda:`device`, merged on `stream` (default: the current torch stream), new device tensors."""
+    lib = load()
+    if width is None or height is None or camera is None:
+        raise ValueError("temporal needs width, height and camera")
+    n = int(width) * int(height)
+    p = A.fw_temporal_params()
+    p.width, p.height, p.samples, p.max_history, p.device = int(width), int(height), int(samples), float(max_history), int(device)
+    p.camera = camera if isinstance(camera, A.fw_camera_settings) else camera.to_abi()
+    prev_camera = camera if prev_camera is None else prev_camera
+    p.prev_camera = prev_camera if isinstance(prev_camera, A.fw_camera_settings) else prev_camera.to_abi()
+    hist = (None, None, None) if history is None else tuple(history)
+    if len(hist) != 3:
+        raise ValueError("history must be (hist_color, hist_moments, hist_aov) or None")
+    names = ("color", "moments", "aov", "hist_color", "hist_moments", "hist_aov", "prev_position")
+    cols = (3, 4, 12, 3, 4, 12, 3)
+    arrays = (color, moments, aov) + hist + (prev_position,)
+    if type(color).__module__.startswith("torch"):
+        import torch
+        for name, c, t in zip(names, cols, arrays):
+            if t is not None:
+                _check_device_tensor(t, (n, c), torch.float32, device, name)
+        dev = color.device
+        out_c = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        out_m = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        out_h = torch.empty((n,), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        p.on_device = 1
+        p.stream = C.c_void_p(stream) if stream else None
+        _check(lib, lib.fw_temporal(C.byref(p), *[None if t is None else t.data_ptr() for t in arrays], out_c.data_ptr(), out_m.data_ptr(),
+                                    out_h.data_ptr()))
+        return out_c, out_m, out_h
+    host = [None if t is None else np.ascontiguousarray(np.asarray(t, np.float32).reshape(n, c)) for c, t in zip(cols, arrays)]
+    out_c = np.empty((n, 3), np.float32)
+    out_m = np.empty((n, 4), np.float32)
+    out_h = np.empty((n,), np.float32)
+    _check(lib, lib.fw_temporal(C.byref(p), *[None if t is None else t.ctypes.data for t in host], out_c.ctypes.data, out_m.ctypes.data,
+                                out_h.ctypes.data))
+    return out_c, out_m, out_h

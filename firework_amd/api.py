@@ -959,6 +959,10 @@ def orthographic_rays(camera: CameraSettings, view_height: float, width: int, he
     return _rays_out(o, d, device)
 
 
+# render_sequence's default cap on the samples a pixel carries over from the frames before it
+DEFAULT_MAX_HISTORY = 64.0
+
+
 def orbit_cameras(camera: CameraSettings, n: int) -> list:
     """n cameras evenly spaced in azimuth around `camera`'s look_at: view k rotates cam_pos - look_at about +Y by 2 pi k / n (computed
     in float64, rounded to float32); look_at, field of view, aperture and focus distance stay.  View 0 is `camera` itself, unchanged."""
@@ -979,6 +983,64 @@ def orbit_cameras(camera: CameraSettings, n: int) -> list:
         cam._cam_pos[1] = camera._cam_pos[1]                 # the height, exactly
         out.append(cam)
     return out
+
+
+def _placement_matrices(desc) -> tuple:
+    """(R (n, 3, 3), t (n, 3)) float64 of a SceneDesc's objects as RenderObjectInternal places them (scene.rs:235-266): world = R local + t,
+    R = Rotor3::into_matrix(rotation) — the identity where 0.5 (trace R - 1) >= 0.999, where the reference skips the rotation."""
+    n = int(desc.desc.n_objects)
+    R, t = np.zeros((n, 3, 3)), np.zeros((n, 3))
+    for i in range(n):
+        o = desc.objects[i]
+        r = o.rotation
+        s, xy, xz, yz = (np.float32(v) for v in (r.s, r.xy, r.xz, r.yz))
+        s2, bxy2, bxz2, byz2 = s * s, xy * xy, xz * xz, yz * yz
+        c0 = (s2 - bxy2 - bxz2 + byz2, np.float32(-2) * (xz * yz + s * xy), np.float32(2) * (xy * yz - s * xz))
+        c1 = (np.float32(2) * (s * xy - xz * yz), s2 - bxy2 + bxz2 - byz2, np.float32(-2) * (s * yz + xy * xz))
+        c2 = (np.float32(2) * (s * xz + xy * yz), np.float32(2) * (s * yz - xy * xz), s2 + bxy2 - bxz2 - byz2)
+        m = np.array([c0, c1, c2], np.float32).T.astype(np.float64)          # columns c0, c1, c2
+        R[i] = m if np.float32(0.5) * (np.float32(m[0, 0] + m[1, 1]) + np.float32(m[2, 2]) - np.float32(1)) < np.float32(0.999) else np.eye(3)
+        t[i] = (o.position.x, o.position.y, o.position.z)
+    return R, t
+
+
+def previous_positions(positions, objects, scene_before, scene_after):
+    """Where the surface points of a frame were one frame earlier, for the rigid placements DeviceScene.update (fw_scene_update) changes:
+    fw_temporal's prev_position.  positions: (N, 3) world positions in the frame rendered from `scene_after` (fw_render_aovs' position
+    columns); objects: (N,) the object each pixel shows, gbuffer()['object'] (FW_NO_HIT, or -1 in an int32 view, where the ray missed).
+    Each point goes back through its object's placement in scene_after and forward through the one in scene_before
+    (RenderObjectInternal, scene.rs:235-266: world = R local + position):  prev = R_b R_a^T (x - p_a) + p_b.  Missed pixels, and pixels of
+    objects that did not move, keep their position bit for bit.  Scenes: Scene or SceneDesc of the same objects — a Scene is read as it
+    is now, so pass the description made before it was moved.  numpy arrays give a float32 array, torch tensors a tensor on their device."""
+    da = scene_after if isinstance(scene_after, SceneDesc) else scene_after.to_desc()
+    db = scene_before if isinstance(scene_before, SceneDesc) else scene_before.to_desc()
+    n_obj = int(da.desc.n_objects)
+    if int(db.desc.n_objects) != n_obj:
+        raise ValueError(f"the scenes have {db.desc.n_objects} and {n_obj} objects")
+    Ra, ta = _placement_matrices(da)
+    Rb, tb = _placement_matrices(db)
+    M = np.einsum("nij,nkj->nik", Rb, Ra)                       # R_b R_a^T
+    moved = np.array([not (np.array_equal(Ra[i], Rb[i]) and np.array_equal(ta[i], tb[i])) for i in range(n_obj)], bool)
+    if type(positions).__module__.startswith("torch"):
+        import torch
+        dev = positions.device
+        obj = objects.to(torch.int64)
+        ok = (obj >= 0) & (obj < n_obj)
+        idx = torch.where(ok, obj, torch.zeros_like(obj))
+        ok = ok & torch.as_tensor(moved, device=dev)[idx] if n_obj else ok
+        x = positions.to(torch.float64)
+        Mt, tat, tbt = (torch.as_tensor(a, device=dev) for a in (M, ta, tb))
+        prev = torch.einsum("nij,nj->ni", Mt[idx], x - tat[idx]) + tbt[idx]
+        return torch.where(ok[:, None], prev.to(torch.float32), positions)
+    pos = np.asarray(positions, np.float32).reshape(-1, 3)
+    obj = np.asarray(objects).reshape(-1).astype(np.int64)
+    obj = np.where(obj == A.FW_NO_HIT, -1, obj)
+    ok = (obj >= 0) & (obj < n_obj)
+    idx = np.where(ok, obj, 0)
+    if n_obj:
+        ok = ok & moved[idx]
+    prev = np.einsum("nij,nj->ni", M[idx], pos.astype(np.float64) - ta[idx]) + tb[idx]
+    return np.where(ok[:, None], prev.astype(np.float32), pos)
 
 
 class Renderer:
@@ -1253,6 +1315,65 @@ class Renderer:
                 ds.close()
         rgb8, gam, lin = _lib.denoise(raw.linear, aov, moments, raw.width, raw.height, iterations, s["gamma"], dev)
         return RenderResult(rgb8, gam, lin, dict(raw.stats), raw.width, raw.height, raw=raw)
+
+    def render_sequence(self, scene, cameras, device: int = 0, temporal: bool = True, max_history: float = DEFAULT_MAX_HISTORY,
+                        iterations: int = 5, aov_samples: int = 8, updates=None):
+        """The frames of a sequence, one after another on one resident scene, each using the frame before it (not in the reference;
+        fw_temporal).  Frame k is rendered with cameras[k] and seed settings["seed"] + k — part of the contract: with one seed
+        for every frame an unmoved camera would merge identical noise.  Per frame: fw_render_adaptive with min_samples = samples (fw_render
+        for fewer than 2 samples), fw_render_aovs at `aov_samples`, fw_temporal against the previous frame's merged colour, moments and
+        guides (a pixel carries over at most `max_history` samples), then fw_denoise with `iterations` on the merged colour and moments;
+        everything stays on the device between the calls.  temporal=False leaves fw_temporal out: frame k then equals
+        render_denoised() with cameras[k] and seed + k bit for bit.  updates[k], if given and not None, is passed to DeviceScene.update
+        before frame k (a moved Scene or a SceneDesc), and the frame's prev_position comes from previous_positions().  Yields one
+        RenderResult of host arrays per frame, .raw = the frame before merging and filtering; .stats["history_mean"] is the mean
+        carried-over count.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        import copy
+        import torch
+        from . import _lib
+        s = self.settings
+        w, h, spp = int(s["width"]), int(s["height"]), int(s["samples"])
+        n = w * h
+        cameras = list(cameras)
+        if updates is not None and len(updates) != len(cameras):
+            raise ValueError("updates must have one entry (a scene or None) per camera")
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            dev = torch.device("cuda", ds.device)
+            f32 = dict(dtype=torch.float32, device=dev)
+            history, prev_cam = None, None
+            for k, cam in enumerate(cameras):
+                r = copy.copy(self); r.settings = dict(s); r.settings["seed"] = int(s["seed"]) + k; r._camera = cam
+                before = None
+                if updates is not None and updates[k] is not None:
+                    before = ds._desc
+                    ds.update(updates[k])
+                out = dict(rgb8=torch.empty((n, 3), dtype=torch.uint8, device=dev), gamma=torch.empty((n, 3), **f32),
+                           linear=torch.empty((n, 3), **f32))
+                if spp >= 2:
+                    out["moments"] = torch.empty((n, 4), **f32)
+                    stats = ds.render_adaptive(r, 1.0, spp, out=out).stats
+                else:
+                    stats = ds.render(r, None, (out["rgb8"].data_ptr(), out["gamma"].data_ptr(), out["linear"].data_ptr()),
+                                      torch.cuda.current_stream(dev).cuda_stream)
+                color, moments = out["linear"], out.get("moments")
+                aov = ds.aovs(r, aov_samples, out=torch.empty((n, 12), **f32))
+                stats = dict(stats)
+                if temporal:
+                    prev_pos = None
+                    if before is not None and history is not None:
+                        rays = torch.from_numpy(ds.camera_rays(r, 0)).to(dev)
+                        objects = _lib.hit_fields(ds.trace(rays, s["use_bvh"], seed=r.settings["seed"]))["object"]
+                        prev_pos = previous_positions(aov[:, 8:11].contiguous(), objects, before, ds._desc).contiguous()
+                    color, moments, n_h = _lib.temporal(color, aov, moments, history, prev_pos, w, h, cam, prev_cam, spp, max_history, ds.device)
+                    history, prev_cam = (color, moments, aov), cam
+                    stats["history_mean"] = float(n_h.mean().item())
+                rgb8, gam, lin = _lib.denoise(color, aov, moments, w, h, iterations, s["gamma"], ds.device)
+                raw = RenderResult(out["rgb8"].cpu().numpy(), out["gamma"].cpu().numpy(), out["linear"].cpu().numpy(), stats, w, h)
+                yield RenderResult(rgb8.cpu().numpy(), gam.cpu().numpy(), lin.cpu().numpy(), dict(stats), w, h, raw=raw)
+        finally:
+            if ds is not scene:
+                ds.close()
 
     def render(self, scene, device: int = 0) -> np.ndarray:
         """`pub fn render(&self, scene: Scene) -> Vec<Color>` (render.rs:109): (W*H, 3) uint8, row 0 = top."""

@@ -10,6 +10,7 @@
 #include "../../include/firework_hip.h"
 #include "fw_device.h"
 #include "fw_build.h"
+#include "fw_temporal.h"
 
 #include <algorithm>
 #include <atomic>
@@ -3457,6 +3458,95 @@ int denoise_impl(const fw_denoise_params *p, const float *color, const float *ao
     return FW_OK;
 }
 
+// fw_temporal's view of the previous camera: make_camera's position and basis, and w and the half extents as make_camera forms them
+static fw::TpCamera temporal_camera(const fw_camera_settings &s, uint32_t width, uint32_t height) {
+    const fw::DCamera c = make_camera(s, width, height);
+    const float PI_F = 3.14159265358979323846f;
+    const float theta = s.vfov * PI_F / 180.f;
+    const V3 w = normalized(tov(s.cam_pos) - tov(s.look_at));
+    fw::TpCamera t;
+    for (int k = 0; k < 3; k++) { t.pos[k] = c.position[k]; t.u[k] = c.u[k]; t.v[k] = c.v[k]; }
+    t.w[0] = w.x; t.w[1] = w.y; t.w[2] = w.z;
+    t.half_height = std::tan(theta / 2.0f);
+    t.half_width = t.half_height * (float)width / (float)height;
+    return t;
+}
+
+static bool camera_finite(const fw_camera_settings &c) {
+    const float f[9] = {c.cam_pos.x, c.cam_pos.y, c.cam_pos.z, c.look_at.x, c.look_at.y, c.look_at.z, c.vfov, c.aperture, c.focus_dist};
+    for (float v : f) if (!std::isfinite(v)) return false;
+    return true;
+}
+
+// fw_temporal: with host arrays one device allocation per call holds the inputs and outputs, released on every way out of this function;
+// with device arrays the kernel works on the caller's memory and nothing is allocated.
+int temporal_impl(const fw_temporal_params *p, const float *color, const float *moments, const float *aov, const float *hist_color,
+                  const float *hist_moments, const float *hist_aov, const float *prev_position, float *out_color, float *out_moments,
+                  float *out_history) {
+    if (!p || !color || !aov) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
+    const int n_hist = (hist_color ? 1 : 0) + (hist_moments ? 1 : 0) + (hist_aov ? 1 : 0);
+    if (n_hist != 0 && n_hist != 3) return fail(FW_ERR_BAD_ARG, "hist_color, hist_moments and hist_aov must be all NULL or all given");
+    {
+        const uint64_t px = (uint64_t)p->width * p->height;
+        const struct { const void *ptr; uint64_t bytes; } outs[3] = {{out_color, px * 12}, {out_moments, px * 16}, {out_history, px * 4}},
+                                                          hist[3] = {{hist_color, px * 12}, {hist_moments, px * 16}, {hist_aov, px * 48}};
+        for (const auto &o : outs)
+            for (const auto &h : hist)
+                if (o.ptr && h.ptr && (uintptr_t)o.ptr < (uintptr_t)h.ptr + h.bytes && (uintptr_t)h.ptr < (uintptr_t)o.ptr + o.bytes)
+                    return fail(FW_ERR_BAD_ARG, "an output overlaps a history array");
+    }
+    if (!(p->max_history > 0.f)) return fail(FW_ERR_BAD_ARG, "max_history must be > 0");
+    if (!camera_finite(p->camera) || !camera_finite(p->prev_camera)) return fail(FW_ERR_BAD_ARG, "camera fields must be finite");
+    if (p->device < 0 || p->device >= MAX_DEVICES) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    if (p->on_device && (((uintptr_t)aov | (uintptr_t)moments | (uintptr_t)hist_color | (uintptr_t)hist_moments | (uintptr_t)hist_aov |
+                          (uintptr_t)out_moments) & 15u))
+        return fail(FW_ERR_BAD_ARG, "device aov, moments, history and out_moments must be 16-byte aligned");
+    if (!moments && p->samples == 0) return fail(FW_ERR_BAD_ARG, "samples must be > 0 without moments");
+    const uint64_t full = (uint64_t)p->width * p->height;
+    if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (p->device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    const size_t n = (size_t)full;
+    const int dev = p->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)p->stream;
+    const fw::TpCamera cam = temporal_camera(p->prev_camera, p->width, p->height);
+    const float *d_col = color, *d_hc = hist_color, *d_pp = prev_position;
+    const float4 *d_mom = (const float4 *)moments, *d_aov = (const float4 *)aov, *d_hm = (const float4 *)hist_moments, *d_ha = (const float4 *)hist_aov;
+    float *d_oc = out_color, *d_oh = out_history; float4 *d_om = (float4 *)out_moments;
+    struct Scratch : DevBuf { int dev; explicit Scratch(int d) : dev(d) {} ~Scratch() { if (p) { (void)hipSetDevice(dev); release(); } } };
+    Scratch scratch(dev);
+    if (!p->on_device) {
+        size_t off = 0;
+        auto put = [&](const void *have, size_t b) { const size_t at = off; if (have) off += (b + 255) & ~(size_t)255; return at; };
+        const size_t o_col = put(color, n * 12), o_mom = put(moments, n * 16), o_aov = put(aov, n * 48), o_hc = put(hist_color, n * 12),
+                     o_hm = put(hist_moments, n * 16), o_ha = put(hist_aov, n * 48), o_pp = put(prev_position, n * 12),
+                     o_oc = put(out_color, n * 12), o_om = put(out_moments, n * 16), o_oh = put(out_history, n * 4);
+        if (int rc = scratch.alloc(std::max<size_t>(off, 256))) return rc;
+        uint8_t *base = (uint8_t *)scratch.p;
+#define FW_TP_UP(dst, type, src, at, bytes) \
+        if (src) { HIPCHK(hipMemcpyAsync(base + (at), src, bytes, hipMemcpyHostToDevice, stream)); dst = (type)(base + (at)); }
+        FW_TP_UP(d_col, const float *, color, o_col, n * 12) FW_TP_UP(d_aov, const float4 *, aov, o_aov, n * 48)
+        FW_TP_UP(d_mom, const float4 *, moments, o_mom, n * 16) FW_TP_UP(d_hc, const float *, hist_color, o_hc, n * 12)
+        FW_TP_UP(d_hm, const float4 *, hist_moments, o_hm, n * 16) FW_TP_UP(d_ha, const float4 *, hist_aov, o_ha, n * 48)
+        FW_TP_UP(d_pp, const float *, prev_position, o_pp, n * 12)
+#undef FW_TP_UP
+        d_oc = out_color ? (float *)(base + o_oc) : nullptr; d_om = out_moments ? (float4 *)(base + o_om) : nullptr;
+        d_oh = out_history ? (float *)(base + o_oh) : nullptr;
+    }
+    fw::launch_temporal(stream, p->width, p->height, cam, (float)p->samples, p->max_history, d_col, d_mom, d_aov, d_hc, d_hm, d_ha, d_pp, d_oc, d_om, d_oh);
+    if (!p->on_device) {
+        if (out_color) HIPCHK(hipMemcpyAsync(out_color, d_oc, n * 12, hipMemcpyDeviceToHost, stream));
+        if (out_moments) HIPCHK(hipMemcpyAsync(out_moments, d_om, n * 16, hipMemcpyDeviceToHost, stream));
+        if (out_history) HIPCHK(hipMemcpyAsync(out_history, d_oh, n * 4, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
 } // namespace
 
 // =========================================================================================================
@@ -3827,6 +3917,14 @@ int fw_denoise(const fw_denoise_params *p, const float *color, const float *aov,
 
 // ---- single-process multi-GPU: one host thread per device, 16x16 tiles dealt diagonally (the scheme of firework_amd/tiles.py),
 // each device renders its pixels with the keys one GPU would use, results are scattered into the caller's buffers.
+int fw_temporal(const fw_temporal_params *p, const float *color, const float *moments, const float *aov, const float *hist_color,
+                const float *hist_moments, const float *hist_aov, const float *prev_position, float *out_color, float *out_moments,
+                float *out_history) {
+    try { return temporal_impl(p, color, moments, aov, hist_color, hist_moments, hist_aov, prev_position, out_color, out_moments, out_history); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_temporal"); }
+}
+
 int fw_render_scene_tiled(const fw_scene_desc *desc, const fw_render_params *params, const int *devices, int n_devices,
                           uint8_t *rgb8, float *gamma_rgb, float *linear_rgb, fw_stats *stats) {
     if (!desc || !params || !devices || n_devices <= 0) return fail(FW_ERR_BAD_ARG, "null argument");

@@ -548,6 +548,66 @@ typedef struct fw_denoise_params {
 int fw_denoise(const fw_denoise_params *p, const float *color, const float *aov, const float *moments,
                float *linear_rgb, float *gamma_rgb, uint8_t *rgb8);
 
+/* fw_temporal: temporal accumulation, the other half of SVGF (Schied et al. 2017) — the previous frame's colour and moments are
+   reprojected through the guide buffers, tested geometrically and merged with the current frame by sample counts; on the device in
+   float32.  N = width x height pixels, row-major, row 0 = top.
+     current : color (N x 3, a linear_rgb), moments (N x 4, fw_render_adaptive's layout: sums of squares of r, g, b and .w = the count
+               n) or NULL, aov (N x 12, fw_render_aovs' records).  moments == NULL: n = params.samples and Q_c = n * (c_c * c_c),
+               which is exact for one sample per pixel and a lower bound on the variance otherwise.
+     history : hist_color (N x 3), hist_moments (N x 4): the previous call's out_color and out_moments; hist_aov (N x 12): the previous
+               frame's guides.  All three NULL = a first frame: out_color = color and out_moments = moments (or the substitute above)
+               bit for bit, out_history = 0.
+     prev_position : N x 3 or NULL — for each current pixel the world position its first-hit surface point had in the previous frame.
+               NULL = a static scene: aov's position.
+     outputs : out_color (N x 3), out_moments (N x 4, the same layout: it feeds fw_denoise and the next fw_temporal unchanged),
+               out_history (N floats: the carried-over count n_h, 0 where the history was rejected).  Any may be NULL; none may overlap a
+               history array (the kernel gathers).
+   Per current pixel p, with X = prev_position[p] or aov[p]'s position, n_p its normal, a_p its albedo, c its colour, (Q_c, n_c) its
+   moments, eps = FW_DENOISE_EPS:
+     1 pass     : coverage 0, or a non-finite c or X: out = the current values, n_h = 0.
+     2 project  : with prev_camera's basis (camera.rs:74-107: w = normalize(cam_pos - look_at), u^ = normalize(cross((0, 1, 0), w)),
+                  v^ = cross(w, u^), half_height = tan(vfov / 2), half_width = half_height * W / H):  e = X - cam_pos;
+                  depth = -e.w (history rejected unless > 0);  u = 1/2 + (e.u^) / (2 half_width depth);
+                  v = 1/2 + (e.v^) / (2 half_height depth);  x = u W - 1/2 the continuous column, row = H - (v H - 1/2) the continuous
+                  row: the inverse of the camera ray through (x + 1/2, row + 1/2) (render.rs:178-179, util.rs's row shift included).
+                  The history is rejected unless -1 < x < W and -1 < row < H.
+     3 taps     : q = (floor x, floor row) + {0, 1}^2 with the bilinear weights b_q.  A tap is dropped if it lies outside the image;
+                  b_q < FW_TEMPORAL_MIN_TAP (a camera that did not move keeps one tap of weight 1); its hist_color, hist_moments, or
+                  hist_aov albedo, coverage or position is not finite; its count is not > 0; its coverage is 0;
+                  n_p.n_q < FW_TEMPORAL_NORMAL_COS (both normalised: AOV normals are means; a zero or non-finite normal, n_p's included,
+                  fails); |n_p.(x_q - X)| > FW_TEMPORAL_PLANE |X - prev cam_pos|.  No surviving tap: the history is rejected.
+                  Otherwise b_q := b_q / sum of the survivors' b.
+     4 resample : demodulated, so that the taps do not blur textures:  mean_h = (a_p + eps) sum b_q hist_color_q / (a_q + eps) per channel;
+                  m2_h = (a_p + eps)^2 sum b_q (Q_q / n_q) / (a_q + eps)^2;  n_h = min(sum b_q n_q, max_history).
+     5 merge    : n = n_h + n_c;  out_color = (n_h mean_h + n_c c) / n;  out Q = n_h m2_h + Q_c;  out .w = n;  out_history = n_h.
+                  A merge that gives a non-finite value is a rejected history.  A rejected history gives the current values and n_h = 0.
+   One launch, one thread per pixel, no atomics: two calls give the same bits.  IEEE float32 without contraction, the kernels' division
+   and square root.  Specular surfaces lag: what is reprojected is the first hit.  Device scratch (host arrays only) is allocated per
+   call and freed on every path.  With on_device every array is a device pointer on `device` and the launch goes to `stream` (complete
+   on return).  Errors, all before HIP is called, in this order: FW_ERR_BAD_ARG for a NULL p, color or aov; width or height 0; a history
+   that is only partly NULL; an output that overlaps a history array; max_history NaN or <= 0 (INFINITY is allowed); a camera with a
+   non-finite field; device < 0; with on_device an aov, moments, history or out_moments array not 16-byte aligned; moments == NULL with
+   samples == 0.  Then FW_ERR_UNSUPPORTED for W x H >= 2^32, FW_ERR_NO_DEVICE without a GPU, FW_ERR_BAD_ARG for a device index past the
+   last one. */
+#define FW_TEMPORAL_NORMAL_COS 0.9f
+#define FW_TEMPORAL_PLANE 0.02f
+#define FW_TEMPORAL_MIN_TAP 1e-3f
+
+typedef struct fw_temporal_params {
+    uint32_t width, height;
+    fw_camera_settings camera;       /* the current frame's camera (not read by the statement above; kept with the frame it describes) */
+    fw_camera_settings prev_camera;  /* the camera hist_aov was rendered with */
+    uint32_t samples;                /* the current frame's count where moments == NULL */
+    float max_history;               /* > 0: the largest sample count a pixel carries over; INFINITY = no cap */
+    int32_t device;
+    int32_t on_device;               /* every array is a device pointer on `device` */
+    void *stream;                    /* hipStream_t, NULL = default */
+} fw_temporal_params;
+
+int fw_temporal(const fw_temporal_params *p, const float *color, const float *moments, const float *aov,
+                const float *hist_color, const float *hist_moments, const float *hist_aov, const float *prev_position,
+                float *out_color, float *out_moments, float *out_history);
+
 /* Diagnostic: the kernels' division / square-root helpers against the compiler's IEEE expansion, bit for bit,
    on n hashed operand pairs.  mode 0 = magnitudes 2^-40..2^40 (must be 0 mismatches), mode 1 = all bit patterns. */
 int fw_selftest_arith(int device, uint32_t n, uint32_t seed, int mode, uint64_t *div_mismatches, uint64_t *sqrt_mismatches);
