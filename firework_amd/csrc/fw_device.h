@@ -309,28 +309,20 @@ void launch_extend(const LaunchCfg &, const DScene &, const DFrame &, DPaths in,
 void launch_extend_exact(const LaunchCfg &, const DScene &, const DFrame &, const DPaths &in, float2 *hits, int segment, bool use_bvh);
 void launch_shade(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
                   float4 *sample_rad, int segment);
-// light sampling: k_shade's light-sampling instantiation (k_shade_ls; the frame has no chain state, no hit4, no EXACT_PRODUCT and
-// deposits every path) and the resolve of one segment's shadow rays after their walk
-void launch_shade_ls(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
-                     float4 *sample_rad, int segment, const DShadow &);
-void launch_shadow_resolve(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment);
-// environment sampling: k_shade_ls with the environment among the sampled lights (k_shade_env; shading mode 0 only: an HDR map
-// is an expensive case), the resolve that also takes environment shadow rays (visible iff they miss), and the table build
-void launch_shade_env(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
-                      float4 *sample_rad, int segment, const DShadow &, const DEnvDist &);
-void launch_shadow_resolve_env(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment);
+// light sampling: k_shade's light-sampling kernels (the frame has no chain state, no hit4, no EXACT_PRODUCT and deposits
+// every path) and the resolve of one segment's shadow rays after their walk.  ed: the environment is among the sampled lights (§9h:
+// k_shade_env; shading mode 0 only: an HDR map is an expensive case); em: the emitters are the entries of *em (§9i: k_shade_pl); both:
+// k_shade_pl_env; neither: §9g's k_shade_ls.  The resolve's rule follows: plain (the closest hit is the sampled light's object), env (also
+// environment shadow rays, visible iff they miss), pl (the full hit code: visible iff the closest hit is the sampled primitive, or a miss
+// for an environment ray)
+void launch_shade_nee(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
+                      float4 *sample_rad, int segment, const DShadow &, const DEnvDist *ed, const DEmitters *em);
+void launch_shadow_resolve(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment, bool env, bool pl);
 // the table of env (w x h): scratch = 2 h + 1 doubles (row totals, the total); p_out (optional): the per-texel probabilities; *total = the total weight
 // (host memory, after a synchronisation of `stream`)
 int build_env_dist(hipStream_t stream, const DEnv &env, float *cdf_m, float *cdf_c, float *dens, float *p_out, double *scratch, double *total);
 // n samples of the table (fw_selftest_env_sample): per sample (dir xyz, reported pdf, drawn index, looked-up index)
 void launch_env_sample_test(hipStream_t stream, const DEnv &env, const DEnvDist &ed, uint32_t n, uint32_t seed32, float *out);
-// every emitter: k_shade_ls / k_shade_env with the entries of *em as the emitters (k_shade_pl, k_shade_pl_env), the resolve that
-// compares the full hit code (visible iff the closest hit is the sampled primitive, or a miss for an environment ray), and the weight pass
-void launch_shade_pl(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
-                     float4 *sample_rad, int segment, const DShadow &, const DEmitters &);
-void launch_shade_pl_env(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
-                         float4 *sample_rad, int segment, const DShadow &, const DEnvDist &, const DEmitters &);
-void launch_shadow_resolve_pl(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment);
 // w[e] of n entries: ent[e].z holds the entry's weight, or for a triangle the object's power (its area is taken from sc.tri here)
 void launch_emitter_weights(hipStream_t stream, const DScene &sc, const uint4 *ent, uint32_t n, float *w);
 // n picks from the point x (fw_selftest_emitter_sample): per pick FW_EMITTER_SAMPLE_FLOATS floats

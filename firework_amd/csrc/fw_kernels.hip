@@ -3552,18 +3552,8 @@ __global__ __launch_bounds__(WB) void k_shade(DScene sc, DFrame f, DPaths in, DP
                                                  float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                  uint32_t n_mat, uint32_t n_tex) {
     const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
-    const float4 *objp = sc.obj, *matp = sc.mat, *texp = sc.tex;
     __shared__ uint16_t shade_list[128];                                 // MODE 2: queue positions of the expensive paths not yet shaded (< 64 + 64)
-    if (sc.has_perlin && MODE != 1 && !CHAIN) { stage_perm(); if (!LDS_TAB) __syncthreads(); }
-    if (LDS_TAB) {
-        const uint32_t no = LDS_TAB == 1 ? sc.n_objects * OBJ_Q : 0u, nm = 2 * n_mat, nt = 2 * n_tex;
-        if (LDS_TAB == 1) for (uint32_t k = threadIdx.x; k < no; k += WB) lds_tables[k] = sc.obj[k];
-        for (uint32_t k = threadIdx.x; k < nm; k += WB) lds_tables[no + k] = sc.mat[k];
-        for (uint32_t k = threadIdx.x; k < nt; k += WB) lds_tables[no + nm + k] = sc.tex[k];
-        __syncthreads();
-        if (LDS_TAB == 1) objp = lds_tables;
-        matp = lds_tables + no; texp = lds_tables + no + nm;
-    }
+#include "fw_shade_tables.inc"
     if (w >= q.n_waves) return;
     const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
     const uint32_t base = w * q.cap;
@@ -3706,146 +3696,31 @@ __global__ __launch_bounds__(WB) void k_shade(DScene sc, DFrame f, DPaths in, DP
 // Light sampling: k_shade with the light sample of every Lambertian / Isotropic vertex appended to the shadow queue, the
 // BSDF's p_b carried with each ray (sh.pb_in / pb_out) and the MIS weight on the emission it reaches.  k_shade's table modes and its
 // modes 0 and 1 (in line; MODE 1: nothing expensive in the scene), without the chain state: a light-sampling frame carries the running
-// product.  A kernel of its own, so that k_shade's instantiations stay as they are.
+// product.  A kernel of its own, so that k_shade's instantiations stay as they are.  Its body is fw_shade_nee.inc, which the kernels of
+// §9h and §9i below include as well: the four differ in their arguments and in what they hand to shade_path.  Shared as text and not as
+// a device function: with the function all 18 instantiations compiled to other instruction streams (instructions +-1 %, SGPR spills up
+// to +10), and included text compiles to the kernel it was (as fw_accumulate_walk.inc does for k_accumulate).
 template <int LDS_TAB, int MODE>
 __attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
 __global__ __launch_bounds__(WB) void k_shade_ls(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
                                                     float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                     uint32_t n_mat, uint32_t n_tex, DShadow sh) {
-    static_assert(MODE == 0 || MODE == 1, "in line only");
-    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
-    const float4 *objp = sc.obj, *matp = sc.mat, *texp = sc.tex;
-    if (sc.has_perlin && MODE != 1) { stage_perm(); if (!LDS_TAB) __syncthreads(); }
-    if (LDS_TAB) {
-        const uint32_t no = LDS_TAB == 1 ? sc.n_objects * OBJ_Q : 0u, nm = 2 * n_mat, nt = 2 * n_tex;
-        if (LDS_TAB == 1) for (uint32_t k = threadIdx.x; k < no; k += WB) lds_tables[k] = sc.obj[k];
-        for (uint32_t k = threadIdx.x; k < nm; k += WB) lds_tables[no + k] = sc.mat[k];
-        for (uint32_t k = threadIdx.x; k < nt; k += WB) lds_tables[no + nm + k] = sc.tex[k];
-        __syncthreads();
-        if (LDS_TAB == 1) objp = lds_tables;
-        matp = lds_tables + no; texp = lds_tables + no + nm;
-    }
-    if (w >= q.n_waves) return;
-    const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
-    const uint32_t base = w * q.cap;
-    uint32_t out_n = 0, sh_n = 0;                                        // survivors / shadow rays written so far (wave-uniform)
-    PH_DECL;
-    float4 ra_n = make_float4(0, 0, 0, 0), st_n = ra_n; float2 rb_n = make_float2(0, 0), hr_n = rb_n; float pb_n = 0.f;
-    auto fetch = [&](uint32_t i) {
-        ra_n = qld(&in.ray_a[i]); rb_n = load_ray_b(in, i, f, segment); st_n = load_state(in, i, segment); hr_n = qld(&hits[i]);
-        pb_n = segment > 0 ? sh.pb_in[i] : 0.f;
-    };
-    if (lane < n) fetch(base + lane);
-    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
-        const uint32_t j = c0 + lane, i = base + j;
-        float4 ra = ra_n, st = st_n; float2 rb = rb_n, hr = hr_n;
-        LsIO ls{pb_n, 0.f, false, Ray{mk(0, 0, 0), mk(0, 0, 0)}, 0u, mk(0, 0, 0)};
-        if (j + 64u < n) fetch(i + 64u);
-        bool alive = false;
-        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
-        if (j < n) {
-            path_id = __float_as_uint(st.w);
-            alive = shade_path<MODE != 0, false, true>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id, hr.x,
-                                                       __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS, nullptr, &sh, &ls);
-        }
-        // k_shade's compaction, with p_b next to the state
-        const unsigned long long mask = __ballot(alive);
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        if (alive) {
-            const uint32_t dst = base + out_n + rank;
-            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
-            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
-            qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
-            sh.pb_out[dst] = ls.pb_out;
-        }
-        if (f.ex.mode) flag_exact(f.ex, alive && needs_exact(f.ex, nr.o.x, nr.o.y, nr.o.z, nr.d.x, nr.d.y, nr.d.z), base + out_n + rank, segment + 1);
-        out_n += (uint32_t)__popcll(mask);
-        // the shadow rays: the same compaction, into the wave's region of the shadow queue
-        const unsigned long long sm = __ballot(ls.shadow);
-        if (sm) {
-            const uint32_t sr = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
-            if (ls.shadow) {
-                const uint32_t d = base + sh_n + sr;
-                sh.ray_a[d] = make_float4(ls.sray.o.x, ls.sray.o.y, ls.sray.o.z, ls.sray.d.x);
-                sh.ray_b[d] = make_float2(ls.sray.d.y, ls.sray.d.z);
-                sh.state[d] = make_float4(ls.pending.x, ls.pending.y, ls.pending.z, __uint_as_float(path_id));
-                sh.obj[d] = ls.sobj;
-            }
-            sh_n += (uint32_t)__popcll(sm);
-        }
-    }
-    if (lane == 0) { q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n; sh.wcount[(size_t)(segment + 1) * q.n_waves + w] = sh_n; }
+    constexpr bool ENV = false, PL = false;
+    const DEnvDist *const edp = nullptr; const DEmitters *const emp = nullptr;
+#include "fw_shade_nee.inc"
 }
-// Environment sampling: k_shade_ls with the environment among the sampled lights (*ed), in shading mode 0 only (an HDR map is an
-// expensive case: the scene never takes mode 1).  A copy of k_shade_ls's body rather than a template parameter of it: with a shared body
-// k_shade_ls's instruction stream and SGPR spills changed, and §9g's kernels stay as they are.
+// Environment sampling: k_shade_ls with the environment among the sampled lights (*ed), in shading mode 0 only.  A kernel of its
+// own around k_shade_ls's body (fw_shade_nee.inc) rather than a template parameter of k_shade_ls: *ed is one more kernel argument, which
+// k_shade_ls would carry too, and §9g's kernels stay as they are.
 template <int LDS_TAB>
 __attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
 __global__ __launch_bounds__(WB) void k_shade_env(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
                                                      float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                      uint32_t n_mat, uint32_t n_tex, DShadow sh, DEnvDist ed) {
-    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
-    const float4 *objp = sc.obj, *matp = sc.mat, *texp = sc.tex;
-    if (sc.has_perlin) { stage_perm(); if (!LDS_TAB) __syncthreads(); }
-    if (LDS_TAB) {
-        const uint32_t no = LDS_TAB == 1 ? sc.n_objects * OBJ_Q : 0u, nm = 2 * n_mat, nt = 2 * n_tex;
-        if (LDS_TAB == 1) for (uint32_t k = threadIdx.x; k < no; k += WB) lds_tables[k] = sc.obj[k];
-        for (uint32_t k = threadIdx.x; k < nm; k += WB) lds_tables[no + k] = sc.mat[k];
-        for (uint32_t k = threadIdx.x; k < nt; k += WB) lds_tables[no + nm + k] = sc.tex[k];
-        __syncthreads();
-        if (LDS_TAB == 1) objp = lds_tables;
-        matp = lds_tables + no; texp = lds_tables + no + nm;
-    }
-    if (w >= q.n_waves) return;
-    const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
-    const uint32_t base = w * q.cap;
-    uint32_t out_n = 0, sh_n = 0;                                        // survivors / shadow rays written so far (wave-uniform)
-    PH_DECL;
-    float4 ra_n = make_float4(0, 0, 0, 0), st_n = ra_n; float2 rb_n = make_float2(0, 0), hr_n = rb_n; float pb_n = 0.f;
-    auto fetch = [&](uint32_t i) {
-        ra_n = qld(&in.ray_a[i]); rb_n = load_ray_b(in, i, f, segment); st_n = load_state(in, i, segment); hr_n = qld(&hits[i]);
-        pb_n = segment > 0 ? sh.pb_in[i] : 0.f;
-    };
-    if (lane < n) fetch(base + lane);
-    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
-        const uint32_t j = c0 + lane, i = base + j;
-        float4 ra = ra_n, st = st_n; float2 rb = rb_n, hr = hr_n;
-        LsIO ls{pb_n, 0.f, false, Ray{mk(0, 0, 0), mk(0, 0, 0)}, 0u, mk(0, 0, 0)};
-        if (j + 64u < n) fetch(i + 64u);
-        bool alive = false;
-        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
-        if (j < n) {
-            path_id = __float_as_uint(st.w);
-            alive = shade_path<false, false, true, true>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id, hr.x,
-                                                            __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS, nullptr, &sh, &ls, &ed);
-        }
-        // k_shade's compaction, with p_b next to the state
-        const unsigned long long mask = __ballot(alive);
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        if (alive) {
-            const uint32_t dst = base + out_n + rank;
-            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
-            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
-            qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
-            sh.pb_out[dst] = ls.pb_out;
-        }
-        if (f.ex.mode) flag_exact(f.ex, alive && needs_exact(f.ex, nr.o.x, nr.o.y, nr.o.z, nr.d.x, nr.d.y, nr.d.z), base + out_n + rank, segment + 1);
-        out_n += (uint32_t)__popcll(mask);
-        // the shadow rays: the same compaction, into the wave's region of the shadow queue
-        const unsigned long long sm = __ballot(ls.shadow);
-        if (sm) {
-            const uint32_t sr = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
-            if (ls.shadow) {
-                const uint32_t d = base + sh_n + sr;
-                sh.ray_a[d] = make_float4(ls.sray.o.x, ls.sray.o.y, ls.sray.o.z, ls.sray.d.x);
-                sh.ray_b[d] = make_float2(ls.sray.d.y, ls.sray.d.z);
-                sh.state[d] = make_float4(ls.pending.x, ls.pending.y, ls.pending.z, __uint_as_float(path_id));
-                sh.obj[d] = ls.sobj;
-            }
-            sh_n += (uint32_t)__popcll(sm);
-        }
-    }
-    if (lane == 0) { q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n; sh.wcount[(size_t)(segment + 1) * q.n_waves + w] = sh_n; }
+    constexpr int MODE = 0;                  // an HDR map is an expensive case: the scene never takes mode 1
+    constexpr bool ENV = true, PL = false;
+    const DEnvDist *const edp = &ed; const DEmitters *const emp = nullptr;
+#include "fw_shade_nee.inc"
 }
 // One segment's shadow rays after their walk: a ray whose closest hit is the light it sampled adds its pending radiance to the path's
 // nee record.  One shadow ray per path and segment, segments in stream order: no atomics.
@@ -3874,146 +3749,26 @@ __global__ __launch_bounds__(WB) void k_shadow_resolve_env(DShadow sh, const flo
         e = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, 0.f);
     }
 }
-// Every emitter: k_shade_ls and k_shade_env with the entries of `em` as the emitters (shade_path's PL).  Copies of their bodies,
-// as k_shade_env is of k_shade_ls's, so that §9g's and §9h's kernels stay as they are.
+// Every emitter: k_shade_ls and k_shade_env with the entries of `em` as the emitters (shade_path's PL).  The same body again,
+// and kernels of their own for the same reason: §9g's and §9h's kernels stay as they are.
 template <int LDS_TAB, int MODE>
 __attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
 __global__ __launch_bounds__(WB) void k_shade_pl(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
                                                     float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                     uint32_t n_mat, uint32_t n_tex, DShadow sh, DEmitters em) {
-    static_assert(MODE == 0 || MODE == 1, "in line only");
-    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
-    const float4 *objp = sc.obj, *matp = sc.mat, *texp = sc.tex;
-    if (sc.has_perlin && MODE != 1) { stage_perm(); if (!LDS_TAB) __syncthreads(); }
-    if (LDS_TAB) {
-        const uint32_t no = LDS_TAB == 1 ? sc.n_objects * OBJ_Q : 0u, nm = 2 * n_mat, nt = 2 * n_tex;
-        if (LDS_TAB == 1) for (uint32_t k = threadIdx.x; k < no; k += WB) lds_tables[k] = sc.obj[k];
-        for (uint32_t k = threadIdx.x; k < nm; k += WB) lds_tables[no + k] = sc.mat[k];
-        for (uint32_t k = threadIdx.x; k < nt; k += WB) lds_tables[no + nm + k] = sc.tex[k];
-        __syncthreads();
-        if (LDS_TAB == 1) objp = lds_tables;
-        matp = lds_tables + no; texp = lds_tables + no + nm;
-    }
-    if (w >= q.n_waves) return;
-    const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
-    const uint32_t base = w * q.cap;
-    uint32_t out_n = 0, sh_n = 0;                                        // survivors / shadow rays written so far (wave-uniform)
-    PH_DECL;
-    float4 ra_n = make_float4(0, 0, 0, 0), st_n = ra_n; float2 rb_n = make_float2(0, 0), hr_n = rb_n; float pb_n = 0.f;
-    auto fetch = [&](uint32_t i) {
-        ra_n = qld(&in.ray_a[i]); rb_n = load_ray_b(in, i, f, segment); st_n = load_state(in, i, segment); hr_n = qld(&hits[i]);
-        pb_n = segment > 0 ? sh.pb_in[i] : 0.f;
-    };
-    if (lane < n) fetch(base + lane);
-    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
-        const uint32_t j = c0 + lane, i = base + j;
-        float4 ra = ra_n, st = st_n; float2 rb = rb_n, hr = hr_n;
-        LsIO ls{pb_n, 0.f, false, Ray{mk(0, 0, 0), mk(0, 0, 0)}, 0u, mk(0, 0, 0)};
-        if (j + 64u < n) fetch(i + 64u);
-        bool alive = false;
-        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
-        if (j < n) {
-            path_id = __float_as_uint(st.w);
-            alive = shade_path<MODE != 0, false, true, false, true>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id,
-                                                                     hr.x, __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS, nullptr, &sh, &ls,
-                                                                     nullptr, &em);
-        }
-        // k_shade's compaction, with p_b next to the state
-        const unsigned long long mask = __ballot(alive);
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        if (alive) {
-            const uint32_t dst = base + out_n + rank;
-            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
-            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
-            qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
-            sh.pb_out[dst] = ls.pb_out;
-        }
-        if (f.ex.mode) flag_exact(f.ex, alive && needs_exact(f.ex, nr.o.x, nr.o.y, nr.o.z, nr.d.x, nr.d.y, nr.d.z), base + out_n + rank, segment + 1);
-        out_n += (uint32_t)__popcll(mask);
-        // the shadow rays: the same compaction, into the wave's region of the shadow queue
-        const unsigned long long sm = __ballot(ls.shadow);
-        if (sm) {
-            const uint32_t sr = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
-            if (ls.shadow) {
-                const uint32_t d = base + sh_n + sr;
-                sh.ray_a[d] = make_float4(ls.sray.o.x, ls.sray.o.y, ls.sray.o.z, ls.sray.d.x);
-                sh.ray_b[d] = make_float2(ls.sray.d.y, ls.sray.d.z);
-                sh.state[d] = make_float4(ls.pending.x, ls.pending.y, ls.pending.z, __uint_as_float(path_id));
-                sh.obj[d] = ls.sobj;
-            }
-            sh_n += (uint32_t)__popcll(sm);
-        }
-    }
-    if (lane == 0) { q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n; sh.wcount[(size_t)(segment + 1) * q.n_waves + w] = sh_n; }
+    constexpr bool ENV = false, PL = true;
+    const DEnvDist *const edp = nullptr; const DEmitters *const emp = &em;
+#include "fw_shade_nee.inc"
 }
 template <int LDS_TAB>
 __attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
 __global__ __launch_bounds__(WB) void k_shade_pl_env(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
                                                      float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                      uint32_t n_mat, uint32_t n_tex, DShadow sh, DEnvDist ed, DEmitters em) {
-    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
-    const float4 *objp = sc.obj, *matp = sc.mat, *texp = sc.tex;
-    if (sc.has_perlin) { stage_perm(); if (!LDS_TAB) __syncthreads(); }
-    if (LDS_TAB) {
-        const uint32_t no = LDS_TAB == 1 ? sc.n_objects * OBJ_Q : 0u, nm = 2 * n_mat, nt = 2 * n_tex;
-        if (LDS_TAB == 1) for (uint32_t k = threadIdx.x; k < no; k += WB) lds_tables[k] = sc.obj[k];
-        for (uint32_t k = threadIdx.x; k < nm; k += WB) lds_tables[no + k] = sc.mat[k];
-        for (uint32_t k = threadIdx.x; k < nt; k += WB) lds_tables[no + nm + k] = sc.tex[k];
-        __syncthreads();
-        if (LDS_TAB == 1) objp = lds_tables;
-        matp = lds_tables + no; texp = lds_tables + no + nm;
-    }
-    if (w >= q.n_waves) return;
-    const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
-    const uint32_t base = w * q.cap;
-    uint32_t out_n = 0, sh_n = 0;                                        // survivors / shadow rays written so far (wave-uniform)
-    PH_DECL;
-    float4 ra_n = make_float4(0, 0, 0, 0), st_n = ra_n; float2 rb_n = make_float2(0, 0), hr_n = rb_n; float pb_n = 0.f;
-    auto fetch = [&](uint32_t i) {
-        ra_n = qld(&in.ray_a[i]); rb_n = load_ray_b(in, i, f, segment); st_n = load_state(in, i, segment); hr_n = qld(&hits[i]);
-        pb_n = segment > 0 ? sh.pb_in[i] : 0.f;
-    };
-    if (lane < n) fetch(base + lane);
-    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
-        const uint32_t j = c0 + lane, i = base + j;
-        float4 ra = ra_n, st = st_n; float2 rb = rb_n, hr = hr_n;
-        LsIO ls{pb_n, 0.f, false, Ray{mk(0, 0, 0), mk(0, 0, 0)}, 0u, mk(0, 0, 0)};
-        if (j + 64u < n) fetch(i + 64u);
-        bool alive = false;
-        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
-        if (j < n) {
-            path_id = __float_as_uint(st.w);
-            alive = shade_path<false, false, true, true, true>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id,
-                                                                  hr.x, __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS, nullptr, &sh, &ls,
-                                                                  &ed, &em);
-        }
-        // k_shade's compaction, with p_b next to the state
-        const unsigned long long mask = __ballot(alive);
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        if (alive) {
-            const uint32_t dst = base + out_n + rank;
-            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
-            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
-            qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
-            sh.pb_out[dst] = ls.pb_out;
-        }
-        if (f.ex.mode) flag_exact(f.ex, alive && needs_exact(f.ex, nr.o.x, nr.o.y, nr.o.z, nr.d.x, nr.d.y, nr.d.z), base + out_n + rank, segment + 1);
-        out_n += (uint32_t)__popcll(mask);
-        // the shadow rays: the same compaction, into the wave's region of the shadow queue
-        const unsigned long long sm = __ballot(ls.shadow);
-        if (sm) {
-            const uint32_t sr = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
-            if (ls.shadow) {
-                const uint32_t d = base + sh_n + sr;
-                sh.ray_a[d] = make_float4(ls.sray.o.x, ls.sray.o.y, ls.sray.o.z, ls.sray.d.x);
-                sh.ray_b[d] = make_float2(ls.sray.d.y, ls.sray.d.z);
-                sh.state[d] = make_float4(ls.pending.x, ls.pending.y, ls.pending.z, __uint_as_float(path_id));
-                sh.obj[d] = ls.sobj;
-            }
-            sh_n += (uint32_t)__popcll(sm);
-        }
-    }
-    if (lane == 0) { q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n; sh.wcount[(size_t)(segment + 1) * q.n_waves + w] = sh_n; }
+    constexpr int MODE = 0;                  // (as k_shade_env)
+    constexpr bool ENV = true, PL = true;
+    const DEnvDist *const edp = &ed; const DEmitters *const emp = &em;
+#include "fw_shade_nee.inc"
 }
 // The resolve of k_shade_pl / k_shade_pl_env: sh.obj holds the sampled primitive's full hit code (object << prim_bits | prim; MISS for an
 // environment ray), and a shadow ray counts iff its closest hit code equals it: a mesh can hide its own triangles, a box its back faces.
@@ -4829,83 +4584,56 @@ void launch_extend_exact(const LaunchCfg &c, const DScene &sc, const DFrame &f, 
     // 8 single-wave workgroups per CU: most launches find an empty list, and dispatching 4 096 workgroups that only read a counter took 12 us
     hipLaunchKernelGGL(k_extend_exact, dim3((uint32_t)c.n_cus * 8u), dim3(EXACT_WB), lds, c.stream, sc, f, in, hits, segment, use_bvh ? 1 : 0, tl, c.exact_form);
 }
+// The shade kernels' table mode (fw_shade_tables.inc's LDS_TAB) and the dynamic LDS it takes: 1 everything in LDS | 2 materials + textures
+// only (the two dependent fetches behind the object record: part2 k_shade 6.7 -> 6.55 ms; a leaner per-kind object fetch on top — 3 loads
+// instead of 6 for an unrotated sphere — did not pay: 6.8 ms) | 0 none
+struct ShadeTables { int lt; size_t lds; };
+static ShadeTables shade_tables(const LaunchCfg &c, const DScene &sc) {
+    const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4), tab = (size_t)sc.n_objects * OBJ_Q * sizeof(float4) + tab_mt;
+    if (c.lds_tables && tab <= LDS_TABLE_LIMIT) return {1, tab};
+    if (c.lds_tables && tab_mt <= LDS_TABLE_LIMIT) return {2, tab_mt};
+    return {0, 0};
+}
 void launch_shade(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
                   float4 *sample_rad, int segment) {
-    size_t tab = ((size_t)sc.n_objects * OBJ_Q + 2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    // table mode: everything in LDS | materials + textures only (the two dependent fetches behind the object record: part2 k_shade
-    // 6.7 -> 6.55 ms; a leaner per-kind object fetch on top — 3 loads instead of 6 for an unrotated sphere — did not pay: 6.8 ms) | none
-    const int lt = (c.lds_tables && tab <= LDS_TABLE_LIMIT) ? 1 : ((c.lds_tables && tab_mt <= LDS_TABLE_LIMIT) ? 2 : 0);
-    const size_t lds = lt == 1 ? tab : (lt == 2 ? tab_mt : 0);
+    const ShadeTables t = shade_tables(c, sc);
     // shading mode (k_shade): 0 everything in line | 1 the scene has nothing expensive | 2 expensive paths through the list
     const int mode = c.shade_mode;
-#define FW_SHADE(L, M, C) hipLaunchKernelGGL((k_shade<L, M, C>), wave_grid(c), dim3(WB), lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex)
+#define FW_SHADE(L, M, C) hipLaunchKernelGGL((k_shade<L, M, C>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex)
 #define FW_SHADE_C(L, M) do { if (f.chain_bits) FW_SHADE(L, M, true); else FW_SHADE(L, M, false); } while (0)
 #if FW_AB
 #define FW_SHADE_L(L) do { if (mode == 2) FW_SHADE(L, 2, false); else if (mode == 1) FW_SHADE_C(L, 1); else FW_SHADE_C(L, 0); } while (0)
 #else
 #define FW_SHADE_L(L) do { if (mode == 1) FW_SHADE_C(L, 1); else FW_SHADE_C(L, 0); } while (0)
 #endif
-    if (lt == 1) FW_SHADE_L(1); else if (lt == 2) FW_SHADE_L(2); else FW_SHADE_L(0);
+    if (t.lt == 1) FW_SHADE_L(1); else if (t.lt == 2) FW_SHADE_L(2); else FW_SHADE_L(0);
 #undef FW_SHADE_L
 #undef FW_SHADE_C
 #undef FW_SHADE
 }
-void launch_shade_ls(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
-                     float4 *sample_rad, int segment, const DShadow &sh) {
-    // (launch_shade's table modes; the shading mode is 0 or 1: a light-sampling frame never takes the list)
-    const size_t tab = ((size_t)sc.n_objects * OBJ_Q + 2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    const int lt = (c.lds_tables && tab <= LDS_TABLE_LIMIT) ? 1 : ((c.lds_tables && tab_mt <= LDS_TABLE_LIMIT) ? 2 : 0);
-    const size_t lds = lt == 1 ? tab : (lt == 2 ? tab_mt : 0);
-#define FW_SHADE_LS(L, M) hipLaunchKernelGGL((k_shade_ls<L, M>), wave_grid(c), dim3(WB), lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, sh)
-#define FW_SHADE_LS_M(L) do { if (c.shade_mode == 1) FW_SHADE_LS(L, 1); else FW_SHADE_LS(L, 0); } while (0)
-    if (lt == 1) FW_SHADE_LS_M(1); else if (lt == 2) FW_SHADE_LS_M(2); else FW_SHADE_LS_M(0);
-#undef FW_SHADE_LS_M
-#undef FW_SHADE_LS
+// The four light-sampling shade kernels: ed = the environment is among the sampled lights (k_shade_env), em = the emitters are the entries
+// of *em (k_shade_pl), both (k_shade_pl_env), neither (k_shade_ls).  launch_shade's table modes; the shading mode is 0 or 1 (a light-sampling
+// frame never takes the list), and 0 alone with ed: an HDR map is an expensive case.
+void launch_shade_nee(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
+                      float4 *sample_rad, int segment, const DShadow &sh, const DEnvDist *ed, const DEmitters *em) {
+    const ShadeTables t = shade_tables(c, sc);
+    const bool m1 = c.shade_mode == 1;
+#define FW_NEE(K, ...) hipLaunchKernelGGL(K, wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, __VA_ARGS__)
+#define FW_NEE_L(L) do { \
+        if (ed && em) FW_NEE(k_shade_pl_env<L>, sh, *ed, *em); \
+        else if (ed) FW_NEE(k_shade_env<L>, sh, *ed); \
+        else if (em) { if (m1) FW_NEE((k_shade_pl<L, 1>), sh, *em); else FW_NEE((k_shade_pl<L, 0>), sh, *em); } \
+        else { if (m1) FW_NEE((k_shade_ls<L, 1>), sh); else FW_NEE((k_shade_ls<L, 0>), sh); } \
+    } while (0)
+    if (t.lt == 1) FW_NEE_L(1); else if (t.lt == 2) FW_NEE_L(2); else FW_NEE_L(0);
+#undef FW_NEE_L
+#undef FW_NEE
 }
-void launch_shadow_resolve(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment) {
-    hipLaunchKernelGGL(k_shadow_resolve, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
-}
-void launch_shade_env(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
-                      float4 *sample_rad, int segment, const DShadow &sh, const DEnvDist &ed) {
-    // (launch_shade_ls's table modes)
-    const size_t tab = ((size_t)sc.n_objects * OBJ_Q + 2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    const int lt = (c.lds_tables && tab <= LDS_TABLE_LIMIT) ? 1 : ((c.lds_tables && tab_mt <= LDS_TABLE_LIMIT) ? 2 : 0);
-    const size_t lds = lt == 1 ? tab : (lt == 2 ? tab_mt : 0);
-#define FW_SHADE_ENV(L) hipLaunchKernelGGL((k_shade_env<L>), wave_grid(c), dim3(WB), lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, sh, ed)
-    if (lt == 1) FW_SHADE_ENV(1); else if (lt == 2) FW_SHADE_ENV(2); else FW_SHADE_ENV(0);
-#undef FW_SHADE_ENV
-}
-void launch_shadow_resolve_env(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment) {
-    hipLaunchKernelGGL(k_shadow_resolve_env, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
-}
-void launch_shade_pl(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
-                     float4 *sample_rad, int segment, const DShadow &sh, const DEmitters &em) {
-    // (launch_shade_ls's table and shading modes)
-    const size_t tab = ((size_t)sc.n_objects * OBJ_Q + 2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    const int lt = (c.lds_tables && tab <= LDS_TABLE_LIMIT) ? 1 : ((c.lds_tables && tab_mt <= LDS_TABLE_LIMIT) ? 2 : 0);
-    const size_t lds = lt == 1 ? tab : (lt == 2 ? tab_mt : 0);
-#define FW_SHADE_PL(L, M) hipLaunchKernelGGL((k_shade_pl<L, M>), wave_grid(c), dim3(WB), lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, sh, em)
-#define FW_SHADE_PL_M(L) do { if (c.shade_mode == 1) FW_SHADE_PL(L, 1); else FW_SHADE_PL(L, 0); } while (0)
-    if (lt == 1) FW_SHADE_PL_M(1); else if (lt == 2) FW_SHADE_PL_M(2); else FW_SHADE_PL_M(0);
-#undef FW_SHADE_PL_M
-#undef FW_SHADE_PL
-}
-void launch_shade_pl_env(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
-                         float4 *sample_rad, int segment, const DShadow &sh, const DEnvDist &ed, const DEmitters &em) {
-    const size_t tab = ((size_t)sc.n_objects * OBJ_Q + 2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    const int lt = (c.lds_tables && tab <= LDS_TABLE_LIMIT) ? 1 : ((c.lds_tables && tab_mt <= LDS_TABLE_LIMIT) ? 2 : 0);
-    const size_t lds = lt == 1 ? tab : (lt == 2 ? tab_mt : 0);
-#define FW_SHADE_PL_ENV(L) hipLaunchKernelGGL((k_shade_pl_env<L>), wave_grid(c), dim3(WB), lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, sh, ed, em)
-    if (lt == 1) FW_SHADE_PL_ENV(1); else if (lt == 2) FW_SHADE_PL_ENV(2); else FW_SHADE_PL_ENV(0);
-#undef FW_SHADE_PL_ENV
-}
-void launch_shadow_resolve_pl(const LaunchCfg &c, const DScene &, const DShadow &sh, const float2 *hits, int segment) {
-    hipLaunchKernelGGL(k_shadow_resolve_pl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment);
+// One resolve kernel per visibility rule (see the three kernels): env / pl as launch_shade_nee's ed / em of the segment's shade
+void launch_shadow_resolve(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment, bool env, bool pl) {
+    if (pl) hipLaunchKernelGGL(k_shadow_resolve_pl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment);
+    else if (env) hipLaunchKernelGGL(k_shadow_resolve_env, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
+    else hipLaunchKernelGGL(k_shadow_resolve, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
 }
 void launch_emitter_weights(hipStream_t stream, const DScene &sc, const uint4 *ent, uint32_t n, float *w) {
     hipLaunchKernelGGL(k_emitter_weights, dim3((n + WB - 1) / WB), dim3(WB), 0, stream, sc, ent, n, w);
@@ -4930,9 +4658,9 @@ void launch_env_sample_test(hipStream_t stream, const DEnv &env, const DEnvDist 
 #if FW_AB
 void launch_bounce(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, float4 *sample_rad,
                    int segment, bool use_bvh) {
-    size_t tab = ((size_t)sc.n_objects * OBJ_Q + 2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4);
-    const bool lds_tab = c.lds_tables && tab <= LDS_TABLE_LIMIT;
-    if (!lds_tab) tab = 0;
+    const ShadeTables t = shade_tables(c, sc);      // k_bounce stages everything or nothing
+    const bool lds_tab = t.lt == 1;
+    const size_t tab = lds_tab ? t.lds : 0;
     int tl = use_bvh ? c.tlas_depth + 1 : 0;
     int levels = tl + c.blas_depth + 1;
     size_t lds = tab + (size_t)levels * WB * sizeof(uint32_t);

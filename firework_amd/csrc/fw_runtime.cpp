@@ -2615,18 +2615,13 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         if (ls) {
             Workspace::Lane &L = ws->lanes[c.lane];
             c.sh.pb_in = (const float *)L.pb[c.cur]; c.sh.pb_out = (float *)L.pb[c.cur ^ 1];
-            if (pl && es) timed(c, 2, [&] { fw::launch_shade_pl_env(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, c.ed, c.em); });
-            else if (pl) timed(c, 2, [&] { fw::launch_shade_pl(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, c.em); });
-            else if (es) timed(c, 2, [&] { fw::launch_shade_env(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, c.ed); });
-            else timed(c, 2, [&] { fw::launch_shade_ls(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh); });
+            timed(c, 2, [&] { fw::launch_shade_nee(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, es ? &c.ed : nullptr, pl ? &c.em : nullptr); });
             if (seg < fw::MAX_SEGMENTS - 1) {     // segments 0-9 scatter (render.rs:21): their shadow rays through the ordinary walks, then the resolve
                 fw::LaunchCfg scfg = c.cfg; scfg.q.wcount = c.sh.wcount;
                 fw::DFrame sfr = c.fr; sfr.seed32 ^= fw::SHADOW_SEED; sfr.ex.mode = 0;
                 const fw::DPaths sp{c.sh.ray_a, c.sh.ray_b, c.sh.state};
                 timed(c, 1, [&] { fw::launch_extend(scfg, sc->d, sfr, sp, (float2 *)L.s_hits, seg + 1, use_bvh, c.park); });
-                if (pl) timed(c, 2, [&] { fw::launch_shadow_resolve_pl(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
-                else if (es) timed(c, 2, [&] { fw::launch_shadow_resolve_env(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
-                else timed(c, 2, [&] { fw::launch_shadow_resolve(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg); });
+                timed(c, 2, [&] { fw::launch_shadow_resolve(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg, es, pl); });
             }
         } else
         timed(c, 2, [&] { fw::launch_shade(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg); });
