@@ -22,7 +22,9 @@ over every emitting primitive, meshes, disks and boxes included, picked by power
 --temporal [MAX_HISTORY] (only with --orbit: the views are rendered one after another as a sequence, each merged with the reprojected
 history of the view before it — a pixel carries over at most MAX_HISTORY samples, default 64 — and then denoised, DESIGN.md §9j;
 --denoise L and --aov-samples keep their meaning; view k renders with seed + k; not with --progressive / --checkpoint / --adaptive /
---camera)."""
+--camera), --camera fisheye [--fisheye-fov DEG] (an equidistant full-frame fisheye along the fixed view's direction, DEG degrees across
+the image diagonal, default 180; combines as the other models do).  The three models' rays are generated on the device
+(fw_render_model)."""
 import argparse
 import sys
 import time
@@ -60,10 +62,13 @@ def main(argv=None):
                     help="importance-sample an HDR environment map at diffuse vertices (with --light-sampling: beside the lights)")
     ap.add_argument("--all-emitters", action="store_true",
                     help="light sampling over every emitting primitive (meshes, disks, boxes too), picked by power; implies --light-sampling")
-    ap.add_argument("--camera", choices=("pinhole", "panorama", "orthographic"), default="pinhole",
-                    help="camera model: the fixed pinhole view (default), an equirectangular panorama from its position, or an orthographic view")
+    ap.add_argument("--camera", choices=("pinhole", "panorama", "orthographic", "fisheye"), default="pinhole",
+                    help="camera model: the fixed pinhole view (default), an equirectangular panorama from its position, an orthographic "
+                         "view, or an equidistant fisheye")
     ap.add_argument("--ortho-height", type=float, default=None, metavar="H",
                     help="with --camera orthographic: the height of the view plane (default: what the pinhole view sees at its look-at point)")
+    ap.add_argument("--fisheye-fov", type=float, default=None, metavar="DEG",
+                    help="with --camera fisheye: the angle across the image diagonal in degrees, in (0, 360] (default 180)")
     opt = ap.parse_args(argv)
     if opt.adaptive is not None and (opt.progressive > 0 or opt.checkpoint):
         ap.error("--adaptive cannot be combined with --progressive or --checkpoint")
@@ -90,6 +95,11 @@ def main(argv=None):
             ap.error("--ortho-height H needs H > 0")
     elif opt.ortho_height is not None:
         ap.error("--ortho-height needs --camera orthographic")
+    if opt.fisheye_fov is not None:
+        if opt.camera != "fisheye":
+            ap.error("--fisheye-fov needs --camera fisheye")
+        if not 0.0 < opt.fisheye_fov <= 360.0:
+            ap.error("--fisheye-fov DEG needs 0 < DEG <= 360")
     if opt.orbit > 0:
         if opt.progressive > 0 or opt.checkpoint or opt.adaptive is not None:
             ap.error("--orbit cannot be combined with --progressive, --checkpoint or --adaptive")
@@ -178,21 +188,21 @@ def denoised(renderer, scene, opt):
 
 
 def camera_model_render(renderer, camera, scene, opt):
-    """--camera panorama / orthographic: the model's rays, made on the device sample by sample, rendered through fw_render_rays in
-    chunks of samples whose rays stay below 1 GiB; returns rgb8."""
-    import functools
+    """--camera panorama / orthographic / fisheye: the model's rays are generated on the device, chunk by chunk of samples, and rendered
+    by fw_render_model; returns rgb8."""
     import math
-    from .api import orthographic_rays, panorama_rays
+    from .api import CameraModel
     if opt.camera == "panorama":
-        model = functools.partial(panorama_rays, camera._cam_pos, opt.width, opt.height, seed=opt.seed, device=opt.device)
+        model = CameraModel.panorama(camera._cam_pos, opt.width, opt.height)
+    elif opt.camera == "fisheye":
+        model = CameraModel.fisheye(camera, 180.0 if opt.fisheye_fov is None else opt.fisheye_fov, opt.width, opt.height)
     else:
         h = opt.ortho_height
         if h is None:       # the height the pinhole view sees at its look-at point
             dist = float(math.dist(camera._cam_pos.tolist(), camera._look_at.tolist()))
             h = 2.0 * math.tan(math.radians(camera._vfov) / 2.0) * dist
-        model = functools.partial(orthographic_rays, camera, h, opt.width, opt.height, seed=opt.seed, device=opt.device)
-    chunk = max(1, min(64, (1 << 30) // (opt.width * opt.height * 24)))
-    return renderer.render_camera_model(scene, model, opt.samples, chunk=chunk, device=opt.device).image(opt.width, opt.height)
+        model = CameraModel.orthographic(camera, h, opt.width, opt.height)
+    return renderer.render_model(scene, model.seed(opt.seed), opt.samples, device=opt.device).image(opt.width, opt.height)
 
 
 def view_paths(pattern, n):

@@ -152,5 +152,14 @@ class fw_temporal_params(C.Structure):
                 ("max_history", f32), ("device", i32), ("on_device", i32), ("stream", C.c_void_p)]
 
 
+# camera models on the device (include/firework_hip.h: fw_model_rays, fw_render_model, fw_render_model_aovs)
+FW_MODEL_PANORAMA, FW_MODEL_ORTHOGRAPHIC, FW_MODEL_FISHEYE = range(3)
+
+
+class fw_camera_model(C.Structure):
+    _fields_ = [("kind", i32), ("width", u32), ("height", u32), ("camera", fw_camera_settings), ("view_height", C.c_double),
+                ("fov", C.c_double), ("jitter", i32), ("seed", u64), ("chunk_samples", u32)]
+
+
 def vec3(v):
     return fw_vec3(float(v[0]), float(v[1]), float(v[2]))

@@ -102,6 +102,14 @@ def load(preload=False, device=None):
                                    C.c_void_p, C.POINTER(A.fw_stats)]
     lib.fw_render_aovs.restype = C.c_int
     lib.fw_render_aovs.argtypes = [C.c_void_p, C.POINTER(A.fw_render_params), C.c_void_p, C.POINTER(A.fw_stats)]
+    lib.fw_model_rays.restype = C.c_int
+    lib.fw_model_rays.argtypes = [C.POINTER(A.fw_camera_model), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+    lib.fw_render_model.restype = C.c_int
+    lib.fw_render_model.argtypes = [C.c_void_p, C.POINTER(A.fw_camera_model), C.POINTER(A.fw_render_rays_params), C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.POINTER(A.fw_stats)]
+    lib.fw_render_model_aovs.restype = C.c_int
+    lib.fw_render_model_aovs.argtypes = [C.c_void_p, C.POINTER(A.fw_camera_model), C.POINTER(A.fw_render_params), C.c_void_p,
+                                         C.POINTER(A.fw_stats)]
     lib.fw_denoise.restype = C.c_int
     lib.fw_denoise.argtypes = [C.POINTER(A.fw_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fw_temporal.restype = C.c_int
@@ -324,6 +332,35 @@ def camera_rays(renderer, sample=0, pixel_ids=None, device=0):
     return out
 
 
+def _model_abi(model, chunk=None):
+    """a fw_camera_model from an api.CameraModel (or a fw_camera_model, copied), with chunk_samples = chunk when given"""
+    m = model.to_abi() if hasattr(model, "to_abi") else A.fw_camera_model.from_buffer_copy(model)
+    if chunk is not None:
+        m.chunk_samples = int(chunk)
+    return m
+
+
+def model_rays(model, first_sample=0, n_samples=1, device=0, out=None, stream=None):
+    """fw_model_rays: the rays of the absolute samples [first_sample, first_sample + n_samples) of a camera model (an api.CameraModel or
+    a fw_camera_model), generated on the device: (n_samples, W * H, 6) float32 origin + direction, row 0 = the image top.  Returns a
+    numpy array; out: a contiguous float32 device tensor of that shape on cuda:`device` to fill instead, on `stream` (default: the
+    current torch stream); returned."""
+    lib = load()
+    m = _model_abi(model)
+    shape = (int(n_samples), int(m.width) * int(m.height), 6)
+    if out is not None:
+        import torch
+        _check_device_tensor(out, shape, torch.float32, device, "out")
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+        _check(lib, lib.fw_model_rays(C.byref(m), int(device), int(first_sample), int(n_samples), out.data_ptr(), 1,
+                                      C.c_void_p(stream) if stream else None))
+        return out
+    rays = np.empty(shape, np.float32)
+    _check(lib, lib.fw_model_rays(C.byref(m), int(device), int(first_sample), int(n_samples), rays.ctypes.data, 0, None))
+    return rays
+
+
 class DeviceScene:
     """An uploaded scene (`fw_scene*`): SoA scene arrays + TLAS/BLAS resident in HBM."""
 
@@ -509,6 +546,75 @@ class DeviceScene:
         _check(lib, lib.fw_render_rays(self.handle, C.byref(p), r.ctypes.data, accum.ctypes.data, rgb8.ctypes.data, gam.ctypes.data,
                                        lin.ctypes.data, C.byref(st)))
         return RaysResult(rgb8, gam, lin, accum, st.as_dict())
+
+    def render_model(self, model, samples, first_sample=0, accum=None, key_base=0, seed=0, use_bvh=True, gamma=2.2, stream=None,
+                     paths_per_batch=0, flags=0, chunk=None, on_device=False):
+        """fw_render_model: samples [first_sample, first_sample + samples) of a camera model (an api.CameraModel or a fw_camera_model)
+        whose rays are generated on the device, chunk samples at a time (None: the model's own setting; 0: automatic).  Bit for bit
+        render_rays() over model_rays().  accum: (W * H, 4) float32 sums of the samples before first_sample, updated in place (None:
+        zeros, only with first_sample 0).  Returns a RaysResult of host arrays, or — accum a device tensor on this scene's device, or
+        on_device=True — of device tensors, rendered on `stream` (default: the current torch stream)."""
+        from .api import RaysResult
+        lib = self._lib
+        m = _model_abi(model, chunk)
+        n = int(m.width) * int(m.height)
+        p = A.fw_render_rays_params()
+        p.n_rays, p.first_sample, p.samples, p.per_sample_rays = n, int(first_sample), int(samples), 1
+        p.key_base, p.seed, p.use_bvh, p.gamma = int(key_base), int(seed), int(bool(use_bvh)), float(gamma)
+        p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
+        st = A.fw_stats()
+        if on_device or (accum is not None and type(accum).__module__.startswith("torch")):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if accum is None:
+                accum = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+            _check_device_tensor(accum, (n, 4), torch.float32, self.device, "accum")
+            rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+            gam = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            lin = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            p.on_device = 1
+            p.stream = C.c_void_p(stream) if stream else None
+            _check(lib, lib.fw_render_model(self.handle, C.byref(m), C.byref(p), accum.data_ptr(), rgb8.data_ptr(), gam.data_ptr(),
+                                            lin.data_ptr(), C.byref(st)))
+            return RaysResult(rgb8, gam, lin, accum, st.as_dict())
+        if accum is None:
+            accum = np.zeros((n, 4), np.float32)
+        if not (isinstance(accum, np.ndarray) and accum.dtype == np.float32 and accum.shape == (n, 4) and accum.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"accum must be a contiguous float32 array of shape ({n}, 4)")
+        rgb8 = np.empty((n, 3), np.uint8)
+        gam = np.empty((n, 3), np.float32)
+        lin = np.empty((n, 3), np.float32)
+        _check(lib, lib.fw_render_model(self.handle, C.byref(m), C.byref(p), accum.ctypes.data, rgb8.ctypes.data, gam.ctypes.data,
+                                        lin.ctypes.data, C.byref(st)))
+        return RaysResult(rgb8, gam, lin, accum, st.as_dict())
+
+    def model_aovs(self, model, samples, seed=0, use_bvh=True, out=None, stream=None):
+        """fw_render_model_aovs: aovs() for a camera model (an api.CameraModel or a fw_camera_model) — the (W * H, 12) float32 first-hit
+        guide records of the model's rays averaged over `samples` samples, keyed by `seed` as a render through the model keys its
+        paths.  out: a contiguous (W * H, 12) float32 device tensor on this scene's device to fill instead, on `stream` (default: the
+        current torch stream); returned.  stats: see aovs_stats after the call."""
+        lib = self._lib
+        m = _model_abi(model)
+        n = int(m.width) * int(m.height)
+        p = A.fw_render_params()
+        p.samples, p.use_bvh, p.seed = int(samples), int(bool(use_bvh)), int(seed)
+        st = A.fw_stats()
+        if out is not None:
+            import torch
+            _check_device_tensor(out, (n, 12), torch.float32, self.device, "out")
+            p.outputs_on_device = 1
+            if stream is None:
+                stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+            p.stream = C.c_void_p(stream) if stream else None
+            _check(lib, lib.fw_render_model_aovs(self.handle, C.byref(m), C.byref(p), out.data_ptr(), C.byref(st)))
+            self.aovs_stats = st.as_dict()
+            return out
+        aov = np.empty((n, 12), np.float32)
+        _check(lib, lib.fw_render_model_aovs(self.handle, C.byref(m), C.byref(p), aov.ctypes.data, C.byref(st)))
+        self.aovs_stats = st.as_dict()
+        return aov
 
     def trace(self, rays, use_bvh, seed=0, key_base=0, rays_per_batch=0, time_kernels=False, stats=None):
         """fw_trace_rays: one root.hit(ray, 0.001, 2e9) per ray.  rays: (n, 6) origin + direction.

@@ -959,6 +959,86 @@ def orthographic_rays(camera: CameraSettings, view_height: float, width: int, he
     return _rays_out(o, d, device)
 
 
+def fisheye_rays(camera: CameraSettings, fov: float, width: int, height: int, sample: int, seed: int = 0, jitter: bool = True, device=None):
+    """Equidistant, full-frame fisheye rays: (W*H, 6) float32, row-major, row 0 = image top, for absolute sample `sample` (jitter as
+    panorama_rays).  The basis is camera.rs's (see orthographic_rays).  `fov` is the full angle across the image diagonal in degrees, in
+    (0, 360].  For pixel (x, row j): a = 2 (x + xi_x) - W, b = H - 2 (j + xi_y), rho = sqrt(a^2 + b^2), r = rho / sqrt(W^2 + H^2) (0 at
+    the centre, 1 in the corners), theta = r * fov / 2 the angle to the view direction (equidistant: proportional to the distance from
+    the centre), d = sin theta * (a u + b v) / rho - cos theta * w, and d = -w where rho = 0; the origin is cam_pos.  Computed in
+    float64, rounded to float32.  The camera's field of view, aperture and focus distance are not used."""
+    w_px, h_px = int(width), int(height)
+    fov = float(fov)
+    if not 0.0 < fov <= 360.0:
+        raise ValueError("fov must be in (0, 360] degrees")
+    pos = np.asarray(camera._cam_pos, np.float64)
+    at = np.asarray(camera._look_at, np.float64)
+    w = pos - at
+    w = w / np.linalg.norm(w)
+    u = np.cross(np.array([0.0, 1.0, 0.0]), w)
+    u = u / np.linalg.norm(u)
+    v = np.cross(w, u)
+    px, py = _pixel_grid(w_px, h_px, sample, seed, jitter)
+    a, b = 2.0 * px - w_px, h_px - 2.0 * py
+    rho = np.sqrt(a * a + b * b)
+    theta = (rho / np.sqrt(float(w_px) * float(w_px) + float(h_px) * float(h_px))) * (fov * (np.pi / 180.0) / 2.0)
+    safe = np.where(rho > 0.0, rho, 1.0)
+    e = (a[:, None] * u + b[:, None] * v) / safe[:, None]
+    d = np.sin(theta)[:, None] * e - np.cos(theta)[:, None] * w
+    d = np.where((rho > 0.0)[:, None], d, -w)
+    o = np.broadcast_to(pos.reshape(1, 3), d.shape)
+    return _rays_out(o, d, device)
+
+
+class CameraModel:
+    """A non-pinhole camera whose rays are generated on the device (fw_camera_model): CameraModel.panorama(...),
+    .orthographic(...) or .fisheye(...), then .seed(s) / .jitter(on) as builders.  .rays(sample) is the numpy float64 statement of what
+    the device generates (panorama_rays, orthographic_rays, fisheye_rays); _lib.model_rays(model, ...) the device's own."""
+
+    def __init__(self, kind: int, width: int, height: int, camera: CameraSettings, view_height: float = 0.0, fov: float = 0.0):
+        self.kind, self.width, self.height, self.camera = int(kind), int(width), int(height), camera
+        self.view_height, self.fov = float(view_height), float(fov)
+        self._seed, self._jitter, self.chunk_samples = 0, True, 0
+
+    @staticmethod
+    def panorama(position, width: int, height: int) -> "CameraModel":
+        """an equirectangular 360-degree image from `position` (panorama_rays)"""
+        pos = _v3(position)
+        return CameraModel(A.FW_MODEL_PANORAMA, width, height, CameraSettings.default().cam_pos(pos).look_at(pos + _v3((0.0, 0.0, -1.0))))
+
+    @staticmethod
+    def orthographic(camera: CameraSettings, view_height: float, width: int, height: int) -> "CameraModel":
+        """parallel rays along the camera's view direction over a view plane `view_height` high (orthographic_rays)"""
+        return CameraModel(A.FW_MODEL_ORTHOGRAPHIC, width, height, camera, view_height=view_height)
+
+    @staticmethod
+    def fisheye(camera: CameraSettings, fov: float, width: int, height: int) -> "CameraModel":
+        """an equidistant full-frame fisheye along the camera's view direction, `fov` degrees across the diagonal (fisheye_rays)"""
+        return CameraModel(A.FW_MODEL_FISHEYE, width, height, camera, fov=fov)
+
+    def seed(self, s):
+        self._seed = int(s)
+        return self
+
+    def jitter(self, on=True):
+        self._jitter = bool(on)
+        return self
+
+    def rays(self, sample: int, device=None):
+        """the numpy statement of one absolute sample's rays: (W*H, 6) float32 (device: see panorama_rays)"""
+        if self.kind == A.FW_MODEL_PANORAMA:
+            return panorama_rays(self.camera._cam_pos, self.width, self.height, sample, self._seed, self._jitter, device)
+        if self.kind == A.FW_MODEL_ORTHOGRAPHIC:
+            return orthographic_rays(self.camera, self.view_height, self.width, self.height, sample, self._seed, self._jitter, device)
+        return fisheye_rays(self.camera, self.fov, self.width, self.height, sample, self._seed, self._jitter, device)
+
+    def to_abi(self) -> A.fw_camera_model:
+        m = A.fw_camera_model()
+        m.kind, m.width, m.height, m.camera = self.kind, self.width, self.height, self.camera.to_abi()
+        m.view_height, m.fov, m.jitter = self.view_height, self.fov, int(self._jitter)
+        m.seed, m.chunk_samples = self._seed & 0xFFFFFFFFFFFFFFFF, int(self.chunk_samples)
+        return m
+
+
 # render_sequence's default cap on the samples a pixel carries over from the frames before it (DESIGN.md §9j)
 DEFAULT_MAX_HISTORY = 64.0
 
@@ -1276,6 +1356,56 @@ class Renderer:
         finally:
             if ds is not scene:
                 ds.close()
+
+    def render_model(self, scene, model: "CameraModel", samples: int, first_sample: int = 0, accum=None, chunk: int = 0, device: int = 0,
+                     stream=None, on_device: bool = False) -> RaysResult:
+        """A CameraModel rendered on the device (not in the reference; fw_render_model): the model's rays of the samples
+        [first_sample, first_sample + samples) are generated by k_model_rays, `chunk` samples at a time (0: as many as fit 256 MiB),
+        and rendered with this renderer's seed, use_bvh, gamma, batch size and flags; its camera, size and sample count are not used.
+        Bit for bit render_rays() over _lib.model_rays(model), for every chunk.  accum and on_device as _lib.DeviceScene.render_model.
+        `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene.  The image is result.image(model.width, model.height)."""
+        from . import _lib
+        s = self.settings
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            return ds.render_model(model, samples, first_sample, accum, seed=s["seed"], use_bvh=s["use_bvh"], gamma=s["gamma"], stream=stream,
+                                   paths_per_batch=s["paths_per_batch"], flags=s["flags"], chunk=chunk, on_device=on_device)
+        finally:
+            if ds is not scene:
+                ds.close()
+
+    def model_aovs(self, scene, model: "CameraModel", samples: int = 8, device: int = 0) -> dict:
+        """aovs() for a CameraModel (fw_render_model_aovs): the first-hit guide buffers of the model's rays, keyed as render_model keys
+        its paths.  Returns (H, W, .) float32 arrays of the model's size, as aovs()."""
+        from . import _lib
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            rec = ds.model_aovs(model, samples, seed=self.settings["seed"], use_bvh=self.settings["use_bvh"])
+        finally:
+            if ds is not scene:
+                ds.close()
+        h, w = int(model.height), int(model.width)
+        return {k: rec[:, c].reshape((h, w, 3) if isinstance(c, slice) else (h, w)) for k, c in _lib.AOV_COLUMNS.items()}
+
+    def render_model_denoised(self, scene, model: "CameraModel", samples: int, iterations: int = 5, aov_samples: int = 8,
+                              device: int = 0) -> RenderResult:
+        """render_model() filtered by fw_denoise with the model's own guide buffers (fw_render_model_aovs at `aov_samples` samples),
+        without moments: the filter's luminance term is off.  Both calls share one uploaded scene.  Returns the filtered frame as a
+        RenderResult whose .raw is the frame before filtering; iterations = 0 returns the raw frame bit for bit."""
+        from . import _lib
+        s = self.settings
+        w, h = int(model.width), int(model.height)
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            res = self.render_model(ds, model, samples)
+            aov = ds.model_aovs(model, aov_samples, seed=s["seed"], use_bvh=s["use_bvh"])
+            dev = ds.device
+        finally:
+            if ds is not scene:
+                ds.close()
+        raw = RenderResult(res.rgb8, res.gamma, res.linear, res.stats, w, h)
+        rgb8, gam, lin = _lib.denoise(raw.linear, aov, None, w, h, iterations, s["gamma"], dev)
+        return RenderResult(rgb8, gam, lin, dict(raw.stats), w, h, raw=raw)
 
     def aovs(self, scene, samples: int = 8, device: int = 0) -> dict:
         """First-hit guide buffers (not in the reference; fw_render_aovs): for `samples` samples of every pixel the camera ray a render

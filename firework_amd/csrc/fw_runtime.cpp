@@ -11,6 +11,7 @@
 #include "fw_device.h"
 #include "fw_build.h"
 #include "fw_temporal.h"
+#include "fw_camera_models.h"
 
 #include <algorithm>
 #include <atomic>
@@ -3030,6 +3031,15 @@ int views_impl(fw_scene *sc, const fw_render_params *p, const fw_camera_settings
 // fw_render_rays: render_impl over a frame of n_rays entries whose paths start from the caller's rays (RayInput; include/firework_hip.h has
 // the contract).  The frame is n_rays x 1 pixels without a camera; batches, lanes, queues, walks, k_shade, the accumulation in sample
 // order and the resolve are the render's own.
+// The frame of a fw_render_rays call as render_impl takes it: n_rays x 1 pixels without a camera.  rays_impl and render_model_impl (whose
+// every chunk is such a call) both build it here, so the two cannot drift apart.
+fw_render_params rays_frame(const fw_render_rays_params *rp, uint32_t samples) {
+    fw_render_params P{};
+    P.width = rp->n_rays; P.height = 1; P.samples = samples; P.gamma = rp->gamma; P.use_bvh = rp->use_bvh; P.seed = rp->seed;
+    P.rng_mode = FW_RNG_CTR; P.paths_per_batch = rp->paths_per_batch; P.flags = rp->flags; P.outputs_on_device = rp->on_device; P.stream = rp->stream;
+    return P;
+}
+
 int rays_impl(fw_scene *sc, const fw_render_rays_params *rp, const float *rays, float *accum, uint8_t *rgb8, float *gamma_rgb,
               float *linear_rgb, fw_stats *stats) {
     // (arguments first, in a fixed order: nothing below dereferences the scene or calls HIP before they are all valid)
@@ -3042,9 +3052,7 @@ int rays_impl(fw_scene *sc, const fw_render_rays_params *rp, const float *rays, 
     if (rp->on_device && (((uintptr_t)accum & 15u) || ((uintptr_t)rays & 3u))) return fail(FW_ERR_BAD_ARG, "device accum must be 16-byte aligned, device rays 4-byte aligned");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
-    fw_render_params P{};
-    P.width = rp->n_rays; P.height = 1; P.samples = rp->samples; P.gamma = rp->gamma; P.use_bvh = rp->use_bvh; P.seed = rp->seed;
-    P.rng_mode = FW_RNG_CTR; P.paths_per_batch = rp->paths_per_batch; P.flags = rp->flags; P.outputs_on_device = rp->on_device; P.stream = rp->stream;
+    const fw_render_params P = rays_frame(rp, rp->samples);
     const RayInput ri{rays, rp->n_rays, rp->per_sample_rays != 0, rp->keys, rp->key_base, rp->on_device != 0};
     return render_impl(sc, &P, rgb8, gamma_rgb, linear_rgb, stats, rp->first_sample, accum, nullptr, nullptr, &ri);
 }
@@ -3264,7 +3272,8 @@ int camera_rays_impl(const fw_render_params *p, int device, uint32_t sample, flo
 // traces the caller's rays — k_trace_load with the real pixel keys (key0 = the batch's first pixel, DFrame.sample0 = s), the render's
 // launch_extend + launch_extend_exact — and k_aov_accumulate adds the batch's values to its pixels' sums; k_aov_finish divides.  The
 // queue geometry, walk configuration and hit-record form are trace_impl's, so every kernel-selecting option selects the same walks.
-int aovs_impl(fw_scene *sc, const fw_render_params *p, float *aov, fw_stats *stats) {
+// dm: fw_render_model_aovs — the one-sample ray buffer is filled by k_model_rays (the model's rays of sample s) instead of k_camera_rays.
+int aovs_impl(fw_scene *sc, const fw_render_params *p, float *aov, fw_stats *stats, const fw::DModel *dm = nullptr) {
     // (arguments first: nothing below dereferences the scene before they are all valid)
     if (!sc || !p || !aov) return fail(FW_ERR_BAD_ARG, "null argument");
     if (p->pixel_ids) return fail(FW_ERR_BAD_ARG, "fw_render_aovs renders whole frames: pixel_ids must be NULL");
@@ -3366,7 +3375,8 @@ int aovs_impl(fw_scene *sc, const fw_render_params *p, float *aov, fw_stats *sta
     HIPCHK(hipMemsetAsync(sum, 0, (size_t)n * 48, stream));
     for (uint32_t s = 0; s < S; s++) {
         cf.sample0 = s;
-        fw::launch_camera_rays(stream, sc->n_cus, cam, cf, n, rays);
+        if (dm) fw::launch_model_rays(stream, sc->n_cus, *dm, s, 1, rays);
+        else fw::launch_camera_rays(stream, sc->n_cus, cam, cf, n, rays);
         fr.sample0 = s;
         for (uint32_t b = 0; b < n_batches; b++) {
             const uint32_t first = b * per, nb = std::min(per, n - first);
@@ -3540,6 +3550,172 @@ int temporal_impl(const fw_temporal_params *p, const float *color, const float *
     HIPCHK(hipStreamSynchronize(stream));
     HIPCHK(hipGetLastError());
     return FW_OK;
+}
+
+// ---- camera models (include/firework_hip.h) ------------------------------------------------------------------
+// The model's own argument checks (FW_ERR_BAD_ARG only) and its device form: camera.rs's basis in float64.  too_large: W x H >= 2^31, which
+// the callers report as FW_ERR_UNSUPPORTED after their own argument checks.
+int model_prepare(const fw_camera_model *m, fw::DModel &d, bool &too_large) {
+    if (m->kind != FW_MODEL_PANORAMA && m->kind != FW_MODEL_ORTHOGRAPHIC && m->kind != FW_MODEL_FISHEYE) return fail(FW_ERR_BAD_ARG, "unknown camera model kind");
+    if (m->width == 0 || m->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
+    if (!camera_finite(m->camera)) return fail(FW_ERR_BAD_ARG, "camera fields must be finite");
+    d = fw::DModel{};
+    d.kind = m->kind; d.width = m->width; d.height = m->height;
+    d.seed32 = (uint32_t)m->seed ^ ((uint32_t)(m->seed >> 32) * 0x9E3779B9u);
+    d.jitter = m->jitter ? 1u : 0u;
+    const double pos[3] = {m->camera.cam_pos.x, m->camera.cam_pos.y, m->camera.cam_pos.z};
+    const double at[3] = {m->camera.look_at.x, m->camera.look_at.y, m->camera.look_at.z};
+    for (int k = 0; k < 3; k++) d.pos[k] = pos[k];
+    if (m->kind != FW_MODEL_PANORAMA) {
+        double w[3] = {pos[0] - at[0], pos[1] - at[1], pos[2] - at[2]};
+        const double wl = std::sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+        if (!(wl > 0.0)) return fail(FW_ERR_BAD_ARG, "cam_pos and look_at must differ");
+        for (double &c : w) c /= wl;
+        double u[3] = {w[2], 0.0, -w[0]};                                   // Y x w
+        const double ul = std::sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+        if (!(ul > 0.0)) return fail(FW_ERR_BAD_ARG, "the view direction must not be parallel to Y");
+        for (double &c : u) c /= ul;
+        const double v[3] = {w[1] * u[2] - w[2] * u[1], w[2] * u[0] - w[0] * u[2], w[0] * u[1] - w[1] * u[0]};     // w x u
+        for (int k = 0; k < 3; k++) { d.u[k] = u[k]; d.v[k] = v[k]; d.w[k] = w[k]; d.dir[k] = at[k] - pos[k]; }
+    }
+    if (m->kind == FW_MODEL_ORTHOGRAPHIC) {
+        if (!std::isfinite(m->view_height) || !(m->view_height > 0.0)) return fail(FW_ERR_BAD_ARG, "view_height must be finite and > 0");
+        d.view_h = m->view_height;
+        d.view_w = m->view_height * (double)m->width / (double)m->height;
+    }
+    if (m->kind == FW_MODEL_FISHEYE) {
+        if (!(m->fov > 0.0 && m->fov <= 360.0)) return fail(FW_ERR_BAD_ARG, "fov must be in (0, 360] degrees");
+        d.half_fov = (m->fov * (3.141592653589793 / 180.0)) / 2.0;
+        d.diag = std::sqrt((double)m->width * (double)m->width + (double)m->height * (double)m->height);
+    }
+    too_large = (uint64_t)m->width * m->height >= (1ull << 31);
+    return FW_OK;
+}
+
+// device scratch of one call, released on every way out of the function that owns it
+struct CallScratch : DevBuf { int dev; explicit CallScratch(int d) : dev(d) {} ~CallScratch() { if (p) { (void)hipSetDevice(dev); release(); } } };
+struct CallEvents { hipEvent_t e[2] = {nullptr, nullptr}; ~CallEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } };
+
+constexpr size_t MODEL_SCRATCH_BYTES = (size_t)256 << 20;     // the automatic chunk of fw_render_model and fw_model_rays' host output
+
+// fw_model_rays: device output — one launch into the caller's memory; host output — slabs of samples through scratch of the call's own
+int model_rays_impl(const fw_camera_model *m, int device, uint32_t first, uint32_t n_samples, float *rays, int on_device, void *stream_) {
+    if (!m || !rays) return fail(FW_ERR_BAD_ARG, "null argument");
+    fw::DModel dm; bool too_large = false;
+    if (int rc = model_prepare(m, dm, too_large)) return rc;
+    if (n_samples == 0) return fail(FW_ERR_BAD_ARG, "n_samples must be > 0");
+    if ((uint64_t)first + n_samples > (1ull << 32)) return fail(FW_ERR_BAD_ARG, "first_sample + n_samples overflows");
+    if (on_device && ((uintptr_t)rays & 3u)) return fail(FW_ERR_BAD_ARG, "rays must be 4-byte aligned");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "W x H must be below 2^31 (the jitter's counter is 32-bit)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n_pix = (size_t)m->width * m->height;
+    if (on_device) {
+        fw::launch_model_rays(stream, device_cus(device), dm, first, n_samples, rays);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+    const uint32_t per = (uint32_t)std::min<uint64_t>(n_samples, std::max<uint64_t>(1, MODEL_SCRATCH_BYTES / (n_pix * 24)));
+    CallScratch scratch(device);
+    if (int rc = scratch.alloc((size_t)per * n_pix * 24)) return rc;
+    for (uint32_t done = 0; done < n_samples; done += per) {
+        const uint32_t k = std::min(per, n_samples - done);
+        fw::launch_model_rays(stream, device_cus(device), dm, first + done, k, (float *)scratch.p);
+        HIPCHK(hipMemcpyAsync(rays + (size_t)done * n_pix * 6, scratch.p, (size_t)k * n_pix * 24, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_render_model: per chunk of samples, k_model_rays into the call's scratch, then render_impl over those device rays on top of the
+// running sums — the fw_render_rays call of the chunk (rays_impl's frame), so the sums and the resolve are its own.
+int render_model_impl(fw_scene *sc, const fw_camera_model *m, const fw_render_rays_params *rp, float *accum, uint8_t *rgb8, float *gamma_rgb,
+                      float *linear_rgb, fw_stats *stats) {
+    if (!sc || !m || !rp) return fail(FW_ERR_BAD_ARG, "null argument");
+    fw::DModel dm; bool too_large = false;
+    if (int rc = model_prepare(m, dm, too_large)) return rc;
+    if (rp->samples == 0 || rp->samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^24");
+    if ((uint64_t)rp->first_sample + rp->samples > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_sample + samples overflows");
+    if (!std::isfinite(rp->gamma) || !(rp->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
+    if ((uint64_t)m->width * m->height != rp->n_rays) return fail(FW_ERR_BAD_ARG, "n_rays must be width x height");
+    if (!accum && rp->first_sample > 0) return fail(FW_ERR_BAD_ARG, "first_sample > 0 needs the accumulation buffer of the samples before it");
+    if (rp->on_device && ((uintptr_t)accum & 15u)) return fail(FW_ERR_BAD_ARG, "device accum must be 16-byte aligned");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "W x H must be below 2^31 (the jitter's counter is 32-bit)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)rp->stream;
+    const size_t n_pix = rp->n_rays;
+    const uint32_t S = rp->samples;
+    const uint32_t chunk = std::min<uint32_t>(S, m->chunk_samples ? m->chunk_samples : (uint32_t)std::max<uint64_t>(1, MODEL_SCRATCH_BYTES / (n_pix * 24)));
+    // the running sums between chunks when the caller keeps none: device memory behind the rays, or a host array
+    const bool own_accum = !accum && chunk < S;
+    const size_t ray_bytes = ((size_t)chunk * n_pix * 24 + 255) & ~(size_t)255;
+    CallScratch scratch(dev);
+    if (int rc = scratch.alloc(ray_bytes + (own_accum && rp->on_device ? n_pix * 16 : 0))) return rc;
+    std::vector<float> host_accum;
+    float *acc = accum;
+    if (own_accum) {
+        if (rp->on_device) { acc = (float *)((uint8_t *)scratch.p + ray_bytes); HIPCHK(hipMemsetAsync(acc, 0, n_pix * 16, stream)); }
+        else { host_accum.assign(n_pix * 4, 0.f); acc = host_accum.data(); }
+    }
+    CallEvents ev;                                    // around the generator's launch, only when the caller reads stats
+    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
+    const int n_cus = device_cus(dev);
+    const bool timing = (rp->flags & FW_FLAG_TIME_KERNELS) != 0;
+
+    fw_stats total{};
+    for (uint32_t done = 0; done < S; done += chunk) {
+        const uint32_t k = std::min(chunk, S - done), first = rp->first_sample + done;
+        const bool last = done + k == S;
+        if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
+        fw::launch_model_rays(stream, n_cus, dm, first, k, (float *)scratch.p);
+        if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
+        const fw_render_params P = rays_frame(rp, k);
+        const RayInput ri{(const float *)scratch.p, rp->n_rays, true, nullptr, rp->key_base, true};
+        fw_stats gs{};
+        if (int rc = render_impl(sc, &P, last ? rgb8 : nullptr, last ? gamma_rgb : nullptr, last ? linear_rgb : nullptr, stats ? &gs : nullptr,
+                                 first, acc, nullptr, nullptr, &ri)) return rc;      // (returns with the stream drained)
+        if (!stats) continue;
+        float gen_ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
+        total.samples += gs.samples; total.rays += gs.rays;
+        for (int s = 0; s < FW_MAX_SEGMENTS; s++) total.rays_per_depth[s] += gs.rays_per_depth[s];
+        total.algorithmic_bytes += gs.algorithmic_bytes;
+        total.ms_render += gs.ms_render + gen_ms; total.ms_raygen += gs.ms_raygen + (timing ? gen_ms : 0.f); total.ms_extend += gs.ms_extend;
+        total.ms_shade += gs.ms_shade; total.ms_accumulate += gs.ms_accumulate; total.ms_d2h += gs.ms_d2h;
+        total.n_extend_launches += gs.n_extend_launches; total.n_shade_launches += gs.n_shade_launches; total.n_batches += gs.n_batches;
+        total.tlas_nodes = gs.tlas_nodes; total.blas_nodes = gs.blas_nodes; total.reserved = gs.reserved;
+        total.bytes_raygen += gs.bytes_raygen + (uint64_t)k * n_pix * 24;                  // (the generator's stores)
+        total.bytes_extend += gs.bytes_extend; total.bytes_shade += gs.bytes_shade; total.bytes_accumulate += gs.bytes_accumulate;
+        total.deposits += gs.deposits; total.parked_rays += gs.parked_rays;
+    }
+    if (stats) {
+        *stats = total;
+        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FW_OK;
+}
+
+// fw_render_model_aovs: aovs_impl over a frame of the model's size whose one-sample ray buffer k_model_rays fills
+int model_aovs_impl(fw_scene *sc, const fw_camera_model *m, const fw_render_params *p, float *aov, fw_stats *stats) {
+    if (!sc || !m || !p || !aov) return fail(FW_ERR_BAD_ARG, "null argument");
+    fw::DModel dm; bool too_large = false;
+    if (int rc = model_prepare(m, dm, too_large)) return rc;
+    if (p->samples == 0 || p->samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^24");
+    if (p->outputs_on_device && ((uintptr_t)aov & 15u)) return fail(FW_ERR_BAD_ARG, "a device aov must be 16-byte aligned");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "W x H must be below 2^31 (the jitter's counter is 32-bit)");
+    fw_render_params P{};
+    P.width = m->width; P.height = m->height; P.samples = p->samples; P.gamma = 1.f; P.use_bvh = p->use_bvh; P.seed = p->seed;
+    P.rng_mode = FW_RNG_CTR; P.outputs_on_device = p->outputs_on_device; P.stream = p->stream;
+    return aovs_impl(sc, &P, aov, stats, &dm);
 }
 
 } // namespace
@@ -3900,6 +4076,25 @@ int fw_render_aovs(fw_scene *scene, const fw_render_params *params, float *aov, 
     try { return aovs_impl(scene, params, aov, stats); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_render_aovs"); }
+}
+
+int fw_model_rays(const fw_camera_model *model, int device, uint32_t first_sample, uint32_t n_samples, float *rays, int on_device, void *stream) {
+    try { return model_rays_impl(model, device, first_sample, n_samples, rays, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_model_rays"); }
+}
+
+int fw_render_model(fw_scene *scene, const fw_camera_model *model, const fw_render_rays_params *rp, float *accum, uint8_t *rgb8,
+                    float *gamma_rgb, float *linear_rgb, fw_stats *stats) {
+    try { return render_model_impl(scene, model, rp, accum, rgb8, gamma_rgb, linear_rgb, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_render_model"); }
+}
+
+int fw_render_model_aovs(fw_scene *scene, const fw_camera_model *model, const fw_render_params *params, float *aov, fw_stats *stats) {
+    try { return model_aovs_impl(scene, model, params, aov, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_render_model_aovs"); }
 }
 
 int fw_denoise(const fw_denoise_params *p, const float *color, const float *aov, const float *moments, float *linear_rgb, float *gamma_rgb,

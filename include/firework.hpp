@@ -178,6 +178,28 @@ struct CameraSettings {   // camera.rs:26-36 defaults
     CameraSettings focus_dist(float d) && { focus_dist_ = d; return std::move(*this); }
 };
 
+// A non-pinhole camera whose rays are generated on the device (fw_camera_model; not in the reference): an equirectangular panorama from a
+// position, parallel rays over a view plane view_height high, or an equidistant full-frame fisheye of fov degrees across the diagonal.
+struct CameraModel {
+    fw_camera_model m{};
+    static CameraModel panorama(Vec3 position, size_t width, size_t height) {
+        return make(FW_MODEL_PANORAMA, CameraSettings::default_().cam_pos(position), width, height, 0.0, 0.0); }
+    static CameraModel orthographic(const CameraSettings &camera, double view_height, size_t width, size_t height) {
+        return make(FW_MODEL_ORTHOGRAPHIC, camera, width, height, view_height, 0.0); }
+    static CameraModel fisheye(const CameraSettings &camera, double fov, size_t width, size_t height) {
+        return make(FW_MODEL_FISHEYE, camera, width, height, 0.0, fov); }
+    CameraModel seed(uint64_t s) && { m.seed = s; return std::move(*this); }
+    CameraModel jitter(bool on) && { m.jitter = on ? 1 : 0; return std::move(*this); }
+    CameraModel chunk_samples(uint32_t n) && { m.chunk_samples = n; return std::move(*this); }
+  private:
+    static CameraModel make(int kind, const CameraSettings &c, size_t width, size_t height, double view_height, double fov) {
+        CameraModel r; r.m.kind = kind; r.m.width = (uint32_t)width; r.m.height = (uint32_t)height;
+        r.m.camera = fw_camera_settings{fw_vec3{c.cam_pos_.x, c.cam_pos_.y, c.cam_pos_.z}, fw_vec3{c.look_at_.x, c.look_at_.y, c.look_at_.z}, c.vfov,
+                                        c.aperture_, c.focus_dist_};
+        r.m.view_height = view_height; r.m.fov = fov; r.m.jitter = 1;
+        return r; }
+};
+
 // Lowers a Scene to the flat arrays of fw_scene_desc (owning storage for the duration of a render call).
 class Lowered {
   public:
@@ -327,6 +349,26 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
         std::vector<std::vector<Color>> views;
         for (size_t v = 0; v < cams.size(); v++) views.emplace_back(all.begin() + v * n, all.begin() + (v + 1) * n);
         return views; }
+
+    // A CameraModel rendered on the device (not in the reference; fw_render_model): samples() samples of every pixel of the model's image
+    // (its own width x height; this renderer's camera and size are not used), the rays generated on the GPU chunk by chunk of samples.
+    std::vector<Color> render_model(const Scene &scene, const CameraModel &model, fw_stats *stats = nullptr) const {
+        const uint64_t n_rays = (uint64_t)model.m.width * model.m.height;
+        if (n_rays >= (1ull << 31))      // fw_render_model's own limit; n_rays is 32-bit, so the library could not even be told the size
+            throw std::runtime_error(std::string(fw_strerror(FW_ERR_UNSUPPORTED)) + " | W x H must be below 2^31");
+        Lowered low(scene);
+        fw_scene *sc = nullptr;
+        int rc = fw_scene_create(&low.desc, device_, &sc);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        const fw_render_params p = params();
+        fw_render_rays_params rp{};
+        rp.n_rays = (uint32_t)n_rays; rp.samples = p.samples; rp.per_sample_rays = 1; rp.seed = p.seed; rp.use_bvh = p.use_bvh;
+        rp.gamma = p.gamma; rp.flags = p.flags;
+        std::vector<Color> buffer((size_t)n_rays, Color{0, 0, 0});
+        rc = fw_render_model(sc, &model.m, &rp, nullptr, reinterpret_cast<uint8_t *>(buffer.data()), nullptr, nullptr, stats);
+        fw_scene_destroy(sc);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        return buffer; }
 
     // A denoised frame (not in the reference): samples() samples per pixel filtered by fw_denoise with `iterations` a-trous steps, guided by
     // fw_render_aovs at aov_samples samples.  The frame comes from fw_render_adaptive with min_samples = samples() (one round at the fixed

@@ -608,6 +608,79 @@ int fw_temporal(const fw_temporal_params *p, const float *color, const float *mo
                 const float *hist_color, const float *hist_moments, const float *hist_aov, const float *prev_position,
                 float *out_color, float *out_moments, float *out_history);
 
+/* ---- camera models on the device (additive at ABI 8) ---------------------------------------------------------------
+   Non-pinhole cameras whose rays are generated on the device (k_model_rays) in the layout fw_render_rays reads: n_samples x W*H x 6
+   floats (origin, direction), sample-major, row-major inside a sample with row 0 = the image top.
+   Jitter: pixel p (= row * W + x) of absolute sample s gets the sub-pixel offset (xi_x, xi_y) in [0, 1)^2, with the 32-bit mix
+       hash32(h) : h ^= h >> 16; h *= 0x7FEB352D; h ^= h >> 15; h *= 0x846CA68B; h ^= h >> 16
+       s32 = (uint32)seed ^ ((uint32)(seed >> 32) * 0x9E3779B9);  key = hash32(s32 ^ hash32(s + 0x9E3779B9))
+       xi_axis = (hash32(hash32(2 p + axis) ^ key) >> 8) * 2^-24,  axis 0 = x, 1 = y
+   (api.pixel_jitter in Python); jitter == 0: (1/2, 1/2).  Everything below is evaluated in float64 on the device and rounded to float32
+   once; the basis is camera.rs's, computed in float64 on the host: w = unit(cam_pos - look_at), u = unit(Y x w), v = w x u.
+   With px = x + xi_x and py = row + xi_y:
+     FW_MODEL_PANORAMA      equirectangular, the inverse of the HDR environment lookup: uu = px / W, vv = 1 - py / H, phi = pi - 2 pi uu,
+                            theta = pi vv - pi / 2, d = (cos theta cos phi, sin theta, cos theta sin phi); origin = cam_pos bit for bit.
+                            look_at, view_height and fov are not used.
+     FW_MODEL_ORTHOGRAPHIC  a view plane view_height high and view_height * W / H wide, centred on cam_pos: with s = px / W and
+                            t = 1 - py / H, origin = (cam_pos + ((s - 1/2) view_width) u) + ((t - 1/2) view_height) v;
+                            d = look_at - cam_pos bit for bit.  fov is not used.
+     FW_MODEL_FISHEYE       equidistant, full frame: a = 2 px - W, b = H - 2 py, rho = sqrt(a a + b b), r = rho / sqrt(W W + H H),
+                            theta = r * (fov / 2 in radians), d = sin theta * ((a u + b v) / rho) - cos theta * w, and d = -w where
+                            rho = 0; origin = cam_pos.  fov is the full angle across the image diagonal in degrees, in (0, 360].
+                            view_height is not used.
+   The camera's vfov, aperture and focus_dist are carried (they must be finite) and not used. */
+typedef enum fw_model_kind {
+    FW_MODEL_PANORAMA = 0,
+    FW_MODEL_ORTHOGRAPHIC = 1,
+    FW_MODEL_FISHEYE = 2
+} fw_model_kind;
+
+typedef struct fw_camera_model {
+    int32_t kind;                /* fw_model_kind */
+    uint32_t width, height;
+    fw_camera_settings camera;   /* cam_pos and look_at */
+    double view_height;          /* orthographic: finite and > 0 */
+    double fov;                  /* fisheye: degrees, in (0, 360] */
+    int32_t jitter;              /* 0: every sample goes through the pixel centres */
+    uint64_t seed;               /* of the jitter (a render's own draws take fw_render_rays_params.seed) */
+    uint32_t chunk_samples;      /* fw_render_model: samples whose rays are generated at a time; 0 = as many as fit 256 MiB */
+} fw_camera_model;
+
+/* fw_model_rays: the rays of the absolute samples [first_sample, first_sample + n_samples) of `model`, n_samples x W*H x 6 floats:
+   fw_camera_rays' counterpart.  `rays` is host memory, or with on_device device memory on `device`, written on `stream` and complete on
+   return.  Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL model or rays, an unknown kind, width or height
+   0, a non-finite camera field, (orthographic, fisheye) cam_pos == look_at or a view direction parallel to Y, (orthographic) a
+   view_height that is not finite and > 0, (fisheye) a fov outside (0, 360], n_samples == 0, first_sample + n_samples > 2^32, with
+   on_device rays not 4-byte aligned; FW_ERR_UNSUPPORTED for W x H >= 2^31 (the jitter's counter 2 p + axis is 32-bit); then
+   FW_ERR_NO_DEVICE without a GPU, and FW_ERR_BAD_ARG for a device index out of range. */
+int fw_model_rays(const fw_camera_model *model, int device, uint32_t first_sample, uint32_t n_samples, float *rays, int on_device,
+                  void *stream);
+
+/* fw_render_model: radiance through a camera model.  Bit for bit — accum, the outputs, stats.rays and rays_per_depth — what
+   fw_render_rays(scene, rp', rays = fw_model_rays(model, first_sample, samples), ...) gives, with rp' = *rp, per_sample_rays = 1 and
+   keys = NULL (entry i is keyed key_base + i), for every chunk size; rp->per_sample_rays and rp->keys are ignored and rp->n_rays must be
+   W x H.  The samples are rendered in chunks of model->chunk_samples (0: the most whose rays fit 256 MiB, at least 1): a chunk's rays
+   are generated into device scratch that the call allocates and frees on every path, then rendered on top of the running sums as a
+   fw_render_rays call of their own.  accum and the outputs are fw_render_rays' (host memory, or device memory with rp->on_device; accum
+   may be NULL only when first_sample == 0).
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, model or rp, what
+   fw_model_rays rejects in the model, samples outside 1..2^24, first_sample + samples >= 2^32, a gamma that is not finite or <= 0,
+   n_rays != W x H, a NULL accum with first_sample > 0, with on_device an accum that is not 16-byte aligned; FW_ERR_UNSUPPORTED for
+   W x H >= 2^31; then FW_ERR_NO_DEVICE.
+   stats: fw_render_rays' fields summed over the chunks (tlas_nodes, blas_nodes and reserved: the last chunk's); ms_render includes the
+   generator's launches, ms_raygen as well under FW_FLAG_TIME_KERNELS; ms_wall covers the whole call.  Synchronisation and the frame
+   graph are fw_render_rays'. */
+int fw_render_model(fw_scene *scene, const fw_camera_model *model, const fw_render_rays_params *rp, float *accum,
+                    uint8_t *rgb8, float *gamma_rgb, float *linear_rgb, fw_stats *stats);
+
+/* fw_render_model_aovs: fw_render_aovs' guide buffers for a camera model: sample s of pixel p is the model's ray (fw_model_rays at
+   sample s), traced and accumulated exactly as fw_render_aovs traces a camera ray — the same record layout, keys (params->seed, p, s,
+   segment 0), walks and accumulation order — so the records feed fw_denoise unchanged.  Of params only samples, use_bvh, seed,
+   outputs_on_device and stream are read; the frame's size is the model's.
+   Errors, in this order: FW_ERR_BAD_ARG for a NULL scene, model, params or aov, what fw_model_rays rejects in the model, samples
+   outside 1..2^24, with outputs_on_device an aov not 16-byte aligned; FW_ERR_UNSUPPORTED for W x H >= 2^31; FW_ERR_NO_DEVICE. */
+int fw_render_model_aovs(fw_scene *scene, const fw_camera_model *model, const fw_render_params *params, float *aov, fw_stats *stats);
+
 /* Diagnostic: the kernels' division / square-root helpers against the compiler's IEEE expansion, bit for bit,
    on n hashed operand pairs.  mode 0 = magnitudes 2^-40..2^40 (must be 0 mismatches), mode 1 = all bit patterns. */
 int fw_selftest_arith(int device, uint32_t n, uint32_t seed, int mode, uint64_t *div_mismatches, uint64_t *sqrt_mismatches);
