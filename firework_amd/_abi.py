@@ -35,6 +35,8 @@ FW_FLAG_ALL_EMITTERS = 16    # with FW_FLAG_LIGHT_SAMPLING: every emitting primi
 FW_EMITTER_RECORD_FLOATS = 5  # fw_selftest_emitters
 FW_EMITTER_SAMPLE_FLOATS = 9  # fw_selftest_emitter_sample
 FW_NO_HIT = 0xFFFFFFFF   # fw_hit.object of a miss
+FW_LIGHT_POINT, FW_LIGHT_SPOT, FW_LIGHT_DIRECTIONAL = range(3)   # fw_light_kind
+FW_MAX_LIGHTS = 65536
 
 f32, i32, u32, u64 = C.c_float, C.c_int32, C.c_uint32, C.c_uint64
 
@@ -80,6 +82,10 @@ class fw_scene_desc(C.Structure):
                 ("materials", C.POINTER(fw_material)), ("n_materials", u32),
                 ("textures", C.POINTER(fw_texture)), ("n_textures", u32),
                 ("environment", fw_environment)]
+
+
+class fw_light(C.Structure):
+    _fields_ = [("kind", i32), ("position", fw_vec3), ("direction", fw_vec3), ("intensity", fw_vec3), ("cos_inner", f32), ("cos_outer", f32)]
 
 
 class fw_camera_settings(C.Structure):

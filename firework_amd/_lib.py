@@ -47,6 +47,10 @@ def load(preload=False, device=None):
     lib.fw_scene_create.argtypes = [C.POINTER(A.fw_scene_desc), C.c_int, C.POINTER(C.c_void_p)]
     lib.fw_scene_update.restype = C.c_int
     lib.fw_scene_update.argtypes = [C.c_void_p, C.POINTER(A.fw_scene_desc)]
+    lib.fw_scene_set_lights.restype = C.c_int
+    lib.fw_scene_set_lights.argtypes = [C.c_void_p, C.POINTER(A.fw_light), C.c_uint32]
+    lib.fw_check_lights.restype = C.c_int
+    lib.fw_check_lights.argtypes = [C.POINTER(A.fw_light), C.c_uint32]
     lib.fw_scene_destroy.restype = None
     lib.fw_scene_destroy.argtypes = [C.c_void_p]
     lib.fw_render.restype = C.c_int
@@ -175,6 +179,20 @@ def selftest_wide_bvh(boxes, fmt):
     stats = (C.c_uint32 * 4)()
     _check(lib, lib.fw_selftest_wide_bvh(b.ctypes.data, b.shape[0], int(fmt), C.byref(bad), stats))
     return int(bad.value), dict(nodes=int(stats[0]), leaves=int(stats[1]), free_slots=int(stats[2]), depth=int(stats[3]))
+
+
+def _light_array(lights):
+    """(ctypes array or None, n) of a sequence of api lights or fw_light records"""
+    recs = [l if isinstance(l, A.fw_light) else l.to_abi() for l in lights]
+    return ((A.fw_light * len(recs))(*recs) if recs else None), len(recs)
+
+
+def check_lights(lights):
+    """fw_check_lights (CPU only, no device touched): raises FireworkError for a list fw_scene_set_lights would refuse.  `lights`: api
+    PointLight / SpotLight / DirectionalLight objects or _abi.fw_light records"""
+    lib = load()
+    arr, n = _light_array(lights)
+    _check(lib, lib.fw_check_lights(arr, n))
 
 
 def selftest_lights(scene_desc):
@@ -372,6 +390,16 @@ class DeviceScene:
         _check(lib, lib.fw_scene_create(scene_desc.ptr(), device, C.byref(h)))
         self.handle = h
         self.device = device
+        self._desc_lights = b""              # the lights the latest description carried, as set
+        if getattr(scene_desc, "lights", None):
+            self.set_lights(scene_desc.lights)
+            self._desc_lights = bytes(_light_array(scene_desc.lights)[0])
+
+    def set_lights(self, lights):
+        """fw_scene_set_lights: replaces this resident scene's point, spot and directional lights; an empty list removes
+        them.  FireworkError for a list the library refuses (the scene is then as it was)."""
+        arr, n = _light_array(lights)
+        _check(self._lib, self._lib.fw_scene_set_lights(self.handle, arr, n))
 
     def update(self, scene):
         """fw_scene_update: moves the objects of this resident scene.  `scene` is a SceneDesc of the scene this one was created from with
@@ -384,6 +412,12 @@ class DeviceScene:
         desc = self._desc.placements(scene) if isinstance(scene, Scene) else scene
         _check(self._lib, self._lib.fw_scene_update(self.handle, desc.ptr()))
         self._desc = desc
+        # (fw_scene_update keeps the lights; a description whose lights differ from the last description's has them set again)
+        lights = getattr(desc, "lights", None) or []
+        arr, n = _light_array(lights)
+        if (bytes(arr) if n else b"") != getattr(self, "_desc_lights", b""):     # (a scene wrapped without __init__ has set none)
+            self.set_lights(lights)
+            self._desc_lights = bytes(arr) if n else b""
 
     def render(self, renderer, pixel_ids=None, out_device_ptrs=None, stream=None):
         """fw_render.  out_device_ptrs = (rgb8, gamma, linear) raw device pointers (ints or None) to

@@ -499,12 +499,52 @@ class RenderObject:
         return self
 
 
+# --------------------------------------------------------------------------- lights without area
+class Light:
+    """A point, spot or directional light: found by next-event estimation alone (no path can hit it), so it lights Lambertian and
+    Isotropic surfaces of a resident scene and nothing else.  The reference has none."""
+
+
+class PointLight(Light):
+    """Radiant intensity `intensity` (rgb, per steradian) from `position`, the same in every direction."""
+
+    def __init__(self, position, intensity):
+        self.position, self.intensity = _v3(position), _v3(intensity)
+
+    def to_abi(self) -> A.fw_light:
+        return A.fw_light(A.FW_LIGHT_POINT, A.vec3(self.position), A.vec3((0, 0, 0)), A.vec3(self.intensity), 0.0, 0.0)
+
+
+class SpotLight(Light):
+    """A point light that shines along `direction`: full intensity within `inner_deg` of the axis, none beyond `outer_deg`, a
+    smoothstep of the cosine between (0 <= inner_deg <= outer_deg <= 180)."""
+
+    def __init__(self, position, direction, intensity, inner_deg, outer_deg):
+        self.position, self.direction, self.intensity = _v3(position), _v3(direction), _v3(intensity)
+        self.inner_deg, self.outer_deg = float(inner_deg), float(outer_deg)
+
+    def to_abi(self) -> A.fw_light:
+        ci, co = np.cos(np.radians(self.inner_deg)), np.cos(np.radians(self.outer_deg))
+        return A.fw_light(A.FW_LIGHT_SPOT, A.vec3(self.position), A.vec3(self.direction), A.vec3(self.intensity), float(ci), float(co))
+
+
+class DirectionalLight(Light):
+    """Parallel light travelling along `direction` (any length), `irradiance` (rgb) on a plane that faces it."""
+
+    def __init__(self, direction, irradiance):
+        self.direction, self.irradiance = _v3(direction), _v3(irradiance)
+
+    def to_abi(self) -> A.fw_light:
+        return A.fw_light(A.FW_LIGHT_DIRECTIONAL, A.vec3((0, 0, 0)), A.vec3(self.direction), A.vec3(self.irradiance), 0.0, 0.0)
+
+
 class Scene:
     """src/scene.rs:19-91"""
 
     def __init__(self):
         self.render_objects: List[RenderObject] = []
         self.materials: List[Material] = []
+        self.lights: List[Light] = []               # point, spot and directional lights (DESIGN.md §9l): not part of fw_scene_desc
         self.environment: Environment = ColorEnv()  # Scene::new(): black ColorEnv (scene.rs:36)
 
     @staticmethod
@@ -526,6 +566,14 @@ class Scene:
     def add_material(self, mat: Material) -> int:
         self.materials.append(mat)
         return len(self.materials) - 1
+
+    def add_light(self, light: Light) -> int:
+        """Adds a PointLight, SpotLight or DirectionalLight.  Resident scenes (DeviceScene and every Renderer call that makes one, render
+        and render_full of a lit scene included) render with them; the tiled multi-GPU path, which passes a bare description, does not."""
+        if not isinstance(light, Light):
+            raise TypeError(f"not a light: {type(light).__name__}")
+        self.lights.append(light)
+        return len(self.lights) - 1
 
     def get_material(self, idx):
         return self.materials[idx]
@@ -687,6 +735,8 @@ class SceneDesc:
         d.textures, d.n_textures = self.textures, len(texs)
         d.environment = env
         self.desc = d
+        # the lights travel beside the description (fw_scene_set_lights): DeviceScene sets them after it created the scene
+        self.lights = [l.to_abi() for l in getattr(scene, "lights", [])]
 
     def ptr(self):
         return C.byref(self.desc)
@@ -721,6 +771,7 @@ class SceneDesc:
         d.textures, d.n_textures = self.textures, self.desc.n_textures
         d.environment = self.desc.environment
         out.desc = d
+        out.lights = [l.to_abi() for l in getattr(scene, "lights", [])]
         return out
 
     def content_hash(self) -> str:
@@ -748,6 +799,9 @@ class SceneDesc:
             for i in range(n):
                 feed(arr[i])
         feed(d.environment)
+        for l in getattr(self, "lights", []):           # (nothing where there are none: such a scene keeps its hash)
+            h.update(b"light")
+            feed(l)
         for a in self._keep:
             if isinstance(a, np.ndarray):
                 h.update(str(a.shape).encode())
@@ -1231,6 +1285,12 @@ class Renderer:
         from . import _lib
         sd = scene if isinstance(scene, SceneDesc) else scene.to_desc()
         ids = None if pixel_ids is None else np.ascontiguousarray(np.asarray(pixel_ids, dtype=np.uint32))
+        if getattr(sd, "lights", None):      # fw_render_scene takes a bare description, which carries no lights: a resident scene does
+            ds = _lib.DeviceScene(sd, device)
+            try:
+                return ds.render(self, ids)
+            finally:
+                ds.close()
         return _lib.render_scene(sd, self, ids, device)
 
     def render_progressive(self, scene, passes: int, device: int = 0, checkpoint: Optional[str] = None):

@@ -266,6 +266,21 @@ struct DEmitters {
 };
 constexpr uint32_t EMITTER_MAX_ENTRIES = 1u << 26;
 
+// ---- point, spot and directional lights (fw_scene_set_lights) ----------------------------------------------------------
+// Lights without area, reached by next-event estimation alone.  rec[3 i .. 3 i + 2] of light i: (position xyz, bits kind), (unit direction
+// xyz, cos_inner), (intensity rgb, cos_outer); kind is fw_light_kind.  n > 0.  p_delta: the probability of picking the group (1 alone, 1/2
+// beside the emitters of DLights, whose p_pick is then (1 - p_delta) / N), uniform inside it.  A kernel argument of its own, beside DShadow.
+struct DDeltaLights {
+    const float4 *rec;
+    uint32_t n;
+    float p_delta;
+};
+constexpr uint32_t DELTA_MAX_LIGHTS = 65536;
+// A delta light's shadow ray in DShadow.obj: a directional light's is MISS (visible iff the walk misses, as an environment ray); a point or
+// spot light's is SHADOW_NEAR (visible iff the walk misses or its closest hit lies at t >= 1, where the light sits).  Emitter rays of the same
+// queue carry object indices, which stay below it (fw_scene_set_lights refuses a scene whose indices could reach it).
+constexpr uint32_t SHADOW_NEAR = 0xfffffffeu;
+
 // launch wrappers (fw_kernels.hip)
 struct LaunchCfg {
     hipStream_t stream;
@@ -316,8 +331,8 @@ void launch_shade(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, 
 // environment shadow rays, visible iff they miss), pl (the full hit code: visible iff the closest hit is the sampled primitive, or a miss
 // for an environment ray)
 void launch_shade_nee(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
-                      float4 *sample_rad, int segment, const DShadow &, const DEnvDist *ed, const DEmitters *em);
-void launch_shadow_resolve(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment, bool env, bool pl);
+                      float4 *sample_rad, int segment, const DShadow &, const DEnvDist *ed, const DEmitters *em, const DDeltaLights *dl = nullptr);
+void launch_shadow_resolve(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment, bool env, bool pl, bool dl = false);
 // the table of env (w x h): scratch = 2 h + 1 doubles (row totals, the total); p_out (optional): the per-texel probabilities; *total = the total weight
 // (host memory, after a synchronisation of `stream`)
 int build_env_dist(hipStream_t stream, const DEnv &env, float *cdf_m, float *cdf_c, float *dens, float *p_out, double *scratch, double *total);

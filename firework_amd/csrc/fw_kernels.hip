@@ -3322,6 +3322,31 @@ __device__ __forceinline__ V3 entry_emit(const DScene &sc, const float4 *matp, c
 // ------------------------------------------------------------------------------------------------
 // One path at its hit (or miss): emission / environment for paths that end here (written to sample_rad, every
 // path writes exactly once), the scattered ray and throughput for those that continue (render.rs:19-31).
+// ------------------------------------------------------------------------------------------------
+// Point, spot and directional lights (fw_scene_set_lights): lights without area, which only next-event estimation reaches.
+// ------------------------------------------------------------------------------------------------
+// Light i of dl seen from x: the shadow ray's direction d (a point or spot light sits at t = 1 of it; a directional light's ray runs until
+// it misses), the unit direction w towards the light and L of §9l's table: I / d^2, I s / d^2 with the spot's smoothstep s, or E.  Returns the
+// ray's code in the shadow queue: SHADOW_NEAR (visible iff the walk misses or its closest hit has t >= 1) or MISS (visible iff it misses).
+__device__ __forceinline__ uint32_t delta_sample(const DDeltaLights &dl, uint32_t i, V3 x, V3 &d, V3 &w, V3 &L) {
+    const float4 r0 = dl.rec[3u * i], r1 = dl.rec[3u * i + 1u], r2 = dl.rec[3u * i + 2u];
+    const uint32_t kind = __float_as_uint(r0.w);
+    const V3 axis = mk(r1.x, r1.y, r1.z), I = mk(r2.x, r2.y, r2.z);
+    if (kind == 2u) { d = -axis; w = d; L = I; return MISS; }
+    d = mk(r0.x, r0.y, r0.z) - x;
+    const float d2 = dot(d, d);
+    L = mk(0.f, 0.f, 0.f); w = L;
+    if (!(d2 > 0.f)) return SHADOW_NEAR;                  // the vertex is the light's own point: nothing to sample
+    w = d / fsqrt(d2);
+    float s = 1.f;
+    if (kind == 1u) {                                     // full inside cos_inner, none outside cos_outer, a smoothstep of the cosine between
+        const float c = -dot(w, axis), ci = r1.w, co = r2.w;
+        if (ci > co) { const float t = fminf(fmaxf(fdiv(c - co, ci - co), 0.f), 1.f); s = t * t * (3.f - 2.f * t); }
+        else s = c >= co ? 1.f : 0.f;
+    }
+    L = fdiv(s, d2) * I;
+    return SHADOW_NEAR;
+}
 // "Expensive" shading (k_shade's deferred list): what a few lanes of a chunk do while the others wait — a texture that is not a
 // constant (three sinf for a checker, 5-10 octaves of Perlin noise, an image lookup behind atan2f + asinf), the Fresnel branch
 // of a dielectric (normalise, refract, powf), a miss into an HDR map (atan2f + asinf + a gather from 100 MB).
@@ -3337,12 +3362,15 @@ __device__ __forceinline__ bool expensive_shading(const DScene &sc, const float4
 // Isotropic vertex (*ls: the shadow ray, left to k_shadow_resolve), and the path's visible light samples (sh->nee) in its deposit.
 // ENV (with LS): k_shade_env: the HDR map is a sampled light as well (*ed), picked with probability ed->p_env.
 // PL (with LS): k_shade_pl / k_shade_pl_env: the emitters are the entries of *em (every emitting primitive, picked by power).
-template <bool CHEAP_ONLY = false, bool CHAIN = false, bool LS = false, bool ENV = false, bool PL = false>
+// DL (with LS, without ENV and PL): k_shade_dl: the point, spot and directional lights of *dl are sampled too, as a group picked
+// with probability dl->p_delta beside §9g's emitters (alone where sh->lt.n = 0).
+template <bool CHEAP_ONLY = false, bool CHAIN = false, bool LS = false, bool ENV = false, bool PL = false, bool DL = false>
 __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, const float4 *objp, const float4 *matp,
                                            const float4 *texp, const Ray &r, V3 beta, uint32_t chain, uint32_t path_id, float t_hit,
                                            uint32_t hit_code, int segment, float4 *__restrict__ sample_rad, Ray &nr, V3 &nbeta, uint32_t &nchain PH_ARG,
                                            const RngKey *pre_key = nullptr,       // pre_key: the path's RNG key, when the caller has fetched it already (k_shade, FW_SHADE_PIPE)
-                                           const DShadow *sh = nullptr, LsIO *ls = nullptr, const DEnvDist *ed = nullptr, const DEmitters *em = nullptr) {
+                                           const DShadow *sh = nullptr, LsIO *ls = nullptr, const DEnvDist *ed = nullptr, const DEmitters *em = nullptr,
+                                           const DDeltaLights *dl = nullptr) {
     bool alive = false;
     const uint32_t obj_index = hit_code == MISS ? MISS : (hit_code >> sc.prim_bits);
     V3 rad = mk(0.f, 0.f, 0.f);
@@ -3405,7 +3433,9 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
                     const float s_ = fdiv(pk * entry_pdf_hit(sc, o, prim, r.o, r.d, t_hit), ls->pb_in);
                     texc = fdiv(1.f, 1.f + s_ * s_) * texc;
                 }
-            } else if (LS && ls->pb_in > 0.f && obj_kind(o) <= 3u) {           // a sampled light, reached from a light-sampling vertex: p_b^2 / (p_b^2 + p_l^2)
+            // (DL with an empty emitter table: p_pick = 0 gives s_ = 0 and weight 1 already, unless light_pdf_hit overflows to inf and 0 x inf
+            //  makes a NaN; the test on lt.n spares that and the work.  DL = false folds it away: the other kernels' code is as it was)
+            } else if (LS && ls->pb_in > 0.f && obj_kind(o) <= 3u && (!DL || sh->lt.n != 0u)) {   // a sampled light, reached from a light-sampling vertex: p_b^2 / (p_b^2 + p_l^2)
                 const float s_ = fdiv(sh->lt.p_pick * light_pdf_hit(o, r.o, r.d, t_hit), ls->pb_in);
                 texc = fdiv(1.f, 1.f + s_ * s_) * texc;
             }
@@ -3449,7 +3479,16 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
                 const V3 n_b = mkind == 0 ? h.normal : mk(0.f, 0.f, 0.f);      // (Isotropic: n + u with n = 0)
                 ls->pb_out = scatter_pdf(n_b, normalized(nr.d));
                 const uint4 lu = draw(key, P_LIGHT, segment, 0);
-                if (ENV && u2f(lu.x) < ed->p_env) {                            // the environment: visible iff the shadow ray misses
+                if (DL && (sh->lt.n == 0u || u2f(lu.x) < dl->p_delta)) {       // a point, spot or directional light: weight 1, no BSDF ray finds it
+                    const uint32_t li = min((uint32_t)(fdiv(u2f(lu.x), dl->p_delta) * (float)dl->n), dl->n - 1u);
+                    V3 d, w, L;
+                    const uint32_t code = delta_sample(*dl, li, h.point, d, w, L);
+                    const float pb = (L.x > 0.f || L.y > 0.f || L.z > 0.f) ? scatter_pdf(n_b, w) : 0.f;
+                    if (pb > 0.f) {
+                        const V3 c = (beta * atten) * L * fdiv(pb, fdiv(dl->p_delta, (float)dl->n));        // beta albedo p_b L / p, p = p_delta / M
+                        if (c.x > 0.f || c.y > 0.f || c.z > 0.f) { ls->shadow = true; ls->sray = Ray{h.point, d}; ls->sobj = code; ls->pending = c; }
+                    }
+                } else if (ENV && u2f(lu.x) < ed->p_env) {                     // the environment: visible iff the shadow ray misses
                     uint32_t t_drawn;
                     const V3 d = env_dist_sample(*ed, draw(key, P_LIGHT, segment, 1), t_drawn);
                     const unsigned long long ti = env_texel(sc.env, d);
@@ -3475,7 +3514,8 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
                     }
                 } else {
                     // (with the environment in the set the emitters share the rest of [0, 1): (xi - p_env) / (1 - p_env) picks among them)
-                    const float xi = ENV ? fdiv(u2f(lu.x) - ed->p_env, 1.f - ed->p_env) : u2f(lu.x);
+                    // (and so beside the delta lights of §9l: (xi - p_delta) / (1 - p_delta))
+                    const float xi = ENV ? fdiv(u2f(lu.x) - ed->p_env, 1.f - ed->p_env) : (DL ? fdiv(u2f(lu.x) - dl->p_delta, 1.f - dl->p_delta) : u2f(lu.x));
                     const uint32_t li = min((uint32_t)(xi * (float)sh->lt.n), sh->lt.n - 1u);
                     const uint32_t lobj = sh->lt.obj[li];
                     const Obj lo = load_obj(objp, lobj);
@@ -3705,8 +3745,8 @@ __attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
 __global__ __launch_bounds__(WB) void k_shade_ls(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
                                                     float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                     uint32_t n_mat, uint32_t n_tex, DShadow sh) {
-    constexpr bool ENV = false, PL = false;
-    const DEnvDist *const edp = nullptr; const DEmitters *const emp = nullptr;
+    constexpr bool ENV = false, PL = false, DL = false;
+    const DEnvDist *const edp = nullptr; const DEmitters *const emp = nullptr; const DDeltaLights *const dlp = nullptr;
 #include "fw_shade_nee.inc"
 }
 // Environment sampling: k_shade_ls with the environment among the sampled lights (*ed), in shading mode 0 only.  A kernel of its
@@ -3718,8 +3758,8 @@ __global__ __launch_bounds__(WB) void k_shade_env(DScene sc, DFrame f, DPaths in
                                                      float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                      uint32_t n_mat, uint32_t n_tex, DShadow sh, DEnvDist ed) {
     constexpr int MODE = 0;                  // an HDR map is an expensive case: the scene never takes mode 1
-    constexpr bool ENV = true, PL = false;
-    const DEnvDist *const edp = &ed; const DEmitters *const emp = nullptr;
+    constexpr bool ENV = true, PL = false, DL = false;
+    const DEnvDist *const edp = &ed; const DEmitters *const emp = nullptr; const DDeltaLights *const dlp = nullptr;
 #include "fw_shade_nee.inc"
 }
 // One segment's shadow rays after their walk: a ray whose closest hit is the light it sampled adds its pending radiance to the path's
@@ -3756,8 +3796,8 @@ __attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
 __global__ __launch_bounds__(WB) void k_shade_pl(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
                                                     float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                     uint32_t n_mat, uint32_t n_tex, DShadow sh, DEmitters em) {
-    constexpr bool ENV = false, PL = true;
-    const DEnvDist *const edp = nullptr; const DEmitters *const emp = &em;
+    constexpr bool ENV = false, PL = true, DL = false;
+    const DEnvDist *const edp = nullptr; const DEmitters *const emp = &em; const DDeltaLights *const dlp = nullptr;
 #include "fw_shade_nee.inc"
 }
 template <int LDS_TAB>
@@ -3766,8 +3806,8 @@ __global__ __launch_bounds__(WB) void k_shade_pl_env(DScene sc, DFrame f, DPaths
                                                      float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                      uint32_t n_mat, uint32_t n_tex, DShadow sh, DEnvDist ed, DEmitters em) {
     constexpr int MODE = 0;                  // (as k_shade_env)
-    constexpr bool ENV = true, PL = true;
-    const DEnvDist *const edp = &ed; const DEmitters *const emp = &em;
+    constexpr bool ENV = true, PL = true, DL = false;
+    const DEnvDist *const edp = &ed; const DEmitters *const emp = &em; const DDeltaLights *const dlp = nullptr;
 #include "fw_shade_nee.inc"
 }
 // The resolve of k_shade_pl / k_shade_pl_env: sh.obj holds the sampled primitive's full hit code (object << prim_bits | prim; MISS for an
@@ -3779,6 +3819,35 @@ __global__ __launch_bounds__(WB) void k_shadow_resolve_pl(DShadow sh, const floa
     for (uint32_t j = lane; j < n; j += 64u) {
         const uint32_t i = base + j;
         if (__float_as_uint(hits[i].y) != sh.obj[i]) continue;
+        const float4 p = sh.state[i];
+        float4 &e = sh.nee[__float_as_uint(p.w)];
+        e = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, 0.f);
+    }
+}
+// Point, spot and directional lights: k_shade_ls with the delta lights of `dl` among the sampled lights (shade_path's DL), the
+// fifth kernel around fw_shade_nee.inc and a kernel of its own for the same reason as the others: §9g-§9i's kernels stay as they are.
+template <int LDS_TAB, int MODE>
+__attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
+__global__ __launch_bounds__(WB) void k_shade_dl(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
+                                                    float4 *__restrict__ sample_rad, DQueue q, int segment,
+                                                    uint32_t n_mat, uint32_t n_tex, DShadow sh, DDeltaLights dl) {
+    constexpr bool ENV = false, PL = false, DL = true;
+    const DEnvDist *const edp = nullptr; const DEmitters *const emp = nullptr; const DDeltaLights *const dlp = &dl;
+#include "fw_shade_nee.inc"
+}
+// The resolve of k_shade_dl, the fourth visibility rule: an emitter's ray counts iff its closest hit is the emitter's object
+// (k_shadow_resolve's rule), a directional light's (sh.obj = MISS) iff the walk misses, and a point or spot light's (SHADOW_NEAR) iff the walk
+// misses or its closest hit lies at or beyond the light, t >= 1.
+__global__ __launch_bounds__(WB) void k_shadow_resolve_dl(DShadow sh, const float2 *__restrict__ hits, DQueue q, int segment, uint32_t prim_bits) {
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    if (w >= q.n_waves) return;
+    const uint32_t n = sh.wcount[(size_t)(segment + 1) * q.n_waves + w], base = w * q.cap;
+    for (uint32_t j = lane; j < n; j += 64u) {
+        const uint32_t i = base + j, want = sh.obj[i];
+        const float2 hr = hits[i];
+        const uint32_t code = __float_as_uint(hr.y);
+        const bool visible = code == MISS ? want >= SHADOW_NEAR : (want == SHADOW_NEAR ? hr.x >= 1.f : (code >> prim_bits) == want);
+        if (!visible) continue;
         const float4 p = sh.state[i];
         float4 &e = sh.nee[__float_as_uint(p.w)];
         e = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, 0.f);
@@ -4611,11 +4680,11 @@ void launch_shade(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths 
 #undef FW_SHADE_C
 #undef FW_SHADE
 }
-// The four light-sampling shade kernels: ed = the environment is among the sampled lights (k_shade_env), em = the emitters are the entries
+// The five light-sampling shade kernels: dl = the delta lights of *dl are sampled (k_shade_dl, §9l: never with ed or em), ed = the environment is among the sampled lights (k_shade_env), em = the emitters are the entries
 // of *em (k_shade_pl), both (k_shade_pl_env), neither (k_shade_ls).  launch_shade's table modes; the shading mode is 0 or 1 (a light-sampling
 // frame never takes the list), and 0 alone with ed: an HDR map is an expensive case.
 void launch_shade_nee(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
-                      float4 *sample_rad, int segment, const DShadow &sh, const DEnvDist *ed, const DEmitters *em) {
+                      float4 *sample_rad, int segment, const DShadow &sh, const DEnvDist *ed, const DEmitters *em, const DDeltaLights *dl) {
     const ShadeTables t = shade_tables(c, sc);
     const bool m1 = c.shade_mode == 1;
 #define FW_NEE(K, ...) hipLaunchKernelGGL(K, wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, __VA_ARGS__)
@@ -4623,15 +4692,17 @@ void launch_shade_nee(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPa
         if (ed && em) FW_NEE(k_shade_pl_env<L>, sh, *ed, *em); \
         else if (ed) FW_NEE(k_shade_env<L>, sh, *ed); \
         else if (em) { if (m1) FW_NEE((k_shade_pl<L, 1>), sh, *em); else FW_NEE((k_shade_pl<L, 0>), sh, *em); } \
-        else { if (m1) FW_NEE((k_shade_ls<L, 1>), sh); else FW_NEE((k_shade_ls<L, 0>), sh); } \
+        else if (!dl) { if (m1) FW_NEE((k_shade_ls<L, 1>), sh); else FW_NEE((k_shade_ls<L, 0>), sh); } \
+        else { if (m1) FW_NEE((k_shade_dl<L, 1>), sh, *dl); else FW_NEE((k_shade_dl<L, 0>), sh, *dl); } \
     } while (0)
     if (t.lt == 1) FW_NEE_L(1); else if (t.lt == 2) FW_NEE_L(2); else FW_NEE_L(0);
 #undef FW_NEE_L
 #undef FW_NEE
 }
 // One resolve kernel per visibility rule (see the three kernels): env / pl as launch_shade_nee's ed / em of the segment's shade
-void launch_shadow_resolve(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment, bool env, bool pl) {
-    if (pl) hipLaunchKernelGGL(k_shadow_resolve_pl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment);
+void launch_shadow_resolve(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment, bool env, bool pl, bool dl) {
+    if (dl) hipLaunchKernelGGL(k_shadow_resolve_dl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
+    else if (pl) hipLaunchKernelGGL(k_shadow_resolve_pl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment);
     else if (env) hipLaunchKernelGGL(k_shadow_resolve_env, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
     else hipLaunchKernelGGL(k_shadow_resolve, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
 }

@@ -988,7 +988,12 @@ struct fw_scene {
     uint32_t emit_cols = 0;       // the table's columns (entries of positive weight)
     size_t emit_ent_off = 0, emit_first_off = 0;
     double emit_build_ms = 0;
+    // point, spot and directional lights (fw_scene_set_lights): fw::DDeltaLights.rec, three float4 per light, in an allocation
+    // of the scene's own that fw_scene_update leaves alone
+    DevBuf dlights;
+    uint32_t n_dlights = 0;
     ~fw_scene() {
+        dlights.release();
         data.release();
         obj_data.release();
         lights.release();
@@ -1935,7 +1940,9 @@ int update_scene_impl(fw_scene *sc, const fw_scene_desc *desc) {
         if (int rc = create_scene_impl(desc, sc->device, &ns, &reach)) return rc;
         DevBuf old_data = sc->data, old_obj = sc->obj_data, old_lights = sc->lights, kept_env = sc->env_dist, old_emitters = sc->emitters;
         const int kept_env_state = sc->env_state; const double kept_env_ms = sc->env_build_ms;
-        *sc = *ns;                                     // (the handle stays the caller's; its DevBufs now name the new allocations)
+        const DevBuf kept_dl = sc->dlights; const uint32_t kept_n_dl = sc->n_dlights;     // (the delta lights stay: `ns` has none, and frees none)
+        *sc = *ns;
+        sc->dlights = kept_dl; sc->n_dlights = kept_n_dl;                                     // (the handle stays the caller's; its DevBufs now name the new allocations)
         ns->data = old_data; ns->obj_data = old_obj; ns->lights = old_lights;   // ... and the old ones go with `ns`
         // (the emitters' table is built again for the new scene, whose triangles are new allocations: the old one goes with `ns`)
         ns->emitters = old_emitters;
@@ -1983,6 +1990,66 @@ int update_scene_impl(fw_scene *sc, const fw_scene_desc *desc) {
     sc->ms_objects = ms_objects; sc->ms_objects_dev = L.dev_times.upload_ms + L.dev_times.kernel_ms + L.dev_times.copy_ms;
     if (O.trace) fprintf(stderr, "[firework] scene_update: %u objects, TLAS build %.2f ms host, %.2f ms device, %u meshes rebuilt, %zu B uploaded, %u hoisted\n",
                          desc->n_objects, sc->ms_objects, sc->ms_objects_dev, 0u, total, sc->d.n_hoisted);
+    return FW_OK;
+}
+
+// ---- fw_scene_set_lights, fw_check_lights ---------------------------------------------------------------------------------
+int check_lights_impl(const fw_light *lights, uint32_t n) {
+    if (n > FW_MAX_LIGHTS) return fail(FW_ERR_BAD_ARG, "lights: more than FW_MAX_LIGHTS (65536) lights");
+    if (n && !lights) return fail(FW_ERR_BAD_ARG, "lights: null argument");
+    for (uint32_t i = 0; i < n; i++) {
+        const fw_light &l = lights[i];
+        auto bad = [&](const char *what) { return fail(FW_ERR_BAD_ARG, "lights[" + std::to_string(i) + "]: " + what); };
+        if (l.kind != FW_LIGHT_POINT && l.kind != FW_LIGHT_SPOT && l.kind != FW_LIGHT_DIRECTIONAL) return bad("unknown kind");
+        for (float v : {l.position.x, l.position.y, l.position.z, l.direction.x, l.direction.y, l.direction.z, l.intensity.x, l.intensity.y,
+                        l.intensity.z, l.cos_inner, l.cos_outer})
+            if (!std::isfinite(v)) return bad("a field is not finite");
+        if (l.intensity.x < 0.f || l.intensity.y < 0.f || l.intensity.z < 0.f) return bad("negative intensity");
+        if (l.kind != FW_LIGHT_POINT && l.direction.x == 0.f && l.direction.y == 0.f && l.direction.z == 0.f) return bad("zero direction");
+        if (l.kind == FW_LIGHT_SPOT && !(-1.f <= l.cos_outer && l.cos_outer <= l.cos_inner && l.cos_inner <= 1.f))
+            return bad("spot cosines must satisfy -1 <= cos_outer <= cos_inner <= 1");
+    }
+    return FW_OK;
+}
+int set_lights_impl(fw_scene *sc, const fw_light *lights, uint32_t n) {
+    if (!sc) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = check_lights_impl(lights, n)) return rc;
+    if (n == 0) { sc->n_dlights = 0; return FW_OK; }
+    // (the shadow queue marks a point light's ray with fw::SHADOW_NEAR, which no emitter's object index may equal)
+    if (sc->d.n_objects >= fw::SHADOW_NEAR) return fail(FW_ERR_UNSUPPORTED, "too many objects for a scene with lights");
+    // fw::DDeltaLights.rec: (position, kind), (unit direction, cos_inner), (intensity, cos_outer); the direction normalised in double
+    std::vector<float> rec((size_t)n * 12, 0.f);
+    for (uint32_t i = 0; i < n; i++) {
+        const fw_light &l = lights[i];
+        float *r = &rec[(size_t)i * 12];
+        const uint32_t kind = (uint32_t)l.kind;
+        r[0] = l.position.x; r[1] = l.position.y; r[2] = l.position.z; std::memcpy(&r[3], &kind, 4);
+        const double dx = l.direction.x, dy = l.direction.y, dz = l.direction.z, len = std::sqrt(dx * dx + dy * dy + dz * dz);
+        if (len > 0) { r[4] = (float)(dx / len); r[5] = (float)(dy / len); r[6] = (float)(dz / len); }
+        r[7] = l.cos_inner;
+        r[8] = l.intensity.x; r[9] = l.intensity.y; r[10] = l.intensity.z; r[11] = l.cos_outer;
+    }
+    const size_t bytes = rec.size() * 4, total = (bytes + 255) & ~(size_t)255;
+    HIPCHK(hipSetDevice(sc->device));
+    Workspace *ws = workspace_for(sc->device);
+    if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
+    std::lock_guard<std::mutex> ws_guard(ws->mu);
+    if (int rc = init_device_locked(ws, sc->device)) return rc;
+    if (int rc = staging_reserve_locked(ws, total)) return rc;
+    if (sc->dlights.bytes < total || !sc->dlights.p) {
+        DevBuf nb;
+        if (int rc = nb.alloc(total)) return rc;
+        sc->dlights.release();                       // (no render of this scene is in flight: every call drains its stream before it returns)
+        sc->dlights = nb;
+    }
+    uint8_t *blob = (uint8_t *)ws->staging;
+    std::memset(blob, 0, total);
+    std::memcpy(blob, rec.data(), bytes);
+    // (a failed upload leaves the scene without lights rather than with half-written ones)
+    sc->n_dlights = 0;
+    fw::launch_upload(ws->upload_stream, blob, sc->dlights.p, total);
+    if (hipEventRecord(ws->ev_upload, ws->upload_stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail(FW_ERR_HIP, "light upload failed");
+    sc->n_dlights = n;
     return FW_OK;
 }
 
@@ -2053,6 +2120,9 @@ void set_walk_cfg(fw::LaunchCfg &cfg, const fw_scene *sc, const Options &O, cons
 static bool light_sampling(const fw_scene *sc, const fw_render_params *p) {
     return (p->flags & FW_FLAG_LIGHT_SAMPLING) != 0 && sc->n_lights > 0 && sc->ls_vertices;
 }
+// The scene's point, spot and directional lights are active where it has some and a material whose vertices sample them:
+// no flag, a delta light can be reached in no other way.  Such a frame takes the light-sampling layout whatever its flags.
+static bool delta_lights(const fw_scene *sc) { return sc->n_dlights > 0 && sc->ls_vertices; }
 // ---- environment sampling -------------------------------------------------------------------------------------------
 // The table of an HDR map on the current device: buf = cdf_m (h floats), cdf_c (w h), dens (w h); p_out (optional, device): the per-texel
 // probabilities; total = the map's total weight.
@@ -2203,7 +2273,7 @@ BatchBudget batch_budget(const fw_scene *sc, const fw_render_params *p, const Op
     // EXACT_PRODUCT: 160 more bytes per slot (ten attenuation records) where the scene has no chain state: half the default batch
     const bool exact_product = O.exact_product && (sc->chain_bits == 0 || O.no_chain);
     // light sampling: 92 more bytes per slot (fw::DShadow) — half the default batch as well (and so with environment sampling)
-    const bool ls = light_sampling(sc, p) || env_sampling(sc, p) || all_emitters(sc, p);
+    const bool ls = light_sampling(sc, p) || env_sampling(sc, p) || all_emitters(sc, p) || delta_lights(sc);
     const uint32_t budget = p->paths_per_batch ? p->paths_per_batch : default_paths_per_batch(O, arena_bytes) / (uint32_t)n_lanes / (exact_product || ls ? 2u : 1u);
     return BatchBudget{n_lanes, exact_product, budget};
 }
@@ -2253,6 +2323,9 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     std::unique_lock<std::mutex> ws_guard(ws->mu, std::defer_lock);
     if (!rd) ws_guard.lock();                                                        // (an adaptive round's caller holds it)
     { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }     // after fw_release_workspace, or a scene made before it
+    const bool dl = delta_lights(sc);
+    if (dl && (p->flags & (FW_FLAG_ENV_SAMPLING | FW_FLAG_ALL_EMITTERS)))
+        return fail(FW_ERR_UNSUPPORTED, "point, spot and directional lights do not combine with FW_FLAG_ENV_SAMPLING or FW_FLAG_ALL_EMITTERS");
     if (int erc = ensure_emitters(sc, p, ws)) return erc;     // (first: its FW_ERR_UNSUPPORTED comes before any launch)
     if (int erc = ensure_env_dist(sc, p, ws)) return erc;
     const Options O = options();
@@ -2279,7 +2352,8 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // pl = the entries replace §9g's lights (k_shade_pl, k_shade_pl_env)
     const bool pl = all_emitters(sc, p);
     const bool ls_lights = !pl && light_sampling(sc, p), es = env_sampling(sc, p);
-    const bool ls = ls_lights || es || pl;
+    // Delta lights (§9l): dl = the scene's are active (k_shade_dl; never with es or pl), beside §9g's emitters where ls_lights
+    const bool ls = ls_lights || es || pl || dl;
     const bool exact_product = bb.exact_product && !ls;
     const uint32_t budget = bb.budget;
     uint32_t spp_b = std::max<uint32_t>(1u, budget / n_pix);
@@ -2528,7 +2602,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // extend always runs beside the other batch's memory-bound shade (left alone, the two lanes drift INTO phase within three segments:
     // profiles/r05a_share_trace.txt).
     struct BatchCtx { fw::DFrame fr; fw::LaunchCfg cfg; fw::DPaths buf[2]; float2 *hits; float4 *srad; fw::DPark park; uint32_t *totals; uint32_t n_paths; int cur; int lane; hipStream_t ls;
-                      fw::DShadow sh; fw::DEnvDist ed; fw::DEmitters em; };
+                      fw::DShadow sh; fw::DEnvDist ed; fw::DEmitters em; fw::DDeltaLights dl; };
     // Measured (profiles/r05j_phase_lock.txt, three interleaved pairs): cornell 33.4-33.8 -> 32.2-32.4 ms — the lock holds the frame in the faster
     // of the two phases it otherwise lands in by chance (profiles/r05h_layout_pad.txt) —, where extend and shade last about as long as each
     // other.  Under use_bvh an extend lasts three shades and waiting for the other batch's costs: suzanne 62.7 -> 67.7, part2 @256 119.6 ->
@@ -2567,13 +2641,15 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         c.park = fw::DPark{(float4 *)L.park_a, (float2 *)L.park_b, (float4 *)L.park_m, q.cap + 64u, (uint32_t *)L.pcount,
                            park_meshes ? (uint32_t *)L.pcount + q.n_waves : nullptr};
         if (park_meshes) HIPCHK(hipMemsetAsync(c.park.ptotal, 0, (size_t)q.n_waves * 4, c.ls));
-        c.sh = fw::DShadow{}; c.ed = fw::DEnvDist{}; c.em = fw::DEmitters{};
+        c.sh = fw::DShadow{}; c.ed = fw::DEnvDist{}; c.em = fw::DEmitters{}; c.dl = fw::DDeltaLights{};
         if (ls) {
             // picking a light: the environment with p_env (1 alone, 1/2 beside emitters), each emitter with (1 - p_env) / n, each entry (§9i)
             // with (1 - p_env) p_i
-            const float p_env = es ? ((ls_lights || pl) ? 0.5f : 1.f) : 0.f;
+            // the delta lights as a group (§9l) with p_delta (1 alone, 1/2 beside emitters), each emitter then with (1 - p_delta) / n
+            const float p_env = es ? ((ls_lights || pl) ? 0.5f : 1.f) : (dl ? (ls_lights ? 0.5f : 1.f) : 0.f);
+            if (dl) c.dl = fw::DDeltaLights{(const float4 *)sc->dlights.p, sc->n_dlights, p_env};
             if (pl) c.em = emitters_of(sc, p_env);
-            c.sh.lt = ls_lights ? fw::DLights{(const uint32_t *)sc->lights.p, sc->n_lights, es ? (1.f - p_env) / (float)sc->n_lights : 1.f / (float)sc->n_lights}
+            c.sh.lt = ls_lights ? fw::DLights{(const uint32_t *)sc->lights.p, sc->n_lights, (es || dl) ? (1.f - p_env) / (float)sc->n_lights : 1.f / (float)sc->n_lights}
                                 : fw::DLights{(const uint32_t *)sc->lights.p, 0u, 0.f};
             if (es) c.ed = env_dist_of(sc->env_dist, sc->d.env, p_env);
             c.sh.ray_a = (float4 *)L.s_ray_a; c.sh.ray_b = (float2 *)L.s_ray_b; c.sh.state = (float4 *)L.s_state; c.sh.obj = (uint32_t *)L.s_obj;
@@ -2616,13 +2692,13 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         if (ls) {
             Workspace::Lane &L = ws->lanes[c.lane];
             c.sh.pb_in = (const float *)L.pb[c.cur]; c.sh.pb_out = (float *)L.pb[c.cur ^ 1];
-            timed(c, 2, [&] { fw::launch_shade_nee(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, es ? &c.ed : nullptr, pl ? &c.em : nullptr); });
+            timed(c, 2, [&] { fw::launch_shade_nee(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg, c.sh, es ? &c.ed : nullptr, pl ? &c.em : nullptr, dl ? &c.dl : nullptr); });
             if (seg < fw::MAX_SEGMENTS - 1) {     // segments 0-9 scatter (render.rs:21): their shadow rays through the ordinary walks, then the resolve
                 fw::LaunchCfg scfg = c.cfg; scfg.q.wcount = c.sh.wcount;
                 fw::DFrame sfr = c.fr; sfr.seed32 ^= fw::SHADOW_SEED; sfr.ex.mode = 0;
                 const fw::DPaths sp{c.sh.ray_a, c.sh.ray_b, c.sh.state};
                 timed(c, 1, [&] { fw::launch_extend(scfg, sc->d, sfr, sp, (float2 *)L.s_hits, seg + 1, use_bvh, c.park); });
-                timed(c, 2, [&] { fw::launch_shadow_resolve(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg, es, pl); });
+                timed(c, 2, [&] { fw::launch_shadow_resolve(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg, es, pl, dl); });
             }
         } else
         timed(c, 2, [&] { fw::launch_shade(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg); });
@@ -4035,6 +4111,18 @@ int fw_scene_update(fw_scene *scene, const fw_scene_desc *desc) {
     try { return update_scene_impl(scene, desc); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_scene_update"); }
+}
+
+int fw_scene_set_lights(fw_scene *scene, const fw_light *lights, uint32_t n) {
+    try { return set_lights_impl(scene, lights, n); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_scene_set_lights"); }
+}
+
+int fw_check_lights(const fw_light *lights, uint32_t n) {
+    try { return check_lights_impl(lights, n); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_check_lights"); }
 }
 
 void fw_release_workspace(int device) {

@@ -5,6 +5,10 @@ Tags: `object_type` (src/serde_compat.rs:22), `material` (src/material.rs:9), `t
 as a path under `value` (texture.rs:251-278).  Field names of the shapes that have no committed YAML in the
 reference (Rect3d, ConstantMedium, Checker/Metal/Dielectric/Isotropic) follow their struct definitions
 (rect3d.rs:10-14, volume.rs:11-15, material.rs:78-81,110-112,184-186).
+
+Beyond the reference: an optional top-level `lights:` list, each entry tagged `light`: `PointLight {position,
+intensity}`, `SpotLight {position, direction, intensity, inner_deg, outer_deg}`, `DirectionalLight {direction, irradiance}`.  A scene
+without lights is written without the key, so files of the reference's format load and dump as they did.
 """
 import os
 
@@ -118,6 +122,17 @@ def _environment(d):
     raise ValueError(f"unknown environment tag {k!r} (user-defined environments cannot cross to the GPU)")
 
 
+def _light(d):
+    k = d["light"]
+    if k == "PointLight":
+        return A.PointLight(_v3(d["position"]), _v3(d["intensity"]))
+    if k == "SpotLight":
+        return A.SpotLight(_v3(d["position"]), _v3(d["direction"]), _v3(d["intensity"]), float(d["inner_deg"]), float(d["outer_deg"]))
+    if k == "DirectionalLight":
+        return A.DirectionalLight(_v3(d["direction"]), _v3(d["irradiance"]))
+    raise ValueError(f"unknown light tag {k!r}")
+
+
 def scene_from_dict(y, base_dir="."):
     scene = A.Scene()
     shapes = [_shape(ro["obj"]) for ro in y.get("render_objects") or []]     # unsupported shapes surface first
@@ -132,6 +147,8 @@ def scene_from_dict(y, base_dir="."):
             o.flip_normals()
         scene.add_object(o)
     scene.set_environment(_environment(y["environment"]))
+    for l in y.get("lights") or []:
+        scene.add_light(_light(l))
     return scene
 
 
@@ -217,6 +234,22 @@ def _shape_d(s):
     raise TypeError(type(s))
 
 
+def _v3s(v):
+    # the shortest decimal that reads back as the same float32 (0.3, not 0.30000001192092896)
+    return {k: float(str(np.float32(x))) for k, x in zip("xyz", v)}
+
+
+def _light_d(l):
+    if isinstance(l, A.PointLight):
+        return {"light": "PointLight", "position": _v3s(l.position), "intensity": _v3s(l.intensity)}
+    if isinstance(l, A.SpotLight):
+        return {"light": "SpotLight", "position": _v3s(l.position), "direction": _v3s(l.direction), "intensity": _v3s(l.intensity),
+                "inner_deg": float(l.inner_deg), "outer_deg": float(l.outer_deg)}
+    if isinstance(l, A.DirectionalLight):
+        return {"light": "DirectionalLight", "direction": _v3s(l.direction), "irradiance": _v3s(l.irradiance)}
+    raise TypeError(type(l))
+
+
 def scene_to_dict(scene):
     e = scene.environment
     if isinstance(e, A.ColorEnv):
@@ -225,7 +258,7 @@ def scene_to_dict(scene):
         env = {"environment": "SkyEnv", "zenith_color": _v3d(e.zenith_color), "horizon_color": _v3d(e.horizon_color)}
     else:
         raise TypeError("only ColorEnv / SkyEnv have a YAML form in the reference")
-    return {
+    out = {
         "render_objects": [{"obj": _shape_d(ro.obj), "position": _v3d(ro._position),
                             "rotation": {"s": float(ro.rotation.s), "bv": {"xy": float(ro.rotation.xy), "xz": float(ro.rotation.xz),
                                                                            "yz": float(ro.rotation.yz)}},
@@ -233,6 +266,9 @@ def scene_to_dict(scene):
         "materials": [_material_d(m) for m in scene.materials],
         "environment": env,
     }
+    if getattr(scene, "lights", None):
+        out["lights"] = [_light_d(l) for l in scene.lights]
+    return out
 
 
 def save_scene(scene, path):

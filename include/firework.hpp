@@ -155,8 +155,23 @@ struct RenderObject {
     RenderObject flip_normals() && { flip = !flip; return std::move(*this); }
 };
 
+// Lights without area (not in the reference; fw_scene_set_lights): found by next-event estimation alone, they light the
+// Lambertian and Isotropic surfaces of every call on this header's Renderer and DeviceScene (render() of a lit scene goes through a resident
+// scene; only its multi-GPU devices() form, fw_render_scene_tiled on a bare description, has none).  intensity: radiant intensity per
+// steradian; irradiance: on a plane that faces the light; direction: any length.
+struct Light { fw_light l{}; };
+struct PointLight { static Light new_(Vec3 position, Vec3 intensity) { Light r; r.l.kind = FW_LIGHT_POINT; r.l.position = lower(position); r.l.intensity = lower(intensity); return r; } };
+struct SpotLight {   // full intensity within inner_deg of the axis, none beyond outer_deg, a smoothstep of the cosine between
+    static Light new_(Vec3 position, Vec3 direction, Vec3 intensity, float inner_deg, float outer_deg) {
+        Light r; r.l.kind = FW_LIGHT_SPOT; r.l.position = lower(position); r.l.direction = lower(direction); r.l.intensity = lower(intensity);
+        r.l.cos_inner = (float)std::cos((double)inner_deg * 3.14159265358979323846 / 180.0); r.l.cos_outer = (float)std::cos((double)outer_deg * 3.14159265358979323846 / 180.0);
+        return r; } };
+struct DirectionalLight { static Light new_(Vec3 direction, Vec3 irradiance) { Light r; r.l.kind = FW_LIGHT_DIRECTIONAL; r.l.direction = lower(direction); r.l.intensity = lower(irradiance); return r; } };
+
 struct Scene {
     std::vector<RenderObject> render_objects; std::vector<Material> materials; Environment environment = ColorEnv::new_({0, 0, 0});   // scene.rs:36
+    std::vector<fw_light> lights;
+    size_t add_light(const Light &l) { lights.push_back(l.l); return lights.size() - 1; }
     static Scene new_() { return {}; }
     RenderObjectIdx add_object(RenderObject o) { render_objects.push_back(std::move(o)); return render_objects.size() - 1; }
     MaterialIdx add_material(Material m) { materials.push_back(std::move(m)); return (MaterialIdx)materials.size() - 1; }
@@ -238,6 +253,16 @@ inline void init(int device = 0, uint64_t arena_bytes = 0) {
     if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
 }
 
+// fw_scene_create, then the scene's lights (fw_scene_set_lights); on failure nothing is left behind
+inline int create_resident(const Scene &scene, const fw_scene_desc *desc, int device, fw_scene **out) {
+    int rc = fw_scene_create(desc, device, out);
+    if (rc == FW_OK && !scene.lights.empty()) {
+        rc = fw_scene_set_lights(*out, scene.lights.data(), (uint32_t)scene.lights.size());
+        if (rc != FW_OK) { fw_scene_destroy(*out); *out = nullptr; }
+    }
+    return rc;
+}
+
 struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithreaded, no BVH, gamma 2.2
     size_t width_ = 1920, height_ = 1080, samples_ = 128; bool multithreaded_ = true, use_bvh_ = false; float gamma_ = 2.2f;
     CameraSettings camera_; uint64_t seed_ = 0; int device_ = 0; bool light_sampling_ = false, env_sampling_ = false, all_emitters_ = false;
@@ -283,6 +308,13 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
         Lowered low(scene);
         fw_render_params p = params();
         std::vector<Color> buffer(width_ * height_, Color{0, 0, 0});
+        if (!scene.lights.empty() && devices_.empty()) {     // fw_render_scene takes a bare description, which carries no lights: a resident scene does
+            fw_scene *sc = nullptr;
+            int lrc = create_resident(scene, &low.desc, device_, &sc);
+            if (lrc == FW_OK) { lrc = fw_render(sc, &p, reinterpret_cast<uint8_t *>(buffer.data()), nullptr, nullptr, stats); fw_scene_destroy(sc); }
+            if (lrc != FW_OK) throw std::runtime_error(std::string(fw_strerror(lrc)) + " | " + fw_last_error());
+            return buffer;
+        }
         int rc = devices_.empty()
                      ? fw_render_scene(&low.desc, &p, device_, reinterpret_cast<uint8_t *>(buffer.data()), nullptr, nullptr, stats)
                      : fw_render_scene_tiled(&low.desc, &p, devices_.data(), (int)devices_.size(), reinterpret_cast<uint8_t *>(buffer.data()), nullptr, nullptr, stats);
@@ -295,7 +327,7 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
     std::vector<Color> render_progressive(const Scene &scene, size_t passes, F on_pass, std::vector<float> *accum_io = nullptr) const {
         Lowered low(scene);
         fw_scene *sc = nullptr;
-        int rc = fw_scene_create(&low.desc, device_, &sc);
+        int rc = create_resident(scene, &low.desc, device_, &sc);
         if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
         std::vector<float> local; std::vector<float> &accum = accum_io ? *accum_io : local;
         accum.assign(width_ * height_ * 4, 0.f);
@@ -319,7 +351,7 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
                                        fw_stats *stats = nullptr) const {
         Lowered low(scene);
         fw_scene *sc = nullptr;
-        int rc = fw_scene_create(&low.desc, device_, &sc);
+        int rc = create_resident(scene, &low.desc, device_, &sc);
         if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
         fw_render_params p = params();
         std::vector<Color> buffer(width_ * height_, Color{0, 0, 0});
@@ -336,7 +368,7 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
     std::vector<std::vector<Color>> render_views(const Scene &scene, const std::vector<CameraSettings> &cameras, fw_stats *stats = nullptr) const {
         Lowered low(scene);
         fw_scene *sc = nullptr;
-        int rc = fw_scene_create(&low.desc, device_, &sc);
+        int rc = create_resident(scene, &low.desc, device_, &sc);
         if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
         fw_render_params p = params();
         std::vector<fw_camera_settings> cams;
@@ -358,7 +390,7 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
             throw std::runtime_error(std::string(fw_strerror(FW_ERR_UNSUPPORTED)) + " | W x H must be below 2^31");
         Lowered low(scene);
         fw_scene *sc = nullptr;
-        int rc = fw_scene_create(&low.desc, device_, &sc);
+        int rc = create_resident(scene, &low.desc, device_, &sc);
         if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
         const fw_render_params p = params();
         fw_render_rays_params rp{};
@@ -377,7 +409,7 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
                                        fw_stats *stats = nullptr) const {
         Lowered low(scene);
         fw_scene *sc = nullptr;
-        int rc = fw_scene_create(&low.desc, device_, &sc);
+        int rc = create_resident(scene, &low.desc, device_, &sc);
         if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
         fw_render_params p = params();
         const size_t n = width_ * height_;
@@ -405,7 +437,7 @@ class DeviceScene {
   public:
     explicit DeviceScene(const Scene &scene, int device = 0) {
         Lowered low(scene);                      // fw_scene_create copies what it needs
-        const int rc = fw_scene_create(&low.desc, device, &sc_);
+        const int rc = create_resident(scene, &low.desc, device, &sc_);
         if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
     }
     ~DeviceScene() { if (sc_) fw_scene_destroy(sc_); }

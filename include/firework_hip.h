@@ -306,6 +306,41 @@ void fw_scene_destroy(fw_scene *scene);
    for it in stream order.  An update must not run at the same time as another call on the same scene. */
 int fw_scene_update(fw_scene *scene, const fw_scene_desc *desc);
 
+/* ---- point, spot and directional lights (additive at ABI 8) ---------------------------------------------------------
+   Lights without area.  No path can hit one, so they are found by next-event estimation alone: where a resident scene has n > 0 of them
+   and some material is Lambertian or Isotropic, every Lambertian and Isotropic vertex of segments 0-9 picks one light and casts a shadow
+   ray at it.  No flag is needed.  The paths themselves (fw_stats.rays, rays_per_depth) are those of the frame without lights, and shadow
+   rays are accounted as under FW_FLAG_LIGHT_SAMPLING, whose frame layout such a frame takes.  The pick: the lights alone, each 1/n; with
+   FW_FLAG_LIGHT_SAMPLING in effect, the group of these lights 1/2 (uniform inside) and the emitters the other half.  Such a sample has
+   MIS weight 1 and adds beta x albedo x p_b(w) x L / p:
+     point        w = normalized(position - x),  L = intensity / d^2,  visible if the shadow ray meets nothing before the light
+     spot         as point, L = intensity s / d^2: c = -w . direction, t = clamp((c - cos_outer) / (cos_inner - cos_outer), 0, 1),
+                  s = t^2 (3 - 2t); with cos_inner == cos_outer, s = 1 where c >= cos_outer and 0 otherwise
+     directional  w = -direction,  L = intensity (an irradiance),  visible if the shadow ray meets nothing at all
+   Honoured by every frame of a resident scene: fw_render, fw_render_progressive, fw_render_views, fw_render_adaptive, fw_render_rays and
+   fw_render_model.  fw_render_aovs and fw_render_model_aovs ignore them (first-hit values carry no lighting).  The one-shot calls that
+   take a fw_scene_desc, fw_render_scene and fw_render_scene_tiled, have no lights: fw_scene_desc carries none.
+   Not supported together: FW_FLAG_ENV_SAMPLING or FW_FLAG_ALL_EMITTERS in a frame whose lights are active gives FW_ERR_UNSUPPORTED. */
+typedef enum { FW_LIGHT_POINT = 0, FW_LIGHT_SPOT = 1, FW_LIGHT_DIRECTIONAL = 2 } fw_light_kind;
+typedef struct fw_light {
+    int32_t kind;
+    fw_vec3 position;    /* point, spot */
+    fw_vec3 direction;   /* spot: the axis it shines along; directional: the direction the light TRAVELS; any non-zero length, normalised by the library */
+    fw_vec3 intensity;   /* point, spot: radiant intensity I (per steradian); directional: irradiance E on a plane facing it; each >= 0, finite */
+    float cos_inner, cos_outer;   /* spot: full intensity inside cos_inner, none outside cos_outer; -1 <= cos_outer <= cos_inner <= 1 */
+} fw_light;
+#define FW_MAX_LIGHTS 65536u
+/* Replaces the scene's lights with lights[0..n); n = 0 (lights may be NULL) removes them, and the scene then renders what it rendered before
+   it had any, bit for bit.  Everything is validated before device state is touched, and a rejected call leaves the scene as it was.
+   FW_ERR_BAD_ARG, with a detail string: a NULL scene, NULL lights with n > 0, n above FW_MAX_LIGHTS, an unknown kind, a non-finite field
+   (of any light, used by its kind or not), a negative intensity, a zero direction of a spot or directional light, spot cosines outside
+   -1 <= cos_outer <= cos_inner <= 1.  Fields a kind does not use (a directional light's position, a point light's direction and
+   cosines) are otherwise ignored.  The lights live in an allocation of the scene's own, uploaded as fw_scene_update uploads; fw_scene_update keeps
+   them.  Must not run at the same time as another call on the same scene. */
+int fw_scene_set_lights(fw_scene *scene, const fw_light *lights, uint32_t n);
+/* The same validation, on the host alone: no device is touched, and none is needed. */
+int fw_check_lights(const fw_light *lights, uint32_t n);
+
 /* The hot path: render.rs:123-161 on an uploaded scene.
    Any output pointer may be NULL.  Sizes are N*3 with N = n_pixels (or width*height),
    index order = pixel_ids order, row 0 = image top (util.rs:31-33):
