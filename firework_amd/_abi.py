@@ -20,7 +20,7 @@ FW_ERR_OOM = -10
 
 # kinds
 FW_TEX_CONSTANT, FW_TEX_CHECKER, FW_TEX_PERLIN, FW_TEX_TURBULENCE, FW_TEX_MARBLE, FW_TEX_IMAGE = range(6)
-FW_MAT_LAMBERTIAN, FW_MAT_METAL, FW_MAT_DIELECTRIC, FW_MAT_EMISSIVE, FW_MAT_ISOTROPIC = range(5)
+FW_MAT_LAMBERTIAN, FW_MAT_METAL, FW_MAT_DIELECTRIC, FW_MAT_EMISSIVE, FW_MAT_ISOTROPIC, FW_MAT_GGX = range(6)   # 5: GgxMat
 (FW_SHAPE_SPHERE, FW_SHAPE_XYRECT, FW_SHAPE_XZRECT, FW_SHAPE_YZRECT, FW_SHAPE_RECT3D,
  FW_SHAPE_TRIANGLE_MESH, FW_SHAPE_CONSTANT_MEDIUM, FW_SHAPE_CONE, FW_SHAPE_CYLINDER, FW_SHAPE_DISK) = range(10)
 FW_ENV_COLOR, FW_ENV_SKY, FW_ENV_HDR = range(3)
@@ -34,6 +34,7 @@ FW_ENV_SAMPLE_FLOATS = 6     # fw_selftest_env_sample
 FW_FLAG_ALL_EMITTERS = 16    # with FW_FLAG_LIGHT_SAMPLING: every emitting primitive, picked by power
 FW_EMITTER_RECORD_FLOATS = 5  # fw_selftest_emitters
 FW_EMITTER_SAMPLE_FLOATS = 9  # fw_selftest_emitter_sample
+FW_GGX_IN_FLOATS, FW_GGX_OUT_FLOATS = 15, 11  # fw_selftest_ggx
 FW_NO_HIT = 0xFFFFFFFF   # fw_hit.object of a miss
 FW_LIGHT_POINT, FW_LIGHT_SPOT, FW_LIGHT_DIRECTIONAL = range(3)   # fw_light_kind
 FW_MAX_LIGHTS = 65536

@@ -85,6 +85,8 @@ def load(preload=False, device=None):
     lib.fw_selftest_emitters.argtypes = [C.POINTER(A.fw_scene_desc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.fw_selftest_emitter_sample.restype = C.c_int
     lib.fw_selftest_emitter_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.fw_selftest_ggx.restype = C.c_int
+    lib.fw_selftest_ggx.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.fw_selftest_bvh_build.restype = C.c_int
     lib.fw_selftest_bvh_build.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     lib.fw_selftest_bvh_trees.restype = C.c_int
@@ -236,6 +238,18 @@ def selftest_emitter_sample(device_scene, x, n, seed=1):
     _check(lib, lib.fw_selftest_emitter_sample(device_scene.handle, xv.ctypes.data, int(n), int(seed) & 0xFFFFFFFF, out.ctypes.data))
     return dict(entry=out[:, 0].copy().view(np.uint32).astype(np.int64), p_pick=out[:, 1].astype(np.float64),
                 p_omega=out[:, 2].astype(np.float64), world=out[:, 3:6].astype(np.float64), obj_point=out[:, 6:9].astype(np.float64))
+
+
+def selftest_ggx(entries, device=0):
+    """fw_selftest_ggx: (n, 15) float32 entries (normal xyz, ray direction xyz, roughness, F0 rgb, xi1, xi2, omega xyz) through the device
+    functions a GgxMat vertex is shaded with.  -> dict of float32 arrays: wi (n, 3), atten (n, 3), alive (n,) bool,
+    fcos (n, 3), pb (n,)"""
+    lib = load()
+    e = np.ascontiguousarray(entries, np.float32)
+    assert e.ndim == 2 and e.shape[1] == A.FW_GGX_IN_FLOATS, e.shape
+    out = np.zeros((e.shape[0], A.FW_GGX_OUT_FLOATS), np.float32)
+    _check(lib, lib.fw_selftest_ggx(int(device), e.shape[0], e.ctypes.data, out.ctypes.data))
+    return dict(wi=out[:, 0:3].copy(), atten=out[:, 3:6].copy(), alive=out[:, 6] != 0, fcos=out[:, 7:10].copy(), pb=out[:, 10].copy())
 
 
 def selftest_env_dist(rgb, device=0):

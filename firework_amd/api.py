@@ -245,6 +245,23 @@ class MetalMat(Material):
 
 
 @dataclass
+class GgxMat(Material):
+    """An isotropic GGX microfacet conductor (FW_MAT_GGX): albedo = the normal-incidence reflectance F0, every component in
+    [0, 1]; roughness in [0.03, 1] (alpha = roughness^2).  Unlike MetalMat its lobe has a density, so point, spot and directional lights
+    and, under FW_FLAG_LIGHT_SAMPLING, sphere and rectangle emitters highlight it.  Scene.to_desc checks the ranges."""
+    albedo: np.ndarray
+    roughness: float
+
+    def __init__(self, albedo, roughness):
+        self.albedo = _v3(albedo)
+        self.roughness = float(roughness)
+
+    @staticmethod
+    def new(albedo, roughness):
+        return GgxMat(albedo, roughness)
+
+
+@dataclass
 class DielectricMat(Material):
     ref_idx: float
 
@@ -642,6 +659,15 @@ class SceneDesc:
                 fm.texture = add_tex(m.albedo)
             elif isinstance(m, MetalMat):
                 fm.kind = A.FW_MAT_METAL
+                fm.albedo = A.vec3(m.albedo)
+                fm.roughness = m.roughness
+            elif isinstance(m, GgxMat):
+                i = len(mats)          # (the library's checks and wording: fw_scene_create would refuse the same)
+                if not (np.float32(0.03) <= np.float32(m.roughness) <= np.float32(1.0)):
+                    raise ValueError(f"material {i}: GgxMat roughness must be in [0.03, 1]")
+                if not all(0.0 <= float(c) <= 1.0 for c in np.asarray(m.albedo, dtype=np.float32)):
+                    raise ValueError(f"material {i}: GgxMat albedo components must be in [0, 1]")
+                fm.kind = A.FW_MAT_GGX
                 fm.albedo = A.vec3(m.albedo)
                 fm.roughness = m.roughness
             elif isinstance(m, DielectricMat):

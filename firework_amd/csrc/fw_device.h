@@ -76,6 +76,7 @@ constexpr uint32_t NODE_LEAF = 1u, NODE_DOUBLE = 2u, NODE_MASK = 0x3fffffffu;
 //      are u = (0,1,0) in the .w lanes and v = (0,0,1) as constants.
 // ---- material: 2 x float4: (bits kind | MF_*, bits texture, roughness, ref_idx) (colour.rgb, -)
 //      colour = Metal albedo, or the ConstantTexture colour when MF_TEX_CONST (no texture fetch needed)
+//      GgxMat (kind 5): the roughness slot m0.z holds alpha = roughness * roughness (float32, computed on the host), colour = F0
 // ---- texture : 2 x float4: (bits kind, scale, bits depth, bits odd) then by kind:
 //        constant (color.rgb -) | checker (bits even - - -) | image (bits byte offset, bits w, bits h, -)
 
@@ -303,6 +304,7 @@ struct LaunchCfg {
     int wblas_fmt, wtlas_fmt;     // WIDE_NONE / WIDE_F32 / WIDE_Q8: the encoding of DScene.wblas / wtlas (FIREWORK_WIDE=0: none; =q8 / =f32 force one)
     uint32_t wblas_nodes, wtlas_nodes, wblas_depth, wtlas_depth;   // wide nodes; wide nodes on the longest root-to-leaf path
     uint32_t debug_wide_levels;   // A/B build, option DEBUG_WIDE_LEVELS: LDS stack levels of the wide walks instead of 3 * depth + 2 (the error word's test); 0: off
+    bool gx;              // the scene holds a GgxMat: the k_shade_gx kernels and k_shadow_resolve_gx
     bool tlas_refill;     // refilling walks: k_extend_tlas (no meshes) / k_extend_tlas_park + k_blas (meshes); FIREWORK_TLAS_REFILL=0: the chunked k_extend_bvh
 };
 constexpr size_t LDS_TREE_LIMIT = 160 * 1024;   // the whole LDS of a CU: one workgroup of the LDS-resident walks per CU
@@ -332,7 +334,9 @@ void launch_shade(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, 
 // for an environment ray)
 void launch_shade_nee(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
                       float4 *sample_rad, int segment, const DShadow &, const DEnvDist *ed, const DEmitters *em, const DDeltaLights *dl = nullptr);
-void launch_shadow_resolve(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment, bool env, bool pl, bool dl = false);
+// (sample_rad: the batch's radiance records, which the resolve of a scene with a GgxMat adds to for paths that ended at their vertex, §9m)
+void launch_shadow_resolve(const LaunchCfg &, const DScene &, const DShadow &, const float2 *hits, int segment, bool env, bool pl, bool dl = false,
+                           float4 *sample_rad = nullptr);
 // the table of env (w x h): scratch = 2 h + 1 doubles (row totals, the total); p_out (optional): the per-texel probabilities; *total = the total weight
 // (host memory, after a synchronisation of `stream`)
 int build_env_dist(hipStream_t stream, const DEnv &env, float *cdf_m, float *cdf_c, float *dens, float *p_out, double *scratch, double *total);
@@ -342,6 +346,8 @@ void launch_env_sample_test(hipStream_t stream, const DEnv &env, const DEnvDist 
 void launch_emitter_weights(hipStream_t stream, const DScene &sc, const uint4 *ent, uint32_t n, float *w);
 // n picks from the point x (fw_selftest_emitter_sample): per pick FW_EMITTER_SAMPLE_FLOATS floats
 void launch_emitter_sample_test(hipStream_t stream, const DScene &sc, const DEmitters &em, float x, float y, float z, uint32_t n, uint32_t seed32, float *out);
+// n entries of fw_selftest_ggx: FW_GGX_IN_FLOATS floats in, FW_GGX_OUT_FLOATS floats out per entry (k_ggx_test)
+void launch_ggx_test(hipStream_t stream, uint32_t n, const float *in, float *out);
 void launch_bounce(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, float4 *sample_rad, int segment,
                    bool use_bvh);
 void launch_queue_totals(const LaunchCfg &, uint32_t *totals, const uint32_t *ptotal);

@@ -154,7 +154,7 @@ struct Phase {
 // ------------------------------------------------------------------------------------------------
 // counter RNG: pcg4d(pixel, sample, dimension, seed32) -> 4 x u32; float = (u >> 8) * 2^-24
 // ------------------------------------------------------------------------------------------------
-enum : uint32_t { P_JITTER = 0, P_LENS = 1, P_SCATTER = 2, P_FRESNEL = 3, P_VOLUME = 4, P_LIGHT = 5 };   // 5: light sampling
+enum : uint32_t { P_JITTER = 0, P_LENS = 1, P_SCATTER = 2, P_FRESNEL = 3, P_VOLUME = 4, P_LIGHT = 5, P_GGX = 6 };   // 5: light sampling; 6: GgxMat's visible normal (§9m)
 
 struct RngKey { uint32_t pixel, sample, seed32; };
 
@@ -3169,6 +3169,8 @@ __device__ __forceinline__ V3 light_emit(const DScene &sc, const float4 *matp, c
     return texture_sample(texp, sc.images, __float_as_uint(m0.y), u, v, rot_fwd(o, p_obj) + obj_pos(o));
 }
 // k_shade_ls's per-path exchange with shade_path: the p_b of the ray being shaded (in) and of the ray it scatters (out), the shadow ray
+// (pending: no component is negative, at least one positive.  In the GX kernels of §9m the sign bit of pending.x is a flag — the path ended at
+//  this vertex — set by GgxMat vertices alone and cleared by the others)
 struct LsIO { float pb_in, pb_out; bool shadow; Ray sray; uint32_t sobj; V3 pending; };
 
 // ------------------------------------------------------------------------------------------------
@@ -3347,6 +3349,75 @@ __device__ __forceinline__ uint32_t delta_sample(const DDeltaLights &dl, uint32_
     L = fdiv(s, d2) * I;
     return SHADOW_NEAR;
 }
+// ------------------------------------------------------------------------------------------------
+// GgxMat (FW_MAT_GGX): an isotropic, two-sided GGX conductor.  Its lobe has a density, so its vertices take light samples.
+// Everything below works in the local frame around the shading normal n (z = n): a direction's cosine with n is its z.
+// ------------------------------------------------------------------------------------------------
+// the branchless basis of Duff et al. 2017 around the unit vector n
+__device__ __forceinline__ void ggx_basis(V3 n, V3 &t, V3 &b) {
+    const float sg = copysignf(1.f, n.z), a = fdiv(-1.f, sg + n.z), c = n.x * n.y * a;
+    t = mk(1.f + sg * n.x * n.x * a, sg * c, -sg * n.x);
+    b = mk(c, sg + n.y * n.y * a, -n.y);
+}
+struct GgxFrame { V3 t, b, n, wo; };            // wo: the unit direction back along the ray, local (wo.z >= 0)
+__device__ __forceinline__ GgxFrame ggx_frame(V3 normal, V3 ray_d) {
+    GgxFrame g;
+    const V3 wo = -normalized(ray_d);
+    g.n = dot(wo, normal) < 0.f ? -normal : normal;
+    ggx_basis(g.n, g.t, g.b);
+    g.wo = mk(dot(wo, g.t), dot(wo, g.b), dot(wo, g.n));
+    return g;
+}
+__device__ __forceinline__ V3 ggx_to_world(const GgxFrame &g, V3 w) { return w.x * g.t + w.y * g.b + w.z * g.n; }
+__device__ __forceinline__ V3 ggx_to_local(const GgxFrame &g, V3 w) { return mk(dot(w, g.t), dot(w, g.b), dot(w, g.n)); }
+// Smith's Lambda of the local direction w (w.z > 0): (-1 + sqrt(1 + alpha^2 tan^2)) / 2, tan^2 = (x^2 + y^2) / z^2
+__device__ __forceinline__ float ggx_lambda(V3 w, float alpha) {
+    const float a2t2 = fdiv(alpha * alpha * (w.x * w.x + w.y * w.y), w.z * w.z);
+    return 0.5f * (fsqrt(1.f + a2t2) - 1.f);
+}
+// D of the unit local half vector h, from its tangential and normal parts (no cancellation near h = n at small alpha)
+__device__ __forceinline__ float ggx_d(V3 h, float alpha) {
+    const float a2 = alpha * alpha, s = (h.x * h.x + h.y * h.y) + a2 * (h.z * h.z);
+    return fdiv(a2, PI_F * (s * s));
+}
+__device__ __forceinline__ V3 ggx_fresnel(V3 f0, float c) {                        // Schlick: F0 + (1 - F0)(1 - c)^5
+    const float m = 1.f - c, m2 = m * m, m5 = m2 * m2 * m;
+    return f0 + m5 * (mk(1.f, 1.f, 1.f) - f0);
+}
+// A direction from the visible normals (Heitz 2018), xi1 and xi2 uniform: wi = reflect(-wo, h), local.  False: wi lies below the surface
+// (the path ends).  atten = F G2 / G1(wo); pb = the density of wi, G1(wo) D(h) / (4 wo.z).
+__device__ __forceinline__ bool ggx_sample(V3 wo, float alpha, V3 f0, float xi1, float xi2, V3 &wi, V3 &atten, float &pb) {
+    const V3 vh = normalized(mk(alpha * wo.x, alpha * wo.y, wo.z));                    // the stretched view
+    const float l2 = vh.x * vh.x + vh.y * vh.y;
+    V3 t1 = mk(1.f, 0.f, 0.f);
+    if (l2 > 0.f) { const float il = fdiv(1.f, fsqrt(l2)); t1 = mk(-vh.y * il, vh.x * il, 0.f); }
+    const V3 t2 = cross(vh, t1);
+    const float r = fsqrt(xi1);
+    float sp, cp; sincosf(2.f * PI_F * xi2, &sp, &cp);
+    const float p1 = r * cp, s = 0.5f * (1.f + vh.z);
+    const float p2 = (1.f - s) * fsqrt(fmaxf(1.f - p1 * p1, 0.f)) + s * (r * sp);      // the projected disk, warped to the visible half
+    const V3 nh = p1 * t1 + p2 * t2 + fsqrt(fmaxf(1.f - p1 * p1 - p2 * p2, 0.f)) * vh;
+    const V3 h = normalized(mk(alpha * nh.x, alpha * nh.y, fmaxf(nh.z, 0.f)));         // unstretched
+    const float oh = dot(wo, h);
+    wi = 2.f * oh * h - wo;
+    atten = mk(0.f, 0.f, 0.f); pb = 0.f;
+    if (!(wi.z > 0.f) || !(wo.z > 0.f)) return false;
+    const float lo = ggx_lambda(wo, alpha), li = ggx_lambda(wi, alpha);
+    atten = fdiv(1.f + lo, 1.f + lo + li) * ggx_fresnel(f0, oh);
+    pb = fdiv(fdiv(ggx_d(h, alpha), 4.f * wo.z), 1.f + lo);                           // (ggx_eval's form)
+    return true;
+}
+// The lobe towards the local unit direction wi: fcos = f cos(theta_i) = F D G2 / (4 wo.z), and the density ggx_sample draws wi with.
+// Both 0 where either direction lies in or below the surface.
+__device__ __forceinline__ float ggx_eval(V3 wo, V3 wi, float alpha, V3 f0, V3 &fcos) {
+    fcos = mk(0.f, 0.f, 0.f);
+    if (!(wi.z > 0.f) || !(wo.z > 0.f)) return 0.f;
+    const V3 h = normalized(wo + wi);
+    const float lo = ggx_lambda(wo, alpha), li = ggx_lambda(wi, alpha);
+    const float d4 = fdiv(ggx_d(h, alpha), 4.f * wo.z);
+    fcos = fdiv(d4, 1.f + lo + li) * ggx_fresnel(f0, dot(wo, h));
+    return fdiv(d4, 1.f + lo);
+}
 // "Expensive" shading (k_shade's deferred list): what a few lanes of a chunk do while the others wait — a texture that is not a
 // constant (three sinf for a checker, 5-10 octaves of Perlin noise, an image lookup behind atan2f + asinf), the Fresnel branch
 // of a dielectric (normalise, refract, powf), a miss into an HDR map (atan2f + asinf + a gather from 100 MB).
@@ -3364,7 +3435,9 @@ __device__ __forceinline__ bool expensive_shading(const DScene &sc, const float4
 // PL (with LS): k_shade_pl / k_shade_pl_env: the emitters are the entries of *em (every emitting primitive, picked by power).
 // DL (with LS, without ENV and PL): k_shade_dl: the point, spot and directional lights of *dl are sampled too, as a group picked
 // with probability dl->p_delta beside §9g's emitters (alone where sh->lt.n = 0).
-template <bool CHEAP_ONLY = false, bool CHAIN = false, bool LS = false, bool ENV = false, bool PL = false, bool DL = false>
+// GX (without CHAIN): the k_shade_gx kernels, which alone a scene with a GgxMat launches: material kind 5, and with LS (without ENV
+// and PL) its light sample and p_b.  Every line of it is behind GX: the other kernels' code is as it was.
+template <bool CHEAP_ONLY = false, bool CHAIN = false, bool LS = false, bool ENV = false, bool PL = false, bool DL = false, bool GX = false>
 __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, const float4 *objp, const float4 *matp,
                                            const float4 *texp, const Ray &r, V3 beta, uint32_t chain, uint32_t path_id, float t_hit,
                                            uint32_t hit_code, int segment, float4 *__restrict__ sample_rad, Ray &nr, V3 &nbeta, uint32_t &nchain PH_ARG,
@@ -3446,6 +3519,14 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
             if (mkind == 0) PH_COUNT(8); else if (mkind == 1) PH_COUNT(9); else if (mkind == 2) PH_COUNT(10); else PH_COUNT(12);
             RngKey key = pre_key ? *pre_key : key_of(f, path_id);
             V3 atten = texc;
+            GgxFrame gf{}; float gx_pb = 0.f;
+            if (GX && mkind == 5u) {                                           // GgxMat: m0.z = alpha, texc = F0
+                gf = ggx_frame(h.normal, r.d);
+                const uint4 gu = draw(key, P_GGX, segment, 0);
+                V3 wi;
+                alive = ggx_sample(gf.wo, m0.z, texc, u2f(gu.x), u2f(gu.y), wi, atten, gx_pb);
+                nr = Ray{h.point, ggx_to_world(gf, wi)};
+            } else
             switch (mkind) {
             case 0: {                                                          // Lambertian material.rs:64-75
                 V3 target = h.point + h.normal + random_in_unit_sphere(key, segment PH_PASS);
@@ -3526,6 +3607,41 @@ __device__ __forceinline__ bool shade_path(const DScene &sc, const DFrame &f, co
                         const float r_ = fdiv(pb, pl);                             // f cos / p_l * p_l^2 / (p_l^2 + p_b^2) = albedo * r / (1 + r^2)
                         const V3 c = (beta * atten) * light_emit<CHEAP_ONLY>(sc, matp, texp, lo, p_obj) * fdiv(r_, 1.f + r_ * r_);
                         if (c.x > 0.f || c.y > 0.f || c.z > 0.f) { ls->shadow = true; ls->sray = Ray{h.point, d}; ls->sobj = lobj; ls->pending = c; }
+                    }
+                }
+            }
+            // (k_shadow_resolve_gx reads the sign bit of a pending radiance's .x as "the path has ended", which only a GgxMat vertex may set:
+            //  a Lambertian or Isotropic vertex of a GX kernel clears it, so that a product of -0.0 — a texture colour may be — cannot set it)
+            if (GX && LS && (mkind == 0 || mkind == 4)) ls->pending.x = fabsf(ls->pending.x);
+            // GgxMat's light sample: the delta lights (weight 1) or §9g's emitters (power heuristic), f cos in the place of albedo p_b.  Under
+            // ENV / PL the vertex is what a Metal vertex is: no light sample, pb_out = 0 and weight 1 for whatever the path meets next
+            // A vertex whose own sample went below the surface ends the path and deposits here, before its shadow ray is walked: the pending
+            // radiance carries the sign bit in .x, and k_shadow_resolve_gx adds it to the path's radiance record instead of its nee record
+            if (GX && LS && !ENV && !PL && mkind == 5u) {
+                ls->pb_out = gx_pb;
+                const uint4 lu = draw(key, P_LIGHT, segment, 0);
+                V3 d = mk(0.f, 0.f, 0.f), w = d, Le = d; float inv_p = 0.f, pl = 0.f; uint32_t code = MISS;
+                const bool delta = DL && (sh->lt.n == 0u || u2f(lu.x) < dl->p_delta);
+                if (delta) {
+                    const uint32_t li = min((uint32_t)(fdiv(u2f(lu.x), dl->p_delta) * (float)dl->n), dl->n - 1u);
+                    code = delta_sample(*dl, li, h.point, d, w, Le);
+                    inv_p = fdiv(1.f, fdiv(dl->p_delta, (float)dl->n));       // 1 / p, p = p_delta / M
+                } else {
+                    const float xi = DL ? fdiv(u2f(lu.x) - dl->p_delta, 1.f - dl->p_delta) : u2f(lu.x);
+                    const uint32_t li = min((uint32_t)(xi * (float)sh->lt.n), sh->lt.n - 1u);
+                    code = sh->lt.obj[li];
+                    const Obj lo = load_obj(objp, code);
+                    V3 p_obj;
+                    pl = sh->lt.p_pick * light_sample(lo, h.point, u2f(lu.y), u2f(lu.z), d, p_obj);
+                    if (pl > 0.f) { w = normalized(d); Le = light_emit<CHEAP_ONLY>(sc, matp, texp, lo, p_obj); }
+                }
+                if (Le.x > 0.f || Le.y > 0.f || Le.z > 0.f) {
+                    V3 fc;
+                    const float pb = ggx_eval(gf.wo, ggx_to_local(gf, w), m0.z, texc, fc);
+                    if (pb > 0.f) {
+                        if (!delta) { const float r_ = fdiv(pb, pl); inv_p = fdiv(1.f, pl * (1.f + r_ * r_)); }   // 1 / p_l x p_l^2 / (p_l^2 + p_b^2)
+                        const V3 c = (beta * fc) * Le * inv_p;
+                        if (c.x > 0.f || c.y > 0.f || c.z > 0.f) { ls->shadow = true; ls->sray = Ray{h.point, d}; ls->sobj = code; ls->pending = mk(alive ? c.x : -c.x, c.y, c.z); }
                     }
                 }
             }
@@ -3745,7 +3861,7 @@ __attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
 __global__ __launch_bounds__(WB) void k_shade_ls(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
                                                     float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                     uint32_t n_mat, uint32_t n_tex, DShadow sh) {
-    constexpr bool ENV = false, PL = false, DL = false;
+    constexpr bool ENV = false, PL = false, DL = false, GX = false;
     const DEnvDist *const edp = nullptr; const DEmitters *const emp = nullptr; const DDeltaLights *const dlp = nullptr;
 #include "fw_shade_nee.inc"
 }
@@ -3758,7 +3874,7 @@ __global__ __launch_bounds__(WB) void k_shade_env(DScene sc, DFrame f, DPaths in
                                                      float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                      uint32_t n_mat, uint32_t n_tex, DShadow sh, DEnvDist ed) {
     constexpr int MODE = 0;                  // an HDR map is an expensive case: the scene never takes mode 1
-    constexpr bool ENV = true, PL = false, DL = false;
+    constexpr bool ENV = true, PL = false, DL = false, GX = false;
     const DEnvDist *const edp = &ed; const DEmitters *const emp = nullptr; const DDeltaLights *const dlp = nullptr;
 #include "fw_shade_nee.inc"
 }
@@ -3796,7 +3912,7 @@ __attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
 __global__ __launch_bounds__(WB) void k_shade_pl(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
                                                     float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                     uint32_t n_mat, uint32_t n_tex, DShadow sh, DEmitters em) {
-    constexpr bool ENV = false, PL = true, DL = false;
+    constexpr bool ENV = false, PL = true, DL = false, GX = false;
     const DEnvDist *const edp = nullptr; const DEmitters *const emp = &em; const DDeltaLights *const dlp = nullptr;
 #include "fw_shade_nee.inc"
 }
@@ -3806,7 +3922,7 @@ __global__ __launch_bounds__(WB) void k_shade_pl_env(DScene sc, DFrame f, DPaths
                                                      float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                      uint32_t n_mat, uint32_t n_tex, DShadow sh, DEnvDist ed, DEmitters em) {
     constexpr int MODE = 0;                  // (as k_shade_env)
-    constexpr bool ENV = true, PL = true, DL = false;
+    constexpr bool ENV = true, PL = true, DL = false, GX = false;
     const DEnvDist *const edp = &ed; const DEmitters *const emp = &em; const DDeltaLights *const dlp = nullptr;
 #include "fw_shade_nee.inc"
 }
@@ -3831,7 +3947,7 @@ __attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
 __global__ __launch_bounds__(WB) void k_shade_dl(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
                                                     float4 *__restrict__ sample_rad, DQueue q, int segment,
                                                     uint32_t n_mat, uint32_t n_tex, DShadow sh, DDeltaLights dl) {
-    constexpr bool ENV = false, PL = false, DL = true;
+    constexpr bool ENV = false, PL = false, DL = true, GX = false;
     const DEnvDist *const edp = nullptr; const DEmitters *const emp = nullptr; const DDeltaLights *const dlp = &dl;
 #include "fw_shade_nee.inc"
 }
@@ -3852,6 +3968,105 @@ __global__ __launch_bounds__(WB) void k_shadow_resolve_dl(DShadow sh, const floa
         float4 &e = sh.nee[__float_as_uint(p.w)];
         e = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, 0.f);
     }
+}
+// GgxMat: the shade kernels of a scene that holds a material of kind 5, and of no other scene: shade_path's GX.  k_shade_gx
+// is k_shade's loop without the chain state (GgxMat's attenuation is no constant of the material) and without the list (modes 0 and 1);
+// k_shade_gx_nee is the sixth kernel around fw_shade_nee.inc, one template over ENV / PL / DL with all three tables as arguments (zeroed
+// where unused) instead of five kernels: none of them exists yet, so none has code to keep.
+template <int LDS_TAB, int MODE>
+__attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
+__global__ __launch_bounds__(WB) void k_shade_gx(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
+                                                    float4 *__restrict__ sample_rad, DQueue q, int segment,
+                                                    uint32_t n_mat, uint32_t n_tex) {
+    static_assert(MODE == 0 || MODE == 1, "in line only");
+    constexpr bool CHAIN = false;
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+#include "fw_shade_tables.inc"
+    if (w >= q.n_waves) return;
+    const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
+    const uint32_t base = w * q.cap;
+    uint32_t out_n = 0;                                                  // survivors written so far (wave-uniform)
+    PH_DECL;
+    auto load_hit = [&](uint32_t idx) { return f.hit4 ? make_float2(0.f, __uint_as_float(reinterpret_cast<const uint32_t *>(hits)[idx])) : qld(&hits[idx]); };
+    float4 ra_n = make_float4(0, 0, 0, 0), st_n = ra_n; float2 rb_n = make_float2(0, 0), hr_n = rb_n;
+    auto fetch = [&](uint32_t i) { ra_n = qld(&in.ray_a[i]); rb_n = load_ray_b(in, i, f, segment); st_n = load_state(in, i, segment); hr_n = load_hit(i); };
+    if (lane < n) fetch(base + lane);
+    // (The third copy of this fetch / shade / compact loop, after k_shade's and fw_shade_nee.inc's: sharing it would risk the shipped kernels'
+    //  code.  A fix to the compaction or to the exact-flag logic below belongs in all three.)
+    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
+        const uint32_t j = c0 + lane, i = base + j;
+        float4 ra = ra_n, st = st_n; float2 rb = rb_n, hr = hr_n;
+        if (j + 64u < n) fetch(i + 64u);
+        bool alive = false;
+        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
+        if (j < n) {
+            path_id = __float_as_uint(st.w);
+            alive = shade_path<MODE != 0, CHAIN, false, false, false, false, true>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id, hr.x,
+                                                                                   __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS);
+        }
+        const unsigned long long mask = __ballot(alive);                 // k_shade's compaction
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (alive) {
+            const uint32_t dst = base + out_n + rank;
+            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
+            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
+            qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
+        }
+        if (f.ex.mode) flag_exact(f.ex, alive && needs_exact(f.ex, nr.o.x, nr.o.y, nr.o.z, nr.d.x, nr.d.y, nr.d.z), base + out_n + rank, segment + 1);
+        out_n += (uint32_t)__popcll(mask);
+    }
+    if (lane == 0) q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n;
+}
+template <int LDS_TAB, int MODE, bool ENV, bool PL, bool DL>
+__attribute__((amdgpu_waves_per_eu(FW_SHADE_WAVES, 8)))
+__global__ __launch_bounds__(WB) void k_shade_gx_nee(DScene sc, DFrame f, DPaths in, DPaths out, const float2 *__restrict__ hits,
+                                                        float4 *__restrict__ sample_rad, DQueue q, int segment,
+                                                        uint32_t n_mat, uint32_t n_tex, DShadow sh, DEnvDist ed, DEmitters em, DDeltaLights dl) {
+    static_assert(!(DL && (ENV || PL)) && !(ENV && MODE != 0), "the combinations of k_shade_ls, _env, _pl, _pl_env and _dl");
+    constexpr bool GX = true;
+    const DEnvDist *const edp = ENV ? &ed : nullptr; const DEmitters *const emp = PL ? &em : nullptr; const DDeltaLights *const dlp = DL ? &dl : nullptr;
+#include "fw_shade_nee.inc"
+}
+// The resolve of k_shade_gx_nee without ENV and PL: k_shadow_resolve_dl's rule (which is k_shadow_resolve's where no delta light is sampled),
+// and a pending radiance with the sign bit in .x belongs to a path that ended at its vertex: it has deposited already (a light-sampling frame
+// deposits every path), and the sample joins its radiance record.  One shadow ray per path and segment: no atomics.
+// (This kernel and k_ggx_test are templates, and every GX kernel is launched from the end of this file, for one reason: the compiler emits
+//  template instantiations after the plain kernels, in the order of their first use, so all of §9m's kernels come after every kernel that
+//  existed before them, which keep their places in the code object.)
+template <int UNUSED = 0>
+__global__ __launch_bounds__(WB) void k_shadow_resolve_gx(DShadow sh, const float2 *__restrict__ hits, DQueue q, int segment, uint32_t prim_bits,
+                                                            float4 *__restrict__ sample_rad) {
+    const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
+    if (w >= q.n_waves) return;
+    const uint32_t n = sh.wcount[(size_t)(segment + 1) * q.n_waves + w], base = w * q.cap;
+    for (uint32_t j = lane; j < n; j += 64u) {
+        const uint32_t i = base + j, want = sh.obj[i];
+        const float2 hr = hits[i];
+        const uint32_t code = __float_as_uint(hr.y);
+        const bool visible = code == MISS ? want >= SHADOW_NEAR : (want == SHADOW_NEAR ? hr.x >= 1.f : (code >> prim_bits) == want);
+        if (!visible) continue;
+        const float4 p = sh.state[i];
+        float4 &e = (__float_as_uint(p.x) >> 31) ? sample_rad[__float_as_uint(p.w)] : sh.nee[__float_as_uint(p.w)];
+        e = make_float4(e.x + fabsf(p.x), e.y + p.y, e.z + p.z, e.w);
+    }
+}
+// fw_selftest_ggx: entry i = (normal xyz, ray direction xyz, roughness, F0 rgb, xi1, xi2, omega xyz) through the functions shade_path calls
+// at a GgxMat vertex -> (omega_i xyz in world space, attenuation rgb, alive, f cos(omega) rgb, p_b(omega))
+template <int UNUSED = 0>
+__global__ __launch_bounds__(WB) void k_ggx_test(uint32_t n, const float *__restrict__ in, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * WB + threadIdx.x;
+    if (i >= n) return;
+    const float *x = in + (size_t)i * FW_GGX_IN_FLOATS;
+    const float alpha = x[6] * x[6];
+    const V3 f0 = mk(x[7], x[8], x[9]);
+    const GgxFrame gf = ggx_frame(mk(x[0], x[1], x[2]), mk(x[3], x[4], x[5]));
+    V3 wi, atten, fc; float pb_s;
+    const bool alive = ggx_sample(gf.wo, alpha, f0, x[10], x[11], wi, atten, pb_s);
+    const V3 d = ggx_to_world(gf, wi);
+    const float pb = ggx_eval(gf.wo, ggx_to_local(gf, normalized(mk(x[12], x[13], x[14]))), alpha, f0, fc);
+    float *o = out + (size_t)i * FW_GGX_OUT_FLOATS;
+    o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = atten.x; o[4] = atten.y; o[5] = atten.z; o[6] = alive ? 1.f : 0.f;
+    o[7] = fc.x; o[8] = fc.y; o[9] = fc.z; o[10] = pb;
 }
 // The entries' weights, once per scene: ent[i].z holds the weight the host computed, or for a triangle (ent[i].w = 5) the
 // object's power, multiplied here by the triangle's object-space area |(p1 - p0) x (p2 - p0)| / 2 from the resident sc.tri.
@@ -4657,6 +4872,11 @@ void launch_extend_exact(const LaunchCfg &c, const DScene &sc, const DFrame &f, 
 // only (the two dependent fetches behind the object record: part2 k_shade 6.7 -> 6.55 ms; a leaner per-kind object fetch on top — 3 loads
 // instead of 6 for an unrotated sphere — did not pay: 6.8 ms) | 0 none
 struct ShadeTables { int lt; size_t lds; };
+// (§9m's launches, defined at the end of this file: see k_shadow_resolve_gx)
+static void launch_shade_gx(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits, float4 *sample_rad, int segment, const ShadeTables &t);
+static void launch_shade_gx_nee(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits, float4 *sample_rad, int segment,
+                                const DShadow &sh, const DEnvDist *ed, const DEmitters *em, const DDeltaLights *dl, const ShadeTables &t);
+static void launch_shadow_resolve_gx(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment, float4 *sample_rad);
 static ShadeTables shade_tables(const LaunchCfg &c, const DScene &sc) {
     const size_t tab_mt = (2 * (size_t)c.n_mat + 2 * (size_t)c.n_tex) * sizeof(float4), tab = (size_t)sc.n_objects * OBJ_Q * sizeof(float4) + tab_mt;
     if (c.lds_tables && tab <= LDS_TABLE_LIMIT) return {1, tab};
@@ -4666,6 +4886,7 @@ static ShadeTables shade_tables(const LaunchCfg &c, const DScene &sc) {
 void launch_shade(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits,
                   float4 *sample_rad, int segment) {
     const ShadeTables t = shade_tables(c, sc);
+    if (c.gx) { launch_shade_gx(c, sc, f, in, out, hits, sample_rad, segment, t); return; }      // a scene with a GgxMat
     // shading mode (k_shade): 0 everything in line | 1 the scene has nothing expensive | 2 expensive paths through the list
     const int mode = c.shade_mode;
 #define FW_SHADE(L, M, C) hipLaunchKernelGGL((k_shade<L, M, C>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex)
@@ -4687,6 +4908,7 @@ void launch_shade_nee(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPa
                       float4 *sample_rad, int segment, const DShadow &sh, const DEnvDist *ed, const DEmitters *em, const DDeltaLights *dl) {
     const ShadeTables t = shade_tables(c, sc);
     const bool m1 = c.shade_mode == 1;
+    if (c.gx) { launch_shade_gx_nee(c, sc, f, in, out, hits, sample_rad, segment, sh, ed, em, dl, t); return; }      // a scene with a GgxMat
 #define FW_NEE(K, ...) hipLaunchKernelGGL(K, wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, __VA_ARGS__)
 #define FW_NEE_L(L) do { \
         if (ed && em) FW_NEE(k_shade_pl_env<L>, sh, *ed, *em); \
@@ -4700,7 +4922,9 @@ void launch_shade_nee(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPa
 #undef FW_NEE
 }
 // One resolve kernel per visibility rule (see the three kernels): env / pl as launch_shade_nee's ed / em of the segment's shade
-void launch_shadow_resolve(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment, bool env, bool pl, bool dl) {
+void launch_shadow_resolve(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment, bool env, bool pl, bool dl, float4 *sample_rad) {
+    // (a scene with a GgxMat, §9m: only without env and pl do its vertices queue shadow rays, and those may belong to paths that have ended)
+    if (c.gx && !env && !pl) { launch_shadow_resolve_gx(c, sc, sh, hits, segment, sample_rad); return; }
     if (dl) hipLaunchKernelGGL(k_shadow_resolve_dl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
     else if (pl) hipLaunchKernelGGL(k_shadow_resolve_pl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment);
     else if (env) hipLaunchKernelGGL(k_shadow_resolve_env, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
@@ -4856,7 +5080,7 @@ __global__ __launch_bounds__(BLOCK) void k_aov_accumulate(DScene sc, DFrame f, D
         const float4 m0 = sc.mat[2 * h.material], m1 = sc.mat[2 * h.material + 1];
         const uint32_t mkind = __float_as_uint(m0.x) & 0xffu, mtex = __float_as_uint(m0.y);
         V3 alb;
-        if (mkind == 1u) alb = mk(m1.x, m1.y, m1.z);                                     // Metal: its albedo
+        if (mkind == 1u || mkind == 5u) alb = mk(m1.x, m1.y, m1.z);                      // Metal: its albedo; GgxMat: F0
         else if (mkind == 2u) alb = mk(1.f, 1.f, 1.f);                                   // Dielectric
         else {
             alb = texture_sample(sc.tex, sc.images, mtex, h.u, h.v, h.point);          // Lambertian, Isotropic, Emissive
@@ -5042,6 +5266,41 @@ void launch_denoise(hipStream_t stream, int n_cus, uint32_t W, uint32_t H, uint3
         ev = src;
     }
     hipLaunchKernelGGL(k_dn_final, dim3(flat_blocks(n, n_cus, 8)), dim3(BLOCK), 0, stream, n, L, color, aov, ev, gamma, rgb8, gamma_rgb, linear_rgb);
+}
+
+// ---- GgxMat: the launches of its kernels, last in the file (see k_shadow_resolve_gx) ----------------------------------------
+// k_shade_gx, modes 0 and 1 (the host gives such a frame no chain state and no list)
+static void launch_shade_gx(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits, float4 *sample_rad, int segment, const ShadeTables &t) {
+#define FW_SHADE_GX(L) do { if (c.shade_mode == 1) hipLaunchKernelGGL((k_shade_gx<L, 1>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex); \
+    else hipLaunchKernelGGL((k_shade_gx<L, 0>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex); } while (0)
+    if (t.lt == 1) FW_SHADE_GX(1); else if (t.lt == 2) FW_SHADE_GX(2); else FW_SHADE_GX(0);
+#undef FW_SHADE_GX
+}
+// k_shade_gx_nee over the five combinations of launch_shade_nee
+static void launch_shade_gx_nee(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits, float4 *sample_rad, int segment,
+                                const DShadow &sh, const DEnvDist *ed, const DEmitters *em, const DDeltaLights *dl, const ShadeTables &t) {
+    const bool m1 = c.shade_mode == 1;
+    const DEnvDist e0{}; const DEmitters p0{}; const DDeltaLights d0{};
+#define FW_GX(L, M, E, P, D) hipLaunchKernelGGL((k_shade_gx_nee<L, M, E, P, D>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, \
+                                            c.n_mat, c.n_tex, sh, ed ? *ed : e0, em ? *em : p0, dl ? *dl : d0)
+#define FW_GX_M(L, P, D) do { if (m1) FW_GX(L, 1, false, P, D); else FW_GX(L, 0, false, P, D); } while (0)
+#define FW_GX_L(L) do { \
+    if (ed && em) FW_GX(L, 0, true, true, false); \
+    else if (ed) FW_GX(L, 0, true, false, false); \
+    else if (em) FW_GX_M(L, true, false); \
+    else if (!dl) FW_GX_M(L, false, false); \
+    else FW_GX_M(L, false, true); \
+    } while (0)
+    if (t.lt == 1) FW_GX_L(1); else if (t.lt == 2) FW_GX_L(2); else FW_GX_L(0);
+#undef FW_GX_L
+#undef FW_GX_M
+#undef FW_GX
+}
+static void launch_shadow_resolve_gx(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment, float4 *sample_rad) {
+    hipLaunchKernelGGL(k_shadow_resolve_gx<0>, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits, sample_rad);
+}
+void launch_ggx_test(hipStream_t stream, uint32_t n, const float *in, float *out) {
+    hipLaunchKernelGGL(k_ggx_test<0>, dim3((n + WB - 1) / WB), dim3(WB), 0, stream, n, in, out);
 }
 
 } // namespace fw

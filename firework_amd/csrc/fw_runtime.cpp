@@ -973,7 +973,8 @@ struct fw_scene {
     double ms_objects = 0, ms_objects_dev = 0;   // the last object-level build: host wall time, device tree builds (FIREWORK_TRACE)
     DevBuf lights;                // the sampled lights' object indices (fw::DLights.obj; FW_FLAG_LIGHT_SAMPLING)
     uint32_t n_lights = 0;
-    bool ls_vertices = false;     // some material is Lambertian or Isotropic: a vertex that samples lights can occur
+    bool ls_vertices = false;     // some material is Lambertian, Isotropic or Ggx: a vertex that samples lights can occur
+    bool has_ggx = false;         // some material is a GgxMat: the frame launches the k_shade_gx kernels
     // the HDR map's sampling table (fw::DEnvDist: cdf_m, cdf_c, dens; FW_FLAG_ENV_SAMPLING), built on the device by the first
     // render that needs it and kept for the scene's life (fw_scene_update never changes the environment)
     DevBuf env_dist;
@@ -1588,7 +1589,11 @@ static int upload_lights(fw_scene *sc, const fw_scene_desc *d) {
     if (int rc = sc->lights.upload(objs.data(), objs.size() * 4)) return rc;
     sc->n_lights = (uint32_t)L.size();
     sc->ls_vertices = false;
-    for (uint32_t m = 0; m < d->n_materials; m++) sc->ls_vertices = sc->ls_vertices || d->materials[m].kind == FW_MAT_LAMBERTIAN || d->materials[m].kind == FW_MAT_ISOTROPIC;
+    sc->has_ggx = false;
+    for (uint32_t m = 0; m < d->n_materials; m++) {
+        sc->has_ggx = sc->has_ggx || d->materials[m].kind == FW_MAT_GGX;
+        sc->ls_vertices = sc->ls_vertices || d->materials[m].kind == FW_MAT_LAMBERTIAN || d->materials[m].kind == FW_MAT_ISOTROPIC || d->materials[m].kind == FW_MAT_GGX;
+    }
     return FW_OK;
 }
 
@@ -1694,7 +1699,12 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out, con
     for (uint32_t i = 0; i < desc->n_materials; i++) {
         const fw_material &m = desc->materials[i];
         float *q = &mats[(size_t)i * 8];
-        if (m.kind < FW_MAT_LAMBERTIAN || m.kind > FW_MAT_ISOTROPIC) return fail(FW_ERR_BAD_ARG, "unknown material kind");
+        if (m.kind < FW_MAT_LAMBERTIAN || m.kind > FW_MAT_GGX) return fail(FW_ERR_BAD_ARG, "unknown material kind");
+        if (m.kind == FW_MAT_GGX) {       // (negated comparisons: a NaN is out of range)
+            if (!(m.roughness >= 0.03f && m.roughness <= 1.f)) return fail(FW_ERR_BAD_ARG, "material " + std::to_string(i) + ": GgxMat roughness must be in [0.03, 1]");
+            if (!(m.albedo.x >= 0.f && m.albedo.x <= 1.f && m.albedo.y >= 0.f && m.albedo.y <= 1.f && m.albedo.z >= 0.f && m.albedo.z <= 1.f))
+                return fail(FW_ERR_BAD_ARG, "material " + std::to_string(i) + ": GgxMat albedo components must be in [0, 1]");
+        }
         bool needs_tex = m.kind == FW_MAT_LAMBERTIAN || m.kind == FW_MAT_EMISSIVE || m.kind == FW_MAT_ISOTROPIC;
         if (needs_tex && (m.texture < 0 || (uint32_t)m.texture >= desc->n_textures)) return fail(FW_ERR_BAD_ARG, "material texture out of range");
         uint32_t mbits = (uint32_t)m.kind;
@@ -1713,6 +1723,7 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out, con
         }
         if (m.kind == FW_MAT_DIELECTRIC) { q[4] = q[5] = q[6] = 1.f; }          // its attenuation (material.rs:128), for the chain state's product
         q[0] = bits_f(mbits); q[1] = bits_f((uint32_t)(needs_tex ? m.texture : 0)); q[2] = m.roughness; q[3] = m.ref_idx;
+        if (m.kind == FW_MAT_GGX) q[2] = m.roughness * m.roughness;              // alpha
     }
     const fw_environment &e = desc->environment;
     if (e.kind < FW_ENV_COLOR || e.kind > FW_ENV_HDR) return fail(FW_ERR_BAD_ARG, "unknown environment kind");
@@ -1831,6 +1842,7 @@ int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out, con
             uint32_t mb; std::memcpy(&mb, &mats[(size_t)i * 8], 4);
             const uint32_t mk = mb & 0xffu;
             if (!(mb & fw::MF_TEX_CONST) && (mk == (uint32_t)FW_MAT_LAMBERTIAN || mk == (uint32_t)FW_MAT_EMISSIVE || mk == (uint32_t)FW_MAT_ISOTROPIC)) constant = false;
+            if (mk == (uint32_t)FW_MAT_GGX) constant = false;          // its attenuation depends on the directions
         }
         uint32_t bits = 1; while ((1u << bits) < desc->n_materials) bits++;
         if (constant && 10u * bits <= 32u) sc->chain_bits = bits;
@@ -2401,7 +2413,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // (the linear scan tests every object anyway: only a mesh's BLAS is walked there)
     // (FIREWORK_FUSED=1, the one-launch-per-segment A/B kernel, has no second pass: it runs without the exact walk)
 #if FW_AB
-    const bool fused_req = O.fused && !ls && !(p->use_bvh && sc->d.has_mesh);
+    const bool fused_req = O.fused && !ls && !(p->use_bvh && sc->d.has_mesh) && !sc->has_ggx;      // (k_bounce has no GgxMat)
     const bool tlas_refill = !O.tlas_refill_off;
 #else
     const bool fused_req = false, tlas_refill = true;
@@ -2526,8 +2538,9 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // 1.90 -> 1.98, volume@64 6.08 -> 6.12) and stays behind FIREWORK_SHADE_LIST=1; FIREWORK_NO_SHADE_DEFER=1 forces mode 0.
     cfg.shade_mode = !sc->has_expensive ? 1 : 0;
 #if FW_AB
-    if (O.no_shade_defer) cfg.shade_mode = 0; else if (sc->has_expensive && O.shade_list && q.cap <= 65536u) cfg.shade_mode = 2;
+    if (O.no_shade_defer) cfg.shade_mode = 0; else if (sc->has_expensive && O.shade_list && q.cap <= 65536u && !sc->has_ggx) cfg.shade_mode = 2;
 #endif
+    cfg.gx = sc->has_ggx;
 
     fw::DCamera cam = vg ? vg->cams[0] : ri ? fw::DCamera{} : make_camera(p->camera, p->width, p->height);
     fw::DFrame fr{};         // (zeroed: the frame graph's key hashes these structs, padding and not-yet-set per-batch fields included)
@@ -2698,7 +2711,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
                 fw::DFrame sfr = c.fr; sfr.seed32 ^= fw::SHADOW_SEED; sfr.ex.mode = 0;
                 const fw::DPaths sp{c.sh.ray_a, c.sh.ray_b, c.sh.state};
                 timed(c, 1, [&] { fw::launch_extend(scfg, sc->d, sfr, sp, (float2 *)L.s_hits, seg + 1, use_bvh, c.park); });
-                timed(c, 2, [&] { fw::launch_shadow_resolve(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg, es, pl, dl); });
+                timed(c, 2, [&] { fw::launch_shadow_resolve(scfg, sc->d, c.sh, (const float2 *)L.s_hits, seg, es, pl, dl, c.srad); });
             }
         } else
         timed(c, 2, [&] { fw::launch_shade(c.cfg, sc->d, c.fr, c.buf[c.cur], c.buf[c.cur ^ 1], c.hits, c.srad, seg); });
@@ -3861,6 +3874,29 @@ int fw_selftest_libm(int device, int fn, uint32_t n, const float *x, const float
         }
     }
     dx.release(); dy.release(); dout.release();
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(FW_ERR_HIP, hipGetErrorString(e));
+    return FW_OK;
+}
+
+// n GgxMat vertices through the shade kernels' own device functions (k_ggx_test)
+int fw_selftest_ggx(int device, uint32_t n, const float *in, float *out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(FW_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev || !in || !out || n == 0 || n > (1u << 24)) return fail(FW_ERR_BAD_ARG, "bad argument");
+    HIPCHK(hipSetDevice(device));
+    DevBuf din, dout;
+    int rc = din.alloc((size_t)n * FW_GGX_IN_FLOATS * 4);
+    if (!rc) rc = dout.alloc((size_t)n * FW_GGX_OUT_FLOATS * 4);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        e = hipMemcpy(din.p, in, (size_t)n * FW_GGX_IN_FLOATS * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            fw::launch_ggx_test(nullptr, n, (const float *)din.p, (float *)dout.p);
+            e = hipMemcpy(out, dout.p, (size_t)n * FW_GGX_OUT_FLOATS * 4, hipMemcpyDeviceToHost);
+        }
+    }
+    din.release(); dout.release();
     if (rc) return rc;
     if (e != hipSuccess) return fail(FW_ERR_HIP, hipGetErrorString(e));
     return FW_OK;

@@ -1,9 +1,9 @@
-// The body of the five light-sampling shade kernels k_shade_ls, k_shade_env, k_shade_pl, k_shade_pl_env and k_shade_dl (fw_kernels.hip, DESIGN
-// §9g-§9i, §9l),
+// The body of the light-sampling shade kernels k_shade_ls, k_shade_env, k_shade_pl, k_shade_pl_env, k_shade_dl and k_shade_gx_nee (fw_kernels.hip,
+// DESIGN §9g-§9i, §9l, §9m),
 // included inside each.  (The same body in a __forceinline__ device function called from four thin kernels compiled all 18 instantiations to
 // different instruction streams — SGPR spills moved by up to 10 — and shipped kernels keep theirs; included text compiles to the kernel it was.)
 // In scope: the kernel's arguments (sc, f, in, out, hits, sample_rad, q, segment, n_mat, n_tex, sh), constexpr (or template parameters)
-// int LDS_TAB, MODE (0 or 1: in line; 1: nothing expensive in the scene) and bool ENV, PL, DL, which are shade_path's, and the three pointers
+// int LDS_TAB, MODE (0 or 1: in line; 1: nothing expensive in the scene) and bool ENV, PL, DL, GX, which are shade_path's, and the three pointers
 // shade_path takes them with: const DEnvDist *const edp (&ed of the kernel's argument where ENV, else nullptr), const DEmitters *const emp
 // (&em where PL, else nullptr) and const DDeltaLights *const dlp (&dl where DL, else nullptr).
 // k_shade's loop without the chain state and the list: a light-sampling frame carries the running product and shades in line.
@@ -31,7 +31,7 @@
         Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
         if (j < n) {
             path_id = __float_as_uint(st.w);
-            alive = shade_path<MODE != 0, CHAIN, true, ENV, PL, DL>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id, hr.x,
+            alive = shade_path<MODE != 0, CHAIN, true, ENV, PL, DL, GX>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), 0u, path_id, hr.x,
                                                                 __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS, nullptr, &sh, &ls, edp, emp, dlp);
         }
         // k_shade's compaction, with p_b next to the state

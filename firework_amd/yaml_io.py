@@ -62,6 +62,8 @@ def _material(d, base_dir):
         return A.LambertianMat(_texture(d["albedo"], base_dir))
     if k == "MetalMat":
         return A.MetalMat(_v3(d["albedo"]), float(d["roughness"]))
+    if k == "GgxMat":
+        return A.GgxMat(_v3(d["albedo"]), float(d["roughness"]))
     if k == "DielectricMat":
         return A.DielectricMat(float(d["ref_idx"]))
     if k == "EmissiveMat":
@@ -184,6 +186,8 @@ def _material_d(m):
         return {"material": "LambertianMat", "albedo": _texture_d(m.albedo)}
     if isinstance(m, A.MetalMat):
         return {"material": "MetalMat", "albedo": _v3d(m.albedo), "roughness": float(m.roughness)}
+    if isinstance(m, A.GgxMat):
+        return {"material": "GgxMat", "albedo": _v3d(m.albedo), "roughness": float(m.roughness)}
     if isinstance(m, A.DielectricMat):
         return {"material": "DielectricMat", "ref_idx": float(m.ref_idx)}
     if isinstance(m, A.EmissiveMat):

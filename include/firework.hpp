@@ -98,6 +98,8 @@ struct Material { fw_material m{}; TexturePtr tex; };
 struct LambertianMat { static Material new_(TexturePtr albedo) { Material r; r.m.kind = FW_MAT_LAMBERTIAN; r.tex = std::move(albedo); return r; }
                        static Material with_color(Vec3 c) { return new_(ConstantTexture::new_(c)); } };
 struct MetalMat { static Material new_(Vec3 albedo, float roughness) { Material r; r.m.kind = FW_MAT_METAL; r.m.albedo = lower(albedo); r.m.roughness = roughness; return r; } };
+// an isotropic GGX conductor (FW_MAT_GGX, firework_hip.h): albedo = F0 in [0, 1], roughness in [0.03, 1]; not in the reference
+struct GgxMat { static Material new_(Vec3 albedo, float roughness) { Material r; r.m.kind = FW_MAT_GGX; r.m.albedo = lower(albedo); r.m.roughness = roughness; return r; } };
 struct DielectricMat { static Material new_(float ref_idx) { Material r; r.m.kind = FW_MAT_DIELECTRIC; r.m.ref_idx = ref_idx; return r; } };
 struct EmissiveMat { static Material new_(TexturePtr albedo) { Material r; r.m.kind = FW_MAT_EMISSIVE; r.tex = std::move(albedo); return r; }
                      static Material with_color(Vec3 c) { return new_(ConstantTexture::new_(c)); } };

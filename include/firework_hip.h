@@ -84,14 +84,33 @@ typedef enum fw_material_kind {
     FW_MAT_METAL = 1,       /* material.rs:77-107  {albedo, roughness} */
     FW_MAT_DIELECTRIC = 2,  /* material.rs:109-151 {ref_idx}           */
     FW_MAT_EMISSIVE = 3,    /* material.rs:153-181 {albedo: texture}   */
-    FW_MAT_ISOTROPIC = 4    /* material.rs:183-204 {texture}           */
+    FW_MAT_ISOTROPIC = 4,   /* material.rs:183-204 {texture}           */
+    FW_MAT_GGX = 5          /* not in the reference: {albedo, roughness}, specified below */
 } fw_material_kind;
+
+/* FW_MAT_GGX: an isotropic GGX microfacet conductor, two-sided.  albedo = the normal-incidence reflectance F0, every
+   component in [0, 1]; roughness in [0.03, 1]; alpha = roughness^2 (float32).  Anything else: FW_ERR_BAD_ARG naming the material's index.
+   Unlike Metal's lobe this one has a density, so its vertices take light samples: the point, spot and directional lights, and under
+   FW_FLAG_LIGHT_SAMPLING the sphere and rectangle emitters.
+     Frame: wo = -normalized(ray direction); n = the hit normal, negated where wo.n < 0; the tangent frame around n is the branchless basis
+       of Duff et al. 2017: s = copysignf(1, n.z), a = -1 / (s + n.z), b = n.x n.y a, t = (1 + s n.x^2 a, s b, -s n.x), u = (b, s + n.y^2 a, -n.y).
+     Sampling: (xi1, xi2) = the x and y words of draw(key, purpose 6, segment, 0).  A visible normal h by Heitz 2018: stretch wo by alpha,
+       sample the projected disk (r = sqrt(xi1), phi = 2 pi xi2), unstretch; no rejection.  wi = reflect(-wo, h).  The path ends where
+       wi.n <= 0; otherwise its attenuation is F(wo.h) G2(wo, wi) / G1(wo), with Schlick's F = F0 + (1 - F0)(1 - wo.h)^5,
+       Lambda(w) = (-1 + sqrt(1 + alpha^2 tan^2(theta_w))) / 2, G1 = 1 / (1 + Lambda), G2 = 1 / (1 + Lambda(wo) + Lambda(wi)).
+     Evaluation (light samples): f cos(theta_i) = F D(h) G2 / (4 wo.n) with h = normalized(wo + wi), density p_b(wi) = G1(wo) D(h) / (4 wo.n),
+       D = alpha^2 / (pi (|h_t|^2 + alpha^2 h_n^2)^2) from h's tangential and normal parts.
+     Light samples: a delta light contributes beta f cos L / p (weight 1); an emitter under FW_FLAG_LIGHT_SAMPLING beta f cos Le / p_l x
+       p_l^2 / (p_l^2 + p_b^2), and an emitter the scattered ray then hits takes p_b^2 / (p_b^2 + p_l^2).  A vertex whose own sample ends the
+       path still takes its light sample.  Under FW_FLAG_ENV_SAMPLING and FW_FLAG_ALL_EMITTERS a GgxMat vertex takes NO light sample, as a
+       Metal vertex: what its path meets next keeps weight 1 (unbiased; light samples there are not built).
+   Every entry point that takes a fw_scene_desc takes the material. */
 
 typedef struct fw_material {
     int32_t kind;
     int32_t texture;   /* Lambertian / Emissive / Isotropic: index into textures */
-    fw_vec3 albedo;    /* Metal */
-    float roughness;   /* Metal */
+    fw_vec3 albedo;    /* Metal; Ggx: F0 */
+    float roughness;   /* Metal, Ggx */
     float ref_idx;     /* Dielectric */
 } fw_material;
 
@@ -801,6 +820,14 @@ int fw_selftest_emitters(const fw_scene_desc *desc, float *out, uint32_t cap, ui
    FW_ERR_UNSUPPORTED (no entry of positive weight, or more than 2^26 entries), FW_ERR_HIP. */
 #define FW_EMITTER_SAMPLE_FLOATS 9
 int fw_selftest_emitter_sample(fw_scene *scene, const float *x, uint32_t n, uint32_t seed, float *out);
+/* Diagnostic (GPU): n FW_MAT_GGX vertices through the device functions the shade kernels call.  in: FW_GGX_IN_FLOATS per entry: the unit
+   normal (xyz), the incoming ray's direction (xyz, any length), roughness, F0 (rgb), xi1, xi2, and a direction omega (xyz, normalised here)
+   to evaluate.  out: FW_GGX_OUT_FLOATS per entry: the sampled wi (xyz, world space), the attenuation (rgb; 0 where not alive), alive (1 or
+   0), f cos(omega) (rgb) and p_b(omega).  Ranges are not checked (roughness^2 is taken as it comes).  Errors: FW_ERR_BAD_ARG (null pointers,
+   n = 0 or above 2^24, device out of range), FW_ERR_NO_DEVICE, FW_ERR_HIP. */
+#define FW_GGX_IN_FLOATS 15
+#define FW_GGX_OUT_FLOATS 11
+int fw_selftest_ggx(int device, uint32_t n, const float *in, float *out);
 
 #ifdef __cplusplus
 }
