@@ -24,7 +24,11 @@ history of the view before it — a pixel carries over at most MAX_HISTORY sampl
 --denoise L and --aov-samples keep their meaning; view k renders with seed + k; not with --progressive / --checkpoint / --adaptive /
 --camera), --camera fisheye [--fisheye-fov DEG] (an equidistant full-frame fisheye along the fixed view's direction, DEG degrees across
 the image diagonal, default 180; combines as the other models do).  The three models' rays are generated on the device
-(fw_render_model)."""
+(fw_render_model).  --bake-probes NX,NY,NZ --probe-min x,y,z --probe-max x,y,z [--probe-dirs D] [--probe-rounds R]
+(no image: a grid of irradiance probes between the two corners, D directions each, default 256, R rounds of -s samples per direction,
+default 1, baked on the device into nine SH coefficients per probe and channel, fw_bake_probes; -o names an .npz with
+positions, sh, sums, rounds, directions and samples; --light-sampling, --env-sampling and --all-emitters apply; not with --camera /
+--denoise / --orbit / --adaptive / --progressive / --checkpoint / --temporal)."""
 import argparse
 import sys
 import time
@@ -69,7 +73,40 @@ def main(argv=None):
                     help="with --camera orthographic: the height of the view plane (default: what the pinhole view sees at its look-at point)")
     ap.add_argument("--fisheye-fov", type=float, default=None, metavar="DEG",
                     help="with --camera fisheye: the angle across the image diagonal in degrees, in (0, 360] (default 180)")
+    ap.add_argument("--bake-probes", default=None, metavar="NX,NY,NZ",
+                    help="bake a grid of irradiance probes (nine SH coefficients per probe and channel) into the .npz named by -o")
+    ap.add_argument("--probe-min", default=None, metavar="X,Y,Z", help="with --bake-probes: the grid's first corner")
+    ap.add_argument("--probe-max", default=None, metavar="X,Y,Z", help="with --bake-probes: the grid's last corner")
+    ap.add_argument("--probe-dirs", type=int, default=None, metavar="D", help="with --bake-probes: directions per probe and round (default 256)")
+    ap.add_argument("--probe-rounds", type=int, default=None, metavar="R", help="with --bake-probes: rounds of -s samples per direction (default 1)")
     opt = ap.parse_args(argv)
+    if opt.bake_probes is not None:
+        if (opt.camera != "pinhole" or opt.denoise is not None or opt.orbit or opt.adaptive is not None or opt.progressive > 0 or opt.checkpoint
+                or opt.temporal is not None):
+            ap.error("--bake-probes cannot be combined with --camera, --denoise, --orbit, --adaptive, --progressive, --checkpoint or --temporal")
+        try:
+            counts = [int(x) for x in opt.bake_probes.split(",")]
+        except ValueError:
+            counts = []
+        if len(counts) != 3 or min(counts) < 1:
+            ap.error("--bake-probes needs NX,NY,NZ, three counts >= 1")
+        corners = []
+        for name, text in (("--probe-min", opt.probe_min), ("--probe-max", opt.probe_max)):
+            try:
+                c = [float(x) for x in (text or "").split(",")]
+            except ValueError:
+                c = []
+            if len(c) != 3 or not all(abs(x) < float("inf") for x in c):
+                ap.error(f"--bake-probes needs {name} x,y,z, three finite numbers")
+            corners.append(c)
+        if opt.probe_dirs is not None and not 1 <= opt.probe_dirs <= 1 << 20:
+            ap.error("--probe-dirs D needs 1 <= D <= 2^20")
+        if opt.probe_rounds is not None and opt.probe_rounds < 1:
+            ap.error("--probe-rounds R needs R >= 1")
+        if not opt.output:
+            ap.error("--bake-probes needs -o FILE.npz")
+    elif opt.probe_min is not None or opt.probe_max is not None or opt.probe_dirs is not None or opt.probe_rounds is not None:
+        ap.error("--probe-min, --probe-max, --probe-dirs and --probe-rounds need --bake-probes")
     if opt.adaptive is not None and (opt.progressive > 0 or opt.checkpoint):
         ap.error("--adaptive cannot be combined with --progressive or --checkpoint")
     if opt.temporal is not None:
@@ -123,6 +160,18 @@ def main(argv=None):
     if opt.all_emitters:       # bits 4 and 16: light sampling over every emitting primitive
         renderer.light_sampling().all_emitters()
     start = time.time()
+    if opt.bake_probes is not None:
+        import numpy as np
+        from .api import ProbeSet
+        probes = ProbeSet.grid(corners[0], corners[1], counts, 256 if opt.probe_dirs is None else opt.probe_dirs).seed(opt.seed)
+        rounds = 1 if opt.probe_rounds is None else opt.probe_rounds
+        sh, sums = renderer.bake_probes(scene, probes, rounds, device=opt.device)
+        print(f"Finished Baking in {int(time.time() - start)} s")
+        print(f'Saving {probes.n_probes} probes to "{opt.output}"')
+        with open(opt.output, "wb") as f:       # (np.savez would append .npz to a name without it)
+            np.savez(f, positions=probes.positions, sh=sh, sums=sums, rounds=np.int64(rounds), directions=np.int64(probes.directions),
+                     samples=np.int64(opt.samples))
+        return 0
     if opt.camera != "pinhole":
         render = camera_model_render(renderer, camera, scene, opt)
     elif opt.orbit > 0 and opt.temporal is not None:

@@ -168,5 +168,10 @@ class fw_camera_model(C.Structure):
                 ("fov", C.c_double), ("jitter", i32), ("seed", u64), ("chunk_samples", u32)]
 
 
+# irradiance probes on the device (include/firework_hip.h: fw_probe_rays, fw_probe_project, fw_bake_probes)
+class fw_probe_set(C.Structure):
+    _fields_ = [("n_probes", u32), ("positions", C.POINTER(f32)), ("directions", u32), ("jitter", i32), ("seed", u64), ("chunk_probes", u32)]
+
+
 def vec3(v):
     return fw_vec3(float(v[0]), float(v[1]), float(v[2]))

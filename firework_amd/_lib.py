@@ -116,6 +116,13 @@ def load(preload=False, device=None):
     lib.fw_render_model_aovs.restype = C.c_int
     lib.fw_render_model_aovs.argtypes = [C.c_void_p, C.POINTER(A.fw_camera_model), C.POINTER(A.fw_render_params), C.c_void_p,
                                          C.POINTER(A.fw_stats)]
+    lib.fw_probe_rays.restype = C.c_int
+    lib.fw_probe_rays.argtypes = [C.POINTER(A.fw_probe_set), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+    lib.fw_probe_project.restype = C.c_int
+    lib.fw_probe_project.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.fw_bake_probes.restype = C.c_int
+    lib.fw_bake_probes.argtypes = [C.c_void_p, C.POINTER(A.fw_probe_set), C.POINTER(A.fw_render_rays_params), C.c_uint32, C.c_uint32, C.c_void_p,
+                                   C.c_void_p, C.POINTER(A.fw_stats)]
     lib.fw_denoise.restype = C.c_int
     lib.fw_denoise.argtypes = [C.POINTER(A.fw_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fw_temporal.restype = C.c_int
@@ -393,6 +400,69 @@ def model_rays(model, first_sample=0, n_samples=1, device=0, out=None, stream=No
     return rays
 
 
+def _probe_abi(probes, chunk=None):
+    """(fw_probe_set, the positions array it points into) from an api.ProbeSet, with chunk_probes = chunk when given"""
+    s, pos = probes.to_abi()
+    if chunk is not None:
+        s.chunk_probes = int(chunk)
+    return s, pos
+
+
+def probe_rays(probes, round=0, first_probe=0, n=None, device=0, out=None, stream=None):
+    """fw_probe_rays: the rays of round `round` of the probes [first_probe, first_probe + n) of an api.ProbeSet (n None: to the last
+    one), generated on the device: (n * D, 6) float32 origin + direction, entry p * D + j = direction j of probe p.  Returns a numpy
+    array; out: a contiguous float32 device tensor of that shape on cuda:`device` to fill instead, on `stream` (default: the current
+    torch stream); returned."""
+    lib = load()
+    s, _pos = _probe_abi(probes)
+    if n is None:
+        n = int(s.n_probes) - int(first_probe)
+    shape = (int(n) * int(s.directions), 6)
+    if out is not None:
+        import torch
+        _check_device_tensor(out, shape, torch.float32, device, "out")
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+        _check(lib, lib.fw_probe_rays(C.byref(s), int(device), int(round), int(first_probe), int(n), out.data_ptr(), 1,
+                                      C.c_void_p(stream) if stream else None))
+        return out
+    rays = np.empty(shape, np.float32)
+    _check(lib, lib.fw_probe_rays(C.byref(s), int(device), int(round), int(first_probe), int(n), rays.ctypes.data, 0, None))
+    return rays
+
+
+def probe_project(rays, accum, samples, directions, sums=None, device=0, stream=None):
+    """fw_probe_project: adds (4 pi / D) sum_j Y_k(d_pj) accum[p D + j] / samples, rounded to float32 once, to sums[p][k].  rays (N * D,
+    6) and accum (N * D, 4) float32, sums (N, 9, 3) float32 updated in place (None: zeros); numpy arrays, or contiguous torch tensors
+    on cuda:`device`, projected on `stream` (default: the current torch stream) where they lie.  Returns sums."""
+    lib = load()
+    d = int(directions)
+    total = int(rays.shape[0])
+    if d < 1 or total % d or tuple(rays.shape) != (total, 6) or tuple(accum.shape) != (total, 4):
+        raise ValueError(f"rays must have shape (N * {d}, 6) and accum (N * {d}, 4)")
+    n = total // d
+    if type(rays).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
+        _check_device_tensor(accum, (total, 4), torch.float32, device, "accum")
+        if sums is None:
+            sums = torch.zeros((n, 9, 3), dtype=torch.float32, device=rays.device)
+        _check_device_tensor(sums, (n, 9, 3), torch.float32, device, "sums")
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+        _check(lib, lib.fw_probe_project(int(device), n, d, int(samples), rays.data_ptr(), accum.data_ptr(), sums.data_ptr(), 1,
+                                         C.c_void_p(stream) if stream else None))
+        return sums
+    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
+    a = np.ascontiguousarray(np.asarray(accum, dtype=np.float32))
+    if sums is None:
+        sums = np.zeros((n, 9, 3), np.float32)
+    if not (isinstance(sums, np.ndarray) and sums.dtype == np.float32 and sums.shape == (n, 9, 3) and sums.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"sums must be a contiguous float32 array of shape ({n}, 9, 3)")
+    _check(lib, lib.fw_probe_project(int(device), n, d, int(samples), r.ctypes.data, a.ctypes.data, sums.ctypes.data, 0, None))
+    return sums
+
+
 class DeviceScene:
     """An uploaded scene (`fw_scene*`): SoA scene arrays + TLAS/BLAS resident in HBM."""
 
@@ -663,6 +733,43 @@ class DeviceScene:
         _check(lib, lib.fw_render_model_aovs(self.handle, C.byref(m), C.byref(p), aov.ctypes.data, C.byref(st)))
         self.aovs_stats = st.as_dict()
         return aov
+
+    def bake_probes(self, probes, rounds, samples, first_round=0, sums=None, seed=0, use_bvh=True, stream=None, paths_per_batch=0, flags=0,
+                    chunk=None, on_device=False):
+        """fw_bake_probes: the rounds [first_round, first_round + rounds) of an api.ProbeSet, `samples` paths per direction and round,
+        `chunk` probes at a time (None: the set's own setting; 0: automatic).  sums: (N, 9, 3) float32 running sums of the rounds
+        before first_round, updated in place (None: zeros, only with first_round 0).  Returns (sh, sums, stats): host arrays, or —
+        sums a device tensor on this scene's device, or on_device=True — device tensors, baked on `stream` (default: the current
+        torch stream).  sh = sums / (first_round + rounds)."""
+        lib = self._lib
+        s, _pos = _probe_abi(probes, chunk)
+        n = int(s.n_probes)
+        p = A.fw_render_rays_params()
+        p.samples, p.seed, p.use_bvh, p.gamma = int(samples), int(seed), int(bool(use_bvh)), 1.0
+        p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
+        st = A.fw_stats()
+        if on_device or (sums is not None and type(sums).__module__.startswith("torch")):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if sums is None:
+                sums = torch.zeros((n, 9, 3), dtype=torch.float32, device=dev)
+            _check_device_tensor(sums, (n, 9, 3), torch.float32, self.device, "sums")
+            sh = torch.empty((n, 9, 3), dtype=torch.float32, device=dev)
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            p.on_device = 1
+            p.stream = C.c_void_p(stream) if stream else None
+            _check(lib, lib.fw_bake_probes(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), sums.data_ptr(), sh.data_ptr(),
+                                           C.byref(st)))
+            return sh, sums, st.as_dict()
+        if sums is None:
+            sums = np.zeros((n, 9, 3), np.float32)
+        if not (isinstance(sums, np.ndarray) and sums.dtype == np.float32 and sums.shape == (n, 9, 3) and sums.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"sums must be a contiguous float32 array of shape ({n}, 9, 3)")
+        sh = np.empty((n, 9, 3), np.float32)
+        _check(lib, lib.fw_bake_probes(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), sums.ctypes.data, sh.ctypes.data,
+                                       C.byref(st)))
+        return sh, sums, st.as_dict()
 
     def trace(self, rays, use_bvh, seed=0, key_base=0, rays_per_batch=0, time_kernels=False, stats=None):
         """fw_trace_rays: one root.hit(ray, 0.001, 2e9) per ray.  rays: (n, 6) origin + direction.

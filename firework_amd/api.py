@@ -1119,6 +1119,115 @@ class CameraModel:
         return m
 
 
+# --------------------------------------------------------------------------- irradiance probes (fw_bake_probes)
+_SH_Y0 = 0.5 * np.sqrt(1.0 / np.pi)
+_SH_C1 = np.sqrt(3.0 / (4.0 * np.pi))
+_SH_C2 = 0.5 * np.sqrt(15.0 / np.pi)
+_SH_C6 = 0.25 * np.sqrt(5.0 / np.pi)
+_SH_C8 = 0.25 * np.sqrt(15.0 / np.pi)
+# the Ramamoorthi-Hanrahan cosine-lobe factors of the bands l = 0, 1, 2, per coefficient
+_SH_COSINE = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+
+
+def sh_basis(dirs) -> np.ndarray:
+    """(..., 9) float64: the real orthonormal spherical harmonics up to l = 2 of the unit directions dirs (..., 3), index k = l (l + 1) + m,
+    polar axis as written (no renormalisation): Y0 = 1/2 sqrt(1/pi), Y1..3 = sqrt(3/4pi) (y, z, x), Y4 = 1/2 sqrt(15/pi) x y,
+    Y5 = 1/2 sqrt(15/pi) y z, Y6 = 1/4 sqrt(5/pi) (3 z z - 1), Y7 = 1/2 sqrt(15/pi) x z, Y8 = 1/4 sqrt(15/pi) (x x - y y)."""
+    d = np.asarray(dirs, np.float64)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    return np.stack([np.full(x.shape, _SH_Y0), _SH_C1 * y, _SH_C1 * z, _SH_C1 * x, (_SH_C2 * x) * y, (_SH_C2 * y) * z,
+                     _SH_C6 * (3.0 * (z * z) - 1.0), (_SH_C2 * x) * z, _SH_C8 * (x * x - y * y)], axis=-1)
+
+
+def sh_project(rays, accum, samples: int, directions: int) -> np.ndarray:
+    """The float64 statement of fw_probe_project: (N, 9, 3) with proj[p][k][c] = (4 pi / D) sum_j Y_k(d_pj) accum[p D + j][c] / samples,
+    for rays (N * D, 6) (the directions as stored) and accum (N * D, 4) (r, g, b sums, then segments)."""
+    D = int(directions)
+    r = np.asarray(rays, np.float64).reshape(-1, D, 6)
+    a = np.asarray(accum, np.float64).reshape(-1, D, 4)[..., :3] / float(samples)
+    return (4.0 * np.pi / D) * np.einsum("pjk,pjc->pkc", sh_basis(r[..., 3:]), a)
+
+
+def sh_radiance(sh, dirs) -> np.ndarray:
+    """The radiance the coefficients sh (..., 9, 3) reconstruct along the unit directions dirs (M, 3): (..., M, 3) float64."""
+    return np.einsum("mk,...kc->...mc", sh_basis(np.asarray(dirs, np.float64).reshape(-1, 3)), np.asarray(sh, np.float64))
+
+
+def sh_irradiance(sh, normals) -> np.ndarray:
+    """The irradiance on surfaces with the unit normals (M, 3) under the radiance sh (..., 9, 3) describes: (..., M, 3) float64, the
+    Ramamoorthi-Hanrahan cosine convolution, band factors pi, 2 pi / 3 and pi / 4."""
+    y = sh_basis(np.asarray(normals, np.float64).reshape(-1, 3)) * _SH_COSINE
+    return np.einsum("mk,...kc->...mc", y, np.asarray(sh, np.float64))
+
+
+class ProbeSet:
+    """Irradiance probes (fw_probe_set): N positions with `directions` rays each, per round a spherical Fibonacci lattice
+    with a Cranley-Patterson shift per (round, probe).  ProbeSet(positions, directions=256) or ProbeSet.grid(lo, hi, (nx, ny, nz)), then
+    .seed(s) / .jitter(on) as builders.  .rays(round) is the numpy float64 statement of what the device generates; _lib.probe_rays(set,
+    ...) the device's own."""
+
+    def __init__(self, positions, directions: int = 256):
+        self.positions = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))
+        self.directions = int(directions)
+        self._seed, self._jitter, self.chunk_probes = 0, True, 0
+
+    @staticmethod
+    def grid(lo, hi, counts, directions: int = 256) -> "ProbeSet":
+        """nx x ny x nz probes on a regular grid from corner lo to corner hi, both included (a count of 1 sits at the middle), x
+        fastest, then y, then z"""
+        lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+        if len(counts) != 3 or any(int(n) < 1 for n in counts):
+            raise ValueError("counts must be three numbers >= 1")
+        axes = [np.linspace(lo[k], hi[k], int(counts[k])) if int(counts[k]) > 1 else np.array([0.5 * (lo[k] + hi[k])]) for k in range(3)]
+        z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+        return ProbeSet(np.stack([x, y, z], axis=-1).reshape(-1, 3), directions)
+
+    @property
+    def n_probes(self) -> int:
+        return int(self.positions.shape[0])
+
+    def seed(self, s):
+        self._seed = int(s)
+        return self
+
+    def jitter(self, on=True):
+        self._jitter = bool(on)
+        return self
+
+    def shifts(self, round: int) -> np.ndarray:
+        """(N, 2) float64: the shift (xi_u, xi_v) of every probe in `round` (pixel_jitter with sample -> round, pixel -> probe)"""
+        n = self.n_probes
+        return pixel_jitter(self._seed, round, n) if self._jitter else np.full((n, 2), 0.5)
+
+    def rays(self, round: int, device=None):
+        """the numpy statement of one round's rays: (N * D, 6) float32, entry p * D + j = direction j of probe p (device: see
+        panorama_rays).  In float64, rounded once: u = (j + xi_u) / D, c = 1 - 2 u, rad = sqrt(max(0, 1 - c c)), t = j g + xi_v with
+        g = (sqrt(5) - 1) / 2, v = t - floor(t), phi = 2 pi v, d = (rad cos phi, c, rad sin phi)."""
+        n, D = self.n_probes, self.directions
+        if D < 1:
+            raise ValueError("directions must be >= 1")
+        xi = self.shifts(round)
+        j = np.arange(D, dtype=np.float64)[None, :]
+        u = (j + xi[:, 0:1]) / float(D)
+        c = 1.0 - 2.0 * u
+        rad = np.sqrt(np.maximum(0.0, 1.0 - c * c))
+        g = (np.sqrt(5.0) - 1.0) / 2.0
+        t = j * g + xi[:, 1:2]
+        v = t - np.floor(t)
+        phi = (2.0 * np.pi) * v
+        d = np.stack([rad * np.cos(phi), c, rad * np.sin(phi)], axis=-1).reshape(n * D, 3)
+        o = np.repeat(self.positions.astype(np.float64), D, axis=0)
+        return _rays_out(o, d, device)
+
+    def to_abi(self):
+        """(fw_probe_set, the float32 positions it points into: keep them alive as long as the struct is used)"""
+        s = A.fw_probe_set()
+        s.n_probes, s.positions = self.n_probes, self.positions.ctypes.data_as(C.POINTER(C.c_float))
+        s.directions, s.jitter = self.directions, int(self._jitter)
+        s.seed, s.chunk_probes = self._seed & 0xFFFFFFFFFFFFFFFF, int(self.chunk_probes)
+        return s, self.positions
+
+
 # render_sequence's default cap on the samples a pixel carries over from the frames before it (DESIGN.md §9j)
 DEFAULT_MAX_HISTORY = 64.0
 
@@ -1456,6 +1565,26 @@ class Renderer:
         try:
             return ds.render_model(model, samples, first_sample, accum, seed=s["seed"], use_bvh=s["use_bvh"], gamma=s["gamma"], stream=stream,
                                    paths_per_batch=s["paths_per_batch"], flags=s["flags"], chunk=chunk, on_device=on_device)
+        finally:
+            if ds is not scene:
+                ds.close()
+
+    def bake_probes(self, scene, probes: "ProbeSet", rounds: int = 1, first_round: int = 0, sums=None, chunk=None, device: int = 0, stream=None,
+                    on_device: bool = False):
+        """Irradiance probes baked on the device (not in the reference; fw_bake_probes): `rounds` rounds of the set's rays, each
+        rendered with settings["samples"] paths per direction and this renderer's seed (+ the round), use_bvh, batch size and flags —
+        lights and light sampling included; its camera, size and gamma are not used — and projected onto nine SH coefficients per
+        probe and channel.  Returns (sh, sums): (N, 9, 3) float32 each, sh = sums / (first_round + rounds); pass sums back with
+        first_round = the rounds it holds to add more.  on_device and chunk as _lib.DeviceScene.bake_probes; the call's stats are kept
+        in self.probe_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        from . import _lib
+        s = self.settings
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            sh, sums, self.probe_stats = ds.bake_probes(probes, rounds, s["samples"], first_round, sums, seed=s["seed"], use_bvh=s["use_bvh"],
+                                                        stream=stream, paths_per_batch=s["paths_per_batch"], flags=s["flags"], chunk=chunk,
+                                                        on_device=on_device)
+            return sh, sums
         finally:
             if ds is not scene:
                 ds.close()

@@ -12,6 +12,7 @@
 #include "fw_build.h"
 #include "fw_temporal.h"
 #include "fw_camera_models.h"
+#include "fw_probes.h"
 
 #include <algorithm>
 #include <atomic>
@@ -3807,6 +3808,209 @@ int model_aovs_impl(fw_scene *sc, const fw_camera_model *m, const fw_render_para
     return aovs_impl(sc, &P, aov, stats, &dm);
 }
 
+// ---- irradiance probes (include/firework_hip.h) ----------------------------------------------------------------
+// The set's own argument checks (FW_ERR_BAD_ARG only).  too_large: n_probes x D >= 2^31, which the callers report as FW_ERR_UNSUPPORTED
+// after their own argument checks.
+int probe_set_check(const fw_probe_set *s, bool &too_large) {
+    if (!s->positions) return fail(FW_ERR_BAD_ARG, "null positions");
+    if (s->n_probes == 0) return fail(FW_ERR_BAD_ARG, "n_probes must be > 0");
+    if (s->directions == 0 || s->directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    for (uint64_t i = 0; i < (uint64_t)s->n_probes * 3; i++)
+        if (!std::isfinite(s->positions[i])) return fail(FW_ERR_BAD_ARG, "probe " + std::to_string(i / 3) + " has a non-finite position");
+    too_large = (uint64_t)s->n_probes * s->directions >= (1ull << 31);
+    return FW_OK;
+}
+
+fw::DProbes probes_device(const fw_probe_set *s, uint32_t round, uint32_t first_probe, const float *d_positions) {
+    fw::DProbes d{};
+    d.directions = s->directions;
+    d.seed32 = (uint32_t)s->seed ^ ((uint32_t)(s->seed >> 32) * 0x9E3779B9u);
+    d.jitter = s->jitter ? 1u : 0u;
+    d.round = round; d.first_probe = first_probe; d.positions = d_positions;
+    return d;
+}
+
+constexpr size_t PROBE_SCRATCH_BYTES = (size_t)256 << 20;     // the automatic chunk of fw_bake_probes and fw_probe_rays' host output
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// fw_probe_rays: the positions of the probes asked for go to scratch of the call's own; device output — one launch into the caller's
+// memory; host output — slabs of probes through the same scratch
+int probe_rays_impl(const fw_probe_set *s, int device, uint32_t round, uint32_t first_probe, uint32_t n, float *rays, int on_device, void *stream_) {
+    if (!s || !rays) return fail(FW_ERR_BAD_ARG, "null argument");
+    bool too_large = false;
+    if (int rc = probe_set_check(s, too_large)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if ((uint64_t)first_probe + n > s->n_probes) return fail(FW_ERR_BAD_ARG, "first_probe + n exceeds n_probes");
+    if (on_device && ((uintptr_t)rays & 3u)) return fail(FW_ERR_BAD_ARG, "rays must be 4-byte aligned");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t D = s->directions;
+    const size_t pos_bytes = align256((size_t)n * 12);
+    const uint32_t per = on_device ? 0u : (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, PROBE_SCRATCH_BYTES / (D * 24)));
+    CallScratch scratch(device);
+    if (int rc = scratch.alloc(pos_bytes + (size_t)per * D * 24)) return rc;
+    const float *d_pos = (const float *)scratch.p;
+    HIPCHK(hipMemcpyAsync(scratch.p, s->positions + (size_t)first_probe * 3, (size_t)n * 12, hipMemcpyHostToDevice, stream));
+    if (on_device) {
+        fw::launch_probe_rays(stream, device_cus(device), probes_device(s, round, first_probe, d_pos), n, rays);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+    float *d_rays = (float *)((uint8_t *)scratch.p + pos_bytes);
+    for (uint32_t done = 0; done < n; done += per) {
+        const uint32_t k = std::min(per, n - done);
+        fw::launch_probe_rays(stream, device_cus(device), probes_device(s, round, first_probe + done, d_pos + (size_t)done * 3), k, d_rays);
+        HIPCHK(hipMemcpyAsync(rays + (size_t)done * D * 6, d_rays, (size_t)k * D * 24, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_probe_project: with host arrays one device allocation per call holds the inputs and the sums, released on every way out; with
+// device arrays the kernel works on the caller's memory and nothing is allocated
+int probe_project_impl(int device, uint32_t n_probes, uint32_t directions, uint32_t samples, const float *rays, const float *accum, float *sums,
+                       int on_device, void *stream_) {
+    if (!rays || !accum || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (n_probes == 0) return fail(FW_ERR_BAD_ARG, "n_probes must be > 0");
+    if (directions == 0 || directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (samples == 0 || samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^24");
+    if (on_device && (((uintptr_t)accum & 15u) || (((uintptr_t)rays | (uintptr_t)sums) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device accum must be 16-byte aligned, device rays and sums 4-byte aligned");
+    if ((uint64_t)n_probes * directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    HIPCHK(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n = (size_t)n_probes * directions, sum_bytes = (size_t)n_probes * 108;
+    CallScratch scratch(device);
+    const float *d_rays = rays, *d_acc = accum; float *d_sums = sums;
+    if (!on_device) {
+        const size_t o_acc = align256(n * 24), o_sums = o_acc + align256(n * 16);
+        if (int rc = scratch.alloc(o_sums + sum_bytes)) return rc;
+        uint8_t *base = (uint8_t *)scratch.p;
+        HIPCHK(hipMemcpyAsync(base, rays, n * 24, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_acc, accum, n * 16, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
+        d_rays = (const float *)base; d_acc = (const float *)(base + o_acc); d_sums = (float *)(base + o_sums);
+    }
+    fw::launch_probe_project(stream, device_cus(device), n_probes, directions, samples, d_rays, d_acc, d_sums);
+    if (!on_device) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+struct ProbeEvents { hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr}; ~ProbeEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } };
+
+// fw_bake_probes: per round and chunk of probes, k_probe_rays into the call's scratch, render_impl over those device rays into a zeroed
+// accum of the scratch — the fw_render_rays call of the chunk (rays_impl's frame) — then k_probe_project into the running sums.
+int bake_probes_impl(fw_scene *sc, const fw_probe_set *s, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, float *sums,
+                     float *sh, fw_stats *stats) {
+    if (!sc || !s || !rp) return fail(FW_ERR_BAD_ARG, "null argument");
+    bool too_large = false;
+    if (int rc = probe_set_check(s, too_large)) return rc;
+    if (rounds == 0) return fail(FW_ERR_BAD_ARG, "rounds must be > 0");
+    if ((uint64_t)first_round + rounds > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_round + rounds overflows");
+    if (rp->samples == 0 || rp->samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^24");
+    if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
+    if (rp->on_device && (((uintptr_t)sums | (uintptr_t)sh) & 3u)) return fail(FW_ERR_BAD_ARG, "device sums and sh must be 4-byte aligned");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)rp->stream;
+    const uint32_t N = s->n_probes, D = s->directions, S = rp->samples;
+    const uint32_t chunk = std::min<uint32_t>(N, s->chunk_probes ? s->chunk_probes : (uint32_t)std::max<uint64_t>(1, PROBE_SCRATCH_BYTES / ((uint64_t)D * 40)));
+    const size_t sum_bytes = (size_t)N * 108;
+    const bool own_sums = !rp->on_device || !sums;        // the running sums live in the scratch: a host caller's, or nobody's
+    const size_t o_rays = align256((size_t)N * 12), o_acc = o_rays + align256((size_t)chunk * D * 24),
+                 o_sums = o_acc + align256((size_t)chunk * D * 16);
+    CallScratch scratch(dev);
+    if (int rc = scratch.alloc(o_sums + (own_sums ? sum_bytes : 0))) return rc;
+    uint8_t *base = (uint8_t *)scratch.p;
+    const float *d_pos = (const float *)base;
+    float *d_rays = (float *)(base + o_rays), *d_acc = (float *)(base + o_acc), *d_sums = own_sums ? (float *)(base + o_sums) : sums;
+    HIPCHK(hipMemcpyAsync(base, s->positions, (size_t)N * 12, hipMemcpyHostToDevice, stream));
+    if (own_sums) {
+        if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
+        else HIPCHK(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
+    }
+    ProbeEvents ev;                                   // around the two kernels' launches, only when the caller reads stats
+    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
+    const int n_cus = device_cus(dev);
+    const bool timing = (rp->flags & FW_FLAG_TIME_KERNELS) != 0;
+
+    fw_stats total{};
+    for (uint32_t r = first_round; r - first_round < rounds; r++) {
+        fw_render_rays_params q = *rp;
+        q.gamma = 1.f; q.on_device = 1; q.seed = rp->seed + r;
+        for (uint32_t p0 = 0; p0 < N; p0 += chunk) {
+            const uint32_t k = std::min(chunk, N - p0), n = k * D;
+            q.n_rays = n;
+            if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
+            fw::launch_probe_rays(stream, n_cus, probes_device(s, r, p0, d_pos + (size_t)p0 * 3), k, d_rays);
+            if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
+            HIPCHK(hipMemsetAsync(d_acc, 0, (size_t)n * 16, stream));
+            const fw_render_params P = rays_frame(&q, S);
+            const RayInput ri{d_rays, n, false, nullptr, p0 * D, true};
+            fw_stats gs{};
+            if (int rc = render_impl(sc, &P, nullptr, nullptr, nullptr, stats ? &gs : nullptr, 0, d_acc, nullptr, nullptr, &ri)) return rc;
+            if (stats) HIPCHK(hipEventRecord(ev.e[2], stream));
+            fw::launch_probe_project(stream, n_cus, k, D, S, d_rays, d_acc, d_sums + (size_t)p0 * 27);
+            if (!stats) continue;
+            HIPCHK(hipEventRecord(ev.e[3], stream));
+            HIPCHK(hipEventSynchronize(ev.e[3]));
+            float gen_ms = 0.f, proj_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
+            HIPCHK(hipEventElapsedTime(&proj_ms, ev.e[2], ev.e[3]));
+            total.samples += gs.samples; total.rays += gs.rays;
+            for (int d = 0; d < FW_MAX_SEGMENTS; d++) total.rays_per_depth[d] += gs.rays_per_depth[d];
+            total.algorithmic_bytes += gs.algorithmic_bytes;
+            total.ms_render += gs.ms_render + gen_ms + proj_ms; total.ms_raygen += gs.ms_raygen + (timing ? gen_ms : 0.f);
+            total.ms_extend += gs.ms_extend; total.ms_shade += gs.ms_shade; total.ms_accumulate += gs.ms_accumulate + (timing ? proj_ms : 0.f);
+            total.ms_d2h += gs.ms_d2h;
+            total.n_extend_launches += gs.n_extend_launches; total.n_shade_launches += gs.n_shade_launches; total.n_batches += gs.n_batches;
+            total.tlas_nodes = gs.tlas_nodes; total.blas_nodes = gs.blas_nodes; total.reserved = gs.reserved;
+            total.bytes_raygen += gs.bytes_raygen + (uint64_t)n * 24;                        // (the generator's stores)
+            total.bytes_extend += gs.bytes_extend; total.bytes_shade += gs.bytes_shade;
+            total.bytes_accumulate += gs.bytes_accumulate + (uint64_t)n * 40 + (uint64_t)k * 216;    // (the projection's loads and its sums)
+            total.deposits += gs.deposits; total.parked_rays += gs.parked_rays;
+        }
+    }
+    // the outputs: sums where the caller keeps them, and sh = sums / rounds so far, divided on the host in double and rounded once
+    std::vector<float> host;
+    const float *h_sums = sums;
+    if (!rp->on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+    else if (sh) { host.resize((size_t)N * 27); h_sums = host.data(); HIPCHK(hipMemcpyAsync(host.data(), d_sums, sum_bytes, hipMemcpyDeviceToHost, stream)); }
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    if (sh) {
+        const double n_rounds = (double)((uint64_t)first_round + rounds);
+        std::vector<float> tmp;
+        float *out = sh;
+        if (rp->on_device) { tmp.resize((size_t)N * 27); out = tmp.data(); }
+        for (size_t i = 0; i < (size_t)N * 27; i++) out[i] = (float)((double)h_sums[i] / n_rounds);
+        if (rp->on_device) {
+            HIPCHK(hipMemcpyAsync(sh, tmp.data(), sum_bytes, hipMemcpyHostToDevice, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+    }
+    if (stats) {
+        *stats = total;
+        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FW_OK;
+}
+
 } // namespace
 
 // =========================================================================================================
@@ -4219,6 +4423,26 @@ int fw_render_model_aovs(fw_scene *scene, const fw_camera_model *model, const fw
     try { return model_aovs_impl(scene, model, params, aov, stats); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_render_model_aovs"); }
+}
+
+int fw_probe_rays(const fw_probe_set *set, int device, uint32_t round, uint32_t first_probe, uint32_t n, float *rays, int on_device, void *stream) {
+    try { return probe_rays_impl(set, device, round, first_probe, n, rays, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_rays"); }
+}
+
+int fw_probe_project(int device, uint32_t n_probes, uint32_t directions, uint32_t samples, const float *rays, const float *accum, float *sums,
+                     int on_device, void *stream) {
+    try { return probe_project_impl(device, n_probes, directions, samples, rays, accum, sums, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_project"); }
+}
+
+int fw_bake_probes(fw_scene *scene, const fw_probe_set *set, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, float *sums,
+                   float *sh, fw_stats *stats) {
+    try { return bake_probes_impl(scene, set, rp, first_round, rounds, sums, sh, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_probes"); }
 }
 
 int fw_denoise(const fw_denoise_params *p, const float *color, const float *aov, const float *moments, float *linear_rgb, float *gamma_rgb,

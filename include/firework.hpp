@@ -217,6 +217,31 @@ struct CameraModel {
         return r; }
 };
 
+// Irradiance probes (fw_probe_set; not in the reference): positions with `directions` rays each and round, baked by Renderer::bake_probes into
+// nine SH coefficients (l <= 2) per probe and colour channel.  grid(): nx x ny x nz probes from corner lo to corner hi, both included (a
+// count of 1 sits at the middle), x fastest, then y, then z.
+struct ProbeSet {
+    std::vector<float> positions;       // n x 3
+    uint32_t directions = 256, chunk = 0; uint64_t seed_ = 0; bool jitter_ = true;
+    static ProbeSet new_(const std::vector<Vec3> &at, uint32_t directions = 256) {
+        ProbeSet r; r.directions = directions;
+        for (const Vec3 &v : at) { r.positions.push_back(v.x); r.positions.push_back(v.y); r.positions.push_back(v.z); }
+        return r; }
+    static ProbeSet grid(Vec3 lo, Vec3 hi, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t directions = 256) {
+        ProbeSet r; r.directions = directions;
+        auto at = [](float a, float b, uint32_t i, uint32_t n) { return n > 1 ? (float)((double)a + ((double)b - (double)a) * (double)i / (double)(n - 1)) : (float)(0.5 * ((double)a + (double)b)); };
+        for (uint32_t z = 0; z < nz; z++) for (uint32_t y = 0; y < ny; y++) for (uint32_t x = 0; x < nx; x++) {
+            r.positions.push_back(at(lo.x, hi.x, x, nx)); r.positions.push_back(at(lo.y, hi.y, y, ny)); r.positions.push_back(at(lo.z, hi.z, z, nz)); }
+        return r; }
+    size_t n_probes() const { return positions.size() / 3; }
+    ProbeSet seed(uint64_t s) && { seed_ = s; return std::move(*this); }
+    ProbeSet jitter(bool on) && { jitter_ = on; return std::move(*this); }
+    ProbeSet chunk_probes(uint32_t n) && { chunk = n; return std::move(*this); }
+    fw_probe_set abi() const {
+        fw_probe_set s{}; s.n_probes = (uint32_t)n_probes(); s.positions = positions.data(); s.directions = directions; s.jitter = jitter_ ? 1 : 0;
+        s.seed = seed_; s.chunk_probes = chunk; return s; }
+};
+
 // Lowers a Scene to the flat arrays of fw_scene_desc (owning storage for the duration of a render call).
 class Lowered {
   public:
@@ -403,6 +428,28 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
         fw_scene_destroy(sc);
         if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
         return buffer; }
+
+    // Irradiance probes baked on the device (not in the reference; fw_bake_probes): `rounds` rounds of the set's rays, samples() paths per
+    // direction and round, with this renderer's seed, use_bvh and flags (its camera, size and gamma are not used).  Returns sh, n x 9 x 3
+    // floats: the mean of the rounds' projections; sums (optional, n x 9 x 3) receives the running sums.
+    std::vector<float> bake_probes(const Scene &scene, const ProbeSet &probes, uint32_t rounds = 1, std::vector<float> *sums = nullptr,
+                                   fw_stats *stats = nullptr) const {
+        if (probes.n_probes() >= (1ull << 32))
+            throw std::runtime_error(std::string(fw_strerror(FW_ERR_UNSUPPORTED)) + " | n_probes x directions must be below 2^31");
+        Lowered low(scene);
+        fw_scene *sc = nullptr;
+        int rc = create_resident(scene, &low.desc, device_, &sc);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        const fw_render_params p = params();
+        fw_render_rays_params rp{};
+        rp.samples = p.samples; rp.seed = p.seed; rp.use_bvh = p.use_bvh; rp.gamma = p.gamma; rp.flags = p.flags;
+        const fw_probe_set set = probes.abi();
+        std::vector<float> sh(probes.n_probes() * 27), acc(probes.n_probes() * 27, 0.f);
+        rc = fw_bake_probes(sc, &set, &rp, 0, rounds, acc.data(), sh.data(), stats);
+        fw_scene_destroy(sc);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        if (sums) *sums = std::move(acc);
+        return sh; }
 
     // A denoised frame (not in the reference): samples() samples per pixel filtered by fw_denoise with `iterations` a-trous steps, guided by
     // fw_render_aovs at aov_samples samples.  The frame comes from fw_render_adaptive with min_samples = samples() (one round at the fixed

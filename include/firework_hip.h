@@ -735,6 +735,73 @@ int fw_render_model(fw_scene *scene, const fw_camera_model *model, const fw_rend
    outside 1..2^24, with outputs_on_device an aov not 16-byte aligned; FW_ERR_UNSUPPORTED for W x H >= 2^31; FW_ERR_NO_DEVICE. */
 int fw_render_model_aovs(fw_scene *scene, const fw_camera_model *model, const fw_render_params *params, float *aov, fw_stats *stats);
 
+/* ---- irradiance probes baked on the device (additive at ABI 8) -----------------------------------------------------
+   A probe set is n_probes positions with D directions each.  Its rays are generated on the device (k_probe_rays) in the layout
+   fw_render_rays reads, and the rendered sums are reduced on the device (k_probe_project) to nine real spherical-harmonics
+   coefficients (l <= 2) per probe and colour channel: neither rays nor radiance leave the device.
+   Rays: entry i = p * D + j is direction j of probe p.  Its origin is positions[p] bit for bit.  Its direction in round r is a
+   spherical Fibonacci lattice with a Cranley-Patterson shift (xi_u, xi_v) per (round, probe): fw_model_rays' hash with sample -> round
+   and pixel -> probe,
+       key = hash32(s32 ^ hash32(r + 0x9E3779B9)),  xi_u = (hash32(hash32(2 p) ^ key) >> 8) * 2^-24,  xi_v likewise from 2 p + 1
+   (api.pixel_jitter(seed, r, n_probes)[p] in Python); jitter == 0: (1/2, 1/2).  Evaluated in float64 in this order and rounded to
+   float32 once:
+       u = (j + xi_u) / D;  c = 1 - 2 u;  rad = sqrt(max(0, 1 - c c));  t = j g + xi_v with g = (sqrt(5) - 1) / 2;  v = t - floor(t);
+       phi = 2 pi v;  d = (rad cos phi, c, rad sin phi)                       (polar axis on world y)
+   The directions are uniform on the sphere (density 1 / 4 pi).  api.ProbeSet.rays(round) is the numpy float64 statement.
+   Basis: real orthonormal SH, index k = l (l + 1) + m, of the unit direction (x, y, z), constants formed in double:
+       Y0 = 1/2 sqrt(1/pi)   Y1 = sqrt(3/4pi) y   Y2 = sqrt(3/4pi) z   Y3 = sqrt(3/4pi) x   Y4 = 1/2 sqrt(15/pi) x y
+       Y5 = 1/2 sqrt(15/pi) y z   Y6 = 1/4 sqrt(5/pi) (3 z z - 1)   Y7 = 1/2 sqrt(15/pi) x z   Y8 = 1/4 sqrt(15/pi) (x x - y y) */
+typedef struct fw_probe_set {
+    uint32_t n_probes;
+    const float *positions;   /* n_probes x 3, host memory always */
+    uint32_t directions;      /* D: rays per probe and round, 1 .. 2^20 */
+    int32_t  jitter;          /* 0: every round uses the shift (1/2, 1/2) */
+    uint64_t seed;            /* of the shifts */
+    uint32_t chunk_probes;    /* fw_bake_probes: probes rendered at a time; 0 = as many as fit 256 MiB of rays + sums, at least 1 */
+} fw_probe_set;
+
+/* fw_probe_rays: the rays of round `round` of the probes [first_probe, first_probe + n): n x D x 6 floats (origin, direction).
+   `rays` is host memory, or with on_device device memory on `device`, written on `stream` and complete on return (fw_model_rays'
+   contract).  Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL set, positions or rays, n_probes == 0,
+   directions outside 1..2^20, a non-finite position (its index is in fw_last_error()), n == 0, first_probe + n > n_probes, with
+   on_device rays not 4-byte aligned; FW_ERR_UNSUPPORTED for n_probes x D >= 2^31; then FW_ERR_NO_DEVICE without a GPU, and
+   FW_ERR_BAD_ARG for a device index out of range. */
+int fw_probe_rays(const fw_probe_set *set, int device, uint32_t round, uint32_t first_probe, uint32_t n, float *rays, int on_device, void *stream);
+
+/* fw_probe_project: adds one round's projection to the running sums.  rays: n_probes x D x 6 floats (the float32 directions are used as
+   stored); accum: n_probes x D x 4 floats, fw_render_progressive's layout (r, g, b sums of `samples` samples, then segments); sums:
+   n_probes x 9 x 3 floats.  For probe p, coefficient k and channel c, in float64,
+       proj[p][k][c] = (4 pi / D) * sum_j Y_k(d_pj) * (double)accum[p D + j].c / samples
+   is rounded to float32 once and added to sums[p][k][c] with one float32 addition.  One wave per probe: lane l accumulates
+   j = l, l + 64, ... in ascending order, and the 64 lanes are combined by a fixed tree; no atomics: the result is a pure function of
+   the inputs.  Host arrays, or with on_device device arrays on `device` (the kernel then works on the caller's memory), launched on
+   `stream` and complete on return.  Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL rays, accum or sums,
+   n_probes == 0, directions outside 1..2^20, samples outside 1..2^24, with on_device an accum that is not 16-byte aligned or rays or
+   sums not 4-byte aligned; FW_ERR_UNSUPPORTED for n_probes x D >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index
+   out of range. */
+int fw_probe_project(int device, uint32_t n_probes, uint32_t directions, uint32_t samples, const float *rays, const float *accum, float *sums, int on_device, void *stream);
+
+/* fw_bake_probes: the rounds [first_round, first_round + rounds) of a probe set against a resident scene.  Of rp, samples (S per
+   round), seed, use_bvh, paths_per_batch, flags, on_device (for sums and sh) and stream are read; n_rays, first_sample,
+   per_sample_rays, keys, key_base and gamma are ignored.  For each round r and each chunk of probes [p0, p1) (set->chunk_probes at a
+   time): k_probe_rays fills device scratch that the call allocates and frees on every path; a zeroed accum is rendered exactly as
+   fw_render_rays would with per_sample_rays = 0, first_sample = 0, samples = S, key_base = p0 D, keys = NULL and seed = rp->seed + r;
+   k_probe_project adds the chunk into sums.
+     sums: n_probes x 9 x 3 floats, the running sums of the rounds [0, first_round) — all zeros when first_round is 0 — to which this
+           call's rounds are added in order; NULL only when first_round == 0 (the sums then start from zero and are not returned).
+     sh  : the same shape, float(sums / (double)(first_round + rounds)); may be NULL.
+   Contracts.  Composition: for every chunk_probes, sums equals bit for bit what fw_probe_rays, fw_render_rays and fw_probe_project
+   give when chained by hand on the device over the whole set.  Progressive: k calls of n rounds leave the sums and sh of one call of
+   k n rounds, bit for bit.  The frames are fw_render_rays' own, so point, spot and directional lights and the light-sampling flags
+   are honoured.
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, set or rp, what
+   fw_probe_rays rejects in the set, rounds == 0, first_round + rounds >= 2^32, samples outside 1..2^24, a NULL sums with
+   first_round > 0, with on_device sums or sh not 4-byte aligned; FW_ERR_UNSUPPORTED for n_probes x D >= 2^31; then FW_ERR_NO_DEVICE.
+   stats: fw_render_rays' fields summed over rounds and chunks as fw_render_model sums them; ms_render includes the two kernels'
+   launches (under FW_FLAG_TIME_KERNELS ms_raygen and ms_accumulate as well); ms_wall covers the whole call.  Synchronisation and the
+   frame graph are fw_render_rays'. */
+int fw_bake_probes(fw_scene *scene, const fw_probe_set *set, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, float *sums, float *sh, fw_stats *stats);
+
 /* Diagnostic: the kernels' division / square-root helpers against the compiler's IEEE expansion, bit for bit,
    on n hashed operand pairs.  mode 0 = magnitudes 2^-40..2^40 (must be 0 mismatches), mode 1 = all bit patterns. */
 int fw_selftest_arith(int device, uint32_t n, uint32_t seed, int mode, uint64_t *div_mismatches, uint64_t *sqrt_mismatches);
