@@ -28,7 +28,11 @@ the image diagonal, default 180; combines as the other models do).  The three mo
 (no image: a grid of irradiance probes between the two corners, D directions each, default 256, R rounds of -s samples per direction,
 default 1, baked on the device into nine SH coefficients per probe and channel, fw_bake_probes; -o names an .npz with
 positions, sh, sums, rounds, directions and samples; --light-sampling, --env-sampling and --all-emitters apply; not with --camera /
---denoise / --orbit / --adaptive / --progressive / --checkpoint / --temporal)."""
+--denoise / --orbit / --adaptive / --progressive / --checkpoint / --temporal).  --bake-lightmap OBJECT,W,H [--lightmap-dirs D]
+[--lightmap-rounds R] [--lightmap-dilate N] (no image: the irradiance over the W x H UV texels of render object OBJECT, which must be
+a triangle mesh with uvs, D cosine-weighted directions per texel, default 64, R rounds of -s samples per direction, default 1, N
+dilation passes over the seams, default 2, baked on the device, fw_bake_lightmap; -o names an .npz with irradiance,
+sums, owner, rounds, directions and samples; the sampling flags apply; refuses what --bake-probes refuses, and --bake-probes)."""
 import argparse
 import sys
 import time
@@ -79,7 +83,33 @@ def main(argv=None):
     ap.add_argument("--probe-max", default=None, metavar="X,Y,Z", help="with --bake-probes: the grid's last corner")
     ap.add_argument("--probe-dirs", type=int, default=None, metavar="D", help="with --bake-probes: directions per probe and round (default 256)")
     ap.add_argument("--probe-rounds", type=int, default=None, metavar="R", help="with --bake-probes: rounds of -s samples per direction (default 1)")
+    ap.add_argument("--bake-lightmap", default=None, metavar="OBJECT,W,H",
+                    help="bake the irradiance over the W x H UV texels of render object OBJECT (a mesh with uvs) into the .npz named by -o")
+    ap.add_argument("--lightmap-dirs", type=int, default=None, metavar="D", help="with --bake-lightmap: directions per texel and round (default 64)")
+    ap.add_argument("--lightmap-rounds", type=int, default=None, metavar="R", help="with --bake-lightmap: rounds of -s samples per direction (default 1)")
+    ap.add_argument("--lightmap-dilate", type=int, default=None, metavar="N", help="with --bake-lightmap: dilation passes over the seams, 0..64 (default 2)")
     opt = ap.parse_args(argv)
+    if opt.bake_lightmap is not None:
+        if (opt.bake_probes is not None or opt.camera != "pinhole" or opt.denoise is not None or opt.orbit or opt.adaptive is not None
+                or opt.progressive > 0 or opt.checkpoint or opt.temporal is not None):
+            ap.error("--bake-lightmap cannot be combined with --bake-probes, --camera, --denoise, --orbit, --adaptive, --progressive, "
+                     "--checkpoint or --temporal")
+        try:
+            lm_args = [int(x) for x in opt.bake_lightmap.split(",")]
+        except ValueError:
+            lm_args = []
+        if len(lm_args) != 3 or lm_args[0] < 0 or not all(1 <= x <= 16384 for x in lm_args[1:]):
+            ap.error("--bake-lightmap needs OBJECT,W,H: an object index >= 0 and a size of 1..16384 each way")
+        if opt.lightmap_dirs is not None and not 1 <= opt.lightmap_dirs <= 1 << 20:
+            ap.error("--lightmap-dirs D needs 1 <= D <= 2^20")
+        if opt.lightmap_rounds is not None and opt.lightmap_rounds < 1:
+            ap.error("--lightmap-rounds R needs R >= 1")
+        if opt.lightmap_dilate is not None and not 0 <= opt.lightmap_dilate <= 64:
+            ap.error("--lightmap-dilate N needs 0 <= N <= 64")
+        if not opt.output:
+            ap.error("--bake-lightmap needs -o FILE.npz")
+    elif opt.lightmap_dirs is not None or opt.lightmap_rounds is not None or opt.lightmap_dilate is not None:
+        ap.error("--lightmap-dirs, --lightmap-rounds and --lightmap-dilate need --bake-lightmap")
     if opt.bake_probes is not None:
         if (opt.camera != "pinhole" or opt.denoise is not None or opt.orbit or opt.adaptive is not None or opt.progressive > 0 or opt.checkpoint
                 or opt.temporal is not None):
@@ -151,9 +181,20 @@ def main(argv=None):
     from .api import CameraSettings, Renderer, save_image
     from .yaml_io import load_scene
 
+    scene = lightmap = None
+    if opt.bake_lightmap is not None:      # the object is looked at before the device is: a wrong one is a message, not a traceback
+        from .api import Lightmap
+        scene = load_scene(opt.scene_file)
+        try:
+            lightmap = Lightmap.of(scene, lm_args[0], lm_args[1], lm_args[2], 64 if opt.lightmap_dirs is None else opt.lightmap_dirs).seed(opt.seed)
+        except ValueError as e:
+            print(f"firework: error: --bake-lightmap: {e}", file=sys.stderr)
+            return 2
+
     _lib.init(opt.device)      # fw_init: context, code objects and the path arena before the timed region, like the loading of the reference's binary (main.rs:40)
 
-    scene = load_scene(opt.scene_file)
+    if scene is None:
+        scene = load_scene(opt.scene_file)
     camera = CameraSettings.default().cam_pos((0.0, 30.0, 50.0)).look_at((0.0, 0.0, 0.0)).field_of_view(40.0)
     renderer = (Renderer.default().width(opt.width).height(opt.height).samples(opt.samples).use_bvh(True)
                 .camera(camera).seed(opt.seed).light_sampling(opt.light_sampling).env_sampling(opt.env_sampling))
@@ -170,6 +211,17 @@ def main(argv=None):
         print(f'Saving {probes.n_probes} probes to "{opt.output}"')
         with open(opt.output, "wb") as f:       # (np.savez would append .npz to a name without it)
             np.savez(f, positions=probes.positions, sh=sh, sums=sums, rounds=np.int64(rounds), directions=np.int64(probes.directions),
+                     samples=np.int64(opt.samples))
+        return 0
+    if lightmap is not None:
+        import numpy as np
+        rounds = 1 if opt.lightmap_rounds is None else opt.lightmap_rounds
+        irradiance, sums = renderer.bake_lightmap(scene, lightmap, rounds, 2 if opt.lightmap_dilate is None else opt.lightmap_dilate, device=opt.device)
+        owner = _lib.lightmap_texels(lightmap, opt.device)[1].reshape(lightmap.height, lightmap.width)
+        print(f"Finished Baking in {int(time.time() - start)} s")
+        print(f'Saving a {lightmap.width} x {lightmap.height} lightmap to "{opt.output}"')
+        with open(opt.output, "wb") as f:       # (np.savez would append .npz to a name without it)
+            np.savez(f, irradiance=irradiance, sums=sums, owner=owner, rounds=np.int64(rounds), directions=np.int64(lightmap.directions),
                      samples=np.int64(opt.samples))
         return 0
     if opt.camera != "pinhole":

@@ -173,5 +173,13 @@ class fw_probe_set(C.Structure):
     _fields_ = [("n_probes", u32), ("positions", C.POINTER(f32)), ("directions", u32), ("jitter", i32), ("seed", u64), ("chunk_probes", u32)]
 
 
+# lightmaps on the device (include/firework_hip.h: fw_lightmap_texels, fw_lightmap_rays, fw_lightmap_reduce, fw_lightmap_dilate,
+# fw_bake_lightmap)
+class fw_lightmap(C.Structure):
+    _fields_ = [("verts", C.POINTER(f32)), ("n_verts", u32), ("indices", C.POINTER(u32)), ("n_indices", u32), ("normals", C.POINTER(f32)),
+                ("uvs", C.POINTER(f32)), ("position", fw_vec3), ("rotation", fw_rotor3), ("flip_normals", i32), ("width", u32), ("height", u32),
+                ("directions", u32), ("jitter", i32), ("seed", u64), ("bias", f32), ("flip", i32), ("chunk_texels", u32)]
+
+
 def vec3(v):
     return fw_vec3(float(v[0]), float(v[1]), float(v[2]))

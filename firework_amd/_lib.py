@@ -123,6 +123,18 @@ def load(preload=False, device=None):
     lib.fw_bake_probes.restype = C.c_int
     lib.fw_bake_probes.argtypes = [C.c_void_p, C.POINTER(A.fw_probe_set), C.POINTER(A.fw_render_rays_params), C.c_uint32, C.c_uint32, C.c_void_p,
                                    C.c_void_p, C.POINTER(A.fw_stats)]
+    lib.fw_lightmap_texels.restype = C.c_int
+    lib.fw_lightmap_texels.argtypes = [C.POINTER(A.fw_lightmap), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_void_p]
+    lib.fw_lightmap_rays.restype = C.c_int
+    lib.fw_lightmap_rays.argtypes = [C.POINTER(A.fw_lightmap), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+    lib.fw_lightmap_reduce.restype = C.c_int
+    lib.fw_lightmap_reduce.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                       C.c_void_p]
+    lib.fw_lightmap_dilate.restype = C.c_int
+    lib.fw_lightmap_dilate.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+    lib.fw_bake_lightmap.restype = C.c_int
+    lib.fw_bake_lightmap.argtypes = [C.c_void_p, C.POINTER(A.fw_lightmap), C.POINTER(A.fw_render_rays_params), C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_void_p, C.c_void_p, C.POINTER(A.fw_stats)]
     lib.fw_denoise.restype = C.c_int
     lib.fw_denoise.argtypes = [C.POINTER(A.fw_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fw_temporal.restype = C.c_int
@@ -463,6 +475,123 @@ def probe_project(rays, accum, samples, directions, sums=None, device=0, stream=
     return sums
 
 
+def _lightmap_abi(lightmap, chunk=None):
+    """(fw_lightmap, the arrays it points into) from an api.Lightmap, with chunk_texels = chunk when given"""
+    s, keep = lightmap.to_abi()
+    if chunk is not None:
+        s.chunk_texels = int(chunk)
+    return s, keep
+
+
+def _stream_arg(stream, torch_device):
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(torch_device).cuda_stream
+    return C.c_void_p(stream) if stream else None
+
+
+def lightmap_texels(lightmap, device=0, on_device=False, stream=None):
+    """fw_lightmap_texels: (records (W * H, 8) float32, owner (W * H,) uint32 — int32 bits on the device — and the number of covered
+    texels) of an api.Lightmap, rasterised on the device.  numpy arrays, or with on_device=True torch tensors on cuda:`device`, written on
+    `stream` (default: the current torch stream)."""
+    lib = load()
+    s, _keep = _lightmap_abi(lightmap)
+    n = int(s.width) * int(s.height)
+    count = C.c_uint32(0)
+    if on_device:
+        import torch
+        dev = torch.device("cuda", int(device))
+        rec = torch.full((n, 8), float("nan"), dtype=torch.float32, device=dev)
+        own = torch.zeros((n,), dtype=torch.int32, device=dev)
+        _check(lib, lib.fw_lightmap_texels(C.byref(s), int(device), rec.data_ptr(), own.data_ptr(), C.byref(count), 1, _stream_arg(stream, dev)))
+        return rec, own, int(count.value)
+    rec = np.full((n, 8), np.nan, np.float32)
+    own = np.zeros((n,), np.uint32)
+    _check(lib, lib.fw_lightmap_texels(C.byref(s), int(device), rec.ctypes.data, own.ctypes.data, C.byref(count), 0, None))
+    return rec, own, int(count.value)
+
+
+def lightmap_covered(lightmap, device=0):
+    """the number of covered texels of an api.Lightmap (fw_lightmap_texels with no arrays)"""
+    lib = load()
+    s, _keep = _lightmap_abi(lightmap)
+    count = C.c_uint32(0)
+    _check(lib, lib.fw_lightmap_texels(C.byref(s), int(device), None, None, C.byref(count), 0, None))
+    return int(count.value)
+
+
+def lightmap_rays(lightmap, round=0, first=0, n=None, device=0, out=None, stream=None):
+    """fw_lightmap_rays: the rays of round `round` of the entries [first, first + n) of an api.Lightmap's covered list (n None: to the
+    last one), generated on the device: (n * D, 6) float32 origin + direction, entry q * D + j = direction j of covered texel q.  Returns
+    a numpy array; out: a contiguous float32 device tensor of that shape on cuda:`device` to fill instead, on `stream` (default: the
+    current torch stream); returned."""
+    lib = load()
+    s, _keep = _lightmap_abi(lightmap)
+    if n is None:
+        n = (int(out.shape[0]) // int(s.directions)) if out is not None else lightmap_covered(lightmap, device) - int(first)
+    shape = (int(n) * int(s.directions), 6)
+    if out is not None:
+        import torch
+        _check_device_tensor(out, shape, torch.float32, device, "out")
+        _check(lib, lib.fw_lightmap_rays(C.byref(s), int(device), int(round), int(first), int(n), out.data_ptr(), 1, _stream_arg(stream, out.device)))
+        return out
+    rays = np.empty(shape, np.float32)
+    _check(lib, lib.fw_lightmap_rays(C.byref(s), int(device), int(round), int(first), int(n), rays.ctypes.data, 0, None))
+    return rays
+
+
+def lightmap_reduce(accum, samples, directions, sums, texel_ids=None, device=0, stream=None):
+    """fw_lightmap_reduce: adds (pi / D) sum_j accum[q D + j] / samples, rounded to float32 once, to sums[texel_ids[q]] (texel_ids None:
+    sums[q]).  accum (n * D, 4) float32; sums (n_texels, 4) or (H, W, 4) float32, updated in place (.w untouched); texel_ids n distinct
+    ids (uint32 numpy / int32 torch).  numpy arrays, or contiguous torch tensors on cuda:`device`, reduced on `stream` (default: the
+    current torch stream) where they lie.  Returns sums."""
+    lib = load()
+    d = int(directions)
+    total = int(accum.shape[0])
+    if d < 1 or total % d or tuple(accum.shape) != (total, 4):
+        raise ValueError(f"accum must have shape (n * {d}, 4)")
+    n = total // d
+    if sums.shape[-1] != 4:
+        raise ValueError("sums must have shape (n_texels, 4) or (H, W, 4)")
+    n_texels = int(np.prod(sums.shape[:-1]))
+    if texel_ids is not None and tuple(texel_ids.shape) != (n,):
+        raise ValueError(f"texel_ids must have shape ({n},)")
+    if type(accum).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(accum, (total, 4), torch.float32, device, "accum")
+        _check_device_tensor(sums, tuple(sums.shape), torch.float32, device, "sums")
+        if texel_ids is not None:
+            _check_device_tensor(texel_ids, (n,), torch.int32, device, "texel_ids")
+        _check(lib, lib.fw_lightmap_reduce(int(device), n, d, int(samples), texel_ids.data_ptr() if texel_ids is not None else None,
+                                           accum.data_ptr(), sums.data_ptr(), n_texels, 1, _stream_arg(stream, accum.device)))
+        return sums
+    a = np.ascontiguousarray(np.asarray(accum, dtype=np.float32))
+    if not (isinstance(sums, np.ndarray) and sums.dtype == np.float32 and sums.flags["C_CONTIGUOUS"]):
+        raise ValueError("sums must be a contiguous float32 array")
+    ids = None if texel_ids is None else np.ascontiguousarray(np.asarray(texel_ids, dtype=np.uint32))
+    _check(lib, lib.fw_lightmap_reduce(int(device), n, d, int(samples), ids.ctypes.data if ids is not None else None, a.ctypes.data,
+                                       sums.ctypes.data, n_texels, 0, None))
+    return sums
+
+
+def lightmap_dilate(image, passes, device=0, stream=None):
+    """fw_lightmap_dilate: `passes` dilation passes of image (H, W, 4) float32 (rgb, a), in place: a contiguous numpy array, or a
+    contiguous torch tensor on cuda:`device`, dilated on `stream` (default: the current torch stream).  Returns image."""
+    lib = load()
+    if len(image.shape) != 3 or image.shape[2] != 4:
+        raise ValueError("image must have shape (H, W, 4)")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    if type(image).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(image, (h, w, 4), torch.float32, device, "image")
+        _check(lib, lib.fw_lightmap_dilate(int(device), w, h, int(passes), image.data_ptr(), 1, _stream_arg(stream, image.device)))
+        return image
+    if not (isinstance(image, np.ndarray) and image.dtype == np.float32 and image.flags["C_CONTIGUOUS"]):
+        raise ValueError("image must be a contiguous float32 array")
+    _check(lib, lib.fw_lightmap_dilate(int(device), w, h, int(passes), image.ctypes.data, 0, None))
+    return image
+
+
 class DeviceScene:
     """An uploaded scene (`fw_scene*`): SoA scene arrays + TLAS/BLAS resident in HBM."""
 
@@ -770,6 +899,42 @@ class DeviceScene:
         _check(lib, lib.fw_bake_probes(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), sums.ctypes.data, sh.ctypes.data,
                                        C.byref(st)))
         return sh, sums, st.as_dict()
+
+    def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,
+                      flags=0, chunk=None, on_device=False):
+        """fw_bake_lightmap: the rounds [first_round, first_round + rounds) of an api.Lightmap, `samples` paths per direction and round,
+        `chunk` covered texels at a time (None: the lightmap's own setting; 0: automatic).  sums: (H, W, 4) float32 running sums of the
+        rounds before first_round, updated in place (None: zeros, only with first_round 0).  Returns (irradiance, sums, stats): host
+        arrays, or — sums a device tensor on this scene's device, or on_device=True — device tensors, baked on `stream` (default: the
+        current torch stream).  irradiance (H, W, 4): rgb = sums / (first_round + rounds) and a = 1 on covered texels, then `dilate`
+        dilation passes (filled texels carry a = 0.5)."""
+        lib = self._lib
+        s, _keep = _lightmap_abi(lightmap, chunk)
+        shape = (int(s.height), int(s.width), 4)
+        p = A.fw_render_rays_params()
+        p.samples, p.seed, p.use_bvh, p.gamma = int(samples), int(seed), int(bool(use_bvh)), 1.0
+        p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
+        st = A.fw_stats()
+        if on_device or (sums is not None and type(sums).__module__.startswith("torch")):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if sums is None:
+                sums = torch.zeros(shape, dtype=torch.float32, device=dev)
+            _check_device_tensor(sums, shape, torch.float32, self.device, "sums")
+            irr = torch.empty(shape, dtype=torch.float32, device=dev)
+            p.on_device = 1
+            p.stream = _stream_arg(stream, dev)
+            _check(lib, lib.fw_bake_lightmap(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), int(dilate), sums.data_ptr(),
+                                             irr.data_ptr(), C.byref(st)))
+            return irr, sums, st.as_dict()
+        if sums is None:
+            sums = np.zeros(shape, np.float32)
+        if not (isinstance(sums, np.ndarray) and sums.dtype == np.float32 and sums.shape == shape and sums.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"sums must be a contiguous float32 array of shape {shape}")
+        irr = np.empty(shape, np.float32)
+        _check(lib, lib.fw_bake_lightmap(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), int(dilate), sums.ctypes.data,
+                                         irr.ctypes.data, C.byref(st)))
+        return irr, sums, st.as_dict()
 
     def trace(self, rays, use_bvh, seed=0, key_base=0, rays_per_batch=0, time_kernels=False, stats=None):
         """fw_trace_rays: one root.hit(ray, 0.001, 2e9) per ray.  rays: (n, 6) origin + direction.

@@ -1228,6 +1228,257 @@ class ProbeSet:
         return s, self.positions
 
 
+# --------------------------------------------------------------------------- lightmaps (fw_bake_lightmap)
+LIGHTMAP_NO_OWNER = 0xFFFFFFFF          # FW_NO_HIT in an owner map
+
+
+def texel_jitter(seed: int, round: int, ids) -> np.ndarray:
+    """(n, 2) float64 in [0, 1): pixel_jitter's hash with sample -> round and pixel -> the texel ids given (any subset, any order)"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    s32 = ((seed & 0xFFFFFFFF) ^ (((seed >> 32) * 0x9E3779B9) & 0xFFFFFFFF)) & 0xFFFFFFFF
+    key = _hash32(np.array([s32 ^ int(_hash32(np.array([(int(round) + 0x9E3779B9) & 0xFFFFFFFF], np.uint32))[0])], np.uint32))[0]
+    ids = np.asarray(ids, np.uint64).reshape(-1)
+    ctr = np.stack([2 * ids, 2 * ids + 1], axis=1).astype(np.uint32)
+    bits = _hash32(_hash32(ctr) ^ key) >> np.uint32(8)
+    return bits.astype(np.float64) * 2.0 ** -24
+
+
+def rotor_rows(rot: "Rotor3") -> np.ndarray:
+    """(3, 3) float32: the rotation matrix of a rotor as the tracer forms it (ultraviolet's Rotor3::into_matrix, float32, this order)"""
+    s, xy, xz, yz = (F32(v) for v in (rot.s, rot.xy, rot.xz, rot.yz))
+    two = F32(2.0)
+    s2, bxy2, bxz2, byz2 = s * s, xy * xy, xz * xz, yz * yz
+    s_bxy, s_bxz, s_byz = s * xy, s * xz, s * yz
+    bxz_byz, bxy_byz, bxy_bxz = xz * yz, xy * yz, xy * xz
+    c0 = [s2 - bxy2 - bxz2 + byz2, -two * (bxz_byz + s_bxy), two * (bxy_byz - s_bxz)]
+    c1 = [two * (s_bxy - bxz_byz), s2 - bxy2 + bxz2 - byz2, -two * (s_byz + bxy_bxz)]
+    c2 = [two * (s_bxz + bxy_byz), two * (s_byz - bxy_bxz), s2 + bxy2 - bxz2 - byz2]
+    return np.array([[c0[i], c1[i], c2[i]] for i in range(3)], F32)
+
+
+def _edge(au, av, bu, bv, pu, pv):
+    return (bu - au) * (pv - av) - (bv - av) * (pu - au)
+
+
+def lightmap_reduce(accum, samples: int, directions: int) -> np.ndarray:
+    """The float64 statement of fw_lightmap_reduce's projection: (n, 3) with proj[q][c] = (pi / D) sum_j accum[q D + j][c] / samples, for
+    accum (n * D, 4) (r, g, b sums, then segments).  The device rounds it to float32 once and adds it to the texel's running sum."""
+    D = int(directions)
+    a = np.asarray(accum, np.float64).reshape(-1, D, 4)[..., :3] / float(samples)
+    return (np.pi / D) * a.sum(axis=1)
+
+
+_DILATE_ORDER = ((-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1))      # (dy, dx)
+
+
+def lightmap_dilate(image, passes: int) -> np.ndarray:
+    """The float32 statement of fw_lightmap_dilate: image (H, W, 4) (rgb, a).  Per pass a texel with a > 0 is copied; a texel with a == 0
+    whose in-image neighbours, in the order (dy, dx) = (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0), (1,1), include n >= 1 with
+    a > 0 takes their float32 sum in that order divided by float32(n), and a = 0.5; otherwise it is unchanged.  No wrap-around."""
+    img = np.array(image, np.float32)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError("image must have shape (H, W, 4)")
+    h, w = img.shape[:2]
+    for _ in range(int(passes)):
+        pad = np.zeros((h + 2, w + 2, 4), np.float32)
+        pad[1:-1, 1:-1] = img
+        total = np.zeros((h, w, 3), np.float32)
+        count = np.zeros((h, w), np.int64)
+        for dy, dx in _DILATE_ORDER:
+            v = pad[1 + dy:1 + dy + h, 1 + dx:1 + dx + w]
+            on = v[..., 3] > 0
+            total = np.where(on[..., None], total + v[..., :3], total)
+            count += on
+        fill = ~(img[..., 3] > 0) & (count > 0)
+        out = img.copy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[..., :3] = np.where(fill[..., None], total / count.astype(np.float32)[..., None], img[..., :3])
+        out[..., 3] = np.where(fill, np.float32(0.5), img[..., 3])
+        img = out
+    return img
+
+
+class Lightmap:
+    """A lightmap (fw_lightmap): irradiance over the UV texels of one placed TriangleMesh.  Lightmap(mesh, width, height,
+    directions=64), then .placement(render_object) or Lightmap.of(scene, object_index, w, h), and .seed(s) / .jitter(on) / .bias(b) /
+    .flip(on) as builders.  .texels(), .covered() and .rays(round) are the numpy float64 statements of what the device computes;
+    _lib.lightmap_texels / _lib.lightmap_rays the device's own.  Texel (x, y), row 0 at the top, id = y W + x, has its centre at
+    u = (x + 1/2) / W, v = 1 - (y + 1/2) / H: ImageTexture's lookup inverted."""
+
+    def __init__(self, mesh: "TriangleMesh", width: int, height: int, directions: int = 64):
+        if not isinstance(mesh, TriangleMesh):
+            raise ValueError("a lightmap needs a TriangleMesh")
+        if mesh.uvs is None:
+            raise ValueError("a lightmap needs a mesh with uvs")
+        self.mesh = mesh
+        self.width, self.height, self.directions = int(width), int(height), int(directions)
+        self._position = np.zeros(3, F32)
+        self.rotation = Rotor3.identity()
+        self._flip_normals = False
+        self._seed, self._jitter, self._bias, self._flip, self.chunk_texels = 0, True, 1e-3, False, 0
+        self._texels = None
+
+    def placement(self, obj: "RenderObject"):
+        """takes position, rotation and flip_normals from a RenderObject"""
+        self._position, self.rotation, self._flip_normals = _v3(obj._position), obj.rotation, bool(obj._flip_normals)
+        self._texels = None
+        return self
+
+    @staticmethod
+    def of(scene, object_index: int, width: int, height: int, directions: int = 64) -> "Lightmap":
+        """the lightmap of object `object_index` of a Scene, which must be a TriangleMesh with uvs (ValueError otherwise)"""
+        objs = scene.render_objects
+        if not 0 <= int(object_index) < len(objs):
+            raise ValueError(f"object {object_index} does not exist: the scene has {len(objs)} objects")
+        ro = objs[int(object_index)]
+        if not isinstance(ro.obj, TriangleMesh) or ro.obj.uvs is None:
+            raise ValueError(f"object {object_index} is not a triangle mesh with uvs ({type(ro.obj).__name__})")
+        return Lightmap(ro.obj, width, height, directions).placement(ro)
+
+    def seed(self, s):
+        self._seed = int(s)
+        return self
+
+    def jitter(self, on=True):
+        self._jitter = bool(on)
+        return self
+
+    def bias(self, b):
+        self._bias = float(b)
+        return self
+
+    def flip(self, on=True):
+        self._flip = bool(on)
+        self._texels = None
+        return self
+
+    def centres(self):
+        """(u, v) float64 arrays of shape (W * H,): the texel centres in texel-id order"""
+        w, h = self.width, self.height
+        if w < 1 or h < 1:
+            raise ValueError("width and height must be >= 1")
+        y, x = np.divmod(np.arange(w * h, dtype=np.int64), w)
+        return (x + 0.5) / float(w), 1.0 - (y + 0.5) / float(h)
+
+    def texels(self):
+        """the numpy statement of fw_lightmap_texels: (records (W * H, 8) float32, owner (W * H,) uint32).  Coverage: the float64 edge
+        functions e(A, B; P) = (B_u - A_u)(P_v - A_v) - (B_v - A_v)(P_u - A_u) of the float32 uvs at the texel centre all >= 0 or all
+        <= 0, zero-area triangles skipped, lowest triangle index first.  Records: float64 barycentrics, (b0 p0 + b1 p1) + b2 p2, the
+        normalised interpolated (or geometric, (p0 - p2) x (p1 - p2)) normal, the placement's transform, one rounding."""
+        if self._texels is not None:
+            return self._texels
+        m = self.mesh
+        n = self.width * self.height
+        pu, pv = self.centres()
+        uv = m.uvs.astype(np.float64)
+        idx = m.indicies.reshape(-1, 3).astype(np.int64)
+        owner = np.full(n, LIGHTMAP_NO_OWNER, np.uint32)
+        for t, (i0, i1, i2) in enumerate(idx):
+            (au, av), (bu, bv), (cu, cv) = uv[i0], uv[i1], uv[i2]
+            if _edge(au, av, bu, bv, cu, cv) == 0.0:
+                continue
+            e0, e1, e2 = _edge(au, av, bu, bv, pu, pv), _edge(bu, bv, cu, cv, pu, pv), _edge(cu, cv, au, av, pu, pv)
+            inside = ((e0 >= 0) & (e1 >= 0) & (e2 >= 0)) | ((e0 <= 0) & (e1 <= 0) & (e2 <= 0))
+            owner[inside & (owner == LIGHTMAP_NO_OWNER)] = t
+        rec = np.zeros((n, 8), np.float32)
+        cov = np.nonzero(owner != LIGHTMAP_NO_OWNER)[0]
+        if cov.size:
+            tri = idx[owner[cov].astype(np.int64)]
+            a, b, c = uv[tri[:, 0]], uv[tri[:, 1]], uv[tri[:, 2]]
+            P = (pu[cov], pv[cov])
+            area = _edge(a[:, 0], a[:, 1], b[:, 0], b[:, 1], c[:, 0], c[:, 1])
+            b0 = (_edge(b[:, 0], b[:, 1], c[:, 0], c[:, 1], *P) / area)[:, None]
+            b1 = (_edge(c[:, 0], c[:, 1], a[:, 0], a[:, 1], *P) / area)[:, None]
+            b2 = (_edge(a[:, 0], a[:, 1], b[:, 0], b[:, 1], *P) / area)[:, None]
+            v = m.verts.astype(np.float64)
+            p0, p1, p2 = v[tri[:, 0]], v[tri[:, 1]], v[tri[:, 2]]
+            pos = (b0 * p0 + b1 * p1) + b2 * p2
+            if m.normals is not None:
+                nv = m.normals.astype(np.float64)
+                nrm = (b0 * nv[tri[:, 0]] + b1 * nv[tri[:, 1]]) + b2 * nv[tri[:, 2]]
+            else:
+                ea, eb = p0 - p2, p1 - p2
+                nrm = np.stack([ea[:, 1] * eb[:, 2] - ea[:, 2] * eb[:, 1], ea[:, 2] * eb[:, 0] - ea[:, 0] * eb[:, 2],
+                                ea[:, 0] * eb[:, 1] - ea[:, 1] * eb[:, 0]], axis=1)
+            with np.errstate(all="ignore"):
+                length = np.sqrt((nrm[:, 0] * nrm[:, 0] + nrm[:, 1] * nrm[:, 1]) + nrm[:, 2] * nrm[:, 2])
+                nrm = nrm / length[:, None]
+                rows = rotor_rows(self.rotation)
+                if F32(0.5) * ((rows[0, 0] + rows[1, 1] + rows[2, 2]) - F32(1.0)) < F32(0.999):
+                    R = rows.astype(np.float64)
+                    pos = np.stack([(R[k, 0] * pos[:, 0] + R[k, 1] * pos[:, 1]) + R[k, 2] * pos[:, 2] for k in range(3)], axis=1)
+                    nrm = np.stack([(R[k, 0] * nrm[:, 0] + R[k, 1] * nrm[:, 1]) + R[k, 2] * nrm[:, 2] for k in range(3)], axis=1)
+                pos = pos + self._position.astype(np.float64)
+                if self._flip_normals != self._flip:
+                    nrm = -nrm
+                both = np.concatenate([pos, nrm], axis=1).astype(np.float32)
+            ok = (length > 0) & np.isfinite(length) & np.all(np.isfinite(both), axis=1)
+            rec[cov[ok], 0:3] = both[ok, 0:3]
+            rec[cov[ok], 4:7] = both[ok, 3:6]
+            owner[cov[~ok]] = LIGHTMAP_NO_OWNER
+        rec[:, 3] = owner.view(np.float32)
+        self._texels = (rec, owner)
+        return self._texels
+
+    def covered(self) -> np.ndarray:
+        """the covered list: the ascending texel ids with an owner, uint32"""
+        return np.nonzero(self.texels()[1] != LIGHTMAP_NO_OWNER)[0].astype(np.uint32)
+
+    def shifts(self, round: int, ids) -> np.ndarray:
+        """(n, 2) float64: the shift (xi_u, xi_v) of the texel ids given in `round`"""
+        ids = np.asarray(ids).reshape(-1)
+        return texel_jitter(self._seed, round, ids) if self._jitter else np.full((ids.size, 2), 0.5)
+
+    def rays(self, round: int, first: int = 0, n=None, device=None):
+        """the numpy statement of one round's rays of the entries [first, first + n) of the covered list: (n * D, 6) float32, entry
+        q * D + j = direction j of covered texel q (device: see panorama_rays).  In float64, rounded once: u = (j + xi_u) / D, r = sqrt u,
+        c = sqrt(max(0, 1 - u)), t = j g + xi_v, phi = 2 pi (t - floor t), l = (r cos phi, r sin phi, c), rotated into Duff et al.'s basis
+        around n = the record's float32 normal divided by its float64 length; origin = position + bias * n (bias 0: the position's bits)."""
+        D = self.directions
+        if D < 1:
+            raise ValueError("directions must be >= 1")
+        ids = self.covered()
+        ids = ids[int(first):] if n is None else ids[int(first):int(first) + int(n)]
+        rec = self.texels()[0][ids.astype(np.int64)]
+        pos, nrm = rec[:, None, 0:3].astype(np.float64), rec[:, None, 4:7].astype(np.float64)
+        xi = self.shifts(round, ids)
+        j = np.arange(D, dtype=np.float64)[None, :]
+        u = (j + xi[:, 0:1]) / float(D)
+        r = np.sqrt(u)
+        c = np.sqrt(np.maximum(0.0, 1.0 - u))
+        g = (np.sqrt(5.0) - 1.0) / 2.0
+        t = j * g + xi[:, 1:2]
+        phi = (2.0 * np.pi) * (t - np.floor(t))
+        lx, ly = r * np.cos(phi), r * np.sin(phi)
+        nrm = nrm / np.sqrt((nrm[..., 0:1] * nrm[..., 0:1] + nrm[..., 1:2] * nrm[..., 1:2]) + nrm[..., 2:3] * nrm[..., 2:3])
+        nx, ny, nz = nrm[..., 0], nrm[..., 1], nrm[..., 2]
+        s = np.copysign(1.0, nz)
+        a = -1.0 / (s + nz)
+        b = (nx * ny) * a
+        T = (1.0 + (s * (nx * nx)) * a, s * b, -s * nx)
+        B = (b, s + (ny * ny) * a, -ny)
+        d = np.stack([(lx * T[k] + ly * B[k]) + c * nrm[..., k] for k in range(3)], axis=-1).reshape(-1, 3)
+        if self._bias == 0.0:
+            o = np.repeat(rec[:, 0:3], D, axis=0).astype(np.float64)
+        else:
+            o = np.repeat((pos + float(F32(self._bias)) * nrm)[:, 0], D, axis=0)
+        return _rays_out(o, d, device)
+
+    def to_abi(self):
+        """(fw_lightmap, the arrays it points into: keep them alive as long as the struct is used)"""
+        m = self.mesh
+        fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        s = A.fw_lightmap()
+        s.verts, s.n_verts = m.verts.ctypes.data_as(fp), m.verts.shape[0]
+        s.indices, s.n_indices = m.indicies.ctypes.data_as(up), m.indicies.shape[0]
+        s.normals = m.normals.ctypes.data_as(fp) if m.normals is not None else None
+        s.uvs = m.uvs.ctypes.data_as(fp)
+        s.position, s.rotation, s.flip_normals = A.vec3(self._position), self.rotation.to_abi(), int(self._flip_normals)
+        s.width, s.height, s.directions, s.jitter = self.width, self.height, self.directions, int(self._jitter)
+        s.seed, s.bias, s.flip, s.chunk_texels = self._seed & 0xFFFFFFFFFFFFFFFF, self._bias, int(self._flip), int(self.chunk_texels)
+        return s, (m.verts, m.indicies, m.normals, m.uvs)
+
+
 # render_sequence's default cap on the samples a pixel carries over from the frames before it (DESIGN.md §9j)
 DEFAULT_MAX_HISTORY = 64.0
 
@@ -1585,6 +1836,27 @@ class Renderer:
                                                         stream=stream, paths_per_batch=s["paths_per_batch"], flags=s["flags"], chunk=chunk,
                                                         on_device=on_device)
             return sh, sums
+        finally:
+            if ds is not scene:
+                ds.close()
+
+    def bake_lightmap(self, scene, lightmap: "Lightmap", rounds: int = 1, dilate: int = 2, first_round: int = 0, sums=None, chunk=None,
+                      device: int = 0, stream=None, on_device: bool = False):
+        """A lightmap baked on the device (not in the reference; fw_bake_lightmap): `rounds` rounds of the lightmap's cosine-weighted
+        rays, each rendered with settings["samples"] paths per direction and this renderer's seed (+ the round), use_bvh, batch size and
+        flags — lights and light sampling included; its camera, size and gamma are not used — and reduced to the irradiance of every
+        covered texel.  Returns (irradiance, sums): (H, W, 4) float32 each; irradiance rgb = sums / (first_round + rounds) with a = 1 on
+        covered texels, then `dilate` dilation passes (a = 0.5 on filled texels, 0 elsewhere); pass sums back with first_round = the
+        rounds it holds to add more.  on_device and chunk as _lib.DeviceScene.bake_lightmap; the call's stats are kept in
+        self.lightmap_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        from . import _lib
+        s = self.settings
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            irr, sums, self.lightmap_stats = ds.bake_lightmap(lightmap, rounds, s["samples"], first_round, sums, dilate, seed=s["seed"],
+                                                              use_bvh=s["use_bvh"], stream=stream, paths_per_batch=s["paths_per_batch"],
+                                                              flags=s["flags"], chunk=chunk, on_device=on_device)
+            return irr, sums
         finally:
             if ds is not scene:
                 ds.close()

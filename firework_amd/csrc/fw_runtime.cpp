@@ -13,6 +13,7 @@
 #include "fw_temporal.h"
 #include "fw_camera_models.h"
 #include "fw_probes.h"
+#include "fw_lightmap.h"
 
 #include <algorithm>
 #include <atomic>
@@ -4011,6 +4012,326 @@ int bake_probes_impl(fw_scene *sc, const fw_probe_set *s, const fw_render_rays_p
     return FW_OK;
 }
 
+// ---- lightmaps (include/firework_hip.h) -------------------------------------------------------------------------
+// The lightmap's own argument checks (FW_ERR_BAD_ARG only).  too_large: the host's upper bound of n_cov x D is >= 2^31, which the callers
+// report as FW_ERR_UNSUPPORTED after their own argument checks.
+int lightmap_check(const fw_lightmap *lm, bool &too_large) {
+    if (!lm->verts || !lm->indices || !lm->uvs) return fail(FW_ERR_BAD_ARG, "null verts, indices or uvs");
+    if (lm->n_verts == 0) return fail(FW_ERR_BAD_ARG, "n_verts must be > 0");
+    if (lm->n_indices == 0 || lm->n_indices % 3u) return fail(FW_ERR_BAD_ARG, "n_indices must be a positive multiple of 3");
+    if (lm->width == 0 || lm->width > 16384u || lm->height == 0 || lm->height > 16384u) return fail(FW_ERR_BAD_ARG, "width and height must be in 1..16384");
+    if (lm->directions == 0 || lm->directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (!std::isfinite(lm->bias) || lm->bias < 0.f) return fail(FW_ERR_BAD_ARG, "bias must be finite and >= 0");
+    const float place[7] = {lm->position.x, lm->position.y, lm->position.z, lm->rotation.s, lm->rotation.xy, lm->rotation.xz, lm->rotation.yz};
+    for (float v : place) if (!std::isfinite(v)) return fail(FW_ERR_BAD_ARG, "the placement (position, rotation) is not finite");
+    for (uint32_t i = 0; i < lm->n_indices; i++)
+        if (lm->indices[i] >= lm->n_verts) return fail(FW_ERR_BAD_ARG, "index " + std::to_string(i) + " is not below n_verts");
+    for (uint64_t i = 0; i < (uint64_t)lm->n_verts * 3; i++)
+        if (!std::isfinite(lm->verts[i])) return fail(FW_ERR_BAD_ARG, "vert " + std::to_string(i / 3) + " is not finite");
+    for (uint64_t i = 0; i < (uint64_t)lm->n_verts * 2; i++)
+        if (!std::isfinite(lm->uvs[i])) return fail(FW_ERR_BAD_ARG, "uv " + std::to_string(i / 2) + " is not finite");
+    if (lm->normals)
+        for (uint64_t i = 0; i < (uint64_t)lm->n_verts * 3; i++)
+            if (!std::isfinite(lm->normals[i])) return fail(FW_ERR_BAD_ARG, "normal " + std::to_string(i / 3) + " is not finite");
+    // an upper bound of the covered texels: the triangles' UV bounding boxes, one texel wider than k_lm_cover's, clipped to the image
+    const double W = lm->width, H = lm->height;
+    const uint64_t all = (uint64_t)lm->width * lm->height;
+    uint64_t cover = 0;
+    for (uint32_t t = 0; t < lm->n_indices / 3u && cover < all; t++) {
+        double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
+        for (int k = 0; k < 3; k++) {
+            const float *uv = lm->uvs + (size_t)lm->indices[t * 3u + k] * 2;
+            lo[0] = std::min(lo[0], (double)uv[0]); hi[0] = std::max(hi[0], (double)uv[0]);
+            lo[1] = std::min(lo[1], 1.0 - (double)uv[1]); hi[1] = std::max(hi[1], 1.0 - (double)uv[1]);
+        }
+        const double x0 = std::max(0.0, std::floor(lo[0] * W - 0.5) - 1.0), x1 = std::min(W - 1.0, std::ceil(hi[0] * W - 0.5) + 1.0);
+        const double y0 = std::max(0.0, std::floor(lo[1] * H - 0.5) - 1.0), y1 = std::min(H - 1.0, std::ceil(hi[1] * H - 0.5) + 1.0);
+        if (x1 >= x0 && y1 >= y0) cover += (uint64_t)(x1 - x0 + 1.0) * (uint64_t)(y1 - y0 + 1.0);
+    }
+    too_large = std::min(cover, all) * lm->directions >= (1ull << 31);
+    return FW_OK;
+}
+
+constexpr size_t LIGHTMAP_SCRATCH_BYTES = (size_t)256 << 20;  // the automatic chunk of fw_bake_lightmap and fw_lightmap_rays' host output
+
+// What every lightmap call makes first, once: the mesh on the device, k_lm_cover and k_lm_texels, the owner map back on the host and the
+// covered list (one host pass over the 4 B / texel owner map: ascending, deterministic) on both sides.
+struct LightmapTexels {
+    CallScratch scratch;
+    float *records = nullptr; uint32_t *owner = nullptr, *list = nullptr;      // device: W H x 8 floats, W H, n_cov
+    std::vector<uint32_t> h_owner, h_list;
+    explicit LightmapTexels(int dev) : scratch(dev) {}
+};
+
+int lightmap_texels_make(const fw_lightmap *lm, int device, hipStream_t stream, LightmapTexels &T) {
+    const size_t n_tex = (size_t)lm->width * lm->height, nv = lm->n_verts;
+    const size_t o_idx = align256(nv * 12), o_nrm = o_idx + align256((size_t)lm->n_indices * 4), o_uv = o_nrm + align256(lm->normals ? nv * 12 : 0),
+                 o_own = o_uv + align256(nv * 8), o_rec = o_own + align256(n_tex * 4), o_list = o_rec + align256(n_tex * 32);
+    if (int rc = T.scratch.alloc(o_list + n_tex * 4)) return rc;
+    uint8_t *base = (uint8_t *)T.scratch.p;
+    HIPCHK(hipMemcpyAsync(base, lm->verts, nv * 12, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(base + o_idx, lm->indices, (size_t)lm->n_indices * 4, hipMemcpyHostToDevice, stream));
+    if (lm->normals) HIPCHK(hipMemcpyAsync(base + o_nrm, lm->normals, nv * 12, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(base + o_uv, lm->uvs, nv * 8, hipMemcpyHostToDevice, stream));
+    T.owner = (uint32_t *)(base + o_own); T.records = (float *)(base + o_rec); T.list = (uint32_t *)(base + o_list);
+    HIPCHK(hipMemsetAsync(T.owner, 0xff, n_tex * 4, stream));
+    fw::DLightmapMesh m{};
+    m.verts = (const float *)base; m.indices = (const uint32_t *)(base + o_idx);
+    m.normals = lm->normals ? (const float *)(base + o_nrm) : nullptr; m.uvs = (const float *)(base + o_uv);
+    m.n_tris = lm->n_indices / 3u; m.width = lm->width; m.height = lm->height;
+    rotor_rows(lm->rotation, m.rows);
+    m.rotated = 0.5f * ((m.rows[0][0] + m.rows[1][1] + m.rows[2][2]) - 1.f) < 0.999f ? 1u : 0u;
+    m.negate = ((lm->flip_normals != 0) != (lm->flip != 0)) ? 1u : 0u;
+    m.position[0] = lm->position.x; m.position[1] = lm->position.y; m.position[2] = lm->position.z;
+    const int n_cus = device_cus(device);
+    fw::launch_lm_cover(stream, n_cus, m, T.owner);
+    fw::launch_lm_texels(stream, n_cus, m, T.owner, (float4 *)T.records);
+    T.h_owner.resize(n_tex);
+    HIPCHK(hipMemcpyAsync(T.h_owner.data(), T.owner, n_tex * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    T.h_list.clear();
+    for (size_t i = 0; i < n_tex; i++) if (T.h_owner[i] != FW_NO_HIT) T.h_list.push_back((uint32_t)i);
+    if (!T.h_list.empty()) HIPCHK(hipMemcpyAsync(T.list, T.h_list.data(), T.h_list.size() * 4, hipMemcpyHostToDevice, stream));
+    return FW_OK;
+}
+
+fw::DLightmapRays lightmap_rays_device(const fw_lightmap *lm, uint32_t round, const LightmapTexels &T, uint32_t first) {
+    fw::DLightmapRays d{};
+    d.directions = lm->directions;
+    d.seed32 = (uint32_t)lm->seed ^ ((uint32_t)(lm->seed >> 32) * 0x9E3779B9u);
+    d.jitter = lm->jitter ? 1u : 0u;
+    d.round = round; d.bias = lm->bias;
+    d.texel_ids = T.list + first; d.records = (const float4 *)T.records;
+    return d;
+}
+
+// the checks every entry point shares once its arguments are valid: a device is visible and `device` names one
+int lightmap_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    HIPCHK(hipSetDevice(device));
+    return FW_OK;
+}
+
+int lightmap_texels_impl(const fw_lightmap *lm, int device, float *records, uint32_t *owner, uint32_t *n_covered, int on_device, void *stream_) {
+    if (!lm) return fail(FW_ERR_BAD_ARG, "null argument");
+    bool too_large = false;
+    if (int rc = lightmap_check(lm, too_large)) return rc;
+    if (on_device && (((uintptr_t)records & 15u) || ((uintptr_t)owner & 3u))) return fail(FW_ERR_BAD_ARG, "device records must be 16-byte aligned, device owner 4-byte aligned");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "covered texels x directions must be below 2^31");
+    if (int rc = lightmap_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    LightmapTexels T(device);
+    if (int rc = lightmap_texels_make(lm, device, stream, T)) return rc;
+    const size_t n_tex = (size_t)lm->width * lm->height;
+    if (records) HIPCHK(hipMemcpyAsync(records, T.records, n_tex * 32, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+    if (owner) {
+        if (on_device) HIPCHK(hipMemcpyAsync(owner, T.owner, n_tex * 4, hipMemcpyDeviceToDevice, stream));
+        else std::memcpy(owner, T.h_owner.data(), n_tex * 4);
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    if (n_covered) *n_covered = (uint32_t)T.h_list.size();
+    return FW_OK;
+}
+
+int lightmap_rays_impl(const fw_lightmap *lm, int device, uint32_t round, uint32_t first, uint32_t n, float *rays, int on_device, void *stream_) {
+    if (!lm || !rays) return fail(FW_ERR_BAD_ARG, "null argument");
+    bool too_large = false;
+    if (int rc = lightmap_check(lm, too_large)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (on_device && ((uintptr_t)rays & 3u)) return fail(FW_ERR_BAD_ARG, "rays must be 4-byte aligned");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "covered texels x directions must be below 2^31");
+    if (int rc = lightmap_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    LightmapTexels T(device);
+    if (int rc = lightmap_texels_make(lm, device, stream, T)) return rc;
+    if ((uint64_t)first + n > T.h_list.size()) { (void)hipStreamSynchronize(stream); return fail(FW_ERR_BAD_ARG, "first + n exceeds the covered list (" + std::to_string(T.h_list.size()) + " texels)"); }
+    const size_t D = lm->directions;
+    const int n_cus = device_cus(device);
+    if (on_device) {
+        fw::launch_lm_rays(stream, n_cus, lightmap_rays_device(lm, round, T, first), n, rays);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, LIGHTMAP_SCRATCH_BYTES / (D * 24)));
+    CallScratch out(device);
+    if (int rc = out.alloc((size_t)per * D * 24)) { (void)hipStreamSynchronize(stream); return rc; }
+    for (uint32_t done = 0; done < n; done += per) {
+        const uint32_t k = std::min(per, n - done);
+        fw::launch_lm_rays(stream, n_cus, lightmap_rays_device(lm, round, T, first + done), k, (float *)out.p);
+        HIPCHK(hipMemcpyAsync(rays + (size_t)done * D * 6, out.p, (size_t)k * D * 24, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+int lightmap_reduce_impl(int device, uint32_t n, uint32_t directions, uint32_t samples, const uint32_t *texel_ids, const float *accum, float *sums,
+                         uint32_t n_texels, int on_device, void *stream_) {
+    if (!accum || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (n == 0 || n_texels == 0) return fail(FW_ERR_BAD_ARG, "n and n_texels must be > 0");
+    if (directions == 0 || directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (samples == 0 || samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^24");
+    if (!texel_ids && n > n_texels) return fail(FW_ERR_BAD_ARG, "n exceeds n_texels");
+    if (texel_ids && !on_device)
+        for (uint32_t q = 0; q < n; q++)
+            if (texel_ids[q] >= n_texels) return fail(FW_ERR_BAD_ARG, "texel id " + std::to_string(q) + " is not below n_texels");
+    if (on_device && ((((uintptr_t)accum | (uintptr_t)sums) & 15u) || ((uintptr_t)texel_ids & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device accum and sums must be 16-byte aligned, device texel_ids 4-byte aligned");
+    if ((uint64_t)n * directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
+    if (int rc = lightmap_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t entries = (size_t)n * directions, sum_bytes = (size_t)n_texels * 16;
+    CallScratch scratch(device);
+    const float *d_acc = accum; float *d_sums = sums; const uint32_t *d_ids = texel_ids;
+    if (!on_device) {
+        const size_t o_sums = align256(entries * 16), o_ids = o_sums + align256(sum_bytes);
+        if (int rc = scratch.alloc(o_ids + (size_t)n * 4)) return rc;
+        uint8_t *base = (uint8_t *)scratch.p;
+        HIPCHK(hipMemcpyAsync(base, accum, entries * 16, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
+        if (texel_ids) HIPCHK(hipMemcpyAsync(base + o_ids, texel_ids, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+        d_acc = (const float *)base; d_sums = (float *)(base + o_sums); d_ids = texel_ids ? (const uint32_t *)(base + o_ids) : nullptr;
+    }
+    fw::launch_lm_reduce(stream, device_cus(device), n, directions, samples, d_ids, d_acc, d_sums);
+    if (!on_device) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// `passes` dilation passes of the image at d_img through the second buffer d_tmp; the result ends in d_img
+int lightmap_dilate_device(hipStream_t stream, uint32_t width, uint32_t height, uint32_t passes, float *d_img, float *d_tmp) {
+    float *src = d_img, *dst = d_tmp;
+    for (uint32_t k = 0; k < passes; k++) { fw::launch_lm_dilate(stream, width, height, src, dst); std::swap(src, dst); }
+    if (src != d_img) HIPCHK(hipMemcpyAsync(d_img, src, (size_t)width * height * 16, hipMemcpyDeviceToDevice, stream));
+    return FW_OK;
+}
+
+int lightmap_dilate_impl(int device, uint32_t width, uint32_t height, uint32_t passes, float *image, int on_device, void *stream_) {
+    if (!image) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (width == 0 || width > 16384u || height == 0 || height > 16384u) return fail(FW_ERR_BAD_ARG, "width and height must be in 1..16384");
+    if (passes > 64u) return fail(FW_ERR_BAD_ARG, "passes must be in 0..64");
+    if (on_device && ((uintptr_t)image & 15u)) return fail(FW_ERR_BAD_ARG, "a device image must be 16-byte aligned");
+    if (int rc = lightmap_device(device)) return rc;
+    if (passes == 0) return FW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t bytes = (size_t)width * height * 16;
+    CallScratch scratch(device);
+    if (int rc = scratch.alloc(align256(bytes) + (on_device ? 0 : bytes))) return rc;
+    float *d_tmp = (float *)scratch.p, *d_img = image;
+    if (!on_device) {
+        d_img = (float *)((uint8_t *)scratch.p + align256(bytes));
+        HIPCHK(hipMemcpyAsync(d_img, image, bytes, hipMemcpyHostToDevice, stream));
+    }
+    if (int rc = lightmap_dilate_device(stream, width, height, passes, d_img, d_tmp)) return rc;
+    if (!on_device) HIPCHK(hipMemcpyAsync(image, d_img, bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_bake_lightmap: per round and chunk of the covered list, k_lm_rays into the call's scratch, render_impl over those device rays into a
+// zeroed accum of the scratch — the fw_render_rays call of the chunk (rays_impl's frame) — then k_lm_reduce into the running sums.
+int bake_lightmap_impl(fw_scene *sc, const fw_lightmap *lm, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, uint32_t dilate,
+                       float *sums, float *irradiance, fw_stats *stats) {
+    if (!sc || !lm || !rp) return fail(FW_ERR_BAD_ARG, "null argument");
+    bool too_large = false;
+    if (int rc = lightmap_check(lm, too_large)) return rc;
+    if (rounds == 0) return fail(FW_ERR_BAD_ARG, "rounds must be > 0");
+    if ((uint64_t)first_round + rounds > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_round + rounds overflows");
+    if (rp->samples == 0 || rp->samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^24");
+    if (dilate > 64u) return fail(FW_ERR_BAD_ARG, "dilate must be in 0..64");
+    if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
+    if (rp->on_device && (((uintptr_t)sums | (uintptr_t)irradiance) & 15u)) return fail(FW_ERR_BAD_ARG, "device sums and irradiance must be 16-byte aligned");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "covered texels x directions must be below 2^31");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)rp->stream;
+    LightmapTexels T(dev);
+    if (int rc = lightmap_texels_make(lm, dev, stream, T)) return rc;
+    const uint32_t N = (uint32_t)T.h_list.size(), D = lm->directions, S = rp->samples;
+    const size_t n_tex = (size_t)lm->width * lm->height, img_bytes = n_tex * 16;
+    const uint32_t chunk = std::max<uint32_t>(1u, std::min<uint32_t>(N, lm->chunk_texels ? lm->chunk_texels
+                                                                                         : (uint32_t)std::max<uint64_t>(1, LIGHTMAP_SCRATCH_BYTES / ((uint64_t)D * 40))));
+    const bool own_sums = !rp->on_device || !sums;        // the running sums live in the scratch: a host caller's, or nobody's
+    const bool own_irr = irradiance && !rp->on_device;
+    const size_t o_acc = align256((size_t)chunk * D * 24), o_sums = o_acc + align256((size_t)chunk * D * 16),
+                 o_irr = o_sums + align256(own_sums ? img_bytes : 0), o_tmp = o_irr + align256(own_irr ? img_bytes : 0);
+    CallScratch scratch(dev);
+    if (int rc = scratch.alloc(o_tmp + (irradiance && dilate ? img_bytes : 0))) { (void)hipStreamSynchronize(stream); return rc; }
+    uint8_t *base = (uint8_t *)scratch.p;
+    float *d_rays = (float *)base, *d_acc = (float *)(base + o_acc), *d_sums = own_sums ? (float *)(base + o_sums) : sums;
+    if (own_sums) {
+        if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, img_bytes, hipMemcpyHostToDevice, stream));
+        else HIPCHK(hipMemsetAsync(d_sums, 0, img_bytes, stream));
+    }
+    ProbeEvents ev;                                   // around the two kernels' launches, only when the caller reads stats
+    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
+    const int n_cus = device_cus(dev);
+    const bool timing = (rp->flags & FW_FLAG_TIME_KERNELS) != 0;
+
+    fw_stats total{};
+    for (uint32_t r = first_round; r - first_round < rounds; r++) {
+        fw_render_rays_params q = *rp;
+        q.gamma = 1.f; q.on_device = 1; q.seed = rp->seed + r;
+        for (uint32_t q0 = 0; q0 < N; q0 += chunk) {
+            const uint32_t k = std::min(chunk, N - q0), n = k * D;
+            q.n_rays = n;
+            if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
+            fw::launch_lm_rays(stream, n_cus, lightmap_rays_device(lm, r, T, q0), k, d_rays);
+            if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
+            HIPCHK(hipMemsetAsync(d_acc, 0, (size_t)n * 16, stream));
+            const fw_render_params P = rays_frame(&q, S);
+            const RayInput ri{d_rays, n, false, nullptr, q0 * D, true};
+            fw_stats gs{};
+            if (int rc = render_impl(sc, &P, nullptr, nullptr, nullptr, stats ? &gs : nullptr, 0, d_acc, nullptr, nullptr, &ri)) { (void)hipStreamSynchronize(stream); return rc; }
+            if (stats) HIPCHK(hipEventRecord(ev.e[2], stream));
+            fw::launch_lm_reduce(stream, n_cus, k, D, S, T.list + q0, d_acc, d_sums);
+            if (!stats) continue;
+            HIPCHK(hipEventRecord(ev.e[3], stream));
+            HIPCHK(hipEventSynchronize(ev.e[3]));
+            float gen_ms = 0.f, red_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
+            HIPCHK(hipEventElapsedTime(&red_ms, ev.e[2], ev.e[3]));
+            total.samples += gs.samples; total.rays += gs.rays;
+            for (int d = 0; d < FW_MAX_SEGMENTS; d++) total.rays_per_depth[d] += gs.rays_per_depth[d];
+            total.algorithmic_bytes += gs.algorithmic_bytes;
+            total.ms_render += gs.ms_render + gen_ms + red_ms; total.ms_raygen += gs.ms_raygen + (timing ? gen_ms : 0.f);
+            total.ms_extend += gs.ms_extend; total.ms_shade += gs.ms_shade; total.ms_accumulate += gs.ms_accumulate + (timing ? red_ms : 0.f);
+            total.ms_d2h += gs.ms_d2h;
+            total.n_extend_launches += gs.n_extend_launches; total.n_shade_launches += gs.n_shade_launches; total.n_batches += gs.n_batches;
+            total.tlas_nodes = gs.tlas_nodes; total.blas_nodes = gs.blas_nodes; total.reserved = gs.reserved;
+            total.bytes_raygen += gs.bytes_raygen + (uint64_t)n * 24 + (uint64_t)k * 36;     // (the generator's stores, its records and ids)
+            total.bytes_extend += gs.bytes_extend; total.bytes_shade += gs.bytes_shade;
+            total.bytes_accumulate += gs.bytes_accumulate + (uint64_t)n * 16 + (uint64_t)k * 28;     // (the reduction's loads and its sums)
+            total.deposits += gs.deposits; total.parked_rays += gs.parked_rays;
+        }
+    }
+    // the outputs: sums where the caller keeps them; irradiance = sums / rounds so far on covered texels, then the dilation
+    if (!rp->on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, img_bytes, hipMemcpyDeviceToHost, stream));
+    if (irradiance) {
+        float *d_irr = own_irr ? (float *)(base + o_irr) : irradiance;
+        fw::launch_lm_resolve(stream, (uint32_t)n_tex, (double)((uint64_t)first_round + rounds), T.owner, d_sums, d_irr);
+        if (int rc = lightmap_dilate_device(stream, lm->width, lm->height, dilate, d_irr, (float *)(base + o_tmp))) { (void)hipStreamSynchronize(stream); return rc; }
+        if (own_irr) HIPCHK(hipMemcpyAsync(irradiance, d_irr, img_bytes, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    if (stats) {
+        *stats = total;
+        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FW_OK;
+}
+
 } // namespace
 
 // =========================================================================================================
@@ -4443,6 +4764,38 @@ int fw_bake_probes(fw_scene *scene, const fw_probe_set *set, const fw_render_ray
     try { return bake_probes_impl(scene, set, rp, first_round, rounds, sums, sh, stats); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_probes"); }
+}
+
+int fw_lightmap_texels(const fw_lightmap *lm, int device, float *records, uint32_t *owner, uint32_t *n_covered, int on_device, void *stream) {
+    try { return lightmap_texels_impl(lm, device, records, owner, n_covered, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_lightmap_texels"); }
+}
+
+int fw_lightmap_rays(const fw_lightmap *lm, int device, uint32_t round, uint32_t first, uint32_t n, float *rays, int on_device, void *stream) {
+    try { return lightmap_rays_impl(lm, device, round, first, n, rays, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_lightmap_rays"); }
+}
+
+int fw_lightmap_reduce(int device, uint32_t n, uint32_t directions, uint32_t samples, const uint32_t *texel_ids, const float *accum, float *sums,
+                       uint32_t n_texels, int on_device, void *stream) {
+    try { return lightmap_reduce_impl(device, n, directions, samples, texel_ids, accum, sums, n_texels, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_lightmap_reduce"); }
+}
+
+int fw_lightmap_dilate(int device, uint32_t width, uint32_t height, uint32_t passes, float *image, int on_device, void *stream) {
+    try { return lightmap_dilate_impl(device, width, height, passes, image, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_lightmap_dilate"); }
+}
+
+int fw_bake_lightmap(fw_scene *scene, const fw_lightmap *lm, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, uint32_t dilate,
+                     float *sums, float *irradiance, fw_stats *stats) {
+    try { return bake_lightmap_impl(scene, lm, rp, first_round, rounds, dilate, sums, irradiance, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_lightmap"); }
 }
 
 int fw_denoise(const fw_denoise_params *p, const float *color, const float *aov, const float *moments, float *linear_rgb, float *gamma_rgb,

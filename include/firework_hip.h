@@ -802,6 +802,107 @@ int fw_probe_project(int device, uint32_t n_probes, uint32_t directions, uint32_
    frame graph are fw_render_rays'. */
 int fw_bake_probes(fw_scene *scene, const fw_probe_set *set, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, float *sums, float *sh, fw_stats *stats);
 
+/* ---- lightmaps baked on the device: irradiance over a mesh's UV texels (additive at ABI 8) ---------------------------
+   A fw_lightmap is one mesh placement and a texture size.  It reads nothing from a scene: the scene is only what the rays are traced
+   against.  All its pointers are host memory.
+   World transform: the tracer's own.  rows = the rotation matrix of `rotation` as fw_object's; a rotation with 1/2 (tr R - 1) >= 0.999
+   (float32) is treated as no rotation; point = R p + position, normal = R n, formed in float64 from the float32 rows as
+   ((R_k0 x + R_k1 y) + R_k2 z) + position_k; the normal is negated once for flip_normals and once for flip.
+   Texels: texel (x, y), row 0 at the top, id = y W + x, has its centre at u = (x + 1/2) / W, v = 1 - (y + 1/2) / H, in float64 — the
+   inverse of ImageTexture's lookup (i = floor(u w), j = floor((1 - v) h)), so a baked map put on the mesh as an image texture lands
+   where it was baked.
+   Coverage (k_lm_cover): with the float32 uvs widened to double, the edge function of the directed edge A -> B at the centre P is
+       e(A, B; P) = ((B_u - A_u) (P_v - A_v)) - ((B_v - A_v) (P_u - A_u)),   every operation rounded in float64 as written;
+   a texel is inside triangle (a, b, c) when e(a, b; P), e(b, c; P), e(c, a; P) are all >= 0 or all <= 0; a triangle with
+   e(a, b; c) == 0 covers nothing; the lowest triangle index that covers a texel owns it (overlaps and shared edges included).
+   Records (k_lm_texels): with area = e(a, b; c), b0 = e(b, c; P) / area, b1 = e(c, a; P) / area, b2 = e(a, b; P) / area, the
+   object-space position is (b0 p0 + b1 p1) + b2 p2 per component, the normal the same interpolation of the vertex normals or, without
+   normals, (p0 - p2) x (p1 - p2) (differences first, then (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x)), divided by its
+   length sqrt((x x + y y) + z z); transformed, rounded to float32 once.  Record of texel id: 8 floats, (position.xyz, owner as bits),
+   (normal.xyz, 0).  A texel whose normal has zero or non-finite length, or whose position or normal is not finite in float32, has no
+   owner; a texel without an owner has the record (0, 0, 0, FW_NO_HIT bits), (0, 0, 0, 0).
+   Covered list: the ascending texel ids with an owner; q indexes it.
+   Rays (k_lm_rays): entry i = q D + j is direction j of covered texel q.  The shift (xi_u, xi_v) is fw_probe_rays' hash with
+   probe -> texel id (api.texel_jitter in Python), so coverage and chunking never change a texel's rays; jitter == 0: (1/2, 1/2).
+   In float64, in this order, rounded to float32 once, with n the record's float32 normal m made unit again, n = m / sqrt((m_x m_x +
+   m_y m_y) + m_z m_z) (the frame is then orthonormal to float64 and d unit to one float32 rounding):
+       u = (j + xi_u) / D;  r = sqrt(u);  c = sqrt(max(0, 1 - u));  t = j g + xi_v with g = (sqrt(5) - 1) / 2;
+       phi = 2 pi (t - floor(t));  l = (r cos phi, r sin phi, c);
+       s = copysign(1, n_z);  a = -1 / (s + n_z);  b = (n_x n_y) a;                          (Duff et al. 2017)
+       T = (1 + (s (n_x n_x)) a, s b, -s n_x);  B = (b, s + (n_y n_y) a, -n_y);  d_k = (l_x T_k + l_y B_k) + l_z n_k
+       origin_k = position_k + bias n_k   (bias == 0: the record's position bit for bit)
+   The directions are cosine-distributed about n (density cos(theta) / pi). */
+typedef struct fw_lightmap {
+    const float *verts;        /* 3 * n_verts floats, fw_shape's meaning */
+    uint32_t n_verts;
+    const uint32_t *indices;   /* n_indices, a multiple of 3 */
+    uint32_t n_indices;
+    const float *normals;      /* NULL or 3 * n_verts floats */
+    const float *uvs;          /* 2 * n_verts floats, required */
+    fw_vec3 position;          /* fw_object's meaning */
+    fw_rotor3 rotation;
+    int32_t flip_normals;
+    uint32_t width, height;    /* each 1 .. 16384 */
+    uint32_t directions;       /* D: rays per texel and round, 1 .. 2^20 */
+    int32_t  jitter;           /* 0: every round uses the shift (1/2, 1/2) */
+    uint64_t seed;             /* of the shifts */
+    float bias;                /* >= 0: the ray origin is position + bias x normal, world units */
+    int32_t flip;              /* bake the other side */
+    uint32_t chunk_texels;     /* fw_bake_lightmap: covered texels rendered at a time; 0 = as many as fit 256 MiB at 40 B per entry, at least 1 */
+} fw_lightmap;
+
+/* "The lightmap's checks" below — what is wrong in the description itself, FW_ERR_BAD_ARG, in this order: NULL verts, indices or uvs; n_verts == 0;
+   n_indices == 0 or not a multiple of 3; width or height outside 1..16384; directions outside 1..2^20; bias negative or not finite; a
+   non-finite position or rotation; a vertex index >= n_verts; a non-finite vert, uv or normal — fw_last_error() names the element.
+   FW_ERR_UNSUPPORTED, which every call reports after its own argument checks and before HIP is called, when n_cov x D >= 2^31 cannot be
+   ruled out from the host: min(W H, the texels of the triangles' clipped UV bounding boxes) x D >= 2^31. */
+
+/* fw_lightmap_texels: records (W H x 8 floats), owner (W H uint32, FW_NO_HIT = none) and *n_covered; each may be NULL.  Host arrays,
+   or with on_device device arrays on `device` (n_covered is host memory always), written on `stream` and complete on return.  Errors, in
+   this order: FW_ERR_BAD_ARG for a NULL lm, the lightmap's checks, with on_device records not 16-byte or owner not 4-byte aligned;
+   FW_ERR_UNSUPPORTED as above; FW_ERR_NO_DEVICE; FW_ERR_BAD_ARG for a device index out of range. */
+int fw_lightmap_texels(const fw_lightmap *lm, int device, float *records, uint32_t *owner, uint32_t *n_covered, int on_device, void *stream);
+
+/* fw_lightmap_rays: the rays of round `round` of the entries [first, first + n) of the covered list: n x D x 6 floats (origin,
+   direction), host memory or with on_device device memory.  Errors: as fw_lightmap_texels with a NULL rays, n == 0, with on_device rays
+   not 4-byte aligned among the argument checks; after the device is found, FW_ERR_BAD_ARG for first + n beyond the covered list. */
+int fw_lightmap_rays(const fw_lightmap *lm, int device, uint32_t round, uint32_t first, uint32_t n, float *rays, int on_device, void *stream);
+
+/* fw_lightmap_reduce: adds one round's cosine-weighted mean to running sums.  accum: n x D x 4 floats, fw_render_progressive's layout;
+   sums: n_texels x 4 floats (an image of W x H texels), 16-byte aligned; texel_ids: n distinct ids < n_texels, or NULL for the identity
+   (then n <= n_texels).  For entry q and channel c, in float64,
+       proj = (pi / D) * sum_j ((double)accum[q D + j].c / samples)
+   with G = the smallest power of two >= min(D, 64): lane l of a group of G takes j = l, l + G, ... in ascending order, the lanes are
+   combined by an xor butterfly over the distances G/2 .. 1; proj is rounded to float32 once and added to sums[texel_ids[q]].c with one
+   float32 addition.  .w is never written.  No atomics: two runs are bit-equal.  Errors, in this order and before HIP is called:
+   FW_ERR_BAD_ARG for a NULL accum or sums, n == 0, n_texels == 0, directions outside 1..2^20, samples outside 1..2^24, n > n_texels
+   without texel_ids, a host texel id >= n_texels, with on_device accum or sums not 16-byte or texel_ids not 4-byte aligned;
+   FW_ERR_UNSUPPORTED for n x D >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index out of range. */
+int fw_lightmap_reduce(int device, uint32_t n, uint32_t directions, uint32_t samples, const uint32_t *texel_ids, const float *accum, float *sums, uint32_t n_texels, int on_device, void *stream);
+
+/* fw_lightmap_dilate: `passes` (0..64) dilation passes over image (W x H x 4 floats: rgb, a), in place.  In a pass a texel with a > 0
+   is copied; a texel with a == 0 looks at its in-image neighbours in the order (dy, dx) = (-1,-1), (-1,0), (-1,1), (0,-1), (0,1),
+   (1,-1), (1,0), (1,1): if n >= 1 of them have a > 0 its rgb becomes their float32 sum in that order divided by (float)n and its a 0.5;
+   otherwise it is unchanged.  No wrap-around.  Errors: FW_ERR_BAD_ARG for a NULL image, width or height outside 1..16384, passes > 64,
+   with on_device an image not 16-byte aligned; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index out of range. */
+int fw_lightmap_dilate(int device, uint32_t width, uint32_t height, uint32_t passes, float *image, int on_device, void *stream);
+
+/* fw_bake_lightmap: the rounds [first_round, first_round + rounds) of a lightmap against a resident scene.  Of rp the fields
+   fw_bake_probes reads are read.  For each round r and each chunk [q0, q1) of the covered list (lm->chunk_texels at a time): k_lm_rays
+   fills device scratch that the call allocates and frees on every path; a zeroed accum is rendered exactly as fw_render_rays would
+   with per_sample_rays = 0, first_sample = 0, samples = S, key_base = q0 D, keys = NULL and seed = rp->seed + r; k_lm_reduce adds the
+   chunk into sums.
+     sums      : W x H x 4 floats (16-byte aligned on the device), the running sums of the rounds [0, first_round); NULL only when
+                 first_round == 0.  .w is never written.
+     irradiance: W x H x 4 floats, may be NULL: covered texels xyz = float(sums / (double)(first_round + rounds)), w = 1, every other
+                 texel 0; then `dilate` (0..64) dilation passes.
+   Contracts.  Composition: for every chunk_texels, sums equals bit for bit fw_lightmap_rays, fw_render_rays and fw_lightmap_reduce
+   chained by hand over the whole covered list.  Progressive: k calls of n rounds leave the sums and irradiance of one call of k n rounds.
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, lm or rp, the lightmap's
+   checks, rounds == 0, first_round + rounds >= 2^32, samples outside 1..2^24, dilate > 64, a NULL sums with first_round > 0, with
+   on_device sums or irradiance not 16-byte aligned; FW_ERR_UNSUPPORTED as above; then FW_ERR_NO_DEVICE.  stats: as fw_bake_probes. */
+int fw_bake_lightmap(fw_scene *scene, const fw_lightmap *lm, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, uint32_t dilate, float *sums, float *irradiance, fw_stats *stats);
+
 /* Diagnostic: the kernels' division / square-root helpers against the compiler's IEEE expansion, bit for bit,
    on n hashed operand pairs.  mode 0 = magnitudes 2^-40..2^40 (must be 0 mismatches), mode 1 = all bit patterns. */
 int fw_selftest_arith(int device, uint32_t n, uint32_t seed, int mode, uint64_t *div_mismatches, uint64_t *sqrt_mismatches);
