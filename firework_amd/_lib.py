@@ -383,6 +383,20 @@ def camera_rays(renderer, sample=0, pixel_ids=None, device=0):
     return out
 
 
+def _stream_arg(stream, torch_device):
+    """the hipStream_t argument of a call on device tensors: `stream` (a raw handle), or for None the current torch stream of torch_device"""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(torch_device).cuda_stream
+    return C.c_void_p(stream) if stream else None
+
+
+def _host_f32(arr, shape, name):
+    """the check of a caller-owned host array that a call updates in place (shape None: any shape)"""
+    if not (isinstance(arr, np.ndarray) and arr.dtype == np.float32 and (shape is None or arr.shape == tuple(shape)) and arr.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"{name} must be a contiguous float32 array" + ("" if shape is None else f" of shape {tuple(shape)}"))
+
+
 def _model_abi(model, chunk=None):
     """a fw_camera_model from an api.CameraModel (or a fw_camera_model, copied), with chunk_samples = chunk when given"""
     m = model.to_abi() if hasattr(model, "to_abi") else A.fw_camera_model.from_buffer_copy(model)
@@ -402,10 +416,7 @@ def model_rays(model, first_sample=0, n_samples=1, device=0, out=None, stream=No
     if out is not None:
         import torch
         _check_device_tensor(out, shape, torch.float32, device, "out")
-        if stream is None:
-            stream = torch.cuda.current_stream(out.device).cuda_stream
-        _check(lib, lib.fw_model_rays(C.byref(m), int(device), int(first_sample), int(n_samples), out.data_ptr(), 1,
-                                      C.c_void_p(stream) if stream else None))
+        _check(lib, lib.fw_model_rays(C.byref(m), int(device), int(first_sample), int(n_samples), out.data_ptr(), 1, _stream_arg(stream, out.device)))
         return out
     rays = np.empty(shape, np.float32)
     _check(lib, lib.fw_model_rays(C.byref(m), int(device), int(first_sample), int(n_samples), rays.ctypes.data, 0, None))
@@ -433,10 +444,7 @@ def probe_rays(probes, round=0, first_probe=0, n=None, device=0, out=None, strea
     if out is not None:
         import torch
         _check_device_tensor(out, shape, torch.float32, device, "out")
-        if stream is None:
-            stream = torch.cuda.current_stream(out.device).cuda_stream
-        _check(lib, lib.fw_probe_rays(C.byref(s), int(device), int(round), int(first_probe), int(n), out.data_ptr(), 1,
-                                      C.c_void_p(stream) if stream else None))
+        _check(lib, lib.fw_probe_rays(C.byref(s), int(device), int(round), int(first_probe), int(n), out.data_ptr(), 1, _stream_arg(stream, out.device)))
         return out
     rays = np.empty(shape, np.float32)
     _check(lib, lib.fw_probe_rays(C.byref(s), int(device), int(round), int(first_probe), int(n), rays.ctypes.data, 0, None))
@@ -460,17 +468,14 @@ def probe_project(rays, accum, samples, directions, sums=None, device=0, stream=
         if sums is None:
             sums = torch.zeros((n, 9, 3), dtype=torch.float32, device=rays.device)
         _check_device_tensor(sums, (n, 9, 3), torch.float32, device, "sums")
-        if stream is None:
-            stream = torch.cuda.current_stream(rays.device).cuda_stream
         _check(lib, lib.fw_probe_project(int(device), n, d, int(samples), rays.data_ptr(), accum.data_ptr(), sums.data_ptr(), 1,
-                                         C.c_void_p(stream) if stream else None))
+                                         _stream_arg(stream, rays.device)))
         return sums
     r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
     a = np.ascontiguousarray(np.asarray(accum, dtype=np.float32))
     if sums is None:
         sums = np.zeros((n, 9, 3), np.float32)
-    if not (isinstance(sums, np.ndarray) and sums.dtype == np.float32 and sums.shape == (n, 9, 3) and sums.flags["C_CONTIGUOUS"]):
-        raise ValueError(f"sums must be a contiguous float32 array of shape ({n}, 9, 3)")
+    _host_f32(sums, (n, 9, 3), "sums")
     _check(lib, lib.fw_probe_project(int(device), n, d, int(samples), r.ctypes.data, a.ctypes.data, sums.ctypes.data, 0, None))
     return sums
 
@@ -481,13 +486,6 @@ def _lightmap_abi(lightmap, chunk=None):
     if chunk is not None:
         s.chunk_texels = int(chunk)
     return s, keep
-
-
-def _stream_arg(stream, torch_device):
-    if stream is None:
-        import torch
-        stream = torch.cuda.current_stream(torch_device).cuda_stream
-    return C.c_void_p(stream) if stream else None
 
 
 def lightmap_texels(lightmap, device=0, on_device=False, stream=None):
@@ -566,8 +564,7 @@ def lightmap_reduce(accum, samples, directions, sums, texel_ids=None, device=0, 
                                            accum.data_ptr(), sums.data_ptr(), n_texels, 1, _stream_arg(stream, accum.device)))
         return sums
     a = np.ascontiguousarray(np.asarray(accum, dtype=np.float32))
-    if not (isinstance(sums, np.ndarray) and sums.dtype == np.float32 and sums.flags["C_CONTIGUOUS"]):
-        raise ValueError("sums must be a contiguous float32 array")
+    _host_f32(sums, None, "sums")
     ids = None if texel_ids is None else np.ascontiguousarray(np.asarray(texel_ids, dtype=np.uint32))
     _check(lib, lib.fw_lightmap_reduce(int(device), n, d, int(samples), ids.ctypes.data if ids is not None else None, a.ctypes.data,
                                        sums.ctypes.data, n_texels, 0, None))
@@ -586,8 +583,7 @@ def lightmap_dilate(image, passes, device=0, stream=None):
         _check_device_tensor(image, (h, w, 4), torch.float32, device, "image")
         _check(lib, lib.fw_lightmap_dilate(int(device), w, h, int(passes), image.data_ptr(), 1, _stream_arg(stream, image.device)))
         return image
-    if not (isinstance(image, np.ndarray) and image.dtype == np.float32 and image.flags["C_CONTIGUOUS"]):
-        raise ValueError("image must be a contiguous float32 array")
+    _host_f32(image, None, "image")
     _check(lib, lib.fw_lightmap_dilate(int(device), w, h, int(passes), image.ctypes.data, 0, None))
     return image
 
@@ -689,9 +685,7 @@ class DeviceScene:
                 if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device.type != "cuda" or (t.device.index or 0) != self.device:
                     raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor of shape {shape} on cuda:{self.device}")
             p.outputs_on_device = 1
-            if stream is None:
-                stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
-            p.stream = C.c_void_p(stream) if stream else None
+            p.stream = _stream_arg(stream, torch.device("cuda", self.device))
             ptr = {k: (out[k].data_ptr() if k in out else None) for k in want}
             _check(lib, lib.fw_render_adaptive(self.handle, C.byref(p), float(tolerance), int(min_samples), ptr["accum"], ptr["moments"],
                                                ptr["rgb8"], ptr["gamma"], ptr["linear"], ptr["round_pixels"], C.byref(st)))
@@ -767,10 +761,8 @@ class DeviceScene:
             rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=rays.device)
             gam = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
             lin = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(rays.device).cuda_stream
             p.on_device = 1
-            p.stream = C.c_void_p(stream) if stream else None
+            p.stream = _stream_arg(stream, rays.device)
             if keys is not None:
                 p.keys = C.cast(C.c_void_p(keys.data_ptr()), C.POINTER(C.c_uint32))
             _check(lib, lib.fw_render_rays(self.handle, C.byref(p), rays.data_ptr(), accum.data_ptr(), rgb8.data_ptr(), gam.data_ptr(),
@@ -785,8 +777,7 @@ class DeviceScene:
             p.keys = k.ctypes.data_as(C.POINTER(C.c_uint32))
         if accum is None:
             accum = np.zeros((n, 4), np.float32)
-        if not (isinstance(accum, np.ndarray) and accum.dtype == np.float32 and accum.shape == (n, 4) and accum.flags["C_CONTIGUOUS"]):
-            raise ValueError(f"accum must be a contiguous float32 array of shape ({n}, 4)")
+        _host_f32(accum, (n, 4), "accum")
         rgb8 = np.empty((n, 3), np.uint8)
         gam = np.empty((n, 3), np.float32)
         lin = np.empty((n, 3), np.float32)
@@ -819,17 +810,14 @@ class DeviceScene:
             rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
             gam = torch.empty((n, 3), dtype=torch.float32, device=dev)
             lin = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
             p.on_device = 1
-            p.stream = C.c_void_p(stream) if stream else None
+            p.stream = _stream_arg(stream, dev)
             _check(lib, lib.fw_render_model(self.handle, C.byref(m), C.byref(p), accum.data_ptr(), rgb8.data_ptr(), gam.data_ptr(),
                                             lin.data_ptr(), C.byref(st)))
             return RaysResult(rgb8, gam, lin, accum, st.as_dict())
         if accum is None:
             accum = np.zeros((n, 4), np.float32)
-        if not (isinstance(accum, np.ndarray) and accum.dtype == np.float32 and accum.shape == (n, 4) and accum.flags["C_CONTIGUOUS"]):
-            raise ValueError(f"accum must be a contiguous float32 array of shape ({n}, 4)")
+        _host_f32(accum, (n, 4), "accum")
         rgb8 = np.empty((n, 3), np.uint8)
         gam = np.empty((n, 3), np.float32)
         lin = np.empty((n, 3), np.float32)
@@ -852,9 +840,7 @@ class DeviceScene:
             import torch
             _check_device_tensor(out, (n, 12), torch.float32, self.device, "out")
             p.outputs_on_device = 1
-            if stream is None:
-                stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
-            p.stream = C.c_void_p(stream) if stream else None
+            p.stream = _stream_arg(stream, torch.device("cuda", self.device))
             _check(lib, lib.fw_render_model_aovs(self.handle, C.byref(m), C.byref(p), out.data_ptr(), C.byref(st)))
             self.aovs_stats = st.as_dict()
             return out
@@ -863,54 +849,9 @@ class DeviceScene:
         self.aovs_stats = st.as_dict()
         return aov
 
-    def bake_probes(self, probes, rounds, samples, first_round=0, sums=None, seed=0, use_bvh=True, stream=None, paths_per_batch=0, flags=0,
-                    chunk=None, on_device=False):
-        """fw_bake_probes: the rounds [first_round, first_round + rounds) of an api.ProbeSet, `samples` paths per direction and round,
-        `chunk` probes at a time (None: the set's own setting; 0: automatic).  sums: (N, 9, 3) float32 running sums of the rounds
-        before first_round, updated in place (None: zeros, only with first_round 0).  Returns (sh, sums, stats): host arrays, or —
-        sums a device tensor on this scene's device, or on_device=True — device tensors, baked on `stream` (default: the current
-        torch stream).  sh = sums / (first_round + rounds)."""
-        lib = self._lib
-        s, _pos = _probe_abi(probes, chunk)
-        n = int(s.n_probes)
-        p = A.fw_render_rays_params()
-        p.samples, p.seed, p.use_bvh, p.gamma = int(samples), int(seed), int(bool(use_bvh)), 1.0
-        p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
-        st = A.fw_stats()
-        if on_device or (sums is not None and type(sums).__module__.startswith("torch")):
-            import torch
-            dev = torch.device("cuda", self.device)
-            if sums is None:
-                sums = torch.zeros((n, 9, 3), dtype=torch.float32, device=dev)
-            _check_device_tensor(sums, (n, 9, 3), torch.float32, self.device, "sums")
-            sh = torch.empty((n, 9, 3), dtype=torch.float32, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            p.on_device = 1
-            p.stream = C.c_void_p(stream) if stream else None
-            _check(lib, lib.fw_bake_probes(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), sums.data_ptr(), sh.data_ptr(),
-                                           C.byref(st)))
-            return sh, sums, st.as_dict()
-        if sums is None:
-            sums = np.zeros((n, 9, 3), np.float32)
-        if not (isinstance(sums, np.ndarray) and sums.dtype == np.float32 and sums.shape == (n, 9, 3) and sums.flags["C_CONTIGUOUS"]):
-            raise ValueError(f"sums must be a contiguous float32 array of shape ({n}, 9, 3)")
-        sh = np.empty((n, 9, 3), np.float32)
-        _check(lib, lib.fw_bake_probes(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), sums.ctypes.data, sh.ctypes.data,
-                                       C.byref(st)))
-        return sh, sums, st.as_dict()
-
-    def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,
-                      flags=0, chunk=None, on_device=False):
-        """fw_bake_lightmap: the rounds [first_round, first_round + rounds) of an api.Lightmap, `samples` paths per direction and round,
-        `chunk` covered texels at a time (None: the lightmap's own setting; 0: automatic).  sums: (H, W, 4) float32 running sums of the
-        rounds before first_round, updated in place (None: zeros, only with first_round 0).  Returns (irradiance, sums, stats): host
-        arrays, or — sums a device tensor on this scene's device, or on_device=True — device tensors, baked on `stream` (default: the
-        current torch stream).  irradiance (H, W, 4): rgb = sums / (first_round + rounds) and a = 1 on covered texels, then `dilate`
-        dilation passes (filled texels carry a = 0.5)."""
-        lib = self._lib
-        s, _keep = _lightmap_abi(lightmap, chunk)
-        shape = (int(s.height), int(s.width), 4)
+    def _bake(self, fn, s, extra, shape, rounds, samples, first_round, sums, seed, use_bvh, stream, paths_per_batch, flags, on_device):
+        """what bake_probes and bake_lightmap share: the bound C function `fn` over its ABI struct `s`, the rounds and the integers `extra`
+        that follow them; sums and the result have `shape`.  Returns (result, sums, stats)."""
         p = A.fw_render_rays_params()
         p.samples, p.seed, p.use_bvh, p.gamma = int(samples), int(seed), int(bool(use_bvh)), 1.0
         p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
@@ -921,20 +862,41 @@ class DeviceScene:
             if sums is None:
                 sums = torch.zeros(shape, dtype=torch.float32, device=dev)
             _check_device_tensor(sums, shape, torch.float32, self.device, "sums")
-            irr = torch.empty(shape, dtype=torch.float32, device=dev)
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
             p.on_device = 1
             p.stream = _stream_arg(stream, dev)
-            _check(lib, lib.fw_bake_lightmap(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), int(dilate), sums.data_ptr(),
-                                             irr.data_ptr(), C.byref(st)))
-            return irr, sums, st.as_dict()
-        if sums is None:
-            sums = np.zeros(shape, np.float32)
-        if not (isinstance(sums, np.ndarray) and sums.dtype == np.float32 and sums.shape == shape and sums.flags["C_CONTIGUOUS"]):
-            raise ValueError(f"sums must be a contiguous float32 array of shape {shape}")
-        irr = np.empty(shape, np.float32)
-        _check(lib, lib.fw_bake_lightmap(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), int(dilate), sums.ctypes.data,
-                                         irr.ctypes.data, C.byref(st)))
-        return irr, sums, st.as_dict()
+            ptrs = sums.data_ptr(), out.data_ptr()
+        else:
+            if sums is None:
+                sums = np.zeros(shape, np.float32)
+            _host_f32(sums, shape, "sums")
+            out = np.empty(shape, np.float32)
+            ptrs = sums.ctypes.data, out.ctypes.data
+        _check(self._lib, fn(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), *extra, *ptrs, C.byref(st)))
+        return out, sums, st.as_dict()
+
+    def bake_probes(self, probes, rounds, samples, first_round=0, sums=None, seed=0, use_bvh=True, stream=None, paths_per_batch=0, flags=0,
+                    chunk=None, on_device=False):
+        """fw_bake_probes: the rounds [first_round, first_round + rounds) of an api.ProbeSet, `samples` paths per direction and round,
+        `chunk` probes at a time (None: the set's own setting; 0: automatic).  sums: (N, 9, 3) float32 running sums of the rounds
+        before first_round, updated in place (None: zeros, only with first_round 0).  Returns (sh, sums, stats): host arrays, or —
+        sums a device tensor on this scene's device, or on_device=True — device tensors, baked on `stream` (default: the current
+        torch stream).  sh = sums / (first_round + rounds)."""
+        s, _pos = _probe_abi(probes, chunk)
+        return self._bake(self._lib.fw_bake_probes, s, (), (int(s.n_probes), 9, 3), rounds, samples, first_round, sums, seed, use_bvh, stream,
+                          paths_per_batch, flags, on_device)
+
+    def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,
+                      flags=0, chunk=None, on_device=False):
+        """fw_bake_lightmap: the rounds [first_round, first_round + rounds) of an api.Lightmap, `samples` paths per direction and round,
+        `chunk` covered texels at a time (None: the lightmap's own setting; 0: automatic).  sums: (H, W, 4) float32 running sums of the
+        rounds before first_round, updated in place (None: zeros, only with first_round 0).  Returns (irradiance, sums, stats): host
+        arrays, or — sums a device tensor on this scene's device, or on_device=True — device tensors, baked on `stream` (default: the
+        current torch stream).  irradiance (H, W, 4): rgb = sums / (first_round + rounds) and a = 1 on covered texels, then `dilate`
+        dilation passes (filled texels carry a = 0.5)."""
+        s, _keep = _lightmap_abi(lightmap, chunk)
+        return self._bake(self._lib.fw_bake_lightmap, s, (int(dilate),), (int(s.height), int(s.width), 4), rounds, samples, first_round, sums, seed,
+                          use_bvh, stream, paths_per_batch, flags, on_device)
 
     def trace(self, rays, use_bvh, seed=0, key_base=0, rays_per_batch=0, time_kernels=False, stats=None):
         """fw_trace_rays: one root.hit(ray, 0.001, 2e9) per ray.  rays: (n, 6) origin + direction.
@@ -960,7 +922,7 @@ class DeviceScene:
             n = int(rays.shape[0])
             out = torch.empty((n, 12), dtype=torch.float32, device=rays.device)
             p.on_device = 1
-            p.stream = C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream or None)
+            p.stream = _stream_arg(None, rays.device)
             _check(lib, lib.fw_trace_rays(self.handle, C.byref(p), rays.data_ptr() if n else None, n, out.data_ptr() if n else None, C.byref(st)))
         else:
             r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32).reshape(-1, 6))
@@ -986,9 +948,7 @@ class DeviceScene:
             import torch
             _check_device_tensor(out, (n, 12), torch.float32, self.device, "out")
             p.outputs_on_device = 1
-            if stream is None:
-                stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
-            p.stream = C.c_void_p(stream) if stream else None
+            p.stream = _stream_arg(stream, torch.device("cuda", self.device))
             _check(lib, lib.fw_render_aovs(self.handle, C.byref(p), out.data_ptr(), C.byref(st)))
             self.aovs_stats = st.as_dict()
             return out
@@ -1075,10 +1035,8 @@ def denoise(color, aov, moments=None, width=None, height=None, iterations=A.FW_D
         rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
         gam = torch.empty((n, 3), dtype=torch.float32, device=dev)
         lin = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
         p.on_device = 1
-        p.stream = C.c_void_p(stream) if stream else None
+        p.stream = _stream_arg(stream, dev)
         _check(lib, lib.fw_denoise(C.byref(p), color.data_ptr(), aov.data_ptr(), None if moments is None else moments.data_ptr(),
                                    lin.data_ptr(), gam.data_ptr(), rgb8.data_ptr()))
         return rgb8, gam, lin
@@ -1126,10 +1084,8 @@ def temporal(color, aov, moments=None, history=None, prev_position=None, width=N
         out_c = torch.empty((n, 3), dtype=torch.float32, device=dev)
         out_m = torch.empty((n, 4), dtype=torch.float32, device=dev)
         out_h = torch.empty((n,), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
         p.on_device = 1
-        p.stream = C.c_void_p(stream) if stream else None
+        p.stream = _stream_arg(stream, dev)
         _check(lib, lib.fw_temporal(C.byref(p), *[None if t is None else t.data_ptr() for t in arrays], out_c.data_ptr(), out_m.data_ptr(),
                                     out_h.data_ptr()))
         return out_c, out_m, out_h

@@ -135,6 +135,41 @@ Options options() { std::lock_guard<std::mutex> g(g_opt_mu); return g_opt; }
         }                                                                                                      \
     } while (0)
 
+// The device checks of an entry point, made once its arguments are valid (the header documents where in each call's order).
+// need_device: a HIP device is visible (their number in *n_out); use_device: and `device` names one, which becomes the current device.
+int need_device(int *n_out = nullptr) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (n_out) *n_out = ndev;
+    return FW_OK;
+}
+int use_device(int device) {
+    int ndev = 0;
+    if (int rc = need_device(&ndev)) return rc;
+    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    HIPCHK(hipSetDevice(device));
+    return FW_OK;
+}
+
+// the 32-bit seed the kernels key their draws with: a 64-bit seed folded
+inline uint32_t seed32_of(uint64_t seed) { return (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x9E3779B9u); }
+
+// The stats of one more render_impl call of a chunked entry point, added to the call's total: the one place that knows which fields
+// add and which take the latest value (the tree sizes, and `reserved`: the depths walked, bit 31 clear where no chunk runs as a frame
+// graph).  ms_scene and ms_wall are the caller's own; what a caller's other kernels took and moved it adds after this.
+void stats_add(fw_stats &total, const fw_stats &part) {
+    total.samples += part.samples; total.rays += part.rays;
+    for (int s = 0; s < FW_MAX_SEGMENTS; s++) total.rays_per_depth[s] += part.rays_per_depth[s];
+    total.algorithmic_bytes += part.algorithmic_bytes;
+    total.ms_render += part.ms_render; total.ms_raygen += part.ms_raygen; total.ms_extend += part.ms_extend; total.ms_shade += part.ms_shade;
+    total.ms_accumulate += part.ms_accumulate; total.ms_d2h += part.ms_d2h;
+    total.n_extend_launches += part.n_extend_launches; total.n_shade_launches += part.n_shade_launches; total.n_batches += part.n_batches;
+    total.tlas_nodes = part.tlas_nodes; total.blas_nodes = part.blas_nodes; total.reserved = part.reserved;
+    total.bytes_raygen += part.bytes_raygen; total.bytes_extend += part.bytes_extend; total.bytes_shade += part.bytes_shade;
+    total.bytes_accumulate += part.bytes_accumulate;
+    total.deposits += part.deposits; total.parked_rays += part.parked_rays;
+}
+
 // ---- host-side f32 vector math; same expressions as the reference (and -ffp-contract=off) ------------
 struct V3 { float x, y, z; float operator[](int i) const { return i == 0 ? x : (i == 1 ? y : z); } };
 inline V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
@@ -2550,7 +2585,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     fr.pixel_ids = rd ? rd->ids : vg ? (const uint32_t *)ws->view_ids.p : ri ? (ray_table ? (const uint32_t *)ws->ray_keys.p : nullptr)
                  : (p->pixel_ids ? (const uint32_t *)ws->pixel_ids.p : (own_order ? (const uint32_t *)ws->tile_ids.p : nullptr));
     fr.scatter_out = own_order ? 1u : 0u;
-    fr.seed32 = (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u);
+    fr.seed32 = seed32_of(p->seed);
     fr.q_n_waves = q.n_waves; fr.q_shift = q.cpw_shift;
     fr.cam_pos[0] = cam.position[0]; fr.cam_pos[1] = cam.position[1]; fr.cam_pos[2] = cam.position[2];
     // (what must not occur in the position is a NEGATIVE zero: -0 + (+0) = +0 is not the position any more, while +0 + (+-0) = +0 is.  Until round 5
@@ -2996,7 +3031,6 @@ int adaptive_impl(fw_scene *sc, const fw_render_params *p, float tol, uint32_t m
     fw_stats total{};
     uint32_t rounds[ADAPTIVE_MAX_ROUNDS] = {};
     uint32_t n_rounds = 0, active = n, done = 0;
-    double ms_classes[4] = {0, 0, 0, 0};
     while (active > 0) {
         if (n_rounds >= ADAPTIVE_MAX_ROUNDS) return fail(FW_ERR_HIP, "adaptive render: more rounds than the schedule allows");
         const uint32_t target = n_rounds == 0 ? min_samples : std::min<uint32_t>(2u * done, p->samples);
@@ -3006,13 +3040,7 @@ int adaptive_impl(fw_scene *sc, const fw_render_params *p, float tol, uint32_t m
         fw_stats rs{};
         if (int rrc = render_impl(sc, &rp, nullptr, nullptr, nullptr, &rs, done, nullptr, &rd)) return rrc;
         rounds[n_rounds++] = active;
-        total.samples += rs.samples; total.rays += rs.rays; total.deposits += rs.deposits; total.parked_rays += rs.parked_rays;
-        for (int d = 0; d < FW_MAX_SEGMENTS; d++) total.rays_per_depth[d] += rs.rays_per_depth[d];
-        total.algorithmic_bytes += rs.algorithmic_bytes;
-        total.bytes_raygen += rs.bytes_raygen; total.bytes_extend += rs.bytes_extend; total.bytes_shade += rs.bytes_shade; total.bytes_accumulate += rs.bytes_accumulate;
-        total.n_batches += rs.n_batches; total.n_extend_launches += rs.n_extend_launches; total.n_shade_launches += rs.n_shade_launches;
-        total.tlas_nodes = rs.tlas_nodes; total.blas_nodes = rs.blas_nodes; total.reserved = rs.reserved;
-        ms_classes[0] += rs.ms_raygen; ms_classes[1] += rs.ms_extend; ms_classes[2] += rs.ms_shade; ms_classes[3] += rs.ms_accumulate;
+        stats_add(total, rs);      // (the per-class times add up to zero unless FW_FLAG_TIME_KERNELS: render_impl reports none then)
         done = target;
         uint32_t *next = (uint32_t *)ws->ad_ids[cur == (const uint32_t *)ws->ad_ids[0].p ? 1 : 0].p;
         fw::launch_adaptive_select(stream, cur, active, d_accum, d_moments, done, done < p->samples, tol, (unsigned long long *)ws->ad_mask.p,
@@ -3045,8 +3073,7 @@ int adaptive_impl(fw_scene *sc, const fw_render_params *p, float tol, uint32_t m
         HIPCHK(hipEventElapsedTime(&ms, ws->ad_ev[0], ws->ad_ev[1]));
         stats->ms_render = ms;
         HIPCHK(hipEventElapsedTime(&ms, ws->ad_ev[1], ws->ev_d2h));
-        stats->ms_d2h = p->outputs_on_device ? 0.0 : ms;
-        if (p->flags & FW_FLAG_TIME_KERNELS) { stats->ms_raygen = ms_classes[0]; stats->ms_extend = ms_classes[1]; stats->ms_shade = ms_classes[2]; stats->ms_accumulate = ms_classes[3]; }
+        stats->ms_d2h = p->outputs_on_device ? 0.0 : ms;      // (both over the whole call, in place of the rounds' sums)
         stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     }
     return FW_OK;
@@ -3100,17 +3127,7 @@ int views_impl(fw_scene *sc, const fw_render_params *p, const fw_camera_settings
         fw_stats gs{};
         if (int rc = render_impl(sc, p, rgb8 ? rgb8 + off : nullptr, gamma_rgb ? gamma_rgb + off : nullptr, linear_rgb ? linear_rgb + off : nullptr,
                                  stats ? &gs : nullptr, 0, nullptr, nullptr, &vg)) return rc;
-        if (!stats) continue;
-        total.samples += gs.samples; total.rays += gs.rays;
-        for (int s = 0; s < FW_MAX_SEGMENTS; s++) total.rays_per_depth[s] += gs.rays_per_depth[s];
-        total.algorithmic_bytes += gs.algorithmic_bytes;
-        total.ms_render += gs.ms_render; total.ms_raygen += gs.ms_raygen; total.ms_extend += gs.ms_extend; total.ms_shade += gs.ms_shade;
-        total.ms_accumulate += gs.ms_accumulate; total.ms_d2h += gs.ms_d2h;
-        total.n_extend_launches += gs.n_extend_launches; total.n_shade_launches += gs.n_shade_launches; total.n_batches += gs.n_batches;
-        total.tlas_nodes = gs.tlas_nodes; total.blas_nodes = gs.blas_nodes;
-        total.reserved = gs.reserved;      // (the depths of the trees walked; bit 31 stays clear: a view group never runs as a frame graph)
-        total.bytes_raygen += gs.bytes_raygen; total.bytes_extend += gs.bytes_extend; total.bytes_shade += gs.bytes_shade; total.bytes_accumulate += gs.bytes_accumulate;
-        total.deposits += gs.deposits; total.parked_rays += gs.parked_rays;
+        if (stats) stats_add(total, gs);
     }
     if (stats) {
         *stats = total;
@@ -3141,8 +3158,7 @@ int rays_impl(fw_scene *sc, const fw_render_rays_params *rp, const float *rays, 
     if (!std::isfinite(rp->gamma) || !(rp->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
     if (!accum && rp->first_sample > 0) return fail(FW_ERR_BAD_ARG, "first_sample > 0 needs the accumulation buffer of the samples before it");
     if (rp->on_device && (((uintptr_t)accum & 15u) || ((uintptr_t)rays & 3u))) return fail(FW_ERR_BAD_ARG, "device accum must be 16-byte aligned, device rays 4-byte aligned");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (int rc = need_device()) return rc;
     const fw_render_params P = rays_frame(rp, rp->samples);
     const RayInput ri{rays, rp->n_rays, rp->per_sample_rays != 0, rp->keys, rp->key_base, rp->on_device != 0};
     return render_impl(sc, &P, rgb8, gamma_rgb, linear_rgb, stats, rp->first_sample, accum, nullptr, nullptr, &ri);
@@ -3253,7 +3269,7 @@ int trace_impl(fw_scene *sc, const fw_trace_params *p, const float *rays, uint32
     fw::DFrame fr{};
     fr.width = 1; fr.height = 1; fr.inv_width = 1.f;              // (camera fields: unused by a trace)
     fr.pixel_ids = ids;
-    fr.seed32 = (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u);
+    fr.seed32 = seed32_of(p->seed);
     fr.sample0 = 0; fr.spp_batch = 1;
     fr.q_n_waves = q.n_waves; fr.q_shift = q.cpw_shift;
     fr.pinhole0 = 0;                                             // caller rays are whole rays
@@ -3327,7 +3343,7 @@ int camera_rays_impl(const fw_render_params *p, int device, uint32_t sample, flo
     if (n_pix == 0) return fail(FW_ERR_BAD_ARG, "no pixels");
     if (p->pixel_ids) for (uint32_t i = 0; i < n_pix; i++) if (p->pixel_ids[i] >= full) return fail(FW_ERR_BAD_ARG, "pixel id out of range");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (int rc = need_device(&ndev)) return rc;
     if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
     if (p->outputs_on_device && ((uintptr_t)rays & 3u)) return fail(FW_ERR_BAD_ARG, "rays must be 4-byte aligned");
     HIPCHK(hipSetDevice(device));
@@ -3343,7 +3359,7 @@ int camera_rays_impl(const fw_render_params *p, int device, uint32_t sample, flo
     fw::DFrame fr{};      // render_impl's frame fields that camera_ray / key_of_linear read, for a batch of one sample
     fr.width = p->width; fr.height = p->height; fr.n_pixels = n_pix; fr.inv_n_pixels = 1.0f / (float)n_pix; fr.inv_width = 1.0f / (float)p->width;
     fr.pixel_ids = p->pixel_ids ? (const uint32_t *)(base + o_ids) : nullptr;
-    fr.seed32 = (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u);
+    fr.seed32 = seed32_of(p->seed);
     fr.sample0 = sample; fr.spp_batch = 1;
     if (p->pixel_ids) HIPCHK(hipMemcpyAsync(base + o_ids, p->pixel_ids, (size_t)n_pix * 4, hipMemcpyHostToDevice, stream));
     float *dst = p->outputs_on_device ? rays : (float *)(base + o_out);
@@ -3374,8 +3390,7 @@ int aovs_impl(fw_scene *sc, const fw_render_params *p, float *aov, fw_stats *sta
     if (p->rng_mode != FW_RNG_CTR) return fail(FW_ERR_UNSUPPORTED, "the HIP path implements FW_RNG_CTR only (FW_RNG_LCG is a sequential stream)");
     const uint64_t full = (uint64_t)p->width * p->height;
     if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (int rc = need_device()) return rc;
     const uint32_t n = (uint32_t)full;
     const auto wall0 = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(sc->device));
@@ -3438,7 +3453,7 @@ int aovs_impl(fw_scene *sc, const fw_render_params *p, float *aov, fw_stats *sta
     uint32_t *const ids = (uint32_t *)(base + o_ids), *const slot_of = (uint32_t *)(base + o_slot), *const totals = (uint32_t *)(base + o_tot);
     const fw::DPark park{(float4 *)(base + o_pa), (float2 *)(base + o_pb), (float4 *)(base + o_pm), q.cap + 64u,
                          park_meshes ? (uint32_t *)(base + o_pc) : nullptr, park_meshes ? (uint32_t *)(base + o_pc) + q.n_waves : nullptr};
-    const uint32_t seed32 = (uint32_t)p->seed ^ ((uint32_t)(p->seed >> 32) * 0x9E3779B9u);
+    const uint32_t seed32 = seed32_of(p->seed);
     fw::DFrame fr{};
     fr.width = 1; fr.height = 1; fr.inv_width = 1.f;
     fr.pixel_ids = ids;
@@ -3516,7 +3531,7 @@ int denoise_impl(const fw_denoise_params *p, const float *color, const float *ao
     const uint64_t full = (uint64_t)p->width * p->height;
     if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (int rc = need_device(&ndev)) return rc;
     if (p->device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
     const uint32_t n = (uint32_t)full, L = p->iterations;
     const int dev = p->device;
@@ -3602,7 +3617,7 @@ int temporal_impl(const fw_temporal_params *p, const float *color, const float *
     const uint64_t full = (uint64_t)p->width * p->height;
     if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (int rc = need_device(&ndev)) return rc;
     if (p->device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
     const size_t n = (size_t)full;
     const int dev = p->device;
@@ -3643,6 +3658,84 @@ int temporal_impl(const fw_temporal_params *p, const float *color, const float *
     return FW_OK;
 }
 
+// ---- what the calls that generate rays, render them and reduce the result share --------------------------------
+// device scratch of one call, released on every way out of the function that owns it
+struct CallScratch : DevBuf { int dev; explicit CallScratch(int d) : dev(d) {} ~CallScratch() { if (p) { (void)hipSetDevice(dev); release(); } } };
+// events around a call's own kernels, created only when the caller reads stats
+template <int N> struct CallEvents { hipEvent_t e[N] = {}; ~CallEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } };
+
+// the rays (and, in a bake, their accum) of an automatic chunk of fw_render_model, fw_bake_probes and fw_bake_lightmap, and the slab of
+// the host output of fw_model_rays, fw_probe_rays and fw_lightmap_rays
+constexpr size_t CALL_SCRATCH_BYTES = (size_t)256 << 20;
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Host output of a ray generator: `n` items of `item_bytes` of rays each go to `dst` in slabs through scratch of the call's own.
+// launch(first_item, k, d_slab) enqueues the generator for the items [first_item, first_item + k).  Returns with the stream drained.
+template <class Launch> int host_slabs(hipStream_t stream, int device, uint32_t n, size_t item_bytes, float *dst, Launch launch) {
+    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / item_bytes));
+    CallScratch slab(device);
+    if (int rc = slab.alloc((size_t)per * item_bytes)) { (void)hipStreamSynchronize(stream); return rc; }
+    for (uint32_t done = 0; done < n; done += per) {
+        const uint32_t k = std::min(per, n - done);
+        launch(done, k, (float *)slab.p);
+        HIPCHK(hipMemcpyAsync((uint8_t *)dst + (size_t)done * item_bytes, slab.p, (size_t)k * item_bytes, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// The rounds of a bake (fw_bake_probes, fw_bake_lightmap): per round r of [first_round, first_round + rounds) and chunk of
+// the `n_items` items (probes, covered texels) with `directions` rays each: generate(r, first_item, k, d_rays) enqueues the rays of
+// k items, render_impl renders them into the zeroed d_acc — the fw_render_rays call of the chunk (rays_impl's frame) with gamma 1, seed
+// + r and key_base = first_item x directions — and reduce(first_item, k, d_rays, d_acc) enqueues the chunk's reduction into the running
+// sums.  total (the caller reads stats): the chunks' stats, plus the two kernels' time and the bytes they move: 24 per ray and gen_item per
+// item generated, red_ray per ray and red_item per item reduced.  The caller owns the checks, the scratch and the outputs; on an error
+// the stream is drained.
+struct BakeRounds {
+    uint32_t first_round, rounds, n_items, directions, chunk;
+    float *d_rays, *d_acc;                             // chunk x directions x 24 and x 16 bytes of the call's scratch
+    uint32_t gen_item, red_ray, red_item;
+};
+template <class Generate, class Reduce>
+int bake_rounds(fw_scene *sc, const fw_render_rays_params *rp, const BakeRounds &b, fw_stats *total, Generate generate, Reduce reduce) {
+    hipStream_t stream = (hipStream_t)rp->stream;
+    const uint32_t S = rp->samples;
+    const bool timing = (rp->flags & FW_FLAG_TIME_KERNELS) != 0;
+    CallEvents<4> ev;                                 // around the two kernels' launches
+    if (total) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
+    for (uint32_t r = b.first_round; r - b.first_round < b.rounds; r++) {      // (first_round + rounds may be 2^32 - 1: r itself never gets there)
+        fw_render_rays_params q = *rp;
+        q.gamma = 1.f; q.on_device = 1; q.seed = rp->seed + r;
+        for (uint32_t i0 = 0; i0 < b.n_items; i0 += b.chunk) {
+            const uint32_t k = std::min(b.chunk, b.n_items - i0), n = k * b.directions;
+            q.n_rays = n;
+            if (total) HIPCHK(hipEventRecord(ev.e[0], stream));
+            generate(r, i0, k, b.d_rays);
+            if (total) HIPCHK(hipEventRecord(ev.e[1], stream));
+            HIPCHK(hipMemsetAsync(b.d_acc, 0, (size_t)n * 16, stream));
+            const fw_render_params P = rays_frame(&q, S);
+            const RayInput ri{b.d_rays, n, false, nullptr, i0 * b.directions, true};
+            fw_stats gs{};
+            if (int rc = render_impl(sc, &P, nullptr, nullptr, nullptr, total ? &gs : nullptr, 0, b.d_acc, nullptr, nullptr, &ri)) { (void)hipStreamSynchronize(stream); return rc; }
+            if (total) HIPCHK(hipEventRecord(ev.e[2], stream));
+            reduce(i0, k, b.d_rays, b.d_acc);
+            if (!total) continue;
+            HIPCHK(hipEventRecord(ev.e[3], stream));
+            HIPCHK(hipEventSynchronize(ev.e[3]));
+            float gen_ms = 0.f, red_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
+            HIPCHK(hipEventElapsedTime(&red_ms, ev.e[2], ev.e[3]));
+            stats_add(*total, gs);
+            total->ms_render += gen_ms + red_ms;
+            if (timing) { total->ms_raygen += gen_ms; total->ms_accumulate += red_ms; }
+            total->bytes_raygen += (uint64_t)n * 24 + (uint64_t)k * b.gen_item;
+            total->bytes_accumulate += (uint64_t)n * b.red_ray + (uint64_t)k * b.red_item;
+        }
+    }
+    return FW_OK;
+}
+
 // ---- camera models (include/firework_hip.h) ------------------------------------------------------------------
 // The model's own argument checks (FW_ERR_BAD_ARG only) and its device form: camera.rs's basis in float64.  too_large: W x H >= 2^31, which
 // the callers report as FW_ERR_UNSUPPORTED after their own argument checks.
@@ -3652,7 +3745,7 @@ int model_prepare(const fw_camera_model *m, fw::DModel &d, bool &too_large) {
     if (!camera_finite(m->camera)) return fail(FW_ERR_BAD_ARG, "camera fields must be finite");
     d = fw::DModel{};
     d.kind = m->kind; d.width = m->width; d.height = m->height;
-    d.seed32 = (uint32_t)m->seed ^ ((uint32_t)(m->seed >> 32) * 0x9E3779B9u);
+    d.seed32 = seed32_of(m->seed);
     d.jitter = m->jitter ? 1u : 0u;
     const double pos[3] = {m->camera.cam_pos.x, m->camera.cam_pos.y, m->camera.cam_pos.z};
     const double at[3] = {m->camera.look_at.x, m->camera.look_at.y, m->camera.look_at.z};
@@ -3683,13 +3776,7 @@ int model_prepare(const fw_camera_model *m, fw::DModel &d, bool &too_large) {
     return FW_OK;
 }
 
-// device scratch of one call, released on every way out of the function that owns it
-struct CallScratch : DevBuf { int dev; explicit CallScratch(int d) : dev(d) {} ~CallScratch() { if (p) { (void)hipSetDevice(dev); release(); } } };
-struct CallEvents { hipEvent_t e[2] = {nullptr, nullptr}; ~CallEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } };
-
-constexpr size_t MODEL_SCRATCH_BYTES = (size_t)256 << 20;     // the automatic chunk of fw_render_model and fw_model_rays' host output
-
-// fw_model_rays: device output — one launch into the caller's memory; host output — slabs of samples through scratch of the call's own
+// fw_model_rays: device output — one launch into the caller's memory; host output — host_slabs of samples
 int model_rays_impl(const fw_camera_model *m, int device, uint32_t first, uint32_t n_samples, float *rays, int on_device, void *stream_) {
     if (!m || !rays) return fail(FW_ERR_BAD_ARG, "null argument");
     fw::DModel dm; bool too_large = false;
@@ -3698,10 +3785,7 @@ int model_rays_impl(const fw_camera_model *m, int device, uint32_t first, uint32
     if ((uint64_t)first + n_samples > (1ull << 32)) return fail(FW_ERR_BAD_ARG, "first_sample + n_samples overflows");
     if (on_device && ((uintptr_t)rays & 3u)) return fail(FW_ERR_BAD_ARG, "rays must be 4-byte aligned");
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "W x H must be below 2^31 (the jitter's counter is 32-bit)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
-    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
-    HIPCHK(hipSetDevice(device));
+    if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     const size_t n_pix = (size_t)m->width * m->height;
     if (on_device) {
@@ -3710,21 +3794,14 @@ int model_rays_impl(const fw_camera_model *m, int device, uint32_t first, uint32
         HIPCHK(hipGetLastError());
         return FW_OK;
     }
-    const uint32_t per = (uint32_t)std::min<uint64_t>(n_samples, std::max<uint64_t>(1, MODEL_SCRATCH_BYTES / (n_pix * 24)));
-    CallScratch scratch(device);
-    if (int rc = scratch.alloc((size_t)per * n_pix * 24)) return rc;
-    for (uint32_t done = 0; done < n_samples; done += per) {
-        const uint32_t k = std::min(per, n_samples - done);
-        fw::launch_model_rays(stream, device_cus(device), dm, first + done, k, (float *)scratch.p);
-        HIPCHK(hipMemcpyAsync(rays + (size_t)done * n_pix * 6, scratch.p, (size_t)k * n_pix * 24, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-    }
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    return host_slabs(stream, device, n_samples, n_pix * 24, rays, [&](uint32_t done, uint32_t k, float *d_rays) {
+        fw::launch_model_rays(stream, device_cus(device), dm, first + done, k, d_rays);
+    });
 }
 
 // fw_render_model: per chunk of samples, k_model_rays into the call's scratch, then render_impl over those device rays on top of the
-// running sums — the fw_render_rays call of the chunk (rays_impl's frame), so the sums and the resolve are its own.
+// running sums — the fw_render_rays call of the chunk (rays_impl's frame), so the sums and the resolve are its own.  Its loop is not
+// bake_rounds': it chunks samples, not items, keeps one accum across the chunks, and only its last chunk resolves.
 int render_model_impl(fw_scene *sc, const fw_camera_model *m, const fw_render_rays_params *rp, float *accum, uint8_t *rgb8, float *gamma_rgb,
                       float *linear_rgb, fw_stats *stats) {
     if (!sc || !m || !rp) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -3737,15 +3814,14 @@ int render_model_impl(fw_scene *sc, const fw_camera_model *m, const fw_render_ra
     if (!accum && rp->first_sample > 0) return fail(FW_ERR_BAD_ARG, "first_sample > 0 needs the accumulation buffer of the samples before it");
     if (rp->on_device && ((uintptr_t)accum & 15u)) return fail(FW_ERR_BAD_ARG, "device accum must be 16-byte aligned");
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "W x H must be below 2^31 (the jitter's counter is 32-bit)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (int rc = need_device()) return rc;
     const auto wall0 = std::chrono::steady_clock::now();
     const int dev = sc->device;
     HIPCHK(hipSetDevice(dev));
     hipStream_t stream = (hipStream_t)rp->stream;
     const size_t n_pix = rp->n_rays;
     const uint32_t S = rp->samples;
-    const uint32_t chunk = std::min<uint32_t>(S, m->chunk_samples ? m->chunk_samples : (uint32_t)std::max<uint64_t>(1, MODEL_SCRATCH_BYTES / (n_pix * 24)));
+    const uint32_t chunk = std::min<uint32_t>(S, m->chunk_samples ? m->chunk_samples : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / (n_pix * 24)));
     // the running sums between chunks when the caller keeps none: device memory behind the rays, or a host array
     const bool own_accum = !accum && chunk < S;
     const size_t ray_bytes = ((size_t)chunk * n_pix * 24 + 255) & ~(size_t)255;
@@ -3757,7 +3833,7 @@ int render_model_impl(fw_scene *sc, const fw_camera_model *m, const fw_render_ra
         if (rp->on_device) { acc = (float *)((uint8_t *)scratch.p + ray_bytes); HIPCHK(hipMemsetAsync(acc, 0, n_pix * 16, stream)); }
         else { host_accum.assign(n_pix * 4, 0.f); acc = host_accum.data(); }
     }
-    CallEvents ev;                                    // around the generator's launch, only when the caller reads stats
+    CallEvents<2> ev;                                 // around the generator's launch
     if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
     const int n_cus = device_cus(dev);
     const bool timing = (rp->flags & FW_FLAG_TIME_KERNELS) != 0;
@@ -3777,16 +3853,10 @@ int render_model_impl(fw_scene *sc, const fw_camera_model *m, const fw_render_ra
         if (!stats) continue;
         float gen_ms = 0.f;
         HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
-        total.samples += gs.samples; total.rays += gs.rays;
-        for (int s = 0; s < FW_MAX_SEGMENTS; s++) total.rays_per_depth[s] += gs.rays_per_depth[s];
-        total.algorithmic_bytes += gs.algorithmic_bytes;
-        total.ms_render += gs.ms_render + gen_ms; total.ms_raygen += gs.ms_raygen + (timing ? gen_ms : 0.f); total.ms_extend += gs.ms_extend;
-        total.ms_shade += gs.ms_shade; total.ms_accumulate += gs.ms_accumulate; total.ms_d2h += gs.ms_d2h;
-        total.n_extend_launches += gs.n_extend_launches; total.n_shade_launches += gs.n_shade_launches; total.n_batches += gs.n_batches;
-        total.tlas_nodes = gs.tlas_nodes; total.blas_nodes = gs.blas_nodes; total.reserved = gs.reserved;
-        total.bytes_raygen += gs.bytes_raygen + (uint64_t)k * n_pix * 24;                  // (the generator's stores)
-        total.bytes_extend += gs.bytes_extend; total.bytes_shade += gs.bytes_shade; total.bytes_accumulate += gs.bytes_accumulate;
-        total.deposits += gs.deposits; total.parked_rays += gs.parked_rays;
+        stats_add(total, gs);
+        total.ms_render += gen_ms;
+        if (timing) total.ms_raygen += gen_ms;
+        total.bytes_raygen += (uint64_t)k * n_pix * 24;                                    // (the generator's stores)
     }
     if (stats) {
         *stats = total;
@@ -3825,17 +3895,14 @@ int probe_set_check(const fw_probe_set *s, bool &too_large) {
 fw::DProbes probes_device(const fw_probe_set *s, uint32_t round, uint32_t first_probe, const float *d_positions) {
     fw::DProbes d{};
     d.directions = s->directions;
-    d.seed32 = (uint32_t)s->seed ^ ((uint32_t)(s->seed >> 32) * 0x9E3779B9u);
+    d.seed32 = seed32_of(s->seed);
     d.jitter = s->jitter ? 1u : 0u;
     d.round = round; d.first_probe = first_probe; d.positions = d_positions;
     return d;
 }
 
-constexpr size_t PROBE_SCRATCH_BYTES = (size_t)256 << 20;     // the automatic chunk of fw_bake_probes and fw_probe_rays' host output
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // fw_probe_rays: the positions of the probes asked for go to scratch of the call's own; device output — one launch into the caller's
-// memory; host output — slabs of probes through the same scratch
+// memory; host output — host_slabs of probes
 int probe_rays_impl(const fw_probe_set *s, int device, uint32_t round, uint32_t first_probe, uint32_t n, float *rays, int on_device, void *stream_) {
     if (!s || !rays) return fail(FW_ERR_BAD_ARG, "null argument");
     bool too_large = false;
@@ -3844,16 +3911,10 @@ int probe_rays_impl(const fw_probe_set *s, int device, uint32_t round, uint32_t 
     if ((uint64_t)first_probe + n > s->n_probes) return fail(FW_ERR_BAD_ARG, "first_probe + n exceeds n_probes");
     if (on_device && ((uintptr_t)rays & 3u)) return fail(FW_ERR_BAD_ARG, "rays must be 4-byte aligned");
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
-    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
-    HIPCHK(hipSetDevice(device));
+    if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const size_t D = s->directions;
-    const size_t pos_bytes = align256((size_t)n * 12);
-    const uint32_t per = on_device ? 0u : (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, PROBE_SCRATCH_BYTES / (D * 24)));
     CallScratch scratch(device);
-    if (int rc = scratch.alloc(pos_bytes + (size_t)per * D * 24)) return rc;
+    if (int rc = scratch.alloc((size_t)n * 12)) return rc;
     const float *d_pos = (const float *)scratch.p;
     HIPCHK(hipMemcpyAsync(scratch.p, s->positions + (size_t)first_probe * 3, (size_t)n * 12, hipMemcpyHostToDevice, stream));
     if (on_device) {
@@ -3862,15 +3923,9 @@ int probe_rays_impl(const fw_probe_set *s, int device, uint32_t round, uint32_t 
         HIPCHK(hipGetLastError());
         return FW_OK;
     }
-    float *d_rays = (float *)((uint8_t *)scratch.p + pos_bytes);
-    for (uint32_t done = 0; done < n; done += per) {
-        const uint32_t k = std::min(per, n - done);
+    return host_slabs(stream, device, n, (size_t)s->directions * 24, rays, [&](uint32_t done, uint32_t k, float *d_rays) {
         fw::launch_probe_rays(stream, device_cus(device), probes_device(s, round, first_probe + done, d_pos + (size_t)done * 3), k, d_rays);
-        HIPCHK(hipMemcpyAsync(rays + (size_t)done * D * 6, d_rays, (size_t)k * D * 24, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-    }
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    });
 }
 
 // fw_probe_project: with host arrays one device allocation per call holds the inputs and the sums, released on every way out; with
@@ -3884,10 +3939,7 @@ int probe_project_impl(int device, uint32_t n_probes, uint32_t directions, uint3
     if (on_device && (((uintptr_t)accum & 15u) || (((uintptr_t)rays | (uintptr_t)sums) & 3u)))
         return fail(FW_ERR_BAD_ARG, "device accum must be 16-byte aligned, device rays and sums 4-byte aligned");
     if ((uint64_t)n_probes * directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
-    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
-    HIPCHK(hipSetDevice(device));
+    if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     const size_t n = (size_t)n_probes * directions, sum_bytes = (size_t)n_probes * 108;
     CallScratch scratch(device);
@@ -3908,10 +3960,8 @@ int probe_project_impl(int device, uint32_t n_probes, uint32_t directions, uint3
     return FW_OK;
 }
 
-struct ProbeEvents { hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr}; ~ProbeEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } };
-
-// fw_bake_probes: per round and chunk of probes, k_probe_rays into the call's scratch, render_impl over those device rays into a zeroed
-// accum of the scratch — the fw_render_rays call of the chunk (rays_impl's frame) — then k_probe_project into the running sums.
+// fw_bake_probes: its own are the argument checks, the scratch (positions, a chunk's rays and accum, the running sums unless the caller's
+// device memory holds them), k_probe_rays and k_probe_project as bake_rounds' generator and reducer, and sh, divided on the host.
 int bake_probes_impl(fw_scene *sc, const fw_probe_set *s, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, float *sums,
                      float *sh, fw_stats *stats) {
     if (!sc || !s || !rp) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -3923,14 +3973,13 @@ int bake_probes_impl(fw_scene *sc, const fw_probe_set *s, const fw_render_rays_p
     if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
     if (rp->on_device && (((uintptr_t)sums | (uintptr_t)sh) & 3u)) return fail(FW_ERR_BAD_ARG, "device sums and sh must be 4-byte aligned");
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (int rc = need_device()) return rc;
     const auto wall0 = std::chrono::steady_clock::now();
     const int dev = sc->device;
     HIPCHK(hipSetDevice(dev));
     hipStream_t stream = (hipStream_t)rp->stream;
     const uint32_t N = s->n_probes, D = s->directions, S = rp->samples;
-    const uint32_t chunk = std::min<uint32_t>(N, s->chunk_probes ? s->chunk_probes : (uint32_t)std::max<uint64_t>(1, PROBE_SCRATCH_BYTES / ((uint64_t)D * 40)));
+    const uint32_t chunk = std::min<uint32_t>(N, s->chunk_probes ? s->chunk_probes : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 40)));
     const size_t sum_bytes = (size_t)N * 108;
     const bool own_sums = !rp->on_device || !sums;        // the running sums live in the scratch: a host caller's, or nobody's
     const size_t o_rays = align256((size_t)N * 12), o_acc = o_rays + align256((size_t)chunk * D * 24),
@@ -3945,48 +3994,13 @@ int bake_probes_impl(fw_scene *sc, const fw_probe_set *s, const fw_render_rays_p
         if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
         else HIPCHK(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
     }
-    ProbeEvents ev;                                   // around the two kernels' launches, only when the caller reads stats
-    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
     const int n_cus = device_cus(dev);
-    const bool timing = (rp->flags & FW_FLAG_TIME_KERNELS) != 0;
-
     fw_stats total{};
-    for (uint32_t r = first_round; r - first_round < rounds; r++) {
-        fw_render_rays_params q = *rp;
-        q.gamma = 1.f; q.on_device = 1; q.seed = rp->seed + r;
-        for (uint32_t p0 = 0; p0 < N; p0 += chunk) {
-            const uint32_t k = std::min(chunk, N - p0), n = k * D;
-            q.n_rays = n;
-            if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
-            fw::launch_probe_rays(stream, n_cus, probes_device(s, r, p0, d_pos + (size_t)p0 * 3), k, d_rays);
-            if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
-            HIPCHK(hipMemsetAsync(d_acc, 0, (size_t)n * 16, stream));
-            const fw_render_params P = rays_frame(&q, S);
-            const RayInput ri{d_rays, n, false, nullptr, p0 * D, true};
-            fw_stats gs{};
-            if (int rc = render_impl(sc, &P, nullptr, nullptr, nullptr, stats ? &gs : nullptr, 0, d_acc, nullptr, nullptr, &ri)) return rc;
-            if (stats) HIPCHK(hipEventRecord(ev.e[2], stream));
-            fw::launch_probe_project(stream, n_cus, k, D, S, d_rays, d_acc, d_sums + (size_t)p0 * 27);
-            if (!stats) continue;
-            HIPCHK(hipEventRecord(ev.e[3], stream));
-            HIPCHK(hipEventSynchronize(ev.e[3]));
-            float gen_ms = 0.f, proj_ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
-            HIPCHK(hipEventElapsedTime(&proj_ms, ev.e[2], ev.e[3]));
-            total.samples += gs.samples; total.rays += gs.rays;
-            for (int d = 0; d < FW_MAX_SEGMENTS; d++) total.rays_per_depth[d] += gs.rays_per_depth[d];
-            total.algorithmic_bytes += gs.algorithmic_bytes;
-            total.ms_render += gs.ms_render + gen_ms + proj_ms; total.ms_raygen += gs.ms_raygen + (timing ? gen_ms : 0.f);
-            total.ms_extend += gs.ms_extend; total.ms_shade += gs.ms_shade; total.ms_accumulate += gs.ms_accumulate + (timing ? proj_ms : 0.f);
-            total.ms_d2h += gs.ms_d2h;
-            total.n_extend_launches += gs.n_extend_launches; total.n_shade_launches += gs.n_shade_launches; total.n_batches += gs.n_batches;
-            total.tlas_nodes = gs.tlas_nodes; total.blas_nodes = gs.blas_nodes; total.reserved = gs.reserved;
-            total.bytes_raygen += gs.bytes_raygen + (uint64_t)n * 24;                        // (the generator's stores)
-            total.bytes_extend += gs.bytes_extend; total.bytes_shade += gs.bytes_shade;
-            total.bytes_accumulate += gs.bytes_accumulate + (uint64_t)n * 40 + (uint64_t)k * 216;    // (the projection's loads and its sums)
-            total.deposits += gs.deposits; total.parked_rays += gs.parked_rays;
-        }
-    }
+    const BakeRounds b{first_round, rounds, N, D, chunk, d_rays, d_acc, 0, 40, 216};       // (the projection's loads and its sums)
+    if (int rc = bake_rounds(sc, rp, b, stats ? &total : nullptr,
+            [&](uint32_t r, uint32_t p0, uint32_t k, float *rays) { fw::launch_probe_rays(stream, n_cus, probes_device(s, r, p0, d_pos + (size_t)p0 * 3), k, rays); },
+            [&](uint32_t p0, uint32_t k, const float *rays, const float *acc) { fw::launch_probe_project(stream, n_cus, k, D, S, rays, acc, d_sums + (size_t)p0 * 27); }))
+        return rc;
     // the outputs: sums where the caller keeps them, and sh = sums / rounds so far, divided on the host in double and rounded once
     std::vector<float> host;
     const float *h_sums = sums;
@@ -4052,8 +4066,6 @@ int lightmap_check(const fw_lightmap *lm, bool &too_large) {
     return FW_OK;
 }
 
-constexpr size_t LIGHTMAP_SCRATCH_BYTES = (size_t)256 << 20;  // the automatic chunk of fw_bake_lightmap and fw_lightmap_rays' host output
-
 // What every lightmap call makes first, once: the mesh on the device, k_lm_cover and k_lm_texels, the owner map back on the host and the
 // covered list (one host pass over the 4 B / texel owner map: ascending, deterministic) on both sides.
 struct LightmapTexels {
@@ -4099,20 +4111,11 @@ int lightmap_texels_make(const fw_lightmap *lm, int device, hipStream_t stream, 
 fw::DLightmapRays lightmap_rays_device(const fw_lightmap *lm, uint32_t round, const LightmapTexels &T, uint32_t first) {
     fw::DLightmapRays d{};
     d.directions = lm->directions;
-    d.seed32 = (uint32_t)lm->seed ^ ((uint32_t)(lm->seed >> 32) * 0x9E3779B9u);
+    d.seed32 = seed32_of(lm->seed);
     d.jitter = lm->jitter ? 1u : 0u;
     d.round = round; d.bias = lm->bias;
     d.texel_ids = T.list + first; d.records = (const float4 *)T.records;
     return d;
-}
-
-// the checks every entry point shares once its arguments are valid: a device is visible and `device` names one
-int lightmap_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
-    if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
-    HIPCHK(hipSetDevice(device));
-    return FW_OK;
 }
 
 int lightmap_texels_impl(const fw_lightmap *lm, int device, float *records, uint32_t *owner, uint32_t *n_covered, int on_device, void *stream_) {
@@ -4121,7 +4124,7 @@ int lightmap_texels_impl(const fw_lightmap *lm, int device, float *records, uint
     if (int rc = lightmap_check(lm, too_large)) return rc;
     if (on_device && (((uintptr_t)records & 15u) || ((uintptr_t)owner & 3u))) return fail(FW_ERR_BAD_ARG, "device records must be 16-byte aligned, device owner 4-byte aligned");
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "covered texels x directions must be below 2^31");
-    if (int rc = lightmap_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     LightmapTexels T(device);
     if (int rc = lightmap_texels_make(lm, device, stream, T)) return rc;
@@ -4144,12 +4147,11 @@ int lightmap_rays_impl(const fw_lightmap *lm, int device, uint32_t round, uint32
     if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
     if (on_device && ((uintptr_t)rays & 3u)) return fail(FW_ERR_BAD_ARG, "rays must be 4-byte aligned");
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "covered texels x directions must be below 2^31");
-    if (int rc = lightmap_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     LightmapTexels T(device);
     if (int rc = lightmap_texels_make(lm, device, stream, T)) return rc;
     if ((uint64_t)first + n > T.h_list.size()) { (void)hipStreamSynchronize(stream); return fail(FW_ERR_BAD_ARG, "first + n exceeds the covered list (" + std::to_string(T.h_list.size()) + " texels)"); }
-    const size_t D = lm->directions;
     const int n_cus = device_cus(device);
     if (on_device) {
         fw::launch_lm_rays(stream, n_cus, lightmap_rays_device(lm, round, T, first), n, rays);
@@ -4157,17 +4159,9 @@ int lightmap_rays_impl(const fw_lightmap *lm, int device, uint32_t round, uint32
         HIPCHK(hipGetLastError());
         return FW_OK;
     }
-    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, LIGHTMAP_SCRATCH_BYTES / (D * 24)));
-    CallScratch out(device);
-    if (int rc = out.alloc((size_t)per * D * 24)) { (void)hipStreamSynchronize(stream); return rc; }
-    for (uint32_t done = 0; done < n; done += per) {
-        const uint32_t k = std::min(per, n - done);
-        fw::launch_lm_rays(stream, n_cus, lightmap_rays_device(lm, round, T, first + done), k, (float *)out.p);
-        HIPCHK(hipMemcpyAsync(rays + (size_t)done * D * 6, out.p, (size_t)k * D * 24, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-    }
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    return host_slabs(stream, device, n, (size_t)lm->directions * 24, rays, [&](uint32_t done, uint32_t k, float *d_rays) {
+        fw::launch_lm_rays(stream, n_cus, lightmap_rays_device(lm, round, T, first + done), k, d_rays);
+    });
 }
 
 int lightmap_reduce_impl(int device, uint32_t n, uint32_t directions, uint32_t samples, const uint32_t *texel_ids, const float *accum, float *sums,
@@ -4183,7 +4177,7 @@ int lightmap_reduce_impl(int device, uint32_t n, uint32_t directions, uint32_t s
     if (on_device && ((((uintptr_t)accum | (uintptr_t)sums) & 15u) || ((uintptr_t)texel_ids & 3u)))
         return fail(FW_ERR_BAD_ARG, "device accum and sums must be 16-byte aligned, device texel_ids 4-byte aligned");
     if ((uint64_t)n * directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
-    if (int rc = lightmap_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     const size_t entries = (size_t)n * directions, sum_bytes = (size_t)n_texels * 16;
     CallScratch scratch(device);
@@ -4217,7 +4211,7 @@ int lightmap_dilate_impl(int device, uint32_t width, uint32_t height, uint32_t p
     if (width == 0 || width > 16384u || height == 0 || height > 16384u) return fail(FW_ERR_BAD_ARG, "width and height must be in 1..16384");
     if (passes > 64u) return fail(FW_ERR_BAD_ARG, "passes must be in 0..64");
     if (on_device && ((uintptr_t)image & 15u)) return fail(FW_ERR_BAD_ARG, "a device image must be 16-byte aligned");
-    if (int rc = lightmap_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (passes == 0) return FW_OK;
     hipStream_t stream = (hipStream_t)stream_;
     const size_t bytes = (size_t)width * height * 16;
@@ -4235,8 +4229,9 @@ int lightmap_dilate_impl(int device, uint32_t width, uint32_t height, uint32_t p
     return FW_OK;
 }
 
-// fw_bake_lightmap: per round and chunk of the covered list, k_lm_rays into the call's scratch, render_impl over those device rays into a
-// zeroed accum of the scratch — the fw_render_rays call of the chunk (rays_impl's frame) — then k_lm_reduce into the running sums.
+// fw_bake_lightmap: its own are the argument checks, the texels, the scratch (a chunk's rays and accum, the running sums and the
+// irradiance unless the caller's device memory holds them, the dilation's second image), k_lm_rays and k_lm_reduce over the covered list
+// as bake_rounds' generator and reducer, and the irradiance: k_lm_resolve and the dilation.
 int bake_lightmap_impl(fw_scene *sc, const fw_lightmap *lm, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, uint32_t dilate,
                        float *sums, float *irradiance, fw_stats *stats) {
     if (!sc || !lm || !rp) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -4249,8 +4244,7 @@ int bake_lightmap_impl(fw_scene *sc, const fw_lightmap *lm, const fw_render_rays
     if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
     if (rp->on_device && (((uintptr_t)sums | (uintptr_t)irradiance) & 15u)) return fail(FW_ERR_BAD_ARG, "device sums and irradiance must be 16-byte aligned");
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "covered texels x directions must be below 2^31");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (int rc = need_device()) return rc;
     const auto wall0 = std::chrono::steady_clock::now();
     const int dev = sc->device;
     HIPCHK(hipSetDevice(dev));
@@ -4260,7 +4254,7 @@ int bake_lightmap_impl(fw_scene *sc, const fw_lightmap *lm, const fw_render_rays
     const uint32_t N = (uint32_t)T.h_list.size(), D = lm->directions, S = rp->samples;
     const size_t n_tex = (size_t)lm->width * lm->height, img_bytes = n_tex * 16;
     const uint32_t chunk = std::max<uint32_t>(1u, std::min<uint32_t>(N, lm->chunk_texels ? lm->chunk_texels
-                                                                                         : (uint32_t)std::max<uint64_t>(1, LIGHTMAP_SCRATCH_BYTES / ((uint64_t)D * 40))));
+                                                                                         : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 40))));
     const bool own_sums = !rp->on_device || !sums;        // the running sums live in the scratch: a host caller's, or nobody's
     const bool own_irr = irradiance && !rp->on_device;
     const size_t o_acc = align256((size_t)chunk * D * 24), o_sums = o_acc + align256((size_t)chunk * D * 16),
@@ -4273,48 +4267,13 @@ int bake_lightmap_impl(fw_scene *sc, const fw_lightmap *lm, const fw_render_rays
         if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, img_bytes, hipMemcpyHostToDevice, stream));
         else HIPCHK(hipMemsetAsync(d_sums, 0, img_bytes, stream));
     }
-    ProbeEvents ev;                                   // around the two kernels' launches, only when the caller reads stats
-    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
     const int n_cus = device_cus(dev);
-    const bool timing = (rp->flags & FW_FLAG_TIME_KERNELS) != 0;
-
     fw_stats total{};
-    for (uint32_t r = first_round; r - first_round < rounds; r++) {
-        fw_render_rays_params q = *rp;
-        q.gamma = 1.f; q.on_device = 1; q.seed = rp->seed + r;
-        for (uint32_t q0 = 0; q0 < N; q0 += chunk) {
-            const uint32_t k = std::min(chunk, N - q0), n = k * D;
-            q.n_rays = n;
-            if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
-            fw::launch_lm_rays(stream, n_cus, lightmap_rays_device(lm, r, T, q0), k, d_rays);
-            if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
-            HIPCHK(hipMemsetAsync(d_acc, 0, (size_t)n * 16, stream));
-            const fw_render_params P = rays_frame(&q, S);
-            const RayInput ri{d_rays, n, false, nullptr, q0 * D, true};
-            fw_stats gs{};
-            if (int rc = render_impl(sc, &P, nullptr, nullptr, nullptr, stats ? &gs : nullptr, 0, d_acc, nullptr, nullptr, &ri)) { (void)hipStreamSynchronize(stream); return rc; }
-            if (stats) HIPCHK(hipEventRecord(ev.e[2], stream));
-            fw::launch_lm_reduce(stream, n_cus, k, D, S, T.list + q0, d_acc, d_sums);
-            if (!stats) continue;
-            HIPCHK(hipEventRecord(ev.e[3], stream));
-            HIPCHK(hipEventSynchronize(ev.e[3]));
-            float gen_ms = 0.f, red_ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
-            HIPCHK(hipEventElapsedTime(&red_ms, ev.e[2], ev.e[3]));
-            total.samples += gs.samples; total.rays += gs.rays;
-            for (int d = 0; d < FW_MAX_SEGMENTS; d++) total.rays_per_depth[d] += gs.rays_per_depth[d];
-            total.algorithmic_bytes += gs.algorithmic_bytes;
-            total.ms_render += gs.ms_render + gen_ms + red_ms; total.ms_raygen += gs.ms_raygen + (timing ? gen_ms : 0.f);
-            total.ms_extend += gs.ms_extend; total.ms_shade += gs.ms_shade; total.ms_accumulate += gs.ms_accumulate + (timing ? red_ms : 0.f);
-            total.ms_d2h += gs.ms_d2h;
-            total.n_extend_launches += gs.n_extend_launches; total.n_shade_launches += gs.n_shade_launches; total.n_batches += gs.n_batches;
-            total.tlas_nodes = gs.tlas_nodes; total.blas_nodes = gs.blas_nodes; total.reserved = gs.reserved;
-            total.bytes_raygen += gs.bytes_raygen + (uint64_t)n * 24 + (uint64_t)k * 36;     // (the generator's stores, its records and ids)
-            total.bytes_extend += gs.bytes_extend; total.bytes_shade += gs.bytes_shade;
-            total.bytes_accumulate += gs.bytes_accumulate + (uint64_t)n * 16 + (uint64_t)k * 28;     // (the reduction's loads and its sums)
-            total.deposits += gs.deposits; total.parked_rays += gs.parked_rays;
-        }
-    }
+    const BakeRounds b{first_round, rounds, N, D, chunk, d_rays, d_acc, 36, 16, 28};       // (the generator's records and ids; the reduction's loads and its sums)
+    if (int rc = bake_rounds(sc, rp, b, stats ? &total : nullptr,
+            [&](uint32_t r, uint32_t q0, uint32_t k, float *rays) { fw::launch_lm_rays(stream, n_cus, lightmap_rays_device(lm, r, T, q0), k, rays); },
+            [&](uint32_t q0, uint32_t k, const float *, const float *acc) { fw::launch_lm_reduce(stream, n_cus, k, D, S, T.list + q0, acc, d_sums); }))
+        return rc;
     // the outputs: sums where the caller keeps them; irradiance = sums / rounds so far on covered texels, then the dilation
     if (!rp->on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, img_bytes, hipMemcpyDeviceToHost, stream));
     if (irradiance) {
@@ -4639,10 +4598,7 @@ int fw_debug_ab(void) { return 1; }      // present only in the A/B build: tests
 
 int fw_init(int device, uint64_t arena_bytes) {
     try {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(FW_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)"); }
-        if (device < 0 || device >= ndev) return fail(FW_ERR_BAD_ARG, "device index out of range");
-        HIPCHK(hipSetDevice(device));
+        if (int rc = use_device(device)) return rc;
         Workspace *ws = workspace_for(device);
         if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
         std::lock_guard<std::mutex> g(ws->mu);
