@@ -32,7 +32,11 @@ positions, sh, sums, rounds, directions and samples; --light-sampling, --env-sam
 [--lightmap-rounds R] [--lightmap-dilate N] (no image: the irradiance over the W x H UV texels of render object OBJECT, which must be
 a triangle mesh with uvs, D cosine-weighted directions per texel, default 64, R rounds of -s samples per direction, default 1, N
 dilation passes over the seams, default 2, baked on the device, fw_bake_lightmap; -o names an .npz with irradiance,
-sums, owner, rounds, directions and samples; the sampling flags apply; refuses what --bake-probes refuses, and --bake-probes)."""
+sums, owner, rounds, directions and samples; the sampling flags apply; refuses what --bake-probes refuses, and --bake-probes).
+--probe-lit PROBES.npz [--probe-no-wrap] (a preview of the fixed view lit from the probes a --bake-probes run saved: one first-hit pass
+of --aov-samples samples and no paths, direct and indirect diffuse light both looked up in the grid, fw_probe_shade; the
+file must hold sh, grid_lo, grid_hi and grid_counts; --probe-no-wrap turns the guard against probes behind the surface off; -s is
+not used; refuses what --bake-probes refuses, --bake-probes and --bake-lightmap)."""
 import argparse
 import sys
 import time
@@ -88,7 +92,21 @@ def main(argv=None):
     ap.add_argument("--lightmap-dirs", type=int, default=None, metavar="D", help="with --bake-lightmap: directions per texel and round (default 64)")
     ap.add_argument("--lightmap-rounds", type=int, default=None, metavar="R", help="with --bake-lightmap: rounds of -s samples per direction (default 1)")
     ap.add_argument("--lightmap-dilate", type=int, default=None, metavar="N", help="with --bake-lightmap: dilation passes over the seams, 0..64 (default 2)")
+    ap.add_argument("--probe-lit", default=None, metavar="PROBES.npz",
+                    help="render the view lit from the irradiance probes that a --bake-probes run saved, without tracing paths")
+    ap.add_argument("--probe-no-wrap", action="store_true", help="with --probe-lit: no guard against light from probes behind the surface")
     opt = ap.parse_args(argv)
+    if opt.probe_lit is not None:
+        if (opt.bake_probes is not None or opt.bake_lightmap is not None or opt.camera != "pinhole" or opt.denoise is not None or opt.orbit
+                or opt.adaptive is not None or opt.progressive > 0 or opt.checkpoint or opt.temporal is not None):
+            ap.error("--probe-lit cannot be combined with --bake-probes, --bake-lightmap, --camera, --denoise, --orbit, --adaptive, "
+                     "--progressive, --checkpoint or --temporal")
+        if opt.aov_samples < 1:
+            ap.error("--aov-samples needs S >= 1")
+        if not opt.output:
+            ap.error("--probe-lit needs -o FILE.png")
+    elif opt.probe_no_wrap:
+        ap.error("--probe-no-wrap needs --probe-lit")
     if opt.bake_lightmap is not None:
         if (opt.bake_probes is not None or opt.camera != "pinhole" or opt.denoise is not None or opt.orbit or opt.adaptive is not None
                 or opt.progressive > 0 or opt.checkpoint or opt.temporal is not None):
@@ -191,6 +209,24 @@ def main(argv=None):
             print(f"firework: error: --bake-lightmap: {e}", file=sys.stderr)
             return 2
 
+    probe_grid = probe_sh = None
+    if opt.probe_lit is not None:          # the file is looked at before the device is: a wrong one is a message, not a traceback
+        import zipfile
+        import numpy as np
+        from .api import ProbeGrid
+        try:
+            with np.load(opt.probe_lit) as z:
+                missing = [k for k in ("sh", "grid_lo", "grid_hi", "grid_counts") if k not in z.files]
+                if missing:
+                    raise ValueError(f"no {', '.join(missing)} in it (bake it with this version's --bake-probes: only a grid can be looked up)")
+                probe_grid = ProbeGrid(z["grid_lo"], z["grid_hi"], z["grid_counts"], not opt.probe_no_wrap)
+                probe_sh = np.asarray(z["sh"], np.float32)
+            if probe_sh.shape != (probe_grid.n_probes, 9, 3):
+                raise ValueError(f"sh has shape {probe_sh.shape}, the grid {probe_grid.n_probes} probes")
+        except (OSError, ValueError, zipfile.BadZipFile) as e:
+            print(f"firework: error: --probe-lit {opt.probe_lit}: {e}", file=sys.stderr)
+            return 2
+
     _lib.init(opt.device)      # fw_init: context, code objects and the path arena before the timed region, like the loading of the reference's binary (main.rs:40)
 
     if scene is None:
@@ -211,7 +247,14 @@ def main(argv=None):
         print(f'Saving {probes.n_probes} probes to "{opt.output}"')
         with open(opt.output, "wb") as f:       # (np.savez would append .npz to a name without it)
             np.savez(f, positions=probes.positions, sh=sh, sums=sums, rounds=np.int64(rounds), directions=np.int64(probes.directions),
-                     samples=np.int64(opt.samples))
+                     samples=np.int64(opt.samples), grid_lo=np.array(probes.grid_lo, np.float64), grid_hi=np.array(probes.grid_hi, np.float64),
+                     grid_counts=np.array(probes.grid_counts, np.int64))
+        return 0
+    if probe_grid is not None:
+        render = renderer.render_probe_lit(scene, probe_grid, probe_sh, opt.aov_samples, device=opt.device).rgb8
+        print(f"Finished Rendering in {int(time.time() - start)} s")
+        print(f'Saving image to "{opt.output}"')
+        save_image(render, opt.output, opt.width, opt.height)
         return 0
     if lightmap is not None:
         import numpy as np

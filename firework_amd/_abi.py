@@ -173,6 +173,18 @@ class fw_probe_set(C.Structure):
     _fields_ = [("n_probes", u32), ("positions", C.POINTER(f32)), ("directions", u32), ("jitter", i32), ("seed", u64), ("chunk_probes", u32)]
 
 
+# baked probes read back (include/firework_hip.h: fw_probe_irradiance, fw_probe_shade)
+FW_PROBE_WRAP = 1
+
+
+class fw_probe_grid(C.Structure):
+    _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("counts", u32 * 3), ("flags", u32)]
+
+
+class fw_probe_shade_params(C.Structure):
+    _fields_ = [("width", u32), ("height", u32), ("gamma", f32), ("device", i32), ("on_device", i32), ("stream", C.c_void_p)]
+
+
 # lightmaps on the device (include/firework_hip.h: fw_lightmap_texels, fw_lightmap_rays, fw_lightmap_reduce, fw_lightmap_dilate,
 # fw_bake_lightmap)
 class fw_lightmap(C.Structure):

@@ -123,6 +123,12 @@ def load(preload=False, device=None):
     lib.fw_bake_probes.restype = C.c_int
     lib.fw_bake_probes.argtypes = [C.c_void_p, C.POINTER(A.fw_probe_set), C.POINTER(A.fw_render_rays_params), C.c_uint32, C.c_uint32, C.c_void_p,
                                    C.c_void_p, C.POINTER(A.fw_stats)]
+    lib.fw_probe_irradiance.restype = C.c_int
+    lib.fw_probe_irradiance.argtypes = [C.POINTER(A.fw_probe_grid), C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                        C.c_int, C.c_void_p]
+    lib.fw_probe_shade.restype = C.c_int
+    lib.fw_probe_shade.argtypes = [C.POINTER(A.fw_probe_grid), C.c_void_p, C.POINTER(A.fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]
     lib.fw_lightmap_texels.restype = C.c_int
     lib.fw_lightmap_texels.argtypes = [C.POINTER(A.fw_lightmap), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_void_p]
     lib.fw_lightmap_rays.restype = C.c_int
@@ -478,6 +484,85 @@ def probe_project(rays, accum, samples, directions, sums=None, device=0, stream=
     _host_f32(sums, (n, 9, 3), "sums")
     _check(lib, lib.fw_probe_project(int(device), n, d, int(samples), r.ctypes.data, a.ctypes.data, sums.ctypes.data, 0, None))
     return sums
+
+
+def _grid_abi(grid):
+    """(fw_probe_grid, its probe count) from an api.ProbeGrid, or an api.ProbeSet made by ProbeSet.grid (wrap on)"""
+    from .api import ProbeGrid
+    g = ProbeGrid.of(grid)
+    return g.to_abi(), g.n_probes
+
+
+def probe_irradiance(grid, sh, positions, normals, out=None, stream=None, device=0):
+    """fw_probe_irradiance: the irradiance the probe grid `grid` (an api.ProbeGrid, or an api.ProbeSet made by ProbeSet.grid) with the
+    coefficients sh (n, 9, 3) float32 gives at the points `positions` with the normals `normals`, (N, 3) float32 each; not clamped.
+    numpy arrays: returns an (N, 3) float32 array (out: a contiguous float32 array of that shape to fill instead).  Torch tensors on
+    cuda:`device`: looked up on `stream` (default: the current torch stream) where they lie, positions and normals contiguous (N, 3)
+    or two column ranges of one contiguous (N, S) tensor such as fw_render_aovs' records (aov[:, 8:11], aov[:, 4:7]); returns a device
+    tensor (out: a contiguous (N, 3) float32 tensor to fill instead)."""
+    lib = load()
+    g, n_probes = _grid_abi(grid)
+    if type(positions).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(sh, (n_probes, 9, 3), torch.float32, device, "sh")
+        n = int(positions.shape[0])
+        stride = int(positions.stride(0)) if n > 1 else max(3, int(positions.stride(0)))
+        for t, name in ((positions, "positions"), (normals, "normals")):
+            if (t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (n, 3) or t.stride(1) != 1 or t.device.type != "cuda"
+                    or (t.device.index or 0) != device or (n > 1 and int(t.stride(0)) != stride) or stride < 3):
+                raise ValueError(f"{name} must be an (N, 3) float32 tensor on cuda:{device} with unit column stride and the same row stride >= 3 as the other")
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float32, device=positions.device)
+        _check_device_tensor(out, (n, 3), torch.float32, device, "out")
+        _check(lib, lib.fw_probe_irradiance(C.byref(g), sh.data_ptr(), int(device), n, positions.data_ptr(), normals.data_ptr(), stride,
+                                            out.data_ptr(), 1, _stream_arg(stream, positions.device)))
+        return out
+    s = np.ascontiguousarray(np.asarray(sh, np.float32).reshape(n_probes, 9, 3))
+    p = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))
+    nr = np.ascontiguousarray(np.asarray(normals, np.float32).reshape(-1, 3))
+    if nr.shape != p.shape:
+        raise ValueError("positions and normals must have the same shape (N, 3)")
+    if out is None:
+        out = np.empty(p.shape, np.float32)
+    _host_f32(out, p.shape, "out")
+    _check(lib, lib.fw_probe_irradiance(C.byref(g), s.ctypes.data, int(device), int(p.shape[0]), p.ctypes.data, nr.ctypes.data, 3, out.ctypes.data,
+                                        0, None))
+    return out
+
+
+def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear")):
+    """fw_probe_shade: fw_render_aovs' records `aov` (N, 12) lit from the probe grid `grid` (see probe_irradiance) with the coefficients
+    sh (n, 9, 3): out = albedo (coverage max(E, 0) / pi + (1 - coverage)), resolved as fw_denoise resolves its outputs.  All host arrays
+    (numpy): returns (rgb8, gamma, linear) host arrays of shape (N, 3).  Contiguous float32 torch tensors on cuda:`device`: shaded on
+    `stream` (default: the current torch stream), returns device tensors.  outputs: which of the three to compute; the others are
+    returned as None.  width * height must be N."""
+    lib = load()
+    g, n_probes = _grid_abi(grid)
+    n = int(width) * int(height)
+    p = A.fw_probe_shade_params()
+    p.width, p.height, p.gamma, p.device = int(width), int(height), float(gamma), int(device)
+    want = [name in outputs for name in ("rgb8", "gamma", "linear")]
+    if type(aov).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(sh, (n_probes, 9, 3), torch.float32, device, "sh")
+        _check_device_tensor(aov, (n, 12), torch.float32, device, "aov")
+        dev = aov.device
+        rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev) if want[0] else None
+        gam = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[1] else None
+        lin = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[2] else None
+        p.on_device = 1
+        p.stream = _stream_arg(stream, dev)
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        _check(lib, lib.fw_probe_shade(C.byref(g), sh.data_ptr(), C.byref(p), aov.data_ptr(), ptr(lin), ptr(gam), ptr(rgb8)))
+        return rgb8, gam, lin
+    s = np.ascontiguousarray(np.asarray(sh, np.float32).reshape(n_probes, 9, 3))
+    a = np.ascontiguousarray(np.asarray(aov, np.float32).reshape(n, 12))
+    rgb8 = np.empty((n, 3), np.uint8) if want[0] else None
+    gam = np.empty((n, 3), np.float32) if want[1] else None
+    lin = np.empty((n, 3), np.float32) if want[2] else None
+    ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
+    _check(lib, lib.fw_probe_shade(C.byref(g), s.ctypes.data, C.byref(p), a.ctypes.data, ptr(lin), ptr(gam), ptr(rgb8)))
+    return rgb8, gam, lin
 
 
 def _lightmap_abi(lightmap, chunk=None):

@@ -1170,17 +1170,21 @@ class ProbeSet:
         self.positions = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))
         self.directions = int(directions)
         self._seed, self._jitter, self.chunk_probes = 0, True, 0
+        self.grid_lo = self.grid_hi = self.grid_counts = None      # set by ProbeSet.grid: what fw_probe_irradiance needs to read sh back
 
     @staticmethod
     def grid(lo, hi, counts, directions: int = 256) -> "ProbeSet":
         """nx x ny x nz probes on a regular grid from corner lo to corner hi, both included (a count of 1 sits at the middle), x
-        fastest, then y, then z"""
+        fastest, then y, then z.  The set remembers the grid: .grid_lo and .grid_hi (float64 triples) and .grid_counts."""
         lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
         if len(counts) != 3 or any(int(n) < 1 for n in counts):
             raise ValueError("counts must be three numbers >= 1")
         axes = [np.linspace(lo[k], hi[k], int(counts[k])) if int(counts[k]) > 1 else np.array([0.5 * (lo[k] + hi[k])]) for k in range(3)]
         z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
-        return ProbeSet(np.stack([x, y, z], axis=-1).reshape(-1, 3), directions)
+        out = ProbeSet(np.stack([x, y, z], axis=-1).reshape(-1, 3), directions)
+        out.grid_lo, out.grid_hi = tuple(float(v) for v in lo), tuple(float(v) for v in hi)
+        out.grid_counts = tuple(int(n) for n in counts)
+        return out
 
     @property
     def n_probes(self) -> int:
@@ -1226,6 +1230,124 @@ class ProbeSet:
         s.directions, s.jitter = self.directions, int(self._jitter)
         s.seed, s.chunk_probes = self._seed & 0xFFFFFFFFFFFFFFFF, int(self.chunk_probes)
         return s, self.positions
+
+
+# --------------------------------------------------------------------------- baked probes read back
+class ProbeGrid:
+    """A probe grid as fw_probe_irradiance and fw_probe_shade read it (fw_probe_grid): the corners and counts ProbeSet.grid was given,
+    and wrap = FW_PROBE_WRAP.  ProbeGrid(lo, hi, counts, wrap=True), or ProbeGrid.of(probes, wrap=True) from a ProbeSet made by
+    ProbeSet.grid (a free ProbeSet: ValueError)."""
+
+    def __init__(self, lo, hi, counts, wrap: bool = True):
+        self.lo, self.hi = tuple(float(v) for v in lo), tuple(float(v) for v in hi)
+        self.counts = tuple(int(n) for n in counts)
+        if len(self.lo) != 3 or len(self.hi) != 3 or len(self.counts) != 3 or min(self.counts) < 1:
+            raise ValueError("a probe grid needs two corners of three numbers and three counts >= 1")
+        self.wrap = bool(wrap)
+
+    @staticmethod
+    def of(grid, wrap: bool = True) -> "ProbeGrid":
+        if isinstance(grid, ProbeGrid):
+            return grid
+        if getattr(grid, "grid_counts", None) is None:
+            raise ValueError("the probes have no grid: only a ProbeSet made by ProbeSet.grid can be looked up")
+        return ProbeGrid(grid.grid_lo, grid.grid_hi, grid.grid_counts, wrap)
+
+    @property
+    def n_probes(self) -> int:
+        return self.counts[0] * self.counts[1] * self.counts[2]
+
+    def to_abi(self) -> A.fw_probe_grid:
+        g = A.fw_probe_grid()
+        for k in range(3):
+            g.lo[k], g.hi[k], g.counts[k] = self.lo[k], self.hi[k], self.counts[k]
+        g.flags = A.FW_PROBE_WRAP if self.wrap else 0
+        return g
+
+
+def probe_lookup(grid, sh, positions, normals, terms: bool = False) -> np.ndarray:
+    """The numpy float64 statement of fw_probe_irradiance (include/firework_hip.h): the irradiance (N, 3) float64 — before the device's
+    one rounding to float32 — that the grid `grid` (a ProbeGrid, or a ProbeSet made by ProbeSet.grid: wrap on) with the coefficients sh
+    (n, 9, 3) gives at the float32 points `positions` with the float32 normals `normals`, (N, 3) each.  Every operation is written in
+    the header's order; only + - * /, floor, min, max and sqrt are used.  terms=True: returns (E, T) with T (N, 3) =
+    sum over corners and k of |w B_k sh|, what a rounding-error bound of the sum scales with."""
+    g = ProbeGrid.of(grid)
+    sh = np.asarray(sh, np.float32).astype(np.float64).reshape(g.n_probes, 9, 3)
+    p = np.asarray(positions, np.float32).astype(np.float64).reshape(-1, 3)
+    nr = np.asarray(normals, np.float32).astype(np.float64).reshape(-1, 3)
+    n = p.shape[0]
+    E, T = np.zeros((n, 3)), np.zeros((n, 3))
+    with np.errstate(all="ignore"):
+        nl2 = (nr[:, 0] * nr[:, 0] + nr[:, 1] * nr[:, 1]) + nr[:, 2] * nr[:, 2]
+        ok = np.all(np.isfinite(p), axis=1) & np.all(np.isfinite(nr), axis=1) & (nl2 > 0.0)
+        nl = np.sqrt(nl2)
+        nh = nr / nl[:, None]
+        x, y, z = nh[:, 0], nh[:, 1], nh[:, 2]
+        idx, f, two = [], [], []
+        for k in range(3):
+            c = g.counts[k]
+            two.append(c > 1)
+            if c > 1:
+                cm1 = float(c - 1)
+                s = ((p[:, k] - g.lo[k]) / (g.hi[k] - g.lo[k])) * cm1
+                s = np.fmin(np.fmax(s, 0.0), cm1)
+                fl = np.fmin(np.floor(s), cm1 - 1.0)
+                idx.append(np.where(ok, fl, 0.0).astype(np.int64))
+                f.append(s - fl)
+            else:
+                idx.append(np.zeros(n, np.int64))
+                f.append(np.zeros(n))
+        corners = [(dx, dy, dz) for dz in range(2 if two[2] else 1) for dy in range(2 if two[1] else 1) for dx in range(2 if two[0] else 1)]
+        w = []
+        for d in corners:
+            wk = [f[k] if d[k] else 1.0 - f[k] for k in range(3)]
+            wd = (wk[0] * wk[1]) * wk[2]
+            if g.wrap:
+                r = []
+                for k in range(3):
+                    if two[k]:
+                        pk = g.lo[k] + (idx[k] + d[k]).astype(np.float64) * ((g.hi[k] - g.lo[k]) / float(g.counts[k] - 1))
+                    else:
+                        pk = 0.5 * (g.lo[k] + g.hi[k])
+                    r.append(pk - p[:, k])
+                rl2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]
+                rl = np.sqrt(rl2)
+                dot = (x * (r[0] / rl) + y * (r[1] / rl)) + z * (r[2] / rl)
+                h = 0.5 * (dot + 1.0)
+                wd = wd * np.where(rl2 > 0.0, h * h + 0.2, 1.2)
+            w.append(wd)
+        if g.wrap:
+            wsum = np.zeros(n)
+            for wd in w:
+                wsum = wsum + wd
+            w = [wd / wsum for wd in w]
+        B = sh_basis(nh) * _SH_COSINE
+        for d, wd in zip(corners, w):
+            probe = ((idx[2] + d[2]) * g.counts[1] + (idx[1] + d[1])) * g.counts[0] + (idx[0] + d[0])
+            c = sh[probe]                                                  # (N, 9, 3)
+            e = B[:, 0, None] * c[:, 0]
+            t = np.abs(e)
+            for k in range(1, 9):
+                term = B[:, k, None] * c[:, k]
+                e = e + term
+                t = t + np.abs(term)
+            E = E + wd[:, None] * e
+            T = T + np.abs(wd)[:, None] * t
+    E[~ok] = 0.0
+    T[~ok] = 0.0
+    return (E, T) if terms else E
+
+
+def probe_shade_ref(grid, sh, aov, irradiance=None) -> np.ndarray:
+    """The float32 statement of fw_probe_shade's shade step, (N, 3) float32 linear colours (before resolve_pixel): with E = probe_lookup
+    at the records' (position, normal) rounded to float32 — or `irradiance`, (N, 3) float32, when given — and clamped at 0,
+    out_c = a_c (v (E_c float32(1 / pi)) + (1 - v)) for fw_render_aovs' records aov (N, 12)."""
+    a = np.asarray(aov, np.float32).reshape(-1, 12)
+    E = probe_lookup(grid, sh, a[:, 8:11], a[:, 4:7]).astype(np.float32) if irradiance is None else np.asarray(irradiance, np.float32).reshape(-1, 3)
+    E = np.where(E > 0, E, np.float32(0.0)).astype(np.float32)
+    v = a[:, 3:4]
+    inv_pi = np.float32(1.0 / np.pi)
+    return (a[:, 0:3] * (v * (E * inv_pi) + (np.float32(1.0) - v))).astype(np.float32)
 
 
 # --------------------------------------------------------------------------- lightmaps (fw_bake_lightmap; DESIGN.md §9o)
@@ -1860,6 +1982,34 @@ class Renderer:
         finally:
             if ds is not scene:
                 ds.close()
+
+    def render_probe_lit(self, scene, probes, sh, aov_samples: int = 8, wrap: bool = True, device: int = 0, model: "CameraModel" = None) -> RenderResult:
+        """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
+        (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
+        from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
+        sh (n, 9, 3), as bake_probes returns them.  One first-hit pass and no paths: direct and indirect diffuse light both come from the
+        probes.  The records stay on the device.  A ProbeSet without a grid: ValueError.  `scene`: a Scene, a SceneDesc or an uploaded
+        _lib.DeviceScene."""
+        import torch
+        from . import _lib
+        grid = ProbeGrid.of(probes, wrap)
+        s = self.settings
+        w, h = (int(model.width), int(model.height)) if model is not None else (int(s["width"]), int(s["height"]))
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            dev = torch.device("cuda", ds.device)
+            aov = torch.empty((w * h, 12), dtype=torch.float32, device=dev)
+            if model is not None:
+                ds.model_aovs(model, aov_samples, seed=s["seed"], use_bvh=s["use_bvh"], out=aov)
+            else:
+                ds.aovs(self, aov_samples, out=aov)
+            d_sh = torch.from_numpy(np.ascontiguousarray(np.asarray(sh, np.float32).reshape(grid.n_probes, 9, 3))).to(dev)
+            rgb8, gam, lin = _lib.probe_shade(grid, d_sh, aov, w, h, s["gamma"], ds.device)
+            stats = dict(ds.aovs_stats)
+        finally:
+            if ds is not scene:
+                ds.close()
+        return RenderResult(rgb8.cpu().numpy(), gam.cpu().numpy(), lin.cpu().numpy(), stats, w, h)
 
     def model_aovs(self, scene, model: "CameraModel", samples: int = 8, device: int = 0) -> dict:
         """aovs() for a CameraModel (fw_render_model_aovs): the first-hit guide buffers of the model's rays, keyed as render_model keys

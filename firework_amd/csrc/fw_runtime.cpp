@@ -14,6 +14,7 @@
 #include "fw_camera_models.h"
 #include "fw_probes.h"
 #include "fw_lightmap.h"
+#include "fw_probe_lookup.h"
 
 #include <algorithm>
 #include <atomic>
@@ -4291,6 +4292,128 @@ int bake_lightmap_impl(fw_scene *sc, const fw_lightmap *lm, const fw_render_rays
     return FW_OK;
 }
 
+// ---- baked probes read back (include/firework_hip.h) -------------------------------------------------------------
+// The grid's own argument checks (FW_ERR_BAD_ARG only) and what the kernels need of it.  too_large: nx ny nz >= 2^31, which the callers
+// report as FW_ERR_UNSUPPORTED after their own argument checks.
+int probe_grid_check(const fw_probe_grid *g, bool &too_large, fw::DProbeGrid &d) {
+    for (int k = 0; k < 3; k++)
+        if (g->counts[k] == 0) return fail(FW_ERR_BAD_ARG, "every count of a probe grid must be > 0");
+    for (int k = 0; k < 3; k++) {
+        if (!std::isfinite(g->lo[k]) || !std::isfinite(g->hi[k])) return fail(FW_ERR_BAD_ARG, "a probe grid's corners must be finite");
+        if (g->counts[k] > 1 && g->hi[k] == g->lo[k]) return fail(FW_ERR_BAD_ARG, "a probe grid axis with more than one probe needs hi != lo");
+        if (!std::isfinite(g->hi[k] - g->lo[k])) return fail(FW_ERR_BAD_ARG, "a probe grid's hi - lo must be finite");
+    }
+    if (g->flags & ~(uint32_t)FW_PROBE_WRAP) return fail(FW_ERR_BAD_ARG, "unknown probe grid flags");
+    const uint64_t xy = (uint64_t)g->counts[0] * g->counts[1];
+    too_large = xy >= (1ull << 31) || xy * g->counts[2] >= (1ull << 31);
+    for (int k = 0; k < 3; k++) {
+        d.lo[k] = g->lo[k];
+        d.span[k] = g->hi[k] - g->lo[k];
+        d.step[k] = g->counts[k] > 1 ? (g->hi[k] - g->lo[k]) / (double)(g->counts[k] - 1) : 0.0;
+        d.mid[k] = 0.5 * (g->lo[k] + g->hi[k]);
+        d.counts[k] = g->counts[k];
+    }
+    d.wrap = g->flags & FW_PROBE_WRAP;
+    return FW_OK;
+}
+
+// fw_probe_irradiance: with device arrays the kernel works on the caller's memory and nothing is allocated; with host arrays one device
+// allocation per call holds sh and a slab of points (24 B in, 12 B out each), released on every way out
+int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device, uint32_t n, const float *positions, const float *normals,
+                          uint32_t stride, float *irradiance, int on_device, void *stream_) {
+    if (!grid || !sh || !positions || !normals || !irradiance) return fail(FW_ERR_BAD_ARG, "null argument");
+    bool too_large = false;
+    fw::DProbeGrid g{};
+    if (int rc = probe_grid_check(grid, too_large, g)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    if (on_device && (((uintptr_t)sh | (uintptr_t)positions | (uintptr_t)normals | (uintptr_t)irradiance) & 3u))
+        return fail(FW_ERR_BAD_ARG, "device arrays must be 4-byte aligned");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (on_device) {
+        fw::launch_probe_irradiance(stream, g, sh, n, positions, normals, stride, irradiance);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+    const size_t sh_bytes = (size_t)g.counts[0] * g.counts[1] * g.counts[2] * 108;
+    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 36));
+    const size_t o_in = align256(sh_bytes), o_out = o_in + align256((size_t)per * 24);
+    std::vector<float> pack((size_t)per * 6);
+    CallScratch scratch(device);
+    if (int rc = scratch.alloc(o_out + (size_t)per * 12)) return rc;
+    uint8_t *base = (uint8_t *)scratch.p;
+    const float *d_in = (const float *)(base + o_in);
+    HIPCHK(hipMemcpyAsync(base, sh, sh_bytes, hipMemcpyHostToDevice, stream));
+    for (uint32_t done = 0; done < n; done += per) {
+        const uint32_t k = std::min(per, n - done);
+        for (uint32_t i = 0; i < k; i++) {
+            const float *ps = positions + (size_t)(done + i) * stride, *ns = normals + (size_t)(done + i) * stride;
+            float *o = pack.data() + (size_t)i * 6;
+            o[0] = ps[0]; o[1] = ps[1]; o[2] = ps[2]; o[3] = ns[0]; o[4] = ns[1]; o[5] = ns[2];
+        }
+        HIPCHK(hipMemcpyAsync(base + o_in, pack.data(), (size_t)k * 24, hipMemcpyHostToDevice, stream));
+        fw::launch_probe_irradiance(stream, g, (const float *)base, k, d_in, d_in + 3, 6, (float *)(base + o_out));
+        HIPCHK(hipMemcpyAsync(irradiance + (size_t)done * 3, base + o_out, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_probe_shade: as fw_probe_irradiance; a host call's slab holds 48 B of record and up to 27 B of outputs per pixel
+int probe_shade_impl(const fw_probe_grid *grid, const float *sh, const fw_probe_shade_params *p, const float *aov, float *linear_rgb,
+                     float *gamma_rgb, uint8_t *rgb8) {
+    if (!grid || !sh || !p || !aov) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (!linear_rgb && !gamma_rgb && !rgb8) return fail(FW_ERR_BAD_ARG, "at least one output is needed");
+    bool too_large = false;
+    fw::DProbeGrid g{};
+    if (int rc = probe_grid_check(grid, too_large, g)) return rc;
+    if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
+    if (!std::isfinite(p->gamma) || !(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
+    if (p->device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    if (p->on_device && (((uintptr_t)aov & 15u) || (((uintptr_t)sh | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device aov must be 16-byte aligned, device sh, linear_rgb and gamma_rgb 4-byte aligned");
+    const uint64_t full = (uint64_t)p->width * p->height;
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
+    if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
+    const int dev = p->device;
+    if (int rc = use_device(dev)) return rc;
+    hipStream_t stream = (hipStream_t)p->stream;
+    const uint32_t n = (uint32_t)full;
+    if (p->on_device) {
+        fw::launch_probe_shade(stream, g, sh, n, aov, p->gamma, rgb8, gamma_rgb, linear_rgb);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+    const size_t sh_bytes = (size_t)g.counts[0] * g.counts[1] * g.counts[2] * 108;
+    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 75));
+    size_t off = 0;
+    auto put = [&](size_t b) { const size_t at = off; off += align256(b); return at; };
+    const size_t o_sh = put(sh_bytes), o_aov = put((size_t)per * 48);
+    const size_t o_lin = linear_rgb ? put((size_t)per * 12) : 0, o_gam = gamma_rgb ? put((size_t)per * 12) : 0, o_8 = rgb8 ? put((size_t)per * 3) : 0;
+    CallScratch scratch(dev);
+    if (int rc = scratch.alloc(off)) return rc;
+    uint8_t *base = (uint8_t *)scratch.p;
+    HIPCHK(hipMemcpyAsync(base + o_sh, sh, sh_bytes, hipMemcpyHostToDevice, stream));
+    for (uint32_t done = 0; done < n; done += per) {
+        const uint32_t k = std::min(per, n - done);
+        HIPCHK(hipMemcpyAsync(base + o_aov, aov + (size_t)done * 12, (size_t)k * 48, hipMemcpyHostToDevice, stream));
+        fw::launch_probe_shade(stream, g, (const float *)(base + o_sh), k, (const float *)(base + o_aov), p->gamma,
+                               rgb8 ? base + o_8 : nullptr, gamma_rgb ? (float *)(base + o_gam) : nullptr, linear_rgb ? (float *)(base + o_lin) : nullptr);
+        if (linear_rgb) HIPCHK(hipMemcpyAsync(linear_rgb + (size_t)done * 3, base + o_lin, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
+        if (gamma_rgb) HIPCHK(hipMemcpyAsync(gamma_rgb + (size_t)done * 3, base + o_gam, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
+        if (rgb8) HIPCHK(hipMemcpyAsync(rgb8 + (size_t)done * 3, base + o_8, (size_t)k * 3, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
 } // namespace
 
 // =========================================================================================================
@@ -4720,6 +4843,20 @@ int fw_bake_probes(fw_scene *scene, const fw_probe_set *set, const fw_render_ray
     try { return bake_probes_impl(scene, set, rp, first_round, rounds, sums, sh, stats); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_probes"); }
+}
+
+int fw_probe_irradiance(const fw_probe_grid *grid, const float *sh, int device, uint32_t n, const float *positions, const float *normals,
+                        uint32_t stride_floats, float *irradiance, int on_device, void *stream) {
+    try { return probe_irradiance_impl(grid, sh, device, n, positions, normals, stride_floats, irradiance, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_irradiance"); }
+}
+
+int fw_probe_shade(const fw_probe_grid *grid, const float *sh, const fw_probe_shade_params *p, const float *aov, float *linear_rgb,
+                   float *gamma_rgb, uint8_t *rgb8) {
+    try { return probe_shade_impl(grid, sh, p, aov, linear_rgb, gamma_rgb, rgb8); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade"); }
 }
 
 int fw_lightmap_texels(const fw_lightmap *lm, int device, float *records, uint32_t *owner, uint32_t *n_covered, int on_device, void *stream) {

@@ -219,10 +219,12 @@ struct CameraModel {
 
 // Irradiance probes (fw_probe_set; not in the reference): positions with `directions` rays each and round, baked by Renderer::bake_probes into
 // nine SH coefficients (l <= 2) per probe and colour channel.  grid(): nx x ny x nz probes from corner lo to corner hi, both included (a
-// count of 1 sits at the middle), x fastest, then y, then z.
+// count of 1 sits at the middle), x fastest, then y, then z; the set keeps the grid (has_grid, grid_abi()), which is what
+// Renderer::probe_lit needs to read the coefficients back.
 struct ProbeSet {
     std::vector<float> positions;       // n x 3
     uint32_t directions = 256, chunk = 0; uint64_t seed_ = 0; bool jitter_ = true;
+    bool has_grid = false; double grid_lo[3] = {0, 0, 0}, grid_hi[3] = {0, 0, 0}; uint32_t grid_counts[3] = {0, 0, 0};
     static ProbeSet new_(const std::vector<Vec3> &at, uint32_t directions = 256) {
         ProbeSet r; r.directions = directions;
         for (const Vec3 &v : at) { r.positions.push_back(v.x); r.positions.push_back(v.y); r.positions.push_back(v.z); }
@@ -232,7 +234,16 @@ struct ProbeSet {
         auto at = [](float a, float b, uint32_t i, uint32_t n) { return n > 1 ? (float)((double)a + ((double)b - (double)a) * (double)i / (double)(n - 1)) : (float)(0.5 * ((double)a + (double)b)); };
         for (uint32_t z = 0; z < nz; z++) for (uint32_t y = 0; y < ny; y++) for (uint32_t x = 0; x < nx; x++) {
             r.positions.push_back(at(lo.x, hi.x, x, nx)); r.positions.push_back(at(lo.y, hi.y, y, ny)); r.positions.push_back(at(lo.z, hi.z, z, nz)); }
+        r.has_grid = true;
+        r.grid_lo[0] = lo.x; r.grid_lo[1] = lo.y; r.grid_lo[2] = lo.z; r.grid_hi[0] = hi.x; r.grid_hi[1] = hi.y; r.grid_hi[2] = hi.z;
+        r.grid_counts[0] = nx; r.grid_counts[1] = ny; r.grid_counts[2] = nz;
         return r; }
+    // the grid as fw_probe_irradiance / fw_probe_shade read it; a set made by new_() has none
+    fw_probe_grid grid_abi(bool wrap = true) const {
+        if (!has_grid) throw std::runtime_error("the probes have no grid: only a ProbeSet made by ProbeSet::grid can be looked up");
+        fw_probe_grid g{};
+        for (int k = 0; k < 3; k++) { g.lo[k] = grid_lo[k]; g.hi[k] = grid_hi[k]; g.counts[k] = grid_counts[k]; }
+        g.flags = wrap ? FW_PROBE_WRAP : 0u; return g; }
     size_t n_probes() const { return positions.size() / 3; }
     ProbeSet seed(uint64_t s) && { seed_ = s; return std::move(*this); }
     ProbeSet jitter(bool on) && { jitter_ = on; return std::move(*this); }
@@ -450,6 +461,31 @@ struct Renderer {   // render.rs:59-218; Default: 1920x1080, 128 spp, multithrea
         if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
         if (sums) *sums = std::move(acc);
         return sh; }
+
+    // A preview lit from baked probes (not in the reference; fw_render_aovs + fw_probe_shade): the first-hit guide buffers of this view at
+    // aov_samples samples, shaded from the grid `probes` (made by ProbeSet::grid) and its coefficients sh (n x 9 x 3, as bake_probes
+    // returns them): out = albedo (coverage max(E, 0) / pi + (1 - coverage)).  One first-hit pass and no paths; direct and indirect diffuse
+    // light both come from the probes.  wrap: FW_PROBE_WRAP, the guard against probes behind the surface.
+    std::vector<Color> probe_lit(const Scene &scene, const ProbeSet &probes, const std::vector<float> &sh, uint32_t aov_samples = 8, bool wrap = true,
+                                 fw_stats *stats = nullptr) const {
+        const fw_probe_grid grid = probes.grid_abi(wrap);
+        if (sh.size() != probes.n_probes() * 27) throw std::runtime_error("sh must hold 9 x 3 coefficients per probe");
+        Lowered low(scene);
+        fw_scene *sc = nullptr;
+        int rc = create_resident(scene, &low.desc, device_, &sc);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        fw_render_params p = params();
+        p.samples = aov_samples;
+        const size_t n = width_ * height_;
+        std::vector<float> aov(n * 12);
+        rc = fw_render_aovs(sc, &p, aov.data(), stats);
+        fw_scene_destroy(sc);
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        fw_probe_shade_params sp{(uint32_t)width_, (uint32_t)height_, p.gamma, device_, 0, nullptr};
+        std::vector<Color> buffer(n, Color{0, 0, 0});
+        rc = fw_probe_shade(&grid, sh.data(), &sp, aov.data(), nullptr, nullptr, reinterpret_cast<uint8_t *>(buffer.data()));
+        if (rc != FW_OK) throw std::runtime_error(std::string(fw_strerror(rc)) + " | " + fw_last_error());
+        return buffer; }
 
     // A denoised frame (not in the reference): samples() samples per pixel filtered by fw_denoise with `iterations` a-trous steps, guided by
     // fw_render_aovs at aov_samples samples.  The frame comes from fw_render_adaptive with min_samples = samples() (one round at the fixed

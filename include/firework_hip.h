@@ -802,6 +802,71 @@ int fw_probe_project(int device, uint32_t n_probes, uint32_t directions, uint32_
    frame graph are fw_render_rays'. */
 int fw_bake_probes(fw_scene *scene, const fw_probe_set *set, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, float *sums, float *sh, fw_stats *stats);
 
+/* ---- baked probes read back: irradiance at arbitrary points, and a frame lit from it (additive at ABI 8) --------------
+   A probe grid is the two corners and the three counts api.ProbeSet.grid was given; sh is what fw_bake_probes wrote for that set,
+   n x 9 x 3 float32 with n = nx ny nz, not repacked.  The lookup at a point p with normal n, everything in float64 from the float32
+   inputs, every operation rounded as written (api.probe_lookup is the numpy statement):
+     Cell, per axis k.  counts_k = 1: i_k = 0, f_k = 0 (a flat axis does not interpolate).  Otherwise
+         s = ((p_k - lo_k) / (hi_k - lo_k)) * (counts_k - 1), clamped to [0, counts_k - 1] (max, then min: a point outside the grid takes
+         the boundary's value);  i_k = min(floor(s), counts_k - 2);  f_k = s - i_k.
+     Corner weights.  Corner (dx, dy, dz) in {0, 1}^3 — on an axis with counts_k = 1 only d_k = 0 — has w = (wx * wy) * wz with
+         wx = 1 - f_x for dx = 0 and f_x for dx = 1, likewise wy and wz.
+     FW_PROBE_WRAP (the usual guard against light from probes behind the surface, without visibility data).  With
+         P_k = lo_k + (i_k + d_k) * ((hi_k - lo_k) / (counts_k - 1)), or 0.5 * (lo_k + hi_k) on a flat axis, r = P - p,
+         rl = sqrt((r_x r_x + r_y r_y) + r_z r_z) and nh = n / sqrt((n_x n_x + n_y n_y) + n_z n_z) per component:
+         h = 0.5 * (((nh_x * (r_x / rl) + nh_y * (r_y / rl)) + nh_z * (r_z / rl)) + 1);  w = w * (h * h + 0.2), or w * 1.2 when r is zero.
+         The weights are then divided by their sum, added in the order dz, dy, dx with dx fastest.  Without the flag the trilinear
+         weights are used as they are.
+     Irradiance.  B_k = A_k * Y_k(nh) with the basis above (Y4 = (C x) y, Y5 = (C y) z, Y7 = (C x) z, Y6 = C (3 (z z) - 1),
+         Y8 = C (x x - y y)) and the cosine lobe's band factors A = pi, 2 pi / 3 (k = 1..3), pi / 4 (k = 4..8), formed in double.  Per
+         corner and channel e = B_0 sh[probe][0][c] + B_1 sh[probe][1][c] + ... with k ascending;  E_c = 0 + w e (corner 0) + w e
+         (corner 1) + ... in the order dz, dy, dx with dx fastest;  E_c is rounded to float32 once.
+   A point whose position is not finite, or whose normal has a non-finite component or zero length, gets (0, 0, 0).
+   fw_probe_irradiance does not clamp: the negative lobes of an l <= 2 reconstruction are the caller's to see.  Every probe the lookup
+   reads is one of the grid's, wherever the point lies.  One lane per point, no atomics: the result is a pure function of the inputs. */
+#define FW_PROBE_WRAP 1u
+typedef struct fw_probe_grid {
+    double   lo[3], hi[3];    /* the two corners ProbeSet.grid was given */
+    uint32_t counts[3];       /* nx, ny, nz >= 1; probe (ix, iy, iz) is entry (iz ny + iy) nx + ix of sh: x fastest, as ProbeSet.grid */
+    uint32_t flags;           /* FW_PROBE_WRAP = 1u */
+} fw_probe_grid;
+
+/* fw_probe_irradiance: the lookup at n points.  positions and normals are read at i * stride_floats, three floats each: a stride of 3
+   is two packed arrays, a stride of 12 with the pointers aov + 8 and aov + 4 reads fw_render_aovs' records in place.  irradiance: n x 3
+   floats.  sh and the point arrays are host memory — staged through one device allocation of the call's own, the points in slabs of at
+   most 256 MiB, freed on every path — or with on_device device memory on `device` (the kernel then works on the caller's memory),
+   launched on `stream` and complete on return.  Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL grid, sh,
+   positions, normals or irradiance, a count of 0, a non-finite corner, hi_k == lo_k on an axis with counts_k > 1, a hi_k - lo_k that
+   overflows, unknown flag bits,
+   n == 0, stride_floats < 3, device < 0, with on_device an array not 4-byte aligned; FW_ERR_UNSUPPORTED for nx ny nz >= 2^31; then
+   FW_ERR_NO_DEVICE without a GPU, and FW_ERR_BAD_ARG for a device index past the last one. */
+int fw_probe_irradiance(const fw_probe_grid *grid, const float *sh, int device, uint32_t n, const float *positions, const float *normals,
+                        uint32_t stride_floats, float *irradiance, int on_device, void *stream);
+
+/* fw_probe_shade: a frame's guide buffers lit from the grid.  aov = fw_render_aovs' records (W x H x 12 floats: albedo a, coverage v,
+   normal, distance, position).  Per pixel E = the lookup at (position, normal), rounded to float32, then max(E, 0); in float32 without
+   contraction
+       out_c = a_c * (v * (E_c * (float)(1 / pi)) + (1 - v))
+   and out goes through resolve_pixel(out, 1, gamma) into linear_rgb / gamma_rgb / rgb8 (any may be NULL, not all three), exactly as
+   fw_denoise writes its outputs.  A pixel with v = 0 passes its albedo through: the environment's clamped colour.  Direct and indirect
+   diffuse light both come from the probes.  The record does not mark emitters, so an EmissiveMat surface shows its clamped emission
+   times E / pi; that and specular transport are out of scope.  Host arrays (staged as fw_probe_irradiance stages its own, the pixels
+   in slabs), or with p->on_device device arrays on p->device, launched on p->stream and complete on return.  Errors, in this order and
+   before HIP is called: FW_ERR_BAD_ARG for a NULL grid, sh, p or aov, all three outputs NULL, what fw_probe_irradiance rejects in the
+   grid, width or height 0, gamma not finite or <= 0, device < 0, with on_device an aov not 16-byte aligned or sh, linear_rgb or
+   gamma_rgb not 4-byte aligned; FW_ERR_UNSUPPORTED for nx ny nz >= 2^31 or W x H >= 2^32; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for
+   a device index past the last one.  Neither call takes or touches a scene: renders, the path arena and the cached frame graph are
+   left as they were. */
+typedef struct fw_probe_shade_params {
+    uint32_t width, height;
+    float gamma;            /* for gamma_rgb / rgb8, as fw_render_params.gamma */
+    int32_t device;
+    int32_t on_device;      /* every array is a device pointer on `device` */
+    void *stream;           /* hipStream_t, NULL = default */
+} fw_probe_shade_params;
+int fw_probe_shade(const fw_probe_grid *grid, const float *sh, const fw_probe_shade_params *p, const float *aov, float *linear_rgb,
+                   float *gamma_rgb, uint8_t *rgb8);
+
 /* ---- lightmaps baked on the device: irradiance over a mesh's UV texels (additive at ABI 8) ---------------------------
    A fw_lightmap is one mesh placement and a texture size.  It reads nothing from a scene: the scene is only what the rays are traced
    against.  All its pointers are host memory.
