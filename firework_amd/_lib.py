@@ -6,6 +6,7 @@ reachable from here.
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -143,6 +144,8 @@ def load(preload=False, device=None):
                                      C.c_void_p, C.c_void_p, C.POINTER(A.fw_stats)]
     lib.fw_denoise.restype = C.c_int
     lib.fw_denoise.argtypes = [C.POINTER(A.fw_denoise_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fw_debug_kernels.restype = C.c_int
+    lib.fw_debug_kernels.argtypes = [C.c_int, C.c_char_p, C.c_uint32]
     lib.fw_temporal.restype = C.c_int
     lib.fw_temporal.argtypes = [C.POINTER(A.fw_temporal_params)] + [C.c_void_p] * 10
     if lib.fw_abi_version() != A.FW_ABI_VERSION:
@@ -191,6 +194,21 @@ class options:
         for k in self.kw:
             set_option(k, None)
         return False
+
+
+def last_kernels(device=0):
+    """fw_debug_kernels: the names of the walk and shade kernels the last call on `device` launched, e.g. 'k_shade_pl<2,0>' or
+    'k_blas_wide<q8,no tris>@12' (@: waves per workgroup of an LDS-resident walk); device -1: every name this build can launch."""
+    lib = load()
+    n = lib.fw_debug_kernels(int(device), None, 0)
+    if n < 0:
+        _check(lib, n)
+    buf = C.create_string_buffer(n + 1)
+    n = lib.fw_debug_kernels(int(device), buf, n + 1)
+    if n < 0:
+        _check(lib, n)
+    text = buf.value.decode()
+    return frozenset(re.split(r",(?![^<]*>)", text)) if text else frozenset()      # (a comma inside <> belongs to a name)
 
 
 def has_ab():

@@ -282,6 +282,144 @@ constexpr uint32_t DELTA_MAX_LIGHTS = 65536;
 // queue carry object indices, which stay below it (fw_scene_set_lights refuses a scene whose indices could reach it).
 constexpr uint32_t SHADOW_NEAR = 0xfffffffeu;
 
+// ---- which kernels a call launched (fw_debug_kernels) ---------------------------------------------------------------------
+// One id per kernel instantiation that launch_extend, launch_extend_exact, launch_shade, launch_shade_nee and launch_shadow_resolve (and the
+// GgxMat launchers behind them) can pick: X(id, printable name, family).  family: -1, or the LDS-resident walk family whose launches also
+// record their waves per workgroup (0 k_blas_wide, 1 k_extend_tlas_wide, 2 the pair-node walks k_blas_lds / k_extend_tlas_lds, always
+// LDS_WAVES).  The first KID_N_WALK ids are the walks.  The A/B build's own kernels follow the product's.
+#define FW_KERNEL_IDS_PRODUCT(X) \
+    X(EXTEND_SCAN, "k_extend_scan<false>", -1) \
+    X(EXTEND_SCAN_PARK, "k_extend_scan<true>", -1) \
+    X(EXTEND_SCAN_PARK_NM, "k_extend_scan<true,true>", -1) \
+    X(EXTEND_SCAN_PARK_NM_S, "k_extend_scan<true,true,true>", -1) \
+    X(EXTEND_TLAS_PARK, "k_extend_tlas_park", -1) \
+    X(EXTEND_TLAS, "k_extend_tlas", -1) \
+    X(EXTEND_TLAS_LDS, "k_extend_tlas_lds", 2) \
+    X(EXTEND_TLAS_WIDE_FF, "k_extend_tlas_wide<false>", 1) \
+    X(EXTEND_TLAS_WIDE_FT, "k_extend_tlas_wide<false,true>", 1) \
+    X(EXTEND_TLAS_WIDE_TF, "k_extend_tlas_wide<true>", 1) \
+    X(EXTEND_TLAS_WIDE_TT, "k_extend_tlas_wide<true,true>", 1) \
+    X(BLAS_WIDE_F32_T, "k_blas_wide<f32,tris>", 0) \
+    X(BLAS_WIDE_F32_N, "k_blas_wide<f32,no tris>", 0) \
+    X(BLAS_WIDE_Q8_T, "k_blas_wide<q8,tris>", 0) \
+    X(BLAS_WIDE_Q8_N, "k_blas_wide<q8,no tris>", 0) \
+    X(BLAS_LDS_T, "k_blas_lds<true>", 2) \
+    X(BLAS_LDS_N, "k_blas_lds<false>", 2) \
+    X(BLAS, "k_blas", -1) \
+    X(EXTEND_LINEAR, "k_extend_linear", -1) \
+    X(EXTEND_LINEAR_NOMESH, "k_extend_linear_nomesh", -1) \
+    X(EXTEND_LINEAR_PLAIN, "k_extend_linear_plain", -1) \
+    X(EXTEND_LINEAR_SIMPLE_N, "k_extend_linear_simple<false>", -1) \
+    X(EXTEND_LINEAR_SIMPLE_M, "k_extend_linear_simple<true>", -1) \
+    X(EXTEND_LINEAR_DEFER_S, "k_extend_linear_defer<true>", -1) \
+    X(EXTEND_LINEAR_DEFER_N, "k_extend_linear_defer<false>", -1) \
+    X(EXTEND_EXACT, "k_extend_exact", -1) \
+    X(SHADE_001, "k_shade<0,0,chain>", -1) \
+    X(SHADE_000, "k_shade<0,0,no chain>", -1) \
+    X(SHADE_011, "k_shade<0,1,chain>", -1) \
+    X(SHADE_010, "k_shade<0,1,no chain>", -1) \
+    X(SHADE_101, "k_shade<1,0,chain>", -1) \
+    X(SHADE_100, "k_shade<1,0,no chain>", -1) \
+    X(SHADE_111, "k_shade<1,1,chain>", -1) \
+    X(SHADE_110, "k_shade<1,1,no chain>", -1) \
+    X(SHADE_201, "k_shade<2,0,chain>", -1) \
+    X(SHADE_200, "k_shade<2,0,no chain>", -1) \
+    X(SHADE_211, "k_shade<2,1,chain>", -1) \
+    X(SHADE_210, "k_shade<2,1,no chain>", -1) \
+    X(SHADE_LS_00, "k_shade_ls<0,0>", -1) \
+    X(SHADE_LS_01, "k_shade_ls<0,1>", -1) \
+    X(SHADE_LS_10, "k_shade_ls<1,0>", -1) \
+    X(SHADE_LS_11, "k_shade_ls<1,1>", -1) \
+    X(SHADE_LS_20, "k_shade_ls<2,0>", -1) \
+    X(SHADE_LS_21, "k_shade_ls<2,1>", -1) \
+    X(SHADE_PL_00, "k_shade_pl<0,0>", -1) \
+    X(SHADE_PL_01, "k_shade_pl<0,1>", -1) \
+    X(SHADE_PL_10, "k_shade_pl<1,0>", -1) \
+    X(SHADE_PL_11, "k_shade_pl<1,1>", -1) \
+    X(SHADE_PL_20, "k_shade_pl<2,0>", -1) \
+    X(SHADE_PL_21, "k_shade_pl<2,1>", -1) \
+    X(SHADE_DL_00, "k_shade_dl<0,0>", -1) \
+    X(SHADE_DL_01, "k_shade_dl<0,1>", -1) \
+    X(SHADE_DL_10, "k_shade_dl<1,0>", -1) \
+    X(SHADE_DL_11, "k_shade_dl<1,1>", -1) \
+    X(SHADE_DL_20, "k_shade_dl<2,0>", -1) \
+    X(SHADE_DL_21, "k_shade_dl<2,1>", -1) \
+    X(SHADE_ENV_0, "k_shade_env<0>", -1) \
+    X(SHADE_ENV_1, "k_shade_env<1>", -1) \
+    X(SHADE_ENV_2, "k_shade_env<2>", -1) \
+    X(SHADE_PL_ENV_0, "k_shade_pl_env<0>", -1) \
+    X(SHADE_PL_ENV_1, "k_shade_pl_env<1>", -1) \
+    X(SHADE_PL_ENV_2, "k_shade_pl_env<2>", -1) \
+    X(SHADE_GX_00, "k_shade_gx<0,0>", -1) \
+    X(SHADE_GX_01, "k_shade_gx<0,1>", -1) \
+    X(SHADE_GX_10, "k_shade_gx<1,0>", -1) \
+    X(SHADE_GX_11, "k_shade_gx<1,1>", -1) \
+    X(SHADE_GX_20, "k_shade_gx<2,0>", -1) \
+    X(SHADE_GX_21, "k_shade_gx<2,1>", -1) \
+    X(SHADE_GX_NEE_00_PL_ENV, "k_shade_gx_nee<0,0,pl_env>", -1) \
+    X(SHADE_GX_NEE_00_ENV, "k_shade_gx_nee<0,0,env>", -1) \
+    X(SHADE_GX_NEE_00_PL, "k_shade_gx_nee<0,0,pl>", -1) \
+    X(SHADE_GX_NEE_01_PL, "k_shade_gx_nee<0,1,pl>", -1) \
+    X(SHADE_GX_NEE_00_LS, "k_shade_gx_nee<0,0,ls>", -1) \
+    X(SHADE_GX_NEE_01_LS, "k_shade_gx_nee<0,1,ls>", -1) \
+    X(SHADE_GX_NEE_00_DL, "k_shade_gx_nee<0,0,dl>", -1) \
+    X(SHADE_GX_NEE_01_DL, "k_shade_gx_nee<0,1,dl>", -1) \
+    X(SHADE_GX_NEE_10_PL_ENV, "k_shade_gx_nee<1,0,pl_env>", -1) \
+    X(SHADE_GX_NEE_10_ENV, "k_shade_gx_nee<1,0,env>", -1) \
+    X(SHADE_GX_NEE_10_PL, "k_shade_gx_nee<1,0,pl>", -1) \
+    X(SHADE_GX_NEE_11_PL, "k_shade_gx_nee<1,1,pl>", -1) \
+    X(SHADE_GX_NEE_10_LS, "k_shade_gx_nee<1,0,ls>", -1) \
+    X(SHADE_GX_NEE_11_LS, "k_shade_gx_nee<1,1,ls>", -1) \
+    X(SHADE_GX_NEE_10_DL, "k_shade_gx_nee<1,0,dl>", -1) \
+    X(SHADE_GX_NEE_11_DL, "k_shade_gx_nee<1,1,dl>", -1) \
+    X(SHADE_GX_NEE_20_PL_ENV, "k_shade_gx_nee<2,0,pl_env>", -1) \
+    X(SHADE_GX_NEE_20_ENV, "k_shade_gx_nee<2,0,env>", -1) \
+    X(SHADE_GX_NEE_20_PL, "k_shade_gx_nee<2,0,pl>", -1) \
+    X(SHADE_GX_NEE_21_PL, "k_shade_gx_nee<2,1,pl>", -1) \
+    X(SHADE_GX_NEE_20_LS, "k_shade_gx_nee<2,0,ls>", -1) \
+    X(SHADE_GX_NEE_21_LS, "k_shade_gx_nee<2,1,ls>", -1) \
+    X(SHADE_GX_NEE_20_DL, "k_shade_gx_nee<2,0,dl>", -1) \
+    X(SHADE_GX_NEE_21_DL, "k_shade_gx_nee<2,1,dl>", -1) \
+    X(SHADOW_RESOLVE, "k_shadow_resolve", -1) \
+    X(SHADOW_RESOLVE_ENV, "k_shadow_resolve_env", -1) \
+    X(SHADOW_RESOLVE_PL, "k_shadow_resolve_pl", -1) \
+    X(SHADOW_RESOLVE_DL, "k_shadow_resolve_dl", -1) \
+    X(SHADOW_RESOLVE_GX, "k_shadow_resolve_gx", -1)
+#if FW_AB
+#define FW_KERNEL_IDS_AB(X) \
+    X(EXTEND_BVH, "k_extend_bvh", -1) \
+    X(SHADE_020, "k_shade<0,2,no chain>", -1) \
+    X(SHADE_120, "k_shade<1,2,no chain>", -1) \
+    X(SHADE_220, "k_shade<2,2,no chain>", -1) \
+    X(BOUNCE_00, "k_bounce<false,false>", -1) \
+    X(BOUNCE_01, "k_bounce<false,true>", -1) \
+    X(BOUNCE_10, "k_bounce<true,false>", -1) \
+    X(BOUNCE_11, "k_bounce<true,true>", -1)
+#else
+#define FW_KERNEL_IDS_AB(X)
+#endif
+#define FW_KERNEL_IDS(X) FW_KERNEL_IDS_PRODUCT(X) FW_KERNEL_IDS_AB(X)
+enum KernelId : uint32_t {
+#define FW_KID_ENUM(id, name, fam) KID_##id,
+    FW_KERNEL_IDS(FW_KID_ENUM)
+#undef FW_KID_ENUM
+    KID_COUNT
+};
+constexpr uint32_t KID_N_WALK = 26;
+extern const char *const KERNEL_NAMES[KID_COUNT];      // fw_kernels.hip
+extern const signed char KERNEL_FAMILY[KID_COUNT];
+// The set a call launched.  It lives in the per-device workspace (under its mutex); the launchers reach it through LaunchCfg.log and pay
+// one OR per launch.  waves[id]: bit 0 / 1 / 2 = a launch with 16 / 12 / 8 waves per workgroup (the ids of a family only).
+struct KernelLog {
+    uint64_t bits[(KID_COUNT + 63) / 64];
+    uint8_t waves[KID_COUNT];
+    void clear() { *this = KernelLog{}; }
+    void add(KernelId id) { bits[id >> 6] |= 1ull << (id & 63u); }
+    void add(KernelId id, uint32_t w) { add(id); waves[id] |= (uint8_t)(w == 16u ? 1u : w == 12u ? 2u : 4u); }
+    void merge(const KernelLog &o) { for (size_t i = 0; i < sizeof bits / sizeof bits[0]; i++) bits[i] |= o.bits[i]; for (uint32_t i = 0; i < KID_COUNT; i++) waves[i] |= o.waves[i]; }
+    bool has(uint32_t id) const { return ((bits[id >> 6] >> (id & 63u)) & 1u) != 0; }
+};
+
 // launch wrappers (fw_kernels.hip)
 struct LaunchCfg {
     hipStream_t stream;
@@ -305,6 +443,7 @@ struct LaunchCfg {
     uint32_t wblas_nodes, wtlas_nodes, wblas_depth, wtlas_depth;   // wide nodes; wide nodes on the longest root-to-leaf path
     uint32_t debug_wide_levels;   // A/B build, option DEBUG_WIDE_LEVELS: LDS stack levels of the wide walks instead of 3 * depth + 2 (the error word's test); 0: off
     bool gx;              // the scene holds a GgxMat: the k_shade_gx kernels and k_shadow_resolve_gx
+    KernelLog *log;       // where the launchers record the kernel they pick (the workspace's; set_walk_cfg's callers set it)
     bool tlas_refill;     // refilling walks: k_extend_tlas (no meshes) / k_extend_tlas_park + k_blas (meshes); FIREWORK_TLAS_REFILL=0: the chunked k_extend_bvh
 };
 constexpr size_t LDS_TREE_LIMIT = 160 * 1024;   // the whole LDS of a CU: one workgroup of the LDS-resident walks per CU

@@ -4775,6 +4775,19 @@ static bool lds_attr_needed(int which) {
 static size_t lds_walk_bytes(size_t tree_bytes, uint32_t waves, uint32_t levels, uint32_t n_queues, uint32_t grid) {
     return tree_bytes + (size_t)waves * levels * 64 * 2 + 16 + 4 * (size_t)((n_queues + grid - 1) / grid);
 }
+// Every launch of a walk or shade kernel records its id in the call's KernelLog (fw_device.h; fw_debug_kernels reads it): one OR
+#define FW_LAUNCH(ID, ...) do { if (c.log) c.log->add(KID_##ID); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+#define FW_LAUNCH_W(ID, W, ...) do { if (c.log) c.log->add(KID_##ID, (uint32_t)(W)); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+const char *const KERNEL_NAMES[KID_COUNT] = {
+#define FW_KID_NAME(id, name, fam) name,
+    FW_KERNEL_IDS(FW_KID_NAME)
+#undef FW_KID_NAME
+};
+const signed char KERNEL_FAMILY[KID_COUNT] = {
+#define FW_KID_FAM(id, name, fam) fam,
+    FW_KERNEL_IDS(FW_KID_FAM)
+#undef FW_KID_FAM
+};
 void launch_extend(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, float2 *hits, int segment, bool use_bvh, DPark park) {
     int tl = use_bvh ? c.tlas_depth + 1 : 0;
     int levels = tl + c.blas_depth + 1;
@@ -4784,10 +4797,10 @@ void launch_extend(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths
     auto walk_grid = [&](uint32_t waves) { return std::min<uint32_t>((uint32_t)c.n_cus, (c.q.n_waves + waves - 1) / waves); };
     if (use_bvh && c.tlas_refill && c.has_mesh) {
         // TLAS walk that parks mesh rays in HBM, then their BLAS walks; a medium around a mesh still walks it in place (blas levels)
-        if (sc.n_objects <= TLAS_SCAN_MAX && !sc.has_medium && c.simple_but_meshes) hipLaunchKernelGGL((k_extend_scan<true, true, true>), eg, dim3(WB), (size_t)levels * WB * sizeof(uint32_t), c.stream, sc, f, in, hits, c.q, segment, tl, park.ray_a, park.ray_b, park.meta, park.pcount, park.stride);
-        else if (sc.n_objects <= TLAS_SCAN_MAX && !sc.has_medium) hipLaunchKernelGGL((k_extend_scan<true, true>), eg, dim3(WB), (size_t)levels * WB * sizeof(uint32_t), c.stream, sc, f, in, hits, c.q, segment, tl, park.ray_a, park.ray_b, park.meta, park.pcount, park.stride);
-        else if (sc.n_objects <= TLAS_SCAN_MAX) hipLaunchKernelGGL(k_extend_scan<true>, eg, dim3(WB), (size_t)levels * WB * sizeof(uint32_t), c.stream, sc, f, in, hits, c.q, segment, tl, park.ray_a, park.ray_b, park.meta, park.pcount, park.stride);
-        else hipLaunchKernelGGL(k_extend_tlas_park, sg, dim3(WB), (size_t)levels * WB * sizeof(uint32_t), c.stream, sc, f, in, hits, c.q, segment, tl, levels, park);
+        if (sc.n_objects <= TLAS_SCAN_MAX && !sc.has_medium && c.simple_but_meshes) FW_LAUNCH(EXTEND_SCAN_PARK_NM_S, (k_extend_scan<true, true, true>), eg, dim3(WB), (size_t)levels * WB * sizeof(uint32_t), c.stream, sc, f, in, hits, c.q, segment, tl, park.ray_a, park.ray_b, park.meta, park.pcount, park.stride);
+        else if (sc.n_objects <= TLAS_SCAN_MAX && !sc.has_medium) FW_LAUNCH(EXTEND_SCAN_PARK_NM, (k_extend_scan<true, true>), eg, dim3(WB), (size_t)levels * WB * sizeof(uint32_t), c.stream, sc, f, in, hits, c.q, segment, tl, park.ray_a, park.ray_b, park.meta, park.pcount, park.stride);
+        else if (sc.n_objects <= TLAS_SCAN_MAX) FW_LAUNCH(EXTEND_SCAN_PARK, k_extend_scan<true>, eg, dim3(WB), (size_t)levels * WB * sizeof(uint32_t), c.stream, sc, f, in, hits, c.q, segment, tl, park.ray_a, park.ray_b, park.meta, park.pcount, park.stride);
+        else FW_LAUNCH(EXTEND_TLAS_PARK, k_extend_tlas_park, sg, dim3(WB), (size_t)levels * WB * sizeof(uint32_t), c.stream, sc, f, in, hits, c.q, segment, tl, levels, park);
         // The parked rays' BLAS walks.  WIDE nodes out of LDS where the scene has them (f32, or quantised for a BLAS too big for those):
         // as many waves per workgroup (16, 12, 8) as fit next to the tree, the triangles too when 16 waves still fit with them.
         if (c.lds_trees && c.wblas_fmt != WIDE_NONE && sc.wblas && c.max_tris < 0x7fffu) {
@@ -4805,9 +4818,9 @@ void launch_extend(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths
                 }
                 const dim3 lg(walk_grid(waves));
                 const size_t bytes = lds_walk_bytes(tree + (lds_tris ? tris : 0), waves, wl, c.q.n_waves, lg.x);
-#define FW_BLAS_WIDE(F, T) hipLaunchKernelGGL((k_blas_wide<F, T>), lg, dim3(waves * 64), bytes, c.stream, sc, park, hits, c.q, c.wblas_nodes, c.n_tris, wl)
-                if (c.wblas_fmt == WIDE_F32) { if (lds_tris) FW_BLAS_WIDE(WIDE_F32, true); else FW_BLAS_WIDE(WIDE_F32, false); }
-                else { if (lds_tris) FW_BLAS_WIDE(WIDE_Q8, true); else FW_BLAS_WIDE(WIDE_Q8, false); }
+#define FW_BLAS_WIDE(ID, F, T) FW_LAUNCH_W(ID, waves, (k_blas_wide<F, T>), lg, dim3(waves * 64), bytes, c.stream, sc, park, hits, c.q, c.wblas_nodes, c.n_tris, wl)
+                if (c.wblas_fmt == WIDE_F32) { if (lds_tris) FW_BLAS_WIDE(BLAS_WIDE_F32_T, WIDE_F32, true); else FW_BLAS_WIDE(BLAS_WIDE_F32_N, WIDE_F32, false); }
+                else { if (lds_tris) FW_BLAS_WIDE(BLAS_WIDE_Q8_T, WIDE_Q8, true); else FW_BLAS_WIDE(BLAS_WIDE_Q8_N, WIDE_Q8, false); }
 #undef FW_BLAS_WIDE
                 return;
             }
@@ -4822,11 +4835,11 @@ void launch_extend(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths
             }
             const dim3 lg(walk_grid(LDS_WAVES));
             if (lds_blas + lds_tris <= LDS_TREE_LIMIT && !c.no_lds_tris)      // the triangles too, when they fit as well
-                hipLaunchKernelGGL(k_blas_lds<true>, lg, dim3(LDS_WAVES * 64), lds_blas + lds_tris, c.stream, sc, park, hits, c.q, c.blas_pair_nodes, c.n_tris, bl);
+                FW_LAUNCH_W(BLAS_LDS_T, LDS_WAVES, k_blas_lds<true>, lg, dim3(LDS_WAVES * 64), lds_blas + lds_tris, c.stream, sc, park, hits, c.q, c.blas_pair_nodes, c.n_tris, bl);
             else
-                hipLaunchKernelGGL(k_blas_lds<false>, lg, dim3(LDS_WAVES * 64), lds_blas, c.stream, sc, park, hits, c.q, c.blas_pair_nodes, c.n_tris, bl);
+                FW_LAUNCH_W(BLAS_LDS_N, LDS_WAVES, k_blas_lds<false>, lg, dim3(LDS_WAVES * 64), lds_blas, c.stream, sc, park, hits, c.q, c.blas_pair_nodes, c.n_tris, bl);
         }
-        else hipLaunchKernelGGL(k_blas, sg, dim3(WB), (size_t)(c.blas_depth + 1) * WB * sizeof(uint32_t), c.stream, sc, park, hits, c.q);
+        else FW_LAUNCH(BLAS, k_blas, sg, dim3(WB), (size_t)(c.blas_depth + 1) * WB * sizeof(uint32_t), c.stream, sc, park, hits, c.q);
     }
     else if (use_bvh && c.tlas_refill) {
         // scenes without meshes: the whole TLAS in LDS when it fits next to the walks' stacks — WIDE nodes where the scene has them
@@ -4843,32 +4856,32 @@ void launch_extend(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths
                     (void)hipFuncSetAttribute(reinterpret_cast<const void *>((k_extend_tlas_wide<false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_TREE_LIMIT);
                 }
                 const dim3 lg(walk_grid(waves));
-                if (!sc.has_medium && c.simple_set) hipLaunchKernelGGL((k_extend_tlas_wide<false, true>), lg, dim3(waves * 64), lds_walk_bytes(tree, waves, wl, c.q.n_waves, lg.x), c.stream, sc, f, in, hits, c.q, segment, c.wtlas_nodes, wl);
-                else if (sc.has_medium && c.simple_set) hipLaunchKernelGGL((k_extend_tlas_wide<true, true>), lg, dim3(waves * 64), lds_walk_bytes(tree, waves, wl, c.q.n_waves, lg.x), c.stream, sc, f, in, hits, c.q, segment, c.wtlas_nodes, wl);
-                else if (sc.has_medium) hipLaunchKernelGGL(k_extend_tlas_wide<true>, lg, dim3(waves * 64), lds_walk_bytes(tree, waves, wl, c.q.n_waves, lg.x), c.stream, sc, f, in, hits, c.q, segment, c.wtlas_nodes, wl);
-                else hipLaunchKernelGGL(k_extend_tlas_wide<false>, lg, dim3(waves * 64), lds_walk_bytes(tree, waves, wl, c.q.n_waves, lg.x), c.stream, sc, f, in, hits, c.q, segment, c.wtlas_nodes, wl);
+                if (!sc.has_medium && c.simple_set) FW_LAUNCH_W(EXTEND_TLAS_WIDE_FT, waves, (k_extend_tlas_wide<false, true>), lg, dim3(waves * 64), lds_walk_bytes(tree, waves, wl, c.q.n_waves, lg.x), c.stream, sc, f, in, hits, c.q, segment, c.wtlas_nodes, wl);
+                else if (sc.has_medium && c.simple_set) FW_LAUNCH_W(EXTEND_TLAS_WIDE_TT, waves, (k_extend_tlas_wide<true, true>), lg, dim3(waves * 64), lds_walk_bytes(tree, waves, wl, c.q.n_waves, lg.x), c.stream, sc, f, in, hits, c.q, segment, c.wtlas_nodes, wl);
+                else if (sc.has_medium) FW_LAUNCH_W(EXTEND_TLAS_WIDE_TF, waves, k_extend_tlas_wide<true>, lg, dim3(waves * 64), lds_walk_bytes(tree, waves, wl, c.q.n_waves, lg.x), c.stream, sc, f, in, hits, c.q, segment, c.wtlas_nodes, wl);
+                else FW_LAUNCH_W(EXTEND_TLAS_WIDE_FF, waves, k_extend_tlas_wide<false>, lg, dim3(waves * 64), lds_walk_bytes(tree, waves, wl, c.q.n_waves, lg.x), c.stream, sc, f, in, hits, c.q, segment, c.wtlas_nodes, wl);
                 return;
             }
         }
         const size_t lds_tlas = lds_walk_bytes((size_t)c.tlas_pair_nodes * 64, LDS_WAVES, (uint32_t)tl, c.q.n_waves, walk_grid(LDS_WAVES));
         if (c.lds_trees && !c.has_mesh && sc.n_objects > TLAS_SCAN_MAX && c.tlas_pair_nodes < 32768u && sc.n_objects < 32768u && lds_tlas <= LDS_TREE_LIMIT) {
             if (lds_attr_needed(1)) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_extend_tlas_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_TREE_LIMIT);
-            hipLaunchKernelGGL(k_extend_tlas_lds, dim3(walk_grid(LDS_WAVES)), dim3(LDS_WAVES * 64), lds_tlas, c.stream,
+            FW_LAUNCH_W(EXTEND_TLAS_LDS, LDS_WAVES, k_extend_tlas_lds, dim3(walk_grid(LDS_WAVES)), dim3(LDS_WAVES * 64), lds_tlas, c.stream,
                                sc, f, in, hits, c.q, segment, c.tlas_pair_nodes, (uint32_t)tl);
         }
-        else if (sc.n_objects <= TLAS_SCAN_MAX) hipLaunchKernelGGL(k_extend_scan<false>, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, (float4 *)nullptr, (float2 *)nullptr, (float4 *)nullptr, (uint32_t *)nullptr, 0u);
-        else hipLaunchKernelGGL(k_extend_tlas, sg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
+        else if (sc.n_objects <= TLAS_SCAN_MAX) FW_LAUNCH(EXTEND_SCAN, k_extend_scan<false>, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, (float4 *)nullptr, (float2 *)nullptr, (float4 *)nullptr, (uint32_t *)nullptr, 0u);
+        else FW_LAUNCH(EXTEND_TLAS, k_extend_tlas, sg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
     }
 #if FW_AB
-    else if (use_bvh) hipLaunchKernelGGL(k_extend_bvh, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
+    else if (use_bvh) FW_LAUNCH(EXTEND_BVH, k_extend_bvh, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
 #endif
-    else if (c.n_defer && c.simple_set) hipLaunchKernelGGL(k_extend_linear_defer<true>, eg, dim3(WB), (size_t)2 * 64 * DEFER_FIELDS * 4 + FW_DEFER_LDS_PAD, c.stream, sc, f, in, hits, c.q, segment, c.n_defer);
-    else if (c.n_defer) hipLaunchKernelGGL(k_extend_linear_defer<false>, eg, dim3(WB), (size_t)2 * 64 * DEFER_FIELDS * 4 + FW_DEFER_LDS_PAD, c.stream, sc, f, in, hits, c.q, segment, c.n_defer);
-    else if (c.simple_set && !sc.has_medium) hipLaunchKernelGGL(k_extend_linear_simple<false>, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
-    else if (c.simple_set) hipLaunchKernelGGL(k_extend_linear_simple<true>, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
-    else if (!c.has_mesh && !sc.has_medium) hipLaunchKernelGGL(k_extend_linear_plain, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
-    else if (!c.has_mesh) hipLaunchKernelGGL(k_extend_linear_nomesh, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
-    else hipLaunchKernelGGL(k_extend_linear, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
+    else if (c.n_defer && c.simple_set) FW_LAUNCH(EXTEND_LINEAR_DEFER_S, k_extend_linear_defer<true>, eg, dim3(WB), (size_t)2 * 64 * DEFER_FIELDS * 4 + FW_DEFER_LDS_PAD, c.stream, sc, f, in, hits, c.q, segment, c.n_defer);
+    else if (c.n_defer) FW_LAUNCH(EXTEND_LINEAR_DEFER_N, k_extend_linear_defer<false>, eg, dim3(WB), (size_t)2 * 64 * DEFER_FIELDS * 4 + FW_DEFER_LDS_PAD, c.stream, sc, f, in, hits, c.q, segment, c.n_defer);
+    else if (c.simple_set && !sc.has_medium) FW_LAUNCH(EXTEND_LINEAR_SIMPLE_N, k_extend_linear_simple<false>, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
+    else if (c.simple_set) FW_LAUNCH(EXTEND_LINEAR_SIMPLE_M, k_extend_linear_simple<true>, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
+    else if (!c.has_mesh && !sc.has_medium) FW_LAUNCH(EXTEND_LINEAR_PLAIN, k_extend_linear_plain, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
+    else if (!c.has_mesh) FW_LAUNCH(EXTEND_LINEAR_NOMESH, k_extend_linear_nomesh, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
+    else FW_LAUNCH(EXTEND_LINEAR, k_extend_linear, eg, dim3(WB), lds, c.stream, sc, f, in, hits, c.q, segment, tl, levels);
 }
 void launch_extend_exact(const LaunchCfg &c, const DScene &sc, const DFrame &f, const DPaths &in, float2 *hits, int segment, bool use_bvh) {
     // stacks sized by the reference trees' depths; the wave-shared mesh stack needs EXACT_STACK entries whatever the depth
@@ -4877,7 +4890,7 @@ void launch_extend_exact(const LaunchCfg &c, const DScene &sc, const DFrame &f, 
     const uint32_t bl = std::max<uint32_t>(std::min<uint32_t>(c.ref_blas_depth + 2u, EXACT_LEVELS), EXACT_STACK / EXACT_WB);
     const size_t lds = (size_t)(tl + bl) * EXACT_WB * 4;
     // 8 single-wave workgroups per CU: most launches find an empty list, and dispatching 4 096 workgroups that only read a counter took 12 us
-    hipLaunchKernelGGL(k_extend_exact, dim3((uint32_t)c.n_cus * 8u), dim3(EXACT_WB), lds, c.stream, sc, f, in, hits, segment, use_bvh ? 1 : 0, tl, c.exact_form);
+    FW_LAUNCH(EXTEND_EXACT, k_extend_exact, dim3((uint32_t)c.n_cus * 8u), dim3(EXACT_WB), lds, c.stream, sc, f, in, hits, segment, use_bvh ? 1 : 0, tl, c.exact_form);
 }
 // The shade kernels' table mode (fw_shade_tables.inc's LDS_TAB) and the dynamic LDS it takes: 1 everything in LDS | 2 materials + textures
 // only (the two dependent fetches behind the object record: part2 k_shade 6.7 -> 6.55 ms; a leaner per-kind object fetch on top — 3 loads
@@ -4900,10 +4913,10 @@ void launch_shade(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths 
     if (c.gx) { launch_shade_gx(c, sc, f, in, out, hits, sample_rad, segment, t); return; }      // a scene with a GgxMat
     // shading mode (k_shade): 0 everything in line | 1 the scene has nothing expensive | 2 expensive paths through the list
     const int mode = c.shade_mode;
-#define FW_SHADE(L, M, C) hipLaunchKernelGGL((k_shade<L, M, C>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex)
-#define FW_SHADE_C(L, M) do { if (f.chain_bits) FW_SHADE(L, M, true); else FW_SHADE(L, M, false); } while (0)
+#define FW_SHADE(L, M, C, CI) FW_LAUNCH(SHADE_##L##M##CI, (k_shade<L, M, C>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex)
+#define FW_SHADE_C(L, M) do { if (f.chain_bits) FW_SHADE(L, M, true, 1); else FW_SHADE(L, M, false, 0); } while (0)
 #if FW_AB
-#define FW_SHADE_L(L) do { if (mode == 2) FW_SHADE(L, 2, false); else if (mode == 1) FW_SHADE_C(L, 1); else FW_SHADE_C(L, 0); } while (0)
+#define FW_SHADE_L(L) do { if (mode == 2) FW_SHADE(L, 2, false, 0); else if (mode == 1) FW_SHADE_C(L, 1); else FW_SHADE_C(L, 0); } while (0)
 #else
 #define FW_SHADE_L(L) do { if (mode == 1) FW_SHADE_C(L, 1); else FW_SHADE_C(L, 0); } while (0)
 #endif
@@ -4920,13 +4933,13 @@ void launch_shade_nee(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPa
     const ShadeTables t = shade_tables(c, sc);
     const bool m1 = c.shade_mode == 1;
     if (c.gx) { launch_shade_gx_nee(c, sc, f, in, out, hits, sample_rad, segment, sh, ed, em, dl, t); return; }      // a scene with a GgxMat
-#define FW_NEE(K, ...) hipLaunchKernelGGL(K, wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, __VA_ARGS__)
+#define FW_NEE(ID, K, ...) FW_LAUNCH(ID, K, wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex, __VA_ARGS__)
 #define FW_NEE_L(L) do { \
-        if (ed && em) FW_NEE(k_shade_pl_env<L>, sh, *ed, *em); \
-        else if (ed) FW_NEE(k_shade_env<L>, sh, *ed); \
-        else if (em) { if (m1) FW_NEE((k_shade_pl<L, 1>), sh, *em); else FW_NEE((k_shade_pl<L, 0>), sh, *em); } \
-        else if (!dl) { if (m1) FW_NEE((k_shade_ls<L, 1>), sh); else FW_NEE((k_shade_ls<L, 0>), sh); } \
-        else { if (m1) FW_NEE((k_shade_dl<L, 1>), sh, *dl); else FW_NEE((k_shade_dl<L, 0>), sh, *dl); } \
+        if (ed && em) FW_NEE(SHADE_PL_ENV_##L, k_shade_pl_env<L>, sh, *ed, *em); \
+        else if (ed) FW_NEE(SHADE_ENV_##L, k_shade_env<L>, sh, *ed); \
+        else if (em) { if (m1) FW_NEE(SHADE_PL_##L##1, (k_shade_pl<L, 1>), sh, *em); else FW_NEE(SHADE_PL_##L##0, (k_shade_pl<L, 0>), sh, *em); } \
+        else if (!dl) { if (m1) FW_NEE(SHADE_LS_##L##1, (k_shade_ls<L, 1>), sh); else FW_NEE(SHADE_LS_##L##0, (k_shade_ls<L, 0>), sh); } \
+        else { if (m1) FW_NEE(SHADE_DL_##L##1, (k_shade_dl<L, 1>), sh, *dl); else FW_NEE(SHADE_DL_##L##0, (k_shade_dl<L, 0>), sh, *dl); } \
     } while (0)
     if (t.lt == 1) FW_NEE_L(1); else if (t.lt == 2) FW_NEE_L(2); else FW_NEE_L(0);
 #undef FW_NEE_L
@@ -4936,10 +4949,10 @@ void launch_shade_nee(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPa
 void launch_shadow_resolve(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment, bool env, bool pl, bool dl, float4 *sample_rad) {
     // (a scene with a GgxMat, §9m: only without env and pl do its vertices queue shadow rays, and those may belong to paths that have ended)
     if (c.gx && !env && !pl) { launch_shadow_resolve_gx(c, sc, sh, hits, segment, sample_rad); return; }
-    if (dl) hipLaunchKernelGGL(k_shadow_resolve_dl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
-    else if (pl) hipLaunchKernelGGL(k_shadow_resolve_pl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment);
-    else if (env) hipLaunchKernelGGL(k_shadow_resolve_env, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
-    else hipLaunchKernelGGL(k_shadow_resolve, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
+    if (dl) FW_LAUNCH(SHADOW_RESOLVE_DL, k_shadow_resolve_dl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
+    else if (pl) FW_LAUNCH(SHADOW_RESOLVE_PL, k_shadow_resolve_pl, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment);
+    else if (env) FW_LAUNCH(SHADOW_RESOLVE_ENV, k_shadow_resolve_env, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
+    else FW_LAUNCH(SHADOW_RESOLVE, k_shadow_resolve, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits);
 }
 void launch_emitter_weights(hipStream_t stream, const DScene &sc, const uint4 *ent, uint32_t n, float *w) {
     hipLaunchKernelGGL(k_emitter_weights, dim3((n + WB - 1) / WB), dim3(WB), 0, stream, sc, ent, n, w);
@@ -4972,9 +4985,9 @@ void launch_bounce(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths
     size_t lds = tab + (size_t)levels * WB * sizeof(uint32_t);
     uint32_t tq = (uint32_t)(tab / sizeof(float4));
     dim3 g = wave_grid(c);
-#define FW_BOUNCE(B, T) hipLaunchKernelGGL((k_bounce<B, T>), g, dim3(WB), lds, c.stream, sc, f, in, out, sample_rad, c.q, segment, tl, c.n_mat, c.n_tex, tq)
-    if (use_bvh) { if (lds_tab) FW_BOUNCE(true, true); else FW_BOUNCE(true, false); }
-    else { if (lds_tab) FW_BOUNCE(false, true); else FW_BOUNCE(false, false); }
+#define FW_BOUNCE(ID, B, T) FW_LAUNCH(ID, (k_bounce<B, T>), g, dim3(WB), lds, c.stream, sc, f, in, out, sample_rad, c.q, segment, tl, c.n_mat, c.n_tex, tq)
+    if (use_bvh) { if (lds_tab) FW_BOUNCE(BOUNCE_11, true, true); else FW_BOUNCE(BOUNCE_10, true, false); }
+    else { if (lds_tab) FW_BOUNCE(BOUNCE_01, false, true); else FW_BOUNCE(BOUNCE_00, false, false); }
 #undef FW_BOUNCE
 }
 #endif   // FW_AB
@@ -5282,8 +5295,8 @@ void launch_denoise(hipStream_t stream, int n_cus, uint32_t W, uint32_t H, uint3
 // ---- GgxMat: the launches of its kernels, last in the file (see k_shadow_resolve_gx) ----------------------------------------
 // k_shade_gx, modes 0 and 1 (the host gives such a frame no chain state and no list)
 static void launch_shade_gx(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, const float2 *hits, float4 *sample_rad, int segment, const ShadeTables &t) {
-#define FW_SHADE_GX(L) do { if (c.shade_mode == 1) hipLaunchKernelGGL((k_shade_gx<L, 1>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex); \
-    else hipLaunchKernelGGL((k_shade_gx<L, 0>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex); } while (0)
+#define FW_SHADE_GX(L) do { if (c.shade_mode == 1) FW_LAUNCH(SHADE_GX_##L##1, (k_shade_gx<L, 1>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex); \
+    else FW_LAUNCH(SHADE_GX_##L##0, (k_shade_gx<L, 0>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, c.n_mat, c.n_tex); } while (0)
     if (t.lt == 1) FW_SHADE_GX(1); else if (t.lt == 2) FW_SHADE_GX(2); else FW_SHADE_GX(0);
 #undef FW_SHADE_GX
 }
@@ -5292,15 +5305,15 @@ static void launch_shade_gx_nee(const LaunchCfg &c, const DScene &sc, const DFra
                                 const DShadow &sh, const DEnvDist *ed, const DEmitters *em, const DDeltaLights *dl, const ShadeTables &t) {
     const bool m1 = c.shade_mode == 1;
     const DEnvDist e0{}; const DEmitters p0{}; const DDeltaLights d0{};
-#define FW_GX(L, M, E, P, D) hipLaunchKernelGGL((k_shade_gx_nee<L, M, E, P, D>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, \
+#define FW_GX(TAG, L, M, E, P, D) FW_LAUNCH(SHADE_GX_NEE_##L##M##_##TAG, (k_shade_gx_nee<L, M, E, P, D>), wave_grid(c), dim3(WB), t.lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, segment, \
                                             c.n_mat, c.n_tex, sh, ed ? *ed : e0, em ? *em : p0, dl ? *dl : d0)
-#define FW_GX_M(L, P, D) do { if (m1) FW_GX(L, 1, false, P, D); else FW_GX(L, 0, false, P, D); } while (0)
+#define FW_GX_M(TAG, L, P, D) do { if (m1) FW_GX(TAG, L, 1, false, P, D); else FW_GX(TAG, L, 0, false, P, D); } while (0)
 #define FW_GX_L(L) do { \
-    if (ed && em) FW_GX(L, 0, true, true, false); \
-    else if (ed) FW_GX(L, 0, true, false, false); \
-    else if (em) FW_GX_M(L, true, false); \
-    else if (!dl) FW_GX_M(L, false, false); \
-    else FW_GX_M(L, false, true); \
+    if (ed && em) FW_GX(PL_ENV, L, 0, true, true, false); \
+    else if (ed) FW_GX(ENV, L, 0, true, false, false); \
+    else if (em) FW_GX_M(PL, L, true, false); \
+    else if (!dl) FW_GX_M(LS, L, false, false); \
+    else FW_GX_M(DL, L, false, true); \
     } while (0)
     if (t.lt == 1) FW_GX_L(1); else if (t.lt == 2) FW_GX_L(2); else FW_GX_L(0);
 #undef FW_GX_L
@@ -5308,7 +5321,7 @@ static void launch_shade_gx_nee(const LaunchCfg &c, const DScene &sc, const DFra
 #undef FW_GX
 }
 static void launch_shadow_resolve_gx(const LaunchCfg &c, const DScene &sc, const DShadow &sh, const float2 *hits, int segment, float4 *sample_rad) {
-    hipLaunchKernelGGL(k_shadow_resolve_gx<0>, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits, sample_rad);
+    FW_LAUNCH(SHADOW_RESOLVE_GX, k_shadow_resolve_gx<0>, wave_grid(c), dim3(WB), 0, c.stream, sh, hits, c.q, segment, sc.prim_bits, sample_rad);
 }
 void launch_ggx_test(hipStream_t stream, uint32_t n, const float *in, float *out) {
     hipLaunchKernelGGL(k_ggx_test<0>, dim3((n + WB - 1) / WB), dim3(WB), 0, stream, n, in, out);

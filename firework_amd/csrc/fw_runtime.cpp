@@ -828,7 +828,9 @@ struct Workspace {
     // GRAPH: the launches of one frame between fork and join, captured the second time the same frame is asked for and replayed from then on.
     // `key` is a hash of every by-value kernel argument struct of the frame (camera, frame, queue, launch configuration, scene) and of
     // the buffers they do not name: anything that changes what a launch would be changes it, and a changed key is only ever a miss.
-    struct FrameGraph { uint64_t key = 0, seen = 0; hipGraphExec_t exec = nullptr; hipStream_t origin = nullptr; bool broken = false; fw::DFrame fr_after{}; } fg;
+    struct FrameGraph { uint64_t key = 0, seen = 0; hipGraphExec_t exec = nullptr; hipStream_t origin = nullptr; bool broken = false; fw::DFrame fr_after{};
+                        fw::KernelLog kernels{}; } fg;      // kernels: what the launchers recorded while `exec` was captured (a replay runs no launcher)
+    fw::KernelLog kernels{};              // the walk and shade kernels the last call on this device launched (fw_debug_kernels); under mu
     std::vector<hipEvent_t> phase_events; // PHASE_LOCK: [lane-in-group][segment] "this batch's extend of the segment has finished"
     DevBuf tile_ids; uint32_t tile_w = 0, tile_h = 0;   // the library's own 16x16-tile pixel order of a (tile_w x tile_h) frame
     // fw_render_adaptive: whole-frame sums and squares, the two id lists the rounds alternate between, the survivor mask, per-block
@@ -2373,6 +2375,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     std::unique_lock<std::mutex> ws_guard(ws->mu, std::defer_lock);
     if (!rd) ws_guard.lock();                                                        // (an adaptive round's caller holds it)
     { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }     // after fw_release_workspace, or a scene made before it
+    if (!rd) ws->kernels.clear();                                                    // (an adaptive call's rounds add up: adaptive_impl clears)
     const bool dl = delta_lights(sc);
     if (dl && (p->flags & (FW_FLAG_ENV_SAMPLING | FW_FLAG_ALL_EMITTERS)))
         return fail(FW_ERR_UNSUPPORTED, "point, spot and directional lights do not combine with FW_FLAG_ENV_SAMPLING or FW_FLAG_ALL_EMITTERS");
@@ -2568,6 +2571,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
 
     fw::LaunchCfg cfg{};
     set_walk_cfg(cfg, sc, O, q, p->use_bvh != 0, tlas_refill);
+    cfg.log = &ws->kernels;
     int max_blocks = sc->n_cus * 8;
     cfg.blocks_other = (int)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n_pix + fw::BLOCK - 1) / fw::BLOCK, (uint64_t)max_blocks));
     // k_shade's list entries are 16-bit queue positions: longer queues (cap > 65536: never with the default geometry) shade in line
@@ -2833,12 +2837,17 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
         if (graph_ok && fg.exec && fg.key == key) {
             HIPCHK(hipGraphLaunch(fg.exec, stream));
             fr = fg.fr_after; done = true; graph_replayed = true;
+            ws->kernels.merge(fg.kernels);
         } else if (graph_ok && fg.seen == key) {
             if (!fg.origin && hipStreamCreateWithFlags(&fg.origin, hipStreamNonBlocking) != hipSuccess) { fg.origin = nullptr; fg.broken = true; }
             if (!fg.broken && hipStreamBeginCapture(fg.origin, hipStreamCaptureModeRelaxed) == hipSuccess) {
                 origin = fg.origin;
                 if (O.trace) fprintf(stderr, "[firework] GRAPH: capturing (%u batches, %d lanes, phase lock %d)\n", n_batches, n_lanes, (int)phase_lock);
+                const fw::KernelLog before = ws->kernels;      // the capture alone: what the replays will report
+                ws->kernels.clear();
                 const int crc = enqueue_frame();
+                fg.kernels = ws->kernels;
+                ws->kernels.merge(before);
                 origin = stream;
                 hipGraph_t g = nullptr;
                 const hipError_t ee = hipStreamEndCapture(fg.origin, &g);
@@ -3003,6 +3012,7 @@ int adaptive_impl(fw_scene *sc, const fw_render_params *p, float tol, uint32_t m
     if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
     std::lock_guard<std::mutex> ws_guard(ws->mu);
     { const int irc = init_device_locked(ws, sc->device); if (irc) return irc; }
+    ws->kernels.clear();
     const Options O = options();
     int rc = FW_OK;
     auto need = [&](DevBuf &b, size_t bytes) { if (!rc) rc = b.alloc(bytes); };
@@ -3260,6 +3270,7 @@ int trace_impl(fw_scene *sc, const fw_trace_params *p, const float *rays, uint32
 
     fw::LaunchCfg cfg{};
     set_walk_cfg(cfg, sc, O, q, use_bvh, tlas_refill);
+    cfg.log = &ws->kernels; ws->kernels.clear();
     cfg.stream = stream;
     cfg.q.wcount = (uint32_t *)(base + o_wc);
     fw::DPaths paths{(float4 *)(base + o_ra), (float2 *)(base + o_rb), nullptr};     // segment 0 reads no path state
@@ -3447,6 +3458,7 @@ int aovs_impl(fw_scene *sc, const fw_render_params *p, float *aov, fw_stats *sta
 
     fw::LaunchCfg cfg{};
     set_walk_cfg(cfg, sc, O, q, use_bvh, tlas_refill);
+    cfg.log = &ws->kernels; ws->kernels.clear();
     cfg.stream = stream;
     cfg.q.wcount = (uint32_t *)(base + o_wc);
     fw::DPaths paths{(float4 *)(base + o_ra), (float2 *)(base + o_rb), nullptr};
@@ -4718,6 +4730,34 @@ int fw_selftest_bvh_trees(int device, const float *boxes, uint32_t n, float *ref
 #if FW_AB
 int fw_debug_ab(void) { return 1; }      // present only in the A/B build: tests of the alternative kernels look for it
 #endif
+
+int fw_debug_kernels(int device, char *buf, uint32_t cap) {
+    try {
+        if (device < -1 || device >= MAX_DEVICES) return fail(FW_ERR_BAD_ARG, "fw_debug_kernels: device out of range");
+        if (!buf && cap > 0) return fail(FW_ERR_BAD_ARG, "fw_debug_kernels: null buffer with cap > 0");
+        std::vector<std::string> names;
+        if (device < 0) for (uint32_t i = 0; i < fw::KID_COUNT; i++) names.push_back(fw::KERNEL_NAMES[i]);
+        else {
+            Workspace *ws = workspace_for(device);
+            if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
+            fw::KernelLog log;
+            { std::lock_guard<std::mutex> g(ws->mu); log = ws->kernels; }
+            for (uint32_t i = 0; i < fw::KID_COUNT; i++) {
+                if (!log.has(i)) continue;
+                if (fw::KERNEL_FAMILY[i] < 0) { names.push_back(fw::KERNEL_NAMES[i]); continue; }
+                const uint32_t waves[3] = {16u, 12u, 8u};
+                for (int b = 0; b < 3; b++) if (log.waves[i] & (1u << b)) names.push_back(std::string(fw::KERNEL_NAMES[i]) + "@" + std::to_string(waves[b]));
+            }
+        }
+        std::sort(names.begin(), names.end());
+        std::string all;
+        for (const std::string &n : names) { if (!all.empty()) all += ','; all += n; }
+        if (cap > 0) { const size_t k = std::min<size_t>(all.size(), (size_t)cap - 1); std::memcpy(buf, all.data(), k); buf[k] = 0; }
+        return (int)all.size();
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_debug_kernels"); }
+}
 
 int fw_init(int device, uint64_t arena_bytes) {
     try {

@@ -1001,6 +1001,19 @@ int fw_selftest_libm(int device, int fn, uint32_t n, const float *x, const float
    Returns FW_ERR_BAD_ARG for a name this build does not know. */
 int fw_set_option(const char *name, const char *value);
 
+/* Diagnostic (additive at ABI 8): which walk and shade kernels the last call on `device` launched.  The library picks one
+   of about a hundred kernel instantiations from the scene's sizes and the options above; every launch of one records its id, and this
+   call writes the recorded names to buf, sorted and separated by commas — names such as k_shade_pl<2,0>, k_extend_linear_defer<true>,
+   k_shadow_resolve_env; the walks that keep their tree in LDS carry their waves per workgroup: k_blas_wide<q8,no tris>@12,
+   k_extend_tlas_wide<true,true>@16, k_blas_lds<true>@16 (a comma inside <> belongs to a name).  The set is cleared when fw_render,
+   fw_render_progressive, fw_render_adaptive, fw_render_aovs, fw_trace_rays or a pass of fw_render_views, fw_render_rays, fw_render_model or
+   a bake starts its work on the device, so after a call of several passes it is the last pass's (an adaptive call: all its rounds').  A
+   frame replayed as a hipGraph (option GRAPH) runs no launcher: it reports the set recorded while the graph was captured.  device = -1:
+   every name this build can launch, without the wave counts (no device is needed).  At most cap - 1 characters and a terminator are
+   written (nothing for cap = 0, where buf may be NULL); returns the length of the whole list, as snprintf does, or FW_ERR_BAD_ARG
+   (device < -1 or out of range, buf = NULL with cap > 0).  No HIP call is made. */
+int fw_debug_kernels(int device, char *buf, uint32_t cap);
+
 /* Diagnostic, CPU only: builds the WIDE nodes the LDS-resident walks step through (four children per node; format 1 = f32 planes,
    2 = planes quantised to 8 bits and rounded outward) over n item boxes (n x 6 floats: min.xyz max.xyz) and checks the finished
    tree: every item the leaf of exactly one slot, every child box as the device decodes it a superset of the exact one (f32: the

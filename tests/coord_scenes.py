@@ -35,10 +35,9 @@ def mesh_ratio(offset, h):
     return max(abs(float(F32(c))) for c in offset) / h
 
 
-def _patch(h, seed):
-    """A bumpy GRID x GRID patch in the xy plane (facing -z) centred at 0, triangle legs h: local coordinates, float64."""
+def _patch(h, seed, n=GRID):
+    """A bumpy n x n patch in the xy plane (facing -z) centred at 0, triangle legs h: local coordinates, float64."""
     rng = np.random.default_rng(seed)
-    n = GRID
     i, j = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
     x = (i - (n - 1) / 2) * h + rng.uniform(-0.15, 0.15, i.shape) * h
     y = (j - (n - 1) / 2) * h + rng.uniform(-0.15, 0.15, i.shape) * h

@@ -23,7 +23,7 @@ def test_header_symbols_are_exported():
     lib = _lib.load()
     names = _declared_symbols()
     assert {"fw_render", "fw_render_scene", "fw_scene_create", "fw_scene_destroy", "fw_device_count", "fw_strerror",
-            "fw_last_error", "fw_abi_version"} <= set(names)
+            "fw_last_error", "fw_abi_version", "fw_debug_kernels"} <= set(names)
     for n in names:
         assert hasattr(lib, n), n
     assert lib.fw_abi_version() == A.FW_ABI_VERSION
@@ -122,3 +122,50 @@ def test_every_option_the_header_names_is_known_to_the_library_and_nothing_else(
     assert lib.fw_set_option(b"NO_SUCH_SWITCH", b"1") == A.FW_ERR_BAD_ARG
     assert b"NO_SUCH_SWITCH" in lib.fw_last_error()
     assert lib.fw_set_option(None, None) == A.FW_OK          # back to what the environment said at load time
+
+
+def _split_names(text):
+    return re.split(r",(?![^<]*>)", text)          # a comma inside <> belongs to a name
+
+
+def test_fw_debug_kernels_argument_checks_and_the_id_table():
+    """fw_debug_kernels (additive at ABI 8) makes no HIP call, so all of its contract but the recording itself is checked here: the argument
+    errors, snprintf's truncation, the empty set of a device no call has used, and the table of every name (device -1) — sorted, no
+    duplicates, the classes the launchers pick from all present, and _lib.last_kernels' split of commas outside <>."""
+    lib = _lib.load()
+    assert lib.fw_abi_version() == 8 == A.FW_ABI_VERSION
+    f = lib.fw_debug_kernels
+    buf = C.create_string_buffer(16)
+    assert f(0, None, 16) == A.FW_ERR_BAD_ARG and b"null buffer" in lib.fw_last_error()
+    assert f(-2, buf, 16) == A.FW_ERR_BAD_ARG and f(64, buf, 16) == A.FW_ERR_BAD_ARG and f(1 << 20, None, 0) == A.FW_ERR_BAD_ARG
+    assert b"device" in lib.fw_last_error()
+    # nothing has rendered on device 5 of this process: the empty list, terminated
+    buf.raw = b"x" * 16
+    assert f(5, buf, 16) == 0 and buf.raw[0] == 0 and buf.raw[1:] == b"x" * 15
+    assert f(5, None, 0) == 0
+    assert _lib.last_kernels(5) == frozenset()
+    # the whole table: cap = 0 writes nothing and returns the length; a short buffer gets cap - 1 characters and a terminator
+    n = f(-1, None, 0)
+    assert n > 1000
+    full = C.create_string_buffer(n + 1)
+    assert f(-1, full, n + 1) == n and len(full.value) == n
+    for cap in (1, 2, 16):
+        buf.raw = b"x" * 16
+        assert f(-1, buf, cap) == n
+        assert buf.raw[:cap] == full.value[:cap - 1] + b"\0" and buf.raw[cap:] == b"x" * (16 - cap)
+    exact = C.create_string_buffer(n)              # one short of the terminator's room: the last character is dropped
+    assert f(-1, exact, n) == n and exact.value == full.value[:n - 1]
+    names = _split_names(full.value.decode())
+    assert names == sorted(names) and len(set(names)) == len(names)
+    assert _lib.last_kernels(-1) == frozenset(names)
+    assert not any("@" in x for x in names)      # the wave counts belong to a launch, not to the table
+    n_ab = 8 if _lib.has_ab() else 0            # k_extend_bvh, k_shade<L,2,no chain>, k_bounce<*,*>
+    assert len(names) == 97 + n_ab
+    count = lambda prefix: sum(x == prefix or x.startswith(prefix + "<") for x in names)
+    assert [count(k) for k in ("k_shade", "k_shade_ls", "k_shade_pl", "k_shade_dl", "k_shade_env", "k_shade_pl_env", "k_shade_gx", "k_shade_gx_nee")] == \
+        [12 + (3 if n_ab else 0), 6, 6, 6, 3, 3, 6, 24]
+    assert [count(k) for k in ("k_extend_scan", "k_extend_tlas_wide", "k_blas_wide", "k_blas_lds", "k_extend_linear_simple", "k_extend_linear_defer")] == [4, 4, 4, 2, 2, 2]
+    for k in ("k_shade<2,0,no chain>", "k_shade_pl<2,0>", "k_blas_wide<q8,tris>", "k_blas_wide<f32,no tris>", "k_extend_scan<true,true,true>", "k_extend_tlas_park",
+              "k_extend_tlas", "k_extend_tlas_lds", "k_blas", "k_extend_linear", "k_extend_linear_nomesh", "k_extend_linear_plain", "k_extend_exact",
+              "k_shadow_resolve", "k_shadow_resolve_env", "k_shadow_resolve_pl", "k_shadow_resolve_dl", "k_shadow_resolve_gx", "k_shade_gx_nee<1,0,pl_env>"):
+        assert k in names, k
