@@ -36,7 +36,12 @@ sums, owner, rounds, directions and samples; the sampling flags apply; refuses w
 --probe-lit PROBES.npz [--probe-no-wrap] (a preview of the fixed view lit from the probes a --bake-probes run saved: one first-hit pass
 of --aov-samples samples and no paths, direct and indirect diffuse light both looked up in the grid, fw_probe_shade; the
 file must hold sh, grid_lo, grid_hi and grid_counts; --probe-no-wrap turns the guard against probes behind the surface off; -s is
-not used; refuses what --bake-probes refuses, --bake-probes and --bake-lightmap)."""
+not used; refuses what --bake-probes refuses, --bake-probes and --bake-lightmap).  --bake-probes ... --probe-depth R
+[--probe-depth-sharpness K] [--probe-depth-max M] (also bakes every probe's R x R octahedral map of depth moments, R in 4, 8, 16, 32,
+weights cos^(2^K), K in 0..8, default 6, distances clamped to M, default the grid's diagonal, over the same --probe-rounds rounds,
+fw_bake_probe_depth; the .npz also gets depth, depth_res, depth_sharpness and depth_max).  --probe-lit then weights every
+probe by its visibility from the surface (fw_probe_shade_vis) when the file holds them; --probe-no-visibility ignores them (the image
+of a file without them), --probe-normal-bias B moves the looked-up point B >= 0 world units along its normal first (default 0)."""
 import argparse
 import sys
 import time
@@ -87,6 +92,11 @@ def main(argv=None):
     ap.add_argument("--probe-max", default=None, metavar="X,Y,Z", help="with --bake-probes: the grid's last corner")
     ap.add_argument("--probe-dirs", type=int, default=None, metavar="D", help="with --bake-probes: directions per probe and round (default 256)")
     ap.add_argument("--probe-rounds", type=int, default=None, metavar="R", help="with --bake-probes: rounds of -s samples per direction (default 1)")
+    ap.add_argument("--probe-depth", type=int, default=None, metavar="R",
+                    help="with --bake-probes: also bake an R x R map of depth moments per probe (R in 4, 8, 16, 32), for --probe-lit's visibility")
+    ap.add_argument("--probe-depth-sharpness", type=int, default=None, metavar="K", help="with --probe-depth: a ray weighs cos^(2^K) in a texel, 0..8 (default 6)")
+    ap.add_argument("--probe-depth-max", type=float, default=None, metavar="M",
+                    help="with --probe-depth: distances are clamped to M > 0, which a miss counts as (default: the grid's diagonal)")
     ap.add_argument("--bake-lightmap", default=None, metavar="OBJECT,W,H",
                     help="bake the irradiance over the W x H UV texels of render object OBJECT (a mesh with uvs) into the .npz named by -o")
     ap.add_argument("--lightmap-dirs", type=int, default=None, metavar="D", help="with --bake-lightmap: directions per texel and round (default 64)")
@@ -95,6 +105,9 @@ def main(argv=None):
     ap.add_argument("--probe-lit", default=None, metavar="PROBES.npz",
                     help="render the view lit from the irradiance probes that a --bake-probes run saved, without tracing paths")
     ap.add_argument("--probe-no-wrap", action="store_true", help="with --probe-lit: no guard against light from probes behind the surface")
+    ap.add_argument("--probe-no-visibility", action="store_true", help="with --probe-lit: ignore the depth moments in the file")
+    ap.add_argument("--probe-normal-bias", type=float, default=None, metavar="B",
+                    help="with --probe-lit and depth moments: look visibility up B >= 0 world units along the normal (default 0)")
     opt = ap.parse_args(argv)
     if opt.probe_lit is not None:
         if (opt.bake_probes is not None or opt.bake_lightmap is not None or opt.camera != "pinhole" or opt.denoise is not None or opt.orbit
@@ -105,8 +118,12 @@ def main(argv=None):
             ap.error("--aov-samples needs S >= 1")
         if not opt.output:
             ap.error("--probe-lit needs -o FILE.png")
+        if opt.probe_normal_bias is not None and not 0.0 <= opt.probe_normal_bias < float("inf"):
+            ap.error("--probe-normal-bias B needs a finite B >= 0")
     elif opt.probe_no_wrap:
         ap.error("--probe-no-wrap needs --probe-lit")
+    elif opt.probe_no_visibility or opt.probe_normal_bias is not None:
+        ap.error("--probe-no-visibility and --probe-normal-bias need --probe-lit")
     if opt.bake_lightmap is not None:
         if (opt.bake_probes is not None or opt.camera != "pinhole" or opt.denoise is not None or opt.orbit or opt.adaptive is not None
                 or opt.progressive > 0 or opt.checkpoint or opt.temporal is not None):
@@ -151,10 +168,23 @@ def main(argv=None):
             ap.error("--probe-dirs D needs 1 <= D <= 2^20")
         if opt.probe_rounds is not None and opt.probe_rounds < 1:
             ap.error("--probe-rounds R needs R >= 1")
+        if opt.probe_depth is not None:
+            if opt.probe_depth not in (4, 8, 16, 32):
+                ap.error("--probe-depth R needs R in 4, 8, 16, 32")
+            if opt.probe_depth_sharpness is not None and not 0 <= opt.probe_depth_sharpness <= 8:
+                ap.error("--probe-depth-sharpness K needs 0 <= K <= 8")
+            if opt.probe_depth_max is not None and not 0.0 < opt.probe_depth_max < float("inf"):
+                ap.error("--probe-depth-max M needs a finite M > 0")
+            if opt.probe_depth_max is None and corners[0] == corners[1]:
+                ap.error("--probe-depth needs --probe-depth-max M for a grid of one point: it has no diagonal")
+        elif opt.probe_depth_sharpness is not None or opt.probe_depth_max is not None:
+            ap.error("--probe-depth-sharpness and --probe-depth-max need --probe-depth")
         if not opt.output:
             ap.error("--bake-probes needs -o FILE.npz")
     elif opt.probe_min is not None or opt.probe_max is not None or opt.probe_dirs is not None or opt.probe_rounds is not None:
         ap.error("--probe-min, --probe-max, --probe-dirs and --probe-rounds need --bake-probes")
+    elif opt.probe_depth is not None or opt.probe_depth_sharpness is not None or opt.probe_depth_max is not None:
+        ap.error("--probe-depth, --probe-depth-sharpness and --probe-depth-max need --bake-probes")
     if opt.adaptive is not None and (opt.progressive > 0 or opt.checkpoint):
         ap.error("--adaptive cannot be combined with --progressive or --checkpoint")
     if opt.temporal is not None:
@@ -209,7 +239,7 @@ def main(argv=None):
             print(f"firework: error: --bake-lightmap: {e}", file=sys.stderr)
             return 2
 
-    probe_grid = probe_sh = None
+    probe_grid = probe_sh = probe_depth = probe_moments = None
     if opt.probe_lit is not None:          # the file is looked at before the device is: a wrong one is a message, not a traceback
         import zipfile
         import numpy as np
@@ -221,8 +251,17 @@ def main(argv=None):
                     raise ValueError(f"no {', '.join(missing)} in it (bake it with this version's --bake-probes: only a grid can be looked up)")
                 probe_grid = ProbeGrid(z["grid_lo"], z["grid_hi"], z["grid_counts"], not opt.probe_no_wrap)
                 probe_sh = np.asarray(z["sh"], np.float32)
+                if "depth" in z.files and not opt.probe_no_visibility:
+                    from .api import ProbeDepth
+                    missing = [k for k in ("depth_res", "depth_sharpness", "depth_max") if k not in z.files]
+                    if missing:
+                        raise ValueError(f"depth without {', '.join(missing)} in it")
+                    probe_depth = ProbeDepth(int(z["depth_res"]), int(z["depth_sharpness"]), float(z["depth_max"]))
+                    probe_moments = np.asarray(z["depth"], np.float32)
             if probe_sh.shape != (probe_grid.n_probes, 9, 3):
                 raise ValueError(f"sh has shape {probe_sh.shape}, the grid {probe_grid.n_probes} probes")
+            if probe_depth is not None and probe_moments.shape != (probe_grid.n_probes, probe_depth.resolution, probe_depth.resolution, 2):
+                raise ValueError(f"depth has shape {probe_moments.shape}, the grid {probe_grid.n_probes} probes of resolution {probe_depth.resolution}")
         except (OSError, ValueError, zipfile.BadZipFile) as e:
             print(f"firework: error: --probe-lit {opt.probe_lit}: {e}", file=sys.stderr)
             return 2
@@ -243,15 +282,25 @@ def main(argv=None):
         probes = ProbeSet.grid(corners[0], corners[1], counts, 256 if opt.probe_dirs is None else opt.probe_dirs).seed(opt.seed)
         rounds = 1 if opt.probe_rounds is None else opt.probe_rounds
         sh, sums = renderer.bake_probes(scene, probes, rounds, device=opt.device)
+        extra = {}
+        if opt.probe_depth is not None:
+            from .api import ProbeDepth
+            diagonal = float(np.sqrt(sum((b - a) ** 2 for a, b in zip(corners[0], corners[1]))))
+            depth = ProbeDepth(opt.probe_depth, 6 if opt.probe_depth_sharpness is None else opt.probe_depth_sharpness,
+                               diagonal if opt.probe_depth_max is None else opt.probe_depth_max)
+            moments, _depth_sums = renderer.bake_probe_depth(scene, probes, depth, rounds, device=opt.device)
+            extra = dict(depth=moments, depth_res=np.int64(depth.resolution), depth_sharpness=np.int64(depth.sharpness_log2),
+                         depth_max=np.float32(depth.max_distance))
         print(f"Finished Baking in {int(time.time() - start)} s")
         print(f'Saving {probes.n_probes} probes to "{opt.output}"')
         with open(opt.output, "wb") as f:       # (np.savez would append .npz to a name without it)
             np.savez(f, positions=probes.positions, sh=sh, sums=sums, rounds=np.int64(rounds), directions=np.int64(probes.directions),
                      samples=np.int64(opt.samples), grid_lo=np.array(probes.grid_lo, np.float64), grid_hi=np.array(probes.grid_hi, np.float64),
-                     grid_counts=np.array(probes.grid_counts, np.int64))
+                     grid_counts=np.array(probes.grid_counts, np.int64), **extra)
         return 0
     if probe_grid is not None:
-        render = renderer.render_probe_lit(scene, probe_grid, probe_sh, opt.aov_samples, device=opt.device).rgb8
+        render = renderer.render_probe_lit(scene, probe_grid, probe_sh, opt.aov_samples, device=opt.device, depth=probe_depth, moments=probe_moments,
+                                           normal_bias=0.0 if opt.probe_normal_bias is None else opt.probe_normal_bias).rgb8
         print(f"Finished Rendering in {int(time.time() - start)} s")
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)

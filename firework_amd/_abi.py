@@ -185,6 +185,23 @@ class fw_probe_shade_params(C.Structure):
     _fields_ = [("width", u32), ("height", u32), ("gamma", f32), ("device", i32), ("on_device", i32), ("stream", C.c_void_p)]
 
 
+# probe visibility (include/firework_hip.h: fw_probe_depth_reduce, fw_bake_probe_depth, fw_probe_irradiance_vis, fw_probe_shade_vis)
+class fw_probe_depth(C.Structure):
+    _fields_ = [("resolution", u32), ("sharpness_log2", u32), ("max_distance", f32)]
+
+
+# the four prototypes (argument types; every one returns int), applied by _lib.load
+PROBE_DEPTH_PROTOTYPES = {
+    "fw_probe_depth_reduce": [C.c_int, C.POINTER(fw_probe_depth), u32, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_bake_probe_depth": [C.c_void_p, C.POINTER(fw_probe_set), C.POINTER(fw_probe_depth), C.POINTER(fw_trace_params), u32, u32, C.c_void_p,
+                            C.c_void_p, C.POINTER(fw_stats)],
+    "fw_probe_irradiance_vis": [C.POINTER(fw_probe_grid), C.c_void_p, C.POINTER(fw_probe_depth), C.c_void_p, f32, C.c_int, u32, C.c_void_p,
+                                C.c_void_p, u32, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_probe_shade_vis": [C.POINTER(fw_probe_grid), C.c_void_p, C.POINTER(fw_probe_depth), C.c_void_p, f32, C.POINTER(fw_probe_shade_params),
+                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
 # lightmaps on the device (include/firework_hip.h: fw_lightmap_texels, fw_lightmap_rays, fw_lightmap_reduce, fw_lightmap_dilate,
 # fw_bake_lightmap)
 class fw_lightmap(C.Structure):

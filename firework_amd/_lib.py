@@ -130,6 +130,9 @@ def load(preload=False, device=None):
     lib.fw_probe_shade.restype = C.c_int
     lib.fw_probe_shade.argtypes = [C.POINTER(A.fw_probe_grid), C.c_void_p, C.POINTER(A.fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
+    for name, argtypes in A.PROBE_DEPTH_PROTOTYPES.items():
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
     lib.fw_lightmap_texels.argtypes = [C.POINTER(A.fw_lightmap), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_void_p]
     lib.fw_lightmap_rays.restype = C.c_int
@@ -511,7 +514,20 @@ def _grid_abi(grid):
     return g.to_abi(), g.n_probes
 
 
-def probe_irradiance(grid, sh, positions, normals, out=None, stream=None, device=0):
+def _vis_args(depth, moments, normal_bias, n_probes, on_device, device):
+    """(fw_probe_depth, moments pointer, bias, what keeps the pointer alive) of a _vis call: moments (n, R, R, 2) float32, a device tensor
+    when the call's other arrays are"""
+    pd = depth.to_abi()
+    shape = (n_probes, int(pd.resolution), int(pd.resolution), 2)
+    if on_device:
+        import torch
+        _check_device_tensor(moments, shape, torch.float32, device, "moments")
+        return pd, moments.data_ptr(), float(normal_bias), moments
+    m = np.ascontiguousarray(np.asarray(moments, np.float32).reshape(shape))
+    return pd, m.ctypes.data, float(normal_bias), m
+
+
+def probe_irradiance(grid, sh, positions, normals, out=None, stream=None, device=0, _vis=None):
     """fw_probe_irradiance: the irradiance the probe grid `grid` (an api.ProbeGrid, or an api.ProbeSet made by ProbeSet.grid) with the
     coefficients sh (n, 9, 3) float32 gives at the points `positions` with the normals `normals`, (N, 3) float32 each; not clamped.
     numpy arrays: returns an (N, 3) float32 array (out: a contiguous float32 array of that shape to fill instead).  Torch tensors on
@@ -532,8 +548,12 @@ def probe_irradiance(grid, sh, positions, normals, out=None, stream=None, device
         if out is None:
             out = torch.empty((n, 3), dtype=torch.float32, device=positions.device)
         _check_device_tensor(out, (n, 3), torch.float32, device, "out")
-        _check(lib, lib.fw_probe_irradiance(C.byref(g), sh.data_ptr(), int(device), n, positions.data_ptr(), normals.data_ptr(), stride,
-                                            out.data_ptr(), 1, _stream_arg(stream, positions.device)))
+        tail = (int(device), n, positions.data_ptr(), normals.data_ptr(), stride, out.data_ptr(), 1, _stream_arg(stream, positions.device))
+        if _vis is not None:
+            pd, mom, bias, _keep = _vis_args(*_vis, n_probes, True, device)
+            _check(lib, lib.fw_probe_irradiance_vis(C.byref(g), sh.data_ptr(), C.byref(pd), mom, bias, *tail))
+        else:
+            _check(lib, lib.fw_probe_irradiance(C.byref(g), sh.data_ptr(), *tail))
         return out
     s = np.ascontiguousarray(np.asarray(sh, np.float32).reshape(n_probes, 9, 3))
     p = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))
@@ -543,12 +563,56 @@ def probe_irradiance(grid, sh, positions, normals, out=None, stream=None, device
     if out is None:
         out = np.empty(p.shape, np.float32)
     _host_f32(out, p.shape, "out")
-    _check(lib, lib.fw_probe_irradiance(C.byref(g), s.ctypes.data, int(device), int(p.shape[0]), p.ctypes.data, nr.ctypes.data, 3, out.ctypes.data,
-                                        0, None))
+    tail = (int(device), int(p.shape[0]), p.ctypes.data, nr.ctypes.data, 3, out.ctypes.data, 0, None)
+    if _vis is not None:
+        pd, mom, bias, _keep = _vis_args(*_vis, n_probes, False, device)
+        _check(lib, lib.fw_probe_irradiance_vis(C.byref(g), s.ctypes.data, C.byref(pd), mom, bias, *tail))
+    else:
+        _check(lib, lib.fw_probe_irradiance(C.byref(g), s.ctypes.data, *tail))
     return out
 
 
-def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear")):
+def probe_irradiance_vis(grid, sh, depth, moments, positions, normals, normal_bias=0.0, out=None, stream=None, device=0):
+    """fw_probe_irradiance_vis: probe_irradiance with every corner probe weighted by its visibility from the point: depth an
+    api.ProbeDepth, moments (n, R, R, 2) float32 as DeviceScene.bake_probe_depth returns them (a device tensor when the points are),
+    normal_bias >= 0 in world units.  Everything else as probe_irradiance."""
+    return probe_irradiance(grid, sh, positions, normals, out, stream, device, _vis=(depth, moments, normal_bias))
+
+
+def probe_depth_reduce(depth, rays, hits, directions, sums=None, device=0, stream=None):
+    """fw_probe_depth_reduce: adds one round's depth sums (A, B, W per texel, each rounded to float32 once) to sums (N, R, R, 4) float32,
+    updated in place (None: zeros); .w is left alone.  rays (N * D, 6) float32 and hits as DeviceScene.trace returns them for those rays:
+    a HIT_DTYPE array for numpy rays, or an (N * D, 12) float32 device tensor for rays on cuda:`device`, reduced on `stream` (default: the
+    current torch stream) where they lie.  Returns sums."""
+    lib = load()
+    pd = depth.to_abi()
+    d, R = int(directions), int(pd.resolution)
+    total = int(rays.shape[0])
+    if d < 1 or total % d or tuple(rays.shape) != (total, 6) or int(hits.shape[0]) != total:
+        raise ValueError(f"rays must have shape (N * {d}, 6) and hits N * {d} records")
+    n = total // d
+    if type(rays).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
+        _check_device_tensor(hits, (total, 12), torch.float32, device, "hits")
+        if sums is None:
+            sums = torch.zeros((n, R, R, 4), dtype=torch.float32, device=rays.device)
+        _check_device_tensor(sums, (n, R, R, 4), torch.float32, device, "sums")
+        _check(lib, lib.fw_probe_depth_reduce(int(device), C.byref(pd), n, d, rays.data_ptr(), hits.data_ptr(), sums.data_ptr(), 1,
+                                              _stream_arg(stream, rays.device)))
+        return sums
+    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
+    h = np.ascontiguousarray(hits)
+    if h.dtype != HIT_DTYPE:
+        raise ValueError("host hits must be an array of HIT_DTYPE")
+    if sums is None:
+        sums = np.zeros((n, R, R, 4), np.float32)
+    _host_f32(sums, (n, R, R, 4), "sums")
+    _check(lib, lib.fw_probe_depth_reduce(int(device), C.byref(pd), n, d, r.ctypes.data, h.ctypes.data, sums.ctypes.data, 0, None))
+    return sums
+
+
+def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear"), _vis=None):
     """fw_probe_shade: fw_render_aovs' records `aov` (N, 12) lit from the probe grid `grid` (see probe_irradiance) with the coefficients
     sh (n, 9, 3): out = albedo (coverage max(E, 0) / pi + (1 - coverage)), resolved as fw_denoise resolves its outputs.  All host arrays
     (numpy): returns (rgb8, gamma, linear) host arrays of shape (N, 3).  Contiguous float32 torch tensors on cuda:`device`: shaded on
@@ -571,7 +635,12 @@ def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, 
         p.on_device = 1
         p.stream = _stream_arg(stream, dev)
         ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        _check(lib, lib.fw_probe_shade(C.byref(g), sh.data_ptr(), C.byref(p), aov.data_ptr(), ptr(lin), ptr(gam), ptr(rgb8)))
+        tail = (C.byref(p), aov.data_ptr(), ptr(lin), ptr(gam), ptr(rgb8))
+        if _vis is not None:
+            pd, mom, bias, _keep = _vis_args(*_vis, n_probes, True, device)
+            _check(lib, lib.fw_probe_shade_vis(C.byref(g), sh.data_ptr(), C.byref(pd), mom, bias, *tail))
+        else:
+            _check(lib, lib.fw_probe_shade(C.byref(g), sh.data_ptr(), *tail))
         return rgb8, gam, lin
     s = np.ascontiguousarray(np.asarray(sh, np.float32).reshape(n_probes, 9, 3))
     a = np.ascontiguousarray(np.asarray(aov, np.float32).reshape(n, 12))
@@ -579,8 +648,19 @@ def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, 
     gam = np.empty((n, 3), np.float32) if want[1] else None
     lin = np.empty((n, 3), np.float32) if want[2] else None
     ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
-    _check(lib, lib.fw_probe_shade(C.byref(g), s.ctypes.data, C.byref(p), a.ctypes.data, ptr(lin), ptr(gam), ptr(rgb8)))
+    tail = (C.byref(p), a.ctypes.data, ptr(lin), ptr(gam), ptr(rgb8))
+    if _vis is not None:
+        pd, mom, bias, _keep = _vis_args(*_vis, n_probes, False, device)
+        _check(lib, lib.fw_probe_shade_vis(C.byref(g), s.ctypes.data, C.byref(pd), mom, bias, *tail))
+    else:
+        _check(lib, lib.fw_probe_shade(C.byref(g), s.ctypes.data, *tail))
     return rgb8, gam, lin
+
+
+def probe_shade_vis(grid, sh, depth, moments, aov, width, height, normal_bias=0.0, gamma=2.2, device=0, stream=None,
+                    outputs=("rgb8", "gamma", "linear")):
+    """fw_probe_shade_vis: probe_shade with the lookup of probe_irradiance_vis (depth, moments, normal_bias: see there)."""
+    return probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, _vis=(depth, moments, normal_bias))
 
 
 def _lightmap_abi(lightmap, chunk=None):
@@ -988,6 +1068,39 @@ class DeviceScene:
         s, _pos = _probe_abi(probes, chunk)
         return self._bake(self._lib.fw_bake_probes, s, (), (int(s.n_probes), 9, 3), rounds, samples, first_round, sums, seed, use_bvh, stream,
                           paths_per_batch, flags, on_device)
+
+    def bake_probe_depth(self, probes, depth, rounds=1, first_round=0, sums=None, seed=0, use_bvh=True, stream=None, rays_per_batch=0, flags=0,
+                         chunk=None, on_device=False):
+        """fw_bake_probe_depth: the rounds [first_round, first_round + rounds) of the depth maps (an api.ProbeDepth) of an api.ProbeSet,
+        `chunk` probes at a time (None: the set's own setting; 0: automatic).  sums: (N, R, R, 4) float32 running sums of the rounds
+        before first_round, updated in place (None: zeros, only with first_round 0).  Returns (moments, sums, stats): moments (N, R, R,
+        2) float32 (mu, mu2); host arrays, or — sums a device tensor on this scene's device, or on_device=True — device tensors, baked
+        on `stream` (default: the current torch stream)."""
+        s, _pos = _probe_abi(probes, chunk)
+        pd = depth.to_abi()
+        n, R = int(s.n_probes), int(pd.resolution)
+        p = A.fw_trace_params()
+        p.use_bvh, p.flags, p.seed, p.rays_per_batch = int(bool(use_bvh)), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rays_per_batch)
+        st = A.fw_stats()
+        if on_device or (sums is not None and type(sums).__module__.startswith("torch")):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if sums is None:
+                sums = torch.zeros((n, R, R, 4), dtype=torch.float32, device=dev)
+            _check_device_tensor(sums, (n, R, R, 4), torch.float32, self.device, "sums")
+            out = torch.empty((n, R, R, 2), dtype=torch.float32, device=dev)
+            p.on_device = 1
+            p.stream = _stream_arg(stream, dev)
+            ptrs = sums.data_ptr(), out.data_ptr()
+        else:
+            if sums is None:
+                sums = np.zeros((n, R, R, 4), np.float32)
+            _host_f32(sums, (n, R, R, 4), "sums")
+            out = np.empty((n, R, R, 2), np.float32)
+            ptrs = sums.ctypes.data, out.ctypes.data
+        _check(self._lib, self._lib.fw_bake_probe_depth(self.handle, C.byref(s), C.byref(pd), C.byref(p), int(first_round), int(rounds), *ptrs,
+                                                        C.byref(st)))
+        return out, sums, st.as_dict()
 
     def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,
                       flags=0, chunk=None, on_device=False):

@@ -1350,6 +1350,203 @@ def probe_shade_ref(grid, sh, aov, irradiance=None) -> np.ndarray:
     return (a[:, 0:3] * (v * (E * inv_pi) + (np.float32(1.0) - v))).astype(np.float32)
 
 
+# --------------------------------------------------------------------------- probe visibility
+class ProbeDepth:
+    """The depth maps of a probe set (fw_probe_depth): every probe has a resolution x resolution octahedral map of the first two moments
+    of the distance to the nearest surface; a ray's weight in a texel is max(0, T.d)^(2^sharpness_log2); distances are clamped to
+    max_distance, which a miss counts as."""
+
+    def __init__(self, resolution: int = 8, sharpness_log2: int = 6, max_distance: float = 1.0e3):
+        self.resolution, self.sharpness_log2, self.max_distance = int(resolution), int(sharpness_log2), float(np.float32(max_distance))
+
+    def to_abi(self) -> A.fw_probe_depth:
+        d = A.fw_probe_depth()
+        d.resolution, d.sharpness_log2, d.max_distance = self.resolution, self.sharpness_log2, self.max_distance
+        return d
+
+
+def _sgn1(v):
+    return np.where(v >= 0.0, 1.0, -1.0)
+
+
+def probe_depth_dirs(R: int) -> np.ndarray:
+    """(R, R, 3) float64, [b][a] = the unit direction of texel (column a, row b) of an R x R octahedral map, as the header states it"""
+    R = int(R)
+    e = ((np.arange(R, dtype=np.float64) + 0.5) * 2.0) / float(R) - 1.0
+    ex, ey = np.broadcast_to(e[None, :], (R, R)), np.broadcast_to(e[:, None], (R, R))
+    z = (1.0 - np.abs(ex)) - np.abs(ey)
+    x = np.where(z < 0.0, (1.0 - np.abs(ey)) * _sgn1(ex), ex)
+    y = np.where(z < 0.0, (1.0 - np.abs(ex)) * _sgn1(ey), ey)
+    l = np.sqrt((x * x + y * y) + z * z)
+    return np.stack([x / l, y / l, z / l], axis=-1)
+
+
+def probe_depth_reduce(pd: "ProbeDepth", rays, hits_t, hits_object, directions: int, terms: bool = False) -> np.ndarray:
+    """The numpy float64 statement of fw_probe_depth_reduce: (N, R, R, 3) float64, the accumulators (A, B, W) of one round before their
+    one rounding to float32, for rays (N * D, 6) float32 (the directions as stored) and the hits' t (float32) and object (uint32,
+    0xFFFFFFFF = miss) columns.  terms=True: returns (sums, G) with G (N, 3) = sum_j |d_j|^(2^k) dist_j^m for m = 1, 2, 0 (the order of
+    A, B, W): what a rounding-error bound of the weights scales with."""
+    D, R, k = int(directions), int(pd.resolution), int(pd.sharpness_log2)
+    d = np.asarray(rays, np.float32).astype(np.float64).reshape(-1, D, 6)[..., 3:]
+    t = np.asarray(hits_t, np.float32).astype(np.float64).reshape(-1, D)
+    miss = np.asarray(hits_object).astype(np.uint32).reshape(-1, D) == np.uint32(0xFFFFFFFF)
+    r_max = float(np.float32(pd.max_distance))
+    T = probe_depth_dirs(R)
+    n = d.shape[0]
+    out = np.zeros((n, R, R, 3))
+    with np.errstate(all="ignore"):
+        length = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+        dist = np.where(miss, r_max, np.fmin(t * length, r_max))
+        for j in range(D):
+            dj = d[:, j, None, None, :]
+            w = np.fmax(0.0, (T[None, ..., 0] * dj[..., 0] + T[None, ..., 1] * dj[..., 1]) + T[None, ..., 2] * dj[..., 2])
+            for _ in range(k):
+                w = w * w
+            dd = dist[:, j, None, None]
+            wd = w * dd
+            out[..., 0] = out[..., 0] + wd
+            out[..., 1] = out[..., 1] + wd * dd
+            out[..., 2] = out[..., 2] + w
+        lk = length ** float(2 ** k)
+        G = np.stack([(lk * dist).sum(axis=1), (lk * dist * dist).sum(axis=1), lk.sum(axis=1)], axis=-1)
+    return (out, G) if terms else out
+
+
+def probe_depth_moments(pd: "ProbeDepth", sums) -> np.ndarray:
+    """The statement of the moments: (N, R, R, 2) float32 (mu, mu2) = float32(sums.x / sums.z), float32(sums.y / sums.z) in float64 from
+    the float32 running sums (N, R, R, 4); a texel with sums.z == 0 gets (r_max, float32(r_max r_max))."""
+    s = np.asarray(sums, np.float32).astype(np.float64)
+    r_max = float(np.float32(pd.max_distance))
+    with np.errstate(all="ignore"):
+        none = s[..., 2] == 0.0
+        mu = np.where(none, r_max, s[..., 0] / s[..., 2])
+        mu2 = np.where(none, float(np.float32(r_max * r_max)), s[..., 1] / s[..., 2])
+        return np.stack([mu, mu2], axis=-1).astype(np.float32)
+
+
+def probe_depth_fetch(R: int, maps, dirs):
+    """(mu, mu2), float64 (M,) each: the bilinear fetch of the header along the unit directions dirs (M, 3) from the maps (M, R, R, 2) —
+    one map per direction — edges clamped."""
+    R = int(R)
+    m = np.asarray(maps, np.float32).astype(np.float64).reshape(-1, R, R, 2)
+    v = np.asarray(dirs, np.float64).reshape(-1, 3)
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    rows = np.arange(m.shape[0])
+    with np.errstate(all="ignore"):
+        s1 = (np.abs(x) + np.abs(y)) + np.abs(z)
+        ox, oy = x / s1, y / s1
+        fx, fy = (1.0 - np.abs(oy)) * _sgn1(ox), (1.0 - np.abs(ox)) * _sgn1(oy)
+        ox, oy = np.where(z < 0.0, fx, ox), np.where(z < 0.0, fy, oy)
+        top = float(R) - 1.0
+        su = np.fmin(np.fmax(((ox + 1.0) * 0.5) * float(R) - 0.5, 0.0), top)
+        sv = np.fmin(np.fmax(((oy + 1.0) * 0.5) * float(R) - 0.5, 0.0), top)
+        iu, jv = np.fmin(np.floor(su), top - 1.0), np.fmin(np.floor(sv), top - 1.0)
+        fu, fv = su - iu, sv - jv
+        i, j = iu.astype(np.int64), jv.astype(np.int64)
+        m00, m10, m01, m11 = m[rows, j, i], m[rows, j, i + 1], m[rows, j + 1, i], m[rows, j + 1, i + 1]
+        gu, gv = (1.0 - fu)[:, None], (1.0 - fv)[:, None]
+        out = ((m00 * gu + m10 * fu[:, None]) * gv) + ((m01 * gu + m11 * fu[:, None]) * fv[:, None])
+    return out[:, 0], out[:, 1]
+
+
+def probe_lookup_vis(grid, sh, pd: "ProbeDepth", moments, positions, normals, normal_bias: float = 0.0, terms: bool = False):
+    """The numpy float64 statement of fw_probe_irradiance_vis (include/firework_hip.h): probe_lookup with every corner's weight multiplied
+    by g — the wrap factor (1 without wrap) times the visibility of the corner's probe from p + normal_bias nh, floored at 1e-6 and
+    crushed below 0.2 — and the weights always divided by their sum.  moments (n, R, R, 2) float32.  terms=True: returns (E, T, W) with T
+    as probe_lookup's and X a dict of per-corner arrays (N, corners), in corner order: the normalised weights "w", and "fac", "v", "g",
+    "dist", "mu", "mu2" and "m1", "m2" (the largest |mu| and |mu2| of the corner probe's map), which the error bound of the weights needs."""
+    g = ProbeGrid.of(grid)
+    R = int(pd.resolution)
+    sh = np.asarray(sh, np.float32).astype(np.float64).reshape(g.n_probes, 9, 3)
+    mom = np.asarray(moments, np.float32).reshape(g.n_probes, R, R, 2)
+    p = np.asarray(positions, np.float32).astype(np.float64).reshape(-1, 3)
+    nr = np.asarray(normals, np.float32).astype(np.float64).reshape(-1, 3)
+    bias = float(np.float32(normal_bias))
+    n = p.shape[0]
+    E, T = np.zeros((n, 3)), np.zeros((n, 3))
+    with np.errstate(all="ignore"):
+        nl2 = (nr[:, 0] * nr[:, 0] + nr[:, 1] * nr[:, 1]) + nr[:, 2] * nr[:, 2]
+        ok = np.all(np.isfinite(p), axis=1) & np.all(np.isfinite(nr), axis=1) & (nl2 > 0.0)
+        nl = np.sqrt(nl2)
+        nh = nr / nl[:, None]
+        nh = np.where(ok[:, None], nh, 0.0)
+        p = np.where(ok[:, None], p, 0.0)
+        x, y, z = nh[:, 0], nh[:, 1], nh[:, 2]
+        q = p + bias * nh
+        idx, f, two = [], [], []
+        for k in range(3):
+            c = g.counts[k]
+            two.append(c > 1)
+            if c > 1:
+                cm1 = float(c - 1)
+                s = ((p[:, k] - g.lo[k]) / (g.hi[k] - g.lo[k])) * cm1
+                s = np.fmin(np.fmax(s, 0.0), cm1)
+                fl = np.fmin(np.floor(s), cm1 - 1.0)
+                idx.append(fl.astype(np.int64))
+                f.append(s - fl)
+            else:
+                idx.append(np.zeros(n, np.int64))
+                f.append(np.zeros(n))
+        corners = [(dx, dy, dz) for dz in range(2 if two[2] else 1) for dy in range(2 if two[1] else 1) for dx in range(2 if two[0] else 1)]
+        w, X = [], {k: [] for k in ("fac", "v", "g", "dist", "mu", "mu2", "m1", "m2")}
+        for d in corners:
+            wk = [f[k] if d[k] else 1.0 - f[k] for k in range(3)]
+            P = []
+            for k in range(3):
+                if two[k]:
+                    P.append(g.lo[k] + (idx[k] + d[k]).astype(np.float64) * ((g.hi[k] - g.lo[k]) / float(g.counts[k] - 1)))
+                else:
+                    P.append(np.full(n, 0.5 * (g.lo[k] + g.hi[k])))
+            fac = np.ones(n)
+            if g.wrap:
+                r = [P[k] - p[:, k] for k in range(3)]
+                rl2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]
+                rl = np.sqrt(rl2)
+                dot = (x * (r[0] / rl) + y * (r[1] / rl)) + z * (r[2] / rl)
+                h = 0.5 * (dot + 1.0)
+                fac = np.where(rl2 > 0.0, h * h + 0.2, 1.2)
+            rv = [q[:, k] - P[k] for k in range(3)]
+            dist = np.sqrt((rv[0] * rv[0] + rv[1] * rv[1]) + rv[2] * rv[2])
+            probe = ((idx[2] + d[2]) * g.counts[1] + (idx[1] + d[1])) * g.counts[0] + (idx[0] + d[0])
+            safe = np.where(dist != 0.0, dist, 1.0)
+            dirs = np.stack([np.where(dist != 0.0, rv[k] / safe, (0.0, 0.0, 1.0)[k]) for k in range(3)], axis=-1)
+            mu, mu2 = probe_depth_fetch(R, mom[probe], dirs)
+            var = np.abs(mu * mu - mu2)
+            t = dist - mu
+            c = var / (var + t * t)
+            v = np.where((dist == 0.0) | (dist <= mu), 1.0, (c * c) * c)
+            gg = np.fmax(1e-6, fac * v)
+            gg = np.where(gg < 0.2, (gg * (gg * gg)) * 25.0, gg)
+            w.append(((wk[0] * wk[1]) * wk[2]) * gg)
+            if terms:
+                am = np.abs(mom.astype(np.float64)).reshape(g.n_probes, -1, 2).max(axis=1)
+                for name, val in (("fac", fac), ("v", v), ("g", gg), ("dist", dist), ("mu", mu), ("mu2", mu2), ("m1", am[probe, 0]), ("m2", am[probe, 1])):
+                    X[name].append(val)
+        wsum = np.zeros(n)
+        for wd in w:
+            wsum = wsum + wd
+        w = [wd / wsum for wd in w]
+        B = sh_basis(nh) * _SH_COSINE
+        for d, wd in zip(corners, w):
+            probe = ((idx[2] + d[2]) * g.counts[1] + (idx[1] + d[1])) * g.counts[0] + (idx[0] + d[0])
+            c = sh[probe]                                                  # (N, 9, 3)
+            e = B[:, 0, None] * c[:, 0]
+            t = np.abs(e)
+            for k in range(1, 9):
+                term = B[:, k, None] * c[:, k]
+                e = e + term
+                t = t + np.abs(term)
+            E = E + wd[:, None] * e
+            T = T + np.abs(wd)[:, None] * t
+    E[~ok] = 0.0
+    T[~ok] = 0.0
+    if not terms:
+        return E
+    X = {k: np.stack(v, axis=-1) for k, v in X.items()}
+    X["w"] = np.stack(w, axis=-1)
+    return E, T, X
+
+
 # --------------------------------------------------------------------------- lightmaps (fw_bake_lightmap; DESIGN.md §9o)
 LIGHTMAP_NO_OWNER = 0xFFFFFFFF          # FW_NO_HIT in an owner map
 
@@ -1962,6 +2159,25 @@ class Renderer:
             if ds is not scene:
                 ds.close()
 
+    def bake_probe_depth(self, scene, probes: "ProbeSet", depth: "ProbeDepth", rounds: int = 1, first_round: int = 0, sums=None, chunk=None,
+                         device: int = 0, stream=None, on_device: bool = False):
+        """The depth maps of a probe set baked on the device (not in the reference; fw_bake_probe_depth): `rounds` rounds
+        of the set's rays traced with this renderer's seed (+ the round), use_bvh and flags, their hit distances reduced to two moments
+        per texel of every probe's octahedral map.  Returns (moments, sums): (N, R, R, 2) and (N, R, R, 4) float32; pass sums back with
+        first_round = the rounds it holds to add more.  on_device and chunk as _lib.DeviceScene.bake_probe_depth; the call's stats are
+        kept in self.probe_depth_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        from . import _lib
+        s = self.settings
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            moments, sums, self.probe_depth_stats = ds.bake_probe_depth(probes, depth, rounds, first_round, sums, seed=s["seed"],
+                                                                        use_bvh=s["use_bvh"], stream=stream, flags=s["flags"], chunk=chunk,
+                                                                        on_device=on_device)
+            return moments, sums
+        finally:
+            if ds is not scene:
+                ds.close()
+
     def bake_lightmap(self, scene, lightmap: "Lightmap", rounds: int = 1, dilate: int = 2, first_round: int = 0, sums=None, chunk=None,
                       device: int = 0, stream=None, on_device: bool = False):
         """A lightmap baked on the device (not in the reference; fw_bake_lightmap): `rounds` rounds of the lightmap's cosine-weighted
@@ -1983,15 +2199,20 @@ class Renderer:
             if ds is not scene:
                 ds.close()
 
-    def render_probe_lit(self, scene, probes, sh, aov_samples: int = 8, wrap: bool = True, device: int = 0, model: "CameraModel" = None) -> RenderResult:
+    def render_probe_lit(self, scene, probes, sh, aov_samples: int = 8, wrap: bool = True, device: int = 0, model: "CameraModel" = None,
+                         depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0) -> RenderResult:
         """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
         (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
         from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
         sh (n, 9, 3), as bake_probes returns them.  One first-hit pass and no paths: direct and indirect diffuse light both come from the
         probes.  The records stay on the device.  A ProbeSet without a grid: ValueError.  `scene`: a Scene, a SceneDesc or an uploaded
-        _lib.DeviceScene."""
+        _lib.DeviceScene.  depth (a ProbeDepth) with moments (n, R, R, 2), as bake_probe_depth returns them: the frame is shaded by
+        fw_probe_shade_vis, every probe weighted by its visibility from the surface point moved normal_bias along its normal
+        (DESIGN.md §9s); depth=None: exactly the calls above."""
         import torch
         from . import _lib
+        if depth is not None and moments is None:
+            raise ValueError("depth needs the moments bake_probe_depth returned")
         grid = ProbeGrid.of(probes, wrap)
         s = self.settings
         w, h = (int(model.width), int(model.height)) if model is not None else (int(s["width"]), int(s["height"]))
@@ -2004,7 +2225,12 @@ class Renderer:
             else:
                 ds.aovs(self, aov_samples, out=aov)
             d_sh = torch.from_numpy(np.ascontiguousarray(np.asarray(sh, np.float32).reshape(grid.n_probes, 9, 3))).to(dev)
-            rgb8, gam, lin = _lib.probe_shade(grid, d_sh, aov, w, h, s["gamma"], ds.device)
+            if depth is not None:
+                R = int(depth.resolution)
+                d_mom = torch.from_numpy(np.ascontiguousarray(np.asarray(moments, np.float32).reshape(grid.n_probes, R, R, 2))).to(dev)
+                rgb8, gam, lin = _lib.probe_shade_vis(grid, d_sh, depth, d_mom, aov, w, h, normal_bias, s["gamma"], ds.device)
+            else:
+                rgb8, gam, lin = _lib.probe_shade(grid, d_sh, aov, w, h, s["gamma"], ds.device)
             stats = dict(ds.aovs_stats)
         finally:
             if ds is not scene:

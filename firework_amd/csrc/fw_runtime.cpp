@@ -15,6 +15,7 @@
 #include "fw_probes.h"
 #include "fw_lightmap.h"
 #include "fw_probe_lookup.h"
+#include "fw_probe_depth.h"
 
 #include <algorithm>
 #include <atomic>
@@ -4329,37 +4330,66 @@ int probe_grid_check(const fw_probe_grid *g, bool &too_large, fw::DProbeGrid &d)
     return FW_OK;
 }
 
+// ---- probe visibility (include/firework_hip.h) --------------------------------------------------------------------
+// A depth description's own argument checks (FW_ERR_BAD_ARG only)
+int probe_depth_check(const fw_probe_depth *pd) {
+    if (pd->resolution != 4 && pd->resolution != 8 && pd->resolution != 16 && pd->resolution != 32)
+        return fail(FW_ERR_BAD_ARG, "a probe depth map's resolution must be 4, 8, 16 or 32");
+    if (pd->sharpness_log2 > 8) return fail(FW_ERR_BAD_ARG, "sharpness_log2 must be in 0..8");
+    if (!std::isfinite(pd->max_distance) || !(pd->max_distance > 0.f)) return fail(FW_ERR_BAD_ARG, "max_distance must be finite and > 0");
+    return FW_OK;
+}
+// What the _vis calls add to fw_probe_irradiance's and fw_probe_shade's arguments; NULL: the call without visibility
+struct ProbeVis { const fw_probe_depth *pd; const float *moments; float normal_bias; };
+int probe_vis_check(const ProbeVis *vis) {
+    if (int rc = probe_depth_check(vis->pd)) return rc;
+    if (!std::isfinite(vis->normal_bias) || vis->normal_bias < 0.f) return fail(FW_ERR_BAD_ARG, "normal_bias must be finite and >= 0");
+    return FW_OK;
+}
+inline bool probe_vis_too_large(const ProbeVis *vis, const fw::DProbeGrid &g) {      // n_probes x R^2 >= 2^31 (n_probes < 2^31 is checked first)
+    return vis && (uint64_t)g.counts[0] * g.counts[1] * g.counts[2] * vis->pd->resolution * vis->pd->resolution >= (1ull << 31);
+}
+
 // fw_probe_irradiance: with device arrays the kernel works on the caller's memory and nothing is allocated; with host arrays one device
-// allocation per call holds sh and a slab of points (24 B in, 12 B out each), released on every way out
+// allocation per call holds sh and a slab of points (24 B in, 12 B out each), released on every way out.  vis: fw_probe_irradiance_vis —
+// the moments are one more array, staged after sh.
 int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device, uint32_t n, const float *positions, const float *normals,
-                          uint32_t stride, float *irradiance, int on_device, void *stream_) {
-    if (!grid || !sh || !positions || !normals || !irradiance) return fail(FW_ERR_BAD_ARG, "null argument");
+                          uint32_t stride, float *irradiance, int on_device, void *stream_, const ProbeVis *vis = nullptr) {
+    if (!grid || !sh || !positions || !normals || !irradiance || (vis && (!vis->pd || !vis->moments))) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (vis) if (int rc = probe_vis_check(vis)) return rc;
     bool too_large = false;
     fw::DProbeGrid g{};
     if (int rc = probe_grid_check(grid, too_large, g)) return rc;
     if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
     if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
     if (device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
-    if (on_device && (((uintptr_t)sh | (uintptr_t)positions | (uintptr_t)normals | (uintptr_t)irradiance) & 3u))
+    if (on_device && (((uintptr_t)sh | (uintptr_t)positions | (uintptr_t)normals | (uintptr_t)irradiance | (uintptr_t)(vis ? vis->moments : nullptr)) & 3u))
         return fail(FW_ERR_BAD_ARG, "device arrays must be 4-byte aligned");
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
+    if (probe_vis_too_large(vis, g)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
+    const auto launch = [&](const float *d_sh, const float *d_mom, uint32_t k, const float *pos, const float *nrm, uint32_t st, float *out) {
+        if (vis) fw::launch_probe_irradiance_vis(stream, g, fw::DProbeVis{d_mom, (double)vis->normal_bias, vis->pd->resolution}, d_sh, k, pos, nrm, st, out);
+        else fw::launch_probe_irradiance(stream, g, d_sh, k, pos, nrm, st, out);
+    };
     if (on_device) {
-        fw::launch_probe_irradiance(stream, g, sh, n, positions, normals, stride, irradiance);
+        launch(sh, vis ? vis->moments : nullptr, n, positions, normals, stride, irradiance);
         HIPCHK(hipStreamSynchronize(stream));
         HIPCHK(hipGetLastError());
         return FW_OK;
     }
-    const size_t sh_bytes = (size_t)g.counts[0] * g.counts[1] * g.counts[2] * 108;
+    const size_t n_probes = (size_t)g.counts[0] * g.counts[1] * g.counts[2];
+    const size_t sh_bytes = n_probes * 108, mom_bytes = vis ? n_probes * vis->pd->resolution * vis->pd->resolution * 8 : 0;
     const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 36));
-    const size_t o_in = align256(sh_bytes), o_out = o_in + align256((size_t)per * 24);
+    const size_t o_mom = align256(sh_bytes), o_in = o_mom + align256(mom_bytes), o_out = o_in + align256((size_t)per * 24);
     std::vector<float> pack((size_t)per * 6);
     CallScratch scratch(device);
     if (int rc = scratch.alloc(o_out + (size_t)per * 12)) return rc;
     uint8_t *base = (uint8_t *)scratch.p;
     const float *d_in = (const float *)(base + o_in);
     HIPCHK(hipMemcpyAsync(base, sh, sh_bytes, hipMemcpyHostToDevice, stream));
+    if (vis) HIPCHK(hipMemcpyAsync(base + o_mom, vis->moments, mom_bytes, hipMemcpyHostToDevice, stream));
     for (uint32_t done = 0; done < n; done += per) {
         const uint32_t k = std::min(per, n - done);
         for (uint32_t i = 0; i < k; i++) {
@@ -4368,7 +4398,7 @@ int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device
             o[0] = ps[0]; o[1] = ps[1]; o[2] = ps[2]; o[3] = ns[0]; o[4] = ns[1]; o[5] = ns[2];
         }
         HIPCHK(hipMemcpyAsync(base + o_in, pack.data(), (size_t)k * 24, hipMemcpyHostToDevice, stream));
-        fw::launch_probe_irradiance(stream, g, (const float *)base, k, d_in, d_in + 3, 6, (float *)(base + o_out));
+        launch((const float *)base, (const float *)(base + o_mom), k, d_in, d_in + 3, 6, (float *)(base + o_out));
         HIPCHK(hipMemcpyAsync(irradiance + (size_t)done * 3, base + o_out, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
     }
@@ -4376,11 +4406,13 @@ int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device
     return FW_OK;
 }
 
-// fw_probe_shade: as fw_probe_irradiance; a host call's slab holds 48 B of record and up to 27 B of outputs per pixel
+// fw_probe_shade: as fw_probe_irradiance; a host call's slab holds 48 B of record and up to 27 B of outputs per pixel.  vis:
+// fw_probe_shade_vis.
 int probe_shade_impl(const fw_probe_grid *grid, const float *sh, const fw_probe_shade_params *p, const float *aov, float *linear_rgb,
-                     float *gamma_rgb, uint8_t *rgb8) {
-    if (!grid || !sh || !p || !aov) return fail(FW_ERR_BAD_ARG, "null argument");
+                     float *gamma_rgb, uint8_t *rgb8, const ProbeVis *vis = nullptr) {
+    if (!grid || !sh || !p || !aov || (vis && (!vis->pd || !vis->moments))) return fail(FW_ERR_BAD_ARG, "null argument");
     if (!linear_rgb && !gamma_rgb && !rgb8) return fail(FW_ERR_BAD_ARG, "at least one output is needed");
+    if (vis) if (int rc = probe_vis_check(vis)) return rc;
     bool too_large = false;
     fw::DProbeGrid g{};
     if (int rc = probe_grid_check(grid, too_large, g)) return rc;
@@ -4389,40 +4421,178 @@ int probe_shade_impl(const fw_probe_grid *grid, const float *sh, const fw_probe_
     if (p->device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
     if (p->on_device && (((uintptr_t)aov & 15u) || (((uintptr_t)sh | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb) & 3u)))
         return fail(FW_ERR_BAD_ARG, "device aov must be 16-byte aligned, device sh, linear_rgb and gamma_rgb 4-byte aligned");
+    if (vis && p->on_device && ((uintptr_t)vis->moments & 3u)) return fail(FW_ERR_BAD_ARG, "device moments must be 4-byte aligned");
     const uint64_t full = (uint64_t)p->width * p->height;
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
+    if (probe_vis_too_large(vis, g)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
     if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
     const int dev = p->device;
     if (int rc = use_device(dev)) return rc;
     hipStream_t stream = (hipStream_t)p->stream;
     const uint32_t n = (uint32_t)full;
+    const auto launch = [&](const float *d_sh, const float *d_mom, uint32_t k, const float *d_aov, uint8_t *o8, float *og, float *ol) {
+        if (vis) fw::launch_probe_shade_vis(stream, g, fw::DProbeVis{d_mom, (double)vis->normal_bias, vis->pd->resolution}, d_sh, k, d_aov, p->gamma, o8, og, ol);
+        else fw::launch_probe_shade(stream, g, d_sh, k, d_aov, p->gamma, o8, og, ol);
+    };
     if (p->on_device) {
-        fw::launch_probe_shade(stream, g, sh, n, aov, p->gamma, rgb8, gamma_rgb, linear_rgb);
+        launch(sh, vis ? vis->moments : nullptr, n, aov, rgb8, gamma_rgb, linear_rgb);
         HIPCHK(hipStreamSynchronize(stream));
         HIPCHK(hipGetLastError());
         return FW_OK;
     }
-    const size_t sh_bytes = (size_t)g.counts[0] * g.counts[1] * g.counts[2] * 108;
+    const size_t n_probes = (size_t)g.counts[0] * g.counts[1] * g.counts[2];
+    const size_t sh_bytes = n_probes * 108, mom_bytes = vis ? n_probes * vis->pd->resolution * vis->pd->resolution * 8 : 0;
     const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 75));
     size_t off = 0;
     auto put = [&](size_t b) { const size_t at = off; off += align256(b); return at; };
-    const size_t o_sh = put(sh_bytes), o_aov = put((size_t)per * 48);
+    const size_t o_sh = put(sh_bytes), o_mom = put(mom_bytes), o_aov = put((size_t)per * 48);
     const size_t o_lin = linear_rgb ? put((size_t)per * 12) : 0, o_gam = gamma_rgb ? put((size_t)per * 12) : 0, o_8 = rgb8 ? put((size_t)per * 3) : 0;
     CallScratch scratch(dev);
     if (int rc = scratch.alloc(off)) return rc;
     uint8_t *base = (uint8_t *)scratch.p;
     HIPCHK(hipMemcpyAsync(base + o_sh, sh, sh_bytes, hipMemcpyHostToDevice, stream));
+    if (vis) HIPCHK(hipMemcpyAsync(base + o_mom, vis->moments, mom_bytes, hipMemcpyHostToDevice, stream));
     for (uint32_t done = 0; done < n; done += per) {
         const uint32_t k = std::min(per, n - done);
         HIPCHK(hipMemcpyAsync(base + o_aov, aov + (size_t)done * 12, (size_t)k * 48, hipMemcpyHostToDevice, stream));
-        fw::launch_probe_shade(stream, g, (const float *)(base + o_sh), k, (const float *)(base + o_aov), p->gamma,
-                               rgb8 ? base + o_8 : nullptr, gamma_rgb ? (float *)(base + o_gam) : nullptr, linear_rgb ? (float *)(base + o_lin) : nullptr);
+        launch((const float *)(base + o_sh), (const float *)(base + o_mom), k, (const float *)(base + o_aov),
+               rgb8 ? base + o_8 : nullptr, gamma_rgb ? (float *)(base + o_gam) : nullptr, linear_rgb ? (float *)(base + o_lin) : nullptr);
         if (linear_rgb) HIPCHK(hipMemcpyAsync(linear_rgb + (size_t)done * 3, base + o_lin, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
         if (gamma_rgb) HIPCHK(hipMemcpyAsync(gamma_rgb + (size_t)done * 3, base + o_gam, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
         if (rgb8) HIPCHK(hipMemcpyAsync(rgb8 + (size_t)done * 3, base + o_8, (size_t)k * 3, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
     }
     HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_probe_depth_reduce: fw_probe_project's shape — with host arrays one device allocation per call holds the inputs and the sums,
+// released on every way out; with device arrays the kernel works on the caller's memory and nothing is allocated
+int probe_depth_reduce_impl(int device, const fw_probe_depth *pd, uint32_t n_probes, uint32_t directions, const float *rays, const fw_hit *hits,
+                            float *sums, int on_device, void *stream_) {
+    if (!pd || !rays || !hits || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = probe_depth_check(pd)) return rc;
+    if (n_probes == 0) return fail(FW_ERR_BAD_ARG, "n_probes must be > 0");
+    if (directions == 0 || directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (on_device && ((((uintptr_t)sums | (uintptr_t)hits) & 15u) || ((uintptr_t)rays & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums and hits must be 16-byte aligned, device rays 4-byte aligned");
+    const uint32_t R = pd->resolution;
+    if ((uint64_t)n_probes * directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
+    if ((uint64_t)n_probes * R * R >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n = (size_t)n_probes * directions, sum_bytes = (size_t)n_probes * R * R * 16;
+    CallScratch scratch(device);
+    const float *d_rays = rays; const fw_hit *d_hits = hits; float *d_sums = sums;
+    if (!on_device) {
+        const size_t o_hits = align256(n * 24), o_sums = o_hits + align256(n * sizeof(fw_hit));
+        if (int rc = scratch.alloc(o_sums + sum_bytes)) return rc;
+        uint8_t *base = (uint8_t *)scratch.p;
+        HIPCHK(hipMemcpyAsync(base, rays, n * 24, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_hits, hits, n * sizeof(fw_hit), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
+        d_rays = (const float *)base; d_hits = (const fw_hit *)(base + o_hits); d_sums = (float *)(base + o_sums);
+    }
+    fw::launch_probe_depth(stream, n_probes, directions, R, pd->sharpness_log2, pd->max_distance, d_rays, d_hits, d_sums);
+    if (!on_device) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_bake_probe_depth: its own are the argument checks, the scratch (positions, a chunk's rays and hits, the running sums unless the
+// caller's device memory holds them), k_probe_rays and k_probe_depth around trace_impl's trace of each chunk, and the moments, divided on
+// the host.  The scratch is released on every way out; on an error the stream is drained.
+int bake_probe_depth_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe_depth *pd, const fw_trace_params *tp, uint32_t first_round,
+                          uint32_t rounds, float *sums, float *moments, fw_stats *stats) {
+    if (!sc || !s || !pd || !tp) return fail(FW_ERR_BAD_ARG, "null argument");
+    bool too_large = false;
+    if (int rc = probe_set_check(s, too_large)) return rc;
+    if (int rc = probe_depth_check(pd)) return rc;
+    if (rounds == 0) return fail(FW_ERR_BAD_ARG, "rounds must be > 0");
+    if ((uint64_t)first_round + rounds > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_round + rounds overflows");
+    if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
+    if (tp->on_device && (((uintptr_t)sums & 15u) || ((uintptr_t)moments & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums must be 16-byte aligned, device moments 4-byte aligned");
+    const uint32_t N = s->n_probes, D = s->directions, R = pd->resolution;
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
+    if ((uint64_t)N * R * R >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
+    if (int rc = need_device()) return rc;
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)tp->stream;
+    const uint32_t chunk = std::min<uint32_t>(N, s->chunk_probes ? s->chunk_probes : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 72)));
+    const size_t n_tex = (size_t)N * R * R, sum_bytes = n_tex * 16;
+    const bool own_sums = !tp->on_device || !sums;        // the running sums live in the scratch: a host caller's, or nobody's
+    const size_t o_rays = align256((size_t)N * 12), o_hits = o_rays + align256((size_t)chunk * D * 24),
+                 o_sums = o_hits + align256((size_t)chunk * D * sizeof(fw_hit));
+    CallScratch scratch(dev);
+    if (int rc = scratch.alloc(o_sums + (own_sums ? sum_bytes : 0))) return rc;
+    uint8_t *base = (uint8_t *)scratch.p;
+    const float *d_pos = (const float *)base;
+    float *d_rays = (float *)(base + o_rays), *d_sums = own_sums ? (float *)(base + o_sums) : sums;
+    fw_hit *d_hits = (fw_hit *)(base + o_hits);
+    HIPCHK(hipMemcpyAsync(base, s->positions, (size_t)N * 12, hipMemcpyHostToDevice, stream));
+    if (own_sums) {
+        if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
+        else HIPCHK(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
+    }
+    const int n_cus = device_cus(dev);
+    fw_stats total{};
+    CallEvents<4> ev;                                     // around the two kernels' launches
+    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
+    for (uint32_t r = first_round; r - first_round < rounds; r++) {      // (first_round + rounds may be 2^32 - 1: r itself never gets there)
+        fw_trace_params q = *tp;
+        q.on_device = 1; q.seed = tp->seed + r;
+        for (uint32_t p0 = 0; p0 < N; p0 += chunk) {
+            const uint32_t k = std::min(chunk, N - p0);
+            q.key_base = p0 * D;
+            if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
+            fw::launch_probe_rays(stream, n_cus, probes_device(s, r, p0, d_pos + (size_t)p0 * 3), k, d_rays);
+            if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
+            fw_stats ts{};
+            if (int rc = trace_impl(sc, &q, d_rays, k * D, d_hits, stats ? &ts : nullptr)) { (void)hipStreamSynchronize(stream); return rc; }
+            if (stats) HIPCHK(hipEventRecord(ev.e[2], stream));
+            fw::launch_probe_depth(stream, k, D, R, pd->sharpness_log2, pd->max_distance, d_rays, d_hits, d_sums + (size_t)p0 * R * R * 4);
+            if (!stats) continue;
+            HIPCHK(hipEventRecord(ev.e[3], stream));
+            HIPCHK(hipEventSynchronize(ev.e[3]));
+            float gen_ms = 0.f, red_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
+            HIPCHK(hipEventElapsedTime(&red_ms, ev.e[2], ev.e[3]));
+            stats_add(total, ts);
+            total.ms_render += gen_ms + red_ms;
+            if (tp->flags & FW_FLAG_TIME_KERNELS) { total.ms_raygen += gen_ms; total.ms_accumulate += red_ms; }
+        }
+    }
+    // the outputs: sums where the caller keeps them, and the moments, divided on the host in double and rounded once
+    std::vector<float> host;
+    const float *h_sums = sums;
+    if (!tp->on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+    else if (moments) { host.resize(n_tex * 4); h_sums = host.data(); HIPCHK(hipMemcpyAsync(host.data(), d_sums, sum_bytes, hipMemcpyDeviceToHost, stream)); }
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    if (moments) {
+        std::vector<float> tmp;
+        float *out = moments;
+        if (tp->on_device) { tmp.resize(n_tex * 2); out = tmp.data(); }
+        const float far1 = pd->max_distance, far2 = (float)((double)pd->max_distance * (double)pd->max_distance);
+        for (size_t i = 0; i < n_tex; i++) {
+            const float *t = h_sums + i * 4;
+            const bool none = t[2] == 0.f;
+            out[2 * i] = none ? far1 : (float)((double)t[0] / (double)t[2]);
+            out[2 * i + 1] = none ? far2 : (float)((double)t[1] / (double)t[2]);
+        }
+        if (tp->on_device) {
+            HIPCHK(hipMemcpyAsync(moments, tmp.data(), n_tex * 8, hipMemcpyHostToDevice, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+    }
+    if (stats) {
+        *stats = total;
+        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
     return FW_OK;
 }
 
@@ -4897,6 +5067,41 @@ int fw_probe_shade(const fw_probe_grid *grid, const float *sh, const fw_probe_sh
     try { return probe_shade_impl(grid, sh, p, aov, linear_rgb, gamma_rgb, rgb8); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade"); }
+}
+
+int fw_probe_depth_reduce(int device, const fw_probe_depth *pd, uint32_t n_probes, uint32_t directions, const float *rays, const fw_hit *hits,
+                          float *sums, int on_device, void *stream) {
+    try { return probe_depth_reduce_impl(device, pd, n_probes, directions, rays, hits, sums, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_depth_reduce"); }
+}
+
+int fw_bake_probe_depth(fw_scene *scene, const fw_probe_set *set, const fw_probe_depth *pd, const fw_trace_params *tp, uint32_t first_round,
+                        uint32_t rounds, float *sums, float *moments, fw_stats *stats) {
+    try { return bake_probe_depth_impl(scene, set, pd, tp, first_round, rounds, sums, moments, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_probe_depth"); }
+}
+
+int fw_probe_irradiance_vis(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias, int device,
+                            uint32_t n, const float *positions, const float *normals, uint32_t stride_floats, float *irradiance, int on_device,
+                            void *stream) {
+    try {
+        const ProbeVis vis{pd, moments, normal_bias};
+        return probe_irradiance_impl(grid, sh, device, n, positions, normals, stride_floats, irradiance, on_device, stream, &vis);
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_irradiance_vis"); }
+}
+
+int fw_probe_shade_vis(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias,
+                       const fw_probe_shade_params *p, const float *aov, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
+    try {
+        const ProbeVis vis{pd, moments, normal_bias};
+        return probe_shade_impl(grid, sh, p, aov, linear_rgb, gamma_rgb, rgb8, &vis);
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_vis"); }
 }
 
 int fw_lightmap_texels(const fw_lightmap *lm, int device, float *records, uint32_t *owner, uint32_t *n_covered, int on_device, void *stream) {

@@ -867,6 +867,89 @@ typedef struct fw_probe_shade_params {
 int fw_probe_shade(const fw_probe_grid *grid, const float *sh, const fw_probe_shade_params *p, const float *aov, float *linear_rgb,
                    float *gamma_rgb, uint8_t *rgb8);
 
+/* ---- probe visibility: depth moments per probe, and lookups weighted by them (additive at ABI 8) ---------------------
+   The lookup above blends a probe in a lit room with a probe in the dark room next door.  Each probe therefore also gets an R x R
+   octahedral map of the first two moments of the distance to the nearest surface, baked from fw_trace_rays' hit distances along the
+   probe's own rays, and the lookup multiplies a corner's weight by a Chebyshev bound of the chance that the corner's probe sees the
+   point.  Everything is float64 from the float32 inputs, every operation rounded as written; max and min are fmax and fmin (a NaN
+   operand loses).  api.probe_depth_dirs, api.probe_depth_reduce, api.probe_depth_moments and api.probe_lookup_vis are the numpy
+   statements.
+     Texel centres.  Texel (a, b) is column a, row b, id = b R + a.  ex = ((a + 0.5) * 2) / R - 1, ey likewise from b;
+         z = (1 - |ex|) - |ey|;  if z < 0: x = (1 - |ey|) * sgn(ex), y = (1 - |ex|) * sgn(ey) with sgn(0) = +1, otherwise x = ex, y = ey;
+         T = (x, y, z) / sqrt((x x + y y) + z z), per component.
+     Reduction of one round (fw_probe_depth_reduce, k_probe_depth).  For probe p and ray j the float32 direction d is used as stored
+         and h = hits[p D + j]:  dist_j = r_max if h.object == FW_NO_HIT, else min((double)h.t * sqrt((dx dx + dy dy) + dz dz), r_max).
+         Per texel c = max(0, (Tx dx + Ty dy) + Tz dz), squared sharpness_log2 times to give w.  Three float64 accumulators start from 0
+         and are updated sequentially in ascending j:  A = A + w*dist;  B = B + (w*dist)*dist;  W = W + w.  Each is rounded to float32
+         once and added with one float32 addition to sums[p][b][a] = (A, B, W, unused): n_probes x R x R x 4 floats, .w never written.
+         One lane owns a texel: no atomics, two runs are bit-equal, and the result does not depend on how the kernel splits the work.
+     Moments: n_probes x R x R x 2 floats.  mu = float((double)sums.x / sums.z), mu2 = float((double)sums.y / sums.z); a texel with
+         sums.z == 0 gets (r_max, float((double)r_max * r_max)).
+     Fetch of (mu, mu2) along a unit direction (x, y, z) from a probe.  s1 = (|x| + |y|) + |z|, ox = x / s1, oy = y / s1; for z < 0 the
+         fold of the texel centres: (ox, oy) <- ((1 - |oy|) * sgn(ox), (1 - |ox|) * sgn(oy)).  su = ((ox + 1) * 0.5) * R - 0.5 clamped to
+         [0, R - 1] (max, then min), i = min(floor(su), R - 2), fu = su - i; sv, j, fv likewise from oy.  Bilinear over the four texel
+         centres, m10 = texel (i + 1, j):  ((m00 (1 - fu) + m10 fu) (1 - fv)) + ((m01 (1 - fu) + m11 fu) fv).  Edges are clamped, not
+         wrapped across the octahedral seams: a stated simplification.
+     Visibility weight of a corner probe P (the lookup's P) for a point p with unit normal nh; normal_bias >= 0 in world units.
+         q = p + normal_bias * nh per component, r' = q - P, dist = sqrt((r'x r'x + r'y r'y) + r'z r'z).  dist == 0: v = 1.  Otherwise
+         (mu, mu2) is fetched along r' / dist;  dist <= mu: v = 1;  otherwise var = |mu mu - mu2|, t = dist - mu, c = var / (var + t t),
+         v = (c c) c.  g = fac * v with fac the lookup's wrap factor (h h + 0.2, or 1.2 at r = 0), or 1 without FW_PROBE_WRAP;
+         g = max(1e-6, g);  if g < 0.2: g = (g * (g * g)) * 25.  The corner's weight is w = ((wx wy) wz) * g, and the weights are always
+         divided by their sum, added in the order dz, dy, dx with dx fastest (positive: every g is).
+   Everything else is fw_probe_irradiance's statement unchanged: the cell, the flat axes, the basis, the order of E's sums, zeros for a
+   non-finite point, one rounding of E.  Seam-correct borders, back-face detection, probe relocation and a view bias are out of scope. */
+typedef struct fw_probe_depth {
+    uint32_t resolution;      /* R in {4, 8, 16, 32}: each probe has an R x R octahedral map */
+    uint32_t sharpness_log2;  /* k in 0..8: a ray's weight in a texel is max(0, T.d)^(2^k), by k squarings — no pow */
+    float    max_distance;    /* r_max > 0, finite: distances are clamped to it; a miss counts as r_max */
+} fw_probe_depth;
+
+/* fw_probe_depth_reduce: adds one round's reduction to the running sums.  rays: n_probes x D x 6 floats; hits: n_probes x D records, as
+   fw_trace_rays wrote them for those rays; sums: n_probes x R x R x 4 floats.  Host arrays — staged through one device allocation of the
+   call's own, freed on every path — or with on_device device arrays on `device` (the kernel then works on the caller's memory), launched
+   on `stream` and complete on return.  Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL pd, rays, hits or sums,
+   a resolution not in {4, 8, 16, 32}, sharpness_log2 > 8, max_distance not finite or <= 0, n_probes == 0, directions outside 1..2^20,
+   with on_device sums or hits not 16-byte aligned or rays not 4-byte aligned; FW_ERR_UNSUPPORTED for n_probes x D >= 2^31 or
+   n_probes x R^2 >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index out of range. */
+int fw_probe_depth_reduce(int device, const fw_probe_depth *pd, uint32_t n_probes, uint32_t directions, const float *rays, const fw_hit *hits,
+                          float *sums, int on_device, void *stream);
+
+/* fw_bake_probe_depth: the rounds [first_round, first_round + rounds) of a probe set's depth maps against a resident scene.  Of tp,
+   use_bvh, flags, seed, rays_per_batch, on_device (for sums and moments) and stream are read; key_base is ignored.  For each round r and
+   each chunk of probes [p0, p1) (set->chunk_probes at a time; 0 = as many as fit 256 MiB at 72 B per ray, at least 1): k_probe_rays
+   fills device scratch that the call allocates and frees on every path; the rays are traced exactly as fw_trace_rays would with
+   on_device = 1, key_base = p0 D and seed = tp->seed + r (so a ConstantMedium draws reproducibly); k_probe_depth adds the chunk into sums.
+     sums   : n_probes x R x R x 4 floats (with on_device 16-byte aligned), the running sums of the rounds [0, first_round) — zeros when
+              first_round is 0 — to which this call's rounds are added in order; NULL only when first_round == 0.
+     moments: n_probes x R x R x 2 floats from the sums after this call, divided on the host; may be NULL.
+   Contracts.  Composition: for every chunk_probes, sums equals bit for bit what fw_probe_rays, fw_trace_rays (seed + r, key_base 0) and
+   fw_probe_depth_reduce give when chained by hand over the whole set.  Progressive: k calls of n rounds leave the sums and moments of one
+   call of k n rounds, bit for bit.
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, set, pd or tp, what
+   fw_probe_rays rejects in the set, what fw_probe_depth_reduce rejects in pd, rounds == 0, first_round + rounds >= 2^32, a NULL sums
+   with first_round > 0, with on_device sums not 16-byte aligned or moments not 4-byte aligned; FW_ERR_UNSUPPORTED for n_probes x D >= 2^31
+   or n_probes x R^2 >= 2^31; then FW_ERR_NO_DEVICE.
+   stats (may be NULL): fw_trace_rays' fields summed over rounds and chunks; ms_render includes the two kernels' launches (under
+   FW_FLAG_TIME_KERNELS ms_raygen and ms_accumulate as well); ms_wall covers the whole call.  Synchronisation and what a trace leaves of
+   renders are fw_trace_rays'. */
+int fw_bake_probe_depth(fw_scene *scene, const fw_probe_set *set, const fw_probe_depth *pd, const fw_trace_params *tp, uint32_t first_round,
+                        uint32_t rounds, float *sums, float *moments, fw_stats *stats);
+
+/* fw_probe_irradiance_vis, fw_probe_shade_vis: fw_probe_irradiance and fw_probe_shade with the visibility weight above
+   (k_probe_irradiance_vis, k_probe_shade_vis: one lane per point, no atomics).  moments: n x R x R x 2 floats for the grid's n probes,
+   host memory or with on_device device memory like sh; a host call stages it after sh.  Every moments index is formed from clamped
+   cell and texel indices: no load leaves the arrays wherever the point lies.  Errors, in this order and before HIP is called:
+   FW_ERR_BAD_ARG for a NULL pointer (the counterpart's, pd, moments; fw_probe_shade_vis then: all three outputs NULL), a resolution not
+   in {4, 8, 16, 32}, sharpness_log2 > 8, max_distance not finite or <= 0, normal_bias negative or not finite, then everything the
+   counterpart rejects, in its order, with on_device moments not 4-byte aligned among the alignment checks; FW_ERR_UNSUPPORTED for
+   nx ny nz >= 2^31, then for n x R^2 >= 2^31, then (fw_probe_shade_vis) for W x H >= 2^32; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a
+   device index past the last one. */
+int fw_probe_irradiance_vis(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias, int device,
+                            uint32_t n, const float *positions, const float *normals, uint32_t stride_floats, float *irradiance, int on_device,
+                            void *stream);
+int fw_probe_shade_vis(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias,
+                       const fw_probe_shade_params *p, const float *aov, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8);
+
 /* ---- lightmaps baked on the device: irradiance over a mesh's UV texels (additive at ABI 8) ---------------------------
    A fw_lightmap is one mesh placement and a texture size.  It reads nothing from a scene: the scene is only what the rays are traced
    against.  All its pointers are host memory.
