@@ -41,7 +41,12 @@ not used; refuses what --bake-probes refuses, --bake-probes and --bake-lightmap)
 weights cos^(2^K), K in 0..8, default 6, distances clamped to M, default the grid's diagonal, over the same --probe-rounds rounds,
 fw_bake_probe_depth; the .npz also gets depth, depth_res, depth_sharpness and depth_max).  --probe-lit then weights every
 probe by its visibility from the surface (fw_probe_shade_vis) when the file holds them; --probe-no-visibility ignores them (the image
-of a file without them), --probe-normal-bias B moves the looked-up point B >= 0 world units along its normal first (default 0)."""
+of a file without them), --probe-normal-bias B moves the looked-up point B >= 0 world units along its normal first (default 0).
+--ao RADIUS [--ao-dirs D] [--ao-rounds R] [--ao-falloff] (the fixed view's ambient occlusion as a grey PNG: one first-hit pass of
+--aov-samples samples, then R rounds, default 1, of D cosine-weighted rays per pixel, default 64, traced from each pixel's surface point;
+a hit nearer than RADIUS > 0 occludes, fully or with --ao-falloff by 1 - dist / RADIUS, fw_bake_ao, DESIGN.md §9t; -s is not used;
+refuses what --probe-lit refuses, and --probe-lit).  --bake-lightmap ... --lightmap-ao RADIUS (also bakes the occlusion over the same
+texels with the same --lightmap-dirs, --lightmap-rounds and --lightmap-dilate; --ao-falloff applies; the .npz also gets ao and bent)."""
 import argparse
 import sys
 import time
@@ -108,7 +113,38 @@ def main(argv=None):
     ap.add_argument("--probe-no-visibility", action="store_true", help="with --probe-lit: ignore the depth moments in the file")
     ap.add_argument("--probe-normal-bias", type=float, default=None, metavar="B",
                     help="with --probe-lit and depth moments: look visibility up B >= 0 world units along the normal (default 0)")
+    ap.add_argument("--ao", type=float, default=None, metavar="RADIUS",
+                    help="render the view's ambient occlusion as a grey PNG: a hit nearer than RADIUS occludes; no paths are traced")
+    ap.add_argument("--ao-dirs", type=int, default=None, metavar="D", help="with --ao: rays per pixel and round (default 64)")
+    ap.add_argument("--ao-rounds", type=int, default=None, metavar="R", help="with --ao: rounds of D rays per pixel (default 1)")
+    ap.add_argument("--ao-falloff", action="store_true", help="with --ao or --lightmap-ao: a hit occludes by 1 - dist / RADIUS, not fully")
+    ap.add_argument("--lightmap-ao", type=float, default=None, metavar="RADIUS",
+                    help="with --bake-lightmap: also bake ambient occlusion and bent normals over the texels into the .npz")
     opt = ap.parse_args(argv)
+    if opt.ao is not None:
+        if (opt.probe_lit is not None or opt.bake_probes is not None or opt.bake_lightmap is not None or opt.camera != "pinhole"
+                or opt.denoise is not None or opt.orbit or opt.adaptive is not None or opt.progressive > 0 or opt.checkpoint or opt.temporal is not None):
+            ap.error("--ao cannot be combined with --probe-lit, --bake-probes, --bake-lightmap, --camera, --denoise, --orbit, --adaptive, "
+                     "--progressive, --checkpoint or --temporal")
+        if not 0.0 < opt.ao < float("inf"):
+            ap.error("--ao RADIUS needs a finite RADIUS > 0")
+        if opt.ao_dirs is not None and not 1 <= opt.ao_dirs <= 1 << 20:
+            ap.error("--ao-dirs D needs 1 <= D <= 2^20")
+        if opt.ao_rounds is not None and opt.ao_rounds < 1:
+            ap.error("--ao-rounds R needs R >= 1")
+        if opt.aov_samples < 1:
+            ap.error("--aov-samples needs S >= 1")
+        if not opt.output:
+            ap.error("--ao needs -o FILE.png")
+    elif opt.ao_dirs is not None or opt.ao_rounds is not None:
+        ap.error("--ao-dirs and --ao-rounds need --ao")
+    elif opt.ao_falloff and opt.lightmap_ao is None:
+        ap.error("--ao-falloff needs --ao or --lightmap-ao")
+    if opt.lightmap_ao is not None:
+        if opt.bake_lightmap is None:
+            ap.error("--lightmap-ao needs --bake-lightmap")
+        if not 0.0 < opt.lightmap_ao < float("inf"):
+            ap.error("--lightmap-ao RADIUS needs a finite RADIUS > 0")
     if opt.probe_lit is not None:
         if (opt.bake_probes is not None or opt.bake_lightmap is not None or opt.camera != "pinhole" or opt.denoise is not None or opt.orbit
                 or opt.adaptive is not None or opt.progressive > 0 or opt.checkpoint or opt.temporal is not None):
@@ -305,16 +341,33 @@ def main(argv=None):
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)
         return 0
+    if opt.ao is not None:
+        import numpy as np
+        from .api import AmbientOcclusion
+        ao = AmbientOcclusion(opt.ao, 64 if opt.ao_dirs is None else opt.ao_dirs, int(opt.ao_falloff)).seed(opt.seed)
+        occ, _bent, _sums = renderer.render_ao(scene, ao, 1 if opt.ao_rounds is None else opt.ao_rounds, opt.aov_samples, device=opt.device)
+        grey = np.clip(np.floor(occ * np.float32(255.99)), 0, 255).astype(np.uint8)
+        print(f"Finished Rendering in {int(time.time() - start)} s")
+        print(f'Saving image to "{opt.output}"')
+        save_image(np.repeat(grey.reshape(-1, 1), 3, axis=1), opt.output, opt.width, opt.height)
+        return 0
     if lightmap is not None:
         import numpy as np
         rounds = 1 if opt.lightmap_rounds is None else opt.lightmap_rounds
         irradiance, sums = renderer.bake_lightmap(scene, lightmap, rounds, 2 if opt.lightmap_dilate is None else opt.lightmap_dilate, device=opt.device)
         owner = _lib.lightmap_texels(lightmap, opt.device)[1].reshape(lightmap.height, lightmap.width)
+        extra = {}
+        if opt.lightmap_ao is not None:
+            from .api import AmbientOcclusion
+            ao = AmbientOcclusion(opt.lightmap_ao, lightmap.directions, int(opt.ao_falloff)).seed(opt.seed)
+            occ, bent, _ao_sums = renderer.bake_lightmap_ao(scene, lightmap, ao, rounds, 2 if opt.lightmap_dilate is None else opt.lightmap_dilate,
+                                                            device=opt.device)
+            extra = dict(ao=occ, bent=bent)
         print(f"Finished Baking in {int(time.time() - start)} s")
         print(f'Saving a {lightmap.width} x {lightmap.height} lightmap to "{opt.output}"')
         with open(opt.output, "wb") as f:       # (np.savez would append .npz to a name without it)
             np.savez(f, irradiance=irradiance, sums=sums, owner=owner, rounds=np.int64(rounds), directions=np.int64(lightmap.directions),
-                     samples=np.int64(opt.samples))
+                     samples=np.int64(opt.samples), **extra)
         return 0
     if opt.camera != "pinhole":
         render = camera_model_render(renderer, camera, scene, opt)

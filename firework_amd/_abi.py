@@ -210,5 +210,19 @@ class fw_lightmap(C.Structure):
                 ("directions", u32), ("jitter", i32), ("seed", u64), ("bias", f32), ("flip", i32), ("chunk_texels", u32)]
 
 
+# ambient occlusion (include/firework_hip.h: fw_ao_rays, fw_ao_reduce, fw_bake_ao)
+class fw_ao(C.Structure):
+    _fields_ = [("directions", u32), ("falloff", u32), ("radius", f32), ("bias", f32), ("jitter", u32), ("chunk_points", u32), ("seed", u64)]
+
+
+# the three prototypes (argument types; every one returns int), applied by _lib.load
+AO_PROTOTYPES = {
+    "fw_ao_rays": [C.POINTER(fw_ao), C.c_int, u32, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_ao_reduce": [C.c_int, C.POINTER(fw_ao), u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_bake_ao": [C.c_void_p, C.POINTER(fw_ao), C.POINTER(fw_trace_params), u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p,
+                   C.c_void_p, C.POINTER(fw_stats)],
+}
+
+
 def vec3(v):
     return fw_vec3(float(v[0]), float(v[1]), float(v[2]))

@@ -130,7 +130,7 @@ def load(preload=False, device=None):
     lib.fw_probe_shade.restype = C.c_int
     lib.fw_probe_shade.argtypes = [C.POINTER(A.fw_probe_grid), C.c_void_p, C.POINTER(A.fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
-    for name, argtypes in A.PROBE_DEPTH_PROTOTYPES.items():
+    for name, argtypes in list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
@@ -771,6 +771,120 @@ def lightmap_dilate(image, passes, device=0, stream=None):
     return image
 
 
+class _AoPoints:
+    """The surface points of an AO call as the C ABI takes them, read in place.  positions and normals: (M, 3) float32 each, contiguous
+    or two column ranges of one contiguous (M, S) array such as fw_render_aovs' records (aov[:, 8:11], aov[:, 4:7]) or
+    fw_lightmap_texels' (rec[:, 0:3], rec[:, 4:7]); numpy arrays, or torch tensors on cuda:`device`.  ids: n distinct ids below M (uint32
+    numpy / int32 torch) or None: every point in order.  Arrays indexed by id (sums, out) have M records."""
+
+    def __init__(self, positions, normals, ids, device):
+        self.torch = type(positions).__module__.startswith("torch")
+        m = self.m = int(positions.shape[0])
+        if m < 1 or tuple(positions.shape) != (m, 3) or tuple(normals.shape) != (m, 3):
+            raise ValueError("positions and normals must have the same shape (M, 3), M >= 1")
+        if self.torch:
+            import torch
+            self.stride = int(positions.stride(0)) if m > 1 else max(3, int(positions.stride(0)))
+            for t, name in ((positions, "positions"), (normals, "normals")):
+                if (t.dtype != torch.float32 or t.stride(1) != 1 or t.device.type != "cuda" or (t.device.index or 0) != device
+                        or (m > 1 and int(t.stride(0)) != self.stride) or self.stride < 3):
+                    raise ValueError(f"{name} must be an (M, 3) float32 tensor on cuda:{device} with unit column stride and the same row stride >= 3 as the other")
+            self.dev = positions.device
+            if ids is not None:
+                _check_device_tensor(ids, (int(ids.shape[0]),), torch.int32, device, "ids")
+                if ids.numel() and not (0 <= int(ids.min()) and int(ids.max()) < m):
+                    raise ValueError(f"every id must be in 0..{m - 1}")
+            self.keep = (positions, normals, ids)
+            self.pos, self.nrm, self.ids = positions.data_ptr(), normals.data_ptr(), (ids.data_ptr() if ids is not None else None)
+        else:
+            p, nr = np.asarray(positions, np.float32), np.asarray(normals, np.float32)
+            if not (p.strides[1] == 4 and p.strides[0] % 4 == 0 and p.strides[0] >= 12 and nr.strides == p.strides):
+                p, nr = np.ascontiguousarray(p), np.ascontiguousarray(nr)
+            self.stride = p.strides[0] // 4
+            if ids is not None:
+                ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+                if ids.size and int(ids.max()) >= m:
+                    raise ValueError(f"every id must be in 0..{m - 1}")
+            self.keep = (p, nr, ids)
+            self.pos, self.nrm, self.ids = p.ctypes.data, nr.ctypes.data, (ids.ctypes.data if ids is not None else None)
+        self.n = int(ids.shape[0]) if ids is not None else m
+
+    def records(self, arr, name):
+        """checks an array indexed by id: (M, 4) or (H, W, 4) float32 with H W = M, where the points lie"""
+        shape = tuple(arr.shape)
+        if shape[-1] != 4 or int(np.prod(shape[:-1])) != self.m:
+            raise ValueError(f"{name} must have shape ({self.m}, 4) or (H, W, 4) with H W = {self.m}")
+        if self.torch:
+            import torch
+            _check_device_tensor(arr, shape, torch.float32, self.dev.index or 0, name)
+            return arr.data_ptr()
+        _host_f32(arr, None, name)
+        return arr.ctypes.data
+
+
+def ao_rays(ao, positions, normals, ids=None, round=0, device=0, out=None, stream=None):
+    """fw_ao_rays: the rays of round `round` of an api.AmbientOcclusion around surface points (see _AoPoints), generated on the device:
+    (n * D, 6) float32 origin + direction, entry q * D + j = direction j of point ids[q] (ids None: q).  numpy points: returns a numpy
+    array.  Points on cuda:`device`: generated on `stream` (default: the current torch stream) where they lie; returns a device tensor
+    (out: a contiguous float32 tensor of that shape to fill instead)."""
+    lib = load()
+    a = ao.to_abi()
+    pts = _AoPoints(positions, normals, ids, device)
+    shape = (pts.n * int(a.directions), 6)
+    if pts.torch:
+        import torch
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=pts.dev)
+        _check_device_tensor(out, shape, torch.float32, device, "out")
+        _check(lib, lib.fw_ao_rays(C.byref(a), int(device), int(round), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, out.data_ptr(), 1,
+                                   _stream_arg(stream, pts.dev)))
+        return out
+    rays = np.empty(shape, np.float32)
+    _check(lib, lib.fw_ao_rays(C.byref(a), int(device), int(round), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, rays.ctypes.data, 0, None))
+    return rays
+
+
+def ao_reduce(ao, rays, hits, sums, ids=None, device=0, stream=None):
+    """fw_ao_reduce: adds one round's reduction (Bx, By, Bz, O, each rounded to float32 once) of an api.AmbientOcclusion to
+    sums[ids[q]] (ids None: sums[q]); sums (M, 4) or (H, W, 4) float32, updated in place.  rays (n * D, 6) float32 and hits as
+    DeviceScene.trace returns them for those rays: a HIT_DTYPE array for numpy rays, or an (n * D, 12) float32 device tensor for rays on
+    cuda:`device`, reduced on `stream` (default: the current torch stream) where they lie; ids n distinct ids (uint32 numpy / int32
+    torch).  Returns sums."""
+    lib = load()
+    a = ao.to_abi()
+    d = int(a.directions)
+    total = int(rays.shape[0])
+    if d < 1 or total % d or tuple(rays.shape) != (total, 6) or int(hits.shape[0]) != total:
+        raise ValueError(f"rays must have shape (n * {d}, 6) and hits n * {d} records")
+    n = total // d
+    m = int(np.prod(tuple(sums.shape)[:-1]))
+    if sums.shape[-1] != 4 or (ids is None and m < n) or (ids is not None and tuple(ids.shape) != (n,)):
+        raise ValueError(f"sums must have shape (M, 4) or (H, W, 4) with M >= {n}, ids shape ({n},)")
+    if type(rays).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
+        _check_device_tensor(hits, (total, 12), torch.float32, device, "hits")
+        _check_device_tensor(sums, tuple(sums.shape), torch.float32, device, "sums")
+        if ids is not None:
+            _check_device_tensor(ids, (n,), torch.int32, device, "ids")
+            if not (0 <= int(ids.min()) and int(ids.max()) < m):
+                raise ValueError(f"every id must be in 0..{m - 1}")
+        _check(lib, lib.fw_ao_reduce(int(device), C.byref(a), n, ids.data_ptr() if ids is not None else None, rays.data_ptr(), hits.data_ptr(),
+                                     sums.data_ptr(), 1, _stream_arg(stream, rays.device)))
+        return sums
+    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
+    h = np.ascontiguousarray(hits)
+    if h.dtype != HIT_DTYPE:
+        raise ValueError("host hits must be an array of HIT_DTYPE")
+    _host_f32(sums, None, "sums")
+    i = None if ids is None else np.ascontiguousarray(np.asarray(ids, dtype=np.uint32))
+    if i is not None and i.size and int(i.max()) >= m:
+        raise ValueError(f"every id must be in 0..{m - 1}")
+    _check(lib, lib.fw_ao_reduce(int(device), C.byref(a), n, i.ctypes.data if i is not None else None, r.ctypes.data, h.ctypes.data,
+                                 sums.ctypes.data, 0, None))
+    return sums
+
+
 class DeviceScene:
     """An uploaded scene (`fw_scene*`): SoA scene arrays + TLAS/BLAS resident in HBM."""
 
@@ -1100,6 +1214,36 @@ class DeviceScene:
             ptrs = sums.ctypes.data, out.ctypes.data
         _check(self._lib, self._lib.fw_bake_probe_depth(self.handle, C.byref(s), C.byref(pd), C.byref(p), int(first_round), int(rounds), *ptrs,
                                                         C.byref(st)))
+        return out, sums, st.as_dict()
+
+    def bake_ao(self, ao, positions, normals, ids=None, rounds=1, first_round=0, sums=None, out=None, seed=0, use_bvh=True, stream=None,
+                rays_per_batch=0, flags=0, chunk=None):
+        """fw_bake_ao: the rounds [first_round, first_round + rounds) of an api.AmbientOcclusion around surface points (see _AoPoints:
+        numpy arrays, or tensors on this scene's device, read in place), `chunk` points at a time (None: the description's own
+        setting; 0: automatic).  sums: (M, 4) or (H, W, 4) float32 running sums (Bx, By, Bz, O) of the rounds before first_round,
+        updated in place (None: zeros, only with first_round 0); out: an array of the same kind to receive (bent.xyz, ao) (None:
+        zeros); both are indexed by id, entries outside ids are not touched.  Returns (out, sums, stats): host arrays for numpy
+        points, device tensors — baked on `stream` (default: the current torch stream) — for device points."""
+        a = ao.to_abi()
+        if chunk is not None:
+            a.chunk_points = int(chunk)
+        pts = _AoPoints(positions, normals, ids, self.device)
+        p = A.fw_trace_params()
+        p.use_bvh, p.flags, p.seed, p.rays_per_batch = int(bool(use_bvh)), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rays_per_batch)
+        st = A.fw_stats()
+        if sums is None and int(first_round) > 0:
+            raise ValueError("first_round > 0 needs the sums of the rounds before it")
+        if pts.torch:
+            import torch
+            zeros = lambda: torch.zeros((pts.m, 4), dtype=torch.float32, device=pts.dev)      # noqa: E731
+            p.on_device = 1
+            p.stream = _stream_arg(stream, pts.dev)
+        else:
+            zeros = lambda: np.zeros((pts.m, 4), np.float32)      # noqa: E731
+        sums = zeros() if sums is None else sums
+        out = zeros() if out is None else out
+        _check(self._lib, self._lib.fw_bake_ao(self.handle, C.byref(a), C.byref(p), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, int(first_round),
+                                               int(rounds), pts.records(sums, "sums"), pts.records(out, "out"), C.byref(st)))
         return out, sums, st.as_dict()
 
     def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,

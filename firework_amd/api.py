@@ -1798,6 +1798,140 @@ class Lightmap:
         return s, (m.verts, m.indicies, m.normals, m.uvs)
 
 
+# --------------------------------------------------------------------------- ambient occlusion (fw_bake_ao)
+class AmbientOcclusion:
+    """Ambient occlusion and bent normals of surface points (fw_ao): `directions` cosine-weighted hemisphere rays per
+    point and round, a hit closer than `radius` occludes (falloff 0: fully; falloff 1: by 1 - dist / radius), origins moved `bias` along
+    the normal.  radius may be inf with falloff 0: any hit occludes.  .seed(s) / .jitter(on) as builders; chunk_points as fw_ao's."""
+
+    def __init__(self, radius: float, directions: int = 64, falloff: int = 0, bias: float = 1e-3):
+        self.radius, self.directions, self.falloff, self.bias = float(np.float32(radius)), int(directions), int(falloff), float(np.float32(bias))
+        self._seed, self._jitter, self.chunk_points = 0, True, 0
+
+    def seed(self, s):
+        self._seed = int(s)
+        return self
+
+    def jitter(self, on=True):
+        self._jitter = bool(on)
+        return self
+
+    def check(self):
+        """what fw_ao_rays rejects in a description, as a ValueError, in its order"""
+        if not 1 <= self.directions <= 1 << 20:
+            raise ValueError("directions must be in 1..2^20")
+        if self.falloff not in (0, 1):
+            raise ValueError("falloff must be 0 or 1")
+        if not self.radius > 0.0:
+            raise ValueError("radius must be > 0")
+        if np.isinf(self.radius) and self.falloff:
+            raise ValueError("an infinite radius needs falloff 0")
+        if not (np.isfinite(self.bias) and self.bias >= 0.0):
+            raise ValueError("bias must be finite and >= 0")
+        return self
+
+    def to_abi(self) -> A.fw_ao:
+        a = A.fw_ao()
+        a.directions, a.falloff, a.radius, a.bias = self.directions & 0xFFFFFFFF, self.falloff & 0xFFFFFFFF, self.radius, self.bias
+        a.jitter, a.chunk_points, a.seed = int(self._jitter), int(self.chunk_points), self._seed & 0xFFFFFFFFFFFFFFFF
+        return a
+
+
+def ao_usable(positions, normals) -> np.ndarray:
+    """(M,) bool: the points fw_ao_rays generates rays for — every component finite and a normal other than (0, 0, 0)"""
+    p, n = np.asarray(positions, np.float32).reshape(-1, 3), np.asarray(normals, np.float32).reshape(-1, 3)
+    return np.all(np.isfinite(p), axis=1) & np.all(np.isfinite(n), axis=1) & np.any(n != 0, axis=1)
+
+
+def ao_rays(ao: "AmbientOcclusion", positions, normals, ids=None, round: int = 0, device=None):
+    """The numpy statement of fw_ao_rays: (n * D, 6) float32, entry q * D + j = direction j of point id = ids[q] (ids None: q) of
+    positions and normals, (M, 3) float32 each (device: see panorama_rays).  Lightmap.rays' statement with the texel id replaced by id;
+    an unusable point (ao_usable) gets D all-zero rays."""
+    D = ao.directions
+    if D < 1:
+        raise ValueError("directions must be >= 1")
+    P, Nn = np.asarray(positions, np.float32).reshape(-1, 3), np.asarray(normals, np.float32).reshape(-1, 3)
+    ids = np.arange(P.shape[0], dtype=np.uint32) if ids is None else np.asarray(ids, np.uint32).reshape(-1)
+    at = ids.astype(np.int64)
+    p32, n32 = P[at], Nn[at]
+    ok = ao_usable(p32, n32)
+    pos, nrm = p32[:, None, :].astype(np.float64), n32[:, None, :].astype(np.float64)
+    xi = texel_jitter(ao._seed, round, ids) if ao._jitter else np.full((ids.size, 2), 0.5)
+    j = np.arange(D, dtype=np.float64)[None, :]
+    with np.errstate(all="ignore"):
+        u = (j + xi[:, 0:1]) / float(D)
+        r = np.sqrt(u)
+        c = np.sqrt(np.maximum(0.0, 1.0 - u))
+        g = (np.sqrt(5.0) - 1.0) / 2.0
+        t = j * g + xi[:, 1:2]
+        phi = (2.0 * np.pi) * (t - np.floor(t))
+        lx, ly = r * np.cos(phi), r * np.sin(phi)
+        nrm = nrm / np.sqrt((nrm[..., 0:1] * nrm[..., 0:1] + nrm[..., 1:2] * nrm[..., 1:2]) + nrm[..., 2:3] * nrm[..., 2:3])
+        nx, ny, nz = nrm[..., 0], nrm[..., 1], nrm[..., 2]
+        s = np.copysign(1.0, nz)
+        a = -1.0 / (s + nz)
+        b = (nx * ny) * a
+        T = (1.0 + (s * (nx * nx)) * a, s * b, -s * nx)
+        B = (b, s + (ny * ny) * a, -ny)
+        d = np.stack([(lx * T[k] + ly * B[k]) + c * nrm[..., k] for k in range(3)], axis=-1)
+        if ao.bias == 0.0:
+            o = np.repeat(p32, D, axis=0).astype(np.float64)
+        else:
+            o = np.repeat((pos + float(F32(ao.bias)) * nrm)[:, 0], D, axis=0)
+    d = np.where(ok[:, None, None], d, 0.0).reshape(-1, 3)
+    o = np.where(np.repeat(ok, D)[:, None], o, 0.0)
+    return _rays_out(o, d, device)
+
+
+def ao_reduce(ao: "AmbientOcclusion", rays, hits_t, hits_object, terms: bool = False):
+    """The numpy float64 statement of fw_ao_reduce: (n, 4) float64, (1 / D) x the accumulators (Bx, By, Bz, O) of one round before their
+    one rounding to float32, for rays (n * D, 6) float32 (the directions as stored) and the hits' t (float32) and object (uint32,
+    0xFFFFFFFF = miss) columns, summed in the device's order (G partial sums, an xor butterfly).  terms=True: returns (sums, T, dist)
+    with T (n, 4) = (1 / D) sum_j |term_j| (what a rounding-error bound of the sums scales with) and dist (n, D) the distances."""
+    D = int(ao.directions)
+    d = np.asarray(rays, np.float32).astype(np.float64).reshape(-1, D, 6)[..., 3:]
+    t = np.asarray(hits_t, np.float32).astype(np.float64).reshape(-1, D)
+    miss = np.asarray(hits_object).astype(np.uint32).reshape(-1, D) == np.uint32(0xFFFFFFFF)
+    radius = float(np.float32(ao.radius))
+    G = 1
+    while G < min(D, 64):
+        G *= 2
+    with np.errstate(all="ignore"):
+        zero = np.all(d == 0.0, axis=-1)
+        dist = t * np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+        o = np.where(miss | (dist >= radius), 0.0, (1.0 - dist / radius) if ao.falloff else 1.0)
+        w = 1.0 - o
+        term = np.stack([w * d[..., 0], w * d[..., 1], w * d[..., 2], o], axis=-1)          # (n, D, 4)
+        term = np.where(zero[..., None], 0.0, term)
+    rows = -(-D // G)                                                                        # lane l takes j = l, l + G, ... in ascending order
+    padded = np.zeros((d.shape[0], rows * G, 4))
+    padded[:, :D] = term
+    part = np.zeros((d.shape[0], G, 4))
+    for row in padded.reshape(-1, rows, G, 4).transpose(1, 0, 2, 3):
+        part = part + row
+    m = G // 2
+    while m >= 1:
+        part = part + part[:, np.arange(G) ^ m]
+        m //= 2
+    out = (1.0 / D) * part[:, 0]
+    if not terms:
+        return out
+    return out, (1.0 / D) * np.abs(term).sum(axis=1), np.where(zero, np.nan, dist)
+
+
+def ao_resolve(sums, rounds: int) -> np.ndarray:
+    """The statement of k_ao_resolve: (..., 4) float32 (bent.xyz, ao) from the float32 running sums (..., 4) of `rounds` rounds:
+    ao = float32(min(1, max(0, 1 - O / rounds))), bent = B / sqrt((Bx Bx + By By) + Bz Bz) in float64, rounded once; (0, 0, 0) where that
+    length is 0 or not finite."""
+    s = np.asarray(sums, np.float32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        length = np.sqrt((s[..., 0] * s[..., 0] + s[..., 1] * s[..., 1]) + s[..., 2] * s[..., 2])
+        ok = (length > 0.0) & np.isfinite(length)
+        bent = np.where(ok[..., None], s[..., 0:3] / length[..., None], 0.0)
+        occ = np.fmin(1.0, np.fmax(0.0, 1.0 - s[..., 3] / float(rounds)))
+        return np.concatenate([bent, occ[..., None]], axis=-1).astype(np.float32)
+
+
 # render_sequence's default cap on the samples a pixel carries over from the frames before it (DESIGN.md §9j)
 DEFAULT_MAX_HISTORY = 64.0
 
@@ -2199,8 +2333,58 @@ class Renderer:
             if ds is not scene:
                 ds.close()
 
+    def render_ao(self, scene, ao: "AmbientOcclusion", rounds: int = 1, samples: int = 1, device: int = 0):
+        """Ambient occlusion and bent normals of this renderer's view (not in the reference; fw_bake_ao): the first-hit
+        guide buffers (fw_render_aovs at `samples` samples) stay on the device, and fw_bake_ao reads each pixel's position and normal from
+        the records in place, tracing `rounds` rounds of ao.directions rays with this renderer's seed (+ the round), use_bvh and flags.
+        Returns (ao (H, W), bent (H, W, 3), sums (H, W, 4)) float32 host arrays; a pixel that missed the scene has ao 1 and bent 0.  The
+        call's stats are kept in self.ao_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        import torch
+        from . import _lib
+        ao.check()
+        s = self.settings
+        w, h = int(s["width"]), int(s["height"])
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            aov = torch.empty((w * h, 12), dtype=torch.float32, device=torch.device("cuda", ds.device))
+            ds.aovs(self, samples, out=aov)
+            out, sums, self.ao_stats = ds.bake_ao(ao, aov[:, 8:11], aov[:, 4:7], None, rounds, seed=s["seed"], use_bvh=s["use_bvh"], flags=s["flags"])
+        finally:
+            if ds is not scene:
+                ds.close()
+        out = out.cpu().numpy().reshape(h, w, 4)
+        return out[..., 3], out[..., 0:3], sums.cpu().numpy().reshape(h, w, 4)
+
+    def bake_lightmap_ao(self, scene, lightmap: "Lightmap", ao: "AmbientOcclusion", rounds: int = 1, dilate: int = 2, device: int = 0):
+        """An ambient-occlusion map over a lightmap's texels (not in the reference; fw_bake_ao): fw_lightmap_texels'
+        records and covered list stay on the device and are read in place; ao.directions, seed, jitter and bias count, the lightmap's
+        own do not.  Returns (ao (H, W), bent (H, W, 3), sums (H, W, 4)) float32 host arrays: ao of the covered texels packed as
+        (ao, ao, ao, 1) and passed through `dilate` passes of fw_lightmap_dilate (texels no pass reaches stay 0); bent and sums are
+        not dilated.  The call's stats are kept in self.ao_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        import torch
+        from . import _lib
+        ao.check()
+        s = self.settings
+        w, h = int(lightmap.width), int(lightmap.height)
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            rec, owner, count = _lib.lightmap_texels(lightmap, ds.device, on_device=True)
+            if count == 0:
+                raise ValueError("the lightmap covers no texel")
+            ids = torch.nonzero(owner != -1).flatten().to(torch.int32).contiguous()          # ascending: the covered list
+            out, sums, self.ao_stats = ds.bake_ao(ao, rec[:, 0:3], rec[:, 4:7], ids, rounds, seed=s["seed"], use_bvh=s["use_bvh"], flags=s["flags"])
+            image = torch.zeros((h * w, 4), dtype=torch.float32, device=rec.device)
+            at = ids.long()
+            image[at] = torch.cat([out[at, 3:4].expand(-1, 3), torch.ones_like(out[at, 3:4])], dim=1)
+            image = _lib.lightmap_dilate(image.reshape(h, w, 4), dilate, ds.device)
+        finally:
+            if ds is not scene:
+                ds.close()
+        return image[..., 0].cpu().numpy(), out[:, 0:3].cpu().numpy().reshape(h, w, 3), sums.cpu().numpy().reshape(h, w, 4)
+
     def render_probe_lit(self, scene, probes, sh, aov_samples: int = 8, wrap: bool = True, device: int = 0, model: "CameraModel" = None,
-                         depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0) -> RenderResult:
+                         depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0, ao: "AmbientOcclusion" = None,
+                         ao_rounds: int = 1) -> RenderResult:
         """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
         (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
         from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
@@ -2208,11 +2392,17 @@ class Renderer:
         probes.  The records stay on the device.  A ProbeSet without a grid: ValueError.  `scene`: a Scene, a SceneDesc or an uploaded
         _lib.DeviceScene.  depth (a ProbeDepth) with moments (n, R, R, 2), as bake_probe_depth returns them: the frame is shaded by
         fw_probe_shade_vis, every probe weighted by its visibility from the surface point moved normal_bias along its normal
-        (DESIGN.md §9s); depth=None: exactly the calls above."""
+        (DESIGN.md §9s); depth=None: exactly the calls above.  ao (an AmbientOcclusion): fw_bake_ao runs `ao_rounds`
+        rounds on the records in place; the irradiance E is looked up by fw_probe_irradiance (with depth: fw_probe_irradiance_vis) along
+        the bent normal where it is not (0, 0, 0) and along the record's normal elsewhere, and not clamped; the frame is
+        out_c = a_c (v (ao (E_c float32(1 / pi))) + (1 - v)) in float32, resolved by fw_denoise at 0 iterations.  ao=None: the calls and
+        the bits above."""
         import torch
         from . import _lib
         if depth is not None and moments is None:
             raise ValueError("depth needs the moments bake_probe_depth returned")
+        if ao is not None:
+            ao.check()
         grid = ProbeGrid.of(probes, wrap)
         s = self.settings
         w, h = (int(model.width), int(model.height)) if model is not None else (int(s["width"]), int(s["height"]))
@@ -2225,9 +2415,23 @@ class Renderer:
             else:
                 ds.aovs(self, aov_samples, out=aov)
             d_sh = torch.from_numpy(np.ascontiguousarray(np.asarray(sh, np.float32).reshape(grid.n_probes, 9, 3))).to(dev)
+            d_mom = None
             if depth is not None:
                 R = int(depth.resolution)
                 d_mom = torch.from_numpy(np.ascontiguousarray(np.asarray(moments, np.float32).reshape(grid.n_probes, R, R, 2))).to(dev)
+            if ao is not None:
+                occ, _sums, self.ao_stats = ds.bake_ao(ao, aov[:, 8:11], aov[:, 4:7], None, ao_rounds, seed=s["seed"], use_bvh=s["use_bvh"],
+                                                       flags=s["flags"])
+                bent = torch.any(occ[:, 0:3] != 0, dim=1, keepdim=True)
+                pos, nrm = aov[:, 8:11].contiguous(), torch.where(bent, occ[:, 0:3], aov[:, 4:7]).contiguous()
+                if depth is not None:
+                    E = _lib.probe_irradiance_vis(grid, d_sh, depth, d_mom, pos, nrm, normal_bias, device=ds.device)
+                else:
+                    E = _lib.probe_irradiance(grid, d_sh, pos, nrm, device=ds.device)
+                v = aov[:, 3:4]
+                lit = aov[:, 0:3] * (v * (occ[:, 3:4] * (E * float(np.float32(1.0 / np.pi)))) + (1.0 - v))
+                rgb8, gam, lin = _lib.denoise(lit.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
+            elif depth is not None:
                 rgb8, gam, lin = _lib.probe_shade_vis(grid, d_sh, depth, d_mom, aov, w, h, normal_bias, s["gamma"], ds.device)
             else:
                 rgb8, gam, lin = _lib.probe_shade(grid, d_sh, aov, w, h, s["gamma"], ds.device)

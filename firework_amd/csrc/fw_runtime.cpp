@@ -16,6 +16,7 @@
 #include "fw_lightmap.h"
 #include "fw_probe_lookup.h"
 #include "fw_probe_depth.h"
+#include "fw_ao.h"
 
 #include <algorithm>
 #include <atomic>
@@ -4596,6 +4597,215 @@ int bake_probe_depth_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe_de
     return FW_OK;
 }
 
+// ---- ambient occlusion (include/firework_hip.h) -------------------------------------------------------------------
+// An AO description's own argument checks (FW_ERR_BAD_ARG only)
+int ao_check(const fw_ao *ao) {
+    if (ao->directions == 0 || ao->directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (ao->falloff > 1u) return fail(FW_ERR_BAD_ARG, "falloff must be 0 or 1");
+    if (!(ao->radius > 0.f)) return fail(FW_ERR_BAD_ARG, "radius must be > 0");
+    if (std::isinf(ao->radius) && ao->falloff) return fail(FW_ERR_BAD_ARG, "an infinite radius needs falloff 0");
+    if (!std::isfinite(ao->bias) || ao->bias < 0.f) return fail(FW_ERR_BAD_ARG, "bias must be finite and >= 0");
+    return FW_OK;
+}
+
+// how many entries an array indexed by id spans: max(ids) + 1, or n without ids (host ids)
+inline uint64_t ao_extent(uint32_t n, const uint32_t *ids) {
+    if (!ids) return n;
+    uint32_t top = 0;
+    for (uint32_t q = 0; q < n; q++) top = std::max(top, ids[q]);
+    return (uint64_t)top + 1u;
+}
+
+// Host points staged on the device: positions and normals over `extent` ids, the ids, and `extra` bytes more for the caller (at *extra_at),
+// in one allocation of `scratch`.  The copies are enqueued on `stream`.
+int ao_stage_points(hipStream_t stream, CallScratch &scratch, uint32_t n, const float *positions, const float *normals, uint32_t stride,
+                    const uint32_t *ids, uint64_t extent, size_t extra, fw::DAoPoints &pts, uint8_t *&extra_at) {
+    const size_t arr = (size_t)((extent - 1u) * stride + 3u) * 4u;
+    const size_t o_nrm = align256(arr), o_ids = o_nrm + align256(arr), o_extra = o_ids + align256(ids ? (size_t)n * 4u : 0);
+    if (int rc = scratch.alloc(o_extra + extra)) return rc;
+    uint8_t *base = (uint8_t *)scratch.p;
+    HIPCHK(hipMemcpyAsync(base, positions, arr, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(base + o_nrm, normals, arr, hipMemcpyHostToDevice, stream));
+    if (ids) HIPCHK(hipMemcpyAsync(base + o_ids, ids, (size_t)n * 4u, hipMemcpyHostToDevice, stream));
+    pts.positions = (const float *)base; pts.normals = (const float *)(base + o_nrm);
+    pts.ids = ids ? (const uint32_t *)(base + o_ids) : nullptr; pts.stride = stride;
+    extra_at = base + o_extra;
+    return FW_OK;
+}
+
+fw::DAoRays ao_rays_device(const fw_ao *ao, uint32_t round, const fw::DAoPoints &pts, uint32_t first) {
+    fw::DAoRays d{};
+    d.pts = pts; d.first = first;
+    d.directions = ao->directions;
+    d.seed32 = seed32_of(ao->seed);
+    d.jitter = ao->jitter ? 1u : 0u;
+    d.round = round; d.bias = ao->bias;
+    return d;
+}
+
+// fw_ao_rays: fw_lightmap_rays' shape — with device arrays the kernel works on the caller's memory; with host arrays the points are
+// staged once and the rays come back in slabs
+int ao_rays_impl(const fw_ao *ao, int device, uint32_t round, uint32_t n, const float *positions, const float *normals, uint32_t stride,
+                 const uint32_t *ids, float *rays, int on_device, void *stream_) {
+    if (!ao || !positions || !normals || !rays) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = ao_check(ao)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (on_device && (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids | (uintptr_t)rays) & 3u))
+        return fail(FW_ERR_BAD_ARG, "device arrays must be 4-byte aligned");
+    if ((uint64_t)n * ao->directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n_cus = device_cus(device);
+    if (on_device) {
+        fw::launch_ao_rays(stream, n_cus, ao_rays_device(ao, round, fw::DAoPoints{positions, normals, ids, stride}, 0), n, rays);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+    CallScratch scratch(device);
+    fw::DAoPoints pts{};
+    uint8_t *extra = nullptr;
+    if (int rc = ao_stage_points(stream, scratch, n, positions, normals, stride, ids, ao_extent(n, ids), 0, pts, extra)) { (void)hipStreamSynchronize(stream); return rc; }
+    return host_slabs(stream, device, n, (size_t)ao->directions * 24, rays, [&](uint32_t done, uint32_t k, float *d_rays) {
+        fw::launch_ao_rays(stream, n_cus, ao_rays_device(ao, round, pts, done), k, d_rays);
+    });
+}
+
+// fw_ao_reduce: fw_probe_depth_reduce's shape
+int ao_reduce_impl(int device, const fw_ao *ao, uint32_t n, const uint32_t *ids, const float *rays, const fw_hit *hits, float *sums, int on_device,
+                   void *stream_) {
+    if (!ao || !rays || !hits || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = ao_check(ao)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (on_device && ((((uintptr_t)sums | (uintptr_t)hits) & 15u) || (((uintptr_t)rays | (uintptr_t)ids) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums and hits must be 16-byte aligned, device rays and ids 4-byte aligned");
+    const uint32_t D = ao->directions;
+    if ((uint64_t)n * D >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t entries = (size_t)n * D;
+    CallScratch scratch(device);
+    const float *d_rays = rays; const fw_hit *d_hits = hits; float *d_sums = sums; const uint32_t *d_ids = ids;
+    size_t sum_bytes = 0;
+    if (!on_device) {
+        sum_bytes = (size_t)ao_extent(n, ids) * 16;
+        const size_t o_hits = align256(entries * 24), o_sums = o_hits + align256(entries * sizeof(fw_hit)), o_ids = o_sums + align256(sum_bytes);
+        if (int rc = scratch.alloc(o_ids + (ids ? (size_t)n * 4 : 0))) return rc;
+        uint8_t *base = (uint8_t *)scratch.p;
+        HIPCHK(hipMemcpyAsync(base, rays, entries * 24, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_hits, hits, entries * sizeof(fw_hit), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
+        if (ids) HIPCHK(hipMemcpyAsync(base + o_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+        d_rays = (const float *)base; d_hits = (const fw_hit *)(base + o_hits); d_sums = (float *)(base + o_sums);
+        d_ids = ids ? (const uint32_t *)(base + o_ids) : nullptr;
+    }
+    fw::launch_ao_reduce(stream, device_cus(device), 0, n, D, ao->falloff, ao->radius, d_ids, d_rays, d_hits, d_sums);
+    if (!on_device) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_bake_ao: bake_probe_depth_impl's loop over surface points.  Its own are the argument checks, the scratch (a host caller's points, a
+// chunk's rays and hits, the running sums and the output unless the caller's device memory holds them), k_ao_rays and k_ao_reduce around
+// trace_impl's trace of each chunk, and k_ao_resolve.  The scratch is released on every way out; on an error the stream is drained.
+// (The loop repeats bake_probe_depth_impl's: one trace-round driver for both is a follow-up.)
+// Drains a stream on every way out of a call but the one that disarms it; declared after the scratch, so it runs before the release.
+struct StreamDrain { hipStream_t s; bool armed = true; ~StreamDrain() { if (armed) (void)hipStreamSynchronize(s); } };
+int bake_ao_impl(fw_scene *sc, const fw_ao *ao, const fw_trace_params *tp, uint32_t N, const float *positions, const float *normals, uint32_t stride,
+                 const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    if (!sc || !ao || !tp || !positions || !normals) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = ao_check(ao)) return rc;
+    if (N == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (rounds == 0) return fail(FW_ERR_BAD_ARG, "rounds must be > 0");
+    if ((uint64_t)first_round + rounds > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_round + rounds overflows");
+    if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
+    if (tp->on_device && ((((uintptr_t)sums | (uintptr_t)out) & 15u) || (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums and out must be 16-byte aligned, device positions, normals and ids 4-byte aligned");
+    const uint32_t D = ao->directions;
+    if ((uint64_t)N * D >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
+    if (int rc = need_device()) return rc;
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)tp->stream;
+    const bool on_device = tp->on_device != 0;
+    const uint32_t chunk = std::min<uint32_t>(N, ao->chunk_points ? ao->chunk_points : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 72)));
+    const bool own_sums = !on_device || !sums;            // the running sums live in the scratch: a host caller's, or nobody's
+    const bool own_out = out && !on_device;
+    // how many records sums and out span: only scratch copies of them need it
+    uint64_t extent = N;
+    if (ids && (own_sums || own_out)) {
+        if (on_device) {
+            std::vector<uint32_t> h_ids(N);
+            HIPCHK(hipMemcpyAsync(h_ids.data(), ids, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            extent = ao_extent(N, h_ids.data());
+        } else extent = ao_extent(N, ids);
+    }
+    const size_t rec_bytes = (size_t)extent * 16;
+    const size_t o_hits = align256((size_t)chunk * D * 24), o_sums = o_hits + align256((size_t)chunk * D * sizeof(fw_hit)),
+                 o_out = o_sums + align256(own_sums ? rec_bytes : 0), work = o_out + (own_out ? rec_bytes : 0);
+    CallScratch scratch(dev);
+    StreamDrain drain{stream};
+    fw::DAoPoints pts{positions, normals, ids, stride};
+    uint8_t *base = nullptr;
+    if (on_device) {
+        if (int rc = scratch.alloc(work)) return rc;
+        base = (uint8_t *)scratch.p;
+    } else if (int rc = ao_stage_points(stream, scratch, N, positions, normals, stride, ids, extent, work, pts, base)) return rc;
+    float *d_rays = (float *)base, *d_sums = own_sums ? (float *)(base + o_sums) : sums, *d_out = own_out ? (float *)(base + o_out) : out;
+    fw_hit *d_hits = (fw_hit *)(base + o_hits);
+    if (own_sums) {
+        if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, rec_bytes, hipMemcpyHostToDevice, stream));
+        else HIPCHK(hipMemsetAsync(d_sums, 0, rec_bytes, stream));
+    }
+    if (own_out && ids) HIPCHK(hipMemcpyAsync(d_out, out, rec_bytes, hipMemcpyHostToDevice, stream));      // entries outside the list stay
+    const int n_cus = device_cus(dev);
+    fw_stats total{};
+    CallEvents<4> ev;                                     // around the two kernels' launches
+    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
+    for (uint32_t r = first_round; r - first_round < rounds; r++) {      // (first_round + rounds may be 2^32 - 1: r itself never gets there)
+        fw_trace_params q = *tp;
+        q.on_device = 1; q.seed = tp->seed + r;
+        for (uint32_t q0 = 0; q0 < N; q0 += chunk) {
+            const uint32_t k = std::min(chunk, N - q0);
+            q.key_base = q0 * D;
+            if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
+            fw::launch_ao_rays(stream, n_cus, ao_rays_device(ao, r, pts, q0), k, d_rays);
+            if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
+            fw_stats ts{};
+            if (int rc = trace_impl(sc, &q, d_rays, k * D, d_hits, stats ? &ts : nullptr)) return rc;
+            if (stats) HIPCHK(hipEventRecord(ev.e[2], stream));
+            fw::launch_ao_reduce(stream, n_cus, q0, k, D, ao->falloff, ao->radius, pts.ids, d_rays, d_hits, d_sums);
+            if (!stats) continue;
+            HIPCHK(hipEventRecord(ev.e[3], stream));
+            HIPCHK(hipEventSynchronize(ev.e[3]));
+            float gen_ms = 0.f, red_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
+            HIPCHK(hipEventElapsedTime(&red_ms, ev.e[2], ev.e[3]));
+            stats_add(total, ts);
+            total.ms_render += gen_ms + red_ms;
+            if (tp->flags & FW_FLAG_TIME_KERNELS) { total.ms_raygen += gen_ms; total.ms_accumulate += red_ms; }
+        }
+    }
+    if (!on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, rec_bytes, hipMemcpyDeviceToHost, stream));
+    if (out) {
+        fw::launch_ao_resolve(stream, N, (double)((uint64_t)first_round + rounds), pts.ids, d_sums, d_out);
+        if (own_out) HIPCHK(hipMemcpyAsync(out, d_out, rec_bytes, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    drain.armed = false;
+    HIPCHK(hipGetLastError());
+    if (stats) {
+        *stats = total;
+        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FW_OK;
+}
+
 } // namespace
 
 // =========================================================================================================
@@ -5081,6 +5291,27 @@ int fw_bake_probe_depth(fw_scene *scene, const fw_probe_set *set, const fw_probe
     try { return bake_probe_depth_impl(scene, set, pd, tp, first_round, rounds, sums, moments, stats); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_probe_depth"); }
+}
+
+int fw_ao_rays(const fw_ao *ao, int device, uint32_t round, uint32_t n, const float *positions, const float *normals, uint32_t stride_floats,
+               const uint32_t *ids, float *rays, int on_device, void *stream) {
+    try { return ao_rays_impl(ao, device, round, n, positions, normals, stride_floats, ids, rays, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_ao_rays"); }
+}
+
+int fw_ao_reduce(int device, const fw_ao *ao, uint32_t n, const uint32_t *ids, const float *rays, const fw_hit *hits, float *sums, int on_device,
+                 void *stream) {
+    try { return ao_reduce_impl(device, ao, n, ids, rays, hits, sums, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_ao_reduce"); }
+}
+
+int fw_bake_ao(fw_scene *scene, const fw_ao *ao, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
+               uint32_t stride_floats, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    try { return bake_ao_impl(scene, ao, tp, n, positions, normals, stride_floats, ids, first_round, rounds, sums, out, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_ao"); }
 }
 
 int fw_probe_irradiance_vis(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias, int device,

@@ -1051,6 +1051,83 @@ int fw_lightmap_dilate(int device, uint32_t width, uint32_t height, uint32_t pas
    on_device sums or irradiance not 16-byte aligned; FW_ERR_UNSUPPORTED as above; then FW_ERR_NO_DEVICE.  stats: as fw_bake_probes. */
 int fw_bake_lightmap(fw_scene *scene, const fw_lightmap *lm, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, uint32_t dilate, float *sums, float *irradiance, fw_stats *stats);
 
+/* ---- ambient occlusion and bent normals of surface points (additive at ABI 8) ----------------------------------------
+   What a probe grid cannot give: occlusion finer than the probe spacing.  For each of n surface points, D cosine-weighted hemisphere
+   rays per round are traced against a resident scene at the renderer's fixed range and their hit distances compared with a radius
+   afterwards; the share of occluded rays gives ao in [0, 1] (1 = open), the mean unoccluded direction the bent normal.  Everything is
+   float64 from the float32 inputs, every operation rounded as written.  api.ao_rays, api.ao_reduce and api.ao_resolve are the numpy
+   statements.
+     Points.  Point q of a call is id = ids ? ids[q] : q; its position and its normal are three floats each at positions + id x
+         stride_floats and normals + id x stride_floats, stride_floats >= 3.  ids: an optional list of n distinct uint32 (the caller
+         promises it).  fw_render_aovs' records are read in place with stride 12, positions = aov + 8, normals = aov + 4;
+         fw_lightmap_texels' records with stride 8, positions = rec, normals = rec + 4 and ids = the covered list.  sums and out are
+         records of 16 B indexed by id: with ids they are shaped like the records, and entries outside the list are never touched.
+         With host arrays and ids every array indexed by id spans max(ids) + 1 entries.  A point is unusable if a component of its
+         position or normal is not finite or its normal is (0, 0, 0) — as of every pixel that missed the scene.
+     Rays (fw_ao_rays, k_ao_rays): fw_lightmap_rays' statement with "texel id" replaced by id — the same hash of (seed, round, id) for
+         the shift (xi_u, xi_v), or (1/2, 1/2) with jitter 0; u = (j + xi_u) / D, r = sqrt u, c = sqrt(max(0, 1 - u)), t = j g + xi_v,
+         phi = 2 pi (t - floor t), l = (r cos phi, r sin phi, c) in the basis of Duff et al. 2017 around n = the float32 normal divided
+         by its float64 length; origin = position + bias * n (bias 0: the position's bits); one rounding to float32.  Entry q D + j,
+         6 floats.  Fed a lightmap's records and covered list with the lightmap's D, seed, jitter, bias and round the rays equal
+         fw_lightmap_rays' bit for bit.  An unusable point gets D all-zero rays, which fw_trace_rays reports as misses and never traces.
+     Reduction of one round (fw_ao_reduce, k_ao_reduce).  For ray j of point q, d the float32 direction as stored and h its hit: an
+         all-zero d contributes nothing; otherwise dist = (double)h.t * sqrt((dx dx + dy dy) + dz dz);  o = 0 if h.object == FW_NO_HIT
+         or dist >= radius, else o = 1 (falloff 0) or 1 - dist / radius (falloff 1).  Four float64 accumulators: O += o and
+         B_k += (1 - o) * d_k.  With G = the smallest power of two >= min(D, 64), partial sum l takes j = l, l + G, ... in ascending
+         order from 0, and the G partial sums are added by an xor butterfly over the distances G/2 ... 1 (x_l <- x_l + x_(l xor m)).
+         Each accumulator is multiplied by the float64 1 / D, rounded to float32 once and added with one float32 addition to
+         sums[id] = (Bx, By, Bz, O).  Two runs are bit-equal; a point's result depends on no other point.
+     Resolve (k_ao_resolve), R = the number of rounds in sums: out[id] = (bx, by, bz, ao) with ao = float(min(1, max(0, 1 - (double)O /
+         R))) and b = B / sqrt((Bx Bx + By By) + Bz Bz) in float64, rounded once; (0, 0, 0) when that length is 0 or not finite.  An
+         unusable point resolves to (0, 0, 0, 1), a fully occluded one to (0, 0, 0, 0). */
+typedef struct fw_ao {
+    uint32_t directions;      /* D, 1..2^20 */
+    uint32_t falloff;         /* 0 hard, 1 linear */
+    float    radius;          /* > 0; +infinity allowed with falloff 0: any hit occludes */
+    float    bias;            /* >= 0, finite */
+    uint32_t jitter;          /* 0: the shift (1/2, 1/2) */
+    uint32_t chunk_points;    /* fw_bake_ao: points per chunk; 0 = as many as fit 256 MiB at 72 B per ray, at least one */
+    uint64_t seed;
+} fw_ao;
+
+/* fw_ao_rays: the rays of round `round` of the n points: n x D x 6 floats.  Host arrays — staged through device allocations of the
+   call's own, freed on every path — or with on_device device arrays on `device`, generated on `stream` and complete on return.
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL ao, positions, normals or rays; directions outside
+   1..2^20, falloff > 1, radius not > 0 (or NaN), an infinite radius with falloff 1, bias negative or not finite; n == 0;
+   stride_floats < 3; with on_device an array not 4-byte aligned; FW_ERR_UNSUPPORTED for n x D >= 2^31; then FW_ERR_NO_DEVICE, and
+   FW_ERR_BAD_ARG for a device index past the last one. */
+int fw_ao_rays(const fw_ao *ao, int device, uint32_t round, uint32_t n, const float *positions, const float *normals, uint32_t stride_floats,
+               const uint32_t *ids, float *rays, int on_device, void *stream);
+
+/* fw_ao_reduce: adds one round's reduction to the running sums.  rays: n x D x 6 floats; hits: n x D records as fw_trace_rays wrote
+   them for those rays; sums: records indexed by id.  Host or device arrays as fw_ao_rays.  Errors, in this order and before HIP is
+   called: FW_ERR_BAD_ARG for a NULL ao, rays, hits or sums; fw_ao_rays' checks of ao; n == 0; with on_device sums or hits not 16-byte
+   aligned, rays or ids not 4-byte aligned; FW_ERR_UNSUPPORTED for n x D >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device
+   index past the last one. */
+int fw_ao_reduce(int device, const fw_ao *ao, uint32_t n, const uint32_t *ids, const float *rays, const fw_hit *hits, float *sums, int on_device,
+                 void *stream);
+
+/* fw_bake_ao: the rounds [first_round, first_round + rounds) of the n points against a resident scene.  Of tp, use_bvh, flags, seed,
+   rays_per_batch, on_device (for positions, normals, ids, sums and out) and stream are read; key_base is ignored.  For each round r and
+   each chunk of points [q0, q1) (ao->chunk_points at a time): k_ao_rays fills device scratch that the call allocates and frees on every
+   path; the rays are traced exactly as fw_trace_rays would with on_device = 1, key_base = q0 D and seed = tp->seed + r (so a
+   ConstantMedium draws reproducibly); k_ao_reduce adds the chunk into sums.  k_ao_resolve finishes.  On an error the stream is drained.
+     sums: the running sums of the rounds [0, first_round) — zeros when first_round is 0 — to which this call's rounds are added in
+           order; NULL only when first_round == 0.
+     out : (bent.xyz, ao) after first_round + rounds rounds; may be NULL.
+   Contracts.  Composition: for every chunk_points, sums equals bit for bit what fw_ao_rays, fw_trace_rays (seed + r, key_base 0) and
+   fw_ao_reduce give when chained by hand over all n points.  Progressive: k calls of n rounds leave the sums and out of one call of k n
+   rounds, bit for bit.
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, ao, tp, positions or
+   normals; fw_ao_rays' checks of ao; n == 0; stride_floats < 3; rounds == 0; first_round + rounds >= 2^32; a NULL sums with
+   first_round > 0; with on_device sums or out not 16-byte aligned, positions, normals or ids not 4-byte aligned; FW_ERR_UNSUPPORTED for
+   n x D >= 2^31; then FW_ERR_NO_DEVICE.
+   stats (may be NULL): fw_trace_rays' fields summed over rounds and chunks (rays = the rays traced: zero rays are not); ms_render
+   includes the two kernels' launches (under FW_FLAG_TIME_KERNELS ms_raygen and ms_accumulate as well); ms_wall covers the whole call.
+   Synchronisation and what a trace leaves of renders are fw_trace_rays'. */
+int fw_bake_ao(fw_scene *scene, const fw_ao *ao, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
+               uint32_t stride_floats, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
+
 /* Diagnostic: the kernels' division / square-root helpers against the compiler's IEEE expansion, bit for bit,
    on n hashed operand pairs.  mode 0 = magnitudes 2^-40..2^40 (must be 0 mismatches), mode 1 = all bit patterns. */
 int fw_selftest_arith(int device, uint32_t n, uint32_t seed, int mode, uint64_t *div_mismatches, uint64_t *sqrt_mismatches);
