@@ -100,7 +100,8 @@ struct DScene {
     const uint32_t *tri_rank; // in-order rank of each triangle in the REFERENCE tree of its mesh (tie-breaking)
     const uint32_t *obj_rank; // same for objects in the reference TLAS
     const float4 *obj_gate;   // per object: box (2 x float4) of its leaf node in the reference TLAS (used with OF_GATE)
-    const float4 *obj_cull;   // per object: enclosing world box (2 x float4) of the object itself: the pre-tests of the linear scan
+    const float4 *obj_cull;   // per object: enclosing world box (2 x float4) of the object itself: the pre-tests of the linear scan; then, per object again,
+                              // the same box as centre and grown half extent (fw_defer_pretest.h: what k_extend_linear_defer tests)
     const float4 *obj_leaf;   // per object: its box in the WALKED trees = its own world box (a gated object: its reference leaf-node box united
                               // with bounds that enclose it): what k_extend_scan / hoisted_hits test before the object
     const float4 *mat;

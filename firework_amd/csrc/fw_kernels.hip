@@ -29,6 +29,7 @@
 #include "../../include/firework_hip.h"     // FW_DENOISE_* (the filter's constants)
 #include "fw_device.h"
 #include "fw_libm.h"
+#include "fw_defer_pretest.h"
 #include <atomic>
 #include <type_traits>
 
@@ -1856,23 +1857,17 @@ void k_extend_linear_defer(DScene sc, DFrame f, DPaths in, float2 *__restrict__ 
                 } else h = hit_object<false, 0, false, SIMPLE>(sc, o, k, r, TMIN, best_t, nullptr, nokey, segment, t, prim);
                 if (h) { best_t = t; best_obj = k; best_prim = prim; }
             }
-            // conservative pre-tests (see closest_hit's segment-0 cull: approximate reciprocals, boxes inflated by 1e-4 of the
-            // scene and ray-origin scale, NaN-dropping min/max), here per lane and also culled against the hit so far
-            const V3 ainv = mk(__builtin_amdgcn_rcpf(r.d.x), __builtin_amdgcn_rcpf(r.d.y), __builtin_amdgcn_rcpf(r.d.z));
-            const float eps = 1e-4f * (fabsf(r.o.x) + fabsf(r.o.y) + fabsf(r.o.z));
-            for (uint32_t d = 0; d < n_def; d++) {
-                const uint32_t k = n_first + d;
-                const float4 lo = sc.obj_cull[2 * (size_t)k], hi = sc.obj_cull[2 * (size_t)k + 1];
-                const float m = eps + 1e-4f * (fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fabsf(lo.z)) + fmaxf(fmaxf(fabsf(hi.x), fabsf(hi.y)), fabsf(hi.z))) + 1e-6f;
-                float t0 = (lo.x - m - r.o.x) * ainv.x, t1 = (hi.x + m - r.o.x) * ainv.x;
-                float tn = fminf(t0, t1), tf = fmaxf(t0, t1);
-                t0 = (lo.y - m - r.o.y) * ainv.y; t1 = (hi.y + m - r.o.y) * ainv.y;
-                tn = fmaxf(tn, fminf(t0, t1)); tf = fminf(tf, fmaxf(t0, t1));
-                t0 = (lo.z - m - r.o.z) * ainv.z; t1 = (hi.z + m - r.o.z) * ainv.z;
-                tn = fmaxf(tn, fminf(t0, t1)); tf = fminf(tf, fmaxf(t0, t1));
-                const bool maybe = !(tf < tn * (1.f - 1e-4f) - 1e-4f) && !(tf < 0.f) && !(tn * (1.f - 1e-4f) - 1e-4f > best_t);
-                if (d == 0) may0 = maybe; else may1 = maybe;
-            }
+            // conservative pre-tests, per lane and culled against the hit so far: fw_defer_pretest.h.  The slab test of closest_hit's
+            // segment-0 cull (boxes inflated by 1e-4 of the scene and ray-origin scale) with the work moved out of the box loop: the
+            // box comes from the host as centre and grown half extent (the second half of obj_cull: nothing wave-uniform is computed
+            // here), the reciprocals are the ones the room's rectangles just used (no v_rcp_f32 of its own), a plane pair is three
+            // fmas around the centre's distance fma(c, inv, -o * inv), whose rounding the host's extra hundredth of margin covers,
+            // and a direction component that is 0, below 2^-40, infinite or NaN lists the ray whatever the slabs say (the exact
+            // test accepts t = 0/0).  91 -> 45 vector instructions per chunk for two boxes (profiles/defer_pretest_isa.txt).
+            const fwpt::RayTerms rt = fwpt::ray_terms(r.o.x, r.o.y, r.o.z, rcx.r, rcy.r, rcz.r);
+            const float4 *const cb = sc.obj_cull + 2 * ((size_t)sc.n_objects + n_first);       // n_def is 1 or 2 (the host: n_defer)
+            may0 = fwpt::pretest_fma(rt, cb[0].x, cb[0].y, cb[0].z, cb[1].x, cb[1].y, cb[1].z, best_t);
+            if (n_def > 1u) may1 = fwpt::pretest_fma(rt, cb[2].x, cb[2].y, cb[2].z, cb[3].x, cb[3].y, cb[3].z, best_t);
         }
         const uint32_t code = best_obj == MISS ? MISS : ((best_obj << sc.prim_bits) | best_prim);
         const bool c1 = may1 && !may0;                                  // straight to list 1; a ray listed for box 0 carries box 1 in bit 31

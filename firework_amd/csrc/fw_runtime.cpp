@@ -17,6 +17,7 @@
 #include "fw_probe_lookup.h"
 #include "fw_probe_depth.h"
 #include "fw_ao.h"
+#include "fw_defer_pretest.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1475,6 +1476,15 @@ int object_level(const fw_scene_desc *desc, int device, const Options &O, const 
         return out;
     };
     L.cull = pack_boxes(own_boxes);       // enclosing world boxes of the objects themselves: the pre-tests of the linear scan (k_extend_linear*)
+    {   // ... and behind them the same boxes as centre and grown half extent, for the box-list scan's fma pre-test (fw_defer_pretest.h)
+        L.cull.resize((size_t)n_obj * 16, 0.f);
+        for (uint32_t i = 0; i < n_obj; i++) {
+            const float *b = &L.cull[(size_t)i * 8];
+            const fwpt::CullBox cb = fwpt::make_cull_box(b, b + 4);
+            float *c = &L.cull[((size_t)n_obj + i) * 8];
+            for (int a = 0; a < 3; a++) { c[a] = cb.c[a]; c[4 + a] = cb.h[a]; }
+        }
+    }
     L.leafb = pack_boxes(build_boxes);    // the objects' boxes in the walked trees (k_extend_scan, hoisted_hits)
     // Hoisting: an object whose box covers most of the scene (part2's r = 5000 fog medium) is met by nearly every ray, so in
     // the tree its leaf is one more divergent leaf test per ray.  Scenes without meshes and too many objects for the scan keep
