@@ -42,6 +42,11 @@ weights cos^(2^K), K in 0..8, default 6, distances clamped to M, default the gri
 fw_bake_probe_depth; the .npz also gets depth, depth_res, depth_sharpness and depth_max).  --probe-lit then weights every
 probe by its visibility from the surface (fw_probe_shade_vis) when the file holds them; --probe-no-visibility ignores them (the image
 of a file without them), --probe-normal-bias B moves the looked-up point B >= 0 world units along its normal first (default 0).
+--bake-probes ... --probe-relocate MIN_FRONT [--probe-relocate-steps K] [--probe-relocate-max F] (first moves probes out of geometry and
+marks those that stay inside inactive, fw_relocate_probes, DESIGN.md §9u: K moving steps, default 4, no offset beyond F, default 0.45,
+of the grid's spacing; sh and depth are baked at the moved positions; the .npz keeps the nominal positions and also gets placement,
+relocate_min_front and relocate_steps).  --probe-lit then reads the probes where they went (fw_probe_shade_placed) when the file holds
+placement; --probe-no-placement ignores it.
 --ao RADIUS [--ao-dirs D] [--ao-rounds R] [--ao-falloff] (the fixed view's ambient occlusion as a grey PNG: one first-hit pass of
 --aov-samples samples, then R rounds, default 1, of D cosine-weighted rays per pixel, default 64, traced from each pixel's surface point;
 a hit nearer than RADIUS > 0 occludes, fully or with --ao-falloff by 1 - dist / RADIUS, fw_bake_ao, DESIGN.md §9t; -s is not used;
@@ -107,6 +112,13 @@ def main(argv=None):
     ap.add_argument("--lightmap-dirs", type=int, default=None, metavar="D", help="with --bake-lightmap: directions per texel and round (default 64)")
     ap.add_argument("--lightmap-rounds", type=int, default=None, metavar="R", help="with --bake-lightmap: rounds of -s samples per direction (default 1)")
     ap.add_argument("--lightmap-dilate", type=int, default=None, metavar="N", help="with --bake-lightmap: dilation passes over the seams, 0..64 (default 2)")
+    ap.add_argument("--probe-relocate", type=float, default=None, metavar="MIN_FRONT",
+                    help="with --bake-probes: first move probes out of geometry (at least MIN_FRONT > 0 from the nearest front face) and mark "
+                         "those that stay inside inactive; sh and depth are baked at the moved positions")
+    ap.add_argument("--probe-relocate-steps", type=int, default=None, metavar="K", help="with --probe-relocate: moving steps before the classification (default 4)")
+    ap.add_argument("--probe-relocate-max", type=float, default=None, metavar="F",
+                    help="with --probe-relocate: the largest offset as a fraction F >= 0 of the grid's spacing per axis (default 0.45)")
+    ap.add_argument("--probe-no-placement", action="store_true", help="with --probe-lit: ignore the placement in the file")
     ap.add_argument("--probe-lit", default=None, metavar="PROBES.npz",
                     help="render the view lit from the irradiance probes that a --bake-probes run saved, without tracing paths")
     ap.add_argument("--probe-no-wrap", action="store_true", help="with --probe-lit: no guard against light from probes behind the surface")
@@ -158,6 +170,8 @@ def main(argv=None):
             ap.error("--probe-normal-bias B needs a finite B >= 0")
     elif opt.probe_no_wrap:
         ap.error("--probe-no-wrap needs --probe-lit")
+    elif opt.probe_no_placement:
+        ap.error("--probe-no-placement needs --probe-lit")
     elif opt.probe_no_visibility or opt.probe_normal_bias is not None:
         ap.error("--probe-no-visibility and --probe-normal-bias need --probe-lit")
     if opt.bake_lightmap is not None:
@@ -215,12 +229,25 @@ def main(argv=None):
                 ap.error("--probe-depth needs --probe-depth-max M for a grid of one point: it has no diagonal")
         elif opt.probe_depth_sharpness is not None or opt.probe_depth_max is not None:
             ap.error("--probe-depth-sharpness and --probe-depth-max need --probe-depth")
+        if opt.probe_relocate is not None:
+            if not 0.0 < opt.probe_relocate < float("inf"):
+                ap.error("--probe-relocate MIN_FRONT needs a finite MIN_FRONT > 0")
+            if opt.probe_relocate_steps is not None and not 0 <= opt.probe_relocate_steps < 1 << 31:
+                ap.error("--probe-relocate-steps K needs K >= 0")
+            if opt.probe_relocate_max is not None and not 0.0 <= opt.probe_relocate_max < float("inf"):
+                ap.error("--probe-relocate-max F needs a finite F >= 0")
+            if max(counts) == 1:
+                ap.error("--probe-relocate needs a grid of more than one probe: a single point has no spacing")
+        elif opt.probe_relocate_steps is not None or opt.probe_relocate_max is not None:
+            ap.error("--probe-relocate-steps and --probe-relocate-max need --probe-relocate")
         if not opt.output:
             ap.error("--bake-probes needs -o FILE.npz")
     elif opt.probe_min is not None or opt.probe_max is not None or opt.probe_dirs is not None or opt.probe_rounds is not None:
         ap.error("--probe-min, --probe-max, --probe-dirs and --probe-rounds need --bake-probes")
     elif opt.probe_depth is not None or opt.probe_depth_sharpness is not None or opt.probe_depth_max is not None:
         ap.error("--probe-depth, --probe-depth-sharpness and --probe-depth-max need --bake-probes")
+    elif opt.probe_relocate is not None or opt.probe_relocate_steps is not None or opt.probe_relocate_max is not None:
+        ap.error("--probe-relocate, --probe-relocate-steps and --probe-relocate-max need --bake-probes")
     if opt.adaptive is not None and (opt.progressive > 0 or opt.checkpoint):
         ap.error("--adaptive cannot be combined with --progressive or --checkpoint")
     if opt.temporal is not None:
@@ -275,7 +302,7 @@ def main(argv=None):
             print(f"firework: error: --bake-lightmap: {e}", file=sys.stderr)
             return 2
 
-    probe_grid = probe_sh = probe_depth = probe_moments = None
+    probe_grid = probe_sh = probe_depth = probe_moments = probe_placement = None
     if opt.probe_lit is not None:          # the file is looked at before the device is: a wrong one is a message, not a traceback
         import zipfile
         import numpy as np
@@ -294,10 +321,14 @@ def main(argv=None):
                         raise ValueError(f"depth without {', '.join(missing)} in it")
                     probe_depth = ProbeDepth(int(z["depth_res"]), int(z["depth_sharpness"]), float(z["depth_max"]))
                     probe_moments = np.asarray(z["depth"], np.float32)
+                if "placement" in z.files and not opt.probe_no_placement:
+                    probe_placement = np.asarray(z["placement"], np.float32)
             if probe_sh.shape != (probe_grid.n_probes, 9, 3):
                 raise ValueError(f"sh has shape {probe_sh.shape}, the grid {probe_grid.n_probes} probes")
             if probe_depth is not None and probe_moments.shape != (probe_grid.n_probes, probe_depth.resolution, probe_depth.resolution, 2):
                 raise ValueError(f"depth has shape {probe_moments.shape}, the grid {probe_grid.n_probes} probes of resolution {probe_depth.resolution}")
+            if probe_placement is not None and probe_placement.shape != (probe_grid.n_probes, 4):
+                raise ValueError(f"placement has shape {probe_placement.shape}, the grid {probe_grid.n_probes} probes")
         except (OSError, ValueError, zipfile.BadZipFile) as e:
             print(f"firework: error: --probe-lit {opt.probe_lit}: {e}", file=sys.stderr)
             return 2
@@ -317,26 +348,37 @@ def main(argv=None):
         from .api import ProbeSet
         probes = ProbeSet.grid(corners[0], corners[1], counts, 256 if opt.probe_dirs is None else opt.probe_dirs).seed(opt.seed)
         rounds = 1 if opt.probe_rounds is None else opt.probe_rounds
-        sh, sums = renderer.bake_probes(scene, probes, rounds, device=opt.device)
         extra = {}
+        nominal = probes
+        if opt.probe_relocate is not None:      # first: sh and depth are then baked where the probes went
+            from .api import ProbeRelocation, probe_spacing
+            fraction = 0.45 if opt.probe_relocate_max is None else opt.probe_relocate_max
+            relocation = ProbeRelocation(opt.probe_relocate, max_offset=tuple(fraction * v for v in probe_spacing(probes)),
+                                         steps=4 if opt.probe_relocate_steps is None else opt.probe_relocate_steps)
+            placement, _survey = renderer.relocate_probes(scene, probes, relocation, device=opt.device)
+            print(f"Relocated {int(np.any(placement[:, 0:3] != 0, axis=1).sum())} probes, {int((placement[:, 3] == 0).sum())} inactive")
+            extra = dict(placement=placement, relocate_min_front=np.float32(relocation.min_front), relocate_steps=np.int64(relocation.steps))
+            probes = nominal.moved(placement)
+        sh, sums = renderer.bake_probes(scene, probes, rounds, device=opt.device)
         if opt.probe_depth is not None:
             from .api import ProbeDepth
             diagonal = float(np.sqrt(sum((b - a) ** 2 for a, b in zip(corners[0], corners[1]))))
             depth = ProbeDepth(opt.probe_depth, 6 if opt.probe_depth_sharpness is None else opt.probe_depth_sharpness,
                                diagonal if opt.probe_depth_max is None else opt.probe_depth_max)
             moments, _depth_sums = renderer.bake_probe_depth(scene, probes, depth, rounds, device=opt.device)
-            extra = dict(depth=moments, depth_res=np.int64(depth.resolution), depth_sharpness=np.int64(depth.sharpness_log2),
-                         depth_max=np.float32(depth.max_distance))
+            extra.update(depth=moments, depth_res=np.int64(depth.resolution), depth_sharpness=np.int64(depth.sharpness_log2),
+                          depth_max=np.float32(depth.max_distance))
         print(f"Finished Baking in {int(time.time() - start)} s")
         print(f'Saving {probes.n_probes} probes to "{opt.output}"')
         with open(opt.output, "wb") as f:       # (np.savez would append .npz to a name without it)
-            np.savez(f, positions=probes.positions, sh=sh, sums=sums, rounds=np.int64(rounds), directions=np.int64(probes.directions),
+            np.savez(f, positions=nominal.positions, sh=sh, sums=sums, rounds=np.int64(rounds), directions=np.int64(probes.directions),
                      samples=np.int64(opt.samples), grid_lo=np.array(probes.grid_lo, np.float64), grid_hi=np.array(probes.grid_hi, np.float64),
                      grid_counts=np.array(probes.grid_counts, np.int64), **extra)
         return 0
     if probe_grid is not None:
         render = renderer.render_probe_lit(scene, probe_grid, probe_sh, opt.aov_samples, device=opt.device, depth=probe_depth, moments=probe_moments,
-                                           normal_bias=0.0 if opt.probe_normal_bias is None else opt.probe_normal_bias).rgb8
+                                           normal_bias=0.0 if opt.probe_normal_bias is None else opt.probe_normal_bias,
+                                           placement=probe_placement).rgb8
         print(f"Finished Rendering in {int(time.time() - start)} s")
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)

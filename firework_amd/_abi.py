@@ -224,5 +224,24 @@ AO_PROTOTYPES = {
 }
 
 
+# probe relocation and classification (include/firework_hip.h: fw_probe_survey, fw_probe_relocate_step, fw_relocate_probes,
+# fw_probe_irradiance_placed, fw_probe_shade_placed)
+class fw_probe_relocate(C.Structure):
+    _fields_ = [("min_front", f32), ("back_fraction", f32), ("max_offset", f32 * 3)]
+
+
+# the five prototypes (argument types; every one returns int), applied by _lib.load
+PROBE_PLACE_PROTOTYPES = {
+    "fw_probe_survey": [C.c_int, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_probe_relocate_step": [C.c_int, C.POINTER(fw_probe_relocate), u32, u32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "fw_relocate_probes": [C.c_void_p, C.POINTER(fw_probe_set), C.POINTER(fw_probe_relocate), C.POINTER(fw_trace_params), u32, u32, C.c_void_p,
+                           C.c_void_p, C.POINTER(fw_stats)],
+    "fw_probe_irradiance_placed": [C.POINTER(fw_probe_grid), C.c_void_p, C.POINTER(fw_probe_depth), C.c_void_p, f32, C.c_void_p, C.c_int, u32,
+                                   C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_probe_shade_placed": [C.POINTER(fw_probe_grid), C.c_void_p, C.POINTER(fw_probe_depth), C.c_void_p, f32, C.c_void_p,
+                              C.POINTER(fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
 def vec3(v):
     return fw_vec3(float(v[0]), float(v[1]), float(v[2]))

@@ -130,7 +130,7 @@ def load(preload=False, device=None):
     lib.fw_probe_shade.restype = C.c_int
     lib.fw_probe_shade.argtypes = [C.POINTER(A.fw_probe_grid), C.c_void_p, C.POINTER(A.fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
-    for name, argtypes in list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()):
+    for name, argtypes in list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()) + list(A.PROBE_PLACE_PROTOTYPES.items()):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
@@ -527,7 +527,28 @@ def _vis_args(depth, moments, normal_bias, n_probes, on_device, device):
     return pd, m.ctypes.data, float(normal_bias), m
 
 
-def probe_irradiance(grid, sh, positions, normals, out=None, stream=None, device=0, _vis=None):
+def _placement_arg(placement, n_probes, on_device, device):
+    """(placement pointer, what keeps it alive) of a _placed call: placement (n, 4) float32 records (ox, oy, oz, a), a device tensor when
+    the call's other arrays are"""
+    if on_device:
+        import torch
+        _check_device_tensor(placement, (n_probes, 4), torch.float32, device, "placement")
+        return placement.data_ptr(), placement
+    m = np.ascontiguousarray(np.asarray(placement, np.float32).reshape(n_probes, 4))
+    return m.ctypes.data, m
+
+
+def _placed_call(fn, g, sh_ptr, vis, placement, n_probes, on_device, device, tail):
+    """fn = fw_probe_irradiance_placed or fw_probe_shade_placed over (grid, sh, pd, moments, normal_bias, placement, *tail); vis None: no
+    visibility (pd and moments NULL)"""
+    pl, _keep_pl = _placement_arg(placement, n_probes, on_device, device)
+    if vis is None:
+        return fn(C.byref(g), sh_ptr, None, None, 0.0, pl, *tail)
+    pd, mom, bias, _keep = _vis_args(*vis, n_probes, on_device, device)
+    return fn(C.byref(g), sh_ptr, C.byref(pd), mom, bias, pl, *tail)
+
+
+def probe_irradiance(grid, sh, positions, normals, out=None, stream=None, device=0, _vis=None, _placed=None):
     """fw_probe_irradiance: the irradiance the probe grid `grid` (an api.ProbeGrid, or an api.ProbeSet made by ProbeSet.grid) with the
     coefficients sh (n, 9, 3) float32 gives at the points `positions` with the normals `normals`, (N, 3) float32 each; not clamped.
     numpy arrays: returns an (N, 3) float32 array (out: a contiguous float32 array of that shape to fill instead).  Torch tensors on
@@ -549,7 +570,9 @@ def probe_irradiance(grid, sh, positions, normals, out=None, stream=None, device
             out = torch.empty((n, 3), dtype=torch.float32, device=positions.device)
         _check_device_tensor(out, (n, 3), torch.float32, device, "out")
         tail = (int(device), n, positions.data_ptr(), normals.data_ptr(), stride, out.data_ptr(), 1, _stream_arg(stream, positions.device))
-        if _vis is not None:
+        if _placed is not None:
+            _check(lib, _placed_call(lib.fw_probe_irradiance_placed, g, sh.data_ptr(), _vis, _placed, n_probes, True, device, tail))
+        elif _vis is not None:
             pd, mom, bias, _keep = _vis_args(*_vis, n_probes, True, device)
             _check(lib, lib.fw_probe_irradiance_vis(C.byref(g), sh.data_ptr(), C.byref(pd), mom, bias, *tail))
         else:
@@ -564,7 +587,9 @@ def probe_irradiance(grid, sh, positions, normals, out=None, stream=None, device
         out = np.empty(p.shape, np.float32)
     _host_f32(out, p.shape, "out")
     tail = (int(device), int(p.shape[0]), p.ctypes.data, nr.ctypes.data, 3, out.ctypes.data, 0, None)
-    if _vis is not None:
+    if _placed is not None:
+        _check(lib, _placed_call(lib.fw_probe_irradiance_placed, g, s.ctypes.data, _vis, _placed, n_probes, False, device, tail))
+    elif _vis is not None:
         pd, mom, bias, _keep = _vis_args(*_vis, n_probes, False, device)
         _check(lib, lib.fw_probe_irradiance_vis(C.byref(g), s.ctypes.data, C.byref(pd), mom, bias, *tail))
     else:
@@ -577,6 +602,78 @@ def probe_irradiance_vis(grid, sh, depth, moments, positions, normals, normal_bi
     api.ProbeDepth, moments (n, R, R, 2) float32 as DeviceScene.bake_probe_depth returns them (a device tensor when the points are),
     normal_bias >= 0 in world units.  Everything else as probe_irradiance."""
     return probe_irradiance(grid, sh, positions, normals, out, stream, device, _vis=(depth, moments, normal_bias))
+
+
+def probe_irradiance_placed(grid, sh, placement, positions, normals, depth=None, moments=None, normal_bias=0.0, out=None, stream=None, device=0):
+    """fw_probe_irradiance_placed: probe_irradiance — or with depth (an api.ProbeDepth) and moments probe_irradiance_vis — over moved and
+    classified probes: placement (n, 4) float32 records (ox, oy, oz, a) as DeviceScene.relocate_probes returns them (a device tensor when
+    the points are).  An inactive probe (a == 0) is skipped and the remaining weights are always normalised.  Everything else as
+    probe_irradiance."""
+    if (depth is None) != (moments is None):
+        raise ValueError("depth and moments are given together or not at all")
+    vis = None if depth is None else (depth, moments, normal_bias)
+    return probe_irradiance(grid, sh, positions, normals, out, stream, device, _vis=vis, _placed=placement)
+
+
+def _hits_arg(hits, total, on_device, device):
+    """(hits pointer, what keeps it alive): a HIT_DTYPE array of `total` records, or an (total, 12) float32 device tensor"""
+    if on_device:
+        import torch
+        _check_device_tensor(hits, (total, 12), torch.float32, device, "hits")
+        return hits.data_ptr(), hits
+    h = np.ascontiguousarray(hits)
+    if h.dtype != HIT_DTYPE or h.shape != (total,):
+        raise ValueError("host hits must be an array of HIT_DTYPE, one record per ray")
+    return h.ctypes.data, h
+
+
+def probe_survey(rays, hits, directions, out=None, device=0, stream=None):
+    """fw_probe_survey: the survey (N, 3, 4) float32 of one round — per probe (back.xyz, dist), (front.xyz, dist) and (n_back, n_front,
+    n_miss, 0) — from rays (N * D, 6) float32 and hits as DeviceScene.trace returns them for those rays: a HIT_DTYPE array for numpy rays,
+    or an (N * D, 12) float32 device tensor for rays on cuda:`device`, surveyed on `stream` (default: the current torch stream) where they
+    lie.  out: an array or tensor of that shape to overwrite instead.  Returns the survey."""
+    lib = load()
+    d = int(directions)
+    total = int(rays.shape[0])
+    if d < 1 or total % d or tuple(rays.shape) != (total, 6) or int(hits.shape[0]) != total:
+        raise ValueError(f"rays must have shape (N * {d}, 6) and hits N * {d} records")
+    n = total // d
+    if type(rays).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
+        h, _keep = _hits_arg(hits, total, True, device)
+        if out is None:
+            out = torch.empty((n, 3, 4), dtype=torch.float32, device=rays.device)
+        _check_device_tensor(out, (n, 3, 4), torch.float32, device, "out")
+        _check(lib, lib.fw_probe_survey(int(device), n, d, rays.data_ptr(), h, out.data_ptr(), 1, _stream_arg(stream, rays.device)))
+        return out
+    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
+    h, _keep = _hits_arg(hits, total, False, device)
+    if out is None:
+        out = np.empty((n, 3, 4), np.float32)
+    _host_f32(out, (n, 3, 4), "out")
+    _check(lib, lib.fw_probe_survey(int(device), n, d, r.ctypes.data, h, out.ctypes.data, 0, None))
+    return out
+
+
+def probe_relocate_step(relocation, survey, placement, directions, move=True, device=0, stream=None):
+    """fw_probe_relocate_step: one step of an api.ProbeRelocation (with a max_offset of its own) over survey (N, 3, 4) and placement (N, 4)
+    float32, which is updated in place and returned: numpy arrays, or contiguous torch tensors on cuda:`device`, stepped on `stream`
+    (default: the current torch stream) where they lie.  move=False writes the state a only."""
+    lib = load()
+    rl = relocation.to_abi()
+    n = int(placement.shape[0])
+    if type(placement).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(survey, (n, 3, 4), torch.float32, device, "survey")
+        _check_device_tensor(placement, (n, 4), torch.float32, device, "placement")
+        _check(lib, lib.fw_probe_relocate_step(int(device), C.byref(rl), n, int(directions), survey.data_ptr(), placement.data_ptr(), int(bool(move)), 1,
+                                               _stream_arg(stream, placement.device)))
+        return placement
+    s = np.ascontiguousarray(np.asarray(survey, np.float32).reshape(n, 3, 4))
+    _host_f32(placement, (n, 4), "placement")
+    _check(lib, lib.fw_probe_relocate_step(int(device), C.byref(rl), n, int(directions), s.ctypes.data, placement.ctypes.data, int(bool(move)), 0, None))
+    return placement
 
 
 def probe_depth_reduce(depth, rays, hits, directions, sums=None, device=0, stream=None):
@@ -612,7 +709,7 @@ def probe_depth_reduce(depth, rays, hits, directions, sums=None, device=0, strea
     return sums
 
 
-def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear"), _vis=None):
+def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear"), _vis=None, _placed=None):
     """fw_probe_shade: fw_render_aovs' records `aov` (N, 12) lit from the probe grid `grid` (see probe_irradiance) with the coefficients
     sh (n, 9, 3): out = albedo (coverage max(E, 0) / pi + (1 - coverage)), resolved as fw_denoise resolves its outputs.  All host arrays
     (numpy): returns (rgb8, gamma, linear) host arrays of shape (N, 3).  Contiguous float32 torch tensors on cuda:`device`: shaded on
@@ -636,7 +733,9 @@ def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, 
         p.stream = _stream_arg(stream, dev)
         ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
         tail = (C.byref(p), aov.data_ptr(), ptr(lin), ptr(gam), ptr(rgb8))
-        if _vis is not None:
+        if _placed is not None:
+            _check(lib, _placed_call(lib.fw_probe_shade_placed, g, sh.data_ptr(), _vis, _placed, n_probes, True, device, tail))
+        elif _vis is not None:
             pd, mom, bias, _keep = _vis_args(*_vis, n_probes, True, device)
             _check(lib, lib.fw_probe_shade_vis(C.byref(g), sh.data_ptr(), C.byref(pd), mom, bias, *tail))
         else:
@@ -649,7 +748,9 @@ def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, 
     lin = np.empty((n, 3), np.float32) if want[2] else None
     ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
     tail = (C.byref(p), a.ctypes.data, ptr(lin), ptr(gam), ptr(rgb8))
-    if _vis is not None:
+    if _placed is not None:
+        _check(lib, _placed_call(lib.fw_probe_shade_placed, g, s.ctypes.data, _vis, _placed, n_probes, False, device, tail))
+    elif _vis is not None:
         pd, mom, bias, _keep = _vis_args(*_vis, n_probes, False, device)
         _check(lib, lib.fw_probe_shade_vis(C.byref(g), s.ctypes.data, C.byref(pd), mom, bias, *tail))
     else:
@@ -661,6 +762,15 @@ def probe_shade_vis(grid, sh, depth, moments, aov, width, height, normal_bias=0.
                     outputs=("rgb8", "gamma", "linear")):
     """fw_probe_shade_vis: probe_shade with the lookup of probe_irradiance_vis (depth, moments, normal_bias: see there)."""
     return probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, _vis=(depth, moments, normal_bias))
+
+
+def probe_shade_placed(grid, sh, placement, aov, width, height, depth=None, moments=None, normal_bias=0.0, gamma=2.2, device=0, stream=None,
+                       outputs=("rgb8", "gamma", "linear")):
+    """fw_probe_shade_placed: probe_shade with the lookup of probe_irradiance_placed (placement, depth, moments, normal_bias: see there)."""
+    if (depth is None) != (moments is None):
+        raise ValueError("depth and moments are given together or not at all")
+    vis = None if depth is None else (depth, moments, normal_bias)
+    return probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, _vis=vis, _placed=placement)
 
 
 def _lightmap_abi(lightmap, chunk=None):
@@ -1215,6 +1325,30 @@ class DeviceScene:
         _check(self._lib, self._lib.fw_bake_probe_depth(self.handle, C.byref(s), C.byref(pd), C.byref(p), int(first_round), int(rounds), *ptrs,
                                                         C.byref(st)))
         return out, sums, st.as_dict()
+
+    def relocate_probes(self, probes, relocation, steps=None, first_step=0, placement=None, seed=0, use_bvh=True, stream=None, rays_per_batch=0,
+                        flags=0, chunk=None):
+        """fw_relocate_probes: the steps [first_step, first_step + steps) of an api.ProbeRelocation (steps None: its own count) over an
+        api.ProbeSet at its nominal positions, then one classifying step; `chunk` probes at a time (None: the set's own setting; 0:
+        automatic).  placement: (N, 4) float32 host records (ox, oy, oz, a), updated in place (None: the neutral (0, 0, 0, 1)).
+        Returns (placement, survey, stats): host arrays always; survey (N, 3, 4) float32 is the classifying step's."""
+        s, _pos = _probe_abi(probes, chunk)
+        rl = relocation.to_abi(probes)
+        n = int(s.n_probes)
+        if placement is None:
+            placement = np.zeros((n, 4), np.float32)
+            placement[:, 3] = 1.0
+        _host_f32(placement, (n, 4), "placement")
+        survey = np.empty((n, 3, 4), np.float32)
+        p = A.fw_trace_params()
+        p.use_bvh, p.flags, p.seed, p.rays_per_batch = int(bool(use_bvh)), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rays_per_batch)
+        if stream is not None:
+            p.stream = C.c_void_p(stream) if stream else None
+        st = A.fw_stats()
+        k = int(relocation.steps if steps is None else steps)
+        _check(self._lib, self._lib.fw_relocate_probes(self.handle, C.byref(s), C.byref(rl), C.byref(p), int(first_step), k, placement.ctypes.data,
+                                                       survey.ctypes.data, C.byref(st)))
+        return placement, survey, st.as_dict()
 
     def bake_ao(self, ao, positions, normals, ids=None, rounds=1, first_round=0, sums=None, out=None, seed=0, use_bvh=True, stream=None,
                 rays_per_batch=0, flags=0, chunk=None):

@@ -1223,6 +1223,16 @@ class ProbeSet:
         o = np.repeat(self.positions.astype(np.float64), D, axis=0)
         return _rays_out(o, d, device)
 
+    def moved(self, placement) -> "ProbeSet":
+        """The set at the moved positions float32((double)position + (double)offset) of a placement (N, 4) (ox, oy, oz, a) — what
+        fw_relocate_probes traces from, and where sh and depth maps are baked for the placed lookups.  Directions, seed, jitter, chunk and
+        the grid are kept: the grid stays the nominal one."""
+        pl = np.asarray(placement, np.float32).reshape(self.n_probes, 4)
+        out = ProbeSet((self.positions.astype(np.float64) + pl[:, 0:3].astype(np.float64)).astype(np.float32), self.directions)
+        out._seed, out._jitter, out.chunk_probes = self._seed, self._jitter, self.chunk_probes
+        out.grid_lo, out.grid_hi, out.grid_counts = self.grid_lo, self.grid_hi, self.grid_counts
+        return out
+
     def to_abi(self):
         """(fw_probe_set, the float32 positions it points into: keep them alive as long as the struct is used)"""
         s = A.fw_probe_set()
@@ -1544,6 +1554,234 @@ def probe_lookup_vis(grid, sh, pd: "ProbeDepth", moments, positions, normals, no
         return E
     X = {k: np.stack(v, axis=-1) for k, v in X.items()}
     X["w"] = np.stack(w, axis=-1)
+    return E, T, X
+
+
+# --------------------------------------------------------------------------- probe relocation and classification
+class ProbeRelocation:
+    """How probes are moved out of geometry (fw_probe_relocate): a probe keeps at least min_front to the nearest front face; one that
+    sees more than back_fraction of back faces is inside geometry and is moved through the nearest of them; no offset may exceed
+    max_offset (three numbers, world units per axis; a move that would is rejected, and the probe ends inactive).  max_offset=None:
+    0.45 x the grid's spacing per axis, on a flat axis the smallest spacing of the other axes — taken from the ProbeSet the relocation is
+    used with.  steps: how many moving steps Renderer.relocate_probes runs before it classifies."""
+
+    def __init__(self, min_front: float, back_fraction: float = 0.25, max_offset=None, steps: int = 4):
+        self.min_front, self.back_fraction = float(np.float32(min_front)), float(np.float32(back_fraction))
+        self.max_offset = None if max_offset is None else tuple(float(np.float32(v)) for v in (max_offset if np.ndim(max_offset) else (max_offset,) * 3))
+        if self.max_offset is not None and len(self.max_offset) != 3:
+            raise ValueError("max_offset must be one number or three")
+        self.steps = int(steps)
+
+    def resolved(self, probes=None) -> "ProbeRelocation":
+        """this relocation with a max_offset of its own: None becomes 0.45 x the spacing of `probes`' grid (a ProbeSet made by
+        ProbeSet.grid, or a ProbeGrid)"""
+        if self.max_offset is not None:
+            return self
+        if probes is None:
+            raise ValueError("max_offset=None needs the probes' grid")
+        return ProbeRelocation(self.min_front, self.back_fraction, tuple(0.45 * v for v in probe_spacing(probes)), self.steps)
+
+    def to_abi(self, probes=None) -> A.fw_probe_relocate:
+        r = self.resolved(probes)
+        a = A.fw_probe_relocate()
+        a.min_front, a.back_fraction = r.min_front, r.back_fraction
+        for k in range(3):
+            a.max_offset[k] = r.max_offset[k]
+        return a
+
+
+def probe_spacing(grid) -> tuple:
+    """the distance between neighbouring probes of a grid (a ProbeGrid, or a ProbeSet made by ProbeSet.grid) per axis; a flat axis takes
+    the smallest spacing of the other axes.  A grid of one probe has none: ValueError."""
+    g = ProbeGrid.of(grid)
+    sp = [abs(g.hi[k] - g.lo[k]) / float(g.counts[k] - 1) if g.counts[k] > 1 else None for k in range(3)]
+    known = [v for v in sp if v is not None]
+    if not known:
+        raise ValueError("a grid of one probe has no spacing: give max_offset")
+    return tuple(v if v is not None else min(known) for v in sp)
+
+
+def neutral_placement(n: int) -> np.ndarray:
+    """(n, 4) float32 records (0, 0, 0, 1): every probe at its nominal position and active"""
+    out = np.zeros((int(n), 4), np.float32)
+    out[:, 3] = 1.0
+    return out
+
+
+def probe_survey(rays, hits_t, hits_normal, hits_object, directions: int, terms: bool = False):
+    """The numpy float64 statement of fw_probe_survey: (N, 3, 4) float64 — (back.xyz, dist), (front.xyz, dist), (n_back, n_front, n_miss,
+    0), the distances before their one rounding to float32 — for rays (N * D, 6) float32 (the directions as stored) and the hits' t
+    (float32), normal (float32, (N * D, 3)) and object (uint32, 0xFFFFFFFF = miss) columns.  terms=True: returns (survey, J) with J (N, 2)
+    int64 the winning ray of each class, -1 for none."""
+    D = int(directions)
+    d32 = np.asarray(rays, np.float32).reshape(-1, D, 6)[..., 3:]
+    d = d32.astype(np.float64)
+    t = np.asarray(hits_t, np.float32).astype(np.float64).reshape(-1, D)
+    nr = np.asarray(hits_normal, np.float32).astype(np.float64).reshape(-1, D, 3)
+    obj = np.asarray(hits_object).astype(np.uint32).reshape(-1, D)
+    n = d.shape[0]
+    rows = np.arange(n)
+    out = np.zeros((n, 3, 4))
+    J = np.full((n, 2), -1, np.int64)
+    with np.errstate(all="ignore"):
+        zero = np.all(d == 0.0, axis=2)
+        miss = ~zero & (obj == np.uint32(0xFFFFFFFF))
+        hit = ~zero & ~miss
+        dist = t * np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+        back = hit & (((nr[..., 0] * d[..., 0] + nr[..., 1] * d[..., 1]) + nr[..., 2] * d[..., 2]) > 0.0)
+        front = hit & ~back
+        for c, m in enumerate((back, front)):
+            dd = np.where(m & ~np.isnan(dist), dist, np.inf)
+            j = np.argmin(dd, axis=1)                      # the first of equal minima: the lowest j
+            dm = dd[rows, j]
+            has = dm < np.inf
+            out[:, c, 0:3] = np.where(has[:, None], d[rows, j], 0.0)
+            out[:, c, 3] = np.where(has, dm, np.inf)
+            J[:, c] = np.where(has, j, -1)
+        out[:, 2, 0], out[:, 2, 1], out[:, 2, 2] = back.sum(axis=1), front.sum(axis=1), miss.sum(axis=1)
+    return (out, J) if terms else out
+
+
+def probe_relocate_step(relocation: "ProbeRelocation", survey, placement, directions: int, move: bool = True) -> np.ndarray:
+    """The numpy statement of fw_probe_relocate_step: the placement (N, 4) float32 after one step of `relocation` (with a max_offset of its
+    own) over the float32 survey (N, 3, 4) and the placement (N, 4) before it, in float64, the candidate rounded to float32 once."""
+    rl = relocation.resolved()
+    sv = np.asarray(survey, np.float32).astype(np.float64).reshape(-1, 3, 4)
+    pl = np.array(np.asarray(placement, np.float32).reshape(-1, 4), np.float32)
+    o = pl[:, 0:3].astype(np.float64)
+    mf = float(np.float32(rl.min_front))
+    inside = sv[:, 2, 0] > float(np.float32(rl.back_fraction)) * float(int(directions))
+    a = np.where(inside, np.float32(0.0), np.float32(1.0)).astype(np.float32)
+    if not move:
+        pl[:, 3] = a
+        return pl
+    with np.errstate(all="ignore"):
+        def unit(v):
+            return v / np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])[:, None]
+        cb = o + unit(sv[:, 0, 0:3]) * (sv[:, 0, 3] + 0.5 * mf)[:, None]
+        cf = o - unit(sv[:, 1, 0:3]) * (mf - sv[:, 1, 3])[:, None]
+        near = ~inside & (sv[:, 2, 1] > 0.0) & (sv[:, 1, 3] < mf)
+        c = np.where(inside[:, None], cb, np.where(near[:, None], cf, o)).astype(np.float32)
+        lim = np.asarray([float(np.float32(v)) for v in rl.max_offset])
+        ok = np.all(np.abs(c.astype(np.float64)) <= lim[None, :], axis=1)
+    pl[:, 0:3] = np.where(ok[:, None], c, pl[:, 0:3])
+    pl[:, 3] = a
+    return pl
+
+
+def probe_lookup_placed(grid, sh, placement, positions, normals, pd: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0,
+                        terms: bool = False):
+    """The numpy float64 statement of fw_probe_irradiance_placed (include/firework_hip.h): probe_lookup — with pd and moments
+    probe_lookup_vis — where a corner's probe stands at P + o, a corner whose a is 0 is skipped (nothing of it enters a sum) and the
+    remaining weights are always divided by their sum; no active corner, or a sum of 0, gives zeros.  placement (n, 4) float32.
+    terms=True: returns (E, T, X) as probe_lookup_vis does, X with "w" and "active" always and the visibility terms when pd is given;
+    a skipped corner's entries are 0."""
+    g = ProbeGrid.of(grid)
+    vis = pd is not None
+    if vis != (moments is not None):
+        raise ValueError("pd and moments are given together or not at all")
+    sh = np.asarray(sh, np.float32).astype(np.float64).reshape(g.n_probes, 9, 3)
+    pl = np.asarray(placement, np.float32).reshape(g.n_probes, 4)
+    off, state = pl[:, 0:3].astype(np.float64), pl[:, 3]
+    if vis:
+        R = int(pd.resolution)
+        mom = np.asarray(moments, np.float32).reshape(g.n_probes, R, R, 2)
+    p = np.asarray(positions, np.float32).astype(np.float64).reshape(-1, 3)
+    nr = np.asarray(normals, np.float32).astype(np.float64).reshape(-1, 3)
+    bias = float(np.float32(normal_bias))
+    n = p.shape[0]
+    E, T = np.zeros((n, 3)), np.zeros((n, 3))
+    with np.errstate(all="ignore"):
+        nl2 = (nr[:, 0] * nr[:, 0] + nr[:, 1] * nr[:, 1]) + nr[:, 2] * nr[:, 2]
+        ok = np.all(np.isfinite(p), axis=1) & np.all(np.isfinite(nr), axis=1) & (nl2 > 0.0)
+        nl = np.sqrt(nl2)
+        nh = np.where(ok[:, None], nr / nl[:, None], 0.0)
+        p = np.where(ok[:, None], p, 0.0)
+        x, y, z = nh[:, 0], nh[:, 1], nh[:, 2]
+        q = p + bias * nh if vis else p
+        idx, f, two = [], [], []
+        for k in range(3):
+            c = g.counts[k]
+            two.append(c > 1)
+            if c > 1:
+                cm1 = float(c - 1)
+                s = ((p[:, k] - g.lo[k]) / (g.hi[k] - g.lo[k])) * cm1
+                s = np.fmin(np.fmax(s, 0.0), cm1)
+                fl = np.fmin(np.floor(s), cm1 - 1.0)
+                idx.append(fl.astype(np.int64))
+                f.append(s - fl)
+            else:
+                idx.append(np.zeros(n, np.int64))
+                f.append(np.zeros(n))
+        corners = [(dx, dy, dz) for dz in range(2 if two[2] else 1) for dy in range(2 if two[1] else 1) for dx in range(2 if two[0] else 1)]
+        w, act = [], []
+        X = {k: [] for k in ("fac", "v", "g", "dist", "mu", "mu2", "m1", "m2")}
+        wsum = np.zeros(n)
+        for d in corners:
+            probe = ((idx[2] + d[2]) * g.counts[1] + (idx[1] + d[1])) * g.counts[0] + (idx[0] + d[0])
+            on = state[probe] != 0.0
+            wk = [f[k] if d[k] else 1.0 - f[k] for k in range(3)]
+            P = []
+            for k in range(3):
+                if two[k]:
+                    nominal = g.lo[k] + (idx[k] + d[k]).astype(np.float64) * ((g.hi[k] - g.lo[k]) / float(g.counts[k] - 1))
+                else:
+                    nominal = np.full(n, 0.5 * (g.lo[k] + g.hi[k]))
+                P.append(nominal + off[probe, k])
+            fac = np.ones(n)
+            if g.wrap:
+                r = [P[k] - p[:, k] for k in range(3)]
+                rl2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]
+                rl = np.sqrt(rl2)
+                dot = (x * (r[0] / rl) + y * (r[1] / rl)) + z * (r[2] / rl)
+                h = 0.5 * (dot + 1.0)
+                fac = np.where(rl2 > 0.0, h * h + 0.2, 1.2)
+            wd = (wk[0] * wk[1]) * wk[2]
+            if vis:
+                rv = [q[:, k] - P[k] for k in range(3)]
+                dist = np.sqrt((rv[0] * rv[0] + rv[1] * rv[1]) + rv[2] * rv[2])
+                safe = np.where(dist != 0.0, dist, 1.0)
+                dirs = np.stack([np.where(dist != 0.0, rv[k] / safe, (0.0, 0.0, 1.0)[k]) for k in range(3)], axis=-1)
+                mu, mu2 = probe_depth_fetch(R, mom[probe], dirs)
+                var = np.abs(mu * mu - mu2)
+                t = dist - mu
+                c = var / (var + t * t)
+                v = np.where((dist == 0.0) | (dist <= mu), 1.0, (c * c) * c)
+                gg = np.fmax(1e-6, fac * v)
+                gg = np.where(gg < 0.2, (gg * (gg * gg)) * 25.0, gg)
+                wd = wd * gg
+                if terms:
+                    am = np.abs(mom.astype(np.float64)).reshape(g.n_probes, -1, 2).max(axis=1)
+                    for name, val in (("fac", fac), ("v", v), ("g", gg), ("dist", dist), ("mu", mu), ("mu2", mu2), ("m1", am[probe, 0]),
+                                      ("m2", am[probe, 1])):
+                        X[name].append(np.where(on, val, 0.0))
+            elif g.wrap:
+                wd = wd * fac
+            wd = np.where(on, wd, 0.0)
+            wsum = np.where(on, wsum + wd, wsum)
+            w.append(wd)
+            act.append(on)
+        some = ok & (wsum != 0.0)
+        w = [np.where(some, wd / np.where(some, wsum, 1.0), 0.0) for wd in w]
+        B = sh_basis(nh) * _SH_COSINE
+        for d, wd, on in zip(corners, w, act):
+            probe = ((idx[2] + d[2]) * g.counts[1] + (idx[1] + d[1])) * g.counts[0] + (idx[0] + d[0])
+            c = sh[probe]                                                  # (N, 9, 3)
+            e = B[:, 0, None] * c[:, 0]
+            t = np.abs(e)
+            for k in range(1, 9):
+                term = B[:, k, None] * c[:, k]
+                e = e + term
+                t = t + np.abs(term)
+            E = np.where(on[:, None], E + wd[:, None] * e, E)
+            T = np.where(on[:, None], T + np.abs(wd)[:, None] * t, T)
+    E[~some] = 0.0
+    T[~some] = 0.0
+    if not terms:
+        return E
+    X = {k: np.stack(v, axis=-1) for k, v in X.items() if v}
+    X["w"] = np.stack(w, axis=-1)
+    X["active"] = np.stack(act, axis=-1)
     return E, T, X
 
 
@@ -2312,6 +2550,25 @@ class Renderer:
             if ds is not scene:
                 ds.close()
 
+    def relocate_probes(self, scene, probes: "ProbeSet", relocation: "ProbeRelocation", first_step: int = 0, placement=None, chunk=None,
+                        device: int = 0, stream=None):
+        """Probes moved out of geometry and classified on the device (not in the reference; fw_relocate_probes):
+        relocation.steps moving steps from `first_step`, each tracing the set's rays from the moved positions with this renderer's seed
+        (+ the step), use_bvh and flags, then one classifying step.  Returns (placement, survey): (N, 4) float32 records (ox, oy, oz, a)
+        and the classifying step's survey (N, 3, 4) float32; pass placement back with first_step = the steps it holds to go on.  Bake sh
+        and depth maps at probes.moved(placement) and hand placement to render_probe_lit.  The call's stats are kept in
+        self.probe_place_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        from . import _lib
+        s = self.settings
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            placement, survey, self.probe_place_stats = ds.relocate_probes(probes, relocation, None, first_step, placement, seed=s["seed"],
+                                                                           use_bvh=s["use_bvh"], stream=stream, flags=s["flags"], chunk=chunk)
+            return placement, survey
+        finally:
+            if ds is not scene:
+                ds.close()
+
     def bake_lightmap(self, scene, lightmap: "Lightmap", rounds: int = 1, dilate: int = 2, first_round: int = 0, sums=None, chunk=None,
                       device: int = 0, stream=None, on_device: bool = False):
         """A lightmap baked on the device (not in the reference; fw_bake_lightmap): `rounds` rounds of the lightmap's cosine-weighted
@@ -2384,7 +2641,7 @@ class Renderer:
 
     def render_probe_lit(self, scene, probes, sh, aov_samples: int = 8, wrap: bool = True, device: int = 0, model: "CameraModel" = None,
                          depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0, ao: "AmbientOcclusion" = None,
-                         ao_rounds: int = 1) -> RenderResult:
+                         ao_rounds: int = 1, placement=None) -> RenderResult:
         """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
         (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
         from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
@@ -2396,7 +2653,9 @@ class Renderer:
         rounds on the records in place; the irradiance E is looked up by fw_probe_irradiance (with depth: fw_probe_irradiance_vis) along
         the bent normal where it is not (0, 0, 0) and along the record's normal elsewhere, and not clamped; the frame is
         out_c = a_c (v (ao (E_c float32(1 / pi))) + (1 - v)) in float32, resolved by fw_denoise at 0 iterations.  ao=None: the calls and
-        the bits above."""
+        the bits above.  placement ((n, 4), as relocate_probes returns it): the frame is shaded by fw_probe_shade_placed
+        — with ao, E is looked up by fw_probe_irradiance_placed — with or without depth; sh and moments are expected to have been baked
+        at probes.moved(placement).  placement=None: the calls and the bits above."""
         import torch
         from . import _lib
         if depth is not None and moments is None:
@@ -2419,18 +2678,25 @@ class Renderer:
             if depth is not None:
                 R = int(depth.resolution)
                 d_mom = torch.from_numpy(np.ascontiguousarray(np.asarray(moments, np.float32).reshape(grid.n_probes, R, R, 2))).to(dev)
+            d_pl = None
+            if placement is not None:
+                d_pl = torch.from_numpy(np.ascontiguousarray(np.asarray(placement, np.float32).reshape(grid.n_probes, 4))).to(dev)
             if ao is not None:
                 occ, _sums, self.ao_stats = ds.bake_ao(ao, aov[:, 8:11], aov[:, 4:7], None, ao_rounds, seed=s["seed"], use_bvh=s["use_bvh"],
                                                        flags=s["flags"])
                 bent = torch.any(occ[:, 0:3] != 0, dim=1, keepdim=True)
                 pos, nrm = aov[:, 8:11].contiguous(), torch.where(bent, occ[:, 0:3], aov[:, 4:7]).contiguous()
-                if depth is not None:
+                if d_pl is not None:
+                    E = _lib.probe_irradiance_placed(grid, d_sh, d_pl, pos, nrm, depth, d_mom, normal_bias, device=ds.device)
+                elif depth is not None:
                     E = _lib.probe_irradiance_vis(grid, d_sh, depth, d_mom, pos, nrm, normal_bias, device=ds.device)
                 else:
                     E = _lib.probe_irradiance(grid, d_sh, pos, nrm, device=ds.device)
                 v = aov[:, 3:4]
                 lit = aov[:, 0:3] * (v * (occ[:, 3:4] * (E * float(np.float32(1.0 / np.pi)))) + (1.0 - v))
                 rgb8, gam, lin = _lib.denoise(lit.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
+            elif d_pl is not None:
+                rgb8, gam, lin = _lib.probe_shade_placed(grid, d_sh, d_pl, aov, w, h, depth, d_mom, normal_bias, s["gamma"], ds.device)
             elif depth is not None:
                 rgb8, gam, lin = _lib.probe_shade_vis(grid, d_sh, depth, d_mom, aov, w, h, normal_bias, s["gamma"], ds.device)
             else:

@@ -17,6 +17,7 @@
 #include "fw_probe_lookup.h"
 #include "fw_probe_depth.h"
 #include "fw_ao.h"
+#include "fw_probe_place.h"
 #include "fw_defer_pretest.h"
 
 #include <algorithm>
@@ -4352,6 +4353,8 @@ int probe_depth_check(const fw_probe_depth *pd) {
 }
 // What the _vis calls add to fw_probe_irradiance's and fw_probe_shade's arguments; NULL: the call without visibility
 struct ProbeVis { const fw_probe_depth *pd; const float *moments; float normal_bias; };
+// What the _placed calls add; NULL: the call over the nominal grid.  In a placed call vis may be NULL: no visibility.
+struct ProbePlaced { const float *placement; };
 int probe_vis_check(const ProbeVis *vis) {
     if (int rc = probe_depth_check(vis->pd)) return rc;
     if (!std::isfinite(vis->normal_bias) || vis->normal_bias < 0.f) return fail(FW_ERR_BAD_ARG, "normal_bias must be finite and >= 0");
@@ -4365,8 +4368,10 @@ inline bool probe_vis_too_large(const ProbeVis *vis, const fw::DProbeGrid &g) { 
 // allocation per call holds sh and a slab of points (24 B in, 12 B out each), released on every way out.  vis: fw_probe_irradiance_vis —
 // the moments are one more array, staged after sh.
 int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device, uint32_t n, const float *positions, const float *normals,
-                          uint32_t stride, float *irradiance, int on_device, void *stream_, const ProbeVis *vis = nullptr) {
-    if (!grid || !sh || !positions || !normals || !irradiance || (vis && (!vis->pd || !vis->moments))) return fail(FW_ERR_BAD_ARG, "null argument");
+                          uint32_t stride, float *irradiance, int on_device, void *stream_, const ProbeVis *vis = nullptr,
+                          const ProbePlaced *pl = nullptr) {
+    if (!grid || !sh || !positions || !normals || !irradiance || (vis && (!vis->pd || !vis->moments)) || (pl && !pl->placement))
+        return fail(FW_ERR_BAD_ARG, "null argument");
     if (vis) if (int rc = probe_vis_check(vis)) return rc;
     bool too_large = false;
     fw::DProbeGrid g{};
@@ -4374,18 +4379,24 @@ int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device
     if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
     if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
     if (device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
-    if (on_device && (((uintptr_t)sh | (uintptr_t)positions | (uintptr_t)normals | (uintptr_t)irradiance | (uintptr_t)(vis ? vis->moments : nullptr)) & 3u))
+    if (on_device && (((uintptr_t)sh | (uintptr_t)positions | (uintptr_t)normals | (uintptr_t)irradiance | (uintptr_t)(vis ? vis->moments : nullptr) |
+                       (uintptr_t)(pl ? pl->placement : nullptr)) & 3u))
         return fail(FW_ERR_BAD_ARG, "device arrays must be 4-byte aligned");
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
     if (probe_vis_too_large(vis, g)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const auto launch = [&](const float *d_sh, const float *d_mom, uint32_t k, const float *pos, const float *nrm, uint32_t st, float *out) {
-        if (vis) fw::launch_probe_irradiance_vis(stream, g, fw::DProbeVis{d_mom, (double)vis->normal_bias, vis->pd->resolution}, d_sh, k, pos, nrm, st, out);
+    const auto launch = [&](const float *d_sh, const float *d_mom, const float *d_pl, uint32_t k, const float *pos, const float *nrm, uint32_t st,
+                            float *out) {
+        if (pl) {
+            const fw::DProbeVis v{d_mom, vis ? (double)vis->normal_bias : 0.0, vis ? vis->pd->resolution : 0u};
+            fw::launch_probe_irradiance_placed(stream, g, vis ? &v : nullptr, d_sh, d_pl, k, pos, nrm, st, out);
+        }
+        else if (vis) fw::launch_probe_irradiance_vis(stream, g, fw::DProbeVis{d_mom, (double)vis->normal_bias, vis->pd->resolution}, d_sh, k, pos, nrm, st, out);
         else fw::launch_probe_irradiance(stream, g, d_sh, k, pos, nrm, st, out);
     };
     if (on_device) {
-        launch(sh, vis ? vis->moments : nullptr, n, positions, normals, stride, irradiance);
+        launch(sh, vis ? vis->moments : nullptr, pl ? pl->placement : nullptr, n, positions, normals, stride, irradiance);
         HIPCHK(hipStreamSynchronize(stream));
         HIPCHK(hipGetLastError());
         return FW_OK;
@@ -4393,7 +4404,8 @@ int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device
     const size_t n_probes = (size_t)g.counts[0] * g.counts[1] * g.counts[2];
     const size_t sh_bytes = n_probes * 108, mom_bytes = vis ? n_probes * vis->pd->resolution * vis->pd->resolution * 8 : 0;
     const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 36));
-    const size_t o_mom = align256(sh_bytes), o_in = o_mom + align256(mom_bytes), o_out = o_in + align256((size_t)per * 24);
+    const size_t pl_bytes = pl ? n_probes * 16 : 0;
+    const size_t o_mom = align256(sh_bytes), o_pl = o_mom + align256(mom_bytes), o_in = o_pl + align256(pl_bytes), o_out = o_in + align256((size_t)per * 24);
     std::vector<float> pack((size_t)per * 6);
     CallScratch scratch(device);
     if (int rc = scratch.alloc(o_out + (size_t)per * 12)) return rc;
@@ -4401,6 +4413,7 @@ int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device
     const float *d_in = (const float *)(base + o_in);
     HIPCHK(hipMemcpyAsync(base, sh, sh_bytes, hipMemcpyHostToDevice, stream));
     if (vis) HIPCHK(hipMemcpyAsync(base + o_mom, vis->moments, mom_bytes, hipMemcpyHostToDevice, stream));
+    if (pl) HIPCHK(hipMemcpyAsync(base + o_pl, pl->placement, pl_bytes, hipMemcpyHostToDevice, stream));
     for (uint32_t done = 0; done < n; done += per) {
         const uint32_t k = std::min(per, n - done);
         for (uint32_t i = 0; i < k; i++) {
@@ -4409,7 +4422,7 @@ int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device
             o[0] = ps[0]; o[1] = ps[1]; o[2] = ps[2]; o[3] = ns[0]; o[4] = ns[1]; o[5] = ns[2];
         }
         HIPCHK(hipMemcpyAsync(base + o_in, pack.data(), (size_t)k * 24, hipMemcpyHostToDevice, stream));
-        launch((const float *)base, (const float *)(base + o_mom), k, d_in, d_in + 3, 6, (float *)(base + o_out));
+        launch((const float *)base, (const float *)(base + o_mom), (const float *)(base + o_pl), k, d_in, d_in + 3, 6, (float *)(base + o_out));
         HIPCHK(hipMemcpyAsync(irradiance + (size_t)done * 3, base + o_out, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
     }
@@ -4420,8 +4433,8 @@ int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device
 // fw_probe_shade: as fw_probe_irradiance; a host call's slab holds 48 B of record and up to 27 B of outputs per pixel.  vis:
 // fw_probe_shade_vis.
 int probe_shade_impl(const fw_probe_grid *grid, const float *sh, const fw_probe_shade_params *p, const float *aov, float *linear_rgb,
-                     float *gamma_rgb, uint8_t *rgb8, const ProbeVis *vis = nullptr) {
-    if (!grid || !sh || !p || !aov || (vis && (!vis->pd || !vis->moments))) return fail(FW_ERR_BAD_ARG, "null argument");
+                     float *gamma_rgb, uint8_t *rgb8, const ProbeVis *vis = nullptr, const ProbePlaced *pl = nullptr) {
+    if (!grid || !sh || !p || !aov || (vis && (!vis->pd || !vis->moments)) || (pl && !pl->placement)) return fail(FW_ERR_BAD_ARG, "null argument");
     if (!linear_rgb && !gamma_rgb && !rgb8) return fail(FW_ERR_BAD_ARG, "at least one output is needed");
     if (vis) if (int rc = probe_vis_check(vis)) return rc;
     bool too_large = false;
@@ -4433,6 +4446,7 @@ int probe_shade_impl(const fw_probe_grid *grid, const float *sh, const fw_probe_
     if (p->on_device && (((uintptr_t)aov & 15u) || (((uintptr_t)sh | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb) & 3u)))
         return fail(FW_ERR_BAD_ARG, "device aov must be 16-byte aligned, device sh, linear_rgb and gamma_rgb 4-byte aligned");
     if (vis && p->on_device && ((uintptr_t)vis->moments & 3u)) return fail(FW_ERR_BAD_ARG, "device moments must be 4-byte aligned");
+    if (pl && p->on_device && ((uintptr_t)pl->placement & 3u)) return fail(FW_ERR_BAD_ARG, "device placement must be 4-byte aligned");
     const uint64_t full = (uint64_t)p->width * p->height;
     if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
     if (probe_vis_too_large(vis, g)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
@@ -4441,12 +4455,17 @@ int probe_shade_impl(const fw_probe_grid *grid, const float *sh, const fw_probe_
     if (int rc = use_device(dev)) return rc;
     hipStream_t stream = (hipStream_t)p->stream;
     const uint32_t n = (uint32_t)full;
-    const auto launch = [&](const float *d_sh, const float *d_mom, uint32_t k, const float *d_aov, uint8_t *o8, float *og, float *ol) {
-        if (vis) fw::launch_probe_shade_vis(stream, g, fw::DProbeVis{d_mom, (double)vis->normal_bias, vis->pd->resolution}, d_sh, k, d_aov, p->gamma, o8, og, ol);
+    const auto launch = [&](const float *d_sh, const float *d_mom, const float *d_pl, uint32_t k, const float *d_aov, uint8_t *o8, float *og,
+                            float *ol) {
+        if (pl) {
+            const fw::DProbeVis v{d_mom, vis ? (double)vis->normal_bias : 0.0, vis ? vis->pd->resolution : 0u};
+            fw::launch_probe_shade_placed(stream, g, vis ? &v : nullptr, d_sh, d_pl, k, d_aov, p->gamma, o8, og, ol);
+        }
+        else if (vis) fw::launch_probe_shade_vis(stream, g, fw::DProbeVis{d_mom, (double)vis->normal_bias, vis->pd->resolution}, d_sh, k, d_aov, p->gamma, o8, og, ol);
         else fw::launch_probe_shade(stream, g, d_sh, k, d_aov, p->gamma, o8, og, ol);
     };
     if (p->on_device) {
-        launch(sh, vis ? vis->moments : nullptr, n, aov, rgb8, gamma_rgb, linear_rgb);
+        launch(sh, vis ? vis->moments : nullptr, pl ? pl->placement : nullptr, n, aov, rgb8, gamma_rgb, linear_rgb);
         HIPCHK(hipStreamSynchronize(stream));
         HIPCHK(hipGetLastError());
         return FW_OK;
@@ -4456,17 +4475,19 @@ int probe_shade_impl(const fw_probe_grid *grid, const float *sh, const fw_probe_
     const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 75));
     size_t off = 0;
     auto put = [&](size_t b) { const size_t at = off; off += align256(b); return at; };
-    const size_t o_sh = put(sh_bytes), o_mom = put(mom_bytes), o_aov = put((size_t)per * 48);
+    const size_t pl_bytes = pl ? n_probes * 16 : 0;
+    const size_t o_sh = put(sh_bytes), o_mom = put(mom_bytes), o_pl = put(pl_bytes), o_aov = put((size_t)per * 48);
     const size_t o_lin = linear_rgb ? put((size_t)per * 12) : 0, o_gam = gamma_rgb ? put((size_t)per * 12) : 0, o_8 = rgb8 ? put((size_t)per * 3) : 0;
     CallScratch scratch(dev);
     if (int rc = scratch.alloc(off)) return rc;
     uint8_t *base = (uint8_t *)scratch.p;
     HIPCHK(hipMemcpyAsync(base + o_sh, sh, sh_bytes, hipMemcpyHostToDevice, stream));
     if (vis) HIPCHK(hipMemcpyAsync(base + o_mom, vis->moments, mom_bytes, hipMemcpyHostToDevice, stream));
+    if (pl) HIPCHK(hipMemcpyAsync(base + o_pl, pl->placement, pl_bytes, hipMemcpyHostToDevice, stream));
     for (uint32_t done = 0; done < n; done += per) {
         const uint32_t k = std::min(per, n - done);
         HIPCHK(hipMemcpyAsync(base + o_aov, aov + (size_t)done * 12, (size_t)k * 48, hipMemcpyHostToDevice, stream));
-        launch((const float *)(base + o_sh), (const float *)(base + o_mom), k, (const float *)(base + o_aov),
+        launch((const float *)(base + o_sh), (const float *)(base + o_mom), (const float *)(base + o_pl), k, (const float *)(base + o_aov),
                rgb8 ? base + o_8 : nullptr, gamma_rgb ? (float *)(base + o_gam) : nullptr, linear_rgb ? (float *)(base + o_lin) : nullptr);
         if (linear_rgb) HIPCHK(hipMemcpyAsync(linear_rgb + (size_t)done * 3, base + o_lin, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
         if (gamma_rgb) HIPCHK(hipMemcpyAsync(gamma_rgb + (size_t)done * 3, base + o_gam, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
@@ -4600,6 +4621,159 @@ int bake_probe_depth_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe_de
             HIPCHK(hipStreamSynchronize(stream));
         }
     }
+    if (stats) {
+        *stats = total;
+        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FW_OK;
+}
+
+// ---- probe relocation and classification (include/firework_hip.h) -------------------------------------------------
+// A relocation's own argument checks (FW_ERR_BAD_ARG only) and what the step kernel needs of it
+int probe_relocate_check(const fw_probe_relocate *rl, fw::DRelocate &d) {
+    if (!std::isfinite(rl->min_front) || !(rl->min_front > 0.f)) return fail(FW_ERR_BAD_ARG, "min_front must be finite and > 0");
+    if (!(rl->back_fraction >= 0.f && rl->back_fraction <= 1.f)) return fail(FW_ERR_BAD_ARG, "back_fraction must be in [0, 1]");
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(rl->max_offset[k]) || rl->max_offset[k] < 0.f) return fail(FW_ERR_BAD_ARG, "every max_offset must be finite and >= 0");
+    d.min_front = (double)rl->min_front;
+    d.back_fraction = (double)rl->back_fraction;
+    for (int k = 0; k < 3; k++) d.max_offset[k] = (double)rl->max_offset[k];
+    return FW_OK;
+}
+
+// fw_probe_survey: fw_probe_depth_reduce's shape; the survey is overwritten, so a host caller's is not uploaded
+int probe_survey_impl(int device, uint32_t n_probes, uint32_t directions, const float *rays, const fw_hit *hits, float *survey, int on_device,
+                      void *stream_) {
+    if (!rays || !hits || !survey) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (n_probes == 0) return fail(FW_ERR_BAD_ARG, "n_probes must be > 0");
+    if (directions == 0 || directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (on_device && ((((uintptr_t)survey | (uintptr_t)hits) & 15u) || ((uintptr_t)rays & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device survey and hits must be 16-byte aligned, device rays 4-byte aligned");
+    if ((uint64_t)n_probes * directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n = (size_t)n_probes * directions, survey_bytes = (size_t)n_probes * 48;
+    CallScratch scratch(device);
+    const float *d_rays = rays; const fw_hit *d_hits = hits; float *d_survey = survey;
+    if (!on_device) {
+        const size_t o_hits = align256(n * 24), o_survey = o_hits + align256(n * sizeof(fw_hit));
+        if (int rc = scratch.alloc(o_survey + survey_bytes)) return rc;
+        uint8_t *base = (uint8_t *)scratch.p;
+        HIPCHK(hipMemcpyAsync(base, rays, n * 24, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_hits, hits, n * sizeof(fw_hit), hipMemcpyHostToDevice, stream));
+        d_rays = (const float *)base; d_hits = (const fw_hit *)(base + o_hits); d_survey = (float *)(base + o_survey);
+    }
+    fw::launch_probe_survey(stream, device_cus(device), n_probes, directions, d_rays, d_hits, d_survey);
+    if (!on_device) HIPCHK(hipMemcpyAsync(survey, d_survey, survey_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_probe_relocate_step: the same shape over the survey (read) and the placement (read and written)
+int probe_relocate_step_impl(int device, const fw_probe_relocate *rl, uint32_t n_probes, uint32_t directions, const float *survey, float *placement,
+                             int move, int on_device, void *stream_) {
+    if (!rl || !survey || !placement) return fail(FW_ERR_BAD_ARG, "null argument");
+    fw::DRelocate L{};
+    if (int rc = probe_relocate_check(rl, L)) return rc;
+    if (n_probes == 0) return fail(FW_ERR_BAD_ARG, "n_probes must be > 0");
+    if (directions == 0 || directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (on_device && (((uintptr_t)survey | (uintptr_t)placement) & 15u)) return fail(FW_ERR_BAD_ARG, "device survey and placement must be 16-byte aligned");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t survey_bytes = (size_t)n_probes * 48, place_bytes = (size_t)n_probes * 16;
+    CallScratch scratch(device);
+    const float *d_survey = survey; float *d_place = placement;
+    if (!on_device) {
+        const size_t o_place = align256(survey_bytes);
+        if (int rc = scratch.alloc(o_place + place_bytes)) return rc;
+        uint8_t *base = (uint8_t *)scratch.p;
+        HIPCHK(hipMemcpyAsync(base, survey, survey_bytes, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_place, placement, place_bytes, hipMemcpyHostToDevice, stream));
+        d_survey = (const float *)base; d_place = (float *)(base + o_place);
+    }
+    fw::launch_probe_relocate_step(stream, L, n_probes, directions, d_survey, d_place, move ? 1 : 0);
+    if (!on_device) HIPCHK(hipMemcpyAsync(placement, d_place, place_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_relocate_probes: bake_probe_depth_impl's loop with the survey and the step in the reduction's place.  Its own are the argument
+// checks, the scratch (the moved positions, a chunk's rays and hits, the survey and the placement), and the moved positions, formed on the
+// host before every step from the placement the step before it copied back.  The scratch is released on every way out; on an error the
+// stream is drained.  (The loop repeats bake_probe_depth_impl's: one trace-round driver for the trace bakes is a follow-up.)
+int relocate_probes_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe_relocate *rl, const fw_trace_params *tp, uint32_t first_step,
+                         uint32_t steps, float *placement, float *survey, fw_stats *stats) {
+    if (!sc || !s || !rl || !tp || !placement) return fail(FW_ERR_BAD_ARG, "null argument");
+    bool too_large = false;
+    if (int rc = probe_set_check(s, too_large)) return rc;
+    fw::DRelocate L{};
+    if (int rc = probe_relocate_check(rl, L)) return rc;
+    const uint32_t N = s->n_probes, D = s->directions;
+    for (uint64_t i = 0; i < (uint64_t)N; i++) {
+        const float *r = placement + i * 4;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]) || !(r[3] == 0.f || r[3] == 1.f))
+            return fail(FW_ERR_BAD_ARG, "placement " + std::to_string(i) + " must have a finite offset and a state of 0 or 1");
+    }
+    if ((uint64_t)first_step + steps + 1 > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_step + steps + 1 overflows");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
+    if (int rc = need_device()) return rc;
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)tp->stream;
+    const uint32_t chunk = std::min<uint32_t>(N, s->chunk_probes ? s->chunk_probes : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 72)));
+    const size_t o_rays = align256((size_t)N * 12), o_hits = o_rays + align256((size_t)chunk * D * 24),
+                 o_survey = o_hits + align256((size_t)chunk * D * sizeof(fw_hit)), o_place = o_survey + align256((size_t)N * 48);
+    CallScratch scratch(dev);
+    if (int rc = scratch.alloc(o_place + (size_t)N * 16)) return rc;
+    uint8_t *base = (uint8_t *)scratch.p;
+    const float *d_pos = (const float *)base;
+    float *d_rays = (float *)(base + o_rays), *d_survey = (float *)(base + o_survey), *d_place = (float *)(base + o_place);
+    fw_hit *d_hits = (fw_hit *)(base + o_hits);
+    HIPCHK(hipMemcpyAsync(d_place, placement, (size_t)N * 16, hipMemcpyHostToDevice, stream));
+    const int n_cus = device_cus(dev);
+    fw_stats total{};
+    CallEvents<4> ev;                                     // around the kernels' launches
+    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
+    std::vector<float> moved((size_t)N * 3);
+    for (uint32_t i = 0; i <= steps; i++) {               // the last one classifies: move = 0
+        const uint32_t st = first_step + i;
+        const int move = i < steps ? 1 : 0;
+        for (size_t q = 0; q < (size_t)N; q++)
+            for (int k = 0; k < 3; k++) moved[q * 3 + k] = (float)((double)s->positions[q * 3 + k] + (double)placement[q * 4 + k]);
+        HIPCHK(hipMemcpyAsync(base, moved.data(), (size_t)N * 12, hipMemcpyHostToDevice, stream));
+        fw_trace_params q = *tp;
+        q.on_device = 1; q.seed = tp->seed + st;
+        for (uint32_t p0 = 0; p0 < N; p0 += chunk) {
+            const uint32_t k = std::min(chunk, N - p0);
+            q.key_base = p0 * D;
+            if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
+            fw::launch_probe_rays(stream, n_cus, probes_device(s, st, p0, d_pos + (size_t)p0 * 3), k, d_rays);
+            if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
+            fw_stats ts{};
+            if (int rc = trace_impl(sc, &q, d_rays, k * D, d_hits, stats ? &ts : nullptr)) { (void)hipStreamSynchronize(stream); return rc; }
+            if (stats) HIPCHK(hipEventRecord(ev.e[2], stream));
+            fw::launch_probe_survey(stream, n_cus, k, D, d_rays, d_hits, d_survey + (size_t)p0 * 12);
+            fw::launch_probe_relocate_step(stream, L, k, D, d_survey + (size_t)p0 * 12, d_place + (size_t)p0 * 4, move);
+            if (!stats) continue;
+            HIPCHK(hipEventRecord(ev.e[3], stream));
+            HIPCHK(hipEventSynchronize(ev.e[3]));
+            float gen_ms = 0.f, red_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
+            HIPCHK(hipEventElapsedTime(&red_ms, ev.e[2], ev.e[3]));
+            stats_add(total, ts);
+            total.ms_render += gen_ms + red_ms;
+            if (tp->flags & FW_FLAG_TIME_KERNELS) { total.ms_raygen += gen_ms; total.ms_accumulate += red_ms; }
+        }
+        // the placement comes back after every step: the next one's positions are formed from it
+        HIPCHK(hipMemcpyAsync(placement, d_place, (size_t)N * 16, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    if (survey) HIPCHK(hipMemcpyAsync(survey, d_survey, (size_t)N * 48, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
     if (stats) {
         *stats = total;
         stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
@@ -5343,6 +5517,53 @@ int fw_probe_shade_vis(const fw_probe_grid *grid, const float *sh, const fw_prob
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_vis"); }
+}
+
+int fw_probe_survey(int device, uint32_t n_probes, uint32_t directions, const float *rays, const fw_hit *hits, float *survey, int on_device,
+                    void *stream) {
+    try { return probe_survey_impl(device, n_probes, directions, rays, hits, survey, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_survey"); }
+}
+
+int fw_probe_relocate_step(int device, const fw_probe_relocate *rl, uint32_t n_probes, uint32_t directions, const float *survey, float *placement,
+                           int move, int on_device, void *stream) {
+    try { return probe_relocate_step_impl(device, rl, n_probes, directions, survey, placement, move, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_relocate_step"); }
+}
+
+int fw_relocate_probes(fw_scene *scene, const fw_probe_set *set, const fw_probe_relocate *rl, const fw_trace_params *tp, uint32_t first_step,
+                       uint32_t steps, float *placement, float *survey, fw_stats *stats) {
+    try { return relocate_probes_impl(scene, set, rl, tp, first_step, steps, placement, survey, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_relocate_probes"); }
+}
+
+// pd and moments both NULL: a placed lookup without visibility; one of them NULL is the counterpart's null argument
+int fw_probe_irradiance_placed(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias,
+                               const float *placement, int device, uint32_t n, const float *positions, const float *normals, uint32_t stride_floats,
+                               float *irradiance, int on_device, void *stream) {
+    try {
+        const ProbeVis vis{pd, moments, normal_bias};
+        const ProbePlaced pl{placement};
+        return probe_irradiance_impl(grid, sh, device, n, positions, normals, stride_floats, irradiance, on_device, stream,
+                                     (pd || moments) ? &vis : nullptr, &pl);
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_irradiance_placed"); }
+}
+
+int fw_probe_shade_placed(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias,
+                          const float *placement, const fw_probe_shade_params *p, const float *aov, float *linear_rgb, float *gamma_rgb,
+                          uint8_t *rgb8) {
+    try {
+        const ProbeVis vis{pd, moments, normal_bias};
+        const ProbePlaced pl{placement};
+        return probe_shade_impl(grid, sh, p, aov, linear_rgb, gamma_rgb, rgb8, (pd || moments) ? &vis : nullptr, &pl);
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_placed"); }
 }
 
 int fw_lightmap_texels(const fw_lightmap *lm, int device, float *records, uint32_t *owner, uint32_t *n_covered, int on_device, void *stream) {

@@ -1128,6 +1128,99 @@ int fw_ao_reduce(int device, const fw_ao *ao, uint32_t n, const uint32_t *ids, c
 int fw_bake_ao(fw_scene *scene, const fw_ao *ao, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
                uint32_t stride_floats, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
 
+/* ---- probe relocation and classification: move probes out of geometry (additive at ABI 8) -----------------------------
+   A grid is laid over a scene without looking at it: some probes land inside objects or a hair from a wall.  A probe's own rays tell:
+   fw_probe_survey reduces one round's hits to "how much of what the probe sees is a back face, and where is the nearest surface",
+   fw_probe_relocate_step moves the probe and marks it active or inactive, fw_relocate_probes drives both against a resident scene, and
+   the _placed lookups read baked probes where they went.  Everything is float64 from the float32 inputs, every operation rounded as
+   written.  api.probe_survey, api.probe_relocate_step and api.probe_lookup_placed are the numpy statements.
+     Placement: one 16-byte record (ox, oy, oz, a) per probe.  o is the offset from the probe's nominal position in world units, a is
+         1.0 (active) or 0.0 (inactive).  The neutral record is (0, 0, 0, 1).
+     Survey: one 48-byte record of three float4s per probe.  [0] = (back.xyz, dist): the stored float32 direction of the nearest
+         back-face hit and its distance, (0, 0, 0, +inf) if none.  [1] the same for the nearest front-face hit.  [2] = (n_back, n_front,
+         n_miss, 0) as floats, exact since D <= 2^20.
+     Survey of one round (fw_probe_survey, k_probe_survey).  For ray j of probe p, d is the stored float32 direction and
+         h = hits[p D + j].  An all-zero d is skipped and counts nowhere.  h.object == FW_NO_HIT is a miss.  Otherwise
+         dist = (double)h.t * sqrt((dx dx + dy dy) + dz dz), and the hit is a back face iff ((nx dx + ny dy) + nz dz) > 0 with the
+         record's float32 normal widened (the products are exact in double), else a front face.  The nearest hit of a class is the
+         smallest dist, ties to the lowest j (a NaN distance is counted but is never the nearest); its distance is rounded to float32
+         once.  A hit is classified by the normal the walk stored, whatever the shape: a ConstantMedium reports +Y, and counts as what
+         that is for the ray.  One wave per probe, the lanes joined by a butterfly of (dist, j) minima and integer sums: no atomics, the
+         result is a pure function of the inputs and does not depend on the launch geometry.
+     Step (fw_probe_relocate_step, k_probe_relocate_step), per probe:  inside = (double)n_back > (double)back_fraction * (double)D;
+         a' = inside ? 0 : 1 (the survey was taken at the current position, so a' classifies that position).  With move == 0 only a is
+         written.  Otherwise the candidate c: if inside, c = o + u_back * (dist_back + 0.5 * min_front) with
+         u = d / sqrt((dx dx + dy dy) + dz dz) per component; else if n_front > 0 and dist_front < min_front,
+         c = o - u_front * (min_front - dist_front); else c = o.  Each component is rounded to float32 once.  If any |c_k| > max_offset_k
+         (or c_k is not a number) the move is rejected, not clamped, and o' = o; otherwise o' = c.  A probe that needs a move it is not
+         allowed stays where it is and comes out inactive at the classifying step.
+     Placed lookup (fw_probe_irradiance_placed, fw_probe_shade_placed): fw_probe_irradiance's statement, or with depth maps
+         fw_probe_irradiance_vis', with these changes.  (i) The corner's probe stands at P'_k = P_k + (double)o_k, used in the wrap term
+         r = P' - p and the visibility term r' = q - P'; the cell and the trilinear weights stay the nominal grid's.  (ii) A corner whose
+         a is 0 is skipped: its sh and moments never enter a sum, so a NaN there does not reach the output.  (iii) The weights of the
+         remaining corners are always divided by their sum, added in the order dz, dy, dx.  (iv) No active corner, or a sum of 0, gives
+         (0, 0, 0).  With every record (0, 0, 0, 1) the output equals the counterpart's bit for bit whenever the counterpart normalises
+         (FW_PROBE_WRAP, or depth maps).  Without wrap and without depth the placed lookup differs from fw_probe_irradiance by the
+         division in (iii) alone.  The sh and the depth maps are expected to have been baked at the moved positions: fw_probe_set takes
+         arbitrary positions, so that is the caller's to do. */
+typedef struct fw_probe_relocate {
+    float min_front;          /* > 0, finite: a probe keeps at least this distance to the nearest front face */
+    float back_fraction;      /* in [0, 1]: a probe that sees more than this share of back faces is inside geometry (DDGI: 0.25) */
+    float max_offset[3];      /* >= 0, finite: the largest |offset| per axis, world units */
+} fw_probe_relocate;
+
+/* fw_probe_survey: overwrites survey (n_probes x 12 floats) from one round's rays (n_probes x D x 6 floats) and the hits fw_trace_rays
+   wrote for them.  Host arrays — staged through one device allocation of the call's own, freed on every path — or with on_device
+   device arrays on `device` (the kernel then works on the caller's memory), launched on `stream` and complete on return.  Errors, in
+   this order and before HIP is called: FW_ERR_BAD_ARG for a NULL rays, hits or survey, n_probes == 0, directions outside 1..2^20, with
+   on_device hits or survey not 16-byte aligned or rays not 4-byte aligned; FW_ERR_UNSUPPORTED for n_probes x D >= 2^31; then
+   FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last one. */
+int fw_probe_survey(int device, uint32_t n_probes, uint32_t directions, const float *rays, const fw_hit *hits, float *survey, int on_device,
+                    void *stream);
+
+/* fw_probe_relocate_step: one step over n_probes probes; survey is read, placement (n_probes x 4 floats) is read and written.  Host or
+   device arrays as fw_probe_survey.  Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL rl, survey or placement,
+   min_front not finite or <= 0, back_fraction outside [0, 1], a max_offset negative or not finite, n_probes == 0, directions outside
+   1..2^20, with on_device survey or placement not 16-byte aligned; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the
+   last one. */
+int fw_probe_relocate_step(int device, const fw_probe_relocate *rl, uint32_t n_probes, uint32_t directions, const float *survey, float *placement,
+                           int move, int on_device, void *stream);
+
+/* fw_relocate_probes: the steps [first_step, first_step + steps) of a probe set against a resident scene, and then one classifying
+   step (move = 0) at s = first_step + steps.  set->positions are the nominal positions; placement is n_probes x 4 floats in host
+   memory always, read and written (start it at (0, 0, 0, 1)); survey is host memory, n_probes x 12 floats, the last step's, and may be
+   NULL.  Of tp, use_bvh, flags, seed, rays_per_batch and stream are read.  For each step s: the moved positions
+   float((double)pos_k + (double)o_k) are formed on the host; then for each chunk of probes [p0, p1) (set->chunk_probes at a time; 0 = as
+   many as fit 256 MiB at 72 B per ray, at least 1) k_probe_rays fills device scratch of the call's own with round s over the moved
+   positions, the rays are traced exactly as fw_trace_rays would with on_device = 1, key_base = p0 D and seed = tp->seed + s,
+   k_probe_survey and k_probe_relocate_step run; the placement is copied back, 16 B per probe.  steps may be 0: classify only.
+   Contracts.  Composition: for every chunk_probes, placement and survey equal bit for bit what fw_probe_rays (a set at the moved
+   positions), fw_trace_rays (seed + s, key_base 0), fw_probe_survey and fw_probe_relocate_step give when chained by hand over the
+   whole set.  Progressive: a call of (0, a) followed by one of (a, b) leaves the placement and survey of one call of (0, a + b), bit
+   for bit.
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, set, rl, tp or placement,
+   what fw_probe_rays rejects in the set, what fw_probe_relocate_step rejects in rl, a placement entry that is not finite or whose a is
+   neither 0 nor 1 (its index is in fw_last_error()), first_step + steps + 1 >= 2^32; FW_ERR_UNSUPPORTED for n_probes x D >= 2^31; then
+   FW_ERR_NO_DEVICE.
+   stats (may be NULL): fw_trace_rays' fields summed over steps and chunks as fw_bake_probe_depth sums them; ms_render includes the three
+   kernels' launches (under FW_FLAG_TIME_KERNELS ms_raygen and ms_accumulate as well); ms_wall covers the whole call.  Synchronisation
+   and what a trace leaves of renders are fw_trace_rays'. */
+int fw_relocate_probes(fw_scene *scene, const fw_probe_set *set, const fw_probe_relocate *rl, const fw_trace_params *tp, uint32_t first_step,
+                       uint32_t steps, float *placement, float *survey, fw_stats *stats);
+
+/* fw_probe_irradiance_placed, fw_probe_shade_placed: the placed lookup above (k_probe_irradiance_placed, k_probe_shade_placed: one lane
+   per point, no atomics).  The arguments are fw_probe_irradiance_vis' and fw_probe_shade_vis', and placement: n x 4 floats for the
+   grid's n probes, host memory or with on_device device memory like sh; a host call stages it after the moments.  pd and moments may
+   both be NULL: no visibility weight (normal_bias is then not read).  Every index is formed from clamped cell and texel indices: no
+   load leaves the arrays wherever the point lies.  Errors: the counterpart's, in its order, with placement among the NULL checks and,
+   with on_device, among the 4-byte alignment checks; exactly one of pd and moments NULL is FW_ERR_BAD_ARG. */
+int fw_probe_irradiance_placed(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias,
+                               const float *placement, int device, uint32_t n, const float *positions, const float *normals, uint32_t stride_floats,
+                               float *irradiance, int on_device, void *stream);
+int fw_probe_shade_placed(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias,
+                          const float *placement, const fw_probe_shade_params *p, const float *aov, float *linear_rgb, float *gamma_rgb,
+                          uint8_t *rgb8);
+
 /* Diagnostic: the kernels' division / square-root helpers against the compiler's IEEE expansion, bit for bit,
    on n hashed operand pairs.  mode 0 = magnitudes 2^-40..2^40 (must be 0 mismatches), mode 1 = all bit patterns. */
 int fw_selftest_arith(int device, uint32_t n, uint32_t seed, int mode, uint64_t *div_mismatches, uint64_t *sqrt_mismatches);
