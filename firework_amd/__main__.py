@@ -47,6 +47,11 @@ marks those that stay inside inactive, fw_relocate_probes, DESIGN.md §9u: K mov
 of the grid's spacing; sh and depth are baked at the moved positions; the .npz keeps the nominal positions and also gets placement,
 relocate_min_front and relocate_steps).  --probe-lit then reads the probes where they went (fw_probe_shade_placed) when the file holds
 placement; --probe-no-placement ignores it.
+--bake-probes ... --probe-radiance R [--probe-radiance-sharpness K] [--probe-radiance-roughness a,b,...] (also bakes every probe's R x R
+octahedral radiance map and its GGX-prefiltered level chain, R in 4, 8, 16, 32, level 0's weights cos^(2^K), default K = 2, one level
+per roughness, default 0.1 .. 1 over as many levels as fit, fw_bake_probe_radiance, DESIGN.md §9v: one render pass feeds the SH and
+the maps; the .npz also gets radiance, radiance_res, radiance_sharpness and radiance_roughness).  --probe-lit then shows reflections on
+GgxMat and MetalMat surfaces (fw_probe_shade_glossy) when the file holds them; --probe-no-radiance ignores them.
 --ao RADIUS [--ao-dirs D] [--ao-rounds R] [--ao-falloff] (the fixed view's ambient occlusion as a grey PNG: one first-hit pass of
 --aov-samples samples, then R rounds, default 1, of D cosine-weighted rays per pixel, default 64, traced from each pixel's surface point;
 a hit nearer than RADIUS > 0 occludes, fully or with --ao-falloff by 1 - dist / RADIUS, fw_bake_ao, DESIGN.md §9t; -s is not used;
@@ -107,6 +112,14 @@ def main(argv=None):
     ap.add_argument("--probe-depth-sharpness", type=int, default=None, metavar="K", help="with --probe-depth: a ray weighs cos^(2^K) in a texel, 0..8 (default 6)")
     ap.add_argument("--probe-depth-max", type=float, default=None, metavar="M",
                     help="with --probe-depth: distances are clamped to M > 0, which a miss counts as (default: the grid's diagonal)")
+    ap.add_argument("--probe-radiance", type=int, default=None, metavar="R",
+                    help="with --bake-probes: also bake an R x R octahedral radiance map per probe with a GGX-prefiltered level chain "
+                         "(R in 4, 8, 16, 32), for --probe-lit's reflections; one render pass feeds it and the SH")
+    ap.add_argument("--probe-radiance-sharpness", type=int, default=None, metavar="K",
+                    help="with --probe-radiance: a ray weighs cos^(2^K) in a texel of level 0, 0..8 (default 2)")
+    ap.add_argument("--probe-radiance-roughness", default=None, metavar="A,B,...",
+                    help="with --probe-radiance: the levels' roughness, ascending in [0, 1] (default: 0.1 .. 1 over as many levels as fit)")
+    ap.add_argument("--probe-no-radiance", action="store_true", help="with --probe-lit: ignore the radiance maps in the file")
     ap.add_argument("--bake-lightmap", default=None, metavar="OBJECT,W,H",
                     help="bake the irradiance over the W x H UV texels of render object OBJECT (a mesh with uvs) into the .npz named by -o")
     ap.add_argument("--lightmap-dirs", type=int, default=None, metavar="D", help="with --bake-lightmap: directions per texel and round (default 64)")
@@ -229,6 +242,23 @@ def main(argv=None):
                 ap.error("--probe-depth needs --probe-depth-max M for a grid of one point: it has no diagonal")
         elif opt.probe_depth_sharpness is not None or opt.probe_depth_max is not None:
             ap.error("--probe-depth-sharpness and --probe-depth-max need --probe-depth")
+        radiance_roughness = None
+        if opt.probe_radiance is not None:
+            if opt.probe_radiance not in (4, 8, 16, 32):
+                ap.error("--probe-radiance R needs R in 4, 8, 16, 32")
+            if opt.probe_radiance_sharpness is not None and not 0 <= opt.probe_radiance_sharpness <= 8:
+                ap.error("--probe-radiance-sharpness K needs 0 <= K <= 8")
+            if opt.probe_radiance_roughness is not None:
+                try:
+                    radiance_roughness = [float(x) for x in opt.probe_radiance_roughness.split(",")]
+                except ValueError:
+                    radiance_roughness = []
+                most = min(4, opt.probe_radiance.bit_length() - 2)
+                if (not 1 <= len(radiance_roughness) <= most or not all(0.0 <= x <= 1.0 for x in radiance_roughness)
+                        or any(b <= a for a, b in zip(radiance_roughness, radiance_roughness[1:]))):
+                    ap.error(f"--probe-radiance-roughness needs 1 to {most} numbers in [0, 1], strictly ascending")
+        elif opt.probe_radiance_sharpness is not None or opt.probe_radiance_roughness is not None:
+            ap.error("--probe-radiance-sharpness and --probe-radiance-roughness need --probe-radiance")
         if opt.probe_relocate is not None:
             if not 0.0 < opt.probe_relocate < float("inf"):
                 ap.error("--probe-relocate MIN_FRONT needs a finite MIN_FRONT > 0")
@@ -248,6 +278,8 @@ def main(argv=None):
         ap.error("--probe-depth, --probe-depth-sharpness and --probe-depth-max need --bake-probes")
     elif opt.probe_relocate is not None or opt.probe_relocate_steps is not None or opt.probe_relocate_max is not None:
         ap.error("--probe-relocate, --probe-relocate-steps and --probe-relocate-max need --bake-probes")
+    elif opt.probe_radiance is not None or opt.probe_radiance_sharpness is not None or opt.probe_radiance_roughness is not None:
+        ap.error("--probe-radiance, --probe-radiance-sharpness and --probe-radiance-roughness need --bake-probes")
     if opt.adaptive is not None and (opt.progressive > 0 or opt.checkpoint):
         ap.error("--adaptive cannot be combined with --progressive or --checkpoint")
     if opt.temporal is not None:
@@ -302,7 +334,7 @@ def main(argv=None):
             print(f"firework: error: --bake-lightmap: {e}", file=sys.stderr)
             return 2
 
-    probe_grid = probe_sh = probe_depth = probe_moments = probe_placement = None
+    probe_grid = probe_sh = probe_depth = probe_moments = probe_placement = probe_radiance = probe_maps = None
     if opt.probe_lit is not None:          # the file is looked at before the device is: a wrong one is a message, not a traceback
         import zipfile
         import numpy as np
@@ -323,12 +355,21 @@ def main(argv=None):
                     probe_moments = np.asarray(z["depth"], np.float32)
                 if "placement" in z.files and not opt.probe_no_placement:
                     probe_placement = np.asarray(z["placement"], np.float32)
+                if "radiance" in z.files and not opt.probe_no_radiance:
+                    from .api import ProbeRadiance
+                    missing = [k for k in ("radiance_res", "radiance_sharpness", "radiance_roughness") if k not in z.files]
+                    if missing:
+                        raise ValueError(f"radiance without {', '.join(missing)} in it")
+                    probe_radiance = ProbeRadiance(int(z["radiance_res"]), int(z["radiance_sharpness"]), np.asarray(z["radiance_roughness"], np.float32))
+                    probe_maps = np.asarray(z["radiance"], np.float32)
             if probe_sh.shape != (probe_grid.n_probes, 9, 3):
                 raise ValueError(f"sh has shape {probe_sh.shape}, the grid {probe_grid.n_probes} probes")
             if probe_depth is not None and probe_moments.shape != (probe_grid.n_probes, probe_depth.resolution, probe_depth.resolution, 2):
                 raise ValueError(f"depth has shape {probe_moments.shape}, the grid {probe_grid.n_probes} probes of resolution {probe_depth.resolution}")
             if probe_placement is not None and probe_placement.shape != (probe_grid.n_probes, 4):
                 raise ValueError(f"placement has shape {probe_placement.shape}, the grid {probe_grid.n_probes} probes")
+            if probe_radiance is not None and probe_maps.shape != (probe_grid.n_probes, probe_radiance.texels, 4):
+                raise ValueError(f"radiance has shape {probe_maps.shape}, the grid {probe_grid.n_probes} probes of {probe_radiance.texels} texels")
         except (OSError, ValueError, zipfile.BadZipFile) as e:
             print(f"firework: error: --probe-lit {opt.probe_lit}: {e}", file=sys.stderr)
             return 2
@@ -359,7 +400,14 @@ def main(argv=None):
             print(f"Relocated {int(np.any(placement[:, 0:3] != 0, axis=1).sum())} probes, {int((placement[:, 3] == 0).sum())} inactive")
             extra = dict(placement=placement, relocate_min_front=np.float32(relocation.min_front), relocate_steps=np.int64(relocation.steps))
             probes = nominal.moved(placement)
-        sh, sums = renderer.bake_probes(scene, probes, rounds, device=opt.device)
+        if opt.probe_radiance is not None:      # one render pass for the SH and the maps: the same sh and sums, bit for bit
+            from .api import ProbeRadiance
+            radiance = ProbeRadiance(opt.probe_radiance, 2 if opt.probe_radiance_sharpness is None else opt.probe_radiance_sharpness, radiance_roughness)
+            maps, _radiance_sums, sh, sums = renderer.bake_probe_radiance(scene, probes, radiance, rounds, chunk=None, with_sh=True, device=opt.device)
+            extra.update(radiance=maps, radiance_res=np.int64(radiance.resolution), radiance_sharpness=np.int64(radiance.sharpness_log2),
+                         radiance_roughness=np.array(radiance.roughness, np.float32))
+        else:
+            sh, sums = renderer.bake_probes(scene, probes, rounds, device=opt.device)
         if opt.probe_depth is not None:
             from .api import ProbeDepth
             diagonal = float(np.sqrt(sum((b - a) ** 2 for a, b in zip(corners[0], corners[1]))))
@@ -378,7 +426,7 @@ def main(argv=None):
     if probe_grid is not None:
         render = renderer.render_probe_lit(scene, probe_grid, probe_sh, opt.aov_samples, device=opt.device, depth=probe_depth, moments=probe_moments,
                                            normal_bias=0.0 if opt.probe_normal_bias is None else opt.probe_normal_bias,
-                                           placement=probe_placement).rgb8
+                                           placement=probe_placement, radiance=probe_radiance, maps=probe_maps).rgb8
         print(f"Finished Rendering in {int(time.time() - start)} s")
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)

@@ -243,5 +243,28 @@ PROBE_PLACE_PROTOTYPES = {
 }
 
 
+# probe radiance maps (include/firework_hip.h: fw_probe_radiance_reduce, fw_probe_radiance_prefilter, fw_bake_probe_radiance,
+# fw_probe_radiance_lookup, fw_probe_shade_glossy)
+FW_PROBE_RADIANCE_MAX_LEVELS = 4
+
+
+class fw_probe_radiance(C.Structure):
+    _fields_ = [("resolution", u32), ("sharpness_log2", u32), ("levels", u32), ("roughness", f32 * FW_PROBE_RADIANCE_MAX_LEVELS)]
+
+
+# the five prototypes (argument types; every one returns int), applied by _lib.load
+PROBE_RADIANCE_PROTOTYPES = {
+    "fw_probe_radiance_reduce": [C.c_int, C.POINTER(fw_probe_radiance), u32, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_probe_radiance_prefilter": [C.c_int, C.POINTER(fw_probe_radiance), u32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_bake_probe_radiance": [C.c_void_p, C.POINTER(fw_probe_set), C.POINTER(fw_probe_radiance), C.POINTER(fw_render_rays_params), u32, u32,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fw_stats)],
+    "fw_probe_radiance_lookup": [C.POINTER(fw_probe_grid), C.POINTER(fw_probe_radiance), C.c_void_p, C.POINTER(fw_probe_depth), C.c_void_p, f32,
+                                 C.c_void_p, C.c_int, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_probe_shade_glossy": [C.POINTER(fw_probe_grid), C.c_void_p, C.POINTER(fw_probe_radiance), C.c_void_p, C.POINTER(fw_probe_depth), C.c_void_p,
+                              f32, C.c_void_p, C.POINTER(fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p,
+                              C.c_void_p],
+}
+
+
 def vec3(v):
     return fw_vec3(float(v[0]), float(v[1]), float(v[2]))

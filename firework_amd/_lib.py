@@ -130,7 +130,8 @@ def load(preload=False, device=None):
     lib.fw_probe_shade.restype = C.c_int
     lib.fw_probe_shade.argtypes = [C.POINTER(A.fw_probe_grid), C.c_void_p, C.POINTER(A.fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
-    for name, argtypes in list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()) + list(A.PROBE_PLACE_PROTOTYPES.items()):
+    for name, argtypes in (list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()) + list(A.PROBE_PLACE_PROTOTYPES.items())
+                           + list(A.PROBE_RADIANCE_PROTOTYPES.items())):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
@@ -707,6 +708,175 @@ def probe_depth_reduce(depth, rays, hits, directions, sums=None, device=0, strea
     _host_f32(sums, (n, R, R, 4), "sums")
     _check(lib, lib.fw_probe_depth_reduce(int(device), C.byref(pd), n, d, r.ctypes.data, h.ctypes.data, sums.ctypes.data, 0, None))
     return sums
+
+
+def probe_radiance_reduce(radiance, rays, accum, samples, directions, sums=None, device=0, stream=None):
+    """fw_probe_radiance_reduce: adds one round's radiance sums (A_r, A_g, A_b, W per texel, each rounded to float32 once) to sums (N, R,
+    R, 4) float32, updated in place (None: zeros).  radiance an api.ProbeRadiance; rays (N * D, 6) and accum (N * D, 4) float32 as
+    DeviceScene.render_rays leaves it: numpy arrays, or contiguous torch tensors on cuda:`device`, reduced on `stream` (default: the
+    current torch stream) where they lie.  Returns sums."""
+    lib = load()
+    pr = radiance.to_abi()
+    d, R = int(directions), int(pr.resolution)
+    total = int(rays.shape[0])
+    if d < 1 or total % d or tuple(rays.shape) != (total, 6) or tuple(accum.shape) != (total, 4):
+        raise ValueError(f"rays must have shape (N * {d}, 6) and accum (N * {d}, 4)")
+    n = total // d
+    if type(rays).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
+        _check_device_tensor(accum, (total, 4), torch.float32, device, "accum")
+        if sums is None:
+            sums = torch.zeros((n, R, R, 4), dtype=torch.float32, device=rays.device)
+        _check_device_tensor(sums, (n, R, R, 4), torch.float32, device, "sums")
+        _check(lib, lib.fw_probe_radiance_reduce(int(device), C.byref(pr), n, d, int(samples), rays.data_ptr(), accum.data_ptr(), sums.data_ptr(), 1,
+                                                 _stream_arg(stream, rays.device)))
+        return sums
+    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
+    a = np.ascontiguousarray(np.asarray(accum, dtype=np.float32))
+    if sums is None:
+        sums = np.zeros((n, R, R, 4), np.float32)
+    _host_f32(sums, (n, R, R, 4), "sums")
+    _check(lib, lib.fw_probe_radiance_reduce(int(device), C.byref(pr), n, d, int(samples), r.ctypes.data, a.ctypes.data, sums.ctypes.data, 0, None))
+    return sums
+
+
+def probe_radiance_prefilter(radiance, sums, out=None, device=0, stream=None):
+    """fw_probe_radiance_prefilter: the maps (N, M, 4) float32 — (r, g, b, flag) per texel of every level, M = radiance.texels — of the
+    sums (N, R, R, 4) float32: level 0 divided, the levels above it GGX-prefiltered from level 0.  numpy arrays, or contiguous torch
+    tensors on cuda:`device`, filtered on `stream` (default: the current torch stream) where they lie.  out: an array or tensor of that
+    shape to overwrite instead.  Returns the maps."""
+    lib = load()
+    pr = radiance.to_abi()
+    R, M = int(pr.resolution), int(radiance.texels)
+    n = int(sums.shape[0])
+    if type(sums).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(sums, (n, R, R, 4), torch.float32, device, "sums")
+        if out is None:
+            out = torch.empty((n, M, 4), dtype=torch.float32, device=sums.device)
+        _check_device_tensor(out, (n, M, 4), torch.float32, device, "out")
+        _check(lib, lib.fw_probe_radiance_prefilter(int(device), C.byref(pr), n, sums.data_ptr(), out.data_ptr(), 1, _stream_arg(stream, sums.device)))
+        return out
+    s = np.ascontiguousarray(np.asarray(sums, np.float32).reshape(n, R, R, 4))
+    if out is None:
+        out = np.empty((n, M, 4), np.float32)
+    _host_f32(out, (n, M, 4), "out")
+    _check(lib, lib.fw_probe_radiance_prefilter(int(device), C.byref(pr), n, s.ctypes.data, out.ctypes.data, 0, None))
+    return out
+
+
+def _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, on_device, device):
+    """the (pr, maps, pd, moments, normal_bias, placement) arguments of fw_probe_radiance_lookup and fw_probe_shade_glossy, and what keeps
+    their pointers alive: maps (n, M, 4) float32; depth with moments, and placement, optional; device tensors when the call's other
+    arrays are"""
+    if (depth is None) != (moments is None):
+        raise ValueError("depth and moments are given together or not at all")
+    pr = radiance.to_abi()
+    shape = (n_probes, int(radiance.texels), 4)
+    keep = [pr]
+    if on_device:
+        import torch
+        _check_device_tensor(maps, shape, torch.float32, device, "maps")
+        mp = maps.data_ptr()
+    else:
+        maps = np.ascontiguousarray(np.asarray(maps, np.float32).reshape(shape))
+        mp = maps.ctypes.data
+    keep.append(maps)
+    pd = mom = pl = None
+    bias = 0.0
+    if depth is not None:
+        pdv, mom, bias, k = _vis_args(depth, moments, normal_bias, n_probes, on_device, device)
+        pd = C.byref(pdv)
+        keep += [pdv, k]
+    if placement is not None:
+        pl, k = _placement_arg(placement, n_probes, on_device, device)
+        keep.append(k)
+    return (C.byref(pr), mp, pd, mom, bias, pl), keep
+
+
+def probe_radiance_lookup(grid, radiance, maps, positions, normals, dirs, roughness, depth=None, moments=None, normal_bias=0.0, placement=None,
+                          out=None, stream=None, device=0):
+    """fw_probe_radiance_lookup: the radiance the probes of `grid` (see probe_irradiance) hold along `dirs` at the roughness `roughness`,
+    seen from the points `positions` with the normals `normals`: maps (n, M, 4) float32 as DeviceScene.bake_probe_radiance returns them
+    for radiance (an api.ProbeRadiance), positions, normals and dirs (N, 3) and roughness (N,) float32; not clamped.  depth with moments,
+    normal_bias and placement weight the corners as probe_irradiance_placed does (placement None: every probe active where it stands).
+    numpy arrays: returns an (N, 3) float32 array.  Contiguous torch tensors on cuda:`device`: looked up on `stream` (default: the current
+    torch stream) where they lie; returns a device tensor.  out: an array or tensor of that shape to fill instead."""
+    lib = load()
+    g, n_probes = _grid_abi(grid)
+    if type(positions).__module__.startswith("torch"):
+        import torch
+        n = int(positions.shape[0])
+        for t, shape, name in ((positions, (n, 3), "positions"), (normals, (n, 3), "normals"), (dirs, (n, 3), "dirs"), (roughness, (n,), "roughness")):
+            _check_device_tensor(t, shape, torch.float32, device, name)
+        head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, True, device)
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float32, device=positions.device)
+        _check_device_tensor(out, (n, 3), torch.float32, device, "out")
+        _check(lib, lib.fw_probe_radiance_lookup(C.byref(g), *head, int(device), n, positions.data_ptr(), normals.data_ptr(), 3, dirs.data_ptr(),
+                                                 roughness.data_ptr(), out.data_ptr(), 1, _stream_arg(stream, positions.device)))
+        return out
+    p = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))
+    n = int(p.shape[0])
+    nr = np.ascontiguousarray(np.asarray(normals, np.float32).reshape(-1, 3))
+    dr = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
+    ro = np.ascontiguousarray(np.asarray(roughness, np.float32).reshape(-1))
+    if nr.shape != p.shape or dr.shape != p.shape or ro.shape != (n,):
+        raise ValueError("positions, normals and dirs must have the same shape (N, 3) and roughness (N,)")
+    head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, False, device)
+    if out is None:
+        out = np.empty((n, 3), np.float32)
+    _host_f32(out, (n, 3), "out")
+    _check(lib, lib.fw_probe_radiance_lookup(C.byref(g), *head, int(device), n, p.ctypes.data, nr.ctypes.data, 3, dr.ctypes.data, ro.ctypes.data,
+                                             out.ctypes.data, 0, None))
+    return out
+
+
+def probe_shade_glossy(grid, sh, radiance, maps, aov, spec, view, width, height, depth=None, moments=None, normal_bias=0.0, placement=None,
+                       gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear")):
+    """fw_probe_shade_glossy: probe_shade_placed where spec's roughness is not > 0, and elsewhere a conductor lit by the radiance maps
+    along the mirrored view direction: spec (N, 4) float32 (F0.rgb, rho), view (N, 3) float32 — or, on the device, three columns of a
+    contiguous (N, S) tensor such as rays[:, 3:6] — the ray direction from the eye.  radiance, maps, depth, moments, normal_bias and
+    placement as probe_radiance_lookup; everything else as probe_shade."""
+    lib = load()
+    g, n_probes = _grid_abi(grid)
+    n = int(width) * int(height)
+    p = A.fw_probe_shade_params()
+    p.width, p.height, p.gamma, p.device = int(width), int(height), float(gamma), int(device)
+    want = [name in outputs for name in ("rgb8", "gamma", "linear")]
+    if type(aov).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(sh, (n_probes, 9, 3), torch.float32, device, "sh")
+        _check_device_tensor(aov, (n, 12), torch.float32, device, "aov")
+        _check_device_tensor(spec, (n, 4), torch.float32, device, "spec")
+        stride = int(view.stride(0)) if n > 1 else max(3, int(view.stride(0)))
+        if (view.dtype != torch.float32 or tuple(view.shape) != (n, 3) or view.stride(1) != 1 or view.device.type != "cuda"
+                or (view.device.index or 0) != device or stride < 3):
+            raise ValueError(f"view must be an (N, 3) float32 tensor on cuda:{device} with unit column stride and a row stride >= 3")
+        head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, True, device)
+        dev = aov.device
+        rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev) if want[0] else None
+        gam = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[1] else None
+        lin = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[2] else None
+        p.on_device = 1
+        p.stream = _stream_arg(stream, dev)
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        _check(lib, lib.fw_probe_shade_glossy(C.byref(g), sh.data_ptr(), *head, C.byref(p), aov.data_ptr(), spec.data_ptr(), view.data_ptr(), stride,
+                                              ptr(lin), ptr(gam), ptr(rgb8)))
+        return rgb8, gam, lin
+    s = np.ascontiguousarray(np.asarray(sh, np.float32).reshape(n_probes, 9, 3))
+    a = np.ascontiguousarray(np.asarray(aov, np.float32).reshape(n, 12))
+    sp = np.ascontiguousarray(np.asarray(spec, np.float32).reshape(n, 4))
+    vw = np.ascontiguousarray(np.asarray(view, np.float32).reshape(n, 3))
+    head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, False, device)
+    rgb8 = np.empty((n, 3), np.uint8) if want[0] else None
+    gam = np.empty((n, 3), np.float32) if want[1] else None
+    lin = np.empty((n, 3), np.float32) if want[2] else None
+    ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
+    _check(lib, lib.fw_probe_shade_glossy(C.byref(g), s.ctypes.data, *head, C.byref(p), a.ctypes.data, sp.ctypes.data, vw.ctypes.data, 3, ptr(lin),
+                                          ptr(gam), ptr(rgb8)))
+    return rgb8, gam, lin
 
 
 def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear"), _vis=None, _placed=None):
@@ -1325,6 +1495,55 @@ class DeviceScene:
         _check(self._lib, self._lib.fw_bake_probe_depth(self.handle, C.byref(s), C.byref(pd), C.byref(p), int(first_round), int(rounds), *ptrs,
                                                         C.byref(st)))
         return out, sums, st.as_dict()
+
+    def bake_probe_radiance(self, probes, radiance, rounds, samples, first_round=0, sums=None, sh_sums=None, with_sh=False, seed=0, use_bvh=True,
+                            stream=None, paths_per_batch=0, flags=0, chunk=None, on_device=False):
+        """fw_bake_probe_radiance: the rounds [first_round, first_round + rounds) of the radiance maps (an api.ProbeRadiance) of an
+        api.ProbeSet, `samples` paths per direction and round, `chunk` probes at a time (None: the set's own setting; 0: automatic).
+        sums: (N, R, R, 4) float32 running sums of the rounds before first_round, updated in place (None: zeros, only with first_round
+        0).  with_sh (or sh_sums, bake_probes' running sums): the same rendered rays are also projected onto SH as bake_probes does.
+        Returns (maps, sums, stats), or with SH (maps, sums, sh, sh_sums, stats): maps (N, M, 4) float32; host arrays, or — sums a device
+        tensor on this scene's device, or on_device=True — device tensors, baked on `stream` (default: the current torch stream)."""
+        s, _pos = _probe_abi(probes, chunk)
+        pr = radiance.to_abi()
+        n, R, M = int(s.n_probes), int(pr.resolution), int(radiance.texels)
+        with_sh = bool(with_sh) or sh_sums is not None
+        p = A.fw_render_rays_params()
+        p.samples, p.seed, p.use_bvh, p.gamma = int(samples), int(seed), int(bool(use_bvh)), 1.0
+        p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
+        st = A.fw_stats()
+        sh = None
+        if on_device or any(t is not None and type(t).__module__.startswith("torch") for t in (sums, sh_sums)):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if sums is None:
+                sums = torch.zeros((n, R, R, 4), dtype=torch.float32, device=dev)
+            _check_device_tensor(sums, (n, R, R, 4), torch.float32, self.device, "sums")
+            maps = torch.empty((n, M, 4), dtype=torch.float32, device=dev)
+            if with_sh:
+                if sh_sums is None:
+                    sh_sums = torch.zeros((n, 9, 3), dtype=torch.float32, device=dev)
+                _check_device_tensor(sh_sums, (n, 9, 3), torch.float32, self.device, "sh_sums")
+                sh = torch.empty((n, 9, 3), dtype=torch.float32, device=dev)
+            p.on_device = 1
+            p.stream = _stream_arg(stream, dev)
+            ptrs = (sums.data_ptr(), maps.data_ptr(), sh_sums.data_ptr() if with_sh else None, sh.data_ptr() if with_sh else None)
+        else:
+            if sums is None:
+                sums = np.zeros((n, R, R, 4), np.float32)
+            _host_f32(sums, (n, R, R, 4), "sums")
+            maps = np.empty((n, M, 4), np.float32)
+            if with_sh:
+                if sh_sums is None:
+                    sh_sums = np.zeros((n, 9, 3), np.float32)
+                _host_f32(sh_sums, (n, 9, 3), "sh_sums")
+                sh = np.empty((n, 9, 3), np.float32)
+            ptrs = (sums.ctypes.data, maps.ctypes.data, sh_sums.ctypes.data if with_sh else None, sh.ctypes.data if with_sh else None)
+        _check(self._lib, self._lib.fw_bake_probe_radiance(self.handle, C.byref(s), C.byref(pr), C.byref(p), int(first_round), int(rounds), *ptrs,
+                                                           C.byref(st)))
+        if with_sh:
+            return maps, sums, sh, sh_sums, st.as_dict()
+        return maps, sums, st.as_dict()
 
     def relocate_probes(self, probes, relocation, steps=None, first_step=0, placement=None, seed=0, use_bvh=True, stream=None, rays_per_batch=0,
                         flags=0, chunk=None):

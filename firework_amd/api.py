@@ -1785,6 +1785,310 @@ def probe_lookup_placed(grid, sh, placement, positions, normals, pd: "ProbeDepth
     return E, T, X
 
 
+# --------------------------------------------------------------------------- probe radiance maps
+class ProbeRadiance:
+    """The radiance maps of a probe set (fw_probe_radiance): every probe has a pyramid of octahedral maps, level l of resolution
+    resolution >> l (at least 4) holding the radiance prefiltered for a GGX lobe of roughness[l]; level 0 is the raw map, a ray's weight
+    in a texel max(0, T.d)^(2^sharpness_log2).  roughness None: linspace(0.1, 1, L) with as many levels as the floor of 4 allows.
+    .levels, .resolutions, .offsets (the texel offset of every level in a probe's pyramid) and .texels (their total, M)."""
+
+    def __init__(self, resolution: int = 8, sharpness_log2: int = 2, roughness=None):
+        self.resolution, self.sharpness_log2 = int(resolution), int(sharpness_log2)
+        if self.resolution not in (4, 8, 16, 32):
+            raise ValueError("resolution must be 4, 8, 16 or 32")
+        if not 0 <= self.sharpness_log2 <= 8:
+            raise ValueError("sharpness_log2 must be in 0..8")
+        most = min(A.FW_PROBE_RADIANCE_MAX_LEVELS, self.resolution.bit_length() - 2)          # R >> (L - 1) >= 4
+        if roughness is None:
+            roughness = np.linspace(0.1, 1.0, most)
+        rho = np.asarray(roughness, np.float32).reshape(-1)
+        if not 1 <= rho.size <= most:
+            raise ValueError(f"resolution {self.resolution} allows 1..{most} levels")
+        if not (np.all(rho >= 0.0) and np.all(rho <= 1.0) and np.all(np.diff(rho) > 0.0)):
+            raise ValueError("roughness must lie in [0, 1] and ascend strictly")
+        self.roughness = tuple(float(v) for v in rho)
+        self.levels = int(rho.size)
+        self.resolutions = tuple(self.resolution >> l for l in range(self.levels))
+        self.offsets = tuple(int(sum(r * r for r in self.resolutions[:l])) for l in range(self.levels))
+        self.texels = int(sum(r * r for r in self.resolutions))
+
+    def to_abi(self) -> A.fw_probe_radiance:
+        d = A.fw_probe_radiance()
+        d.resolution, d.sharpness_log2, d.levels = self.resolution, self.sharpness_log2, self.levels
+        for l, v in enumerate(self.roughness):
+            d.roughness[l] = v
+        return d
+
+
+def probe_radiance_reduce(pr: "ProbeRadiance", rays, accum, samples: int, directions: int, terms: bool = False):
+    """The numpy float64 statement of fw_probe_radiance_reduce: (N, R, R, 4) float64, the accumulators (A_r, A_g, A_b, W) of one round
+    before their one rounding to float32, for rays (N * D, 6) float32 (the directions as stored) and accum (N * D, 4) float32.
+    terms=True: returns (sums, G, B) with G (N, 4) = sum_j |d_j|^(2^k) |L_cj| (1 for W) and B (N, R, R, 4) the sums of the terms'
+    magnitudes: what a rounding-error bound scales with."""
+    D, R, k = int(directions), int(pr.resolution), int(pr.sharpness_log2)
+    d = np.asarray(rays, np.float32).astype(np.float64).reshape(-1, D, 6)[..., 3:]
+    a = np.asarray(accum, np.float32).astype(np.float64).reshape(-1, D, 4)
+    T = probe_depth_dirs(R)
+    n = d.shape[0]
+    out, mag = np.zeros((n, R, R, 4)), np.zeros((n, R, R, 4))
+    with np.errstate(all="ignore"):
+        L = a[..., 0:3] / float(int(samples))
+        for j in range(D):
+            dj = d[:, j, None, None, :]
+            w = np.fmax(0.0, (T[None, ..., 0] * dj[..., 0] + T[None, ..., 1] * dj[..., 1]) + T[None, ..., 2] * dj[..., 2])
+            for _ in range(k):
+                w = w * w
+            on = w > 0.0
+            for c in range(3):
+                term = w * L[:, j, None, None, c]
+                out[..., c] = np.where(on, out[..., c] + term, out[..., c])
+                mag[..., c] = np.where(on, mag[..., c] + np.abs(term), mag[..., c])
+            out[..., 3] = np.where(on, out[..., 3] + w, out[..., 3])
+        mag[..., 3] = out[..., 3]
+        length = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+        lk = length ** float(2 ** k)
+        G = np.stack([(lk * np.abs(L[..., c])).sum(axis=1) for c in range(3)] + [lk.sum(axis=1)], axis=-1)
+    return (out, G, mag) if terms else out
+
+
+def probe_radiance_sources(R: int):
+    """(S, omega): the unit directions (R * R, 3) of an R x R octahedral map's texels in ascending id, and their solid angles
+    omega = (4 / (R R)) / ((len len) len), len the length of the texel's centre on the octahedron: the map's Jacobian at the centre"""
+    R = int(R)
+    e = ((np.arange(R, dtype=np.float64) + 0.5) * 2.0) / float(R) - 1.0
+    ex, ey = np.broadcast_to(e[None, :], (R, R)), np.broadcast_to(e[:, None], (R, R))
+    z = (1.0 - np.abs(ex)) - np.abs(ey)
+    x = np.where(z < 0.0, (1.0 - np.abs(ey)) * _sgn1(ex), ex)
+    y = np.where(z < 0.0, (1.0 - np.abs(ex)) * _sgn1(ey), ey)
+    ln = np.sqrt((x * x + y * y) + z * z)
+    S = np.stack([x / ln, y / ln, z / ln], axis=-1).reshape(R * R, 3)
+    omega = ((4.0 / (float(R) * float(R))) / ((ln * ln) * ln)).reshape(R * R)
+    return S, omega
+
+
+def probe_radiance_weights(pr: "ProbeRadiance", level: int):
+    """(w, c, den): the prefilter's weight of every source texel of level 0 in every output texel of `level` >= 1, (R_l^2, R^2) float64 —
+    w = ((a2 / (den den)) c) omega with c = (Tx Sx + Ty Sy) + Tz Sz, h = (1 + c) 0.5, den = h (a2 - 1) + 1, a2 = (rho rho)(rho rho) —
+    with w = 0 where !(c > 0): those sources are skipped"""
+    S, omega = probe_radiance_sources(pr.resolution)
+    T = probe_depth_dirs(pr.resolutions[level]).reshape(-1, 3)
+    rho = float(np.float32(pr.roughness[level]))
+    a = rho * rho
+    a2 = a * a
+    c = (T[:, None, 0] * S[None, :, 0] + T[:, None, 1] * S[None, :, 1]) + T[:, None, 2] * S[None, :, 2]
+    h = (1.0 + c) * 0.5
+    den = h * (a2 - 1.0) + 1.0
+    w = ((a2 / (den * den)) * c) * omega[None, :]
+    return np.where(c > 0.0, w, 0.0), c, den
+
+
+def probe_radiance_prefilter(pr: "ProbeRadiance", sums, terms: bool = False):
+    """The numpy statement of fw_probe_radiance_prefilter: maps (N, M, 4) float32 from the float32 running sums (N, R, R, 4).  Level 0 is
+    float32((double)A_c / W) with flag 1, zeros where W == 0; a texel of a level >= 1 is float32(A_c / Wt) over the flagged source texels
+    of level 0 in ascending id with probe_radiance_weights' weights, zeros where Wt == 0.  terms=True: returns (maps, X), X a list with one
+    dict per level >= 1 of the float64 values before the rounding: "q" (N, R_l^2, 3), "Wt" (N, R_l^2), "B" (N, R_l^2, 3) = sum w |L|, and
+    "on" (N, R^2), the sources' flags."""
+    R, M = int(pr.resolution), int(pr.texels)
+    s = np.asarray(sums, np.float32).astype(np.float64).reshape(-1, R * R, 4)
+    n = s.shape[0]
+    maps = np.zeros((n, M, 4), np.float32)
+    X = []
+    with np.errstate(all="ignore"):
+        none = s[..., 3] == 0.0
+        lv0 = np.where(none[..., None], 0.0, s[..., 0:3] / s[..., 3:4]).astype(np.float32)
+        maps[:, :R * R, 0:3] = lv0
+        maps[:, :R * R, 3] = np.where(none, 0.0, 1.0)
+        L0 = lv0.astype(np.float64)
+        for l in range(1, pr.levels):
+            w, c, _den = probe_radiance_weights(pr, l)
+            m = w.shape[0]
+            A, B, Wt = np.zeros((n, m, 3)), np.zeros((n, m, 3)), np.zeros((n, m))
+            for j in range(R * R):
+                on = (~none[:, j])[:, None] & (c[None, :, j] > 0.0)                        # (n, m)
+                term = w[None, :, j, None] * L0[:, None, j, :]
+                Wt = np.where(on, Wt + w[None, :, j], Wt)
+                A = np.where(on[..., None], A + term, A)
+                B = np.where(on[..., None], B + np.abs(term), B)
+            zero = Wt == 0.0
+            q = np.where(zero[..., None], 0.0, A / np.where(zero, 1.0, Wt)[..., None])
+            o = pr.offsets[l]
+            maps[:, o:o + m, 0:3] = q.astype(np.float32)
+            maps[:, o:o + m, 3] = np.where(zero, 0.0, 1.0)
+            X.append({"q": q, "Wt": Wt, "B": B, "on": ~none})
+    return (maps, X) if terms else maps
+
+
+def probe_radiance_fetch(R: int, maps, dirs):
+    """(M, 3) float64: the bilinear fetch of the header along the unit directions dirs (M, 3) from the level maps (M, R * R, 4) — one map
+    per direction — edges clamped, the flags not read"""
+    R = int(R)
+    m = np.asarray(maps, np.float32).astype(np.float64).reshape(-1, R, R, 4)[..., 0:3]
+    v = np.asarray(dirs, np.float64).reshape(-1, 3)
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    rows = np.arange(m.shape[0])
+    with np.errstate(all="ignore"):
+        s1 = (np.abs(x) + np.abs(y)) + np.abs(z)
+        ox, oy = x / s1, y / s1
+        fx, fy = (1.0 - np.abs(oy)) * _sgn1(ox), (1.0 - np.abs(ox)) * _sgn1(oy)
+        ox, oy = np.where(z < 0.0, fx, ox), np.where(z < 0.0, fy, oy)
+        top = float(R) - 1.0
+        su = np.fmin(np.fmax(((ox + 1.0) * 0.5) * float(R) - 0.5, 0.0), top)
+        sv = np.fmin(np.fmax(((oy + 1.0) * 0.5) * float(R) - 0.5, 0.0), top)
+        iu, jv = np.fmin(np.floor(su), top - 1.0), np.fmin(np.floor(sv), top - 1.0)
+        fu, fv = su - iu, sv - jv
+        i, j = iu.astype(np.int64), jv.astype(np.int64)
+        m00, m10, m01, m11 = m[rows, j, i], m[rows, j, i + 1], m[rows, j + 1, i], m[rows, j + 1, i + 1]
+        gu, gv = (1.0 - fu)[:, None], (1.0 - fv)[:, None]
+        return ((m00 * gu + m10 * fu[:, None]) * gv) + ((m01 * gu + m11 * fu[:, None]) * fv[:, None])
+
+
+def probe_radiance_level(pr: "ProbeRadiance", roughness):
+    """(l, t): the lower level of the pair a lookup at `roughness` (float64 array) blends, and the blend — rho clamped to the chain's
+    range, l the largest level with rho_l <= rho capped at L - 2, t = (rho - rho_l) / (rho_(l+1) - rho_l); with one level (0, 0)"""
+    rough = np.asarray(roughness, np.float64)
+    rr = [float(np.float32(v)) for v in pr.roughness]
+    if pr.levels == 1:
+        return np.zeros(rough.shape, np.int64), np.zeros(rough.shape)
+    rho = np.fmin(np.fmax(rough, rr[0]), rr[-1])
+    l = np.zeros(rough.shape, np.int64)
+    for k in range(1, pr.levels - 1):
+        l = np.where(rr[k] <= rho, k, l)
+    lo, hi = np.asarray(rr)[l], np.asarray(rr)[l + 1]
+    return l, (rho - lo) / (hi - lo)
+
+
+def probe_radiance_lookup(grid, pr: "ProbeRadiance", maps, positions, normals, dirs, roughness, pd: "ProbeDepth" = None, moments=None,
+                          normal_bias: float = 0.0, placement=None, terms: bool = False):
+    """The numpy float64 statement of fw_probe_radiance_lookup (include/firework_hip.h): the corner weights of probe_lookup_placed
+    (placement None: every record (0, 0, 0, 1)), and per active corner the rgb of the level pair probe_radiance_level picks, each fetched
+    bilinearly along r = dirs / |dirs| and blended m = m_l (1 - t) + m_(l+1) t (one level: m = m_0); Out_c = sum (w_d / wsum) m_c.  Zeros
+    for a non-finite position, normal, dir or roughness, a zero normal or dir, no active corner or a zero weight sum.  maps (n, M, 4)
+    float32.  terms=True: returns (E, T, X): T = sum |w_d| (|m_l| (1 - t) + |m_(l+1)| t) with the fetches taken of the texels'
+    magnitudes, and X probe_lookup_placed's terms with "probe" (N, corners), "level" and "t" (N,)."""
+    g = ProbeGrid.of(grid)
+    M = int(pr.texels)
+    mp = np.asarray(maps, np.float32).reshape(g.n_probes, M, 4)
+    if placement is None:
+        placement = np.tile(np.array([0.0, 0.0, 0.0, 1.0], np.float32), (g.n_probes, 1))
+    p32 = np.asarray(positions, np.float32).reshape(-1, 3)
+    n = p32.shape[0]
+    _E, _T, X = probe_lookup_placed(g, np.zeros((g.n_probes, 9, 3), np.float32), placement, p32, normals, pd, moments, normal_bias, terms=True)
+    dv = np.asarray(dirs, np.float32).astype(np.float64).reshape(-1, 3)
+    ro = np.asarray(roughness, np.float32).astype(np.float64).reshape(-1)
+    p = p32.astype(np.float64)
+    E, T = np.zeros((n, 3)), np.zeros((n, 3))
+    with np.errstate(all="ignore"):
+        dl2 = (dv[:, 0] * dv[:, 0] + dv[:, 1] * dv[:, 1]) + dv[:, 2] * dv[:, 2]
+        ok = np.all(np.isfinite(dv), axis=1) & np.isfinite(ro) & (dl2 > 0.0)
+        r = dv / np.sqrt(dl2)[:, None]
+        r = np.where(ok[:, None], r, (0.0, 0.0, 1.0))
+        level, t = probe_radiance_level(pr, np.where(ok, ro, 0.0))
+        pos = np.where(np.all(np.isfinite(p), axis=1)[:, None], p, 0.0)
+        idx = []
+        for k in range(3):
+            c = g.counts[k]
+            if c > 1:
+                cm1 = float(c - 1)
+                s = np.fmin(np.fmax(((pos[:, k] - g.lo[k]) / (g.hi[k] - g.lo[k])) * cm1, 0.0), cm1)
+                idx.append(np.fmin(np.floor(s), cm1 - 1.0).astype(np.int64))
+            else:
+                idx.append(np.zeros(n, np.int64))
+        two = [c > 1 for c in g.counts]
+        corners = [(dx, dy, dz) for dz in range(2 if two[2] else 1) for dy in range(2 if two[1] else 1) for dx in range(2 if two[0] else 1)]
+        probes = []
+        for ci, d in enumerate(corners):
+            probe = ((idx[2] + d[2]) * g.counts[1] + (idx[1] + d[1])) * g.counts[0] + (idx[0] + d[0])
+            probes.append(probe)
+            wd, on = X["w"][:, ci], X["active"][:, ci] & ok
+            m, ma = np.zeros((n, 3)), np.zeros((n, 3))
+            for l in range(pr.levels):
+                Rl, o = pr.resolutions[l], pr.offsets[l]
+                lower, upper = level == l, (level + 1 == l) & (pr.levels > 1)
+                if not (lower.any() or upper.any()):
+                    continue
+                tex = mp[probe, o:o + Rl * Rl]
+                f = probe_radiance_fetch(Rl, tex, r)
+                fa = probe_radiance_fetch(Rl, np.abs(tex), r)
+                if pr.levels == 1:
+                    m, ma = f, fa
+                else:
+                    m = np.where(lower[:, None], f * (1.0 - t)[:, None], m)
+                    ma = np.where(lower[:, None], fa * (1.0 - t)[:, None], ma)
+                    m = np.where(upper[:, None], m + f * t[:, None], m)
+                    ma = np.where(upper[:, None], ma + fa * t[:, None], ma)
+            E = np.where(on[:, None], E + wd[:, None] * m, E)
+            T = np.where(on[:, None], T + np.abs(wd)[:, None] * ma, T)
+    some = ok & (np.abs(X["w"]).sum(axis=1) != 0.0)
+    E[~some] = 0.0
+    T[~some] = 0.0
+    if not terms:
+        return E
+    X = dict(X)
+    X["probe"], X["level"], X["t"] = np.stack(probes, axis=-1), level, t
+    return E, T, X
+
+
+def probe_glossy_ref(aov, spec, view, diffuse, radiance=None, *, grid=None, pr: "ProbeRadiance" = None, maps=None, pd: "ProbeDepth" = None,
+                     moments=None, normal_bias: float = 0.0, placement=None):
+    """The float32 statement of fw_probe_shade_glossy's linear output, (N, 3) float32: a pixel with !(rho > 0) takes `diffuse` (N, 3), the
+    linear output of the placed shade of the same records; a glossy pixel is v (F Ls) + (1 - v) a with F_c = f0_c + (1 - f0_c) float32(S),
+    S = ((m m)(m m)) m, m = 1 - min(1, max(0, -(nh.u))), u = view / |view|, and Ls = max(radiance, 0): the lookup along
+    r = float32(u - (2 (nh.u)) nh) at rho, as probe_glossy_dirs returns it — `radiance` (N, 3) float32 when given (the device lookup's
+    own output), else probe_radiance_lookup over grid, pr, maps and the optional terms.  Ls = 0 and S = 0 for an unusable view, normal
+    or position."""
+    a = np.asarray(aov, np.float32).reshape(-1, 12)
+    sp = np.asarray(spec, np.float32).reshape(-1, 4)
+    r, S, ok = probe_glossy_dirs(aov, view)
+    if radiance is None:
+        radiance = probe_radiance_lookup(grid, pr, maps, a[:, 8:11], a[:, 4:7], r, sp[:, 3], pd, moments, normal_bias, placement).astype(np.float32)
+    with np.errstate(all="ignore"):
+        Ls = np.asarray(radiance, np.float32).reshape(-1, 3)
+        Ls = np.where(ok[:, None] & (Ls > 0), Ls, np.float32(0.0)).astype(np.float32)
+        Sf = np.where(ok, S, 0.0).astype(np.float32)[:, None]
+        f0, v, one = sp[:, 0:3], a[:, 3:4], np.float32(1.0)
+        F = (f0 + (one - f0) * Sf).astype(np.float32)
+        out = (v * (F * Ls) + (one - v) * a[:, 0:3]).astype(np.float32)
+    glossy = sp[:, 3] > 0
+    return np.where(glossy[:, None], out, np.asarray(diffuse, np.float32).reshape(-1, 3)).astype(np.float32)
+
+
+def material_spec_table(desc: "SceneDesc") -> np.ndarray:
+    """(n_materials + 1, 4) float32: fw_probe_shade_glossy's (F0.rgb, rho) of every material of a scene description — a GgxMat (albedo,
+    roughness), a MetalMat (albedo, roughness clipped to [0.03, 1]), every other material zeros (rho = 0: diffuse) — and a last row of
+    zeros for a miss"""
+    n = int(desc.desc.n_materials)
+    table = np.zeros((n + 1, 4), np.float32)
+    for i in range(n):
+        m = desc.materials[i]
+        if m.kind in (A.FW_MAT_GGX, A.FW_MAT_METAL):
+            rho = np.float32(m.roughness)
+            if m.kind == A.FW_MAT_METAL:
+                rho = np.float32(min(max(rho, np.float32(0.03)), np.float32(1.0)))
+            table[i] = (m.albedo.x, m.albedo.y, m.albedo.z, rho)
+    return table
+
+
+def probe_glossy_dirs(aov, view):
+    """(r, S, ok) of fw_probe_shade_glossy: r (N, 3) float32, the view direction mirrored about the record's unit normal; S (N,) float64,
+    Schlick's weight; ok (N,), False where the view, the normal or the position is not finite or the view or the normal is zero (r is
+    then (0, 0, 1) and S 0)"""
+    a = np.asarray(aov, np.float32).reshape(-1, 12).astype(np.float64)
+    vw = np.asarray(view, np.float32).astype(np.float64).reshape(-1, 3)
+    nr = a[:, 4:7]
+    with np.errstate(all="ignore"):
+        nl2 = (nr[:, 0] * nr[:, 0] + nr[:, 1] * nr[:, 1]) + nr[:, 2] * nr[:, 2]
+        vl2 = (vw[:, 0] * vw[:, 0] + vw[:, 1] * vw[:, 1]) + vw[:, 2] * vw[:, 2]
+        ok = (np.all(np.isfinite(a[:, 8:11]), axis=1) & np.all(np.isfinite(nr), axis=1) & np.all(np.isfinite(vw), axis=1) & (nl2 > 0.0)
+              & (vl2 > 0.0))
+        nh = nr / np.sqrt(nl2)[:, None]
+        u = vw / np.sqrt(vl2)[:, None]
+        c = (nh[:, 0] * u[:, 0] + nh[:, 1] * u[:, 1]) + nh[:, 2] * u[:, 2]
+        r = (u - (2.0 * c)[:, None] * nh).astype(np.float32)
+        m = 1.0 - np.fmin(1.0, np.fmax(0.0, -c))
+        S = ((m * m) * (m * m)) * m
+    return np.where(ok[:, None], r, np.float32([0.0, 0.0, 1.0])).astype(np.float32), np.where(ok, S, 0.0), ok
+
+
 # --------------------------------------------------------------------------- lightmaps (fw_bake_lightmap; DESIGN.md §9o)
 LIGHTMAP_NO_OWNER = 0xFFFFFFFF          # FW_NO_HIT in an owner map
 
@@ -2550,6 +2854,27 @@ class Renderer:
             if ds is not scene:
                 ds.close()
 
+    def bake_probe_radiance(self, scene, probes: "ProbeSet", pr: "ProbeRadiance", rounds: int = 1, first_round: int = 0, sums=None,
+                            on_device: bool = False, chunk=0, with_sh: bool = False, sh_sums=None, device: int = 0, stream=None):
+        """The radiance maps of a probe set baked on the device (not in the reference; fw_bake_probe_radiance): bake_probes'
+        rounds — the same rays, rendered with settings["samples"] paths per direction and this renderer's seed (+ the round), use_bvh,
+        batch size and flags — reduced into every probe's octahedral map and prefiltered for the roughness chain of pr.  Returns (maps,
+        sums): (N, M, 4) and (N, R, R, 4) float32; pass sums back with first_round = the rounds it holds to add more.  with_sh: the same
+        rendered rays are also projected as bake_probes projects them, and (maps, sums, sh, sh_sums) is returned (sh_sums: bake_probes'
+        running sums to add to).  on_device and chunk as _lib.DeviceScene.bake_probe_radiance; the call's stats are kept in
+        self.probe_radiance_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        from . import _lib
+        s = self.settings
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            out = ds.bake_probe_radiance(probes, pr, rounds, s["samples"], first_round, sums, sh_sums, with_sh, seed=s["seed"], use_bvh=s["use_bvh"],
+                                         stream=stream, paths_per_batch=s["paths_per_batch"], flags=s["flags"], chunk=chunk, on_device=on_device)
+            self.probe_radiance_stats = out[-1]
+            return out[:-1]
+        finally:
+            if ds is not scene:
+                ds.close()
+
     def relocate_probes(self, scene, probes: "ProbeSet", relocation: "ProbeRelocation", first_step: int = 0, placement=None, chunk=None,
                         device: int = 0, stream=None):
         """Probes moved out of geometry and classified on the device (not in the reference; fw_relocate_probes):
@@ -2641,7 +2966,7 @@ class Renderer:
 
     def render_probe_lit(self, scene, probes, sh, aov_samples: int = 8, wrap: bool = True, device: int = 0, model: "CameraModel" = None,
                          depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0, ao: "AmbientOcclusion" = None,
-                         ao_rounds: int = 1, placement=None) -> RenderResult:
+                         ao_rounds: int = 1, placement=None, radiance: "ProbeRadiance" = None, maps=None) -> RenderResult:
         """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
         (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
         from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
@@ -2655,11 +2980,20 @@ class Renderer:
         out_c = a_c (v (ao (E_c float32(1 / pi))) + (1 - v)) in float32, resolved by fw_denoise at 0 iterations.  ao=None: the calls and
         the bits above.  placement ((n, 4), as relocate_probes returns it): the frame is shaded by fw_probe_shade_placed
         — with ao, E is looked up by fw_probe_irradiance_placed — with or without depth; sh and moments are expected to have been baked
-        at probes.moved(placement).  placement=None: the calls and the bits above."""
+        at probes.moved(placement).  placement=None: the calls and the bits above.  radiance (a ProbeRadiance) with maps ((n, M, 4), as
+        bake_probe_radiance returns them): conductors show reflections.  The view's sample-0 rays (fw_camera_rays; with
+        `model`, fw_model_rays) are traced on the device by fw_trace_rays; each hit's material gives the pixel's (F0, rho) — a GgxMat
+        (albedo, roughness), a MetalMat (albedo, roughness clipped to [0.03, 1]), every other material and every miss rho = 0 — and the
+        frame is shaded by fw_probe_shade_glossy with those rays' directions as the view, with or without depth and placement.
+        radiance=None: the calls and the bits above.  radiance together with ao: ValueError."""
         import torch
         from . import _lib
         if depth is not None and moments is None:
             raise ValueError("depth needs the moments bake_probe_depth returned")
+        if radiance is not None and maps is None:
+            raise ValueError("radiance needs the maps bake_probe_radiance returned")
+        if radiance is not None and ao is not None:
+            raise ValueError("radiance and ao cannot be combined: the ambient-occlusion frame has no specular term")
         if ao is not None:
             ao.check()
         grid = ProbeGrid.of(probes, wrap)
@@ -2695,6 +3029,18 @@ class Renderer:
                 v = aov[:, 3:4]
                 lit = aov[:, 0:3] * (v * (occ[:, 3:4] * (E * float(np.float32(1.0 / np.pi)))) + (1.0 - v))
                 rgb8, gam, lin = _lib.denoise(lit.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
+            elif radiance is not None:
+                d_maps = torch.from_numpy(np.ascontiguousarray(np.asarray(maps, np.float32).reshape(grid.n_probes, radiance.texels, 4))).to(dev)
+                if model is not None:
+                    rays = _lib.model_rays(model, 0, 1, ds.device, out=torch.empty((1, w * h, 6), dtype=torch.float32, device=dev))[0]
+                else:
+                    rays = torch.from_numpy(ds.camera_rays(self, 0)).to(dev)
+                hit = _lib.hit_fields(ds.trace(rays, s["use_bvh"], seed=s["seed"]))
+                table = torch.from_numpy(material_spec_table(ds._desc)).to(dev)
+                miss = torch.full_like(hit["material"], table.shape[0] - 1)
+                spec = table[torch.where(hit["object"] == -1, miss, hit["material"]).long()].contiguous()
+                rgb8, gam, lin = _lib.probe_shade_glossy(grid, d_sh, radiance, d_maps, aov, spec, rays[:, 3:6], w, h, depth, d_mom, normal_bias, d_pl,
+                                                         s["gamma"], ds.device)
             elif d_pl is not None:
                 rgb8, gam, lin = _lib.probe_shade_placed(grid, d_sh, d_pl, aov, w, h, depth, d_mom, normal_bias, s["gamma"], ds.device)
             elif depth is not None:

@@ -1,0 +1,579 @@
+// fw_probe_radiance.hip — probe radiance maps for gfx950: the reduction of rendered radiance into per-probe octahedral maps, their GGX
+// prefilter, the lookup of reflected radiance and the glossy probe shade (include/firework_hip.h has the statement, DESIGN.md §9v the
+// design).
+//
+//   k_probe_radiance_reduce     k_probe_depth's structure with radiance in the place of distance: one workgroup of 256 lanes per probe.
+//                               256 directions at a time, lane l turns ray and accum c0 + l (12 B of direction, 16 B of accum) into
+//                               (d.xyz, L.rgb) in float64 and stages the 48 B in LDS (12 KB); after the barrier every lane walks the staged
+//                               chunk in ascending j for its texels t = lane, lane + 256, ... (at most four, R = 32) with broadcast reads.
+//                               A texel's four float64 accumulators stay in registers across the chunks; at the end each is rounded to
+//                               float32 once and added to the texel's running sums with one float32 addition.  A texel is one lane's and
+//                               its sum is sequential in j: no atomics, no dependence on the launch geometry.
+//   k_probe_radiance_prefilter  one workgroup of 256 lanes per probe, grid-stride over probes.  A probe-independent table of the source
+//                               texels' (S.xyz, omega) in float64 is computed once per workgroup into LDS (32 B x R^2, 32 KB at R = 32); the
+//                               current probe's level 0 is divided out of its sums, written, and staged beside the table as float4 (16 KB).
+//                               Lane l owns the output texels l, l + 256 of the levels >= 1 (336 at R = 32, so at most two) and walks the
+//                               source in ascending id with broadcast LDS reads, four float64 accumulators per owned texel in registers.
+//                               48 KB of static LDS: three workgroups per CU.
+//   k_probe_radiance_lookup     one lane per point: the placed lookup's corner weights, then per active corner two bilinear fetches of
+//                               four 16-byte texels each.  No LDS, no atomics, no barrier.
+//   k_probe_shade_glossy        one lane per pixel: fw_probe_shade_placed's arithmetic where rho is not > 0, else the lookup along the
+//                               mirrored view direction under a Schlick Fresnel term.
+//
+// Every maps index is formed from a clamped cell index and texel indices clamped to [0, R_l - 2] plus 0 or 1, so no load leaves the
+// arrays wherever the point lies and whatever the maps hold.  No inline assembly anywhere.
+//
+// A file of its own, last on the link line: the code objects of the other files stay byte for byte what they were.  What it needs of
+// fw_probe_depth.hip (the texel centres, sgn, the fold, the bilinear fetch), of fw_probe_place.hip (the placed corner weights and the SH
+// sum) and of fw_kernels.hip (fdiv, resolve_pixel) is restated here: the same bits.
+//
+// Numerics: -ffp-contract=off, so + - * / round as written and in the order of api.probe_radiance_reduce / _prefilter / _lookup; floor,
+// min, max and fabs are exact; sqrt is the device library's float64 function.
+#include "fw_probe_radiance.h"
+#include "fw_libm.h"
+#include <algorithm>
+#include <cmath>
+
+namespace fw {
+namespace {
+
+constexpr int PR_BLOCK = 256;
+constexpr int PR_MAXT = 4;                      // reduce: texels per lane at R = 32
+constexpr int PF_MAXO = 2;                      // prefilter: output texels per lane at R = 32, four levels (256 + 64 + 16 = 336)
+constexpr int PF_MAXSRC = 32 * 32;              // prefilter: source texels at R = 32
+constexpr int PL_BLOCK = 256;                   // the lookup and the shade
+
+__device__ __forceinline__ double sgn1(double v) { return v >= 0.0 ? 1.0 : -1.0; }      // sgn(0) = +1
+
+// texel t = b R + a of an R x R octahedral map: its centre on the octahedron (x, y, z) and that point's length
+__device__ __forceinline__ double texel_point(uint32_t t, uint32_t R, double &x, double &y, double &z) {
+    const uint32_t b = t / R, a = t - b * R;
+    const double Rd = (double)R;
+    const double ex = (((double)a + 0.5) * 2.0) / Rd - 1.0, ey = (((double)b + 0.5) * 2.0) / Rd - 1.0;
+    z = (1.0 - fabs(ex)) - fabs(ey);
+    x = ex; y = ey;
+    if (z < 0.0) { x = (1.0 - fabs(ey)) * sgn1(ex); y = (1.0 - fabs(ex)) * sgn1(ey); }
+    return sqrt((x * x + y * y) + z * z);
+}
+// the unit direction of that texel (fw_probe_depth.hip's texel_dir)
+__device__ __forceinline__ void texel_dir(uint32_t t, uint32_t R, double T[3]) {
+    double x, y, z;
+    const double l = texel_point(t, R, x, y, z);
+    T[0] = x / l; T[1] = y / l; T[2] = z / l;
+}
+
+__global__ __launch_bounds__(PR_BLOCK) void k_probe_radiance_reduce(uint32_t n_probes, uint32_t directions, uint32_t R, uint32_t k, double samples,
+                                                                    const float *__restrict__ rays, const float4 *__restrict__ accum,
+                                                                    float4 *__restrict__ sums) {
+    __shared__ double st[PR_BLOCK * 6];                                                 // (dx, dy, dz, Lr, Lg, Lb) of the staged directions
+    const uint32_t lane = threadIdx.x;
+    const uint32_t n_tex = R * R;
+    const uint32_t nq = (n_tex + PR_BLOCK - 1u) / PR_BLOCK;                             // wave-uniform: 1, or 4 at R = 32
+    double T[PR_MAXT][3];
+#pragma unroll
+    for (int q = 0; q < PR_MAXT; q++) {
+        T[q][0] = T[q][1] = T[q][2] = 0.0;
+        const uint32_t t = lane + (uint32_t)q * PR_BLOCK;
+        if (t < n_tex) texel_dir(t, R, T[q]);
+    }
+    for (uint32_t p = blockIdx.x; p < n_probes; p += gridDim.x) {
+        const size_t base = (size_t)p * directions;                                    // < 2^31
+        double A0[PR_MAXT], A1[PR_MAXT], A2[PR_MAXT], W[PR_MAXT];
+#pragma unroll
+        for (int q = 0; q < PR_MAXT; q++) { A0[q] = 0.0; A1[q] = 0.0; A2[q] = 0.0; W[q] = 0.0; }
+        for (uint32_t c0 = 0; c0 < directions; c0 += PR_BLOCK) {
+            const uint32_t cnt = min((uint32_t)PR_BLOCK, directions - c0);
+            if (lane < cnt) {
+                const size_t e = base + c0 + lane;
+                const float *r = rays + e * 6u + 3u;
+                const float4 a = accum[e];
+                double *s = st + lane * 6u;
+                s[0] = (double)r[0]; s[1] = (double)r[1]; s[2] = (double)r[2];
+                s[3] = (double)a.x / samples; s[4] = (double)a.y / samples; s[5] = (double)a.z / samples;
+            }
+            __syncthreads();
+            for (uint32_t j = 0; j < cnt; j++) {
+                const double dx = st[j * 6u], dy = st[j * 6u + 1u], dz = st[j * 6u + 2u];
+                const double l0 = st[j * 6u + 3u], l1 = st[j * 6u + 4u], l2 = st[j * 6u + 5u];
+#pragma unroll
+                for (int q = 0; q < PR_MAXT; q++) {
+                    if ((uint32_t)q < nq && lane + (uint32_t)q * PR_BLOCK < n_tex) {
+                        double w = fmax(0.0, (T[q][0] * dx + T[q][1] * dy) + T[q][2] * dz);
+                        for (uint32_t s = 0; s < k; s++) w = w * w;
+                        if (w > 0.0) {                                                  // a ray outside the lobe never touches the texel
+                            A0[q] = A0[q] + w * l0;
+                            A1[q] = A1[q] + w * l1;
+                            A2[q] = A2[q] + w * l2;
+                            W[q] = W[q] + w;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int q = 0; q < PR_MAXT; q++) {
+            const uint32_t t = lane + (uint32_t)q * PR_BLOCK;
+            if (t < n_tex) {
+                float4 *s = sums + ((size_t)p * n_tex + t);                             // < 2^31 texels
+                float4 v = *s;
+                v.x = v.x + (float)A0[q]; v.y = v.y + (float)A1[q]; v.z = v.z + (float)A2[q]; v.w = v.w + (float)W[q];
+                *s = v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(PR_BLOCK) void k_probe_radiance_prefilter(uint32_t n_probes, DProbeRadiance pr, const float4 *__restrict__ sums,
+                                                                       float4 *__restrict__ maps) {
+    __shared__ double tab[PF_MAXSRC * 4];                                               // (Sx, Sy, Sz, omega) of the source texels: 32 KB
+    __shared__ float4 lv0[PF_MAXSRC];                                                   // the current probe's level 0: 16 KB
+    const uint32_t lane = threadIdx.x;
+    const uint32_t R = pr.R, n_src = R * R, M = pr.texels, n_out = M - n_src;          // n_out <= 336
+    const double Rd = (double)R;
+    const double cell = 4.0 / (Rd * Rd);
+    for (uint32_t s = lane; s < n_src; s += PR_BLOCK) {
+        double x, y, z;
+        const double len = texel_point(s, R, x, y, z);
+        double *e = tab + s * 4u;
+        e[0] = x / len; e[1] = y / len; e[2] = z / len;
+        e[3] = cell / ((len * len) * len);
+    }
+    // the lane's output texels o = lane, lane + 256 of the levels >= 1, counted from the start of level 1
+    double T[PF_MAXO][3], am1[PF_MAXO], a2[PF_MAXO];
+    bool own[PF_MAXO];
+#pragma unroll
+    for (int q = 0; q < PF_MAXO; q++) {
+        T[q][0] = T[q][1] = T[q][2] = 0.0; am1[q] = 0.0; a2[q] = 0.0;
+        const uint32_t o = lane + (uint32_t)q * PR_BLOCK;
+        own[q] = o < n_out;
+        if (own[q]) {
+            uint32_t off = 0u;
+            for (uint32_t l = 1u; l < pr.levels; l++) {
+                const uint32_t Rl = R >> l, nl = Rl * Rl;
+                if (o < off + nl) {
+                    texel_dir(o - off, Rl, T[q]);
+                    const double rho = l == 1u ? pr.rho[1] : (l == 2u ? pr.rho[2] : pr.rho[3]);
+                    const double a = rho * rho;
+                    a2[q] = a * a;
+                    am1[q] = a2[q] - 1.0;
+                    break;
+                }
+                off += nl;
+            }
+        }
+    }
+    const bool second = n_out > (uint32_t)PR_BLOCK;                                     // wave-uniform: only R = 32 with four levels
+    for (uint32_t p = blockIdx.x; p < n_probes; p += gridDim.x) {
+        float4 *__restrict__ out = maps + (size_t)p * M;                                // n_probes x M < 2^31 texels
+        const float4 *__restrict__ in = sums + (size_t)p * n_src;
+        for (uint32_t s = lane; s < n_src; s += PR_BLOCK) {
+            const float4 v = in[s];
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!(v.w == 0.f)) {
+                const double W = (double)v.w;
+                o.x = (float)((double)v.x / W); o.y = (float)((double)v.y / W); o.z = (float)((double)v.z / W); o.w = 1.f;
+            }
+            lv0[s] = o;
+            out[s] = o;
+        }
+        __syncthreads();                                                                // the table (first pass) and level 0 are in LDS
+        if (n_out > 0u) {
+            double A0[PF_MAXO], A1[PF_MAXO], A2[PF_MAXO], Wt[PF_MAXO];
+#pragma unroll
+            for (int q = 0; q < PF_MAXO; q++) { A0[q] = 0.0; A1[q] = 0.0; A2[q] = 0.0; Wt[q] = 0.0; }
+            for (uint32_t s = 0; s < n_src; s++) {
+                const float4 L = lv0[s];                                                // broadcast reads: every lane the same address
+                if (L.w == 0.f) continue;                                               // workgroup-uniform
+                const double Sx = tab[s * 4u], Sy = tab[s * 4u + 1u], Sz = tab[s * 4u + 2u], om = tab[s * 4u + 3u];
+                const double l0 = (double)L.x, l1 = (double)L.y, l2 = (double)L.z;
+#pragma unroll
+                for (int q = 0; q < PF_MAXO; q++) {
+                    if ((q == 0 || second) && own[q]) {
+                        const double c = (T[q][0] * Sx + T[q][1] * Sy) + T[q][2] * Sz;
+                        if (c > 0.0) {
+                            const double h = (1.0 + c) * 0.5;
+                            const double den = h * am1[q] + 1.0;
+                            const double w = ((a2[q] / (den * den)) * c) * om;
+                            Wt[q] = Wt[q] + w;
+                            A0[q] = A0[q] + w * l0;
+                            A1[q] = A1[q] + w * l1;
+                            A2[q] = A2[q] + w * l2;
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < PF_MAXO; q++) {
+                if (own[q]) {
+                    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (!(Wt[q] == 0.0)) { o.x = (float)(A0[q] / Wt[q]); o.y = (float)(A1[q] / Wt[q]); o.z = (float)(A2[q] / Wt[q]); o.w = 1.f; }
+                    out[n_src + lane + (uint32_t)q * PR_BLOCK] = o;                     // < M: own[q]
+                }
+            }
+        }
+        __syncthreads();                                                                // level 0 is overwritten by the next probe
+    }
+}
+
+// the constants of fw_probe_lookup.hip's LookupConst, restated
+struct RadConst { double y0, c1, c2, c6, c8, a0, a1, a2; };
+
+__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.40282347e+38f; }   // false for NaN and +-inf
+
+// where a unit direction falls in an R x R octahedral map: the first texel (column iu, row jv, both in [0, R - 2] whatever the
+// direction is) of the four that the bilinear fetch reads, and the fractions (fw_probe_depth.hip's depth_fetch)
+__device__ __forceinline__ void octa_cell(uint32_t R, double x, double y, double z, uint32_t &iu, uint32_t &jv, double &fu, double &fv) {
+    const double s1 = (fabs(x) + fabs(y)) + fabs(z);
+    double ox = x / s1, oy = y / s1;
+    if (z < 0.0) {
+        const double fx = (1.0 - fabs(oy)) * sgn1(ox), fy = (1.0 - fabs(ox)) * sgn1(oy);
+        ox = fx; oy = fy;
+    }
+    const double Rd = (double)R, top = Rd - 1.0;
+    const double su = fmin(fmax(((ox + 1.0) * 0.5) * Rd - 0.5, 0.0), top), sv = fmin(fmax(((oy + 1.0) * 0.5) * Rd - 0.5, 0.0), top);
+    const double i = fmin(floor(su), top - 1.0), j = fmin(floor(sv), top - 1.0);         // fmin and fmax drop a NaN: still in [0, R - 2]
+    fu = su - i; fv = sv - j;
+    iu = (uint32_t)i; jv = (uint32_t)j;
+}
+
+// depth_fetch of fw_probe_depth.hip over octa_cell
+__device__ __forceinline__ void depth_fetch(const float *__restrict__ m, uint32_t R, double x, double y, double z, double &mu, double &mu2) {
+    uint32_t iu, jv;
+    double fu, fv;
+    octa_cell(R, x, y, z, iu, jv, fu, fv);
+    const float *__restrict__ r0 = m + ((size_t)(jv * R + iu)) * 2u;
+    const float *__restrict__ r1 = r0 + (size_t)R * 2u;
+    const double gu = 1.0 - fu, gv = 1.0 - fv;
+    mu = (((double)r0[0] * gu + (double)r0[2] * fu) * gv) + (((double)r1[0] * gu + (double)r1[2] * fu) * fv);
+    mu2 = (((double)r0[1] * gu + (double)r0[3] * fu) * gv) + (((double)r1[1] * gu + (double)r1[3] * fu) * fv);
+}
+
+// the rgb of one level (R x R texels of 16 B at `m`) along the unit direction (x, y, z): bilinear, edges clamped; the flags are not read
+__device__ __forceinline__ void radiance_fetch(const float4 *__restrict__ m, uint32_t R, double x, double y, double z, double c[3]) {
+    uint32_t iu, jv;
+    double fu, fv;
+    octa_cell(R, x, y, z, iu, jv, fu, fv);
+    const float4 *__restrict__ r0 = m + (size_t)(jv * R + iu);
+    const float4 *__restrict__ r1 = r0 + R;
+    const float4 t00 = r0[0], t10 = r0[1], t01 = r1[0], t11 = r1[1];
+    const double gu = 1.0 - fu, gv = 1.0 - fv;
+    c[0] = (((double)t00.x * gu + (double)t10.x * fu) * gv) + (((double)t01.x * gu + (double)t11.x * fu) * fv);
+    c[1] = (((double)t00.y * gu + (double)t10.y * fu) * gv) + (((double)t01.y * gu + (double)t11.y * fu) * fv);
+    c[2] = (((double)t00.z * gu + (double)t10.z * fu) * gv) + (((double)t01.z * gu + (double)t11.z * fu) * fv);
+}
+
+// The corner weights of fw_probe_place.hip's probe_lookup_placed, restated: the unit normal, the probes of the cell's corners, the
+// weights of the active ones and their sum.  placement NULL: every record is (0, 0, 0, 1).
+struct Corners {
+    double x, y, z;             // the unit normal
+    double w[8], wsum;
+    uint32_t probe[8], active;
+    bool usable;                // the position and the normal are finite and the normal is not zero
+};
+
+template <bool DEPTH>
+__device__ __forceinline__ bool corner_weights(const DProbeGrid &G, const DProbeVis &V, const float *__restrict__ placement, float pxf, float pyf,
+                                               float pzf, float nxf, float nyf, float nzf, Corners &C) {
+    C.usable = false;
+    if (!(finite_f(pxf) && finite_f(pyf) && finite_f(pzf) && finite_f(nxf) && finite_f(nyf) && finite_f(nzf))) return false;
+    const double p[3] = {(double)pxf, (double)pyf, (double)pzf};
+    const double nx = (double)nxf, ny = (double)nyf, nz = (double)nzf;
+    const double nl2 = (nx * nx + ny * ny) + nz * nz;
+    if (!(nl2 > 0.0)) return false;
+    const double nl = sqrt(nl2);
+    const double x = nx / nl, y = ny / nl, z = nz / nl;
+    C.x = x; C.y = y; C.z = z;
+    C.usable = true;
+    double q[3] = {p[0], p[1], p[2]};
+    if (DEPTH) { q[0] = p[0] + V.bias * x; q[1] = p[1] + V.bias * y; q[2] = p[2] + V.bias * z; }
+
+    // the cell: the nominal grid's
+    uint32_t i[3];
+    double f[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        i[k] = 0u; f[k] = 0.0;
+        if (G.counts[k] > 1u) {
+            const double cm1 = (double)(G.counts[k] - 1u);
+            double s = ((p[k] - G.lo[k]) / G.span[k]) * cm1;
+            s = fmin(fmax(s, 0.0), cm1);
+            const double fl = fmin(floor(s), cm1 - 1.0);
+            i[k] = (uint32_t)fl;
+            f[k] = s - fl;
+        }
+    }
+    const bool two[3] = {G.counts[0] > 1u, G.counts[1] > 1u, G.counts[2] > 1u};      // wave-uniform: a flat axis has one corner
+    const size_t map_floats = DEPTH ? (size_t)V.R * V.R * 2u : 0u;
+
+    // the corner weights, corner d = 4 dz + 2 dy + dx
+    uint32_t active = 0u;
+    double wsum = 0.0;
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        const int dx = d & 1, dy = (d >> 1) & 1, dz = d >> 2;
+        C.w[d] = 0.0;
+        C.probe[d] = 0u;
+        if ((dx == 0 || two[0]) && (dy == 0 || two[1]) && (dz == 0 || two[2])) {
+            const uint32_t probe = ((i[2] + (uint32_t)dz) * G.counts[1] + (i[1] + (uint32_t)dy)) * G.counts[0] + (i[0] + (uint32_t)dx);   // < 2^31
+            C.probe[d] = probe;
+            float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+            if (placement) {
+                const float *__restrict__ pl = placement + (size_t)probe * 4u;
+                if (pl[3] == 0.f) continue;                                            // inactive: nothing of this probe is read
+                o0 = pl[0]; o1 = pl[1]; o2 = pl[2];
+            }
+            active |= 1u << d;
+            const double wx = dx ? f[0] : 1.0 - f[0], wy = dy ? f[1] : 1.0 - f[1], wz = dz ? f[2] : 1.0 - f[2];
+            const int dd[3] = {dx, dy, dz};
+            const double off[3] = {(double)o0, (double)o1, (double)o2};
+            double P[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) P[k] = (two[k] ? G.lo[k] + (double)(i[k] + (uint32_t)dd[k]) * G.step[k] : G.mid[k]) + off[k];
+            double fac = 1.0;
+            if (G.wrap) {
+                const double r[3] = {P[0] - p[0], P[1] - p[1], P[2] - p[2]};
+                const double rl2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+                fac = 1.2;
+                if (rl2 > 0.0) {
+                    const double rl = sqrt(rl2);
+                    const double dot = (x * (r[0] / rl) + y * (r[1] / rl)) + z * (r[2] / rl);
+                    const double h = 0.5 * (dot + 1.0);
+                    fac = h * h + 0.2;
+                }
+            }
+            double wd = (wx * wy) * wz;
+            if (DEPTH) {
+                // the visibility of this probe from the biased point
+                const double rv[3] = {q[0] - P[0], q[1] - P[1], q[2] - P[2]};
+                const double dist = sqrt((rv[0] * rv[0] + rv[1] * rv[1]) + rv[2] * rv[2]);
+                double v = 1.0;
+                if (dist != 0.0) {
+                    double mu, mu2;
+                    depth_fetch(V.moments + (size_t)probe * map_floats, V.R, rv[0] / dist, rv[1] / dist, rv[2] / dist, mu, mu2);
+                    if (!(dist <= mu)) {
+                        const double var = fabs(mu * mu - mu2);
+                        const double t = dist - mu;
+                        const double c = var / (var + t * t);
+                        v = (c * c) * c;
+                    }
+                }
+                double g = fmax(1e-6, fac * v);
+                if (g < 0.2) g = (g * (g * g)) * 25.0;
+                wd = wd * g;
+            } else if (G.wrap) {
+                wd = wd * fac;
+            }
+            wsum = wsum + wd;
+            C.w[d] = wd;
+        }
+    }
+    C.active = active;
+    C.wsum = wsum;
+    return !(wsum == 0.0);                                                             // false: no active corner, or none with a weight
+}
+
+// the SH sum of probe_lookup_placed over those corners: E[c] in float64 before its one rounding
+__device__ __forceinline__ void corners_sh(const Corners &C, const RadConst &K, const float *__restrict__ sh, double E[3]) {
+    const double x = C.x, y = C.y, z = C.z;
+    const double B[9] = {K.a0 * K.y0,           K.a1 * (K.c1 * y),       K.a1 * (K.c1 * z),
+                         K.a1 * (K.c1 * x),     K.a2 * ((K.c2 * x) * y), K.a2 * ((K.c2 * y) * z),
+                         K.a2 * (K.c6 * (3.0 * (z * z) - 1.0)), K.a2 * ((K.c2 * x) * z), K.a2 * (K.c8 * (x * x - y * y))};
+    double e0 = 0.0, e1 = 0.0, e2 = 0.0;
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        if (C.active & (1u << d)) {
+            const float *__restrict__ s = sh + (size_t)C.probe[d] * 27u;
+            double c0 = B[0] * (double)s[0], c1 = B[0] * (double)s[1], c2 = B[0] * (double)s[2];
+#pragma unroll
+            for (int k = 1; k < 9; k++) {
+                c0 = c0 + B[k] * (double)s[3 * k];
+                c1 = c1 + B[k] * (double)s[3 * k + 1];
+                c2 = c2 + B[k] * (double)s[3 * k + 2];
+            }
+            const double wd = C.w[d] / C.wsum;
+            e0 = e0 + wd * c0; e1 = e1 + wd * c1; e2 = e2 + wd * c2;
+        }
+    }
+    E[0] = e0; E[1] = e1; E[2] = e2;
+}
+
+// the radiance sum over those corners along (dx, dy, dz), which need not be a unit vector, at roughness `rough`: E[c] in float64 before
+// its one rounding; false for a direction or a roughness the statement answers with zeros
+__device__ __forceinline__ bool corners_radiance(const Corners &C, const DProbeRadiance &pr, const float4 *__restrict__ maps, double dx, double dy,
+                                                 double dz, double rough, double E[3]) {
+    const double dl2 = (dx * dx + dy * dy) + dz * dz;
+    if (!(dl2 > 0.0) || !(dl2 <= 1.79769313486231570e+308) || !(fabs(rough) <= 1.79769313486231570e+308)) return false;
+    const double dl = sqrt(dl2);
+    const double rx = dx / dl, ry = dy / dl, rz = dz / dl;
+    // the level pair and the blend
+    const uint32_t L = pr.levels;
+    const double top = L == 1u ? pr.rho[0] : (L == 2u ? pr.rho[1] : (L == 3u ? pr.rho[2] : pr.rho[3]));
+    const double rho = fmin(fmax(rough, pr.rho[0]), top);
+    uint32_t l = 0u;
+    double lo = pr.rho[0], hi = pr.rho[1];
+    if (L > 2u && pr.rho[1] <= rho) { l = 1u; lo = pr.rho[1]; hi = pr.rho[2]; }
+    if (L > 3u && pr.rho[2] <= rho) { l = 2u; lo = pr.rho[2]; hi = pr.rho[3]; }
+    const bool pair = L > 1u;
+    const double t = pair ? (rho - lo) / (hi - lo) : 0.0;
+    const double t1 = 1.0 - t;
+    const uint32_t R = pr.R;
+    const uint32_t off0 = l == 0u ? 0u : (l == 1u ? R * R : R * R + (R >> 1) * (R >> 1));
+    const uint32_t Rl = R >> l, Rn = Rl >> 1;
+    const uint32_t off1 = off0 + Rl * Rl;
+    double e0 = 0.0, e1 = 0.0, e2 = 0.0;
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        if (C.active & (1u << d)) {
+            const float4 *__restrict__ m = maps + (size_t)C.probe[d] * pr.texels;      // n_probes x M < 2^31 texels
+            double c[3];
+            radiance_fetch(m + off0, Rl, rx, ry, rz, c);
+            if (pair) {
+                double n[3];
+                radiance_fetch(m + off1, Rn, rx, ry, rz, n);
+                c[0] = c[0] * t1 + n[0] * t; c[1] = c[1] * t1 + n[1] * t; c[2] = c[2] * t1 + n[2] * t;
+            }
+            const double wd = C.w[d] / C.wsum;
+            e0 = e0 + wd * c[0]; e1 = e1 + wd * c[1]; e2 = e2 + wd * c[2];
+        }
+    }
+    E[0] = e0; E[1] = e1; E[2] = e2;
+    return true;
+}
+
+template <bool DEPTH>
+__global__ __launch_bounds__(PL_BLOCK) void k_probe_radiance_lookup(DProbeGrid G, DProbeVis V, DProbeRadiance pr, const float4 *__restrict__ maps,
+                                                                    const float *__restrict__ placement, uint32_t n,
+                                                                    const float *__restrict__ positions, const float *__restrict__ normals,
+                                                                    uint32_t stride, const float *__restrict__ dirs,
+                                                                    const float *__restrict__ roughness, float *__restrict__ out) {
+    const uint32_t q = blockIdx.x * PL_BLOCK + threadIdx.x;                           // one point per lane: the grid covers n
+    if (q < n) {
+        const float *pp = positions + (size_t)q * stride, *nn = normals + (size_t)q * stride, *dd = dirs + (size_t)q * 3u;
+        const float rough = roughness[q];
+        Corners C;
+        double E[3];
+        float r = 0.f, g = 0.f, b = 0.f;
+        if (finite_f(dd[0]) && finite_f(dd[1]) && finite_f(dd[2]) && finite_f(rough) &&
+            corner_weights<DEPTH>(G, V, placement, pp[0], pp[1], pp[2], nn[0], nn[1], nn[2], C) &&
+            corners_radiance(C, pr, maps, (double)dd[0], (double)dd[1], (double)dd[2], (double)rough, E)) {
+            r = (float)E[0]; g = (float)E[1]; b = (float)E[2];
+        }
+        float *o = out + (size_t)q * 3u;
+        o[0] = r; o[1] = g; o[2] = b;
+    }
+}
+
+// fw_kernels.hip's fdiv and resolve_pixel, as fw_probe_lookup.hip restates them: the same bits
+__device__ __forceinline__ float fdiv(float a, float b) {
+    float r = __builtin_amdgcn_rcpf(b);
+    r = fmaf(fmaf(-b, r, 1.0f), r, r);
+    float q = a * r;
+    q = fmaf(fmaf(-b, q, a), r, q);
+    q = fmaf(fmaf(-b, q, a), r, q);
+    return __builtin_amdgcn_div_fixupf(q, b, a);
+}
+__device__ __forceinline__ uint8_t sat_u8(float f) { if (!(f > 0.f)) return 0; if (f >= 255.f) return 255; return (uint8_t)f; }
+__device__ __forceinline__ float clamp01(float x) { return (x != x) ? x : (x < 0.f ? 0.f : (x > 1.f ? 1.f : x)); }
+__device__ __forceinline__ void resolve_pixel(float cr, float cg, float cb, float spp, float gamma, uint32_t p, uint8_t *rgb8, float *gamma_rgb,
+                                              float *linear_rgb) {
+    const float tr = fdiv(cr, spp), tg = fdiv(cg, spp), tb = fdiv(cb, spp);
+    const float ig = fdiv(1.f, gamma);
+    const float gr = clamp01(fwlm::powf_glibc(tr, ig)), gg = clamp01(fwlm::powf_glibc(tg, ig)), gb = clamp01(fwlm::powf_glibc(tb, ig));
+    if (linear_rgb) { linear_rgb[3 * (size_t)p] = tr; linear_rgb[3 * (size_t)p + 1] = tg; linear_rgb[3 * (size_t)p + 2] = tb; }
+    if (gamma_rgb) { gamma_rgb[3 * (size_t)p] = gr; gamma_rgb[3 * (size_t)p + 1] = gg; gamma_rgb[3 * (size_t)p + 2] = gb; }
+    if (rgb8) { rgb8[3 * (size_t)p] = sat_u8(gr * 255.99f); rgb8[3 * (size_t)p + 1] = sat_u8(gg * 255.99f); rgb8[3 * (size_t)p + 2] = sat_u8(gb * 255.99f); }
+}
+
+template <bool DEPTH>
+__global__ __launch_bounds__(PL_BLOCK) void k_probe_shade_glossy(DProbeGrid G, DProbeVis V, DProbeRadiance pr, RadConst K, const float *__restrict__ sh,
+                                                                 const float4 *__restrict__ maps, const float *__restrict__ placement, uint32_t n,
+                                                                 const float4 *__restrict__ aov, const float4 *__restrict__ spec,
+                                                                 const float *__restrict__ view, uint32_t view_stride, float gamma, uint8_t *rgb8,
+                                                                 float *gamma_rgb, float *linear_rgb) {
+    const float inv_pi = (float)(1.0 / 3.141592653589793);
+    const uint32_t p = blockIdx.x * PL_BLOCK + threadIdx.x;                           // one pixel per lane: the grid covers n
+    if (p < n) {
+        const float4 a = aov[3 * (size_t)p], nd = aov[3 * (size_t)p + 1], xa = aov[3 * (size_t)p + 2];
+        const float4 sp = spec[p];
+        Corners C;
+        const bool ok = corner_weights<DEPTH>(G, V, placement, xa.x, xa.y, xa.z, nd.x, nd.y, nd.z, C);
+        const float v = a.w, rest = 1.f - v;
+        if (!(sp.w > 0.f)) {                                                           // diffuse: fw_probe_shade_placed's arithmetic
+            double E[3];
+            float er = 0.f, eg = 0.f, eb = 0.f;
+            if (ok) { corners_sh(C, K, sh, E); er = (float)E[0]; eg = (float)E[1]; eb = (float)E[2]; }
+            er = er > 0.f ? er : 0.f; eg = eg > 0.f ? eg : 0.f; eb = eb > 0.f ? eb : 0.f;
+            resolve_pixel(a.x * (v * (er * inv_pi) + rest), a.y * (v * (eg * inv_pi) + rest), a.z * (v * (eb * inv_pi) + rest), 1.0f, gamma, p, rgb8,
+                          gamma_rgb, linear_rgb);
+            return;
+        }
+        // glossy: the lookup along the mirrored view direction under Schlick's Fresnel term
+        const float *vw = view + (size_t)p * view_stride;
+        const float vxf = vw[0], vyf = vw[1], vzf = vw[2];
+        float l0 = 0.f, l1 = 0.f, l2 = 0.f, Sf = 0.f;
+        if (finite_f(vxf) && finite_f(vyf) && finite_f(vzf)) {
+            const double vx = (double)vxf, vy = (double)vyf, vz = (double)vzf;
+            const double vl2 = (vx * vx + vy * vy) + vz * vz;
+            if (vl2 > 0.0 && C.usable) {
+                const double vl = sqrt(vl2);
+                const double ux = vx / vl, uy = vy / vl, uz = vz / vl;
+                const double c = (C.x * ux + C.y * uy) + C.z * uz;
+                const double c2 = 2.0 * c;
+                const float rx = (float)(ux - c2 * C.x), ry = (float)(uy - c2 * C.y), rz = (float)(uz - c2 * C.z);
+                const double cost = fmin(1.0, fmax(0.0, -c));
+                const double m = 1.0 - cost;
+                Sf = (float)(((m * m) * (m * m)) * m);
+                double E[3];
+                if (ok && finite_f(sp.w) && corners_radiance(C, pr, maps, (double)rx, (double)ry, (double)rz, (double)sp.w, E)) {
+                    l0 = (float)E[0]; l1 = (float)E[1]; l2 = (float)E[2];
+                }
+            }
+        }
+        l0 = fmaxf(l0, 0.f); l1 = fmaxf(l1, 0.f); l2 = fmaxf(l2, 0.f);
+        const float f0 = sp.x + (1.f - sp.x) * Sf, f1 = sp.y + (1.f - sp.y) * Sf, f2 = sp.z + (1.f - sp.z) * Sf;
+        resolve_pixel(v * (f0 * l0) + rest * a.x, v * (f1 * l1) + rest * a.y, v * (f2 * l2) + rest * a.z, 1.0f, gamma, p, rgb8, gamma_rgb, linear_rgb);
+    }
+}
+
+RadConst rad_const() {
+    const double PI = 3.141592653589793;
+    return RadConst{0.5 * std::sqrt(1.0 / PI), std::sqrt(3.0 / (4.0 * PI)), 0.5 * std::sqrt(15.0 / PI), 0.25 * std::sqrt(5.0 / PI),
+                    0.25 * std::sqrt(15.0 / PI), PI, 2.0 * PI / 3.0, PI / 4.0};
+}
+uint32_t rad_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + PL_BLOCK - 1) / PL_BLOCK); }        // n > 0; at most 2^24 blocks
+
+} // namespace
+
+void launch_probe_radiance_reduce(hipStream_t stream, uint32_t n, uint32_t directions, const DProbeRadiance &pr, uint32_t samples, const float *rays,
+                                  const float *accum, float *sums) {
+    hipLaunchKernelGGL(k_probe_radiance_reduce, dim3(n), dim3(PR_BLOCK), 0, stream, n, directions, pr.R, pr.k, (double)samples, rays,
+                       (const float4 *)accum, (float4 *)sums);                          // n < 2^27: one workgroup per probe
+}
+
+void launch_probe_radiance_prefilter(hipStream_t stream, int n_cus, uint32_t n, const DProbeRadiance &pr, const float *sums, float *maps) {
+    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(n, (uint32_t)std::max(1, n_cus) * 3u));      // 48 KB of LDS: three per CU
+    hipLaunchKernelGGL(k_probe_radiance_prefilter, dim3(blocks), dim3(PR_BLOCK), 0, stream, n, pr, (const float4 *)sums, (float4 *)maps);
+}
+
+void launch_probe_radiance_lookup(hipStream_t stream, const DProbeGrid &g, const DProbeVis *v, const DProbeRadiance &pr, const float *maps,
+                                  const float *placement, uint32_t n, const float *positions, const float *normals, uint32_t stride_floats,
+                                  const float *dirs, const float *roughness, float *radiance) {
+    if (v) hipLaunchKernelGGL(k_probe_radiance_lookup<true>, dim3(rad_blocks(n)), dim3(PL_BLOCK), 0, stream, g, *v, pr, (const float4 *)maps, placement,
+                              n, positions, normals, stride_floats, dirs, roughness, radiance);
+    else hipLaunchKernelGGL(k_probe_radiance_lookup<false>, dim3(rad_blocks(n)), dim3(PL_BLOCK), 0, stream, g, DProbeVis{nullptr, 0.0, 0u}, pr,
+                            (const float4 *)maps, placement, n, positions, normals, stride_floats, dirs, roughness, radiance);
+}
+
+void launch_probe_shade_glossy(hipStream_t stream, const DProbeGrid &g, const DProbeVis *v, const DProbeRadiance &pr, const float *sh,
+                               const float *maps, const float *placement, uint32_t n, const float *aov, const float *spec, const float *view,
+                               uint32_t view_stride, float gamma, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
+    if (v) hipLaunchKernelGGL(k_probe_shade_glossy<true>, dim3(rad_blocks(n)), dim3(PL_BLOCK), 0, stream, g, *v, pr, rad_const(), sh,
+                              (const float4 *)maps, placement, n, (const float4 *)aov, (const float4 *)spec, view, view_stride, gamma, rgb8,
+                              gamma_rgb, linear_rgb);
+    else hipLaunchKernelGGL(k_probe_shade_glossy<false>, dim3(rad_blocks(n)), dim3(PL_BLOCK), 0, stream, g, DProbeVis{nullptr, 0.0, 0u}, pr,
+                            rad_const(), sh, (const float4 *)maps, placement, n, (const float4 *)aov, (const float4 *)spec, view, view_stride, gamma,
+                            rgb8, gamma_rgb, linear_rgb);
+}
+
+} // namespace fw

@@ -18,6 +18,7 @@
 #include "fw_probe_depth.h"
 #include "fw_ao.h"
 #include "fw_probe_place.h"
+#include "fw_probe_radiance.h"
 #include "fw_defer_pretest.h"
 
 #include <algorithm>
@@ -4990,6 +4991,349 @@ int bake_ao_impl(fw_scene *sc, const fw_ao *ao, const fw_trace_params *tp, uint3
     return FW_OK;
 }
 
+// ---- probe radiance maps (include/firework_hip.h) ------------------------------------------------------------------
+// A radiance description's own argument checks (FW_ERR_BAD_ARG only) and what the kernels need of it
+int probe_radiance_check(const fw_probe_radiance *pr, fw::DProbeRadiance &d) {
+    if (pr->resolution != 4 && pr->resolution != 8 && pr->resolution != 16 && pr->resolution != 32)
+        return fail(FW_ERR_BAD_ARG, "a probe radiance map's resolution must be 4, 8, 16 or 32");
+    if (pr->sharpness_log2 > 8) return fail(FW_ERR_BAD_ARG, "sharpness_log2 must be in 0..8");
+    if (pr->levels == 0 || pr->levels > FW_PROBE_RADIANCE_MAX_LEVELS || (pr->resolution >> (pr->levels - 1)) < 4)
+        return fail(FW_ERR_BAD_ARG, "levels must be >= 1 and the last level's resolution at least 4");
+    for (uint32_t l = 0; l < pr->levels; l++) {
+        const float rho = pr->roughness[l];
+        if (!(rho >= 0.f && rho <= 1.f)) return fail(FW_ERR_BAD_ARG, "every level's roughness must be in [0, 1]");
+        if (l > 0 && !(rho > pr->roughness[l - 1])) return fail(FW_ERR_BAD_ARG, "the levels' roughness must ascend strictly");
+    }
+    d = fw::DProbeRadiance{};
+    d.R = pr->resolution; d.k = pr->sharpness_log2; d.levels = pr->levels;
+    for (uint32_t l = 0; l < pr->levels; l++) { d.texels += (d.R >> l) * (d.R >> l); d.rho[l] = (double)pr->roughness[l]; }
+    return FW_OK;
+}
+
+// fw_probe_radiance_reduce: fw_probe_depth_reduce's shape
+int probe_radiance_reduce_impl(int device, const fw_probe_radiance *pr, uint32_t n_probes, uint32_t directions, uint32_t samples, const float *rays,
+                               const float *accum, float *sums, int on_device, void *stream_) {
+    if (!pr || !rays || !accum || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
+    fw::DProbeRadiance d{};
+    if (int rc = probe_radiance_check(pr, d)) return rc;
+    if (n_probes == 0) return fail(FW_ERR_BAD_ARG, "n_probes must be > 0");
+    if (directions == 0 || directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (samples == 0 || samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^24");
+    if (on_device && ((((uintptr_t)sums | (uintptr_t)accum) & 15u) || ((uintptr_t)rays & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums and accum must be 16-byte aligned, device rays 4-byte aligned");
+    const uint32_t R = d.R;
+    if ((uint64_t)n_probes * directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
+    if ((uint64_t)n_probes * R * R >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n = (size_t)n_probes * directions, sum_bytes = (size_t)n_probes * R * R * 16;
+    CallScratch scratch(device);
+    const float *d_rays = rays, *d_acc = accum; float *d_sums = sums;
+    if (!on_device) {
+        const size_t o_acc = align256(n * 24), o_sums = o_acc + align256(n * 16);
+        if (int rc = scratch.alloc(o_sums + sum_bytes)) return rc;
+        uint8_t *base = (uint8_t *)scratch.p;
+        HIPCHK(hipMemcpyAsync(base, rays, n * 24, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_acc, accum, n * 16, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
+        d_rays = (const float *)base; d_acc = (const float *)(base + o_acc); d_sums = (float *)(base + o_sums);
+    }
+    fw::launch_probe_radiance_reduce(stream, n_probes, directions, d, samples, d_rays, d_acc, d_sums);
+    if (!on_device) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_probe_radiance_prefilter: the maps are overwritten, so a host caller's are not uploaded
+int probe_radiance_prefilter_impl(int device, const fw_probe_radiance *pr, uint32_t n_probes, const float *sums, float *maps, int on_device,
+                                  void *stream_) {
+    if (!pr || !sums || !maps) return fail(FW_ERR_BAD_ARG, "null argument");
+    fw::DProbeRadiance d{};
+    if (int rc = probe_radiance_check(pr, d)) return rc;
+    if (n_probes == 0) return fail(FW_ERR_BAD_ARG, "n_probes must be > 0");
+    if (on_device && (((uintptr_t)sums | (uintptr_t)maps) & 15u)) return fail(FW_ERR_BAD_ARG, "device sums and maps must be 16-byte aligned");
+    if ((uint64_t)n_probes * d.texels >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x texels must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t sum_bytes = (size_t)n_probes * d.R * d.R * 16, map_bytes = (size_t)n_probes * d.texels * 16;
+    CallScratch scratch(device);
+    const float *d_sums = sums; float *d_maps = maps;
+    if (!on_device) {
+        const size_t o_maps = align256(sum_bytes);
+        if (int rc = scratch.alloc(o_maps + map_bytes)) return rc;
+        uint8_t *base = (uint8_t *)scratch.p;
+        HIPCHK(hipMemcpyAsync(base, sums, sum_bytes, hipMemcpyHostToDevice, stream));
+        d_sums = (const float *)base; d_maps = (float *)(base + o_maps);
+    }
+    fw::launch_probe_radiance_prefilter(stream, device_cus(device), n_probes, d, d_sums, d_maps);
+    if (!on_device) HIPCHK(hipMemcpyAsync(maps, d_maps, map_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_bake_probe_radiance: bake_probes_impl with k_probe_radiance_reduce as bake_rounds' reducer — and, with sh_sums or sh, k_probe_project
+// beside it on the same rendered accum — and one prefilter of the final sums.  Its own are the argument checks, the scratch (positions, a
+// chunk's rays and accum, and whichever running sums and maps the caller's device memory does not hold) and sh, divided on the host.
+int bake_probe_radiance_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe_radiance *pr, const fw_render_rays_params *rp, uint32_t first_round,
+                             uint32_t rounds, float *sums, float *maps, float *sh_sums, float *sh, fw_stats *stats) {
+    if (!sc || !s || !pr || !rp) return fail(FW_ERR_BAD_ARG, "null argument");
+    bool too_large = false;
+    if (int rc = probe_set_check(s, too_large)) return rc;
+    fw::DProbeRadiance d{};
+    if (int rc = probe_radiance_check(pr, d)) return rc;
+    if (rounds == 0) return fail(FW_ERR_BAD_ARG, "rounds must be > 0");
+    if ((uint64_t)first_round + rounds > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_round + rounds overflows");
+    if (rp->samples == 0 || rp->samples > (1u << 24)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^24");
+    const bool with_sh = sh_sums || sh;
+    if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
+    if (with_sh && !sh_sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sh_sums of the rounds before it");
+    if (rp->on_device && ((((uintptr_t)sums | (uintptr_t)maps) & 15u) || (((uintptr_t)sh_sums | (uintptr_t)sh) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums and maps must be 16-byte aligned, device sh_sums and sh 4-byte aligned");
+    const uint32_t N = s->n_probes, D = s->directions, S = rp->samples, R = d.R;
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
+    if ((uint64_t)N * d.texels >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x texels must be below 2^31");
+    if (int rc = need_device()) return rc;
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)rp->stream;
+    const uint32_t chunk = std::min<uint32_t>(N, s->chunk_probes ? s->chunk_probes : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 40)));
+    const size_t sum_bytes = (size_t)N * R * R * 16, map_bytes = (size_t)N * d.texels * 16, sh_bytes = (size_t)N * 108;
+    const bool own_sums = !rp->on_device || !sums, own_sh = with_sh && (!rp->on_device || !sh_sums), own_maps = maps && !rp->on_device;
+    size_t off = 0;
+    auto put = [&](size_t b) { const size_t at = off; off += align256(b); return at; };
+    const size_t o_pos = put((size_t)N * 12), o_rays = put((size_t)chunk * D * 24), o_acc = put((size_t)chunk * D * 16);
+    const size_t o_sums = put(own_sums ? sum_bytes : 0), o_sh = put(own_sh ? sh_bytes : 0), o_maps = put(own_maps ? map_bytes : 0);
+    CallScratch scratch(dev);
+    if (int rc = scratch.alloc(off)) return rc;
+    uint8_t *base = (uint8_t *)scratch.p;
+    const float *d_pos = (const float *)(base + o_pos);
+    float *d_rays = (float *)(base + o_rays), *d_acc = (float *)(base + o_acc);
+    float *d_sums = own_sums ? (float *)(base + o_sums) : sums, *d_sh = own_sh ? (float *)(base + o_sh) : sh_sums;
+    float *d_maps = own_maps ? (float *)(base + o_maps) : maps;
+    HIPCHK(hipMemcpyAsync(base + o_pos, s->positions, (size_t)N * 12, hipMemcpyHostToDevice, stream));
+    if (own_sums) {
+        if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
+        else HIPCHK(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
+    }
+    if (own_sh) {
+        if (sh_sums) HIPCHK(hipMemcpyAsync(d_sh, sh_sums, sh_bytes, hipMemcpyHostToDevice, stream));
+        else HIPCHK(hipMemsetAsync(d_sh, 0, sh_bytes, stream));
+    }
+    const int n_cus = device_cus(dev);
+    fw_stats total{};
+    // (the reducers' loads and their sums: 40 B per ray and 32 B per texel; the projection's 40 B per ray and 216 B per probe)
+    const BakeRounds b{first_round, rounds, N, D, chunk, d_rays, d_acc, 0, with_sh ? 80u : 40u, R * R * 32u + (with_sh ? 216u : 0u)};
+    if (int rc = bake_rounds(sc, rp, b, stats ? &total : nullptr,
+            [&](uint32_t r, uint32_t p0, uint32_t k, float *rays) { fw::launch_probe_rays(stream, n_cus, probes_device(s, r, p0, d_pos + (size_t)p0 * 3), k, rays); },
+            [&](uint32_t p0, uint32_t k, const float *rays, const float *acc) {
+                fw::launch_probe_radiance_reduce(stream, k, D, d, S, rays, acc, d_sums + (size_t)p0 * R * R * 4);
+                if (with_sh) fw::launch_probe_project(stream, n_cus, k, D, S, rays, acc, d_sh + (size_t)p0 * 27);
+            }))
+        return rc;
+    if (maps) {
+        CallEvents<2> ev;                                 // around the prefilter: its time joins the reducers'
+        if (stats) { for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(ev.e[0], stream)); }
+        fw::launch_probe_radiance_prefilter(stream, n_cus, N, d, d_sums, d_maps);
+        if (stats) {
+            HIPCHK(hipEventRecord(ev.e[1], stream));
+            HIPCHK(hipEventSynchronize(ev.e[1]));
+            float pf_ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&pf_ms, ev.e[0], ev.e[1]));
+            total.ms_render += pf_ms;
+            if (rp->flags & FW_FLAG_TIME_KERNELS) total.ms_accumulate += pf_ms;
+            total.bytes_accumulate += (uint64_t)N * ((uint64_t)R * R + d.texels) * 16;
+        }
+    }
+    // the outputs: sums, sh_sums and maps where the caller keeps them, and sh = sh_sums / rounds so far, divided on the host in double
+    std::vector<float> host;
+    const float *h_sh = sh_sums;
+    if (!rp->on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+    if (own_maps) HIPCHK(hipMemcpyAsync(maps, d_maps, map_bytes, hipMemcpyDeviceToHost, stream));
+    if (!rp->on_device && sh_sums) HIPCHK(hipMemcpyAsync(sh_sums, d_sh, sh_bytes, hipMemcpyDeviceToHost, stream));
+    else if (sh) { host.resize((size_t)N * 27); h_sh = host.data(); HIPCHK(hipMemcpyAsync(host.data(), d_sh, sh_bytes, hipMemcpyDeviceToHost, stream)); }
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    if (sh) {
+        const double n_rounds = (double)((uint64_t)first_round + rounds);
+        std::vector<float> tmp;
+        float *out = sh;
+        if (rp->on_device) { tmp.resize((size_t)N * 27); out = tmp.data(); }
+        for (size_t i = 0; i < (size_t)N * 27; i++) out[i] = (float)((double)h_sh[i] / n_rounds);
+        if (rp->on_device) {
+            HIPCHK(hipMemcpyAsync(sh, tmp.data(), sh_bytes, hipMemcpyHostToDevice, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+    }
+    if (stats) {
+        *stats = total;
+        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return FW_OK;
+}
+
+// What fw_probe_radiance_lookup and fw_probe_shade_glossy share beside the grid: the maps, and the optional visibility and placement
+struct ProbeRadianceArgs {
+    const fw_probe_radiance *pr; const float *maps;
+    const fw_probe_depth *pd; const float *moments; float normal_bias;
+    const float *placement;
+};
+
+// fw_probe_radiance_lookup: probe_irradiance_impl's shape over the placed lookup's arguments; a host call's slab holds 40 B in and 12 B
+// out per point
+int probe_radiance_lookup_impl(const fw_probe_grid *grid, const ProbeRadianceArgs &a, int device, uint32_t n, const float *positions,
+                               const float *normals, uint32_t stride, const float *dirs, const float *roughness, float *radiance, int on_device,
+                               void *stream_) {
+    const bool with_vis = a.pd || a.moments;
+    if (!grid || !a.pr || !a.maps || !positions || !normals || !dirs || !roughness || !radiance || (with_vis && (!a.pd || !a.moments)))
+        return fail(FW_ERR_BAD_ARG, "null argument");
+    fw::DProbeRadiance d{};
+    if (int rc = probe_radiance_check(a.pr, d)) return rc;
+    const ProbeVis vis{a.pd, a.moments, a.normal_bias};
+    if (with_vis) if (int rc = probe_vis_check(&vis)) return rc;
+    bool too_large = false;
+    fw::DProbeGrid g{};
+    if (int rc = probe_grid_check(grid, too_large, g)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    if (on_device && ((((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)dirs | (uintptr_t)roughness | (uintptr_t)radiance | (uintptr_t)a.moments |
+                        (uintptr_t)a.placement) & 3u) || ((uintptr_t)a.maps & 15u)))
+        return fail(FW_ERR_BAD_ARG, "device maps must be 16-byte aligned, the other device arrays 4-byte aligned");
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
+    if (probe_vis_too_large(with_vis ? &vis : nullptr, g)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
+    const size_t n_probes = (size_t)g.counts[0] * g.counts[1] * g.counts[2];
+    if ((uint64_t)n_probes * d.texels >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x texels must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const auto launch = [&](const float *d_maps, const float *d_mom, const float *d_pl, uint32_t k, const float *pos, const float *nrm, uint32_t st,
+                            const float *dir, const float *rough, float *out) {
+        const fw::DProbeVis v{d_mom, with_vis ? (double)a.normal_bias : 0.0, with_vis ? a.pd->resolution : 0u};
+        fw::launch_probe_radiance_lookup(stream, g, with_vis ? &v : nullptr, d, d_maps, d_pl, k, pos, nrm, st, dir, rough, out);
+    };
+    if (on_device) {
+        launch(a.maps, a.moments, a.placement, n, positions, normals, stride, dirs, roughness, radiance);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+    const size_t map_bytes = n_probes * d.texels * 16, mom_bytes = with_vis ? n_probes * a.pd->resolution * a.pd->resolution * 8 : 0;
+    const size_t pl_bytes = a.placement ? n_probes * 16 : 0;
+    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 52));
+    size_t off = 0;
+    auto put = [&](size_t b) { const size_t at = off; off += align256(b); return at; };
+    const size_t o_maps = put(map_bytes), o_mom = put(mom_bytes), o_pl = put(pl_bytes), o_in = put((size_t)per * 24), o_dir = put((size_t)per * 12),
+                 o_rough = put((size_t)per * 4), o_out = put((size_t)per * 12);
+    std::vector<float> pack((size_t)per * 6);
+    CallScratch scratch(device);
+    if (int rc = scratch.alloc(off)) return rc;
+    uint8_t *base = (uint8_t *)scratch.p;
+    const float *d_in = (const float *)(base + o_in);
+    HIPCHK(hipMemcpyAsync(base + o_maps, a.maps, map_bytes, hipMemcpyHostToDevice, stream));
+    if (with_vis) HIPCHK(hipMemcpyAsync(base + o_mom, a.moments, mom_bytes, hipMemcpyHostToDevice, stream));
+    if (a.placement) HIPCHK(hipMemcpyAsync(base + o_pl, a.placement, pl_bytes, hipMemcpyHostToDevice, stream));
+    for (uint32_t done = 0; done < n; done += per) {
+        const uint32_t k = std::min(per, n - done);
+        for (uint32_t i = 0; i < k; i++) {
+            const float *ps = positions + (size_t)(done + i) * stride, *ns = normals + (size_t)(done + i) * stride;
+            float *o = pack.data() + (size_t)i * 6;
+            o[0] = ps[0]; o[1] = ps[1]; o[2] = ps[2]; o[3] = ns[0]; o[4] = ns[1]; o[5] = ns[2];
+        }
+        HIPCHK(hipMemcpyAsync(base + o_in, pack.data(), (size_t)k * 24, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_dir, dirs + (size_t)done * 3, (size_t)k * 12, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_rough, roughness + done, (size_t)k * 4, hipMemcpyHostToDevice, stream));
+        launch((const float *)(base + o_maps), (const float *)(base + o_mom), a.placement ? (const float *)(base + o_pl) : nullptr, k, d_in, d_in + 3, 6,
+               (const float *)(base + o_dir), (const float *)(base + o_rough), (float *)(base + o_out));
+        HIPCHK(hipMemcpyAsync(radiance + (size_t)done * 3, base + o_out, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
+// fw_probe_shade_glossy: probe_shade_impl's shape; a host call's slab holds 48 B of record, 16 B of spec, 12 B of view and up to 27 B of
+// outputs per pixel
+int probe_shade_glossy_impl(const fw_probe_grid *grid, const float *sh, const ProbeRadianceArgs &a, const fw_probe_shade_params *p, const float *aov,
+                            const float *spec, const float *view, uint32_t view_stride, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
+    const bool with_vis = a.pd || a.moments;
+    if (!grid || !sh || !a.pr || !a.maps || !p || !aov || !spec || !view || (with_vis && (!a.pd || !a.moments))) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (!linear_rgb && !gamma_rgb && !rgb8) return fail(FW_ERR_BAD_ARG, "at least one output is needed");
+    fw::DProbeRadiance d{};
+    if (int rc = probe_radiance_check(a.pr, d)) return rc;
+    const ProbeVis vis{a.pd, a.moments, a.normal_bias};
+    if (with_vis) if (int rc = probe_vis_check(&vis)) return rc;
+    bool too_large = false;
+    fw::DProbeGrid g{};
+    if (int rc = probe_grid_check(grid, too_large, g)) return rc;
+    if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
+    if (!std::isfinite(p->gamma) || !(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
+    if (view_stride < 3) return fail(FW_ERR_BAD_ARG, "view_stride_floats must be >= 3");
+    if (p->device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    if (p->on_device && ((((uintptr_t)aov | (uintptr_t)spec | (uintptr_t)a.maps) & 15u) ||
+                         (((uintptr_t)sh | (uintptr_t)view | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb | (uintptr_t)a.moments | (uintptr_t)a.placement) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device aov, spec and maps must be 16-byte aligned, the other device arrays 4-byte aligned");
+    const uint64_t full = (uint64_t)p->width * p->height;
+    if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
+    if (probe_vis_too_large(with_vis ? &vis : nullptr, g)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
+    const size_t n_probes = (size_t)g.counts[0] * g.counts[1] * g.counts[2];
+    if ((uint64_t)n_probes * d.texels >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x texels must be below 2^31");
+    if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
+    const int dev = p->device;
+    if (int rc = use_device(dev)) return rc;
+    hipStream_t stream = (hipStream_t)p->stream;
+    const uint32_t n = (uint32_t)full;
+    const auto launch = [&](const float *d_sh, const float *d_maps, const float *d_mom, const float *d_pl, uint32_t k, const float *d_aov,
+                            const float *d_spec, const float *d_view, uint32_t st, uint8_t *o8, float *og, float *ol) {
+        const fw::DProbeVis v{d_mom, with_vis ? (double)a.normal_bias : 0.0, with_vis ? a.pd->resolution : 0u};
+        fw::launch_probe_shade_glossy(stream, g, with_vis ? &v : nullptr, d, d_sh, d_maps, d_pl, k, d_aov, d_spec, d_view, st, p->gamma, o8, og, ol);
+    };
+    if (p->on_device) {
+        launch(sh, a.maps, a.moments, a.placement, n, aov, spec, view, view_stride, rgb8, gamma_rgb, linear_rgb);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+    const size_t sh_bytes = n_probes * 108, map_bytes = n_probes * d.texels * 16;
+    const size_t mom_bytes = with_vis ? n_probes * a.pd->resolution * a.pd->resolution * 8 : 0, pl_bytes = a.placement ? n_probes * 16 : 0;
+    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 103));
+    size_t off = 0;
+    auto put = [&](size_t b) { const size_t at = off; off += align256(b); return at; };
+    const size_t o_sh = put(sh_bytes), o_maps = put(map_bytes), o_mom = put(mom_bytes), o_pl = put(pl_bytes), o_aov = put((size_t)per * 48),
+                 o_spec = put((size_t)per * 16), o_view = put((size_t)per * 12);
+    const size_t o_lin = linear_rgb ? put((size_t)per * 12) : 0, o_gam = gamma_rgb ? put((size_t)per * 12) : 0, o_8 = rgb8 ? put((size_t)per * 3) : 0;
+    std::vector<float> pack((size_t)per * 3);
+    CallScratch scratch(dev);
+    if (int rc = scratch.alloc(off)) return rc;
+    uint8_t *base = (uint8_t *)scratch.p;
+    HIPCHK(hipMemcpyAsync(base + o_sh, sh, sh_bytes, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(base + o_maps, a.maps, map_bytes, hipMemcpyHostToDevice, stream));
+    if (with_vis) HIPCHK(hipMemcpyAsync(base + o_mom, a.moments, mom_bytes, hipMemcpyHostToDevice, stream));
+    if (a.placement) HIPCHK(hipMemcpyAsync(base + o_pl, a.placement, pl_bytes, hipMemcpyHostToDevice, stream));
+    for (uint32_t done = 0; done < n; done += per) {
+        const uint32_t k = std::min(per, n - done);
+        for (uint32_t i = 0; i < k; i++) {
+            const float *vs = view + (size_t)(done + i) * view_stride;
+            float *o = pack.data() + (size_t)i * 3;
+            o[0] = vs[0]; o[1] = vs[1]; o[2] = vs[2];
+        }
+        HIPCHK(hipMemcpyAsync(base + o_aov, aov + (size_t)done * 12, (size_t)k * 48, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_spec, spec + (size_t)done * 4, (size_t)k * 16, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(base + o_view, pack.data(), (size_t)k * 12, hipMemcpyHostToDevice, stream));
+        launch((const float *)(base + o_sh), (const float *)(base + o_maps), (const float *)(base + o_mom),
+               a.placement ? (const float *)(base + o_pl) : nullptr, k, (const float *)(base + o_aov), (const float *)(base + o_spec),
+               (const float *)(base + o_view), 3, rgb8 ? base + o_8 : nullptr, gamma_rgb ? (float *)(base + o_gam) : nullptr,
+               linear_rgb ? (float *)(base + o_lin) : nullptr);
+        if (linear_rgb) HIPCHK(hipMemcpyAsync(linear_rgb + (size_t)done * 3, base + o_lin, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
+        if (gamma_rgb) HIPCHK(hipMemcpyAsync(gamma_rgb + (size_t)done * 3, base + o_gam, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
+        if (rgb8) HIPCHK(hipMemcpyAsync(rgb8 + (size_t)done * 3, base + o_8, (size_t)k * 3, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    HIPCHK(hipGetLastError());
+    return FW_OK;
+}
+
 } // namespace
 
 // =========================================================================================================
@@ -5564,6 +5908,49 @@ int fw_probe_shade_placed(const fw_probe_grid *grid, const float *sh, const fw_p
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_placed"); }
+}
+
+int fw_probe_radiance_reduce(int device, const fw_probe_radiance *pr, uint32_t n_probes, uint32_t directions, uint32_t samples, const float *rays,
+                             const float *accum, float *sums, int on_device, void *stream) {
+    try { return probe_radiance_reduce_impl(device, pr, n_probes, directions, samples, rays, accum, sums, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_radiance_reduce"); }
+}
+
+int fw_probe_radiance_prefilter(int device, const fw_probe_radiance *pr, uint32_t n_probes, const float *sums, float *maps, int on_device,
+                                void *stream) {
+    try { return probe_radiance_prefilter_impl(device, pr, n_probes, sums, maps, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_radiance_prefilter"); }
+}
+
+int fw_bake_probe_radiance(fw_scene *scene, const fw_probe_set *set, const fw_probe_radiance *pr, const fw_render_rays_params *rp,
+                           uint32_t first_round, uint32_t rounds, float *sums, float *maps, float *sh_sums, float *sh, fw_stats *stats) {
+    try { return bake_probe_radiance_impl(scene, set, pr, rp, first_round, rounds, sums, maps, sh_sums, sh, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_probe_radiance"); }
+}
+
+int fw_probe_radiance_lookup(const fw_probe_grid *grid, const fw_probe_radiance *pr, const float *maps, const fw_probe_depth *pd, const float *moments,
+                             float normal_bias, const float *placement, int device, uint32_t n, const float *positions, const float *normals,
+                             uint32_t stride_floats, const float *dirs, const float *roughness, float *radiance, int on_device, void *stream) {
+    try {
+        const ProbeRadianceArgs a{pr, maps, pd, moments, normal_bias, placement};
+        return probe_radiance_lookup_impl(grid, a, device, n, positions, normals, stride_floats, dirs, roughness, radiance, on_device, stream);
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_radiance_lookup"); }
+}
+
+int fw_probe_shade_glossy(const fw_probe_grid *grid, const float *sh, const fw_probe_radiance *pr, const float *maps, const fw_probe_depth *pd,
+                          const float *moments, float normal_bias, const float *placement, const fw_probe_shade_params *p, const float *aov,
+                          const float *spec, const float *view, uint32_t view_stride_floats, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
+    try {
+        const ProbeRadianceArgs a{pr, maps, pd, moments, normal_bias, placement};
+        return probe_shade_glossy_impl(grid, sh, a, p, aov, spec, view, view_stride_floats, linear_rgb, gamma_rgb, rgb8);
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_glossy"); }
 }
 
 int fw_lightmap_texels(const fw_lightmap *lm, int device, float *records, uint32_t *owner, uint32_t *n_covered, int on_device, void *stream) {

@@ -1221,6 +1221,104 @@ int fw_probe_shade_placed(const fw_probe_grid *grid, const float *sh, const fw_p
                           const float *placement, const fw_probe_shade_params *p, const float *aov, float *linear_rgb, float *gamma_rgb,
                           uint8_t *rgb8);
 
+/* Probe radiance maps (additive at ABI 8).  Nine SH coefficients cannot hold a highlight, so every probe also gets an
+   octahedral map of the radiance its rays saw, with a chain of GGX-prefiltered levels, which a lookup reads along a reflected
+   direction.  Everything below is float64 arithmetic from the float32 inputs, every operation rounded as written; max and min are
+   fmax and fmin; no atomics.  Texel centres, sgn, the fold and the bilinear fetch are fw_probe_depth's (above), at each level's own
+   resolution.  api.probe_radiance_reduce, api.probe_radiance_prefilter, api.probe_radiance_lookup and api.probe_glossy_ref are the
+   numpy statements.
+     Layout.  Level l has resolution R_l = R >> l.  A probe's pyramid has M = sum_l R_l^2 texels; level l starts at texel sum_(i<l)
+         R_i^2, and within a level texel (column a, row b) is b R_l + a.  maps: n_probes x M x 4 floats (r, g, b, flag), flag 1.0 where
+         the texel has data, else 0.0.  sums: n_probes x R x R x 4 floats (A_r, A_g, A_b, W), all four written.  On the device both
+         are 16-byte aligned.
+     Reduction of one round (fw_probe_radiance_reduce, k_probe_radiance_reduce): fw_probe_depth_reduce with radiance in the place of
+         distance.  For ray j of probe p, L_c = (double)accum[p D + j].c / samples, and per texel w = max(0, (Tx dx + Ty dy) + Tz dz)
+         squared sharpness_log2 times.  A ray with !(w > 0) is skipped for that texel, so a NaN radiance reaches only the texels whose
+         lobe it falls in.  Otherwise, sequentially in ascending j, A_c = A_c + w L_c and W = W + w.  Each accumulator is rounded to
+         float32 once and added to sums with one float32 addition.  One lane owns a texel: the result is a pure function of the
+         inputs and does not depend on the launch geometry.
+     Prefilter (fw_probe_radiance_prefilter, k_probe_radiance_prefilter).  Level 0: float((double)A_c / W) with flag 1; a texel with
+         W == 0 gets (0, 0, 0, 0).  Level 0 is not filtered: roughness[0] states what the raw lobe is taken to stand for.  Level
+         l >= 1, output texel with centre direction T at resolution R_l:  a = (double)rho_l rho_l, a2 = a a; over the source texels s of
+         level 0 in ascending id, with their stored float32 values: s is skipped if its flag is 0; c = (Tx Sx + Ty Sy) + Tz Sz, and s
+         is skipped if !(c > 0); h = (1 + c) 0.5; den = h (a2 - 1) + 1; w = ((a2 / (den den)) c) omega_s with
+         omega_s = (4 / (R R)) / ((len len) len), len the length of the source texel's (x, y, z) before normalisation (the octahedral
+         map's Jacobian at the centre); Wt = Wt + w and A_c = A_c + w L_c.  The texel is float(A_c / Wt) with flag 1, or zeros if
+         Wt == 0.  This is the split-sum prefilter with n = v = r: the GGX D times n.l, integrated over the map.
+     Lookup (fw_probe_radiance_lookup, k_probe_radiance_lookup).  The corner weights are exactly the placed lookup's (above): always
+         normalised, inactive corners skipped, wrap and visibility as there; placement NULL means every record is (0, 0, 0, 1), and pd
+         and moments may both be NULL.  r = dirs / sqrt((x x + y y) + z z) per component.  rho = min(max(roughness, rho_0), rho_(L-1));
+         l is the largest level with rho_l <= rho, capped at L - 2; t = (rho - rho_l) / (rho_(l+1) - rho_l).  Per active corner the rgb of
+         levels l and l + 1 is fetched bilinearly along r as fw_probe_depth's moments are, at R_l and R_(l+1), edges clamped, the flags
+         not read, and m = m_l (1 - t) + m_(l+1) t.  With L = 1 only level 0 is read and m = m_0.  Out_c = sum (w_d / wsum) m_c in the
+         order dz, dy, dx, rounded to float32 once and not clamped.  Zeros for a non-finite position, normal, dir or roughness, a zero
+         normal or dir, a point with no active corner, or a zero weight sum.  Every index is formed from clamped cell and texel
+         indices, so no load leaves the arrays.  Out of scope: parallax correction — each probe is read along r itself, as if the
+         reflected surface were infinitely far away.
+     Glossy shade (fw_probe_shade_glossy, k_probe_shade_glossy).  spec: W H x 4 floats (F0.rgb, rho).  view: three floats per pixel at
+         view_stride_floats, the ray direction from the eye (a ray buffer is read in place with the pointer rays + 3 and stride 6).  A
+         pixel with !(rho > 0) gets fw_probe_shade_placed's output bit for bit (a NULL placement taken as neutral).  Otherwise, with nh
+         the unit normal:  u = view / |view|;  c = (nhx ux + nhy uy) + nhz uz;  r_k = float(u_k - (2 c) nh_k);  cos = min(1, max(0, -c));
+         m = 1 - cos;  S = ((m m) (m m)) m;  Ls = the lookup above at (position, normal, r, rho), rounded to float32, then max(., 0);
+         S = 0 and Ls = 0 for a non-finite or zero view, a non-finite position or a non-finite or zero normal, and Ls = 0 wherever the
+         lookup answers with zeros.  In float32 without contraction
+         F_c = f0_c + (1 - f0_c) * (float)S and out_c = v * (F_c * Ls_c) + (1 - v) * a_c with v the record's coverage and a its albedo;
+         the outputs are resolved as fw_probe_shade's.  A conductor has no diffuse lobe.  Simplification: the split sum's shadowing
+         factor (the second, BRDF-integral term) is left out. */
+#define FW_PROBE_RADIANCE_MAX_LEVELS 4
+typedef struct fw_probe_radiance {
+    uint32_t resolution;      /* R in {4, 8, 16, 32} */
+    uint32_t sharpness_log2;  /* k in 0..8, as fw_probe_depth */
+    uint32_t levels;          /* L >= 1; level l has resolution R >> l, and the last level's is >= 4 (R = 4: L = 1; R = 32: up to 4) */
+    float    roughness[FW_PROBE_RADIANCE_MAX_LEVELS]; /* rho_l in [0, 1], strictly ascending over l < L; entries >= L are not read */
+} fw_probe_radiance;
+
+/* fw_probe_radiance_reduce: adds one round's reduction to the running sums.  rays: n_probes x D x 6 floats; accum: n_probes x D x 4
+   floats as fw_render_rays leaves it (fw_probe_project's input); host arrays, or with on_device device arrays on `device`, launched
+   on `stream` and complete on return.  Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL pr, rays, accum or
+   sums, a resolution outside {4, 8, 16, 32}, sharpness_log2 > 8, levels == 0 or a last level below resolution 4, a roughness outside
+   [0, 1] or not strictly ascending, n_probes == 0, directions outside 1..2^20, samples outside 1..2^24, with on_device sums or accum
+   not 16-byte aligned or rays not 4-byte aligned; FW_ERR_UNSUPPORTED for n_probes x D >= 2^31 or n_probes x R^2 >= 2^31; then
+   FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index out of range. */
+int fw_probe_radiance_reduce(int device, const fw_probe_radiance *pr, uint32_t n_probes, uint32_t directions, uint32_t samples, const float *rays,
+                             const float *accum, float *sums, int on_device, void *stream);
+
+/* fw_probe_radiance_prefilter: overwrites maps from sums.  Errors, in this order: FW_ERR_BAD_ARG for a NULL pr, sums or maps, what
+   fw_probe_radiance_reduce rejects in pr, n_probes == 0, with on_device arrays not 16-byte aligned; FW_ERR_UNSUPPORTED for
+   n_probes x M >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index out of range. */
+int fw_probe_radiance_prefilter(int device, const fw_probe_radiance *pr, uint32_t n_probes, const float *sums, float *maps, int on_device,
+                                void *stream);
+
+/* fw_bake_probe_radiance: fw_bake_probes' loop — the same rays, the same frames, the same seeds rp->seed + r with key_base = p0 D — with
+   k_probe_radiance_reduce on each chunk and, at the end, one prefilter of the final sums into maps (may be NULL).  With sh_sums or sh
+   not NULL the same rendered accum also goes through k_probe_project: one render feeds both bakes.
+     sums   : n_probes x R x R x 4 floats, the running sums of the rounds [0, first_round); NULL only when first_round == 0.
+     sh_sums, sh : fw_bake_probes' sums and sh; sh_sums may be NULL with first_round == 0 (sh is then still written).
+   Contracts, bit for bit and for every chunk_probes.  Composition: sums equals fw_probe_rays, fw_render_rays and
+   fw_probe_radiance_reduce chained by hand.  sh_sums and sh equal what fw_bake_probes gives for the same arguments.  Progressive: k
+   calls of n rounds equal one call of k n rounds.  fw_render is left as it was.
+   Errors: fw_bake_probes', in its order, with pr's after the set's; a NULL sums with first_round > 0, and, when sh_sums or sh is given,
+   a NULL sh_sums with first_round > 0; with on_device sums or maps not 16-byte aligned, sh_sums or sh not 4-byte aligned;
+   FW_ERR_UNSUPPORTED for n_probes x D >= 2^31 or n_probes x M >= 2^31; then FW_ERR_NO_DEVICE.  stats: as fw_bake_probes; the
+   prefilter's time is part of ms_render (and of ms_accumulate under FW_FLAG_TIME_KERNELS). */
+int fw_bake_probe_radiance(fw_scene *scene, const fw_probe_set *set, const fw_probe_radiance *pr, const fw_render_rays_params *rp,
+                           uint32_t first_round, uint32_t rounds, float *sums, float *maps, float *sh_sums, float *sh, fw_stats *stats);
+
+/* fw_probe_radiance_lookup: the lookup above at n points (one lane per point, 16-byte texel loads, no LDS).  positions and normals at
+   stride_floats; dirs n x 3 and roughness n, packed; radiance n x 3.  Host arrays, or with on_device device arrays.  Errors: the placed
+   lookup's in its order, with pr, maps, dirs and roughness among the NULL checks, pr's own checks before pd's, maps 16-byte aligned
+   with on_device, and FW_ERR_UNSUPPORTED for n_probes x M >= 2^31. */
+int fw_probe_radiance_lookup(const fw_probe_grid *grid, const fw_probe_radiance *pr, const float *maps, const fw_probe_depth *pd, const float *moments,
+                             float normal_bias, const float *placement, int device, uint32_t n, const float *positions, const float *normals,
+                             uint32_t stride_floats, const float *dirs, const float *roughness, float *radiance, int on_device, void *stream);
+
+/* fw_probe_shade_glossy: the glossy shade above over fw_probe_shade_placed's arguments (placement may be NULL).  Errors: its
+   counterpart's in its order, with pr, maps, spec and view among the NULL checks, view_stride_floats < 3 after gamma, and with on_device
+   spec and maps 16-byte aligned like aov. */
+int fw_probe_shade_glossy(const fw_probe_grid *grid, const float *sh, const fw_probe_radiance *pr, const float *maps, const fw_probe_depth *pd,
+                          const float *moments, float normal_bias, const float *placement, const fw_probe_shade_params *p, const float *aov,
+                          const float *spec, const float *view, uint32_t view_stride_floats, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8);
+
 /* Diagnostic: the kernels' division / square-root helpers against the compiler's IEEE expansion, bit for bit,
    on n hashed operand pairs.  mode 0 = magnitudes 2^-40..2^40 (must be 0 mismatches), mode 1 = all bit patterns. */
 int fw_selftest_arith(int device, uint32_t n, uint32_t seed, int mode, uint64_t *div_mismatches, uint64_t *sqrt_mismatches);
