@@ -3685,68 +3685,184 @@ int temporal_impl(const fw_temporal_params *p, const float *color, const float *
     return FW_OK;
 }
 
-// ---- what the calls that generate rays, render them and reduce the result share --------------------------------
+// ---- what the calls that stage arrays, generate rays, render or trace them and reduce the result share --------
 // device scratch of one call, released on every way out of the function that owns it
 struct CallScratch : DevBuf { int dev; explicit CallScratch(int d) : dev(d) {} ~CallScratch() { if (p) { (void)hipSetDevice(dev); release(); } } };
 // events around a call's own kernels, created only when the caller reads stats
 template <int N> struct CallEvents { hipEvent_t e[N] = {}; ~CallEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } };
 
-// the rays (and, in a bake, their accum) of an automatic chunk of fw_render_model, fw_bake_probes and fw_bake_lightmap, and the slab of
-// the host output of fw_model_rays, fw_probe_rays and fw_lightmap_rays
+// the rays (and, in a bake, their accum or hits) of an automatic chunk of fw_render_model and the bakers, and the slab of a host call's
+// per-item arrays
 constexpr size_t CALL_SCRATCH_BYTES = (size_t)256 << 20;
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// The arrays of one call on the device.  Each is declared once, with its byte size, as read (IN), read and written (INOUT), overwritten
+// (OUT), the call's own work space (WORK) or work space that starts as zeros (ZERO).  A caller's device array is used where it lies; a
+// host array (every array of a host call, and whatever is declared `host_always`) and the work space get 256-byte aligned slots of one
+// allocation: none at all when no slot is needed.  up() allocates and enqueues the uploads and the zeroing in declaration order;
+// finish() enqueues the downloads not made yet in declaration order, drains the stream and reports the kernels' error.  From up() to
+// the end of finish() every way out drains the stream before the scratch is released.  A NULL array takes no slot and stays NULL.
+struct Staged {
+    enum Kind { IN, INOUT, OUT, WORK, ZERO };
+    struct Slot { Kind kind; void *host; size_t bytes, at; bool staged, back; };
+    hipStream_t stream; bool on_device; CallScratch scratch;
+    Slot slots[12] = {}; int n_slots = 0; size_t off = 0; bool armed = false;
+    Staged(int device, hipStream_t stream_, bool on_device_) : stream(stream_), on_device(on_device_), scratch(device) {}
+    ~Staged() { if (armed) (void)hipStreamSynchronize(stream); }
+    int add(Kind kind, const void *p, size_t bytes, bool host_always = false) {
+        const bool staged = kind == WORK || kind == ZERO || (p && (host_always || !on_device));
+        slots[n_slots] = Slot{kind, const_cast<void *>(p), bytes, off, staged, staged && (kind == INOUT || kind == OUT)};
+        if (staged) off += align256(bytes);
+        return n_slots++;
+    }
+    // running sums: the caller's device memory, a host caller's staged in and out, or — NULL — zeros in the scratch that nobody reads back
+    int add_sums(float *sums, size_t bytes) { return sums ? add(INOUT, sums, bytes) : add(ZERO, nullptr, bytes); }
+    template <class T> T *ptr(int i) const { const Slot &s = slots[i]; return s.staged ? (T *)((uint8_t *)scratch.p + s.at) : (T *)s.host; }
+    int put(int i, const void *src) { HIPCHK(hipMemcpyAsync(ptr<void>(i), src, slots[i].bytes, hipMemcpyHostToDevice, stream)); return FW_OK; }
+    int get(int i, void *dst) { HIPCHK(hipMemcpyAsync(dst, ptr<void>(i), slots[i].bytes, hipMemcpyDeviceToHost, stream)); return FW_OK; }
+    int up() {
+        if (int rc = scratch.alloc(off)) return rc;
+        armed = true;
+        for (int i = 0; i < n_slots; i++) {
+            const Slot &s = slots[i];
+            if (!s.staged || !s.bytes) continue;
+            if (s.kind == IN || s.kind == INOUT) { if (int rc = put(i, s.host)) return rc; }
+            else if (s.kind == ZERO) HIPCHK(hipMemsetAsync(ptr<void>(i), 0, s.bytes, stream));
+        }
+        return FW_OK;
+    }
+    // a staged INOUT or OUT slot goes back to its host array, once
+    int download(int i) {
+        if (!slots[i].back) return FW_OK;
+        slots[i].back = false;
+        return get(i, slots[i].host);
+    }
+    // where the slot's content lands on the host: a host caller's own array (its download), else — if `need` — `keep`; else nowhere (NULL)
+    int fetch(int i, bool need, std::vector<float> &keep, const float *&landed) {
+        landed = nullptr;
+        if (slots[i].back) { landed = (const float *)slots[i].host; return download(i); }
+        if (!need) return FW_OK;
+        keep.resize(slots[i].bytes / 4);
+        landed = keep.data();
+        return get(i, keep.data());
+    }
+    int finish() {
+        for (int i = 0; i < n_slots; i++) if (int rc = download(i)) return rc;
+        HIPCHK(hipStreamSynchronize(stream));
+        armed = false;
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+};
+
+// The per-item arrays of a call over n items.  Device arrays: one launch over the caller's memory.  Host arrays: slabs of `per` items
+// through slots of `st` — declare every array before st.up() — and per slab: the inputs copied in (a strided one packed first: three
+// floats per item from `host`, three more from `with`), launch(first_item, k), the outputs copied back, the stream drained.  `pack` is
+// the one strided input's host staging: a call declares at most one.
+struct HostSlabs {
+    struct Arr { void *host; size_t item; uint32_t stride; const float *with; int slot; bool out; };
+    Staged &st; uint32_t n, per;
+    Arr arrs[8] = {}; int n_arrs = 0; std::vector<float> pack;
+    HostSlabs(Staged &st_, uint32_t n_, size_t slab_item_bytes) : st(st_), n(n_), per((uint32_t)std::min<uint64_t>(n_, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / slab_item_bytes))) {}
+    int add(const void *host, size_t item, uint32_t stride, const float *with, bool out) {
+        const bool slab = host && !st.on_device;
+        arrs[n_arrs] = Arr{const_cast<void *>(host), item, stride, with, slab ? st.add(Staged::WORK, nullptr, (size_t)per * item) : -1, out};
+        if (slab && stride) pack.resize((size_t)per * item / 4);
+        return n_arrs++;
+    }
+    int in(const void *host, size_t item, uint32_t stride = 0, const float *with = nullptr) { return add(host, item, stride, with, false); }
+    int out(void *host, size_t item) { return add(host, item, 0, nullptr, true); }
+    template <class T> T *ptr(int a) const { return arrs[a].slot < 0 ? (T *)arrs[a].host : st.ptr<T>(arrs[a].slot); }
+    // of a strided input: where its second three floats are, and its stride on the device
+    const float *with(int a) const { return arrs[a].slot < 0 ? arrs[a].with : ptr<float>(a) + 3; }
+    uint32_t stride(int a) const { return arrs[a].slot < 0 ? arrs[a].stride : (uint32_t)(arrs[a].item / 4); }
+    template <class Launch> int run(Launch launch) {
+        if (st.on_device) launch(0u, n);
+        else for (uint32_t done = 0; done < n; done += per) {
+            const uint32_t k = std::min(per, n - done);
+            for (int a = 0; a < n_arrs; a++) {
+                const Arr &A = arrs[a];
+                if (A.slot < 0 || A.out) continue;
+                const void *src = (const uint8_t *)A.host + (size_t)done * A.item;
+                if (A.stride) {
+                    const size_t w = A.item / 4;
+                    for (uint32_t i = 0; i < k; i++) {
+                        const float *ps = (const float *)A.host + (size_t)(done + i) * A.stride;
+                        float *o = pack.data() + (size_t)i * w;
+                        o[0] = ps[0]; o[1] = ps[1]; o[2] = ps[2];
+                        if (A.with) { const float *ns = A.with + (size_t)(done + i) * A.stride; o[3] = ns[0]; o[4] = ns[1]; o[5] = ns[2]; }
+                    }
+                    src = pack.data();
+                }
+                HIPCHK(hipMemcpyAsync(st.ptr<void>(A.slot), src, (size_t)k * A.item, hipMemcpyHostToDevice, st.stream));
+            }
+            launch(done, k);
+            for (int a = 0; a < n_arrs; a++) {
+                const Arr &A = arrs[a];
+                if (A.slot >= 0 && A.out) HIPCHK(hipMemcpyAsync((uint8_t *)A.host + (size_t)done * A.item, st.ptr<void>(A.slot), (size_t)k * A.item, hipMemcpyDeviceToHost, st.stream));
+            }
+            HIPCHK(hipStreamSynchronize(st.stream));
+        }
+        if (st.on_device) HIPCHK(hipStreamSynchronize(st.stream));
+        st.armed = false;
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+};
 
 // Host output of a ray generator: `n` items of `item_bytes` of rays each go to `dst` in slabs through scratch of the call's own.
 // launch(first_item, k, d_slab) enqueues the generator for the items [first_item, first_item + k).  Returns with the stream drained.
 template <class Launch> int host_slabs(hipStream_t stream, int device, uint32_t n, size_t item_bytes, float *dst, Launch launch) {
-    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / item_bytes));
-    CallScratch slab(device);
-    if (int rc = slab.alloc((size_t)per * item_bytes)) { (void)hipStreamSynchronize(stream); return rc; }
-    for (uint32_t done = 0; done < n; done += per) {
-        const uint32_t k = std::min(per, n - done);
-        launch(done, k, (float *)slab.p);
-        HIPCHK(hipMemcpyAsync((uint8_t *)dst + (size_t)done * item_bytes, slab.p, (size_t)k * item_bytes, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-    }
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    Staged st(device, stream, false);
+    HostSlabs sl(st, n, item_bytes);
+    const int rays = sl.out(dst, item_bytes);
+    if (int rc = st.up()) { (void)hipStreamSynchronize(stream); return rc; }
+    return sl.run([&](uint32_t done, uint32_t k) { launch(done, k, sl.ptr<float>(rays)); });
 }
 
-// The rounds of a bake (fw_bake_probes, fw_bake_lightmap): per round r of [first_round, first_round + rounds) and chunk of
-// the `n_items` items (probes, covered texels) with `directions` rays each: generate(r, first_item, k, d_rays) enqueues the rays of
-// k items, render_impl renders them into the zeroed d_acc — the fw_render_rays call of the chunk (rays_impl's frame) with gamma 1, seed
-// + r and key_base = first_item x directions — and reduce(first_item, k, d_rays, d_acc) enqueues the chunk's reduction into the running
-// sums.  total (the caller reads stats): the chunks' stats, plus the two kernels' time and the bytes they move: 24 per ray and gen_item per
-// item generated, red_ray per ray and red_item per item reduced.  The caller owns the checks, the scratch and the outputs; on an error
-// the stream is drained.
-struct BakeRounds {
-    uint32_t first_round, rounds, n_items, directions, chunk;
-    float *d_rays, *d_acc;                             // chunk x directions x 24 and x 16 bytes of the call's scratch
-    uint32_t gen_item, red_ray, red_item;
-};
-template <class Generate, class Reduce>
-int bake_rounds(fw_scene *sc, const fw_render_rays_params *rp, const BakeRounds &b, fw_stats *total, Generate generate, Reduce reduce) {
-    hipStream_t stream = (hipStream_t)rp->stream;
-    const uint32_t S = rp->samples;
-    const bool timing = (rp->flags & FW_FLAG_TIME_KERNELS) != 0;
+// A float output that the host computes: fill(out) writes its n floats — into a host caller's array, or into a temporary that is then
+// copied to the caller's device memory
+template <class Fill> int host_output(hipStream_t stream, float *dst, size_t n, bool on_device, Fill fill) {
+    std::vector<float> tmp;
+    float *out = dst;
+    if (on_device) { tmp.resize(n); out = tmp.data(); }
+    fill(out);
+    if (on_device) {
+        HIPCHK(hipMemcpyAsync(dst, tmp.data(), n * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    return FW_OK;
+}
+// sh = sums / rounds so far, divided on the host in double and rounded once (fw_bake_probes, fw_bake_probe_radiance)
+int sh_from_sums(hipStream_t stream, const float *h_sums, size_t n, uint32_t first_round, uint32_t rounds, float *sh, bool on_device) {
+    const double n_rounds = (double)((uint64_t)first_round + rounds);
+    return host_output(stream, sh, n, on_device, [&](float *out) { for (size_t i = 0; i < n; i++) out[i] = (float)((double)h_sums[i] / n_rounds); });
+}
+// the stats of a chunked call, handed to the caller that reads them
+void stats_finish(fw_stats *stats, const fw_stats &total, std::chrono::steady_clock::time_point wall0) {
+    if (!stats) return;
+    *stats = total;
+    stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+}
+
+// The chunks of one round of a bake: per chunk of the `n_items` items (probes, covered texels, points) generate(first_item,
+// k) enqueues the rays of k items, middle(first_item, k, stats or NULL) renders or traces them and reduce(first_item, k) enqueues the
+// chunk's reduction.  total (the caller reads stats): the middle steps' stats, plus the two kernels' time — in ms_render always, in
+// ms_raygen / ms_accumulate with FW_FLAG_TIME_KERNELS.  The caller owns the checks, the scratch, the outputs and the draining.
+struct BakeChunks {
+    hipStream_t stream; uint32_t n_items, chunk; bool timing; fw_stats *total;
     CallEvents<4> ev;                                 // around the two kernels' launches
-    if (total) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
-    for (uint32_t r = b.first_round; r - b.first_round < b.rounds; r++) {      // (first_round + rounds may be 2^32 - 1: r itself never gets there)
-        fw_render_rays_params q = *rp;
-        q.gamma = 1.f; q.on_device = 1; q.seed = rp->seed + r;
-        for (uint32_t i0 = 0; i0 < b.n_items; i0 += b.chunk) {
-            const uint32_t k = std::min(b.chunk, b.n_items - i0), n = k * b.directions;
-            q.n_rays = n;
+    int begin() { if (total) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e)); return FW_OK; }
+    template <class Generate, class Middle, class Reduce> int round(Generate generate, Middle middle, Reduce reduce) {
+        for (uint32_t i0 = 0; i0 < n_items; i0 += chunk) {
+            const uint32_t k = std::min(chunk, n_items - i0);
             if (total) HIPCHK(hipEventRecord(ev.e[0], stream));
-            generate(r, i0, k, b.d_rays);
+            generate(i0, k);
             if (total) HIPCHK(hipEventRecord(ev.e[1], stream));
-            HIPCHK(hipMemsetAsync(b.d_acc, 0, (size_t)n * 16, stream));
-            const fw_render_params P = rays_frame(&q, S);
-            const RayInput ri{b.d_rays, n, false, nullptr, i0 * b.directions, true};
             fw_stats gs{};
-            if (int rc = render_impl(sc, &P, nullptr, nullptr, nullptr, total ? &gs : nullptr, 0, b.d_acc, nullptr, nullptr, &ri)) { (void)hipStreamSynchronize(stream); return rc; }
+            if (int rc = middle(i0, k, total ? &gs : nullptr)) return rc;
             if (total) HIPCHK(hipEventRecord(ev.e[2], stream));
-            reduce(i0, k, b.d_rays, b.d_acc);
+            reduce(i0, k);
             if (!total) continue;
             HIPCHK(hipEventRecord(ev.e[3], stream));
             HIPCHK(hipEventSynchronize(ev.e[3]));
@@ -3756,10 +3872,70 @@ int bake_rounds(fw_scene *sc, const fw_render_rays_params *rp, const BakeRounds 
             stats_add(*total, gs);
             total->ms_render += gen_ms + red_ms;
             if (timing) { total->ms_raygen += gen_ms; total->ms_accumulate += red_ms; }
-            total->bytes_raygen += (uint64_t)n * 24 + (uint64_t)k * b.gen_item;
-            total->bytes_accumulate += (uint64_t)n * b.red_ray + (uint64_t)k * b.red_item;
         }
+        return FW_OK;
     }
+};
+
+// The rounds of a bake that renders (fw_bake_probes, fw_bake_lightmap, fw_bake_probe_radiance): per round r of [first_round, first_round
+// + rounds) BakeChunks' chunks with render_impl as the middle step: the chunk's `directions` rays per item rendered into the zeroed
+// d_acc — the fw_render_rays call of the chunk (rays_impl's frame) with gamma 1, seed + r and key_base = first_item x directions.
+// generate(r, first_item, k, d_rays) and reduce(first_item, k, d_rays, d_acc) are the caller's kernels; their bytes join the chunk's
+// stats: 24 per ray and gen_item per item generated, red_ray per ray and red_item per item reduced.
+struct BakeRounds {
+    uint32_t first_round, rounds, n_items, directions, chunk;
+    float *d_rays, *d_acc;                             // chunk x directions x 24 and x 16 bytes of the call's scratch
+    uint32_t gen_item, red_ray, red_item;
+};
+template <class Generate, class Reduce>
+int bake_rounds(fw_scene *sc, const fw_render_rays_params *rp, const BakeRounds &b, fw_stats *total, Generate generate, Reduce reduce) {
+    hipStream_t stream = (hipStream_t)rp->stream;
+    BakeChunks c{stream, b.n_items, b.chunk, (rp->flags & FW_FLAG_TIME_KERNELS) != 0, total};
+    if (int rc = c.begin()) return rc;
+    for (uint32_t r = b.first_round; r - b.first_round < b.rounds; r++) {      // (first_round + rounds may be 2^32 - 1: r itself never gets there)
+        fw_render_rays_params q = *rp;
+        q.gamma = 1.f; q.on_device = 1; q.seed = rp->seed + r;
+        const auto render = [&](uint32_t i0, uint32_t k, fw_stats *gs) {
+            const uint32_t n = k * b.directions;
+            q.n_rays = n;
+            HIPCHK(hipMemsetAsync(b.d_acc, 0, (size_t)n * 16, stream));
+            const fw_render_params P = rays_frame(&q, rp->samples);
+            const RayInput ri{b.d_rays, n, false, nullptr, i0 * b.directions, true};
+            if (int rc = render_impl(sc, &P, nullptr, nullptr, nullptr, gs, 0, b.d_acc, nullptr, nullptr, &ri)) return rc;
+            if (gs) {
+                gs->bytes_raygen += (uint64_t)n * 24 + (uint64_t)k * b.gen_item;
+                gs->bytes_accumulate += (uint64_t)n * b.red_ray + (uint64_t)k * b.red_item;
+            }
+            return (int)FW_OK;
+        };
+        if (int rc = c.round([&](uint32_t i0, uint32_t k) { generate(r, i0, k, b.d_rays); }, render,
+                             [&](uint32_t i0, uint32_t k) { reduce(i0, k, b.d_rays, b.d_acc); }))
+            return rc;
+    }
+    return FW_OK;
+}
+
+// The same for a bake that traces (fw_bake_probe_depth, fw_bake_ao, and fw_relocate_probes one step at a time): the middle step of round
+// r is trace_impl over the chunk's rays with seed + r and key_base = first_item x directions.  The traced bakes count no bytes of their own.
+struct TraceRounds {
+    uint32_t n_items, directions, chunk;
+    float *d_rays; fw_hit *d_hits;                     // chunk x directions x 24 bytes and x one fw_hit of the call's scratch
+};
+template <class Generate, class Reduce>
+int trace_round(fw_scene *sc, const fw_trace_params *tp, const TraceRounds &b, BakeChunks &c, uint32_t r, Generate generate, Reduce reduce) {
+    fw_trace_params q = *tp;
+    q.on_device = 1; q.seed = tp->seed + r;
+    return c.round([&](uint32_t i0, uint32_t k) { generate(r, i0, k, b.d_rays); },
+                   [&](uint32_t i0, uint32_t k, fw_stats *gs) { q.key_base = i0 * b.directions; return trace_impl(sc, &q, b.d_rays, k * b.directions, b.d_hits, gs); },
+                   [&](uint32_t i0, uint32_t k) { reduce(i0, k, b.d_rays, b.d_hits); });
+}
+template <class Generate, class Reduce>
+int trace_rounds(fw_scene *sc, const fw_trace_params *tp, const TraceRounds &b, uint32_t first_round, uint32_t rounds, fw_stats *total, Generate generate,
+                 Reduce reduce) {
+    BakeChunks c{(hipStream_t)tp->stream, b.n_items, b.chunk, (tp->flags & FW_FLAG_TIME_KERNELS) != 0, total};
+    if (int rc = c.begin()) return rc;
+    for (uint32_t r = first_round; r - first_round < rounds; r++)      // (first_round + rounds may be 2^32 - 1: r itself never gets there)
+        if (int rc = trace_round(sc, tp, b, c, r, generate, reduce)) return rc;
     return FW_OK;
 }
 
@@ -3955,8 +4131,8 @@ int probe_rays_impl(const fw_probe_set *s, int device, uint32_t round, uint32_t 
     });
 }
 
-// fw_probe_project: with host arrays one device allocation per call holds the inputs and the sums, released on every way out; with
-// device arrays the kernel works on the caller's memory and nothing is allocated
+// fw_probe_project: a one-shot call over Staged arrays — with host arrays one device allocation per call holds the inputs and the sums,
+// released on every way out; with device arrays the kernel works on the caller's memory and nothing is allocated
 int probe_project_impl(int device, uint32_t n_probes, uint32_t directions, uint32_t samples, const float *rays, const float *accum, float *sums,
                        int on_device, void *stream_) {
     if (!rays || !accum || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -3968,27 +4144,16 @@ int probe_project_impl(int device, uint32_t n_probes, uint32_t directions, uint3
     if ((uint64_t)n_probes * directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const size_t n = (size_t)n_probes * directions, sum_bytes = (size_t)n_probes * 108;
-    CallScratch scratch(device);
-    const float *d_rays = rays, *d_acc = accum; float *d_sums = sums;
-    if (!on_device) {
-        const size_t o_acc = align256(n * 24), o_sums = o_acc + align256(n * 16);
-        if (int rc = scratch.alloc(o_sums + sum_bytes)) return rc;
-        uint8_t *base = (uint8_t *)scratch.p;
-        HIPCHK(hipMemcpyAsync(base, rays, n * 24, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_acc, accum, n * 16, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
-        d_rays = (const float *)base; d_acc = (const float *)(base + o_acc); d_sums = (float *)(base + o_sums);
-    }
-    fw::launch_probe_project(stream, device_cus(device), n_probes, directions, samples, d_rays, d_acc, d_sums);
-    if (!on_device) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    const size_t n = (size_t)n_probes * directions;
+    Staged st(device, stream, on_device != 0);
+    const int i_rays = st.add(Staged::IN, rays, n * 24), i_acc = st.add(Staged::IN, accum, n * 16), i_sums = st.add(Staged::INOUT, sums, (size_t)n_probes * 108);
+    if (int rc = st.up()) return rc;
+    fw::launch_probe_project(stream, device_cus(device), n_probes, directions, samples, st.ptr<const float>(i_rays), st.ptr<const float>(i_acc), st.ptr<float>(i_sums));
+    return st.finish();
 }
 
-// fw_bake_probes: its own are the argument checks, the scratch (positions, a chunk's rays and accum, the running sums unless the caller's
-// device memory holds them), k_probe_rays and k_probe_project as bake_rounds' generator and reducer, and sh, divided on the host.
+// fw_bake_probes: its own are the argument checks, the Staged arrays (positions, a chunk's rays and accum, the running sums unless the
+// caller's device memory holds them), k_probe_rays and k_probe_project as bake_rounds' generator and reducer, and sh, divided on the host.
 int bake_probes_impl(fw_scene *sc, const fw_probe_set *s, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, float *sums,
                      float *sh, fw_stats *stats) {
     if (!sc || !s || !rp) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -4007,49 +4172,26 @@ int bake_probes_impl(fw_scene *sc, const fw_probe_set *s, const fw_render_rays_p
     hipStream_t stream = (hipStream_t)rp->stream;
     const uint32_t N = s->n_probes, D = s->directions, S = rp->samples;
     const uint32_t chunk = std::min<uint32_t>(N, s->chunk_probes ? s->chunk_probes : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 40)));
-    const size_t sum_bytes = (size_t)N * 108;
-    const bool own_sums = !rp->on_device || !sums;        // the running sums live in the scratch: a host caller's, or nobody's
-    const size_t o_rays = align256((size_t)N * 12), o_acc = o_rays + align256((size_t)chunk * D * 24),
-                 o_sums = o_acc + align256((size_t)chunk * D * 16);
-    CallScratch scratch(dev);
-    if (int rc = scratch.alloc(o_sums + (own_sums ? sum_bytes : 0))) return rc;
-    uint8_t *base = (uint8_t *)scratch.p;
-    const float *d_pos = (const float *)base;
-    float *d_rays = (float *)(base + o_rays), *d_acc = (float *)(base + o_acc), *d_sums = own_sums ? (float *)(base + o_sums) : sums;
-    HIPCHK(hipMemcpyAsync(base, s->positions, (size_t)N * 12, hipMemcpyHostToDevice, stream));
-    if (own_sums) {
-        if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
-        else HIPCHK(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
-    }
+    Staged st(dev, stream, rp->on_device != 0);
+    const int i_pos = st.add(Staged::IN, s->positions, (size_t)N * 12, true), i_rays = st.add(Staged::WORK, nullptr, (size_t)chunk * D * 24),
+              i_acc = st.add(Staged::WORK, nullptr, (size_t)chunk * D * 16), i_sums = st.add_sums(sums, (size_t)N * 108);
+    if (int rc = st.up()) return rc;
+    const float *d_pos = st.ptr<const float>(i_pos);
+    float *d_sums = st.ptr<float>(i_sums);
     const int n_cus = device_cus(dev);
     fw_stats total{};
-    const BakeRounds b{first_round, rounds, N, D, chunk, d_rays, d_acc, 0, 40, 216};       // (the projection's loads and its sums)
+    const BakeRounds b{first_round, rounds, N, D, chunk, st.ptr<float>(i_rays), st.ptr<float>(i_acc), 0, 40, 216};       // (the projection's loads and its sums)
     if (int rc = bake_rounds(sc, rp, b, stats ? &total : nullptr,
             [&](uint32_t r, uint32_t p0, uint32_t k, float *rays) { fw::launch_probe_rays(stream, n_cus, probes_device(s, r, p0, d_pos + (size_t)p0 * 3), k, rays); },
             [&](uint32_t p0, uint32_t k, const float *rays, const float *acc) { fw::launch_probe_project(stream, n_cus, k, D, S, rays, acc, d_sums + (size_t)p0 * 27); }))
         return rc;
-    // the outputs: sums where the caller keeps them, and sh = sums / rounds so far, divided on the host in double and rounded once
-    std::vector<float> host;
-    const float *h_sums = sums;
-    if (!rp->on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-    else if (sh) { host.resize((size_t)N * 27); h_sums = host.data(); HIPCHK(hipMemcpyAsync(host.data(), d_sums, sum_bytes, hipMemcpyDeviceToHost, stream)); }
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    if (sh) {
-        const double n_rounds = (double)((uint64_t)first_round + rounds);
-        std::vector<float> tmp;
-        float *out = sh;
-        if (rp->on_device) { tmp.resize((size_t)N * 27); out = tmp.data(); }
-        for (size_t i = 0; i < (size_t)N * 27; i++) out[i] = (float)((double)h_sums[i] / n_rounds);
-        if (rp->on_device) {
-            HIPCHK(hipMemcpyAsync(sh, tmp.data(), sum_bytes, hipMemcpyHostToDevice, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-        }
-    }
-    if (stats) {
-        *stats = total;
-        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    }
+    // the outputs: sums where the caller keeps them, and sh = sums / rounds so far
+    std::vector<float> keep;
+    const float *h_sums = nullptr;
+    if (int rc = st.fetch(i_sums, sh != nullptr, keep, h_sums)) return rc;
+    if (int rc = st.finish()) return rc;
+    if (sh) if (int rc = sh_from_sums(stream, h_sums, (size_t)N * 27, first_round, rounds, sh, rp->on_device != 0)) return rc;
+    stats_finish(stats, total, wall0);
     return FW_OK;
 }
 
@@ -4094,29 +4236,28 @@ int lightmap_check(const fw_lightmap *lm, bool &too_large) {
 }
 
 // What every lightmap call makes first, once: the mesh on the device, k_lm_cover and k_lm_texels, the owner map back on the host and the
-// covered list (one host pass over the 4 B / texel owner map: ascending, deterministic) on both sides.
+// covered list (one host pass over the 4 B / texel owner map: ascending, deterministic) on both sides.  Its Staged arrays live as long as
+// the call's, and drain the stream before they are released.
 struct LightmapTexels {
-    CallScratch scratch;
+    Staged st;                                                                 // the mesh, the owner map, the records and the list
     float *records = nullptr; uint32_t *owner = nullptr, *list = nullptr;      // device: W H x 8 floats, W H, n_cov
     std::vector<uint32_t> h_owner, h_list;
-    explicit LightmapTexels(int dev) : scratch(dev) {}
+    explicit LightmapTexels(int dev) : st(dev, nullptr, false) {}
 };
 
 int lightmap_texels_make(const fw_lightmap *lm, int device, hipStream_t stream, LightmapTexels &T) {
     const size_t n_tex = (size_t)lm->width * lm->height, nv = lm->n_verts;
-    const size_t o_idx = align256(nv * 12), o_nrm = o_idx + align256((size_t)lm->n_indices * 4), o_uv = o_nrm + align256(lm->normals ? nv * 12 : 0),
-                 o_own = o_uv + align256(nv * 8), o_rec = o_own + align256(n_tex * 4), o_list = o_rec + align256(n_tex * 32);
-    if (int rc = T.scratch.alloc(o_list + n_tex * 4)) return rc;
-    uint8_t *base = (uint8_t *)T.scratch.p;
-    HIPCHK(hipMemcpyAsync(base, lm->verts, nv * 12, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(base + o_idx, lm->indices, (size_t)lm->n_indices * 4, hipMemcpyHostToDevice, stream));
-    if (lm->normals) HIPCHK(hipMemcpyAsync(base + o_nrm, lm->normals, nv * 12, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(base + o_uv, lm->uvs, nv * 8, hipMemcpyHostToDevice, stream));
-    T.owner = (uint32_t *)(base + o_own); T.records = (float *)(base + o_rec); T.list = (uint32_t *)(base + o_list);
+    Staged &st = T.st;
+    st.stream = stream;
+    const int i_verts = st.add(Staged::IN, lm->verts, nv * 12), i_idx = st.add(Staged::IN, lm->indices, (size_t)lm->n_indices * 4),
+              i_nrm = st.add(Staged::IN, lm->normals, nv * 12), i_uv = st.add(Staged::IN, lm->uvs, nv * 8),
+              i_own = st.add(Staged::WORK, nullptr, n_tex * 4), i_rec = st.add(Staged::WORK, nullptr, n_tex * 32), i_list = st.add(Staged::WORK, nullptr, n_tex * 4);
+    if (int rc = st.up()) return rc;
+    T.owner = st.ptr<uint32_t>(i_own); T.records = st.ptr<float>(i_rec); T.list = st.ptr<uint32_t>(i_list);
     HIPCHK(hipMemsetAsync(T.owner, 0xff, n_tex * 4, stream));
     fw::DLightmapMesh m{};
-    m.verts = (const float *)base; m.indices = (const uint32_t *)(base + o_idx);
-    m.normals = lm->normals ? (const float *)(base + o_nrm) : nullptr; m.uvs = (const float *)(base + o_uv);
+    m.verts = st.ptr<const float>(i_verts); m.indices = st.ptr<const uint32_t>(i_idx);
+    m.normals = st.ptr<const float>(i_nrm); m.uvs = st.ptr<const float>(i_uv);
     m.n_tris = lm->n_indices / 3u; m.width = lm->width; m.height = lm->height;
     rotor_rows(lm->rotation, m.rows);
     m.rotated = 0.5f * ((m.rows[0][0] + m.rows[1][1] + m.rows[2][2]) - 1.f) < 0.999f ? 1u : 0u;
@@ -4126,7 +4267,7 @@ int lightmap_texels_make(const fw_lightmap *lm, int device, hipStream_t stream, 
     fw::launch_lm_cover(stream, n_cus, m, T.owner);
     fw::launch_lm_texels(stream, n_cus, m, T.owner, (float4 *)T.records);
     T.h_owner.resize(n_tex);
-    HIPCHK(hipMemcpyAsync(T.h_owner.data(), T.owner, n_tex * 4, hipMemcpyDeviceToHost, stream));
+    if (int rc = st.get(i_own, T.h_owner.data())) return rc;
     HIPCHK(hipStreamSynchronize(stream));
     HIPCHK(hipGetLastError());
     T.h_list.clear();
@@ -4206,23 +4347,12 @@ int lightmap_reduce_impl(int device, uint32_t n, uint32_t directions, uint32_t s
     if ((uint64_t)n * directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const size_t entries = (size_t)n * directions, sum_bytes = (size_t)n_texels * 16;
-    CallScratch scratch(device);
-    const float *d_acc = accum; float *d_sums = sums; const uint32_t *d_ids = texel_ids;
-    if (!on_device) {
-        const size_t o_sums = align256(entries * 16), o_ids = o_sums + align256(sum_bytes);
-        if (int rc = scratch.alloc(o_ids + (size_t)n * 4)) return rc;
-        uint8_t *base = (uint8_t *)scratch.p;
-        HIPCHK(hipMemcpyAsync(base, accum, entries * 16, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
-        if (texel_ids) HIPCHK(hipMemcpyAsync(base + o_ids, texel_ids, (size_t)n * 4, hipMemcpyHostToDevice, stream));
-        d_acc = (const float *)base; d_sums = (float *)(base + o_sums); d_ids = texel_ids ? (const uint32_t *)(base + o_ids) : nullptr;
-    }
-    fw::launch_lm_reduce(stream, device_cus(device), n, directions, samples, d_ids, d_acc, d_sums);
-    if (!on_device) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    Staged st(device, stream, on_device != 0);
+    const int i_acc = st.add(Staged::IN, accum, (size_t)n * directions * 16), i_sums = st.add(Staged::INOUT, sums, (size_t)n_texels * 16),
+              i_ids = st.add(Staged::IN, texel_ids, (size_t)n * 4);
+    if (int rc = st.up()) return rc;
+    fw::launch_lm_reduce(stream, device_cus(device), n, directions, samples, st.ptr<const uint32_t>(i_ids), st.ptr<const float>(i_acc), st.ptr<float>(i_sums));
+    return st.finish();
 }
 
 // `passes` dilation passes of the image at d_img through the second buffer d_tmp; the result ends in d_img
@@ -4242,21 +4372,14 @@ int lightmap_dilate_impl(int device, uint32_t width, uint32_t height, uint32_t p
     if (passes == 0) return FW_OK;
     hipStream_t stream = (hipStream_t)stream_;
     const size_t bytes = (size_t)width * height * 16;
-    CallScratch scratch(device);
-    if (int rc = scratch.alloc(align256(bytes) + (on_device ? 0 : bytes))) return rc;
-    float *d_tmp = (float *)scratch.p, *d_img = image;
-    if (!on_device) {
-        d_img = (float *)((uint8_t *)scratch.p + align256(bytes));
-        HIPCHK(hipMemcpyAsync(d_img, image, bytes, hipMemcpyHostToDevice, stream));
-    }
-    if (int rc = lightmap_dilate_device(stream, width, height, passes, d_img, d_tmp)) return rc;
-    if (!on_device) HIPCHK(hipMemcpyAsync(image, d_img, bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    Staged st(device, stream, on_device != 0);
+    const int i_tmp = st.add(Staged::WORK, nullptr, bytes), i_img = st.add(Staged::INOUT, image, bytes);
+    if (int rc = st.up()) return rc;
+    if (int rc = lightmap_dilate_device(stream, width, height, passes, st.ptr<float>(i_img), st.ptr<float>(i_tmp))) return rc;
+    return st.finish();
 }
 
-// fw_bake_lightmap: its own are the argument checks, the texels, the scratch (a chunk's rays and accum, the running sums and the
+// fw_bake_lightmap: its own are the argument checks, the texels, the Staged arrays (a chunk's rays and accum, the running sums and the
 // irradiance unless the caller's device memory holds them, the dilation's second image), k_lm_rays and k_lm_reduce over the covered list
 // as bake_rounds' generator and reducer, and the irradiance: k_lm_resolve and the dilation.
 int bake_lightmap_impl(fw_scene *sc, const fw_lightmap *lm, const fw_render_rays_params *rp, uint32_t first_round, uint32_t rounds, uint32_t dilate,
@@ -4282,39 +4405,28 @@ int bake_lightmap_impl(fw_scene *sc, const fw_lightmap *lm, const fw_render_rays
     const size_t n_tex = (size_t)lm->width * lm->height, img_bytes = n_tex * 16;
     const uint32_t chunk = std::max<uint32_t>(1u, std::min<uint32_t>(N, lm->chunk_texels ? lm->chunk_texels
                                                                                          : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 40))));
-    const bool own_sums = !rp->on_device || !sums;        // the running sums live in the scratch: a host caller's, or nobody's
-    const bool own_irr = irradiance && !rp->on_device;
-    const size_t o_acc = align256((size_t)chunk * D * 24), o_sums = o_acc + align256((size_t)chunk * D * 16),
-                 o_irr = o_sums + align256(own_sums ? img_bytes : 0), o_tmp = o_irr + align256(own_irr ? img_bytes : 0);
-    CallScratch scratch(dev);
-    if (int rc = scratch.alloc(o_tmp + (irradiance && dilate ? img_bytes : 0))) { (void)hipStreamSynchronize(stream); return rc; }
-    uint8_t *base = (uint8_t *)scratch.p;
-    float *d_rays = (float *)base, *d_acc = (float *)(base + o_acc), *d_sums = own_sums ? (float *)(base + o_sums) : sums;
-    if (own_sums) {
-        if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, img_bytes, hipMemcpyHostToDevice, stream));
-        else HIPCHK(hipMemsetAsync(d_sums, 0, img_bytes, stream));
-    }
+    Staged st(dev, stream, rp->on_device != 0);
+    const int i_rays = st.add(Staged::WORK, nullptr, (size_t)chunk * D * 24), i_acc = st.add(Staged::WORK, nullptr, (size_t)chunk * D * 16),
+              i_sums = st.add_sums(sums, img_bytes), i_irr = st.add(Staged::OUT, irradiance, img_bytes),
+              i_tmp = st.add(Staged::WORK, nullptr, irradiance && dilate ? img_bytes : 0);
+    if (int rc = st.up()) return rc;
+    float *d_sums = st.ptr<float>(i_sums);
     const int n_cus = device_cus(dev);
     fw_stats total{};
-    const BakeRounds b{first_round, rounds, N, D, chunk, d_rays, d_acc, 36, 16, 28};       // (the generator's records and ids; the reduction's loads and its sums)
+    const BakeRounds b{first_round, rounds, N, D, chunk, st.ptr<float>(i_rays), st.ptr<float>(i_acc), 36, 16, 28};       // (the generator's records and ids; the reduction's loads and its sums)
     if (int rc = bake_rounds(sc, rp, b, stats ? &total : nullptr,
             [&](uint32_t r, uint32_t q0, uint32_t k, float *rays) { fw::launch_lm_rays(stream, n_cus, lightmap_rays_device(lm, r, T, q0), k, rays); },
             [&](uint32_t q0, uint32_t k, const float *, const float *acc) { fw::launch_lm_reduce(stream, n_cus, k, D, S, T.list + q0, acc, d_sums); }))
         return rc;
     // the outputs: sums where the caller keeps them; irradiance = sums / rounds so far on covered texels, then the dilation
-    if (!rp->on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, img_bytes, hipMemcpyDeviceToHost, stream));
+    if (int rc = st.download(i_sums)) return rc;
     if (irradiance) {
-        float *d_irr = own_irr ? (float *)(base + o_irr) : irradiance;
+        float *d_irr = st.ptr<float>(i_irr);
         fw::launch_lm_resolve(stream, (uint32_t)n_tex, (double)((uint64_t)first_round + rounds), T.owner, d_sums, d_irr);
-        if (int rc = lightmap_dilate_device(stream, lm->width, lm->height, dilate, d_irr, (float *)(base + o_tmp))) { (void)hipStreamSynchronize(stream); return rc; }
-        if (own_irr) HIPCHK(hipMemcpyAsync(irradiance, d_irr, img_bytes, hipMemcpyDeviceToHost, stream));
+        if (int rc = lightmap_dilate_device(stream, lm->width, lm->height, dilate, d_irr, st.ptr<float>(i_tmp))) return rc;
     }
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    if (stats) {
-        *stats = total;
-        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    }
+    if (int rc = st.finish()) return rc;
+    stats_finish(stats, total, wall0);
     return FW_OK;
 }
 
@@ -4352,155 +4464,118 @@ int probe_depth_check(const fw_probe_depth *pd) {
     if (!std::isfinite(pd->max_distance) || !(pd->max_distance > 0.f)) return fail(FW_ERR_BAD_ARG, "max_distance must be finite and > 0");
     return FW_OK;
 }
-// What the _vis calls add to fw_probe_irradiance's and fw_probe_shade's arguments; NULL: the call without visibility
-struct ProbeVis { const fw_probe_depth *pd; const float *moments; float normal_bias; };
-// What the _placed calls add; NULL: the call over the nominal grid.  In a placed call vis may be NULL: no visibility.
-struct ProbePlaced { const float *placement; };
-int probe_vis_check(const ProbeVis *vis) {
-    if (int rc = probe_depth_check(vis->pd)) return rc;
-    if (!std::isfinite(vis->normal_bias) || vis->normal_bias < 0.f) return fail(FW_ERR_BAD_ARG, "normal_bias must be finite and >= 0");
+// What the probe lookups (fw_probe_irradiance and fw_probe_shade with their _vis and _placed forms, fw_probe_radiance_lookup and
+// fw_probe_shade_glossy) take beside the grid, in one form: the tables, and which of the optional ones the entry point uses (DESIGN.md
+// §9s, §9u, §9v).  vis / placed: their pointers must not be NULL; otherwise they are not looked at.
+struct ProbeLookupArgs {
+    const float *sh;
+    const fw_probe_radiance *pr; const float *maps;
+    const fw_probe_depth *pd; const float *moments; float normal_bias;
+    const float *placement;
+    bool vis, placed;
+};
+// what the checks make of them for the kernels
+struct ProbeLookup { fw::DProbeGrid g{}; fw::DProbeRadiance d{}; bool too_large = false; size_t n_probes = 0; };
+int probe_radiance_check(const fw_probe_radiance *pr, fw::DProbeRadiance &d);
+
+// The lookups' shared checks, first part (FW_ERR_BAD_ARG only): the null pointers (own_null: the call's own), the shades' outputs, the
+// radiance description, the visibility and the grid.  The call's own checks and its alignment check follow, then probe_lookup_sizes.
+int probe_lookup_check(const fw_probe_grid *grid, const ProbeLookupArgs &a, bool own_null, bool no_output, ProbeLookup &L) {
+    if (!grid || own_null || (a.vis && (!a.pd || !a.moments)) || (a.placed && !a.placement)) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (no_output) return fail(FW_ERR_BAD_ARG, "at least one output is needed");
+    if (a.pr) if (int rc = probe_radiance_check(a.pr, L.d)) return rc;
+    if (a.vis) {
+        if (int rc = probe_depth_check(a.pd)) return rc;
+        if (!std::isfinite(a.normal_bias) || a.normal_bias < 0.f) return fail(FW_ERR_BAD_ARG, "normal_bias must be finite and >= 0");
+    }
+    if (int rc = probe_grid_check(grid, L.too_large, L.g)) return rc;
+    L.n_probes = (size_t)L.g.counts[0] * L.g.counts[1] * L.g.counts[2];
     return FW_OK;
 }
-inline bool probe_vis_too_large(const ProbeVis *vis, const fw::DProbeGrid &g) {      // n_probes x R^2 >= 2^31 (n_probes < 2^31 is checked first)
-    return vis && (uint64_t)g.counts[0] * g.counts[1] * g.counts[2] * vis->pd->resolution * vis->pd->resolution >= (1ull << 31);
+// second part (FW_ERR_UNSUPPORTED only): the tables' sizes
+int probe_lookup_sizes(const ProbeLookupArgs &a, const ProbeLookup &L) {
+    if (L.too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
+    if (a.vis && (uint64_t)L.n_probes * a.pd->resolution * a.pd->resolution >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
+    if (a.pr && (uint64_t)L.n_probes * L.d.texels >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x texels must be below 2^31");
+    return FW_OK;
+}
+// the tables as Staged inputs, in the order a host call uploads them; one that is not in use takes no slot and is NULL
+struct ProbeTables { int sh, maps, mom, pl; };
+ProbeTables probe_tables_stage(Staged &st, const ProbeLookupArgs &a, const ProbeLookup &L) {
+    const size_t R = a.vis ? a.pd->resolution : 0;
+    return ProbeTables{st.add(Staged::IN, a.sh, L.n_probes * 108), st.add(Staged::IN, a.pr ? a.maps : nullptr, L.n_probes * L.d.texels * 16),
+                       st.add(Staged::IN, a.vis ? a.moments : nullptr, L.n_probes * R * R * 8), st.add(Staged::IN, a.placed ? a.placement : nullptr, L.n_probes * 16)};
+}
+fw::DProbeVis probe_vis_device(const ProbeLookupArgs &a, const float *d_moments) {
+    return fw::DProbeVis{d_moments, a.vis ? (double)a.normal_bias : 0.0, a.vis ? a.pd->resolution : 0u};
 }
 
-// fw_probe_irradiance: with device arrays the kernel works on the caller's memory and nothing is allocated; with host arrays one device
-// allocation per call holds sh and a slab of points (24 B in, 12 B out each), released on every way out.  vis: fw_probe_irradiance_vis —
-// the moments are one more array, staged after sh.
-int probe_irradiance_impl(const fw_probe_grid *grid, const float *sh, int device, uint32_t n, const float *positions, const float *normals,
-                          uint32_t stride, float *irradiance, int on_device, void *stream_, const ProbeVis *vis = nullptr,
-                          const ProbePlaced *pl = nullptr) {
-    if (!grid || !sh || !positions || !normals || !irradiance || (vis && (!vis->pd || !vis->moments)) || (pl && !pl->placement))
-        return fail(FW_ERR_BAD_ARG, "null argument");
-    if (vis) if (int rc = probe_vis_check(vis)) return rc;
-    bool too_large = false;
-    fw::DProbeGrid g{};
-    if (int rc = probe_grid_check(grid, too_large, g)) return rc;
+// fw_probe_irradiance and its _vis and _placed forms: with device arrays the kernel works on the caller's memory and nothing is allocated;
+// with host arrays one device allocation per call holds the tables and a slab of points (24 B in, 12 B out each), released on every way out
+int probe_irradiance_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, int device, uint32_t n, const float *positions, const float *normals,
+                          uint32_t stride, float *irradiance, int on_device, void *stream_) {
+    ProbeLookup L;
+    if (int rc = probe_lookup_check(grid, a, !a.sh || !positions || !normals || !irradiance, false, L)) return rc;
     if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
     if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
     if (device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
-    if (on_device && (((uintptr_t)sh | (uintptr_t)positions | (uintptr_t)normals | (uintptr_t)irradiance | (uintptr_t)(vis ? vis->moments : nullptr) |
-                       (uintptr_t)(pl ? pl->placement : nullptr)) & 3u))
+    if (on_device && (((uintptr_t)a.sh | (uintptr_t)positions | (uintptr_t)normals | (uintptr_t)irradiance | (uintptr_t)(a.vis ? a.moments : nullptr) |
+                       (uintptr_t)(a.placed ? a.placement : nullptr)) & 3u))
         return fail(FW_ERR_BAD_ARG, "device arrays must be 4-byte aligned");
-    if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
-    if (probe_vis_too_large(vis, g)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
+    if (int rc = probe_lookup_sizes(a, L)) return rc;
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const auto launch = [&](const float *d_sh, const float *d_mom, const float *d_pl, uint32_t k, const float *pos, const float *nrm, uint32_t st,
-                            float *out) {
-        if (pl) {
-            const fw::DProbeVis v{d_mom, vis ? (double)vis->normal_bias : 0.0, vis ? vis->pd->resolution : 0u};
-            fw::launch_probe_irradiance_placed(stream, g, vis ? &v : nullptr, d_sh, d_pl, k, pos, nrm, st, out);
-        }
-        else if (vis) fw::launch_probe_irradiance_vis(stream, g, fw::DProbeVis{d_mom, (double)vis->normal_bias, vis->pd->resolution}, d_sh, k, pos, nrm, st, out);
-        else fw::launch_probe_irradiance(stream, g, d_sh, k, pos, nrm, st, out);
-    };
-    if (on_device) {
-        launch(sh, vis ? vis->moments : nullptr, pl ? pl->placement : nullptr, n, positions, normals, stride, irradiance);
-        HIPCHK(hipStreamSynchronize(stream));
-        HIPCHK(hipGetLastError());
-        return FW_OK;
-    }
-    const size_t n_probes = (size_t)g.counts[0] * g.counts[1] * g.counts[2];
-    const size_t sh_bytes = n_probes * 108, mom_bytes = vis ? n_probes * vis->pd->resolution * vis->pd->resolution * 8 : 0;
-    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 36));
-    const size_t pl_bytes = pl ? n_probes * 16 : 0;
-    const size_t o_mom = align256(sh_bytes), o_pl = o_mom + align256(mom_bytes), o_in = o_pl + align256(pl_bytes), o_out = o_in + align256((size_t)per * 24);
-    std::vector<float> pack((size_t)per * 6);
-    CallScratch scratch(device);
-    if (int rc = scratch.alloc(o_out + (size_t)per * 12)) return rc;
-    uint8_t *base = (uint8_t *)scratch.p;
-    const float *d_in = (const float *)(base + o_in);
-    HIPCHK(hipMemcpyAsync(base, sh, sh_bytes, hipMemcpyHostToDevice, stream));
-    if (vis) HIPCHK(hipMemcpyAsync(base + o_mom, vis->moments, mom_bytes, hipMemcpyHostToDevice, stream));
-    if (pl) HIPCHK(hipMemcpyAsync(base + o_pl, pl->placement, pl_bytes, hipMemcpyHostToDevice, stream));
-    for (uint32_t done = 0; done < n; done += per) {
-        const uint32_t k = std::min(per, n - done);
-        for (uint32_t i = 0; i < k; i++) {
-            const float *ps = positions + (size_t)(done + i) * stride, *ns = normals + (size_t)(done + i) * stride;
-            float *o = pack.data() + (size_t)i * 6;
-            o[0] = ps[0]; o[1] = ps[1]; o[2] = ps[2]; o[3] = ns[0]; o[4] = ns[1]; o[5] = ns[2];
-        }
-        HIPCHK(hipMemcpyAsync(base + o_in, pack.data(), (size_t)k * 24, hipMemcpyHostToDevice, stream));
-        launch((const float *)base, (const float *)(base + o_mom), (const float *)(base + o_pl), k, d_in, d_in + 3, 6, (float *)(base + o_out));
-        HIPCHK(hipMemcpyAsync(irradiance + (size_t)done * 3, base + o_out, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-    }
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    Staged st(device, stream, on_device != 0);
+    const ProbeTables t = probe_tables_stage(st, a, L);
+    HostSlabs sl(st, n, 36);
+    const int a_pts = sl.in(positions, 24, stride, normals), a_out = sl.out(irradiance, 12);
+    if (int rc = st.up()) return rc;
+    return sl.run([&](uint32_t, uint32_t k) {
+        const float *d_sh = st.ptr<const float>(t.sh), *pos = sl.ptr<const float>(a_pts), *nrm = sl.with(a_pts);
+        float *out = sl.ptr<float>(a_out);
+        const fw::DProbeVis v = probe_vis_device(a, st.ptr<const float>(t.mom));
+        if (a.placed) fw::launch_probe_irradiance_placed(stream, L.g, a.vis ? &v : nullptr, d_sh, st.ptr<const float>(t.pl), k, pos, nrm, sl.stride(a_pts), out);
+        else if (a.vis) fw::launch_probe_irradiance_vis(stream, L.g, v, d_sh, k, pos, nrm, sl.stride(a_pts), out);
+        else fw::launch_probe_irradiance(stream, L.g, d_sh, k, pos, nrm, sl.stride(a_pts), out);
+    });
 }
 
-// fw_probe_shade: as fw_probe_irradiance; a host call's slab holds 48 B of record and up to 27 B of outputs per pixel.  vis:
-// fw_probe_shade_vis.
-int probe_shade_impl(const fw_probe_grid *grid, const float *sh, const fw_probe_shade_params *p, const float *aov, float *linear_rgb,
-                     float *gamma_rgb, uint8_t *rgb8, const ProbeVis *vis = nullptr, const ProbePlaced *pl = nullptr) {
-    if (!grid || !sh || !p || !aov || (vis && (!vis->pd || !vis->moments)) || (pl && !pl->placement)) return fail(FW_ERR_BAD_ARG, "null argument");
-    if (!linear_rgb && !gamma_rgb && !rgb8) return fail(FW_ERR_BAD_ARG, "at least one output is needed");
-    if (vis) if (int rc = probe_vis_check(vis)) return rc;
-    bool too_large = false;
-    fw::DProbeGrid g{};
-    if (int rc = probe_grid_check(grid, too_large, g)) return rc;
+// fw_probe_shade and its _vis and _placed forms: as fw_probe_irradiance; a host call's slab holds 48 B of record and up to 27 B of outputs
+// per pixel
+int probe_shade_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, const fw_probe_shade_params *p, const float *aov, float *linear_rgb,
+                     float *gamma_rgb, uint8_t *rgb8) {
+    ProbeLookup L;
+    if (int rc = probe_lookup_check(grid, a, !a.sh || !p || !aov, !linear_rgb && !gamma_rgb && !rgb8, L)) return rc;
     if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
     if (!std::isfinite(p->gamma) || !(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
     if (p->device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
-    if (p->on_device && (((uintptr_t)aov & 15u) || (((uintptr_t)sh | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb) & 3u)))
+    if (p->on_device && (((uintptr_t)aov & 15u) || (((uintptr_t)a.sh | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb) & 3u)))
         return fail(FW_ERR_BAD_ARG, "device aov must be 16-byte aligned, device sh, linear_rgb and gamma_rgb 4-byte aligned");
-    if (vis && p->on_device && ((uintptr_t)vis->moments & 3u)) return fail(FW_ERR_BAD_ARG, "device moments must be 4-byte aligned");
-    if (pl && p->on_device && ((uintptr_t)pl->placement & 3u)) return fail(FW_ERR_BAD_ARG, "device placement must be 4-byte aligned");
+    if (a.vis && p->on_device && ((uintptr_t)a.moments & 3u)) return fail(FW_ERR_BAD_ARG, "device moments must be 4-byte aligned");
+    if (a.placed && p->on_device && ((uintptr_t)a.placement & 3u)) return fail(FW_ERR_BAD_ARG, "device placement must be 4-byte aligned");
     const uint64_t full = (uint64_t)p->width * p->height;
-    if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
-    if (probe_vis_too_large(vis, g)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
+    if (int rc = probe_lookup_sizes(a, L)) return rc;
     if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
     const int dev = p->device;
     if (int rc = use_device(dev)) return rc;
     hipStream_t stream = (hipStream_t)p->stream;
-    const uint32_t n = (uint32_t)full;
-    const auto launch = [&](const float *d_sh, const float *d_mom, const float *d_pl, uint32_t k, const float *d_aov, uint8_t *o8, float *og,
-                            float *ol) {
-        if (pl) {
-            const fw::DProbeVis v{d_mom, vis ? (double)vis->normal_bias : 0.0, vis ? vis->pd->resolution : 0u};
-            fw::launch_probe_shade_placed(stream, g, vis ? &v : nullptr, d_sh, d_pl, k, d_aov, p->gamma, o8, og, ol);
-        }
-        else if (vis) fw::launch_probe_shade_vis(stream, g, fw::DProbeVis{d_mom, (double)vis->normal_bias, vis->pd->resolution}, d_sh, k, d_aov, p->gamma, o8, og, ol);
-        else fw::launch_probe_shade(stream, g, d_sh, k, d_aov, p->gamma, o8, og, ol);
-    };
-    if (p->on_device) {
-        launch(sh, vis ? vis->moments : nullptr, pl ? pl->placement : nullptr, n, aov, rgb8, gamma_rgb, linear_rgb);
-        HIPCHK(hipStreamSynchronize(stream));
-        HIPCHK(hipGetLastError());
-        return FW_OK;
-    }
-    const size_t n_probes = (size_t)g.counts[0] * g.counts[1] * g.counts[2];
-    const size_t sh_bytes = n_probes * 108, mom_bytes = vis ? n_probes * vis->pd->resolution * vis->pd->resolution * 8 : 0;
-    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 75));
-    size_t off = 0;
-    auto put = [&](size_t b) { const size_t at = off; off += align256(b); return at; };
-    const size_t pl_bytes = pl ? n_probes * 16 : 0;
-    const size_t o_sh = put(sh_bytes), o_mom = put(mom_bytes), o_pl = put(pl_bytes), o_aov = put((size_t)per * 48);
-    const size_t o_lin = linear_rgb ? put((size_t)per * 12) : 0, o_gam = gamma_rgb ? put((size_t)per * 12) : 0, o_8 = rgb8 ? put((size_t)per * 3) : 0;
-    CallScratch scratch(dev);
-    if (int rc = scratch.alloc(off)) return rc;
-    uint8_t *base = (uint8_t *)scratch.p;
-    HIPCHK(hipMemcpyAsync(base + o_sh, sh, sh_bytes, hipMemcpyHostToDevice, stream));
-    if (vis) HIPCHK(hipMemcpyAsync(base + o_mom, vis->moments, mom_bytes, hipMemcpyHostToDevice, stream));
-    if (pl) HIPCHK(hipMemcpyAsync(base + o_pl, pl->placement, pl_bytes, hipMemcpyHostToDevice, stream));
-    for (uint32_t done = 0; done < n; done += per) {
-        const uint32_t k = std::min(per, n - done);
-        HIPCHK(hipMemcpyAsync(base + o_aov, aov + (size_t)done * 12, (size_t)k * 48, hipMemcpyHostToDevice, stream));
-        launch((const float *)(base + o_sh), (const float *)(base + o_mom), (const float *)(base + o_pl), k, (const float *)(base + o_aov),
-               rgb8 ? base + o_8 : nullptr, gamma_rgb ? (float *)(base + o_gam) : nullptr, linear_rgb ? (float *)(base + o_lin) : nullptr);
-        if (linear_rgb) HIPCHK(hipMemcpyAsync(linear_rgb + (size_t)done * 3, base + o_lin, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
-        if (gamma_rgb) HIPCHK(hipMemcpyAsync(gamma_rgb + (size_t)done * 3, base + o_gam, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
-        if (rgb8) HIPCHK(hipMemcpyAsync(rgb8 + (size_t)done * 3, base + o_8, (size_t)k * 3, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-    }
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    Staged st(dev, stream, p->on_device != 0);
+    const ProbeTables t = probe_tables_stage(st, a, L);
+    HostSlabs sl(st, (uint32_t)full, 75);
+    const int a_aov = sl.in(aov, 48), a_lin = sl.out(linear_rgb, 12), a_gam = sl.out(gamma_rgb, 12), a_8 = sl.out(rgb8, 3);
+    if (int rc = st.up()) return rc;
+    return sl.run([&](uint32_t, uint32_t k) {
+        const float *d_sh = st.ptr<const float>(t.sh), *d_aov = sl.ptr<const float>(a_aov);
+        uint8_t *o8 = sl.ptr<uint8_t>(a_8);
+        float *og = sl.ptr<float>(a_gam), *ol = sl.ptr<float>(a_lin);
+        const fw::DProbeVis v = probe_vis_device(a, st.ptr<const float>(t.mom));
+        if (a.placed) fw::launch_probe_shade_placed(stream, L.g, a.vis ? &v : nullptr, d_sh, st.ptr<const float>(t.pl), k, d_aov, p->gamma, o8, og, ol);
+        else if (a.vis) fw::launch_probe_shade_vis(stream, L.g, v, d_sh, k, d_aov, p->gamma, o8, og, ol);
+        else fw::launch_probe_shade(stream, L.g, d_sh, k, d_aov, p->gamma, o8, og, ol);
+    });
 }
 
-// fw_probe_depth_reduce: fw_probe_project's shape — with host arrays one device allocation per call holds the inputs and the sums,
-// released on every way out; with device arrays the kernel works on the caller's memory and nothing is allocated
+// fw_probe_depth_reduce: fw_probe_project's shape
 int probe_depth_reduce_impl(int device, const fw_probe_depth *pd, uint32_t n_probes, uint32_t directions, const float *rays, const fw_hit *hits,
                             float *sums, int on_device, void *stream_) {
     if (!pd || !rays || !hits || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -4514,28 +4589,19 @@ int probe_depth_reduce_impl(int device, const fw_probe_depth *pd, uint32_t n_pro
     if ((uint64_t)n_probes * R * R >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const size_t n = (size_t)n_probes * directions, sum_bytes = (size_t)n_probes * R * R * 16;
-    CallScratch scratch(device);
-    const float *d_rays = rays; const fw_hit *d_hits = hits; float *d_sums = sums;
-    if (!on_device) {
-        const size_t o_hits = align256(n * 24), o_sums = o_hits + align256(n * sizeof(fw_hit));
-        if (int rc = scratch.alloc(o_sums + sum_bytes)) return rc;
-        uint8_t *base = (uint8_t *)scratch.p;
-        HIPCHK(hipMemcpyAsync(base, rays, n * 24, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_hits, hits, n * sizeof(fw_hit), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
-        d_rays = (const float *)base; d_hits = (const fw_hit *)(base + o_hits); d_sums = (float *)(base + o_sums);
-    }
-    fw::launch_probe_depth(stream, n_probes, directions, R, pd->sharpness_log2, pd->max_distance, d_rays, d_hits, d_sums);
-    if (!on_device) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    const size_t n = (size_t)n_probes * directions;
+    Staged st(device, stream, on_device != 0);
+    const int i_rays = st.add(Staged::IN, rays, n * 24), i_hits = st.add(Staged::IN, hits, n * sizeof(fw_hit)),
+              i_sums = st.add(Staged::INOUT, sums, (size_t)n_probes * R * R * 16);
+    if (int rc = st.up()) return rc;
+    fw::launch_probe_depth(stream, n_probes, directions, R, pd->sharpness_log2, pd->max_distance, st.ptr<const float>(i_rays), st.ptr<const fw_hit>(i_hits),
+                           st.ptr<float>(i_sums));
+    return st.finish();
 }
 
-// fw_bake_probe_depth: its own are the argument checks, the scratch (positions, a chunk's rays and hits, the running sums unless the
-// caller's device memory holds them), k_probe_rays and k_probe_depth around trace_impl's trace of each chunk, and the moments, divided on
-// the host.  The scratch is released on every way out; on an error the stream is drained.
+// fw_bake_probe_depth: its own are the argument checks, the Staged arrays (positions, a chunk's rays and hits, the running sums unless the
+// caller's device memory holds them), k_probe_rays and k_probe_depth as trace_rounds' generator and reducer, and the moments, divided on
+// the host.
 int bake_probe_depth_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe_depth *pd, const fw_trace_params *tp, uint32_t first_round,
                           uint32_t rounds, float *sums, float *moments, fw_stats *stats) {
     if (!sc || !s || !pd || !tp) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -4556,76 +4622,40 @@ int bake_probe_depth_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe_de
     HIPCHK(hipSetDevice(dev));
     hipStream_t stream = (hipStream_t)tp->stream;
     const uint32_t chunk = std::min<uint32_t>(N, s->chunk_probes ? s->chunk_probes : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 72)));
-    const size_t n_tex = (size_t)N * R * R, sum_bytes = n_tex * 16;
-    const bool own_sums = !tp->on_device || !sums;        // the running sums live in the scratch: a host caller's, or nobody's
-    const size_t o_rays = align256((size_t)N * 12), o_hits = o_rays + align256((size_t)chunk * D * 24),
-                 o_sums = o_hits + align256((size_t)chunk * D * sizeof(fw_hit));
-    CallScratch scratch(dev);
-    if (int rc = scratch.alloc(o_sums + (own_sums ? sum_bytes : 0))) return rc;
-    uint8_t *base = (uint8_t *)scratch.p;
-    const float *d_pos = (const float *)base;
-    float *d_rays = (float *)(base + o_rays), *d_sums = own_sums ? (float *)(base + o_sums) : sums;
-    fw_hit *d_hits = (fw_hit *)(base + o_hits);
-    HIPCHK(hipMemcpyAsync(base, s->positions, (size_t)N * 12, hipMemcpyHostToDevice, stream));
-    if (own_sums) {
-        if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
-        else HIPCHK(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
-    }
+    const size_t n_tex = (size_t)N * R * R;
+    Staged st(dev, stream, tp->on_device != 0);
+    const int i_pos = st.add(Staged::IN, s->positions, (size_t)N * 12, true), i_rays = st.add(Staged::WORK, nullptr, (size_t)chunk * D * 24),
+              i_hits = st.add(Staged::WORK, nullptr, (size_t)chunk * D * sizeof(fw_hit)), i_sums = st.add_sums(sums, n_tex * 16);
+    if (int rc = st.up()) return rc;
+    const float *d_pos = st.ptr<const float>(i_pos);
+    float *d_sums = st.ptr<float>(i_sums);
     const int n_cus = device_cus(dev);
     fw_stats total{};
-    CallEvents<4> ev;                                     // around the two kernels' launches
-    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
-    for (uint32_t r = first_round; r - first_round < rounds; r++) {      // (first_round + rounds may be 2^32 - 1: r itself never gets there)
-        fw_trace_params q = *tp;
-        q.on_device = 1; q.seed = tp->seed + r;
-        for (uint32_t p0 = 0; p0 < N; p0 += chunk) {
-            const uint32_t k = std::min(chunk, N - p0);
-            q.key_base = p0 * D;
-            if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
-            fw::launch_probe_rays(stream, n_cus, probes_device(s, r, p0, d_pos + (size_t)p0 * 3), k, d_rays);
-            if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
-            fw_stats ts{};
-            if (int rc = trace_impl(sc, &q, d_rays, k * D, d_hits, stats ? &ts : nullptr)) { (void)hipStreamSynchronize(stream); return rc; }
-            if (stats) HIPCHK(hipEventRecord(ev.e[2], stream));
-            fw::launch_probe_depth(stream, k, D, R, pd->sharpness_log2, pd->max_distance, d_rays, d_hits, d_sums + (size_t)p0 * R * R * 4);
-            if (!stats) continue;
-            HIPCHK(hipEventRecord(ev.e[3], stream));
-            HIPCHK(hipEventSynchronize(ev.e[3]));
-            float gen_ms = 0.f, red_ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
-            HIPCHK(hipEventElapsedTime(&red_ms, ev.e[2], ev.e[3]));
-            stats_add(total, ts);
-            total.ms_render += gen_ms + red_ms;
-            if (tp->flags & FW_FLAG_TIME_KERNELS) { total.ms_raygen += gen_ms; total.ms_accumulate += red_ms; }
-        }
-    }
+    const TraceRounds b{N, D, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
+    if (int rc = trace_rounds(sc, tp, b, first_round, rounds, stats ? &total : nullptr,
+            [&](uint32_t r, uint32_t p0, uint32_t k, float *rays) { fw::launch_probe_rays(stream, n_cus, probes_device(s, r, p0, d_pos + (size_t)p0 * 3), k, rays); },
+            [&](uint32_t p0, uint32_t k, const float *rays, const fw_hit *hits) {
+                fw::launch_probe_depth(stream, k, D, R, pd->sharpness_log2, pd->max_distance, rays, hits, d_sums + (size_t)p0 * R * R * 4);
+            }))
+        return rc;
     // the outputs: sums where the caller keeps them, and the moments, divided on the host in double and rounded once
-    std::vector<float> host;
-    const float *h_sums = sums;
-    if (!tp->on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-    else if (moments) { host.resize(n_tex * 4); h_sums = host.data(); HIPCHK(hipMemcpyAsync(host.data(), d_sums, sum_bytes, hipMemcpyDeviceToHost, stream)); }
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
+    std::vector<float> keep;
+    const float *h_sums = nullptr;
+    if (int rc = st.fetch(i_sums, moments != nullptr, keep, h_sums)) return rc;
+    if (int rc = st.finish()) return rc;
     if (moments) {
-        std::vector<float> tmp;
-        float *out = moments;
-        if (tp->on_device) { tmp.resize(n_tex * 2); out = tmp.data(); }
         const float far1 = pd->max_distance, far2 = (float)((double)pd->max_distance * (double)pd->max_distance);
-        for (size_t i = 0; i < n_tex; i++) {
-            const float *t = h_sums + i * 4;
-            const bool none = t[2] == 0.f;
-            out[2 * i] = none ? far1 : (float)((double)t[0] / (double)t[2]);
-            out[2 * i + 1] = none ? far2 : (float)((double)t[1] / (double)t[2]);
-        }
-        if (tp->on_device) {
-            HIPCHK(hipMemcpyAsync(moments, tmp.data(), n_tex * 8, hipMemcpyHostToDevice, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-        }
+        if (int rc = host_output(stream, moments, n_tex * 2, tp->on_device != 0, [&](float *out) {
+                for (size_t i = 0; i < n_tex; i++) {
+                    const float *t = h_sums + i * 4;
+                    const bool none = t[2] == 0.f;
+                    out[2 * i] = none ? far1 : (float)((double)t[0] / (double)t[2]);
+                    out[2 * i + 1] = none ? far2 : (float)((double)t[1] / (double)t[2]);
+                }
+            }))
+            return rc;
     }
-    if (stats) {
-        *stats = total;
-        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    }
+    stats_finish(stats, total, wall0);
     return FW_OK;
 }
 
@@ -4653,22 +4683,13 @@ int probe_survey_impl(int device, uint32_t n_probes, uint32_t directions, const 
     if ((uint64_t)n_probes * directions >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x directions must be below 2^31");
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const size_t n = (size_t)n_probes * directions, survey_bytes = (size_t)n_probes * 48;
-    CallScratch scratch(device);
-    const float *d_rays = rays; const fw_hit *d_hits = hits; float *d_survey = survey;
-    if (!on_device) {
-        const size_t o_hits = align256(n * 24), o_survey = o_hits + align256(n * sizeof(fw_hit));
-        if (int rc = scratch.alloc(o_survey + survey_bytes)) return rc;
-        uint8_t *base = (uint8_t *)scratch.p;
-        HIPCHK(hipMemcpyAsync(base, rays, n * 24, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_hits, hits, n * sizeof(fw_hit), hipMemcpyHostToDevice, stream));
-        d_rays = (const float *)base; d_hits = (const fw_hit *)(base + o_hits); d_survey = (float *)(base + o_survey);
-    }
-    fw::launch_probe_survey(stream, device_cus(device), n_probes, directions, d_rays, d_hits, d_survey);
-    if (!on_device) HIPCHK(hipMemcpyAsync(survey, d_survey, survey_bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    const size_t n = (size_t)n_probes * directions;
+    Staged st(device, stream, on_device != 0);
+    const int i_rays = st.add(Staged::IN, rays, n * 24), i_hits = st.add(Staged::IN, hits, n * sizeof(fw_hit)),
+              i_survey = st.add(Staged::OUT, survey, (size_t)n_probes * 48);
+    if (int rc = st.up()) return rc;
+    fw::launch_probe_survey(stream, device_cus(device), n_probes, directions, st.ptr<const float>(i_rays), st.ptr<const fw_hit>(i_hits), st.ptr<float>(i_survey));
+    return st.finish();
 }
 
 // fw_probe_relocate_step: the same shape over the survey (read) and the placement (read and written)
@@ -4682,28 +4703,16 @@ int probe_relocate_step_impl(int device, const fw_probe_relocate *rl, uint32_t n
     if (on_device && (((uintptr_t)survey | (uintptr_t)placement) & 15u)) return fail(FW_ERR_BAD_ARG, "device survey and placement must be 16-byte aligned");
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const size_t survey_bytes = (size_t)n_probes * 48, place_bytes = (size_t)n_probes * 16;
-    CallScratch scratch(device);
-    const float *d_survey = survey; float *d_place = placement;
-    if (!on_device) {
-        const size_t o_place = align256(survey_bytes);
-        if (int rc = scratch.alloc(o_place + place_bytes)) return rc;
-        uint8_t *base = (uint8_t *)scratch.p;
-        HIPCHK(hipMemcpyAsync(base, survey, survey_bytes, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_place, placement, place_bytes, hipMemcpyHostToDevice, stream));
-        d_survey = (const float *)base; d_place = (float *)(base + o_place);
-    }
-    fw::launch_probe_relocate_step(stream, L, n_probes, directions, d_survey, d_place, move ? 1 : 0);
-    if (!on_device) HIPCHK(hipMemcpyAsync(placement, d_place, place_bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    Staged st(device, stream, on_device != 0);
+    const int i_survey = st.add(Staged::IN, survey, (size_t)n_probes * 48), i_place = st.add(Staged::INOUT, placement, (size_t)n_probes * 16);
+    if (int rc = st.up()) return rc;
+    fw::launch_probe_relocate_step(stream, L, n_probes, directions, st.ptr<const float>(i_survey), st.ptr<float>(i_place), move ? 1 : 0);
+    return st.finish();
 }
 
-// fw_relocate_probes: bake_probe_depth_impl's loop with the survey and the step in the reduction's place.  Its own are the argument
-// checks, the scratch (the moved positions, a chunk's rays and hits, the survey and the placement), and the moved positions, formed on the
-// host before every step from the placement the step before it copied back.  The scratch is released on every way out; on an error the
-// stream is drained.  (The loop repeats bake_probe_depth_impl's: one trace-round driver for the trace bakes is a follow-up.)
+// fw_relocate_probes: per step one round of the traced bakes' chunks (trace_round) with the survey and the step as the
+// reduction.  Its own are the argument checks, the Staged arrays (the moved positions, a chunk's rays and hits, the survey and the
+// placement), and the moved positions, formed on the host before every step from the placement the step before it copied back.
 int relocate_probes_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe_relocate *rl, const fw_trace_params *tp, uint32_t first_step,
                          uint32_t steps, float *placement, float *survey, fw_stats *stats) {
     if (!sc || !s || !rl || !tp || !placement) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -4725,60 +4734,38 @@ int relocate_probes_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe_rel
     HIPCHK(hipSetDevice(dev));
     hipStream_t stream = (hipStream_t)tp->stream;
     const uint32_t chunk = std::min<uint32_t>(N, s->chunk_probes ? s->chunk_probes : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 72)));
-    const size_t o_rays = align256((size_t)N * 12), o_hits = o_rays + align256((size_t)chunk * D * 24),
-                 o_survey = o_hits + align256((size_t)chunk * D * sizeof(fw_hit)), o_place = o_survey + align256((size_t)N * 48);
-    CallScratch scratch(dev);
-    if (int rc = scratch.alloc(o_place + (size_t)N * 16)) return rc;
-    uint8_t *base = (uint8_t *)scratch.p;
-    const float *d_pos = (const float *)base;
-    float *d_rays = (float *)(base + o_rays), *d_survey = (float *)(base + o_survey), *d_place = (float *)(base + o_place);
-    fw_hit *d_hits = (fw_hit *)(base + o_hits);
-    HIPCHK(hipMemcpyAsync(d_place, placement, (size_t)N * 16, hipMemcpyHostToDevice, stream));
+    Staged st(dev, stream, false);                        // (the placement and the survey are host arrays whatever tp->on_device says)
+    const int i_pos = st.add(Staged::WORK, nullptr, (size_t)N * 12), i_rays = st.add(Staged::WORK, nullptr, (size_t)chunk * D * 24),
+              i_hits = st.add(Staged::WORK, nullptr, (size_t)chunk * D * sizeof(fw_hit)), i_survey = st.add(Staged::WORK, nullptr, (size_t)N * 48),
+              i_place = st.add(Staged::IN, placement, (size_t)N * 16);
+    if (int rc = st.up()) return rc;
+    const float *d_pos = st.ptr<const float>(i_pos);
+    float *d_survey = st.ptr<float>(i_survey), *d_place = st.ptr<float>(i_place);
     const int n_cus = device_cus(dev);
     fw_stats total{};
-    CallEvents<4> ev;                                     // around the kernels' launches
-    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
+    const TraceRounds b{N, D, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
+    BakeChunks c{stream, N, chunk, (tp->flags & FW_FLAG_TIME_KERNELS) != 0, stats ? &total : nullptr};
+    if (int rc = c.begin()) return rc;
     std::vector<float> moved((size_t)N * 3);
     for (uint32_t i = 0; i <= steps; i++) {               // the last one classifies: move = 0
-        const uint32_t st = first_step + i;
         const int move = i < steps ? 1 : 0;
         for (size_t q = 0; q < (size_t)N; q++)
             for (int k = 0; k < 3; k++) moved[q * 3 + k] = (float)((double)s->positions[q * 3 + k] + (double)placement[q * 4 + k]);
-        HIPCHK(hipMemcpyAsync(base, moved.data(), (size_t)N * 12, hipMemcpyHostToDevice, stream));
-        fw_trace_params q = *tp;
-        q.on_device = 1; q.seed = tp->seed + st;
-        for (uint32_t p0 = 0; p0 < N; p0 += chunk) {
-            const uint32_t k = std::min(chunk, N - p0);
-            q.key_base = p0 * D;
-            if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
-            fw::launch_probe_rays(stream, n_cus, probes_device(s, st, p0, d_pos + (size_t)p0 * 3), k, d_rays);
-            if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
-            fw_stats ts{};
-            if (int rc = trace_impl(sc, &q, d_rays, k * D, d_hits, stats ? &ts : nullptr)) { (void)hipStreamSynchronize(stream); return rc; }
-            if (stats) HIPCHK(hipEventRecord(ev.e[2], stream));
-            fw::launch_probe_survey(stream, n_cus, k, D, d_rays, d_hits, d_survey + (size_t)p0 * 12);
-            fw::launch_probe_relocate_step(stream, L, k, D, d_survey + (size_t)p0 * 12, d_place + (size_t)p0 * 4, move);
-            if (!stats) continue;
-            HIPCHK(hipEventRecord(ev.e[3], stream));
-            HIPCHK(hipEventSynchronize(ev.e[3]));
-            float gen_ms = 0.f, red_ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
-            HIPCHK(hipEventElapsedTime(&red_ms, ev.e[2], ev.e[3]));
-            stats_add(total, ts);
-            total.ms_render += gen_ms + red_ms;
-            if (tp->flags & FW_FLAG_TIME_KERNELS) { total.ms_raygen += gen_ms; total.ms_accumulate += red_ms; }
-        }
+        if (int rc = st.put(i_pos, moved.data())) return rc;
+        if (int rc = trace_round(sc, tp, b, c, first_step + i,
+                [&](uint32_t r, uint32_t p0, uint32_t k, float *rays) { fw::launch_probe_rays(stream, n_cus, probes_device(s, r, p0, d_pos + (size_t)p0 * 3), k, rays); },
+                [&](uint32_t p0, uint32_t k, const float *rays, const fw_hit *hits) {
+                    fw::launch_probe_survey(stream, n_cus, k, D, rays, hits, d_survey + (size_t)p0 * 12);
+                    fw::launch_probe_relocate_step(stream, L, k, D, d_survey + (size_t)p0 * 12, d_place + (size_t)p0 * 4, move);
+                }))
+            return rc;
         // the placement comes back after every step: the next one's positions are formed from it
-        HIPCHK(hipMemcpyAsync(placement, d_place, (size_t)N * 16, hipMemcpyDeviceToHost, stream));
+        if (int rc = st.get(i_place, placement)) return rc;
         HIPCHK(hipStreamSynchronize(stream));
     }
-    if (survey) HIPCHK(hipMemcpyAsync(survey, d_survey, (size_t)N * 48, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    if (stats) {
-        *stats = total;
-        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    }
+    if (survey) if (int rc = st.get(i_survey, survey)) return rc;
+    if (int rc = st.finish()) return rc;
+    stats_finish(stats, total, wall0);
     return FW_OK;
 }
 
@@ -4801,21 +4788,15 @@ inline uint64_t ao_extent(uint32_t n, const uint32_t *ids) {
     return (uint64_t)top + 1u;
 }
 
-// Host points staged on the device: positions and normals over `extent` ids, the ids, and `extra` bytes more for the caller (at *extra_at),
-// in one allocation of `scratch`.  The copies are enqueued on `stream`.
-int ao_stage_points(hipStream_t stream, CallScratch &scratch, uint32_t n, const float *positions, const float *normals, uint32_t stride,
-                    const uint32_t *ids, uint64_t extent, size_t extra, fw::DAoPoints &pts, uint8_t *&extra_at) {
+// Surface points as Staged inputs: a host caller's positions and normals over `extent` ids and its ids go to the device, a device caller's
+// are read where they lie
+struct AoSlots { int pos, nrm, ids; };
+AoSlots ao_points_stage(Staged &st, uint32_t n, const float *positions, const float *normals, uint32_t stride, const uint32_t *ids, uint64_t extent) {
     const size_t arr = (size_t)((extent - 1u) * stride + 3u) * 4u;
-    const size_t o_nrm = align256(arr), o_ids = o_nrm + align256(arr), o_extra = o_ids + align256(ids ? (size_t)n * 4u : 0);
-    if (int rc = scratch.alloc(o_extra + extra)) return rc;
-    uint8_t *base = (uint8_t *)scratch.p;
-    HIPCHK(hipMemcpyAsync(base, positions, arr, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(base + o_nrm, normals, arr, hipMemcpyHostToDevice, stream));
-    if (ids) HIPCHK(hipMemcpyAsync(base + o_ids, ids, (size_t)n * 4u, hipMemcpyHostToDevice, stream));
-    pts.positions = (const float *)base; pts.normals = (const float *)(base + o_nrm);
-    pts.ids = ids ? (const uint32_t *)(base + o_ids) : nullptr; pts.stride = stride;
-    extra_at = base + o_extra;
-    return FW_OK;
+    return AoSlots{st.add(Staged::IN, positions, arr), st.add(Staged::IN, normals, arr), st.add(Staged::IN, ids, (size_t)n * 4u)};
+}
+fw::DAoPoints ao_points_device(const Staged &st, const AoSlots &a, uint32_t stride) {
+    return fw::DAoPoints{st.ptr<const float>(a.pos), st.ptr<const float>(a.nrm), st.ptr<const uint32_t>(a.ids), stride};
 }
 
 fw::DAoRays ao_rays_device(const fw_ao *ao, uint32_t round, const fw::DAoPoints &pts, uint32_t first) {
@@ -4842,16 +4823,14 @@ int ao_rays_impl(const fw_ao *ao, int device, uint32_t round, uint32_t n, const 
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     const int n_cus = device_cus(device);
+    Staged st(device, stream, on_device != 0);
+    const AoSlots slots = ao_points_stage(st, n, positions, normals, stride, ids, on_device ? n : ao_extent(n, ids));
+    if (int rc = st.up()) return rc;
+    const fw::DAoPoints pts = ao_points_device(st, slots, stride);
     if (on_device) {
-        fw::launch_ao_rays(stream, n_cus, ao_rays_device(ao, round, fw::DAoPoints{positions, normals, ids, stride}, 0), n, rays);
-        HIPCHK(hipStreamSynchronize(stream));
-        HIPCHK(hipGetLastError());
-        return FW_OK;
+        fw::launch_ao_rays(stream, n_cus, ao_rays_device(ao, round, pts, 0), n, rays);
+        return st.finish();
     }
-    CallScratch scratch(device);
-    fw::DAoPoints pts{};
-    uint8_t *extra = nullptr;
-    if (int rc = ao_stage_points(stream, scratch, n, positions, normals, stride, ids, ao_extent(n, ids), 0, pts, extra)) { (void)hipStreamSynchronize(stream); return rc; }
     return host_slabs(stream, device, n, (size_t)ao->directions * 24, rays, [&](uint32_t done, uint32_t k, float *d_rays) {
         fw::launch_ao_rays(stream, n_cus, ao_rays_device(ao, round, pts, done), k, d_rays);
     });
@@ -4870,34 +4849,18 @@ int ao_reduce_impl(int device, const fw_ao *ao, uint32_t n, const uint32_t *ids,
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     const size_t entries = (size_t)n * D;
-    CallScratch scratch(device);
-    const float *d_rays = rays; const fw_hit *d_hits = hits; float *d_sums = sums; const uint32_t *d_ids = ids;
-    size_t sum_bytes = 0;
-    if (!on_device) {
-        sum_bytes = (size_t)ao_extent(n, ids) * 16;
-        const size_t o_hits = align256(entries * 24), o_sums = o_hits + align256(entries * sizeof(fw_hit)), o_ids = o_sums + align256(sum_bytes);
-        if (int rc = scratch.alloc(o_ids + (ids ? (size_t)n * 4 : 0))) return rc;
-        uint8_t *base = (uint8_t *)scratch.p;
-        HIPCHK(hipMemcpyAsync(base, rays, entries * 24, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_hits, hits, entries * sizeof(fw_hit), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
-        if (ids) HIPCHK(hipMemcpyAsync(base + o_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, stream));
-        d_rays = (const float *)base; d_hits = (const fw_hit *)(base + o_hits); d_sums = (float *)(base + o_sums);
-        d_ids = ids ? (const uint32_t *)(base + o_ids) : nullptr;
-    }
-    fw::launch_ao_reduce(stream, device_cus(device), 0, n, D, ao->falloff, ao->radius, d_ids, d_rays, d_hits, d_sums);
-    if (!on_device) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    Staged st(device, stream, on_device != 0);
+    const int i_rays = st.add(Staged::IN, rays, entries * 24), i_hits = st.add(Staged::IN, hits, entries * sizeof(fw_hit)),
+              i_sums = st.add(Staged::INOUT, sums, on_device ? 0 : (size_t)ao_extent(n, ids) * 16), i_ids = st.add(Staged::IN, ids, (size_t)n * 4);
+    if (int rc = st.up()) return rc;
+    fw::launch_ao_reduce(stream, device_cus(device), 0, n, D, ao->falloff, ao->radius, st.ptr<const uint32_t>(i_ids), st.ptr<const float>(i_rays),
+                         st.ptr<const fw_hit>(i_hits), st.ptr<float>(i_sums));
+    return st.finish();
 }
 
-// fw_bake_ao: bake_probe_depth_impl's loop over surface points.  Its own are the argument checks, the scratch (a host caller's points, a
-// chunk's rays and hits, the running sums and the output unless the caller's device memory holds them), k_ao_rays and k_ao_reduce around
-// trace_impl's trace of each chunk, and k_ao_resolve.  The scratch is released on every way out; on an error the stream is drained.
-// (The loop repeats bake_probe_depth_impl's: one trace-round driver for both is a follow-up.)
-// Drains a stream on every way out of a call but the one that disarms it; declared after the scratch, so it runs before the release.
-struct StreamDrain { hipStream_t s; bool armed = true; ~StreamDrain() { if (armed) (void)hipStreamSynchronize(s); } };
+// fw_bake_ao: its own are the argument checks, the Staged arrays (a host caller's points, a chunk's rays and hits, the running sums and
+// the output unless the caller's device memory holds them), k_ao_rays and k_ao_reduce as trace_rounds' generator and reducer, and
+// k_ao_resolve.
 int bake_ao_impl(fw_scene *sc, const fw_ao *ao, const fw_trace_params *tp, uint32_t N, const float *positions, const float *normals, uint32_t stride,
                  const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
     if (!sc || !ao || !tp || !positions || !normals) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -4918,11 +4881,9 @@ int bake_ao_impl(fw_scene *sc, const fw_ao *ao, const fw_trace_params *tp, uint3
     hipStream_t stream = (hipStream_t)tp->stream;
     const bool on_device = tp->on_device != 0;
     const uint32_t chunk = std::min<uint32_t>(N, ao->chunk_points ? ao->chunk_points : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 72)));
-    const bool own_sums = !on_device || !sums;            // the running sums live in the scratch: a host caller's, or nobody's
-    const bool own_out = out && !on_device;
-    // how many records sums and out span: only scratch copies of them need it
+    // how many records sums and out span: only scratch copies of them need it (a host caller's, or the sums nobody keeps)
     uint64_t extent = N;
-    if (ids && (own_sums || own_out)) {
+    if (ids && (!on_device || !sums)) {
         if (on_device) {
             std::vector<uint32_t> h_ids(N);
             HIPCHK(hipMemcpyAsync(h_ids.data(), ids, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
@@ -4931,63 +4892,26 @@ int bake_ao_impl(fw_scene *sc, const fw_ao *ao, const fw_trace_params *tp, uint3
         } else extent = ao_extent(N, ids);
     }
     const size_t rec_bytes = (size_t)extent * 16;
-    const size_t o_hits = align256((size_t)chunk * D * 24), o_sums = o_hits + align256((size_t)chunk * D * sizeof(fw_hit)),
-                 o_out = o_sums + align256(own_sums ? rec_bytes : 0), work = o_out + (own_out ? rec_bytes : 0);
-    CallScratch scratch(dev);
-    StreamDrain drain{stream};
-    fw::DAoPoints pts{positions, normals, ids, stride};
-    uint8_t *base = nullptr;
-    if (on_device) {
-        if (int rc = scratch.alloc(work)) return rc;
-        base = (uint8_t *)scratch.p;
-    } else if (int rc = ao_stage_points(stream, scratch, N, positions, normals, stride, ids, extent, work, pts, base)) return rc;
-    float *d_rays = (float *)base, *d_sums = own_sums ? (float *)(base + o_sums) : sums, *d_out = own_out ? (float *)(base + o_out) : out;
-    fw_hit *d_hits = (fw_hit *)(base + o_hits);
-    if (own_sums) {
-        if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, rec_bytes, hipMemcpyHostToDevice, stream));
-        else HIPCHK(hipMemsetAsync(d_sums, 0, rec_bytes, stream));
-    }
-    if (own_out && ids) HIPCHK(hipMemcpyAsync(d_out, out, rec_bytes, hipMemcpyHostToDevice, stream));      // entries outside the list stay
+    Staged st(dev, stream, on_device);
+    const AoSlots slots = ao_points_stage(st, N, positions, normals, stride, ids, extent);
+    const int i_rays = st.add(Staged::WORK, nullptr, (size_t)chunk * D * 24), i_hits = st.add(Staged::WORK, nullptr, (size_t)chunk * D * sizeof(fw_hit)),
+              i_sums = st.add_sums(sums, rec_bytes), i_out = st.add(ids ? Staged::INOUT : Staged::OUT, out, rec_bytes);      // (with ids, entries outside the list stay)
+    if (int rc = st.up()) return rc;
+    const fw::DAoPoints pts = ao_points_device(st, slots, stride);
+    float *d_sums = st.ptr<float>(i_sums);
     const int n_cus = device_cus(dev);
     fw_stats total{};
-    CallEvents<4> ev;                                     // around the two kernels' launches
-    if (stats) for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e));
-    for (uint32_t r = first_round; r - first_round < rounds; r++) {      // (first_round + rounds may be 2^32 - 1: r itself never gets there)
-        fw_trace_params q = *tp;
-        q.on_device = 1; q.seed = tp->seed + r;
-        for (uint32_t q0 = 0; q0 < N; q0 += chunk) {
-            const uint32_t k = std::min(chunk, N - q0);
-            q.key_base = q0 * D;
-            if (stats) HIPCHK(hipEventRecord(ev.e[0], stream));
-            fw::launch_ao_rays(stream, n_cus, ao_rays_device(ao, r, pts, q0), k, d_rays);
-            if (stats) HIPCHK(hipEventRecord(ev.e[1], stream));
-            fw_stats ts{};
-            if (int rc = trace_impl(sc, &q, d_rays, k * D, d_hits, stats ? &ts : nullptr)) return rc;
-            if (stats) HIPCHK(hipEventRecord(ev.e[2], stream));
-            fw::launch_ao_reduce(stream, n_cus, q0, k, D, ao->falloff, ao->radius, pts.ids, d_rays, d_hits, d_sums);
-            if (!stats) continue;
-            HIPCHK(hipEventRecord(ev.e[3], stream));
-            HIPCHK(hipEventSynchronize(ev.e[3]));
-            float gen_ms = 0.f, red_ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&gen_ms, ev.e[0], ev.e[1]));
-            HIPCHK(hipEventElapsedTime(&red_ms, ev.e[2], ev.e[3]));
-            stats_add(total, ts);
-            total.ms_render += gen_ms + red_ms;
-            if (tp->flags & FW_FLAG_TIME_KERNELS) { total.ms_raygen += gen_ms; total.ms_accumulate += red_ms; }
-        }
-    }
-    if (!on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, rec_bytes, hipMemcpyDeviceToHost, stream));
-    if (out) {
-        fw::launch_ao_resolve(stream, N, (double)((uint64_t)first_round + rounds), pts.ids, d_sums, d_out);
-        if (own_out) HIPCHK(hipMemcpyAsync(out, d_out, rec_bytes, hipMemcpyDeviceToHost, stream));
-    }
-    HIPCHK(hipStreamSynchronize(stream));
-    drain.armed = false;
-    HIPCHK(hipGetLastError());
-    if (stats) {
-        *stats = total;
-        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    }
+    const TraceRounds b{N, D, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
+    if (int rc = trace_rounds(sc, tp, b, first_round, rounds, stats ? &total : nullptr,
+            [&](uint32_t r, uint32_t q0, uint32_t k, float *rays) { fw::launch_ao_rays(stream, n_cus, ao_rays_device(ao, r, pts, q0), k, rays); },
+            [&](uint32_t q0, uint32_t k, const float *rays, const fw_hit *hits) {
+                fw::launch_ao_reduce(stream, n_cus, q0, k, D, ao->falloff, ao->radius, pts.ids, rays, hits, d_sums);
+            }))
+        return rc;
+    if (int rc = st.download(i_sums)) return rc;
+    if (out) fw::launch_ao_resolve(stream, N, (double)((uint64_t)first_round + rounds), pts.ids, d_sums, st.ptr<float>(i_out));
+    if (int rc = st.finish()) return rc;
+    stats_finish(stats, total, wall0);
     return FW_OK;
 }
 
@@ -5026,23 +4950,13 @@ int probe_radiance_reduce_impl(int device, const fw_probe_radiance *pr, uint32_t
     if ((uint64_t)n_probes * R * R >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const size_t n = (size_t)n_probes * directions, sum_bytes = (size_t)n_probes * R * R * 16;
-    CallScratch scratch(device);
-    const float *d_rays = rays, *d_acc = accum; float *d_sums = sums;
-    if (!on_device) {
-        const size_t o_acc = align256(n * 24), o_sums = o_acc + align256(n * 16);
-        if (int rc = scratch.alloc(o_sums + sum_bytes)) return rc;
-        uint8_t *base = (uint8_t *)scratch.p;
-        HIPCHK(hipMemcpyAsync(base, rays, n * 24, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_acc, accum, n * 16, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
-        d_rays = (const float *)base; d_acc = (const float *)(base + o_acc); d_sums = (float *)(base + o_sums);
-    }
-    fw::launch_probe_radiance_reduce(stream, n_probes, directions, d, samples, d_rays, d_acc, d_sums);
-    if (!on_device) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    const size_t n = (size_t)n_probes * directions;
+    Staged st(device, stream, on_device != 0);
+    const int i_rays = st.add(Staged::IN, rays, n * 24), i_acc = st.add(Staged::IN, accum, n * 16),
+              i_sums = st.add(Staged::INOUT, sums, (size_t)n_probes * R * R * 16);
+    if (int rc = st.up()) return rc;
+    fw::launch_probe_radiance_reduce(stream, n_probes, directions, d, samples, st.ptr<const float>(i_rays), st.ptr<const float>(i_acc), st.ptr<float>(i_sums));
+    return st.finish();
 }
 
 // fw_probe_radiance_prefilter: the maps are overwritten, so a host caller's are not uploaded
@@ -5056,26 +4970,17 @@ int probe_radiance_prefilter_impl(int device, const fw_probe_radiance *pr, uint3
     if ((uint64_t)n_probes * d.texels >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x texels must be below 2^31");
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const size_t sum_bytes = (size_t)n_probes * d.R * d.R * 16, map_bytes = (size_t)n_probes * d.texels * 16;
-    CallScratch scratch(device);
-    const float *d_sums = sums; float *d_maps = maps;
-    if (!on_device) {
-        const size_t o_maps = align256(sum_bytes);
-        if (int rc = scratch.alloc(o_maps + map_bytes)) return rc;
-        uint8_t *base = (uint8_t *)scratch.p;
-        HIPCHK(hipMemcpyAsync(base, sums, sum_bytes, hipMemcpyHostToDevice, stream));
-        d_sums = (const float *)base; d_maps = (float *)(base + o_maps);
-    }
-    fw::launch_probe_radiance_prefilter(stream, device_cus(device), n_probes, d, d_sums, d_maps);
-    if (!on_device) HIPCHK(hipMemcpyAsync(maps, d_maps, map_bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    Staged st(device, stream, on_device != 0);
+    const int i_sums = st.add(Staged::IN, sums, (size_t)n_probes * d.R * d.R * 16), i_maps = st.add(Staged::OUT, maps, (size_t)n_probes * d.texels * 16);
+    if (int rc = st.up()) return rc;
+    fw::launch_probe_radiance_prefilter(stream, device_cus(device), n_probes, d, st.ptr<const float>(i_sums), st.ptr<float>(i_maps));
+    return st.finish();
 }
 
 // fw_bake_probe_radiance: bake_probes_impl with k_probe_radiance_reduce as bake_rounds' reducer — and, with sh_sums or sh, k_probe_project
-// beside it on the same rendered accum — and one prefilter of the final sums.  Its own are the argument checks, the scratch (positions, a
-// chunk's rays and accum, and whichever running sums and maps the caller's device memory does not hold) and sh, divided on the host.
+// beside it on the same rendered accum — and one prefilter of the final sums.  Its own are the argument checks, the Staged arrays
+// (positions, a chunk's rays and accum, and whichever running sums and maps the caller's device memory does not hold) and sh, divided on
+// the host.
 int bake_probe_radiance_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe_radiance *pr, const fw_render_rays_params *rp, uint32_t first_round,
                              uint32_t rounds, float *sums, float *maps, float *sh_sums, float *sh, fw_stats *stats) {
     if (!sc || !s || !pr || !rp) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -5100,32 +5005,18 @@ int bake_probe_radiance_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe
     HIPCHK(hipSetDevice(dev));
     hipStream_t stream = (hipStream_t)rp->stream;
     const uint32_t chunk = std::min<uint32_t>(N, s->chunk_probes ? s->chunk_probes : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * 40)));
-    const size_t sum_bytes = (size_t)N * R * R * 16, map_bytes = (size_t)N * d.texels * 16, sh_bytes = (size_t)N * 108;
-    const bool own_sums = !rp->on_device || !sums, own_sh = with_sh && (!rp->on_device || !sh_sums), own_maps = maps && !rp->on_device;
-    size_t off = 0;
-    auto put = [&](size_t b) { const size_t at = off; off += align256(b); return at; };
-    const size_t o_pos = put((size_t)N * 12), o_rays = put((size_t)chunk * D * 24), o_acc = put((size_t)chunk * D * 16);
-    const size_t o_sums = put(own_sums ? sum_bytes : 0), o_sh = put(own_sh ? sh_bytes : 0), o_maps = put(own_maps ? map_bytes : 0);
-    CallScratch scratch(dev);
-    if (int rc = scratch.alloc(off)) return rc;
-    uint8_t *base = (uint8_t *)scratch.p;
-    const float *d_pos = (const float *)(base + o_pos);
-    float *d_rays = (float *)(base + o_rays), *d_acc = (float *)(base + o_acc);
-    float *d_sums = own_sums ? (float *)(base + o_sums) : sums, *d_sh = own_sh ? (float *)(base + o_sh) : sh_sums;
-    float *d_maps = own_maps ? (float *)(base + o_maps) : maps;
-    HIPCHK(hipMemcpyAsync(base + o_pos, s->positions, (size_t)N * 12, hipMemcpyHostToDevice, stream));
-    if (own_sums) {
-        if (sums) HIPCHK(hipMemcpyAsync(d_sums, sums, sum_bytes, hipMemcpyHostToDevice, stream));
-        else HIPCHK(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
-    }
-    if (own_sh) {
-        if (sh_sums) HIPCHK(hipMemcpyAsync(d_sh, sh_sums, sh_bytes, hipMemcpyHostToDevice, stream));
-        else HIPCHK(hipMemsetAsync(d_sh, 0, sh_bytes, stream));
-    }
+    Staged st(dev, stream, rp->on_device != 0);
+    const int i_pos = st.add(Staged::IN, s->positions, (size_t)N * 12, true), i_rays = st.add(Staged::WORK, nullptr, (size_t)chunk * D * 24),
+              i_acc = st.add(Staged::WORK, nullptr, (size_t)chunk * D * 16), i_sums = st.add_sums(sums, (size_t)N * R * R * 16),
+              i_sh = with_sh ? st.add_sums(sh_sums, (size_t)N * 108) : st.add(Staged::IN, nullptr, 0),
+              i_maps = st.add(Staged::OUT, maps, (size_t)N * d.texels * 16);
+    if (int rc = st.up()) return rc;
+    const float *d_pos = st.ptr<const float>(i_pos);
+    float *d_sums = st.ptr<float>(i_sums), *d_sh = st.ptr<float>(i_sh);
     const int n_cus = device_cus(dev);
     fw_stats total{};
     // (the reducers' loads and their sums: 40 B per ray and 32 B per texel; the projection's 40 B per ray and 216 B per probe)
-    const BakeRounds b{first_round, rounds, N, D, chunk, d_rays, d_acc, 0, with_sh ? 80u : 40u, R * R * 32u + (with_sh ? 216u : 0u)};
+    const BakeRounds b{first_round, rounds, N, D, chunk, st.ptr<float>(i_rays), st.ptr<float>(i_acc), 0, with_sh ? 80u : 40u, R * R * 32u + (with_sh ? 216u : 0u)};
     if (int rc = bake_rounds(sc, rp, b, stats ? &total : nullptr,
             [&](uint32_t r, uint32_t p0, uint32_t k, float *rays) { fw::launch_probe_rays(stream, n_cus, probes_device(s, r, p0, d_pos + (size_t)p0 * 3), k, rays); },
             [&](uint32_t p0, uint32_t k, const float *rays, const float *acc) {
@@ -5136,7 +5027,7 @@ int bake_probe_radiance_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe
     if (maps) {
         CallEvents<2> ev;                                 // around the prefilter: its time joins the reducers'
         if (stats) { for (hipEvent_t &e : ev.e) HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(ev.e[0], stream)); }
-        fw::launch_probe_radiance_prefilter(stream, n_cus, N, d, d_sums, d_maps);
+        fw::launch_probe_radiance_prefilter(stream, n_cus, N, d, d_sums, st.ptr<float>(i_maps));
         if (stats) {
             HIPCHK(hipEventRecord(ev.e[1], stream));
             HIPCHK(hipEventSynchronize(ev.e[1]));
@@ -5147,191 +5038,77 @@ int bake_probe_radiance_impl(fw_scene *sc, const fw_probe_set *s, const fw_probe
             total.bytes_accumulate += (uint64_t)N * ((uint64_t)R * R + d.texels) * 16;
         }
     }
-    // the outputs: sums, sh_sums and maps where the caller keeps them, and sh = sh_sums / rounds so far, divided on the host in double
-    std::vector<float> host;
-    const float *h_sh = sh_sums;
-    if (!rp->on_device && sums) HIPCHK(hipMemcpyAsync(sums, d_sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-    if (own_maps) HIPCHK(hipMemcpyAsync(maps, d_maps, map_bytes, hipMemcpyDeviceToHost, stream));
-    if (!rp->on_device && sh_sums) HIPCHK(hipMemcpyAsync(sh_sums, d_sh, sh_bytes, hipMemcpyDeviceToHost, stream));
-    else if (sh) { host.resize((size_t)N * 27); h_sh = host.data(); HIPCHK(hipMemcpyAsync(host.data(), d_sh, sh_bytes, hipMemcpyDeviceToHost, stream)); }
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
-    if (sh) {
-        const double n_rounds = (double)((uint64_t)first_round + rounds);
-        std::vector<float> tmp;
-        float *out = sh;
-        if (rp->on_device) { tmp.resize((size_t)N * 27); out = tmp.data(); }
-        for (size_t i = 0; i < (size_t)N * 27; i++) out[i] = (float)((double)h_sh[i] / n_rounds);
-        if (rp->on_device) {
-            HIPCHK(hipMemcpyAsync(sh, tmp.data(), sh_bytes, hipMemcpyHostToDevice, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-        }
-    }
-    if (stats) {
-        *stats = total;
-        stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    }
+    // the outputs: sums, maps and sh_sums where the caller keeps them, and sh = sh_sums / rounds so far
+    std::vector<float> keep;
+    const float *h_sh = nullptr;
+    if (int rc = st.download(i_sums)) return rc;
+    if (int rc = st.download(i_maps)) return rc;
+    if (with_sh) if (int rc = st.fetch(i_sh, sh != nullptr, keep, h_sh)) return rc;
+    if (int rc = st.finish()) return rc;
+    if (sh) if (int rc = sh_from_sums(stream, h_sh, (size_t)N * 27, first_round, rounds, sh, rp->on_device != 0)) return rc;
+    stats_finish(stats, total, wall0);
     return FW_OK;
 }
 
-// What fw_probe_radiance_lookup and fw_probe_shade_glossy share beside the grid: the maps, and the optional visibility and placement
-struct ProbeRadianceArgs {
-    const fw_probe_radiance *pr; const float *maps;
-    const fw_probe_depth *pd; const float *moments; float normal_bias;
-    const float *placement;
-};
-
-// fw_probe_radiance_lookup: probe_irradiance_impl's shape over the placed lookup's arguments; a host call's slab holds 40 B in and 12 B
-// out per point
-int probe_radiance_lookup_impl(const fw_probe_grid *grid, const ProbeRadianceArgs &a, int device, uint32_t n, const float *positions,
+// fw_probe_radiance_lookup: probe_irradiance_impl's shape; a host call's slab holds 40 B in and 12 B out per point
+int probe_radiance_lookup_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, int device, uint32_t n, const float *positions,
                                const float *normals, uint32_t stride, const float *dirs, const float *roughness, float *radiance, int on_device,
                                void *stream_) {
-    const bool with_vis = a.pd || a.moments;
-    if (!grid || !a.pr || !a.maps || !positions || !normals || !dirs || !roughness || !radiance || (with_vis && (!a.pd || !a.moments)))
-        return fail(FW_ERR_BAD_ARG, "null argument");
-    fw::DProbeRadiance d{};
-    if (int rc = probe_radiance_check(a.pr, d)) return rc;
-    const ProbeVis vis{a.pd, a.moments, a.normal_bias};
-    if (with_vis) if (int rc = probe_vis_check(&vis)) return rc;
-    bool too_large = false;
-    fw::DProbeGrid g{};
-    if (int rc = probe_grid_check(grid, too_large, g)) return rc;
+    ProbeLookup L;
+    if (int rc = probe_lookup_check(grid, a, !a.pr || !a.maps || !positions || !normals || !dirs || !roughness || !radiance, false, L)) return rc;
     if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
     if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
     if (device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
     if (on_device && ((((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)dirs | (uintptr_t)roughness | (uintptr_t)radiance | (uintptr_t)a.moments |
                         (uintptr_t)a.placement) & 3u) || ((uintptr_t)a.maps & 15u)))
         return fail(FW_ERR_BAD_ARG, "device maps must be 16-byte aligned, the other device arrays 4-byte aligned");
-    if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
-    if (probe_vis_too_large(with_vis ? &vis : nullptr, g)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
-    const size_t n_probes = (size_t)g.counts[0] * g.counts[1] * g.counts[2];
-    if ((uint64_t)n_probes * d.texels >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x texels must be below 2^31");
+    if (int rc = probe_lookup_sizes(a, L)) return rc;
     if (int rc = use_device(device)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const auto launch = [&](const float *d_maps, const float *d_mom, const float *d_pl, uint32_t k, const float *pos, const float *nrm, uint32_t st,
-                            const float *dir, const float *rough, float *out) {
-        const fw::DProbeVis v{d_mom, with_vis ? (double)a.normal_bias : 0.0, with_vis ? a.pd->resolution : 0u};
-        fw::launch_probe_radiance_lookup(stream, g, with_vis ? &v : nullptr, d, d_maps, d_pl, k, pos, nrm, st, dir, rough, out);
-    };
-    if (on_device) {
-        launch(a.maps, a.moments, a.placement, n, positions, normals, stride, dirs, roughness, radiance);
-        HIPCHK(hipStreamSynchronize(stream));
-        HIPCHK(hipGetLastError());
-        return FW_OK;
-    }
-    const size_t map_bytes = n_probes * d.texels * 16, mom_bytes = with_vis ? n_probes * a.pd->resolution * a.pd->resolution * 8 : 0;
-    const size_t pl_bytes = a.placement ? n_probes * 16 : 0;
-    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 52));
-    size_t off = 0;
-    auto put = [&](size_t b) { const size_t at = off; off += align256(b); return at; };
-    const size_t o_maps = put(map_bytes), o_mom = put(mom_bytes), o_pl = put(pl_bytes), o_in = put((size_t)per * 24), o_dir = put((size_t)per * 12),
-                 o_rough = put((size_t)per * 4), o_out = put((size_t)per * 12);
-    std::vector<float> pack((size_t)per * 6);
-    CallScratch scratch(device);
-    if (int rc = scratch.alloc(off)) return rc;
-    uint8_t *base = (uint8_t *)scratch.p;
-    const float *d_in = (const float *)(base + o_in);
-    HIPCHK(hipMemcpyAsync(base + o_maps, a.maps, map_bytes, hipMemcpyHostToDevice, stream));
-    if (with_vis) HIPCHK(hipMemcpyAsync(base + o_mom, a.moments, mom_bytes, hipMemcpyHostToDevice, stream));
-    if (a.placement) HIPCHK(hipMemcpyAsync(base + o_pl, a.placement, pl_bytes, hipMemcpyHostToDevice, stream));
-    for (uint32_t done = 0; done < n; done += per) {
-        const uint32_t k = std::min(per, n - done);
-        for (uint32_t i = 0; i < k; i++) {
-            const float *ps = positions + (size_t)(done + i) * stride, *ns = normals + (size_t)(done + i) * stride;
-            float *o = pack.data() + (size_t)i * 6;
-            o[0] = ps[0]; o[1] = ps[1]; o[2] = ps[2]; o[3] = ns[0]; o[4] = ns[1]; o[5] = ns[2];
-        }
-        HIPCHK(hipMemcpyAsync(base + o_in, pack.data(), (size_t)k * 24, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_dir, dirs + (size_t)done * 3, (size_t)k * 12, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_rough, roughness + done, (size_t)k * 4, hipMemcpyHostToDevice, stream));
-        launch((const float *)(base + o_maps), (const float *)(base + o_mom), a.placement ? (const float *)(base + o_pl) : nullptr, k, d_in, d_in + 3, 6,
-               (const float *)(base + o_dir), (const float *)(base + o_rough), (float *)(base + o_out));
-        HIPCHK(hipMemcpyAsync(radiance + (size_t)done * 3, base + o_out, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-    }
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    Staged st(device, stream, on_device != 0);
+    const ProbeTables t = probe_tables_stage(st, a, L);
+    HostSlabs sl(st, n, 52);
+    const int a_pts = sl.in(positions, 24, stride, normals), a_dir = sl.in(dirs, 12), a_rough = sl.in(roughness, 4), a_out = sl.out(radiance, 12);
+    if (int rc = st.up()) return rc;
+    return sl.run([&](uint32_t, uint32_t k) {
+        const fw::DProbeVis v = probe_vis_device(a, st.ptr<const float>(t.mom));
+        fw::launch_probe_radiance_lookup(stream, L.g, a.vis ? &v : nullptr, L.d, st.ptr<const float>(t.maps), st.ptr<const float>(t.pl), k,
+                                         sl.ptr<const float>(a_pts), sl.with(a_pts), sl.stride(a_pts), sl.ptr<const float>(a_dir), sl.ptr<const float>(a_rough),
+                                         sl.ptr<float>(a_out));
+    });
 }
 
 // fw_probe_shade_glossy: probe_shade_impl's shape; a host call's slab holds 48 B of record, 16 B of spec, 12 B of view and up to 27 B of
 // outputs per pixel
-int probe_shade_glossy_impl(const fw_probe_grid *grid, const float *sh, const ProbeRadianceArgs &a, const fw_probe_shade_params *p, const float *aov,
-                            const float *spec, const float *view, uint32_t view_stride, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
-    const bool with_vis = a.pd || a.moments;
-    if (!grid || !sh || !a.pr || !a.maps || !p || !aov || !spec || !view || (with_vis && (!a.pd || !a.moments))) return fail(FW_ERR_BAD_ARG, "null argument");
-    if (!linear_rgb && !gamma_rgb && !rgb8) return fail(FW_ERR_BAD_ARG, "at least one output is needed");
-    fw::DProbeRadiance d{};
-    if (int rc = probe_radiance_check(a.pr, d)) return rc;
-    const ProbeVis vis{a.pd, a.moments, a.normal_bias};
-    if (with_vis) if (int rc = probe_vis_check(&vis)) return rc;
-    bool too_large = false;
-    fw::DProbeGrid g{};
-    if (int rc = probe_grid_check(grid, too_large, g)) return rc;
+int probe_shade_glossy_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, const fw_probe_shade_params *p, const float *aov, const float *spec,
+                            const float *view, uint32_t view_stride, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
+    ProbeLookup L;
+    if (int rc = probe_lookup_check(grid, a, !a.sh || !a.pr || !a.maps || !p || !aov || !spec || !view, !linear_rgb && !gamma_rgb && !rgb8, L)) return rc;
     if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
     if (!std::isfinite(p->gamma) || !(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
     if (view_stride < 3) return fail(FW_ERR_BAD_ARG, "view_stride_floats must be >= 3");
     if (p->device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
     if (p->on_device && ((((uintptr_t)aov | (uintptr_t)spec | (uintptr_t)a.maps) & 15u) ||
-                         (((uintptr_t)sh | (uintptr_t)view | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb | (uintptr_t)a.moments | (uintptr_t)a.placement) & 3u)))
+                         (((uintptr_t)a.sh | (uintptr_t)view | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb | (uintptr_t)a.moments | (uintptr_t)a.placement) & 3u)))
         return fail(FW_ERR_BAD_ARG, "device aov, spec and maps must be 16-byte aligned, the other device arrays 4-byte aligned");
     const uint64_t full = (uint64_t)p->width * p->height;
-    if (too_large) return fail(FW_ERR_UNSUPPORTED, "nx x ny x nz must be below 2^31");
-    if (probe_vis_too_large(with_vis ? &vis : nullptr, g)) return fail(FW_ERR_UNSUPPORTED, "n_probes x resolution^2 must be below 2^31");
-    const size_t n_probes = (size_t)g.counts[0] * g.counts[1] * g.counts[2];
-    if ((uint64_t)n_probes * d.texels >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n_probes x texels must be below 2^31");
+    if (int rc = probe_lookup_sizes(a, L)) return rc;
     if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
     const int dev = p->device;
     if (int rc = use_device(dev)) return rc;
     hipStream_t stream = (hipStream_t)p->stream;
-    const uint32_t n = (uint32_t)full;
-    const auto launch = [&](const float *d_sh, const float *d_maps, const float *d_mom, const float *d_pl, uint32_t k, const float *d_aov,
-                            const float *d_spec, const float *d_view, uint32_t st, uint8_t *o8, float *og, float *ol) {
-        const fw::DProbeVis v{d_mom, with_vis ? (double)a.normal_bias : 0.0, with_vis ? a.pd->resolution : 0u};
-        fw::launch_probe_shade_glossy(stream, g, with_vis ? &v : nullptr, d, d_sh, d_maps, d_pl, k, d_aov, d_spec, d_view, st, p->gamma, o8, og, ol);
-    };
-    if (p->on_device) {
-        launch(sh, a.maps, a.moments, a.placement, n, aov, spec, view, view_stride, rgb8, gamma_rgb, linear_rgb);
-        HIPCHK(hipStreamSynchronize(stream));
-        HIPCHK(hipGetLastError());
-        return FW_OK;
-    }
-    const size_t sh_bytes = n_probes * 108, map_bytes = n_probes * d.texels * 16;
-    const size_t mom_bytes = with_vis ? n_probes * a.pd->resolution * a.pd->resolution * 8 : 0, pl_bytes = a.placement ? n_probes * 16 : 0;
-    const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, CALL_SCRATCH_BYTES / 103));
-    size_t off = 0;
-    auto put = [&](size_t b) { const size_t at = off; off += align256(b); return at; };
-    const size_t o_sh = put(sh_bytes), o_maps = put(map_bytes), o_mom = put(mom_bytes), o_pl = put(pl_bytes), o_aov = put((size_t)per * 48),
-                 o_spec = put((size_t)per * 16), o_view = put((size_t)per * 12);
-    const size_t o_lin = linear_rgb ? put((size_t)per * 12) : 0, o_gam = gamma_rgb ? put((size_t)per * 12) : 0, o_8 = rgb8 ? put((size_t)per * 3) : 0;
-    std::vector<float> pack((size_t)per * 3);
-    CallScratch scratch(dev);
-    if (int rc = scratch.alloc(off)) return rc;
-    uint8_t *base = (uint8_t *)scratch.p;
-    HIPCHK(hipMemcpyAsync(base + o_sh, sh, sh_bytes, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(base + o_maps, a.maps, map_bytes, hipMemcpyHostToDevice, stream));
-    if (with_vis) HIPCHK(hipMemcpyAsync(base + o_mom, a.moments, mom_bytes, hipMemcpyHostToDevice, stream));
-    if (a.placement) HIPCHK(hipMemcpyAsync(base + o_pl, a.placement, pl_bytes, hipMemcpyHostToDevice, stream));
-    for (uint32_t done = 0; done < n; done += per) {
-        const uint32_t k = std::min(per, n - done);
-        for (uint32_t i = 0; i < k; i++) {
-            const float *vs = view + (size_t)(done + i) * view_stride;
-            float *o = pack.data() + (size_t)i * 3;
-            o[0] = vs[0]; o[1] = vs[1]; o[2] = vs[2];
-        }
-        HIPCHK(hipMemcpyAsync(base + o_aov, aov + (size_t)done * 12, (size_t)k * 48, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_spec, spec + (size_t)done * 4, (size_t)k * 16, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(base + o_view, pack.data(), (size_t)k * 12, hipMemcpyHostToDevice, stream));
-        launch((const float *)(base + o_sh), (const float *)(base + o_maps), (const float *)(base + o_mom),
-               a.placement ? (const float *)(base + o_pl) : nullptr, k, (const float *)(base + o_aov), (const float *)(base + o_spec),
-               (const float *)(base + o_view), 3, rgb8 ? base + o_8 : nullptr, gamma_rgb ? (float *)(base + o_gam) : nullptr,
-               linear_rgb ? (float *)(base + o_lin) : nullptr);
-        if (linear_rgb) HIPCHK(hipMemcpyAsync(linear_rgb + (size_t)done * 3, base + o_lin, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
-        if (gamma_rgb) HIPCHK(hipMemcpyAsync(gamma_rgb + (size_t)done * 3, base + o_gam, (size_t)k * 12, hipMemcpyDeviceToHost, stream));
-        if (rgb8) HIPCHK(hipMemcpyAsync(rgb8 + (size_t)done * 3, base + o_8, (size_t)k * 3, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-    }
-    HIPCHK(hipGetLastError());
-    return FW_OK;
+    Staged st(dev, stream, p->on_device != 0);
+    const ProbeTables t = probe_tables_stage(st, a, L);
+    HostSlabs sl(st, (uint32_t)full, 103);
+    const int a_aov = sl.in(aov, 48), a_spec = sl.in(spec, 16), a_view = sl.in(view, 12, view_stride);
+    const int a_lin = sl.out(linear_rgb, 12), a_gam = sl.out(gamma_rgb, 12), a_8 = sl.out(rgb8, 3);
+    if (int rc = st.up()) return rc;
+    return sl.run([&](uint32_t, uint32_t k) {
+        const fw::DProbeVis v = probe_vis_device(a, st.ptr<const float>(t.mom));
+        fw::launch_probe_shade_glossy(stream, L.g, a.vis ? &v : nullptr, L.d, st.ptr<const float>(t.sh), st.ptr<const float>(t.maps), st.ptr<const float>(t.pl), k,
+                                      sl.ptr<const float>(a_aov), sl.ptr<const float>(a_spec), sl.ptr<const float>(a_view), sl.stride(a_view), p->gamma,
+                                      sl.ptr<uint8_t>(a_8), sl.ptr<float>(a_gam), sl.ptr<float>(a_lin));
+    });
 }
 
 } // namespace
@@ -5795,14 +5572,14 @@ int fw_bake_probes(fw_scene *scene, const fw_probe_set *set, const fw_render_ray
 
 int fw_probe_irradiance(const fw_probe_grid *grid, const float *sh, int device, uint32_t n, const float *positions, const float *normals,
                         uint32_t stride_floats, float *irradiance, int on_device, void *stream) {
-    try { return probe_irradiance_impl(grid, sh, device, n, positions, normals, stride_floats, irradiance, on_device, stream); }
+    try { return probe_irradiance_impl(grid, ProbeLookupArgs{sh}, device, n, positions, normals, stride_floats, irradiance, on_device, stream); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_irradiance"); }
 }
 
 int fw_probe_shade(const fw_probe_grid *grid, const float *sh, const fw_probe_shade_params *p, const float *aov, float *linear_rgb,
                    float *gamma_rgb, uint8_t *rgb8) {
-    try { return probe_shade_impl(grid, sh, p, aov, linear_rgb, gamma_rgb, rgb8); }
+    try { return probe_shade_impl(grid, ProbeLookupArgs{sh}, p, aov, linear_rgb, gamma_rgb, rgb8); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade"); }
 }
@@ -5846,8 +5623,8 @@ int fw_probe_irradiance_vis(const fw_probe_grid *grid, const float *sh, const fw
                             uint32_t n, const float *positions, const float *normals, uint32_t stride_floats, float *irradiance, int on_device,
                             void *stream) {
     try {
-        const ProbeVis vis{pd, moments, normal_bias};
-        return probe_irradiance_impl(grid, sh, device, n, positions, normals, stride_floats, irradiance, on_device, stream, &vis);
+        const ProbeLookupArgs a{sh, nullptr, nullptr, pd, moments, normal_bias, nullptr, true, false};
+        return probe_irradiance_impl(grid, a, device, n, positions, normals, stride_floats, irradiance, on_device, stream);
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_irradiance_vis"); }
@@ -5856,8 +5633,8 @@ int fw_probe_irradiance_vis(const fw_probe_grid *grid, const float *sh, const fw
 int fw_probe_shade_vis(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias,
                        const fw_probe_shade_params *p, const float *aov, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
     try {
-        const ProbeVis vis{pd, moments, normal_bias};
-        return probe_shade_impl(grid, sh, p, aov, linear_rgb, gamma_rgb, rgb8, &vis);
+        const ProbeLookupArgs a{sh, nullptr, nullptr, pd, moments, normal_bias, nullptr, true, false};
+        return probe_shade_impl(grid, a, p, aov, linear_rgb, gamma_rgb, rgb8);
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_vis"); }
@@ -5889,10 +5666,8 @@ int fw_probe_irradiance_placed(const fw_probe_grid *grid, const float *sh, const
                                const float *placement, int device, uint32_t n, const float *positions, const float *normals, uint32_t stride_floats,
                                float *irradiance, int on_device, void *stream) {
     try {
-        const ProbeVis vis{pd, moments, normal_bias};
-        const ProbePlaced pl{placement};
-        return probe_irradiance_impl(grid, sh, device, n, positions, normals, stride_floats, irradiance, on_device, stream,
-                                     (pd || moments) ? &vis : nullptr, &pl);
+        const ProbeLookupArgs a{sh, nullptr, nullptr, pd, moments, normal_bias, placement, pd || moments, true};
+        return probe_irradiance_impl(grid, a, device, n, positions, normals, stride_floats, irradiance, on_device, stream);
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_irradiance_placed"); }
@@ -5902,9 +5677,8 @@ int fw_probe_shade_placed(const fw_probe_grid *grid, const float *sh, const fw_p
                           const float *placement, const fw_probe_shade_params *p, const float *aov, float *linear_rgb, float *gamma_rgb,
                           uint8_t *rgb8) {
     try {
-        const ProbeVis vis{pd, moments, normal_bias};
-        const ProbePlaced pl{placement};
-        return probe_shade_impl(grid, sh, p, aov, linear_rgb, gamma_rgb, rgb8, (pd || moments) ? &vis : nullptr, &pl);
+        const ProbeLookupArgs a{sh, nullptr, nullptr, pd, moments, normal_bias, placement, pd || moments, true};
+        return probe_shade_impl(grid, a, p, aov, linear_rgb, gamma_rgb, rgb8);
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_placed"); }
@@ -5935,7 +5709,7 @@ int fw_probe_radiance_lookup(const fw_probe_grid *grid, const fw_probe_radiance 
                              float normal_bias, const float *placement, int device, uint32_t n, const float *positions, const float *normals,
                              uint32_t stride_floats, const float *dirs, const float *roughness, float *radiance, int on_device, void *stream) {
     try {
-        const ProbeRadianceArgs a{pr, maps, pd, moments, normal_bias, placement};
+        const ProbeLookupArgs a{nullptr, pr, maps, pd, moments, normal_bias, placement, pd || moments, placement != nullptr};
         return probe_radiance_lookup_impl(grid, a, device, n, positions, normals, stride_floats, dirs, roughness, radiance, on_device, stream);
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
@@ -5946,8 +5720,8 @@ int fw_probe_shade_glossy(const fw_probe_grid *grid, const float *sh, const fw_p
                           const float *moments, float normal_bias, const float *placement, const fw_probe_shade_params *p, const float *aov,
                           const float *spec, const float *view, uint32_t view_stride_floats, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
     try {
-        const ProbeRadianceArgs a{pr, maps, pd, moments, normal_bias, placement};
-        return probe_shade_glossy_impl(grid, sh, a, p, aov, spec, view, view_stride_floats, linear_rgb, gamma_rgb, rgb8);
+        const ProbeLookupArgs a{sh, pr, maps, pd, moments, normal_bias, placement, pd || moments, placement != nullptr};
+        return probe_shade_glossy_impl(grid, a, p, aov, spec, view, view_stride_floats, linear_rgb, gamma_rgb, rgb8);
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_glossy"); }
