@@ -56,7 +56,12 @@ GgxMat and MetalMat surfaces (fw_probe_shade_glossy) when the file holds them; -
 --aov-samples samples, then R rounds, default 1, of D cosine-weighted rays per pixel, default 64, traced from each pixel's surface point;
 a hit nearer than RADIUS > 0 occludes, fully or with --ao-falloff by 1 - dist / RADIUS, fw_bake_ao, DESIGN.md §9t; -s is not used;
 refuses what --probe-lit refuses, and --probe-lit).  --bake-lightmap ... --lightmap-ao RADIUS (also bakes the occlusion over the same
-texels with the same --lightmap-dirs, --lightmap-rounds and --lightmap-dilate; --ao-falloff applies; the .npz also gets ao and bent)."""
+texels with the same --lightmap-dirs, --lightmap-rounds and --lightmap-dilate; --ao-falloff applies; the .npz also gets ao and bent).
+--direct-light [--direct-bias B] (the fixed view lit by the scene's point, spot and directional lights alone: one first-hit pass of
+--aov-samples samples, then one shadow ray per pixel and light, origins moved B >= 0, default 0.001, along the normal: sharp shadows and
+GgxMat highlights without a path, fw_bake_direct; -s is not used; refuses what --ao refuses, and --ao).  --probe-lit FILE
+--direct-light (adds that light, which no probe holds, to the probe-lit frame).  --bake-lightmap ... --lightmap-direct [--direct-bias B]
+(adds the lights' irradiance at each covered texel before the dilation; the .npz also gets direct)."""
 import argparse
 import sys
 import time
@@ -145,7 +150,29 @@ def main(argv=None):
     ap.add_argument("--ao-falloff", action="store_true", help="with --ao or --lightmap-ao: a hit occludes by 1 - dist / RADIUS, not fully")
     ap.add_argument("--lightmap-ao", type=float, default=None, metavar="RADIUS",
                     help="with --bake-lightmap: also bake ambient occlusion and bent normals over the texels into the .npz")
+    ap.add_argument("--direct-light", action="store_true",
+                    help="render the direct light of the scene's point, spot and directional lights; with --probe-lit: add it to that frame")
+    ap.add_argument("--lightmap-direct", action="store_true",
+                    help="with --bake-lightmap: add the direct irradiance of the scene's point, spot and directional lights to the texels")
+    ap.add_argument("--direct-bias", type=float, default=None, metavar="B",
+                    help="with --direct-light or --lightmap-direct: move shadow-ray origins B >= 0 world units along the normal (default 0.001)")
     opt = ap.parse_args(argv)
+    if opt.direct_light:
+        if (opt.ao is not None or opt.bake_probes is not None or opt.bake_lightmap is not None or opt.camera != "pinhole" or opt.denoise is not None
+                or opt.orbit or opt.adaptive is not None or opt.progressive > 0 or opt.checkpoint or opt.temporal is not None):
+            ap.error("--direct-light cannot be combined with --ao, --bake-probes, --bake-lightmap, --camera, --denoise, --orbit, --adaptive, "
+                     "--progressive, --checkpoint or --temporal")
+        if opt.aov_samples < 1:
+            ap.error("--aov-samples needs S >= 1")
+        if not opt.output:
+            ap.error("--direct-light needs -o FILE.png")
+    if opt.lightmap_direct and opt.bake_lightmap is None:
+        ap.error("--lightmap-direct needs --bake-lightmap")
+    if opt.direct_bias is not None:
+        if not (opt.direct_light or opt.lightmap_direct):
+            ap.error("--direct-bias needs --direct-light or --lightmap-direct")
+        if not 0.0 <= opt.direct_bias < float("inf"):
+            ap.error("--direct-bias B needs a finite B >= 0")
     if opt.ao is not None:
         if (opt.probe_lit is not None or opt.bake_probes is not None or opt.bake_lightmap is not None or opt.camera != "pinhole"
                 or opt.denoise is not None or opt.orbit or opt.adaptive is not None or opt.progressive > 0 or opt.checkpoint or opt.temporal is not None):
@@ -426,7 +453,13 @@ def main(argv=None):
     if probe_grid is not None:
         render = renderer.render_probe_lit(scene, probe_grid, probe_sh, opt.aov_samples, device=opt.device, depth=probe_depth, moments=probe_moments,
                                            normal_bias=0.0 if opt.probe_normal_bias is None else opt.probe_normal_bias,
-                                           placement=probe_placement, radiance=probe_radiance, maps=probe_maps).rgb8
+                                           placement=probe_placement, radiance=probe_radiance, maps=probe_maps, direct=direct_light(opt)).rgb8
+        print(f"Finished Rendering in {int(time.time() - start)} s")
+        print(f'Saving image to "{opt.output}"')
+        save_image(render, opt.output, opt.width, opt.height)
+        return 0
+    if opt.direct_light:
+        render = renderer.render_direct(scene, direct_light(opt), opt.aov_samples, device=opt.device).rgb8
         print(f"Finished Rendering in {int(time.time() - start)} s")
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)
@@ -444,15 +477,18 @@ def main(argv=None):
     if lightmap is not None:
         import numpy as np
         rounds = 1 if opt.lightmap_rounds is None else opt.lightmap_rounds
-        irradiance, sums = renderer.bake_lightmap(scene, lightmap, rounds, 2 if opt.lightmap_dilate is None else opt.lightmap_dilate, device=opt.device)
+        irradiance, sums = renderer.bake_lightmap(scene, lightmap, rounds, 2 if opt.lightmap_dilate is None else opt.lightmap_dilate, device=opt.device,
+                                                  direct=direct_light(opt, opt.lightmap_direct))
         owner = _lib.lightmap_texels(lightmap, opt.device)[1].reshape(lightmap.height, lightmap.width)
         extra = {}
+        if opt.lightmap_direct:
+            extra = dict(direct=renderer.lightmap_direct)
         if opt.lightmap_ao is not None:
             from .api import AmbientOcclusion
             ao = AmbientOcclusion(opt.lightmap_ao, lightmap.directions, int(opt.ao_falloff)).seed(opt.seed)
             occ, bent, _ao_sums = renderer.bake_lightmap_ao(scene, lightmap, ao, rounds, 2 if opt.lightmap_dilate is None else opt.lightmap_dilate,
                                                             device=opt.device)
-            extra = dict(ao=occ, bent=bent)
+            extra.update(ao=occ, bent=bent)
         print(f"Finished Baking in {int(time.time() - start)} s")
         print(f'Saving a {lightmap.width} x {lightmap.height} lightmap to "{opt.output}"')
         with open(opt.output, "wb") as f:       # (np.savez would append .npz to a name without it)
@@ -506,6 +542,14 @@ def main(argv=None):
         print(f"{name}: no display on this node; pass -o/--output to save the image", file=sys.stderr)
         return 2
     return 0
+
+
+def direct_light(opt, on=None):
+    """the DirectLight of --direct-light (or of `on`), or None"""
+    if not (opt.direct_light if on is None else on):
+        return None
+    from .api import DirectLight
+    return DirectLight(1e-3 if opt.direct_bias is None else opt.direct_bias)
 
 
 def denoised(renderer, scene, opt):

@@ -224,6 +224,23 @@ AO_PROTOTYPES = {
 }
 
 
+# direct light of point, spot and directional lights at surface points (include/firework_hip.h: fw_direct_rays, fw_direct_reduce,
+# fw_bake_direct)
+class fw_direct(C.Structure):
+    _fields_ = [("lobe", u32), ("face_view", u32), ("bias", f32), ("chunk_points", u32)]
+
+
+# the three prototypes (argument types; every one returns int), applied by _lib.load
+DIRECT_PROTOTYPES = {
+    "fw_direct_rays": [C.POINTER(fw_direct), C.c_void_p, u32, C.c_int, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p,
+                       C.c_void_p, C.c_int, C.c_void_p],
+    "fw_direct_reduce": [C.c_int, C.POINTER(fw_direct), C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p,
+                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_bake_direct": [C.c_void_p, C.POINTER(fw_direct), C.POINTER(fw_trace_params), u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32,
+                       C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.POINTER(fw_stats)],
+}
+
+
 # probe relocation and classification (include/firework_hip.h: fw_probe_survey, fw_probe_relocate_step, fw_relocate_probes,
 # fw_probe_irradiance_placed, fw_probe_shade_placed)
 class fw_probe_relocate(C.Structure):

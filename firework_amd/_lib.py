@@ -131,7 +131,7 @@ def load(preload=False, device=None):
     lib.fw_probe_shade.argtypes = [C.POINTER(A.fw_probe_grid), C.c_void_p, C.POINTER(A.fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
     for name, argtypes in (list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()) + list(A.PROBE_PLACE_PROTOTYPES.items())
-                           + list(A.PROBE_RADIANCE_PROTOTYPES.items())):
+                           + list(A.PROBE_RADIANCE_PROTOTYPES.items()) + list(A.DIRECT_PROTOTYPES.items())):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
@@ -1165,6 +1165,109 @@ def ao_reduce(ao, rays, hits, sums, ids=None, device=0, stream=None):
     return sums
 
 
+class _DirectPoints(_AoPoints):
+    """_AoPoints with a direct-light call's optional per-id arrays, of the points' kind (numpy / torch on cuda:`device`).  view: (M, 3)
+    float32, contiguous or a column range of a contiguous (M, S) array such as a ray buffer's rays[:, 3:6]; spec: (M, 4) float32
+    contiguous (F0.rgb, rho), needs view.  Arrays indexed by id (sums, out) have M records of 8 floats."""
+
+    def __init__(self, positions, normals, ids, view, spec, device):
+        super().__init__(positions, normals, ids, device)
+        m = self.m
+        self.view, self.view_stride, self.spec = None, 3, None
+        if spec is not None and view is None:
+            raise ValueError("spec needs view")
+        if view is not None:
+            if tuple(view.shape) != (m, 3):
+                raise ValueError(f"view must have shape ({m}, 3)")
+            if self.torch:
+                import torch
+                if view.dtype != torch.float32 or view.stride(1) != 1 or view.device != self.dev or (m > 1 and int(view.stride(0)) < 3):
+                    raise ValueError("view must be an (M, 3) float32 tensor on the points' device with unit column stride and a row stride >= 3")
+                self.view, self.view_stride = view.data_ptr(), (int(view.stride(0)) if m > 1 else 3)
+            else:
+                v = np.asarray(view, np.float32)
+                if not (v.strides[1] == 4 and v.strides[0] % 4 == 0 and v.strides[0] >= 12):
+                    v = np.ascontiguousarray(v)
+                view = v
+                self.view, self.view_stride = v.ctypes.data, v.strides[0] // 4
+        if spec is not None:
+            if tuple(spec.shape) != (m, 4):
+                raise ValueError(f"spec must have shape ({m}, 4)")
+            if self.torch:
+                import torch
+                _check_device_tensor(spec, (m, 4), torch.float32, self.dev.index or 0, "spec")
+                self.spec = spec.data_ptr()
+            else:
+                spec = np.ascontiguousarray(np.asarray(spec, np.float32))
+                self.spec = spec.ctypes.data
+        self.keep = self.keep + (view, spec)
+
+    def records8(self, arr, name):
+        """checks an array indexed by id: (M, 8) or (H, W, 8) float32 with H W = M, where the points lie"""
+        shape = tuple(arr.shape)
+        if shape[-1] != 8 or int(np.prod(shape[:-1])) != self.m:
+            raise ValueError(f"{name} must have shape ({self.m}, 8) or (H, W, 8) with H W = {self.m}")
+        if self.torch:
+            import torch
+            _check_device_tensor(arr, shape, torch.float32, self.dev.index or 0, name)
+            return arr.data_ptr()
+        _host_f32(arr, None, name)
+        return arr.ctypes.data
+
+
+def direct_rays(direct, lights, positions, normals, ids=None, view=None, spec=None, device=0, out=None, stream=None):
+    """fw_direct_rays: the shadow rays of an api.DirectLight from surface points (see _DirectPoints) towards `lights` (api lights or
+    fw_light records), generated on the device: (n * Ln, 6) float32, entry q * Ln + i = point ids[q] (ids None: q) towards light i, or
+    six zeros.  numpy points: returns a numpy array.  Points on cuda:`device`: generated on `stream` (default: the current torch stream)
+    where they lie; returns a device tensor (out: a contiguous float32 tensor of that shape to fill instead)."""
+    lib = load()
+    d = direct.to_abi()
+    arr, ln = _light_array(lights)
+    pts = _DirectPoints(positions, normals, ids, view, spec, device)
+    shape = (pts.n * ln, 6)
+    if pts.torch:
+        import torch
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=pts.dev)
+        _check_device_tensor(out, shape, torch.float32, device, "out")
+        _check(lib, lib.fw_direct_rays(C.byref(d), arr, ln, int(device), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride,
+                                       pts.spec, out.data_ptr(), 1, _stream_arg(stream, pts.dev)))
+        return out
+    rays = np.empty(shape, np.float32)
+    _check(lib, lib.fw_direct_rays(C.byref(d), arr, ln, int(device), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride, pts.spec,
+                                   rays.ctypes.data, 0, None))
+    return rays
+
+
+def direct_reduce(direct, lights, positions, normals, rays, hits, sums, ids=None, view=None, spec=None, device=0, stream=None):
+    """fw_direct_reduce: adds one round's reduction (E.rgb, N, S.rgb, each rounded to float32 once) of an api.DirectLight to sums[ids[q]]
+    (ids None: sums[q]); sums (M, 8) or (H, W, 8) float32, updated in place; its last float is never written.  rays (n * Ln, 6) float32
+    and hits as DeviceScene.trace returns them for those rays: a HIT_DTYPE array for numpy rays, or an (n * Ln, 12) float32 device
+    tensor for rays on cuda:`device`, reduced on `stream` (default: the current torch stream) where they lie.  Returns sums."""
+    lib = load()
+    d = direct.to_abi()
+    arr, ln = _light_array(lights)
+    pts = _DirectPoints(positions, normals, ids, view, spec, device)
+    total = pts.n * ln
+    if tuple(rays.shape) != (total, 6) or int(hits.shape[0]) != total:
+        raise ValueError(f"rays must have shape ({total}, 6) and hits {total} records")
+    p_sums = pts.records8(sums, "sums")
+    if pts.torch:
+        import torch
+        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
+        _check_device_tensor(hits, (total, 12), torch.float32, device, "hits")
+        _check(lib, lib.fw_direct_reduce(int(device), C.byref(d), arr, ln, pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride,
+                                         pts.spec, rays.data_ptr(), hits.data_ptr(), p_sums, 1, _stream_arg(stream, pts.dev)))
+        return sums
+    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
+    h = np.ascontiguousarray(hits)
+    if h.dtype != HIT_DTYPE:
+        raise ValueError("host hits must be an array of HIT_DTYPE")
+    _check(lib, lib.fw_direct_reduce(int(device), C.byref(d), arr, ln, pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride, pts.spec,
+                                     r.ctypes.data, h.ctypes.data, p_sums, 0, None))
+    return sums
+
+
 class DeviceScene:
     """An uploaded scene (`fw_scene*`): SoA scene arrays + TLAS/BLAS resident in HBM."""
 
@@ -1597,6 +1700,37 @@ class DeviceScene:
         out = zeros() if out is None else out
         _check(self._lib, self._lib.fw_bake_ao(self.handle, C.byref(a), C.byref(p), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, int(first_round),
                                                int(rounds), pts.records(sums, "sums"), pts.records(out, "out"), C.byref(st)))
+        return out, sums, st.as_dict()
+
+    def bake_direct(self, direct, positions, normals, ids=None, view=None, spec=None, rounds=1, first_round=0, sums=None, out=None, seed=0,
+                    use_bvh=True, stream=None, rays_per_batch=0, flags=0, chunk=None):
+        """fw_bake_direct: the rounds [first_round, first_round + rounds) of an api.DirectLight at surface points (see _DirectPoints:
+        numpy arrays, or tensors on this scene's device, read in place) under this scene's own lights (set_lights), `chunk` points at a
+        time (None: the description's own setting; 0: automatic).  sums: (M, 8) or (H, W, 8) float32 running sums (E.rgb, N, S.rgb, -)
+        of the rounds before first_round, updated in place (None: zeros, only with first_round 0); out: an array of the same kind to
+        receive sums / rounds (None: zeros); both are indexed by id, entries outside ids are not touched.  Returns (out, sums, stats):
+        host arrays for numpy points, device tensors — baked on `stream` (default: the current torch stream) — for device points."""
+        d = direct.to_abi()
+        if chunk is not None:
+            d.chunk_points = int(chunk)
+        pts = _DirectPoints(positions, normals, ids, view, spec, self.device)
+        p = A.fw_trace_params()
+        p.use_bvh, p.flags, p.seed, p.rays_per_batch = int(bool(use_bvh)), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rays_per_batch)
+        st = A.fw_stats()
+        if sums is None and int(first_round) > 0:
+            raise ValueError("first_round > 0 needs the sums of the rounds before it")
+        if pts.torch:
+            import torch
+            zeros = lambda: torch.zeros((pts.m, 8), dtype=torch.float32, device=pts.dev)      # noqa: E731
+            p.on_device = 1
+            p.stream = _stream_arg(stream, pts.dev)
+        else:
+            zeros = lambda: np.zeros((pts.m, 8), np.float32)      # noqa: E731
+        sums = zeros() if sums is None else sums
+        out = zeros() if out is None else out
+        _check(self._lib, self._lib.fw_bake_direct(self.handle, C.byref(d), C.byref(p), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view,
+                                                   pts.view_stride, pts.spec, int(first_round), int(rounds), pts.records8(sums, "sums"),
+                                                   pts.records8(out, "out"), C.byref(st)))
         return out, sums, st.as_dict()
 
     def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,

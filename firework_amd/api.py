@@ -2474,6 +2474,217 @@ def ao_resolve(sums, rounds: int) -> np.ndarray:
         return np.concatenate([bent, occ[..., None]], axis=-1).astype(np.float32)
 
 
+# --------------------------------------------------------------------------- direct light of delta lights (fw_bake_direct)
+class DirectLight:
+    """The direct light of a scene's point, spot and directional lights at surface points (fw_direct): one shadow ray per
+    point and light, origins moved `bias` along the normal.  lobe "cosine": E is the irradiance; "renderer": E is pi x what the path
+    tracer's light sample adds per unit albedo at a Lambertian vertex (2 c^3).  face_view: with view directions, the side of a surface
+    the eye sees is the side that is lit.  chunk_points as fw_direct's."""
+    LOBES = {"cosine": 0, "renderer": 1}
+
+    def __init__(self, bias: float = 1e-3, lobe: str = "cosine", face_view: bool = True):
+        self.bias, self.lobe, self.face_view, self.chunk_points = float(np.float32(bias)), lobe, face_view, 0
+
+    def check(self):
+        """what fw_direct_rays rejects in a description, as a ValueError, in its order"""
+        if self.lobe not in self.LOBES:
+            raise ValueError('lobe must be "cosine" or "renderer"')
+        if self.face_view not in (False, True, 0, 1):
+            raise ValueError("face_view must be False or True")
+        if not (np.isfinite(self.bias) and self.bias >= 0.0):
+            raise ValueError("bias must be finite and >= 0")
+        return self
+
+    def to_abi(self) -> A.fw_direct:
+        self.check()
+        d = A.fw_direct()
+        d.lobe, d.face_view, d.bias, d.chunk_points = self.LOBES[self.lobe], int(bool(self.face_view)), self.bias, int(self.chunk_points)
+        return d
+
+
+def light_records(lights):
+    """(kind (Ln,) uint32, rec (Ln, 12) float64) of api lights or fw_light records as a resident scene keeps them: (position, -),
+    (direction, cos_inner), (intensity, cos_outer), every field a float32 value, the direction divided by its float64 length and
+    rounded to float32"""
+    kind, rec = np.zeros(len(lights), np.uint32), np.zeros((len(lights), 12), np.float64)
+    for i, light in enumerate(lights):
+        l = light if isinstance(light, A.fw_light) else light.to_abi()
+        kind[i] = l.kind
+        d = np.array([l.direction.x, l.direction.y, l.direction.z], np.float64)
+        n = np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        if n > 0:
+            d = (d / n).astype(np.float32).astype(np.float64)
+        rec[i] = (l.position.x, l.position.y, l.position.z, 0.0, d[0], d[1], d[2], l.cos_inner, l.intensity.x, l.intensity.y, l.intensity.z,
+                  l.cos_outer)
+    return kind, rec
+
+
+def _dot3(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _direct_points(direct: "DirectLight", positions, normals, ids, view, spec):
+    """(ids, p32 (n, 3) float32, usable (n,), nh (n, 3) float64, view (n, 3) float64 or None, spec (n, 4) float32 or None) of a call"""
+    P, Nn = np.asarray(positions, np.float32).reshape(-1, 3), np.asarray(normals, np.float32).reshape(-1, 3)
+    ids = np.arange(P.shape[0], dtype=np.uint32) if ids is None else np.asarray(ids, np.uint32).reshape(-1)
+    at = ids.astype(np.int64)
+    p32, n32 = P[at], Nn[at]
+    ok = ao_usable(p32, n32)
+    n64 = n32.astype(np.float64)
+    with np.errstate(all="ignore"):
+        nh = n64 / np.sqrt((n64[:, 0:1] * n64[:, 0:1] + n64[:, 1:2] * n64[:, 1:2]) + n64[:, 2:3] * n64[:, 2:3])
+        vw = None
+        if view is not None:
+            vw = np.asarray(view, np.float32).reshape(-1, 3)[at].astype(np.float64)
+            if direct.face_view:
+                nh = np.where((_dot3(nh, vw) > 0.0)[:, None], -nh, nh)
+    sp = None if spec is None else np.asarray(spec, np.float32).reshape(-1, 4)[at]
+    if sp is not None and vw is None:
+        raise ValueError("spec needs view")
+    return ids, p32, ok, nh, vw, sp
+
+
+def _spot_factor(c, ci, co):
+    with np.errstate(all="ignore"):
+        t = np.fmin(np.fmax((c - co) / (ci - co), 0.0), 1.0)
+        return np.where(ci > co, (t * t) * (3.0 - 2.0 * t), np.where(c >= co, 1.0, 0.0))
+
+
+def _direct_geometry(kind, rec, d):
+    """(d2, w, s) of directions d (n, Ln, 3) float64 towards the lights: the squared length, the unit direction, the spot factor (1 for
+    the other kinds)"""
+    with np.errstate(all="ignore"):
+        d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        w = d / np.sqrt(d2)[..., None]
+        s = np.where(kind[None, :] == 1, _spot_factor(-_dot3(w, rec[None, :, 4:7]), rec[None, :, 7], rec[None, :, 11]), 1.0)
+    return d2, w, s
+
+
+def direct_rays(direct: "DirectLight", lights, positions, normals, ids=None, view=None, spec=None, device=None, terms: bool = False):
+    """The numpy statement of fw_direct_rays: (n * Ln, 6) float32, entry q * Ln + i = the shadow ray of point id = ids[q] (ids None: q)
+    towards light i, or six zeros (include/firework_hip.h has the rules).  positions, normals, view (M, 3) and spec (M, 4) float32,
+    indexed by id (device: see panorama_rays).  terms=True: returns (rays, t) with t a dict of (n, Ln) float64 arrays — c = nh . w, cs =
+    a spot's -(w . axis) (nan for the other kinds), d2 — the quantities the culling decisions compare with their thresholds."""
+    direct.check()
+    kind, rec = light_records(lights)
+    Ln = kind.size
+    ids, p32, ok, nh, vw, sp = _direct_points(direct, positions, normals, ids, view, spec)
+    n = ids.size
+    with np.errstate(all="ignore"):
+        p64 = p32.astype(np.float64)
+        o = p64 if direct.bias == 0.0 else p64 + float(F32(direct.bias)) * nh
+        d = np.where((kind == 2)[None, :, None], -rec[None, :, 4:7], rec[None, :, 0:3] - o[:, None, :])
+        d2, w, s = _direct_geometry(kind, rec, d)
+        c = _dot3(nh[:, None, :], w)
+        o32 = np.repeat(o.astype(np.float32)[:, None, :], Ln, axis=1)
+        d32 = d.astype(np.float32)
+        lit = ok[:, None] & np.any(rec[:, 8:11] != 0.0, axis=1)[None, :] & (d2 > 0.0) & np.isfinite(d2) & (c > 0.0) & (s != 0.0)
+        if sp is not None:
+            lit &= ~(sp[:, 3] < 0)[:, None]
+        lit &= np.all(np.isfinite(o32), axis=-1) & np.all(np.isfinite(d32), axis=-1) & np.any(d32 != 0, axis=-1)
+    rays = _rays_out(np.where(lit[..., None], o32, np.float32(0)).reshape(-1, 3), np.where(lit[..., None], d32, np.float32(0)).reshape(-1, 3), device)
+    if not terms:
+        return rays
+    cs = np.where(kind[None, :] == 1, -_dot3(w, rec[None, :, 4:7]), np.nan)
+    return rays, dict(c=c, cs=np.broadcast_to(cs, (n, Ln)), d2=d2)
+
+
+def direct_reduce(direct: "DirectLight", lights, positions, normals, rays, hits_t, hits_object, ids=None, view=None, spec=None, terms: bool = False):
+    """The numpy float64 statement of fw_direct_reduce: (n, 7) float64, the accumulators (E.rgb, N, S.rgb) of one round before their one
+    rounding to float32, for rays (n * Ln, 6) float32 (as stored) and the hits' t (float32) and object (uint32, 0xFFFFFFFF = miss)
+    columns, summed in the device's order (G partial sums, an xor butterfly).  terms=True: returns (acc, T, vis) with T (n, 7) = sum_i
+    |term_i| (what a rounding-error bound of the sums scales with) and vis (n, Ln) bool, the entries that count as visible (N's terms)."""
+    direct.check()
+    kind, rec = light_records(lights)
+    Ln = kind.size
+    ids, p32, ok, nh, vw, sp = _direct_points(direct, positions, normals, ids, view, spec)
+    n = ids.size
+    d = np.asarray(rays, np.float32).astype(np.float64).reshape(n, Ln, 6)[..., 3:]
+    t32 = np.asarray(hits_t, np.float32).reshape(n, Ln)
+    miss = np.asarray(hits_object).astype(np.uint32).reshape(n, Ln) == np.uint32(0xFFFFFFFF)
+    rho = np.zeros(n, np.float32) if sp is None else sp[:, 3]
+    f0 = np.zeros((n, 3)) if sp is None else sp[:, 0:3].astype(np.float64)
+    glossy = rho > 0
+    with np.errstate(all="ignore"):
+        if vw is None:
+            wo, co, lo, takes = np.zeros((n, 3)), np.zeros(n), np.zeros(n), ok & ~(rho < 0) & ~glossy
+        else:
+            wo = -(vw / np.sqrt(_dot3(vw, vw))[:, None])
+            co = _dot3(nh, wo)
+            takes = ok & ~(rho < 0) & (~glossy | (co > 0.0))
+        al = (rho * rho).astype(np.float64)                                                # the float32 product, widened
+        al2 = al * al
+        if vw is not None:
+            tw = wo - co[:, None] * nh
+            lo = 0.5 * (np.sqrt(1.0 + al2 * (_dot3(tw, tw) / (co * co))) - 1.0)
+        d2, w, s = _direct_geometry(kind, rec, d)
+        c = _dot3(nh[:, None, :], w)
+        live = takes[:, None] & np.any(d != 0.0, axis=-1) & np.isfinite(d2) & (c > 0.0)
+        vis = live & (miss | ((kind != 2)[None, :] & (t32 >= np.float32(1.0))))
+        L = np.where((kind == 2)[None, :, None], rec[None, :, 8:11], (rec[None, :, 8:11] * s[..., None]) / d2[..., None])
+        g = 2.0 * ((c * c) * c) if direct.lobe == "renderer" else c
+        e = L * g[..., None]
+        # GgxMat's f cos around nh without a tangent frame
+        h0 = wo[:, None, :] + w
+        h = h0 / np.sqrt(_dot3(h0, h0))[..., None]
+        hn, oh = _dot3(nh[:, None, :], h), _dot3(wo[:, None, :], h)
+        th = h - hn[..., None] * nh[:, None, :]
+        sd = _dot3(th, th) + al2[:, None] * (hn * hn)
+        D = al2[:, None] / (np.pi * (sd * sd))
+        tu = w - c[..., None] * nh[:, None, :]
+        li = 0.5 * (np.sqrt(1.0 + al2[:, None] * (_dot3(tu, tu) / (c * c))) - 1.0)
+        gg = (D / (4.0 * co[:, None])) / ((1.0 + lo[:, None]) + li)
+        m = 1.0 - oh
+        m5 = ((m * m) * (m * m)) * m
+        sg = L * ((f0[:, None, :] + (1.0 - f0[:, None, :]) * m5[..., None]) * gg[..., None])
+        term = np.zeros((n, Ln, 7))
+        term[..., 0:3] = np.where((vis & ~glossy[:, None])[..., None], e, 0.0)
+        term[..., 3] = np.where(vis, 1.0, 0.0)
+        term[..., 4:7] = np.where((vis & glossy[:, None])[..., None], sg, 0.0)
+    G = 1
+    while G < min(Ln, 64):
+        G *= 2
+    rows = -(-Ln // G)                                                                       # lane l takes i = l, l + G, ... in ascending order
+    padded = np.zeros((n, rows * G, 7))
+    padded[:, :Ln] = term
+    part = np.zeros((n, G, 7))
+    for row in padded.reshape(n, rows, G, 7).transpose(1, 0, 2, 3):
+        part = part + row
+    mm = G // 2
+    while mm >= 1:
+        part = part + part[:, np.arange(G) ^ mm]
+        mm //= 2
+    acc = part[:, 0]
+    if not terms:
+        return acc
+    return acc, np.abs(term).sum(axis=1), vis
+
+
+def direct_resolve(sums, rounds: int) -> np.ndarray:
+    """The statement of k_direct_resolve: (..., 8) float32, the float32 running sums (..., 8) of `rounds` rounds divided by their number
+    in float64 and rounded once; the eighth float 0"""
+    s = np.asarray(sums, np.float32).astype(np.float64)
+    out = (s / float(rounds)).astype(np.float32)
+    out[..., 7] = 0.0
+    return out
+
+
+def material_direct_table(desc: "SceneDesc") -> np.ndarray:
+    """(n_materials + 1, 4) float32: fw_bake_direct's (F0.rgb, rho) of every material of a scene description — a GgxMat (albedo,
+    roughness): a glossy point; a Lambertian or Isotropic material zeros: a diffuse point; a Metal, Dielectric or Emissive material and
+    the last row, a miss, rho = -1: they take no light sample"""
+    n = int(desc.desc.n_materials)
+    table = np.zeros((n + 1, 4), np.float32)
+    table[:, 3] = -1.0
+    for i in range(n):
+        m = desc.materials[i]
+        if m.kind == A.FW_MAT_GGX:
+            table[i] = (m.albedo.x, m.albedo.y, m.albedo.z, np.float32(m.roughness))
+        elif m.kind in (A.FW_MAT_LAMBERTIAN, A.FW_MAT_ISOTROPIC):
+            table[i] = 0.0
+    return table
+
+
 # render_sequence's default cap on the samples a pixel carries over from the frames before it (DESIGN.md §9j)
 DEFAULT_MAX_HISTORY = 64.0
 
@@ -2895,21 +3106,44 @@ class Renderer:
                 ds.close()
 
     def bake_lightmap(self, scene, lightmap: "Lightmap", rounds: int = 1, dilate: int = 2, first_round: int = 0, sums=None, chunk=None,
-                      device: int = 0, stream=None, on_device: bool = False):
+                      device: int = 0, stream=None, on_device: bool = False, direct: "DirectLight" = None):
         """A lightmap baked on the device (not in the reference; fw_bake_lightmap): `rounds` rounds of the lightmap's cosine-weighted
         rays, each rendered with settings["samples"] paths per direction and this renderer's seed (+ the round), use_bvh, batch size and
         flags — lights and light sampling included; its camera, size and gamma are not used — and reduced to the irradiance of every
         covered texel.  Returns (irradiance, sums): (H, W, 4) float32 each; irradiance rgb = sums / (first_round + rounds) with a = 1 on
         covered texels, then `dilate` dilation passes (a = 0.5 on filled texels, 0 elsewhere); pass sums back with first_round = the
         rounds it holds to add more.  on_device and chunk as _lib.DeviceScene.bake_lightmap; the call's stats are kept in
-        self.lightmap_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        self.lightmap_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene.  direct (a DirectLight with the cosine lobe;
+        DESIGN.md §9w): what a lightmap's rays cannot hit — the scene's point, spot and directional lights at the texel itself — is
+        added.  fw_bake_lightmap runs with 0 dilation passes; fw_bake_direct runs one round on fw_lightmap_texels' records and covered
+        list in place; irradiance.rgb += E on the covered texels in float32; then fw_lightmap_dilate runs `dilate` passes.  sums stay
+        the rays' own.  E (H, W, 3) is kept in self.lightmap_direct and the call's stats in self.direct_stats.  Another lobe:
+        ValueError.  direct=None: the calls and the bits above."""
         from . import _lib
         s = self.settings
+        if direct is not None and direct.check().lobe != "cosine":
+            raise ValueError('a lightmap holds irradiance: direct needs the lobe "cosine"')
         ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
         try:
-            irr, sums, self.lightmap_stats = ds.bake_lightmap(lightmap, rounds, s["samples"], first_round, sums, dilate, seed=s["seed"],
-                                                              use_bvh=s["use_bvh"], stream=stream, paths_per_batch=s["paths_per_batch"],
-                                                              flags=s["flags"], chunk=chunk, on_device=on_device)
+            irr, sums, self.lightmap_stats = ds.bake_lightmap(lightmap, rounds, s["samples"], first_round, sums, dilate if direct is None else 0,
+                                                              seed=s["seed"], use_bvh=s["use_bvh"], stream=stream,
+                                                              paths_per_batch=s["paths_per_batch"], flags=s["flags"], chunk=chunk, on_device=on_device)
+            if direct is not None:
+                import torch
+                w, h = int(lightmap.width), int(lightmap.height)
+                rec, owner, count = _lib.lightmap_texels(lightmap, ds.device, on_device=True)
+                if count == 0:
+                    raise ValueError("the lightmap covers no texel")
+                ids = torch.nonzero(owner != -1).flatten().to(torch.int32).contiguous()          # ascending: the covered list
+                out, _dsums, self.direct_stats = ds.bake_direct(direct, rec[:, 0:3], rec[:, 4:7], ids, None, None, 1, seed=s["seed"],
+                                                                use_bvh=s["use_bvh"], flags=s["flags"])
+                host = not type(irr).__module__.startswith("torch")
+                image = (torch.from_numpy(np.ascontiguousarray(irr)).to(rec.device) if host else irr).reshape(h * w, 4)
+                at = ids.long()
+                image[at, 0:3] = image[at, 0:3] + out[at, 0:3]
+                image = _lib.lightmap_dilate(image.reshape(h, w, 4), dilate, ds.device)
+                self.lightmap_direct = out[:, 0:3].reshape(h, w, 3).cpu().numpy()
+                irr = image.cpu().numpy() if host else image
             return irr, sums
         finally:
             if ds is not scene:
@@ -2964,9 +3198,63 @@ class Renderer:
                 ds.close()
         return image[..., 0].cpu().numpy(), out[:, 0:3].cpu().numpy().reshape(h, w, 3), sums.cpu().numpy().reshape(h, w, 4)
 
+    def _direct_term(self, ds, direct: "DirectLight", aov, model, rays=None):
+        """(term (N, 3), out (N, 8), spec (N, 4), rays (N, 6)) device tensors: the direct light of the resident scene's point, spot and
+        directional lights at the pixels of the records `aov`.  The view's sample-0 rays (fw_camera_rays; with `model`,
+        fw_model_rays; or `rays`, already made) are traced by fw_trace_rays; each hit's material gives the pixel's (F0, rho)
+        (material_direct_table) and the rays' directions the view; fw_bake_direct runs one round on the records in place.  In float32,
+        term = a ((v E) float32(1 / pi)) for a pixel with !(rho > 0) and v S for a glossy one.  The call's stats are kept in
+        self.direct_stats."""
+        import torch
+        from . import _lib
+        s = self.settings
+        dev = aov.device
+        n = int(aov.shape[0])
+        if rays is None:
+            if model is not None:
+                rays = _lib.model_rays(model, 0, 1, ds.device, out=torch.empty((1, n, 6), dtype=torch.float32, device=dev))[0]
+            else:
+                rays = torch.from_numpy(ds.camera_rays(self, 0)).to(dev)
+        hit = _lib.hit_fields(ds.trace(rays, s["use_bvh"], seed=s["seed"]))
+        table = torch.from_numpy(material_direct_table(ds._desc)).to(dev)
+        miss = torch.full_like(hit["material"], table.shape[0] - 1)
+        spec = table[torch.where(hit["object"] == -1, miss, hit["material"]).long()].contiguous()
+        out, _sums, self.direct_stats = ds.bake_direct(direct, aov[:, 8:11], aov[:, 4:7], None, rays[:, 3:6], spec, 1, seed=s["seed"],
+                                                       use_bvh=s["use_bvh"], flags=s["flags"])
+        v = aov[:, 3:4]
+        term = torch.where(spec[:, 3:4] > 0, v * out[:, 4:7], aov[:, 0:3] * ((v * out[:, 0:3]) * float(np.float32(1.0 / np.pi))))
+        return term, out, spec, rays
+
+    def render_direct(self, scene, direct: "DirectLight", aov_samples: int = 1, model: "CameraModel" = None, device: int = 0) -> RenderResult:
+        """The direct light of the scene's point, spot and directional lights in this renderer's view (not in the reference;
+        fw_bake_direct): sharp shadows and GgxMat highlights without a path.  The first-hit guide buffers (fw_render_aovs
+        at `aov_samples` samples; with `model`, fw_render_model_aovs) stay on the device; _direct_term gives the frame, resolved by
+        fw_denoise at 0 iterations.  Area emitters and the environment are not in it: probes and lightmaps hold them.  The call's stats
+        are kept in self.direct_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        import torch
+        from . import _lib
+        direct.check()
+        s = self.settings
+        w, h = (int(model.width), int(model.height)) if model is not None else (int(s["width"]), int(s["height"]))
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            aov = torch.empty((w * h, 12), dtype=torch.float32, device=torch.device("cuda", ds.device))
+            if model is not None:
+                ds.model_aovs(model, aov_samples, seed=s["seed"], use_bvh=s["use_bvh"], out=aov)
+            else:
+                ds.aovs(self, aov_samples, out=aov)
+            term = self._direct_term(ds, direct, aov, model)[0]
+            rgb8, gam, lin = _lib.denoise(term.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
+            stats = dict(ds.aovs_stats)
+        finally:
+            if ds is not scene:
+                ds.close()
+        return RenderResult(rgb8.cpu().numpy(), gam.cpu().numpy(), lin.cpu().numpy(), stats, w, h)
+
     def render_probe_lit(self, scene, probes, sh, aov_samples: int = 8, wrap: bool = True, device: int = 0, model: "CameraModel" = None,
                          depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0, ao: "AmbientOcclusion" = None,
-                         ao_rounds: int = 1, placement=None, radiance: "ProbeRadiance" = None, maps=None) -> RenderResult:
+                         ao_rounds: int = 1, placement=None, radiance: "ProbeRadiance" = None, maps=None,
+                         direct: "DirectLight" = None) -> RenderResult:
         """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
         (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
         from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
@@ -2985,9 +3273,15 @@ class Renderer:
         `model`, fw_model_rays) are traced on the device by fw_trace_rays; each hit's material gives the pixel's (F0, rho) — a GgxMat
         (albedo, roughness), a MetalMat (albedo, roughness clipped to [0.03, 1]), every other material and every miss rho = 0 — and the
         frame is shaded by fw_probe_shade_glossy with those rays' directions as the view, with or without depth and placement.
-        radiance=None: the calls and the bits above.  radiance together with ao: ValueError."""
+        radiance=None: the calls and the bits above.  radiance together with ao: ValueError.  direct (a DirectLight):
+        the direct light of the scene's point, spot and directional lights, which no probe holds — _direct_term's frame, fw_bake_direct
+        on the records in place — is added in float32 to the linear frame of whichever branch ran and the sum resolved by fw_denoise
+        at 0 iterations; with ao, only the probes' term is multiplied by ao.  The call's stats are kept in self.direct_stats.
+        direct=None: the calls and the bits above."""
         import torch
         from . import _lib
+        if direct is not None:
+            direct.check()
         if depth is not None and moments is None:
             raise ValueError("depth needs the moments bake_probe_depth returned")
         if radiance is not None and maps is None:
@@ -3015,6 +3309,7 @@ class Renderer:
             d_pl = None
             if placement is not None:
                 d_pl = torch.from_numpy(np.ascontiguousarray(np.asarray(placement, np.float32).reshape(grid.n_probes, 4))).to(dev)
+            rays = None
             if ao is not None:
                 occ, _sums, self.ao_stats = ds.bake_ao(ao, aov[:, 8:11], aov[:, 4:7], None, ao_rounds, seed=s["seed"], use_bvh=s["use_bvh"],
                                                        flags=s["flags"])
@@ -3047,6 +3342,9 @@ class Renderer:
                 rgb8, gam, lin = _lib.probe_shade_vis(grid, d_sh, depth, d_mom, aov, w, h, normal_bias, s["gamma"], ds.device)
             else:
                 rgb8, gam, lin = _lib.probe_shade(grid, d_sh, aov, w, h, s["gamma"], ds.device)
+            if direct is not None:
+                term = self._direct_term(ds, direct, aov, model, rays)[0]
+                rgb8, gam, lin = _lib.denoise((lin.reshape(-1, 3) + term).contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
             stats = dict(ds.aovs_stats)
         finally:
             if ds is not scene:

@@ -19,6 +19,7 @@
 #include "fw_ao.h"
 #include "fw_probe_place.h"
 #include "fw_probe_radiance.h"
+#include "fw_direct.h"
 #include "fw_defer_pretest.h"
 
 #include <algorithm>
@@ -2077,13 +2078,9 @@ int check_lights_impl(const fw_light *lights, uint32_t n) {
     }
     return FW_OK;
 }
-int set_lights_impl(fw_scene *sc, const fw_light *lights, uint32_t n) {
-    if (!sc) return fail(FW_ERR_BAD_ARG, "null argument");
-    if (int rc = check_lights_impl(lights, n)) return rc;
-    if (n == 0) { sc->n_dlights = 0; return FW_OK; }
-    // (the shadow queue marks a point light's ray with fw::SHADOW_NEAR, which no emitter's object index may equal)
-    if (sc->d.n_objects >= fw::SHADOW_NEAR) return fail(FW_ERR_UNSUPPORTED, "too many objects for a scene with lights");
-    // fw::DDeltaLights.rec: (position, kind), (unit direction, cos_inner), (intensity, cos_outer); the direction normalised in double
+// fw::DDeltaLights.rec of checked lights (fw_scene_set_lights, fw_direct_rays, fw_direct_reduce): (position, kind), (unit direction,
+// cos_inner), (intensity, cos_outer); the direction normalised in double
+std::vector<float> light_records(const fw_light *lights, uint32_t n) {
     std::vector<float> rec((size_t)n * 12, 0.f);
     for (uint32_t i = 0; i < n; i++) {
         const fw_light &l = lights[i];
@@ -2095,6 +2092,15 @@ int set_lights_impl(fw_scene *sc, const fw_light *lights, uint32_t n) {
         r[7] = l.cos_inner;
         r[8] = l.intensity.x; r[9] = l.intensity.y; r[10] = l.intensity.z; r[11] = l.cos_outer;
     }
+    return rec;
+}
+int set_lights_impl(fw_scene *sc, const fw_light *lights, uint32_t n) {
+    if (!sc) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = check_lights_impl(lights, n)) return rc;
+    if (n == 0) { sc->n_dlights = 0; return FW_OK; }
+    // (the shadow queue marks a point light's ray with fw::SHADOW_NEAR, which no emitter's object index may equal)
+    if (sc->d.n_objects >= fw::SHADOW_NEAR) return fail(FW_ERR_UNSUPPORTED, "too many objects for a scene with lights");
+    const std::vector<float> rec = light_records(lights, n);
     const size_t bytes = rec.size() * 4, total = (bytes + 255) & ~(size_t)255;
     HIPCHK(hipSetDevice(sc->device));
     Workspace *ws = workspace_for(sc->device);
@@ -4915,6 +4921,171 @@ int bake_ao_impl(fw_scene *sc, const fw_ao *ao, const fw_trace_params *tp, uint3
     return FW_OK;
 }
 
+// ---- direct light of point, spot and directional lights at surface points (include/firework_hip.h) --------------------
+// A description's own argument checks (FW_ERR_BAD_ARG only)
+int direct_check(const fw_direct *dp) {
+    if (dp->lobe > 1u) return fail(FW_ERR_BAD_ARG, "lobe must be 0 or 1");
+    if (dp->face_view > 1u) return fail(FW_ERR_BAD_ARG, "face_view must be 0 or 1");
+    if (!std::isfinite(dp->bias) || dp->bias < 0.f) return fail(FW_ERR_BAD_ARG, "bias must be finite and >= 0");
+    return FW_OK;
+}
+// the checks of the points that the three calls share, after the description's and before the alignment's
+int direct_points_check(uint32_t n, uint32_t stride, const float *view, uint32_t view_stride, const float *spec) {
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (view && view_stride < 3) return fail(FW_ERR_BAD_ARG, "view_stride_floats must be >= 3");
+    if (spec && !view) return fail(FW_ERR_BAD_ARG, "spec needs view: a glossy point is lit towards the eye");
+    return FW_OK;
+}
+
+// Surface points with their optional view directions and spec records as Staged inputs (ao_points_stage's rule)
+struct DirectSlots { AoSlots pts; int view, spec; };
+DirectSlots direct_points_stage(Staged &st, uint32_t n, const float *positions, const float *normals, uint32_t stride, const uint32_t *ids,
+                                const float *view, uint32_t view_stride, const float *spec, uint64_t extent) {
+    DirectSlots s;
+    s.pts = ao_points_stage(st, n, positions, normals, stride, ids, extent);
+    s.view = st.add(Staged::IN, view, (size_t)((extent - 1u) * view_stride + 3u) * 4u);
+    s.spec = st.add(Staged::IN, spec, (size_t)extent * 16u);
+    return s;
+}
+fw::DDirect direct_device(const Staged &st, const DirectSlots &s, uint32_t stride, uint32_t view_stride, const fw_direct *dp, const float4 *lights,
+                          uint32_t n_lights, uint32_t first) {
+    fw::DDirect d{};
+    d.pts = fw::DDirectPoints{st.ptr<const float>(s.pts.pos), st.ptr<const float>(s.pts.nrm), st.ptr<const uint32_t>(s.pts.ids),
+                              st.ptr<const float>(s.view), st.ptr<const float4>(s.spec), stride, view_stride};
+    d.lights = lights; d.n_lights = n_lights; d.first = first;
+    d.lobe = dp->lobe; d.face_view = dp->face_view; d.bias = dp->bias;
+    return d;
+}
+
+// fw_direct_rays: fw_ao_rays' shape, plus the light records built on the host (fw_scene_set_lights' own) and staged with the points
+int direct_rays_impl(const fw_direct *dp, const fw_light *lights, uint32_t n_lights, int device, uint32_t n, const float *positions, const float *normals,
+                     uint32_t stride, const uint32_t *ids, const float *view, uint32_t view_stride, const float *spec, float *rays, int on_device,
+                     void *stream_) {
+    if (!dp || !lights || !positions || !normals || !rays) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = direct_check(dp)) return rc;
+    if (n_lights == 0) return fail(FW_ERR_BAD_ARG, "n_lights must be > 0");
+    if (int rc = check_lights_impl(lights, n_lights)) return rc;
+    if (int rc = direct_points_check(n, stride, view, view_stride, spec)) return rc;
+    if (on_device && (((uintptr_t)spec & 15u) || (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids | (uintptr_t)view | (uintptr_t)rays) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device spec must be 16-byte aligned, device positions, normals, ids, view and rays 4-byte aligned");
+    if ((uint64_t)n * n_lights >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x n_lights must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n_cus = device_cus(device);
+    const std::vector<float> rec = light_records(lights, n_lights);
+    Staged st(device, stream, on_device != 0);
+    const DirectSlots slots = direct_points_stage(st, n, positions, normals, stride, ids, view, view_stride, spec, on_device ? n : ao_extent(n, ids));
+    const int i_rec = st.add(Staged::IN, rec.data(), rec.size() * 4, true);
+    if (int rc = st.up()) return rc;
+    const float4 *d_rec = st.ptr<const float4>(i_rec);
+    if (on_device) {
+        fw::launch_direct_rays(stream, n_cus, direct_device(st, slots, stride, view_stride, dp, d_rec, n_lights, 0), n, rays);
+        return st.finish();
+    }
+    return host_slabs(stream, device, n, (size_t)n_lights * 24, rays, [&](uint32_t done, uint32_t k, float *d_rays) {
+        fw::launch_direct_rays(stream, n_cus, direct_device(st, slots, stride, view_stride, dp, d_rec, n_lights, done), k, d_rays);
+    });
+}
+
+// fw_direct_reduce: fw_ao_reduce's shape with the points and the light records it reads again
+int direct_reduce_impl(int device, const fw_direct *dp, const fw_light *lights, uint32_t n_lights, uint32_t n, const float *positions, const float *normals,
+                       uint32_t stride, const uint32_t *ids, const float *view, uint32_t view_stride, const float *spec, const float *rays,
+                       const fw_hit *hits, float *sums, int on_device, void *stream_) {
+    if (!dp || !lights || !positions || !normals || !rays || !hits || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = direct_check(dp)) return rc;
+    if (n_lights == 0) return fail(FW_ERR_BAD_ARG, "n_lights must be > 0");
+    if (int rc = check_lights_impl(lights, n_lights)) return rc;
+    if (int rc = direct_points_check(n, stride, view, view_stride, spec)) return rc;
+    if (on_device && ((((uintptr_t)sums | (uintptr_t)hits | (uintptr_t)spec) & 15u)
+                      || (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids | (uintptr_t)view | (uintptr_t)rays) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums, hits and spec must be 16-byte aligned, device positions, normals, ids, view and rays 4-byte aligned");
+    if ((uint64_t)n * n_lights >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x n_lights must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t entries = (size_t)n * n_lights;
+    const std::vector<float> rec = light_records(lights, n_lights);
+    const uint64_t extent = on_device ? n : ao_extent(n, ids);
+    Staged st(device, stream, on_device != 0);
+    const DirectSlots slots = direct_points_stage(st, n, positions, normals, stride, ids, view, view_stride, spec, extent);
+    const int i_rec = st.add(Staged::IN, rec.data(), rec.size() * 4, true), i_rays = st.add(Staged::IN, rays, entries * 24),
+              i_hits = st.add(Staged::IN, hits, entries * sizeof(fw_hit)), i_sums = st.add(Staged::INOUT, sums, on_device ? 0 : (size_t)extent * 32);
+    if (int rc = st.up()) return rc;
+    fw::launch_direct_reduce(stream, device_cus(device), direct_device(st, slots, stride, view_stride, dp, st.ptr<const float4>(i_rec), n_lights, 0), n,
+                             st.ptr<const float>(i_rays), st.ptr<const fw_hit>(i_hits), st.ptr<float>(i_sums));
+    return st.finish();
+}
+
+// fw_bake_direct: fw_bake_ao's shape — its own are the argument checks, the Staged arrays, k_direct_rays and k_direct_reduce as
+// trace_rounds' generator and reducer over the scene's own light records where they lie, and k_direct_resolve.  The scene is looked at
+// only after a device was found: Ln is the scene's, and a scene exists only where a device does.
+int bake_direct_impl(fw_scene *sc, const fw_direct *dp, const fw_trace_params *tp, uint32_t N, const float *positions, const float *normals,
+                     uint32_t stride, const uint32_t *ids, const float *view, uint32_t view_stride, const float *spec, uint32_t first_round,
+                     uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    if (!sc || !dp || !tp || !positions || !normals) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = direct_check(dp)) return rc;
+    if (int rc = direct_points_check(N, stride, view, view_stride, spec)) return rc;
+    if (rounds == 0) return fail(FW_ERR_BAD_ARG, "rounds must be > 0");
+    if ((uint64_t)first_round + rounds > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_round + rounds overflows");
+    if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
+    if (tp->on_device && ((((uintptr_t)sums | (uintptr_t)out | (uintptr_t)spec) & 15u)
+                          || (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids | (uintptr_t)view) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums, out and spec must be 16-byte aligned, device positions, normals, ids and view 4-byte aligned");
+    if (int rc = need_device()) return rc;
+    const uint32_t Ln = sc->n_dlights;
+    if ((uint64_t)N * Ln >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x the scene's lights must be below 2^31");
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)tp->stream;
+    const bool on_device = tp->on_device != 0;
+    const uint32_t chunk = std::min<uint32_t>(N, dp->chunk_points ? dp->chunk_points
+                                                                  : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)std::max(Ln, 1u) * 72)));
+    // how many records sums and out span: only scratch copies of them need it (a host caller's, or the sums nobody keeps)
+    uint64_t extent = N;
+    if (ids && (!on_device || !sums)) {
+        if (on_device) {
+            std::vector<uint32_t> h_ids(N);
+            HIPCHK(hipMemcpyAsync(h_ids.data(), ids, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            extent = ao_extent(N, h_ids.data());
+        } else extent = ao_extent(N, ids);
+    }
+    const size_t rec_bytes = (size_t)extent * 32;
+    Staged st(dev, stream, on_device);
+    const DirectSlots slots = direct_points_stage(st, N, positions, normals, stride, ids, view, view_stride, spec, extent);
+    const int i_rays = st.add(Staged::WORK, nullptr, (size_t)chunk * Ln * 24), i_hits = st.add(Staged::WORK, nullptr, (size_t)chunk * Ln * sizeof(fw_hit)),
+              i_sums = st.add_sums(sums, rec_bytes), i_out = st.add(ids ? Staged::INOUT : Staged::OUT, out, rec_bytes);      // (with ids, entries outside the list stay)
+    if (int rc = st.up()) return rc;
+    float *d_sums = st.ptr<float>(i_sums);
+    const int n_cus = device_cus(dev);
+    fw_stats total{};
+    const uint32_t *d_ids = st.ptr<const uint32_t>(slots.pts.ids);
+    if (Ln > 0) {
+        {   // the light records arrive on the upload stream: the first kernel here reads them before any trace has waited for them
+            Workspace *ws = workspace_for(dev);
+            if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
+            std::lock_guard<std::mutex> ws_guard(ws->mu);
+            if (ws->ev_upload) HIPCHK(hipStreamWaitEvent(stream, ws->ev_upload, 0));
+        }
+        const float4 *d_rec = (const float4 *)sc->dlights.p;
+        const TraceRounds b{N, Ln, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
+        if (int rc = trace_rounds(sc, tp, b, first_round, rounds, stats ? &total : nullptr,
+                [&](uint32_t, uint32_t q0, uint32_t k, float *rays) {
+                    fw::launch_direct_rays(stream, n_cus, direct_device(st, slots, stride, view_stride, dp, d_rec, Ln, q0), k, rays);
+                },
+                [&](uint32_t q0, uint32_t k, const float *rays, const fw_hit *hits) {
+                    fw::launch_direct_reduce(stream, n_cus, direct_device(st, slots, stride, view_stride, dp, d_rec, Ln, q0), k, rays, hits, d_sums);
+                }))
+            return rc;
+    }
+    if (int rc = st.download(i_sums)) return rc;
+    if (out) fw::launch_direct_resolve(stream, N, (double)((uint64_t)first_round + rounds), d_ids, d_sums, st.ptr<float>(i_out));
+    if (int rc = st.finish()) return rc;
+    stats_finish(stats, total, wall0);
+    return FW_OK;
+}
+
 // ---- probe radiance maps (include/firework_hip.h) ------------------------------------------------------------------
 // A radiance description's own argument checks (FW_ERR_BAD_ARG only) and what the kernels need of it
 int probe_radiance_check(const fw_probe_radiance *pr, fw::DProbeRadiance &d) {
@@ -5617,6 +5788,33 @@ int fw_bake_ao(fw_scene *scene, const fw_ao *ao, const fw_trace_params *tp, uint
     try { return bake_ao_impl(scene, ao, tp, n, positions, normals, stride_floats, ids, first_round, rounds, sums, out, stats); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_ao"); }
+}
+
+int fw_direct_rays(const fw_direct *direct, const fw_light *lights, uint32_t n_lights, int device, uint32_t n, const float *positions,
+                   const float *normals, uint32_t stride_floats, const uint32_t *ids, const float *view, uint32_t view_stride_floats,
+                   const float *spec, float *rays, int on_device, void *stream) {
+    try { return direct_rays_impl(direct, lights, n_lights, device, n, positions, normals, stride_floats, ids, view, view_stride_floats, spec, rays, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_direct_rays"); }
+}
+
+int fw_direct_reduce(int device, const fw_direct *direct, const fw_light *lights, uint32_t n_lights, uint32_t n, const float *positions,
+                     const float *normals, uint32_t stride_floats, const uint32_t *ids, const float *view, uint32_t view_stride_floats,
+                     const float *spec, const float *rays, const fw_hit *hits, float *sums, int on_device, void *stream) {
+    try {
+        return direct_reduce_impl(device, direct, lights, n_lights, n, positions, normals, stride_floats, ids, view, view_stride_floats, spec, rays, hits, sums,
+                                  on_device, stream);
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_direct_reduce"); }
+}
+
+int fw_bake_direct(fw_scene *scene, const fw_direct *direct, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
+                   uint32_t stride_floats, const uint32_t *ids, const float *view, uint32_t view_stride_floats, const float *spec,
+                   uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    try { return bake_direct_impl(scene, direct, tp, n, positions, normals, stride_floats, ids, view, view_stride_floats, spec, first_round, rounds, sums, out, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_direct"); }
 }
 
 int fw_probe_irradiance_vis(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias, int device,

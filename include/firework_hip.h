@@ -1128,6 +1128,106 @@ int fw_ao_reduce(int device, const fw_ao *ao, uint32_t n, const uint32_t *ids, c
 int fw_bake_ao(fw_scene *scene, const fw_ao *ao, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
                uint32_t stride_floats, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
 
+/* ---- direct light of point, spot and directional lights at surface points (additive at ABI 8) -------------------------
+   What probes and lightmaps lack: a light without area is hit by no ray, so nothing baked from rays holds it.  For each of n surface
+   points and each of Ln lights one shadow ray is made, traced by the ordinary walks against a resident scene, resolved by
+   fw_scene_set_lights' visibility rule and reduced per point.  Everything is float64 from the float32 inputs, every operation rounded as
+   written (no contraction).  api.direct_rays, api.direct_reduce and api.direct_resolve are the numpy statements.
+     Lights.  A light's record is what fw_scene_set_lights keeps: (position, kind), (direction, cos_inner), (intensity, cos_outer), twelve
+         float32, the direction divided by its float64 length and rounded to float32.  fw_bake_direct reads the resident scene's records;
+         the two stand-alone calls build them from a fw_light array with the same host code, after fw_check_lights' checks.
+     Points.  fw_bake_ao's addressing: point q of a call is id = ids ? ids[q] : q; position and normal three floats each at id x
+         stride_floats, stride_floats >= 3; ids an optional list of n distinct uint32; a point is unusable if a component of its position
+         or normal is not finite or its normal is (0, 0, 0).  fw_render_aovs' records are read in place with stride 12 (positions = aov
+         + 8, normals = aov + 4), fw_lightmap_texels' with stride 8 and the covered list.  view (may be NULL): the direction from the
+         eye, three floats at view + id x view_stride_floats — a ray buffer is read in place at rays + 3 with stride 6.  spec (may be
+         NULL, needs view): (F0.rgb, rho), four floats at spec + id x 4.  rho > 0: a glossy point (GgxMat); rho < 0: a point that takes no
+         light sample (Metal, Dielectric, Emissive, a miss); any other rho, or no spec: a diffuse point.  sums and out are records of 32 B
+         indexed by id; entries outside the list are never touched.  With host arrays and ids every array indexed by id spans max(ids)
+         + 1 entries.
+     Normal.  nh = the float32 normal divided by its float64 length; with view and face_view = 1 negated where nh . view > 0 (the dot
+         product as (x x + y y) + z z on the view as stored): the side the eye sees is the side that is lit.
+     Ray of point q and light i, entry q Ln + i, six floats rounded to float32 once: origin o = position + bias * nh (bias 0: the
+         position's bits); direction d = the light's position - o for a point or spot light (not normalised: the light sits at t = 1), d
+         = -(the record's direction) for a directional one.  With d2 = (dx dx + dy dy) + dz dz, w = d / sqrt(d2), c = nh . w and for a
+         spot s = smooth(-(w . axis)): smooth(x) = 1 if x >= cos_outer else 0 where cos_inner <= cos_outer, otherwise t t (3 - 2 t) with
+         t = min(max((x - cos_outer) / (cos_inner - cos_outer), 0), 1).  The entry is six zeros — which fw_trace_rays reports as a miss
+         and never traces — if the point is unusable; spec is given and rho < 0; the three intensities are 0; d2 is 0 or not finite; not
+         c > 0; a spot's s is 0; or a rounded component is not finite or the rounded direction is (0, 0, 0).
+     Reduction of one round.  Entry (q, i) is a function of the stored float32 ray, its hit h, the light's record, nh, view and spec.  It
+         contributes nothing if its stored direction is (0, 0, 0), the point is unusable or has rho < 0, a glossy point has no view or
+         not wo . nh > 0, d2 of the stored direction is not finite, or not c > 0 (d2, w, c, s as above, from the stored direction).
+         V = 1 if h.object == FW_NO_HIT; otherwise V = 1 iff the light is a point or spot light and h.t >= 1.0f; V = 0 contributes
+         nothing more.  L = (I s) / d2 for a point or spot light (s = 1 for a point light), L = I for a directional one.
+           N += 1.
+           diffuse point:  E_k += L_k g,  g = c (lobe 0: E is an irradiance) or 2 ((c c) c) (lobe 1: pi x what fw_scene_set_lights'
+               light sample adds per unit albedo at a Lambertian vertex, whose density is 2 c^3 / pi).
+           glossy point:   S_k += L_k ((F0_k + (1 - F0_k) m5) gg): GgxMat's f cos = F D G2 / (4 wo . n) with wo = -(view / |view|), co =
+               nh . wo, alpha = (double)(rho * rho) (the float32 product), a2 = alpha alpha, tan2(x, z) = |x - z nh|^2 / (z z),
+               Lambda(x, z) = 0.5 (sqrt(1 + a2 tan2(x, z)) - 1), h = (wo + w) / |wo + w|, hn = nh . h, oh = wo . h,
+               sd = |h - hn nh|^2 + a2 (hn hn), D = a2 / (pi (sd sd)), gg = (D / (4 co)) / ((1 + Lambda(wo, co)) + Lambda(w, c)),
+               m = 1 - oh, m5 = ((m m)(m m)) m.  A conductor has no diffuse term: E gets nothing.
+         Seven float64 accumulators per point (E.rgb, N, S.rgb).  With G = the smallest power of two >= min(Ln, 64), partial sum l takes
+         i = l, l + G, ... in ascending order from 0, and the G partial sums are added by an xor butterfly over the distances G/2 ... 1
+         (x_l <- x_l + x_(l xor m)): k_ao_reduce's tree with "directions" read as "lights".  Each accumulator is rounded to float32 once
+         and added with one float32 addition to sums[id] = (E.rgb, N), (S.rgb, untouched): the eighth float is never written.  Two runs
+         are bit-equal; a point's result depends on no other point.
+     Resolve, R = the number of rounds in sums: out[id] = float((double)sums[id] / R) for the seven floats, the eighth 0.  Rounds exist
+         because a ConstantMedium makes visibility a draw (round r traces with seed + r); without media every round is the same and one
+         is exact.  An unusable point resolves to zeros. */
+typedef struct fw_direct {
+    uint32_t lobe;            /* 0 cosine (irradiance), 1 the renderer's diffuse lobe 2 c^3 */
+    uint32_t face_view;       /* 0 / 1; ignored without view */
+    float    bias;            /* >= 0, finite */
+    uint32_t chunk_points;    /* fw_bake_direct: points per chunk; 0 = as many as fit 256 MiB at 72 B per ray, at least one */
+} fw_direct;
+
+/* fw_direct_rays: the n x Ln x 6 floats of the shadow rays.  Host arrays — staged through device allocations of the call's own, freed
+   on every path — or with on_device device arrays on `device` (lights is always a host array), generated on `stream` and complete on
+   return.  Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL direct, lights, positions, normals or rays; lobe
+   > 1, face_view > 1, bias negative or not finite; n_lights == 0, then fw_check_lights' refusals with its messages; n == 0;
+   stride_floats < 3; view with view_stride_floats < 3; spec without view (whether an entry has rho > 0 cannot be checked on device
+   arrays); with on_device spec not 16-byte aligned or another array not 4-byte aligned; FW_ERR_UNSUPPORTED for n x Ln >= 2^31; then
+   FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last one. */
+int fw_direct_rays(const fw_direct *direct, const fw_light *lights, uint32_t n_lights, int device, uint32_t n, const float *positions,
+                   const float *normals, uint32_t stride_floats, const uint32_t *ids, const float *view, uint32_t view_stride_floats,
+                   const float *spec, float *rays, int on_device, void *stream);
+
+/* fw_direct_reduce: adds one round's reduction to the running sums.  rays: n x Ln x 6 floats; hits: n x Ln records as fw_trace_rays
+   wrote them for those rays; sums: records of 32 B indexed by id.  Host or device arrays as fw_direct_rays.  Errors, in this order and
+   before HIP is called: FW_ERR_BAD_ARG for a NULL direct, lights, positions, normals, rays, hits or sums; then fw_direct_rays' checks
+   from lobe to spec without view; with on_device sums, hits or spec not 16-byte aligned or another array not 4-byte aligned;
+   FW_ERR_UNSUPPORTED for n x Ln >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last one. */
+int fw_direct_reduce(int device, const fw_direct *direct, const fw_light *lights, uint32_t n_lights, uint32_t n, const float *positions,
+                     const float *normals, uint32_t stride_floats, const uint32_t *ids, const float *view, uint32_t view_stride_floats,
+                     const float *spec, const float *rays, const fw_hit *hits, float *sums, int on_device, void *stream);
+
+/* fw_bake_direct: the rounds [first_round, first_round + rounds) of the n points under the resident scene's own lights
+   (fw_scene_set_lights), read on the device where they lie.  Of tp, use_bvh, flags, seed, rays_per_batch, on_device (for positions,
+   normals, ids, view, spec, sums and out) and stream are read; key_base is ignored.  For each round r and each chunk of points [q0, q1)
+   (direct->chunk_points at a time): k_direct_rays fills device scratch that the call allocates and frees on every path; the rays are
+   traced exactly as fw_trace_rays would with on_device = 1, key_base = q0 Ln and seed = tp->seed + r; k_direct_reduce adds the chunk
+   into sums.  k_direct_resolve finishes.  On an error the stream is drained.  A scene without lights returns FW_OK, traces nothing,
+   leaves sums as it was and writes out from it.
+     sums: the running sums of the rounds [0, first_round) — zeros when first_round is 0 — to which this call's rounds are added in
+           order; NULL only when first_round == 0.
+     out : the resolved records after first_round + rounds rounds; may be NULL.
+   Contracts.  Composition: for every chunk_points, sums equals bit for bit what fw_direct_rays, fw_trace_rays (on_device, seed + r,
+   key_base 0) and fw_direct_reduce give when chained by hand over all n points with the scene's lights.  Progressive: k calls of m rounds
+   leave the sums and out of one call of k m rounds, bit for bit.  Renders, and the frame graph's key, are left as fw_trace_rays leaves
+   them.
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, direct, tp, positions or
+   normals; lobe > 1, face_view > 1, a bad bias; n == 0; stride_floats < 3; view with view_stride_floats < 3; spec without view; rounds
+   == 0; first_round + rounds >= 2^32; a NULL sums with first_round > 0; with on_device sums, out or spec not 16-byte aligned, another
+   array not 4-byte aligned; then FW_ERR_NO_DEVICE; then — Ln is the scene's, and a scene exists only where a device does —
+   FW_ERR_UNSUPPORTED for n x Ln >= 2^31.
+   stats (may be NULL): fw_bake_ao's — fw_trace_rays' fields summed over rounds and chunks (rays = the rays traced: zero rays are
+   not); ms_render includes the two kernels' launches (under FW_FLAG_TIME_KERNELS ms_raygen and ms_accumulate as well); ms_wall covers
+   the whole call.  Synchronisation and what a trace leaves of renders are fw_trace_rays'. */
+int fw_bake_direct(fw_scene *scene, const fw_direct *direct, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
+                   uint32_t stride_floats, const uint32_t *ids, const float *view, uint32_t view_stride_floats, const float *spec,
+                   uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
+
 /* ---- probe relocation and classification: move probes out of geometry (additive at ABI 8) -----------------------------
    A grid is laid over a scene without looking at it: some probes land inside objects or a hair from a wall.  A probe's own rays tell:
    fw_probe_survey reduces one round's hits to "how much of what the probe sees is a back face, and where is the nearest surface",
