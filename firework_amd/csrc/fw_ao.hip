@@ -16,14 +16,12 @@
 // No atomics, no inline assembly; k_ao_rays alone uses LDS (1536 B) and a barrier.  A point's result depends on no other point and not
 // on the launch geometry; two runs are bit-equal.
 //
-// A file of its own, last on the link line: the code objects of the other files stay byte for byte what they were.  What it needs of
-// fw_lightmap.hip (hash32, the lattice, the frame) is restated here: the same bits.
+// What it has in common with fw_lightmap.hip (the jitter draw, the lattice, the frame, grid_for) is fw_shared.h's.
 //
 // Numerics: -ffp-contract=off, so + - * / round as written and in the order of api.ao_rays / api.ao_reduce / api.ao_resolve; sin, cos
 // and sqrt are the device library's float64 functions.
 #include "fw_ao.h"
-#include <algorithm>
-#include <cmath>
+#include "fw_shared.h"
 
 namespace fw {
 namespace {
@@ -32,18 +30,10 @@ constexpr int AO_BLOCK = 256;
 constexpr int AO_WAVES = AO_BLOCK / 64;
 constexpr int AR_BLOCK = 64;
 
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.40282347e+38f; }   // false for NaN and +-inf
-
 __global__ __launch_bounds__(AR_BLOCK) void k_ao_rays(DAoRays R, uint32_t n_entries, float *__restrict__ out) {
     __shared__ float tr[6 * 64];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_chunks = (n_entries + 63u) / 64u;                                    // n_entries < 2^31
-    const double PI = 3.141592653589793, G = 0.6180339887498949;                        // G = (sqrt(5) - 1) / 2
     const double Dd = (double)R.directions;
     for (uint32_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const uint32_t id0 = c * 64u;
@@ -53,41 +43,20 @@ __global__ __launch_bounds__(AR_BLOCK) void k_ao_rays(DAoRays R, uint32_t n_entr
             const uint32_t q = i / R.directions, j = i - q * R.directions;
             const uint32_t id = R.pts.ids ? R.pts.ids[(size_t)R.first + q] : R.first + q;
             double xi_u = 0.5, xi_v = 0.5;
-            if (R.jitter) {
-                const uint32_t key = hash32(R.seed32 ^ hash32(R.round + 0x9E3779B9u));
-                xi_u = (double)(hash32(hash32(2u * id) ^ key) >> 8) * 0x1p-24;
-                xi_v = (double)(hash32(hash32(2u * id + 1u) ^ key) >> 8) * 0x1p-24;
-            }
+            if (R.jitter) { const Jitter xi = jitter_pair(R.seed32, R.round, id); xi_u = xi.u; xi_v = xi.v; }
             const float *pp = R.pts.positions + (size_t)id * R.pts.stride, *pn = R.pts.normals + (size_t)id * R.pts.stride;
             const float px = pp[0], py = pp[1], pz = pp[2], fx = pn[0], fy = pn[1], fz = pn[2];
-            const double u = ((double)j + xi_u) / Dd;
-            const double r = sqrt(u);
-            const double cz = sqrt(fmax(0.0, 1.0 - u));
-            const double t = (double)j * G + xi_v;
-            const double phi = (2.0 * PI) * (t - floor(t));
-            const double lx = r * cos(phi), ly = r * sin(phi);
-            // the float32 normal made unit again in float64: the frame is then orthonormal to float64 and d unit to one float32 rounding
-            const double rx = (double)fx, ry = (double)fy, rz = (double)fz;
-            const double rl2 = (rx * rx + ry * ry) + rz * rz;
-            const double rl = sqrt(rl2);
-            const double nx = rx / rl, ny = ry / rl, nz = rz / rl;
-            const double s = copysign(1.0, nz);
-            const double a = -1.0 / (s + nz);
-            const double b = (nx * ny) * a;
-            const double tx = 1.0 + (s * (nx * nx)) * a, ty = s * b, tz = -s * nx;
-            const double bx = b, by = s + (ny * ny) * a, bz = -ny;
-            const bool usable = finite_f(px) && finite_f(py) && finite_f(pz) && finite_f(fx) && finite_f(fy) && finite_f(fz) && rl2 > 0.0;
+            const CosineDir cd = cosine_dir(j, Dd, xi_u, xi_v, fx, fy, fz);
+            const bool usable = finite_f(px) && finite_f(py) && finite_f(pz) && finite_f(fx) && finite_f(fy) && finite_f(fz) && cd.rl2 > 0.0;
             float *d = tr + lane * 6u;
             if (!usable) { d[0] = 0.f; d[1] = 0.f; d[2] = 0.f; d[3] = 0.f; d[4] = 0.f; d[5] = 0.f; }
             else {
                 if (R.bias == 0.f) { d[0] = px; d[1] = py; d[2] = pz; }
                 else {
                     const double bd = (double)R.bias;
-                    d[0] = (float)((double)px + bd * nx); d[1] = (float)((double)py + bd * ny); d[2] = (float)((double)pz + bd * nz);
+                    d[0] = (float)((double)px + bd * cd.nx); d[1] = (float)((double)py + bd * cd.ny); d[2] = (float)((double)pz + bd * cd.nz);
                 }
-                d[3] = (float)((lx * tx + ly * bx) + cz * nx);
-                d[4] = (float)((lx * ty + ly * by) + cz * ny);
-                d[5] = (float)((lx * tz + ly * bz) + cz * nz);
+                d[3] = (float)cd.dx; d[4] = (float)cd.dy; d[5] = (float)cd.dz;
             }
         }
         __syncthreads();
@@ -149,11 +118,6 @@ __global__ __launch_bounds__(AO_BLOCK) void k_ao_resolve(uint32_t n, double roun
         o.w = (float)fmin(1.0, fmax(0.0, 1.0 - (double)s.w / rounds));
         out[id] = o;
     }
-}
-
-inline uint32_t grid_for(uint64_t items, uint32_t per_block, int n_cus, uint32_t per_cu) {
-    const uint64_t want = (items + per_block - 1u) / per_block;
-    return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(want, (uint64_t)std::max(1, n_cus) * per_cu));
 }
 
 } // namespace

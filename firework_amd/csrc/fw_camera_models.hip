@@ -8,25 +8,20 @@
 // wave stores the block as six dword stores per lane at consecutive addresses (k_camera_rays' transposition in fw_kernels.hip): every store
 // instruction covers 256 contiguous bytes instead of 64 lanes 24 bytes apart.  Dword stores, not wider ones: a sample's slab starts at
 // s * W*H * 24 bytes, which is 16-byte aligned only for an even W*H.
-// One wave per workgroup, so the barrier orders the LDS accesses only.  No atomics, no inline assembly.  A file of its own: the code objects
-// of fw_kernels.hip and fw_build.hip stay byte for byte what they were.
+// One wave per workgroup, so the barrier orders the LDS accesses only.  No atomics, no inline assembly.  The jitter draw and grid_for are
+// fw_shared.h's.
 //
 // Numerics: -ffp-contract=off, so + - * / round as written and in the order of api.panorama_rays / orthographic_rays / fisheye_rays;
 // sin, cos and sqrt are the device library's float64 functions, a few float64 ulps from the host's: after the rounding to float32 a
 // component equals the host's or is its neighbour.
 #include "../../include/firework_hip.h"     // FW_MODEL_*
 #include "fw_camera_models.h"
-#include <algorithm>
+#include "fw_shared.h"
 
 namespace fw {
 namespace {
 
 constexpr int MR_BLOCK = 64;
-
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return x;
-}
 
 __global__ __launch_bounds__(MR_BLOCK) void k_model_rays(DModel m, uint32_t first, uint32_t n_samples, uint32_t n_pix, uint32_t chunks_per_sample,
                                                          float *__restrict__ out) {
@@ -42,11 +37,7 @@ __global__ __launch_bounds__(MR_BLOCK) void k_model_rays(DModel m, uint32_t firs
             const uint32_t p = id0 + lane;
             const uint32_t row = p / m.width, x = p - row * m.width;
             double xi_x = 0.5, xi_y = 0.5;
-            if (m.jitter) {
-                const uint32_t key = hash32(m.seed32 ^ hash32(first + s + 0x9E3779B9u));
-                xi_x = (double)(hash32(hash32(2u * p) ^ key) >> 8) * 0x1p-24;
-                xi_y = (double)(hash32(hash32(2u * p + 1u) ^ key) >> 8) * 0x1p-24;
-            }
+            if (m.jitter) { const Jitter xi = jitter_pair(m.seed32, first + s, p); xi_x = xi.u; xi_y = xi.v; }
             const double px = (double)x + xi_x, py = (double)row + xi_y;
             const double W = (double)m.width, H = (double)m.height;
             double o0 = m.pos[0], o1 = m.pos[1], o2 = m.pos[2], d0, d1, d2;
@@ -90,8 +81,7 @@ void launch_model_rays(hipStream_t stream, int n_cus, const DModel &m, uint32_t 
     const uint32_t n_pix = m.width * m.height;                               // < 2^31
     const uint32_t cps = (n_pix + 63u) / 64u;
     const uint64_t chunks = (uint64_t)n * cps;
-    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(chunks, (uint64_t)std::max(1, n_cus) * 128u));
-    hipLaunchKernelGGL(k_model_rays, dim3(blocks), dim3(MR_BLOCK), 0, stream, m, first, n, n_pix, cps, out);
+    hipLaunchKernelGGL(k_model_rays, dim3(grid_for(chunks, 1u, n_cus, 128u)), dim3(MR_BLOCK), 0, stream, m, first, n, n_pix, cps, out);
 }
 
 } // namespace fw

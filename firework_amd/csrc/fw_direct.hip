@@ -19,13 +19,12 @@
 // No atomics, no inline assembly; k_direct_rays alone uses LDS (18 KiB) and barriers.  Every index is formed from q < n and i < Ln; no load
 // depends on the content of a record.  A point's result depends on no other point and not on the launch geometry; two runs are bit-equal.
 //
-// A file of its own, last on the link line: the code objects of the other files stay byte for byte what they were.
+// finite_f and grid_for are fw_shared.h's.
 //
 // Numerics: -ffp-contract=off, so + - * / round as written and in the order of api.direct_rays / api.direct_reduce / api.direct_resolve;
 // sqrt is the device library's float64 function.
 #include "fw_direct.h"
-#include <algorithm>
-#include <cmath>
+#include "fw_shared.h"
 
 namespace fw {
 namespace {
@@ -35,7 +34,6 @@ constexpr int DR_TILE = 256;                     // light records per LDS tile
 constexpr int DD_BLOCK = 256;
 constexpr int DD_WAVES = DD_BLOCK / 64;
 
-__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.40282347e+38f; }   // false for NaN and +-inf
 __device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }
 __device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) { return (ax * bx + ay * by) + az * bz; }
 
@@ -226,11 +224,6 @@ __global__ __launch_bounds__(DD_BLOCK) void k_direct_resolve(uint32_t n, double 
                                            (float)((double)a.w / rounds));
         out[2u * (size_t)id + 1u] = make_float4((float)((double)b.x / rounds), (float)((double)b.y / rounds), (float)((double)b.z / rounds), 0.f);
     }
-}
-
-inline uint32_t grid_for(uint64_t items, uint32_t per_block, int n_cus, uint32_t per_cu) {
-    const uint64_t want = (items + per_block - 1u) / per_block;
-    return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(want, (uint64_t)std::max(1, n_cus) * per_cu));
 }
 
 } // namespace

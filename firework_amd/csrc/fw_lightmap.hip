@@ -16,14 +16,12 @@
 //   k_lm_resolve   irradiance = sums / rounds on covered texels with a = 1, zero elsewhere.
 //   k_lm_dilate    one dilation pass, one lane per texel, from one buffer to the other.
 //
-// A file of its own, after the others on the link line: the code objects of fw_kernels.hip, fw_build.hip, fw_temporal.hip,
-// fw_camera_models.hip and fw_probes.hip stay byte for byte what they were.
+// The jitter draw, the cosine lattice with its tangent frame (k_ao_rays uses the same) and grid_for are fw_shared.h's.
 //
 // Numerics: -ffp-contract=off, so + - * / round as written and in the order of api.Lightmap's numpy statements; sin, cos and sqrt are the
 // device library's float64 functions, a few float64 ulps from the host's.
 #include "fw_lightmap.h"
-#include <algorithm>
-#include <cmath>
+#include "fw_shared.h"
 
 namespace fw {
 namespace {
@@ -31,11 +29,6 @@ namespace {
 constexpr int LM_BLOCK = 256;
 constexpr int LM_WAVES = LM_BLOCK / 64;
 constexpr int LR_BLOCK = 64;
-
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return x;
-}
 
 // the edge function of the header: ((bu - au) (pv - av)) - ((bv - av) (pu - au)), every operation rounded in float64
 __device__ __forceinline__ double edge(double au, double av, double bu, double bv, double pu, double pv) {
@@ -139,7 +132,6 @@ __global__ __launch_bounds__(LR_BLOCK) void k_lm_rays(DLightmapRays R, uint32_t 
     __shared__ float tr[6 * 64];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_chunks = (n_entries + 63u) / 64u;                                    // n_entries < 2^31
-    const double PI = 3.141592653589793, G = 0.6180339887498949;                        // G = (sqrt(5) - 1) / 2
     const double Dd = (double)R.directions;
     for (uint32_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const uint32_t id0 = c * 64u;
@@ -149,36 +141,16 @@ __global__ __launch_bounds__(LR_BLOCK) void k_lm_rays(DLightmapRays R, uint32_t 
             const uint32_t q = i / R.directions, j = i - q * R.directions;
             const uint32_t texel = R.texel_ids[q];                                        // 2 texel + 1 < 2^32: W x H <= 2^28
             double xi_u = 0.5, xi_v = 0.5;
-            if (R.jitter) {
-                const uint32_t key = hash32(R.seed32 ^ hash32(R.round + 0x9E3779B9u));
-                xi_u = (double)(hash32(hash32(2u * texel) ^ key) >> 8) * 0x1p-24;
-                xi_v = (double)(hash32(hash32(2u * texel + 1u) ^ key) >> 8) * 0x1p-24;
-            }
+            if (R.jitter) { const Jitter xi = jitter_pair(R.seed32, R.round, texel); xi_u = xi.u; xi_v = xi.v; }
             const float4 rp = R.records[(size_t)texel * 2u], rn = R.records[(size_t)texel * 2u + 1u];
-            const double u = ((double)j + xi_u) / Dd;
-            const double r = sqrt(u);
-            const double cz = sqrt(fmax(0.0, 1.0 - u));
-            const double t = (double)j * G + xi_v;
-            const double phi = (2.0 * PI) * (t - floor(t));
-            const double lx = r * cos(phi), ly = r * sin(phi);
-            // the float32 normal made unit again in float64: the frame is then orthonormal to float64 and d unit to one float32 rounding
-            const double rx = (double)rn.x, ry = (double)rn.y, rz = (double)rn.z;
-            const double rl = sqrt((rx * rx + ry * ry) + rz * rz);
-            const double nx = rx / rl, ny = ry / rl, nz = rz / rl;
-            const double s = copysign(1.0, nz);
-            const double a = -1.0 / (s + nz);
-            const double b = (nx * ny) * a;
-            const double tx = 1.0 + (s * (nx * nx)) * a, ty = s * b, tz = -s * nx;
-            const double bx = b, by = s + (ny * ny) * a, bz = -ny;
+            const CosineDir cd = cosine_dir(j, Dd, xi_u, xi_v, rn.x, rn.y, rn.z);
             float *d = tr + lane * 6u;
             if (R.bias == 0.f) { d[0] = rp.x; d[1] = rp.y; d[2] = rp.z; }
             else {
                 const double bd = (double)R.bias;
-                d[0] = (float)((double)rp.x + bd * nx); d[1] = (float)((double)rp.y + bd * ny); d[2] = (float)((double)rp.z + bd * nz);
+                d[0] = (float)((double)rp.x + bd * cd.nx); d[1] = (float)((double)rp.y + bd * cd.ny); d[2] = (float)((double)rp.z + bd * cd.nz);
             }
-            d[3] = (float)((lx * tx + ly * bx) + cz * nx);
-            d[4] = (float)((lx * ty + ly * by) + cz * ny);
-            d[5] = (float)((lx * tz + ly * bz) + cz * nz);
+            d[3] = (float)cd.dx; d[4] = (float)cd.dy; d[5] = (float)cd.dz;
         }
         __syncthreads();
         float *dst = out + (size_t)id0 * 6u;
@@ -252,11 +224,6 @@ __global__ __launch_bounds__(LM_BLOCK) void k_lm_dilate(uint32_t width, uint32_t
         }
         out[id] = o;
     }
-}
-
-inline uint32_t grid_for(uint64_t items, uint32_t per_block, int n_cus, uint32_t per_cu) {
-    const uint64_t want = (items + per_block - 1u) / per_block;
-    return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(want, (uint64_t)std::max(1, n_cus) * per_cu));
 }
 
 } // namespace

@@ -1,7 +1,8 @@
-// fw_probe_place.h — what the host runtime (fw_runtime.cpp) and the probe-placement kernels (fw_probe_place.hip) share.  A header of its
-// own, so that the translation units of the other kernel files read exactly what they read before.
+// fw_probe_place.h — what the host runtime (fw_runtime.cpp) and the probe-placement kernels (fw_probe_place.hip) share.
+// The lookups over placed probes are fw_probe_lookup.h's.
 #pragma once
-#include "fw_probe_depth.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace fw {
 
@@ -21,12 +22,5 @@ void launch_probe_survey(hipStream_t stream, int n_cus, uint32_t n, uint32_t dir
 // writes placement[p].w only.
 void launch_probe_relocate_step(hipStream_t stream, const DRelocate &rl, uint32_t n, uint32_t directions, const float *survey, float *placement,
                                 int move);
-
-// launch_probe_irradiance_vis and launch_probe_shade_vis (fw_probe_depth.h) over moved and classified probes: the same arguments, and
-// placement (n_probes x 4 floats, device memory, 4-byte aligned).  v == NULL: no visibility weight.
-void launch_probe_irradiance_placed(hipStream_t stream, const DProbeGrid &g, const DProbeVis *v, const float *sh, const float *placement, uint32_t n,
-                                    const float *positions, const float *normals, uint32_t stride_floats, float *irradiance);
-void launch_probe_shade_placed(hipStream_t stream, const DProbeGrid &g, const DProbeVis *v, const float *sh, const float *placement, uint32_t n,
-                               const float *aov, float gamma, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb);
 
 } // namespace fw

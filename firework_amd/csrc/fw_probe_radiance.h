@@ -1,7 +1,7 @@
-// fw_probe_radiance.h — what the host runtime (fw_runtime.cpp) and the probe-radiance kernels (fw_probe_radiance.hip) share.  A header of
-// its own, so that the translation units of the other .hip files read exactly what they read before.
+// fw_probe_radiance.h — what the host runtime (fw_runtime.cpp) and the probe-radiance kernels (fw_probe_radiance.hip) share (DESIGN.md
+// §9v).
 #pragma once
-#include "fw_probe_depth.h"
+#include "fw_probe_lookup.h"    // DProbeGrid, DProbeVis
 
 namespace fw {
 

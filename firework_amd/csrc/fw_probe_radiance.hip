@@ -23,16 +23,13 @@
 // Every maps index is formed from a clamped cell index and texel indices clamped to [0, R_l - 2] plus 0 or 1, so no load leaves the
 // arrays wherever the point lies and whatever the maps hold.  No inline assembly anywhere.
 //
-// A file of its own, last on the link line: the code objects of the other files stay byte for byte what they were.  What it needs of
-// fw_probe_depth.hip (the texel centres, sgn, the fold, the bilinear fetch), of fw_probe_place.hip (the placed corner weights and the SH
-// sum) and of fw_kernels.hip (fdiv, resolve_pixel) is restated here: the same bits.
+// The corner weights, the SH sum and the diffuse shade step are fw_probe_corners.h's (the placed statement: PLACED, with NULL for "no
+// placement"); the texel centres, the octahedral fold and the float32 tail are fw_shared.h's.
 //
 // Numerics: -ffp-contract=off, so + - * / round as written and in the order of api.probe_radiance_reduce / _prefilter / _lookup; floor,
 // min, max and fabs are exact; sqrt is the device library's float64 function.
 #include "fw_probe_radiance.h"
-#include "fw_libm.h"
-#include <algorithm>
-#include <cmath>
+#include "fw_probe_corners.h"
 
 namespace fw {
 namespace {
@@ -42,25 +39,6 @@ constexpr int PR_MAXT = 4;                      // reduce: texels per lane at R 
 constexpr int PF_MAXO = 2;                      // prefilter: output texels per lane at R = 32, four levels (256 + 64 + 16 = 336)
 constexpr int PF_MAXSRC = 32 * 32;              // prefilter: source texels at R = 32
 constexpr int PL_BLOCK = 256;                   // the lookup and the shade
-
-__device__ __forceinline__ double sgn1(double v) { return v >= 0.0 ? 1.0 : -1.0; }      // sgn(0) = +1
-
-// texel t = b R + a of an R x R octahedral map: its centre on the octahedron (x, y, z) and that point's length
-__device__ __forceinline__ double texel_point(uint32_t t, uint32_t R, double &x, double &y, double &z) {
-    const uint32_t b = t / R, a = t - b * R;
-    const double Rd = (double)R;
-    const double ex = (((double)a + 0.5) * 2.0) / Rd - 1.0, ey = (((double)b + 0.5) * 2.0) / Rd - 1.0;
-    z = (1.0 - fabs(ex)) - fabs(ey);
-    x = ex; y = ey;
-    if (z < 0.0) { x = (1.0 - fabs(ey)) * sgn1(ex); y = (1.0 - fabs(ex)) * sgn1(ey); }
-    return sqrt((x * x + y * y) + z * z);
-}
-// the unit direction of that texel (fw_probe_depth.hip's texel_dir)
-__device__ __forceinline__ void texel_dir(uint32_t t, uint32_t R, double T[3]) {
-    double x, y, z;
-    const double l = texel_point(t, R, x, y, z);
-    T[0] = x / l; T[1] = y / l; T[2] = z / l;
-}
 
 __global__ __launch_bounds__(PR_BLOCK) void k_probe_radiance_reduce(uint32_t n_probes, uint32_t directions, uint32_t R, uint32_t k, double samples,
                                                                     const float *__restrict__ rays, const float4 *__restrict__ accum,
@@ -216,39 +194,6 @@ __global__ __launch_bounds__(PR_BLOCK) void k_probe_radiance_prefilter(uint32_t 
     }
 }
 
-// the constants of fw_probe_lookup.hip's LookupConst, restated
-struct RadConst { double y0, c1, c2, c6, c8, a0, a1, a2; };
-
-__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.40282347e+38f; }   // false for NaN and +-inf
-
-// where a unit direction falls in an R x R octahedral map: the first texel (column iu, row jv, both in [0, R - 2] whatever the
-// direction is) of the four that the bilinear fetch reads, and the fractions (fw_probe_depth.hip's depth_fetch)
-__device__ __forceinline__ void octa_cell(uint32_t R, double x, double y, double z, uint32_t &iu, uint32_t &jv, double &fu, double &fv) {
-    const double s1 = (fabs(x) + fabs(y)) + fabs(z);
-    double ox = x / s1, oy = y / s1;
-    if (z < 0.0) {
-        const double fx = (1.0 - fabs(oy)) * sgn1(ox), fy = (1.0 - fabs(ox)) * sgn1(oy);
-        ox = fx; oy = fy;
-    }
-    const double Rd = (double)R, top = Rd - 1.0;
-    const double su = fmin(fmax(((ox + 1.0) * 0.5) * Rd - 0.5, 0.0), top), sv = fmin(fmax(((oy + 1.0) * 0.5) * Rd - 0.5, 0.0), top);
-    const double i = fmin(floor(su), top - 1.0), j = fmin(floor(sv), top - 1.0);         // fmin and fmax drop a NaN: still in [0, R - 2]
-    fu = su - i; fv = sv - j;
-    iu = (uint32_t)i; jv = (uint32_t)j;
-}
-
-// depth_fetch of fw_probe_depth.hip over octa_cell
-__device__ __forceinline__ void depth_fetch(const float *__restrict__ m, uint32_t R, double x, double y, double z, double &mu, double &mu2) {
-    uint32_t iu, jv;
-    double fu, fv;
-    octa_cell(R, x, y, z, iu, jv, fu, fv);
-    const float *__restrict__ r0 = m + ((size_t)(jv * R + iu)) * 2u;
-    const float *__restrict__ r1 = r0 + (size_t)R * 2u;
-    const double gu = 1.0 - fu, gv = 1.0 - fv;
-    mu = (((double)r0[0] * gu + (double)r0[2] * fu) * gv) + (((double)r1[0] * gu + (double)r1[2] * fu) * fv);
-    mu2 = (((double)r0[1] * gu + (double)r0[3] * fu) * gv) + (((double)r1[1] * gu + (double)r1[3] * fu) * fv);
-}
-
 // the rgb of one level (R x R texels of 16 B at `m`) along the unit direction (x, y, z): bilinear, edges clamped; the flags are not read
 __device__ __forceinline__ void radiance_fetch(const float4 *__restrict__ m, uint32_t R, double x, double y, double z, double c[3]) {
     uint32_t iu, jv;
@@ -263,144 +208,9 @@ __device__ __forceinline__ void radiance_fetch(const float4 *__restrict__ m, uin
     c[2] = (((double)t00.z * gu + (double)t10.z * fu) * gv) + (((double)t01.z * gu + (double)t11.z * fu) * fv);
 }
 
-// The corner weights of fw_probe_place.hip's probe_lookup_placed, restated: the unit normal, the probes of the cell's corners, the
-// weights of the active ones and their sum.  placement NULL: every record is (0, 0, 0, 1).
-struct Corners {
-    double x, y, z;             // the unit normal
-    double w[8], wsum;
-    uint32_t probe[8], active;
-    bool usable;                // the position and the normal are finite and the normal is not zero
-};
-
-template <bool DEPTH>
-__device__ __forceinline__ bool corner_weights(const DProbeGrid &G, const DProbeVis &V, const float *__restrict__ placement, float pxf, float pyf,
-                                               float pzf, float nxf, float nyf, float nzf, Corners &C) {
-    C.usable = false;
-    if (!(finite_f(pxf) && finite_f(pyf) && finite_f(pzf) && finite_f(nxf) && finite_f(nyf) && finite_f(nzf))) return false;
-    const double p[3] = {(double)pxf, (double)pyf, (double)pzf};
-    const double nx = (double)nxf, ny = (double)nyf, nz = (double)nzf;
-    const double nl2 = (nx * nx + ny * ny) + nz * nz;
-    if (!(nl2 > 0.0)) return false;
-    const double nl = sqrt(nl2);
-    const double x = nx / nl, y = ny / nl, z = nz / nl;
-    C.x = x; C.y = y; C.z = z;
-    C.usable = true;
-    double q[3] = {p[0], p[1], p[2]};
-    if (DEPTH) { q[0] = p[0] + V.bias * x; q[1] = p[1] + V.bias * y; q[2] = p[2] + V.bias * z; }
-
-    // the cell: the nominal grid's
-    uint32_t i[3];
-    double f[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        i[k] = 0u; f[k] = 0.0;
-        if (G.counts[k] > 1u) {
-            const double cm1 = (double)(G.counts[k] - 1u);
-            double s = ((p[k] - G.lo[k]) / G.span[k]) * cm1;
-            s = fmin(fmax(s, 0.0), cm1);
-            const double fl = fmin(floor(s), cm1 - 1.0);
-            i[k] = (uint32_t)fl;
-            f[k] = s - fl;
-        }
-    }
-    const bool two[3] = {G.counts[0] > 1u, G.counts[1] > 1u, G.counts[2] > 1u};      // wave-uniform: a flat axis has one corner
-    const size_t map_floats = DEPTH ? (size_t)V.R * V.R * 2u : 0u;
-
-    // the corner weights, corner d = 4 dz + 2 dy + dx
-    uint32_t active = 0u;
-    double wsum = 0.0;
-#pragma unroll
-    for (int d = 0; d < 8; d++) {
-        const int dx = d & 1, dy = (d >> 1) & 1, dz = d >> 2;
-        C.w[d] = 0.0;
-        C.probe[d] = 0u;
-        if ((dx == 0 || two[0]) && (dy == 0 || two[1]) && (dz == 0 || two[2])) {
-            const uint32_t probe = ((i[2] + (uint32_t)dz) * G.counts[1] + (i[1] + (uint32_t)dy)) * G.counts[0] + (i[0] + (uint32_t)dx);   // < 2^31
-            C.probe[d] = probe;
-            float o0 = 0.f, o1 = 0.f, o2 = 0.f;
-            if (placement) {
-                const float *__restrict__ pl = placement + (size_t)probe * 4u;
-                if (pl[3] == 0.f) continue;                                            // inactive: nothing of this probe is read
-                o0 = pl[0]; o1 = pl[1]; o2 = pl[2];
-            }
-            active |= 1u << d;
-            const double wx = dx ? f[0] : 1.0 - f[0], wy = dy ? f[1] : 1.0 - f[1], wz = dz ? f[2] : 1.0 - f[2];
-            const int dd[3] = {dx, dy, dz};
-            const double off[3] = {(double)o0, (double)o1, (double)o2};
-            double P[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) P[k] = (two[k] ? G.lo[k] + (double)(i[k] + (uint32_t)dd[k]) * G.step[k] : G.mid[k]) + off[k];
-            double fac = 1.0;
-            if (G.wrap) {
-                const double r[3] = {P[0] - p[0], P[1] - p[1], P[2] - p[2]};
-                const double rl2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
-                fac = 1.2;
-                if (rl2 > 0.0) {
-                    const double rl = sqrt(rl2);
-                    const double dot = (x * (r[0] / rl) + y * (r[1] / rl)) + z * (r[2] / rl);
-                    const double h = 0.5 * (dot + 1.0);
-                    fac = h * h + 0.2;
-                }
-            }
-            double wd = (wx * wy) * wz;
-            if (DEPTH) {
-                // the visibility of this probe from the biased point
-                const double rv[3] = {q[0] - P[0], q[1] - P[1], q[2] - P[2]};
-                const double dist = sqrt((rv[0] * rv[0] + rv[1] * rv[1]) + rv[2] * rv[2]);
-                double v = 1.0;
-                if (dist != 0.0) {
-                    double mu, mu2;
-                    depth_fetch(V.moments + (size_t)probe * map_floats, V.R, rv[0] / dist, rv[1] / dist, rv[2] / dist, mu, mu2);
-                    if (!(dist <= mu)) {
-                        const double var = fabs(mu * mu - mu2);
-                        const double t = dist - mu;
-                        const double c = var / (var + t * t);
-                        v = (c * c) * c;
-                    }
-                }
-                double g = fmax(1e-6, fac * v);
-                if (g < 0.2) g = (g * (g * g)) * 25.0;
-                wd = wd * g;
-            } else if (G.wrap) {
-                wd = wd * fac;
-            }
-            wsum = wsum + wd;
-            C.w[d] = wd;
-        }
-    }
-    C.active = active;
-    C.wsum = wsum;
-    return !(wsum == 0.0);                                                             // false: no active corner, or none with a weight
-}
-
-// the SH sum of probe_lookup_placed over those corners: E[c] in float64 before its one rounding
-__device__ __forceinline__ void corners_sh(const Corners &C, const RadConst &K, const float *__restrict__ sh, double E[3]) {
-    const double x = C.x, y = C.y, z = C.z;
-    const double B[9] = {K.a0 * K.y0,           K.a1 * (K.c1 * y),       K.a1 * (K.c1 * z),
-                         K.a1 * (K.c1 * x),     K.a2 * ((K.c2 * x) * y), K.a2 * ((K.c2 * y) * z),
-                         K.a2 * (K.c6 * (3.0 * (z * z) - 1.0)), K.a2 * ((K.c2 * x) * z), K.a2 * (K.c8 * (x * x - y * y))};
-    double e0 = 0.0, e1 = 0.0, e2 = 0.0;
-#pragma unroll
-    for (int d = 0; d < 8; d++) {
-        if (C.active & (1u << d)) {
-            const float *__restrict__ s = sh + (size_t)C.probe[d] * 27u;
-            double c0 = B[0] * (double)s[0], c1 = B[0] * (double)s[1], c2 = B[0] * (double)s[2];
-#pragma unroll
-            for (int k = 1; k < 9; k++) {
-                c0 = c0 + B[k] * (double)s[3 * k];
-                c1 = c1 + B[k] * (double)s[3 * k + 1];
-                c2 = c2 + B[k] * (double)s[3 * k + 2];
-            }
-            const double wd = C.w[d] / C.wsum;
-            e0 = e0 + wd * c0; e1 = e1 + wd * c1; e2 = e2 + wd * c2;
-        }
-    }
-    E[0] = e0; E[1] = e1; E[2] = e2;
-}
-
 // the radiance sum over those corners along (dx, dy, dz), which need not be a unit vector, at roughness `rough`: E[c] in float64 before
 // its one rounding; false for a direction or a roughness the statement answers with zeros
-__device__ __forceinline__ bool corners_radiance(const Corners &C, const DProbeRadiance &pr, const float4 *__restrict__ maps, double dx, double dy,
+__device__ __forceinline__ bool corners_radiance(const DProbeGrid &G, const Corners &C, const DProbeRadiance &pr, const float4 *__restrict__ maps, double dx, double dy,
                                                  double dz, double rough, double E[3]) {
     const double dl2 = (dx * dx + dy * dy) + dz * dz;
     if (!(dl2 > 0.0) || !(dl2 <= 1.79769313486231570e+308) || !(fabs(rough) <= 1.79769313486231570e+308)) return false;
@@ -425,7 +235,7 @@ __device__ __forceinline__ bool corners_radiance(const Corners &C, const DProbeR
 #pragma unroll
     for (int d = 0; d < 8; d++) {
         if (C.active & (1u << d)) {
-            const float4 *__restrict__ m = maps + (size_t)C.probe[d] * pr.texels;      // n_probes x M < 2^31 texels
+            const float4 *__restrict__ m = maps + (size_t)corner_probe(G, C.cell, d) * pr.texels;      // n_probes x M < 2^31 texels
             double c[3];
             radiance_fetch(m + off0, Rl, rx, ry, rz, c);
             if (pair) {
@@ -441,8 +251,10 @@ __device__ __forceinline__ bool corners_radiance(const Corners &C, const DProbeR
     return true;
 }
 
+// Four waves per SIMD, not the five its 90 VGPRs would allow: a point gathers up to 1 KB of texels, and on random points the fifth wave
+// costs 0.4 % (profiles/probe_lookup.txt)
 template <bool DEPTH>
-__global__ __launch_bounds__(PL_BLOCK) void k_probe_radiance_lookup(DProbeGrid G, DProbeVis V, DProbeRadiance pr, const float4 *__restrict__ maps,
+__global__ __launch_bounds__(PL_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_probe_radiance_lookup(DProbeGrid G, DProbeVis V, DProbeRadiance pr, const float4 *__restrict__ maps,
                                                                     const float *__restrict__ placement, uint32_t n,
                                                                     const float *__restrict__ positions, const float *__restrict__ normals,
                                                                     uint32_t stride, const float *__restrict__ dirs,
@@ -455,8 +267,8 @@ __global__ __launch_bounds__(PL_BLOCK) void k_probe_radiance_lookup(DProbeGrid G
         double E[3];
         float r = 0.f, g = 0.f, b = 0.f;
         if (finite_f(dd[0]) && finite_f(dd[1]) && finite_f(dd[2]) && finite_f(rough) &&
-            corner_weights<DEPTH>(G, V, placement, pp[0], pp[1], pp[2], nn[0], nn[1], nn[2], C) &&
-            corners_radiance(C, pr, maps, (double)dd[0], (double)dd[1], (double)dd[2], (double)rough, E)) {
+            corner_weights<true, DEPTH>(G, V, placement, pp[0], pp[1], pp[2], nn[0], nn[1], nn[2], C) &&
+            corners_radiance(G, C, pr, maps, (double)dd[0], (double)dd[1], (double)dd[2], (double)rough, E)) {
             r = (float)E[0]; g = (float)E[1]; b = (float)E[2];
         }
         float *o = out + (size_t)q * 3u;
@@ -464,48 +276,21 @@ __global__ __launch_bounds__(PL_BLOCK) void k_probe_radiance_lookup(DProbeGrid G
     }
 }
 
-// fw_kernels.hip's fdiv and resolve_pixel, as fw_probe_lookup.hip restates them: the same bits
-__device__ __forceinline__ float fdiv(float a, float b) {
-    float r = __builtin_amdgcn_rcpf(b);
-    r = fmaf(fmaf(-b, r, 1.0f), r, r);
-    float q = a * r;
-    q = fmaf(fmaf(-b, q, a), r, q);
-    q = fmaf(fmaf(-b, q, a), r, q);
-    return __builtin_amdgcn_div_fixupf(q, b, a);
-}
-__device__ __forceinline__ uint8_t sat_u8(float f) { if (!(f > 0.f)) return 0; if (f >= 255.f) return 255; return (uint8_t)f; }
-__device__ __forceinline__ float clamp01(float x) { return (x != x) ? x : (x < 0.f ? 0.f : (x > 1.f ? 1.f : x)); }
-__device__ __forceinline__ void resolve_pixel(float cr, float cg, float cb, float spp, float gamma, uint32_t p, uint8_t *rgb8, float *gamma_rgb,
-                                              float *linear_rgb) {
-    const float tr = fdiv(cr, spp), tg = fdiv(cg, spp), tb = fdiv(cb, spp);
-    const float ig = fdiv(1.f, gamma);
-    const float gr = clamp01(fwlm::powf_glibc(tr, ig)), gg = clamp01(fwlm::powf_glibc(tg, ig)), gb = clamp01(fwlm::powf_glibc(tb, ig));
-    if (linear_rgb) { linear_rgb[3 * (size_t)p] = tr; linear_rgb[3 * (size_t)p + 1] = tg; linear_rgb[3 * (size_t)p + 2] = tb; }
-    if (gamma_rgb) { gamma_rgb[3 * (size_t)p] = gr; gamma_rgb[3 * (size_t)p + 1] = gg; gamma_rgb[3 * (size_t)p + 2] = gb; }
-    if (rgb8) { rgb8[3 * (size_t)p] = sat_u8(gr * 255.99f); rgb8[3 * (size_t)p + 1] = sat_u8(gg * 255.99f); rgb8[3 * (size_t)p + 2] = sat_u8(gb * 255.99f); }
-}
-
 template <bool DEPTH>
-__global__ __launch_bounds__(PL_BLOCK) void k_probe_shade_glossy(DProbeGrid G, DProbeVis V, DProbeRadiance pr, RadConst K, const float *__restrict__ sh,
+__global__ __launch_bounds__(PL_BLOCK) void k_probe_shade_glossy(DProbeGrid G, DProbeVis V, DProbeRadiance pr, ShLookupConst K, const float *__restrict__ sh,
                                                                  const float4 *__restrict__ maps, const float *__restrict__ placement, uint32_t n,
                                                                  const float4 *__restrict__ aov, const float4 *__restrict__ spec,
                                                                  const float *__restrict__ view, uint32_t view_stride, float gamma, uint8_t *rgb8,
                                                                  float *gamma_rgb, float *linear_rgb) {
-    const float inv_pi = (float)(1.0 / 3.141592653589793);
     const uint32_t p = blockIdx.x * PL_BLOCK + threadIdx.x;                           // one pixel per lane: the grid covers n
     if (p < n) {
         const float4 a = aov[3 * (size_t)p], nd = aov[3 * (size_t)p + 1], xa = aov[3 * (size_t)p + 2];
         const float4 sp = spec[p];
         Corners C;
-        const bool ok = corner_weights<DEPTH>(G, V, placement, xa.x, xa.y, xa.z, nd.x, nd.y, nd.z, C);
+        const bool ok = corner_weights<true, DEPTH>(G, V, placement, xa.x, xa.y, xa.z, nd.x, nd.y, nd.z, C);
         const float v = a.w, rest = 1.f - v;
         if (!(sp.w > 0.f)) {                                                           // diffuse: fw_probe_shade_placed's arithmetic
-            double E[3];
-            float er = 0.f, eg = 0.f, eb = 0.f;
-            if (ok) { corners_sh(C, K, sh, E); er = (float)E[0]; eg = (float)E[1]; eb = (float)E[2]; }
-            er = er > 0.f ? er : 0.f; eg = eg > 0.f ? eg : 0.f; eb = eb > 0.f ? eb : 0.f;
-            resolve_pixel(a.x * (v * (er * inv_pi) + rest), a.y * (v * (eg * inv_pi) + rest), a.z * (v * (eb * inv_pi) + rest), 1.0f, gamma, p, rgb8,
-                          gamma_rgb, linear_rgb);
+            shade_diffuse(G, C, ok, K, sh, a, gamma, p, rgb8, gamma_rgb, linear_rgb);
             return;
         }
         // glossy: the lookup along the mirrored view direction under Schlick's Fresnel term
@@ -525,7 +310,7 @@ __global__ __launch_bounds__(PL_BLOCK) void k_probe_shade_glossy(DProbeGrid G, D
                 const double m = 1.0 - cost;
                 Sf = (float)(((m * m) * (m * m)) * m);
                 double E[3];
-                if (ok && finite_f(sp.w) && corners_radiance(C, pr, maps, (double)rx, (double)ry, (double)rz, (double)sp.w, E)) {
+                if (ok && finite_f(sp.w) && corners_radiance(G, C, pr, maps, (double)rx, (double)ry, (double)rz, (double)sp.w, E)) {
                     l0 = (float)E[0]; l1 = (float)E[1]; l2 = (float)E[2];
                 }
             }
@@ -536,11 +321,6 @@ __global__ __launch_bounds__(PL_BLOCK) void k_probe_shade_glossy(DProbeGrid G, D
     }
 }
 
-RadConst rad_const() {
-    const double PI = 3.141592653589793;
-    return RadConst{0.5 * std::sqrt(1.0 / PI), std::sqrt(3.0 / (4.0 * PI)), 0.5 * std::sqrt(15.0 / PI), 0.25 * std::sqrt(5.0 / PI),
-                    0.25 * std::sqrt(15.0 / PI), PI, 2.0 * PI / 3.0, PI / 4.0};
-}
 uint32_t rad_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + PL_BLOCK - 1) / PL_BLOCK); }        // n > 0; at most 2^24 blocks
 
 } // namespace
@@ -552,8 +332,8 @@ void launch_probe_radiance_reduce(hipStream_t stream, uint32_t n, uint32_t direc
 }
 
 void launch_probe_radiance_prefilter(hipStream_t stream, int n_cus, uint32_t n, const DProbeRadiance &pr, const float *sums, float *maps) {
-    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(n, (uint32_t)std::max(1, n_cus) * 3u));      // 48 KB of LDS: three per CU
-    hipLaunchKernelGGL(k_probe_radiance_prefilter, dim3(blocks), dim3(PR_BLOCK), 0, stream, n, pr, (const float4 *)sums, (float4 *)maps);
+    hipLaunchKernelGGL(k_probe_radiance_prefilter, dim3(grid_for(n, 1u, n_cus, 3u)), dim3(PR_BLOCK), 0, stream, n, pr, (const float4 *)sums,
+                       (float4 *)maps);                                                 // 48 KB of LDS: three per CU
 }
 
 void launch_probe_radiance_lookup(hipStream_t stream, const DProbeGrid &g, const DProbeVis *v, const DProbeRadiance &pr, const float *maps,
@@ -568,11 +348,11 @@ void launch_probe_radiance_lookup(hipStream_t stream, const DProbeGrid &g, const
 void launch_probe_shade_glossy(hipStream_t stream, const DProbeGrid &g, const DProbeVis *v, const DProbeRadiance &pr, const float *sh,
                                const float *maps, const float *placement, uint32_t n, const float *aov, const float *spec, const float *view,
                                uint32_t view_stride, float gamma, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
-    if (v) hipLaunchKernelGGL(k_probe_shade_glossy<true>, dim3(rad_blocks(n)), dim3(PL_BLOCK), 0, stream, g, *v, pr, rad_const(), sh,
+    if (v) hipLaunchKernelGGL(k_probe_shade_glossy<true>, dim3(rad_blocks(n)), dim3(PL_BLOCK), 0, stream, g, *v, pr, sh_lookup_const(), sh,
                               (const float4 *)maps, placement, n, (const float4 *)aov, (const float4 *)spec, view, view_stride, gamma, rgb8,
                               gamma_rgb, linear_rgb);
     else hipLaunchKernelGGL(k_probe_shade_glossy<false>, dim3(rad_blocks(n)), dim3(PL_BLOCK), 0, stream, g, DProbeVis{nullptr, 0.0, 0u}, pr,
-                            rad_const(), sh, (const float4 *)maps, placement, n, (const float4 *)aov, (const float4 *)spec, view, view_stride, gamma,
+                            sh_lookup_const(), sh, (const float4 *)maps, placement, n, (const float4 *)aov, (const float4 *)spec, view, view_stride, gamma,
                             rgb8, gamma_rgb, linear_rgb);
 }
 

@@ -11,25 +11,18 @@
 //                     __shfl_xor steps (below), the result is rounded to float32 once and added to the probe's 27 running sums.
 //                     No atomics, no LDS, no barrier; the result is a pure function of the inputs.
 //
-// A file of its own, after the others on the link line: the code objects of fw_kernels.hip, fw_build.hip, fw_temporal.hip and
-// fw_camera_models.hip stay byte for byte what they were.
+// The hashes and the jitter draw are fw_shared.h's.
 //
 // Numerics: -ffp-contract=off, so + - * / round as written and in the order of api.ProbeSet.rays / api.sh_project; sin, cos and sqrt are
 // the device library's float64 functions, a few float64 ulps from the host's.
 #include "fw_probes.h"
-#include <algorithm>
-#include <cmath>
+#include "fw_shared.h"
 
 namespace fw {
 namespace {
 
 constexpr int PR_BLOCK = 64;
 constexpr int PP_WAVES = 4;
-
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return x;
-}
 
 __global__ __launch_bounds__(PR_BLOCK) void k_probe_rays(DProbes P, uint32_t n_entries, float *__restrict__ out) {
     __shared__ float tr[6 * 64];
@@ -44,12 +37,7 @@ __global__ __launch_bounds__(PR_BLOCK) void k_probe_rays(DProbes P, uint32_t n_e
             const uint32_t i = id0 + lane;
             const uint32_t pl = i / P.directions, j = i - pl * P.directions;
             double xi_u = 0.5, xi_v = 0.5;
-            if (P.jitter) {
-                const uint32_t p = P.first_probe + pl;                                    // 2 p + 1 < 2^32
-                const uint32_t key = hash32(P.seed32 ^ hash32(P.round + 0x9E3779B9u));
-                xi_u = (double)(hash32(hash32(2u * p) ^ key) >> 8) * 0x1p-24;
-                xi_v = (double)(hash32(hash32(2u * p + 1u) ^ key) >> 8) * 0x1p-24;
-            }
+            if (P.jitter) { const Jitter xi = jitter_pair(P.seed32, P.round, P.first_probe + pl); xi_u = xi.u; xi_v = xi.v; }     // 2 p + 1 < 2^32
             const double u = ((double)j + xi_u) / Dd;
             const double ct = 1.0 - 2.0 * u;
             const double rad = sqrt(fmax(0.0, 1.0 - ct * ct));
@@ -126,9 +114,7 @@ __global__ __launch_bounds__(PP_WAVES * 64) void k_probe_project(ShConst K, uint
 
 void launch_probe_rays(hipStream_t stream, int n_cus, const DProbes &p, uint32_t n, float *out) {
     const uint32_t n_entries = n * p.directions;                              // < 2^31
-    const uint32_t chunks = (n_entries + 63u) / 64u;
-    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(chunks, (uint32_t)std::max(1, n_cus) * 128u));
-    hipLaunchKernelGGL(k_probe_rays, dim3(blocks), dim3(PR_BLOCK), 0, stream, p, n_entries, out);
+    hipLaunchKernelGGL(k_probe_rays, dim3(grid_for(n_entries, 64u, n_cus, 128u)), dim3(PR_BLOCK), 0, stream, p, n_entries, out);
 }
 
 void launch_probe_project(hipStream_t stream, int n_cus, uint32_t n, uint32_t directions, uint32_t samples, const float *rays,
@@ -136,9 +122,8 @@ void launch_probe_project(hipStream_t stream, int n_cus, uint32_t n, uint32_t di
     const double PI = 3.141592653589793;
     const ShConst K{0.5 * std::sqrt(1.0 / PI), std::sqrt(3.0 / (4.0 * PI)), 0.5 * std::sqrt(15.0 / PI), 0.25 * std::sqrt(5.0 / PI),
                     0.25 * std::sqrt(15.0 / PI), 4.0 * PI};
-    const uint32_t want = (n + PP_WAVES - 1u) / PP_WAVES;
-    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(want, (uint32_t)std::max(1, n_cus) * 32u));
-    hipLaunchKernelGGL(k_probe_project, dim3(blocks), dim3(PP_WAVES * 64), 0, stream, K, n, directions, samples, rays, (const float4 *)accum, sums);
+    hipLaunchKernelGGL(k_probe_project, dim3(grid_for(n, PP_WAVES, n_cus, 32u)), dim3(PP_WAVES * 64), 0, stream, K, n, directions, samples, rays,
+                       (const float4 *)accum, sums);
 }
 
 } // namespace fw

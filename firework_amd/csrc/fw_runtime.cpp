@@ -4540,9 +4540,7 @@ int probe_irradiance_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, i
         const float *d_sh = st.ptr<const float>(t.sh), *pos = sl.ptr<const float>(a_pts), *nrm = sl.with(a_pts);
         float *out = sl.ptr<float>(a_out);
         const fw::DProbeVis v = probe_vis_device(a, st.ptr<const float>(t.mom));
-        if (a.placed) fw::launch_probe_irradiance_placed(stream, L.g, a.vis ? &v : nullptr, d_sh, st.ptr<const float>(t.pl), k, pos, nrm, sl.stride(a_pts), out);
-        else if (a.vis) fw::launch_probe_irradiance_vis(stream, L.g, v, d_sh, k, pos, nrm, sl.stride(a_pts), out);
-        else fw::launch_probe_irradiance(stream, L.g, d_sh, k, pos, nrm, sl.stride(a_pts), out);
+        fw::launch_probe_irradiance(stream, L.g, a.vis ? &v : nullptr, d_sh, st.ptr<const float>(t.pl), k, pos, nrm, sl.stride(a_pts), out);
     });
 }
 
@@ -4575,9 +4573,7 @@ int probe_shade_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, const 
         uint8_t *o8 = sl.ptr<uint8_t>(a_8);
         float *og = sl.ptr<float>(a_gam), *ol = sl.ptr<float>(a_lin);
         const fw::DProbeVis v = probe_vis_device(a, st.ptr<const float>(t.mom));
-        if (a.placed) fw::launch_probe_shade_placed(stream, L.g, a.vis ? &v : nullptr, d_sh, st.ptr<const float>(t.pl), k, d_aov, p->gamma, o8, og, ol);
-        else if (a.vis) fw::launch_probe_shade_vis(stream, L.g, v, d_sh, k, d_aov, p->gamma, o8, og, ol);
-        else fw::launch_probe_shade(stream, L.g, d_sh, k, d_aov, p->gamma, o8, og, ol);
+        fw::launch_probe_shade(stream, L.g, a.vis ? &v : nullptr, d_sh, st.ptr<const float>(t.pl), k, d_aov, p->gamma, o8, og, ol);
     });
 }
 

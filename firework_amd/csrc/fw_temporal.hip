@@ -6,12 +6,12 @@
 //
 // 16 x 16 tiles, thread t = pixel (t & 15, t >> 4) of its tile: a wave is a 16 x 4 block of pixels, so under a coherent camera motion
 // its taps fall into a compact region of the previous frame.  No atomics, no LDS, no inline assembly: every output is one thread's.
-// A file of its own: fw_kernels.hip's code object stays byte for byte what it was.
 //
-// Numerics: -ffp-contract=off, + - * IEEE as written; division and square root are fw_kernels.hip's fdiv / fsqrt restated below (the
-// same correctly rounded bits).
+// Numerics: -ffp-contract=off, + - * IEEE as written; division is fw_shared.h's fdiv and the square root fw_kernels.hip's fsqrt, written
+// out below (the same correctly rounded bits).
 #include "../../include/firework_hip.h"     // FW_DENOISE_EPS, FW_TEMPORAL_*
 #include "fw_temporal.h"
+#include "fw_shared.h"          // fdiv, finite_f
 
 namespace fw {
 namespace {
@@ -19,16 +19,7 @@ namespace {
 constexpr uint32_t TP_TILE = 16;
 constexpr int TP_BLOCK = 256;
 
-// fw_kernels.hip's fdiv / fsqrt (see there for why): the compiler's Newton chain without the scaling steps, v_div_fixup for the IEEE
-// special cases; v_sqrt_f32 corrected by the exact residuals of its neighbours.
-__device__ __forceinline__ float fdiv(float a, float b) {
-    float r = __builtin_amdgcn_rcpf(b);
-    r = fmaf(fmaf(-b, r, 1.0f), r, r);
-    float q = a * r;
-    q = fmaf(fmaf(-b, q, a), r, q);
-    q = fmaf(fmaf(-b, q, a), r, q);
-    return __builtin_amdgcn_div_fixupf(q, b, a);
-}
+// fw_kernels.hip's fsqrt (see there for why): v_sqrt_f32 corrected by the exact residuals of its neighbours.
 __device__ __forceinline__ float fsqrt(float x) {
     float s = __builtin_amdgcn_sqrtf(x);
     float sd = __uint_as_float(__float_as_uint(s) - 1u), su = __uint_as_float(__float_as_uint(s) + 1u);
@@ -37,7 +28,6 @@ __device__ __forceinline__ float fsqrt(float x) {
     s = (vu > 0.f) ? su : s;
     return s;
 }
-__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.40282347e+38f; }   // false for NaN and +-inf
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return finite_f(x) && finite_f(y) && finite_f(z); }
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 

@@ -936,7 +936,7 @@ int fw_bake_probe_depth(fw_scene *scene, const fw_probe_set *set, const fw_probe
                         uint32_t rounds, float *sums, float *moments, fw_stats *stats);
 
 /* fw_probe_irradiance_vis, fw_probe_shade_vis: fw_probe_irradiance and fw_probe_shade with the visibility weight above
-   (k_probe_irradiance_vis, k_probe_shade_vis: one lane per point, no atomics).  moments: n x R x R x 2 floats for the grid's n probes,
+   (k_probe_irradiance and k_probe_shade with DEPTH: one lane per point, no atomics).  moments: n x R x R x 2 floats for the grid's n probes,
    host memory or with on_device device memory like sh; a host call stages it after sh.  Every moments index is formed from clamped
    cell and texel indices: no load leaves the arrays wherever the point lies.  Errors, in this order and before HIP is called:
    FW_ERR_BAD_ARG for a NULL pointer (the counterpart's, pd, moments; fw_probe_shade_vis then: all three outputs NULL), a resolution not
@@ -1308,7 +1308,7 @@ int fw_probe_relocate_step(int device, const fw_probe_relocate *rl, uint32_t n_p
 int fw_relocate_probes(fw_scene *scene, const fw_probe_set *set, const fw_probe_relocate *rl, const fw_trace_params *tp, uint32_t first_step,
                        uint32_t steps, float *placement, float *survey, fw_stats *stats);
 
-/* fw_probe_irradiance_placed, fw_probe_shade_placed: the placed lookup above (k_probe_irradiance_placed, k_probe_shade_placed: one lane
+/* fw_probe_irradiance_placed, fw_probe_shade_placed: the placed lookup above (k_probe_irradiance and k_probe_shade with PLACED: one lane
    per point, no atomics).  The arguments are fw_probe_irradiance_vis' and fw_probe_shade_vis', and placement: n x 4 floats for the
    grid's n probes, host memory or with on_device device memory like sh; a host call stages it after the moments.  pd and moments may
    both be NULL: no visibility weight (normal_bias is then not read).  Every index is formed from clamped cell and texel indices: no

@@ -4,8 +4,8 @@ Renderer.bake_probe_depth, Renderer.render_probe_lit with depth)
 k_probe_depth against the numpy float64 statement (api.probe_depth_reduce) within the bound of tests/probe_depth_ref.py — derived from the
 order of operations, nothing in it measured — over every chunk boundary of the directions, every texel count per lane, host and device
 arrays, a side stream, NaN-filled and pre-filled sums; the bake against the three public calls chained by hand, bit for bit, for every
-chunking, progressively, with fw_render left as it was; a probe in a sphere's centre; k_probe_irradiance_vis against api.probe_lookup_vis
-within the derived bound over test_gpu_probe_lookup.py's grids and point families; k_probe_shade_vis bit for bit on the lookup's own
+chunking, progressively, with fw_render left as it was; a probe in a sphere's centre; fw_probe_irradiance_vis against api.probe_lookup_vis
+within the derived bound over test_gpu_probe_lookup.py's grids and point families; fw_probe_shade_vis bit for bit on the lookup's own
 output; the leak between two rooms closed end to end; render_probe_lit with and without depth; the CLI's round trip."""
 import os
 

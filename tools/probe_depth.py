@@ -6,7 +6,7 @@ profiles/probe_depth.txt.  Nothing here is a gate.
                                                     FW_FLAG_TIME_KERNELS, its parts — k_probe_rays (ms_raygen), the walks (ms_extend) and
                                                     k_probe_depth (ms_accumulate: device events around the launch) — one warm-up call,
                                                     then medians of N (default 5).  Beside it fw_bake_probes at S = 1 on the same set.
-    python tools/probe_depth.py lookup [--calls N]  k_probe_irradiance_vis against k_probe_irradiance on the same 1920 x 1080 buffer of
+    python tools/probe_depth.py lookup [--calls N]  k_probe_irradiance with the depth maps against without, on the same 1920 x 1080 buffer of
                                                     fw_render_aovs records (cornell), in place at stride 12, alternated in one process:
                                                     3 warm-up calls each, then N (default 20) calls each timed by device events around the
                                                     call (host call and stream drain included); medians.
@@ -89,8 +89,9 @@ def lookup(calls):
         ds.close()
     d_sh, d_mom = torch.from_numpy(sh).to(dev), torch.from_numpy(moments).to(dev)
     out = torch.empty((W * H, 3), dtype=torch.float32, device=dev)
-    fns = dict(k_probe_irradiance=lambda: _lib.probe_irradiance(grid, d_sh, aov[:, 8:11], aov[:, 4:7], out=out),
-               k_probe_irradiance_vis=lambda: _lib.probe_irradiance_vis(grid, d_sh, pd, d_mom, aov[:, 8:11], aov[:, 4:7], 0.0, out=out))
+    plain, vis = "k_probe_irradiance<false, false>", "k_probe_irradiance<false, true>"      # <PLACED, DEPTH>
+    fns = {plain: lambda: _lib.probe_irradiance(grid, d_sh, aov[:, 8:11], aov[:, 4:7], out=out),
+           vis: lambda: _lib.probe_irradiance_vis(grid, d_sh, pd, d_mom, aov[:, 8:11], aov[:, 4:7], 0.0, out=out)}
     for fn in fns.values():
         for _ in range(WARMUP):
             fn()
@@ -107,8 +108,8 @@ def lookup(calls):
     print(f"{W * H} points (cornell's fw_render_aovs records in place, stride 12), {grid.n_probes} probes, R = {RES}; alternated, {calls} calls each after "
           f"{WARMUP}, device events around the calls (host call and stream drain included)")
     for name, t in ms.items():
-        print(f"{name:24s} median {np.median(t):7.3f} ms  min {min(t):7.3f}  max {max(t):7.3f}")
-    print(f"ratio vis / plain {np.median(ms['k_probe_irradiance_vis']) / np.median(ms['k_probe_irradiance']):.2f}")
+        print(f"{name:34s} median {np.median(t):7.3f} ms  min {min(t):7.3f}  max {max(t):7.3f}")
+    print(f"ratio vis / plain {np.median(ms[vis]) / np.median(ms[plain]):.2f}")
 
 
 def _rooms():

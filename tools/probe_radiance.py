@@ -8,8 +8,8 @@ calls, N (default 7) calls each, the kernels of a part alternated; medians, with
   maps    32 768 probes, D = 256, seeded random unit rays, radiances and hits on the device; for R = 16 (three levels) and R = 32 (four):
           k_probe_radiance_reduce and k_probe_radiance_prefilter, beside k_probe_depth at the same R on the same rays.
   points  1920 x 1080 seeded random records inside a 32 x 32 x 32 grid; for R = 16 and R = 32: k_probe_radiance_lookup beside
-          k_probe_irradiance_placed, and k_probe_shade_glossy (every pixel glossy) beside k_probe_shade_placed, on the same records, with
-          a neutral placement and without depth maps.
+          k_probe_irradiance<true, false>, and k_probe_shade_glossy (every pixel glossy) beside k_probe_shade<true, false> (<PLACED,
+          DEPTH>: the placed forms), on the same records, with a neutral placement and without depth maps.
   bake    cornell, the same 32 768 probes, D = 256, one round of one sample, R = 16 and R = 32: fw_bake_probe_radiance's ms_render
           (first launch to last) and, under FW_FLAG_TIME_KERNELS, k_probe_rays (ms_raygen) and the reducers with the prefilter
           (ms_accumulate); the prefilter of the bake's own sums alone beside them.
@@ -112,13 +112,13 @@ def points_part(calls, say):
     for R, chain in CHAINS.items():
         pr = api.ProbeRadiance(R, 2, chain)
         maps = torch.rand((n_probes, pr.texels, 4), generator=g, device=dev)
-        ms = timed(dict(k_probe_radiance_lookup=lambda: _lib.probe_radiance_lookup(grid, pr, maps, pos, nrm, dirs, rough, placement=neutral, out=out),
-                        k_probe_irradiance_placed=lambda: _lib.probe_irradiance_placed(grid, sh, neutral, pos, nrm, out=out),
-                        k_probe_shade_glossy=lambda: _lib.probe_shade_glossy(grid, sh, pr, maps, rec, spec, dirs, W, H, placement=neutral),
-                        k_probe_shade_placed=lambda: _lib.probe_shade_placed(grid, sh, neutral, rec, W, H)), calls)
+        ms = timed({"k_probe_radiance_lookup": lambda: _lib.probe_radiance_lookup(grid, pr, maps, pos, nrm, dirs, rough, placement=neutral, out=out),
+                    "k_probe_irradiance<true, false>": lambda: _lib.probe_irradiance_placed(grid, sh, neutral, pos, nrm, out=out),
+                    "k_probe_shade_glossy": lambda: _lib.probe_shade_glossy(grid, sh, pr, maps, rec, spec, dirs, W, H, placement=neutral),
+                    "k_probe_shade<true, false>": lambda: _lib.probe_shade_placed(grid, sh, neutral, rec, W, H)}, calls)
         say(f" R = {R}, {pr.levels} levels: maps of {n_probes * pr.texels * 16 / 2 ** 20:.0f} MiB; a point reads 8 corners x 2 levels x 4 texels x 16 B = 1024 B of them")
-        for name in ("k_probe_radiance_lookup", "k_probe_irradiance_placed", "k_probe_shade_glossy", "k_probe_shade_placed"):
-            say(line(name, ms[name], f"{n / np.median(ms[name]) / 1e6:7.2f} G points/s"))
+        for name, t in ms.items():
+            say(line(name, t, f"{n / np.median(t) / 1e6:7.2f} G points/s"))
         del maps
 
 
