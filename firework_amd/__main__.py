@@ -61,7 +61,12 @@ texels with the same --lightmap-dirs, --lightmap-rounds and --lightmap-dilate; -
 --aov-samples samples, then one shadow ray per pixel and light, origins moved B >= 0, default 0.001, along the normal: sharp shadows and
 GgxMat highlights without a path, fw_bake_direct; -s is not used; refuses what --ao refuses, and --ao).  --probe-lit FILE
 --direct-light (adds that light, which no probe holds, to the probe-lit frame).  --bake-lightmap ... --lightmap-direct [--direct-bias B]
-(adds the lights' irradiance at each covered texel before the dilation; the .npz also gets direct)."""
+(adds the lights' irradiance at each covered texel before the dilation; the .npz also gets direct).
+--sun-sky EL,AZ[,TURBIDITY] [--sun-sky-size W,H] [--sun disc|light|none] (replaces the scene's environment by an analytic sun and sky,
+the sun EL degrees above the horizon at azimuth AZ degrees, baked on the device into a W x H map, default 2048,1024, fw_sky_map,
+DESIGN.md §9x; the sun is a disc in the map, the default, which --env-sampling finds; or a directional light of the same energy beside
+a map without it, which --light-sampling and --direct-light find; or absent; --sun light refuses --env-sampling; combines with every
+other flag)."""
 import argparse
 import sys
 import time
@@ -156,7 +161,34 @@ def main(argv=None):
                     help="with --bake-lightmap: add the direct irradiance of the scene's point, spot and directional lights to the texels")
     ap.add_argument("--direct-bias", type=float, default=None, metavar="B",
                     help="with --direct-light or --lightmap-direct: move shadow-ray origins B >= 0 world units along the normal (default 0.001)")
+    ap.add_argument("--sun-sky", default=None, metavar="EL,AZ[,TURBIDITY]",
+                    help="replace the scene's environment by an analytic sun and sky: the sun EL degrees above the horizon at azimuth AZ degrees")
+    ap.add_argument("--sun-sky-size", default=None, metavar="W,H", help="with --sun-sky: the size of the baked map (default 2048,1024)")
+    ap.add_argument("--sun", choices=("disc", "light", "none"), default=None,
+                    help="with --sun-sky: the sun as a disc in the map (default), as a directional light beside it, or not at all")
     opt = ap.parse_args(argv)
+    sun_sky = None
+    if opt.sun_sky is not None:
+        try:
+            sun_sky = [float(x) for x in opt.sun_sky.split(",")]
+        except ValueError:
+            sun_sky = []
+        if not 2 <= len(sun_sky) <= 3 or not all(abs(x) < float("inf") for x in sun_sky) or not -90.0 <= sun_sky[0] <= 90.0:
+            ap.error("--sun-sky needs EL,AZ[,TURBIDITY]: finite numbers, EL in [-90, 90] degrees")
+        if len(sun_sky) == 3 and not 0.0 <= sun_sky[2] <= 64.0:
+            ap.error("--sun-sky TURBIDITY needs 0 <= TURBIDITY <= 64")
+        sun_sky_size = [2048, 1024]
+        if opt.sun_sky_size is not None:
+            try:
+                sun_sky_size = [int(x) for x in opt.sun_sky_size.split(",")]
+            except ValueError:
+                sun_sky_size = []
+            if len(sun_sky_size) != 2 or not all(2 <= x <= 32768 for x in sun_sky_size):
+                ap.error("--sun-sky-size needs W,H, each in 2..32768")
+        if opt.sun == "light" and opt.env_sampling:       # delta lights and environment sampling together are FW_ERR_UNSUPPORTED
+            ap.error("--sun light cannot be combined with --env-sampling: pass --sun disc for the map's own sun to be sampled")
+    elif opt.sun_sky_size is not None or opt.sun is not None:
+        ap.error("--sun-sky-size and --sun need --sun-sky")
     if opt.direct_light:
         if (opt.ao is not None or opt.bake_probes is not None or opt.bake_lightmap is not None or opt.camera != "pinhole" or opt.denoise is not None
                 or opt.orbit or opt.adaptive is not None or opt.progressive > 0 or opt.checkpoint or opt.temporal is not None):
@@ -405,7 +437,10 @@ def main(argv=None):
 
     if scene is None:
         scene = load_scene(opt.scene_file)
-    camera = CameraSettings.default().cam_pos((0.0, 30.0, 50.0)).look_at((0.0, 0.0, 0.0)).field_of_view(40.0)
+    if sun_sky is not None:
+        from .api import SunSky, SunSkyEnv
+        scene.set_environment(SunSkyEnv(SunSky(sun_sky[0], sun_sky[1], *sun_sky[2:]), sun_sky_size[0], sun_sky_size[1], opt.sun or "disc"))
+    camera =CameraSettings.default().cam_pos((0.0, 30.0, 50.0)).look_at((0.0, 0.0, 0.0)).field_of_view(40.0)
     renderer = (Renderer.default().width(opt.width).height(opt.height).samples(opt.samples).use_bvh(True)
                 .camera(camera).seed(opt.seed).light_sampling(opt.light_sampling).env_sampling(opt.env_sampling))
     if opt.all_emitters:       # bits 4 and 16: light sampling over every emitting primitive

@@ -241,6 +241,24 @@ DIRECT_PROTOTYPES = {
 }
 
 
+# SunSky: an analytic sun-and-sky environment (include/firework_hip.h: fw_check_sky, fw_sky_map, fw_sky_radiance, fw_sky_sun)
+FW_SKY_DISC = 1
+
+
+class fw_sky(C.Structure):
+    _fields_ = [("sun_elevation", f32), ("sun_azimuth", f32), ("turbidity", f32), ("sun_irradiance", fw_vec3), ("sun_radius", f32),
+                ("altitude", f32), ("ground_albedo", fw_vec3), ("view_steps", u32), ("light_steps", u32), ("sun_samples", u32), ("flags", u32)]
+
+
+# the four prototypes (argument types; every one returns int), applied by _lib.load
+SKY_PROTOTYPES = {
+    "fw_check_sky": [C.POINTER(fw_sky)],
+    "fw_sky_map": [C.POINTER(fw_sky), C.c_int, u32, u32, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_sky_radiance": [C.POINTER(fw_sky), C.c_int, u32, C.c_void_p, u32, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_sky_sun": [C.POINTER(fw_sky), C.POINTER(fw_light)],
+}
+
+
 # probe relocation and classification (include/firework_hip.h: fw_probe_survey, fw_probe_relocate_step, fw_relocate_probes,
 # fw_probe_irradiance_placed, fw_probe_shade_placed)
 class fw_probe_relocate(C.Structure):

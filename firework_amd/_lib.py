@@ -131,7 +131,7 @@ def load(preload=False, device=None):
     lib.fw_probe_shade.argtypes = [C.POINTER(A.fw_probe_grid), C.c_void_p, C.POINTER(A.fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
     for name, argtypes in (list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()) + list(A.PROBE_PLACE_PROTOTYPES.items())
-                           + list(A.PROBE_RADIANCE_PROTOTYPES.items()) + list(A.DIRECT_PROTOTYPES.items())):
+                           + list(A.PROBE_RADIANCE_PROTOTYPES.items()) + list(A.DIRECT_PROTOTYPES.items()) + list(A.SKY_PROTOTYPES.items())):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
@@ -1266,6 +1266,71 @@ def direct_reduce(direct, lights, positions, normals, rays, hits, sums, ids=None
     _check(lib, lib.fw_direct_reduce(int(device), C.byref(d), arr, ln, pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride, pts.spec,
                                      r.ctypes.data, h.ctypes.data, p_sums, 0, None))
     return sums
+
+
+def _sky_abi(sky):
+    """a fw_sky from an api.SunSky (or a fw_sky, copied)"""
+    return sky.to_abi() if hasattr(sky, "to_abi") else A.fw_sky.from_buffer_copy(sky)
+
+
+def check_sky(sky):
+    """fw_check_sky: raises FireworkError for what the sky calls refuse in a description; touches no device"""
+    lib = load()
+    s = _sky_abi(sky)
+    _check(lib, lib.fw_check_sky(C.byref(s)))
+
+
+def sky_map(sky, width, height, device=0, out=None, stream=None):
+    """fw_sky_map: the (height, width, 3) float32 equirectangular map of an api.SunSky (or a fw_sky), row 0 at the top, baked on the
+    device: what HdrEnvironment takes.  Returns a numpy array; out: a contiguous float32 device tensor of that shape on cuda:`device`
+    to fill instead, on `stream` (default: the current torch stream); returned."""
+    lib = load()
+    s = _sky_abi(sky)
+    shape = (int(height), int(width), 3)
+    if out is not None:
+        import torch
+        _check_device_tensor(out, shape, torch.float32, device, "out")
+        _check(lib, lib.fw_sky_map(C.byref(s), int(device), int(width), int(height), out.data_ptr(), 1, _stream_arg(stream, out.device)))
+        return out
+    rgb = np.empty(shape, np.float32)
+    _check(lib, lib.fw_sky_map(C.byref(s), int(device), int(width), int(height), rgb.ctypes.data, 0, None))
+    return rgb
+
+
+def sky_radiance(sky, dirs, device=0, out=None, stream=None):
+    """fw_sky_radiance: the (n, 3) float32 radiance of an api.SunSky along directions of any length.  dirs: (n, k) float32 with k >= 3
+    whose rows start with the direction — a view such as rays[:, 3:] of an (n, 6) ray buffer is read in place — as a numpy array
+    (returns a numpy array) or a tensor on cuda:`device` (evaluated on `stream`, default the current torch stream, where it lies;
+    returns a device tensor; out: a contiguous float32 tensor of that shape to fill instead)."""
+    lib = load()
+    s = _sky_abi(sky)
+    if isinstance(dirs, np.ndarray) or not hasattr(dirs, "data_ptr"):
+        d = np.asarray(dirs, dtype=np.float32)
+        if d.ndim != 2 or d.shape[1] < 3 or d.strides[1] != 4 or d.strides[0] % 4 or d.strides[0] < 12:
+            d = np.ascontiguousarray(d.reshape(-1, d.shape[-1])[:, :3])
+        n, stride = int(d.shape[0]), d.strides[0] // 4
+        rgb = np.empty((n, 3), np.float32)
+        _check(lib, lib.fw_sky_radiance(C.byref(s), int(device), n, d.ctypes.data, stride, rgb.ctypes.data, 0, None))
+        return rgb
+    import torch
+    if (dirs.dim() != 2 or dirs.shape[1] < 3 or dirs.dtype != torch.float32 or dirs.stride(1) != 1 or dirs.stride(0) < 3 or dirs.device.type != "cuda"
+            or (dirs.device.index or 0) != device):
+        raise ValueError(f"dirs must be an (n, >= 3) float32 tensor with unit inner stride on cuda:{device}")
+    n = int(dirs.shape[0])
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=dirs.device)
+    _check_device_tensor(out, (n, 3), torch.float32, device, "out")
+    _check(lib, lib.fw_sky_radiance(C.byref(s), int(device), n, dirs.data_ptr(), int(dirs.stride(0)), out.data_ptr(), 1, _stream_arg(stream, dirs.device)))
+    return out
+
+
+def sky_sun(sky):
+    """fw_sky_sun: the sun of an api.SunSky as a fw_light (FW_LIGHT_DIRECTIONAL, direction -s, irradiance E0 T(O)); host only"""
+    lib = load()
+    s = _sky_abi(sky)
+    out = A.fw_light()
+    _check(lib, lib.fw_sky_sun(C.byref(s), C.byref(out)))
+    return out
 
 
 class DeviceScene:

@@ -485,6 +485,307 @@ class HdrEnvironment(Environment):
         self.pixels = p
 
 
+# --------------------------------------------------------------------------- SunSky
+SKY_RG, SKY_RT, SKY_HR, SKY_HM, SKY_G = 6360000.0, 6420000.0, 7994.0, 1200.0, 0.76
+SKY_BETA_R = np.array([5.8e-6, 13.5e-6, 33.1e-6])
+
+
+class SunSky:
+    """An analytic sun and sky (fw_sky; include/firework_hip.h has the statement): the sun at `elevation_deg` above the horizon and
+    azimuth `azimuth_deg` (panorama_rays' phi), an atmosphere of `turbidity` times the clear Mie load, `sun_irradiance` (rgb) above the
+    atmosphere on a plane facing the sun — a linear scale of everything: the exposure — seen from `altitude` metres over ground of
+    `ground_albedo`.  view_steps / light_steps / sun_samples are the quadrature's NV, NL and S."""
+
+    def __init__(self, elevation_deg, azimuth_deg, turbidity=1.0, sun_irradiance=(5.0, 5.0, 5.0), sun_radius=0.00465, altitude=1.0,
+                 ground_albedo=(0.3, 0.3, 0.3), view_steps=32, light_steps=16, sun_samples=8):
+        self.elevation_deg, self.azimuth_deg, self.turbidity = float(elevation_deg), float(azimuth_deg), float(turbidity)
+        self.sun_irradiance, self.sun_radius, self.altitude = _v3(sun_irradiance), float(sun_radius), float(altitude)
+        self.ground_albedo = _v3(ground_albedo)
+        self.view_steps, self.light_steps, self.sun_samples = int(view_steps), int(light_steps), int(sun_samples)
+
+    def check(self):
+        """what fw_check_sky rejects in a description, as a ValueError, in its order"""
+        f = np.float32
+        if not -f(np.pi / 2) <= f(np.radians(self.elevation_deg)) <= f(np.pi / 2):
+            raise ValueError("elevation_deg must be in [-90, 90]")
+        if not np.isfinite(f(np.radians(self.azimuth_deg))):
+            raise ValueError("azimuth_deg must be finite")
+        if not 0.0 <= f(self.turbidity) <= 64.0:
+            raise ValueError("turbidity must be in [0, 64]")
+        if not (np.all(np.isfinite(self.sun_irradiance)) and np.all(self.sun_irradiance >= 0)):
+            raise ValueError("sun_irradiance must be finite and >= 0")
+        if not 0.0 < f(self.sun_radius) <= f(0.1):
+            raise ValueError("sun_radius must be in (0, 0.1]")
+        if not 1.0 <= f(self.altitude) <= 50000.0:
+            raise ValueError("altitude must be in [1, 50000]")
+        if not (np.all(self.ground_albedo >= 0) and np.all(self.ground_albedo <= 1)):
+            raise ValueError("ground_albedo must be in [0, 1]")
+        if not 1 <= self.view_steps <= 64:
+            raise ValueError("view_steps must be in 1..64")
+        if not 1 <= self.light_steps <= 32:
+            raise ValueError("light_steps must be in 1..32")
+        if not 1 <= self.sun_samples <= 16:
+            raise ValueError("sun_samples must be in 1..16")
+        return self
+
+    def to_abi(self, disc: bool = False) -> A.fw_sky:
+        self.check()
+        s = A.fw_sky()
+        s.sun_elevation, s.sun_azimuth, s.turbidity = np.radians(self.elevation_deg), np.radians(self.azimuth_deg), self.turbidity
+        s.sun_irradiance, s.sun_radius, s.altitude, s.ground_albedo = A.vec3(self.sun_irradiance), self.sun_radius, self.altitude, A.vec3(self.ground_albedo)
+        s.view_steps, s.light_steps, s.sun_samples, s.flags = self.view_steps, self.light_steps, self.sun_samples, A.FW_SKY_DISC if disc else 0
+        return s
+
+    def sun_direction(self) -> np.ndarray:
+        """s, the unit direction towards the sun, float64 from the float32 angles"""
+        return _sky_constants(self)["s"]
+
+    def sun_light(self) -> "DirectionalLight":
+        """the sun as a DirectionalLight of the disc's energy: direction -s, irradiance E0 T(O) (api.sky_sun)"""
+        direction, irradiance = sky_sun(self)
+        return DirectionalLight(direction, irradiance)
+
+
+def _sky_constants(sky) -> dict:
+    """fw_sky's fields widened to float64 and what the host derives from them (fw_runtime.cpp: sky_device)"""
+    a = sky if isinstance(sky, A.fw_sky) else sky.to_abi()
+    el, az = np.float64(a.sun_elevation), np.float64(a.sun_azimuth)
+    ce = np.cos(el)
+    k = dict(s=np.array([ce * np.cos(az), np.sin(el), ce * np.sin(az)]), oy=SKY_RG + np.float64(a.altitude), beta_m=21e-6 * np.float64(a.turbidity),
+             e0=np.array([a.sun_irradiance.x, a.sun_irradiance.y, a.sun_irradiance.z], np.float64),
+             albedo_pi=np.array([a.ground_albedo.x, a.ground_albedo.y, a.ground_albedo.z], np.float64) / np.pi,
+             cos_sr=np.cos(np.float64(a.sun_radius)), radius=np.float64(a.sun_radius), el=el, nv=int(a.view_steps), nl=int(a.light_steps),
+             ss=int(a.sun_samples), flags=int(a.flags))
+    k["beta_me"] = 1.1 * k["beta_m"]
+    k["O"] = np.array([0.0, k["oy"], 0.0])
+    return k
+
+
+def _sky_ground(P, w):
+    """(meets the ground, b, disc, |disc| / P.P where b < 0 else inf: how far the decision is from its threshold)"""
+    b = _dot3(P, w)
+    pp = _dot3(P, P)
+    disc = b * b - (pp - SKY_RG * SKY_RG)
+    return (b < 0.0) & (disc > 0.0), b, disc, np.where(b < 0.0, np.abs(disc) / pp, np.inf)
+
+
+def _sky_depth(P, w, n: int):
+    """D(P, w, N): (dR, dM), P (..., 3), w (3,)"""
+    b = _dot3(P, w)
+    tl = -b + np.sqrt(b * b - (_dot3(P, P) - SKY_RT * SKY_RT))
+    dr, dm = np.zeros_like(tl), np.zeros_like(tl)
+    nd, nn = np.float64(n), np.float64(n * n)
+    for k in range(n):
+        f = (np.float64(k) + 0.5) / nd
+        t, wd = tl * (f * f), tl * (np.float64(2 * k + 1) / nn)
+        Q = P + t[..., None] * w
+        h = np.sqrt(_dot3(Q, Q)) - SKY_RG
+        dr = dr + np.exp(-h / SKY_HR) * wd
+        dm = dm + np.exp(-h / SKY_HM) * wd
+    return dr, dm
+
+
+def _sky_transmittance(k, P):
+    """T(P) (..., 3) and the ground decision's margin"""
+    shadow, _, _, margin = _sky_ground(P, k["s"])
+    lr, lm = _sky_depth(P, k["s"], k["nl"])
+    T = np.exp(-(SKY_BETA_R * lr[..., None] + (k["beta_me"] * lm)[..., None]))
+    return np.where(shadow[..., None], 0.0, T), margin
+
+
+def _sky_along(k, d, terms=None):
+    """the radiance (n, 3) float64 along unit directions d (n, 3) float64, without the disc.  terms: a dict that receives `margin` (the
+    smallest |disc| / P.P of the ground decisions made with b < 0), `tau_max` (the largest optical depth of an unshadowed sample) and,
+    per direction, `scatter` (n, 3), `ground_nocos` (n, 3: the ground's term without its cosine) and `t_max` (n,): what
+    tests/sky_ref.py's bound is made of"""
+    O, s, nv = k["O"], k["s"], k["nv"]
+    n = d.shape[0]
+    Ob = np.broadcast_to(O, d.shape)
+    hit, bo, dg, margin = _sky_ground(Ob, d) if n else (np.zeros(0, bool), np.zeros(0), np.zeros(0), np.zeros(0))
+    tmax = -bo + np.sqrt(bo * bo - (_dot3(O, O) - SKY_RT * SKY_RT))
+    with np.errstate(invalid="ignore"):
+        tmax = np.where(hit, -bo - np.sqrt(dg), tmax)
+    nd, nn = np.float64(nv), np.float64(nv * nv)
+    o_r, o_m = np.zeros(n), np.zeros(n)
+    sr, sm = np.zeros((n, 3)), np.zeros((n, 3))
+    low, tau_max = (np.min(margin) if n else np.inf), 0.0
+    for i in range(nv):
+        f = (np.float64(i) + 0.5) / nd
+        t, wd = tmax * (f * f), tmax * (np.float64(2 * i + 1) / nn)
+        P = O + t[:, None] * d
+        h = np.sqrt(_dot3(P, P)) - SKY_RG
+        hr, hm = np.exp(-h / SKY_HR) * wd, np.exp(-h / SKY_HM) * wd
+        shadow, _, _, m = _sky_ground(P, s)
+        lr, lm = _sky_depth(P, s, k["nl"])
+        ar, am = (o_r + 0.5 * hr) + lr, (o_m + 0.5 * hm) + lm
+        tau = SKY_BETA_R * ar[:, None] + (k["beta_me"] * am)[:, None]
+        att = np.where(shadow[:, None], 0.0, np.exp(-tau))
+        sr, sm = sr + att * hr[:, None], sm + att * hm[:, None]
+        o_r, o_m = o_r + hr, o_m + hm
+        if n:
+            low = min(low, np.min(m))
+            if not np.all(shadow):
+                tau_max = max(tau_max, float(np.max(tau[~shadow])))
+    mu = _dot3(d, s)
+    m1 = 1.0 + mu * mu
+    p_r = (3.0 / (16.0 * np.pi)) * m1
+    x = (1.0 + SKY_G * SKY_G) - (2.0 * SKY_G) * mu
+    p_m = ((3.0 / (8.0 * np.pi)) * ((1.0 - SKY_G * SKY_G) * m1)) / ((2.0 + SKY_G * SKY_G) * (x * np.sqrt(x)))
+    L = k["e0"] * ((sr * SKY_BETA_R) * p_r[:, None] + (sm * k["beta_m"]) * p_m[:, None])
+    scatter, ground_nocos = L.copy(), np.zeros((n, 3))
+    if np.any(hit):
+        q = np.nonzero(hit)[0]
+        G = O + tmax[q, None] * d[q]
+        gl = np.sqrt(_dot3(G, G))
+        cg = np.maximum(_dot3(G / gl[:, None], s), 0.0)
+        T, _ = _sky_transmittance(k, G)
+        through = np.exp(-(SKY_BETA_R * o_r[q, None] + (k["beta_me"] * o_m[q])[:, None]))
+        L[q] = L[q] + (((through * k["albedo_pi"]) * k["e0"]) * T) * cg[:, None]
+        ground_nocos[q] = np.where(cg[:, None] > 0.0, ((through * k["albedo_pi"]) * k["e0"]) * T, 0.0)
+        if q.size:
+            tau_max = max(tau_max, float(np.max(SKY_BETA_R * o_r[q, None] + (k["beta_me"] * o_m[q])[:, None])))
+    if terms is not None:
+        terms["margin"] = min(terms.get("margin", np.inf), float(low))
+        terms["tau_max"] = max(terms.get("tau_max", 0.0), tau_max)
+        terms["scatter"], terms["ground_nocos"], terms["t_max"] = scatter, ground_nocos, tmax
+    return L
+
+
+def sky_sun(sky):
+    """The numpy statement of fw_sky_sun: (direction -s, irradiance E0 T(O)) of the sun as a directional light, float32 (3,) each"""
+    k = _sky_constants(sky)
+    T, _ = _sky_transmittance(k, k["O"])
+    return (-k["s"]).astype(np.float32), (k["e0"] * T).astype(np.float32)
+
+
+def sky_radiance(sky, dirs, disc: bool = None, terms: dict = None) -> np.ndarray:
+    """The numpy statement of fw_sky_radiance: (n, 3) float32 along directions of any length (n, 3); zeros for a zero or non-finite
+    direction.  disc: draw the sun (None: as the fw_sky's flags say, False for an api.SunSky).  terms as _sky_along's, plus `edge`: the
+    smallest |d . s - cos(sun_radius)|."""
+    k = _sky_constants(sky)
+    disc = bool(k["flags"] & A.FW_SKY_DISC) if disc is None else disc
+    r = np.asarray(dirs, np.float32).astype(np.float64).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        l2 = _dot3(r, r)
+        ok = (l2 > 0.0) & np.isfinite(l2)
+        d = r[ok] / np.sqrt(l2[ok])[:, None]
+    L = _sky_along(k, d, terms)
+    if terms is not None:
+        terms["ok"] = ok
+    if disc:
+        T, _ = _sky_transmittance(k, k["O"])
+        mu = _dot3(d, k["s"])
+        L = L + np.where((mu >= k["cos_sr"])[:, None], (k["e0"] * T) / ((2.0 * np.pi) * (1.0 - k["cos_sr"])), 0.0)
+        if terms is not None and mu.size:
+            terms["edge"] = min(terms.get("edge", np.inf), float(np.min(np.abs(mu - k["cos_sr"]))))
+    out = np.zeros((r.shape[0], 3), np.float32)
+    out[ok] = L.astype(np.float32)
+    return out
+
+
+def _sky_map_dirs(xf, jf, w: int, h: int) -> np.ndarray:
+    """panorama_rays' direction of the map points (x + fx, j + fy), float64"""
+    u, v = xf / np.float64(w), 1.0 - jf / np.float64(h)
+    phi, theta = np.pi - (2.0 * np.pi) * u, np.pi * v - np.pi / 2.0
+    ct = np.cos(theta)
+    return np.stack([ct * np.cos(phi), np.sin(theta), ct * np.sin(phi)], axis=-1)
+
+
+def sky_omega_row(w: int, h: int) -> np.ndarray:
+    """Omega_j: the solid angle of one texel of each row (h,)"""
+    y = np.arange(h, dtype=np.float64)
+    return ((2.0 * np.pi) / np.float64(w)) * (np.cos((y * np.pi) / np.float64(h)) - np.cos(((y + 1.0) * np.pi) / np.float64(h)))
+
+
+def sky_env_texel(s, w: int, h: int) -> int:
+    """the texel the FW_ENV_HDR lookup reads for the direction s: env_sample's float32 arithmetic"""
+    f = np.float32
+    d = np.asarray(s, np.float64).astype(f)
+    phi, theta = np.arctan2(d[2], d[0]).astype(f), np.arcsin(np.clip(d[1], f(-1), f(1))).astype(f)
+    u = f(1) - (phi + f(np.pi)) / f(2 * np.pi)
+    v = (theta + f(np.pi / 2)) / f(np.pi)
+    x, y = np.floor(np.maximum(u * f(w), f(0))), np.floor(np.maximum((f(1) - v) * f(h), f(0)))
+    idx = np.floor(np.float64(f(y) * f(w))) + np.float64(x)
+    return int(min(idx, w * h - 1))
+
+
+def sky_disc(sky, width: int, height: int, terms: dict = None):
+    """The disc's share of a map: (ids, gain) — the flat texel ids it covers and E0 T(O) c_t / A (n, 3) float64 for each — and A.  Empty
+    where the sun is below the observer's horizon.  terms receives `edge`: the smallest |d . s - cos(sun_radius)| of a sample."""
+    k = _sky_constants(sky)
+    w, h, S = int(width), int(height), k["ss"]
+    T, _ = _sky_transmittance(k, k["O"])
+    if _sky_ground(k["O"], k["s"])[0]:
+        return np.zeros(0, np.int64), np.zeros((0, 3)), 0.0
+    et = k["e0"] * T
+    # rows farther than sun_radius from the sun's latitude hold no sample (a latitude difference is at most the angle): their n_t is 0
+    theta_edge = np.pi * (1.0 - np.arange(h + 1) / h) - np.pi / 2
+    rows = np.nonzero((theta_edge[:-1] >= k["el"] - k["radius"] - 1e-9) & (theta_edge[1:] <= k["el"] + k["radius"] + 1e-9))[0]
+    off = (np.arange(S, dtype=np.float64) + 0.5) / np.float64(S)
+    x = np.arange(w, dtype=np.float64)
+    counts = np.zeros((h, w), np.int64)
+    for j in rows:
+        xf = (x[:, None, None] + off[None, None, :]) + np.zeros((1, S, 1))
+        jf = (np.float64(j) + off[None, :, None]) + np.zeros((w, 1, S))
+        mu = _dot3(_sky_map_dirs(xf, jf, w, h), k["s"])
+        counts[j] = np.sum(mu >= k["cos_sr"], axis=(1, 2))
+        if terms is not None:
+            terms["edge"] = min(terms.get("edge", np.inf), float(np.min(np.abs(mu - k["cos_sr"]))))
+    omega = sky_omega_row(w, h)
+    s2 = np.float64(S * S)
+    A_ = np.float64(0.0)
+    for j in range(h):
+        A_ = A_ + (np.float64(counts[j].sum()) / s2) * omega[j]
+    if A_ == 0.0:
+        t = sky_env_texel(k["s"], w, h)
+        return np.array([t], np.int64), ((et * 1.0) / omega[t // w])[None, :], float(omega[t // w])
+    ids = np.nonzero(counts.reshape(-1))[0]
+    c = counts.reshape(-1)[ids] / s2
+    return ids, (et[None, :] * c[:, None]) / A_, float(A_)
+
+
+def sky_map(sky, width: int, height: int, disc: bool = None, texels=None, terms: dict = None) -> np.ndarray:
+    """The numpy statement of fw_sky_map: (height, width, 3) float32, row 0 at the top.  disc as sky_radiance's.  texels: flat texel
+    ids to evaluate instead of the whole map -> (n, 3).  terms as _sky_along's and sky_disc's."""
+    k = _sky_constants(sky)
+    w, h = int(width), int(height)
+    if w < 2 or h < 2:
+        raise ValueError("width and height must be >= 2")
+    disc = bool(k["flags"] & A.FW_SKY_DISC) if disc is None else disc
+    ids = np.arange(w * h, dtype=np.int64) if texels is None else np.asarray(texels, np.int64).reshape(-1)
+    j, x = np.divmod(ids, w)
+    L = _sky_along(k, _sky_map_dirs(x + 0.5, j + 0.5, w, h), terms)
+    if terms is not None:
+        terms["radiance"] = L.copy()                            # float64, before the disc
+    if disc:
+        covered, gain, _ = sky_disc(sky, w, h, terms)
+        pos = {int(t): i for i, t in enumerate(ids)}
+        for t, g in zip(covered, gain):
+            if int(t) in pos:
+                L[pos[int(t)]] = L[pos[int(t)]] + g
+    out = L.astype(np.float32)
+    return out.reshape(h, w, 3) if texels is None else out
+
+
+class SunSkyEnv(Environment):
+    """A SunSky as a scene's environment: its width x height map, baked on the GPU (_lib.sky_map) when the scene's descriptor is built
+    and passed as FW_ENV_HDR.  sun: "disc" draws the sun into the map (for FW_FLAG_ENV_SAMPLING to find), "light" leaves it out and adds
+    sky.sun_light() to the scene's lights (a delta sun: sharp shadows through next-event estimation and fw_bake_direct), "none" neither."""
+    SUNS = ("disc", "light", "none")
+
+    def __init__(self, sky: SunSky, width: int = 2048, height: int = 1024, sun: str = "disc"):
+        if sun not in self.SUNS:
+            raise ValueError('sun must be "disc", "light" or "none"')
+        if int(width) < 2 or int(height) < 2:
+            raise ValueError("width and height must be >= 2")
+        self.sky, self.width, self.height, self.sun = sky.check(), int(width), int(height), sun
+
+    def bake(self, device: int = 0) -> np.ndarray:
+        """the (height, width, 3) float32 map; raises _lib's no-device error without a GPU"""
+        from . import _lib
+        return _lib.sky_map(self.sky.to_abi(disc=self.sun == "disc"), self.width, self.height, device=device)
+
+
 # --------------------------------------------------------------------------- RenderObject / Scene
 class RenderObject:
     """src/scene.rs:270-334"""
@@ -596,6 +897,13 @@ class Scene:
         return self.materials[idx]
 
     def set_environment(self, env: Environment):
+        """A SunSkyEnv with sun="light" brings its sun: sky.sun_light() joins self.lights, and leaves with the environment that brought it."""
+        brought = getattr(self, "_sky_light", None)
+        self.lights = [l for l in self.lights if l is not brought]
+        self._sky_light = None
+        if isinstance(env, SunSkyEnv) and env.sun == "light":
+            self._sky_light = env.sky.sun_light()
+            self.lights.append(self._sky_light)
         self.environment = env
 
     # ---- flatten to the C ABI -------------------------------------------------
@@ -744,6 +1052,12 @@ class SceneDesc:
             env.hdr_h, env.hdr_w = e.pixels.shape[0], e.pixels.shape[1]
             env.hdr_rgb = e.pixels.ctypes.data_as(C.POINTER(C.c_float))
             self._keep.append(e.pixels)
+        elif isinstance(e, SunSkyEnv):
+            pixels = e.bake()                                   # on the GPU, once per description; no device: _lib's error
+            env.kind = A.FW_ENV_HDR
+            env.hdr_h, env.hdr_w = pixels.shape[0], pixels.shape[1]
+            env.hdr_rgb = pixels.ctypes.data_as(C.POINTER(C.c_float))
+            self._keep.append(pixels)
         else:
             raise TypeError(f"unknown environment {type(e).__name__}")
 

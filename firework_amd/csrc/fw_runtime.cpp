@@ -20,6 +20,7 @@
 #include "fw_probe_place.h"
 #include "fw_probe_radiance.h"
 #include "fw_direct.h"
+#include "fw_sky.h"
 #include "fw_defer_pretest.h"
 
 #include <algorithm>
@@ -5278,6 +5279,124 @@ int probe_shade_glossy_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a,
     });
 }
 
+// ---- SunSky: fw_check_sky, fw_sky_map, fw_sky_radiance, fw_sky_sun --------------------------------------------------------
+int sky_check(const fw_sky *s) {
+    if (!s) return fail(FW_ERR_BAD_ARG, "null argument");
+    const float half_pi = 1.5707964f;                                                 // float(pi / 2): the largest elevation a float can ask for
+    if (!(s->sun_elevation >= -half_pi && s->sun_elevation <= half_pi)) return fail(FW_ERR_BAD_ARG, "sun_elevation must be in [-pi/2, pi/2]");
+    if (!std::isfinite(s->sun_azimuth)) return fail(FW_ERR_BAD_ARG, "sun_azimuth must be finite");
+    if (!(s->turbidity >= 0.f && s->turbidity <= 64.f)) return fail(FW_ERR_BAD_ARG, "turbidity must be in [0, 64]");
+    for (float v : {s->sun_irradiance.x, s->sun_irradiance.y, s->sun_irradiance.z})
+        if (!(v >= 0.f && std::isfinite(v))) return fail(FW_ERR_BAD_ARG, "sun_irradiance must be finite and >= 0");
+    if (!(s->sun_radius > 0.f && s->sun_radius <= 0.1f)) return fail(FW_ERR_BAD_ARG, "sun_radius must be in (0, 0.1]");
+    if (!(s->altitude >= 1.f && s->altitude <= 50000.f)) return fail(FW_ERR_BAD_ARG, "altitude must be in [1, 50000]");
+    for (float v : {s->ground_albedo.x, s->ground_albedo.y, s->ground_albedo.z})
+        if (!(v >= 0.f && v <= 1.f)) return fail(FW_ERR_BAD_ARG, "ground_albedo must be in [0, 1]");
+    if (s->view_steps < 1 || s->view_steps > 64) return fail(FW_ERR_BAD_ARG, "view_steps must be in 1..64");
+    if (s->light_steps < 1 || s->light_steps > 32) return fail(FW_ERR_BAD_ARG, "light_steps must be in 1..32");
+    if (s->sun_samples < 1 || s->sun_samples > 16) return fail(FW_ERR_BAD_ARG, "sun_samples must be in 1..16");
+    if (s->flags & ~FW_SKY_DISC) return fail(FW_ERR_BAD_ARG, "flags has an unknown bit");
+    return FW_OK;
+}
+
+// the sky as the kernels read it; `below`: the sun is under the observer's horizon (no disc, no light)
+fw::DSky sky_device(const fw_sky *s, bool &below) {
+    fw::DSky K{};
+    const double el = (double)s->sun_elevation, az = (double)s->sun_azimuth, ce = std::cos(el);
+    K.s[0] = ce * std::cos(az); K.s[1] = std::sin(el); K.s[2] = ce * std::sin(az);
+    K.oy = fw::SKY_RG + (double)s->altitude;
+    K.beta_r[0] = 5.8e-6; K.beta_r[1] = 13.5e-6; K.beta_r[2] = 33.1e-6;
+    K.beta_m = 21e-6 * (double)s->turbidity; K.beta_me = 1.1 * K.beta_m;
+    const double e0[3] = {s->sun_irradiance.x, s->sun_irradiance.y, s->sun_irradiance.z};
+    const double al[3] = {s->ground_albedo.x, s->ground_albedo.y, s->ground_albedo.z};
+    K.cos_sr = std::cos((double)s->sun_radius);
+    K.nv = s->view_steps; K.nl = s->light_steps; K.ss = s->sun_samples; K.flags = s->flags;
+    double T[3], b, disc;
+    fw::sky_sun_transmittance(K, 0.0, K.oy, 0.0, T);
+    below = fw::sky_ground(0.0, K.oy, 0.0, K.s[0], K.s[1], K.s[2], b, disc);
+    for (int c = 0; c < 3; c++) {
+        K.e0[c] = e0[c]; K.albedo_pi[c] = al[c] / fw::SKY_PI;
+        K.et[c] = e0[c] * T[c];
+        K.disc_l[c] = K.et[c] / ((2.0 * fw::SKY_PI) * (1.0 - K.cos_sr));
+    }
+    return K;
+}
+
+// the rows k_sky_sun visits, its rejection bound, and the texel the FW_ENV_HDR lookup reads for s (env_sample's float32 arithmetic)
+fw::DSkyDisc sky_disc(const fw_sky *s, const fw::DSky &K, uint32_t W, uint32_t H) {
+    fw::DSkyDisc D{};
+    const double PI = fw::SKY_PI, el = (double)s->sun_elevation, reach = (double)s->sun_radius + PI / (double)H;
+    const double top = (double)H * (0.5 - (el + reach) / PI) - 0.5, bottom = (double)H * (0.5 - (el - reach) / PI) - 0.5;
+    D.row_lo = (uint32_t)std::min<double>(std::max(std::floor(top) - 1.0, 0.0), (double)H - 1.0);
+    D.row_hi = (uint32_t)std::min<double>(std::max(std::ceil(bottom) + 1.0, 0.0), (double)H - 1.0);
+    D.cos_reject = std::cos(std::min(PI, reach + 2.0 * PI / (double)W));
+    const float dx = (float)K.s[0], dy = (float)K.s[1], dz = (float)K.s[2], pi_f = (float)PI, two_pi_f = (float)(2.0 * PI), half_pi_f = (float)(PI / 2.0);
+    const float phi = std::atan2(dz, dx), theta = std::asin(std::min(std::max(dy, -1.f), 1.f));
+    const float u = 1.f - (phi + pi_f) / two_pi_f, v = (theta + half_pi_f) / pi_f;
+    const double x = std::floor((double)std::max(u * (float)W, 0.f)), y = std::floor((double)std::max((1.f - v) * (float)H, 0.f));
+    const double idx = std::floor((double)((float)y * (float)W)) + x;
+    D.fallback = (uint32_t)std::min(idx, (double)W * (double)H - 1.0);
+    return D;
+}
+
+// fw_sky_map: fw_model_rays' shape — device output: the launches into the caller's memory; host output — host_slabs of rows
+int sky_map_impl(const fw_sky *s, int device, uint32_t W, uint32_t H, float *rgb, int on_device, void *stream_) {
+    if (!s || !rgb) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = sky_check(s)) return rc;
+    if (W < 2 || H < 2) return fail(FW_ERR_BAD_ARG, "width and height must be >= 2");
+    if (on_device && ((uintptr_t)rgb & 3u)) return fail(FW_ERR_BAD_ARG, "rgb must be 4-byte aligned");
+    if ((uint64_t)W * H >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "W x H must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n_cus = device_cus(device);
+    bool below = false;
+    const fw::DSky K = sky_device(s, below);
+    const fw::DSkyDisc D = sky_disc(s, K, W, H);
+    const bool disc = (s->flags & FW_SKY_DISC) && !below;
+    auto launch = [&](uint32_t first_row, uint32_t k, float *d_rgb) {
+        fw::launch_sky_map(stream, n_cus, K, W, H, first_row, k, d_rgb);
+        if (disc) fw::launch_sky_sun(stream, K, D, W, H, first_row, k, d_rgb);
+    };
+    if (on_device) {
+        launch(0u, H, rgb);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+    return host_slabs(stream, device, H, (size_t)W * 12, rgb, launch);
+}
+
+// fw_sky_radiance: fw_ao_rays' shape — device arrays: one launch over the caller's memory; host arrays: slabs of directions, packed
+int sky_radiance_impl(const fw_sky *s, int device, uint32_t n, const float *dirs, uint32_t stride, float *rgb, int on_device, void *stream_) {
+    if (!s || !dirs || !rgb) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = sky_check(s)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (on_device && (((uintptr_t)dirs | (uintptr_t)rgb) & 3u)) return fail(FW_ERR_BAD_ARG, "device arrays must be 4-byte aligned");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n_cus = device_cus(device);
+    bool below = false;
+    const fw::DSky K = sky_device(s, below);
+    Staged st(device, stream, on_device != 0);
+    HostSlabs sl(st, n, 24);
+    const int a_dirs = sl.in(dirs, 12, stride), a_rgb = sl.out(rgb, 12);
+    if (int rc = st.up()) return rc;
+    return sl.run([&](uint32_t, uint32_t k) { fw::launch_sky_dirs(stream, n_cus, K, k, sl.ptr<const float>(a_dirs), sl.stride(a_dirs), sl.ptr<float>(a_rgb)); });
+}
+
+int sky_sun_impl(const fw_sky *s, fw_light *out) {
+    if (!s || !out) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = sky_check(s)) return rc;
+    bool below = false;
+    const fw::DSky K = sky_device(s, below);
+    *out = fw_light{};
+    out->kind = FW_LIGHT_DIRECTIONAL;
+    out->direction = fw_vec3{(float)-K.s[0], (float)-K.s[1], (float)-K.s[2]};
+    out->intensity = fw_vec3{(float)K.et[0], (float)K.et[1], (float)K.et[2]};
+    return FW_OK;
+}
+
 } // namespace
 
 // =========================================================================================================
@@ -5811,6 +5930,30 @@ int fw_bake_direct(fw_scene *scene, const fw_direct *direct, const fw_trace_para
     try { return bake_direct_impl(scene, direct, tp, n, positions, normals, stride_floats, ids, view, view_stride_floats, spec, first_round, rounds, sums, out, stats); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_direct"); }
+}
+
+int fw_check_sky(const fw_sky *sky) {
+    try { return sky_check(sky); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_check_sky"); }
+}
+
+int fw_sky_map(const fw_sky *sky, int device, uint32_t width, uint32_t height, float *rgb, int on_device, void *stream) {
+    try { return sky_map_impl(sky, device, width, height, rgb, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_sky_map"); }
+}
+
+int fw_sky_radiance(const fw_sky *sky, int device, uint32_t n, const float *dirs, uint32_t stride_floats, float *rgb, int on_device, void *stream) {
+    try { return sky_radiance_impl(sky, device, n, dirs, stride_floats, rgb, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_sky_radiance"); }
+}
+
+int fw_sky_sun(const fw_sky *sky, fw_light *out) {
+    try { return sky_sun_impl(sky, out); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_sky_sun"); }
 }
 
 int fw_probe_irradiance_vis(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias, int device,

@@ -8,7 +8,10 @@ reference (Rect3d, ConstantMedium, Checker/Metal/Dielectric/Isotropic) follow th
 
 Beyond the reference: an optional top-level `lights:` list, each entry tagged `light`: `PointLight {position,
 intensity}`, `SpotLight {position, direction, intensity, inner_deg, outer_deg}`, `DirectionalLight {direction, irradiance}`.  A scene
-without lights is written without the key, so files of the reference's format load and dump as they did.
+without lights is written without the key, so files of the reference's format load and dump as they did.  And one more `environment`
+tag: `SunSkyEnv {width, height, sun: disc | light | none, sky: {elevation_deg, azimuth_deg, turbidity, sun_irradiance,
+sun_radius, altitude, ground_albedo, view_steps, light_steps, sun_samples}}`; only the two angles are required.  With `sun: light` the
+sun's DirectionalLight is the environment's own: it is not written into `lights:` and comes back when the file is loaded.
 """
 import os
 
@@ -121,6 +124,12 @@ def _environment(d):
         return A.ColorEnv(_v3(d["color"]))
     if k == "SkyEnv":
         return A.SkyEnv(_v3(d["zenith_color"]), _v3(d["horizon_color"]))
+    if k == "SunSkyEnv":        # the map is baked when the scene's descriptor is built: loading needs no device
+        s = d["sky"]
+        opt = {n: (_v3(s[n]) if n in ("sun_irradiance", "ground_albedo") else int(s[n]) if n.endswith(("_steps", "_samples")) else float(s[n]))
+               for n in ("turbidity", "sun_irradiance", "sun_radius", "altitude", "ground_albedo", "view_steps", "light_steps", "sun_samples") if n in s}
+        return A.SunSkyEnv(A.SunSky(float(s["elevation_deg"]), float(s["azimuth_deg"]), **opt), int(d.get("width", 2048)), int(d.get("height", 1024)),
+                           str(d.get("sun", "disc")))
     raise ValueError(f"unknown environment tag {k!r} (user-defined environments cannot cross to the GPU)")
 
 
@@ -260,8 +269,15 @@ def scene_to_dict(scene):
         env = {"environment": "ColorEnv", "color": _v3d(e.color)}
     elif isinstance(e, A.SkyEnv):
         env = {"environment": "SkyEnv", "zenith_color": _v3d(e.zenith_color), "horizon_color": _v3d(e.horizon_color)}
+    elif isinstance(e, A.SunSkyEnv):
+        k = e.sky
+        env = {"environment": "SunSkyEnv", "width": int(e.width), "height": int(e.height), "sun": e.sun,
+               "sky": {"elevation_deg": float(k.elevation_deg), "azimuth_deg": float(k.azimuth_deg), "turbidity": float(k.turbidity),
+                       "sun_irradiance": _v3s(k.sun_irradiance), "sun_radius": float(k.sun_radius), "altitude": float(k.altitude),
+                       "ground_albedo": _v3s(k.ground_albedo), "view_steps": int(k.view_steps), "light_steps": int(k.light_steps),
+                       "sun_samples": int(k.sun_samples)}}
     else:
-        raise TypeError("only ColorEnv / SkyEnv have a YAML form in the reference")
+        raise TypeError("only ColorEnv / SkyEnv / SunSkyEnv have a YAML form (an HdrEnvironment is an array, not a description)")
     out = {
         "render_objects": [{"obj": _shape_d(ro.obj), "position": _v3d(ro._position),
                             "rotation": {"s": float(ro.rotation.s), "bv": {"xy": float(ro.rotation.xy), "xz": float(ro.rotation.xz),
@@ -270,8 +286,9 @@ def scene_to_dict(scene):
         "materials": [_material_d(m) for m in scene.materials],
         "environment": env,
     }
-    if getattr(scene, "lights", None):
-        out["lights"] = [_light_d(l) for l in scene.lights]
+    lights = [l for l in getattr(scene, "lights", None) or [] if l is not getattr(scene, "_sky_light", None)]   # a SunSkyEnv's own sun comes back with it
+    if lights:
+        out["lights"] = [_light_d(l) for l in lights]
     return out
 
 

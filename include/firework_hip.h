@@ -1228,6 +1228,77 @@ int fw_bake_direct(fw_scene *scene, const fw_direct *direct, const fw_trace_para
                    uint32_t stride_floats, const uint32_t *ids, const float *view, uint32_t view_stride_floats, const float *spec,
                    uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
 
+/* ---- SunSky: an analytic sun-and-sky environment (additive at ABI 8) ----------------------------------------------------
+   Outdoor light from six numbers: single scattering of the sun through a Rayleigh and Mie atmosphere around a spherical ground, as an
+   equirectangular map that loads as FW_ENV_HDR (fw_sky_map), along given directions (fw_sky_radiance), and the sun itself as a
+   FW_LIGHT_DIRECTIONAL of the same energy (fw_sky_sun).  Everything is float64 from the float32 fields, every operation rounded as
+   written (no contraction), one rounding to float32 at the end.  api.sky_radiance, api.sky_map and api.sky_sun are the numpy statements.
+     Constants, metres: Rg = 6360000, Rt = 6420000, H_R = 7994, H_M = 1200, beta_R = (5.8e-6, 13.5e-6, 33.1e-6), beta_M = 21e-6 x
+         turbidity with extinction beta_Me = 1.1 beta_M, g = 0.76.  The observer is O = (0, Rg + altitude, 0); the sun's direction is
+         s = (cos el cos az, sin el, cos el sin az).  Dot products are (x x + y y) + z z.
+     Ground test of (P, w): b = P . w, disc = b b - (P . P - Rg Rg); the ray meets the ground iff b < 0 and disc > 0.
+     Optical depth D(P, w, N) = (dR, dM): t_l = -b + sqrt(b b - (P . P - Rt Rt)); for k = 0 .. N - 1 in order: f = (k + 0.5) / N,
+         t = t_l (f f), width = t_l ((2 k + 1) / (N N)), Q = P + t w, h = sqrt(Q . Q) - Rg, dR += exp(-h / H_R) width, dM += exp(-h /
+         H_M) width.  The spacing is quadratic: the samples crowd towards P, where the air is.
+     T(P), per channel: exp(-(beta_R lR + beta_Me lM)) with (lR, lM) = D(P, s, NL), or 0 where (P, s) meets the ground.
+     Radiance along the unit direction d: t_max = the atmosphere's exit from O (t_l of (O, d)), or where (O, d) meets the ground the hit
+         -b - sqrt(disc).  oR = oM = 0; for i = 0 .. NV - 1 in order: f, t and width as above with t_max and NV, P = O + t d, h as above,
+         hr = exp(-h / H_R) width, hm = exp(-h / H_M) width, (lR, lM) = D(P, s, NL), aR = (oR + 0.5 hr) + lR, aM = (oM + 0.5 hm) + lM,
+         att_c = exp(-(beta_R,c aR + beta_Me aM)) or 0 where (P, s) meets the ground, S_R,c += att_c hr, S_M,c += att_c hm, then oR += hr,
+         oM += hm.  With mu = d . s, m = 1 + mu mu, x = (1 + g g) - (2 g) mu:  p_R = (3 / (16 pi)) m,  p_M = ((3 / (8 pi)) ((1 - g g) m))
+         / ((2 + g g) (x sqrt x)) — no pow —  and  L_c = E0_c ((S_R,c beta_R,c) p_R + (S_M,c beta_M) p_M).  A ground hit at G = O + t_max d
+         adds (((exp(-(beta_R,c oR + beta_Me oM)) (albedo_c / pi)) E0_c) T_c(G)) max((G / |G|) . s, 0).
+         Simplifications: single scattering, no ozone, the ground is lit by the sun alone, no limb darkening.
+     Map.  Texel (x, row j) of the W x H map, row 0 at the top, is the radiance along its centre's direction by panorama_rays' formula,
+         the exact inverse of the FW_ENV_HDR lookup: u = (x + 0.5) / W, v = 1 - (j + 0.5) / H, phi = pi - (2 pi) u, theta = pi v - pi /
+         2, d = (cos theta cos phi, sin theta, cos theta sin phi).
+     Disc (FW_SKY_DISC, and only where (O, s) does not meet the ground).  n_t = the number of the S x S directions of texel t at the
+         offsets ((a + 0.5) / S, (b + 0.5) / S) in place of (0.5, 0.5) with d . s >= cos(sun_radius), c_t = n_t / (S S).  Omega_j = ((2
+         pi) / W) (cos((j pi) / H) - cos(((j + 1) pi) / H)) is the solid angle of a texel of row j.  A = sum over the rows j in ascending
+         order, from 0.0, of (N_j / (S S)) Omega_j with N_j = the exact integer sum of n_t over the row.  If A = 0, the texel that the
+         FW_ENV_HDR lookup reads for s (float32, as env_sample computes it) takes c = 1 and A = its Omega.  Texel t then holds
+         float(L_t + (E0 T(O) c_t) / A): sum_t disc_t Omega_t = E0 T(O) at every resolution, the energy of fw_sky_sun's light.
+     Directions (fw_sky_radiance): d = the three floats divided by their float64 length; a zero or non-finite length gives (0, 0, 0).
+         With FW_SKY_DISC a direction with d . s >= cos(sun_radius) gains E0 T(O) / ((2 pi) (1 - cos(sun_radius))).
+     Two runs are bit-equal; a texel's value depends on no other texel. */
+#define FW_SKY_DISC 1u
+typedef struct fw_sky {
+    float sun_elevation, sun_azimuth; /* radians; elevation in [-pi/2, pi/2]; azimuth is panorama_rays' phi */
+    float turbidity;                  /* multiplies the Mie coefficient; [0, 64] */
+    fw_vec3 sun_irradiance;           /* E0 above the atmosphere, on a plane facing the sun; each >= 0, finite: the exposure */
+    float sun_radius;                 /* angular radius of the disc, radians, (0, 0.1]; the sun's is 0.00465 */
+    float altitude;                   /* the observer's height in metres, [1, 50000] */
+    fw_vec3 ground_albedo;            /* [0, 1] each */
+    uint32_t view_steps, light_steps; /* NV in 1..64 (default 32), NL in 1..32 (default 16) */
+    uint32_t sun_samples;             /* S in 1..16: S x S samples per texel for the disc's coverage (default 8) */
+    uint32_t flags;                   /* FW_SKY_DISC: draw the sun into the map and the directions */
+} fw_sky;
+
+/* fw_check_sky: FW_OK, or FW_ERR_BAD_ARG for, in this order: a NULL sky; sun_elevation not finite or outside [-pi/2, pi/2]; sun_azimuth
+   not finite; turbidity outside [0, 64]; a sun_irradiance component negative or not finite; sun_radius outside (0, 0.1]; altitude
+   outside [1, 50000]; a ground_albedo component outside [0, 1]; view_steps outside 1..64; light_steps outside 1..32; sun_samples
+   outside 1..16; flags with an unknown bit.  A NaN is outside every range.  Touches no device. */
+int fw_check_sky(const fw_sky *sky);
+
+/* fw_sky_map: the W x H x 3 floats of the map.  `rgb` is host memory — filled in slabs of rows through device scratch of the call's own,
+   freed on every path — or with on_device device memory on `device`, written on `stream` and complete on return; overwritten.
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL sky or rgb; fw_check_sky's refusals; width or height < 2;
+   with on_device rgb not 4-byte aligned; FW_ERR_UNSUPPORTED for W x H >= 2^31; then FW_ERR_NO_DEVICE without a GPU (rgb untouched),
+   and FW_ERR_BAD_ARG for a device index out of range. */
+int fw_sky_map(const fw_sky *sky, int device, uint32_t width, uint32_t height, float *rgb, int on_device, void *stream);
+
+/* fw_sky_radiance: rgb[q] = the radiance along the three floats at dirs + q x stride_floats, q < n; a ray buffer is read in place at
+   rays + 3 with stride 6.  Host arrays or with on_device device arrays, as fw_sky_map.  Errors, in this order and before HIP is called:
+   FW_ERR_BAD_ARG for a NULL sky, dirs or rgb; fw_check_sky's refusals; n == 0; stride_floats < 3; with on_device an array not 4-byte
+   aligned; then FW_ERR_NO_DEVICE (rgb untouched), and FW_ERR_BAD_ARG for a device index out of range. */
+int fw_sky_radiance(const fw_sky *sky, int device, uint32_t n, const float *dirs, uint32_t stride_floats, float *rgb, int on_device,
+                    void *stream);
+
+/* fw_sky_sun: the sun as a light: kind FW_LIGHT_DIRECTIONAL, direction float(-s), intensity float(E0 T(O)) — zeros where the sun is
+   below the observer's horizon — every other field 0.  Host only: touches no device.  FW_ERR_BAD_ARG for a NULL sky or out, and
+   fw_check_sky's refusals. */
+int fw_sky_sun(const fw_sky *sky, fw_light *out);
+
 /* ---- probe relocation and classification: move probes out of geometry (additive at ABI 8) -----------------------------
    A grid is laid over a scene without looking at it: some probes land inside objects or a hair from a wall.  A probe's own rays tell:
    fw_probe_survey reduces one round's hits to "how much of what the probe sees is a back face, and where is the nearest surface",
