@@ -66,7 +66,12 @@ GgxMat highlights without a path, fw_bake_direct; -s is not used
 the sun EL degrees above the horizon at azimuth AZ degrees, baked on the device into a W x H map, default 2048,1024, fw_sky_map,
 DESIGN.md §9x; the sun is a disc in the map, the default, which --env-sampling finds; or a directional light of the same energy beside
 a map without it, which --light-sampling and --direct-light find; or absent; --sun light refuses --env-sampling; combines with every
-other flag)."""
+other flag).
+--probe-lit FILE --probe-split-sum [N_MU,N_RHO] [--probe-energy] (shades GgxMat and MetalMat pixels with the split sum's BRDF term,
+F0 A + B from an N_MU x N_RHO table of the GGX directional albedo, default 64,64, each in 2..256, baked on the device in the call,
+fw_ggx_table and fw_probe_shade_split, DESIGN.md §9y, in the place of the bare Schlick term: a rough conductor is no longer several
+times too bright; --probe-energy also multiplies by 1 + F0 (1 / (A + B) - 1), the single-lobe energy compensation; both need a file
+that holds radiance maps and refuse --probe-no-radiance)."""
 import argparse
 import sys
 import time
@@ -166,7 +171,24 @@ def main(argv=None):
     ap.add_argument("--sun-sky-size", default=None, metavar="W,H", help="with --sun-sky: the size of the baked map (default 2048,1024)")
     ap.add_argument("--sun", choices=("disc", "light", "none"), default=None,
                     help="with --sun-sky: the sun as a disc in the map (default), as a directional light beside it, or not at all")
+    ap.add_argument("--probe-split-sum", nargs="?", const="64,64", default=None, metavar="N_MU,N_RHO",
+                    help="with --probe-lit: shade glossy pixels with the split sum's BRDF term from an N_MU x N_RHO GGX albedo table (default 64,64)")
+    ap.add_argument("--probe-energy", action="store_true", help="with --probe-split-sum: the single-lobe energy compensation")
     opt = ap.parse_args(argv)
+    split_sum = None
+    if opt.probe_split_sum is not None:
+        if opt.probe_lit is None:
+            ap.error("--probe-split-sum needs --probe-lit")
+        if opt.probe_no_radiance:
+            ap.error("--probe-split-sum cannot be combined with --probe-no-radiance: the term multiplies the radiance maps' lookup")
+        try:
+            split_sum = [int(x) for x in opt.probe_split_sum.split(",")]
+        except ValueError:
+            split_sum = []
+        if len(split_sum) != 2 or not all(2 <= x <= 256 for x in split_sum):
+            ap.error("--probe-split-sum needs N_MU,N_RHO, each in 2..256")
+    elif opt.probe_energy:
+        ap.error("--probe-energy needs --probe-split-sum")
     sun_sky = None
     if opt.sun_sky is not None:
         try:
@@ -429,6 +451,8 @@ def main(argv=None):
                 raise ValueError(f"placement has shape {probe_placement.shape}, the grid {probe_grid.n_probes} probes")
             if probe_radiance is not None and probe_maps.shape != (probe_grid.n_probes, probe_radiance.texels, 4):
                 raise ValueError(f"radiance has shape {probe_maps.shape}, the grid {probe_grid.n_probes} probes of {probe_radiance.texels} texels")
+            if split_sum is not None and probe_radiance is None:
+                raise ValueError("--probe-split-sum needs radiance maps and the file holds none (bake it with --probe-radiance R)")
         except (OSError, ValueError, zipfile.BadZipFile) as e:
             print(f"firework: error: --probe-lit {opt.probe_lit}: {e}", file=sys.stderr)
             return 2
@@ -486,9 +510,14 @@ def main(argv=None):
                      grid_counts=np.array(probes.grid_counts, np.int64), **extra)
         return 0
     if probe_grid is not None:
+        ggx_table = None
+        if split_sum is not None:
+            from .api import GgxTable
+            ggx_table = GgxTable(split_sum[0], split_sum[1], energy=opt.probe_energy)
         render = renderer.render_probe_lit(scene, probe_grid, probe_sh, opt.aov_samples, device=opt.device, depth=probe_depth, moments=probe_moments,
                                            normal_bias=0.0 if opt.probe_normal_bias is None else opt.probe_normal_bias,
-                                           placement=probe_placement, radiance=probe_radiance, maps=probe_maps, direct=direct_light(opt)).rgb8
+                                           placement=probe_placement, radiance=probe_radiance, maps=probe_maps, direct=direct_light(opt),
+                                           ggx_table=ggx_table).rgb8
         print(f"Finished Rendering in {int(time.time() - start)} s")
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)

@@ -301,5 +301,26 @@ PROBE_RADIANCE_PROTOTYPES = {
 }
 
 
+# the split sum's BRDF term: a GGX albedo table (include/firework_hip.h: fw_check_ggx_quad, fw_ggx_terms, fw_ggx_table,
+# fw_ggx_table_lookup, fw_probe_shade_split)
+FW_SPLIT_ENERGY = 1
+
+
+class fw_ggx_quad(C.Structure):
+    _fields_ = [("m1", u32), ("m2", u32)]
+
+
+# the five prototypes (argument types; every one returns int), applied by _lib.load
+GGX_TABLE_PROTOTYPES = {
+    "fw_check_ggx_quad": [C.POINTER(fw_ggx_quad)],
+    "fw_ggx_terms": [C.POINTER(fw_ggx_quad), C.c_int, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_ggx_table": [C.POINTER(fw_ggx_quad), C.c_int, u32, u32, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_ggx_table_lookup": [C.c_int, u32, u32, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_probe_shade_split": [C.POINTER(fw_probe_grid), C.c_void_p, C.POINTER(fw_probe_radiance), C.c_void_p, C.POINTER(fw_probe_depth), C.c_void_p,
+                             f32, C.c_void_p, C.POINTER(fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, u32, u32,
+                             C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
 def vec3(v):
     return fw_vec3(float(v[0]), float(v[1]), float(v[2]))

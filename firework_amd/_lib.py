@@ -131,7 +131,8 @@ def load(preload=False, device=None):
     lib.fw_probe_shade.argtypes = [C.POINTER(A.fw_probe_grid), C.c_void_p, C.POINTER(A.fw_probe_shade_params), C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
     for name, argtypes in (list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()) + list(A.PROBE_PLACE_PROTOTYPES.items())
-                           + list(A.PROBE_RADIANCE_PROTOTYPES.items()) + list(A.DIRECT_PROTOTYPES.items()) + list(A.SKY_PROTOTYPES.items())):
+                           + list(A.PROBE_RADIANCE_PROTOTYPES.items()) + list(A.DIRECT_PROTOTYPES.items()) + list(A.SKY_PROTOTYPES.items())
+                           + list(A.GGX_TABLE_PROTOTYPES.items())):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
@@ -1331,6 +1332,162 @@ def sky_sun(sky):
     out = A.fw_light()
     _check(lib, lib.fw_sky_sun(C.byref(s), C.byref(out)))
     return out
+
+
+def _quad_abi(quad):
+    """a fw_ggx_quad from an api.GgxTable, an (m1, m2) pair or a fw_ggx_quad (copied)"""
+    if hasattr(quad, "to_abi"):
+        return quad.to_abi()
+    if isinstance(quad, A.fw_ggx_quad):
+        return A.fw_ggx_quad.from_buffer_copy(quad)
+    return A.fw_ggx_quad(int(quad[0]), int(quad[1]))
+
+
+def check_ggx_quad(quad):
+    """fw_check_ggx_quad: raises FireworkError for a quadrature the table calls refuse; touches no device"""
+    lib = load()
+    q = _quad_abi(quad)
+    _check(lib, lib.fw_check_ggx_quad(C.byref(q)))
+
+
+def _pairs_arg(mu, rho, device):
+    """(n, mu, rho, on_device) of a list of (mu, rho) pairs: contiguous float32 (n,) numpy arrays or tensors on cuda:`device`"""
+    if type(mu).__module__.startswith("torch"):
+        import torch
+        n = int(mu.shape[0])
+        _check_device_tensor(mu, (n,), torch.float32, device, "mu")
+        _check_device_tensor(rho, (n,), torch.float32, device, "rho")
+        return n, mu, rho, True
+    m = np.ascontiguousarray(np.asarray(mu, np.float32).reshape(-1))
+    r = np.ascontiguousarray(np.asarray(rho, np.float32).reshape(-1))
+    if m.shape != r.shape:
+        raise ValueError("mu and rho must have the same shape (n,)")
+    return int(m.shape[0]), m, r, False
+
+
+def ggx_terms(quad, mu, rho, device=0, out=None, stream=None):
+    """fw_ggx_terms: the (n, 2) float32 terms (A, B) of GgxMat's directional albedo F0 A + B at the pairs (mu[q], rho[q]), integrated on
+    the device with the quadrature `quad` (an api.GgxTable, an (m1, m2) pair or a fw_ggx_quad).  numpy arrays: returns a numpy array.
+    Contiguous float32 tensors on cuda:`device`: evaluated on `stream` (default: the current torch stream) where they lie; returns a
+    device tensor.  out: an array or tensor of that shape to fill instead."""
+    lib = load()
+    q = _quad_abi(quad)
+    n, m, r, on_device = _pairs_arg(mu, rho, device)
+    if on_device:
+        import torch
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float32, device=m.device)
+        _check_device_tensor(out, (n, 2), torch.float32, device, "out")
+        _check(lib, lib.fw_ggx_terms(C.byref(q), int(device), n, m.data_ptr(), r.data_ptr(), out.data_ptr(), 1, _stream_arg(stream, m.device)))
+        return out
+    if out is None:
+        out = np.empty((n, 2), np.float32)
+    _host_f32(out, (n, 2), "out")
+    _check(lib, lib.fw_ggx_terms(C.byref(q), int(device), n, m.ctypes.data, r.ctypes.data, out.ctypes.data, 0, None))
+    return out
+
+
+def ggx_table(quad, n_mu=None, n_rho=None, device=0, out=None, stream=None):
+    """fw_ggx_table: the (n_rho, n_mu, 2) float32 table of the terms (A, B) at the texel centres, baked on the device.  quad: an
+    api.GgxTable (whose n_mu and n_rho are the defaults), an (m1, m2) pair or a fw_ggx_quad.  Returns a numpy array; out: a contiguous
+    float32 device tensor of that shape on cuda:`device` to fill instead, on `stream` (default: the current torch stream); returned."""
+    lib = load()
+    q = _quad_abi(quad)
+    if (n_mu is None or n_rho is None) and not hasattr(quad, "n_mu"):
+        raise ValueError("n_mu and n_rho are needed with a quadrature that is not an api.GgxTable")
+    n_mu = int(quad.n_mu if n_mu is None else n_mu)
+    n_rho = int(quad.n_rho if n_rho is None else n_rho)
+    shape = (n_rho, n_mu, 2)
+    if out is not None:
+        import torch
+        _check_device_tensor(out, shape, torch.float32, device, "out")
+        _check(lib, lib.fw_ggx_table(C.byref(q), int(device), n_mu, n_rho, out.data_ptr(), 1, _stream_arg(stream, out.device)))
+        return out
+    table = np.empty(shape, np.float32)
+    _check(lib, lib.fw_ggx_table(C.byref(q), int(device), n_mu, n_rho, table.ctypes.data, 0, None))
+    return table
+
+
+def _table_arg(table, on_device, device):
+    """(pointer, n_mu, n_rho, what keeps it alive) of an (n_rho, n_mu, 2) float32 table"""
+    if on_device:
+        import torch
+        if table.dim() != 3:
+            raise ValueError("table must have the shape (n_rho, n_mu, 2)")
+        _check_device_tensor(table, (table.shape[0], table.shape[1], 2), torch.float32, device, "table")
+        return table.data_ptr(), int(table.shape[1]), int(table.shape[0]), table
+    t = np.ascontiguousarray(np.asarray(table, np.float32))
+    if t.ndim != 3 or t.shape[2] != 2:
+        raise ValueError("table must have the shape (n_rho, n_mu, 2)")
+    return t.ctypes.data, int(t.shape[1]), int(t.shape[0]), t
+
+
+def ggx_table_lookup(table, mu, rho, device=0, out=None, stream=None):
+    """fw_ggx_table_lookup: the (n, 2) float32 bilinear lookup of an (n_rho, n_mu, 2) table at the pairs (mu[q], rho[q]), edges clamped,
+    zeros for a non-finite pair.  numpy arrays or contiguous float32 tensors on cuda:`device` (the table too), as ggx_terms."""
+    lib = load()
+    n, m, r, on_device = _pairs_arg(mu, rho, device)
+    tp, n_mu, n_rho, _keep = _table_arg(table, on_device, device)
+    if on_device:
+        import torch
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float32, device=m.device)
+        _check_device_tensor(out, (n, 2), torch.float32, device, "out")
+        _check(lib, lib.fw_ggx_table_lookup(int(device), n_mu, n_rho, tp, n, m.data_ptr(), r.data_ptr(), out.data_ptr(), 1, _stream_arg(stream, m.device)))
+        return out
+    if out is None:
+        out = np.empty((n, 2), np.float32)
+    _host_f32(out, (n, 2), "out")
+    _check(lib, lib.fw_ggx_table_lookup(int(device), n_mu, n_rho, tp, n, m.ctypes.data, r.ctypes.data, out.ctypes.data, 0, None))
+    return out
+
+
+def probe_shade_split(grid, sh, radiance, maps, aov, spec, view, table, width, height, flags=0, depth=None, moments=None, normal_bias=0.0,
+                      placement=None, gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear")):
+    """fw_probe_shade_split: probe_shade_glossy with the split sum's BRDF term: a glossy pixel is v ((F0 A + B) Ls) + (1 - v) a with (A, B)
+    looked up in `table` ((n_rho, n_mu, 2) float32, as ggx_table returns it; a device tensor when the other arrays are) at the cosine of
+    the view and the pixel's roughness; flags: FW_SPLIT_ENERGY multiplies by 1 + F0 (1 / (A + B) - 1).  Everything else as
+    probe_shade_glossy."""
+    lib = load()
+    g, n_probes = _grid_abi(grid)
+    n = int(width) * int(height)
+    p = A.fw_probe_shade_params()
+    p.width, p.height, p.gamma, p.device = int(width), int(height), float(gamma), int(device)
+    want = [name in outputs for name in ("rgb8", "gamma", "linear")]
+    if type(aov).__module__.startswith("torch"):
+        import torch
+        _check_device_tensor(sh, (n_probes, 9, 3), torch.float32, device, "sh")
+        _check_device_tensor(aov, (n, 12), torch.float32, device, "aov")
+        _check_device_tensor(spec, (n, 4), torch.float32, device, "spec")
+        stride = int(view.stride(0)) if n > 1 else max(3, int(view.stride(0)))
+        if (view.dtype != torch.float32 or tuple(view.shape) != (n, 3) or view.stride(1) != 1 or view.device.type != "cuda"
+                or (view.device.index or 0) != device or stride < 3):
+            raise ValueError(f"view must be an (N, 3) float32 tensor on cuda:{device} with unit column stride and a row stride >= 3")
+        head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, True, device)
+        tp, n_mu, n_rho, _kt = _table_arg(table, True, device)
+        dev = aov.device
+        rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev) if want[0] else None
+        gam = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[1] else None
+        lin = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[2] else None
+        p.on_device = 1
+        p.stream = _stream_arg(stream, dev)
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        _check(lib, lib.fw_probe_shade_split(C.byref(g), sh.data_ptr(), *head, C.byref(p), aov.data_ptr(), spec.data_ptr(), view.data_ptr(), stride,
+                                             tp, n_mu, n_rho, int(flags), ptr(lin), ptr(gam), ptr(rgb8)))
+        return rgb8, gam, lin
+    s = np.ascontiguousarray(np.asarray(sh, np.float32).reshape(n_probes, 9, 3))
+    a = np.ascontiguousarray(np.asarray(aov, np.float32).reshape(n, 12))
+    sp = np.ascontiguousarray(np.asarray(spec, np.float32).reshape(n, 4))
+    vw = np.ascontiguousarray(np.asarray(view, np.float32).reshape(n, 3))
+    head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, False, device)
+    tp, n_mu, n_rho, _kt = _table_arg(table, False, device)
+    rgb8 = np.empty((n, 3), np.uint8) if want[0] else None
+    gam = np.empty((n, 3), np.float32) if want[1] else None
+    lin = np.empty((n, 3), np.float32) if want[2] else None
+    ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
+    _check(lib, lib.fw_probe_shade_split(C.byref(g), s.ctypes.data, *head, C.byref(p), a.ctypes.data, sp.ctypes.data, vw.ctypes.data, 3, tp, n_mu,
+                                         n_rho, int(flags), ptr(lin), ptr(gam), ptr(rgb8)))
+    return rgb8, gam, lin
 
 
 class DeviceScene:

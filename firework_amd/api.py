@@ -2403,6 +2403,184 @@ def probe_glossy_dirs(aov, view):
     return np.where(ok[:, None], r, np.float32([0.0, 0.0, 1.0])).astype(np.float32), np.where(ok, S, 0.0), ok
 
 
+# --------------------------------------------------------------------------- the split sum's BRDF term: a GGX albedo table
+class GgxTable:
+    """The table of GgxMat's directional albedo that fw_probe_shade_split reads (fw_ggx_table): n_rho x n_mu texels of the two terms
+    (A, B) of F0 A + B at the centres mu_i = (i + 0.5) / n_mu, rho_j = (j + 0.5) / n_rho, each integrated over m1 x m2 midpoints of the
+    visible-normal square.  energy: shade with FW_SPLIT_ENERGY, the single-lobe energy compensation 1 + F0 (1 / (A + B) - 1)."""
+
+    def __init__(self, n_mu: int = 64, n_rho: int = 64, m1: int = 128, m2: int = 128, energy: bool = False):
+        self.n_mu, self.n_rho, self.m1, self.m2, self.energy = int(n_mu), int(n_rho), int(m1), int(m2), bool(energy)
+        self.check()
+
+    def check(self):
+        if not (2 <= self.n_mu <= 256 and 2 <= self.n_rho <= 256):
+            raise ValueError("n_mu and n_rho must be in 2..256")
+        if not (1 <= self.m1 <= 1024 and 1 <= self.m2 <= 1024):
+            raise ValueError("m1 and m2 must be in 1..1024")
+        return self
+
+    @property
+    def flags(self) -> int:
+        return A.FW_SPLIT_ENERGY if self.energy else 0
+
+    def to_abi(self) -> A.fw_ggx_quad:
+        return A.fw_ggx_quad(self.m1, self.m2)
+
+
+def ggx_terms(mu, rho, m1: int = 128, m2: int = 128, terms: bool = False):
+    """The numpy float64 statement of fw_ggx_terms: (n, 2) float32, the terms (A, B) of GgxMat's directional albedo F0 A + B at the
+    float32 pairs (mu, rho), by the m1 x m2 midpoint rule over the visible-normal square in the kernel's order: lane l of 256 adds the
+    samples l, l + 256, ... (id = a m2 + b), the partials go through the xor tree of each run of 64 and the four runs are added in
+    order.  Zeros for a mu outside (0, 1], a rho outside [0, 1] or a NaN.  terms: also a dict with the float64 values before their one
+    rounding ("AB", (n, 2)), the smallest |wi.z| over the samples ("min_wz", (n,)), the largest amplification of the one
+    ill-conditioned step, 1 / (2 (1 - p1^2 - p2^2)) where the root's argument is positive ("amp", (n,)), and the number of samples
+    whose argument is not positive ("clamped", (n,))."""
+    m1, m2 = int(m1), int(m2)
+    muf = np.asarray(mu, np.float32).reshape(-1)
+    rhof = np.asarray(rho, np.float32).reshape(-1)
+    n = muf.shape[0]
+    with np.errstate(all="ignore"):
+        ok = (muf > 0) & (muf <= 1) & (rhof >= 0) & (rhof <= 1)
+        cm = np.where(ok, muf, np.float32(1.0)).astype(np.float64)[:, None]
+        alpha = np.where(ok, rhof * rhof, np.float32(0.0)).astype(np.float64)[:, None]
+        a2 = alpha * alpha
+        sx = np.sqrt(np.fmax(1.0 - cm * cm, 0.0))
+        vx = alpha * sx
+        vl = np.sqrt(vx * vx + cm * cm)
+        vhx, vhz = vx / vl, cm / vl
+        s = 0.5 * (1.0 + vhz)
+        s1 = 1.0 - s
+        lo1 = 1.0 + 0.5 * (np.sqrt(1.0 + a2 * ((sx * sx) / (cm * cm))) - 1.0)
+        sr = np.sqrt((np.arange(m1, dtype=np.float64) + 0.5) / float(m1))
+        phi = (2.0 * np.pi) * ((np.arange(m2, dtype=np.float64) + 0.5) / float(m2))
+        cphi, sphi = np.cos(phi), np.sin(phi)
+        total = m1 * m2
+        trips = (total + 255) // 256
+        accA, accB = np.zeros((n, 256)), np.zeros((n, 256))
+        min_wz, amp, clamped = np.full(n, np.inf), np.zeros(n), np.zeros(n, np.int64)
+        for it in range(trips):
+            raw = it * 256 + np.arange(256)
+            valid = (raw < total)[None, :]
+            ids = np.minimum(raw, total - 1)
+            a, b = ids // m2, ids % m2
+            r, cp, sp = sr[a][None, :], cphi[b][None, :], sphi[b][None, :]
+            p1 = r * cp
+            q1 = 1.0 - p1 * p1
+            p2 = s1 * np.sqrt(np.fmax(q1, 0.0)) + s * (r * sp)
+            arg = q1 - p2 * p2
+            nz = np.sqrt(np.fmax(arg, 0.0))
+            nhx, nhz = nz * vhx - p2 * vhz, p2 * vhx + nz * vhz
+            gx, gy, gz = alpha * nhx, alpha * p1, np.fmax(nhz, 0.0)
+            hl = np.sqrt((gx * gx + gy * gy) + gz * gz)
+            hx, hy, hz = gx / hl, gy / hl, gz / hl
+            oh = sx * hx + cm * hz
+            t2 = 2.0 * oh
+            wx, wy, wz = t2 * hx - sx, t2 * hy, t2 * hz - cm
+            alive = wz > 0.0
+            zz, xy = np.where(alive, wz, 1.0), np.where(alive, wx * wx + wy * wy, 0.0)
+            li = 0.5 * (np.sqrt(1.0 + a2 * (xy / (zz * zz))) - 1.0)
+            k = np.where(alive & valid, lo1 / (lo1 + li), 0.0)
+            m = np.fmax(1.0 - oh, 0.0)
+            fc = ((m * m) * (m * m)) * m
+            accA = accA + k * (1.0 - fc)
+            accB = accB + k * fc
+            if terms:
+                min_wz = np.minimum(min_wz, np.min(np.where(valid, np.abs(wz), np.inf), axis=1))
+                amp = np.maximum(amp, np.max(np.where(valid & (arg > 0.0), 0.5 / np.where(arg > 0.0, arg, 1.0), 0.0), axis=1))
+                clamped += np.sum(valid & ~(arg > 0.0), axis=1)
+
+        def tree(v):
+            v = v.reshape(n, 4, 64)
+            lanes = np.arange(64)
+            for d in (32, 16, 8, 4, 2, 1):
+                v = v + v[:, :, lanes ^ d]
+            w = v[:, :, 0]
+            return ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+
+        count = float(m1) * float(m2)
+        AB = np.stack([tree(accA) / count, tree(accB) / count], axis=1)
+        AB = np.where(ok[:, None], AB, 0.0)
+    out = AB.astype(np.float32)
+    if terms:
+        return out, {"AB": AB, "min_wz": np.where(ok, min_wz, np.inf), "amp": np.where(ok, amp, 0.0), "clamped": np.where(ok, clamped, 0), "ok": ok}
+    return out
+
+
+def ggx_table_centres(n_mu: int, n_rho: int):
+    """(mu (n_rho, n_mu), rho (n_rho, n_mu)) float32: the texel centres of a GGX table, divided in float64 and rounded once"""
+    mu = ((np.arange(int(n_mu), dtype=np.float64) + 0.5) / float(n_mu)).astype(np.float32)
+    rho = ((np.arange(int(n_rho), dtype=np.float64) + 0.5) / float(n_rho)).astype(np.float32)
+    return np.broadcast_to(mu[None, :], (int(n_rho), int(n_mu))).copy(), np.broadcast_to(rho[:, None], (int(n_rho), int(n_mu))).copy()
+
+
+def ggx_table(n_mu: int = 64, n_rho: int = 64, m1: int = 128, m2: int = 128) -> np.ndarray:
+    """The numpy statement of fw_ggx_table: (n_rho, n_mu, 2) float32, ggx_terms at the texel centres"""
+    mu, rho = ggx_table_centres(n_mu, n_rho)
+    return ggx_terms(mu.reshape(-1), rho.reshape(-1), m1, m2).reshape(int(n_rho), int(n_mu), 2)
+
+
+def ggx_table_lookup(table, mu, rho) -> np.ndarray:
+    """The numpy float64 statement of fw_ggx_table_lookup: (n, 2) float32, the bilinear lookup of an (n_rho, n_mu, 2) float32 table at
+    the float32 pairs (mu, rho): x = min(max(mu n_mu - 0.5, 0), n_mu - 1), i0 = min(int(x), n_mu - 2), tx = x - i0, likewise y, and
+    ((t00 (1 - tx) + t10 tx) (1 - ty)) + ((t01 (1 - tx) + t11 tx) ty), rounded once; zeros for a non-finite mu or rho"""
+    t = np.asarray(table, np.float32)
+    n_rho, n_mu = int(t.shape[0]), int(t.shape[1])
+    t = t.astype(np.float64)
+    muf = np.asarray(mu, np.float32).reshape(-1)
+    rhof = np.asarray(rho, np.float32).reshape(-1)
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(muf) & np.isfinite(rhof)
+        x = np.fmin(np.fmax(np.where(ok, muf, 0).astype(np.float64) * float(n_mu) - 0.5, 0.0), float(n_mu) - 1.0)
+        y = np.fmin(np.fmax(np.where(ok, rhof, 0).astype(np.float64) * float(n_rho) - 0.5, 0.0), float(n_rho) - 1.0)
+        i0, j0 = np.minimum(x.astype(np.int64), n_mu - 2), np.minimum(y.astype(np.int64), n_rho - 2)
+        tx, ty = (x - i0)[:, None], (y - j0)[:, None]
+        ux, uy = 1.0 - tx, 1.0 - ty
+        t00, t10, t01, t11 = t[j0, i0], t[j0, i0 + 1], t[j0 + 1, i0], t[j0 + 1, i0 + 1]
+        out = ((t00 * ux + t10 * tx) * uy) + ((t01 * ux + t11 * tx) * ty)
+        return np.where(ok[:, None], out, 0.0).astype(np.float32)
+
+
+def probe_split_mu(aov, view) -> np.ndarray:
+    """(N,) float32: fw_probe_shade_split's mu_f = float32(min(1, max(0, -(nh.u)))), and 0 for an unusable view, normal or position"""
+    a = np.asarray(aov, np.float32).reshape(-1, 12).astype(np.float64)
+    vw = np.asarray(view, np.float32).astype(np.float64).reshape(-1, 3)
+    nr = a[:, 4:7]
+    _r, _S, ok = probe_glossy_dirs(aov, view)
+    with np.errstate(all="ignore"):
+        nh = nr / np.sqrt((nr[:, 0] * nr[:, 0] + nr[:, 1] * nr[:, 1]) + nr[:, 2] * nr[:, 2])[:, None]
+        u = vw / np.sqrt((vw[:, 0] * vw[:, 0] + vw[:, 1] * vw[:, 1]) + vw[:, 2] * vw[:, 2])[:, None]
+        c = (nh[:, 0] * u[:, 0] + nh[:, 1] * u[:, 1]) + nh[:, 2] * u[:, 2]
+        return np.where(ok, np.fmin(1.0, np.fmax(0.0, -c)), 0.0).astype(np.float32)
+
+
+def probe_split_ref(aov, spec, view, diffuse, radiance, terms=None, table=None, flags: int = 0) -> np.ndarray:
+    """The float32 statement of fw_probe_shade_split's linear output, (N, 3) float32: a pixel with !(rho > 0) takes `diffuse` (N, 3), the
+    linear output of the placed shade of the same records; a glossy pixel is v (spec Ls) + (1 - v) a with Ls = max(radiance, 0) — the
+    lookup along probe_glossy_dirs' r at rho, (N, 3) float32, 0 for an unusable view, normal or position — spec_c = f0_c A + B and,
+    with FW_SPLIT_ENERGY in flags, spec_c (1 + f0_c g), g = 1 / (A + B) - 1 where A + B > 0, else 0.  (A, B) = `terms` (N, 2) float32
+    when given (the device lookup's own output), else ggx_table_lookup(table, probe_split_mu(aov, view), rho)."""
+    a = np.asarray(aov, np.float32).reshape(-1, 12)
+    sp = np.asarray(spec, np.float32).reshape(-1, 4)
+    _r, _S, ok = probe_glossy_dirs(aov, view)
+    if terms is None:
+        terms = ggx_table_lookup(table, probe_split_mu(aov, view), sp[:, 3])
+    ab = np.asarray(terms, np.float32).reshape(-1, 2)
+    with np.errstate(all="ignore"):
+        Ls = np.asarray(radiance, np.float32).reshape(-1, 3)
+        Ls = np.where(ok[:, None] & (Ls > 0), Ls, np.float32(0.0)).astype(np.float32)
+        f0, v, one = sp[:, 0:3], a[:, 3:4], np.float32(1.0)
+        Af, Bf = ab[:, 0:1], ab[:, 1:2]
+        s = (f0 * Af + Bf).astype(np.float32)
+        if int(flags) & A.FW_SPLIT_ENERGY:
+            e1 = (Af + Bf).astype(np.float32)
+            g = np.where(e1 > 0, one / np.where(e1 > 0, e1, one) - one, np.float32(0.0)).astype(np.float32)
+            s = (s * (one + f0 * g)).astype(np.float32)
+        out = (v * (s * Ls) + (one - v) * a[:, 0:3]).astype(np.float32)
+    glossy = sp[:, 3] > 0
+    return np.where(glossy[:, None], out, np.asarray(diffuse, np.float32).reshape(-1, 3)).astype(np.float32)
+
+
 # --------------------------------------------------------------------------- lightmaps (fw_bake_lightmap; DESIGN.md §9o)
 LIGHTMAP_NO_OWNER = 0xFFFFFFFF          # FW_NO_HIT in an owner map
 
@@ -3568,7 +3746,7 @@ class Renderer:
     def render_probe_lit(self, scene, probes, sh, aov_samples: int = 8, wrap: bool = True, device: int = 0, model: "CameraModel" = None,
                          depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0, ao: "AmbientOcclusion" = None,
                          ao_rounds: int = 1, placement=None, radiance: "ProbeRadiance" = None, maps=None,
-                         direct: "DirectLight" = None) -> RenderResult:
+                         direct: "DirectLight" = None, ggx_table: "GgxTable" = None, table=None) -> RenderResult:
         """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
         (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
         from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
@@ -3591,11 +3769,22 @@ class Renderer:
         the direct light of the scene's point, spot and directional lights, which no probe holds — _direct_term's frame, fw_bake_direct
         on the records in place — is added in float32 to the linear frame of whichever branch ran and the sum resolved by fw_denoise
         at 0 iterations; with ao, only the probes' term is multiplied by ao.  The call's stats are kept in self.direct_stats.
-        direct=None: the calls and the bits above."""
+        direct=None: the calls and the bits above.  ggx_table (a GgxTable), with radiance: the glossy pixels are shaded
+        by fw_probe_shade_split — F0 A + B from the table in the place of the bare Schlick term, with ggx_table.energy the energy
+        compensation — and every other pixel as before; the table is baked on the device in the call (fw_ggx_table) unless `table`,
+        (n_rho, n_mu, 2) as _lib.ggx_table returns it, is passed.  ggx_table without radiance: ValueError.  ggx_table=None: the
+        calls and the bits above."""
         import torch
         from . import _lib
         if direct is not None:
             direct.check()
+        if ggx_table is not None:
+            if radiance is None:
+                raise ValueError("ggx_table needs radiance: the split sum's BRDF term multiplies the radiance maps' lookup")
+            ggx_table.check()
+        elif table is not None:
+            raise ValueError("table needs the GgxTable it was baked for")
+        baked = table                                                                     # (the radiance branch has a material table of its own)
         if depth is not None and moments is None:
             raise ValueError("depth needs the moments bake_probe_depth returned")
         if radiance is not None and maps is None:
@@ -3648,8 +3837,17 @@ class Renderer:
                 table = torch.from_numpy(material_spec_table(ds._desc)).to(dev)
                 miss = torch.full_like(hit["material"], table.shape[0] - 1)
                 spec = table[torch.where(hit["object"] == -1, miss, hit["material"]).long()].contiguous()
-                rgb8, gam, lin = _lib.probe_shade_glossy(grid, d_sh, radiance, d_maps, aov, spec, rays[:, 3:6], w, h, depth, d_mom, normal_bias, d_pl,
-                                                         s["gamma"], ds.device)
+                if ggx_table is not None:
+                    if baked is None:
+                        d_tab = _lib.ggx_table(ggx_table, device=ds.device,
+                                               out=torch.empty((ggx_table.n_rho, ggx_table.n_mu, 2), dtype=torch.float32, device=dev))
+                    else:
+                        d_tab = torch.from_numpy(np.ascontiguousarray(np.asarray(baked, np.float32).reshape(ggx_table.n_rho, ggx_table.n_mu, 2))).to(dev)
+                    rgb8, gam, lin = _lib.probe_shade_split(grid, d_sh, radiance, d_maps, aov, spec, rays[:, 3:6], d_tab, w, h, ggx_table.flags, depth,
+                                                            d_mom, normal_bias, d_pl, s["gamma"], ds.device)
+                else:
+                    rgb8, gam, lin = _lib.probe_shade_glossy(grid, d_sh, radiance, d_maps, aov, spec, rays[:, 3:6], w, h, depth, d_mom, normal_bias,
+                                                             d_pl, s["gamma"], ds.device)
             elif d_pl is not None:
                 rgb8, gam, lin = _lib.probe_shade_placed(grid, d_sh, d_pl, aov, w, h, depth, d_mom, normal_bias, s["gamma"], ds.device)
             elif depth is not None:

@@ -30,6 +30,7 @@
 // min, max and fabs are exact; sqrt is the device library's float64 function.
 #include "fw_probe_radiance.h"
 #include "fw_probe_corners.h"
+#include "fw_probe_radiance_fetch.h"
 
 namespace fw {
 namespace {
@@ -192,63 +193,6 @@ __global__ __launch_bounds__(PR_BLOCK) void k_probe_radiance_prefilter(uint32_t 
         }
         __syncthreads();                                                                // level 0 is overwritten by the next probe
     }
-}
-
-// the rgb of one level (R x R texels of 16 B at `m`) along the unit direction (x, y, z): bilinear, edges clamped; the flags are not read
-__device__ __forceinline__ void radiance_fetch(const float4 *__restrict__ m, uint32_t R, double x, double y, double z, double c[3]) {
-    uint32_t iu, jv;
-    double fu, fv;
-    octa_cell(R, x, y, z, iu, jv, fu, fv);
-    const float4 *__restrict__ r0 = m + (size_t)(jv * R + iu);
-    const float4 *__restrict__ r1 = r0 + R;
-    const float4 t00 = r0[0], t10 = r0[1], t01 = r1[0], t11 = r1[1];
-    const double gu = 1.0 - fu, gv = 1.0 - fv;
-    c[0] = (((double)t00.x * gu + (double)t10.x * fu) * gv) + (((double)t01.x * gu + (double)t11.x * fu) * fv);
-    c[1] = (((double)t00.y * gu + (double)t10.y * fu) * gv) + (((double)t01.y * gu + (double)t11.y * fu) * fv);
-    c[2] = (((double)t00.z * gu + (double)t10.z * fu) * gv) + (((double)t01.z * gu + (double)t11.z * fu) * fv);
-}
-
-// the radiance sum over those corners along (dx, dy, dz), which need not be a unit vector, at roughness `rough`: E[c] in float64 before
-// its one rounding; false for a direction or a roughness the statement answers with zeros
-__device__ __forceinline__ bool corners_radiance(const DProbeGrid &G, const Corners &C, const DProbeRadiance &pr, const float4 *__restrict__ maps, double dx, double dy,
-                                                 double dz, double rough, double E[3]) {
-    const double dl2 = (dx * dx + dy * dy) + dz * dz;
-    if (!(dl2 > 0.0) || !(dl2 <= 1.79769313486231570e+308) || !(fabs(rough) <= 1.79769313486231570e+308)) return false;
-    const double dl = sqrt(dl2);
-    const double rx = dx / dl, ry = dy / dl, rz = dz / dl;
-    // the level pair and the blend
-    const uint32_t L = pr.levels;
-    const double top = L == 1u ? pr.rho[0] : (L == 2u ? pr.rho[1] : (L == 3u ? pr.rho[2] : pr.rho[3]));
-    const double rho = fmin(fmax(rough, pr.rho[0]), top);
-    uint32_t l = 0u;
-    double lo = pr.rho[0], hi = pr.rho[1];
-    if (L > 2u && pr.rho[1] <= rho) { l = 1u; lo = pr.rho[1]; hi = pr.rho[2]; }
-    if (L > 3u && pr.rho[2] <= rho) { l = 2u; lo = pr.rho[2]; hi = pr.rho[3]; }
-    const bool pair = L > 1u;
-    const double t = pair ? (rho - lo) / (hi - lo) : 0.0;
-    const double t1 = 1.0 - t;
-    const uint32_t R = pr.R;
-    const uint32_t off0 = l == 0u ? 0u : (l == 1u ? R * R : R * R + (R >> 1) * (R >> 1));
-    const uint32_t Rl = R >> l, Rn = Rl >> 1;
-    const uint32_t off1 = off0 + Rl * Rl;
-    double e0 = 0.0, e1 = 0.0, e2 = 0.0;
-#pragma unroll
-    for (int d = 0; d < 8; d++) {
-        if (C.active & (1u << d)) {
-            const float4 *__restrict__ m = maps + (size_t)corner_probe(G, C.cell, d) * pr.texels;      // n_probes x M < 2^31 texels
-            double c[3];
-            radiance_fetch(m + off0, Rl, rx, ry, rz, c);
-            if (pair) {
-                double n[3];
-                radiance_fetch(m + off1, Rn, rx, ry, rz, n);
-                c[0] = c[0] * t1 + n[0] * t; c[1] = c[1] * t1 + n[1] * t; c[2] = c[2] * t1 + n[2] * t;
-            }
-            const double wd = C.w[d] / C.wsum;
-            e0 = e0 + wd * c[0]; e1 = e1 + wd * c[1]; e2 = e2 + wd * c[2];
-        }
-    }
-    E[0] = e0; E[1] = e1; E[2] = e2;
-    return true;
 }
 
 // Four waves per SIMD, not the five its 90 VGPRs would allow: a point gathers up to 1 KB of texels, and on random points the fifth wave

@@ -21,6 +21,7 @@
 #include "fw_probe_radiance.h"
 #include "fw_direct.h"
 #include "fw_sky.h"
+#include "fw_ggx_table.h"
 #include "fw_defer_pretest.h"
 
 #include <algorithm>
@@ -5397,6 +5398,116 @@ int sky_sun_impl(const fw_sky *s, fw_light *out) {
     return FW_OK;
 }
 
+// ---- the GGX albedo table: fw_check_ggx_quad, fw_ggx_terms, fw_ggx_table, fw_ggx_table_lookup, fw_probe_shade_split -------
+int ggx_quad_check(const fw_ggx_quad *q) {
+    if (!q) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (q->m1 < 1 || q->m1 > fw::GGX_MAX_M) return fail(FW_ERR_BAD_ARG, "m1 must be in 1..1024");
+    if (q->m2 < 1 || q->m2 > fw::GGX_MAX_M) return fail(FW_ERR_BAD_ARG, "m2 must be in 1..1024");
+    return FW_OK;
+}
+int ggx_table_sizes(uint32_t n_mu, uint32_t n_rho) {
+    if (n_mu < fw::GGX_MIN_N || n_mu > fw::GGX_MAX_N || n_rho < fw::GGX_MIN_N || n_rho > fw::GGX_MAX_N) return fail(FW_ERR_BAD_ARG, "n_mu and n_rho must be in 2..256");
+    return FW_OK;
+}
+
+// fw_ggx_terms: fw_sky_radiance's shape — device arrays: one launch over the caller's memory; host arrays: slabs of pairs
+int ggx_terms_impl(const fw_ggx_quad *q, int device, uint32_t n, const float *mu, const float *rho, float *terms, int on_device, void *stream_) {
+    if (!q || !mu || !rho || !terms) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = ggx_quad_check(q)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (on_device && ((((uintptr_t)mu | (uintptr_t)rho) & 3u) || ((uintptr_t)terms & 7u)))
+        return fail(FW_ERR_BAD_ARG, "device terms must be 8-byte aligned, device mu and rho 4-byte aligned");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n_cus = device_cus(device);
+    Staged st(device, stream, on_device != 0);
+    HostSlabs sl(st, n, 16);
+    const int a_mu = sl.in(mu, 4), a_rho = sl.in(rho, 4), a_out = sl.out(terms, 8);
+    if (int rc = st.up()) return rc;
+    return sl.run([&](uint32_t, uint32_t k) {
+        fw::launch_ggx_terms(stream, n_cus, q->m1, q->m2, k, sl.ptr<const float>(a_mu), sl.ptr<const float>(a_rho), 0u, 0u, 0u, sl.ptr<float>(a_out));
+    });
+}
+
+// fw_ggx_table: fw_sky_map's shape — device output: one launch into the caller's memory; host output: host_slabs of texels
+int ggx_table_impl(const fw_ggx_quad *q, int device, uint32_t n_mu, uint32_t n_rho, float *table, int on_device, void *stream_) {
+    if (!q || !table) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = ggx_quad_check(q)) return rc;
+    if (int rc = ggx_table_sizes(n_mu, n_rho)) return rc;
+    if (on_device && ((uintptr_t)table & 7u)) return fail(FW_ERR_BAD_ARG, "device table must be 8-byte aligned");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n_cus = device_cus(device);
+    auto launch = [&](uint32_t first, uint32_t k, float *d_terms) {
+        fw::launch_ggx_terms(stream, n_cus, q->m1, q->m2, k, nullptr, nullptr, first, n_mu, n_rho, d_terms);
+    };
+    if (on_device) {
+        launch(0u, n_mu * n_rho, table);
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipGetLastError());
+        return FW_OK;
+    }
+    return host_slabs(stream, device, n_mu * n_rho, 8, table, launch);
+}
+
+// fw_ggx_table_lookup: fw_ggx_terms' shape with the table as a staged input
+int ggx_table_lookup_impl(int device, uint32_t n_mu, uint32_t n_rho, const float *table, uint32_t n, const float *mu, const float *rho, float *terms,
+                          int on_device, void *stream_) {
+    if (!table || !mu || !rho || !terms) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = ggx_table_sizes(n_mu, n_rho)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (on_device && ((((uintptr_t)mu | (uintptr_t)rho) & 3u) || (((uintptr_t)terms | (uintptr_t)table) & 7u)))
+        return fail(FW_ERR_BAD_ARG, "device table and terms must be 8-byte aligned, device mu and rho 4-byte aligned");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    Staged st(device, stream, on_device != 0);
+    const int a_tab = st.add(Staged::IN, table, (size_t)n_mu * n_rho * 8);
+    HostSlabs sl(st, n, 16);
+    const int a_mu = sl.in(mu, 4), a_rho = sl.in(rho, 4), a_out = sl.out(terms, 8);
+    if (int rc = st.up()) return rc;
+    return sl.run([&](uint32_t, uint32_t k) {
+        fw::launch_ggx_table_lookup(stream, n_mu, n_rho, st.ptr<const float>(a_tab), k, sl.ptr<const float>(a_mu), sl.ptr<const float>(a_rho), sl.ptr<float>(a_out));
+    });
+}
+
+// fw_probe_shade_split: probe_shade_glossy_impl with the table as one more staged input
+int probe_shade_split_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, const fw_probe_shade_params *p, const float *aov, const float *spec,
+                           const float *view, uint32_t view_stride, const float *table, uint32_t n_mu, uint32_t n_rho, uint32_t flags,
+                           float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
+    ProbeLookup L;
+    if (!grid || !a.sh || !a.pr || !a.maps || !p || !aov || !spec || !view || !table || (a.vis && (!a.pd || !a.moments)) || (a.placed && !a.placement))
+        return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = ggx_table_sizes(n_mu, n_rho)) return rc;
+    if (flags & ~FW_SPLIT_ENERGY) return fail(FW_ERR_BAD_ARG, "flags has an unknown bit");
+    if (int rc = probe_lookup_check(grid, a, false, !linear_rgb && !gamma_rgb && !rgb8, L)) return rc;
+    if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
+    if (!std::isfinite(p->gamma) || !(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
+    if (view_stride < 3) return fail(FW_ERR_BAD_ARG, "view_stride_floats must be >= 3");
+    if (p->device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
+    if (p->on_device && ((((uintptr_t)aov | (uintptr_t)spec | (uintptr_t)a.maps) & 15u) || ((uintptr_t)table & 7u) ||
+                         (((uintptr_t)a.sh | (uintptr_t)view | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb | (uintptr_t)a.moments | (uintptr_t)a.placement) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device aov, spec and maps must be 16-byte aligned, device table 8-byte aligned, the other device arrays 4-byte aligned");
+    const uint64_t full = (uint64_t)p->width * p->height;
+    if (int rc = probe_lookup_sizes(a, L)) return rc;
+    if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
+    const int dev = p->device;
+    if (int rc = use_device(dev)) return rc;
+    hipStream_t stream = (hipStream_t)p->stream;
+    Staged st(dev, stream, p->on_device != 0);
+    const ProbeTables t = probe_tables_stage(st, a, L);
+    const int a_tab = st.add(Staged::IN, table, (size_t)n_mu * n_rho * 8);
+    HostSlabs sl(st, (uint32_t)full, 103);
+    const int a_aov = sl.in(aov, 48), a_spec = sl.in(spec, 16), a_view = sl.in(view, 12, view_stride);
+    const int a_lin = sl.out(linear_rgb, 12), a_gam = sl.out(gamma_rgb, 12), a_8 = sl.out(rgb8, 3);
+    if (int rc = st.up()) return rc;
+    return sl.run([&](uint32_t, uint32_t k) {
+        const fw::DProbeVis v = probe_vis_device(a, st.ptr<const float>(t.mom));
+        fw::launch_probe_split_shade(stream, L.g, a.vis ? &v : nullptr, L.d, st.ptr<const float>(t.sh), st.ptr<const float>(t.maps), st.ptr<const float>(t.pl), k,
+                                     sl.ptr<const float>(a_aov), sl.ptr<const float>(a_spec), sl.ptr<const float>(a_view), sl.stride(a_view),
+                                     st.ptr<const float>(a_tab), n_mu, n_rho, flags, p->gamma, sl.ptr<uint8_t>(a_8), sl.ptr<float>(a_gam), sl.ptr<float>(a_lin));
+    });
+}
+
 } // namespace
 
 // =========================================================================================================
@@ -5954,6 +6065,43 @@ int fw_sky_sun(const fw_sky *sky, fw_light *out) {
     try { return sky_sun_impl(sky, out); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_sky_sun"); }
+}
+
+int fw_check_ggx_quad(const fw_ggx_quad *quad) {
+    try { return ggx_quad_check(quad); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_check_ggx_quad"); }
+}
+
+int fw_ggx_terms(const fw_ggx_quad *quad, int device, uint32_t n, const float *mu, const float *rho, float *terms, int on_device, void *stream) {
+    try { return ggx_terms_impl(quad, device, n, mu, rho, terms, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_ggx_terms"); }
+}
+
+int fw_ggx_table(const fw_ggx_quad *quad, int device, uint32_t n_mu, uint32_t n_rho, float *table, int on_device, void *stream) {
+    try { return ggx_table_impl(quad, device, n_mu, n_rho, table, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_ggx_table"); }
+}
+
+int fw_ggx_table_lookup(int device, uint32_t n_mu, uint32_t n_rho, const float *table, uint32_t n, const float *mu, const float *rho, float *terms,
+                        int on_device, void *stream) {
+    try { return ggx_table_lookup_impl(device, n_mu, n_rho, table, n, mu, rho, terms, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_ggx_table_lookup"); }
+}
+
+int fw_probe_shade_split(const fw_probe_grid *grid, const float *sh, const fw_probe_radiance *pr, const float *maps, const fw_probe_depth *pd,
+                         const float *moments, float normal_bias, const float *placement, const fw_probe_shade_params *p, const float *aov,
+                         const float *spec, const float *view, uint32_t view_stride_floats, const float *table, uint32_t n_mu, uint32_t n_rho,
+                         uint32_t flags, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
+    try {
+        const ProbeLookupArgs a{sh, pr, maps, pd, moments, normal_bias, placement, pd || moments, placement != nullptr};
+        return probe_shade_split_impl(grid, a, p, aov, spec, view, view_stride_floats, table, n_mu, n_rho, flags, linear_rgb, gamma_rgb, rgb8);
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_split"); }
 }
 
 int fw_probe_irradiance_vis(const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias, int device,

@@ -1435,7 +1435,8 @@ int fw_probe_shade_placed(const fw_probe_grid *grid, const float *sh, const fw_p
          lookup answers with zeros.  In float32 without contraction
          F_c = f0_c + (1 - f0_c) * (float)S and out_c = v * (F_c * Ls_c) + (1 - v) * a_c with v the record's coverage and a its albedo;
          the outputs are resolved as fw_probe_shade's.  A conductor has no diffuse lobe.  Simplification: the split sum's shadowing
-         factor (the second, BRDF-integral term) is left out. */
+         factor (the second, BRDF-integral term) is left out of this call; fw_probe_shade_split (below) is the same shade with that
+         term, read from a table that fw_ggx_table bakes. */
 #define FW_PROBE_RADIANCE_MAX_LEVELS 4
 typedef struct fw_probe_radiance {
     uint32_t resolution;      /* R in {4, 8, 16, 32} */
@@ -1489,6 +1490,83 @@ int fw_probe_radiance_lookup(const fw_probe_grid *grid, const fw_probe_radiance 
 int fw_probe_shade_glossy(const fw_probe_grid *grid, const float *sh, const fw_probe_radiance *pr, const float *maps, const fw_probe_depth *pd,
                           const float *moments, float normal_bias, const float *placement, const fw_probe_shade_params *p, const float *aov,
                           const float *spec, const float *view, uint32_t view_stride_floats, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8);
+
+/* ---- the split sum's BRDF term: a GGX albedo table (additive at ABI 8) -------------------------------------------------
+   FW_MAT_GGX's directional albedo at the cosine mu of the view and the roughness rho is F0 A + B per channel, with two numbers
+   (A, B) that depend on (mu, rho) alone: fw_ggx_terms integrates them, fw_ggx_table lays them out over (mu, rho), fw_ggx_table_lookup
+   reads the table, and fw_probe_shade_split is fw_probe_shade_glossy with F0 A + B in the place of the bare Schlick term.  Everything
+   is float64 from the float32 inputs, every operation rounded as written (no contraction), max and min are fmax and fmin, one rounding
+   to float32 at the end.  api.ggx_terms, api.ggx_table, api.ggx_table_lookup and api.probe_split_ref are the numpy statements.
+     Terms at (mu, rho), mu in (0, 1], rho in [0, 1]; zeros for a mu or rho outside its range or not finite.  alpha = the float32 product
+         rho rho, widened (as FW_MAT_GGX forms it), a2 = alpha alpha.  wo = (sx, 0, mu) with sx = sqrt(max(1 - mu mu, 0)).  The visible
+         normal is FW_MAT_GGX's (Heitz 2018, above) for this wo:  vx = alpha sx;  vl = sqrt(vx vx + mu mu);  Vh = (vhx, 0, vhz) = (vx / vl,
+         0, mu / vl);  T1 = (0, 1, 0), which is (-Vh.y, Vh.x, 0) / |.| wherever that exists and as good a tangent as any where it does not
+         (Vh = z);  T2 = Vh x T1 = (-vhz, 0, vhx);  s = 0.5 (1 + vhz);  Lo = 0.5 (sqrt(1 + a2 ((sx sx) / (mu mu))) - 1).
+         Sample (a, b), a < m1, b < m2:  xi1 = (a + 0.5) / m1, xi2 = (b + 0.5) / m2 — midpoints of the visible-normal square, so that the
+         integrand is continuous at the horizon, where Lambda(wi) grows without bound;  r = sqrt(xi1);  phi = (2 pi) xi2;  p1 = r cos phi;
+         q1 = 1 - p1 p1;  p2 = (1 - s) sqrt(max(q1, 0)) + s (r sin phi);  nz = sqrt(max(q1 - p2 p2, 0));  nh = (nz vhx - p2 vhz, p1,
+         p2 vhx + nz vhz);  g = (alpha nh.x, alpha nh.y, max(nh.z, 0));  h = g / sqrt((g.x g.x + g.y g.y) + g.z g.z);  oh = sx h.x + mu h.z;
+         wi = ((2 oh) h.x - sx, (2 oh) h.y, (2 oh) h.z - mu).  Where wi.z > 0:  Li = 0.5 (sqrt(1 + a2 ((wi.x wi.x + wi.y wi.y) / (wi.z
+         wi.z))) - 1) and k = (1 + Lo) / ((1 + Lo) + Li) — the renderer's attenuation F G2 / G1 without F;  elsewhere k = 0.
+         m = max(1 - oh, 0) (the max guards a rounding of oh past 1);  Fc = ((m m) (m m)) m;  the sample's terms are k (1 - Fc) and k Fc.
+         Sum: sample id = a m2 + b.  Lane l of 256 adds the terms of the samples l, l + 256, ... in ascending order from 0.0.  The 256
+         partials are added by a fixed tree: within each run of 64 lanes, for d = 32, 16, 8, 4, 2, 1 every lane takes v = v + v[lane
+         xor d] (all 64 then hold one value); the four runs' values are added as ((w0 + w1) + w2) + w3.  A and B are those sums
+         divided by the product (double)m1 (double)m2.  The albedo of a material is F0 A + B; E1 = A + B is that of a white one.
+     fw_ggx_quad = { m1 in 1..1024, m2 in 1..1024 }; the default is 128 x 128.  Against the same rule at 2048 x 2048 the terms differ by
+         at most 6.5e-3 at 64 x 64, 8.8e-4 at 128 x 128 and 5.5e-4 at 256 x 256 over mu in {1/64, 0.1, 0.5, 0.99} x rho in {1/64, 0.05,
+         0.1, 0.3, 0.6, 1}; xi1 is the dimension that matters.
+     Table.  n_mu and n_rho in 2..256.  Texel (i, j) holds the terms at the centres mu_i = float((i + 0.5) / n_mu) and rho_j =
+         float((j + 0.5) / n_rho), both divisions in float64.  table[j][i] = (A, B): n_rho x n_mu x 2 floats.  fw_ggx_table equals
+         fw_ggx_terms at those centres bit for bit.
+     Lookup at (mu, rho):  x = min(max(mu n_mu - 0.5, 0), n_mu - 1);  i0 = min((int)x, n_mu - 2);  tx = x - i0;  likewise y, j0 and ty
+         from rho and n_rho;  out = ((t00 (1 - tx) + t10 tx) (1 - ty)) + ((t01 (1 - tx) + t11 tx) ty) per component with t10 the texel
+         (i0 + 1, j0) and t01 the texel (i0, j0 + 1), rounded to float32 once.  Zeros for a non-finite mu or rho.  Every index lies in
+         the table whatever mu and rho hold.  At a texel centre of a power-of-two size x = i exactly and the texel's bits come back.
+         No division, root or transcendental: a device is expected to equal numpy bit for bit.
+     Split shade (fw_probe_shade_split, k_probe_split_shade).  fw_probe_shade_glossy's arguments, the table, its sizes and flags.  A
+         pixel with !(rho > 0) gets fw_probe_shade_placed's output bit for bit.  A glossy pixel forms u, c, r and Ls exactly as the
+         glossy shade above;  mu_f = float(min(1, max(0, -c))), and 0 for a non-finite or zero view, a non-finite position or a
+         non-finite or zero normal;  (A, B) = the lookup at (mu_f, rho).  Then in float32 without contraction:  spec_c = f0_c * A + B;
+         with FW_SPLIT_ENERGY:  E1 = A + B,  g = (E1 > 0) ? 1 / E1 - 1 : 0,  spec_c = spec_c * (1 + f0_c * g) — the usual single-lobe
+         compensation: a white conductor returns all the light it receives; without the flag nothing is multiplied;
+         out_c = v * (spec_c * Ls_c) + (1 - v) * a_c.  The outputs are resolved as fw_probe_shade's. */
+#define FW_SPLIT_ENERGY 1u
+typedef struct fw_ggx_quad {
+    uint32_t m1, m2; /* samples of xi1 and of xi2, each in 1..1024 (default 128 x 128) */
+} fw_ggx_quad;
+
+/* fw_check_ggx_quad: FW_OK, or FW_ERR_BAD_ARG for, in this order: a NULL quad; m1 outside 1..1024; m2 outside 1..1024.  Touches no
+   device. */
+int fw_check_ggx_quad(const fw_ggx_quad *quad);
+
+/* fw_ggx_terms: terms[q] = (A, B) at (mu[q], rho[q]), q < n (one workgroup per pair; a pair's terms do not depend on the batch).
+   Host arrays — through device scratch of the call's own, freed on every path — or with on_device device arrays on `device`, launched
+   on `stream` and complete on return; terms (n x 2 floats) is overwritten.  Errors, in this order and before HIP is called:
+   FW_ERR_BAD_ARG for a NULL quad, mu, rho or terms; fw_check_ggx_quad's refusals; n == 0; with on_device terms not 8-byte aligned or
+   mu or rho not 4-byte aligned; then FW_ERR_NO_DEVICE without a GPU (terms untouched), and FW_ERR_BAD_ARG for a device index out of
+   range. */
+int fw_ggx_terms(const fw_ggx_quad *quad, int device, uint32_t n, const float *mu, const float *rho, float *terms, int on_device, void *stream);
+
+/* fw_ggx_table: the n_rho x n_mu x 2 floats of the table, host memory or with on_device device memory, as fw_ggx_terms; overwritten.
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL quad or table; fw_check_ggx_quad's refusals; n_mu or n_rho
+   outside 2..256; with on_device table not 8-byte aligned; then FW_ERR_NO_DEVICE (table untouched), and FW_ERR_BAD_ARG for a device
+   index out of range. */
+int fw_ggx_table(const fw_ggx_quad *quad, int device, uint32_t n_mu, uint32_t n_rho, float *table, int on_device, void *stream);
+
+/* fw_ggx_table_lookup: terms[q] = the lookup above of `table` at (mu[q], rho[q]), q < n (one lane per pair, four 8-byte loads).  Host
+   arrays or with on_device device arrays, as fw_ggx_terms.  Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL
+   table, mu, rho or terms; n_mu or n_rho outside 2..256; n == 0; with on_device table or terms not 8-byte aligned or mu or rho not
+   4-byte aligned; then FW_ERR_NO_DEVICE (terms untouched), and FW_ERR_BAD_ARG for a device index out of range. */
+int fw_ggx_table_lookup(int device, uint32_t n_mu, uint32_t n_rho, const float *table, uint32_t n, const float *mu, const float *rho, float *terms,
+                        int on_device, void *stream);
+
+/* fw_probe_shade_split: the split shade above.  Errors: fw_probe_shade_glossy's in its order, with table among the NULL checks, then
+   n_mu or n_rho outside 2..256 and flags with an unknown bit straight after the NULL checks, and with on_device table 8-byte aligned. */
+int fw_probe_shade_split(const fw_probe_grid *grid, const float *sh, const fw_probe_radiance *pr, const float *maps, const fw_probe_depth *pd,
+                         const float *moments, float normal_bias, const float *placement, const fw_probe_shade_params *p, const float *aov,
+                         const float *spec, const float *view, uint32_t view_stride_floats, const float *table, uint32_t n_mu, uint32_t n_rho,
+                         uint32_t flags, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8);
 
 /* Diagnostic: the kernels' division / square-root helpers against the compiler's IEEE expansion, bit for bit,
    on n hashed operand pairs.  mode 0 = magnitudes 2^-40..2^40 (must be 0 mismatches), mode 1 = all bit patterns. */
