@@ -5,6 +5,7 @@ visible, every call raises.  The CPU oracle under oracle/ is test infrastructure
 reachable from here.
 """
 import ctypes as C
+import math
 import os
 import re
 
@@ -421,9 +422,132 @@ def _stream_arg(stream, torch_device):
 
 
 def _host_f32(arr, shape, name):
-    """the check of a caller-owned host array that a call updates in place (shape None: any shape)"""
-    if not (isinstance(arr, np.ndarray) and arr.dtype == np.float32 and (shape is None or arr.shape == tuple(shape)) and arr.flags["C_CONTIGUOUS"]):
-        raise ValueError(f"{name} must be a contiguous float32 array" + ("" if shape is None else f" of shape {tuple(shape)}"))
+    """the check of a caller-owned host array that a call updates in place"""
+    if not (isinstance(arr, np.ndarray) and arr.dtype == np.float32 and arr.shape == tuple(shape) and arr.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"{name} must be a contiguous float32 array of shape {tuple(shape)}")
+
+
+def _check_device_tensor(t, shape, dtype, device, name):
+    if (tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device.type != "cuda"
+            or (t.device.index or 0) != device):
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on cuda:{device}")
+
+
+_HOST_DTYPES = dict(f32=np.float32, u8=np.uint8, ids=np.uint32)
+_DEVICE_DTYPES = dict(f32="float32", u8="uint8", ids="int32")      # (torch's, by name: torch is imported on the device side only)
+
+
+class _Side:
+    """Where the arrays of one call lie — host (numpy) arrays, or torch tensors on cuda:`device` — and how each of them reaches the C ABI.
+    The only place that tells the two apart: `first`, the call's first array, decides (or on_device=True does), and torch is imported for
+    the device side only.  Every method returns the array as the call uses it and ptr() its pointer.  The object holds whatever a pointer
+    points into, so a wrapper that keeps its _Side in a local until the C function has returned needs no keepalive of its own."""
+
+    def __init__(self, first, device, on_device=False):
+        self.device = int(device)
+        self.on_device = bool(on_device) or type(first).__module__.startswith("torch")
+        self._keep = []
+        if self.on_device:
+            import torch
+            self._torch, self.dev = torch, torch.device("cuda", self.device)
+
+    def _dtype(self, kind):
+        """kind: "f32", "u8", or "ids": uint32 on the host, their int32 bits on the device"""
+        return getattr(self._torch, _DEVICE_DTYPES[kind]) if self.on_device else _HOST_DTYPES[kind]
+
+    def ptr(self, a):
+        return None if a is None else a.data_ptr() if self.on_device else a.ctypes.data
+
+    def ptrs(self, *arrays):
+        return tuple(self.ptr(a) for a in arrays)
+
+    def count(self, a, cols):
+        """N of an (N, cols) input: a device tensor's rows; a host array may have any shape of N * cols elements"""
+        return int(a.shape[0]) if self.on_device else int(np.size(a)) // cols
+
+    def inp(self, a, shape, name, kind="f32", below=None):
+        """an input array of `shape` (None stays None).  Host: converted only if it is not a contiguous array of the dtype already.
+        Device: checked, never copied.  below: every element must be in 0..below-1."""
+        if a is None:
+            return None
+        if self.on_device:
+            _check_device_tensor(a, shape, self._dtype(kind), self.device, name)
+        else:
+            a = np.asarray(a, self._dtype(kind))
+            if a.size != math.prod(shape):
+                raise ValueError(f"{name} must have shape {tuple(shape)}")
+            a = np.ascontiguousarray(a.reshape(shape))
+        if below is not None and a.shape[0] and not (0 <= int(a.min()) and int(a.max()) < below):
+            raise ValueError(f"every id must be in 0..{below - 1}")
+        self._keep.append(a)
+        return a
+
+    def hits(self, hits, total):
+        """DeviceScene.trace's records of `total` rays: a HIT_DTYPE array on the host, an (total, 12) float32 tensor on the device"""
+        if self.on_device:
+            return self.inp(hits, (total, 12), "hits")
+        h = np.ascontiguousarray(hits)
+        if h.dtype != HIT_DTYPE or h.shape != (total,):
+            raise ValueError("host hits must be an array of HIT_DTYPE, one record per ray")
+        self._keep.append(h)
+        return h
+
+    def columns(self, n, *named):
+        """(arrays, row stride in floats) of (n, 3) float32 inputs given as (array, name) pairs and read in place: each contiguous, or all
+        of them column ranges of one contiguous (n, S) array — fw_render_aovs' records (aov[:, 8:11], aov[:, 4:7]), a ray buffer's
+        rays[:, 3:6] — with unit column stride and one common row stride >= 3.  Host arrays laid out otherwise are copied."""
+        arrays = [a for a, _ in named]
+        if self.on_device:
+            s0 = int(arrays[0].stride(0)) if arrays[0].dim() == 2 else 0
+            stride = s0 if n > 1 else max(3, s0)
+            for t, name in named:
+                if (t.dtype != self._torch.float32 or tuple(t.shape) != (n, 3) or t.stride(1) != 1 or t.device.type != "cuda"
+                        or (t.device.index or 0) != self.device or (n > 1 and int(t.stride(0)) != stride) or stride < 3):
+                    raise ValueError(f"{name} must be an ({n}, 3) float32 tensor on cuda:{self.device} with unit column stride and a row stride >= 3, "
+                                     "the same as the arrays it comes with")
+        else:
+            arrays = [np.asarray(a, np.float32) for a in arrays]
+            for a, (_, name) in zip(arrays, named):
+                if a.size != n * 3:
+                    raise ValueError(f"{name} must have shape ({n}, 3)")
+            arrays = [a.reshape(n, 3) for a in arrays]
+            st = arrays[0].strides
+            if not (st[1] == 4 and st[0] % 4 == 0 and st[0] >= 12 and all(a.strides == st for a in arrays)):
+                arrays = [np.ascontiguousarray(a) for a in arrays]
+            stride = arrays[0].strides[0] // 4
+        self._keep += arrays
+        return arrays, stride
+
+    def new(self, shape, kind="f32", fill=None):
+        """a new output on the call's side: uninitialised, or filled with `fill`"""
+        if self.on_device:
+            if fill is None:
+                return self._torch.empty(shape, dtype=self._dtype(kind), device=self.dev)
+            return self._torch.full(shape, fill, dtype=self._dtype(kind), device=self.dev)
+        return np.empty(shape, self._dtype(kind)) if fill is None else np.full(shape, fill, self._dtype(kind))
+
+    def new_hits(self, n):
+        """new records of n rays for fw_trace_rays to fill, of the kind hits() takes"""
+        return self.new((n, 12)) if self.on_device else np.zeros(n, HIT_DTYPE)
+
+    def out(self, a, shape, name, fill=None):
+        """a float32 array that the call writes or updates in place: the caller's own `a`, checked and never copied, or for None a new one"""
+        if a is None:
+            return self.new(shape, fill=fill)
+        if self.on_device:
+            _check_device_tensor(a, shape, self._torch.float32, self.device, name)
+        else:
+            _host_f32(a, shape, name)
+        return a
+
+    def tail(self, stream):
+        """the (on_device, stream) arguments that end a call; stream None: the current torch stream"""
+        return (1, _stream_arg(stream, self.dev)) if self.on_device else (0, None)
+
+    def params(self, p, stream=None):
+        """the same two, for a call that carries them in its params struct"""
+        if self.on_device:
+            p.on_device, p.stream = 1, _stream_arg(stream, self.dev)
 
 
 def _model_abi(model, chunk=None):
@@ -441,15 +565,10 @@ def model_rays(model, first_sample=0, n_samples=1, device=0, out=None, stream=No
     current torch stream); returned."""
     lib = load()
     m = _model_abi(model)
-    shape = (int(n_samples), int(m.width) * int(m.height), 6)
-    if out is not None:
-        import torch
-        _check_device_tensor(out, shape, torch.float32, device, "out")
-        _check(lib, lib.fw_model_rays(C.byref(m), int(device), int(first_sample), int(n_samples), out.data_ptr(), 1, _stream_arg(stream, out.device)))
-        return out
-    rays = np.empty(shape, np.float32)
-    _check(lib, lib.fw_model_rays(C.byref(m), int(device), int(first_sample), int(n_samples), rays.ctypes.data, 0, None))
-    return rays
+    s = _Side(out, device)
+    out = s.out(out, (int(n_samples), int(m.width) * int(m.height), 6), "out")
+    _check(lib, lib.fw_model_rays(C.byref(m), int(device), int(first_sample), int(n_samples), s.ptr(out), *s.tail(stream)))
+    return out
 
 
 def _probe_abi(probes, chunk=None):
@@ -466,18 +585,26 @@ def probe_rays(probes, round=0, first_probe=0, n=None, device=0, out=None, strea
     array; out: a contiguous float32 device tensor of that shape on cuda:`device` to fill instead, on `stream` (default: the current
     torch stream); returned."""
     lib = load()
-    s, _pos = _probe_abi(probes)
+    ps, _pos = _probe_abi(probes)
     if n is None:
-        n = int(s.n_probes) - int(first_probe)
-    shape = (int(n) * int(s.directions), 6)
-    if out is not None:
-        import torch
-        _check_device_tensor(out, shape, torch.float32, device, "out")
-        _check(lib, lib.fw_probe_rays(C.byref(s), int(device), int(round), int(first_probe), int(n), out.data_ptr(), 1, _stream_arg(stream, out.device)))
-        return out
-    rays = np.empty(shape, np.float32)
-    _check(lib, lib.fw_probe_rays(C.byref(s), int(device), int(round), int(first_probe), int(n), rays.ctypes.data, 0, None))
-    return rays
+        n = int(ps.n_probes) - int(first_probe)
+    s = _Side(out, device)
+    out = s.out(out, (int(n) * int(ps.directions), 6), "out")
+    _check(lib, lib.fw_probe_rays(C.byref(ps), int(device), int(round), int(first_probe), int(n), s.ptr(out), *s.tail(stream)))
+    return out
+
+
+def _per_probe(rays, other, other_cols, directions):
+    """(N, N * D) of one round's rays (N * D, 6) and the (N * D, ...) array that comes with them: accum (other_cols 4) or hits (None)"""
+    d = int(directions)
+    total = int(rays.shape[0])
+    ok = d >= 1 and total % d == 0 and tuple(rays.shape) == (total, 6)
+    if other_cols is None:
+        if not ok or int(other.shape[0]) != total:
+            raise ValueError(f"rays must have shape (N * {d}, 6) and hits N * {d} records")
+    elif not ok or tuple(other.shape) != (total, other_cols):
+        raise ValueError(f"rays must have shape (N * {d}, 6) and accum (N * {d}, {other_cols})")
+    return total // d, total
 
 
 def probe_project(rays, accum, samples, directions, sums=None, device=0, stream=None):
@@ -485,27 +612,11 @@ def probe_project(rays, accum, samples, directions, sums=None, device=0, stream=
     6) and accum (N * D, 4) float32, sums (N, 9, 3) float32 updated in place (None: zeros); numpy arrays, or contiguous torch tensors
     on cuda:`device`, projected on `stream` (default: the current torch stream) where they lie.  Returns sums."""
     lib = load()
-    d = int(directions)
-    total = int(rays.shape[0])
-    if d < 1 or total % d or tuple(rays.shape) != (total, 6) or tuple(accum.shape) != (total, 4):
-        raise ValueError(f"rays must have shape (N * {d}, 6) and accum (N * {d}, 4)")
-    n = total // d
-    if type(rays).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
-        _check_device_tensor(accum, (total, 4), torch.float32, device, "accum")
-        if sums is None:
-            sums = torch.zeros((n, 9, 3), dtype=torch.float32, device=rays.device)
-        _check_device_tensor(sums, (n, 9, 3), torch.float32, device, "sums")
-        _check(lib, lib.fw_probe_project(int(device), n, d, int(samples), rays.data_ptr(), accum.data_ptr(), sums.data_ptr(), 1,
-                                         _stream_arg(stream, rays.device)))
-        return sums
-    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
-    a = np.ascontiguousarray(np.asarray(accum, dtype=np.float32))
-    if sums is None:
-        sums = np.zeros((n, 9, 3), np.float32)
-    _host_f32(sums, (n, 9, 3), "sums")
-    _check(lib, lib.fw_probe_project(int(device), n, d, int(samples), r.ctypes.data, a.ctypes.data, sums.ctypes.data, 0, None))
+    n, total = _per_probe(rays, accum, 4, directions)
+    s = _Side(rays, device)
+    r, a = s.inp(rays, (total, 6), "rays"), s.inp(accum, (total, 4), "accum")
+    sums = s.out(sums, (n, 9, 3), "sums", fill=0.0)
+    _check(lib, lib.fw_probe_project(int(device), n, int(directions), int(samples), *s.ptrs(r, a, sums), *s.tail(stream)))
     return sums
 
 
@@ -516,86 +627,55 @@ def _grid_abi(grid):
     return g.to_abi(), g.n_probes
 
 
-def _vis_args(depth, moments, normal_bias, n_probes, on_device, device):
-    """(fw_probe_depth, moments pointer, bias, what keeps the pointer alive) of a _vis call: moments (n, R, R, 2) float32, a device tensor
-    when the call's other arrays are"""
-    pd = depth.to_abi()
-    shape = (n_probes, int(pd.resolution), int(pd.resolution), 2)
-    if on_device:
-        import torch
-        _check_device_tensor(moments, shape, torch.float32, device, "moments")
-        return pd, moments.data_ptr(), float(normal_bias), moments
-    m = np.ascontiguousarray(np.asarray(moments, np.float32).reshape(shape))
-    return pd, m.ctypes.data, float(normal_bias), m
+def _vis_of(depth, moments, normal_bias):
+    """the visibility of a lookup as (depth, moments, normal_bias), or None without one"""
+    if (depth is None) != (moments is None):
+        raise ValueError("depth and moments are given together or not at all")
+    return None if depth is None else (depth, moments, normal_bias)
 
 
-def _placement_arg(placement, n_probes, on_device, device):
-    """(placement pointer, what keeps it alive) of a _placed call: placement (n, 4) float32 records (ox, oy, oz, a), a device tensor when
-    the call's other arrays are"""
-    if on_device:
-        import torch
-        _check_device_tensor(placement, (n_probes, 4), torch.float32, device, "placement")
-        return placement.data_ptr(), placement
-    m = np.ascontiguousarray(np.asarray(placement, np.float32).reshape(n_probes, 4))
-    return m.ctypes.data, m
-
-
-def _placed_call(fn, g, sh_ptr, vis, placement, n_probes, on_device, device, tail):
-    """fn = fw_probe_irradiance_placed or fw_probe_shade_placed over (grid, sh, pd, moments, normal_bias, placement, *tail); vis None: no
-    visibility (pd and moments NULL)"""
-    pl, _keep_pl = _placement_arg(placement, n_probes, on_device, device)
+def _vis_args(s, vis, n_probes):
+    """[fw_probe_depth, moments pointer, normal_bias] of a lookup; vis (see _vis_of) None: no visibility, [NULL, NULL, 0].  moments
+    (n, R, R, 2) float32, on the side of the call's other arrays"""
     if vis is None:
-        return fn(C.byref(g), sh_ptr, None, None, 0.0, pl, *tail)
-    pd, mom, bias, _keep = _vis_args(*vis, n_probes, on_device, device)
-    return fn(C.byref(g), sh_ptr, C.byref(pd), mom, bias, pl, *tail)
+        return [None, None, 0.0]
+    depth, moments, normal_bias = vis
+    pd = depth.to_abi()
+    R = int(pd.resolution)
+    return [C.byref(pd), s.ptr(s.inp(moments, (n_probes, R, R, 2), "moments")), float(normal_bias)]
+
+
+def _placement_arg(s, placement, n_probes):
+    """the placement pointer of a lookup: (n, 4) float32 records (ox, oy, oz, a), on the side of the call's other arrays; None: NULL"""
+    return s.ptr(s.inp(placement, (n_probes, 4), "placement"))
+
+
+def _sh_lookup(s, lib, stem, g, sh, n_probes, vis, placement):
+    """(the entry point, its leading arguments) of fw_probe_irradiance or fw_probe_shade (`stem`): the plain form, _vis with a visibility
+    only, _placed with a placement (and there a visibility or NULLs)"""
+    head = [C.byref(g), s.ptr(s.inp(sh, (n_probes, 9, 3), "sh"))]
+    if placement is not None:
+        return getattr(lib, stem + "_placed"), head + _vis_args(s, vis, n_probes) + [_placement_arg(s, placement, n_probes)]
+    if vis is not None:
+        return getattr(lib, stem + "_vis"), head + _vis_args(s, vis, n_probes)
+    return getattr(lib, stem), head
 
 
 def probe_irradiance(grid, sh, positions, normals, out=None, stream=None, device=0, _vis=None, _placed=None):
     """fw_probe_irradiance: the irradiance the probe grid `grid` (an api.ProbeGrid, or an api.ProbeSet made by ProbeSet.grid) with the
     coefficients sh (n, 9, 3) float32 gives at the points `positions` with the normals `normals`, (N, 3) float32 each; not clamped.
     numpy arrays: returns an (N, 3) float32 array (out: a contiguous float32 array of that shape to fill instead).  Torch tensors on
-    cuda:`device`: looked up on `stream` (default: the current torch stream) where they lie, positions and normals contiguous (N, 3)
-    or two column ranges of one contiguous (N, S) tensor such as fw_render_aovs' records (aov[:, 8:11], aov[:, 4:7]); returns a device
-    tensor (out: a contiguous (N, 3) float32 tensor to fill instead)."""
+    cuda:`device`: looked up on `stream` (default: the current torch stream) where they lie; returns a device tensor (out: a contiguous
+    (N, 3) float32 tensor to fill instead).  positions and normals: contiguous (N, 3), or two column ranges of one contiguous (N, S)
+    array such as fw_render_aovs' records (aov[:, 8:11], aov[:, 4:7]), read in place."""
     lib = load()
     g, n_probes = _grid_abi(grid)
-    if type(positions).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(sh, (n_probes, 9, 3), torch.float32, device, "sh")
-        n = int(positions.shape[0])
-        stride = int(positions.stride(0)) if n > 1 else max(3, int(positions.stride(0)))
-        for t, name in ((positions, "positions"), (normals, "normals")):
-            if (t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (n, 3) or t.stride(1) != 1 or t.device.type != "cuda"
-                    or (t.device.index or 0) != device or (n > 1 and int(t.stride(0)) != stride) or stride < 3):
-                raise ValueError(f"{name} must be an (N, 3) float32 tensor on cuda:{device} with unit column stride and the same row stride >= 3 as the other")
-        if out is None:
-            out = torch.empty((n, 3), dtype=torch.float32, device=positions.device)
-        _check_device_tensor(out, (n, 3), torch.float32, device, "out")
-        tail = (int(device), n, positions.data_ptr(), normals.data_ptr(), stride, out.data_ptr(), 1, _stream_arg(stream, positions.device))
-        if _placed is not None:
-            _check(lib, _placed_call(lib.fw_probe_irradiance_placed, g, sh.data_ptr(), _vis, _placed, n_probes, True, device, tail))
-        elif _vis is not None:
-            pd, mom, bias, _keep = _vis_args(*_vis, n_probes, True, device)
-            _check(lib, lib.fw_probe_irradiance_vis(C.byref(g), sh.data_ptr(), C.byref(pd), mom, bias, *tail))
-        else:
-            _check(lib, lib.fw_probe_irradiance(C.byref(g), sh.data_ptr(), *tail))
-        return out
-    s = np.ascontiguousarray(np.asarray(sh, np.float32).reshape(n_probes, 9, 3))
-    p = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))
-    nr = np.ascontiguousarray(np.asarray(normals, np.float32).reshape(-1, 3))
-    if nr.shape != p.shape:
-        raise ValueError("positions and normals must have the same shape (N, 3)")
-    if out is None:
-        out = np.empty(p.shape, np.float32)
-    _host_f32(out, p.shape, "out")
-    tail = (int(device), int(p.shape[0]), p.ctypes.data, nr.ctypes.data, 3, out.ctypes.data, 0, None)
-    if _placed is not None:
-        _check(lib, _placed_call(lib.fw_probe_irradiance_placed, g, s.ctypes.data, _vis, _placed, n_probes, False, device, tail))
-    elif _vis is not None:
-        pd, mom, bias, _keep = _vis_args(*_vis, n_probes, False, device)
-        _check(lib, lib.fw_probe_irradiance_vis(C.byref(g), s.ctypes.data, C.byref(pd), mom, bias, *tail))
-    else:
-        _check(lib, lib.fw_probe_irradiance(C.byref(g), s.ctypes.data, *tail))
+    s = _Side(positions, device)
+    n = s.count(positions, 3)
+    fn, head = _sh_lookup(s, lib, "fw_probe_irradiance", g, sh, n_probes, _vis, _placed)
+    (p, nr), stride = s.columns(n, (positions, "positions"), (normals, "normals"))
+    out = s.out(out, (n, 3), "out")
+    _check(lib, fn(*head, int(device), n, *s.ptrs(p, nr), stride, s.ptr(out), *s.tail(stream)))
     return out
 
 
@@ -611,22 +691,7 @@ def probe_irradiance_placed(grid, sh, placement, positions, normals, depth=None,
     classified probes: placement (n, 4) float32 records (ox, oy, oz, a) as DeviceScene.relocate_probes returns them (a device tensor when
     the points are).  An inactive probe (a == 0) is skipped and the remaining weights are always normalised.  Everything else as
     probe_irradiance."""
-    if (depth is None) != (moments is None):
-        raise ValueError("depth and moments are given together or not at all")
-    vis = None if depth is None else (depth, moments, normal_bias)
-    return probe_irradiance(grid, sh, positions, normals, out, stream, device, _vis=vis, _placed=placement)
-
-
-def _hits_arg(hits, total, on_device, device):
-    """(hits pointer, what keeps it alive): a HIT_DTYPE array of `total` records, or an (total, 12) float32 device tensor"""
-    if on_device:
-        import torch
-        _check_device_tensor(hits, (total, 12), torch.float32, device, "hits")
-        return hits.data_ptr(), hits
-    h = np.ascontiguousarray(hits)
-    if h.dtype != HIT_DTYPE or h.shape != (total,):
-        raise ValueError("host hits must be an array of HIT_DTYPE, one record per ray")
-    return h.ctypes.data, h
+    return probe_irradiance(grid, sh, positions, normals, out, stream, device, _vis=_vis_of(depth, moments, normal_bias), _placed=placement)
 
 
 def probe_survey(rays, hits, directions, out=None, device=0, stream=None):
@@ -635,26 +700,11 @@ def probe_survey(rays, hits, directions, out=None, device=0, stream=None):
     or an (N * D, 12) float32 device tensor for rays on cuda:`device`, surveyed on `stream` (default: the current torch stream) where they
     lie.  out: an array or tensor of that shape to overwrite instead.  Returns the survey."""
     lib = load()
-    d = int(directions)
-    total = int(rays.shape[0])
-    if d < 1 or total % d or tuple(rays.shape) != (total, 6) or int(hits.shape[0]) != total:
-        raise ValueError(f"rays must have shape (N * {d}, 6) and hits N * {d} records")
-    n = total // d
-    if type(rays).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
-        h, _keep = _hits_arg(hits, total, True, device)
-        if out is None:
-            out = torch.empty((n, 3, 4), dtype=torch.float32, device=rays.device)
-        _check_device_tensor(out, (n, 3, 4), torch.float32, device, "out")
-        _check(lib, lib.fw_probe_survey(int(device), n, d, rays.data_ptr(), h, out.data_ptr(), 1, _stream_arg(stream, rays.device)))
-        return out
-    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
-    h, _keep = _hits_arg(hits, total, False, device)
-    if out is None:
-        out = np.empty((n, 3, 4), np.float32)
-    _host_f32(out, (n, 3, 4), "out")
-    _check(lib, lib.fw_probe_survey(int(device), n, d, r.ctypes.data, h, out.ctypes.data, 0, None))
+    n, total = _per_probe(rays, hits, None, directions)
+    s = _Side(rays, device)
+    r, h = s.inp(rays, (total, 6), "rays"), s.hits(hits, total)
+    out = s.out(out, (n, 3, 4), "out")
+    _check(lib, lib.fw_probe_survey(int(device), n, int(directions), *s.ptrs(r, h, out), *s.tail(stream)))
     return out
 
 
@@ -665,16 +715,10 @@ def probe_relocate_step(relocation, survey, placement, directions, move=True, de
     lib = load()
     rl = relocation.to_abi()
     n = int(placement.shape[0])
-    if type(placement).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(survey, (n, 3, 4), torch.float32, device, "survey")
-        _check_device_tensor(placement, (n, 4), torch.float32, device, "placement")
-        _check(lib, lib.fw_probe_relocate_step(int(device), C.byref(rl), n, int(directions), survey.data_ptr(), placement.data_ptr(), int(bool(move)), 1,
-                                               _stream_arg(stream, placement.device)))
-        return placement
-    s = np.ascontiguousarray(np.asarray(survey, np.float32).reshape(n, 3, 4))
-    _host_f32(placement, (n, 4), "placement")
-    _check(lib, lib.fw_probe_relocate_step(int(device), C.byref(rl), n, int(directions), s.ctypes.data, placement.ctypes.data, int(bool(move)), 0, None))
+    s = _Side(placement, device)
+    sv = s.inp(survey, (n, 3, 4), "survey")
+    s.out(placement, (n, 4), "placement")
+    _check(lib, lib.fw_probe_relocate_step(int(device), C.byref(rl), n, int(directions), *s.ptrs(sv, placement), int(bool(move)), *s.tail(stream)))
     return placement
 
 
@@ -685,29 +729,12 @@ def probe_depth_reduce(depth, rays, hits, directions, sums=None, device=0, strea
     current torch stream) where they lie.  Returns sums."""
     lib = load()
     pd = depth.to_abi()
-    d, R = int(directions), int(pd.resolution)
-    total = int(rays.shape[0])
-    if d < 1 or total % d or tuple(rays.shape) != (total, 6) or int(hits.shape[0]) != total:
-        raise ValueError(f"rays must have shape (N * {d}, 6) and hits N * {d} records")
-    n = total // d
-    if type(rays).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
-        _check_device_tensor(hits, (total, 12), torch.float32, device, "hits")
-        if sums is None:
-            sums = torch.zeros((n, R, R, 4), dtype=torch.float32, device=rays.device)
-        _check_device_tensor(sums, (n, R, R, 4), torch.float32, device, "sums")
-        _check(lib, lib.fw_probe_depth_reduce(int(device), C.byref(pd), n, d, rays.data_ptr(), hits.data_ptr(), sums.data_ptr(), 1,
-                                              _stream_arg(stream, rays.device)))
-        return sums
-    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
-    h = np.ascontiguousarray(hits)
-    if h.dtype != HIT_DTYPE:
-        raise ValueError("host hits must be an array of HIT_DTYPE")
-    if sums is None:
-        sums = np.zeros((n, R, R, 4), np.float32)
-    _host_f32(sums, (n, R, R, 4), "sums")
-    _check(lib, lib.fw_probe_depth_reduce(int(device), C.byref(pd), n, d, r.ctypes.data, h.ctypes.data, sums.ctypes.data, 0, None))
+    R = int(pd.resolution)
+    n, total = _per_probe(rays, hits, None, directions)
+    s = _Side(rays, device)
+    r, h = s.inp(rays, (total, 6), "rays"), s.hits(hits, total)
+    sums = s.out(sums, (n, R, R, 4), "sums", fill=0.0)
+    _check(lib, lib.fw_probe_depth_reduce(int(device), C.byref(pd), n, int(directions), *s.ptrs(r, h, sums), *s.tail(stream)))
     return sums
 
 
@@ -718,27 +745,12 @@ def probe_radiance_reduce(radiance, rays, accum, samples, directions, sums=None,
     current torch stream) where they lie.  Returns sums."""
     lib = load()
     pr = radiance.to_abi()
-    d, R = int(directions), int(pr.resolution)
-    total = int(rays.shape[0])
-    if d < 1 or total % d or tuple(rays.shape) != (total, 6) or tuple(accum.shape) != (total, 4):
-        raise ValueError(f"rays must have shape (N * {d}, 6) and accum (N * {d}, 4)")
-    n = total // d
-    if type(rays).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
-        _check_device_tensor(accum, (total, 4), torch.float32, device, "accum")
-        if sums is None:
-            sums = torch.zeros((n, R, R, 4), dtype=torch.float32, device=rays.device)
-        _check_device_tensor(sums, (n, R, R, 4), torch.float32, device, "sums")
-        _check(lib, lib.fw_probe_radiance_reduce(int(device), C.byref(pr), n, d, int(samples), rays.data_ptr(), accum.data_ptr(), sums.data_ptr(), 1,
-                                                 _stream_arg(stream, rays.device)))
-        return sums
-    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
-    a = np.ascontiguousarray(np.asarray(accum, dtype=np.float32))
-    if sums is None:
-        sums = np.zeros((n, R, R, 4), np.float32)
-    _host_f32(sums, (n, R, R, 4), "sums")
-    _check(lib, lib.fw_probe_radiance_reduce(int(device), C.byref(pr), n, d, int(samples), r.ctypes.data, a.ctypes.data, sums.ctypes.data, 0, None))
+    R = int(pr.resolution)
+    n, total = _per_probe(rays, accum, 4, directions)
+    s = _Side(rays, device)
+    r, a = s.inp(rays, (total, 6), "rays"), s.inp(accum, (total, 4), "accum")
+    sums = s.out(sums, (n, R, R, 4), "sums", fill=0.0)
+    _check(lib, lib.fw_probe_radiance_reduce(int(device), C.byref(pr), n, int(directions), int(samples), *s.ptrs(r, a, sums), *s.tail(stream)))
     return sums
 
 
@@ -751,49 +763,19 @@ def probe_radiance_prefilter(radiance, sums, out=None, device=0, stream=None):
     pr = radiance.to_abi()
     R, M = int(pr.resolution), int(radiance.texels)
     n = int(sums.shape[0])
-    if type(sums).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(sums, (n, R, R, 4), torch.float32, device, "sums")
-        if out is None:
-            out = torch.empty((n, M, 4), dtype=torch.float32, device=sums.device)
-        _check_device_tensor(out, (n, M, 4), torch.float32, device, "out")
-        _check(lib, lib.fw_probe_radiance_prefilter(int(device), C.byref(pr), n, sums.data_ptr(), out.data_ptr(), 1, _stream_arg(stream, sums.device)))
-        return out
-    s = np.ascontiguousarray(np.asarray(sums, np.float32).reshape(n, R, R, 4))
-    if out is None:
-        out = np.empty((n, M, 4), np.float32)
-    _host_f32(out, (n, M, 4), "out")
-    _check(lib, lib.fw_probe_radiance_prefilter(int(device), C.byref(pr), n, s.ctypes.data, out.ctypes.data, 0, None))
+    s = _Side(sums, device)
+    sm = s.inp(sums, (n, R, R, 4), "sums")
+    out = s.out(out, (n, M, 4), "out")
+    _check(lib, lib.fw_probe_radiance_prefilter(int(device), C.byref(pr), n, *s.ptrs(sm, out), *s.tail(stream)))
     return out
 
 
-def _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, on_device, device):
-    """the (pr, maps, pd, moments, normal_bias, placement) arguments of fw_probe_radiance_lookup and fw_probe_shade_glossy, and what keeps
-    their pointers alive: maps (n, M, 4) float32; depth with moments, and placement, optional; device tensors when the call's other
-    arrays are"""
-    if (depth is None) != (moments is None):
-        raise ValueError("depth and moments are given together or not at all")
+def _radiance_args(s, radiance, maps, vis, placement, n_probes):
+    """the [pr, maps, pd, moments, normal_bias, placement] arguments of fw_probe_radiance_lookup and the glossy shades: maps (n, M, 4)
+    float32; vis (see _vis_of) and placement optional; on the side of the call's other arrays"""
     pr = radiance.to_abi()
-    shape = (n_probes, int(radiance.texels), 4)
-    keep = [pr]
-    if on_device:
-        import torch
-        _check_device_tensor(maps, shape, torch.float32, device, "maps")
-        mp = maps.data_ptr()
-    else:
-        maps = np.ascontiguousarray(np.asarray(maps, np.float32).reshape(shape))
-        mp = maps.ctypes.data
-    keep.append(maps)
-    pd = mom = pl = None
-    bias = 0.0
-    if depth is not None:
-        pdv, mom, bias, k = _vis_args(depth, moments, normal_bias, n_probes, on_device, device)
-        pd = C.byref(pdv)
-        keep += [pdv, k]
-    if placement is not None:
-        pl, k = _placement_arg(placement, n_probes, on_device, device)
-        keep.append(k)
-    return (C.byref(pr), mp, pd, mom, bias, pl), keep
+    mp = s.inp(maps, (n_probes, int(radiance.texels), 4), "maps")
+    return [C.byref(pr), s.ptr(mp)] + _vis_args(s, vis, n_probes) + [_placement_arg(s, placement, n_probes)]
 
 
 def probe_radiance_lookup(grid, radiance, maps, positions, normals, dirs, roughness, depth=None, moments=None, normal_bias=0.0, placement=None,
@@ -806,77 +788,48 @@ def probe_radiance_lookup(grid, radiance, maps, positions, normals, dirs, roughn
     torch stream) where they lie; returns a device tensor.  out: an array or tensor of that shape to fill instead."""
     lib = load()
     g, n_probes = _grid_abi(grid)
-    if type(positions).__module__.startswith("torch"):
-        import torch
-        n = int(positions.shape[0])
-        for t, shape, name in ((positions, (n, 3), "positions"), (normals, (n, 3), "normals"), (dirs, (n, 3), "dirs"), (roughness, (n,), "roughness")):
-            _check_device_tensor(t, shape, torch.float32, device, name)
-        head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, True, device)
-        if out is None:
-            out = torch.empty((n, 3), dtype=torch.float32, device=positions.device)
-        _check_device_tensor(out, (n, 3), torch.float32, device, "out")
-        _check(lib, lib.fw_probe_radiance_lookup(C.byref(g), *head, int(device), n, positions.data_ptr(), normals.data_ptr(), 3, dirs.data_ptr(),
-                                                 roughness.data_ptr(), out.data_ptr(), 1, _stream_arg(stream, positions.device)))
-        return out
-    p = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))
-    n = int(p.shape[0])
-    nr = np.ascontiguousarray(np.asarray(normals, np.float32).reshape(-1, 3))
-    dr = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
-    ro = np.ascontiguousarray(np.asarray(roughness, np.float32).reshape(-1))
-    if nr.shape != p.shape or dr.shape != p.shape or ro.shape != (n,):
-        raise ValueError("positions, normals and dirs must have the same shape (N, 3) and roughness (N,)")
-    head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, False, device)
-    if out is None:
-        out = np.empty((n, 3), np.float32)
-    _host_f32(out, (n, 3), "out")
-    _check(lib, lib.fw_probe_radiance_lookup(C.byref(g), *head, int(device), n, p.ctypes.data, nr.ctypes.data, 3, dr.ctypes.data, ro.ctypes.data,
-                                             out.ctypes.data, 0, None))
+    s = _Side(positions, device)
+    n = s.count(positions, 3)
+    p, nr, dr = (s.inp(a, (n, 3), name) for a, name in ((positions, "positions"), (normals, "normals"), (dirs, "dirs")))
+    ro = s.inp(roughness, (n,), "roughness")
+    head = _radiance_args(s, radiance, maps, _vis_of(depth, moments, normal_bias), placement, n_probes)
+    out = s.out(out, (n, 3), "out")
+    _check(lib, lib.fw_probe_radiance_lookup(C.byref(g), *head, int(device), n, *s.ptrs(p, nr), 3, *s.ptrs(dr, ro, out), *s.tail(stream)))
     return out
 
 
-def probe_shade_glossy(grid, sh, radiance, maps, aov, spec, view, width, height, depth=None, moments=None, normal_bias=0.0, placement=None,
-                       gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear")):
-    """fw_probe_shade_glossy: probe_shade_placed where spec's roughness is not > 0, and elsewhere a conductor lit by the radiance maps
-    along the mirrored view direction: spec (N, 4) float32 (F0.rgb, rho), view (N, 3) float32 — or, on the device, three columns of a
-    contiguous (N, S) tensor such as rays[:, 3:6] — the ray direction from the eye.  radiance, maps, depth, moments, normal_bias and
-    placement as probe_radiance_lookup; everything else as probe_shade."""
+def _table_arg(s, table):
+    """(pointer, n_mu, n_rho) of an (n_rho, n_mu, 2) float32 table, on the side of the call's other arrays"""
+    shape = tuple(table.shape) if s.on_device else np.shape(table)
+    if len(shape) != 3 or shape[2] != 2:
+        raise ValueError("table must have the shape (n_rho, n_mu, 2)")
+    return s.ptr(s.inp(table, shape, "table")), int(shape[1]), int(shape[0])
+
+
+def _probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, vis=None, placement=None, glossy=None, split=None):
+    """The one body of probe_shade and its _vis, _placed, _glossy and _split forms.  vis: see _vis_of; glossy: (radiance, maps, spec, view)
+    or None for the diffuse forms; split: (table, flags) or None, with glossy only."""
     lib = load()
     g, n_probes = _grid_abi(grid)
     n = int(width) * int(height)
+    s = _Side(aov, device)
     p = A.fw_probe_shade_params()
     p.width, p.height, p.gamma, p.device = int(width), int(height), float(gamma), int(device)
-    want = [name in outputs for name in ("rgb8", "gamma", "linear")]
-    if type(aov).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(sh, (n_probes, 9, 3), torch.float32, device, "sh")
-        _check_device_tensor(aov, (n, 12), torch.float32, device, "aov")
-        _check_device_tensor(spec, (n, 4), torch.float32, device, "spec")
-        stride = int(view.stride(0)) if n > 1 else max(3, int(view.stride(0)))
-        if (view.dtype != torch.float32 or tuple(view.shape) != (n, 3) or view.stride(1) != 1 or view.device.type != "cuda"
-                or (view.device.index or 0) != device or stride < 3):
-            raise ValueError(f"view must be an (N, 3) float32 tensor on cuda:{device} with unit column stride and a row stride >= 3")
-        head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, True, device)
-        dev = aov.device
-        rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev) if want[0] else None
-        gam = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[1] else None
-        lin = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[2] else None
-        p.on_device = 1
-        p.stream = _stream_arg(stream, dev)
-        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        _check(lib, lib.fw_probe_shade_glossy(C.byref(g), sh.data_ptr(), *head, C.byref(p), aov.data_ptr(), spec.data_ptr(), view.data_ptr(), stride,
-                                              ptr(lin), ptr(gam), ptr(rgb8)))
-        return rgb8, gam, lin
-    s = np.ascontiguousarray(np.asarray(sh, np.float32).reshape(n_probes, 9, 3))
-    a = np.ascontiguousarray(np.asarray(aov, np.float32).reshape(n, 12))
-    sp = np.ascontiguousarray(np.asarray(spec, np.float32).reshape(n, 4))
-    vw = np.ascontiguousarray(np.asarray(view, np.float32).reshape(n, 3))
-    head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, False, device)
-    rgb8 = np.empty((n, 3), np.uint8) if want[0] else None
-    gam = np.empty((n, 3), np.float32) if want[1] else None
-    lin = np.empty((n, 3), np.float32) if want[2] else None
-    ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
-    _check(lib, lib.fw_probe_shade_glossy(C.byref(g), s.ctypes.data, *head, C.byref(p), a.ctypes.data, sp.ctypes.data, vw.ctypes.data, 3, ptr(lin),
-                                          ptr(gam), ptr(rgb8)))
+    if glossy is None:
+        fn, head = _sh_lookup(s, lib, "fw_probe_shade", g, sh, n_probes, vis, placement)
+        mid = (C.byref(p), s.ptr(s.inp(aov, (n, 12), "aov")))
+    else:
+        radiance, maps, spec, view = glossy
+        fn, head = lib.fw_probe_shade_glossy, [C.byref(g), s.ptr(s.inp(sh, (n_probes, 9, 3), "sh"))]
+        a, sp = s.inp(aov, (n, 12), "aov"), s.inp(spec, (n, 4), "spec")
+        (vw,), stride = s.columns(n, (view, "view"))
+        head += _radiance_args(s, radiance, maps, vis, placement, n_probes)
+        mid = (C.byref(p), *s.ptrs(a, sp, vw), stride)
+        if split is not None:
+            fn, mid = lib.fw_probe_shade_split, mid + _table_arg(s, split[0]) + (int(split[1]),)
+    rgb8, gam, lin = (s.new((n, 3), kind) if name in outputs else None for name, kind in (("rgb8", "u8"), ("gamma", "f32"), ("linear", "f32")))
+    s.params(p, stream)
+    _check(lib, fn(*head, *mid, *s.ptrs(lin, gam, rgb8)))
     return rgb8, gam, lin
 
 
@@ -886,62 +839,39 @@ def probe_shade(grid, sh, aov, width, height, gamma=2.2, device=0, stream=None, 
     (numpy): returns (rgb8, gamma, linear) host arrays of shape (N, 3).  Contiguous float32 torch tensors on cuda:`device`: shaded on
     `stream` (default: the current torch stream), returns device tensors.  outputs: which of the three to compute; the others are
     returned as None.  width * height must be N."""
-    lib = load()
-    g, n_probes = _grid_abi(grid)
-    n = int(width) * int(height)
-    p = A.fw_probe_shade_params()
-    p.width, p.height, p.gamma, p.device = int(width), int(height), float(gamma), int(device)
-    want = [name in outputs for name in ("rgb8", "gamma", "linear")]
-    if type(aov).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(sh, (n_probes, 9, 3), torch.float32, device, "sh")
-        _check_device_tensor(aov, (n, 12), torch.float32, device, "aov")
-        dev = aov.device
-        rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev) if want[0] else None
-        gam = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[1] else None
-        lin = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[2] else None
-        p.on_device = 1
-        p.stream = _stream_arg(stream, dev)
-        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        tail = (C.byref(p), aov.data_ptr(), ptr(lin), ptr(gam), ptr(rgb8))
-        if _placed is not None:
-            _check(lib, _placed_call(lib.fw_probe_shade_placed, g, sh.data_ptr(), _vis, _placed, n_probes, True, device, tail))
-        elif _vis is not None:
-            pd, mom, bias, _keep = _vis_args(*_vis, n_probes, True, device)
-            _check(lib, lib.fw_probe_shade_vis(C.byref(g), sh.data_ptr(), C.byref(pd), mom, bias, *tail))
-        else:
-            _check(lib, lib.fw_probe_shade(C.byref(g), sh.data_ptr(), *tail))
-        return rgb8, gam, lin
-    s = np.ascontiguousarray(np.asarray(sh, np.float32).reshape(n_probes, 9, 3))
-    a = np.ascontiguousarray(np.asarray(aov, np.float32).reshape(n, 12))
-    rgb8 = np.empty((n, 3), np.uint8) if want[0] else None
-    gam = np.empty((n, 3), np.float32) if want[1] else None
-    lin = np.empty((n, 3), np.float32) if want[2] else None
-    ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
-    tail = (C.byref(p), a.ctypes.data, ptr(lin), ptr(gam), ptr(rgb8))
-    if _placed is not None:
-        _check(lib, _placed_call(lib.fw_probe_shade_placed, g, s.ctypes.data, _vis, _placed, n_probes, False, device, tail))
-    elif _vis is not None:
-        pd, mom, bias, _keep = _vis_args(*_vis, n_probes, False, device)
-        _check(lib, lib.fw_probe_shade_vis(C.byref(g), s.ctypes.data, C.byref(pd), mom, bias, *tail))
-    else:
-        _check(lib, lib.fw_probe_shade(C.byref(g), s.ctypes.data, *tail))
-    return rgb8, gam, lin
+    return _probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, _vis, _placed)
 
 
 def probe_shade_vis(grid, sh, depth, moments, aov, width, height, normal_bias=0.0, gamma=2.2, device=0, stream=None,
                     outputs=("rgb8", "gamma", "linear")):
     """fw_probe_shade_vis: probe_shade with the lookup of probe_irradiance_vis (depth, moments, normal_bias: see there)."""
-    return probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, _vis=(depth, moments, normal_bias))
+    return _probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, (depth, moments, normal_bias))
 
 
 def probe_shade_placed(grid, sh, placement, aov, width, height, depth=None, moments=None, normal_bias=0.0, gamma=2.2, device=0, stream=None,
                        outputs=("rgb8", "gamma", "linear")):
     """fw_probe_shade_placed: probe_shade with the lookup of probe_irradiance_placed (placement, depth, moments, normal_bias: see there)."""
-    if (depth is None) != (moments is None):
-        raise ValueError("depth and moments are given together or not at all")
-    vis = None if depth is None else (depth, moments, normal_bias)
-    return probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, _vis=vis, _placed=placement)
+    return _probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, _vis_of(depth, moments, normal_bias), placement)
+
+
+def probe_shade_glossy(grid, sh, radiance, maps, aov, spec, view, width, height, depth=None, moments=None, normal_bias=0.0, placement=None,
+                       gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear")):
+    """fw_probe_shade_glossy: probe_shade_placed where spec's roughness is not > 0, and elsewhere a conductor lit by the radiance maps
+    along the mirrored view direction: spec (N, 4) float32 (F0.rgb, rho), view (N, 3) float32 — contiguous, or three columns of a
+    contiguous (N, S) array such as rays[:, 3:6], read in place — the ray direction from the eye.  radiance, maps, depth, moments,
+    normal_bias and placement as probe_radiance_lookup; everything else as probe_shade."""
+    return _probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, _vis_of(depth, moments, normal_bias), placement,
+                        glossy=(radiance, maps, spec, view))
+
+
+def probe_shade_split(grid, sh, radiance, maps, aov, spec, view, table, width, height, flags=0, depth=None, moments=None, normal_bias=0.0,
+                      placement=None, gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear")):
+    """fw_probe_shade_split: probe_shade_glossy with the split sum's BRDF term: a glossy pixel is v ((F0 A + B) Ls) + (1 - v) a with (A, B)
+    looked up in `table` ((n_rho, n_mu, 2) float32, as ggx_table returns it; a device tensor when the other arrays are) at the cosine of
+    the view and the pixel's roughness; flags: FW_SPLIT_ENERGY multiplies by 1 + F0 (1 / (A + B) - 1).  Everything else as
+    probe_shade_glossy."""
+    return _probe_shade(grid, sh, aov, width, height, gamma, device, stream, outputs, _vis_of(depth, moments, normal_bias), placement,
+                        glossy=(radiance, maps, spec, view), split=(table, flags))
 
 
 def _lightmap_abi(lightmap, chunk=None):
@@ -957,19 +887,12 @@ def lightmap_texels(lightmap, device=0, on_device=False, stream=None):
     texels) of an api.Lightmap, rasterised on the device.  numpy arrays, or with on_device=True torch tensors on cuda:`device`, written on
     `stream` (default: the current torch stream)."""
     lib = load()
-    s, _keep = _lightmap_abi(lightmap)
-    n = int(s.width) * int(s.height)
+    lm, _keep = _lightmap_abi(lightmap)
+    n = int(lm.width) * int(lm.height)
     count = C.c_uint32(0)
-    if on_device:
-        import torch
-        dev = torch.device("cuda", int(device))
-        rec = torch.full((n, 8), float("nan"), dtype=torch.float32, device=dev)
-        own = torch.zeros((n,), dtype=torch.int32, device=dev)
-        _check(lib, lib.fw_lightmap_texels(C.byref(s), int(device), rec.data_ptr(), own.data_ptr(), C.byref(count), 1, _stream_arg(stream, dev)))
-        return rec, own, int(count.value)
-    rec = np.full((n, 8), np.nan, np.float32)
-    own = np.zeros((n,), np.uint32)
-    _check(lib, lib.fw_lightmap_texels(C.byref(s), int(device), rec.ctypes.data, own.ctypes.data, C.byref(count), 0, None))
+    s = _Side(None, device, on_device)
+    rec, own = s.new((n, 8), fill=float("nan")), s.new((n,), "ids", fill=0)
+    _check(lib, lib.fw_lightmap_texels(C.byref(lm), int(device), *s.ptrs(rec, own), C.byref(count), *s.tail(stream)))
     return rec, own, int(count.value)
 
 
@@ -988,18 +911,13 @@ def lightmap_rays(lightmap, round=0, first=0, n=None, device=0, out=None, stream
     a numpy array; out: a contiguous float32 device tensor of that shape on cuda:`device` to fill instead, on `stream` (default: the
     current torch stream); returned."""
     lib = load()
-    s, _keep = _lightmap_abi(lightmap)
+    lm, _keep = _lightmap_abi(lightmap)
     if n is None:
-        n = (int(out.shape[0]) // int(s.directions)) if out is not None else lightmap_covered(lightmap, device) - int(first)
-    shape = (int(n) * int(s.directions), 6)
-    if out is not None:
-        import torch
-        _check_device_tensor(out, shape, torch.float32, device, "out")
-        _check(lib, lib.fw_lightmap_rays(C.byref(s), int(device), int(round), int(first), int(n), out.data_ptr(), 1, _stream_arg(stream, out.device)))
-        return out
-    rays = np.empty(shape, np.float32)
-    _check(lib, lib.fw_lightmap_rays(C.byref(s), int(device), int(round), int(first), int(n), rays.ctypes.data, 0, None))
-    return rays
+        n = (int(out.shape[0]) // int(lm.directions)) if out is not None else lightmap_covered(lightmap, device) - int(first)
+    s = _Side(out, device)
+    out = s.out(out, (int(n) * int(lm.directions), 6), "out")
+    _check(lib, lib.fw_lightmap_rays(C.byref(lm), int(device), int(round), int(first), int(n), s.ptr(out), *s.tail(stream)))
+    return out
 
 
 def lightmap_reduce(accum, samples, directions, sums, texel_ids=None, device=0, stream=None):
@@ -1018,20 +936,10 @@ def lightmap_reduce(accum, samples, directions, sums, texel_ids=None, device=0, 
     n_texels = int(np.prod(sums.shape[:-1]))
     if texel_ids is not None and tuple(texel_ids.shape) != (n,):
         raise ValueError(f"texel_ids must have shape ({n},)")
-    if type(accum).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(accum, (total, 4), torch.float32, device, "accum")
-        _check_device_tensor(sums, tuple(sums.shape), torch.float32, device, "sums")
-        if texel_ids is not None:
-            _check_device_tensor(texel_ids, (n,), torch.int32, device, "texel_ids")
-        _check(lib, lib.fw_lightmap_reduce(int(device), n, d, int(samples), texel_ids.data_ptr() if texel_ids is not None else None,
-                                           accum.data_ptr(), sums.data_ptr(), n_texels, 1, _stream_arg(stream, accum.device)))
-        return sums
-    a = np.ascontiguousarray(np.asarray(accum, dtype=np.float32))
-    _host_f32(sums, None, "sums")
-    ids = None if texel_ids is None else np.ascontiguousarray(np.asarray(texel_ids, dtype=np.uint32))
-    _check(lib, lib.fw_lightmap_reduce(int(device), n, d, int(samples), ids.ctypes.data if ids is not None else None, a.ctypes.data,
-                                       sums.ctypes.data, n_texels, 0, None))
+    s = _Side(accum, device)
+    a, ids = s.inp(accum, (total, 4), "accum"), s.inp(texel_ids, (n,), "texel_ids", "ids")
+    s.out(sums, tuple(sums.shape), "sums")
+    _check(lib, lib.fw_lightmap_reduce(int(device), n, d, int(samples), *s.ptrs(ids, a, sums), n_texels, *s.tail(stream)))
     return sums
 
 
@@ -1042,13 +950,9 @@ def lightmap_dilate(image, passes, device=0, stream=None):
     if len(image.shape) != 3 or image.shape[2] != 4:
         raise ValueError("image must have shape (H, W, 4)")
     h, w = int(image.shape[0]), int(image.shape[1])
-    if type(image).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(image, (h, w, 4), torch.float32, device, "image")
-        _check(lib, lib.fw_lightmap_dilate(int(device), w, h, int(passes), image.data_ptr(), 1, _stream_arg(stream, image.device)))
-        return image
-    _host_f32(image, None, "image")
-    _check(lib, lib.fw_lightmap_dilate(int(device), w, h, int(passes), image.ctypes.data, 0, None))
+    s = _Side(image, device)
+    s.out(image, (h, w, 4), "image")
+    _check(lib, lib.fw_lightmap_dilate(int(device), w, h, int(passes), s.ptr(image), *s.tail(stream)))
     return image
 
 
@@ -1056,73 +960,37 @@ class _AoPoints:
     """The surface points of an AO call as the C ABI takes them, read in place.  positions and normals: (M, 3) float32 each, contiguous
     or two column ranges of one contiguous (M, S) array such as fw_render_aovs' records (aov[:, 8:11], aov[:, 4:7]) or
     fw_lightmap_texels' (rec[:, 0:3], rec[:, 4:7]); numpy arrays, or torch tensors on cuda:`device`.  ids: n distinct ids below M (uint32
-    numpy / int32 torch) or None: every point in order.  Arrays indexed by id (sums, out) have M records."""
+    numpy / int32 torch) or None: every point in order.  Arrays indexed by id (sums, out) have M records.  side: the call's _Side."""
 
     def __init__(self, positions, normals, ids, device):
-        self.torch = type(positions).__module__.startswith("torch")
+        s = self.side = _Side(positions, device)
         m = self.m = int(positions.shape[0])
         if m < 1 or tuple(positions.shape) != (m, 3) or tuple(normals.shape) != (m, 3):
             raise ValueError("positions and normals must have the same shape (M, 3), M >= 1")
-        if self.torch:
-            import torch
-            self.stride = int(positions.stride(0)) if m > 1 else max(3, int(positions.stride(0)))
-            for t, name in ((positions, "positions"), (normals, "normals")):
-                if (t.dtype != torch.float32 or t.stride(1) != 1 or t.device.type != "cuda" or (t.device.index or 0) != device
-                        or (m > 1 and int(t.stride(0)) != self.stride) or self.stride < 3):
-                    raise ValueError(f"{name} must be an (M, 3) float32 tensor on cuda:{device} with unit column stride and the same row stride >= 3 as the other")
-            self.dev = positions.device
-            if ids is not None:
-                _check_device_tensor(ids, (int(ids.shape[0]),), torch.int32, device, "ids")
-                if ids.numel() and not (0 <= int(ids.min()) and int(ids.max()) < m):
-                    raise ValueError(f"every id must be in 0..{m - 1}")
-            self.keep = (positions, normals, ids)
-            self.pos, self.nrm, self.ids = positions.data_ptr(), normals.data_ptr(), (ids.data_ptr() if ids is not None else None)
-        else:
-            p, nr = np.asarray(positions, np.float32), np.asarray(normals, np.float32)
-            if not (p.strides[1] == 4 and p.strides[0] % 4 == 0 and p.strides[0] >= 12 and nr.strides == p.strides):
-                p, nr = np.ascontiguousarray(p), np.ascontiguousarray(nr)
-            self.stride = p.strides[0] // 4
-            if ids is not None:
-                ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
-                if ids.size and int(ids.max()) >= m:
-                    raise ValueError(f"every id must be in 0..{m - 1}")
-            self.keep = (p, nr, ids)
-            self.pos, self.nrm, self.ids = p.ctypes.data, nr.ctypes.data, (ids.ctypes.data if ids is not None else None)
-        self.n = int(ids.shape[0]) if ids is not None else m
+        (p, nr), self.stride = s.columns(m, (positions, "positions"), (normals, "normals"))
+        self.n = m if ids is None else len(ids)
+        self.pos, self.nrm, self.ids = s.ptrs(p, nr, s.inp(ids, (self.n,), "ids", "ids", below=m))
 
-    def records(self, arr, name):
-        """checks an array indexed by id: (M, 4) or (H, W, 4) float32 with H W = M, where the points lie"""
+    def records(self, arr, name, floats=4):
+        """the pointer of an array indexed by id, checked: (M, floats) or (H, W, floats) float32 with H W = M, where the points lie"""
         shape = tuple(arr.shape)
-        if shape[-1] != 4 or int(np.prod(shape[:-1])) != self.m:
-            raise ValueError(f"{name} must have shape ({self.m}, 4) or (H, W, 4) with H W = {self.m}")
-        if self.torch:
-            import torch
-            _check_device_tensor(arr, shape, torch.float32, self.dev.index or 0, name)
-            return arr.data_ptr()
-        _host_f32(arr, None, name)
-        return arr.ctypes.data
+        if shape[-1] != floats or int(np.prod(shape[:-1])) != self.m:
+            raise ValueError(f"{name} must have shape ({self.m}, {floats}) or (H, W, {floats}) with H W = {self.m}")
+        return self.side.ptr(self.side.out(arr, shape, name))
 
 
 def ao_rays(ao, positions, normals, ids=None, round=0, device=0, out=None, stream=None):
     """fw_ao_rays: the rays of round `round` of an api.AmbientOcclusion around surface points (see _AoPoints), generated on the device:
     (n * D, 6) float32 origin + direction, entry q * D + j = direction j of point ids[q] (ids None: q).  numpy points: returns a numpy
-    array.  Points on cuda:`device`: generated on `stream` (default: the current torch stream) where they lie; returns a device tensor
-    (out: a contiguous float32 tensor of that shape to fill instead)."""
+    array.  Points on cuda:`device`: generated on `stream` (default: the current torch stream) where they lie; returns a device tensor.
+    out: a contiguous float32 array or tensor of that shape to fill instead."""
     lib = load()
     a = ao.to_abi()
     pts = _AoPoints(positions, normals, ids, device)
-    shape = (pts.n * int(a.directions), 6)
-    if pts.torch:
-        import torch
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=pts.dev)
-        _check_device_tensor(out, shape, torch.float32, device, "out")
-        _check(lib, lib.fw_ao_rays(C.byref(a), int(device), int(round), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, out.data_ptr(), 1,
-                                   _stream_arg(stream, pts.dev)))
-        return out
-    rays = np.empty(shape, np.float32)
-    _check(lib, lib.fw_ao_rays(C.byref(a), int(device), int(round), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, rays.ctypes.data, 0, None))
-    return rays
+    s = pts.side
+    out = s.out(out, (pts.n * int(a.directions), 6), "out")
+    _check(lib, lib.fw_ao_rays(C.byref(a), int(device), int(round), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, s.ptr(out), *s.tail(stream)))
+    return out
 
 
 def ao_reduce(ao, rays, hits, sums, ids=None, device=0, stream=None):
@@ -1141,28 +1009,11 @@ def ao_reduce(ao, rays, hits, sums, ids=None, device=0, stream=None):
     m = int(np.prod(tuple(sums.shape)[:-1]))
     if sums.shape[-1] != 4 or (ids is None and m < n) or (ids is not None and tuple(ids.shape) != (n,)):
         raise ValueError(f"sums must have shape (M, 4) or (H, W, 4) with M >= {n}, ids shape ({n},)")
-    if type(rays).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
-        _check_device_tensor(hits, (total, 12), torch.float32, device, "hits")
-        _check_device_tensor(sums, tuple(sums.shape), torch.float32, device, "sums")
-        if ids is not None:
-            _check_device_tensor(ids, (n,), torch.int32, device, "ids")
-            if not (0 <= int(ids.min()) and int(ids.max()) < m):
-                raise ValueError(f"every id must be in 0..{m - 1}")
-        _check(lib, lib.fw_ao_reduce(int(device), C.byref(a), n, ids.data_ptr() if ids is not None else None, rays.data_ptr(), hits.data_ptr(),
-                                     sums.data_ptr(), 1, _stream_arg(stream, rays.device)))
-        return sums
-    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
-    h = np.ascontiguousarray(hits)
-    if h.dtype != HIT_DTYPE:
-        raise ValueError("host hits must be an array of HIT_DTYPE")
-    _host_f32(sums, None, "sums")
-    i = None if ids is None else np.ascontiguousarray(np.asarray(ids, dtype=np.uint32))
-    if i is not None and i.size and int(i.max()) >= m:
-        raise ValueError(f"every id must be in 0..{m - 1}")
-    _check(lib, lib.fw_ao_reduce(int(device), C.byref(a), n, i.ctypes.data if i is not None else None, r.ctypes.data, h.ctypes.data,
-                                 sums.ctypes.data, 0, None))
+    s = _Side(rays, device)
+    r, h = s.inp(rays, (total, 6), "rays"), s.hits(hits, total)
+    s.out(sums, tuple(sums.shape), "sums")
+    i = s.inp(ids, (n,), "ids", "ids", below=m)
+    _check(lib, lib.fw_ao_reduce(int(device), C.byref(a), n, *s.ptrs(i, r, h, sums), *s.tail(stream)))
     return sums
 
 
@@ -1173,71 +1024,29 @@ class _DirectPoints(_AoPoints):
 
     def __init__(self, positions, normals, ids, view, spec, device):
         super().__init__(positions, normals, ids, device)
-        m = self.m
-        self.view, self.view_stride, self.spec = None, 3, None
         if spec is not None and view is None:
             raise ValueError("spec needs view")
+        self.view, self.view_stride = None, 3
         if view is not None:
-            if tuple(view.shape) != (m, 3):
-                raise ValueError(f"view must have shape ({m}, 3)")
-            if self.torch:
-                import torch
-                if view.dtype != torch.float32 or view.stride(1) != 1 or view.device != self.dev or (m > 1 and int(view.stride(0)) < 3):
-                    raise ValueError("view must be an (M, 3) float32 tensor on the points' device with unit column stride and a row stride >= 3")
-                self.view, self.view_stride = view.data_ptr(), (int(view.stride(0)) if m > 1 else 3)
-            else:
-                v = np.asarray(view, np.float32)
-                if not (v.strides[1] == 4 and v.strides[0] % 4 == 0 and v.strides[0] >= 12):
-                    v = np.ascontiguousarray(v)
-                view = v
-                self.view, self.view_stride = v.ctypes.data, v.strides[0] // 4
-        if spec is not None:
-            if tuple(spec.shape) != (m, 4):
-                raise ValueError(f"spec must have shape ({m}, 4)")
-            if self.torch:
-                import torch
-                _check_device_tensor(spec, (m, 4), torch.float32, self.dev.index or 0, "spec")
-                self.spec = spec.data_ptr()
-            else:
-                spec = np.ascontiguousarray(np.asarray(spec, np.float32))
-                self.spec = spec.ctypes.data
-        self.keep = self.keep + (view, spec)
-
-    def records8(self, arr, name):
-        """checks an array indexed by id: (M, 8) or (H, W, 8) float32 with H W = M, where the points lie"""
-        shape = tuple(arr.shape)
-        if shape[-1] != 8 or int(np.prod(shape[:-1])) != self.m:
-            raise ValueError(f"{name} must have shape ({self.m}, 8) or (H, W, 8) with H W = {self.m}")
-        if self.torch:
-            import torch
-            _check_device_tensor(arr, shape, torch.float32, self.dev.index or 0, name)
-            return arr.data_ptr()
-        _host_f32(arr, None, name)
-        return arr.ctypes.data
+            (v,), self.view_stride = self.side.columns(self.m, (view, "view"))
+            self.view = self.side.ptr(v)
+        self.spec = self.side.ptr(self.side.inp(spec, (self.m, 4), "spec"))
 
 
 def direct_rays(direct, lights, positions, normals, ids=None, view=None, spec=None, device=0, out=None, stream=None):
     """fw_direct_rays: the shadow rays of an api.DirectLight from surface points (see _DirectPoints) towards `lights` (api lights or
     fw_light records), generated on the device: (n * Ln, 6) float32, entry q * Ln + i = point ids[q] (ids None: q) towards light i, or
     six zeros.  numpy points: returns a numpy array.  Points on cuda:`device`: generated on `stream` (default: the current torch stream)
-    where they lie; returns a device tensor (out: a contiguous float32 tensor of that shape to fill instead)."""
+    where they lie; returns a device tensor.  out: a contiguous float32 array or tensor of that shape to fill instead."""
     lib = load()
     d = direct.to_abi()
     arr, ln = _light_array(lights)
     pts = _DirectPoints(positions, normals, ids, view, spec, device)
-    shape = (pts.n * ln, 6)
-    if pts.torch:
-        import torch
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=pts.dev)
-        _check_device_tensor(out, shape, torch.float32, device, "out")
-        _check(lib, lib.fw_direct_rays(C.byref(d), arr, ln, int(device), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride,
-                                       pts.spec, out.data_ptr(), 1, _stream_arg(stream, pts.dev)))
-        return out
-    rays = np.empty(shape, np.float32)
-    _check(lib, lib.fw_direct_rays(C.byref(d), arr, ln, int(device), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride, pts.spec,
-                                   rays.ctypes.data, 0, None))
-    return rays
+    s = pts.side
+    out = s.out(out, (pts.n * ln, 6), "out")
+    _check(lib, lib.fw_direct_rays(C.byref(d), arr, ln, int(device), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride,
+                                   pts.spec, s.ptr(out), *s.tail(stream)))
+    return out
 
 
 def direct_reduce(direct, lights, positions, normals, rays, hits, sums, ids=None, view=None, spec=None, device=0, stream=None):
@@ -1249,23 +1058,14 @@ def direct_reduce(direct, lights, positions, normals, rays, hits, sums, ids=None
     d = direct.to_abi()
     arr, ln = _light_array(lights)
     pts = _DirectPoints(positions, normals, ids, view, spec, device)
+    s = pts.side
     total = pts.n * ln
     if tuple(rays.shape) != (total, 6) or int(hits.shape[0]) != total:
         raise ValueError(f"rays must have shape ({total}, 6) and hits {total} records")
-    p_sums = pts.records8(sums, "sums")
-    if pts.torch:
-        import torch
-        _check_device_tensor(rays, (total, 6), torch.float32, device, "rays")
-        _check_device_tensor(hits, (total, 12), torch.float32, device, "hits")
-        _check(lib, lib.fw_direct_reduce(int(device), C.byref(d), arr, ln, pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride,
-                                         pts.spec, rays.data_ptr(), hits.data_ptr(), p_sums, 1, _stream_arg(stream, pts.dev)))
-        return sums
-    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
-    h = np.ascontiguousarray(hits)
-    if h.dtype != HIT_DTYPE:
-        raise ValueError("host hits must be an array of HIT_DTYPE")
-    _check(lib, lib.fw_direct_reduce(int(device), C.byref(d), arr, ln, pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride, pts.spec,
-                                     r.ctypes.data, h.ctypes.data, p_sums, 0, None))
+    p_sums = pts.records(sums, "sums", 8)
+    r, h = s.inp(rays, (total, 6), "rays"), s.hits(hits, total)
+    _check(lib, lib.fw_direct_reduce(int(device), C.byref(d), arr, ln, pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride,
+                                     pts.spec, *s.ptrs(r, h), p_sums, *s.tail(stream)))
     return sums
 
 
@@ -1286,42 +1086,31 @@ def sky_map(sky, width, height, device=0, out=None, stream=None):
     device: what HdrEnvironment takes.  Returns a numpy array; out: a contiguous float32 device tensor of that shape on cuda:`device`
     to fill instead, on `stream` (default: the current torch stream); returned."""
     lib = load()
-    s = _sky_abi(sky)
-    shape = (int(height), int(width), 3)
-    if out is not None:
-        import torch
-        _check_device_tensor(out, shape, torch.float32, device, "out")
-        _check(lib, lib.fw_sky_map(C.byref(s), int(device), int(width), int(height), out.data_ptr(), 1, _stream_arg(stream, out.device)))
-        return out
-    rgb = np.empty(shape, np.float32)
-    _check(lib, lib.fw_sky_map(C.byref(s), int(device), int(width), int(height), rgb.ctypes.data, 0, None))
-    return rgb
+    sk = _sky_abi(sky)
+    s = _Side(out, device)
+    out = s.out(out, (int(height), int(width), 3), "out")
+    _check(lib, lib.fw_sky_map(C.byref(sk), int(device), int(width), int(height), s.ptr(out), *s.tail(stream)))
+    return out
 
 
 def sky_radiance(sky, dirs, device=0, out=None, stream=None):
     """fw_sky_radiance: the (n, 3) float32 radiance of an api.SunSky along directions of any length.  dirs: (n, k) float32 with k >= 3
     whose rows start with the direction — a view such as rays[:, 3:] of an (n, 6) ray buffer is read in place — as a numpy array
     (returns a numpy array) or a tensor on cuda:`device` (evaluated on `stream`, default the current torch stream, where it lies;
-    returns a device tensor; out: a contiguous float32 tensor of that shape to fill instead)."""
+    returns a device tensor).  out: a contiguous float32 array or tensor of that shape to fill instead."""
     lib = load()
-    s = _sky_abi(sky)
-    if isinstance(dirs, np.ndarray) or not hasattr(dirs, "data_ptr"):
-        d = np.asarray(dirs, dtype=np.float32)
-        if d.ndim != 2 or d.shape[1] < 3 or d.strides[1] != 4 or d.strides[0] % 4 or d.strides[0] < 12:
-            d = np.ascontiguousarray(d.reshape(-1, d.shape[-1])[:, :3])
-        n, stride = int(d.shape[0]), d.strides[0] // 4
-        rgb = np.empty((n, 3), np.float32)
-        _check(lib, lib.fw_sky_radiance(C.byref(s), int(device), n, d.ctypes.data, stride, rgb.ctypes.data, 0, None))
-        return rgb
-    import torch
-    if (dirs.dim() != 2 or dirs.shape[1] < 3 or dirs.dtype != torch.float32 or dirs.stride(1) != 1 or dirs.stride(0) < 3 or dirs.device.type != "cuda"
-            or (dirs.device.index or 0) != device):
-        raise ValueError(f"dirs must be an (n, >= 3) float32 tensor with unit inner stride on cuda:{device}")
+    sk = _sky_abi(sky)
+    s = _Side(dirs, device)
+    if not s.on_device:
+        dirs = np.asarray(dirs, dtype=np.float32)
+        if dirs.ndim != 2:
+            dirs = dirs.reshape(-1, dirs.shape[-1])
+    if len(dirs.shape) != 2 or dirs.shape[1] < 3:
+        raise ValueError("dirs must have shape (n, k) with k >= 3")
     n = int(dirs.shape[0])
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=dirs.device)
-    _check_device_tensor(out, (n, 3), torch.float32, device, "out")
-    _check(lib, lib.fw_sky_radiance(C.byref(s), int(device), n, dirs.data_ptr(), int(dirs.stride(0)), out.data_ptr(), 1, _stream_arg(stream, dirs.device)))
+    (d,), stride = s.columns(n, (dirs[:, :3], "dirs"))
+    out = s.out(out, (n, 3), "out")
+    _check(lib, lib.fw_sky_radiance(C.byref(sk), int(device), n, s.ptr(d), stride, s.ptr(out), *s.tail(stream)))
     return out
 
 
@@ -1350,19 +1139,10 @@ def check_ggx_quad(quad):
     _check(lib, lib.fw_check_ggx_quad(C.byref(q)))
 
 
-def _pairs_arg(mu, rho, device):
-    """(n, mu, rho, on_device) of a list of (mu, rho) pairs: contiguous float32 (n,) numpy arrays or tensors on cuda:`device`"""
-    if type(mu).__module__.startswith("torch"):
-        import torch
-        n = int(mu.shape[0])
-        _check_device_tensor(mu, (n,), torch.float32, device, "mu")
-        _check_device_tensor(rho, (n,), torch.float32, device, "rho")
-        return n, mu, rho, True
-    m = np.ascontiguousarray(np.asarray(mu, np.float32).reshape(-1))
-    r = np.ascontiguousarray(np.asarray(rho, np.float32).reshape(-1))
-    if m.shape != r.shape:
-        raise ValueError("mu and rho must have the same shape (n,)")
-    return int(m.shape[0]), m, r, False
+def _pairs_arg(s, mu, rho):
+    """(n, mu, rho) of a list of (mu, rho) pairs: contiguous float32 (n,) arrays on the side `s` of the call"""
+    n = s.count(mu, 1)
+    return n, s.inp(mu, (n,), "mu"), s.inp(rho, (n,), "rho")
 
 
 def ggx_terms(quad, mu, rho, device=0, out=None, stream=None):
@@ -1372,18 +1152,10 @@ def ggx_terms(quad, mu, rho, device=0, out=None, stream=None):
     device tensor.  out: an array or tensor of that shape to fill instead."""
     lib = load()
     q = _quad_abi(quad)
-    n, m, r, on_device = _pairs_arg(mu, rho, device)
-    if on_device:
-        import torch
-        if out is None:
-            out = torch.empty((n, 2), dtype=torch.float32, device=m.device)
-        _check_device_tensor(out, (n, 2), torch.float32, device, "out")
-        _check(lib, lib.fw_ggx_terms(C.byref(q), int(device), n, m.data_ptr(), r.data_ptr(), out.data_ptr(), 1, _stream_arg(stream, m.device)))
-        return out
-    if out is None:
-        out = np.empty((n, 2), np.float32)
-    _host_f32(out, (n, 2), "out")
-    _check(lib, lib.fw_ggx_terms(C.byref(q), int(device), n, m.ctypes.data, r.ctypes.data, out.ctypes.data, 0, None))
+    s = _Side(mu, device)
+    n, m, r = _pairs_arg(s, mu, rho)
+    out = s.out(out, (n, 2), "out")
+    _check(lib, lib.fw_ggx_terms(C.byref(q), int(device), n, *s.ptrs(m, r, out), *s.tail(stream)))
     return out
 
 
@@ -1397,97 +1169,22 @@ def ggx_table(quad, n_mu=None, n_rho=None, device=0, out=None, stream=None):
         raise ValueError("n_mu and n_rho are needed with a quadrature that is not an api.GgxTable")
     n_mu = int(quad.n_mu if n_mu is None else n_mu)
     n_rho = int(quad.n_rho if n_rho is None else n_rho)
-    shape = (n_rho, n_mu, 2)
-    if out is not None:
-        import torch
-        _check_device_tensor(out, shape, torch.float32, device, "out")
-        _check(lib, lib.fw_ggx_table(C.byref(q), int(device), n_mu, n_rho, out.data_ptr(), 1, _stream_arg(stream, out.device)))
-        return out
-    table = np.empty(shape, np.float32)
-    _check(lib, lib.fw_ggx_table(C.byref(q), int(device), n_mu, n_rho, table.ctypes.data, 0, None))
-    return table
-
-
-def _table_arg(table, on_device, device):
-    """(pointer, n_mu, n_rho, what keeps it alive) of an (n_rho, n_mu, 2) float32 table"""
-    if on_device:
-        import torch
-        if table.dim() != 3:
-            raise ValueError("table must have the shape (n_rho, n_mu, 2)")
-        _check_device_tensor(table, (table.shape[0], table.shape[1], 2), torch.float32, device, "table")
-        return table.data_ptr(), int(table.shape[1]), int(table.shape[0]), table
-    t = np.ascontiguousarray(np.asarray(table, np.float32))
-    if t.ndim != 3 or t.shape[2] != 2:
-        raise ValueError("table must have the shape (n_rho, n_mu, 2)")
-    return t.ctypes.data, int(t.shape[1]), int(t.shape[0]), t
+    s = _Side(out, device)
+    out = s.out(out, (n_rho, n_mu, 2), "out")
+    _check(lib, lib.fw_ggx_table(C.byref(q), int(device), n_mu, n_rho, s.ptr(out), *s.tail(stream)))
+    return out
 
 
 def ggx_table_lookup(table, mu, rho, device=0, out=None, stream=None):
     """fw_ggx_table_lookup: the (n, 2) float32 bilinear lookup of an (n_rho, n_mu, 2) table at the pairs (mu[q], rho[q]), edges clamped,
     zeros for a non-finite pair.  numpy arrays or contiguous float32 tensors on cuda:`device` (the table too), as ggx_terms."""
     lib = load()
-    n, m, r, on_device = _pairs_arg(mu, rho, device)
-    tp, n_mu, n_rho, _keep = _table_arg(table, on_device, device)
-    if on_device:
-        import torch
-        if out is None:
-            out = torch.empty((n, 2), dtype=torch.float32, device=m.device)
-        _check_device_tensor(out, (n, 2), torch.float32, device, "out")
-        _check(lib, lib.fw_ggx_table_lookup(int(device), n_mu, n_rho, tp, n, m.data_ptr(), r.data_ptr(), out.data_ptr(), 1, _stream_arg(stream, m.device)))
-        return out
-    if out is None:
-        out = np.empty((n, 2), np.float32)
-    _host_f32(out, (n, 2), "out")
-    _check(lib, lib.fw_ggx_table_lookup(int(device), n_mu, n_rho, tp, n, m.ctypes.data, r.ctypes.data, out.ctypes.data, 0, None))
+    s = _Side(mu, device)
+    n, m, r = _pairs_arg(s, mu, rho)
+    tp, n_mu, n_rho = _table_arg(s, table)
+    out = s.out(out, (n, 2), "out")
+    _check(lib, lib.fw_ggx_table_lookup(int(device), n_mu, n_rho, tp, n, *s.ptrs(m, r, out), *s.tail(stream)))
     return out
-
-
-def probe_shade_split(grid, sh, radiance, maps, aov, spec, view, table, width, height, flags=0, depth=None, moments=None, normal_bias=0.0,
-                      placement=None, gamma=2.2, device=0, stream=None, outputs=("rgb8", "gamma", "linear")):
-    """fw_probe_shade_split: probe_shade_glossy with the split sum's BRDF term: a glossy pixel is v ((F0 A + B) Ls) + (1 - v) a with (A, B)
-    looked up in `table` ((n_rho, n_mu, 2) float32, as ggx_table returns it; a device tensor when the other arrays are) at the cosine of
-    the view and the pixel's roughness; flags: FW_SPLIT_ENERGY multiplies by 1 + F0 (1 / (A + B) - 1).  Everything else as
-    probe_shade_glossy."""
-    lib = load()
-    g, n_probes = _grid_abi(grid)
-    n = int(width) * int(height)
-    p = A.fw_probe_shade_params()
-    p.width, p.height, p.gamma, p.device = int(width), int(height), float(gamma), int(device)
-    want = [name in outputs for name in ("rgb8", "gamma", "linear")]
-    if type(aov).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(sh, (n_probes, 9, 3), torch.float32, device, "sh")
-        _check_device_tensor(aov, (n, 12), torch.float32, device, "aov")
-        _check_device_tensor(spec, (n, 4), torch.float32, device, "spec")
-        stride = int(view.stride(0)) if n > 1 else max(3, int(view.stride(0)))
-        if (view.dtype != torch.float32 or tuple(view.shape) != (n, 3) or view.stride(1) != 1 or view.device.type != "cuda"
-                or (view.device.index or 0) != device or stride < 3):
-            raise ValueError(f"view must be an (N, 3) float32 tensor on cuda:{device} with unit column stride and a row stride >= 3")
-        head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, True, device)
-        tp, n_mu, n_rho, _kt = _table_arg(table, True, device)
-        dev = aov.device
-        rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev) if want[0] else None
-        gam = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[1] else None
-        lin = torch.empty((n, 3), dtype=torch.float32, device=dev) if want[2] else None
-        p.on_device = 1
-        p.stream = _stream_arg(stream, dev)
-        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        _check(lib, lib.fw_probe_shade_split(C.byref(g), sh.data_ptr(), *head, C.byref(p), aov.data_ptr(), spec.data_ptr(), view.data_ptr(), stride,
-                                             tp, n_mu, n_rho, int(flags), ptr(lin), ptr(gam), ptr(rgb8)))
-        return rgb8, gam, lin
-    s = np.ascontiguousarray(np.asarray(sh, np.float32).reshape(n_probes, 9, 3))
-    a = np.ascontiguousarray(np.asarray(aov, np.float32).reshape(n, 12))
-    sp = np.ascontiguousarray(np.asarray(spec, np.float32).reshape(n, 4))
-    vw = np.ascontiguousarray(np.asarray(view, np.float32).reshape(n, 3))
-    head, _keep = _radiance_args(radiance, maps, depth, moments, normal_bias, placement, n_probes, False, device)
-    tp, n_mu, n_rho, _kt = _table_arg(table, False, device)
-    rgb8 = np.empty((n, 3), np.uint8) if want[0] else None
-    gam = np.empty((n, 3), np.float32) if want[1] else None
-    lin = np.empty((n, 3), np.float32) if want[2] else None
-    ptr = lambda t: None if t is None else t.ctypes.data      # noqa: E731
-    _check(lib, lib.fw_probe_shade_split(C.byref(g), s.ctypes.data, *head, C.byref(p), a.ctypes.data, sp.ctypes.data, vw.ctypes.data, 3, tp, n_mu,
-                                         n_rho, int(flags), ptr(lin), ptr(gam), ptr(rgb8)))
-    return rgb8, gam, lin
 
 
 class DeviceScene:
@@ -1627,6 +1324,18 @@ class DeviceScene:
         _check(lib, lib.fw_render_views(self.handle, C.byref(p), cams, v, rgb8.ctypes.data, gam.ctypes.data, lin.ctypes.data, C.byref(st)))
         return ViewsResult(rgb8, gam, lin, st.as_dict(), p.width, p.height, pixel_ids is not None)
 
+    def _rays_call(self, fn, head, p, s, stream, accum):
+        """what render_rays and render_model share: fn(scene, *head, accum, rgb8, gamma, linear, stats) with accum (N, 4) float32 updated
+        in place (None: zeros) and three new outputs on the side `s`.  Returns the RaysResult."""
+        from .api import RaysResult
+        n = int(p.n_rays)
+        st = A.fw_stats()
+        accum = s.out(accum, (n, 4), "accum", fill=0.0)
+        rgb8, gam, lin = s.new((n, 3), "u8"), s.new((n, 3)), s.new((n, 3))
+        s.params(p, stream)
+        _check(self._lib, fn(self.handle, *head, *s.ptrs(accum, rgb8, gam, lin), C.byref(st)))
+        return RaysResult(rgb8, gam, lin, accum, st.as_dict())
+
     def render_rays(self, rays, samples, first_sample=0, accum=None, keys=None, key_base=0, seed=0, use_bvh=True, gamma=2.2, stream=None,
                     paths_per_batch=0, flags=0):
         """fw_render_rays: radiance along the caller's rays, samples [first_sample, first_sample + samples) of N entries.  rays: (S, N, 6)
@@ -1637,9 +1346,6 @@ class DeviceScene:
         - contiguous torch tensors on this scene's device (rays, and keys / accum when given): rendered on `stream` (default: the current
           torch stream) into new device tensors; returns a RaysResult of tensors.  Device rays are the fast path: host rays pass
           through pinned staging batch by batch."""
-        from .api import RaysResult
-        lib = self._lib
-        on_device = type(rays).__module__.startswith("torch")
         shape = tuple(rays.shape)
         if len(shape) == 3 and shape[2] == 6 and shape[0] == int(samples):
             per_sample, n = 1, int(shape[1])
@@ -1651,41 +1357,11 @@ class DeviceScene:
         p.n_rays, p.first_sample, p.samples, p.per_sample_rays = n, int(first_sample), int(samples), per_sample
         p.key_base, p.seed, p.use_bvh, p.gamma = int(key_base), int(seed), int(bool(use_bvh)), float(gamma)
         p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
-        st = A.fw_stats()
-        if on_device:
-            import torch
-            _check_device_tensor(rays, shape, torch.float32, self.device, "rays")
-            if keys is not None:
-                _check_device_tensor(keys, (n,), torch.int32, self.device, "keys")      # (the bits of uint32 keys)
-            if accum is None:
-                accum = torch.zeros((n, 4), dtype=torch.float32, device=rays.device)
-            _check_device_tensor(accum, (n, 4), torch.float32, self.device, "accum")
-            rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=rays.device)
-            gam = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
-            lin = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
-            p.on_device = 1
-            p.stream = _stream_arg(stream, rays.device)
-            if keys is not None:
-                p.keys = C.cast(C.c_void_p(keys.data_ptr()), C.POINTER(C.c_uint32))
-            _check(lib, lib.fw_render_rays(self.handle, C.byref(p), rays.data_ptr(), accum.data_ptr(), rgb8.data_ptr(), gam.data_ptr(),
-                                           lin.data_ptr(), C.byref(st)))
-            return RaysResult(rgb8, gam, lin, accum, st.as_dict())
-        r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32))
-        k = None
+        s = _Side(rays, self.device)
+        r = s.inp(rays, shape, "rays")
         if keys is not None:
-            k = np.ascontiguousarray(np.asarray(keys, dtype=np.uint32))
-            if k.shape != (n,):
-                raise ValueError(f"keys must have shape ({n},)")
-            p.keys = k.ctypes.data_as(C.POINTER(C.c_uint32))
-        if accum is None:
-            accum = np.zeros((n, 4), np.float32)
-        _host_f32(accum, (n, 4), "accum")
-        rgb8 = np.empty((n, 3), np.uint8)
-        gam = np.empty((n, 3), np.float32)
-        lin = np.empty((n, 3), np.float32)
-        _check(lib, lib.fw_render_rays(self.handle, C.byref(p), r.ctypes.data, accum.ctypes.data, rgb8.ctypes.data, gam.ctypes.data,
-                                       lin.ctypes.data, C.byref(st)))
-        return RaysResult(rgb8, gam, lin, accum, st.as_dict())
+            p.keys = C.cast(C.c_void_p(s.ptr(s.inp(keys, (n,), "keys", "ids"))), C.POINTER(C.c_uint32))      # (on the device: the bits of uint32 keys)
+        return self._rays_call(self._lib.fw_render_rays, (C.byref(p), s.ptr(r)), p, s, stream, accum)
 
     def render_model(self, model, samples, first_sample=0, accum=None, key_base=0, seed=0, use_bvh=True, gamma=2.2, stream=None,
                      paths_per_batch=0, flags=0, chunk=None, on_device=False):
@@ -1694,38 +1370,12 @@ class DeviceScene:
         render_rays() over model_rays().  accum: (W * H, 4) float32 sums of the samples before first_sample, updated in place (None:
         zeros, only with first_sample 0).  Returns a RaysResult of host arrays, or — accum a device tensor on this scene's device, or
         on_device=True — of device tensors, rendered on `stream` (default: the current torch stream)."""
-        from .api import RaysResult
-        lib = self._lib
         m = _model_abi(model, chunk)
-        n = int(m.width) * int(m.height)
         p = A.fw_render_rays_params()
-        p.n_rays, p.first_sample, p.samples, p.per_sample_rays = n, int(first_sample), int(samples), 1
+        p.n_rays, p.first_sample, p.samples, p.per_sample_rays = int(m.width) * int(m.height), int(first_sample), int(samples), 1
         p.key_base, p.seed, p.use_bvh, p.gamma = int(key_base), int(seed), int(bool(use_bvh)), float(gamma)
         p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
-        st = A.fw_stats()
-        if on_device or (accum is not None and type(accum).__module__.startswith("torch")):
-            import torch
-            dev = torch.device("cuda", self.device)
-            if accum is None:
-                accum = torch.zeros((n, 4), dtype=torch.float32, device=dev)
-            _check_device_tensor(accum, (n, 4), torch.float32, self.device, "accum")
-            rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
-            gam = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            lin = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            p.on_device = 1
-            p.stream = _stream_arg(stream, dev)
-            _check(lib, lib.fw_render_model(self.handle, C.byref(m), C.byref(p), accum.data_ptr(), rgb8.data_ptr(), gam.data_ptr(),
-                                            lin.data_ptr(), C.byref(st)))
-            return RaysResult(rgb8, gam, lin, accum, st.as_dict())
-        if accum is None:
-            accum = np.zeros((n, 4), np.float32)
-        _host_f32(accum, (n, 4), "accum")
-        rgb8 = np.empty((n, 3), np.uint8)
-        gam = np.empty((n, 3), np.float32)
-        lin = np.empty((n, 3), np.float32)
-        _check(lib, lib.fw_render_model(self.handle, C.byref(m), C.byref(p), accum.ctypes.data, rgb8.ctypes.data, gam.ctypes.data,
-                                        lin.ctypes.data, C.byref(st)))
-        return RaysResult(rgb8, gam, lin, accum, st.as_dict())
+        return self._rays_call(self._lib.fw_render_model, (C.byref(m), C.byref(p)), p, _Side(accum, self.device, on_device), stream, accum)
 
     def model_aovs(self, model, samples, seed=0, use_bvh=True, out=None, stream=None):
         """fw_render_model_aovs: aovs() for a camera model (an api.CameraModel or a fw_camera_model) — the (W * H, 12) float32 first-hit
@@ -1758,23 +1408,11 @@ class DeviceScene:
         p.samples, p.seed, p.use_bvh, p.gamma = int(samples), int(seed), int(bool(use_bvh)), 1.0
         p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
         st = A.fw_stats()
-        if on_device or (sums is not None and type(sums).__module__.startswith("torch")):
-            import torch
-            dev = torch.device("cuda", self.device)
-            if sums is None:
-                sums = torch.zeros(shape, dtype=torch.float32, device=dev)
-            _check_device_tensor(sums, shape, torch.float32, self.device, "sums")
-            out = torch.empty(shape, dtype=torch.float32, device=dev)
-            p.on_device = 1
-            p.stream = _stream_arg(stream, dev)
-            ptrs = sums.data_ptr(), out.data_ptr()
-        else:
-            if sums is None:
-                sums = np.zeros(shape, np.float32)
-            _host_f32(sums, shape, "sums")
-            out = np.empty(shape, np.float32)
-            ptrs = sums.ctypes.data, out.ctypes.data
-        _check(self._lib, fn(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), *extra, *ptrs, C.byref(st)))
+        side = _Side(sums, self.device, on_device)
+        sums = side.out(sums, shape, "sums", fill=0.0)
+        out = side.new(shape)
+        side.params(p, stream)
+        _check(self._lib, fn(self.handle, C.byref(s), C.byref(p), int(first_round), int(rounds), *extra, *side.ptrs(sums, out), C.byref(st)))
         return out, sums, st.as_dict()
 
     def bake_probes(self, probes, rounds, samples, first_round=0, sums=None, seed=0, use_bvh=True, stream=None, paths_per_batch=0, flags=0,
@@ -1801,24 +1439,12 @@ class DeviceScene:
         p = A.fw_trace_params()
         p.use_bvh, p.flags, p.seed, p.rays_per_batch = int(bool(use_bvh)), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rays_per_batch)
         st = A.fw_stats()
-        if on_device or (sums is not None and type(sums).__module__.startswith("torch")):
-            import torch
-            dev = torch.device("cuda", self.device)
-            if sums is None:
-                sums = torch.zeros((n, R, R, 4), dtype=torch.float32, device=dev)
-            _check_device_tensor(sums, (n, R, R, 4), torch.float32, self.device, "sums")
-            out = torch.empty((n, R, R, 2), dtype=torch.float32, device=dev)
-            p.on_device = 1
-            p.stream = _stream_arg(stream, dev)
-            ptrs = sums.data_ptr(), out.data_ptr()
-        else:
-            if sums is None:
-                sums = np.zeros((n, R, R, 4), np.float32)
-            _host_f32(sums, (n, R, R, 4), "sums")
-            out = np.empty((n, R, R, 2), np.float32)
-            ptrs = sums.ctypes.data, out.ctypes.data
-        _check(self._lib, self._lib.fw_bake_probe_depth(self.handle, C.byref(s), C.byref(pd), C.byref(p), int(first_round), int(rounds), *ptrs,
-                                                        C.byref(st)))
+        side = _Side(sums, self.device, on_device)
+        sums = side.out(sums, (n, R, R, 4), "sums", fill=0.0)
+        out = side.new((n, R, R, 2))
+        side.params(p, stream)
+        _check(self._lib, self._lib.fw_bake_probe_depth(self.handle, C.byref(s), C.byref(pd), C.byref(p), int(first_round), int(rounds),
+                                                        *side.ptrs(sums, out), C.byref(st)))
         return out, sums, st.as_dict()
 
     def bake_probe_radiance(self, probes, radiance, rounds, samples, first_round=0, sums=None, sh_sums=None, with_sh=False, seed=0, use_bvh=True,
@@ -1837,35 +1463,16 @@ class DeviceScene:
         p.samples, p.seed, p.use_bvh, p.gamma = int(samples), int(seed), int(bool(use_bvh)), 1.0
         p.paths_per_batch, p.flags = int(paths_per_batch), int(flags)
         st = A.fw_stats()
+        side = _Side(sh_sums if sums is None else sums, self.device, on_device)
+        sums = side.out(sums, (n, R, R, 4), "sums", fill=0.0)
+        maps = side.new((n, M, 4))
         sh = None
-        if on_device or any(t is not None and type(t).__module__.startswith("torch") for t in (sums, sh_sums)):
-            import torch
-            dev = torch.device("cuda", self.device)
-            if sums is None:
-                sums = torch.zeros((n, R, R, 4), dtype=torch.float32, device=dev)
-            _check_device_tensor(sums, (n, R, R, 4), torch.float32, self.device, "sums")
-            maps = torch.empty((n, M, 4), dtype=torch.float32, device=dev)
-            if with_sh:
-                if sh_sums is None:
-                    sh_sums = torch.zeros((n, 9, 3), dtype=torch.float32, device=dev)
-                _check_device_tensor(sh_sums, (n, 9, 3), torch.float32, self.device, "sh_sums")
-                sh = torch.empty((n, 9, 3), dtype=torch.float32, device=dev)
-            p.on_device = 1
-            p.stream = _stream_arg(stream, dev)
-            ptrs = (sums.data_ptr(), maps.data_ptr(), sh_sums.data_ptr() if with_sh else None, sh.data_ptr() if with_sh else None)
-        else:
-            if sums is None:
-                sums = np.zeros((n, R, R, 4), np.float32)
-            _host_f32(sums, (n, R, R, 4), "sums")
-            maps = np.empty((n, M, 4), np.float32)
-            if with_sh:
-                if sh_sums is None:
-                    sh_sums = np.zeros((n, 9, 3), np.float32)
-                _host_f32(sh_sums, (n, 9, 3), "sh_sums")
-                sh = np.empty((n, 9, 3), np.float32)
-            ptrs = (sums.ctypes.data, maps.ctypes.data, sh_sums.ctypes.data if with_sh else None, sh.ctypes.data if with_sh else None)
-        _check(self._lib, self._lib.fw_bake_probe_radiance(self.handle, C.byref(s), C.byref(pr), C.byref(p), int(first_round), int(rounds), *ptrs,
-                                                           C.byref(st)))
+        if with_sh:
+            sh_sums = side.out(sh_sums, (n, 9, 3), "sh_sums", fill=0.0)
+            sh = side.new((n, 9, 3))
+        side.params(p, stream)
+        _check(self._lib, self._lib.fw_bake_probe_radiance(self.handle, C.byref(s), C.byref(pr), C.byref(p), int(first_round), int(rounds),
+                                                           *side.ptrs(sums, maps, sh_sums, sh), C.byref(st)))
         if with_sh:
             return maps, sums, sh, sh_sums, st.as_dict()
         return maps, sums, st.as_dict()
@@ -1894,6 +1501,21 @@ class DeviceScene:
                                                        survey.ctypes.data, C.byref(st)))
         return placement, survey, st.as_dict()
 
+    def _bake_points(self, fn, desc, pts, floats, head, rounds, first_round, sums, out, seed, use_bvh, stream, rays_per_batch, flags):
+        """what bake_ao and bake_direct share: the bound C function `fn` over its description `desc`, the points `pts` with the arguments
+        `head` that state them, and sums and out of `floats` floats per point (None: zeros).  Returns (out, sums, stats)."""
+        p = A.fw_trace_params()
+        p.use_bvh, p.flags, p.seed, p.rays_per_batch = int(bool(use_bvh)), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rays_per_batch)
+        st = A.fw_stats()
+        if sums is None and int(first_round) > 0:
+            raise ValueError("first_round > 0 needs the sums of the rounds before it")
+        pts.side.params(p, stream)
+        sums = pts.side.new((pts.m, floats), fill=0.0) if sums is None else sums
+        out = pts.side.new((pts.m, floats), fill=0.0) if out is None else out
+        _check(self._lib, fn(self.handle, C.byref(desc), C.byref(p), *head, int(first_round), int(rounds), pts.records(sums, "sums", floats),
+                             pts.records(out, "out", floats), C.byref(st)))
+        return out, sums, st.as_dict()
+
     def bake_ao(self, ao, positions, normals, ids=None, rounds=1, first_round=0, sums=None, out=None, seed=0, use_bvh=True, stream=None,
                 rays_per_batch=0, flags=0, chunk=None):
         """fw_bake_ao: the rounds [first_round, first_round + rounds) of an api.AmbientOcclusion around surface points (see _AoPoints:
@@ -1906,23 +1528,8 @@ class DeviceScene:
         if chunk is not None:
             a.chunk_points = int(chunk)
         pts = _AoPoints(positions, normals, ids, self.device)
-        p = A.fw_trace_params()
-        p.use_bvh, p.flags, p.seed, p.rays_per_batch = int(bool(use_bvh)), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rays_per_batch)
-        st = A.fw_stats()
-        if sums is None and int(first_round) > 0:
-            raise ValueError("first_round > 0 needs the sums of the rounds before it")
-        if pts.torch:
-            import torch
-            zeros = lambda: torch.zeros((pts.m, 4), dtype=torch.float32, device=pts.dev)      # noqa: E731
-            p.on_device = 1
-            p.stream = _stream_arg(stream, pts.dev)
-        else:
-            zeros = lambda: np.zeros((pts.m, 4), np.float32)      # noqa: E731
-        sums = zeros() if sums is None else sums
-        out = zeros() if out is None else out
-        _check(self._lib, self._lib.fw_bake_ao(self.handle, C.byref(a), C.byref(p), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, int(first_round),
-                                               int(rounds), pts.records(sums, "sums"), pts.records(out, "out"), C.byref(st)))
-        return out, sums, st.as_dict()
+        return self._bake_points(self._lib.fw_bake_ao, a, pts, 4, (pts.n, pts.pos, pts.nrm, pts.stride, pts.ids), rounds, first_round, sums, out,
+                                 seed, use_bvh, stream, rays_per_batch, flags)
 
     def bake_direct(self, direct, positions, normals, ids=None, view=None, spec=None, rounds=1, first_round=0, sums=None, out=None, seed=0,
                     use_bvh=True, stream=None, rays_per_batch=0, flags=0, chunk=None):
@@ -1936,24 +1543,9 @@ class DeviceScene:
         if chunk is not None:
             d.chunk_points = int(chunk)
         pts = _DirectPoints(positions, normals, ids, view, spec, self.device)
-        p = A.fw_trace_params()
-        p.use_bvh, p.flags, p.seed, p.rays_per_batch = int(bool(use_bvh)), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rays_per_batch)
-        st = A.fw_stats()
-        if sums is None and int(first_round) > 0:
-            raise ValueError("first_round > 0 needs the sums of the rounds before it")
-        if pts.torch:
-            import torch
-            zeros = lambda: torch.zeros((pts.m, 8), dtype=torch.float32, device=pts.dev)      # noqa: E731
-            p.on_device = 1
-            p.stream = _stream_arg(stream, pts.dev)
-        else:
-            zeros = lambda: np.zeros((pts.m, 8), np.float32)      # noqa: E731
-        sums = zeros() if sums is None else sums
-        out = zeros() if out is None else out
-        _check(self._lib, self._lib.fw_bake_direct(self.handle, C.byref(d), C.byref(p), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view,
-                                                   pts.view_stride, pts.spec, int(first_round), int(rounds), pts.records8(sums, "sums"),
-                                                   pts.records8(out, "out"), C.byref(st)))
-        return out, sums, st.as_dict()
+        head = (pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride, pts.spec)
+        return self._bake_points(self._lib.fw_bake_direct, d, pts, 8, head, rounds, first_round, sums, out, seed, use_bvh, stream, rays_per_batch,
+                                 flags)
 
     def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,
                       flags=0, chunk=None, on_device=False):
@@ -1974,7 +1566,6 @@ class DeviceScene:
           float32 tensor on the device (columns: HIT_COLUMNS; hit_fields() gives the int32 views of material / object / prim).
         A ray with a non-finite component or a zero direction comes back as a miss (object == FW_NO_HIT).  Ray i's medium draws are
         keyed (seed, key_base + i).  stats: a dict to fill with fw_stats."""
-        lib = self._lib
         p = A.fw_trace_params()
         p.use_bvh = int(bool(use_bvh))
         p.flags = A.FW_FLAG_TIME_KERNELS if time_kernels else 0
@@ -1982,22 +1573,12 @@ class DeviceScene:
         p.key_base = int(key_base)
         p.rays_per_batch = int(rays_per_batch)
         st = A.fw_stats()
-        if type(rays).__module__.startswith("torch"):
-            import torch
-            if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.dim() != 2 or rays.shape[1] != 6:
-                raise ValueError("device rays must be a contiguous (n, 6) float32 tensor")
-            if rays.device.type != "cuda" or (rays.device.index or 0) != self.device:
-                raise ValueError(f"device rays must live on the scene's device (cuda:{self.device})")
-            n = int(rays.shape[0])
-            out = torch.empty((n, 12), dtype=torch.float32, device=rays.device)
-            p.on_device = 1
-            p.stream = _stream_arg(None, rays.device)
-            _check(lib, lib.fw_trace_rays(self.handle, C.byref(p), rays.data_ptr() if n else None, n, out.data_ptr() if n else None, C.byref(st)))
-        else:
-            r = np.ascontiguousarray(np.asarray(rays, dtype=np.float32).reshape(-1, 6))
-            n = int(r.shape[0])
-            out = np.zeros(n, HIT_DTYPE)
-            _check(lib, lib.fw_trace_rays(self.handle, C.byref(p), r.ctypes.data, n, out.ctypes.data, C.byref(st)))
+        s = _Side(rays, self.device)
+        n = s.count(rays, 6)
+        r = s.inp(rays, (n, 6), "rays")
+        out = s.new_hits(n)
+        s.params(p)
+        _check(self._lib, self._lib.fw_trace_rays(self.handle, C.byref(p), s.ptr(r), n, s.ptr(out), C.byref(st)))
         if stats is not None:
             stats.update(st.as_dict())
         return out
@@ -2077,12 +1658,6 @@ def render_scene_tiled(scene_desc, renderer, devices):
 AOV_COLUMNS = dict(albedo=slice(0, 3), coverage=3, normal=slice(4, 7), distance=7, position=slice(8, 11))
 
 
-def _check_device_tensor(t, shape, dtype, device, name):
-    if (tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device.type != "cuda"
-            or (t.device.index or 0) != device):
-        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on cuda:{device}")
-
-
 def denoise(color, aov, moments=None, width=None, height=None, iterations=A.FW_DENOISE_ITERATIONS, gamma=2.2, device=0, stream=None):
     """fw_denoise: the edge-avoiding a-trous filter (include/firework_hip.h) of a linear frame `color` (N, 3) guided by fw_render_aovs'
     records `aov` (N, 12), with fw_render_adaptive's `moments` (N, 4) for the luminance term, or None.  All host arrays (numpy): returns
@@ -2094,29 +1669,11 @@ def denoise(color, aov, moments=None, width=None, height=None, iterations=A.FW_D
     n = int(width) * int(height)
     p = A.fw_denoise_params()
     p.width, p.height, p.iterations, p.gamma, p.device = int(width), int(height), int(iterations), float(gamma), int(device)
-    if type(color).__module__.startswith("torch"):
-        import torch
-        _check_device_tensor(color, (n, 3), torch.float32, device, "color")
-        _check_device_tensor(aov, (n, 12), torch.float32, device, "aov")
-        if moments is not None:
-            _check_device_tensor(moments, (n, 4), torch.float32, device, "moments")
-        dev = color.device
-        rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
-        gam = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        lin = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        p.on_device = 1
-        p.stream = _stream_arg(stream, dev)
-        _check(lib, lib.fw_denoise(C.byref(p), color.data_ptr(), aov.data_ptr(), None if moments is None else moments.data_ptr(),
-                                   lin.data_ptr(), gam.data_ptr(), rgb8.data_ptr()))
-        return rgb8, gam, lin
-    c = np.ascontiguousarray(np.asarray(color, np.float32).reshape(n, 3))
-    a = np.ascontiguousarray(np.asarray(aov, np.float32).reshape(n, 12))
-    m = None if moments is None else np.ascontiguousarray(np.asarray(moments, np.float32).reshape(n, 4))
-    rgb8 = np.empty((n, 3), np.uint8)
-    gam = np.empty((n, 3), np.float32)
-    lin = np.empty((n, 3), np.float32)
-    _check(lib, lib.fw_denoise(C.byref(p), c.ctypes.data, a.ctypes.data, None if m is None else m.ctypes.data, lin.ctypes.data,
-                               gam.ctypes.data, rgb8.ctypes.data))
+    s = _Side(color, device)
+    c, a, m = s.inp(color, (n, 3), "color"), s.inp(aov, (n, 12), "aov"), s.inp(moments, (n, 4), "moments")
+    rgb8, gam, lin = s.new((n, 3), "u8"), s.new((n, 3)), s.new((n, 3))
+    s.params(p, stream)
+    _check(lib, lib.fw_denoise(C.byref(p), *s.ptrs(c, a, m, lin, gam, rgb8)))
     return rgb8, gam, lin
 
 
@@ -2143,25 +1700,9 @@ def temporal(color, aov, moments=None, history=None, prev_position=None, width=N
         raise ValueError("history must be (hist_color, hist_moments, hist_aov) or None")
     names = ("color", "moments", "aov", "hist_color", "hist_moments", "hist_aov", "prev_position")
     cols = (3, 4, 12, 3, 4, 12, 3)
-    arrays = (color, moments, aov) + hist + (prev_position,)
-    if type(color).__module__.startswith("torch"):
-        import torch
-        for name, c, t in zip(names, cols, arrays):
-            if t is not None:
-                _check_device_tensor(t, (n, c), torch.float32, device, name)
-        dev = color.device
-        out_c = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        out_m = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        out_h = torch.empty((n,), dtype=torch.float32, device=dev)
-        p.on_device = 1
-        p.stream = _stream_arg(stream, dev)
-        _check(lib, lib.fw_temporal(C.byref(p), *[None if t is None else t.data_ptr() for t in arrays], out_c.data_ptr(), out_m.data_ptr(),
-                                    out_h.data_ptr()))
-        return out_c, out_m, out_h
-    host = [None if t is None else np.ascontiguousarray(np.asarray(t, np.float32).reshape(n, c)) for c, t in zip(cols, arrays)]
-    out_c = np.empty((n, 3), np.float32)
-    out_m = np.empty((n, 4), np.float32)
-    out_h = np.empty((n,), np.float32)
-    _check(lib, lib.fw_temporal(C.byref(p), *[None if t is None else t.ctypes.data for t in host], out_c.ctypes.data, out_m.ctypes.data,
-                                out_h.ctypes.data))
+    s = _Side(color, device)
+    ins = [s.inp(t, (n, c), name) for name, c, t in zip(names, cols, (color, moments, aov) + hist + (prev_position,))]
+    out_c, out_m, out_h = s.new((n, 3)), s.new((n, 4)), s.new((n,))
+    s.params(p, stream)
+    _check(lib, lib.fw_temporal(C.byref(p), *s.ptrs(*ins, out_c, out_m, out_h)))
     return out_c, out_m, out_h

@@ -12,7 +12,7 @@
 //                        16, 8, 4, 2, 1 within a wave, the four waves' partials through LDS added in wave order by lane 0.  8 B stored
 //                        per pair.  Every barrier is reached by all 256 lanes: whether a pair is in range is workgroup-uniform.
 //   k_ggx_table_lookup   one lane per pair: four 8-byte loads at indices clamped to the table, a bilinear blend in float64.
-//   k_probe_split_shade  one lane per pixel: k_probe_shade_glossy's structure with the table lookup in the place of Schlick's term.
+//   k_probe_split_shade  one lane per pixel: k_probe_shade_glossy's pixel (shade_glossy_pixel) with the table lookup as its specular term.
 //
 // No atomics, no inline assembly.  Every table index is formed from i0 in [0, n_mu - 2] and j0 in [0, n_rho - 2] plus 0 or 1, whatever
 // mu and rho hold, so no load leaves the table; the maps are read through fw_probe_radiance_fetch.h, whose indices are clamped likewise.
@@ -132,6 +132,23 @@ __global__ __launch_bounds__(GL_BLOCK) void k_ggx_table_lookup(uint32_t n_mu, ui
     }
 }
 
+// the split sum's term F0 A + B with (A, B) from the table at (cos, rho), times 1 + F0 (1 / (A + B) - 1) under FW_SPLIT_ENERGY; where
+// nothing is seen the table is read at cos = 0
+struct TableTerm {
+    const float2 *__restrict__ table; uint32_t n_mu, n_rho, flags;
+    static constexpr double UNSEEN = 0.0;
+    __device__ __forceinline__ void operator()(double cost, const float4 &sp, float &s0, float &s1, float &s2) const {
+        float A, B;
+        ggx_table_fetch(table, n_mu, n_rho, (float)cost, sp.w, A, B);
+        s0 = sp.x * A + B; s1 = sp.y * A + B; s2 = sp.z * A + B;
+        if (flags & 1u) {                                                              // FW_SPLIT_ENERGY
+            const float e1 = A + B;
+            const float g = e1 > 0.f ? 1.f / e1 - 1.f : 0.f;
+            s0 = s0 * (1.f + sp.x * g); s1 = s1 * (1.f + sp.y * g); s2 = s2 * (1.f + sp.z * g);
+        }
+    }
+};
+
 template <bool DEPTH>
 __global__ __launch_bounds__(GL_BLOCK) void k_probe_split_shade(DProbeGrid G, DProbeVis V, DProbeRadiance pr, ShLookupConst K, const float *__restrict__ sh,
                                                                 const float4 *__restrict__ maps, const float *__restrict__ placement, uint32_t n,
@@ -140,47 +157,8 @@ __global__ __launch_bounds__(GL_BLOCK) void k_probe_split_shade(DProbeGrid G, DP
                                                                 const float2 *__restrict__ table, uint32_t n_mu, uint32_t n_rho, uint32_t flags,
                                                                 float gamma, uint8_t *rgb8, float *gamma_rgb, float *linear_rgb) {
     const uint32_t p = blockIdx.x * GL_BLOCK + threadIdx.x;                            // one pixel per lane: the grid covers n
-    if (p < n) {
-        const float4 a = aov[3 * (size_t)p], nd = aov[3 * (size_t)p + 1], xa = aov[3 * (size_t)p + 2];
-        const float4 sp = spec[p];
-        Corners C;
-        const bool ok = corner_weights<true, DEPTH>(G, V, placement, xa.x, xa.y, xa.z, nd.x, nd.y, nd.z, C);
-        const float v = a.w, rest = 1.f - v;
-        if (!(sp.w > 0.f)) {                                                           // diffuse: fw_probe_shade_placed's arithmetic
-            shade_diffuse(G, C, ok, K, sh, a, gamma, p, rgb8, gamma_rgb, linear_rgb);
-            return;
-        }
-        // glossy: u, c, r and Ls as k_probe_shade_glossy forms them; the table at (mu, rho) in the place of Schlick's term
-        const float *vw = view + (size_t)p * view_stride;
-        const float vxf = vw[0], vyf = vw[1], vzf = vw[2];
-        float l0 = 0.f, l1 = 0.f, l2 = 0.f, muf = 0.f;
-        if (finite_f(vxf) && finite_f(vyf) && finite_f(vzf)) {
-            const double vx = (double)vxf, vy = (double)vyf, vz = (double)vzf;
-            const double vl2 = (vx * vx + vy * vy) + vz * vz;
-            if (vl2 > 0.0 && C.usable) {
-                const double vl = sqrt(vl2);
-                const double ux = vx / vl, uy = vy / vl, uz = vz / vl;
-                const double c = (C.x * ux + C.y * uy) + C.z * uz;
-                const double c2 = 2.0 * c;
-                const float rx = (float)(ux - c2 * C.x), ry = (float)(uy - c2 * C.y), rz = (float)(uz - c2 * C.z);
-                muf = (float)fmin(1.0, fmax(0.0, -c));
-                double E[3];
-                if (ok && finite_f(sp.w) && corners_radiance(G, C, pr, maps, (double)rx, (double)ry, (double)rz, (double)sp.w, E)) {
-                    l0 = (float)E[0]; l1 = (float)E[1]; l2 = (float)E[2];
-                }
-            }
-        }
-        l0 = fmaxf(l0, 0.f); l1 = fmaxf(l1, 0.f); l2 = fmaxf(l2, 0.f);
-        float A, B;
-        ggx_table_fetch(table, n_mu, n_rho, muf, sp.w, A, B);
-        float s0 = sp.x * A + B, s1 = sp.y * A + B, s2 = sp.z * A + B;
-        if (flags & 1u) {                                                              // FW_SPLIT_ENERGY
-            const float e1 = A + B;
-            const float g = e1 > 0.f ? 1.f / e1 - 1.f : 0.f;
-            s0 = s0 * (1.f + sp.x * g); s1 = s1 * (1.f + sp.y * g); s2 = s2 * (1.f + sp.z * g);
-        }
-        resolve_pixel(v * (s0 * l0) + rest * a.x, v * (s1 * l1) + rest * a.y, v * (s2 * l2) + rest * a.z, 1.0f, gamma, p, rgb8, gamma_rgb, linear_rgb);
-    }
+    if (p < n) shade_glossy_pixel<DEPTH>(G, V, pr, K, sh, maps, placement, p, aov, spec, view, view_stride, gamma, rgb8, gamma_rgb, linear_rgb,
+                                         TableTerm{table, n_mu, n_rho, flags});
 }
 
 uint32_t gl_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + GL_BLOCK - 1) / GL_BLOCK); }          // n > 0; at most 2^24 blocks

@@ -220,6 +220,16 @@ __global__ __launch_bounds__(PL_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
     }
 }
 
+// Schlick's Fresnel term F0 + (1 - F0) m^5, m = 1 - cos, with m^5 formed in float64 and rounded once; where nothing is seen m = 0
+struct SchlickTerm {
+    static constexpr double UNSEEN = 1.0;
+    __device__ __forceinline__ void operator()(double cost, const float4 &sp, float &s0, float &s1, float &s2) const {
+        const double m = 1.0 - cost;
+        const float Sf = (float)(((m * m) * (m * m)) * m);
+        s0 = sp.x + (1.f - sp.x) * Sf; s1 = sp.y + (1.f - sp.y) * Sf; s2 = sp.z + (1.f - sp.z) * Sf;
+    }
+};
+
 template <bool DEPTH>
 __global__ __launch_bounds__(PL_BLOCK) void k_probe_shade_glossy(DProbeGrid G, DProbeVis V, DProbeRadiance pr, ShLookupConst K, const float *__restrict__ sh,
                                                                  const float4 *__restrict__ maps, const float *__restrict__ placement, uint32_t n,
@@ -227,42 +237,7 @@ __global__ __launch_bounds__(PL_BLOCK) void k_probe_shade_glossy(DProbeGrid G, D
                                                                  const float *__restrict__ view, uint32_t view_stride, float gamma, uint8_t *rgb8,
                                                                  float *gamma_rgb, float *linear_rgb) {
     const uint32_t p = blockIdx.x * PL_BLOCK + threadIdx.x;                           // one pixel per lane: the grid covers n
-    if (p < n) {
-        const float4 a = aov[3 * (size_t)p], nd = aov[3 * (size_t)p + 1], xa = aov[3 * (size_t)p + 2];
-        const float4 sp = spec[p];
-        Corners C;
-        const bool ok = corner_weights<true, DEPTH>(G, V, placement, xa.x, xa.y, xa.z, nd.x, nd.y, nd.z, C);
-        const float v = a.w, rest = 1.f - v;
-        if (!(sp.w > 0.f)) {                                                           // diffuse: fw_probe_shade_placed's arithmetic
-            shade_diffuse(G, C, ok, K, sh, a, gamma, p, rgb8, gamma_rgb, linear_rgb);
-            return;
-        }
-        // glossy: the lookup along the mirrored view direction under Schlick's Fresnel term
-        const float *vw = view + (size_t)p * view_stride;
-        const float vxf = vw[0], vyf = vw[1], vzf = vw[2];
-        float l0 = 0.f, l1 = 0.f, l2 = 0.f, Sf = 0.f;
-        if (finite_f(vxf) && finite_f(vyf) && finite_f(vzf)) {
-            const double vx = (double)vxf, vy = (double)vyf, vz = (double)vzf;
-            const double vl2 = (vx * vx + vy * vy) + vz * vz;
-            if (vl2 > 0.0 && C.usable) {
-                const double vl = sqrt(vl2);
-                const double ux = vx / vl, uy = vy / vl, uz = vz / vl;
-                const double c = (C.x * ux + C.y * uy) + C.z * uz;
-                const double c2 = 2.0 * c;
-                const float rx = (float)(ux - c2 * C.x), ry = (float)(uy - c2 * C.y), rz = (float)(uz - c2 * C.z);
-                const double cost = fmin(1.0, fmax(0.0, -c));
-                const double m = 1.0 - cost;
-                Sf = (float)(((m * m) * (m * m)) * m);
-                double E[3];
-                if (ok && finite_f(sp.w) && corners_radiance(G, C, pr, maps, (double)rx, (double)ry, (double)rz, (double)sp.w, E)) {
-                    l0 = (float)E[0]; l1 = (float)E[1]; l2 = (float)E[2];
-                }
-            }
-        }
-        l0 = fmaxf(l0, 0.f); l1 = fmaxf(l1, 0.f); l2 = fmaxf(l2, 0.f);
-        const float f0 = sp.x + (1.f - sp.x) * Sf, f1 = sp.y + (1.f - sp.y) * Sf, f2 = sp.z + (1.f - sp.z) * Sf;
-        resolve_pixel(v * (f0 * l0) + rest * a.x, v * (f1 * l1) + rest * a.y, v * (f2 * l2) + rest * a.z, 1.0f, gamma, p, rgb8, gamma_rgb, linear_rgb);
-    }
+    if (p < n) shade_glossy_pixel<DEPTH>(G, V, pr, K, sh, maps, placement, p, aov, spec, view, view_stride, gamma, rgb8, gamma_rgb, linear_rgb, SchlickTerm{});
 }
 
 uint32_t rad_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + PL_BLOCK - 1) / PL_BLOCK); }        // n > 0; at most 2^24 blocks

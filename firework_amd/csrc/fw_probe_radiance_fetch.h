@@ -1,6 +1,7 @@
 // fw_probe_radiance_fetch.h — the device side of the radiance lookup (include/firework_hip.h, "Lookup" under the probe radiance maps;
 // DESIGN.md §9v), one copy for the files that read radiance maps: fw_probe_radiance.hip (k_probe_radiance_lookup, k_probe_shade_glossy)
-// and fw_ggx_table.hip (k_probe_split_shade).  Internal linkage, as everything in fw_shared.h and fw_probe_corners.h.
+// and fw_ggx_table.hip (k_probe_split_shade), and the pixel of those two shades, shade_glossy_pixel, stated once over its specular term.
+// Internal linkage, as everything in fw_shared.h and fw_probe_corners.h.
 //
 // Numerics: -ffp-contract=off, so + - * / round as written and in the order of api.probe_radiance_lookup: do not reassociate.
 #pragma once
@@ -65,6 +66,52 @@ __device__ __forceinline__ bool corners_radiance(const DProbeGrid &G, const Corn
     }
     E[0] = e0; E[1] = e1; E[2] = e2;
     return true;
+}
+
+// One pixel p of the glossy probe shades (k_probe_shade_glossy, k_probe_split_shade): fw_probe_shade_placed's arithmetic where the
+// pixel's roughness is not > 0; elsewhere v (s Ls) + (1 - v) albedo, with Ls the radiance of the maps along the mirrored view direction,
+// clamped at zero, and s the specular term that the caller supplies: term(cos, sp, s0, s1, s2) gets the cosine between the normal and
+// the direction to the eye, clamped to [0, 1], as a double, and the pixel's spec record (F0.rgb, rho).  Where the view or the normal is
+// unusable Ls is zero and the term is asked at Term::UNSEEN.
+template <bool DEPTH, class Term>
+__device__ __forceinline__ void shade_glossy_pixel(const DProbeGrid &G, const DProbeVis &V, const DProbeRadiance &pr, const ShLookupConst &K,
+                                                   const float *__restrict__ sh, const float4 *__restrict__ maps, const float *__restrict__ placement,
+                                                   uint32_t p, const float4 *__restrict__ aov, const float4 *__restrict__ spec,
+                                                   const float *__restrict__ view, uint32_t view_stride, float gamma, uint8_t *rgb8, float *gamma_rgb,
+                                                   float *linear_rgb, const Term &term) {
+    const float4 a = aov[3 * (size_t)p], nd = aov[3 * (size_t)p + 1], xa = aov[3 * (size_t)p + 2];
+    const float4 sp = spec[p];
+    Corners C;
+    const bool ok = corner_weights<true, DEPTH>(G, V, placement, xa.x, xa.y, xa.z, nd.x, nd.y, nd.z, C);
+    const float v = a.w, rest = 1.f - v;
+    if (!(sp.w > 0.f)) {                                                               // diffuse: fw_probe_shade_placed's arithmetic
+        shade_diffuse(G, C, ok, K, sh, a, gamma, p, rgb8, gamma_rgb, linear_rgb);
+        return;
+    }
+    const float *vw = view + (size_t)p * view_stride;
+    const float vxf = vw[0], vyf = vw[1], vzf = vw[2];
+    float l0 = 0.f, l1 = 0.f, l2 = 0.f;
+    double cost = Term::UNSEEN;
+    if (finite_f(vxf) && finite_f(vyf) && finite_f(vzf)) {
+        const double vx = (double)vxf, vy = (double)vyf, vz = (double)vzf;
+        const double vl2 = (vx * vx + vy * vy) + vz * vz;
+        if (vl2 > 0.0 && C.usable) {
+            const double vl = sqrt(vl2);
+            const double ux = vx / vl, uy = vy / vl, uz = vz / vl;
+            const double c = (C.x * ux + C.y * uy) + C.z * uz;
+            const double c2 = 2.0 * c;
+            const float rx = (float)(ux - c2 * C.x), ry = (float)(uy - c2 * C.y), rz = (float)(uz - c2 * C.z);
+            cost = fmin(1.0, fmax(0.0, -c));
+            double E[3];
+            if (ok && finite_f(sp.w) && corners_radiance(G, C, pr, maps, (double)rx, (double)ry, (double)rz, (double)sp.w, E)) {
+                l0 = (float)E[0]; l1 = (float)E[1]; l2 = (float)E[2];
+            }
+        }
+    }
+    l0 = fmaxf(l0, 0.f); l1 = fmaxf(l1, 0.f); l2 = fmaxf(l2, 0.f);
+    float s0, s1, s2;
+    term(cost, sp, s0, s1, s2);
+    resolve_pixel(v * (s0 * l0) + rest * a.x, v * (s1 * l1) + rest * a.y, v * (s2 * l2) + rest * a.z, 1.0f, gamma, p, rgb8, gamma_rgb, linear_rgb);
 }
 
 } // namespace

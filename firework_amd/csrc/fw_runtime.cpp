@@ -5247,39 +5247,6 @@ int probe_radiance_lookup_impl(const fw_probe_grid *grid, const ProbeLookupArgs 
     });
 }
 
-// fw_probe_shade_glossy: probe_shade_impl's shape; a host call's slab holds 48 B of record, 16 B of spec, 12 B of view and up to 27 B of
-// outputs per pixel
-int probe_shade_glossy_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, const fw_probe_shade_params *p, const float *aov, const float *spec,
-                            const float *view, uint32_t view_stride, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
-    ProbeLookup L;
-    if (int rc = probe_lookup_check(grid, a, !a.sh || !a.pr || !a.maps || !p || !aov || !spec || !view, !linear_rgb && !gamma_rgb && !rgb8, L)) return rc;
-    if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
-    if (!std::isfinite(p->gamma) || !(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
-    if (view_stride < 3) return fail(FW_ERR_BAD_ARG, "view_stride_floats must be >= 3");
-    if (p->device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
-    if (p->on_device && ((((uintptr_t)aov | (uintptr_t)spec | (uintptr_t)a.maps) & 15u) ||
-                         (((uintptr_t)a.sh | (uintptr_t)view | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb | (uintptr_t)a.moments | (uintptr_t)a.placement) & 3u)))
-        return fail(FW_ERR_BAD_ARG, "device aov, spec and maps must be 16-byte aligned, the other device arrays 4-byte aligned");
-    const uint64_t full = (uint64_t)p->width * p->height;
-    if (int rc = probe_lookup_sizes(a, L)) return rc;
-    if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
-    const int dev = p->device;
-    if (int rc = use_device(dev)) return rc;
-    hipStream_t stream = (hipStream_t)p->stream;
-    Staged st(dev, stream, p->on_device != 0);
-    const ProbeTables t = probe_tables_stage(st, a, L);
-    HostSlabs sl(st, (uint32_t)full, 103);
-    const int a_aov = sl.in(aov, 48), a_spec = sl.in(spec, 16), a_view = sl.in(view, 12, view_stride);
-    const int a_lin = sl.out(linear_rgb, 12), a_gam = sl.out(gamma_rgb, 12), a_8 = sl.out(rgb8, 3);
-    if (int rc = st.up()) return rc;
-    return sl.run([&](uint32_t, uint32_t k) {
-        const fw::DProbeVis v = probe_vis_device(a, st.ptr<const float>(t.mom));
-        fw::launch_probe_shade_glossy(stream, L.g, a.vis ? &v : nullptr, L.d, st.ptr<const float>(t.sh), st.ptr<const float>(t.maps), st.ptr<const float>(t.pl), k,
-                                      sl.ptr<const float>(a_aov), sl.ptr<const float>(a_spec), sl.ptr<const float>(a_view), sl.stride(a_view), p->gamma,
-                                      sl.ptr<uint8_t>(a_8), sl.ptr<float>(a_gam), sl.ptr<float>(a_lin));
-    });
-}
-
 // ---- SunSky: fw_check_sky, fw_sky_map, fw_sky_radiance, fw_sky_sun --------------------------------------------------------
 int sky_check(const fw_sky *s) {
     if (!s) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -5470,15 +5437,21 @@ int ggx_table_lookup_impl(int device, uint32_t n_mu, uint32_t n_rho, const float
     });
 }
 
-// fw_probe_shade_split: probe_shade_glossy_impl with the table as one more staged input
-int probe_shade_split_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, const fw_probe_shade_params *p, const float *aov, const float *spec,
-                           const float *view, uint32_t view_stride, const float *table, uint32_t n_mu, uint32_t n_rho, uint32_t flags,
-                           float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
+// fw_probe_shade_glossy (split false: Schlick's term; table, n_mu, n_rho and flags are not looked at) and fw_probe_shade_split (split true:
+// the table is one more staged input): probe_shade_impl's shape; a host call's slab holds 48 B of record, 16 B of spec, 12 B of view and
+// up to 27 B of outputs per pixel
+int probe_shade_glossy_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, const fw_probe_shade_params *p, const float *aov, const float *spec,
+                            const float *view, uint32_t view_stride, bool split, const float *table, uint32_t n_mu, uint32_t n_rho, uint32_t flags,
+                            float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
     ProbeLookup L;
-    if (!grid || !a.sh || !a.pr || !a.maps || !p || !aov || !spec || !view || !table || (a.vis && (!a.pd || !a.moments)) || (a.placed && !a.placement))
+    if (!split) table = nullptr;
+    if (!grid || !a.sh || !a.pr || !a.maps || !p || !aov || !spec || !view || (split && !table) || (a.vis && (!a.pd || !a.moments)) ||
+        (a.placed && !a.placement))
         return fail(FW_ERR_BAD_ARG, "null argument");
-    if (int rc = ggx_table_sizes(n_mu, n_rho)) return rc;
-    if (flags & ~FW_SPLIT_ENERGY) return fail(FW_ERR_BAD_ARG, "flags has an unknown bit");
+    if (split) {
+        if (int rc = ggx_table_sizes(n_mu, n_rho)) return rc;
+        if (flags & ~FW_SPLIT_ENERGY) return fail(FW_ERR_BAD_ARG, "flags has an unknown bit");
+    }
     if (int rc = probe_lookup_check(grid, a, false, !linear_rgb && !gamma_rgb && !rgb8, L)) return rc;
     if (p->width == 0 || p->height == 0) return fail(FW_ERR_BAD_ARG, "width and height must be > 0");
     if (!std::isfinite(p->gamma) || !(p->gamma > 0.f)) return fail(FW_ERR_BAD_ARG, "gamma must be finite and > 0");
@@ -5486,7 +5459,8 @@ int probe_shade_split_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, 
     if (p->device < 0) return fail(FW_ERR_BAD_ARG, "device index out of range");
     if (p->on_device && ((((uintptr_t)aov | (uintptr_t)spec | (uintptr_t)a.maps) & 15u) || ((uintptr_t)table & 7u) ||
                          (((uintptr_t)a.sh | (uintptr_t)view | (uintptr_t)linear_rgb | (uintptr_t)gamma_rgb | (uintptr_t)a.moments | (uintptr_t)a.placement) & 3u)))
-        return fail(FW_ERR_BAD_ARG, "device aov, spec and maps must be 16-byte aligned, device table 8-byte aligned, the other device arrays 4-byte aligned");
+        return fail(FW_ERR_BAD_ARG, split ? "device aov, spec and maps must be 16-byte aligned, device table 8-byte aligned, the other device arrays 4-byte aligned"
+                                          : "device aov, spec and maps must be 16-byte aligned, the other device arrays 4-byte aligned");
     const uint64_t full = (uint64_t)p->width * p->height;
     if (int rc = probe_lookup_sizes(a, L)) return rc;
     if (full > 0xffffffffull) return fail(FW_ERR_UNSUPPORTED, "image too large");
@@ -5495,16 +5469,21 @@ int probe_shade_split_impl(const fw_probe_grid *grid, const ProbeLookupArgs &a, 
     hipStream_t stream = (hipStream_t)p->stream;
     Staged st(dev, stream, p->on_device != 0);
     const ProbeTables t = probe_tables_stage(st, a, L);
-    const int a_tab = st.add(Staged::IN, table, (size_t)n_mu * n_rho * 8);
+    const int a_tab = st.add(Staged::IN, table, split ? (size_t)n_mu * n_rho * 8 : 0);      // (no table: no slot, NULL)
     HostSlabs sl(st, (uint32_t)full, 103);
     const int a_aov = sl.in(aov, 48), a_spec = sl.in(spec, 16), a_view = sl.in(view, 12, view_stride);
     const int a_lin = sl.out(linear_rgb, 12), a_gam = sl.out(gamma_rgb, 12), a_8 = sl.out(rgb8, 3);
     if (int rc = st.up()) return rc;
     return sl.run([&](uint32_t, uint32_t k) {
         const fw::DProbeVis v = probe_vis_device(a, st.ptr<const float>(t.mom));
-        fw::launch_probe_split_shade(stream, L.g, a.vis ? &v : nullptr, L.d, st.ptr<const float>(t.sh), st.ptr<const float>(t.maps), st.ptr<const float>(t.pl), k,
-                                     sl.ptr<const float>(a_aov), sl.ptr<const float>(a_spec), sl.ptr<const float>(a_view), sl.stride(a_view),
-                                     st.ptr<const float>(a_tab), n_mu, n_rho, flags, p->gamma, sl.ptr<uint8_t>(a_8), sl.ptr<float>(a_gam), sl.ptr<float>(a_lin));
+        const float *d_sh = st.ptr<const float>(t.sh), *d_maps = st.ptr<const float>(t.maps), *d_pl = st.ptr<const float>(t.pl);
+        const float *d_aov = sl.ptr<const float>(a_aov), *d_spec = sl.ptr<const float>(a_spec), *d_view = sl.ptr<const float>(a_view);
+        uint8_t *o8 = sl.ptr<uint8_t>(a_8);
+        float *og = sl.ptr<float>(a_gam), *ol = sl.ptr<float>(a_lin);
+        if (split) fw::launch_probe_split_shade(stream, L.g, a.vis ? &v : nullptr, L.d, d_sh, d_maps, d_pl, k, d_aov, d_spec, d_view, sl.stride(a_view),
+                                                st.ptr<const float>(a_tab), n_mu, n_rho, flags, p->gamma, o8, og, ol);
+        else fw::launch_probe_shade_glossy(stream, L.g, a.vis ? &v : nullptr, L.d, d_sh, d_maps, d_pl, k, d_aov, d_spec, d_view, sl.stride(a_view), p->gamma,
+                                           o8, og, ol);
     });
 }
 
@@ -6098,7 +6077,7 @@ int fw_probe_shade_split(const fw_probe_grid *grid, const float *sh, const fw_pr
                          uint32_t flags, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
     try {
         const ProbeLookupArgs a{sh, pr, maps, pd, moments, normal_bias, placement, pd || moments, placement != nullptr};
-        return probe_shade_split_impl(grid, a, p, aov, spec, view, view_stride_floats, table, n_mu, n_rho, flags, linear_rgb, gamma_rgb, rgb8);
+        return probe_shade_glossy_impl(grid, a, p, aov, spec, view, view_stride_floats, true, table, n_mu, n_rho, flags, linear_rgb, gamma_rgb, rgb8);
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_split"); }
@@ -6206,7 +6185,7 @@ int fw_probe_shade_glossy(const fw_probe_grid *grid, const float *sh, const fw_p
                           const float *spec, const float *view, uint32_t view_stride_floats, float *linear_rgb, float *gamma_rgb, uint8_t *rgb8) {
     try {
         const ProbeLookupArgs a{sh, pr, maps, pd, moments, normal_bias, placement, pd || moments, placement != nullptr};
-        return probe_shade_glossy_impl(grid, a, p, aov, spec, view, view_stride_floats, linear_rgb, gamma_rgb, rgb8);
+        return probe_shade_glossy_impl(grid, a, p, aov, spec, view, view_stride_floats, false, nullptr, 0, 0, 0, linear_rgb, gamma_rgb, rgb8);
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_probe_shade_glossy"); }

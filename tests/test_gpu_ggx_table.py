@@ -220,6 +220,56 @@ def test_split_shade_is_the_float32_statement_on_the_lookups_outputs(w, h):
                          _lib.probe_shade_split(grid, sh, pr, maps, rec, spec, view, table, w, h, 1, pd, moments, bias, placement, gamma)[2])
 
 
+@pytest.mark.parametrize("with_depth", [False, True])
+def test_the_glossy_and_the_split_shade_share_one_pixel(with_depth):
+    """k_probe_shade_glossy and k_probe_split_shade run one pixel body (shade_glossy_pixel) with two specular terms: on a 16 x 16 image over
+    a 2 x 2 x 2 grid with every kind of pixel, each is its own float32 statement bit for bit, and the two agree bit for bit wherever the
+    term is not used — the diffuse pixels — and on `linear` wherever it is multiplied by a coverage of zero."""
+    rng = np.random.default_rng(7 + with_depth)
+    w = h = 16
+    n = w * h
+    table = _table(16, 16)
+    grid = ProbeGrid((0.0, -1.0, 2.0), (1.0, 1.0, 3.5), (2, 2, 2), True)
+    sh = rng.normal(size=(8, 9, 3)).astype(np.float32)
+    pr = ProbeRadiance(8)
+    maps = rng.uniform(0.0, 4.0, size=(8, pr.texels, 4)).astype(np.float32)
+    pd, moments, bias = None, None, 0.0
+    if with_depth:
+        pd, bias = ProbeDepth(4, 6, 10.0), 0.05
+        m = rng.uniform(0.2, 3.0, size=(8, 4, 4))
+        moments = np.stack([m, m * m + rng.uniform(0.05, 1.0, size=m.shape)], axis=-1).astype(np.float32)
+    placement = np.tile(np.array([0.0, 0.0, 0.0, 1.0], np.float32), (8, 1))
+    pts, nrm, view = _points(grid, n, rng)
+    rec = np.zeros((n, 12), np.float32)
+    rec[:, 0:3] = rng.uniform(0.0, 1.0, size=(n, 3))
+    rec[:, 3] = np.array([0.0, 0.25, 1.0], np.float32)[np.arange(n) % 3]                 # coverage 0, between, 1
+    rec[:, 4:7], rec[:, 8:11] = nrm, pts
+    rec[::11, 4:7] = 0.0                                                                  # an unusable normal
+    spec = np.empty((n, 4), np.float32)
+    spec[:, 0:3] = rng.uniform(0.0, 1.0, size=(n, 3))
+    spec[:, 3] = np.array([0.3, 0.0, 0.05, 1.0, 0.6], np.float32)[np.arange(n) % 5]      # roughness 0: the diffuse branch
+    view[5], view[12, 1], view[6], view[13, 2] = 0.0, NAN, 0.0, NAN                       # zero and NaN views at several coverages
+    glossy = spec[:, 3] > 0
+    for kind in ((rec[:, 3] == 0), (rec[:, 3] == 1), ~np.any(rec[:, 4:7] != 0, axis=1), np.all(view == 0, axis=1), np.any(np.isnan(view), axis=1)):
+        assert np.any(kind & glossy), "every kind of pixel on the glossy branch"
+    assert np.any(~glossy) and np.any((rec[:, 3] == 0) & ~glossy)
+    diffuse = _lib.probe_shade_placed(grid, sh, placement, rec, w, h, pd, moments, bias)[2]
+    r, _S, _ok = api.probe_glossy_dirs(rec, view)
+    rho = np.where(glossy, spec[:, 3], np.float32(0.5)).astype(np.float32)
+    Ls = _lib.probe_radiance_lookup(grid, pr, maps, rec[:, 8:11], rec[:, 4:7], r, rho, pd, moments, bias, placement)
+    terms = _lib.ggx_table_lookup(table, api.probe_split_mu(rec, view), rho)
+    g8, gg, gl = _lib.probe_shade_glossy(grid, sh, pr, maps, rec, spec, view, w, h, pd, moments, bias, placement)
+    assert _same(gl, api.probe_glossy_ref(rec, spec, view, diffuse, Ls))
+    for flags in (0, A.FW_SPLIT_ENERGY):
+        s8, sg, sl = _lib.probe_shade_split(grid, sh, pr, maps, rec, spec, view, table, w, h, flags, pd, moments, bias, placement)
+        assert _same(sl, api.probe_split_ref(rec, spec, view, diffuse, Ls, terms=terms, flags=flags)), flags
+        assert _same(sl[~glossy], gl[~glossy]) and _same(sg[~glossy], gg[~glossy]) and np.array_equal(s8[~glossy], g8[~glossy])
+        assert _same(sl[~glossy], diffuse[~glossy])
+        unseen = rec[:, 3] == 0
+        assert _same(sl[unseen], gl[unseen]) and np.any(unseen & glossy)
+        assert not _same(sl[glossy], gl[glossy])                                          # and elsewhere the two terms differ
+
+
 def _floor_records(mus, per, c, f0, rho):
     """hand-made records of a floor y = 0 seen along directions of cosine mu, `per` pixels each: (rec, spec, view)"""
     n = len(mus) * per
