@@ -71,7 +71,12 @@ other flag).
 F0 A + B from an N_MU x N_RHO table of the GGX directional albedo, default 64,64, each in 2..256, baked on the device in the call,
 fw_ggx_table and fw_probe_shade_split, DESIGN.md §9y, in the place of the bare Schlick term: a rough conductor is no longer several
 times too bright; --probe-energy also multiplies by 1 + F0 (1 / (A + B) - 1), the single-lobe energy compensation; both need a file
-that holds radiance maps and refuse --probe-no-radiance)."""
+that holds radiance maps and refuse --probe-no-radiance).
+--probe-lit FILE --probe-gather D[,ROUNDS] [--gather-bias B] (a final gather: the probes are read one bounce away, at the hits of D
+cosine-weighted gather rays per pixel and round, default 1 round, origins moved B >= 0, default 0.001, along the normal; a ray that hits
+an emitter brings its emission, one that misses the environment: contact shadows, near-field colour bleeding and directly seen emitters
+from the same probes file, fw_bake_gather; with --direct-light the lights are added at the gather hits as well; refuses
+--ao, --probe-split-sum and a file's radiance maps in use: pass --probe-no-radiance)."""
 import argparse
 import sys
 import time
@@ -174,7 +179,29 @@ def main(argv=None):
     ap.add_argument("--probe-split-sum", nargs="?", const="64,64", default=None, metavar="N_MU,N_RHO",
                     help="with --probe-lit: shade glossy pixels with the split sum's BRDF term from an N_MU x N_RHO GGX albedo table (default 64,64)")
     ap.add_argument("--probe-energy", action="store_true", help="with --probe-split-sum: the single-lobe energy compensation")
+    ap.add_argument("--probe-gather", default=None, metavar="D[,ROUNDS]",
+                    help="with --probe-lit: read the probes one bounce away, at the hits of D gather rays per pixel and round (default 1 round)")
+    ap.add_argument("--gather-bias", type=float, default=None, metavar="B",
+                    help="with --probe-gather: move gather-ray origins B >= 0 world units along the normal (default 0.001)")
     opt = ap.parse_args(argv)
+    gather = None
+    if opt.probe_gather is not None:
+        if opt.probe_lit is None:
+            ap.error("--probe-gather needs --probe-lit")
+        if opt.ao is not None:
+            ap.error("--probe-gather cannot be combined with --ao: the gather rays find the occluders themselves")
+        if opt.probe_split_sum is not None:
+            ap.error("--probe-gather cannot be combined with --probe-split-sum: the gathered frame has no specular term")
+        try:
+            gather = [int(x) for x in opt.probe_gather.split(",")]
+        except ValueError:
+            gather = []
+        if not 1 <= len(gather) <= 2 or not 1 <= gather[0] <= 1 << 20 or (len(gather) == 2 and gather[1] < 1):
+            ap.error("--probe-gather needs D[,ROUNDS]: 1 <= D <= 2^20, ROUNDS >= 1")
+        if opt.gather_bias is not None and not 0.0 <= opt.gather_bias < float("inf"):
+            ap.error("--gather-bias B needs a finite B >= 0")
+    elif opt.gather_bias is not None:
+        ap.error("--gather-bias needs --probe-gather")
     split_sum = None
     if opt.probe_split_sum is not None:
         if opt.probe_lit is None:
@@ -451,6 +478,8 @@ def main(argv=None):
                 raise ValueError(f"placement has shape {probe_placement.shape}, the grid {probe_grid.n_probes} probes")
             if probe_radiance is not None and probe_maps.shape != (probe_grid.n_probes, probe_radiance.texels, 4):
                 raise ValueError(f"radiance has shape {probe_maps.shape}, the grid {probe_grid.n_probes} probes of {probe_radiance.texels} texels")
+            if gather is not None and probe_radiance is not None:
+                raise ValueError("--probe-gather cannot be combined with the radiance maps the file holds: pass --probe-no-radiance")
             if split_sum is not None and probe_radiance is None:
                 raise ValueError("--probe-split-sum needs radiance maps and the file holds none (bake it with --probe-radiance R)")
         except (OSError, ValueError, zipfile.BadZipFile) as e:
@@ -514,10 +543,14 @@ def main(argv=None):
         if split_sum is not None:
             from .api import GgxTable
             ggx_table = GgxTable(split_sum[0], split_sum[1], energy=opt.probe_energy)
+        final_gather = None
+        if gather is not None:
+            from .api import FinalGather
+            final_gather = FinalGather(gather[0], 1e-3 if opt.gather_bias is None else opt.gather_bias).seed(opt.seed)
         render = renderer.render_probe_lit(scene, probe_grid, probe_sh, opt.aov_samples, device=opt.device, depth=probe_depth, moments=probe_moments,
                                            normal_bias=0.0 if opt.probe_normal_bias is None else opt.probe_normal_bias,
                                            placement=probe_placement, radiance=probe_radiance, maps=probe_maps, direct=direct_light(opt),
-                                           ggx_table=ggx_table).rgb8
+                                           ggx_table=ggx_table, gather=final_gather, gather_rounds=gather[1] if gather and len(gather) == 2 else 1).rgb8
         print(f"Finished Rendering in {int(time.time() - start)} s")
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)

@@ -133,7 +133,7 @@ def load(preload=False, device=None):
                                    C.c_void_p]
     for name, argtypes in (list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()) + list(A.PROBE_PLACE_PROTOTYPES.items())
                            + list(A.PROBE_RADIANCE_PROTOTYPES.items()) + list(A.DIRECT_PROTOTYPES.items()) + list(A.SKY_PROTOTYPES.items())
-                           + list(A.GGX_TABLE_PROTOTYPES.items())):
+                           + list(A.GGX_TABLE_PROTOTYPES.items()) + list(A.GATHER_PROTOTYPES.items())):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
@@ -1069,6 +1069,29 @@ def direct_reduce(direct, lights, positions, normals, rays, hits, sums, ids=None
     return sums
 
 
+def gather_reduce(surface, irradiance, directions, sums, direct=None, ids=None, device=0, stream=None):
+    """fw_gather_reduce: adds one round's reduction (E.rgb, sky, each rounded to float32 once) of a final gather to sums[ids[q]] (ids
+    None: sums[q]); sums (M, 4) or (H, W, 4) float32, updated in place.  surface (n * D, 16) float32 as DeviceScene.hit_surface returns
+    it, irradiance (n * D, 3) float32 the probe lookup at those records, direct (n * D, 8) float32 as DeviceScene.bake_direct's out for
+    them, or None: numpy arrays, or tensors on cuda:`device`, reduced on `stream` (default: the current torch stream) where they lie; ids
+    n distinct ids (uint32 numpy / int32 torch).  Returns sums."""
+    lib = load()
+    d = int(directions)
+    total = int(surface.shape[0])
+    if d < 1 or total % d or tuple(surface.shape) != (total, 16):
+        raise ValueError(f"surface must have shape (n * {d}, 16)")
+    n = total // d
+    m = int(np.prod(tuple(sums.shape)[:-1]))
+    if sums.shape[-1] != 4 or (ids is None and m < n) or (ids is not None and tuple(ids.shape) != (n,)):
+        raise ValueError(f"sums must have shape (M, 4) or (H, W, 4) with M >= {n}, ids shape ({n},)")
+    s = _Side(surface, device)
+    rec, e, ed = s.inp(surface, (total, 16), "surface"), s.inp(irradiance, (total, 3), "irradiance"), s.inp(direct, (total, 8), "direct")
+    s.out(sums, tuple(sums.shape), "sums")
+    i = s.inp(ids, (n,), "ids", "ids", below=m)
+    _check(lib, lib.fw_gather_reduce(int(device), d, n, *s.ptrs(i, rec, e, ed, sums), *s.tail(stream)))
+    return sums
+
+
 def _sky_abi(sky):
     """a fw_sky from an api.SunSky (or a fw_sky, copied)"""
     return sky.to_abi() if hasattr(sky, "to_abi") else A.fw_sky.from_buffer_copy(sky)
@@ -1547,6 +1570,27 @@ class DeviceScene:
         return self._bake_points(self._lib.fw_bake_direct, d, pts, 8, head, rounds, first_round, sums, out, seed, use_bvh, stream, rays_per_batch,
                                  flags)
 
+    def bake_gather(self, gather, grid, sh, positions, normals, ids=None, depth=None, moments=None, normal_bias=0.0, placement=None, rounds=1,
+                    first_round=0, sums=None, out=None, seed=0, use_bvh=True, stream=None, rays_per_batch=0, flags=0, chunk=None):
+        """fw_bake_gather: the rounds [first_round, first_round + rounds) of an api.FinalGather at surface points (see _AoPoints: numpy
+        arrays, or tensors on this scene's device, read in place) against this scene and the baked probes (grid, sh; depth + moments:
+        the visibility weight; placement: moved and classified probes), of the points' kind, `chunk` points at a time (None: the
+        description's own setting; 0: automatic).  sums: (M, 4) or (H, W, 4) float32 running sums (Er, Eg, Eb, sky) of the rounds before
+        first_round, updated in place (None: zeros, only with first_round 0); out: an array of the same kind to receive sums / rounds
+        (None: zeros); both are indexed by id, entries outside ids are not touched.  Returns (out, sums, stats): host arrays for numpy
+        points, device tensors — baked on `stream` (default: the current torch stream) — for device points."""
+        g = gather.to_abi()
+        if chunk is not None:
+            g.chunk_points = int(chunk)
+        pts = _AoPoints(positions, normals, ids, self.device)
+        s = pts.side
+        gr, n_probes = _grid_abi(grid)
+        vis = _vis_of(depth, moments, normal_bias)
+        head = (C.byref(gr), s.ptr(s.inp(sh, (n_probes, 9, 3), "sh")), *_vis_args(s, vis, n_probes), _placement_arg(s, placement, n_probes),
+                pts.n, pts.pos, pts.nrm, pts.stride, pts.ids)
+        return self._bake_points(self._lib.fw_bake_gather, g, pts, 4, head, rounds, first_round, sums, out, seed, use_bvh, stream, rays_per_batch,
+                                 flags)
+
     def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,
                       flags=0, chunk=None, on_device=False):
         """fw_bake_lightmap: the rounds [first_round, first_round + rounds) of an api.Lightmap, `samples` paths per direction and round,
@@ -1581,6 +1625,19 @@ class DeviceScene:
         _check(self._lib, self._lib.fw_trace_rays(self.handle, C.byref(p), s.ptr(r), n, s.ptr(out), C.byref(st)))
         if stats is not None:
             stats.update(st.as_dict())
+        return out
+
+    def hit_surface(self, rays, hits, out=None, stream=None):
+        """fw_hit_surface: the material at the hits `trace` returned for `rays` on this scene, as an (n, 16) float32 array (columns:
+        SURFACE_COLUMNS): albedo, kind (the material's, -1 a miss, -2 a ray that was not traced), the normal facing the ray, distance,
+        position, 0, the emitted radiance (an emitter's, or the environment's on a miss; not clamped), 0.  numpy rays with a HIT_DTYPE
+        array, or device tensors ((n, 6) and (n, 12) float32) on this scene's device, evaluated on `stream` (default: the current torch
+        stream) where they lie.  out: a contiguous (n, 16) float32 array or tensor of the rays' kind to fill instead; returned."""
+        s = _Side(rays, self.device)
+        n = s.count(rays, 6)
+        r, h = s.inp(rays, (n, 6), "rays"), s.hits(hits, n)
+        out = s.out(out, (n, 16), "out")
+        _check(self._lib, self._lib.fw_hit_surface(self.handle, *s.ptrs(r, h), n, s.ptr(out), *s.tail(stream)))
         return out
 
     def aovs(self, renderer, samples, out=None, stream=None):
@@ -1656,6 +1713,8 @@ def render_scene_tiled(scene_desc, renderer, devices):
 
 # columns of fw_render_aovs' (N, 12) records
 AOV_COLUMNS = dict(albedo=slice(0, 3), coverage=3, normal=slice(4, 7), distance=7, position=slice(8, 11))
+# column of each field in the (n, 16) float32 records DeviceScene.hit_surface returns
+SURFACE_COLUMNS = dict(albedo=slice(0, 3), kind=3, normal=slice(4, 7), distance=7, position=slice(8, 11), emitted=slice(12, 15))
 
 
 def denoise(color, aov, moments=None, width=None, height=None, iterations=A.FW_DENOISE_ITERATIONS, gamma=2.2, device=0, stream=None):

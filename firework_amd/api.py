@@ -2966,6 +2966,103 @@ def ao_resolve(sums, rounds: int) -> np.ndarray:
         return np.concatenate([bent, occ[..., None]], axis=-1).astype(np.float32)
 
 
+# --------------------------------------------------------------------------- final gather (fw_bake_gather)
+class FinalGather:
+    """One bounce of gather rays lit from baked probes (fw_gather): `directions` cosine-weighted hemisphere rays per point
+    and round, origins moved `bias` along the normal; each ray brings back the emission of the emitter it hit, the environment where it
+    missed, or hit albedo x E(hit) / pi with E from the probes at the hit.  direct=True adds the scene's point, spot and directional
+    lights at the gather hits, their shadow rays moved direct_bias along the hit's normal.  .seed(s) / .jitter(on) as builders;
+    chunk_points as fw_gather's."""
+
+    def __init__(self, directions: int = 64, bias: float = 1e-3, direct: bool = False, direct_bias: float = 1e-3):
+        self.directions, self.bias, self.direct, self.direct_bias = int(directions), float(np.float32(bias)), bool(direct), float(np.float32(direct_bias))
+        self._seed, self._jitter, self.chunk_points = 0, True, 0
+
+    def seed(self, s):
+        self._seed = int(s)
+        return self
+
+    def jitter(self, on=True):
+        self._jitter = bool(on)
+        return self
+
+    def check(self):
+        """what fw_bake_gather rejects in a description, as a ValueError, in its order"""
+        if not 1 <= self.directions <= 1 << 20:
+            raise ValueError("directions must be in 1..2^20")
+        if not (np.isfinite(self.bias) and self.bias >= 0.0):
+            raise ValueError("bias must be finite and >= 0")
+        if not (np.isfinite(self.direct_bias) and self.direct_bias >= 0.0):
+            raise ValueError("direct_bias must be finite and >= 0")
+        return self
+
+    def ao(self) -> "AmbientOcclusion":
+        """the AmbientOcclusion whose rays the gather rays are, bit for bit"""
+        return AmbientOcclusion(float("inf"), self.directions, 0, self.bias).seed(self._seed).jitter(self._jitter)
+
+    def to_abi(self) -> A.fw_gather:
+        g = A.fw_gather()
+        g.directions, g.jitter, g.bias, g.direct_bias = self.directions & 0xFFFFFFFF, int(self._jitter), self.bias, self.direct_bias
+        g.flags, g.chunk_points, g.seed = (A.FW_GATHER_DIRECT if self.direct else 0), int(self.chunk_points), self._seed & 0xFFFFFFFFFFFFFFFF
+        return g
+
+
+def surface_facing(normal, direction) -> np.ndarray:
+    """The float32 statement of a surface record's normal (fw_hit_surface): n / len(n) with len(n) = sqrt((x x + y y) + z z), (0, 0, 0)
+    where that length is 0, negated where (nx dx + ny dy) + nz dz > 0 on the hit's normal and the ray's direction as stored: (..., 3)
+    float32, every operation rounded to float32 as written."""
+    n, d = np.asarray(normal, np.float32), np.asarray(direction, np.float32)
+    with np.errstate(all="ignore"):
+        length = np.sqrt((n[..., 0] * n[..., 0] + n[..., 1] * n[..., 1]) + n[..., 2] * n[..., 2], dtype=np.float32)
+        unit = np.where((length == 0)[..., None], np.float32(0), n / length[..., None]).astype(np.float32)
+        away = (n[..., 0] * d[..., 0] + n[..., 1] * d[..., 1]) + n[..., 2] * d[..., 2] > 0
+    return np.where(away[..., None], -unit, unit).astype(np.float32)
+
+
+def gather_reduce(surface, irradiance, directions: int, direct=None) -> np.ndarray:
+    """The numpy float64 statement of fw_gather_reduce: (n, 4) float64, (pi / D) x the accumulators L.rgb and (1 / D) x sky of one round
+    before their one rounding to float32, for surface (n * D, 16) float32 records, irradiance (n * D, 3) float32 and direct (n * D, 8)
+    float32 or None, summed in the device's order (G partial sums, an xor butterfly)."""
+    D = int(directions)
+    s = np.asarray(surface, np.float32).astype(np.float64).reshape(-1, D, 16)
+    E = np.asarray(irradiance, np.float32).astype(np.float64).reshape(-1, D, 3)
+    n = s.shape[0]
+    kind = s[..., 3]
+    T = np.where(E > 0.0, E, 0.0)
+    if direct is not None:
+        T = T + np.asarray(direct, np.float32).astype(np.float64).reshape(-1, D, 8)[..., 0:3]
+    inv_pi = 1.0 / 3.141592653589793
+    with np.errstate(all="ignore"):
+        L = (s[..., 0:3] * T) * inv_pi
+    emits = (kind == -1.0) | (kind == 3.0)
+    L = np.where(emits[..., None], s[..., 12:15], L)
+    term = np.concatenate([L, (kind == -1.0)[..., None].astype(np.float64)], axis=-1)       # (n, D, 4)
+    live = kind != -2.0
+    G = 1
+    while G < min(D, 64):
+        G *= 2
+    rows = -(-D // G)                                                                        # lane l takes j = l, l + G, ... in ascending order
+    padded = np.zeros((n, rows * G, 4))
+    padded[:, :D] = term
+    take = np.zeros((n, rows * G), bool)
+    take[:, :D] = live
+    part = np.zeros((n, G, 4))
+    with np.errstate(all="ignore"):
+        for row, on in zip(padded.reshape(n, rows, G, 4).transpose(1, 0, 2, 3), take.reshape(n, rows, G).transpose(1, 0, 2)):
+            part = np.where(on[..., None], part + row, part)                                 # (a ray that contributes nothing adds nothing: -0 and NaN stay out)
+        m = G // 2
+        while m >= 1:
+            part = part + part[:, np.arange(G) ^ m]
+            m //= 2
+        return np.concatenate([(3.141592653589793 / D) * part[:, 0, 0:3], (1.0 / D) * part[:, 0, 3:4]], axis=-1)
+
+
+def gather_resolve(sums, rounds: int) -> np.ndarray:
+    """The statement of k_gather_resolve: (..., 4) float32 (E.rgb, sky) = float32(sums / rounds) from the float32 running sums."""
+    with np.errstate(all="ignore"):
+        return (np.asarray(sums, np.float32).astype(np.float64) / float(rounds)).astype(np.float32)
+
+
 # --------------------------------------------------------------------------- direct light of delta lights (fw_bake_direct; DESIGN.md §9w)
 class DirectLight:
     """The direct light of a scene's point, spot and directional lights at surface points (fw_direct): one shadow ray per
@@ -3743,10 +3840,55 @@ class Renderer:
                 ds.close()
         return RenderResult(rgb8.cpu().numpy(), gam.cpu().numpy(), lin.cpu().numpy(), stats, w, h)
 
+    def _gather(self, ds, gather: "FinalGather", rounds, grid, d_sh, aov, depth, d_mom, normal_bias, d_pl, direct=None):
+        """(out (N, 4), sums (N, 4)) device tensors: fw_bake_gather on the records `aov` in place (stride 12, aov + 8 / aov + 4) with this
+        renderer's seed, use_bvh and flags; with `direct`, a DirectLight, FW_GATHER_DIRECT with its bias.  The call's stats are kept in
+        self.gather_stats."""
+        import copy
+        s = self.settings
+        g = copy.copy(gather)
+        if direct is not None:
+            g.direct, g.direct_bias = True, direct.bias
+        out, sums, self.gather_stats = ds.bake_gather(g, grid, d_sh, aov[:, 8:11], aov[:, 4:7], None, depth, d_mom, normal_bias, d_pl, rounds,
+                                                      seed=s["seed"], use_bvh=s["use_bvh"], flags=s["flags"])
+        return out, sums
+
+    def render_gather(self, scene, gather: "FinalGather", probes, sh, rounds: int = 1, samples: int = 1, wrap: bool = True, device: int = 0,
+                      depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0, placement=None):
+        """The irradiance gathered at this renderer's view from baked probes (not in the reference; fw_bake_gather): the
+        first-hit guide buffers (fw_render_aovs at `samples` samples) stay on the device, and fw_bake_gather reads each pixel's position
+        and normal from the records in place, tracing `rounds` rounds of gather.directions rays with this renderer's seed (+ the round),
+        use_bvh and flags; probes, sh, depth, moments, normal_bias and placement as render_probe_lit takes them.  Returns (E (H, W, 3),
+        sky (H, W), sums (H, W, 4)) float32 host arrays; a pixel that missed the scene has E 0 and sky 0.  The call's stats are kept in
+        self.gather_stats.  `scene`: a Scene, a SceneDesc or an uploaded _lib.DeviceScene."""
+        import torch
+        from . import _lib
+        gather.check()
+        if depth is not None and moments is None:
+            raise ValueError("depth needs the moments bake_probe_depth returned")
+        grid = ProbeGrid.of(probes, wrap)
+        s = self.settings
+        w, h = int(s["width"]), int(s["height"])
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            dev = torch.device("cuda", ds.device)
+            to = lambda a, shape: None if a is None else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).reshape(shape))).to(dev)
+            aov = torch.empty((w * h, 12), dtype=torch.float32, device=dev)
+            ds.aovs(self, samples, out=aov)
+            R = int(depth.resolution) if depth is not None else 0
+            out, sums = self._gather(ds, gather, rounds, grid, to(sh, (grid.n_probes, 9, 3)), aov, depth,
+                                     to(moments if depth is not None else None, (grid.n_probes, R, R, 2)), normal_bias, to(placement, (grid.n_probes, 4)))
+        finally:
+            if ds is not scene:
+                ds.close()
+        out = out.cpu().numpy().reshape(h, w, 4)
+        return out[..., 0:3], out[..., 3], sums.cpu().numpy().reshape(h, w, 4)
+
     def render_probe_lit(self, scene, probes, sh, aov_samples: int = 8, wrap: bool = True, device: int = 0, model: "CameraModel" = None,
                          depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0, ao: "AmbientOcclusion" = None,
                          ao_rounds: int = 1, placement=None, radiance: "ProbeRadiance" = None, maps=None,
-                         direct: "DirectLight" = None, ggx_table: "GgxTable" = None, table=None) -> RenderResult:
+                         direct: "DirectLight" = None, ggx_table: "GgxTable" = None, table=None, gather: "FinalGather" = None,
+                         gather_rounds: int = 1) -> RenderResult:
         """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
         (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
         from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
@@ -3773,11 +3915,20 @@ class Renderer:
         by fw_probe_shade_split — F0 A + B from the table in the place of the bare Schlick term, with ggx_table.energy the energy
         compensation — and every other pixel as before; the table is baked on the device in the call (fw_ggx_table) unless `table`,
         (n_rho, n_mu, 2) as _lib.ggx_table returns it, is passed.  ggx_table without radiance: ValueError.  ggx_table=None: the
-        calls and the bits above."""
+        calls and the bits above.  gather (a FinalGather): the probes are read one bounce away instead of at the
+        pixel — fw_bake_gather runs `gather_rounds` rounds on the records in place, with depth, moments, normal_bias and placement
+        passed on to the lookup at the gather hits; with Eg its out, the frame is out_c = a_c (v (Eg_c float32(1 / pi)) + (1 - v))
+        in float32, resolved by fw_denoise at 0 iterations.  With direct, the gather adds the delta lights at its hits as well
+        (FW_GATHER_DIRECT with direct's bias), and the receivers' own term is added as above.  The call's stats are kept in
+        self.gather_stats.  gather together with ao or radiance: ValueError.  gather=None: the calls and the bits above."""
         import torch
         from . import _lib
         if direct is not None:
             direct.check()
+        if gather is not None:
+            if ao is not None or radiance is not None:
+                raise ValueError("gather cannot be combined with ao or radiance: the gathered frame has neither term")
+            gather.check()
         if ggx_table is not None:
             if radiance is None:
                 raise ValueError("ggx_table needs radiance: the split sum's BRDF term multiplies the radiance maps' lookup")
@@ -3813,7 +3964,12 @@ class Renderer:
             if placement is not None:
                 d_pl = torch.from_numpy(np.ascontiguousarray(np.asarray(placement, np.float32).reshape(grid.n_probes, 4))).to(dev)
             rays = None
-            if ao is not None:
+            if gather is not None:
+                Eg = self._gather(ds, gather, gather_rounds, grid, d_sh, aov, depth, d_mom, normal_bias, d_pl, direct)[0]
+                v = aov[:, 3:4]
+                lit = aov[:, 0:3] * (v * (Eg[:, 0:3] * float(np.float32(1.0 / np.pi))) + (1.0 - v))
+                rgb8, gam, lin = _lib.denoise(lit.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
+            elif ao is not None:
                 occ, _sums, self.ao_stats = ds.bake_ao(ao, aov[:, 8:11], aov[:, 4:7], None, ao_rounds, seed=s["seed"], use_bvh=s["use_bvh"],
                                                        flags=s["flags"])
                 bent = torch.any(occ[:, 0:3] != 0, dim=1, keepdim=True)

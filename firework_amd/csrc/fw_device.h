@@ -502,6 +502,10 @@ void launch_camera_rays(hipStream_t stream, int n_cus, const DCamera &, const DF
 void launch_aov_accumulate(hipStream_t stream, int n_cus, const DScene &, const DFrame &, const DPaths &in, const float2 *hits, const uint32_t *slot_of,
                            uint32_t n, uint32_t first, float4 *sum);
 void launch_aov_finish(hipStream_t stream, int n_cus, uint32_t n, uint32_t spp, float4 *aov);
+// fw_hit_surface: the material at n caller-supplied hits (rays n x 6 floats, hits n records of 48 B as k_trace_store wrote them) as four
+// float4 per ray: (albedo, kind), (facing normal, distance), (position, 0), (emitted, 0).  n_mat: the scene's material count — a record
+// whose material or object is outside the scene's tables is written as kind -2 and loads nothing.
+void launch_hit_surface(hipStream_t stream, int n_cus, const DScene &, uint32_t n_mat, const float *rays, const float4 *hits, uint32_t n, float4 *surface);
 // fw_denoise on device arrays: the prep pass, L a-trous iterations ping-ponging between ev0 and ev1 (guide: 2 x float4 per pixel, ev0 / ev1:
 // one float4 per pixel; all unused at L = 0), the final remodulation and resolve
 void launch_denoise(hipStream_t stream, int n_cus, uint32_t W, uint32_t H, uint32_t L, const float *color, const float4 *aov, const float4 *moments,

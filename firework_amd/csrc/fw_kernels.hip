@@ -5115,6 +5115,50 @@ __global__ __launch_bounds__(BLOCK) void k_aov_accumulate(DScene sc, DFrame f, D
         s[0] = a; s[1] = b; s[2] = c;
     }
 }
+// fw_hit_surface (include/firework_hip.h has the statement): the material at the caller's own hits, one lane per ray.  What it reads of
+// the scene are the material and texture tables and the environment: the hit's material is checked against n_mat and its object against
+// the scene's object count first, so no load leaves the tables whatever the records hold (texture_sample bounds u, v and the point
+// itself).  Emission and the environment are not clamped.
+__global__ __launch_bounds__(BLOCK) void k_hit_surface(DScene sc, uint32_t n_mat, const float *__restrict__ rays, const float4 *__restrict__ hits,
+                                                       uint32_t n, float4 *__restrict__ out) {
+    if (sc.has_perlin) stage_perm();       // (a scene-wide, block-uniform condition)
+    __syncthreads();
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const float *r = rays + (size_t)i * 6u;
+        const float ox = r[0], oy = r[1], oz = r[2], dx = r[3], dy = r[4], dz = r[5];
+        const float4 h0 = hits[3 * (size_t)i], h1 = hits[3 * (size_t)i + 1], h2 = hits[3 * (size_t)i + 2];
+        const uint32_t material = __float_as_uint(h2.y), object = __float_as_uint(h2.z);
+        float4 o0 = make_float4(0.f, 0.f, 0.f, -2.f), o1 = make_float4(0.f, 0.f, 0.f, 0.f), o2 = o1, o3 = o1;
+        const bool traced = finite_f(ox) && finite_f(oy) && finite_f(oz) && finite_f(dx) && finite_f(dy) && finite_f(dz)
+                            && !(dx == 0.f && dy == 0.f && dz == 0.f);
+        if (traced && object == MISS) {
+            const float l = len_plain(dx, dy, dz);
+            const V3 c = env_sample(sc.env, mk(fdiv(dx, l), fdiv(dy, l), fdiv(dz, l)));
+            o0.w = -1.f;
+            o3 = make_float4(c.x, c.y, c.z, 0.f);
+        } else if (traced && material < n_mat && object < sc.n_objects) {
+            const float4 m0 = sc.mat[2 * material], m1 = sc.mat[2 * material + 1];
+            const uint32_t mkind = __float_as_uint(m0.x) & 0xffu, mtex = __float_as_uint(m0.y);
+            const V3 point = mk(h0.y, h0.z, h0.w);
+            V3 alb = mk(0.f, 0.f, 0.f), emi = mk(0.f, 0.f, 0.f);
+            if (mkind == 1u || mkind == 5u) alb = mk(m1.x, m1.y, m1.z);                      // Metal: its albedo; GgxMat: F0
+            else if (mkind == 2u) alb = mk(1.f, 1.f, 1.f);                                   // Dielectric
+            else {
+                const V3 t = texture_sample(sc.tex, sc.images, mtex, h1.w, h2.x, point);     // Lambertian, Isotropic, Emissive
+                if (mkind == 3u) emi = t; else alb = t;                                      // (an emitter never scatters)
+            }
+            const float nl = len_plain(h1.x, h1.y, h1.z);
+            V3 nrm = nl == 0.f ? mk(0.f, 0.f, 0.f) : mk(fdiv(h1.x, nl), fdiv(h1.y, nl), fdiv(h1.z, nl));
+            if ((h1.x * dx + h1.y * dy) + h1.z * dz > 0.f) nrm = mk(-nrm.x, -nrm.y, -nrm.z);  // the side the ray arrived from
+            o0 = make_float4(alb.x, alb.y, alb.z, (float)mkind);
+            o1 = make_float4(nrm.x, nrm.y, nrm.z, h0.x * len_plain(dx, dy, dz));
+            o2 = make_float4(point.x, point.y, point.z, 0.f);
+            o3 = make_float4(emi.x, emi.y, emi.z, 0.f);
+        }
+        float4 *s = out + 4 * (size_t)i;
+        s[0] = o0; s[1] = o1; s[2] = o2; s[3] = o3;
+    }
+}
 // sums -> the records: albedo and normal / S, distance and position / hits (0 without hits), coverage = hits / S
 __global__ __launch_bounds__(BLOCK) void k_aov_finish(uint32_t n, float spp, float4 *__restrict__ aov) {
     for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < n; p += gridDim.x * BLOCK) {
@@ -5258,6 +5302,9 @@ static uint32_t flat_blocks(uint64_t n, int n_cus, uint32_t per_cu) {
 void launch_aov_accumulate(hipStream_t stream, int n_cus, const DScene &sc, const DFrame &f, const DPaths &in, const float2 *hits, const uint32_t *slot_of,
                            uint32_t n, uint32_t first, float4 *sum) {
     hipLaunchKernelGGL(k_aov_accumulate, dim3(flat_blocks(n, n_cus, 32)), dim3(BLOCK), 0, stream, sc, f, in, hits, slot_of, n, first, sum);
+}
+void launch_hit_surface(hipStream_t stream, int n_cus, const DScene &sc, uint32_t n_mat, const float *rays, const float4 *hits, uint32_t n, float4 *surface) {
+    hipLaunchKernelGGL(k_hit_surface, dim3(flat_blocks(n, n_cus, 32)), dim3(BLOCK), 0, stream, sc, n_mat, rays, hits, n, surface);
 }
 void launch_aov_finish(hipStream_t stream, int n_cus, uint32_t n, uint32_t spp, float4 *aov) {
     hipLaunchKernelGGL(k_aov_finish, dim3(flat_blocks(n, n_cus, 8)), dim3(BLOCK), 0, stream, n, (float)spp, aov);

@@ -22,6 +22,7 @@
 #include "fw_direct.h"
 #include "fw_sky.h"
 #include "fw_ggx_table.h"
+#include "fw_gather.h"
 #include "fw_defer_pretest.h"
 
 #include <algorithm>
@@ -3714,7 +3715,7 @@ struct Staged {
     enum Kind { IN, INOUT, OUT, WORK, ZERO };
     struct Slot { Kind kind; void *host; size_t bytes, at; bool staged, back; };
     hipStream_t stream; bool on_device; CallScratch scratch;
-    Slot slots[12] = {}; int n_slots = 0; size_t off = 0; bool armed = false;
+    Slot slots[16] = {}; int n_slots = 0; size_t off = 0; bool armed = false;
     Staged(int device, hipStream_t stream_, bool on_device_) : stream(stream_), on_device(on_device_), scratch(device) {}
     ~Staged() { if (armed) (void)hipStreamSynchronize(stream); }
     int add(Kind kind, const void *p, size_t bytes, bool host_always = false) {
@@ -5084,6 +5085,173 @@ int bake_direct_impl(fw_scene *sc, const fw_direct *dp, const fw_trace_params *t
     return FW_OK;
 }
 
+// ---- final gather (include/firework_hip.h) -------------------------------------------------------------------------
+// the stream waits for the scene's upload, as a trace's does
+int wait_scene_upload(int dev, hipStream_t stream) {
+    Workspace *ws = workspace_for(dev);
+    if (!ws) return fail(FW_ERR_OOM, "no workspace for this device");
+    std::lock_guard<std::mutex> ws_guard(ws->mu);
+    if (ws->ev_upload) HIPCHK(hipStreamWaitEvent(stream, ws->ev_upload, 0));
+    return FW_OK;
+}
+
+// fw_hit_surface: fw_trace_rays' argument pattern; with device arrays the kernel works on the caller's memory, with host arrays the rays,
+// hits and records pass through slabs of one device allocation (136 B per ray)
+int hit_surface_impl(fw_scene *sc, const float *rays, const fw_hit *hits, uint32_t n, float *surface, int on_device, void *stream_) {
+    if (!sc) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (n == 0) return FW_OK;
+    if (!rays || !hits || !surface) return fail(FW_ERR_BAD_ARG, "null rays, hits or surface");
+    if (((uintptr_t)rays & 3u) || (on_device && (((uintptr_t)hits | (uintptr_t)surface) & 15u)))
+        return fail(FW_ERR_BAD_ARG, "rays must be 4-byte aligned, device hits and surface 16-byte aligned");
+    if (int rc = need_device()) return rc;
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = wait_scene_upload(dev, stream)) return rc;
+    Staged st(dev, stream, on_device != 0);
+    HostSlabs sl(st, n, 24 + sizeof(fw_hit) + 64);
+    const int a_rays = sl.in(rays, 24), a_hits = sl.in(hits, sizeof(fw_hit)), a_out = sl.out(surface, 64);
+    if (int rc = st.up()) return rc;
+    return sl.run([&](uint32_t, uint32_t k) {
+        fw::launch_hit_surface(stream, sc->n_cus, sc->d, sc->n_mat, sl.ptr<const float>(a_rays), sl.ptr<const float4>(a_hits), k, sl.ptr<float4>(a_out));
+    });
+}
+
+// fw_gather_reduce: fw_ao_reduce's shape
+int gather_reduce_impl(int device, uint32_t D, uint32_t n, const uint32_t *ids, const float *surface, const float *irradiance, const float *direct,
+                       float *sums, int on_device, void *stream_) {
+    if (!surface || !irradiance || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (D == 0 || D > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (on_device && ((((uintptr_t)sums | (uintptr_t)surface) & 15u) || (((uintptr_t)irradiance | (uintptr_t)direct | (uintptr_t)ids) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums and surface must be 16-byte aligned, device irradiance, direct and ids 4-byte aligned");
+    if ((uint64_t)n * D >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t entries = (size_t)n * D;
+    Staged st(device, stream, on_device != 0);
+    const int i_surf = st.add(Staged::IN, surface, entries * 64), i_irr = st.add(Staged::IN, irradiance, entries * 12),
+              i_dir = st.add(Staged::IN, direct, entries * 32), i_sums = st.add(Staged::INOUT, sums, on_device ? 0 : (size_t)ao_extent(n, ids) * 16),
+              i_ids = st.add(Staged::IN, ids, (size_t)n * 4);
+    if (int rc = st.up()) return rc;
+    fw::launch_gather_reduce(stream, device_cus(device), 0, n, D, st.ptr<const uint32_t>(i_ids), st.ptr<const float>(i_surf), st.ptr<const float>(i_irr),
+                             st.ptr<const float>(i_dir), st.ptr<float>(i_sums));
+    return st.finish();
+}
+
+// A gather description's own argument checks (FW_ERR_BAD_ARG only); the flags are checked after the probe tables
+int gather_check(const fw_gather *g) {
+    if (g->directions == 0 || g->directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (!std::isfinite(g->bias) || g->bias < 0.f) return fail(FW_ERR_BAD_ARG, "bias must be finite and >= 0");
+    if (!std::isfinite(g->direct_bias) || g->direct_bias < 0.f) return fail(FW_ERR_BAD_ARG, "direct_bias must be finite and >= 0");
+    return FW_OK;
+}
+
+// fw_bake_gather: fw_bake_ao's shape — k_ao_rays as trace_rounds' generator; its reducer is the rest of the chain over the chunk's rays and
+// hits: k_hit_surface, the probe lookup at the records read in place, with FW_GATHER_DIRECT fw_bake_direct's kernels around a second
+// trace, and k_gather_reduce.  The reducer returns nothing, so the second trace's code leaves through `chain_rc`: once it is set the
+// remaining chunks' kernels are not launched and the call returns it.
+int bake_gather_impl(fw_scene *sc, const fw_gather *g, const fw_trace_params *tp, const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd,
+                     const float *moments, float normal_bias, const float *placement, uint32_t N, const float *positions, const float *normals,
+                     uint32_t stride, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    if (!sc || !g || !tp || !positions || !normals) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = gather_check(g)) return rc;
+    if (N == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (rounds == 0) return fail(FW_ERR_BAD_ARG, "rounds must be > 0");
+    if ((uint64_t)first_round + rounds > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_round + rounds overflows");
+    if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
+    if (tp->on_device && ((((uintptr_t)sums | (uintptr_t)out) & 15u) || (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums and out must be 16-byte aligned, device positions, normals and ids 4-byte aligned");
+    const ProbeLookupArgs a{sh, nullptr, nullptr, pd, moments, normal_bias, placement, pd || moments, placement != nullptr};
+    ProbeLookup L;
+    if (int rc = probe_lookup_check(grid, a, !sh, false, L)) return rc;
+    if (tp->on_device && (((uintptr_t)sh | (uintptr_t)moments | (uintptr_t)placement) & 3u)) return fail(FW_ERR_BAD_ARG, "device sh, moments and placement must be 4-byte aligned");
+    if (g->flags & ~(uint32_t)FW_GATHER_DIRECT) return fail(FW_ERR_BAD_ARG, "unknown gather flags");
+    const uint32_t D = g->directions;
+    if ((uint64_t)N * D >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
+    if (int rc = probe_lookup_sizes(a, L)) return rc;
+    if (int rc = need_device()) return rc;
+    const uint32_t Ln = (g->flags & FW_GATHER_DIRECT) ? sc->n_dlights : 0u;
+    if ((uint64_t)N * D * Ln >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions x the scene's lights must be below 2^31");
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)tp->stream;
+    const bool on_device = tp->on_device != 0;
+    const uint64_t ray_bytes = 24 + sizeof(fw_hit) + 64 + 12 + (Ln ? (uint64_t)Ln * 72 + 64 : 0);
+    const uint32_t chunk = std::min<uint32_t>(N, g->chunk_points ? g->chunk_points : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * ray_bytes)));
+    // how many records sums and out span: only scratch copies of them need it (a host caller's, or the sums nobody keeps)
+    uint64_t extent = N;
+    if (ids && (!on_device || !sums)) {
+        if (on_device) {
+            std::vector<uint32_t> h_ids(N);
+            HIPCHK(hipMemcpyAsync(h_ids.data(), ids, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            extent = ao_extent(N, h_ids.data());
+        } else extent = ao_extent(N, ids);
+    }
+    const size_t rec_bytes = (size_t)extent * 16, cd = (size_t)chunk * D;
+    Staged st(dev, stream, on_device);
+    const AoSlots slots = ao_points_stage(st, N, positions, normals, stride, ids, extent);
+    const ProbeTables t = probe_tables_stage(st, a, L);
+    const int i_rays = st.add(Staged::WORK, nullptr, cd * 24), i_hits = st.add(Staged::WORK, nullptr, cd * sizeof(fw_hit)),
+              i_surf = st.add(Staged::WORK, nullptr, cd * 64), i_irr = st.add(Staged::WORK, nullptr, cd * 12);
+    const int i_drays = Ln ? st.add(Staged::WORK, nullptr, cd * Ln * 24) : -1, i_dhits = Ln ? st.add(Staged::WORK, nullptr, cd * Ln * sizeof(fw_hit)) : -1,
+              i_dsums = Ln ? st.add(Staged::WORK, nullptr, cd * 32) : -1;
+    const int i_sums = st.add_sums(sums, rec_bytes), i_out = st.add(ids ? Staged::INOUT : Staged::OUT, out, rec_bytes);      // (with ids, entries outside the list stay)
+    if (int rc = st.up()) return rc;
+    const fw::DAoPoints pts = ao_points_device(st, slots, stride);
+    float *d_sums = st.ptr<float>(i_sums), *d_surf = st.ptr<float>(i_surf), *d_irr = st.ptr<float>(i_irr);
+    const float *d_sh = st.ptr<const float>(t.sh), *d_pl = st.ptr<const float>(t.pl);
+    const fw::DProbeVis vis = probe_vis_device(a, st.ptr<const float>(t.mom));
+    const int n_cus = device_cus(dev);
+    fw_ao ao{};
+    ao.directions = D; ao.falloff = 0; ao.radius = std::numeric_limits<float>::infinity(); ao.bias = g->bias; ao.jitter = g->jitter; ao.seed = g->seed;
+    fw_stats total{};
+    int chain_rc = FW_OK;
+    uint32_t round = first_round;              // the reducer's round: trace_rounds hands it to the generator only
+    const TraceRounds b{N, D, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
+    if (int rc = trace_rounds(sc, tp, b, first_round, rounds, stats ? &total : nullptr,
+            [&](uint32_t r, uint32_t q0, uint32_t k, float *rays) {
+                round = r;
+                if (!chain_rc) fw::launch_ao_rays(stream, n_cus, ao_rays_device(&ao, r, pts, q0), k, rays);
+            },
+            [&](uint32_t q0, uint32_t k, const float *rays, const fw_hit *hits) {
+                if (chain_rc) return;
+                const uint32_t kd = k * D;
+                fw::launch_hit_surface(stream, sc->n_cus, sc->d, sc->n_mat, rays, (const float4 *)hits, kd, (float4 *)d_surf);
+                fw::launch_probe_irradiance(stream, L.g, a.vis ? &vis : nullptr, d_sh, d_pl, kd, d_surf + 8, d_surf + 4, 16, d_irr);
+                const float *d_direct = nullptr;
+                if (Ln) {
+                    fw::DDirect dd{};
+                    dd.pts = fw::DDirectPoints{d_surf + 8, d_surf + 4, nullptr, nullptr, nullptr, 16, 3};
+                    dd.lights = (const float4 *)sc->dlights.p; dd.n_lights = Ln; dd.first = 0;
+                    dd.lobe = 0; dd.face_view = 0; dd.bias = g->direct_bias;
+                    float *drays = st.ptr<float>(i_drays), *dsums = st.ptr<float>(i_dsums);
+                    fw_hit *dhits = st.ptr<fw_hit>(i_dhits);
+                    fw::launch_direct_rays(stream, n_cus, dd, kd, drays);
+                    fw_trace_params q = *tp;
+                    q.on_device = 1; q.seed = tp->seed + round; q.key_base = q0 * D * Ln;
+                    fw_stats gs{};
+                    chain_rc = trace_impl(sc, &q, drays, kd * Ln, dhits, stats ? &gs : nullptr);
+                    if (chain_rc) return;
+                    if (stats) { gs.ms_render = 0.0; stats_add(total, gs); }       // (its time lies inside the reducer's own span)
+                    if (hipMemsetAsync(dsums, 0, (size_t)kd * 32, stream) != hipSuccess) { chain_rc = fail(FW_ERR_HIP, "hipMemsetAsync failed"); return; }
+                    fw::launch_direct_reduce(stream, n_cus, dd, kd, drays, dhits, dsums);
+                    d_direct = dsums;                                             // one round: out = float(sums / 1) = sums
+                }
+                fw::launch_gather_reduce(stream, n_cus, q0, k, D, pts.ids, d_surf, d_irr, d_direct, d_sums);
+            }))
+        return rc;
+    if (chain_rc) return chain_rc;
+    if (int rc = st.download(i_sums)) return rc;
+    if (out) fw::launch_gather_resolve(stream, N, (double)((uint64_t)first_round + rounds), pts.ids, d_sums, st.ptr<float>(i_out));
+    if (int rc = st.finish()) return rc;
+    stats_finish(stats, total, wall0);
+    return FW_OK;
+}
+
 // ---- probe radiance maps (include/firework_hip.h) ------------------------------------------------------------------
 // A radiance description's own argument checks (FW_ERR_BAD_ARG only) and what the kernels need of it
 int probe_radiance_check(const fw_probe_radiance *pr, fw::DProbeRadiance &d) {
@@ -6020,6 +6188,30 @@ int fw_bake_direct(fw_scene *scene, const fw_direct *direct, const fw_trace_para
     try { return bake_direct_impl(scene, direct, tp, n, positions, normals, stride_floats, ids, view, view_stride_floats, spec, first_round, rounds, sums, out, stats); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_direct"); }
+}
+
+int fw_hit_surface(fw_scene *scene, const float *rays, const fw_hit *hits, uint32_t n, float *surface, int on_device, void *stream) {
+    try { return hit_surface_impl(scene, rays, hits, n, surface, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_hit_surface"); }
+}
+
+int fw_gather_reduce(int device, uint32_t directions, uint32_t n, const uint32_t *ids, const float *surface, const float *irradiance,
+                     const float *direct, float *sums, int on_device, void *stream) {
+    try { return gather_reduce_impl(device, directions, n, ids, surface, irradiance, direct, sums, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_gather_reduce"); }
+}
+
+int fw_bake_gather(fw_scene *scene, const fw_gather *g, const fw_trace_params *tp, const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd,
+                   const float *moments, float normal_bias, const float *placement, uint32_t n, const float *positions, const float *normals,
+                   uint32_t stride_floats, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    try {
+        return bake_gather_impl(scene, g, tp, grid, sh, pd, moments, normal_bias, placement, n, positions, normals, stride_floats, ids, first_round, rounds,
+                                sums, out, stats);
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_gather"); }
 }
 
 int fw_check_sky(const fw_sky *sky) {

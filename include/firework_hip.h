@@ -1675,6 +1675,101 @@ int fw_selftest_emitter_sample(fw_scene *scene, const float *x, uint32_t n, uint
 #define FW_GGX_OUT_FLOATS 11
 int fw_selftest_ggx(int device, uint32_t n, const float *in, float *out);
 
+/* ---- final gather: gather rays lit from baked probes (additive at ABI 8) ------------------------------------------------
+   The classic consumer of an irradiance cache.  A probe lookup at the receiver cannot change faster than the probe spacing; one bounce of
+   cosine-weighted gather rays from the receiver can: each ray brings back the emission of the emitter it hit, the environment where it
+   missed, or hit albedo x E(hit point) / pi with E read from the probes at the hit, where the probes' blur no longer shows.  Three calls:
+   fw_hit_surface evaluates the material at a caller's hits (what fw_trace_rays leaves out), fw_gather_reduce sums the rays' radiance per
+   receiver, fw_bake_gather chains rays, trace, surface, probe lookup, optionally the delta lights and the reduction.  api.surface_facing,
+   api.gather_reduce and api.gather_resolve are the numpy statements.
+     Surface record (fw_hit_surface, k_hit_surface): 16 floats (64 B) per ray,
+           (albedo.xyz, kind) (facing normal.xyz, distance) (position.xyz, 0) (emitted.xyz, 0):
+         the normal at floats 4..6 and the position at floats 8..10 as in fw_render_aovs' records, so every point reader reads them in place
+         with stride 16.  All arithmetic is IEEE float32 without contraction; len(v) = sqrt((x x + y y) + z z).
+         - A ray with a non-finite component or an all-zero direction — fw_trace_rays never traces it: kind = -2, every other float 0.
+         - A miss (object == FW_NO_HIT): kind = -1, emitted = the environment along d / len(d), not clamped; every other float 0.
+         - A hit whose material is not below the scene's material count, or whose object is not below its object count: kind = -2, every
+           other float 0.  No load leaves the scene's tables, whatever the hit records hold.
+         - A hit: kind = the material's kind (FW_MAT_*, 0..5) as a float.  albedo: the texture at (u, v, point) for Lambertian and
+           Isotropic, the albedo for Metal, F0 for FW_MAT_GGX, (1, 1, 1) for Dielectric, (0, 0, 0) for Emissive, which never scatters.
+           emitted: the texture at (u, v, point) for Emissive, not clamped; 0 otherwise.  distance = t x len(d); position = point;
+           normal = n / len(n) with n the hit's normal as stored, (0, 0, 0) if that length is 0, negated when (nx dx + ny dy) + nz dz > 0:
+           it faces the side the ray arrived from.
+     Reduction of one round (fw_gather_reduce, k_gather_reduce): float64 from the float32 inputs, every operation rounded as written.  For
+         ray j of point q with its surface record s, the irradiance E at it (3 floats) and, with `direct`, the record Ed (fw_bake_direct's
+         out, 8 floats, floats 0..2 read): kind -2 contributes nothing; kind -1 L = s.emitted and sky += 1; kind 3 (Emissive) L =
+         s.emitted; any other kind T_c = (E_c > 0 ? E_c : 0) (+ Ed_c with direct) and L_c = (s.albedo_c x T_c) x (1 / pi), 1 / pi the
+         float64 quotient.  Four float64 accumulators (L.rgb, sky) in k_ao_reduce's order: with G = the smallest power of two >= min(D, 64),
+         partial sum l takes j = l, l + G, ... in ascending order from 0, and the G partial sums are added by an xor butterfly over the
+         distances G/2 ... 1 (x_l <- x_l + x_(l xor m)).  L is multiplied by the float64 pi / D — the rays are cosine-weighted, so the
+         receiver's irradiance is pi times the mean radiance — and sky by the float64 1 / D; each is rounded to float32 once and added with
+         one float32 addition to sums[id] = (Er, Eg, Eb, sky), indexed by id as fw_ao_reduce indexes its own.  No atomics; two runs are
+         bit-equal; a point's result depends on no other point.
+     Resolve (k_gather_resolve), R = the number of rounds in sums: out[id] = float((double)sums[id] / R) for the four floats.  An unusable
+         point resolves to zeros. */
+
+/* fw_hit_surface: the surface records of n rays and the hits fw_trace_rays wrote for them on this scene.  rays n x 6 floats, hits n
+   records, surface n x 16 floats; host arrays — staged through one device allocation of the call's own, freed on every path — or with
+   on_device device arrays on the scene's device, evaluated on `stream` (which waits for the scene's upload) and complete on return.
+   Errors, in fw_trace_rays' pattern and before the scene is looked at: FW_ERR_BAD_ARG for a NULL scene; n == 0 returns FW_OK and writes
+   nothing; FW_ERR_BAD_ARG for NULL rays, hits or surface, rays not 4-byte aligned, with on_device hits or surface not 16-byte aligned;
+   then FW_ERR_NO_DEVICE. */
+int fw_hit_surface(fw_scene *scene, const float *rays, const fw_hit *hits, uint32_t n, float *surface, int on_device, void *stream);
+
+/* fw_gather_reduce: adds one round's reduction to the running sums.  surface: n x D records; irradiance: n x D x 3 floats, the probe
+   lookup at those records; direct: n x D x 8 floats or NULL; sums: records of 16 B indexed by id.  Host or device arrays as fw_ao_reduce.
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL surface, irradiance or sums; directions outside 1..2^20;
+   n == 0; with on_device sums or surface not 16-byte aligned, irradiance, direct or ids not 4-byte aligned; FW_ERR_UNSUPPORTED for
+   n x D >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last one. */
+int fw_gather_reduce(int device, uint32_t directions, uint32_t n, const uint32_t *ids, const float *surface, const float *irradiance,
+                     const float *direct, float *sums, int on_device, void *stream);
+
+#define FW_GATHER_DIRECT 1u   /* add the scene's point, spot and directional lights at the gather hits */
+typedef struct fw_gather {
+    uint32_t directions;     /* D, 1..2^20 */
+    uint32_t jitter;         /* fw_ao's */
+    float    bias;           /* gather-ray origin offset along the receiver's normal, >= 0, finite */
+    float    direct_bias;    /* fw_direct.bias for the shadow rays at the gather hits */
+    uint32_t flags;          /* FW_GATHER_DIRECT */
+    uint32_t chunk_points;   /* 0: as many as fit 256 MiB at this call's bytes per ray (148, plus Ln x 72 + 64 with direct), at least one */
+    uint64_t seed;
+} fw_gather;
+
+/* fw_bake_gather: the rounds [first_round, first_round + rounds) of the n points against a resident scene and a baked probe grid.  Points,
+   ids, sums, out, first_round / rounds and what is read of tp are fw_bake_ao's.  For each round r and each chunk of points [q0, q1)
+   (chunk_points at a time), in device scratch that the call allocates and frees on every path:
+     1. k_ao_rays with fw_ao{D, falloff 0, radius +inf, bias, jitter, seed}: fw_ao_rays' rays bit for bit;
+     2. the trace, as fw_bake_ao runs it: on_device, seed = tp->seed + r, key_base = q0 D;
+     3. k_hit_surface over the chunk's rays and hits;
+     4. the probe lookup at the records read in place (stride 16, positions = rec + 8, normals = rec + 4): with placement
+        fw_probe_irradiance_placed's (pd and moments both NULL: without visibility), else with pd fw_probe_irradiance_vis', else
+        fw_probe_irradiance's — the bits of that public call on those records;
+     5. with FW_GATHER_DIRECT on a scene that has lights (Ln of them): fw_bake_direct's kernels, one round, over the same records — lobe 0,
+        face_view 0, bias = direct_bias, no ids, view or spec — the shadow rays traced after the gather rays' trace has returned, with
+        seed = tp->seed + r and a key base that gives entry e = q D + j (q counted in the whole call) and light i the key e Ln + i: what
+        fw_bake_direct gives when called by hand over all n D records with tp->seed + r, whatever the chunking.  Without the flag or
+        without lights the step does not run and the reduction reads no direct records;
+     6. k_gather_reduce into sums.
+   After the last round k_gather_resolve writes out.  On an error the stream is drained.
+     sums: the running sums (Er, Eg, Eb, sky) of the rounds [0, first_round), NULL only when first_round == 0;  out: sums / rounds so far:
+           the irradiance gathered at the point and the share of its rays that saw the environment; may be NULL.
+   Contracts.  Composition: for every chunk_points, sums equals bit for bit what the public calls give when chained by hand over all n
+   points: fw_ao_rays, fw_trace_rays, fw_hit_surface, the lookup, (fw_bake_direct,) fw_gather_reduce.  Progressive: k calls of m rounds
+   leave the sums and out of one call of k m rounds, bit for bit.  Renders, and the frame graph's key, are left as fw_trace_rays leaves
+   them.
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, g, tp, positions or normals;
+   directions outside 1..2^20, a bias or direct_bias negative or not finite; n == 0; stride_floats < 3; rounds == 0; first_round + rounds
+   >= 2^32; a NULL sums with first_round > 0; with on_device sums or out not 16-byte aligned, positions, normals or ids not 4-byte
+   aligned; then fw_probe_irradiance_placed's checks of grid, sh, pd, moments, normal_bias and (with on_device) the tables' alignment;
+   unknown flag bits; FW_ERR_UNSUPPORTED for n x D >= 2^31 and the tables' sizes; then FW_ERR_NO_DEVICE; then — Ln is the scene's —
+   FW_ERR_UNSUPPORTED for n x D x Ln >= 2^31.
+   stats (may be NULL): fw_bake_ao's, summed over both traces; the shadow rays' trace lies inside the reduction's span of ms_render (and
+   of ms_accumulate under FW_FLAG_TIME_KERNELS).  Synchronisation and what a trace leaves of renders are fw_trace_rays'. */
+int fw_bake_gather(fw_scene *scene, const fw_gather *g, const fw_trace_params *tp,
+                   const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias, const float *placement,
+                   uint32_t n, const float *positions, const float *normals, uint32_t stride_floats, const uint32_t *ids,
+                   uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
