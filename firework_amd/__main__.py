@@ -76,7 +76,13 @@ that holds radiance maps and refuse --probe-no-radiance).
 cosine-weighted gather rays per pixel and round, default 1 round, origins moved B >= 0, default 0.001, along the normal; a ray that hits
 an emitter brings its emission, one that misses the environment: contact shadows, near-field colour bleeding and directly seen emitters
 from the same probes file, fw_bake_gather; with --direct-light the lights are added at the gather hits as well; refuses
---ao, --probe-split-sum and a file's radiance maps in use: pass --probe-no-radiance)."""
+--ao, --probe-split-sum and a file's radiance maps in use: pass --probe-no-radiance).
+--probe-lit FILE --probe-reflect D[,ROUNDS] [--reflect-bias B] (traced reflections on GgxMat and MetalMat pixels: D reflection rays per
+glossy pixel and round, default 1 round, drawn from the GGX lobe around the view direction, origins moved B >= 0, default 0.001, along
+the normal, lit at their hits as gather rays are and summed with the weight F G2 / G1: parallax-correct reflections with the split sum's
+BRDF term and no radiance maps, fw_bake_reflect; every other pixel is shaded as without the flag, --probe-gather
+included; with --direct-light the lights are added at the reflection rays' hits as well; refuses --ao, --probe-split-sum and a file's
+radiance maps in use: pass --probe-no-radiance)."""
 import argparse
 import sys
 import time
@@ -183,7 +189,29 @@ def main(argv=None):
                     help="with --probe-lit: read the probes one bounce away, at the hits of D gather rays per pixel and round (default 1 round)")
     ap.add_argument("--gather-bias", type=float, default=None, metavar="B",
                     help="with --probe-gather: move gather-ray origins B >= 0 world units along the normal (default 0.001)")
+    ap.add_argument("--probe-reflect", default=None, metavar="D[,ROUNDS]",
+                    help="with --probe-lit: trace D GGX-sampled reflection rays per glossy pixel and round (default 1 round), lit from the probes at their hits")
+    ap.add_argument("--reflect-bias", type=float, default=None, metavar="B",
+                    help="with --probe-reflect: move reflection-ray origins B >= 0 world units along the normal (default 0.001)")
     opt = ap.parse_args(argv)
+    reflect = None
+    if opt.probe_reflect is not None:
+        if opt.probe_lit is None:
+            ap.error("--probe-reflect needs --probe-lit")
+        if opt.ao is not None:
+            ap.error("--probe-reflect cannot be combined with --ao: the ambient-occlusion frame has no specular term")
+        if opt.probe_split_sum is not None:
+            ap.error("--probe-reflect cannot be combined with --probe-split-sum: the reflection rays' weights carry that term already")
+        try:
+            reflect = [int(x) for x in opt.probe_reflect.split(",")]
+        except ValueError:
+            reflect = []
+        if not 1 <= len(reflect) <= 2 or not 1 <= reflect[0] <= 1 << 20 or (len(reflect) == 2 and reflect[1] < 1):
+            ap.error("--probe-reflect needs D[,ROUNDS]: 1 <= D <= 2^20, ROUNDS >= 1")
+        if opt.reflect_bias is not None and not 0.0 <= opt.reflect_bias < float("inf"):
+            ap.error("--reflect-bias B needs a finite B >= 0")
+    elif opt.reflect_bias is not None:
+        ap.error("--reflect-bias needs --probe-reflect")
     gather = None
     if opt.probe_gather is not None:
         if opt.probe_lit is None:
@@ -480,6 +508,8 @@ def main(argv=None):
                 raise ValueError(f"radiance has shape {probe_maps.shape}, the grid {probe_grid.n_probes} probes of {probe_radiance.texels} texels")
             if gather is not None and probe_radiance is not None:
                 raise ValueError("--probe-gather cannot be combined with the radiance maps the file holds: pass --probe-no-radiance")
+            if reflect is not None and probe_radiance is not None:
+                raise ValueError("--probe-reflect cannot be combined with the radiance maps the file holds: pass --probe-no-radiance")
             if split_sum is not None and probe_radiance is None:
                 raise ValueError("--probe-split-sum needs radiance maps and the file holds none (bake it with --probe-radiance R)")
         except (OSError, ValueError, zipfile.BadZipFile) as e:
@@ -547,10 +577,15 @@ def main(argv=None):
         if gather is not None:
             from .api import FinalGather
             final_gather = FinalGather(gather[0], 1e-3 if opt.gather_bias is None else opt.gather_bias).seed(opt.seed)
+        reflection = None
+        if reflect is not None:
+            from .api import ReflectionGather
+            reflection = ReflectionGather(reflect[0]).bias(1e-3 if opt.reflect_bias is None else opt.reflect_bias).seed(opt.seed)
         render = renderer.render_probe_lit(scene, probe_grid, probe_sh, opt.aov_samples, device=opt.device, depth=probe_depth, moments=probe_moments,
                                            normal_bias=0.0 if opt.probe_normal_bias is None else opt.probe_normal_bias,
                                            placement=probe_placement, radiance=probe_radiance, maps=probe_maps, direct=direct_light(opt),
-                                           ggx_table=ggx_table, gather=final_gather, gather_rounds=gather[1] if gather and len(gather) == 2 else 1).rgb8
+                                           ggx_table=ggx_table, gather=final_gather, gather_rounds=gather[1] if gather and len(gather) == 2 else 1,
+                                           reflect=reflection, reflect_rounds=reflect[1] if reflect and len(reflect) == 2 else 1).rgb8
         print(f"Finished Rendering in {int(time.time() - start)} s")
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)

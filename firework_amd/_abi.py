@@ -259,6 +259,25 @@ GATHER_PROTOTYPES = {
 }
 
 
+# reflection gather (include/firework_hip.h: fw_reflect_rays, fw_reflect_reduce, fw_bake_reflect)
+FW_REFLECT_DIRECT = 1
+
+
+class fw_reflect(C.Structure):
+    _fields_ = [("directions", u32), ("jitter", u32), ("bias", f32), ("direct_bias", f32), ("flags", u32), ("chunk_points", u32), ("seed", u64)]
+
+
+# the three prototypes (argument types; every one returns int), applied by _lib.load
+REFLECT_PROTOTYPES = {
+    "fw_reflect_rays": [C.POINTER(fw_reflect), C.c_int, u32, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p,
+                        C.c_void_p, C.c_int, C.c_void_p],
+    "fw_reflect_reduce": [C.c_int, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_bake_reflect": [C.c_void_p, C.POINTER(fw_reflect), C.POINTER(fw_trace_params), C.POINTER(fw_probe_grid), C.c_void_p, C.POINTER(fw_probe_depth),
+                        C.c_void_p, f32, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p,
+                        C.c_void_p, C.POINTER(fw_stats)],
+}
+
+
 # SunSky: an analytic sun-and-sky environment (include/firework_hip.h: fw_check_sky, fw_sky_map, fw_sky_radiance, fw_sky_sun)
 FW_SKY_DISC = 1
 

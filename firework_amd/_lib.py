@@ -133,7 +133,7 @@ def load(preload=False, device=None):
                                    C.c_void_p]
     for name, argtypes in (list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()) + list(A.PROBE_PLACE_PROTOTYPES.items())
                            + list(A.PROBE_RADIANCE_PROTOTYPES.items()) + list(A.DIRECT_PROTOTYPES.items()) + list(A.SKY_PROTOTYPES.items())
-                           + list(A.GGX_TABLE_PROTOTYPES.items()) + list(A.GATHER_PROTOTYPES.items())):
+                           + list(A.GGX_TABLE_PROTOTYPES.items()) + list(A.GATHER_PROTOTYPES.items()) + list(A.REFLECT_PROTOTYPES.items())):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
@@ -1092,6 +1092,49 @@ def gather_reduce(surface, irradiance, directions, sums, direct=None, ids=None, 
     return sums
 
 
+def reflect_rays(reflect, positions, normals, view, spec, ids=None, round=0, device=0, out=None, weights=None, stream=None):
+    """fw_reflect_rays: the reflection rays of round `round` of an api.ReflectionGather at glossy surface points (see _DirectPoints;
+    view and spec are required), generated on the device: (rays (n * D, 6) float32 origin + direction, weights (n * D, 2) float32
+    (g, s)), entry q * D + j = ray j of point ids[q] (ids None: q).  numpy points: returns numpy arrays.  Points on cuda:`device`:
+    generated on `stream` (default: the current torch stream) where they lie; returns device tensors.  out, weights: contiguous
+    float32 arrays or tensors of those shapes to fill instead."""
+    lib = load()
+    g = reflect.to_abi()
+    if view is None or spec is None:
+        raise ValueError("reflection rays need view and spec")
+    pts = _DirectPoints(positions, normals, ids, view, spec, device)
+    s = pts.side
+    total = pts.n * int(g.directions)
+    out, weights = s.out(out, (total, 6), "out"), s.out(weights, (total, 2), "weights")
+    _check(lib, lib.fw_reflect_rays(C.byref(g), int(device), int(round), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride,
+                                    pts.spec, *s.ptrs(out, weights), *s.tail(stream)))
+    return out, weights
+
+
+def reflect_reduce(surface, irradiance, weights, directions, sums, direct=None, ids=None, device=0, stream=None):
+    """fw_reflect_reduce: adds one round's reduction (P.rgb, alive, Q.rgb, sky, each rounded to float32 once) of a reflection gather to
+    sums[ids[q]] (ids None: sums[q]); sums (M, 8) or (H, W, 8) float32, updated in place.  surface, irradiance and direct as
+    gather_reduce takes them, weights (n * D, 2) float32 as reflect_rays returns them: numpy arrays, or tensors on cuda:`device`,
+    reduced on `stream` (default: the current torch stream) where they lie; ids n distinct ids (uint32 numpy / int32 torch).
+    Returns sums."""
+    lib = load()
+    d = int(directions)
+    total = int(surface.shape[0])
+    if d < 1 or total % d or tuple(surface.shape) != (total, 16):
+        raise ValueError(f"surface must have shape (n * {d}, 16)")
+    n = total // d
+    m = int(np.prod(tuple(sums.shape)[:-1]))
+    if sums.shape[-1] != 8 or (ids is None and m < n) or (ids is not None and tuple(ids.shape) != (n,)):
+        raise ValueError(f"sums must have shape (M, 8) or (H, W, 8) with M >= {n}, ids shape ({n},)")
+    s = _Side(surface, device)
+    rec, e, ed = s.inp(surface, (total, 16), "surface"), s.inp(irradiance, (total, 3), "irradiance"), s.inp(direct, (total, 8), "direct")
+    w = s.inp(weights, (total, 2), "weights")
+    s.out(sums, tuple(sums.shape), "sums")
+    i = s.inp(ids, (n,), "ids", "ids", below=m)
+    _check(lib, lib.fw_reflect_reduce(int(device), d, n, *s.ptrs(i, rec, e, ed, w, sums), *s.tail(stream)))
+    return sums
+
+
 def _sky_abi(sky):
     """a fw_sky from an api.SunSky (or a fw_sky, copied)"""
     return sky.to_abi() if hasattr(sky, "to_abi") else A.fw_sky.from_buffer_copy(sky)
@@ -1524,9 +1567,11 @@ class DeviceScene:
                                                        survey.ctypes.data, C.byref(st)))
         return placement, survey, st.as_dict()
 
-    def _bake_points(self, fn, desc, pts, floats, head, rounds, first_round, sums, out, seed, use_bvh, stream, rays_per_batch, flags):
-        """what bake_ao and bake_direct share: the bound C function `fn` over its description `desc`, the points `pts` with the arguments
-        `head` that state them, and sums and out of `floats` floats per point (None: zeros).  Returns (out, sums, stats)."""
+    def _bake_points(self, fn, desc, pts, floats, head, rounds, first_round, sums, out, seed, use_bvh, stream, rays_per_batch, flags, out_floats=None):
+        """what the point bakers share: the bound C function `fn` over its description `desc`, the points `pts` with the arguments
+        `head` that state them, and sums of `floats` and out of `out_floats` (None: `floats`) floats per point (None: zeros).  Returns
+        (out, sums, stats)."""
+        out_floats = floats if out_floats is None else out_floats
         p = A.fw_trace_params()
         p.use_bvh, p.flags, p.seed, p.rays_per_batch = int(bool(use_bvh)), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rays_per_batch)
         st = A.fw_stats()
@@ -1534,9 +1579,9 @@ class DeviceScene:
             raise ValueError("first_round > 0 needs the sums of the rounds before it")
         pts.side.params(p, stream)
         sums = pts.side.new((pts.m, floats), fill=0.0) if sums is None else sums
-        out = pts.side.new((pts.m, floats), fill=0.0) if out is None else out
+        out = pts.side.new((pts.m, out_floats), fill=0.0) if out is None else out
         _check(self._lib, fn(self.handle, C.byref(desc), C.byref(p), *head, int(first_round), int(rounds), pts.records(sums, "sums", floats),
-                             pts.records(out, "out", floats), C.byref(st)))
+                             pts.records(out, "out", out_floats), C.byref(st)))
         return out, sums, st.as_dict()
 
     def bake_ao(self, ao, positions, normals, ids=None, rounds=1, first_round=0, sums=None, out=None, seed=0, use_bvh=True, stream=None,
@@ -1590,6 +1635,30 @@ class DeviceScene:
                 pts.n, pts.pos, pts.nrm, pts.stride, pts.ids)
         return self._bake_points(self._lib.fw_bake_gather, g, pts, 4, head, rounds, first_round, sums, out, seed, use_bvh, stream, rays_per_batch,
                                  flags)
+
+    def bake_reflect(self, reflect, grid, sh, positions, normals, view, spec, ids=None, depth=None, moments=None, normal_bias=0.0, placement=None,
+                     rounds=1, first_round=0, sums=None, out=None, seed=0, use_bvh=True, stream=None, rays_per_batch=0, flags=0, chunk=None):
+        """fw_bake_reflect: the rounds [first_round, first_round + rounds) of an api.ReflectionGather at glossy surface points (see
+        _DirectPoints: numpy arrays, or tensors on this scene's device, read in place; view (M, 3) and spec (M, 4) are required)
+        against this scene and the baked probes (grid, sh; depth + moments: the visibility weight; placement: moved and classified
+        probes), `chunk` points at a time (None: the description's own setting; 0: automatic).  sums: (M, 8) or (H, W, 8) float32
+        running sums (P.rgb, alive, Q.rgb, sky) of the rounds before first_round, updated in place (None: zeros, only with first_round
+        0); out: (M, 4) or (H, W, 4) float32 to receive (S.rgb, alive) (None: zeros); both are indexed by id, entries outside ids are
+        not touched.  Returns (out, sums, stats): host arrays for numpy points, device tensors — baked on `stream` (default: the
+        current torch stream) — for device points."""
+        g = reflect.to_abi()
+        if chunk is not None:
+            g.chunk_points = int(chunk)
+        if view is None or spec is None:
+            raise ValueError("a reflection gather needs view and spec")
+        pts = _DirectPoints(positions, normals, ids, view, spec, self.device)
+        s = pts.side
+        gr, n_probes = _grid_abi(grid)
+        vis = _vis_of(depth, moments, normal_bias)
+        head = (C.byref(gr), s.ptr(s.inp(sh, (n_probes, 9, 3), "sh")), *_vis_args(s, vis, n_probes), _placement_arg(s, placement, n_probes),
+                pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride, pts.spec)
+        return self._bake_points(self._lib.fw_bake_reflect, g, pts, 8, head, rounds, first_round, sums, out, seed, use_bvh, stream, rays_per_batch,
+                                 flags, out_floats=4)
 
     def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,
                       flags=0, chunk=None, on_device=False):

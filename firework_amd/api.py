@@ -3063,6 +3063,203 @@ def gather_resolve(sums, rounds: int) -> np.ndarray:
         return (np.asarray(sums, np.float32).astype(np.float64) / float(rounds)).astype(np.float32)
 
 
+# --------------------------------------------------------------------------- reflection gather (fw_bake_reflect)
+class ReflectionGather:
+    """GGX-sampled reflection rays lit from baked probes (fw_reflect): `directions` rays per glossy point and round, drawn
+    from the visible-normal lobe of the point's (F0, rho) around its view direction, origins moved `bias` along the normal facing the
+    eye; each ray brings back what a gather ray brings back (FinalGather) and is summed with the estimator's weight F G2 / G1.
+    .direct_bias(b) adds the scene's point, spot and directional lights at the hits, their shadow rays moved b along the hit's normal
+    (.direct_bias(None) takes them out again).  .bias(b) / .seed(s) / .jitter(on) as builders; chunk_points as fw_reflect's."""
+
+    def __init__(self, directions: int = 16):
+        self.directions = int(directions)
+        self._bias, self.direct, self._direct_bias = float(np.float32(1e-3)), False, float(np.float32(1e-3))
+        self._seed, self._jitter, self.chunk_points = 0, True, 0
+
+    def bias(self, b):
+        self._bias = float(np.float32(b))
+        return self
+
+    def direct_bias(self, b):
+        self.direct = b is not None
+        if b is not None:
+            self._direct_bias = float(np.float32(b))
+        return self
+
+    def seed(self, s):
+        self._seed = int(s)
+        return self
+
+    def jitter(self, on=True):
+        self._jitter = bool(on)
+        return self
+
+    def check(self):
+        """what fw_bake_reflect rejects in a description, as a ValueError, in its order"""
+        if not 1 <= self.directions <= 1 << 20:
+            raise ValueError("directions must be in 1..2^20")
+        if not (np.isfinite(self._bias) and self._bias >= 0.0):
+            raise ValueError("bias must be finite and >= 0")
+        if not (np.isfinite(self._direct_bias) and self._direct_bias >= 0.0):
+            raise ValueError("direct_bias must be finite and >= 0")
+        return self
+
+    def to_abi(self) -> A.fw_reflect:
+        g = A.fw_reflect()
+        g.directions, g.jitter, g.bias, g.direct_bias = self.directions & 0xFFFFFFFF, int(self._jitter), self._bias, self._direct_bias
+        g.flags, g.chunk_points, g.seed = (A.FW_REFLECT_DIRECT if self.direct else 0), int(self.chunk_points), self._seed & 0xFFFFFFFFFFFFFFFF
+        return g
+
+
+def reflect_usable(positions, normals, view, spec) -> np.ndarray:
+    """(M,) bool: the points fw_reflect_rays generates rays for — position, normal and view finite, normal and view other than
+    (0, 0, 0), rho = spec[:, 3] finite and > 0"""
+    p, n = np.asarray(positions, np.float32).reshape(-1, 3), np.asarray(normals, np.float32).reshape(-1, 3)
+    v, rho = np.asarray(view, np.float32).reshape(-1, 3), np.asarray(spec, np.float32).reshape(-1, 4)[:, 3]
+    with np.errstate(all="ignore"):
+        return (np.all(np.isfinite(p), axis=1) & np.all(np.isfinite(n), axis=1) & np.all(np.isfinite(v), axis=1) & np.any(n != 0, axis=1)
+                & np.any(v != 0, axis=1) & np.isfinite(rho) & (rho > 0))
+
+
+def reflect_rays(reflect: "ReflectionGather", positions, normals, view, spec, ids=None, round: int = 0, device=None, terms: bool = False):
+    """The numpy float64 statement of fw_reflect_rays: (rays (n * D, 6) float32, weights (n * D, 2) float32), entry q * D + j = ray j of
+    point id = ids[q] (ids None: q) of positions, normals, view, (M, 3) float32 each, and spec (M, 4) float32 (F0.rgb, rho); weights =
+    (g, s) with g = G2 / G1 and s = (1 - wo.h)^5 (device: see panorama_rays; it moves the rays only).  An unusable point
+    (reflect_usable) gets D all-zero rays and weights, a dead ray (wi.z <= 0 or wo.z <= 0 in the point's frame) the same.  terms=True:
+    also a dict with the float64 "wi_z" and "wo_z" (n, D) of every ray and "usable" (n,)."""
+    D = reflect.directions
+    if D < 1:
+        raise ValueError("directions must be >= 1")
+    P, Nn = np.asarray(positions, np.float32).reshape(-1, 3), np.asarray(normals, np.float32).reshape(-1, 3)
+    V, Sp = np.asarray(view, np.float32).reshape(-1, 3), np.asarray(spec, np.float32).reshape(-1, 4)
+    ids = np.arange(P.shape[0], dtype=np.uint32) if ids is None else np.asarray(ids, np.uint32).reshape(-1)
+    at = ids.astype(np.int64)
+    p32, n32, v32, rho32 = P[at], Nn[at], V[at], Sp[at, 3]
+    ok = reflect_usable(p32, n32, v32, Sp[at])
+    xi = texel_jitter(reflect._seed, round, ids) if reflect._jitter else np.full((ids.size, 2), 0.5)
+    j = np.arange(D, dtype=np.float64)[None, :]
+    with np.errstate(all="ignore"):
+        xi1 = (j + xi[:, 0:1]) / float(D)
+        t = j * ((np.sqrt(5.0) - 1.0) / 2.0) + xi[:, 1:2]
+        xi2 = t - np.floor(t)
+        alpha = (rho32 * rho32).astype(np.float64)[:, None]                                  # the float32 product, widened
+        a2 = alpha * alpha
+        # the frame: the normal made unit in float64, wo = -view / |view|, the normal flipped towards wo, Duff's basis
+        r, vw = n32.astype(np.float64), v32.astype(np.float64)
+        rl = np.sqrt((r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]) + r[:, 2] * r[:, 2])
+        vl = np.sqrt((vw[:, 0] * vw[:, 0] + vw[:, 1] * vw[:, 1]) + vw[:, 2] * vw[:, 2])
+        nx, ny, nz = r[:, 0] / rl, r[:, 1] / rl, r[:, 2] / rl
+        wx, wy, wz = -(vw[:, 0] / vl), -(vw[:, 1] / vl), -(vw[:, 2] / vl)
+        away = (wx * nx + wy * ny) + wz * nz < 0.0
+        nx, ny, nz = np.where(away, -nx, nx), np.where(away, -ny, ny), np.where(away, -nz, nz)
+        s = np.copysign(1.0, nz)
+        a = -1.0 / (s + nz)
+        b = (nx * ny) * a
+        T = (1.0 + (s * (nx * nx)) * a, s * b, -s * nx)
+        B = (b, s + (ny * ny) * a, -ny)
+        Nv = (nx, ny, nz)
+        ox = ((wx * T[0] + wy * T[1]) + wz * T[2])[:, None]
+        oy = ((wx * B[0] + wy * B[1]) + wz * B[2])[:, None]
+        oz = ((wx * nx + wy * ny) + wz * nz)[:, None]
+        # the visible normal of Heitz 2018 for this wo
+        vx, vy = alpha * ox, alpha * oy
+        vlen = np.sqrt((vx * vx + vy * vy) + oz * oz)
+        vhx, vhy, vhz = vx / vlen, vy / vlen, oz / vlen
+        l2 = vhx * vhx + vhy * vhy
+        il = 1.0 / np.sqrt(np.where(l2 > 0.0, l2, 1.0))
+        t1x, t1y = np.where(l2 > 0.0, -vhy * il, 1.0), np.where(l2 > 0.0, vhx * il, 0.0)
+        t2x, t2y, t2z = -(vhz * t1y), vhz * t1x, vhx * t1y - vhy * t1x
+        sh = 0.5 * (1.0 + vhz)
+        lo1 = 1.0 + 0.5 * (np.sqrt(1.0 + a2 * ((ox * ox + oy * oy) / (oz * oz))) - 1.0)
+        rr = np.sqrt(xi1)
+        phi = (2.0 * np.pi) * xi2
+        p1 = rr * np.cos(phi)
+        q1 = 1.0 - p1 * p1
+        p2 = (1.0 - sh) * np.sqrt(np.fmax(q1, 0.0)) + sh * (rr * np.sin(phi))
+        pz = np.sqrt(np.fmax(q1 - p2 * p2, 0.0))
+        nhx, nhy, nhz = (p1 * t1x + p2 * t2x) + pz * vhx, (p1 * t1y + p2 * t2y) + pz * vhy, p2 * t2z + pz * vhz
+        gx, gy, gz = alpha * nhx, alpha * nhy, np.fmax(nhz, 0.0)
+        hl = np.sqrt((gx * gx + gy * gy) + gz * gz)
+        hx, hy, hz = gx / hl, gy / hl, gz / hl
+        oh = (ox * hx + oy * hy) + oz * hz
+        t2 = 2.0 * oh
+        ix, iy, iz = t2 * hx - ox, t2 * hy - oy, t2 * hz - oz
+        alive = (iz > 0.0) & (oz > 0.0) & ok[:, None]
+        zz, xy = np.where(alive, iz, 1.0), np.where(alive, ix * ix + iy * iy, 0.0)
+        li = 0.5 * (np.sqrt(1.0 + a2 * (xy / (zz * zz))) - 1.0)
+        g = lo1 / (lo1 + li)
+        m = np.fmax(1.0 - oh, 0.0)
+        sw = ((m * m) * (m * m)) * m
+        d = np.stack([(ix * T[k][:, None] + iy * B[k][:, None]) + iz * Nv[k][:, None] for k in range(3)], axis=-1)
+        nrm = np.stack(Nv, axis=-1)
+        o = p32.astype(np.float64) + float(F32(reflect._bias)) * nrm
+        o = np.broadcast_to(o[:, None, :], d.shape)
+    d = np.where(alive[..., None], d, 0.0).reshape(-1, 3)
+    o = np.where(alive[..., None], o, 0.0).reshape(-1, 3)
+    w = np.where(alive[..., None], np.stack([g, sw], axis=-1), 0.0).reshape(-1, 2).astype(np.float32)
+    rays = _rays_out(o, d, device)
+    if terms:
+        return rays, w, {"wi_z": np.where(ok[:, None], iz, np.nan), "wo_z": np.where(ok[:, None], np.broadcast_to(oz, iz.shape), np.nan), "usable": ok}
+    return rays, w
+
+
+def reflect_reduce(surface, irradiance, weights, directions: int, direct=None) -> np.ndarray:
+    """The numpy float64 statement of fw_reflect_reduce: (n, 8) float64, (1 / D) x the accumulators (P.rgb, alive, Q.rgb, sky) of one
+    round before their one rounding to float32, for surface (n * D, 16) float32 records, irradiance (n * D, 3) float32, weights
+    (n * D, 2) float32 (g, s) and direct (n * D, 8) float32 or None: per ray L as gather_reduce forms it, P += (g (1 - s)) L,
+    Q += (g s) L, alive += [g > 0], sky += [kind == -1], summed in the device's order (G partial sums, an xor butterfly)."""
+    D = int(directions)
+    s = np.asarray(surface, np.float32).astype(np.float64).reshape(-1, D, 16)
+    E = np.asarray(irradiance, np.float32).astype(np.float64).reshape(-1, D, 3)
+    w = np.asarray(weights, np.float32).astype(np.float64).reshape(-1, D, 2)
+    n = s.shape[0]
+    kind = s[..., 3]
+    T = np.where(E > 0.0, E, 0.0)
+    if direct is not None:
+        T = T + np.asarray(direct, np.float32).astype(np.float64).reshape(-1, D, 8)[..., 0:3]
+    inv_pi = 1.0 / 3.141592653589793
+    with np.errstate(all="ignore"):
+        L = (s[..., 0:3] * T) * inv_pi
+        emits = (kind == -1.0) | (kind == 3.0)
+        L = np.where(emits[..., None], s[..., 12:15], L)
+        g, sw = w[..., 0:1], w[..., 1:2]
+        term = np.concatenate([(g * (1.0 - sw)) * L, (g * sw) * L, (kind == -1.0)[..., None].astype(np.float64)], axis=-1)      # (n, D, 7)
+    live = kind != -2.0
+    count = (w[..., 0] > 0.0).astype(np.float64)                                              # (counted whatever the ray's kind is)
+    G = 1
+    while G < min(D, 64):
+        G *= 2
+    rows = -(-D // G)                                                                        # lane l takes j = l, l + G, ... in ascending order
+    padded = np.zeros((n, rows * G, 7))
+    padded[:, :D] = term
+    take = np.zeros((n, rows * G), bool)
+    take[:, :D] = live
+    ones = np.zeros((n, rows * G))
+    ones[:, :D] = count
+    part, alive = np.zeros((n, G, 7)), np.zeros((n, G))
+    with np.errstate(all="ignore"):
+        for row, on, c in zip(padded.reshape(n, rows, G, 7).transpose(1, 0, 2, 3), take.reshape(n, rows, G).transpose(1, 0, 2),
+                              ones.reshape(n, rows, G).transpose(1, 0, 2)):
+            part = np.where(on[..., None], part + row, part)                                 # (a ray that contributes nothing adds nothing: -0 and NaN stay out)
+            alive = alive + c
+        m = G // 2
+        while m >= 1:
+            part, alive = part + part[:, np.arange(G) ^ m], alive + alive[:, np.arange(G) ^ m]
+            m //= 2
+        inv = 1.0 / D
+        return np.concatenate([inv * part[:, 0, 0:3], inv * alive[:, 0:1], inv * part[:, 0, 3:6], inv * part[:, 0, 6:7]], axis=-1)
+
+
+def reflect_resolve(sums, spec, rounds: int) -> np.ndarray:
+    """The statement of k_reflect_resolve: (..., 4) float32 (S.rgb, alive) from the float32 running sums (..., 8) = (P.rgb, alive, Q.rgb,
+    sky) of `rounds` rounds and spec (..., 4) float32 (F0.rgb, rho): S_c = float32((f0_c P_c + Q_c) / rounds), alive / rounds."""
+    s = np.asarray(sums, np.float32).astype(np.float64)
+    f0 = np.asarray(spec, np.float32).astype(np.float64).reshape(s.shape[:-1] + (4,))[..., 0:3]
+    with np.errstate(all="ignore"):
+        S = (f0 * s[..., 0:3] + s[..., 4:7]) / float(rounds)
+        return np.concatenate([S, s[..., 3:4] / float(rounds)], axis=-1).astype(np.float32)
+
+
 # --------------------------------------------------------------------------- direct light of delta lights (fw_bake_direct; DESIGN.md §9w)
 class DirectLight:
     """The direct light of a scene's point, spot and directional lights at surface points (fw_direct): one shadow ray per
@@ -3884,11 +4081,73 @@ class Renderer:
         out = out.cpu().numpy().reshape(h, w, 4)
         return out[..., 0:3], out[..., 3], sums.cpu().numpy().reshape(h, w, 4)
 
+    def _view_spec(self, ds, model, w, h, dev):
+        """(rays (N, 6), spec (N, 4)) device tensors of the glossy shades: the view's sample-0 rays (fw_camera_rays; with `model`,
+        fw_model_rays) traced by fw_trace_rays, and each hit's (F0, rho) from material_spec_table — rho = 0 for a miss"""
+        import torch
+        from . import _lib
+        s = self.settings
+        if model is not None:
+            rays = _lib.model_rays(model, 0, 1, ds.device, out=torch.empty((1, w * h, 6), dtype=torch.float32, device=dev))[0]
+        else:
+            rays = torch.from_numpy(ds.camera_rays(self, 0)).to(dev)
+        hit = _lib.hit_fields(ds.trace(rays, s["use_bvh"], seed=s["seed"]))
+        table = torch.from_numpy(material_spec_table(ds._desc)).to(dev)
+        miss = torch.full_like(hit["material"], table.shape[0] - 1)
+        return rays, table[torch.where(hit["object"] == -1, miss, hit["material"]).long()].contiguous()
+
+    def _reflect(self, ds, reflect: "ReflectionGather", rounds, grid, d_sh, aov, rays, spec, depth, d_mom, normal_bias, d_pl, direct=None):
+        """(out (N, 4), sums (N, 8)) device tensors: fw_bake_reflect on the records `aov` in place (stride 12, aov + 8 / aov + 4) with the
+        view rays[:, 3:6] and `spec`, this renderer's seed, use_bvh and flags; with `direct`, a DirectLight, FW_REFLECT_DIRECT with its
+        bias.  The call's stats are kept in self.reflect_stats."""
+        import copy
+        s = self.settings
+        g = copy.copy(reflect)
+        if direct is not None:
+            g.direct_bias(direct.bias)
+        out, sums, self.reflect_stats = ds.bake_reflect(g, grid, d_sh, aov[:, 8:11], aov[:, 4:7], rays[:, 3:6], spec, None, depth, d_mom, normal_bias,
+                                                        d_pl, rounds, seed=s["seed"], use_bvh=s["use_bvh"], flags=s["flags"])
+        return out, sums
+
+    def render_reflect(self, scene, reflect: "ReflectionGather", probes, sh, rounds: int = 1, samples: int = 1, wrap: bool = True, device: int = 0,
+                       depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0, placement=None):
+        """The radiance reflected towards this renderer's view by its glossy pixels, from baked probes (not in the reference;
+        fw_bake_reflect): the first-hit guide buffers (fw_render_aovs at `samples` samples) stay on the device, view
+        and spec are built as render_probe_lit's radiance branch builds them (the sample-0 rays traced, material_spec_table), and
+        fw_bake_reflect reads each pixel from the records in place, tracing `rounds` rounds of reflect.directions rays with this
+        renderer's seed (+ the round), use_bvh and flags; probes, sh, depth, moments, normal_bias and placement as render_probe_lit
+        takes them.  Returns (S (H, W, 3), alive (H, W), sums (H, W, 8)) float32 host arrays; a pixel that is not glossy (rho = 0) or
+        missed the scene has S 0 and alive 0.  The call's stats are kept in self.reflect_stats.  `scene`: a Scene, a SceneDesc or an
+        uploaded _lib.DeviceScene."""
+        import torch
+        from . import _lib
+        reflect.check()
+        if depth is not None and moments is None:
+            raise ValueError("depth needs the moments bake_probe_depth returned")
+        grid = ProbeGrid.of(probes, wrap)
+        s = self.settings
+        w, h = int(s["width"]), int(s["height"])
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            dev = torch.device("cuda", ds.device)
+            to = lambda a, shape: None if a is None else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).reshape(shape))).to(dev)
+            aov = torch.empty((w * h, 12), dtype=torch.float32, device=dev)
+            ds.aovs(self, samples, out=aov)
+            rays, spec = self._view_spec(ds, None, w, h, dev)
+            R = int(depth.resolution) if depth is not None else 0
+            out, sums = self._reflect(ds, reflect, rounds, grid, to(sh, (grid.n_probes, 9, 3)), aov, rays, spec, depth,
+                                      to(moments if depth is not None else None, (grid.n_probes, R, R, 2)), normal_bias, to(placement, (grid.n_probes, 4)))
+        finally:
+            if ds is not scene:
+                ds.close()
+        out = out.cpu().numpy().reshape(h, w, 4)
+        return out[..., 0:3], out[..., 3], sums.cpu().numpy().reshape(h, w, 8)
+
     def render_probe_lit(self, scene, probes, sh, aov_samples: int = 8, wrap: bool = True, device: int = 0, model: "CameraModel" = None,
                          depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0, ao: "AmbientOcclusion" = None,
                          ao_rounds: int = 1, placement=None, radiance: "ProbeRadiance" = None, maps=None,
                          direct: "DirectLight" = None, ggx_table: "GgxTable" = None, table=None, gather: "FinalGather" = None,
-                         gather_rounds: int = 1) -> RenderResult:
+                         gather_rounds: int = 1, reflect: "ReflectionGather" = None, reflect_rounds: int = 1) -> RenderResult:
         """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
         (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
         from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
@@ -3920,11 +4179,23 @@ class Renderer:
         passed on to the lookup at the gather hits; with Eg its out, the frame is out_c = a_c (v (Eg_c float32(1 / pi)) + (1 - v))
         in float32, resolved by fw_denoise at 0 iterations.  With direct, the gather adds the delta lights at its hits as well
         (FW_GATHER_DIRECT with direct's bias), and the receivers' own term is added as above.  The call's stats are kept in
-        self.gather_stats.  gather together with ao or radiance: ValueError.  gather=None: the calls and the bits above."""
+        self.gather_stats.  gather together with ao or radiance: ValueError.  gather=None: the calls and the bits above.  reflect (a
+        ReflectionGather): traced reflections on conductors — view and spec are built as for radiance,
+        fw_bake_reflect runs `reflect_rounds` rounds on the records in place with depth, moments, normal_bias and placement passed
+        on to the lookup at the hits, and with S its out a pixel with rho > 0 becomes out_c = v S_c + (1 - v) a_c in float32 while
+        every other pixel keeps the linear value of the branch above that ran (plain, depth, placement or gather); the frame is
+        resolved by fw_denoise at 0 iterations.  With direct, the lights are added at the reflection rays' hits as well
+        (FW_REFLECT_DIRECT with direct's bias), and the receivers' own term is added as above.  The call's stats are kept in
+        self.reflect_stats.  reflect together with radiance or ao: ValueError.  reflect=None: the calls and the bits above."""
         import torch
         from . import _lib
         if direct is not None:
             direct.check()
+        if reflect is not None:
+            if ao is not None or radiance is not None:
+                raise ValueError("reflect cannot be combined with radiance or ao: the traced reflections take the radiance maps' place, and "
+                                 "the ambient-occlusion frame has no specular term")
+            reflect.check()
         if gather is not None:
             if ao is not None or radiance is not None:
                 raise ValueError("gather cannot be combined with ao or radiance: the gathered frame has neither term")
@@ -3985,14 +4256,7 @@ class Renderer:
                 rgb8, gam, lin = _lib.denoise(lit.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
             elif radiance is not None:
                 d_maps = torch.from_numpy(np.ascontiguousarray(np.asarray(maps, np.float32).reshape(grid.n_probes, radiance.texels, 4))).to(dev)
-                if model is not None:
-                    rays = _lib.model_rays(model, 0, 1, ds.device, out=torch.empty((1, w * h, 6), dtype=torch.float32, device=dev))[0]
-                else:
-                    rays = torch.from_numpy(ds.camera_rays(self, 0)).to(dev)
-                hit = _lib.hit_fields(ds.trace(rays, s["use_bvh"], seed=s["seed"]))
-                table = torch.from_numpy(material_spec_table(ds._desc)).to(dev)
-                miss = torch.full_like(hit["material"], table.shape[0] - 1)
-                spec = table[torch.where(hit["object"] == -1, miss, hit["material"]).long()].contiguous()
+                rays, spec = self._view_spec(ds, model, w, h, dev)
                 if ggx_table is not None:
                     if baked is None:
                         d_tab = _lib.ggx_table(ggx_table, device=ds.device,
@@ -4010,6 +4274,12 @@ class Renderer:
                 rgb8, gam, lin = _lib.probe_shade_vis(grid, d_sh, depth, d_mom, aov, w, h, normal_bias, s["gamma"], ds.device)
             else:
                 rgb8, gam, lin = _lib.probe_shade(grid, d_sh, aov, w, h, s["gamma"], ds.device)
+            if reflect is not None:
+                rays, spec = self._view_spec(ds, model, w, h, dev)
+                S = self._reflect(ds, reflect, reflect_rounds, grid, d_sh, aov, rays, spec, depth, d_mom, normal_bias, d_pl, direct)[0]
+                v = aov[:, 3:4]
+                lit = torch.where(spec[:, 3:4] > 0, v * S[:, 0:3] + (1.0 - v) * aov[:, 0:3], lin.reshape(-1, 3))
+                rgb8, gam, lin = _lib.denoise(lit.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
             if direct is not None:
                 term = self._direct_term(ds, direct, aov, model, rays)[0]
                 rgb8, gam, lin = _lib.denoise((lin.reshape(-1, 3) + term).contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)

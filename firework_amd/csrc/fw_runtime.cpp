@@ -23,6 +23,7 @@
 #include "fw_sky.h"
 #include "fw_ggx_table.h"
 #include "fw_gather.h"
+#include "fw_reflect.h"
 #include "fw_defer_pretest.h"
 
 #include <algorithm>
@@ -3715,7 +3716,7 @@ struct Staged {
     enum Kind { IN, INOUT, OUT, WORK, ZERO };
     struct Slot { Kind kind; void *host; size_t bytes, at; bool staged, back; };
     hipStream_t stream; bool on_device; CallScratch scratch;
-    Slot slots[16] = {}; int n_slots = 0; size_t off = 0; bool armed = false;
+    Slot slots[20] = {}; int n_slots = 0; size_t off = 0; bool armed = false;
     Staged(int device, hipStream_t stream_, bool on_device_) : stream(stream_), on_device(on_device_), scratch(device) {}
     ~Staged() { if (armed) (void)hipStreamSynchronize(stream); }
     int add(Kind kind, const void *p, size_t bytes, bool host_always = false) {
@@ -5147,10 +5148,67 @@ int gather_check(const fw_gather *g) {
     return FW_OK;
 }
 
+// how many records a point call's sums and out span: only scratch copies of them need it (a host caller's, or the sums nobody keeps)
+int points_extent(hipStream_t stream, uint32_t N, const uint32_t *ids, bool on_device, const float *sums, uint64_t &extent) {
+    extent = N;
+    if (!ids || (on_device && sums)) return FW_OK;
+    if (on_device) {
+        std::vector<uint32_t> h_ids(N);
+        HIPCHK(hipMemcpyAsync(h_ids.data(), ids, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        extent = ao_extent(N, h_ids.data());
+    } else extent = ao_extent(N, ids);
+    return FW_OK;
+}
+
+// What fw_bake_gather and fw_bake_reflect do with a chunk's rays and hits before their own reduction (fw_bake_gather's steps 3 to 5):
+// k_hit_surface, the probe lookup at the records read in place and, on a scene with Ln lights, fw_bake_direct's kernels for one round
+// around a second trace.  The drivers' reducer returns nothing, so the second trace's code leaves through `rc`: once it is set nothing
+// more is launched and the call returns it.
+struct HitLightSlots { int surf, irr, drays, dhits, dsums; };
+HitLightSlots hit_light_stage(Staged &st, size_t cd, uint32_t Ln) {
+    HitLightSlots s;
+    s.surf = st.add(Staged::WORK, nullptr, cd * 64); s.irr = st.add(Staged::WORK, nullptr, cd * 12);
+    s.drays = Ln ? st.add(Staged::WORK, nullptr, cd * Ln * 24) : -1; s.dhits = Ln ? st.add(Staged::WORK, nullptr, cd * Ln * sizeof(fw_hit)) : -1;
+    s.dsums = Ln ? st.add(Staged::WORK, nullptr, cd * 32) : -1;
+    return s;
+}
+struct HitLight {
+    fw_scene *sc; const fw_trace_params *tp; const Staged &st; HitLightSlots s; uint32_t D, Ln; float direct_bias;
+    const ProbeLookup &L; const fw::DProbeVis *vis; const float *d_sh, *d_pl; fw_stats *total;
+    int rc = FW_OK;
+    float *surf() const { return st.ptr<float>(s.surf); }
+    float *irr() const { return st.ptr<float>(s.irr); }
+    // the chunk [q0, q0 + k) of round `round`: fills surf() and irr(); returns the chunk's direct records (fw_bake_direct's out), or NULL
+    const float *run(uint32_t round, uint32_t q0, uint32_t k, const float *rays, const fw_hit *hits) {
+        hipStream_t stream = (hipStream_t)tp->stream;
+        const int n_cus = device_cus(sc->device);
+        const uint32_t kd = k * D;
+        float *d_surf = surf();
+        fw::launch_hit_surface(stream, sc->n_cus, sc->d, sc->n_mat, rays, (const float4 *)hits, kd, (float4 *)d_surf);
+        fw::launch_probe_irradiance(stream, L.g, vis, d_sh, d_pl, kd, d_surf + 8, d_surf + 4, 16, irr());
+        if (!Ln) return nullptr;
+        fw::DDirect dd{};
+        dd.pts = fw::DDirectPoints{d_surf + 8, d_surf + 4, nullptr, nullptr, nullptr, 16, 3};
+        dd.lights = (const float4 *)sc->dlights.p; dd.n_lights = Ln; dd.first = 0;
+        dd.lobe = 0; dd.face_view = 0; dd.bias = direct_bias;
+        float *drays = st.ptr<float>(s.drays), *dsums = st.ptr<float>(s.dsums);
+        fw_hit *dhits = st.ptr<fw_hit>(s.dhits);
+        fw::launch_direct_rays(stream, n_cus, dd, kd, drays);
+        fw_trace_params q = *tp;
+        q.on_device = 1; q.seed = tp->seed + round; q.key_base = q0 * D * Ln;
+        fw_stats gs{};
+        rc = trace_impl(sc, &q, drays, kd * Ln, dhits, total ? &gs : nullptr);
+        if (rc) return nullptr;
+        if (total) { gs.ms_render = 0.0; stats_add(*total, gs); }          // (its time lies inside the reducer's own span)
+        if (hipMemsetAsync(dsums, 0, (size_t)kd * 32, stream) != hipSuccess) { rc = fail(FW_ERR_HIP, "hipMemsetAsync failed"); return nullptr; }
+        fw::launch_direct_reduce(stream, n_cus, dd, kd, drays, dhits, dsums);
+        return dsums;                                                      // one round: out = float(sums / 1) = sums
+    }
+};
+
 // fw_bake_gather: fw_bake_ao's shape — k_ao_rays as trace_rounds' generator; its reducer is the rest of the chain over the chunk's rays and
-// hits: k_hit_surface, the probe lookup at the records read in place, with FW_GATHER_DIRECT fw_bake_direct's kernels around a second
-// trace, and k_gather_reduce.  The reducer returns nothing, so the second trace's code leaves through `chain_rc`: once it is set the
-// remaining chunks' kernels are not launched and the call returns it.
+// hits: HitLight's steps and k_gather_reduce.
 int bake_gather_impl(fw_scene *sc, const fw_gather *g, const fw_trace_params *tp, const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd,
                      const float *moments, float normal_bias, const float *placement, uint32_t N, const float *positions, const float *normals,
                      uint32_t stride, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
@@ -5181,72 +5239,187 @@ int bake_gather_impl(fw_scene *sc, const fw_gather *g, const fw_trace_params *tp
     const bool on_device = tp->on_device != 0;
     const uint64_t ray_bytes = 24 + sizeof(fw_hit) + 64 + 12 + (Ln ? (uint64_t)Ln * 72 + 64 : 0);
     const uint32_t chunk = std::min<uint32_t>(N, g->chunk_points ? g->chunk_points : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * ray_bytes)));
-    // how many records sums and out span: only scratch copies of them need it (a host caller's, or the sums nobody keeps)
-    uint64_t extent = N;
-    if (ids && (!on_device || !sums)) {
-        if (on_device) {
-            std::vector<uint32_t> h_ids(N);
-            HIPCHK(hipMemcpyAsync(h_ids.data(), ids, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            extent = ao_extent(N, h_ids.data());
-        } else extent = ao_extent(N, ids);
-    }
+    uint64_t extent;
+    if (int rc = points_extent(stream, N, ids, on_device, sums, extent)) return rc;
     const size_t rec_bytes = (size_t)extent * 16, cd = (size_t)chunk * D;
     Staged st(dev, stream, on_device);
     const AoSlots slots = ao_points_stage(st, N, positions, normals, stride, ids, extent);
     const ProbeTables t = probe_tables_stage(st, a, L);
-    const int i_rays = st.add(Staged::WORK, nullptr, cd * 24), i_hits = st.add(Staged::WORK, nullptr, cd * sizeof(fw_hit)),
-              i_surf = st.add(Staged::WORK, nullptr, cd * 64), i_irr = st.add(Staged::WORK, nullptr, cd * 12);
-    const int i_drays = Ln ? st.add(Staged::WORK, nullptr, cd * Ln * 24) : -1, i_dhits = Ln ? st.add(Staged::WORK, nullptr, cd * Ln * sizeof(fw_hit)) : -1,
-              i_dsums = Ln ? st.add(Staged::WORK, nullptr, cd * 32) : -1;
+    const int i_rays = st.add(Staged::WORK, nullptr, cd * 24), i_hits = st.add(Staged::WORK, nullptr, cd * sizeof(fw_hit));
+    const HitLightSlots hs = hit_light_stage(st, cd, Ln);
     const int i_sums = st.add_sums(sums, rec_bytes), i_out = st.add(ids ? Staged::INOUT : Staged::OUT, out, rec_bytes);      // (with ids, entries outside the list stay)
     if (int rc = st.up()) return rc;
     const fw::DAoPoints pts = ao_points_device(st, slots, stride);
-    float *d_sums = st.ptr<float>(i_sums), *d_surf = st.ptr<float>(i_surf), *d_irr = st.ptr<float>(i_irr);
-    const float *d_sh = st.ptr<const float>(t.sh), *d_pl = st.ptr<const float>(t.pl);
+    float *d_sums = st.ptr<float>(i_sums);
     const fw::DProbeVis vis = probe_vis_device(a, st.ptr<const float>(t.mom));
     const int n_cus = device_cus(dev);
     fw_ao ao{};
     ao.directions = D; ao.falloff = 0; ao.radius = std::numeric_limits<float>::infinity(); ao.bias = g->bias; ao.jitter = g->jitter; ao.seed = g->seed;
     fw_stats total{};
-    int chain_rc = FW_OK;
+    HitLight hl{sc, tp, st, hs, D, Ln, g->direct_bias, L, a.vis ? &vis : nullptr, st.ptr<const float>(t.sh), st.ptr<const float>(t.pl), stats ? &total : nullptr};
     uint32_t round = first_round;              // the reducer's round: trace_rounds hands it to the generator only
     const TraceRounds b{N, D, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
     if (int rc = trace_rounds(sc, tp, b, first_round, rounds, stats ? &total : nullptr,
             [&](uint32_t r, uint32_t q0, uint32_t k, float *rays) {
                 round = r;
-                if (!chain_rc) fw::launch_ao_rays(stream, n_cus, ao_rays_device(&ao, r, pts, q0), k, rays);
+                if (!hl.rc) fw::launch_ao_rays(stream, n_cus, ao_rays_device(&ao, r, pts, q0), k, rays);
             },
             [&](uint32_t q0, uint32_t k, const float *rays, const fw_hit *hits) {
-                if (chain_rc) return;
-                const uint32_t kd = k * D;
-                fw::launch_hit_surface(stream, sc->n_cus, sc->d, sc->n_mat, rays, (const float4 *)hits, kd, (float4 *)d_surf);
-                fw::launch_probe_irradiance(stream, L.g, a.vis ? &vis : nullptr, d_sh, d_pl, kd, d_surf + 8, d_surf + 4, 16, d_irr);
-                const float *d_direct = nullptr;
-                if (Ln) {
-                    fw::DDirect dd{};
-                    dd.pts = fw::DDirectPoints{d_surf + 8, d_surf + 4, nullptr, nullptr, nullptr, 16, 3};
-                    dd.lights = (const float4 *)sc->dlights.p; dd.n_lights = Ln; dd.first = 0;
-                    dd.lobe = 0; dd.face_view = 0; dd.bias = g->direct_bias;
-                    float *drays = st.ptr<float>(i_drays), *dsums = st.ptr<float>(i_dsums);
-                    fw_hit *dhits = st.ptr<fw_hit>(i_dhits);
-                    fw::launch_direct_rays(stream, n_cus, dd, kd, drays);
-                    fw_trace_params q = *tp;
-                    q.on_device = 1; q.seed = tp->seed + round; q.key_base = q0 * D * Ln;
-                    fw_stats gs{};
-                    chain_rc = trace_impl(sc, &q, drays, kd * Ln, dhits, stats ? &gs : nullptr);
-                    if (chain_rc) return;
-                    if (stats) { gs.ms_render = 0.0; stats_add(total, gs); }       // (its time lies inside the reducer's own span)
-                    if (hipMemsetAsync(dsums, 0, (size_t)kd * 32, stream) != hipSuccess) { chain_rc = fail(FW_ERR_HIP, "hipMemsetAsync failed"); return; }
-                    fw::launch_direct_reduce(stream, n_cus, dd, kd, drays, dhits, dsums);
-                    d_direct = dsums;                                             // one round: out = float(sums / 1) = sums
-                }
-                fw::launch_gather_reduce(stream, n_cus, q0, k, D, pts.ids, d_surf, d_irr, d_direct, d_sums);
+                if (hl.rc) return;
+                const float *d_direct = hl.run(round, q0, k, rays, hits);
+                if (!hl.rc) fw::launch_gather_reduce(stream, n_cus, q0, k, D, pts.ids, hl.surf(), hl.irr(), d_direct, d_sums);
             }))
         return rc;
-    if (chain_rc) return chain_rc;
+    if (hl.rc) return hl.rc;
     if (int rc = st.download(i_sums)) return rc;
     if (out) fw::launch_gather_resolve(stream, N, (double)((uint64_t)first_round + rounds), pts.ids, d_sums, st.ptr<float>(i_out));
+    if (int rc = st.finish()) return rc;
+    stats_finish(stats, total, wall0);
+    return FW_OK;
+}
+
+// ---- reflection gather (include/firework_hip.h) -------------------------------------------------------------------
+// A reflection description's own argument checks (FW_ERR_BAD_ARG only); the flags are checked after the probe tables
+int reflect_check(const fw_reflect *g) {
+    if (g->directions == 0 || g->directions > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (!std::isfinite(g->bias) || g->bias < 0.f) return fail(FW_ERR_BAD_ARG, "bias must be finite and >= 0");
+    if (!std::isfinite(g->direct_bias) || g->direct_bias < 0.f) return fail(FW_ERR_BAD_ARG, "direct_bias must be finite and >= 0");
+    return FW_OK;
+}
+// the checks of the points that fw_reflect_rays and fw_bake_reflect share, after the description's and before the alignment's
+int reflect_points_check(uint32_t n, uint32_t stride, uint32_t view_stride) {
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (view_stride < 3) return fail(FW_ERR_BAD_ARG, "view_stride_floats must be >= 3");
+    return FW_OK;
+}
+fw::DReflectRays reflect_rays_device(const Staged &st, const DirectSlots &s, uint32_t stride, uint32_t view_stride, const fw_reflect *g, uint32_t round,
+                                     uint32_t first) {
+    fw::DReflectRays d{};
+    d.pts = fw::DReflectPoints{st.ptr<const float>(s.pts.pos), st.ptr<const float>(s.pts.nrm), st.ptr<const uint32_t>(s.pts.ids),
+                               st.ptr<const float>(s.view), st.ptr<const float4>(s.spec), stride, view_stride};
+    d.first = first; d.directions = g->directions;
+    d.seed32 = seed32_of(g->seed);
+    d.jitter = g->jitter ? 1u : 0u;
+    d.round = round; d.bias = g->bias;
+    return d;
+}
+
+// fw_reflect_rays: fw_ao_rays' shape with two outputs — with device arrays the kernel works on the caller's memory; with host arrays the
+// points are staged once and the rays and weights come back in slabs (32 B per ray)
+int reflect_rays_impl(const fw_reflect *g, int device, uint32_t round, uint32_t n, const float *positions, const float *normals, uint32_t stride,
+                      const uint32_t *ids, const float *view, uint32_t view_stride, const float *spec, float *rays, float *weights, int on_device,
+                      void *stream_) {
+    if (!g || !positions || !normals || !view || !spec || !rays || !weights) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = reflect_check(g)) return rc;
+    if (int rc = reflect_points_check(n, stride, view_stride)) return rc;
+    if (on_device && (((uintptr_t)spec & 15u) || ((uintptr_t)weights & 7u)
+                      || (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids | (uintptr_t)view | (uintptr_t)rays) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device spec must be 16-byte aligned, device weights 8-byte aligned, device positions, normals, ids, view and rays 4-byte aligned");
+    const uint32_t D = g->directions;
+    if ((uint64_t)n * D >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n_cus = device_cus(device);
+    Staged st(device, stream, on_device != 0);
+    const DirectSlots slots = direct_points_stage(st, n, positions, normals, stride, ids, view, view_stride, spec, on_device ? n : ao_extent(n, ids));
+    HostSlabs sl(st, n, (size_t)D * 32);
+    const int a_rays = sl.out(rays, (size_t)D * 24), a_w = sl.out(weights, (size_t)D * 8);
+    if (int rc = st.up()) return rc;
+    return sl.run([&](uint32_t done, uint32_t k) {
+        fw::launch_reflect_rays(stream, n_cus, reflect_rays_device(st, slots, stride, view_stride, g, round, done), k, sl.ptr<float>(a_rays), sl.ptr<float>(a_w));
+    });
+}
+
+// fw_reflect_reduce: fw_gather_reduce's shape with the weights
+int reflect_reduce_impl(int device, uint32_t D, uint32_t n, const uint32_t *ids, const float *surface, const float *irradiance, const float *direct,
+                        const float *weights, float *sums, int on_device, void *stream_) {
+    if (!surface || !irradiance || !weights || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (D == 0 || D > (1u << 20)) return fail(FW_ERR_BAD_ARG, "directions must be in 1..2^20");
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (on_device && ((((uintptr_t)sums | (uintptr_t)surface) & 15u) || ((uintptr_t)weights & 7u)
+                      || (((uintptr_t)irradiance | (uintptr_t)direct | (uintptr_t)ids) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums and surface must be 16-byte aligned, device weights 8-byte aligned, device irradiance, direct and ids 4-byte aligned");
+    if ((uint64_t)n * D >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t entries = (size_t)n * D;
+    Staged st(device, stream, on_device != 0);
+    const int i_surf = st.add(Staged::IN, surface, entries * 64), i_irr = st.add(Staged::IN, irradiance, entries * 12),
+              i_dir = st.add(Staged::IN, direct, entries * 32), i_w = st.add(Staged::IN, weights, entries * 8),
+              i_sums = st.add(Staged::INOUT, sums, on_device ? 0 : (size_t)ao_extent(n, ids) * 32), i_ids = st.add(Staged::IN, ids, (size_t)n * 4);
+    if (int rc = st.up()) return rc;
+    fw::launch_reflect_reduce(stream, device_cus(device), 0, n, D, st.ptr<const uint32_t>(i_ids), st.ptr<const float>(i_surf), st.ptr<const float>(i_irr),
+                              st.ptr<const float>(i_dir), st.ptr<const float>(i_w), st.ptr<float>(i_sums));
+    return st.finish();
+}
+
+// fw_bake_reflect: fw_bake_gather's shape — k_reflect_rays as trace_rounds' generator, which fills the chunk's weights beside its rays;
+// the reducer is HitLight's steps over the chunk's rays and hits and k_reflect_reduce
+int bake_reflect_impl(fw_scene *sc, const fw_reflect *g, const fw_trace_params *tp, const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd,
+                      const float *moments, float normal_bias, const float *placement, uint32_t N, const float *positions, const float *normals,
+                      uint32_t stride, const uint32_t *ids, const float *view, uint32_t view_stride, const float *spec, uint32_t first_round,
+                      uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    if (!sc || !g || !tp || !positions || !normals || !view || !spec) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = reflect_check(g)) return rc;
+    if (int rc = reflect_points_check(N, stride, view_stride)) return rc;
+    if (rounds == 0) return fail(FW_ERR_BAD_ARG, "rounds must be > 0");
+    if ((uint64_t)first_round + rounds > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_round + rounds overflows");
+    if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
+    if (tp->on_device && ((((uintptr_t)sums | (uintptr_t)out | (uintptr_t)spec) & 15u)
+                          || (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids | (uintptr_t)view) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums, out and spec must be 16-byte aligned, device positions, normals, ids and view 4-byte aligned");
+    const ProbeLookupArgs a{sh, nullptr, nullptr, pd, moments, normal_bias, placement, pd || moments, placement != nullptr};
+    ProbeLookup L;
+    if (int rc = probe_lookup_check(grid, a, !sh, false, L)) return rc;
+    if (tp->on_device && (((uintptr_t)sh | (uintptr_t)moments | (uintptr_t)placement) & 3u)) return fail(FW_ERR_BAD_ARG, "device sh, moments and placement must be 4-byte aligned");
+    if (g->flags & ~(uint32_t)FW_REFLECT_DIRECT) return fail(FW_ERR_BAD_ARG, "unknown reflect flags");
+    const uint32_t D = g->directions;
+    if ((uint64_t)N * D >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
+    if (int rc = probe_lookup_sizes(a, L)) return rc;
+    if (int rc = need_device()) return rc;
+    const uint32_t Ln = (g->flags & FW_REFLECT_DIRECT) ? sc->n_dlights : 0u;
+    if ((uint64_t)N * D * Ln >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions x the scene's lights must be below 2^31");
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)tp->stream;
+    const bool on_device = tp->on_device != 0;
+    const uint64_t ray_bytes = 24 + sizeof(fw_hit) + 8 + 64 + 12 + (Ln ? (uint64_t)Ln * 72 + 64 : 0);
+    const uint32_t chunk = std::min<uint32_t>(N, g->chunk_points ? g->chunk_points : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)D * ray_bytes)));
+    uint64_t extent;
+    if (int rc = points_extent(stream, N, ids, on_device, sums, extent)) return rc;
+    const size_t cd = (size_t)chunk * D;
+    Staged st(dev, stream, on_device);
+    const DirectSlots slots = direct_points_stage(st, N, positions, normals, stride, ids, view, view_stride, spec, extent);
+    const ProbeTables t = probe_tables_stage(st, a, L);
+    const int i_rays = st.add(Staged::WORK, nullptr, cd * 24), i_hits = st.add(Staged::WORK, nullptr, cd * sizeof(fw_hit)),
+              i_w = st.add(Staged::WORK, nullptr, cd * 8);
+    const HitLightSlots hs = hit_light_stage(st, cd, Ln);
+    const int i_sums = st.add_sums(sums, (size_t)extent * 32), i_out = st.add(ids ? Staged::INOUT : Staged::OUT, out, (size_t)extent * 16);      // (with ids, entries outside the list stay)
+    if (int rc = st.up()) return rc;
+    float *d_sums = st.ptr<float>(i_sums), *d_w = st.ptr<float>(i_w);
+    const uint32_t *d_ids = st.ptr<const uint32_t>(slots.pts.ids);
+    const fw::DProbeVis vis = probe_vis_device(a, st.ptr<const float>(t.mom));
+    const int n_cus = device_cus(dev);
+    fw_stats total{};
+    HitLight hl{sc, tp, st, hs, D, Ln, g->direct_bias, L, a.vis ? &vis : nullptr, st.ptr<const float>(t.sh), st.ptr<const float>(t.pl), stats ? &total : nullptr};
+    uint32_t round = first_round;              // the reducer's round: trace_rounds hands it to the generator only
+    const TraceRounds b{N, D, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
+    if (int rc = trace_rounds(sc, tp, b, first_round, rounds, stats ? &total : nullptr,
+            [&](uint32_t r, uint32_t q0, uint32_t k, float *rays) {
+                round = r;
+                if (!hl.rc) fw::launch_reflect_rays(stream, n_cus, reflect_rays_device(st, slots, stride, view_stride, g, r, q0), k, rays, d_w);
+            },
+            [&](uint32_t q0, uint32_t k, const float *rays, const fw_hit *hits) {
+                if (hl.rc) return;
+                const float *d_direct = hl.run(round, q0, k, rays, hits);
+                if (!hl.rc) fw::launch_reflect_reduce(stream, n_cus, q0, k, D, d_ids, hl.surf(), hl.irr(), d_direct, d_w, d_sums);
+            }))
+        return rc;
+    if (hl.rc) return hl.rc;
+    if (int rc = st.download(i_sums)) return rc;
+    if (out) fw::launch_reflect_resolve(stream, N, (double)((uint64_t)first_round + rounds), d_ids, st.ptr<const float>(slots.spec), d_sums, st.ptr<float>(i_out));
     if (int rc = st.finish()) return rc;
     stats_finish(stats, total, wall0);
     return FW_OK;
@@ -6212,6 +6385,33 @@ int fw_bake_gather(fw_scene *scene, const fw_gather *g, const fw_trace_params *t
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_gather"); }
+}
+
+int fw_reflect_rays(const fw_reflect *reflect, int device, uint32_t round, uint32_t n, const float *positions, const float *normals,
+                    uint32_t stride_floats, const uint32_t *ids, const float *view, uint32_t view_stride_floats, const float *spec, float *rays,
+                    float *weights, int on_device, void *stream) {
+    try { return reflect_rays_impl(reflect, device, round, n, positions, normals, stride_floats, ids, view, view_stride_floats, spec, rays, weights, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_reflect_rays"); }
+}
+
+int fw_reflect_reduce(int device, uint32_t directions, uint32_t n, const uint32_t *ids, const float *surface, const float *irradiance,
+                      const float *direct, const float *weights, float *sums, int on_device, void *stream) {
+    try { return reflect_reduce_impl(device, directions, n, ids, surface, irradiance, direct, weights, sums, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_reflect_reduce"); }
+}
+
+int fw_bake_reflect(fw_scene *scene, const fw_reflect *reflect, const fw_trace_params *tp, const fw_probe_grid *grid, const float *sh,
+                    const fw_probe_depth *pd, const float *moments, float normal_bias, const float *placement, uint32_t n, const float *positions,
+                    const float *normals, uint32_t stride_floats, const uint32_t *ids, const float *view, uint32_t view_stride_floats, const float *spec,
+                    uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    try {
+        return bake_reflect_impl(scene, reflect, tp, grid, sh, pd, moments, normal_bias, placement, n, positions, normals, stride_floats, ids, view,
+                                 view_stride_floats, spec, first_round, rounds, sums, out, stats);
+    }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_reflect"); }
 }
 
 int fw_check_sky(const fw_sky *sky) {

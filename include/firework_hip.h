@@ -1770,6 +1770,110 @@ int fw_bake_gather(fw_scene *scene, const fw_gather *g, const fw_trace_params *t
                    uint32_t n, const float *positions, const float *normals, uint32_t stride_floats, const uint32_t *ids,
                    uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
 
+/* ---- reflection gather: GGX-sampled reflection rays lit from baked probes (additive at ABI 8) --------------------------
+   The specular counterpart of the final gather.  fw_probe_shade_glossy reads each probe's radiance map along the mirrored direction as
+   if the reflected surface were infinitely far away; a reflection ray from the receiver meets what is really there.  From each glossy
+   point D rays are drawn from FW_MAT_GGX's visible-normal lobe around its view direction, traced and lit at their hits exactly as the
+   final gather's rays are, and summed with the estimator's weight F G2 / G1 — which carries the split sum's BRDF term F0 A + B with it.
+   Three calls: fw_reflect_rays makes the rays and their weights, fw_reflect_reduce sums what they brought back, fw_bake_reflect chains
+   rays, trace, surface, probe lookup, optionally the delta lights, and the reduction.  api.reflect_rays, api.reflect_reduce and
+   api.reflect_resolve are the numpy statements.  A glossy surface that a reflection ray hits is lit as if it were diffuse — its F0 (a
+   MetalMat's albedo) times the irradiance from the probes over pi — which is the final gather's own simplification: one bounce, no
+   recursion.
+     Points: fw_ao_rays' (position and normal three floats each at id x stride_floats, id = ids ? ids[q] : q), plus per id the view —
+         three floats at id x view_stride_floats, the direction from the eye towards the point, any length — and spec, four packed floats
+         (F0.rgb, rho) as fw_probe_shade_glossy takes them.  A point is usable when position, normal and view are finite, normal and view
+         are not (0, 0, 0), and rho is finite and > 0.  An unusable point gets D all-zero rays and all-zero weights.
+     Ray j of round r at id (fw_reflect_rays, k_reflect_rays).  Everything is float64 from the float32 inputs, every operation rounded as
+         written (no contraction), max is fmax, sqrt, sin and cos are the library's float64 functions, one rounding to float32 at the end.
+         1. (xi_u, xi_v) = the two shifts fw_ao_rays draws for (seed, r, id); (1/2, 1/2) with jitter == 0.
+         2. xi1 = (j + xi_u) / D;  t = j G + xi_v with G = 0.6180339887498949, fw_ao_rays' constant;  xi2 = t - floor(t).
+         3. alpha = the float32 product rho rho, widened (as FW_MAT_GGX forms it);  a2 = alpha alpha.
+         4. Frame.  n = normal / sqrt((x x + y y) + z z);  u = view / sqrt((x x + y y) + z z);  wo = (-u.x, -u.y, -u.z);  if (wo.x n.x +
+            wo.y n.y) + wo.z n.z < 0 then n = -n: it faces the eye.  The tangent frame around n is Duff et al.'s, as FW_MAT_GGX and
+            fw_ao_rays form it:  s = copysign(1, n.z);  a = -1 / (s + n.z);  b = (n.x n.y) a;  T = (1 + (s (n.x n.x)) a, s b, -s n.x);
+            B = (b, s + (n.y n.y) a, -n.y).  Local wo:  o = ((wo.x T.x + wo.y T.y) + wo.z T.z, the same with B, the same with n).
+         5. The visible normal (Heitz 2018, FW_MAT_GGX's) for this o:  v = (alpha o.x, alpha o.y);  vl = sqrt((v.x v.x + v.y v.y) + o.z
+            o.z);  Vh = (v.x / vl, v.y / vl, o.z / vl);  l2 = Vh.x Vh.x + Vh.y Vh.y;  T1 = (-Vh.y il, Vh.x il, 0) with il = 1 / sqrt(l2)
+            where l2 > 0, else (1, 0, 0);  T2 = Vh x T1 = (-(Vh.z T1.y), Vh.z T1.x, Vh.x T1.y - Vh.y T1.x);  sh = 0.5 (1 + Vh.z);
+            r = sqrt(xi1);  phi = (2 pi) xi2;  p1 = r cos phi;  q1 = 1 - p1 p1;  p2 = (1 - sh) sqrt(max(q1, 0)) + sh (r sin phi);
+            pz = sqrt(max(q1 - p2 p2, 0));  nh = ((p1 T1.x + p2 T2.x) + pz Vh.x, (p1 T1.y + p2 T2.y) + pz Vh.y, p2 T2.z + pz Vh.z);
+            g = (alpha nh.x, alpha nh.y, max(nh.z, 0));  h = g / sqrt((g.x g.x + g.y g.y) + g.z g.z);  oh = (o.x h.x + o.y h.y) + o.z h.z;
+            wi = ((2 oh) h.x - o.x, (2 oh) h.y - o.y, (2 oh) h.z - o.z).
+         6. The ray is dead unless wi.z > 0 and o.z > 0 (a NaN is dead): six zeros and the weights (0, 0).  fw_trace_rays never traces
+            such a ray and fw_hit_surface gives it kind -2.  Otherwise direction = float(((wi.x T.c + wi.y B.c) + wi.z n.c)) per
+            component c and origin = float(position.c + bias n.c), n the normal facing the eye.
+         7. Weights (g, s), each rounded to float32 once:  Lo1 = 1 + 0.5 (sqrt(1 + a2 ((o.x o.x + o.y o.y) / (o.z o.z))) - 1);
+            Li = 0.5 (sqrt(1 + a2 ((wi.x wi.x + wi.y wi.y) / (wi.z wi.z))) - 1);  g = Lo1 / (Lo1 + Li), which is G2 / G1;  m = max(1 -
+            oh, 0);  s = ((m m) (m m)) m, Schlick's weight.  Fresnel is per channel, F_c = f0_c + (1 - f0_c) s, and is applied in the
+            resolve: neither the rays nor the sums depend on F0.
+         rays: n x D x 6 floats, weights: n x D x 2 floats, entry q D + j.
+     Reduction of one round (fw_reflect_reduce, k_reflect_reduce): float64 from the float32 inputs, every operation rounded as written.
+         Per ray its radiance L is fw_gather_reduce's: kind -2 nothing; kind -1 L = emitted and sky += 1; kind 3 L = emitted; any other
+         kind T_c = (E_c > 0 ? E_c : 0) (+ Ed_c with direct), L_c = (albedo_c T_c) (1 / pi).  Eight accumulators: P_c += (g (1 - s)) L_c;
+         Q_c += (g s) L_c;  alive += 1 where the float32 g > 0, whatever the ray's kind;  sky as above.  The order is fw_gather_reduce's:
+         G = the smallest power of two >= min(D, 64), partial sum l takes j = l, l + G, ... ascending from 0, the G partial sums are
+         added by an xor butterfly over the distances G/2 ... 1.  Each accumulator is multiplied by the float64 1 / D, rounded to
+         float32 once and added with one float32 addition to sums[id], a record of 32 B: (P.rgb, alive, Q.rgb, sky).  No atomics; two
+         runs are bit-equal; a point's result depends on no other point.
+     Resolve (k_reflect_resolve), R = the number of rounds in sums and f0 = spec[id]:  out[id].c = float(((double)f0_c P_c + Q_c) / R)
+         for the three channels, out[id].w = float(alive / R): the reflected radiance towards the eye and the share of the rays that
+         left the surface.  Under a constant environment of radiance 1 it estimates FW_MAT_GGX's directional albedo F0 A + B
+         (fw_ggx_terms).  An unusable point resolves to zeros. */
+#define FW_REFLECT_DIRECT 1u   /* add the scene's point, spot and directional lights at the reflection rays' hits */
+typedef struct fw_reflect {
+    uint32_t directions;     /* D, 1..2^20 */
+    uint32_t jitter;         /* fw_ao's */
+    float    bias;           /* ray origin offset along the normal facing the eye, >= 0, finite */
+    float    direct_bias;    /* fw_direct.bias for the shadow rays at the hits */
+    uint32_t flags;          /* FW_REFLECT_DIRECT */
+    uint32_t chunk_points;   /* 0: as many as fit 256 MiB at this call's bytes per ray (156, plus Ln x 72 + 64 with direct), at least one */
+    uint64_t seed;
+} fw_reflect;
+
+/* fw_reflect_rays: the rays and weights of round `round` at n points.  Host or device arrays as fw_ao_rays; rays n x D x 6 floats,
+   weights n x D x 2 floats.  Only directions, jitter, bias and seed of the description are read beyond its checks.
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL reflect, positions, normals, view, spec, rays or weights;
+   directions outside 1..2^20, a bias or direct_bias negative or not finite; n == 0; stride_floats < 3; view_stride_floats < 3; with
+   on_device spec not 16-byte aligned, weights not 8-byte aligned, positions, normals, ids, view or rays not 4-byte aligned;
+   FW_ERR_UNSUPPORTED for n x D >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last one. */
+int fw_reflect_rays(const fw_reflect *reflect, int device, uint32_t round, uint32_t n, const float *positions, const float *normals,
+                    uint32_t stride_floats, const uint32_t *ids, const float *view, uint32_t view_stride_floats, const float *spec,
+                    float *rays, float *weights, int on_device, void *stream);
+
+/* fw_reflect_reduce: adds one round's reduction to the running sums.  surface, irradiance and direct as fw_gather_reduce takes them;
+   weights: n x D x 2 floats as fw_reflect_rays wrote them; sums: records of 32 B indexed by id.  Host or device arrays.
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL surface, irradiance, weights or sums; directions outside
+   1..2^20; n == 0; with on_device sums or surface not 16-byte aligned, weights not 8-byte aligned, irradiance, direct or ids not 4-byte
+   aligned; FW_ERR_UNSUPPORTED for n x D >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last one. */
+int fw_reflect_reduce(int device, uint32_t directions, uint32_t n, const uint32_t *ids, const float *surface, const float *irradiance,
+                      const float *direct, const float *weights, float *sums, int on_device, void *stream);
+
+/* fw_bake_reflect: the rounds [first_round, first_round + rounds) of the n points against a resident scene and a baked probe grid:
+   fw_bake_gather's statement with its step 1 replaced by k_reflect_rays (rays and weights of the chunk) and its step 6 by
+   k_reflect_reduce; steps 2 to 5 — the trace with seed = tp->seed + r and key_base = q0 D, k_hit_surface, the plain, visibility or
+   placed lookup at the records in place, with FW_REFLECT_DIRECT fw_bake_direct's kernels at the hits — are the same code.  After the
+   last round k_reflect_resolve writes out.  Points, ids, first_round / rounds and what is read of tp are fw_bake_ao's; view,
+   view_stride_floats and spec as fw_reflect_rays takes them.
+     sums: the running sums (P.rgb, alive, Q.rgb, sky), 8 floats per id, of the rounds [0, first_round), NULL only when first_round == 0;
+     out:  4 floats per id, (S.rgb, alive): the resolve above; may be NULL.
+   Contracts.  Composition: for every chunk_points, sums equals bit for bit what the public calls give when chained by hand over all n
+   points: fw_reflect_rays, fw_trace_rays, fw_hit_surface, the lookup, (fw_bake_direct,) fw_reflect_reduce.  Progressive: k calls of m
+   rounds leave the sums and out of one call of k m rounds, bit for bit.  Renders, and the frame graph's key, are left as fw_trace_rays
+   leaves them.
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, reflect, tp, positions,
+   normals, view or spec; directions outside 1..2^20, a bias or direct_bias negative or not finite; n == 0; stride_floats < 3;
+   view_stride_floats < 3; rounds == 0; first_round + rounds >= 2^32; a NULL sums with first_round > 0; with on_device sums, out or
+   spec not 16-byte aligned, positions, normals, ids or view not 4-byte aligned; then fw_probe_irradiance_placed's checks of grid, sh,
+   pd, moments, normal_bias and (with on_device) the tables' alignment; unknown flag bits; FW_ERR_UNSUPPORTED for n x D >= 2^31 and
+   the tables' sizes; then FW_ERR_NO_DEVICE; then — Ln is the scene's — FW_ERR_UNSUPPORTED for n x D x Ln >= 2^31.
+   stats (may be NULL): fw_bake_gather's. */
+int fw_bake_reflect(fw_scene *scene, const fw_reflect *reflect, const fw_trace_params *tp,
+                    const fw_probe_grid *grid, const float *sh, const fw_probe_depth *pd, const float *moments, float normal_bias, const float *placement,
+                    uint32_t n, const float *positions, const float *normals, uint32_t stride_floats, const uint32_t *ids,
+                    const float *view, uint32_t view_stride_floats, const float *spec,
+                    uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
