@@ -82,7 +82,14 @@ glossy pixel and round, default 1 round, drawn from the GGX lobe around the view
 the normal, lit at their hits as gather rays are and summed with the weight F G2 / G1: parallax-correct reflections with the split sum's
 BRDF term and no radiance maps, fw_bake_reflect; every other pixel is shaded as without the flag, --probe-gather
 included; with --direct-light the lights are added at the reflection rays' hits as well; refuses --ao, --probe-split-sum and a file's
-radiance maps in use: pass --probe-no-radiance)."""
+radiance maps in use: pass --probe-no-radiance).
+--area-light S[,ROUNDS] [--area-bias B] (the fixed view lit by the scene's sampled area lights alone, every EmissiveMat sphere and
+axis-aligned rectangle: one first-hit pass of --aov-samples samples, then S shadow rays per pixel, light and round, default 1 round,
+towards points drawn on the light as the pixel sees it, origins moved B >= 0, default 0.001, along the normal: soft shadows without a
+path, fw_bake_area; -s is not used; refuses what --direct-light refuses, and --direct-light).  --probe-lit FILE
+--probe-gather D --area-light S (the final-gather split: the gather rays bring back nothing from those lights, FW_GATHER_NO_LIGHTS, and
+the lights' sampled irradiance is added to the gathered one before shading).  --probe-lit FILE --area-light S without --probe-gather is
+an error: the probes already hold the emitters' direct light, and adding it would count it twice."""
 import argparse
 import sys
 import time
@@ -193,7 +200,36 @@ def main(argv=None):
                     help="with --probe-lit: trace D GGX-sampled reflection rays per glossy pixel and round (default 1 round), lit from the probes at their hits")
     ap.add_argument("--reflect-bias", type=float, default=None, metavar="B",
                     help="with --probe-reflect: move reflection-ray origins B >= 0 world units along the normal (default 0.001)")
+    ap.add_argument("--area-light", default=None, metavar="S[,ROUNDS]",
+                    help="render the direct light of the scene's sphere and rectangle emitters, S shadow rays per pixel, light and round "
+                         "(default 1 round); with --probe-lit and --probe-gather: the final-gather split")
+    ap.add_argument("--area-bias", type=float, default=None, metavar="B",
+                    help="with --area-light: move shadow-ray origins B >= 0 world units along the normal (default 0.001)")
     opt = ap.parse_args(argv)
+    area = None
+    if opt.area_light is not None:
+        if opt.probe_lit is not None and opt.probe_gather is None:
+            ap.error("--probe-lit with --area-light needs --probe-gather: the probes already hold the emitters' direct light, so adding the "
+                     "area lights' to a probe lookup at the pixel would count it twice")
+        if (opt.direct_light and opt.probe_lit is None) or opt.ao is not None or opt.bake_probes is not None or opt.bake_lightmap is not None \
+                or opt.camera != "pinhole" or opt.denoise is not None or opt.orbit or opt.adaptive is not None or opt.progressive > 0 or opt.checkpoint \
+                or opt.temporal is not None:
+            ap.error("--area-light cannot be combined with --direct-light (without --probe-lit), --ao, --bake-probes, --bake-lightmap, --camera, "
+                     "--denoise, --orbit, --adaptive, --progressive, --checkpoint or --temporal")
+        try:
+            area = [int(x) for x in opt.area_light.split(",")]
+        except ValueError:
+            area = []
+        if not 1 <= len(area) <= 2 or not 1 <= area[0] <= 1 << 20 or (len(area) == 2 and area[1] < 1):
+            ap.error("--area-light needs S[,ROUNDS]: 1 <= S <= 2^20, ROUNDS >= 1")
+        if opt.area_bias is not None and not 0.0 <= opt.area_bias < float("inf"):
+            ap.error("--area-bias B needs a finite B >= 0")
+        if opt.aov_samples < 1:
+            ap.error("--aov-samples needs S >= 1")
+        if not opt.output:
+            ap.error("--area-light needs -o FILE.png")
+    elif opt.area_bias is not None:
+        ap.error("--area-bias needs --area-light")
     reflect = None
     if opt.probe_reflect is not None:
         if opt.probe_lit is None:
@@ -577,6 +613,10 @@ def main(argv=None):
         if gather is not None:
             from .api import FinalGather
             final_gather = FinalGather(gather[0], 1e-3 if opt.gather_bias is None else opt.gather_bias).seed(opt.seed)
+        area_light = None
+        if area is not None:
+            from .api import AreaLight
+            area_light = AreaLight(area[0], 1e-3 if opt.area_bias is None else opt.area_bias).seed(opt.seed)
         reflection = None
         if reflect is not None:
             from .api import ReflectionGather
@@ -585,7 +625,16 @@ def main(argv=None):
                                            normal_bias=0.0 if opt.probe_normal_bias is None else opt.probe_normal_bias,
                                            placement=probe_placement, radiance=probe_radiance, maps=probe_maps, direct=direct_light(opt),
                                            ggx_table=ggx_table, gather=final_gather, gather_rounds=gather[1] if gather and len(gather) == 2 else 1,
-                                           reflect=reflection, reflect_rounds=reflect[1] if reflect and len(reflect) == 2 else 1).rgb8
+                                           reflect=reflection, reflect_rounds=reflect[1] if reflect and len(reflect) == 2 else 1,
+                                           area=area_light, area_rounds=area[1] if area and len(area) == 2 else 1).rgb8
+        print(f"Finished Rendering in {int(time.time() - start)} s")
+        print(f'Saving image to "{opt.output}"')
+        save_image(render, opt.output, opt.width, opt.height)
+        return 0
+    if area is not None:
+        from .api import AreaLight
+        area_light = AreaLight(area[0], 1e-3 if opt.area_bias is None else opt.area_bias).seed(opt.seed)
+        render = renderer.render_area(scene, area_light, area[1] if len(area) == 2 else 1, opt.aov_samples, device=opt.device).rgb8
         print(f"Finished Rendering in {int(time.time() - start)} s")
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)

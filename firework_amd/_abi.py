@@ -278,6 +278,27 @@ REFLECT_PROTOTYPES = {
 }
 
 
+# sphere and rectangle emitters sampled at surface points (include/firework_hip.h: fw_scene_area_lights, fw_area_rays, fw_area_reduce,
+# fw_area_mask, fw_bake_area); FW_GATHER_NO_LIGHTS is fw_gather.flags' bit for the gather's complement
+FW_GATHER_NO_LIGHTS = 4
+
+
+class fw_area(C.Structure):
+    _fields_ = [("samples", u32), ("jitter", u32), ("bias", f32), ("chunk_points", u32), ("seed", u64)]
+
+
+# the five prototypes (argument types; every one returns int), applied by _lib.load
+AREA_PROTOTYPES = {
+    "fw_scene_area_lights": [C.c_void_p, C.c_void_p, u32, C.POINTER(u32)],
+    "fw_area_rays": [C.POINTER(fw_area), C.c_void_p, u32, C.c_int, u32, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                     C.c_void_p],
+    "fw_area_reduce": [C.c_int, u32, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_area_mask": [C.c_int, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_bake_area": [C.c_void_p, C.POINTER(fw_area), C.POINTER(fw_trace_params), u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, u32, C.c_void_p,
+                     C.c_void_p, C.POINTER(fw_stats)],
+}
+
+
 # SunSky: an analytic sun-and-sky environment (include/firework_hip.h: fw_check_sky, fw_sky_map, fw_sky_radiance, fw_sky_sun)
 FW_SKY_DISC = 1
 

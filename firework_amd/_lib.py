@@ -133,7 +133,8 @@ def load(preload=False, device=None):
                                    C.c_void_p]
     for name, argtypes in (list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()) + list(A.PROBE_PLACE_PROTOTYPES.items())
                            + list(A.PROBE_RADIANCE_PROTOTYPES.items()) + list(A.DIRECT_PROTOTYPES.items()) + list(A.SKY_PROTOTYPES.items())
-                           + list(A.GGX_TABLE_PROTOTYPES.items()) + list(A.GATHER_PROTOTYPES.items()) + list(A.REFLECT_PROTOTYPES.items())):
+                           + list(A.GGX_TABLE_PROTOTYPES.items()) + list(A.GATHER_PROTOTYPES.items()) + list(A.REFLECT_PROTOTYPES.items())
+                           + list(A.AREA_PROTOTYPES.items())):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
@@ -254,8 +255,13 @@ def selftest_lights(scene_desc):
     _check(lib, lib.fw_selftest_lights(scene_desc.ptr(), None, 0, C.byref(n)))
     out = np.zeros((max(1, n.value), A.FW_LIGHT_RECORD_FLOATS), np.float32)
     _check(lib, lib.fw_selftest_lights(scene_desc.ptr(), out.ctypes.data, n.value, C.byref(n)))
+    return _light_dicts(out[:n.value])
+
+
+def _light_dicts(records):
+    """fw_selftest_lights' records ((Ln, FW_LIGHT_RECORD_FLOATS) float32) as a list of dicts"""
     lights = []
-    for r in out[:n.value]:
+    for r in records:
         d = dict(obj=int(r[0]), kind=int(r[1]), area=float(r[14]), p_pick=float(r[15]))
         if d["kind"] == A.FW_SHAPE_SPHERE:
             d["centre"], d["radius"] = r[2:5].astype(np.float64), float(r[5])
@@ -263,6 +269,17 @@ def selftest_lights(scene_desc):
             d["corners"] = r[2:14].reshape(4, 3).astype(np.float64)
         lights.append(d)
     return lights
+
+
+def light_records(scene_desc):
+    """fw_selftest_lights' records themselves: (Ln, FW_LIGHT_RECORD_FLOATS) float32, what area_rays takes as `lights` (CPU only)"""
+    lib = load()
+    n = C.c_uint32()
+    _check(lib, lib.fw_selftest_lights(scene_desc.ptr(), None, 0, C.byref(n)))
+    out = np.zeros((n.value, A.FW_LIGHT_RECORD_FLOATS), np.float32)
+    if n.value:
+        _check(lib, lib.fw_selftest_lights(scene_desc.ptr(), out.ctypes.data, n.value, C.byref(n)))
+    return out
 
 
 def selftest_emitters(scene_desc):
@@ -1135,6 +1152,79 @@ def reflect_reduce(surface, irradiance, weights, directions, sums, direct=None, 
     return sums
 
 
+def _light_records(lights):
+    """(contiguous (Ln, 16) float32 host array, Ln) of area-light records as light_records / DeviceScene.area_lights return them"""
+    rec = np.ascontiguousarray(np.asarray(lights, np.float32).reshape(-1, A.FW_LIGHT_RECORD_FLOATS))
+    return rec, int(rec.shape[0])
+
+
+def _light_objects(objects):
+    """(contiguous uint32 host array, Ln) of the lights' object indices; area-light records ((Ln, 16) float32) give their first column"""
+    o = np.asarray(objects)
+    if o.ndim == 2:
+        o = o[:, 0]
+    o = np.ascontiguousarray(o.astype(np.uint32).reshape(-1))
+    return o, int(o.size)
+
+
+def area_rays(area, lights, positions, normals, ids=None, round=0, device=0, out=None, weights=None, stream=None):
+    """fw_area_rays: the shadow rays of round `round` of an api.AreaLight from surface points (see _AoPoints) towards points drawn on
+    `lights` ((Ln, 16) float32 records, a host array always), generated on the device: (rays (n * Ln * S, 6) float32 origin +
+    direction, weights (n * Ln * S,) float32), entry (q * Ln + i) * S + s = sample s of light i from point ids[q] (ids None: q); a dead
+    entry is six zeros and the weight 0.  numpy points: returns numpy arrays.  Points on cuda:`device`: generated on `stream`
+    (default: the current torch stream) where they lie; returns device tensors.  out, weights: contiguous float32 arrays or tensors of
+    those shapes to fill instead."""
+    lib = load()
+    a = area.to_abi()
+    rec, ln = _light_records(lights)
+    pts = _AoPoints(positions, normals, ids, device)
+    s = pts.side
+    total = pts.n * ln * int(a.samples)
+    out, weights = s.out(out, (total, 6), "out"), s.out(weights, (total,), "weights")
+    _check(lib, lib.fw_area_rays(C.byref(a), rec.ctypes.data, ln, int(device), int(round), pts.n, pts.pos, pts.nrm, pts.stride, pts.ids,
+                                 *s.ptrs(out, weights), *s.tail(stream)))
+    return out, weights
+
+
+def area_reduce(weights, hits, surface, objects, samples, sums, ids=None, device=0, stream=None):
+    """fw_area_reduce: adds one round's reduction (E.rgb, vis, each rounded to float32 once) of an api.AreaLight to sums[ids[q]] (ids
+    None: sums[q]); sums (M, 4) or (H, W, 4) float32, updated in place.  weights (n * Ln * S,) float32 as area_rays returns them, hits as
+    DeviceScene.trace returns them for those rays, surface (n * Ln * S, 16) float32 as DeviceScene.hit_surface returns it for them: numpy
+    arrays (hits a HIT_DTYPE array), or tensors on cuda:`device`, reduced on `stream` (default: the current torch stream) where they
+    lie.  objects: the Ln lights' object indices (or their records), a host array always.  Returns sums."""
+    lib = load()
+    obj, ln = _light_objects(objects)
+    m = ln * int(samples)
+    total = int(surface.shape[0])
+    if m < 1 or total % m or tuple(surface.shape) != (total, 16) or int(hits.shape[0]) != total:
+        raise ValueError(f"surface must have shape (n * {m}, 16) and hits n * {m} records")
+    n = total // m
+    rows = int(np.prod(tuple(sums.shape)[:-1]))
+    if sums.shape[-1] != 4 or (ids is None and rows < n) or (ids is not None and tuple(ids.shape) != (n,)):
+        raise ValueError(f"sums must have shape (M, 4) or (H, W, 4) with M >= {n}, ids shape ({n},)")
+    s = _Side(surface, device)
+    w, h, rec = s.inp(weights, (total,), "weights"), s.hits(hits, total), s.inp(surface, (total, 16), "surface")
+    s.out(sums, tuple(sums.shape), "sums")
+    i = s.inp(ids, (n,), "ids", "ids", below=rows)
+    _check(lib, lib.fw_area_reduce(int(device), int(samples), obj.ctypes.data, ln, n, *s.ptrs(i, w, h, rec, sums), *s.tail(stream)))
+    return sums
+
+
+def area_mask(hits, surface, objects, device=0, stream=None):
+    """fw_area_mask: rewrites in place — to kind -2, every other float 0 — the records of `surface` ((n, 16) float32, contiguous, the
+    caller's own) whose kind is 3 and whose hit lies on one of `objects` (the lights' object indices or their records, ascending; a host
+    array always).  hits as DeviceScene.trace returned them: numpy arrays, or tensors on cuda:`device`, rewritten on `stream` (default:
+    the current torch stream) where they lie.  Returns surface."""
+    lib = load()
+    obj, ln = _light_objects(objects)
+    n = int(surface.shape[0])
+    s = _Side(surface, device)
+    h = s.hits(hits, n)
+    s.out(surface, (n, 16), "surface")
+    _check(lib, lib.fw_area_mask(int(device), obj.ctypes.data, ln, n, *s.ptrs(h, surface), *s.tail(stream)))
+    return surface
+
+
 def _sky_abi(sky):
     """a fw_sky from an api.SunSky (or a fw_sky, copied)"""
     return sky.to_abi() if hasattr(sky, "to_abi") else A.fw_sky.from_buffer_copy(sky)
@@ -1659,6 +1749,33 @@ class DeviceScene:
                 pts.n, pts.pos, pts.nrm, pts.stride, pts.ids, pts.view, pts.view_stride, pts.spec)
         return self._bake_points(self._lib.fw_bake_reflect, g, pts, 8, head, rounds, first_round, sums, out, seed, use_bvh, stream, rays_per_batch,
                                  flags, out_floats=4)
+
+    def area_lights(self):
+        """fw_scene_area_lights: the records of this resident scene's sampled area lights — every EmissiveMat sphere and axis-aligned
+        rectangle, where fw_scene_update last put them — as (Ln, 16) float32 (object, kind, 12 geometry floats, area, p_pick), in
+        ascending object order: what area_rays takes as `lights`."""
+        n = C.c_uint32()
+        _check(self._lib, self._lib.fw_scene_area_lights(self.handle, None, 0, C.byref(n)))
+        out = np.zeros((n.value, A.FW_LIGHT_RECORD_FLOATS), np.float32)
+        if n.value:
+            _check(self._lib, self._lib.fw_scene_area_lights(self.handle, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def bake_area(self, area, positions, normals, ids=None, rounds=1, first_round=0, sums=None, out=None, seed=0, use_bvh=True, stream=None,
+                  rays_per_batch=0, flags=0, chunk=None):
+        """fw_bake_area: the rounds [first_round, first_round + rounds) of an api.AreaLight at surface points (see _AoPoints: numpy
+        arrays, or tensors on this scene's device, read in place) under this scene's own sampled area lights (area_lights), `chunk`
+        points at a time (None: the description's own setting; 0: automatic).  sums: (M, 4) or (H, W, 4) float32 running sums (Er, Eg,
+        Eb, vis) of the rounds before first_round, updated in place (None: zeros, only with first_round 0); out: an array of the same
+        kind to receive sums / rounds (None: zeros); both are indexed by id, entries outside ids are not touched.  Returns (out, sums,
+        stats): host arrays for numpy points, device tensors — baked on `stream` (default: the current torch stream) — for device
+        points."""
+        a = area.to_abi()
+        if chunk is not None:
+            a.chunk_points = int(chunk)
+        pts = _AoPoints(positions, normals, ids, self.device)
+        return self._bake_points(self._lib.fw_bake_area, a, pts, 4, (pts.n, pts.pos, pts.nrm, pts.stride, pts.ids), rounds, first_round, sums, out,
+                                 seed, use_bvh, stream, rays_per_batch, flags)
 
     def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,
                       flags=0, chunk=None, on_device=False):

@@ -2971,11 +2971,13 @@ class FinalGather:
     """One bounce of gather rays lit from baked probes (fw_gather): `directions` cosine-weighted hemisphere rays per point
     and round, origins moved `bias` along the normal; each ray brings back the emission of the emitter it hit, the environment where it
     missed, or hit albedo x E(hit) / pi with E from the probes at the hit.  direct=True adds the scene's point, spot and directional
-    lights at the gather hits, their shadow rays moved direct_bias along the hit's normal.  .seed(s) / .jitter(on) as builders;
-    chunk_points as fw_gather's."""
+    lights at the gather hits, their shadow rays moved direct_bias along the hit's normal.  no_lights=True (FW_GATHER_NO_LIGHTS) is the
+    complement of an AreaLight: a ray that hits one of the scene's sampled area lights brings back nothing.  .seed(s) / .jitter(on) as
+    builders; chunk_points as fw_gather's."""
 
-    def __init__(self, directions: int = 64, bias: float = 1e-3, direct: bool = False, direct_bias: float = 1e-3):
+    def __init__(self, directions: int = 64, bias: float = 1e-3, direct: bool = False, direct_bias: float = 1e-3, no_lights: bool = False):
         self.directions, self.bias, self.direct, self.direct_bias = int(directions), float(np.float32(bias)), bool(direct), float(np.float32(direct_bias))
+        self.no_lights = bool(no_lights)
         self._seed, self._jitter, self.chunk_points = 0, True, 0
 
     def seed(self, s):
@@ -3003,7 +3005,8 @@ class FinalGather:
     def to_abi(self) -> A.fw_gather:
         g = A.fw_gather()
         g.directions, g.jitter, g.bias, g.direct_bias = self.directions & 0xFFFFFFFF, int(self._jitter), self.bias, self.direct_bias
-        g.flags, g.chunk_points, g.seed = (A.FW_GATHER_DIRECT if self.direct else 0), int(self.chunk_points), self._seed & 0xFFFFFFFFFFFFFFFF
+        g.flags = (A.FW_GATHER_DIRECT if self.direct else 0) | (A.FW_GATHER_NO_LIGHTS if getattr(self, "no_lights", False) else 0)
+        g.chunk_points, g.seed = int(self.chunk_points), self._seed & 0xFFFFFFFFFFFFFFFF
         return g
 
 
@@ -3258,6 +3261,181 @@ def reflect_resolve(sums, spec, rounds: int) -> np.ndarray:
     with np.errstate(all="ignore"):
         S = (f0 * s[..., 0:3] + s[..., 4:7]) / float(rounds)
         return np.concatenate([S, s[..., 3:4] / float(rounds)], axis=-1).astype(np.float32)
+
+
+# --------------------------------------------------------------------------- area lights at surface points (fw_bake_area)
+class AreaLight:
+    """The direct light of a scene's sampled area lights — every EmissiveMat sphere and axis-aligned rectangle — at surface points
+    (fw_area): `samples` shadow rays per point, light and round towards points drawn on the light as the point sees it,
+    origins moved `bias` along the normal.  .seed(s) / .jitter(on) as builders; chunk_points as fw_area's."""
+
+    def __init__(self, samples: int = 16, bias: float = 1e-3):
+        self.samples, self.bias = int(samples), float(np.float32(bias))
+        self._seed, self._jitter, self.chunk_points = 0, True, 0
+
+    def seed(self, s):
+        self._seed = int(s)
+        return self
+
+    def jitter(self, on=True):
+        self._jitter = bool(on)
+        return self
+
+    def check(self):
+        """what fw_area_rays rejects in a description, as a ValueError, in its order"""
+        if not 1 <= self.samples <= 1 << 20:
+            raise ValueError("samples must be in 1..2^20")
+        if not (np.isfinite(self.bias) and self.bias >= 0.0):
+            raise ValueError("bias must be finite and >= 0")
+        return self
+
+    def to_abi(self) -> A.fw_area:
+        a = A.fw_area()
+        a.samples, a.jitter, a.bias = self.samples & 0xFFFFFFFF, int(self._jitter), self.bias
+        a.chunk_points, a.seed = int(self.chunk_points), self._seed & 0xFFFFFFFFFFFFFFFF
+        return a
+
+
+def _dotd(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def area_rays(area: "AreaLight", lights, positions, normals, ids=None, round: int = 0, device=None):
+    """The numpy statement of fw_area_rays: (rays (n * Ln * S, 6) float32, weights (n * Ln * S,) float32), entry (q * Ln + i) * S + s =
+    sample s of light i ((Ln, 16) float32 records: object, kind, 12 geometry floats, area, p_pick) from point id = ids[q] (ids None: q)
+    of positions and normals, (M, 3) float32 each (device: see panorama_rays; the weights stay numpy).  Float64 from the float32 inputs
+    in the header's order, one rounding to float32; a dead entry is six zeros and the weight 0."""
+    S = int(area.samples)
+    if S < 1:
+        raise ValueError("samples must be >= 1")
+    L = np.asarray(lights, np.float32).reshape(-1, A.FW_LIGHT_RECORD_FLOATS)
+    Ln = L.shape[0]
+    P, Nn = np.asarray(positions, np.float32).reshape(-1, 3), np.asarray(normals, np.float32).reshape(-1, 3)
+    ids = np.arange(P.shape[0], dtype=np.uint32) if ids is None else np.asarray(ids, np.uint32).reshape(-1)
+    at = ids.astype(np.int64)
+    n = at.size
+    p32, n32 = P[at], Nn[at]
+    usable = ao_usable(p32, n32)[:, None, None]                                              # (n, 1, 1), broadcast over (n, Ln, S)
+    item = (at[:, None] * Ln + np.arange(Ln, dtype=np.int64)[None, :]).reshape(-1)
+    xi = (texel_jitter(area._seed, round, item) if area._jitter else np.full((n * Ln, 2), 0.5)).reshape(n, Ln, 1, 2)
+    s = np.arange(S, dtype=np.float64)[None, None, :]
+    G = 0.6180339887498949
+    PI = 3.141592653589793
+    Lg = L.astype(np.float64)
+    kind = L[:, 1][None, :, None]
+    with np.errstate(all="ignore"):
+        a1 = (s + xi[..., 0]) / float(S)
+        u1 = a1 - np.floor(a1)
+        a2 = s * G + xi[..., 1]
+        u2 = a2 - np.floor(a2)
+        r = n32.astype(np.float64)
+        rl = np.sqrt((r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]) + r[:, 2] * r[:, 2])
+        nh = [(r[:, k] / rl)[:, None, None] for k in range(3)]
+        p = [p32[:, k].astype(np.float64)[:, None, None] for k in range(3)]
+        bias = float(F32(area.bias))
+        o = p if area.bias == 0.0 else [p[k] + bias * nh[k] for k in range(3)]
+        # rectangles
+        c0 = [Lg[:, 2 + k][None, :, None] for k in range(3)]
+        e1 = [Lg[:, 5 + k][None, :, None] - c0[k] for k in range(3)]
+        e2 = [Lg[:, 11 + k][None, :, None] - c0[k] for k in range(3)]
+        dr = [((c0[k] + u1 * e1[k]) + u2 * e2[k]) - o[k] for k in range(3)]
+        nl = [e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]]
+        Ar = np.sqrt(_dotd(nl, nl))
+        d2 = _dotd(dr, dr)
+        dl = np.sqrt(d2)
+        w = [dr[k] / dl for k in range(3)]
+        cr_r = _dotd(nh, w)
+        cl = np.abs(_dotd(nl, w) / Ar)
+        g_r = ((cr_r * cl) * Ar) / d2
+        live_r = (cr_r > 0.0) & (Ar > 0.0)
+        # spheres
+        v = [c0[k] - o[k] for k in range(3)]
+        dv = _dotd(v, v)
+        rr = Lg[:, 5][None, :, None]
+        r2 = rr * rr
+        s2 = r2 / dv
+        cmax = np.sqrt(1.0 - s2)
+        omc = s2 / (1.0 + cmax)
+        om = u1 * omc
+        ct = 1.0 - om
+        st = np.sqrt(np.fmax(om * (2.0 - om), 0.0))
+        phi = (2.0 * PI) * u2
+        lx, ly = st * np.cos(phi), st * np.sin(phi)
+        dist = np.sqrt(dv)
+        wv = [v[k] / dist for k in range(3)]
+        sg = np.copysign(1.0, wv[2])
+        a = -1.0 / (sg + wv[2])
+        b = (wv[0] * wv[1]) * a
+        T = (1.0 + (sg * (wv[0] * wv[0])) * a, sg * b, -sg * wv[0])
+        B = (b, sg + (wv[1] * wv[1]) * a, -wv[1])
+        ex = [(lx * T[k] + ly * B[k]) + ct * wv[k] for k in range(3)]
+        bb = _dotd(ex, v)
+        tt = bb - np.sqrt(np.fmax(bb * bb - (dv - r2), 0.0))
+        ds = [tt * ex[k] for k in range(3)]
+        dls = np.sqrt(_dotd(ds, ds))
+        cr_s = _dotd(nh, [ds[k] / dls for k in range(3)])
+        g_s = (cr_s * (2.0 * PI)) * omc
+        live_s = (dv > r2) & (cr_s > 0.0)
+        sphere = np.broadcast_to(kind == 0, g_s.shape)
+        g = np.where(sphere, g_s, g_r)
+        d = np.stack([np.where(sphere, ds[k], dr[k]) for k in range(3)], axis=-1)
+        o3 = np.stack([np.broadcast_to(o[k], g.shape) for k in range(3)], axis=-1)
+        gf, df, of = g.astype(np.float32), d.astype(np.float32), o3.astype(np.float32)
+        live = (usable & np.where(sphere, live_s, live_r) & np.isfinite(g) & (gf > 0) & np.isfinite(gf) & np.all(np.isfinite(df), axis=-1)
+                & np.all(np.isfinite(of), axis=-1) & np.any(df != 0, axis=-1))
+    weights = np.where(live, gf, np.float32(0)).astype(np.float32).reshape(-1)
+    of = np.where(live[..., None], of, np.float32(0)).reshape(-1, 3)
+    df = np.where(live[..., None], df, np.float32(0)).reshape(-1, 3)
+    return _rays_out(of, df, device), weights
+
+
+def area_reduce(weights, hits_object, surface, objects, samples: int) -> np.ndarray:
+    """The numpy float64 statement of fw_area_reduce: (n, 4) float64, (1 / S) x the accumulators E.rgb and (1 / M) x V of one round
+    before their one rounding to float32, for weights (n * M,) float32, the hits' object column (uint32), surface (n * M, 16) float32
+    records and the Ln lights' object indices, M = Ln * S, summed in the device's order (G partial sums, an xor butterfly)."""
+    S = int(samples)
+    obj = np.asarray(objects).astype(np.uint32).reshape(-1)
+    M = obj.size * S
+    w = np.asarray(weights, np.float32).reshape(-1, M)
+    n = w.shape[0]
+    h = np.asarray(hits_object).astype(np.uint32).reshape(n, M)
+    s = np.asarray(surface, np.float32).reshape(n, M, 16)
+    counts = (w > 0) & (h == np.repeat(obj, S)[None, :]) & (s[..., 3] == np.float32(3))
+    with np.errstate(all="ignore"):
+        term = np.concatenate([s[..., 12:15].astype(np.float64) * w.astype(np.float64)[..., None], np.ones((n, M, 1))], axis=-1)
+    G = 1
+    while G < min(M, 64):
+        G *= 2
+    rows = -(-M // G)                                                                        # lane l takes m = l, l + G, ... in ascending order
+    padded = np.zeros((n, rows * G, 4))
+    padded[:, :M] = term
+    take = np.zeros((n, rows * G), bool)
+    take[:, :M] = counts
+    part = np.zeros((n, G, 4))
+    with np.errstate(all="ignore"):
+        for row, on in zip(padded.reshape(n, rows, G, 4).transpose(1, 0, 2, 3), take.reshape(n, rows, G).transpose(1, 0, 2)):
+            part = np.where(on[..., None], part + row, part)                                 # (an entry that does not count adds nothing)
+        m = G // 2
+        while m >= 1:
+            part = part + part[:, np.arange(G) ^ m]
+            m //= 2
+        return np.concatenate([(1.0 / S) * part[:, 0, 0:3], (1.0 / M) * part[:, 0, 3:4]], axis=-1)
+
+
+def area_resolve(sums, rounds: int) -> np.ndarray:
+    """The statement of k_area_resolve: (..., 4) float32 (E.rgb, vis) = float32(sums / rounds) from the float32 running sums."""
+    with np.errstate(all="ignore"):
+        return (np.asarray(sums, np.float32).astype(np.float64) / float(rounds)).astype(np.float32)
+
+
+def area_mask(hits_object, surface, objects) -> np.ndarray:
+    """The statement of fw_area_mask: a copy of surface ((n, 16) float32) in which every record of kind 3 whose hit's object is one of
+    `objects` is (kind -2, every other float 0); every other record keeps its bits."""
+    s = np.array(np.asarray(surface, np.float32).reshape(-1, 16))
+    hit = (s[:, 3] == np.float32(3)) & np.isin(np.asarray(hits_object).astype(np.uint32).reshape(-1), np.asarray(objects).astype(np.uint32))
+    s[hit] = 0
+    s[hit, 3] = -2
+    return s
 
 
 # --------------------------------------------------------------------------- direct light of delta lights (fw_bake_direct; DESIGN.md §9w)
@@ -4037,13 +4215,52 @@ class Renderer:
                 ds.close()
         return RenderResult(rgb8.cpu().numpy(), gam.cpu().numpy(), lin.cpu().numpy(), stats, w, h)
 
-    def _gather(self, ds, gather: "FinalGather", rounds, grid, d_sh, aov, depth, d_mom, normal_bias, d_pl, direct=None):
+    def _area(self, ds, area: "AreaLight", rounds, aov):
+        """(out (N, 4), sums (N, 4)) device tensors: fw_bake_area on the records `aov` in place (stride 12, aov + 8 / aov + 4) with this
+        renderer's seed, use_bvh and flags.  The call's stats are kept in self.area_stats."""
+        s = self.settings
+        out, sums, self.area_stats = ds.bake_area(area, aov[:, 8:11], aov[:, 4:7], None, rounds, seed=s["seed"], use_bvh=s["use_bvh"], flags=s["flags"])
+        return out, sums
+
+    def render_area(self, scene, area: "AreaLight", rounds: int = 1, aov_samples: int = 1, model: "CameraModel" = None, device: int = 0) -> RenderResult:
+        """This renderer's view lit by the scene's sampled area lights alone — every EmissiveMat sphere and axis-aligned rectangle — by
+        light sampling (not in the reference; fw_bake_area): soft shadows without a path.  The first-hit guide buffers
+        (fw_render_aovs at `aov_samples` samples; with `model`, fw_render_model_aovs) stay on the device and fw_bake_area reads each
+        pixel's position and normal from the records in place, `rounds` rounds of area.samples shadow rays per light with this
+        renderer's seed (+ the round), use_bvh and flags.  With E its out the frame is, as render_direct composes a diffuse pixel,
+        a ((v E) float32(1 / pi)) in float32, resolved by fw_denoise at 0 iterations.  The emitters themselves, every other emitter, the
+        environment and indirect light are not in it.  The call's stats are kept in self.area_stats.  `scene`: a Scene, a SceneDesc or
+        an uploaded _lib.DeviceScene."""
+        import torch
+        from . import _lib
+        area.check()
+        s = self.settings
+        w, h = (int(model.width), int(model.height)) if model is not None else (int(s["width"]), int(s["height"]))
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            aov = torch.empty((w * h, 12), dtype=torch.float32, device=torch.device("cuda", ds.device))
+            if model is not None:
+                ds.model_aovs(model, aov_samples, seed=s["seed"], use_bvh=s["use_bvh"], out=aov)
+            else:
+                ds.aovs(self, aov_samples, out=aov)
+            E = self._area(ds, area, rounds, aov)[0]
+            term = aov[:, 0:3] * ((aov[:, 3:4] * E[:, 0:3]) * float(np.float32(1.0 / np.pi)))
+            rgb8, gam, lin = _lib.denoise(term.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
+            stats = dict(ds.aovs_stats)
+        finally:
+            if ds is not scene:
+                ds.close()
+        return RenderResult(rgb8.cpu().numpy(), gam.cpu().numpy(), lin.cpu().numpy(), stats, w, h)
+
+    def _gather(self, ds, gather: "FinalGather", rounds, grid, d_sh, aov, depth, d_mom, normal_bias, d_pl, direct=None, no_lights=False):
         """(out (N, 4), sums (N, 4)) device tensors: fw_bake_gather on the records `aov` in place (stride 12, aov + 8 / aov + 4) with this
-        renderer's seed, use_bvh and flags; with `direct`, a DirectLight, FW_GATHER_DIRECT with its bias.  The call's stats are kept in
-        self.gather_stats."""
+        renderer's seed, use_bvh and flags; with `direct`, a DirectLight, FW_GATHER_DIRECT with its bias; with no_lights,
+        FW_GATHER_NO_LIGHTS.  The call's stats are kept in self.gather_stats."""
         import copy
         s = self.settings
         g = copy.copy(gather)
+        if no_lights:
+            g.no_lights = True
         if direct is not None:
             g.direct, g.direct_bias = True, direct.bias
         out, sums, self.gather_stats = ds.bake_gather(g, grid, d_sh, aov[:, 8:11], aov[:, 4:7], None, depth, d_mom, normal_bias, d_pl, rounds,
@@ -4147,7 +4364,8 @@ class Renderer:
                          depth: "ProbeDepth" = None, moments=None, normal_bias: float = 0.0, ao: "AmbientOcclusion" = None,
                          ao_rounds: int = 1, placement=None, radiance: "ProbeRadiance" = None, maps=None,
                          direct: "DirectLight" = None, ggx_table: "GgxTable" = None, table=None, gather: "FinalGather" = None,
-                         gather_rounds: int = 1, reflect: "ReflectionGather" = None, reflect_rounds: int = 1) -> RenderResult:
+                         gather_rounds: int = 1, reflect: "ReflectionGather" = None, reflect_rounds: int = 1, area: "AreaLight" = None,
+                         area_rounds: int = 1) -> RenderResult:
         """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
         (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
         from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
@@ -4186,9 +4404,19 @@ class Renderer:
         every other pixel keeps the linear value of the branch above that ran (plain, depth, placement or gather); the frame is
         resolved by fw_denoise at 0 iterations.  With direct, the lights are added at the reflection rays' hits as well
         (FW_REFLECT_DIRECT with direct's bias), and the receivers' own term is added as above.  The call's stats are kept in
-        self.reflect_stats.  reflect together with radiance or ao: ValueError.  reflect=None: the calls and the bits above."""
+        self.reflect_stats.  reflect together with radiance or ao: ValueError.  reflect=None: the calls and the bits above.  area (an
+        AreaLight), with gather: the final-gather split — the gather runs with FW_GATHER_NO_LIGHTS, so its rays bring
+        back nothing from the scene's sampled area lights, fw_bake_area runs `area_rounds` rounds on the records in place, and its
+        out's E is added in float32 to Eg before the gathered frame is shaded: out_c = a_c (v ((Eg_c + Ea_c) float32(1 / pi)) + (1 -
+        v)).  The call's stats are kept in self.area_stats.  area without gather: ValueError, because the probes' SH already holds the
+        emitters' direct light and adding it would count it twice.  area=None: the calls and the bits above."""
         import torch
         from . import _lib
+        if area is not None:
+            if gather is None:
+                raise ValueError("area needs gather: the probes' SH already holds the emitters' direct light, so adding the area lights' "
+                                 "to a probe lookup at the pixel would count it twice")
+            area.check()
         if direct is not None:
             direct.check()
         if reflect is not None:
@@ -4236,9 +4464,11 @@ class Renderer:
                 d_pl = torch.from_numpy(np.ascontiguousarray(np.asarray(placement, np.float32).reshape(grid.n_probes, 4))).to(dev)
             rays = None
             if gather is not None:
-                Eg = self._gather(ds, gather, gather_rounds, grid, d_sh, aov, depth, d_mom, normal_bias, d_pl, direct)[0]
+                Eg = self._gather(ds, gather, gather_rounds, grid, d_sh, aov, depth, d_mom, normal_bias, d_pl, direct, area is not None)[0][:, 0:3]
+                if area is not None:
+                    Eg = Eg + self._area(ds, area, area_rounds, aov)[0][:, 0:3]
                 v = aov[:, 3:4]
-                lit = aov[:, 0:3] * (v * (Eg[:, 0:3] * float(np.float32(1.0 / np.pi))) + (1.0 - v))
+                lit = aov[:, 0:3] * (v * (Eg * float(np.float32(1.0 / np.pi))) + (1.0 - v))
                 rgb8, gam, lin = _lib.denoise(lit.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
             elif ao is not None:
                 occ, _sums, self.ao_stats = ds.bake_ao(ao, aov[:, 8:11], aov[:, 4:7], None, ao_rounds, seed=s["seed"], use_bvh=s["use_bvh"],

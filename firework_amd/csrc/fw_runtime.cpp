@@ -24,6 +24,7 @@
 #include "fw_ggx_table.h"
 #include "fw_gather.h"
 #include "fw_reflect.h"
+#include "fw_area.h"
 #include "fw_defer_pretest.h"
 
 #include <algorithm>
@@ -1023,6 +1024,8 @@ struct fw_scene {
     double ms_objects = 0, ms_objects_dev = 0;   // the last object-level build: host wall time, device tree builds (FIREWORK_TRACE)
     DevBuf lights;                // the sampled lights' object indices (fw::DLights.obj; FW_FLAG_LIGHT_SAMPLING)
     uint32_t n_lights = 0;
+    std::vector<float> light_recs;   // the same lights as fw_selftest_lights' records (fw_scene_area_lights), and their device copy (k_area_rays)
+    DevBuf area_recs;
     bool ls_vertices = false;     // some material is Lambertian, Isotropic or Ggx: a vertex that samples lights can occur
     bool has_ggx = false;         // some material is a GgxMat: the frame launches the k_shade_gx kernels
     // the HDR map's sampling table (fw::DEnvDist: cdf_m, cdf_c, dens; FW_FLAG_ENV_SAMPLING), built on the device by the first
@@ -1048,6 +1051,7 @@ struct fw_scene {
         data.release();
         obj_data.release();
         lights.release();
+        area_recs.release();
         env_dist.release();
         emitters.release();
     }
@@ -1591,6 +1595,12 @@ static std::vector<LightRec> scene_lights(const fw_scene_desc *d) {
     for (LightRec &r : out) r.p_pick = 1.f / (float)out.size();
     return out;
 }
+// a record as fw_selftest_lights and fw_scene_area_lights return it and k_area_rays reads it: FW_LIGHT_RECORD_FLOATS floats
+static void light_record_floats(const LightRec &l, float *r) {
+    r[0] = (float)l.obj; r[1] = (float)l.kind;
+    std::memcpy(r + 2, l.pts, sizeof l.pts);
+    r[14] = l.area; r[15] = l.p_pick;
+}
 // FW_FLAG_ALL_EMITTERS: an EmissiveMat's power, max(r, g, b) of a ConstantTexture with a negative or non-finite channel
 // counted as 0, and 1 for any other texture
 static double emitter_power(const fw_scene_desc *d, const fw_material &m) {
@@ -1646,6 +1656,10 @@ static int upload_lights(fw_scene *sc, const fw_scene_desc *d) {
     std::vector<uint32_t> objs(L.size());
     for (size_t i = 0; i < L.size(); i++) objs[i] = L[i].obj;
     if (int rc = sc->lights.upload(objs.data(), objs.size() * 4)) return rc;
+    std::vector<float> recs(L.size() * FW_LIGHT_RECORD_FLOATS);
+    for (size_t i = 0; i < L.size(); i++) light_record_floats(L[i], &recs[i * FW_LIGHT_RECORD_FLOATS]);
+    if (int rc = sc->area_recs.upload(recs.data(), recs.size() * 4)) return rc;
+    sc->light_recs.swap(recs);
     sc->n_lights = (uint32_t)L.size();
     sc->ls_vertices = false;
     sc->has_ggx = false;
@@ -2009,12 +2023,12 @@ int update_scene_impl(fw_scene *sc, const fw_scene_desc *desc) {
         const auto t0 = now();
         fw_scene *ns = nullptr;
         if (int rc = create_scene_impl(desc, sc->device, &ns, &reach)) return rc;
-        DevBuf old_data = sc->data, old_obj = sc->obj_data, old_lights = sc->lights, kept_env = sc->env_dist, old_emitters = sc->emitters;
+        DevBuf old_data = sc->data, old_obj = sc->obj_data, old_lights = sc->lights, old_area = sc->area_recs, kept_env = sc->env_dist, old_emitters = sc->emitters;
         const int kept_env_state = sc->env_state; const double kept_env_ms = sc->env_build_ms;
         const DevBuf kept_dl = sc->dlights; const uint32_t kept_n_dl = sc->n_dlights;     // (the delta lights stay: `ns` has none, and frees none)
         *sc = *ns;
         sc->dlights = kept_dl; sc->n_dlights = kept_n_dl;                                     // (the handle stays the caller's; its DevBufs now name the new allocations)
-        ns->data = old_data; ns->obj_data = old_obj; ns->lights = old_lights;   // ... and the old ones go with `ns`
+        ns->data = old_data; ns->obj_data = old_obj; ns->lights = old_lights; ns->area_recs = old_area;   // ... and the old ones go with `ns`
         // (the emitters' table is built again for the new scene, whose triangles are new allocations: the old one goes with `ns`)
         ns->emitters = old_emitters;
         // (the environment's table stays: the map is the same)
@@ -5177,6 +5191,7 @@ struct HitLight {
     fw_scene *sc; const fw_trace_params *tp; const Staged &st; HitLightSlots s; uint32_t D, Ln; float direct_bias;
     const ProbeLookup &L; const fw::DProbeVis *vis; const float *d_sh, *d_pl; fw_stats *total;
     int rc = FW_OK;
+    const uint32_t *mask_objs = nullptr; uint32_t n_mask = 0;      // FW_GATHER_NO_LIGHTS: the scene's sampled lights, masked out of the records
     float *surf() const { return st.ptr<float>(s.surf); }
     float *irr() const { return st.ptr<float>(s.irr); }
     // the chunk [q0, q0 + k) of round `round`: fills surf() and irr(); returns the chunk's direct records (fw_bake_direct's out), or NULL
@@ -5186,6 +5201,7 @@ struct HitLight {
         const uint32_t kd = k * D;
         float *d_surf = surf();
         fw::launch_hit_surface(stream, sc->n_cus, sc->d, sc->n_mat, rays, (const float4 *)hits, kd, (float4 *)d_surf);
+        if (n_mask) fw::launch_area_mask(stream, n_cus, kd, mask_objs, n_mask, hits, d_surf);
         fw::launch_probe_irradiance(stream, L.g, vis, d_sh, d_pl, kd, d_surf + 8, d_surf + 4, 16, irr());
         if (!Ln) return nullptr;
         fw::DDirect dd{};
@@ -5225,7 +5241,7 @@ int bake_gather_impl(fw_scene *sc, const fw_gather *g, const fw_trace_params *tp
     ProbeLookup L;
     if (int rc = probe_lookup_check(grid, a, !sh, false, L)) return rc;
     if (tp->on_device && (((uintptr_t)sh | (uintptr_t)moments | (uintptr_t)placement) & 3u)) return fail(FW_ERR_BAD_ARG, "device sh, moments and placement must be 4-byte aligned");
-    if (g->flags & ~(uint32_t)FW_GATHER_DIRECT) return fail(FW_ERR_BAD_ARG, "unknown gather flags");
+    if (g->flags & ~(uint32_t)(FW_GATHER_DIRECT | FW_GATHER_NO_LIGHTS)) return fail(FW_ERR_BAD_ARG, "unknown gather flags");
     const uint32_t D = g->directions;
     if ((uint64_t)N * D >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
     if (int rc = probe_lookup_sizes(a, L)) return rc;
@@ -5257,6 +5273,7 @@ int bake_gather_impl(fw_scene *sc, const fw_gather *g, const fw_trace_params *tp
     ao.directions = D; ao.falloff = 0; ao.radius = std::numeric_limits<float>::infinity(); ao.bias = g->bias; ao.jitter = g->jitter; ao.seed = g->seed;
     fw_stats total{};
     HitLight hl{sc, tp, st, hs, D, Ln, g->direct_bias, L, a.vis ? &vis : nullptr, st.ptr<const float>(t.sh), st.ptr<const float>(t.pl), stats ? &total : nullptr};
+    if (g->flags & FW_GATHER_NO_LIGHTS) { hl.mask_objs = (const uint32_t *)sc->lights.p; hl.n_mask = sc->n_lights; }
     uint32_t round = first_round;              // the reducer's round: trace_rounds hands it to the generator only
     const TraceRounds b{N, D, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
     if (int rc = trace_rounds(sc, tp, b, first_round, rounds, stats ? &total : nullptr,
@@ -5420,6 +5437,177 @@ int bake_reflect_impl(fw_scene *sc, const fw_reflect *g, const fw_trace_params *
     if (hl.rc) return hl.rc;
     if (int rc = st.download(i_sums)) return rc;
     if (out) fw::launch_reflect_resolve(stream, N, (double)((uint64_t)first_round + rounds), d_ids, st.ptr<const float>(slots.spec), d_sums, st.ptr<float>(i_out));
+    if (int rc = st.finish()) return rc;
+    stats_finish(stats, total, wall0);
+    return FW_OK;
+}
+
+// ---- sphere and rectangle emitters sampled at surface points (include/firework_hip.h) ------------------------------
+// A description's own argument checks (FW_ERR_BAD_ARG only)
+int area_check(const fw_area *ap) {
+    if (ap->samples == 0 || ap->samples > (1u << 20)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^20");
+    if (!std::isfinite(ap->bias) || ap->bias < 0.f) return fail(FW_ERR_BAD_ARG, "bias must be finite and >= 0");
+    return FW_OK;
+}
+// caller-made light records: a count in 1..FW_MAX_LIGHTS and a shape kind that fw_selftest_lights writes in each
+int area_lights_check(const float *lights, uint32_t n_lights) {
+    if (n_lights == 0 || n_lights > FW_MAX_LIGHTS) return fail(FW_ERR_BAD_ARG, "n_lights must be in 1..FW_MAX_LIGHTS");
+    for (uint32_t i = 0; i < n_lights; i++) {
+        const float k = lights[(size_t)i * FW_LIGHT_RECORD_FLOATS + 1];
+        if (!(k == 0.f || k == 1.f || k == 2.f || k == 3.f)) return fail(FW_ERR_BAD_ARG, "lights[" + std::to_string(i) + "]: unknown kind");
+    }
+    return FW_OK;
+}
+// a list of light objects: a count in 1..FW_MAX_LIGHTS, strictly ascending where the call searches it
+int area_objects_check(const uint32_t *objects, uint32_t n_objects, bool ascending) {
+    if (n_objects == 0 || n_objects > FW_MAX_LIGHTS) return fail(FW_ERR_BAD_ARG, "n_objects must be in 1..FW_MAX_LIGHTS");
+    if (ascending) for (uint32_t i = 1; i < n_objects; i++) if (!(objects[i - 1] < objects[i])) return fail(FW_ERR_BAD_ARG, "objects must ascend strictly");
+    return FW_OK;
+}
+fw::DAreaRays area_rays_device(const fw_area *ap, uint32_t round, const fw::DAoPoints &pts, const float4 *lights, uint32_t n_lights, uint32_t first) {
+    fw::DAreaRays d{};
+    d.pts = pts; d.lights = lights; d.n_lights = n_lights; d.samples = ap->samples; d.first = first;
+    d.seed32 = seed32_of(ap->seed);
+    d.jitter = ap->jitter ? 1u : 0u;
+    d.round = round; d.bias = ap->bias;
+    return d;
+}
+
+// fw_scene_area_lights: the records kept with the scene since its creation or its last update
+int scene_area_lights_impl(fw_scene *sc, float *out, uint32_t cap, uint32_t *n) {
+    if (!sc || !n || (!out && cap > 0)) return fail(FW_ERR_BAD_ARG, "null argument");
+    *n = sc->n_lights;
+    const size_t k = std::min<size_t>(cap, sc->n_lights);
+    if (k) std::memcpy(out, sc->light_recs.data(), k * FW_LIGHT_RECORD_FLOATS * 4);
+    return FW_OK;
+}
+
+// fw_area_rays: fw_reflect_rays' shape — the light records are the caller's host array, staged with the points
+int area_rays_impl(const fw_area *ap, const float *lights, uint32_t n_lights, int device, uint32_t round, uint32_t n, const float *positions,
+                   const float *normals, uint32_t stride, const uint32_t *ids, float *rays, float *weights, int on_device, void *stream_) {
+    if (!ap || !lights || !positions || !normals || !rays || !weights) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = area_check(ap)) return rc;
+    if (int rc = area_lights_check(lights, n_lights)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (on_device && (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids | (uintptr_t)rays | (uintptr_t)weights) & 3u))
+        return fail(FW_ERR_BAD_ARG, "device arrays must be 4-byte aligned");
+    const uint64_t M = (uint64_t)n_lights * ap->samples;
+    if ((uint64_t)n * M >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x n_lights x samples must be below 2^31");
+    const uint64_t extent = on_device ? n : ao_extent(n, ids);
+    if (extent * n_lights >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "id x n_lights must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n_cus = device_cus(device);
+    Staged st(device, stream, on_device != 0);
+    const AoSlots slots = ao_points_stage(st, n, positions, normals, stride, ids, extent);
+    const int i_rec = st.add(Staged::IN, lights, (size_t)n_lights * 64, true);
+    HostSlabs sl(st, n, (size_t)M * 28);
+    const int a_rays = sl.out(rays, (size_t)M * 24), a_w = sl.out(weights, (size_t)M * 4);
+    if (int rc = st.up()) return rc;
+    const fw::DAoPoints pts = ao_points_device(st, slots, stride);
+    return sl.run([&](uint32_t done, uint32_t k) {
+        fw::launch_area_rays(stream, n_cus, area_rays_device(ap, round, pts, st.ptr<const float4>(i_rec), n_lights, done), k, sl.ptr<float>(a_rays),
+                             sl.ptr<float>(a_w));
+    });
+}
+
+// fw_area_reduce: fw_gather_reduce's shape with the weights, the hits and the lights' objects
+int area_reduce_impl(int device, uint32_t S, const uint32_t *objects, uint32_t n_objects, uint32_t n, const uint32_t *ids, const float *weights,
+                     const fw_hit *hits, const float *surface, float *sums, int on_device, void *stream_) {
+    if (!objects || !weights || !hits || !surface || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (S == 0 || S > (1u << 20)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^20");
+    if (int rc = area_objects_check(objects, n_objects, false)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (on_device && ((((uintptr_t)sums | (uintptr_t)hits | (uintptr_t)surface) & 15u) || (((uintptr_t)weights | (uintptr_t)ids) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums, hits and surface must be 16-byte aligned, device weights and ids 4-byte aligned");
+    const uint64_t M = (uint64_t)n_objects * S;
+    if ((uint64_t)n * M >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x n_objects x samples must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t entries = (size_t)n * M;
+    Staged st(device, stream, on_device != 0);
+    const int i_obj = st.add(Staged::IN, objects, (size_t)n_objects * 4, true), i_w = st.add(Staged::IN, weights, entries * 4),
+              i_hits = st.add(Staged::IN, hits, entries * sizeof(fw_hit)), i_surf = st.add(Staged::IN, surface, entries * 64),
+              i_sums = st.add(Staged::INOUT, sums, on_device ? 0 : (size_t)ao_extent(n, ids) * 16), i_ids = st.add(Staged::IN, ids, (size_t)n * 4);
+    if (int rc = st.up()) return rc;
+    fw::launch_area_reduce(stream, device_cus(device), 0, n, n_objects, S, st.ptr<const uint32_t>(i_ids), st.ptr<const uint32_t>(i_obj),
+                           st.ptr<const float>(i_w), st.ptr<const fw_hit>(i_hits), st.ptr<const float>(i_surf), st.ptr<float>(i_sums));
+    return st.finish();
+}
+
+// fw_area_mask: the records are rewritten where they lie (device arrays) or pass through the call's own copy (host arrays)
+int area_mask_impl(int device, const uint32_t *objects, uint32_t n_objects, uint32_t n, const fw_hit *hits, float *surface, int on_device, void *stream_) {
+    if (!objects || !hits || !surface) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = area_objects_check(objects, n_objects, true)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (on_device && (((uintptr_t)hits | (uintptr_t)surface) & 15u)) return fail(FW_ERR_BAD_ARG, "device hits and surface must be 16-byte aligned");
+    if (n >= (1u << 31)) return fail(FW_ERR_UNSUPPORTED, "n must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    Staged st(device, stream, on_device != 0);
+    const int i_obj = st.add(Staged::IN, objects, (size_t)n_objects * 4, true), i_hits = st.add(Staged::IN, hits, (size_t)n * sizeof(fw_hit)),
+              i_surf = st.add(Staged::INOUT, surface, on_device ? 0 : (size_t)n * 64);
+    if (int rc = st.up()) return rc;
+    fw::launch_area_mask(stream, device_cus(device), n, st.ptr<const uint32_t>(i_obj), n_objects, st.ptr<const fw_hit>(i_hits), st.ptr<float>(i_surf));
+    return st.finish();
+}
+
+// fw_bake_area: fw_bake_ao's shape — k_area_rays as trace_rounds' generator over the scene's own light records where they lie, which
+// fills the chunk's weights beside its rays; the reducer is k_hit_surface over the chunk's rays and hits and k_area_reduce.  The scene
+// is looked at only after a device was found: Ln is the scene's, and a scene exists only where a device does.
+int bake_area_impl(fw_scene *sc, const fw_area *ap, const fw_trace_params *tp, uint32_t N, const float *positions, const float *normals, uint32_t stride,
+                   const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    if (!sc || !ap || !tp || !positions || !normals) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = area_check(ap)) return rc;
+    if (N == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (rounds == 0) return fail(FW_ERR_BAD_ARG, "rounds must be > 0");
+    if ((uint64_t)first_round + rounds > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_round + rounds overflows");
+    if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
+    if (tp->on_device && ((((uintptr_t)sums | (uintptr_t)out) & 15u) || (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums and out must be 16-byte aligned, device positions, normals and ids 4-byte aligned");
+    if (int rc = need_device()) return rc;
+    const uint32_t Ln = sc->n_lights, S = ap->samples;
+    const uint64_t M = (uint64_t)Ln * S;
+    if ((uint64_t)N * M >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x the scene's sampled lights x samples must be below 2^31");
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)tp->stream;
+    const bool on_device = tp->on_device != 0;
+    uint64_t extent;
+    if (int rc = points_extent(stream, N, ids, on_device, sums, extent)) return rc;
+    if (extent * std::max(Ln, 1u) >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "id x the scene's sampled lights must be below 2^31");
+    const uint32_t chunk = std::min<uint32_t>(N, ap->chunk_points ? ap->chunk_points : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / (std::max<uint64_t>(M, 1) * 140)));
+    const size_t rec_bytes = (size_t)extent * 16, cm = (size_t)chunk * M;
+    Staged st(dev, stream, on_device);
+    const AoSlots slots = ao_points_stage(st, N, positions, normals, stride, ids, extent);
+    const int i_rays = st.add(Staged::WORK, nullptr, cm * 24), i_hits = st.add(Staged::WORK, nullptr, cm * sizeof(fw_hit)),
+              i_w = st.add(Staged::WORK, nullptr, cm * 4), i_surf = st.add(Staged::WORK, nullptr, cm * 64);
+    const int i_sums = st.add_sums(sums, rec_bytes), i_out = st.add(ids ? Staged::INOUT : Staged::OUT, out, rec_bytes);      // (with ids, entries outside the list stay)
+    if (int rc = st.up()) return rc;
+    const fw::DAoPoints pts = ao_points_device(st, slots, stride);
+    float *d_sums = st.ptr<float>(i_sums), *d_w = st.ptr<float>(i_w), *d_surf = st.ptr<float>(i_surf);
+    const int n_cus = device_cus(dev);
+    fw_stats total{};
+    if (Ln > 0) {
+        const float4 *d_rec = (const float4 *)sc->area_recs.p;
+        const uint32_t *d_obj = (const uint32_t *)sc->lights.p;
+        const TraceRounds b{N, (uint32_t)M, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
+        if (int rc = trace_rounds(sc, tp, b, first_round, rounds, stats ? &total : nullptr,
+                [&](uint32_t r, uint32_t q0, uint32_t k, float *rays) {
+                    fw::launch_area_rays(stream, n_cus, area_rays_device(ap, r, pts, d_rec, Ln, q0), k, rays, d_w);
+                },
+                [&](uint32_t q0, uint32_t k, const float *rays, const fw_hit *hits) {
+                    const uint32_t km = k * (uint32_t)M;
+                    fw::launch_hit_surface(stream, sc->n_cus, sc->d, sc->n_mat, rays, (const float4 *)hits, km, (float4 *)d_surf);
+                    fw::launch_area_reduce(stream, n_cus, q0, k, Ln, S, pts.ids, d_obj, d_w, hits, d_surf, d_sums);
+                }))
+            return rc;
+    }
+    if (int rc = st.download(i_sums)) return rc;
+    if (out) fw::launch_area_resolve(stream, N, (double)((uint64_t)first_round + rounds), pts.ids, d_sums, st.ptr<float>(i_out));
     if (int rc = st.finish()) return rc;
     stats_finish(stats, total, wall0);
     return FW_OK;
@@ -5963,12 +6151,7 @@ int fw_selftest_lights(const fw_scene_desc *desc, float *out, uint32_t cap, uint
     try {
         const std::vector<LightRec> L = scene_lights(desc);
         *n = (uint32_t)L.size();
-        for (uint32_t i = 0; i < cap && i < *n; i++) {
-            float *r = out + (size_t)i * FW_LIGHT_RECORD_FLOATS;
-            r[0] = (float)L[i].obj; r[1] = (float)L[i].kind;
-            std::memcpy(r + 2, L[i].pts, sizeof L[i].pts);
-            r[14] = L[i].area; r[15] = L[i].p_pick;
-        }
+        for (uint32_t i = 0; i < cap && i < *n; i++) light_record_floats(L[i], out + (size_t)i * FW_LIGHT_RECORD_FLOATS);
         return FW_OK;
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
@@ -6385,6 +6568,39 @@ int fw_bake_gather(fw_scene *scene, const fw_gather *g, const fw_trace_params *t
     }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_gather"); }
+}
+
+int fw_scene_area_lights(fw_scene *scene, float *out, uint32_t cap, uint32_t *n) {
+    try { return scene_area_lights_impl(scene, out, cap, n); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_scene_area_lights"); }
+}
+
+int fw_area_rays(const fw_area *area, const float *lights, uint32_t n_lights, int device, uint32_t round, uint32_t n, const float *positions,
+                 const float *normals, uint32_t stride_floats, const uint32_t *ids, float *rays, float *weights, int on_device, void *stream) {
+    try { return area_rays_impl(area, lights, n_lights, device, round, n, positions, normals, stride_floats, ids, rays, weights, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_area_rays"); }
+}
+
+int fw_area_reduce(int device, uint32_t samples, const uint32_t *objects, uint32_t n_objects, uint32_t n, const uint32_t *ids, const float *weights,
+                   const fw_hit *hits, const float *surface, float *sums, int on_device, void *stream) {
+    try { return area_reduce_impl(device, samples, objects, n_objects, n, ids, weights, hits, surface, sums, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_area_reduce"); }
+}
+
+int fw_area_mask(int device, const uint32_t *objects, uint32_t n_objects, uint32_t n, const fw_hit *hits, float *surface, int on_device, void *stream) {
+    try { return area_mask_impl(device, objects, n_objects, n, hits, surface, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_area_mask"); }
+}
+
+int fw_bake_area(fw_scene *scene, const fw_area *area, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
+                 uint32_t stride_floats, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    try { return bake_area_impl(scene, area, tp, n, positions, normals, stride_floats, ids, first_round, rounds, sums, out, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_area"); }
 }
 
 int fw_reflect_rays(const fw_reflect *reflect, int device, uint32_t round, uint32_t n, const float *positions, const float *normals,

@@ -1725,12 +1725,15 @@ int fw_gather_reduce(int device, uint32_t directions, uint32_t n, const uint32_t
                      const float *direct, float *sums, int on_device, void *stream);
 
 #define FW_GATHER_DIRECT 1u   /* add the scene's point, spot and directional lights at the gather hits */
+#define FW_GATHER_NO_LIGHTS 4u   /* the complement of fw_bake_area: a gather ray that hits one of the scene's sampled area lights (fw_scene_area_lights)
+                                    brings back nothing — between steps 3 and 4 k_area_mask (fw_area_mask) rewrites those records of the chunk to
+                                    kind -2.  Bit 2 is unassigned and refused. */
 typedef struct fw_gather {
     uint32_t directions;     /* D, 1..2^20 */
     uint32_t jitter;         /* fw_ao's */
     float    bias;           /* gather-ray origin offset along the receiver's normal, >= 0, finite */
     float    direct_bias;    /* fw_direct.bias for the shadow rays at the gather hits */
-    uint32_t flags;          /* FW_GATHER_DIRECT */
+    uint32_t flags;          /* FW_GATHER_DIRECT | FW_GATHER_NO_LIGHTS */
     uint32_t chunk_points;   /* 0: as many as fit 256 MiB at this call's bytes per ray (148, plus Ln x 72 + 64 with direct), at least one */
     uint64_t seed;
 } fw_gather;
@@ -1873,6 +1876,106 @@ int fw_bake_reflect(fw_scene *scene, const fw_reflect *reflect, const fw_trace_p
                     uint32_t n, const float *positions, const float *normals, uint32_t stride_floats, const uint32_t *ids,
                     const float *view, uint32_t view_stride_floats, const float *spec,
                     uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
+
+/* ---- sphere and rectangle emitters sampled at surface points (additive at ABI 8) ---------------------------------------
+   The direct irradiance of the lights FW_FLAG_LIGHT_SAMPLING samples — every EmissiveMat sphere and axis-aligned rectangle — at arbitrary
+   surface points, by light sampling: what a final gather's cosine-weighted rays find only by chance when the lamp is small.  From each
+   point S shadow rays per light and round go to points drawn on the light as the point sees it; a ray counts where it reaches that light
+   itself (the renderer's own rule), and then carries the emission fw_hit_surface evaluates at its hit, times a geometric weight.  Lights
+   are summed, not picked.  Five calls: fw_scene_area_lights returns a resident scene's light records, fw_area_rays makes rays and
+   weights, fw_area_reduce sums what reached its light, fw_area_mask takes the sampled lights out of a final gather's records (the
+   gather's complement, FW_GATHER_NO_LIGHTS), fw_bake_area chains rays, trace, surface and reduction.  api.area_rays, api.area_reduce,
+   api.area_resolve and api.area_mask are the numpy statements.
+     Light records: FW_LIGHT_RECORD_FLOATS = 16 floats each as fw_selftest_lights writes them — object, kind, 12 geometry floats (a
+         sphere: centre.xyz, radius, 8 unused; a rectangle: the world corners c0 .. c3 in order around it), area, p_pick.  Only kind and
+         the geometry are read by the rays; the object is what the reduction and the mask compare a hit's object with.
+     Points: fw_ao_rays' (position and normal three floats each at id x stride_floats, id = ids ? ids[q] : q; unusable if a component
+         is not finite or the normal is (0, 0, 0)).  The caller promises id x Ln + i < 2^31 for every id.
+     Entry e = (q Ln + i) S + s: sample s of light i from point q (fw_area_rays, k_area_rays).  Everything is float64 from the float32
+         inputs, every operation rounded as written (no contraction), |v| = sqrt((x x + y y) + z z), a . b = (ax bx + ay by) + az bz,
+         max is fmax, sqrt, sin, cos and floor are the library's float64 functions, each output rounded to float32 once.
+         1. (xi_u, xi_v) = the two shifts fw_ao_rays draws for (seed, round, item id Ln + i); (1/2, 1/2) with jitter == 0.
+            a1 = (s + xi_u) / S;  u1 = a1 - floor(a1);  a2 = s G + xi_v with G = 0.6180339887498949;  u2 = a2 - floor(a2).
+         2. n = normal / |normal|;  o = position (bias == 0) or position + bias n, per component.
+         3. A rectangle (kind 1..3):  e1 = c1 - c0;  e2 = c3 - c0;  d = ((c0 + u1 e1) + u2 e2) - o per component;  nl = e1 x e2 =
+            (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y - e1.y e2.x);  A = |nl|;  d2 = d . d;  w = d / sqrt(d2);
+            cr = n . w;  cl = |(nl . w) / A|;  g = ((cr cl) A) / d2.  Live only if cr > 0 and A > 0.
+         4. A sphere (kind 0), light_sample's construction:  v = centre - o;  dv = v . v;  r2 = radius radius;  live only
+            if dv > r2;  s2 = r2 / dv;  cmax = sqrt(1 - s2);  omc = s2 / (1 + cmax);  om = u1 omc;  ct = 1 - om;  st = sqrt(max(om (2 -
+            om), 0));  phi = (2 pi) u2;  lx = st cos phi;  ly = st sin phi;  wv = v / sqrt(dv);  the frame (T, B) around wv is Duff et
+            al.'s as fw_ao_rays forms it around n;  dir = (lx T + ly B) + ct wv per component;  b = dir . v;  t = b - sqrt(max(b b - (dv -
+            r2), 0));  d = t dir: the near intersection;  cr = n . (d / |d|);  g = (cr (2 pi)) omc.  Live only if cr > 0.
+         5. The entry is dead unless the point is usable, the conditions above hold, g is finite, float(g) > 0 and finite, the six
+            rounded floats are finite and the rounded direction is not (0, 0, 0) — a NaN anywhere is dead.  A dead entry is six zeros
+            and the weight 0: fw_trace_rays never traces it.  A live entry is (float(o), float(d)) and the weight float(g): the light
+            sits at t = 1 along the ray.
+     Reduction of one round (fw_area_reduce, k_area_reduce) over the M = Ln S entries m = i S + s of point q, with the weight w, the hit
+         h that fw_trace_rays wrote for the ray and the record r that fw_hit_surface wrote for that hit: the entry counts exactly where
+         w > 0, h.object == objects[i] and r.kind == 3 (FW_MAT_EMISSIVE) — so whatever stops the walk on the way occludes, a
+         ConstantMedium included.  Four float64 accumulators: E_c += (double)r.emitted_c x (double)w and V += 1.  The order is
+         fw_ao_reduce's over M: G = the smallest power of two >= min(M, 64), partial sum l takes m = l, l + G, ... ascending from 0, the
+         G partial sums are added by an xor butterfly over the distances G/2 ... 1.  E is multiplied by the float64 1 / S and V by the
+         float64 1 / M; each is rounded to float32 once and added with one float32 addition to sums[id] = (Er, Eg, Eb, vis).  No
+         atomics; two runs are bit-equal; a point's result depends on no other point.
+     Resolve (k_area_resolve), R = the number of rounds in sums: out[id] = float((double)sums[id] / R) for the four floats: the area
+         lights' irradiance at the point and the share of its shadow rays that arrived.
+     Mask (fw_area_mask, k_area_mask): record e is rewritten to (kind -2, every other float 0) where its kind is 3 and hits[e].object is
+         in the strictly ascending list `objects` (binary search); every other record keeps its bits. */
+typedef struct fw_area {
+    uint32_t samples;        /* S per light, 1..2^20 */
+    uint32_t jitter;         /* fw_ao's */
+    float    bias;           /* shadow-ray origin offset along the point's normal, >= 0, finite */
+    uint32_t chunk_points;   /* fw_bake_area: points per chunk; 0 = as many as fit 256 MiB at 140 B per entry, at least one */
+    uint64_t seed;
+} fw_area;
+
+/* fw_scene_area_lights: the records fw_selftest_lights would give for the description the resident scene now represents, objects moved
+   by fw_scene_update included, in ascending object order.  *n = their number; the first min(cap, *n) are written to out (host memory).
+   CPU only.  FW_ERR_BAD_ARG for a NULL scene or n, or a NULL out with cap > 0. */
+int fw_scene_area_lights(fw_scene *scene, float *out, uint32_t cap, uint32_t *n);
+
+/* fw_area_rays: the shadow rays and weights of round `round` from n points towards n_lights records (host memory always).  rays n x Ln
+   x S x 6 floats, weights n x Ln x S floats; host or device arrays as fw_ao_rays.
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL area, lights, positions, normals, rays or weights; samples
+   outside 1..2^20, bias negative or not finite; n_lights outside 1..FW_MAX_LIGHTS or a record whose kind is not 0..3; n == 0;
+   stride_floats < 3; with on_device an array not 4-byte aligned; FW_ERR_UNSUPPORTED for n x Ln x S >= 2^31, and for (the largest id +
+   1) x Ln >= 2^31 (host ids; n x Ln with device arrays); then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last. */
+int fw_area_rays(const fw_area *area, const float *lights, uint32_t n_lights, int device, uint32_t round, uint32_t n, const float *positions,
+                 const float *normals, uint32_t stride_floats, const uint32_t *ids, float *rays, float *weights, int on_device, void *stream);
+
+/* fw_area_reduce: adds one round's reduction to the running sums.  objects: the n_objects = Ln lights' object indices in the records'
+   order (host memory always); weights n x M floats, hits n x M records, surface n x M x 16 floats; sums records of 16 B indexed by id.
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL objects, weights, hits, surface or sums; samples outside
+   1..2^20; n_objects outside 1..FW_MAX_LIGHTS; n == 0; with on_device sums, hits or surface not 16-byte aligned, weights or ids not
+   4-byte aligned; FW_ERR_UNSUPPORTED for n x M >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last. */
+int fw_area_reduce(int device, uint32_t samples, const uint32_t *objects, uint32_t n_objects, uint32_t n, const uint32_t *ids, const float *weights,
+                   const fw_hit *hits, const float *surface, float *sums, int on_device, void *stream);
+
+/* fw_area_mask: rewrites in place the records of n hits that lie on one of `objects` (host memory always, strictly ascending).
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL objects, hits or surface; n_objects outside
+   1..FW_MAX_LIGHTS or a list that does not ascend strictly; n == 0; with on_device hits or surface not 16-byte aligned;
+   FW_ERR_UNSUPPORTED for n >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last. */
+int fw_area_mask(int device, const uint32_t *objects, uint32_t n_objects, uint32_t n, const fw_hit *hits, float *surface, int on_device, void *stream);
+
+/* fw_bake_area: the rounds [first_round, first_round + rounds) of the n points against a resident scene and its own sampled lights (Ln
+   of them).  Points, ids, sums, out, first_round / rounds and what is read of tp are fw_bake_ao's.  For each round r and each chunk of
+   points [q0, q1) (chunk_points at a time), in device scratch that the call allocates and frees on every path:
+     1. k_area_rays: fw_area_rays' rays and weights for the scene's records, bit for bit;
+     2. the trace, as fw_bake_ao runs it: on_device, seed = tp->seed + r, key_base = q0 Ln S;
+     3. k_hit_surface over the chunk's rays and hits;
+     4. k_area_reduce into sums.
+   After the last round k_area_resolve writes out.  A scene without sampled lights traces nothing: sums stay as they are and out is
+   their resolve — zeros.  On an error the stream is drained.
+   Contracts.  Composition: for every chunk_points, sums equals bit for bit what fw_area_rays, fw_trace_rays (seed + r, key_base 0),
+   fw_hit_surface and fw_area_reduce give when chained by hand over all n points.  Progressive: k calls of m rounds leave the sums and
+   out of one call of k m rounds, bit for bit.  Renders, and the frame graph's key, are left as fw_trace_rays leaves them.
+   Errors, in this order and before the scene is looked at or HIP is called: FW_ERR_BAD_ARG for a NULL scene, area, tp, positions or
+   normals; samples outside 1..2^20, bias negative or not finite; n == 0; stride_floats < 3; rounds == 0; first_round + rounds >= 2^32;
+   a NULL sums with first_round > 0; with on_device sums or out not 16-byte aligned, positions, normals or ids not 4-byte aligned; then
+   FW_ERR_NO_DEVICE; then — Ln is the scene's — FW_ERR_UNSUPPORTED for n x Ln x S >= 2^31.
+   stats (may be NULL): fw_bake_ao's. */
+int fw_bake_area(fw_scene *scene, const fw_area *area, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
+                 uint32_t stride_floats, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
 
 #ifdef __cplusplus
 }
