@@ -414,10 +414,12 @@ extern const signed char KERNEL_FAMILY[KID_COUNT];
 struct KernelLog {
     uint64_t bits[(KID_COUNT + 63) / 64];
     uint8_t waves[KID_COUNT];
+    uint8_t fused;      // k_segments_boxlist<SIMPLE, CHAIN> launches: bit SIMPLE * 2 + CHAIN.  Not an id of the table: a fused launch runs the text of
+                        // k_extend_linear_defer<SIMPLE> and k_shade<1,1,CHAIN> and records THEIR ids (the census' rows cover that text); this says which launch it was
     void clear() { *this = KernelLog{}; }
     void add(KernelId id) { bits[id >> 6] |= 1ull << (id & 63u); }
     void add(KernelId id, uint32_t w) { add(id); waves[id] |= (uint8_t)(w == 16u ? 1u : w == 12u ? 2u : 4u); }
-    void merge(const KernelLog &o) { for (size_t i = 0; i < sizeof bits / sizeof bits[0]; i++) bits[i] |= o.bits[i]; for (uint32_t i = 0; i < KID_COUNT; i++) waves[i] |= o.waves[i]; }
+    void merge(const KernelLog &o) { for (size_t i = 0; i < sizeof bits / sizeof bits[0]; i++) bits[i] |= o.bits[i]; for (uint32_t i = 0; i < KID_COUNT; i++) waves[i] |= o.waves[i]; fused |= o.fused; }
     bool has(uint32_t id) const { return ((bits[id >> 6] >> (id & 63u)) & 1u) != 0; }
 };
 
@@ -466,6 +468,12 @@ void launch_extend(const LaunchCfg &, const DScene &, const DFrame &, DPaths in,
 void launch_extend_exact(const LaunchCfg &, const DScene &, const DFrame &, const DPaths &in, float2 *hits, int segment, bool use_bvh);
 void launch_shade(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, const float2 *hits,
                   float4 *sample_rad, int segment);
+// Box-list frames (DESIGN §5 "Fused segments"): segments first .. last of a batch — launch_extend + launch_shade of each — in ONE launch of
+// k_segments_boxlist, `in` holding segment first's queue; can_fuse_segments: the launchers' part of the eligibility (the scan is
+// k_extend_linear_defer, table mode 1, shading mode 1, no GgxMat), which the caller completes (no trees, no exact walk, no light sampling)
+bool can_fuse_segments(const LaunchCfg &, const DScene &);
+void launch_segments(const LaunchCfg &, const DScene &, const DFrame &, DPaths in, DPaths out, float2 *hits, float4 *sample_rad, int first, int last);
+extern const char *const FUSED_KERNEL_NAMES[4];      // by KernelLog.fused's bit
 // light sampling: k_shade's light-sampling kernels (the frame has no chain state, no hit4, no EXACT_PRODUCT and deposits
 // every path) and the resolve of one segment's shadow rays after their walk.  ed: the environment is among the sampled lights (§9h:
 // k_shade_env; shading mode 0 only: an HDR map is an expensive case); em: the emitters are the entries of *em (§9i: k_shade_pl); both:

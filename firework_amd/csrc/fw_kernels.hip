@@ -548,6 +548,29 @@ __device__ __forceinline__ Obj load_obj(const float4 *__restrict__ objs, uint32_
     o.aux0 = __float_as_uint(r4.w); o.aux1 = __float_as_uint(r5.w);
     return o;
 }
+// A scene table read through the CONSTANT address space: memory no kernel writes.  A wave-uniform load from it is a scalar load whatever
+// else the kernel stores — through a plain pointer the compiler must first prove that no store of the kernel can reach the table, which
+// it can for k_extend_linear_defer (its one store goes through a __restrict__ pointer) and cannot for k_segments_boxlist, whose shade
+// phase stores through the queue pointers: its scan's object records came through 32 vector loads per chunk and the frame took 49.5 ms
+// instead of 30.7 (profiles/fused_segments_ab.txt).  (k_extend_linear_defer keeps its plain pointers: through these its scalar loads are
+// merged differently, and shipped kernels keep their instruction streams.)
+struct ConstQuads {
+    const __attribute__((address_space(4))) f4v *p;
+    __device__ __forceinline__ float4 operator[](size_t i) const { const f4v v = p[i]; return make_float4(v.x, v.y, v.z, v.w); }
+    __device__ __forceinline__ ConstQuads operator+(size_t n) const { return ConstQuads{p + n}; }
+    __device__ __forceinline__ ConstQuads &operator+=(size_t n) { p += n; return *this; }
+};
+__device__ __forceinline__ ConstQuads const_quads(const float4 *q) { return ConstQuads{(const __attribute__((address_space(4))) f4v *)q}; }
+__device__ __forceinline__ Obj load_obj(ConstQuads objs, uint32_t j) {
+    const ConstQuads p = objs + (size_t)j * OBJ_Q;
+    float4 r0 = p[0], r3 = p[3], r4 = p[4], r5 = p[5];
+    Obj o;
+    o.q0 = make_float4(r3.x, r3.y, r3.z, r0.x); o.q1 = make_float4(r4.x, r4.y, r4.z, r0.y); o.q2 = make_float4(r5.x, r5.y, r5.z, r0.z);
+    o.q3 = p[1]; o.q4 = p[2];
+    o.kf = __float_as_uint(r0.w); o.material = __float_as_uint(r3.w);
+    o.aux0 = __float_as_uint(r4.w); o.aux1 = __float_as_uint(r5.w);
+    return o;
+}
 // Per-lane (TLAS leaf) fetch for k_extend: only what the intersection needs.  An unrotated sphere costs two
 // 16-byte loads instead of six — these divergent gathers, not arithmetic, bound the BVH scenes (64 B/clk/CU).
 __device__ __forceinline__ Obj load_obj_for_hit(const float4 *__restrict__ objs, uint32_t j) {
@@ -1766,117 +1789,9 @@ void k_extend_linear_defer(DScene sc, DFrame f, DPaths in, float2 *__restrict__ 
     const uint32_t w = wave_index(), lane = threadIdx.x & 63u;
     if (w >= q.n_waves) return;
     const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w], base = w * q.cap;
-    const float TMIN = 0.001f, TMAX = 2e9f;                          // render.rs:19
-    const uint32_t n_first = sc.n_objects - n_def;
     uint32_t *const L0 = lds_defer, *const L1 = lds_defer + DEFER_FIELDS * 64u;
-    uint32_t cnt0 = 0, cnt1 = 0;
-    const RngKey nokey{0, 0, 0};
-    auto write_final = [&](uint32_t slot, float t, uint32_t code) {
-        if (f.hit4) reinterpret_cast<uint32_t *>(hits)[slot] = code; else qst(&hits[slot], make_float2(t, __uint_as_float(code)));
-    };
-    auto put = [&](uint32_t *L, uint32_t e, uint32_t sb, float t, uint32_t code, const Ray &r) {
-        L[e] = sb; L[64u + e] = __float_as_uint(t); L[128u + e] = code;
-        L[192u + e] = __float_as_uint(r.o.x); L[256u + e] = __float_as_uint(r.o.y); L[320u + e] = __float_as_uint(r.o.z);
-        L[384u + e] = __float_as_uint(r.d.x); L[448u + e] = __float_as_uint(r.d.y); L[512u + e] = __float_as_uint(r.d.z);
-    };
-    auto get = [&](const uint32_t *L, uint32_t e, uint32_t &sb, float &t, uint32_t &code, Ray &r) {
-        sb = L[e]; t = __uint_as_float(L[64u + e]); code = L[128u + e];
-        r.o = mk(__uint_as_float(L[192u + e]), __uint_as_float(L[256u + e]), __uint_as_float(L[320u + e]));
-        r.d = mk(__uint_as_float(L[384u + e]), __uint_as_float(L[448u + e]), __uint_as_float(L[512u + e]));
-    };
-    // the exact test of deferred object d for the first `take` entries of its list, one per lane, the object record wave-uniform
-    auto test = [&](uint32_t d, const Ray &r, float &t, uint32_t &code) {
-        const uint32_t k = n_first + d;
-        const Obj o = load_obj(sc.obj, k);                            // scalar loads
-        float tt; uint32_t prim;
-        if (hit_rect3d(o.q3, o.q4, to_object_space(o, r), TMIN, t, tt, prim)) { t = tt; code = (k << sc.prim_bits) | prim; }   // a plain Rect3d (the host checks)
-    };
-    // Lists never overflow: before a chunk appends its candidates, make_room runs whichever list could not take them (and list 1 first when
-    // it could not take what list 0's run passes on — the entries flagged in bit 31, counted beforehand).  A run so has between
-    // 65 - (the chunk's candidates) and 64 lanes busy.  One textual copy of each run: the two places list 1 may have to run are the two
-    // trips of a loop.
-    auto append = [&](uint32_t *L, uint32_t &cnt, bool want, uint32_t sb, float t, uint32_t code, const Ray &r) {
-        const unsigned long long m = __ballot(want);
-        if (!m) return;
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        if (want) put(L, cnt + rank, sb, t, code, r);
-        cnt += (uint32_t)__popcll(m);
-    };
-    // need0 / need1: entries the caller is about to append to list 0 / list 1 (65: run whatever is there — the end of the queue)
-    auto make_room = [&](uint32_t need0, uint32_t need1) {
-        const bool r0 = cnt0 != 0u && cnt0 + need0 > 64u;
-        const uint32_t pass_on = r0 ? (uint32_t)__popcll(__ballot(lane < cnt0 && (L0[lane] >> 31) != 0u)) : 0u;
-#pragma nounroll
-        for (int phase = 0; phase < 2; phase++) {
-            const bool r1 = cnt1 != 0u && (phase == 0 ? cnt1 + pass_on > 64u : cnt1 + need1 > 64u);
-            if (r1) {
-                uint32_t sb = 0, code = MISS; float t = TMAX; Ray r{mk(0, 0, 0), mk(0, 0, 1)};
-                if (lane < cnt1) { get(L1, lane, sb, t, code, r); test(1, r, t, code); write_final(sb, t, code); }
-                cnt1 = 0;
-            }
-            if (phase == 0 && r0) {
-                uint32_t sb = 0, code = MISS; float t = TMAX; Ray r{mk(0, 0, 0), mk(0, 0, 1)};
-                const bool on = lane < cnt0;
-                if (on) { get(L0, lane, sb, t, code, r); test(0, r, t, code); }
-                cnt0 = 0;
-                const bool more = on && (sb >> 31) != 0u;              // listed for the second box too
-                const uint32_t slot = sb & 0x7fffffffu;
-                if (on && !more) write_final(slot, t, code);
-                append(L1, cnt1, more, slot, t, code, r);
-            }
-        }
-    };
-    float4 ra_n = make_float4(0, 0, 0, 0); float2 rb_n = make_float2(0, 0);
-    if (lane < n) { ra_n = qld(&in.ray_a[base + lane]); rb_n = load_ray_b(in, base + lane, f, segment); }
-    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
-        const uint32_t j = c0 + lane, i = base + j;
-        const float4 ra = ra_n; const float2 rb = rb_n;
-        if (j + 64u < n) { ra_n = qld(&in.ray_a[i + 64u]); rb_n = load_ray_b(in, i + 64u, f, segment); }
-        const bool active = j < n;
-        float best_t = TMAX; uint32_t best_obj = MISS, best_prim = 0;
-        bool may0 = false, may1 = false;
-        const Ray r = make_ray(ra, rb, f, segment);
-        if (active) {
-            const float4 *op = sc.obj;
-            // A room's walls are PLAIN rectangles (no rotation, no degenerate interval), two or three per axis: they share the reciprocal of
-            // their axis' direction component — v_rcp_f32 is a quarter-rate instruction, and the generic test computed it once per rectangle —
-            // and skip the generic dispatch.  Wave-uniform branch (the record came through scalar loads); the quotients are hit_rect's, bit for
-            // bit.  k_extend 16.2 -> 14.25 ms, cornell 36.0 -> 33.2 ms (gpurun_out/r04y/cornell_rcp.txt).  (The same in the generic linear scans
-            // costs them registers they do not have — hdri 7.3 -> 7.8 ms, volume 13.8 -> 15.1 —, and spelled out inside hit_rect3d, where the
-            // compiler already shares them, it lost as well: r04y/shared_rcp.txt.)
-            const Rcp rcx = make_rcp(r.d.x), rcy = make_rcp(r.d.y), rcz = make_rcp(r.d.z);
-            for (uint32_t k = 0; k < n_first; k++, op += OBJ_Q) {
-                const Obj o = load_obj(op, 0);
-                float t; uint32_t prim = 0; bool h;
-                const uint32_t kind = obj_kind(o);
-                if (kind >= 1u && kind <= 3u && !(obj_flags(o) & OF_ROTATED) && o.q4.y == 0.f) {
-                    const Ray ro{r.o - mk(o.q0.w, o.q1.w, o.q2.w), r.d};                                 // to_object_space without a rotation
-                    if (kind == 1u) h = hit_rect_rcp<0>(o.q3.x, o.q3.y, o.q3.z, o.q3.w, o.q4.x, ro, rcz, TMIN, best_t, t);
-                    else if (kind == 2u) h = hit_rect_rcp<1>(o.q3.x, o.q3.y, o.q3.z, o.q3.w, o.q4.x, ro, rcy, TMIN, best_t, t);
-                    else h = hit_rect_rcp<2>(o.q3.x, o.q3.y, o.q3.z, o.q3.w, o.q4.x, ro, rcx, TMIN, best_t, t);
-                } else h = hit_object<false, 0, false, SIMPLE>(sc, o, k, r, TMIN, best_t, nullptr, nokey, segment, t, prim);
-                if (h) { best_t = t; best_obj = k; best_prim = prim; }
-            }
-            // conservative pre-tests, per lane and culled against the hit so far: fw_defer_pretest.h.  The slab test of closest_hit's
-            // segment-0 cull (boxes inflated by 1e-4 of the scene and ray-origin scale) with the work moved out of the box loop: the
-            // box comes from the host as centre and grown half extent (the second half of obj_cull: nothing wave-uniform is computed
-            // here), the reciprocals are the ones the room's rectangles just used (no v_rcp_f32 of its own), a plane pair is three
-            // fmas around the centre's distance fma(c, inv, -o * inv), whose rounding the host's extra hundredth of margin covers,
-            // and a direction component that is 0, below 2^-40, infinite or NaN lists the ray whatever the slabs say (the exact
-            // test accepts t = 0/0).  91 -> 45 vector instructions per chunk for two boxes (profiles/defer_pretest_isa.txt).
-            const fwpt::RayTerms rt = fwpt::ray_terms(r.o.x, r.o.y, r.o.z, rcx.r, rcy.r, rcz.r);
-            const float4 *const cb = sc.obj_cull + 2 * ((size_t)sc.n_objects + n_first);       // n_def is 1 or 2 (the host: n_defer)
-            may0 = fwpt::pretest_fma(rt, cb[0].x, cb[0].y, cb[0].z, cb[1].x, cb[1].y, cb[1].z, best_t);
-            if (n_def > 1u) may1 = fwpt::pretest_fma(rt, cb[2].x, cb[2].y, cb[2].z, cb[3].x, cb[3].y, cb[3].z, best_t);
-        }
-        const uint32_t code = best_obj == MISS ? MISS : ((best_obj << sc.prim_bits) | best_prim);
-        const bool c1 = may1 && !may0;                                  // straight to list 1; a ray listed for box 0 carries box 1 in bit 31
-        make_room((uint32_t)__popcll(__ballot(may0)), (uint32_t)__popcll(__ballot(c1)));
-        if (active && !may0 && !may1) write_final(i, best_t, code);
-        append(L0, cnt0, may0, i | (may1 ? 0x80000000u : 0u), best_t, code, r);
-        append(L1, cnt1, c1, i, best_t, code, r);
-    }
-    make_room(65u, 65u);
+    const float4 *const scan_objs = sc.obj, *const scan_cull = sc.obj_cull;
+#include "fw_extend_defer.inc"
 }
 
 // (The first attempt of round 2 to DEFER the expensive shapes of the linear scan — k_extend_linear_defer above is the second: cornell's two rotated boxes are 12 of a ray's 18 rectangle
@@ -3720,140 +3635,74 @@ __global__ __launch_bounds__(WB) void k_shade(DScene sc, DFrame f, DPaths in, DP
     const uint32_t n = q.wcount[(size_t)segment * q.n_waves + w];
     const uint32_t base = w * q.cap;
     uint32_t out_n = 0;                                                  // survivors written so far (wave-uniform)
-    uint32_t list_n = 0;                                                 // MODE 2: entries of shade_list (wave-uniform)
-    PH_DECL;
-// ---- K7: compaction inside the wave's private queue: ballot -> mbcnt prefix -> dense stores --------
-    auto compact = [&](bool alive, const Ray &nr, V3 nbeta, uint32_t nchain, uint32_t path_id, uint32_t c0 = 0xffffffffu) {
-        const unsigned long long mask = __ballot(alive);
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-#if FW_SHADE_STATIC_STORES
-        // Round 5: EVERY lane stores, the dead ones into slots of the wave's own output window that no survivor of this chunk can take and
-        // that a later chunk overwrites or nobody reads (position c0 + 64 + lane >= out_n + 64, clamped to the window's last slot, which a
-        // survivor reaches only when all 64 lanes survive).  Why: on gfx9 loads and stores share ONE in-order counter (vmcnt), and with the
-        // stores behind `if (alive)` — a branch the wave may skip — the compiler cannot know how many of them follow the next chunk's
-        // prefetch loads, so the loop-top wait for those loads was `s_waitcnt vmcnt(0)`: every chunk of every wave waited for the L2's
-        // acknowledgement of its own stores (54 % of k_shade's wave time in s_waitcnt, profiles/r04z_c2_sq.json).  With a static store count
-        // the wait is vmcnt(3): the loads, nothing younger.
-        if (c0 != 0xffffffffu) {
-#if FW_SHADE_STATIC_STORES == 2     // timing variant: every dead lane into ONE slot (the window's last: no survivor takes it while any lane died) — the waits without the traffic
-            const uint32_t dst = base + (alive ? out_n + rank : q.cap - 1u);
-#else
-            const uint32_t dst = base + (alive ? out_n + rank : min(c0 + 64u + lane, q.cap - 1u));
-#endif
-            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
-            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
-            if (CHAIN) qst(&reinterpret_cast<float2 *>(out.state)[dst], make_float2(__uint_as_float(nchain), __uint_as_float(path_id)));
-            else qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
-        } else
-#endif
-        if (alive) {
-            const uint32_t dst = base + out_n + rank;
-            qst(&out.ray_a[dst], make_float4(nr.o.x, nr.o.y, nr.o.z, nr.d.x));
-            qst(&out.ray_b[dst], make_float2(nr.d.y, nr.d.z));
-            if (CHAIN) qst(&reinterpret_cast<float2 *>(out.state)[dst], make_float2(__uint_as_float(nchain), __uint_as_float(path_id)));
-            else qst(&out.state[dst], make_float4(nbeta.x, nbeta.y, nbeta.z, __uint_as_float(path_id)));
-        }
-        if (f.ex.mode)     // a new ray whose result depends on traversal order: k_extend_exact walks it literally (DExact)
-            flag_exact(f.ex, alive && needs_exact(f.ex, nr.o.x, nr.o.y, nr.o.z, nr.d.x, nr.d.y, nr.d.z), base + out_n + rank, segment + 1);
-        out_n += (uint32_t)__popcll(mask);
-    };
-    auto load_st = [&](uint32_t idx) { return CHAIN ? load_state_chain(in, idx, segment) : load_state(in, idx, segment); };
-    auto load_hit = [&](uint32_t idx) { return f.hit4 ? make_float2(0.f, __uint_as_float(reinterpret_cast<const uint32_t *>(hits)[idx])) : qld(&hits[idx]); };
-    // MODE 2: the last `take` listed paths, one per lane, with the full shading code
-    auto run_list = [&](uint32_t take) {
-        bool alive = false;
-        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
-        if (lane < take) {
-            const uint32_t i = base + shade_list[list_n - take + lane];
-            const float4 ra = qld(&in.ray_a[i]), st = load_st(i); const float2 rb = load_ray_b(in, i, f, segment), hr = load_hit(i);
-            path_id = __float_as_uint(st.w);
-            alive = shade_path<false, CHAIN>(sc, f, objp, matp, texp, make_ray(ra, rb, f, segment), mk(st.x, st.y, st.z), __float_as_uint(st.x), path_id, hr.x, __float_as_uint(hr.y), segment, sample_rad, nr, nbeta, nchain PH_PASS);
-        }
-        list_n -= take;
-        compact(alive, nr, nbeta, nchain, path_id);
-    };
-    // software pipeline: next chunk's ray / state / hit are in flight while the current chunk is shaded
-    float4 ra_n = make_float4(0, 0, 0, 0), st_n = ra_n; float2 rb_n = make_float2(0, 0), hr_n = rb_n;
-#if FW_SHADE_PIPE
-    // Round 5: what the prefetch really needs on gfx9.  Loads and stores share ONE in-order counter (vmcnt): waiting for a load means
-    // waiting for everything issued before it, and a wait's immediate is the number of YOUNGER operations that may stay outstanding — which
-    // the compiler can only use when that number is the same on every path.  The loop used to issue the next chunk's loads at its top
-    // behind `if (j + 64 < n)`, gather the path's pixel id (key_of) in the middle and store the survivors behind `if (alive)`: the gather's
-    // wait (vmcnt(0): in-order) completed the prefetch a few hundred instructions after it was issued, and the next top's wait (vmcnt(0):
-    // unknown store count) completed the stores — every chunk of every wave sat out an HBM round trip and an L2 write acknowledgement
-    // (54 % of the wave time in s_waitcnt at 0.79 instruction issue, profiles/r04z_c2_sq.json; fewer instructions or a deeper prefetch
-    // changed nothing: DESIGN §5 rounds 1-4).  Now: (A) the chunk's dependent gathers are issued FIRST (the pixel id), (B) then the next
-    // chunk's loads, always the same four instructions (indices clamped to the queue's last entry, and where a stream is not read at all —
-    // segment-0 state, ray_b of pinhole camera rays — one hot address stands in), (C) the shading, (D) the stores, every lane
-    // (FW_SHADE_STATIC_STORES).  The waits become vmcnt(4) for the gather and vmcnt(3) at the top.
-    auto prefetch = [&](uint32_t jn) {       // jn: queue position, clamped by the caller
-        const uint32_t in_ = base + jn;
-        ra_n = qld(&in.ray_a[in_]);
-        rb_n = qld(&in.ray_b[short_rays(f, segment) ? base : in_]);
-        if (CHAIN) { const float2 v = qld(&reinterpret_cast<const float2 *>(in.state)[segment == 0 ? base : in_]); st_n = make_float4(v.x, 0.f, 0.f, v.y); }
-        else st_n = qld(&in.state[segment == 0 ? base : in_]);
-        hr_n = load_hit(in_);
-    };
-    auto fix_implicit = [&](float4 &st_, float2 &rb_, uint32_t slot) {      // the streams that are not stored at segment 0 (load_state*, load_ray_b)
-        if (segment == 0) st_ = CHAIN ? make_float4(0.f, 0.f, 0.f, __uint_as_float(slot)) : make_float4(1.f, 1.f, 1.f, __uint_as_float(slot));
-        if (short_rays(f, segment)) rb_ = make_float2(0.f, 0.f);
-    };
-    if (n) {
-        prefetch(min(lane, n - 1u));
-        // ... and the loop is entered with the same operations behind the first chunk's loads as every later trip has behind its own: three
-        // stores (here into the first 64 output slots, which chunk 0's survivors overwrite or nobody reads) — the wait at the top of the loop
-        // is compiled once, for the entry and for the back edge, with the smaller of the two counts
-        const uint32_t d0 = base + lane;
-        qst(&out.ray_a[d0], make_float4(0.f, 0.f, 0.f, 0.f));
-        qst(&out.ray_b[d0], make_float2(0.f, 0.f));
-        if (CHAIN) qst(&reinterpret_cast<float2 *>(out.state)[d0], make_float2(0.f, 0.f)); else qst(&out.state[d0], make_float4(0.f, 0.f, 0.f, 0.f));
-    }
-#else
-    if (lane < n) { ra_n = qld(&in.ray_a[base + lane]); rb_n = load_ray_b(in, base + lane, f, segment); st_n = load_st(base + lane); hr_n = load_hit(base + lane); }
-#endif
-    for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
-        const uint32_t j = c0 + lane;
-        const uint32_t i = base + j;
-        float4 ra = ra_n, st = st_n; float2 rb = rb_n, hr = hr_n;
-#if FW_SHADE_PIPE
-        fix_implicit(st, rb, i);
-        const RngKey key_ = key_of(f, __float_as_uint(st.w));        // (A) the chunk's own gather, before (B) the prefetch
-        prefetch(min(j + 64u, n - 1u));
-        const RngKey *pre_key = &key_;
-#else
-        if (j + 64u < n) { ra_n = qld(&in.ray_a[i + 64u]); rb_n = load_ray_b(in, i + 64u, f, segment); st_n = load_st(i + 64u); hr_n = load_hit(i + 64u); }
-        const RngKey *pre_key = nullptr;
-#endif
-        bool alive = false, later = false;
-        Ray nr{mk(0, 0, 0), mk(0, 0, 0)}; V3 nbeta = mk(0, 0, 0); uint32_t path_id = 0, nchain = 0;
-        if (j < n) {
-            PH_T0;
-            Ray r = make_ray(ra, rb, f, segment);
-            V3 beta = mk(st.x, st.y, st.z);
-            path_id = __float_as_uint(st.w);
-            const uint32_t hit_code = __float_as_uint(hr.y);
-#ifdef FW_ABL_SHADE_COPY     // timing ablation (wrong frames): the queue streams and the compaction alone — every hit path survives unchanged
-            alive = hit_code != MISS && segment < 10; nr = r; nbeta = beta; nchain = __float_as_uint(st.x) + (pre_key ? pre_key->pixel & 1u : 0u);
-#else
-            if (MODE == 2 && expensive_shading(sc, objp, matp, hit_code)) later = true;
-            else alive = shade_path<MODE != 0, CHAIN>(sc, f, objp, matp, texp, r, beta, __float_as_uint(st.x), path_id, hr.x, hit_code, segment, sample_rad, nr, nbeta, nchain PH_PASS, pre_key);
-#endif
-            PH_ADD(0);
-        }
-        { PH_T0; compact(alive, nr, nbeta, nchain, path_id, c0); PH_ADD(7); }
-        if (MODE == 2) {
-            const unsigned long long lm = __ballot(later);
-            if (lm) {
-                const uint32_t lr = __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
-                if (later) shade_list[list_n + lr] = (uint16_t)j;
-                list_n += (uint32_t)__popcll(lm);
-                if (list_n >= 64u) run_list(64u);
-            }
-        }
-    }
-    if (MODE == 2) while (list_n) run_list(min(list_n, 64u));
+#include "fw_shade_body.inc"
     if (lane == 0) q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n;
     PH_FLUSH(1);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_segments_boxlist: every segment of a wave's queue in ONE launch (DESIGN §5 "Fused segments"; option FUSE_SEGMENTS).
+//
+// The queues are wave-private: wave w's queue of segment s + 1 depends on nothing but wave w's queue of segment s.  So one wave runs
+// scan(s), shade(s), scan(s + 1), ... over its own queue — the text of k_extend_linear_defer<SIMPLE> and of k_shade<1, 1, CHAIN>
+// (fw_extend_defer.inc, fw_shade_body.inc) in a loop — and a batch is one launch instead of 22.  Nothing is live across a phase but a
+// few scalars, so the kernel needs the larger of the two kernels' registers, not their sum, and on every SIMD waves in the issue-bound
+// scan sit beside waves in the memory-bound shade for the whole batch, not only where two launches' tails meet.
+// The rules that keep it the unfused frame bit for bit:
+//  - a phase ends with s_waitcnt vmcnt(0) and a workgroup-scope release / acquire fence (phase_end): lanes read slots that OTHER lanes of
+//    the wave wrote — compacted survivors, and hit records stored by slot from the list runs.  One wave, one CU, a write-through L1: no
+//    device-scope fence;
+//  - nothing the wave holds in a register is read back from memory: the next phase's n is out_n.  wcount[(s + 1) n_waves + w] is written
+//    for k_queue_totals and never loaded here (its address is wave-uniform: the load would come from the scalar cache, which vector
+//    stores do not update).  The queue arrays and the hit records are not __restrict__ here and go through vector loads as ever;
+//  - no flags, no spin-waits, no atomics but shade_path's dep_bits: a wave's progress depends on no other wave;
+//  - RNG keys, home slots, deposits and dep_bits are by path id, as in the two kernels.
+// Dynamic LDS: the tables of fw_shade_tables.inc (table_quads float4), staged once, then the scan's two lists.
+// ------------------------------------------------------------------------------------------------
+template <bool SIMPLE, bool CHAIN>
+__global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(6, 8)))
+void k_segments_boxlist(DScene sc, DFrame f, DPaths in, DPaths out, float2 *hits, float4 *sample_rad, DQueue q, int first, int last,
+                        uint32_t n_def, uint32_t n_mat, uint32_t n_tex, uint32_t table_quads) {
+    constexpr int LDS_TAB = 1, MODE = 1;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(wave_index()), lane0 = threadIdx.x & 63u;      // (w: provably wave-uniform, so that the counters' addresses are scalars)
+    uint16_t *const shade_list = nullptr;                                // (MODE 2's list: not in this kernel)
+#include "fw_shade_tables.inc"
+    if (w >= q.n_waves) return;
+    uint32_t *const L0 = reinterpret_cast<uint32_t *>(lds_tables + table_quads), *const L1 = L0 + DEFER_FIELDS * 64u;
+    const uint32_t base0 = w * q.cap;
+    // Each phase takes its lane and base through an empty asm: opaque to the optimiser, so that the addresses a phase forms from them are
+    // formed in the phase, as in the kernel it came from.  (Left visible, they are invariants of the segment loop: hoisted out of it, live
+    // across both phases and spilled — 44 to 52 B of scratch per lane.)
+#define FW_PHASE_IDS uint32_t lane = lane0, base = base0; asm volatile("" : "+v"(lane), "+s"(base))
+    uint32_t n = q.wcount[(size_t)first * q.n_waves + w];               // k_raygen's count (an earlier launch's store)
+    auto phase_end = [] {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    };
+#pragma nounroll
+    for (int segment = first; segment <= last; segment++) {
+        if (n == 0u) {                                                   // nothing left: the remaining counters are zeros
+            if (lane0 == 0) for (int s = segment; s <= last; s++) q.wcount[(size_t)(s + 1) * q.n_waves + w] = 0u;
+            return;
+        }
+        {
+            FW_PHASE_IDS;
+            const ConstQuads scan_objs = const_quads(sc.obj), scan_cull = const_quads(sc.obj_cull);
+#include "fw_extend_defer.inc"
+        }
+        phase_end();
+        uint32_t out_n = 0;
+        {
+            FW_PHASE_IDS;
+#include "fw_shade_body.inc"
+        }
+        if (lane0 == 0) q.wcount[(size_t)(segment + 1) * q.n_waves + w] = out_n;
+        phase_end();
+        const DPaths t = in; in = out; out = t;
+        n = out_n;
+    }
+#undef FW_PHASE_IDS
 }
 // Light sampling: k_shade with the light sample of every Lambertian / Isotropic vertex appended to the shadow queue, the
 // BSDF's p_b carried with each ray (sh.pb_in / pb_out) and the MIS weight on the emission it reaches.  k_shade's table modes and its
@@ -4778,6 +4627,7 @@ const char *const KERNEL_NAMES[KID_COUNT] = {
     FW_KERNEL_IDS(FW_KID_NAME)
 #undef FW_KID_NAME
 };
+const char *const FUSED_KERNEL_NAMES[4] = {"k_segments_boxlist<false,no chain>", "k_segments_boxlist<false,chain>", "k_segments_boxlist<true,no chain>", "k_segments_boxlist<true,chain>"};
 const signed char KERNEL_FAMILY[KID_COUNT] = {
 #define FW_KID_FAM(id, name, fam) fam,
     FW_KERNEL_IDS(FW_KID_FAM)
@@ -4920,6 +4770,28 @@ void launch_shade(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths 
 #undef FW_SHADE_C
 #undef FW_SHADE
 }
+// k_segments_boxlist: what of a frame's eligibility the launchers decide (the host adds its own: fw_runtime.cpp, fuse_segments) — the
+// scan is k_extend_linear_defer's, the shading k_shade<1, 1, *>'s: table mode 1, shading mode 1, no GgxMat
+bool can_fuse_segments(const LaunchCfg &c, const DScene &sc) {
+    return c.n_defer > 0 && !c.gx && c.shade_mode == 1 && shade_tables(c, sc).lt == 1;
+}
+// Segments first .. last of a batch in one launch: launch_extend + launch_shade of each, in[.] and out[.] swapping roles.  The log takes
+// the ids of the two kernels whose text runs (their rows of the census cover this text) and the fused instantiation's own bit.
+void launch_segments(const LaunchCfg &c, const DScene &sc, const DFrame &f, DPaths in, DPaths out, float2 *hits, float4 *sample_rad, int first, int last) {
+    const ShadeTables t = shade_tables(c, sc);
+    const size_t lds = t.lds + (size_t)2 * 64 * DEFER_FIELDS * 4;
+    const uint32_t tq = (uint32_t)(t.lds / sizeof(float4));
+    const bool chain = f.chain_bits != 0;
+    if (c.log) {
+        c.log->add(c.simple_set ? KID_EXTEND_LINEAR_DEFER_S : KID_EXTEND_LINEAR_DEFER_N);
+        c.log->add(chain ? KID_SHADE_111 : KID_SHADE_110);
+        c.log->fused |= (uint8_t)(1u << ((c.simple_set ? 2u : 0u) | (chain ? 1u : 0u)));
+    }
+#define FW_SEGMENTS(S, C) hipLaunchKernelGGL((k_segments_boxlist<S, C>), wave_grid(c), dim3(WB), lds, c.stream, sc, f, in, out, hits, sample_rad, c.q, first, last, c.n_defer, c.n_mat, c.n_tex, tq)
+    if (c.simple_set) { if (chain) FW_SEGMENTS(true, true); else FW_SEGMENTS(true, false); }
+    else { if (chain) FW_SEGMENTS(false, true); else FW_SEGMENTS(false, false); }
+#undef FW_SEGMENTS
+}
 // The five light-sampling shade kernels: dl = the delta lights of *dl are sampled (k_shade_dl, §9l: never with ed or em), ed = the environment is among the sampled lights (k_shade_env), em = the emitters are the entries
 // of *em (k_shade_pl), both (k_shade_pl_env), neither (k_shade_ls).  launch_shade's table modes; the shading mode is 0 or 1 (a light-sampling
 // frame never takes the list), and 0 alone with ed: an HDR map is an expensive case.
@@ -4997,6 +4869,7 @@ void preload_kernels() {
     FW_TOUCH((k_shade<0, 0, false>)); FW_TOUCH((k_shade<0, 0, true>)); FW_TOUCH((k_shade<0, 1, false>)); FW_TOUCH((k_shade<0, 1, true>));
     FW_TOUCH((k_shade<1, 0, false>)); FW_TOUCH((k_shade<1, 0, true>)); FW_TOUCH((k_shade<1, 1, false>)); FW_TOUCH((k_shade<1, 1, true>));
     FW_TOUCH((k_shade<2, 0, false>)); FW_TOUCH((k_shade<2, 0, true>)); FW_TOUCH((k_shade<2, 1, false>)); FW_TOUCH((k_shade<2, 1, true>));
+    FW_TOUCH((k_segments_boxlist<true, true>)); FW_TOUCH((k_segments_boxlist<true, false>)); FW_TOUCH((k_segments_boxlist<false, true>)); FW_TOUCH((k_segments_boxlist<false, false>));
 #undef FW_TOUCH
     (void)hipGetLastError();
 }

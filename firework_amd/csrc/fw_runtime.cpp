@@ -65,6 +65,7 @@ struct Options {
     double wide_node_cost = 0.0005;   // WIDE_NODE_COST: the constant a wide node costs in the collapse, in root areas (wide_convert)
     int wide = -1;                // WIDE=0|f32|q8: no wide nodes / force an encoding (-1: by size)
     int build = -1;               // BUILD=host|device: where a scene's trees are built (-1: by size, BUILD_MIN)
+    int fuse_segments = -1;       // FUSE_SEGMENTS=0|1: a box-list batch's segments in one launch of k_segments_boxlist (-1: off — fused frames did not clear the 2 x spread bar over the unfused launches at the same queue count)
     long waves = 0;               // WAVES=n wave queues (0: the library's choice)
     long long paths_per_batch = 0;
     std::string dump_path;        // DUMP_PATH=file (tools/diverge.py)
@@ -74,7 +75,7 @@ struct Options {
 #endif
 };
 const char *const OPTION_NAMES[] = {"BVH", "NO_EXACT", "EXACT_ALL", "EXACT_FORM", "NO_DEFER", "NO_HIT4", "NO_HOIST", "NO_LDS_TABLES", "NO_LDS_TREES", "NO_LDS_TRIS",
-                                    "NO_SHORT_RAYS", "NO_TILE_ORDER", "NO_ZERO_SKIP", "DEP_PIXEL_MAJOR", "DEP_SLOT_MAJOR", "NO_CHAIN", "EXACT_PRODUCT", "PHASE_LOCK", "GRAPH", "SOFT_SHEAR_LOG2", "EXACT_SHEAR_LOG2", "EXACT_FAR_X", "WIDE_NODE_COST", "TRACE", "STREAMS", "WIDE", "BUILD", "WAVES",
+                                    "NO_SHORT_RAYS", "NO_TILE_ORDER", "NO_ZERO_SKIP", "DEP_PIXEL_MAJOR", "DEP_SLOT_MAJOR", "NO_CHAIN", "EXACT_PRODUCT", "PHASE_LOCK", "FUSE_SEGMENTS", "GRAPH", "SOFT_SHEAR_LOG2", "EXACT_SHEAR_LOG2", "EXACT_FAR_X", "WIDE_NODE_COST", "TRACE", "STREAMS", "WIDE", "BUILD", "WAVES",
                                     "PATHS_PER_BATCH", "DUMP_PATH",
 #if FW_AB
                                     "FUSED", "TLAS_REFILL", "SHADE_LIST", "NO_SHADE_DEFER", "STAGGER", "DEBUG_WIDE_LEVELS",
@@ -102,6 +103,7 @@ bool option_apply(Options &o, const char *name, const char *v) {      // v == nu
     else if (n == "NO_CHAIN") o.no_chain = on();
     else if (n == "EXACT_PRODUCT") o.exact_product = v && atoi(v) != 0;
     else if (n == "PHASE_LOCK") o.phase_lock = v ? (atoi(v) != 0 ? 1 : 0) : -1;
+    else if (n == "FUSE_SEGMENTS") o.fuse_segments = v ? (atoi(v) != 0 ? 1 : 0) : -1;
     else if (n == "GRAPH") o.graph = v ? (atoi(v) != 0 ? 1 : 0) : -1;
     else if (n == "SOFT_SHEAR_LOG2") o.soft_shear_log2 = v ? (int)num() : 5;
     else if (n == "EXACT_SHEAR_LOG2") o.exact_shear_log2 = v ? (int)num() : 10;
@@ -2179,6 +2181,16 @@ uint32_t default_paths_per_batch(const Options &O, size_t arena_bytes) {
 // The fields of the launch configuration that select and size the walks (launch_extend / launch_extend_exact): the scene's trees and
 // the options.  One function for render_impl and trace_impl, so that a trace runs the kernels a render of the scene runs.  Assigns
 // fields of a struct the caller has zeroed (the frame graph's key hashes its bytes, padding included).
+// k_shade's shading mode for a frame (LaunchCfg.shade_mode); cap: slots per queue (the A/B build's list mode holds 16-bit positions)
+static int frame_shade_mode(const fw_scene *sc, const Options &O, uint32_t cap) {
+    int mode = !sc->has_expensive ? 1 : 0;
+#if FW_AB
+    if (O.no_shade_defer) mode = 0; else if (sc->has_expensive && O.shade_list && cap <= 65536u && !sc->has_ggx) mode = 2;
+#else
+    (void)O; (void)cap;
+#endif
+    return mode;
+}
 void set_walk_cfg(fw::LaunchCfg &cfg, const fw_scene *sc, const Options &O, const fw::DQueue &q, bool use_bvh, bool tlas_refill) {
     cfg.q = q;
     cfg.tlas_depth = (int)sc->tlas_depth; cfg.blas_depth = (int)sc->blas_depth;
@@ -2464,30 +2476,6 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     n_lanes = (int)std::min<uint32_t>((uint32_t)n_lanes, n_batches);
     if (vg && spp_b >= (1u << 21)) return fail(FW_ERR_UNSUPPORTED, "too many samples per batch for a view group");   // (the quotients: key_of_linear, dep_bit_of)
 
-    // wave-private queues: many more waves than are resident, each owning >= 8 chunks of 64 paths when the batch allows
-    fw::DQueue q{};
-    // How many: whole rounds of resident waves for BOTH queue kernels (k_extend_linear holds 7 waves per SIMD, k_extend_bvh 5,
-    // k_shade 4 -> multiples of lcm x SIMDs), and 16-50 chunks per wave so that the half-empty last chunk of a queue stays
-    // small; measured on cornell (tools/waves_sweep.sh): whole frame 86 016 waves 41.1 ms vs 131 072: 42.0; the 1/4 share of
-    // a 4-GPU frame 57 344: 12.7 vs 13.7 ms; the 1/8 share 28 672: 6.30 vs 6.67 ms.
-    const uint32_t unit = (uint32_t)sc->n_cus * 4u * (p->use_bvh ? 20u : 28u);
-    const uint64_t chunks = ((uint64_t)max_paths + 63u) / 64u;
-    uint32_t want_waves = unit * (uint32_t)std::min<uint64_t>(3u, std::max<uint64_t>(1u, chunks / ((uint64_t)unit * 16u)));
-    // Round 4 (gpurun_out/r04i/share_waves.txt, r04j/cornell_waves.txt): with TWO batches in flight on a linear scene (the box lists: cornell)
-    // fewer, longer queues overlap better — whole frame 86 016 waves 36.4-37.0 ms, 28 672: 35.2-35.3 (its exclusive pass is slower: 40.6 vs
-    // 37.8) — and a small share keeps its queues long with 12 288: rank 0's eighth of the frame 5.9 -> 5.5 ms (79 -> 85 % of ideal).
-    if (!p->use_bvh && n_lanes > 1) want_waves = chunks >= (1u << 20) ? unit : (uint32_t)sc->n_cus * 48u;
-    if (O.waves > 0) want_waves = (uint32_t)O.waves;
-    q.n_waves = std::max(4u, std::min(want_waves, (max_paths + 511u) / 512u));
-    q.n_waves = (q.n_waves + 7u) & ~7u;       // a multiple of 8: one contiguous eighth of the queues per XCD (fw_kernels.hip: wave_index)
-    uint32_t chunks_per_wave = (max_paths + q.n_waves * 64u - 1) / (q.n_waves * 64u);
-    q.cpw_shift = 0;
-    while ((1u << q.cpw_shift) < chunks_per_wave) q.cpw_shift++;      // power of two: chunk -> (wave, row) is a shift
-    q.cap = 64u << q.cpw_shift;
-    uint64_t cap64 = (uint64_t)q.cap * q.n_waves;
-    if (cap64 > 0x7fffffffull) return fail(FW_ERR_UNSUPPORTED, "too many path slots");
-    uint32_t cap = (uint32_t)cap64;
-
     // the exact walk: ill-conditioned mesh rays in any mode, far origins and "every ray" (FIREWORK_EXACT_ALL) under use_bvh only
     // (the linear scan tests every object anyway: only a mesh's BLAS is walked there)
     // (FIREWORK_FUSED=1, the one-launch-per-segment A/B kernel, has no second pass: it runs without the exact walk)
@@ -2501,6 +2489,62 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     //  which caller rays along an axis have and camera rays practically never)
     const uint32_t exact_mode = fused_req ? 0u : ((sc->ex.mode & 1u) | (p->use_bvh ? (sc->ex.mode & 6u) | (ri ? fw::EX_TRACE_ZERO : 0u)
                                                                                    : ((sc->ex.mode & 4u) && sc->d.has_mesh ? 4u : 0u)));
+    // FUSE_SEGMENTS=1: a batch's 11 x (extend, shade) as ONE launch of k_segments_boxlist (fw_kernels.hip; DESIGN §5 "Fused segments") where
+    // the frame takes k_extend_linear_defer and k_shade<1,1,*> and nothing else between k_raygen and k_accumulate: no trees, no exact walk,
+    // no light sampling, no GgxMat, and neither per-launch timing nor the one-path dump, which want the launches apart.  An ineligible frame
+    // keeps its launches.  Decided here, before the queue count, which follows from it.  Off by default: DESIGN §8.
+    const bool timing = (p->flags & FW_FLAG_TIME_KERNELS) != 0;
+#if FW_AB
+    const bool stagger = n_lanes > 1 && O.stagger;   // experiment: batch b's first k_extend waits for batch b-1's
+#else
+    const bool stagger = false;
+#endif
+    // FIREWORK_DUMP_PATH=file, one pixel x one sample: after every k_extend the path's ray, state and hit record are copied out
+    // and written to `file` as 11 x 16 floats (ray_a[4] ray_b[2] state[4] hit[2] alive pad[3]) behind a header of 8 u32
+    // (magic, pinhole0, hit4, prim_bits, bits of cam_pos[3], n_defer).  Debug aid of tools/diverge.py; never on a timed path.
+    const char *dump_file = O.dump_path.c_str();
+    const bool dump_one = *dump_file && n_pix == 1 && p->samples == 1 && !fused_req;
+    fw::LaunchCfg cfg{};
+    {
+        fw::DQueue none{};
+        set_walk_cfg(cfg, sc, O, none, p->use_bvh != 0, tlas_refill);      // (again below, with the queues)
+        cfg.shade_mode = frame_shade_mode(sc, O, 0u); cfg.gx = sc->has_ggx;
+    }
+    const bool fuse_segments = O.fuse_segments == 1 && !p->use_bvh && exact_mode == 0 && !ls && !fused_req && !stagger && !timing && !dump_one &&
+                               fw::can_fuse_segments(cfg, sc->d);
+    // wave-private queues: many more waves than are resident, each owning >= 8 chunks of 64 paths when the batch allows
+    fw::DQueue q{};
+    constexpr uint64_t BIG_BATCH_CHUNKS = 1u << 20;     // batches of 67 M paths and more (what the counts below were measured at: 134 M)
+    // How many: whole rounds of resident waves for BOTH queue kernels (k_extend_linear holds 7 waves per SIMD, k_extend_bvh 5,
+    // k_shade 4 -> multiples of lcm x SIMDs), and 16-50 chunks per wave so that the half-empty last chunk of a queue stays
+    // small; measured on cornell (tools/waves_sweep.sh): whole frame 86 016 waves 41.1 ms vs 131 072: 42.0; the 1/4 share of
+    // a 4-GPU frame 57 344: 12.7 vs 13.7 ms; the 1/8 share 28 672: 6.30 vs 6.67 ms.
+    const uint32_t unit = (uint32_t)sc->n_cus * 4u * (p->use_bvh ? 20u : 28u);
+    const uint64_t chunks = ((uint64_t)max_paths + 63u) / 64u;
+    uint32_t want_waves = unit * (uint32_t)std::min<uint64_t>(3u, std::max<uint64_t>(1u, chunks / ((uint64_t)unit * 16u)));
+    // Round 4 (gpurun_out/r04i/share_waves.txt, r04j/cornell_waves.txt): with TWO batches in flight on a linear scene (the box lists: cornell)
+    // fewer, longer queues overlap better — whole frame 86 016 waves 36.4-37.0 ms, 28 672: 35.2-35.3 (its exclusive pass is slower: 40.6 vs
+    // 37.8) — and a small share keeps its queues long with 12 288: rank 0's eighth of the frame 5.9 -> 5.5 ms (79 -> 85 % of ideal).
+    if (!p->use_bvh && n_lanes > 1) want_waves = chunks >= BIG_BATCH_CHUNKS ? unit : (uint32_t)sc->n_cus * 48u;
+    // The kernels have changed since (k_extend 17.1 -> 13.7 ms), and the big box-list batches of the cheap shading mode (cornell: k_extend_linear_defer and
+    // k_shade<1,1,*>) now run faster on twice the queues (profiles/fused_segments_ab.txt, seven interleaved rounds at 134 M paths per batch:
+    // 28 672 queues 31.15 ms, 57 344: 30.15, 86 016: 30.89; an earlier set 114 688: 31.59).  Other scenes and smaller batches: not measured, as they were.
+    if (!p->use_bvh && n_lanes > 1 && chunks >= BIG_BATCH_CHUNKS && cfg.n_defer > 0 && cfg.shade_mode == 1 && !ls) want_waves = 2u * unit;
+    // A fused frame wants MORE queues still: with one round of resident waves it is slower than its two kernels apart.  Same file: 6 144 queues 39.2 ms, 12 288: 35.4, 28 672: 31.5, 57 344: 29.98,
+    // 86 016: 29.85, 114 688: 29.61, 229 376: 30.5.  (Why more rounds help was not looked into: that waves of later rounds sit in other phases
+    // is a guess.)  A smaller batch keeps the count it has.
+    if (fuse_segments && chunks >= BIG_BATCH_CHUNKS) want_waves = 4u * unit;
+    if (O.waves > 0) want_waves = (uint32_t)O.waves;
+    q.n_waves = std::max(4u, std::min(want_waves, (max_paths + 511u) / 512u));
+    q.n_waves = (q.n_waves + 7u) & ~7u;       // a multiple of 8: one contiguous eighth of the queues per XCD (fw_kernels.hip: wave_index)
+    uint32_t chunks_per_wave = (max_paths + q.n_waves * 64u - 1) / (q.n_waves * 64u);
+    q.cpw_shift = 0;
+    while ((1u << q.cpw_shift) < chunks_per_wave) q.cpw_shift++;      // power of two: chunk -> (wave, row) is a shift
+    q.cap = 64u << q.cpw_shift;
+    uint64_t cap64 = (uint64_t)q.cap * q.n_waves;
+    if (cap64 > 0x7fffffffull) return fail(FW_ERR_UNSUPPORTED, "too many path slots");
+    uint32_t cap = (uint32_t)cap64;
+
     const bool park_meshes = p->use_bvh && sc->d.has_mesh != 0 && tlas_refill;
     const bool stage_rays = ri && ri->per_sample && !ri->on_device;      // host rays of every sample: one batch's slab per lane
     int rc = FW_OK;
@@ -2607,7 +2651,6 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     else if (!rd) HIPCHK(hipMemsetAsync(ws->accum.p, 0, (size_t)n_pix * 16, stream));
     HIPCHK(hipMemsetAsync(ws->totals.p, 0, (size_t)n_batches * fw::COUNT_STRIDE * 4, stream));
 
-    fw::LaunchCfg cfg{};
     set_walk_cfg(cfg, sc, O, q, p->use_bvh != 0, tlas_refill);
     cfg.log = &ws->kernels;
     int max_blocks = sc->n_cus * 8;
@@ -2616,10 +2659,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // Default: the cheap loop alone where the scene has nothing expensive (cornell k_shade -5 %), everything in line otherwise — the
     // list (mode 2) is slower wherever it was measured (gpurun_out/r03h: part2@16 11.7 -> 12.0 ms, hdri@64 5.5 -> 6.1, random_spheres
     // 1.90 -> 1.98, volume@64 6.08 -> 6.12) and stays behind FIREWORK_SHADE_LIST=1; FIREWORK_NO_SHADE_DEFER=1 forces mode 0.
-    cfg.shade_mode = !sc->has_expensive ? 1 : 0;
-#if FW_AB
-    if (O.no_shade_defer) cfg.shade_mode = 0; else if (sc->has_expensive && O.shade_list && q.cap <= 65536u && !sc->has_ggx) cfg.shade_mode = 2;
-#endif
+    cfg.shade_mode = frame_shade_mode(sc, O, q.cap);
     cfg.gx = sc->has_ggx;
 
     fw::DCamera cam = vg ? vg->cams[0] : ri ? fw::DCamera{} : make_camera(p->camera, p->width, p->height);
@@ -2649,9 +2689,8 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     fr.chain_bits = (O.no_chain || fused_req || cfg.shade_mode == 2 || ls) ? 0u : sc->chain_bits;      // k_bounce and k_shade's list mode (A/B build) carry the running product
     fr.skip_zero_deposits = (env.kind == 0 && env.color[0] == 0.f && env.color[1] == 0.f && env.color[2] == 0.f && !O.no_zero_skip && !ls) ? 1u : 0u;
 
-    // per-launch timing (FW_FLAG_TIME_KERNELS): one event after every launch on the launch's own stream; the end of
+    // per-launch timing (FW_FLAG_TIME_KERNELS, `timing` above): one event after every launch on the launch's own stream; the end of
     // launch k is the start of launch k+1 of that lane.  With several lanes the intervals overlap in wall time.
-    const bool timing = (p->flags & FW_FLAG_TIME_KERNELS) != 0;
     const bool count_deposits = (p->flags & FW_FLAG_COUNT_DEPOSITS) != 0 && fr.skip_zero_deposits != 0;   // otherwise every terminated path writes one
     const size_t per_batch_launches = 1 + 3 * fw::MAX_SEGMENTS + 2 + (ls ? 2 * (fw::MAX_SEGMENTS - 1) : 0);     // raygen, 11 x (extend, exact extend, shade), queue totals, accumulate; light sampling: 10 x (shadow walk, resolve)
     std::vector<std::vector<int>> ev_class(n_lanes);   // per lane: class of the launch that ENDS at events[1 + k]
@@ -2666,17 +2705,6 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // Off by default: the frame is VALU-bound, not HBM-bound, and the fused kernel's lower occupancy costs more than the
     // bytes save (cornell 62.0 vs 55.5 ms, hdri 35.5 vs 38.5 ms, 1/8-frame shares 9.2 vs 8.3 ms).  Never with parked mesh rays.
     const bool fused = fused_req;
-#if FW_AB
-    const bool stagger = n_lanes > 1 && O.stagger;   // experiment: batch b's first k_extend waits for batch b-1's
-#else
-    const bool stagger = false;
-#endif
-
-    // FIREWORK_DUMP_PATH=file, one pixel x one sample: after every k_extend the path's ray, state and hit record are copied out
-    // and written to `file` as 11 x 16 floats (ray_a[4] ray_b[2] state[4] hit[2] alive pad[3]) behind a header of 8 u32
-    // (magic, pinhole0, hit4, prim_bits, bits of cam_pos[3], n_defer).  Debug aid of tools/diverge.py; never on a timed path.
-    const char *dump_file = O.dump_path.c_str();
-    const bool dump_one = *dump_file && n_pix == 1 && p->samples == 1 && !fused;
     std::vector<float> dump_rec(dump_one ? (size_t)fw::MAX_SEGMENTS * 16 : 0, 0.f);
 
     HIPCHK(hipEventRecord(ws->events[0], stream));
@@ -2705,7 +2733,8 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
     // on for the box-list scenes of the linear scan when a batch holds PHASE_LOCK_MIN_CHUNKS chunks of 64 paths (between the two sizes it
     // was measured to pay and not to pay at), off elsewhere.
     constexpr uint64_t PHASE_LOCK_MIN_CHUNKS = 3u << 19;      // 100 M paths
-    const bool phase_lock = n_lanes == 2 && !fused && (O.phase_lock == 1 || (O.phase_lock < 0 && !p->use_bvh && cfg.n_defer > 0 && chunks >= PHASE_LOCK_MIN_CHUNKS));
+    // (the lock ties launches that a fused frame, FUSE_SEGMENTS=1, does not have)
+    const bool phase_lock = !fuse_segments && n_lanes == 2 && !fused && (O.phase_lock == 1 || (O.phase_lock < 0 && !p->use_bvh && cfg.n_defer > 0 && chunks >= PHASE_LOCK_MIN_CHUNKS));
     std::vector<hipEvent_t> &pe = ws->phase_events;
     while (phase_lock && pe.size() < 2 * (size_t)fw::MAX_SEGMENTS) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); pe.push_back(e); }
     float4 *const accum = rd ? rd->accum : (float4 *)ws->accum.p;
@@ -2837,6 +2866,13 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
             else if (vg) timed(ctx[g], 0, [&] { fw::launch_raygen_views(ctx[g].cfg, (const fw::DCamera *)ws->view_cams.p, n_view, ctx[g].fr, ctx[g].buf[0], ctx[g].srad, ctx[g].n_paths); });
             else timed(ctx[g], 0, [&] { fw::launch_raygen(ctx[g].cfg, cam, ctx[g].fr, ctx[g].buf[0], ctx[g].srad, ctx[g].n_paths); });
         }
+        if (fuse_segments)
+            for (int g = 0; g < group; g++) {
+                BatchCtx &c = ctx[g];
+                fw::launch_segments(c.cfg, sc->d, c.fr, c.buf[0], c.buf[1], c.hits, c.srad, 0, fw::MAX_SEGMENTS - 1);
+                c.cur = fw::MAX_SEGMENTS & 1;
+            }
+        else
         for (int seg = 0; seg < fw::MAX_SEGMENTS; seg++)
             for (int g = 0; g < group; g++)
                 if (int src = segment(b0 + (uint32_t)g, ctx[g], seg, g, group)) return src;
@@ -2864,7 +2900,7 @@ int render_impl(fw_scene *sc, const fw_render_params *p, uint8_t *rgb8, float *g
             auto mix = [&](const void *ptr, size_t n) { const unsigned char *b = (const unsigned char *)ptr; for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; } };
             fw::LaunchCfg kc = cfg; kc.stream = nullptr;
             mix(&cam, sizeof cam); mix(&fr, sizeof fr); mix(&kc, sizeof kc); mix(&sc->d, sizeof sc->d); mix(&q, sizeof q);
-            const uint64_t scalars[] = {n_batches, (uint64_t)n_lanes, spp_b, first_sample, p->samples, n_pix, max_paths, cap, exact_mode, (uint64_t)park_meshes, (uint64_t)phase_lock,
+            const uint64_t scalars[] = {n_batches, (uint64_t)n_lanes, spp_b, first_sample, p->samples, n_pix, max_paths, cap, exact_mode, (uint64_t)park_meshes, (uint64_t)phase_lock, (uint64_t)fuse_segments,
                                         (uint64_t)count_deposits, (uint64_t)exact_product, (uint64_t)use_bvh, (uint64_t)fused, (uint64_t)stagger, (uint64_t)(uintptr_t)accum, (uint64_t)(uintptr_t)ws->totals.p,
                                         (uint64_t)(uintptr_t)ws->arena.p, (uint64_t)ws->arena.bytes};
             mix(scalars, sizeof scalars);
@@ -6333,6 +6369,9 @@ int fw_debug_kernels(int device, char *buf, uint32_t cap) {
                 const uint32_t waves[3] = {16u, 12u, 8u};
                 for (int b = 0; b < 3; b++) if (log.waves[i] & (1u << b)) names.push_back(std::string(fw::KERNEL_NAMES[i]) + "@" + std::to_string(waves[b]));
             }
+            // a fused launch (FUSE_SEGMENTS): beside the two kernels whose text it ran, its own name.  Names of a call only: the table of
+            // device -1 lists kernel texts, and this one has none of its own
+            for (int b = 0; b < 4; b++) if (log.fused & (1u << b)) names.push_back(fw::FUSED_KERNEL_NAMES[b]);
         }
         std::sort(names.begin(), names.end());
         std::string all;

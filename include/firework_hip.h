@@ -1595,6 +1595,8 @@ int fw_selftest_libm(int device, int fn, uint32_t n, const float *x, const float
                            a path deposits — render.rs:23-28's own association, the pre-gamma means then equal the CPU oracle's bit for bit
                            (scenes of constant textures always do: their 8-byte chain state).  Default off: the running product, ~1 ulp away
      PHASE_LOCK=0|1        the two batches in flight tied in anti-phase by one event per segment (default: big box-list batches)
+     FUSE_SEGMENTS=0|1     1: a box-list batch's segments in one launch (k_segments_boxlist) where the frame is eligible; the frame is the
+                           unfused frame bit for bit.  Default off
      GRAPH=0|1             a frame asked for twice in a row is captured into a hipGraph and replayed from then on (default: frames of
                            small batches, whose launches are short); fw_stats.reserved bit 31 reports a replay
      TRACE, DUMP_PATH=file                            host-side timing trace; one path's records (tools/diverge.py)
