@@ -6,8 +6,8 @@ ARCH ?= gfx950
 # -fno-slp-vectorize: packed f32 (v_pk_mul/add/fma) issues at half the rate of the scalar forms on gfx950
 # (tools/microbench.hip), so SLP-packed pairs gain nothing and their repacking v_movs cost: k_extend<false> 25.1 -> 20.3 ms.
 HIPFLAGS ?= -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize --offload-arch=$(ARCH) -Wall -Wno-unused-function
-SRC = firework_amd/csrc/fw_kernels.hip firework_amd/csrc/fw_build.hip firework_amd/csrc/fw_temporal.hip firework_amd/csrc/fw_camera_models.hip firework_amd/csrc/fw_probes.hip firework_amd/csrc/fw_lightmap.hip firework_amd/csrc/fw_probe_lookup.hip firework_amd/csrc/fw_runtime.cpp firework_amd/csrc/fw_probe_depth.hip firework_amd/csrc/fw_ao.hip firework_amd/csrc/fw_probe_place.hip firework_amd/csrc/fw_probe_radiance.hip firework_amd/csrc/fw_direct.hip firework_amd/csrc/fw_sky.hip firework_amd/csrc/fw_ggx_table.hip firework_amd/csrc/fw_gather.hip firework_amd/csrc/fw_reflect.hip firework_amd/csrc/fw_area.hip
-HDR = firework_amd/csrc/fw_accumulate_walk.inc firework_amd/csrc/fw_shade_nee.inc firework_amd/csrc/fw_shade_tables.inc firework_amd/csrc/fw_shade_body.inc firework_amd/csrc/fw_extend_defer.inc firework_amd/csrc/fw_device.h firework_amd/csrc/fw_build.h firework_amd/csrc/fw_temporal.h firework_amd/csrc/fw_camera_models.h firework_amd/csrc/fw_probes.h firework_amd/csrc/fw_lightmap.h firework_amd/csrc/fw_probe_lookup.h firework_amd/csrc/fw_probe_corners.h firework_amd/csrc/fw_shared.h firework_amd/csrc/fw_probe_depth.h firework_amd/csrc/fw_ao.h firework_amd/csrc/fw_probe_place.h firework_amd/csrc/fw_probe_radiance.h firework_amd/csrc/fw_direct.h firework_amd/csrc/fw_sky.h firework_amd/csrc/fw_probe_radiance_fetch.h firework_amd/csrc/fw_ggx_table.h firework_amd/csrc/fw_gather.h firework_amd/csrc/fw_reflect.h firework_amd/csrc/fw_area.h firework_amd/csrc/fw_libm.h firework_amd/csrc/fw_defer_pretest.h include/firework_hip.h Makefile
+SRC = firework_amd/csrc/fw_kernels.hip firework_amd/csrc/fw_build.hip firework_amd/csrc/fw_temporal.hip firework_amd/csrc/fw_camera_models.hip firework_amd/csrc/fw_probes.hip firework_amd/csrc/fw_lightmap.hip firework_amd/csrc/fw_probe_lookup.hip firework_amd/csrc/fw_runtime.cpp firework_amd/csrc/fw_probe_depth.hip firework_amd/csrc/fw_ao.hip firework_amd/csrc/fw_probe_place.hip firework_amd/csrc/fw_probe_radiance.hip firework_amd/csrc/fw_direct.hip firework_amd/csrc/fw_sky.hip firework_amd/csrc/fw_ggx_table.hip firework_amd/csrc/fw_gather.hip firework_amd/csrc/fw_reflect.hip firework_amd/csrc/fw_area.hip firework_amd/csrc/fw_emitters.hip
+HDR = firework_amd/csrc/fw_accumulate_walk.inc firework_amd/csrc/fw_shade_nee.inc firework_amd/csrc/fw_shade_tables.inc firework_amd/csrc/fw_shade_body.inc firework_amd/csrc/fw_extend_defer.inc firework_amd/csrc/fw_device.h firework_amd/csrc/fw_build.h firework_amd/csrc/fw_temporal.h firework_amd/csrc/fw_camera_models.h firework_amd/csrc/fw_probes.h firework_amd/csrc/fw_lightmap.h firework_amd/csrc/fw_probe_lookup.h firework_amd/csrc/fw_probe_corners.h firework_amd/csrc/fw_shared.h firework_amd/csrc/fw_probe_depth.h firework_amd/csrc/fw_ao.h firework_amd/csrc/fw_probe_place.h firework_amd/csrc/fw_probe_radiance.h firework_amd/csrc/fw_direct.h firework_amd/csrc/fw_sky.h firework_amd/csrc/fw_probe_radiance_fetch.h firework_amd/csrc/fw_ggx_table.h firework_amd/csrc/fw_gather.h firework_amd/csrc/fw_reflect.h firework_amd/csrc/fw_area.h firework_amd/csrc/fw_emitters.h firework_amd/csrc/fw_libm.h firework_amd/csrc/fw_defer_pretest.h include/firework_hip.h Makefile
 LIB = firework_amd/lib/libfirework_hip.so
 
 all: $(LIB) oracle examples

@@ -89,7 +89,12 @@ towards points drawn on the light as the pixel sees it, origins moved B >= 0, de
 path, fw_bake_area; -s is not used; refuses what --direct-light refuses, and --direct-light).  --probe-lit FILE
 --probe-gather D --area-light S (the final-gather split: the gather rays bring back nothing from those lights, FW_GATHER_NO_LIGHTS, and
 the lights' sampled irradiance is added to the gathered one before shading).  --probe-lit FILE --area-light S without --probe-gather is
-an error: the probes already hold the emitters' direct light, and adding it would count it twice."""
+an error: the probes already hold the emitters' direct light, and adding it would count it twice.
+--emitter-light S[,ROUNDS] [--emitter-bias B] (the same three behaviours over every emitter of the scene — spheres, rectangles, Rect3d
+faces, disks and mesh triangles: S shadow rays per pixel and round whatever the number of emitters, each towards an emitter picked in
+proportion to area x power, fw_bake_emitters; alone the view lit by the emitters alone; with --probe-lit FILE
+--probe-gather D the split with FW_GATHER_NO_EMITTERS; with --probe-lit alone an error; refuses what --area-light refuses, and
+--area-light)."""
 import argparse
 import sys
 import time
@@ -205,7 +210,38 @@ def main(argv=None):
                          "(default 1 round); with --probe-lit and --probe-gather: the final-gather split")
     ap.add_argument("--area-bias", type=float, default=None, metavar="B",
                     help="with --area-light: move shadow-ray origins B >= 0 world units along the normal (default 0.001)")
+    ap.add_argument("--emitter-light", default=None, metavar="S[,ROUNDS]",
+                    help="render the direct light of every emitter of the scene, S shadow rays per pixel and round towards emitters picked by "
+                         "power (default 1 round); with --probe-lit and --probe-gather: the final-gather split")
+    ap.add_argument("--emitter-bias", type=float, default=None, metavar="B",
+                    help="with --emitter-light: move shadow-ray origins B >= 0 world units along the normal (default 0.001)")
     opt = ap.parse_args(argv)
+    emit = None
+    if opt.emitter_light is not None:
+        if opt.area_light is not None:
+            ap.error("--emitter-light cannot be combined with --area-light: the area lights are among the emitters and would be sampled twice")
+        if opt.probe_lit is not None and opt.probe_gather is None:
+            ap.error("--probe-lit with --emitter-light needs --probe-gather: the probes already hold the emitters' direct light, so adding the "
+                     "sampled emitters' to a probe lookup at the pixel would count it twice")
+        if (opt.direct_light and opt.probe_lit is None) or opt.ao is not None or opt.bake_probes is not None or opt.bake_lightmap is not None \
+                or opt.camera != "pinhole" or opt.denoise is not None or opt.orbit or opt.adaptive is not None or opt.progressive > 0 or opt.checkpoint \
+                or opt.temporal is not None:
+            ap.error("--emitter-light cannot be combined with --direct-light (without --probe-lit), --ao, --bake-probes, --bake-lightmap, --camera, "
+                     "--denoise, --orbit, --adaptive, --progressive, --checkpoint or --temporal")
+        try:
+            emit = [int(x) for x in opt.emitter_light.split(",")]
+        except ValueError:
+            emit = []
+        if not 1 <= len(emit) <= 2 or not 1 <= emit[0] <= 1 << 20 or (len(emit) == 2 and emit[1] < 1):
+            ap.error("--emitter-light needs S[,ROUNDS]: 1 <= S <= 2^20, ROUNDS >= 1")
+        if opt.emitter_bias is not None and not 0.0 <= opt.emitter_bias < float("inf"):
+            ap.error("--emitter-bias B needs a finite B >= 0")
+        if opt.aov_samples < 1:
+            ap.error("--aov-samples needs S >= 1")
+        if not opt.output:
+            ap.error("--emitter-light needs -o FILE.png")
+    elif opt.emitter_bias is not None:
+        ap.error("--emitter-bias needs --emitter-light")
     area = None
     if opt.area_light is not None:
         if opt.probe_lit is not None and opt.probe_gather is None:
@@ -617,6 +653,10 @@ def main(argv=None):
         if area is not None:
             from .api import AreaLight
             area_light = AreaLight(area[0], 1e-3 if opt.area_bias is None else opt.area_bias).seed(opt.seed)
+        emitter_lights = None
+        if emit is not None:
+            from .api import EmitterLights
+            emitter_lights = EmitterLights(emit[0], 1e-3 if opt.emitter_bias is None else opt.emitter_bias).seed(opt.seed)
         reflection = None
         if reflect is not None:
             from .api import ReflectionGather
@@ -626,7 +666,8 @@ def main(argv=None):
                                            placement=probe_placement, radiance=probe_radiance, maps=probe_maps, direct=direct_light(opt),
                                            ggx_table=ggx_table, gather=final_gather, gather_rounds=gather[1] if gather and len(gather) == 2 else 1,
                                            reflect=reflection, reflect_rounds=reflect[1] if reflect and len(reflect) == 2 else 1,
-                                           area=area_light, area_rounds=area[1] if area and len(area) == 2 else 1).rgb8
+                                           area=area_light, area_rounds=area[1] if area and len(area) == 2 else 1,
+                                           emitters=emitter_lights, emitters_rounds=emit[1] if emit and len(emit) == 2 else 1).rgb8
         print(f"Finished Rendering in {int(time.time() - start)} s")
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)
@@ -635,6 +676,14 @@ def main(argv=None):
         from .api import AreaLight
         area_light = AreaLight(area[0], 1e-3 if opt.area_bias is None else opt.area_bias).seed(opt.seed)
         render = renderer.render_area(scene, area_light, area[1] if len(area) == 2 else 1, opt.aov_samples, device=opt.device).rgb8
+        print(f"Finished Rendering in {int(time.time() - start)} s")
+        print(f'Saving image to "{opt.output}"')
+        save_image(render, opt.output, opt.width, opt.height)
+        return 0
+    if emit is not None:
+        from .api import EmitterLights
+        emitter_lights = EmitterLights(emit[0], 1e-3 if opt.emitter_bias is None else opt.emitter_bias).seed(opt.seed)
+        render = renderer.render_emitters(scene, emitter_lights, emit[1] if len(emit) == 2 else 1, opt.aov_samples, device=opt.device).rgb8
         print(f"Finished Rendering in {int(time.time() - start)} s")
         print(f'Saving image to "{opt.output}"')
         save_image(render, opt.output, opt.width, opt.height)

@@ -299,6 +299,31 @@ AREA_PROTOTYPES = {
 }
 
 
+# every emitter sampled at surface points, picked by power (include/firework_hip.h: fw_selftest_emitters_records, fw_scene_emitters,
+# fw_emitters_cdf, fw_emitters_rays, fw_emitters_reduce, fw_bake_emitters); FW_GATHER_NO_EMITTERS is fw_gather.flags' bit for the
+# gather's complement
+FW_GATHER_NO_EMITTERS = 16
+FW_EMITTERS_RECORD_FLOATS = 16
+
+
+class fw_emitters(C.Structure):
+    _fields_ = [("samples", u32), ("jitter", u32), ("bias", f32), ("chunk_points", u32), ("seed", u64)]
+
+
+# the six prototypes (argument types; every one returns int), applied by _lib.load
+EMITTERS_PROTOTYPES = {
+    "fw_selftest_emitters_records": [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.POINTER(u32)],
+    "fw_scene_emitters": [C.c_void_p, C.c_void_p, C.c_void_p, u32, C.POINTER(u32)],
+    "fw_emitters_cdf": [C.c_void_p, u32, C.c_void_p, C.POINTER(C.c_double)],
+    "fw_emitters_rays": [C.POINTER(fw_emitters), C.c_void_p, C.c_void_p, u32, C.c_int, u32, u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, C.c_void_p,
+                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "fw_emitters_reduce": [C.c_int, u32, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                           C.c_void_p],
+    "fw_bake_emitters": [C.c_void_p, C.POINTER(fw_emitters), C.POINTER(fw_trace_params), u32, C.c_void_p, C.c_void_p, u32, C.c_void_p, u32, u32,
+                         C.c_void_p, C.c_void_p, C.POINTER(fw_stats)],
+}
+
+
 # SunSky: an analytic sun-and-sky environment (include/firework_hip.h: fw_check_sky, fw_sky_map, fw_sky_radiance, fw_sky_sun)
 FW_SKY_DISC = 1
 

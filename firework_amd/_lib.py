@@ -134,7 +134,7 @@ def load(preload=False, device=None):
     for name, argtypes in (list(A.PROBE_DEPTH_PROTOTYPES.items()) + list(A.AO_PROTOTYPES.items()) + list(A.PROBE_PLACE_PROTOTYPES.items())
                            + list(A.PROBE_RADIANCE_PROTOTYPES.items()) + list(A.DIRECT_PROTOTYPES.items()) + list(A.SKY_PROTOTYPES.items())
                            + list(A.GGX_TABLE_PROTOTYPES.items()) + list(A.GATHER_PROTOTYPES.items()) + list(A.REFLECT_PROTOTYPES.items())
-                           + list(A.AREA_PROTOTYPES.items())):
+                           + list(A.AREA_PROTOTYPES.items()) + list(A.EMITTERS_PROTOTYPES.items())):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = argtypes
     lib.fw_lightmap_texels.restype = C.c_int
@@ -1225,6 +1225,92 @@ def area_mask(hits, surface, objects, device=0, stream=None):
     return surface
 
 
+def emitters_records(scene_desc):
+    """fw_selftest_emitters_records (CPU only): the world-space records ((N, 16) float32: object, kind, 12 geometry floats, area, weight)
+    and codes ((N, 2) uint32: object, prim) of a SceneDesc's emitter entries, in fw_selftest_emitters' order: what emitters_rays and
+    emitters_reduce take"""
+    lib = load()
+    n = C.c_uint32()
+    _check(lib, lib.fw_selftest_emitters_records(scene_desc.ptr(), None, None, 0, C.byref(n)))
+    rec, codes = np.zeros((n.value, A.FW_EMITTERS_RECORD_FLOATS), np.float32), np.zeros((n.value, 2), np.uint32)
+    if n.value:
+        _check(lib, lib.fw_selftest_emitters_records(scene_desc.ptr(), rec.ctypes.data, codes.ctypes.data, n.value, C.byref(n)))
+    return rec, codes
+
+
+def emitters_cdf(weights):
+    """fw_emitters_cdf (CPU only): (cdf (N,) float64, total) of float32 weights — the records' last column — as api.emitters_cdf states it;
+    total 0 means "no emitters" and the cdf is zeros"""
+    lib = load()
+    w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+    cdf, total = np.zeros(w.size, np.float64), C.c_double()
+    _check(lib, lib.fw_emitters_cdf(w.ctypes.data, int(w.size), cdf.ctypes.data, C.byref(total)))
+    return cdf, total.value
+
+
+def _emitters_list(records, cdf):
+    """(contiguous (N, 16) float32 records, contiguous (N,) float64 cdf, N), host arrays"""
+    rec = np.ascontiguousarray(np.asarray(records, np.float32).reshape(-1, A.FW_EMITTERS_RECORD_FLOATS))
+    c = np.ascontiguousarray(np.asarray(cdf, np.float64).reshape(-1))
+    if c.size != rec.shape[0]:
+        raise ValueError("cdf must have one value per record")
+    return rec, c, int(rec.shape[0])
+
+
+def _picks(s, picks, total):
+    """the picks of a call on side s: the caller's own (a contiguous uint32 array, or an int32 tensor of their bits), or a new one"""
+    if picks is None:
+        return s.new((total,), "ids")
+    if s.on_device:
+        _check_device_tensor(picks, (total,), s._dtype("ids"), s.device, "picks")
+    elif not (isinstance(picks, np.ndarray) and picks.dtype == np.uint32 and picks.shape == (total,) and picks.flags.c_contiguous):
+        raise ValueError(f"picks must be a contiguous uint32 array of shape ({total},)")
+    return picks
+
+
+def emitters_rays(emitters, records, cdf, positions, normals, ids=None, round=0, device=0, out=None, weights=None, picks=None, stream=None):
+    """fw_emitters_rays: the shadow rays of round `round` of an api.EmitterLights from surface points (see _AoPoints) towards entries of
+    `records` ((N, 16) float32) picked through `cdf` ((N,) float64; host arrays always), generated on the device: (rays (n * S, 6)
+    float32, weights (n * S,) float32, picks (n * S,) uint32 — on the device their int32 bits), entry q * S + s = sample s from point
+    ids[q] (ids None: q); a dead entry is six zeros, the weight 0 and the pick 0xffffffff.  numpy points: returns numpy arrays.  Points on
+    cuda:`device`: generated on `stream` (default: the current torch stream) where they lie; returns device tensors.  out, weights,
+    picks: contiguous arrays or tensors of those shapes to fill instead."""
+    lib = load()
+    a = emitters.to_abi()
+    rec, c, ne = _emitters_list(records, cdf)
+    pts = _AoPoints(positions, normals, ids, device)
+    s = pts.side
+    total = pts.n * int(a.samples)
+    out, weights, picks = s.out(out, (total, 6), "out"), s.out(weights, (total,), "weights"), _picks(s, picks, total)
+    _check(lib, lib.fw_emitters_rays(C.byref(a), rec.ctypes.data, c.ctypes.data, ne, int(device), int(round), pts.n, pts.pos, pts.nrm, pts.stride,
+                                     pts.ids, *s.ptrs(out, weights, picks), *s.tail(stream)))
+    return out, weights, picks
+
+
+def emitters_reduce(picks, weights, hits, surface, codes, samples, sums, ids=None, device=0, stream=None):
+    """fw_emitters_reduce: adds one round's reduction (E.rgb, vis, each rounded to float32 once) of an api.EmitterLights to sums[ids[q]]
+    (ids None: sums[q]); sums (M, 4) or (H, W, 4) float32, updated in place.  picks and weights (n * S,) as emitters_rays returns them,
+    hits as DeviceScene.trace returns them for those rays, surface (n * S, 16) float32 as DeviceScene.hit_surface returns it for them:
+    numpy arrays (hits a HIT_DTYPE array), or tensors on cuda:`device`, reduced on `stream` (default: the current torch stream) where
+    they lie.  codes: (N, 2) uint32 (object, prim) per entry, a host array always.  Returns sums."""
+    lib = load()
+    cod = np.ascontiguousarray(np.asarray(codes).astype(np.uint32).reshape(-1, 2))
+    m = int(samples)
+    total = int(surface.shape[0])
+    if m < 1 or total % m or tuple(surface.shape) != (total, 16) or int(hits.shape[0]) != total:
+        raise ValueError(f"surface must have shape (n * {m}, 16) and hits n * {m} records")
+    n = total // m
+    rows = int(np.prod(tuple(sums.shape)[:-1]))
+    if sums.shape[-1] != 4 or (ids is None and rows < n) or (ids is not None and tuple(ids.shape) != (n,)):
+        raise ValueError(f"sums must have shape (M, 4) or (H, W, 4) with M >= {n}, ids shape ({n},)")
+    s = _Side(surface, device)
+    p, w, h, rec = s.inp(picks, (total,), "picks", "ids"), s.inp(weights, (total,), "weights"), s.hits(hits, total), s.inp(surface, (total, 16), "surface")
+    s.out(sums, tuple(sums.shape), "sums")
+    i = s.inp(ids, (n,), "ids", "ids", below=rows)
+    _check(lib, lib.fw_emitters_reduce(int(device), m, cod.ctypes.data, int(cod.shape[0]), n, *s.ptrs(i, p, w, h, rec, sums), *s.tail(stream)))
+    return sums
+
+
 def _sky_abi(sky):
     """a fw_sky from an api.SunSky (or a fw_sky, copied)"""
     return sky.to_abi() if hasattr(sky, "to_abi") else A.fw_sky.from_buffer_copy(sky)
@@ -1775,6 +1861,30 @@ class DeviceScene:
             a.chunk_points = int(chunk)
         pts = _AoPoints(positions, normals, ids, self.device)
         return self._bake_points(self._lib.fw_bake_area, a, pts, 4, (pts.n, pts.pos, pts.nrm, pts.stride, pts.ids), rounds, first_round, sums, out,
+                                 seed, use_bvh, stream, rays_per_batch, flags)
+
+    def emitters(self):
+        """fw_scene_emitters: (records (N, 16) float32, codes (N, 2) uint32) of this resident scene's emitter entries — every EmissiveMat
+        sphere, rectangle, Rect3d face, disk and mesh triangle of positive power, where fw_scene_update last put them — in
+        fw_selftest_emitters' order: what emitters_rays and emitters_reduce take."""
+        n = C.c_uint32()
+        _check(self._lib, self._lib.fw_scene_emitters(self.handle, None, None, 0, C.byref(n)))
+        rec, codes = np.zeros((n.value, A.FW_EMITTERS_RECORD_FLOATS), np.float32), np.zeros((n.value, 2), np.uint32)
+        if n.value:
+            _check(self._lib, self._lib.fw_scene_emitters(self.handle, rec.ctypes.data, codes.ctypes.data, n.value, C.byref(n)))
+        return rec, codes
+
+    def bake_emitters(self, emitters, positions, normals, ids=None, rounds=1, first_round=0, sums=None, out=None, seed=0, use_bvh=True, stream=None,
+                      rays_per_batch=0, flags=0, chunk=None):
+        """fw_bake_emitters: the rounds [first_round, first_round + rounds) of an api.EmitterLights at surface points (see _AoPoints:
+        numpy arrays, or tensors on this scene's device, read in place) under this scene's own emitter entries (emitters), picked by
+        power, `chunk` points at a time (None: the description's own setting; 0: automatic).  sums, out and the return value as
+        bake_area's: (out, sums, stats) with (Er, Eg, Eb, vis) per id."""
+        a = emitters.to_abi()
+        if chunk is not None:
+            a.chunk_points = int(chunk)
+        pts = _AoPoints(positions, normals, ids, self.device)
+        return self._bake_points(self._lib.fw_bake_emitters, a, pts, 4, (pts.n, pts.pos, pts.nrm, pts.stride, pts.ids), rounds, first_round, sums, out,
                                  seed, use_bvh, stream, rays_per_batch, flags)
 
     def bake_lightmap(self, lightmap, rounds, samples, first_round=0, sums=None, dilate=2, seed=0, use_bvh=True, stream=None, paths_per_batch=0,

@@ -2972,12 +2972,14 @@ class FinalGather:
     and round, origins moved `bias` along the normal; each ray brings back the emission of the emitter it hit, the environment where it
     missed, or hit albedo x E(hit) / pi with E from the probes at the hit.  direct=True adds the scene's point, spot and directional
     lights at the gather hits, their shadow rays moved direct_bias along the hit's normal.  no_lights=True (FW_GATHER_NO_LIGHTS) is the
-    complement of an AreaLight: a ray that hits one of the scene's sampled area lights brings back nothing.  .seed(s) / .jitter(on) as
-    builders; chunk_points as fw_gather's."""
+    complement of an AreaLight: a ray that hits one of the scene's sampled area lights brings back nothing; no_emitters=True
+    (FW_GATHER_NO_EMITTERS) is the complement of an EmitterLights: the same for every object with an emitter entry (the two exclude each
+    other).  .seed(s) / .jitter(on) as builders; chunk_points as fw_gather's."""
 
-    def __init__(self, directions: int = 64, bias: float = 1e-3, direct: bool = False, direct_bias: float = 1e-3, no_lights: bool = False):
+    def __init__(self, directions: int = 64, bias: float = 1e-3, direct: bool = False, direct_bias: float = 1e-3, no_lights: bool = False,
+                 no_emitters: bool = False):
         self.directions, self.bias, self.direct, self.direct_bias = int(directions), float(np.float32(bias)), bool(direct), float(np.float32(direct_bias))
-        self.no_lights = bool(no_lights)
+        self.no_lights, self.no_emitters = bool(no_lights), bool(no_emitters)
         self._seed, self._jitter, self.chunk_points = 0, True, 0
 
     def seed(self, s):
@@ -3006,6 +3008,7 @@ class FinalGather:
         g = A.fw_gather()
         g.directions, g.jitter, g.bias, g.direct_bias = self.directions & 0xFFFFFFFF, int(self._jitter), self.bias, self.direct_bias
         g.flags = (A.FW_GATHER_DIRECT if self.direct else 0) | (A.FW_GATHER_NO_LIGHTS if getattr(self, "no_lights", False) else 0)
+        g.flags |= A.FW_GATHER_NO_EMITTERS if getattr(self, "no_emitters", False) else 0
         g.chunk_points, g.seed = int(self.chunk_points), self._seed & 0xFFFFFFFFFFFFFFFF
         return g
 
@@ -3436,6 +3439,223 @@ def area_mask(hits_object, surface, objects) -> np.ndarray:
     s[hit] = 0
     s[hit, 3] = -2
     return s
+
+
+# --------------------------------------------------------------------------- every emitter at surface points (fw_bake_emitters)
+class EmitterLights:
+    """The direct light of every emitting primitive of a scene — EmissiveMat spheres, rectangles, Rect3d faces, disks and mesh triangles —
+    at surface points (fw_emitters): `samples` shadow rays per point and round whatever the number of emitters, each
+    towards an entry picked in proportion to area x power, origins moved `bias` along the normal.  .seed(s) / .jitter(on) as builders;
+    chunk_points as fw_emitters'."""
+
+    def __init__(self, samples: int = 16, bias: float = 1e-3):
+        self.samples, self.bias = int(samples), float(np.float32(bias))
+        self._seed, self._jitter, self.chunk_points = 0, True, 0
+
+    def seed(self, s):
+        self._seed = int(s)
+        return self
+
+    def jitter(self, on=True):
+        self._jitter = bool(on)
+        return self
+
+    def check(self):
+        """what fw_emitters_rays rejects in a description, as a ValueError, in its order"""
+        if not 1 <= self.samples <= 1 << 20:
+            raise ValueError("samples must be in 1..2^20")
+        if not (np.isfinite(self.bias) and self.bias >= 0.0):
+            raise ValueError("bias must be finite and >= 0")
+        return self
+
+    def to_abi(self) -> A.fw_emitters:
+        a = A.fw_emitters()
+        a.samples, a.jitter, a.bias = self.samples & 0xFFFFFFFF, int(self._jitter), self.bias
+        a.chunk_points, a.seed = int(self.chunk_points), self._seed & 0xFFFFFFFFFFFFFFFF
+        return a
+
+
+def emitters_cdf(weights):
+    """The numpy statement of fw_emitters_cdf: (cdf (N,) float64, total): float64 inclusive prefix sums of the float32 weights in entry
+    order, a negative or non-finite weight counted as 0, each divided by the last; total 0: "no emitters", the cdf is zeros."""
+    w = np.asarray(weights, np.float32).reshape(-1).astype(np.float64)
+    w = np.where(np.isfinite(w) & (w > 0), w, 0.0)
+    c = np.zeros(w.size)
+    total = 0.0
+    for i in range(w.size):                                                                  # (sequential: np.cumsum's order is its own)
+        total = total + float(w[i])
+        c[i] = total
+    if not (total > 0.0 and np.isfinite(total)):
+        return np.zeros(w.size), 0.0
+    return c / total, total
+
+
+def emitters_rays(emitters: "EmitterLights", records, cdf, positions, normals, ids=None, round: int = 0, device=None):
+    """The numpy statement of fw_emitters_rays: (rays (n * S, 6) float32, weights (n * S,) float32, picks (n * S,) uint32), entry q * S +
+    s = sample s from point id = ids[q] (ids None: q) of positions and normals, (M, 3) float32 each, towards the entry of `records` ((N,
+    16) float32) picked through `cdf` ((N,) float64 as emitters_cdf gives it; device: see panorama_rays; weights and picks stay numpy).
+    Float64 from the float32 inputs in the header's order, one rounding to float32; a dead entry is six zeros, weight 0, pick 0xffffffff."""
+    of, df, weights, picks, _margin = _emitters_entries(emitters, records, cdf, positions, normals, ids, round)
+    return _rays_out(of, df, device), weights, picks
+
+
+def _emitters_entries(emitters, records, cdf, positions, normals, ids, round):
+    """emitters_rays' arithmetic: (origins (n * S, 3), directions (n * S, 3), weights, picks, margin), margin (n * S,) float64 = how far
+    the entry's liveness tests (n . w > 0, a sphere's |v|^2 > r^2) are from their boundary in float64 (NaN at an unusable point)"""
+    S = int(emitters.samples)
+    if S < 1:
+        raise ValueError("samples must be >= 1")
+    L = np.asarray(records, np.float32).reshape(-1, A.FW_EMITTERS_RECORD_FLOATS)
+    cd = np.asarray(cdf, np.float64).reshape(-1)
+    N = L.shape[0]
+    if N < 1 or cd.size != N or not cd[-1] == 1.0:
+        raise ValueError("records and a cdf that ends in 1 are needed")
+    P, Nn = np.asarray(positions, np.float32).reshape(-1, 3), np.asarray(normals, np.float32).reshape(-1, 3)
+    ids = np.arange(P.shape[0], dtype=np.uint32) if ids is None else np.asarray(ids, np.uint32).reshape(-1)
+    at = ids.astype(np.int64)
+    n = at.size
+    p32, n32 = P[at], Nn[at]
+    usable = ao_usable(p32, n32)[:, None]                                                    # (n, 1), broadcast over (n, S)
+    xj = (texel_jitter(emitters._seed, round, at) if emitters._jitter else np.full((n, 2), 0.5)).reshape(n, 1, 2)
+    s = np.arange(S, dtype=np.float64)[None, :]
+    G = 0.6180339887498949
+    PI = 3.141592653589793
+    with np.errstate(all="ignore"):
+        a1 = (s + xj[..., 0]) / float(S)
+        xi = a1 - np.floor(a1)
+        a2 = s * G + xj[..., 1]
+        u2 = a2 - np.floor(a2)
+        pick = np.minimum(np.searchsorted(cd, xi, side="right"), N - 1)                      # the first index with cdf[index] > xi
+        lo = np.where(pick > 0, cd[np.maximum(pick - 1, 0)], 0.0)
+        pp = cd[pick] - lo
+        u1 = np.minimum((xi - lo) / pp, 1.0 - 2.0 ** -53)
+        Lg = L.astype(np.float64)[pick]                                                      # (n, S, 16)
+        kind = L[:, 1][pick]
+        g12 = [Lg[..., 2 + k] for k in range(12)]
+        r = n32.astype(np.float64)
+        rl = np.sqrt((r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]) + r[:, 2] * r[:, 2])
+        nh = [(r[:, k] / rl)[:, None] for k in range(3)]
+        p = [p32[:, k].astype(np.float64)[:, None] for k in range(3)]
+        bias = float(F32(emitters.bias))
+        o = p if emitters.bias == 0.0 else [p[k] + bias * nh[k] for k in range(3)]
+        c0, q1, q2, c3 = g12[0:3], g12[3:6], g12[6:9], g12[9:12]
+        cross = lambda a, b: [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+        # rectangles and Rect3d faces: corners c0, c1 = q1, c3
+        e1 = [q1[k] - c0[k] for k in range(3)]
+        e2r = [c3[k] - c0[k] for k in range(3)]
+        d_r = [((c0[k] + u1 * e1[k]) + u2 * e2r[k]) - o[k] for k in range(3)]
+        nl_r = cross(e1, e2r)
+        L_r = np.sqrt(_dotd(nl_r, nl_r))
+        A_r = L_r
+        # triangles: v0 = c0, v1 = q1, v2 = q2
+        e2t = [q2[k] - c0[k] for k in range(3)]
+        sq = np.sqrt(u1)
+        b0, b1, b2 = 1.0 - sq, sq * (1.0 - u2), sq * u2
+        d_t = [((b0 * c0[k] + b1 * q1[k]) + b2 * q2[k]) - o[k] for k in range(3)]
+        nl_t = cross(e1, e2t)
+        L_t = np.sqrt(_dotd(nl_t, nl_t))
+        A_t = L_t / 2.0
+        # disks: centre c0, axes q1 and q2, then r, r_in, phi_max
+        ro2, ri2 = c3[0] * c3[0], c3[1] * c3[1]
+        rr_d = np.sqrt(ri2 + u1 * (ro2 - ri2))
+        phi_d = u2 * c3[2]
+        ca, sa = rr_d * np.cos(phi_d), rr_d * np.sin(phi_d)
+        d_d = [((c0[k] + ca * q1[k]) + sa * q2[k]) - o[k] for k in range(3)]
+        nl_d = cross(q1, q2)
+        L_d = np.sqrt(_dotd(nl_d, nl_d))
+        A_d = (0.5 * c3[2]) * (ro2 - ri2)
+        is_t, is_d = kind == 5, kind == 9
+        sel = lambda t, dk, rc: np.where(is_t, t, np.where(is_d, dk, rc))
+        df_ = [sel(d_t[k], d_d[k], d_r[k]) for k in range(3)]
+        nl = [sel(nl_t[k], nl_d[k], nl_r[k]) for k in range(3)]
+        Ln_, Ar = sel(L_t, L_d, L_r), sel(A_t, A_d, A_r)
+        d2 = _dotd(df_, df_)
+        dl = np.sqrt(d2)
+        w = [df_[k] / dl for k in range(3)]
+        cr_f = _dotd(nh, w)
+        cl = np.abs(_dotd(nl, w) / Ln_)
+        g_f = ((cr_f * cl) * Ar) / d2
+        live_f = (cr_f > 0.0) & (Ar > 0.0) & (Ln_ > 0.0)
+        # spheres: area_rays' cone
+        v = [c0[k] - o[k] for k in range(3)]
+        dv = _dotd(v, v)
+        rr = g12[3]
+        r2 = rr * rr
+        s2 = r2 / dv
+        cmax = np.sqrt(1.0 - s2)
+        omc = s2 / (1.0 + cmax)
+        om = u1 * omc
+        ct = 1.0 - om
+        st = np.sqrt(np.fmax(om * (2.0 - om), 0.0))
+        phi = (2.0 * PI) * u2
+        lx, ly = st * np.cos(phi), st * np.sin(phi)
+        dist = np.sqrt(dv)
+        wv = [v[k] / dist for k in range(3)]
+        sg = np.copysign(1.0, wv[2])
+        a = -1.0 / (sg + wv[2])
+        b = (wv[0] * wv[1]) * a
+        T = (1.0 + (sg * (wv[0] * wv[0])) * a, sg * b, -sg * wv[0])
+        B = (b, sg + (wv[1] * wv[1]) * a, -wv[1])
+        ex = [(lx * T[k] + ly * B[k]) + ct * wv[k] for k in range(3)]
+        bb = _dotd(ex, v)
+        tt = bb - np.sqrt(np.fmax(bb * bb - (dv - r2), 0.0))
+        ds = [tt * ex[k] for k in range(3)]
+        dls = np.sqrt(_dotd(ds, ds))
+        cr_s = _dotd(nh, [ds[k] / dls for k in range(3)])
+        g_s = (cr_s * (2.0 * PI)) * omc
+        live_s = (dv > r2) & (cr_s > 0.0)
+        sphere = kind == 0
+        g = np.where(sphere, g_s, g_f) / pp
+        d = np.stack([np.where(sphere, ds[k], df_[k]) for k in range(3)], axis=-1)
+        o3 = np.stack([np.broadcast_to(o[k], g.shape) for k in range(3)], axis=-1)
+        gf, df, of = g.astype(np.float32), d.astype(np.float32), o3.astype(np.float32)
+        live = (usable & np.where(sphere, live_s, live_f) & np.isfinite(g) & (gf > 0) & np.isfinite(gf) & np.all(np.isfinite(df), axis=-1)
+                & np.all(np.isfinite(of), axis=-1) & np.any(df != 0, axis=-1))
+    weights = np.where(live, gf, np.float32(0)).astype(np.float32).reshape(-1)
+    picks = np.where(live, pick, 0xFFFFFFFF).astype(np.uint32).reshape(-1)
+    of = np.where(live[..., None], of, np.float32(0)).reshape(-1, 3)
+    df = np.where(live[..., None], df, np.float32(0)).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        margin = np.where(sphere, np.minimum(np.abs(cr_s), np.abs(dv - r2)), np.abs(cr_f)).reshape(-1)
+    return of, df, weights, picks, margin
+
+
+def emitters_reduce(picks, weights, hits_object, hits_prim, surface, codes, samples: int) -> np.ndarray:
+    """The numpy float64 statement of fw_emitters_reduce: (n, 4) float64, (1 / S) x the accumulators E.rgb and V of one round before their
+    one rounding to float32, for picks (n * S,) uint32, weights (n * S,) float32, the hits' object and prim columns (uint32), surface (n *
+    S, 16) float32 records and codes (N, 2) uint32, summed in the device's order (G partial sums, an xor butterfly)."""
+    S = int(samples)
+    cod = np.asarray(codes).astype(np.uint32).reshape(-1, 2)
+    w = np.asarray(weights, np.float32).reshape(-1, S)
+    n = w.shape[0]
+    pk = np.asarray(picks).astype(np.uint32).reshape(n, S)
+    ho, hp = np.asarray(hits_object).astype(np.uint32).reshape(n, S), np.asarray(hits_prim).astype(np.uint32).reshape(n, S)
+    s = np.asarray(surface, np.float32).reshape(n, S, 16)
+    valid = pk < cod.shape[0]
+    at = np.where(valid, pk, 0).astype(np.int64)
+    counts = (w > 0) & valid & (ho == cod[at, 0]) & (hp == cod[at, 1]) & (s[..., 3] == np.float32(3))
+    with np.errstate(all="ignore"):
+        term = np.concatenate([s[..., 12:15].astype(np.float64) * w.astype(np.float64)[..., None], np.ones((n, S, 1))], axis=-1)
+    G = 1
+    while G < min(S, 64):
+        G *= 2
+    rows = -(-S // G)                                                                        # lane l takes m = l, l + G, ... in ascending order
+    padded = np.zeros((n, rows * G, 4))
+    padded[:, :S] = term
+    take = np.zeros((n, rows * G), bool)
+    take[:, :S] = counts
+    part = np.zeros((n, G, 4))
+    with np.errstate(all="ignore"):
+        for row, on in zip(padded.reshape(n, rows, G, 4).transpose(1, 0, 2, 3), take.reshape(n, rows, G).transpose(1, 0, 2)):
+            part = np.where(on[..., None], part + row, part)                                 # (an entry that does not count adds nothing)
+        m = G // 2
+        while m >= 1:
+            part = part + part[:, np.arange(G) ^ m]
+            m //= 2
+        return (1.0 / S) * part[:, 0, :]
+
+
+emitters_resolve = area_resolve
 
 
 # --------------------------------------------------------------------------- direct light of delta lights (fw_bake_direct; DESIGN.md §9w)
@@ -4252,15 +4472,55 @@ class Renderer:
                 ds.close()
         return RenderResult(rgb8.cpu().numpy(), gam.cpu().numpy(), lin.cpu().numpy(), stats, w, h)
 
-    def _gather(self, ds, gather: "FinalGather", rounds, grid, d_sh, aov, depth, d_mom, normal_bias, d_pl, direct=None, no_lights=False):
+    def _emitters(self, ds, emitters: "EmitterLights", rounds, aov):
+        """(out (N, 4), sums (N, 4)) device tensors: fw_bake_emitters on the records `aov` in place (stride 12, aov + 8 / aov + 4) with
+        this renderer's seed, use_bvh and flags.  The call's stats are kept in self.emitters_stats."""
+        s = self.settings
+        out, sums, self.emitters_stats = ds.bake_emitters(emitters, aov[:, 8:11], aov[:, 4:7], None, rounds, seed=s["seed"], use_bvh=s["use_bvh"],
+                                                          flags=s["flags"])
+        return out, sums
+
+    def render_emitters(self, scene, emitters: "EmitterLights", rounds: int = 1, aov_samples: int = 1, model: "CameraModel" = None,
+                        device: int = 0) -> RenderResult:
+        """This renderer's view lit by every emitter of the scene alone — spheres, rectangles, Rect3d faces, disks and mesh triangles —
+        by light sampling with the emitter picked by power (not in the reference; fw_bake_emitters).  Composed exactly
+        as render_area composes: the first-hit guide buffers stay on the device, fw_bake_emitters reads each pixel's position and normal
+        from the records in place, `rounds` rounds of emitters.samples shadow rays, and with E its out the frame is a ((v E) float32(1 /
+        pi)) in float32, resolved by fw_denoise at 0 iterations.  The call's stats are kept in self.emitters_stats.  `scene`: a Scene,
+        a SceneDesc or an uploaded _lib.DeviceScene."""
+        import torch
+        from . import _lib
+        emitters.check()
+        s = self.settings
+        w, h = (int(model.width), int(model.height)) if model is not None else (int(s["width"]), int(s["height"]))
+        ds = scene if isinstance(scene, _lib.DeviceScene) else _lib.DeviceScene(scene if isinstance(scene, SceneDesc) else scene.to_desc(), device)
+        try:
+            aov = torch.empty((w * h, 12), dtype=torch.float32, device=torch.device("cuda", ds.device))
+            if model is not None:
+                ds.model_aovs(model, aov_samples, seed=s["seed"], use_bvh=s["use_bvh"], out=aov)
+            else:
+                ds.aovs(self, aov_samples, out=aov)
+            E = self._emitters(ds, emitters, rounds, aov)[0]
+            term = aov[:, 0:3] * ((aov[:, 3:4] * E[:, 0:3]) * float(np.float32(1.0 / np.pi)))
+            rgb8, gam, lin = _lib.denoise(term.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)
+            stats = dict(ds.aovs_stats)
+        finally:
+            if ds is not scene:
+                ds.close()
+        return RenderResult(rgb8.cpu().numpy(), gam.cpu().numpy(), lin.cpu().numpy(), stats, w, h)
+
+    def _gather(self, ds, gather: "FinalGather", rounds, grid, d_sh, aov, depth, d_mom, normal_bias, d_pl, direct=None, no_lights=False,
+                no_emitters=False):
         """(out (N, 4), sums (N, 4)) device tensors: fw_bake_gather on the records `aov` in place (stride 12, aov + 8 / aov + 4) with this
         renderer's seed, use_bvh and flags; with `direct`, a DirectLight, FW_GATHER_DIRECT with its bias; with no_lights,
-        FW_GATHER_NO_LIGHTS.  The call's stats are kept in self.gather_stats."""
+        FW_GATHER_NO_LIGHTS; with no_emitters, FW_GATHER_NO_EMITTERS.  The call's stats are kept in self.gather_stats."""
         import copy
         s = self.settings
         g = copy.copy(gather)
         if no_lights:
             g.no_lights = True
+        if no_emitters:
+            g.no_emitters = True
         if direct is not None:
             g.direct, g.direct_bias = True, direct.bias
         out, sums, self.gather_stats = ds.bake_gather(g, grid, d_sh, aov[:, 8:11], aov[:, 4:7], None, depth, d_mom, normal_bias, d_pl, rounds,
@@ -4365,7 +4625,7 @@ class Renderer:
                          ao_rounds: int = 1, placement=None, radiance: "ProbeRadiance" = None, maps=None,
                          direct: "DirectLight" = None, ggx_table: "GgxTable" = None, table=None, gather: "FinalGather" = None,
                          gather_rounds: int = 1, reflect: "ReflectionGather" = None, reflect_rounds: int = 1, area: "AreaLight" = None,
-                         area_rounds: int = 1) -> RenderResult:
+                         area_rounds: int = 1, emitters: "EmitterLights" = None, emitters_rounds: int = 1) -> RenderResult:
         """A preview lit from baked probes (not in the reference): the first-hit guide buffers of this renderer's view
         (fw_render_aovs at `aov_samples` samples; with `model`, a CameraModel, fw_render_model_aovs through it) shaded by fw_probe_shade
         from the probe grid `probes` (a ProbeSet made by ProbeSet.grid, or a ProbeGrid, whose own wrap then counts) and its coefficients
@@ -4409,9 +4669,20 @@ class Renderer:
         back nothing from the scene's sampled area lights, fw_bake_area runs `area_rounds` rounds on the records in place, and its
         out's E is added in float32 to Eg before the gathered frame is shaded: out_c = a_c (v ((Eg_c + Ea_c) float32(1 / pi)) + (1 -
         v)).  The call's stats are kept in self.area_stats.  area without gather: ValueError, because the probes' SH already holds the
-        emitters' direct light and adding it would count it twice.  area=None: the calls and the bits above."""
+        emitters' direct light and adding it would count it twice.  area=None: the calls and the bits above.  emitters (an
+        EmitterLights), with gather: the same split over every emitter — the gather runs with FW_GATHER_NO_EMITTERS,
+        fw_bake_emitters runs `emitters_rounds` rounds on the records in place, and its out's E is added in float32 to Eg before
+        shading, as area's is.  The call's stats are kept in self.emitters_stats.  emitters without gather, or together with area (a
+        sphere or rectangle emitter would be sampled twice): ValueError.  emitters=None: the calls and the bits above."""
         import torch
         from . import _lib
+        if emitters is not None:
+            if gather is None:
+                raise ValueError("emitters needs gather: the probes' SH already holds the emitters' direct light, so adding the sampled "
+                                 "emitters' to a probe lookup at the pixel would count it twice")
+            if area is not None:
+                raise ValueError("emitters and area exclude each other: the area lights are among the emitters and would be sampled twice")
+            emitters.check()
         if area is not None:
             if gather is None:
                 raise ValueError("area needs gather: the probes' SH already holds the emitters' direct light, so adding the area lights' "
@@ -4464,9 +4735,12 @@ class Renderer:
                 d_pl = torch.from_numpy(np.ascontiguousarray(np.asarray(placement, np.float32).reshape(grid.n_probes, 4))).to(dev)
             rays = None
             if gather is not None:
-                Eg = self._gather(ds, gather, gather_rounds, grid, d_sh, aov, depth, d_mom, normal_bias, d_pl, direct, area is not None)[0][:, 0:3]
+                Eg = self._gather(ds, gather, gather_rounds, grid, d_sh, aov, depth, d_mom, normal_bias, d_pl, direct, area is not None,
+                                  emitters is not None)[0][:, 0:3]
                 if area is not None:
                     Eg = Eg + self._area(ds, area, area_rounds, aov)[0][:, 0:3]
+                if emitters is not None:
+                    Eg = Eg + self._emitters(ds, emitters, emitters_rounds, aov)[0][:, 0:3]
                 v = aov[:, 3:4]
                 lit = aov[:, 0:3] * (v * (Eg * float(np.float32(1.0 / np.pi))) + (1.0 - v))
                 rgb8, gam, lin = _lib.denoise(lit.contiguous(), aov, None, w, h, 0, s["gamma"], ds.device)

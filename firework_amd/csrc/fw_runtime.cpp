@@ -25,6 +25,7 @@
 #include "fw_gather.h"
 #include "fw_reflect.h"
 #include "fw_area.h"
+#include "fw_emitters.h"
 #include "fw_defer_pretest.h"
 
 #include <algorithm>
@@ -1000,7 +1001,8 @@ struct SceneKeep {
 // ---- every emitter (FW_FLAG_ALL_EMITTERS): the entries of a description, object by object (scene_emitters) ----------------
 // obj, shape kind, its entries [first, first + count); pre[k]: entry k's weight (area x power) — for a mesh the object's power, the areas of
 // its triangles come from the device's copy of them (fw::launch_emitter_weights)
-struct EmitterObj { uint32_t obj, kind, count; uint64_t first; float pre[6]; };
+// shape, pos, rot, power: the object's shape index, placement (rotor_rows' rows) and emitter_power, which the world-space records of §9zc read
+struct EmitterObj { uint32_t obj, kind, count; uint64_t first; float pre[6]; int32_t shape; float pos[3]; float rot[3][3]; double power; };
 
 struct fw_scene {
     int device = 0;
@@ -1044,6 +1046,15 @@ struct fw_scene {
     uint32_t emit_cols = 0;       // the table's columns (entries of positive weight)
     size_t emit_ent_off = 0, emit_first_off = 0;
     double emit_build_ms = 0;
+    // every emitter at surface points (fw_scene_emitters, fw_bake_emitters, FW_GATHER_NO_EMITTERS): the entries' world-space
+    // records, their (object, prim) codes, their CDF and the ascending objects that have entries, built by the first call that needs
+    // them (es_state 0 -> 1) and again after every fw_scene_update, which resets es_state; es_dev: one allocation, records | cdf | codes | objects
+    std::vector<float> es_rec;
+    std::vector<uint32_t> es_codes, es_objs;
+    std::vector<double> es_cdf;
+    double es_total = 0;          // the weights' float64 sum: 0 = no emitters
+    DevBuf es_dev;
+    int es_state = 0;
     // point, spot and directional lights (fw_scene_set_lights): fw::DDeltaLights.rec, three float4 per light, in an allocation
     // of the scene's own that fw_scene_update leaves alone
     DevBuf dlights;
@@ -1056,6 +1067,7 @@ struct fw_scene {
         area_recs.release();
         env_dist.release();
         emitters.release();
+        es_dev.release();
     }
 };
 
@@ -1638,6 +1650,8 @@ static std::vector<EmitterObj> scene_emitters(const fw_scene_desc *d, uint64_t &
         const double power = emitter_power(d, d->materials[s.material]);
         if (!(power > 0.0)) continue;        // a black emitter: no entries (it emits nothing, so nothing is lost)
         EmitterObj e{}; e.obj = i; e.kind = (uint32_t)s.kind; e.first = n_entries;
+        e.shape = o.shape; e.power = power; e.pos[0] = o.position.x; e.pos[1] = o.position.y; e.pos[2] = o.position.z;
+        rotor_rows(o.rotation, e.rot);
         if (s.kind == FW_SHAPE_TRIANGLE_MESH) { e.count = (s.verts && s.indices) ? s.n_indices / 3 : 0u; e.pre[0] = (float)power; }
         else {
             double area[6];
@@ -1654,6 +1668,7 @@ static std::vector<EmitterObj> scene_emitters(const fw_scene_desc *d, uint64_t &
 // the device's copy (object indices) and the scene's light-sampling facts; at creation and after every fw_scene_update
 static int upload_lights(fw_scene *sc, const fw_scene_desc *d) {
     sc->emit_objs = scene_emitters(d, sc->n_entries);
+    sc->es_state = 0;             // (the objects may have moved: §9zc's records are built again by the next call that needs them)
     const std::vector<LightRec> L = scene_lights(d);
     std::vector<uint32_t> objs(L.size());
     for (size_t i = 0; i < L.size(); i++) objs[i] = L[i].obj;
@@ -1671,6 +1686,114 @@ static int upload_lights(fw_scene *sc, const fw_scene_desc *d) {
     }
     return FW_OK;
 }
+
+// ---- every emitter at surface points: §9i's entries as world-space records ---------------------------------------------
+// A record is FW_EMITTERS_RECORD_FLOATS floats: object, kind, 12 geometry floats, area, weight; codes holds (object, prim) per entry.
+// Spheres and rectangles are scene_lights' records float for float; every other point is the float64 image of its object-space point,
+// ((R0 x + R1 y) + R2 z) + position per component with rotor_rows' float32 rows, rotated exactly where the walks rotate (OF_ROTATED),
+// rounded to float32 once.  tris: a mesh's triangles in object space, 9 floats each.
+static void emitters_world(const EmitterObj &e, bool rotated, double x, double y, double z, float *out) {
+    const double p[3] = {x, y, z};
+    for (int c = 0; c < 3; c++) {
+        const double w = rotated ? ((double)e.rot[c][0] * x + (double)e.rot[c][1] * y) + (double)e.rot[c][2] * z : p[c];
+        out[c] = (float)(w + (double)e.pos[c]);
+    }
+}
+static void emitters_object_records(const EmitterObj &e, const fw_shape &s, const float *tris, float *rec, uint32_t *codes) {
+    const bool rotated = 0.5f * ((e.rot[0][0] + e.rot[1][1] + e.rot[2][2]) - 1.f) < 0.999f;     // fw::OF_ROTATED
+    const V3 pos{e.pos[0], e.pos[1], e.pos[2]};
+    double area[6] = {0, 0, 0, 0, 0, 0};
+    if (e.kind != FW_SHAPE_TRIANGLE_MESH) emitter_areas(s, area);
+    for (uint32_t k = 0; k < e.count; k++) {
+        float *r = rec + (size_t)k * FW_EMITTERS_RECORD_FLOATS;
+        std::memset(r, 0, FW_EMITTERS_RECORD_FLOATS * 4);
+        float *g = r + 2;
+        double a = area[e.kind == FW_SHAPE_TRIANGLE_MESH ? 0 : k];
+        r[0] = (float)e.obj; r[1] = (float)e.kind;
+        codes[2 * (size_t)k] = e.obj; codes[2 * (size_t)k + 1] = k;
+        if (e.kind == FW_SHAPE_SPHERE) { g[0] = pos.x; g[1] = pos.y; g[2] = pos.z; g[3] = s.radius; }
+        else if (e.kind >= FW_SHAPE_XYRECT && e.kind <= FW_SHAPE_YZRECT) {                     // scene_lights' corners
+            const float ca[4] = {s.a_min, s.a_max, s.a_max, s.a_min}, cb[4] = {s.b_min, s.b_min, s.b_max, s.b_max};
+            for (int c = 0; c < 4; c++) {
+                const V3 p = e.kind == FW_SHAPE_XYRECT ? V3{ca[c], cb[c], s.k} : (e.kind == FW_SHAPE_XZRECT ? V3{ca[c], s.k, cb[c]} : V3{s.k, ca[c], cb[c]});
+                const V3 w = (rotated ? mat_mul(e.rot, p) : p) + pos;
+                g[3 * c] = w.x; g[3 * c + 1] = w.y; g[3 * c + 2] = w.z;
+            }
+        } else if (e.kind == FW_SHAPE_RECT3D) {                                               // box_face's bounds, float32 as the walks form them
+            const float lo[3] = {s.pos.x, s.pos.y, s.pos.z}, hi[3] = {s.pos.x + s.size.x, s.pos.y + s.size.y, s.pos.z + s.size.z};
+            const uint32_t ax = k >> 1;                                                       // 0: an XY face at z, 1: XZ at y, 2: YZ at x
+            const int ia = ax == 2 ? 1 : 0, ib = ax == 0 ? 1 : 2, ik = ax == 0 ? 2 : (ax == 1 ? 1 : 0);
+            const float kk = (k & 1u) ? lo[ik] : hi[ik];
+            const float ca[4] = {lo[ia], hi[ia], hi[ia], lo[ia]}, cb[4] = {lo[ib], lo[ib], hi[ib], hi[ib]};
+            for (int c = 0; c < 4; c++) {
+                double p[3]; p[ia] = ca[c]; p[ib] = cb[c]; p[ik] = kk;
+                emitters_world(e, rotated, p[0], p[1], p[2], g + 3 * c);
+            }
+        } else if (e.kind == FW_SHAPE_TRIANGLE_MESH) {
+            const float *t = tris + (size_t)k * 9;
+            for (int c = 0; c < 3; c++) emitters_world(e, rotated, t[3 * c], t[3 * c + 1], t[3 * c + 2], g + 3 * c);
+            const double e1[3] = {(double)t[3] - t[0], (double)t[4] - t[1], (double)t[5] - t[2]}, e2[3] = {(double)t[6] - t[0], (double)t[7] - t[1], (double)t[8] - t[2]};
+            const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+            a = 0.5 * std::sqrt(cx * cx + cy * cy + cz * cz);                                 // fw_selftest_emitters' area
+        } else {                                                                              // a disk: the y = 0 plane of its object
+            g[0] = pos.x; g[1] = pos.y; g[2] = pos.z;
+            for (int c = 0; c < 3; c++) { g[3 + c] = rotated ? e.rot[c][0] : (c == 0 ? 1.f : 0.f); g[6 + c] = rotated ? e.rot[c][2] : (c == 2 ? 1.f : 0.f); }
+            g[9] = s.radius; g[10] = s.inner_radius; g[11] = s.phi_max;
+        }
+        r[14] = (float)a; r[15] = (float)emitter_weight(a * e.power);
+    }
+}
+// fw_emitters_cdf: float64 inclusive prefix sums of the float32 weights in entry order (negative and non-finite weights count as 0),
+// each divided by the last.  Returns the total; 0 (or a total that is not finite): no emitters, cdf is zeros.
+static double emitters_cdf(const float *w, uint64_t n, double *cdf) {
+    double total = 0;
+    for (uint64_t i = 0; i < n; i++) { total = total + emitter_weight((double)w[i]); cdf[i] = total; }
+    if (!(total > 0.0) || !std::isfinite(total)) { for (uint64_t i = 0; i < n; i++) cdf[i] = 0.0; return 0.0; }
+    for (uint64_t i = 0; i < n; i++) cdf[i] = cdf[i] / total;
+    return total;
+}
+// the records, codes, CDF and objects of a resident scene as it now stands, on the host and in es_dev; a mesh's triangles come from the
+// device's copy of them (the description's arrays are the caller's and may be gone).  FW_ERR_UNSUPPORTED above 2^24 entries.
+static int ensure_emitters_surface(fw_scene *sc) {
+    if (sc->es_state == 1) return FW_OK;
+    const uint64_t N = sc->n_entries;
+    if (N > (1ull << 24)) return fail(FW_ERR_UNSUPPORTED, "more than 2^24 emitter entries");
+    HIPCHK(hipSetDevice(sc->device));
+    std::vector<float> rec((size_t)N * FW_EMITTERS_RECORD_FLOATS), w((size_t)N);
+    std::vector<uint32_t> codes((size_t)N * 2), objs;
+    std::vector<double> cdf((size_t)N);
+    std::vector<float> tri4, tris;
+    int32_t tris_of = -1;                  // the shape whose triangles `tris` holds: objects that share a mesh read it once
+    bool synced = false;
+    for (const EmitterObj &e : sc->emit_objs) {
+        if (e.shape < 0 || (size_t)e.shape >= sc->keep.shapes.size()) return fail(FW_ERR_BAD_ARG, "emitter object without a shape");
+        if (e.kind == FW_SHAPE_TRIANGLE_MESH && e.shape != tris_of) {
+            if ((size_t)e.shape >= sc->keep.sp.size() || !sc->d.tri) return fail(FW_ERR_BAD_ARG, "emitter mesh without triangles");
+            tri4.resize((size_t)e.count * 12); tris.resize((size_t)e.count * 9);
+            if (!synced) { HIPCHK(hipDeviceSynchronize()); synced = true; }                   // (the scene's upload has landed)
+            HIPCHK(hipMemcpy(tri4.data(), sc->d.tri + 3 * (size_t)sc->keep.sp[e.shape].aux1, tri4.size() * 4, hipMemcpyDeviceToHost));
+            for (size_t v = 0; v < (size_t)e.count * 3; v++) for (int c = 0; c < 3; c++) tris[v * 3 + c] = tri4[v * 4 + c];
+            tris_of = e.shape;
+        }
+        emitters_object_records(e, sc->keep.shapes[e.shape], tris.data(), &rec[(size_t)e.first * FW_EMITTERS_RECORD_FLOATS], &codes[(size_t)e.first * 2]);
+        objs.push_back(e.obj);                                                                // (scene_emitters walks the objects in ascending order)
+    }
+    for (uint64_t i = 0; i < N; i++) w[i] = rec[(size_t)i * FW_EMITTERS_RECORD_FLOATS + 15];
+    const double total = emitters_cdf(w.data(), N, cdf.data());
+    const size_t b_rec = (size_t)N * 64, b_cdf = (size_t)N * 8, b_codes = (size_t)N * 8, b_objs = objs.size() * 4;
+    std::vector<uint8_t> blob(b_rec + b_cdf + b_codes + b_objs);
+    if (b_rec) { std::memcpy(blob.data(), rec.data(), b_rec); std::memcpy(blob.data() + b_rec, cdf.data(), b_cdf); std::memcpy(blob.data() + b_rec + b_cdf, codes.data(), b_codes); }
+    if (b_objs) std::memcpy(blob.data() + b_rec + b_cdf + b_codes, objs.data(), b_objs);
+    if (int rc = sc->es_dev.upload(blob.data(), blob.size())) return rc;
+    sc->es_rec.swap(rec); sc->es_codes.swap(codes); sc->es_cdf.swap(cdf); sc->es_objs.swap(objs);
+    sc->es_total = total;
+    sc->es_state = 1;
+    return FW_OK;
+}
+static const float4 *emitters_surface_records(const fw_scene *sc) { return (const float4 *)sc->es_dev.p; }
+static const double *emitters_surface_cdf(const fw_scene *sc) { return (const double *)((const uint8_t *)sc->es_dev.p + sc->es_cdf.size() * 64); }
+static const uint32_t *emitters_surface_codes(const fw_scene *sc) { return (const uint32_t *)((const uint8_t *)sc->es_dev.p + sc->es_cdf.size() * 72); }
+static const uint32_t *emitters_surface_objs(const fw_scene *sc) { return (const uint32_t *)((const uint8_t *)sc->es_dev.p + sc->es_cdf.size() * 80); }
 
 int create_scene_impl(const fw_scene_desc *desc, int device, fw_scene **out, const std::vector<float> *reach = nullptr) {
     if (!desc || !out) return fail(FW_ERR_BAD_ARG, "null argument");
@@ -2025,7 +2148,7 @@ int update_scene_impl(fw_scene *sc, const fw_scene_desc *desc) {
         const auto t0 = now();
         fw_scene *ns = nullptr;
         if (int rc = create_scene_impl(desc, sc->device, &ns, &reach)) return rc;
-        DevBuf old_data = sc->data, old_obj = sc->obj_data, old_lights = sc->lights, old_area = sc->area_recs, kept_env = sc->env_dist, old_emitters = sc->emitters;
+        DevBuf old_data = sc->data, old_obj = sc->obj_data, old_lights = sc->lights, old_area = sc->area_recs, kept_env = sc->env_dist, old_emitters = sc->emitters, old_es = sc->es_dev;
         const int kept_env_state = sc->env_state; const double kept_env_ms = sc->env_build_ms;
         const DevBuf kept_dl = sc->dlights; const uint32_t kept_n_dl = sc->n_dlights;     // (the delta lights stay: `ns` has none, and frees none)
         *sc = *ns;
@@ -2033,6 +2156,7 @@ int update_scene_impl(fw_scene *sc, const fw_scene_desc *desc) {
         ns->data = old_data; ns->obj_data = old_obj; ns->lights = old_lights; ns->area_recs = old_area;   // ... and the old ones go with `ns`
         // (the emitters' table is built again for the new scene, whose triangles are new allocations: the old one goes with `ns`)
         ns->emitters = old_emitters;
+        ns->es_dev = old_es;                  // (§9zc's records too: `ns` has built none)
         // (the environment's table stays: the map is the same)
         ns->env_dist = sc->env_dist; sc->env_dist = kept_env; sc->env_state = kept_env_state; sc->env_build_ms = kept_env_ms;
         fw_scene_destroy(ns);
@@ -5277,7 +5401,9 @@ int bake_gather_impl(fw_scene *sc, const fw_gather *g, const fw_trace_params *tp
     ProbeLookup L;
     if (int rc = probe_lookup_check(grid, a, !sh, false, L)) return rc;
     if (tp->on_device && (((uintptr_t)sh | (uintptr_t)moments | (uintptr_t)placement) & 3u)) return fail(FW_ERR_BAD_ARG, "device sh, moments and placement must be 4-byte aligned");
-    if (g->flags & ~(uint32_t)(FW_GATHER_DIRECT | FW_GATHER_NO_LIGHTS)) return fail(FW_ERR_BAD_ARG, "unknown gather flags");
+    if (g->flags & ~(uint32_t)(FW_GATHER_DIRECT | FW_GATHER_NO_LIGHTS | FW_GATHER_NO_EMITTERS)) return fail(FW_ERR_BAD_ARG, "unknown gather flags");
+    if ((g->flags & FW_GATHER_NO_LIGHTS) && (g->flags & FW_GATHER_NO_EMITTERS))
+        return fail(FW_ERR_BAD_ARG, "gather flags: FW_GATHER_NO_LIGHTS and FW_GATHER_NO_EMITTERS exclude each other");
     const uint32_t D = g->directions;
     if ((uint64_t)N * D >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x directions must be below 2^31");
     if (int rc = probe_lookup_sizes(a, L)) return rc;
@@ -5287,6 +5413,7 @@ int bake_gather_impl(fw_scene *sc, const fw_gather *g, const fw_trace_params *tp
     const auto wall0 = std::chrono::steady_clock::now();
     const int dev = sc->device;
     HIPCHK(hipSetDevice(dev));
+    if (g->flags & FW_GATHER_NO_EMITTERS) if (int rc = ensure_emitters_surface(sc)) return rc;     // (§9zc: the entries' objects, built on first use)
     hipStream_t stream = (hipStream_t)tp->stream;
     const bool on_device = tp->on_device != 0;
     const uint64_t ray_bytes = 24 + sizeof(fw_hit) + 64 + 12 + (Ln ? (uint64_t)Ln * 72 + 64 : 0);
@@ -5310,6 +5437,7 @@ int bake_gather_impl(fw_scene *sc, const fw_gather *g, const fw_trace_params *tp
     fw_stats total{};
     HitLight hl{sc, tp, st, hs, D, Ln, g->direct_bias, L, a.vis ? &vis : nullptr, st.ptr<const float>(t.sh), st.ptr<const float>(t.pl), stats ? &total : nullptr};
     if (g->flags & FW_GATHER_NO_LIGHTS) { hl.mask_objs = (const uint32_t *)sc->lights.p; hl.n_mask = sc->n_lights; }
+    if (g->flags & FW_GATHER_NO_EMITTERS) { hl.mask_objs = emitters_surface_objs(sc); hl.n_mask = (uint32_t)sc->es_objs.size(); }
     uint32_t round = first_round;              // the reducer's round: trace_rounds hands it to the generator only
     const TraceRounds b{N, D, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
     if (int rc = trace_rounds(sc, tp, b, first_round, rounds, stats ? &total : nullptr,
@@ -5639,6 +5767,186 @@ int bake_area_impl(fw_scene *sc, const fw_area *ap, const fw_trace_params *tp, u
                     const uint32_t km = k * (uint32_t)M;
                     fw::launch_hit_surface(stream, sc->n_cus, sc->d, sc->n_mat, rays, (const float4 *)hits, km, (float4 *)d_surf);
                     fw::launch_area_reduce(stream, n_cus, q0, k, Ln, S, pts.ids, d_obj, d_w, hits, d_surf, d_sums);
+                }))
+            return rc;
+    }
+    if (int rc = st.download(i_sums)) return rc;
+    if (out) fw::launch_area_resolve(stream, N, (double)((uint64_t)first_round + rounds), pts.ids, d_sums, st.ptr<float>(i_out));
+    if (int rc = st.finish()) return rc;
+    stats_finish(stats, total, wall0);
+    return FW_OK;
+}
+
+// ---- every emitter sampled at surface points, picked by power (include/firework_hip.h) -------------------------------
+int emitters_check(const fw_emitters *ep) {
+    if (ep->samples == 0 || ep->samples > (1u << 20)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^20");
+    if (!std::isfinite(ep->bias) || ep->bias < 0.f) return fail(FW_ERR_BAD_ARG, "bias must be finite and >= 0");
+    return FW_OK;
+}
+// caller-made records and their cdf: a count in 1..2^24, a kind fw_scene_emitters writes in each, and a cdf the kernel's searches end in
+int emitters_list_check(const float *records, const double *cdf, uint32_t n_entries) {
+    if (n_entries == 0 || n_entries > (1u << 24)) return fail(FW_ERR_BAD_ARG, "n_entries must be in 1..2^24");
+    double prev = 0.0;
+    for (uint32_t i = 0; i < n_entries; i++) {
+        const float k = records[(size_t)i * FW_EMITTERS_RECORD_FLOATS + 1];
+        if (!(k == 0.f || k == 1.f || k == 2.f || k == 3.f || k == 4.f || k == 5.f || k == 9.f)) return fail(FW_ERR_BAD_ARG, "records[" + std::to_string(i) + "]: unknown kind");
+        if (!(cdf[i] >= prev && cdf[i] <= 1.0)) return fail(FW_ERR_BAD_ARG, "cdf must not decrease and must stay in [0, 1]");
+        prev = cdf[i];
+    }
+    if (prev != 1.0) return fail(FW_ERR_BAD_ARG, "cdf must end in 1");
+    return FW_OK;
+}
+fw::DEmittersRays emitters_rays_device(const fw_emitters *ep, uint32_t round, const fw::DAoPoints &pts, const float4 *records, const double *cdf,
+                                       uint32_t n_entries, uint32_t first) {
+    fw::DEmittersRays d{};
+    d.pts = pts; d.records = records; d.cdf = cdf; d.n_entries = n_entries; d.samples = ep->samples; d.first = first;
+    d.seed32 = seed32_of(ep->seed);
+    d.jitter = ep->jitter ? 1u : 0u;
+    d.round = round; d.bias = ep->bias;
+    return d;
+}
+
+// fw_selftest_emitters_records: the description's own arrays give a mesh's triangles
+int selftest_emitters_records_impl(const fw_scene_desc *desc, float *records, uint32_t *codes, uint32_t cap, uint32_t *n) {
+    if (!desc || !n || ((!records || !codes) && cap > 0)) return fail(FW_ERR_BAD_ARG, "null argument");
+    uint64_t total = 0;
+    const std::vector<EmitterObj> E = scene_emitters(desc, total);
+    *n = (uint32_t)std::min<uint64_t>(total, 0xffffffffull);
+    std::vector<float> rec, tris;
+    std::vector<uint32_t> cod;
+    for (const EmitterObj &e : E) {
+        if (e.first >= cap) break;
+        const fw_shape &s = desc->shapes[e.shape];
+        rec.assign((size_t)e.count * FW_EMITTERS_RECORD_FLOATS, 0.f); cod.assign((size_t)e.count * 2, 0u);
+        if (e.kind == FW_SHAPE_TRIANGLE_MESH) {
+            tris.assign((size_t)e.count * 9, 0.f);
+            for (size_t v = 0; v < (size_t)e.count * 3; v++) { const uint32_t vi = s.indices[v]; if (vi < s.n_verts) for (int c = 0; c < 3; c++) tris[v * 3 + c] = s.verts[3 * (size_t)vi + c]; }
+        }
+        emitters_object_records(e, s, tris.data(), rec.data(), cod.data());
+        const size_t k = (size_t)std::min<uint64_t>(e.count, cap - e.first);
+        std::memcpy(records + (size_t)e.first * FW_EMITTERS_RECORD_FLOATS, rec.data(), k * FW_EMITTERS_RECORD_FLOATS * 4);
+        std::memcpy(codes + (size_t)e.first * 2, cod.data(), k * 8);
+    }
+    return FW_OK;
+}
+
+int scene_emitters_impl(fw_scene *sc, float *records, uint32_t *codes, uint32_t cap, uint32_t *n) {
+    if (!sc || !n || ((!records || !codes) && cap > 0)) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = ensure_emitters_surface(sc)) return rc;
+    *n = (uint32_t)sc->es_cdf.size();
+    const size_t k = std::min<size_t>(cap, sc->es_cdf.size());
+    if (k) { std::memcpy(records, sc->es_rec.data(), k * FW_EMITTERS_RECORD_FLOATS * 4); std::memcpy(codes, sc->es_codes.data(), k * 8); }
+    return FW_OK;
+}
+
+int emitters_cdf_impl(const float *weights, uint32_t n, double *cdf, double *total) {
+    if (!weights || !cdf || n == 0) return fail(FW_ERR_BAD_ARG, "null argument or n == 0");
+    const double t = emitters_cdf(weights, n, cdf);
+    if (total) *total = t;
+    return FW_OK;
+}
+
+// fw_emitters_rays: fw_area_rays' shape with a third output; the records and the cdf are the caller's host arrays, staged with the points
+int emitters_rays_impl(const fw_emitters *ep, const float *records, const double *cdf, uint32_t n_entries, int device, uint32_t round, uint32_t n,
+                       const float *positions, const float *normals, uint32_t stride, const uint32_t *ids, float *rays, float *weights, uint32_t *picks,
+                       int on_device, void *stream_) {
+    if (!ep || !records || !cdf || !positions || !normals || !rays || !weights || !picks) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = emitters_check(ep)) return rc;
+    if (int rc = emitters_list_check(records, cdf, n_entries)) return rc;
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (on_device && (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids | (uintptr_t)rays | (uintptr_t)weights | (uintptr_t)picks) & 3u))
+        return fail(FW_ERR_BAD_ARG, "device arrays must be 4-byte aligned");
+    const uint64_t S = ep->samples;
+    if ((uint64_t)n * S >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x samples must be below 2^31");
+    const uint64_t extent = on_device ? n : ao_extent(n, ids);
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n_cus = device_cus(device);
+    Staged st(device, stream, on_device != 0);
+    const AoSlots slots = ao_points_stage(st, n, positions, normals, stride, ids, extent);
+    const int i_rec = st.add(Staged::IN, records, (size_t)n_entries * 64, true), i_cdf = st.add(Staged::IN, cdf, (size_t)n_entries * 8, true);
+    HostSlabs sl(st, n, (size_t)S * 32);
+    const int a_rays = sl.out(rays, (size_t)S * 24), a_w = sl.out(weights, (size_t)S * 4), a_p = sl.out(picks, (size_t)S * 4);
+    if (int rc = st.up()) return rc;
+    const fw::DAoPoints pts = ao_points_device(st, slots, stride);
+    return sl.run([&](uint32_t done, uint32_t k) {
+        fw::launch_emitters_rays(stream, n_cus, emitters_rays_device(ep, round, pts, st.ptr<const float4>(i_rec), st.ptr<const double>(i_cdf), n_entries, done),
+                                 k, sl.ptr<float>(a_rays), sl.ptr<float>(a_w), sl.ptr<uint32_t>(a_p));
+    });
+}
+
+// fw_emitters_reduce: fw_area_reduce's shape with the picks and the entries' codes
+int emitters_reduce_impl(int device, uint32_t S, const uint32_t *codes, uint32_t n_entries, uint32_t n, const uint32_t *ids, const uint32_t *picks,
+                         const float *weights, const fw_hit *hits, const float *surface, float *sums, int on_device, void *stream_) {
+    if (!codes || !picks || !weights || !hits || !surface || !sums) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (S == 0 || S > (1u << 20)) return fail(FW_ERR_BAD_ARG, "samples must be in 1..2^20");
+    if (n_entries == 0 || n_entries > (1u << 24)) return fail(FW_ERR_BAD_ARG, "n_entries must be in 1..2^24");
+    if (n == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (on_device && ((((uintptr_t)sums | (uintptr_t)hits | (uintptr_t)surface) & 15u) || (((uintptr_t)weights | (uintptr_t)picks | (uintptr_t)ids) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums, hits and surface must be 16-byte aligned, device picks, weights and ids 4-byte aligned");
+    if ((uint64_t)n * S >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x samples must be below 2^31");
+    if (int rc = use_device(device)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t entries = (size_t)n * S;
+    Staged st(device, stream, on_device != 0);
+    const int i_codes = st.add(Staged::IN, codes, (size_t)n_entries * 8, true), i_p = st.add(Staged::IN, picks, entries * 4), i_w = st.add(Staged::IN, weights, entries * 4),
+              i_hits = st.add(Staged::IN, hits, entries * sizeof(fw_hit)), i_surf = st.add(Staged::IN, surface, entries * 64),
+              i_sums = st.add(Staged::INOUT, sums, on_device ? 0 : (size_t)ao_extent(n, ids) * 16), i_ids = st.add(Staged::IN, ids, (size_t)n * 4);
+    if (int rc = st.up()) return rc;
+    fw::launch_emitters_reduce(stream, device_cus(device), 0, n, S, st.ptr<const uint32_t>(i_ids), st.ptr<const uint32_t>(i_codes), n_entries,
+                               st.ptr<const uint32_t>(i_p), st.ptr<const float>(i_w), st.ptr<const fw_hit>(i_hits), st.ptr<const float>(i_surf), st.ptr<float>(i_sums));
+    return st.finish();
+}
+
+// fw_bake_emitters: fw_bake_area's shape — k_emitters_rays as trace_rounds' generator over the scene's own records and cdf where they lie,
+// which fills the chunk's weights and picks beside its rays; the reducer is k_hit_surface and k_emitters_reduce
+int bake_emitters_impl(fw_scene *sc, const fw_emitters *ep, const fw_trace_params *tp, uint32_t N, const float *positions, const float *normals,
+                       uint32_t stride, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    if (!sc || !ep || !tp || !positions || !normals) return fail(FW_ERR_BAD_ARG, "null argument");
+    if (int rc = emitters_check(ep)) return rc;
+    if (N == 0) return fail(FW_ERR_BAD_ARG, "n must be > 0");
+    if (stride < 3) return fail(FW_ERR_BAD_ARG, "stride_floats must be >= 3");
+    if (rounds == 0) return fail(FW_ERR_BAD_ARG, "rounds must be > 0");
+    if ((uint64_t)first_round + rounds > 0xffffffffull) return fail(FW_ERR_BAD_ARG, "first_round + rounds overflows");
+    if (!sums && first_round > 0) return fail(FW_ERR_BAD_ARG, "first_round > 0 needs the sums of the rounds before it");
+    if (tp->on_device && ((((uintptr_t)sums | (uintptr_t)out) & 15u) || (((uintptr_t)positions | (uintptr_t)normals | (uintptr_t)ids) & 3u)))
+        return fail(FW_ERR_BAD_ARG, "device sums and out must be 16-byte aligned, device positions, normals and ids 4-byte aligned");
+    if (int rc = need_device()) return rc;
+    if (int rc = ensure_emitters_surface(sc)) return rc;
+    const uint32_t S = ep->samples;
+    if ((uint64_t)N * S >= (1ull << 31)) return fail(FW_ERR_UNSUPPORTED, "n x samples must be below 2^31");
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int dev = sc->device;
+    HIPCHK(hipSetDevice(dev));
+    hipStream_t stream = (hipStream_t)tp->stream;
+    const bool on_device = tp->on_device != 0;
+    uint64_t extent;
+    if (int rc = points_extent(stream, N, ids, on_device, sums, extent)) return rc;
+    const uint32_t chunk = std::min<uint32_t>(N, ep->chunk_points ? ep->chunk_points : (uint32_t)std::max<uint64_t>(1, CALL_SCRATCH_BYTES / ((uint64_t)S * 144)));
+    const size_t rec_bytes = (size_t)extent * 16, cm = (size_t)chunk * S;
+    Staged st(dev, stream, on_device);
+    const AoSlots slots = ao_points_stage(st, N, positions, normals, stride, ids, extent);
+    const int i_rays = st.add(Staged::WORK, nullptr, cm * 24), i_hits = st.add(Staged::WORK, nullptr, cm * sizeof(fw_hit)),
+              i_w = st.add(Staged::WORK, nullptr, cm * 4), i_p = st.add(Staged::WORK, nullptr, cm * 4), i_surf = st.add(Staged::WORK, nullptr, cm * 64);
+    const int i_sums = st.add_sums(sums, rec_bytes), i_out = st.add(ids ? Staged::INOUT : Staged::OUT, out, rec_bytes);      // (with ids, entries outside the list stay)
+    if (int rc = st.up()) return rc;
+    const fw::DAoPoints pts = ao_points_device(st, slots, stride);
+    float *d_sums = st.ptr<float>(i_sums), *d_w = st.ptr<float>(i_w), *d_surf = st.ptr<float>(i_surf);
+    uint32_t *d_p = st.ptr<uint32_t>(i_p);
+    const int n_cus = device_cus(dev);
+    fw_stats total{};
+    const uint32_t Ne = (uint32_t)sc->es_cdf.size();
+    if (Ne > 0 && sc->es_total > 0.0) {
+        const TraceRounds b{N, S, chunk, st.ptr<float>(i_rays), st.ptr<fw_hit>(i_hits)};
+        if (int rc = trace_rounds(sc, tp, b, first_round, rounds, stats ? &total : nullptr,
+                [&](uint32_t r, uint32_t q0, uint32_t k, float *rays) {
+                    fw::launch_emitters_rays(stream, n_cus, emitters_rays_device(ep, r, pts, emitters_surface_records(sc), emitters_surface_cdf(sc), Ne, q0), k, rays, d_w, d_p);
+                },
+                [&](uint32_t q0, uint32_t k, const float *rays, const fw_hit *hits) {
+                    const uint32_t km = k * S;
+                    fw::launch_hit_surface(stream, sc->n_cus, sc->d, sc->n_mat, rays, (const float4 *)hits, km, (float4 *)d_surf);
+                    fw::launch_emitters_reduce(stream, n_cus, q0, k, S, pts.ids, emitters_surface_codes(sc), Ne, d_p, d_w, hits, d_surf, d_sums);
                 }))
             return rc;
     }
@@ -6640,6 +6948,46 @@ int fw_bake_area(fw_scene *scene, const fw_area *area, const fw_trace_params *tp
     try { return bake_area_impl(scene, area, tp, n, positions, normals, stride_floats, ids, first_round, rounds, sums, out, stats); }
     catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
     catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_area"); }
+}
+
+int fw_selftest_emitters_records(const fw_scene_desc *desc, float *records, uint32_t *codes, uint32_t cap, uint32_t *n) {
+    try { return selftest_emitters_records_impl(desc, records, codes, cap, n); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_selftest_emitters_records"); }
+}
+
+int fw_scene_emitters(fw_scene *scene, float *records, uint32_t *codes, uint32_t cap, uint32_t *n) {
+    try { return scene_emitters_impl(scene, records, codes, cap, n); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_scene_emitters"); }
+}
+
+int fw_emitters_cdf(const float *weights, uint32_t n, double *cdf, double *total) {
+    try { return emitters_cdf_impl(weights, n, cdf, total); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_emitters_cdf"); }
+}
+
+int fw_emitters_rays(const fw_emitters *emitters, const float *records, const double *cdf, uint32_t n_entries, int device, uint32_t round, uint32_t n,
+                     const float *positions, const float *normals, uint32_t stride_floats, const uint32_t *ids, float *rays, float *weights,
+                     uint32_t *picks, int on_device, void *stream) {
+    try { return emitters_rays_impl(emitters, records, cdf, n_entries, device, round, n, positions, normals, stride_floats, ids, rays, weights, picks, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_emitters_rays"); }
+}
+
+int fw_emitters_reduce(int device, uint32_t samples, const uint32_t *codes, uint32_t n_entries, uint32_t n, const uint32_t *ids, const uint32_t *picks,
+                       const float *weights, const fw_hit *hits, const float *surface, float *sums, int on_device, void *stream) {
+    try { return emitters_reduce_impl(device, samples, codes, n_entries, n, ids, picks, weights, hits, surface, sums, on_device, stream); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_emitters_reduce"); }
+}
+
+int fw_bake_emitters(fw_scene *scene, const fw_emitters *emitters, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
+                     uint32_t stride_floats, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats) {
+    try { return bake_emitters_impl(scene, emitters, tp, n, positions, normals, stride_floats, ids, first_round, rounds, sums, out, stats); }
+    catch (std::bad_alloc &) { return fail(FW_ERR_OOM, "host allocation failed"); }
+    catch (...) { return fail(FW_ERR_BAD_ARG, "unexpected exception in fw_bake_emitters"); }
 }
 
 int fw_reflect_rays(const fw_reflect *reflect, int device, uint32_t round, uint32_t n, const float *positions, const float *normals,

@@ -1730,12 +1730,15 @@ int fw_gather_reduce(int device, uint32_t directions, uint32_t n, const uint32_t
 #define FW_GATHER_NO_LIGHTS 4u   /* the complement of fw_bake_area: a gather ray that hits one of the scene's sampled area lights (fw_scene_area_lights)
                                     brings back nothing — between steps 3 and 4 k_area_mask (fw_area_mask) rewrites those records of the chunk to
                                     kind -2.  Bit 2 is unassigned and refused. */
+#define FW_GATHER_NO_EMITTERS 16u   /* the complement of fw_bake_emitters: k_area_mask runs over the ascending objects that have an entry in
+                                       fw_scene_emitters' list in place of the sampled area lights' objects.  Together with
+                                       FW_GATHER_NO_LIGHTS: FW_ERR_BAD_ARG ("gather flags").  Bits 2 and 8 stay unassigned and refused. */
 typedef struct fw_gather {
     uint32_t directions;     /* D, 1..2^20 */
     uint32_t jitter;         /* fw_ao's */
     float    bias;           /* gather-ray origin offset along the receiver's normal, >= 0, finite */
     float    direct_bias;    /* fw_direct.bias for the shadow rays at the gather hits */
-    uint32_t flags;          /* FW_GATHER_DIRECT | FW_GATHER_NO_LIGHTS */
+    uint32_t flags;          /* FW_GATHER_DIRECT | FW_GATHER_NO_LIGHTS or FW_GATHER_NO_EMITTERS */
     uint32_t chunk_points;   /* 0: as many as fit 256 MiB at this call's bytes per ray (148, plus Ln x 72 + 64 with direct), at least one */
     uint64_t seed;
 } fw_gather;
@@ -1978,6 +1981,94 @@ int fw_area_mask(int device, const uint32_t *objects, uint32_t n_objects, uint32
    stats (may be NULL): fw_bake_ao's. */
 int fw_bake_area(fw_scene *scene, const fw_area *area, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
                  uint32_t stride_floats, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
+
+/* ---- every emitter sampled at surface points, picked by power (additive at ABI 8) ----------------------------------------
+   The direct irradiance of every emitting primitive of a scene — FW_FLAG_ALL_EMITTERS' entries (§9i): EmissiveMat spheres, axis-aligned
+   rectangles, Rect3d faces, disks and mesh triangles — at arbitrary surface points.  Each point sends S shadow rays per round whatever the
+   number of entries, each towards an entry picked in proportion to area x power through a CDF, with the pick's probability in the weight.
+   api.emitters_cdf, api.emitters_rays and api.emitters_reduce are the numpy statements; resolve and mask are fw_bake_area's.
+     Records: FW_EMITTERS_RECORD_FLOATS = 16 floats per entry, in fw_selftest_emitters' order: object, kind (FW_SHAPE_*), 12 geometry
+         floats, area, weight (fw_selftest_emitters' two).  Geometry, in the world, rotated exactly where the walks rotate the object:
+         a sphere: centre.xyz, radius, 8 zeros and a rectangle: its corners c0 .. c3 in order around it — both fw_selftest_lights'
+         floats; a Rect3d face: its four corners in the rectangle's order ((lo, lo), (hi, lo), (hi, hi), (lo, hi) in the face's two axes,
+         bounds pos and the float32 pos + size); a triangle: v0, v1, v2, three zeros; a disk: centre, the images of the object's x and z
+         axes, then radius, inner_radius, phi_max.  Every point other than a sphere's and a rectangle's is float(((R0 x + R1 y) + R2 z) +
+         position) per component in float64, R the object's float32 rotation rows (the identity where the walks do not rotate).
+         codes: two words per entry, (object, prim): a Rect3d's face, a mesh's triangle, else 0.
+     CDF (fw_emitters_cdf): float64 inclusive prefix sums of the float32 weights in entry order, a negative or non-finite weight counted
+         as 0, each divided by the last: the last positive entry and every one after it is exactly 1.  An entry's probability is p_i =
+         cdf[i] - cdf[i - 1] (cdf[-1] = 0).  A total of 0: "no emitters", the cdf is zeros and nothing may be sampled from it.
+     Entry e = q S + s: sample s from point q (fw_emitters_rays, k_emitters_rays); numerics and points are fw_area_rays'.
+         1. (xi_u, xi_v) = the two shifts fw_ao_rays draws for (seed, round, item id); (1/2, 1/2) with jitter == 0.
+            a1 = (s + xi_u) / S;  xi = a1 - floor(a1);  a2 = s G + xi_v with G = 0.6180339887498949;  u2 = a2 - floor(a2).
+         2. The pick i = the first index with cdf[i] > xi;  lo = i ? cdf[i - 1] : 0;  p = cdf[i] - lo;  u1 = min((xi - lo) / p, 1 - 2^-53).
+         3. n and o as fw_area_rays' step 2.
+         4. A sphere: fw_area_rays' step 4 with (u1, u2), g its g.  A rectangle or Rect3d face: fw_area_rays' step 3, g its g.
+         5. A triangle: e1 = v1 - v0;  e2 = v2 - v0;  sq = sqrt(u1);  (b0, b1, b2) = (1 - sq, sq (1 - u2), sq u2);  d = ((b0 v0 + b1 v1)
+            + b2 v2) - o;  nl = e1 x e2;  L = |nl|;  A = L / 2.  A disk: r2 = r r;  i2 = r_in r_in;  rr = sqrt(i2 + u1 (r2 - i2));  phi =
+            u2 phi_max;  d = ((c + (rr cos phi) ax) + (rr sin phi) az) - o;  nl = ax x az;  L = |nl|;  A = (0.5 phi_max) (r2 - i2).
+            Both: d2 = d . d;  w = d / sqrt(d2);  cr = n . w;  cl = |(nl . w) / L|;  g = ((cr cl) A) / d2 (the rectangle's form, where
+            A = L).  Live only if cr > 0, A > 0 and L > 0.
+         6. The weight is float(g / p).  Dead exactly as fw_area_rays' step 5 with g / p for g: six zeros, the weight 0 and the pick
+            0xffffffff; a live entry is (float(o), float(d)), the weight and the pick i.
+     Reduction of one round (fw_emitters_reduce, k_emitters_reduce) over the S entries of point q: an entry counts exactly where its
+         weight > 0, its pick i < n_entries, the hit's object and prim equal codes[2 i] and codes[2 i + 1], and fw_hit_surface's record
+         has kind 3.  Accumulators, order, butterfly and rounding are fw_area_reduce's with M = S; E and V are both multiplied by the
+         float64 1 / S. */
+#define FW_EMITTERS_RECORD_FLOATS 16
+typedef struct fw_emitters {
+    uint32_t samples;        /* S per point and round, 1..2^20 */
+    uint32_t jitter;         /* fw_ao's */
+    float    bias;           /* shadow-ray origin offset along the point's normal, >= 0, finite */
+    uint32_t chunk_points;   /* fw_bake_emitters: points per chunk; 0 = as many as fit 256 MiB at 144 B per entry, at least one */
+    uint64_t seed;
+} fw_emitters;
+
+/* fw_selftest_emitters_records (CPU only): the records and codes of a description's entries.  *n = their number; the first min(cap, *n)
+   records (16 floats) and codes (2 words) are written; either array may be NULL with cap == 0.  FW_ERR_BAD_ARG for a NULL desc or n, or a
+   NULL records or codes with cap > 0. */
+int fw_selftest_emitters_records(const fw_scene_desc *desc, float *records, uint32_t *codes, uint32_t cap, uint32_t *n);
+
+/* fw_scene_emitters: the same for the description a resident scene now represents, objects moved by fw_scene_update included.  The list
+   is built by the first call that needs it (this one, fw_bake_emitters, fw_bake_gather with FW_GATHER_NO_EMITTERS) and again after every
+   fw_scene_update; a mesh's triangles are read back from the device (objects in a row that share a mesh read it once), so where a mesh emits that first call
+   synchronises the whole device once, whatever stream its caller passed.  FW_ERR_BAD_ARG as above; FW_ERR_UNSUPPORTED above 2^24 entries. */
+int fw_scene_emitters(fw_scene *scene, float *records, uint32_t *codes, uint32_t cap, uint32_t *n);
+
+/* fw_emitters_cdf (CPU only): cdf[0..n) from weights[0..n).  *total (may be NULL) = the float64 sum; 0: no emitters, cdf is zeros.
+   FW_ERR_BAD_ARG for a NULL weights or cdf or n == 0. */
+int fw_emitters_cdf(const float *weights, uint32_t n, double *cdf, double *total);
+
+/* fw_emitters_rays: the shadow rays, weights and picks of round `round` from n points towards n_entries records with their cdf (host
+   memory always).  rays n x S x 6 floats, weights n x S floats, picks n x S words; host or device arrays as fw_ao_rays.
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL emitters, records, cdf, positions, normals, rays, weights or
+   picks; samples outside 1..2^20, bias negative or not finite; n_entries outside 1..2^24, a record whose kind is not 0..5 or 9, a cdf
+   that decreases, leaves [0, 1] or does not end in 1; n == 0; stride_floats < 3; with on_device an array not 4-byte aligned;
+   FW_ERR_UNSUPPORTED for n x S >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last. */
+int fw_emitters_rays(const fw_emitters *emitters, const float *records, const double *cdf, uint32_t n_entries, int device, uint32_t round, uint32_t n,
+                     const float *positions, const float *normals, uint32_t stride_floats, const uint32_t *ids, float *rays, float *weights,
+                     uint32_t *picks, int on_device, void *stream);
+
+/* fw_emitters_reduce: adds one round's reduction to the running sums.  codes: 2 x n_entries words (host memory always); picks and weights
+   n x S words, hits n x S records, surface n x S x 16 floats; sums records of 16 B indexed by id.
+   Errors, in this order and before HIP is called: FW_ERR_BAD_ARG for a NULL codes, picks, weights, hits, surface or sums; samples outside
+   1..2^20; n_entries outside 1..2^24; n == 0; with on_device sums, hits or surface not 16-byte aligned, picks, weights or ids not 4-byte
+   aligned; FW_ERR_UNSUPPORTED for n x S >= 2^31; then FW_ERR_NO_DEVICE, and FW_ERR_BAD_ARG for a device index past the last. */
+int fw_emitters_reduce(int device, uint32_t samples, const uint32_t *codes, uint32_t n_entries, uint32_t n, const uint32_t *ids, const uint32_t *picks,
+                       const float *weights, const fw_hit *hits, const float *surface, float *sums, int on_device, void *stream);
+
+/* fw_bake_emitters: the rounds [first_round, first_round + rounds) of the n points against a resident scene and its own entries.  Points,
+   ids, sums, out, first_round / rounds and what is read of tp are fw_bake_ao's.  For each round r and each chunk of points [q0, q1):
+     1. k_emitters_rays: fw_emitters_rays' rays, weights and picks for fw_scene_emitters' records and their fw_emitters_cdf, bit for bit;
+     2. the trace, as fw_bake_ao runs it: on_device, seed = tp->seed + r, key_base = q0 S;
+     3. k_hit_surface over the chunk's rays and hits;
+     4. k_emitters_reduce into sums.
+   After the last round k_area_resolve writes out.  A scene without entries, or whose weights sum to 0, traces nothing: sums stay as they
+   are and out is their resolve — zeros.  Composition and progressive contracts are fw_bake_area's.
+   Errors, in this order and before the scene is looked at or HIP is called: fw_bake_area's with `emitters` for `area`; then
+   FW_ERR_NO_DEVICE; then FW_ERR_UNSUPPORTED for more than 2^24 entries and for n x S >= 2^31.  stats (may be NULL): fw_bake_ao's. */
+int fw_bake_emitters(fw_scene *scene, const fw_emitters *emitters, const fw_trace_params *tp, uint32_t n, const float *positions, const float *normals,
+                     uint32_t stride_floats, const uint32_t *ids, uint32_t first_round, uint32_t rounds, float *sums, float *out, fw_stats *stats);
 
 #ifdef __cplusplus
 }
